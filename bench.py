@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- consensus bases/s of the DAGCon hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (normalise -> build -> merge -> best path)
 over one batch of synthetic targets that is already resident in HBM, results
@@ -66,6 +66,48 @@ def fasta_bytes(batch, results):
         for r0, r1, seq in segs:
             out.append(b">%s/%d_%d\n%s\n" % (tid.encode(), r0, r1, seq))
     return b"".join(out)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, results, first_target, budget, suffix=""):
+    """What the timed path handed its caller in one step (per target [(range0, range1, seq)]) as
+    out_dir/<name><suffix>.npy: targets (global index of each dumped target), seg_count (its number of
+    segments), range0 / range1 / seq_len per segment (float64), seq (the segments' bases as ASCII codes,
+    concatenated in order, float32).  When the whole output exceeds `budget` bytes, targets are taken in
+    one fixed seeded order until the next would not fit, so two builds are compared on the same targets."""
+    import numpy as np
+
+    def cost(segs):
+        return 16 + sum(24 + 4 * len(s) for _, _, s in segs)
+
+    T = len(results)
+    headers = 1024                                      # six .npy headers
+    if headers + sum(cost(segs) for segs in results) <= budget:
+        keep = list(range(T))
+    else:
+        keep, used = [], headers
+        for t in np.random.default_rng(20261015).permutation(T):
+            c = cost(results[t])
+            if used + c > budget:
+                break
+            keep.append(int(t)); used += c
+        keep.sort()
+    segs = [s for t in keep for s in results[t]]
+    arrays = {
+        "targets": np.array([first_target + t for t in keep], np.float64),
+        "seg_count": np.array([len(results[t]) for t in keep], np.float64),
+        "range0": np.array([r0 for r0, _, _ in segs], np.float64),
+        "range1": np.array([r1 for _, r1, _ in segs], np.float64),
+        "seq_len": np.array([len(s) for _, _, s in segs], np.float64),
+        "seq": np.frombuffer(b"".join(s for _, _, s in segs), np.uint8).astype(np.float32),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+    return {"dir": out_dir, "targets": len(keep), "of_targets": T,
+            "bytes": sum(a.nbytes for a in arrays.values()), "files": sorted(f"{n}{suffix}.npy" for n in arrays)}
 
 
 def cpu_baseline(batch, sample_targets, opts, cores, faithful=False):
@@ -748,6 +790,10 @@ def worker(args, rank, world, local_rank):
     value = bases_all * args.steps / dt
 
     # ---- everything below is outside the timed region ----
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, res, lo, DUMP_LIMIT_BYTES // world,
+                              suffix=f"_rank{rank}" if world > 1 else "")
     my_fasta = fasta_bytes(batch, res)
     cores = min(len(os.sched_getaffinity(0)), 16)
     cpu = None
@@ -823,6 +869,8 @@ def worker(args, rank, world, local_rank):
             "fasta_gather_ok": gather_ok,
             "fasta_sha256": hashlib.sha256(my_fasta).hexdigest() if n_gpus == 1 else None,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if cpu is not None and not args.no_cpu and n_gpus == 1:      # (the CPU legs belong to the N = 1 line)
             v, n, cdt = cpu
             line["cpu_baseline"] = {
@@ -970,7 +1018,16 @@ def main():
     ap.add_argument("--stream-verify", type=int, default=64,
                     help="targets of every generated batch checked against the oracle (-1: all, 0: none)")
     ap.add_argument("--rehearse", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32/64, "
+                         "at most 64 MB; a fixed seeded sample of targets when larger)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and (args.stream_batches or args.targets_total or args.rehearse):
+        ap.error("--dump-outputs belongs to the driver's line, not to --stream-batches / --targets-total / --rehearse")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args)

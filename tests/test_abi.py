@@ -58,9 +58,9 @@ def test_default_opts_are_pbdagcon_defaults():
 
 def test_no_device_fails_loudly():
     """Without a GPU the product refuses to run: there is no CPU fallback."""
-    import torch
     from pbdagcon_amd import capi
-    if torch.cuda.is_available():
+    from util import gpu_present
+    if gpu_present():
         pytest.skip("a GPU is present")
     with pytest.raises(capi.DagconError) as e:
         capi.Context()

@@ -39,6 +39,49 @@ def test_synth_shape():
             assert nt >= 600 and s - 1 + nt <= 1000
 
 
+def test_bench_dump_outputs_round_trips_and_keeps_to_its_budget(tmp_path):
+    """bench.py --dump-outputs: the arrays spell the caller's per-target segments exactly, in float32 /
+    float64; over the budget a fixed seeded sample of whole targets is written, the same one every time."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(7)
+    res = [[(int(a), int(a) + int(n), bytes(rng.choice(list(b"ACGT"), int(n)).tolist()))
+            for a, n in zip(rng.integers(0, 900, k), rng.integers(1, 400, k))] for k in rng.integers(0, 4, 60)]
+
+    def load(d):
+        a = {n: np.load(os.path.join(d, n + ".npy")) for n in ("targets", "seg_count", "range0", "range1", "seq_len", "seq")}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        segs, o, b = [], 0, 0
+        for t, k in zip(a["targets"].astype(int), a["seg_count"].astype(int)):
+            one = []
+            for i in range(o, o + k):
+                n = int(a["seq_len"][i])
+                one.append((int(a["range0"][i]), int(a["range1"][i]), a["seq"][b:b + n].astype(np.uint8).tobytes()))
+                b += n
+            segs.append((t, one)); o += k
+        assert o == a["range0"].size and b == a["seq"].size
+        return segs, sum(os.path.getsize(os.path.join(d, n + ".npy")) for n in a)
+
+    info = bench.dump_outputs(str(tmp_path / "full"), res, 100, 64 << 20)
+    assert info["targets"] == len(res) and load(tmp_path / "full")[0] == [(100 + t, segs) for t, segs in enumerate(res)]
+    budget = 20000
+    info = bench.dump_outputs(str(tmp_path / "a"), res, 100, budget)
+    part, size = load(tmp_path / "a")
+    assert 0 < info["targets"] < len(res) and size <= budget
+    assert [t for t, _ in part] == sorted(t for t, _ in part) and all(res[t - 100] == segs for t, segs in part)
+    bench.dump_outputs(str(tmp_path / "b"), res, 100, budget)
+    assert load(tmp_path / "b")[0] == part
+
+
+def test_bench_rejects_zero_steps():
+    """--steps is the number of timed steps, and ms_per_step divides by it: zero is refused up front."""
+    out = _bench("--steps", "0")
+    assert out.returncode == 2 and "--steps" in out.stderr
+
+
 def test_shard_ranges_cover_and_balance():
     from pbdagcon_amd.shard import shard_ranges
     rng = np.random.default_rng(0)
@@ -219,8 +262,8 @@ def test_bench_streams_the_global_target_space_over_ranks():
 
 def test_bench_without_a_gpu_fails_loudly():
     """The measured path has no CPU stand-in: without a device bench.py ends with an error."""
-    import torch
-    if torch.cuda.is_available():
+    from util import gpu_present
+    if gpu_present():
         import pytest
         pytest.skip("a GPU is present")
     out = _bench("--steps", "1", "--warmup", "0", "--targets", "2", "--tlen", "600", "--coverage", "8")

@@ -27,17 +27,16 @@ def test_parse_pre_matches_reference_vectors():
 
 
 def test_parse_pre_against_live_reference_build():
-    if oracle.ref_lib() is None:
-        import pytest
-        pytest.skip("oracle/_ref not present")
-    rng = np.random.default_rng(5)
-    for i in range(200):
-        n, m = int(rng.integers(1, 40)), int(rng.integers(1, 40))
-        q = bytes(b"ACGTacgtN-"[j] for j in rng.integers(0, 10, n))
-        t = bytes(b"ACGTN"[j] for j in rng.integers(0, 5, m))
-        line = b" ".join([b"q%d" % i, b"t%d" % (i % 3), b"+-"[i % 2:i % 2 + 1], b"%d" % rng.integers(1, 9999),
-                          b"%d" % rng.integers(0, 999), b"%d" % rng.integers(0, 9999), q, t])
-        assert oracle.parse_pre(line) == oracle.ref_parse_pre(line)
+    """200 seeded .pre lines against the reference's parsePre: the digests of its answers
+    (tests/golden/ref_fuzz_hashes.json), and live when oracle/_ref exists."""
+    from util import golden_module
+    oracle.build()
+    fz = golden_module("make_ref_fuzz")
+    gold = json.load(open(os.path.join(GOLD, "ref_fuzz_hashes.json")))
+    got = fz.pre_answers(oracle.parse_pre)
+    assert len(got) == 200 and fz.digests(got) == gold["pre"]
+    if oracle.ref_lib() is not None:
+        assert got == fz.pre_answers(oracle.ref_parse_pre)
 
 
 def test_simple_aligner_kat():

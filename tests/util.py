@@ -1,7 +1,30 @@
 """Shared helpers for the parity tests."""
+import subprocess
+import sys
+
 import numpy as np
 
 import oracle
+
+
+def gpu_present():
+    """Whether torch sees a GPU, asked in a child process.  torch carries a HIP runtime of its own; once it
+    has opened the device in the test process, the library's runtime finds no device there, and every
+    in-process GPU test after it would fail."""
+    out = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    return out.stdout.split()[-1] == "True"
+
+
+def golden_module(name):
+    """tests/golden/<name>.py as a module: a fixture's generator holds the inputs its tests replay."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location(name, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name + ".py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
 
 
 def oracle_batch(batch, min_cov=6, min_len=500, trim=50, min_weight=None):

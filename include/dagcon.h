@@ -207,6 +207,30 @@ int dagcon_align(dagcon_ctx *ctx, uint32_t n, const uint64_t *q_off, const uint3
                  uint32_t *aln_len);
 
 /*
+ * dazcon --trace-panels: n overlaps of a .las re-aligned inside their trace-point panels, as the reference's
+ * Compute_Trace_PTS does (DazAlnProvider.cpp:304-351).  Pair a is q_blob[q_off[a] .. +q_len[a]) (the B interval)
+ * against t_blob[t_off[a] .. +t_len[a]) (the A interval), cut into the panels p in [panel_begin[a], panel_begin[a+1]):
+ * panel p takes the next panel_t_len[p] bases of t and panel_q_len[p] bases of q.  Each panel is aligned on its own,
+ * a unit-cost edit distance with both corners fixed, ties broken per cell diagonal first, then a q base against a gap
+ * in t, then a t base against a gap in q; the pair's alignment is its panels' concatenated, written as dagcon_align
+ * writes it (qaln / taln at out_off[a], room for q_len[a] + t_len[a] columns, '-' for gaps; length in aln_len[a]).
+ * panel_dist (optional) receives each panel's edit distance, -1 for the panels of a pair that was not aligned.
+ * A pair with a panel wider or longer than DAGCON_PANEL_MAX_SIDE bases is not aligned: aln_len 0, counted by
+ * dagcon_align_dropped.  DAGCON_ERR_INVALID_ARG when a pair's panels do not add up to its t_len / q_len.
+ * DALIGNER is not in the reference tree: PARITY UNPINNED, the tie-breaks are this build's own.
+ */
+#define DAGCON_PANEL_MAX_SIDE 512u
+int dagcon_align_panels(dagcon_ctx *ctx, uint32_t n,
+                        const uint64_t *q_off, const uint32_t *q_len,
+                        const uint64_t *t_off, const uint32_t *t_len,
+                        const char *q_blob, uint64_t q_bytes, const char *t_blob, uint64_t t_bytes,
+                        const uint64_t *panel_begin,   /* [n + 1] */
+                        const uint32_t *panel_t_len,   /* [panel_begin[n]] A bases per panel */
+                        const uint32_t *panel_q_len,   /* [panel_begin[n]] B bases per panel */
+                        const uint64_t *out_off, char *qaln, char *taln, uint32_t *aln_len,
+                        int32_t *panel_dist);          /* [panel_begin[n]] edit distance per panel, or NULL */
+
+/*
  * What main.cpp:117-145 does with -a, in one call: the records of a batch of targets as the .pre format carries
  * them (Alignment.cpp:82-112: tstart is Alignment::start as parsePre leaves it, q / t the unaligned sequences) are
  * re-aligned as by dagcon_align, start / end / strand handled as SimpleAligner.cpp:51-62 does (start = tstart,
@@ -262,7 +286,9 @@ int dagcon_debug_counters(dagcon_ctx *ctx, unsigned long long *out8);
 /* Records of the last dagcon_align / dagcon_consensus_pre on this context whose corners the widest band could not
  * connect (sequences of very different lengths, indels of hundreds of bases): their alignment has length 0 and the
  * min_len filter then drops them, where the reference's SDPAlign + GuidedAlign (SimpleAligner.cpp:35-48) always
- * returns something.  The calls succeed; a caller that cares asks here (the pbdagcon host warns on stderr). */
+ * returns something.  After dagcon_align_panels: the pairs it did not align because a panel was larger than
+ * DAGCON_PANEL_MAX_SIDE (length 0 as well).  The calls succeed; a caller that cares asks here (the pbdagcon host
+ * warns on stderr, dazcon --trace-panels aligns those pairs again with dagcon_align). */
 uint32_t dagcon_align_dropped(dagcon_ctx *ctx);
 
 /* Host arithmetic only (no device, no context): the pieces dagcon_upload would cut the merge and bestPath

@@ -30,7 +30,7 @@ EXPORTS = [
     "dagcon_last_error", "dagcon_consensus", "dagcon_upload", "dagcon_run", "dagcon_sync",
     "dagcon_fetch", "dagcon_get_timings", "dagcon_normalize", "dagcon_debug_graph",
     "dagcon_debug_counters", "dagcon_host_alloc", "dagcon_host_free", "dagcon_align",
-    "dagcon_consensus_pre", "dagcon_debug_plan", "dagcon_align_dropped",
+    "dagcon_consensus_pre", "dagcon_debug_plan", "dagcon_align_dropped", "dagcon_align_panels",
 ]
 ABI_VERSION = 2
 
@@ -118,6 +118,10 @@ def load() -> C.CDLL:
                                    C.c_uint32, vp, vp, vp, vp, vp]
     L.dagcon_debug_graph.argtypes = [vp, C.c_uint32, C.POINTER(GraphDump)]
     L.dagcon_align.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp]
+    L.dagcon_align_panels.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp,
+                                      vp, vp, vp, vp, vp]
+    L.dagcon_align_dropped.argtypes = [vp]
+    L.dagcon_align_dropped.restype = C.c_uint32
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
     L.dagcon_host_free.restype = None
@@ -350,6 +354,42 @@ class Context:
                                       qa.ctypes.data, ta.ctypes.data, ln.ctypes.data))
         return [(qa[int(oo[a]):int(oo[a]) + int(ln[a])].tobytes(), ta[int(oo[a]):int(oo[a]) + int(ln[a])].tobytes())
                 for a in range(n)]
+
+    def align_panels(self, pairs, panels):
+        """pairs = [(qseq, tseq)] (B interval, A interval), panels[a] = [(A bases, B bases)] per trace-point panel
+        -> ([(qaln, taln)], [[distance per panel]]) (dagcon_align_panels; an overlap with a panel larger than
+        DAGCON_PANEL_MAX_SIDE comes back as (b"", b"") with distances -1, and counts in align_dropped())."""
+        n = len(pairs)
+        if n == 0:
+            return [], []
+        ql = np.array([len(q) for q, _ in pairs], dtype=np.uint32)
+        tl = np.array([len(t) for _, t in pairs], dtype=np.uint32)
+        qo, to, oo = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        qo[1:] = np.cumsum(ql[:-1], dtype=np.uint64)
+        to[1:] = np.cumsum(tl[:-1], dtype=np.uint64)
+        oo[1:] = np.cumsum((ql[:-1].astype(np.uint64) + tl[:-1]), dtype=np.uint64)
+        pb = np.zeros(n + 1, np.uint64)
+        pb[1:] = np.cumsum([len(p) for p in panels], dtype=np.uint64)
+        np_ = int(pb[-1])
+        ptl = np.array([x for p in panels for x, _ in p] or [0], dtype=np.uint32)
+        pql = np.array([y for p in panels for _, y in p] or [0], dtype=np.uint32)
+        qb = np.frombuffer(b"".join(q for q, _ in pairs) or b"\0", dtype=np.uint8)
+        tb = np.frombuffer(b"".join(t for _, t in pairs) or b"\0", dtype=np.uint8)
+        total = int(ql.sum()) + int(tl.sum()) + 1
+        qa, ta = np.zeros(total, np.uint8), np.zeros(total, np.uint8)
+        ln = np.zeros(n, np.uint32)
+        dist = np.zeros(max(np_, 1), np.int32)
+        self._chk(self.L.dagcon_align_panels(self.h, n, qo.ctypes.data, ql.ctypes.data, to.ctypes.data, tl.ctypes.data,
+                                             qb.ctypes.data, int(ql.sum()), tb.ctypes.data, int(tl.sum()), pb.ctypes.data,
+                                             ptl.ctypes.data, pql.ctypes.data, oo.ctypes.data, qa.ctypes.data,
+                                             ta.ctypes.data, ln.ctypes.data, dist.ctypes.data))
+        alns = [(qa[int(oo[a]):int(oo[a]) + int(ln[a])].tobytes(), ta[int(oo[a]):int(oo[a]) + int(ln[a])].tobytes())
+                for a in range(n)]
+        return alns, [dist[int(pb[a]):int(pb[a + 1])].tolist() for a in range(n)]
+
+    def align_dropped(self):
+        """Pairs the last align / align_panels / consensus_pre left unaligned (dagcon_align_dropped)."""
+        return int(self.L.dagcon_align_dropped(self.h))
 
     def consensus_pre(self, targets, strict=True):
         """targets = [(tlen, [(tstart, strand, qseq, tseq)])]: .pre records per target (Alignment.cpp:82-112)

@@ -27,6 +27,7 @@
 #include "k_merge_q.hip.h"
 #include "k_bestpath.hip.h"
 #include "k_align.hip.h"
+#include "k_align_panels.hip.h"
 
 namespace {
 
@@ -137,6 +138,7 @@ struct Ctx {
     DevBuf d_nodes, d_best, d_queue, d_score, d_cns_tmp, d_bp_tt, d_score_b;
     DevBuf d_pool, d_stk, d_cuts, d_cuts_bp, d_bp_stat, d_bp_len, d_nextcut, d_tile_list, d_rd, d_pro_state, d_sh_cnt, d_seg_done, d_wl_first, d_queue0, d_bp_end, d_bp_ab, d_defer, d_cns_tmp0;
     DevBuf d_al[14];                                // dagcon_align: blobs, offsets, outputs, directions, launch order, widths
+    DevBuf d_pn[18];                                // dagcon_align_panels: blobs, panels, scratch, outputs, launch order
     DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
 
     uint64_t norm_cap = 0, node_cap = 0, pool_cap = 0, cns_cap = 0, seg_cap = 0;
@@ -558,6 +560,7 @@ void dagcon_destroy(dagcon_ctx *ctx) {
                      &c->d_st};
     for (DevBuf *b : all) free_buf(*b);
     for (DevBuf &b : c->d_al) free_buf(b);
+    for (DevBuf &b : c->d_pn) free_buf(b);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1301,6 +1304,134 @@ int dagcon_align(dagcon_ctx *ctx, uint32_t n, const uint64_t *q_off, const uint3
     if (r != DAGCON_OK) return r;
     HIPCHK(c, d2h(c, qaln, c->d_al[7].p, out_bytes));
     HIPCHK(c, d2h(c, taln, c->d_al[8].p, out_bytes));
+    return DAGCON_OK;
+}
+
+// dazcon --trace-panels (k_align_panels.hip.h).  A kernel instance per panel size: C cells a lane (n <= 64 C), R rows of
+// directions in LDS (m <= R); as many waves a workgroup as keep its LDS at 64 KiB or less, four at most.
+extern "C++" {
+template <int C, int R>
+static void launch_panels(hipStream_t s, const DgPanelParams &pp) {
+    constexpr int per_wave = R * 64 * (C <= 4 ? 1 : 2);
+    constexpr int WPB = per_wave >= 65536 ? 1 : 65536 / per_wave > 4 ? 4 : 65536 / per_wave;
+    hipLaunchKernelGGL((k_align_panel<C, R, WPB>), dim3((pp.n + WPB - 1) / WPB), dim3(64 * WPB), 0, s, pp);
+}
+}
+
+int dagcon_align_panels(dagcon_ctx *ctx, uint32_t n, const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off,
+                        const uint32_t *t_len, const char *q_blob, uint64_t q_bytes, const char *t_blob, uint64_t t_bytes,
+                        const uint64_t *panel_begin, const uint32_t *panel_t_len, const uint32_t *panel_q_len,
+                        const uint64_t *out_off, char *qaln, char *taln, uint32_t *aln_len, int32_t *panel_dist) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    c->align_dropped = 0;
+    if (n == 0) return DAGCON_OK;
+    if (!q_off || !q_len || !t_off || !t_len || !q_blob || !t_blob || !panel_begin || !out_off || !qaln || !taln || !aln_len)
+        return fail(c, DAGCON_ERR_INVALID_ARG, "NULL argument");
+    const uint64_t np = panel_begin[n];
+    if (np && (!panel_t_len || !panel_q_len)) return fail(c, DAGCON_ERR_INVALID_ARG, "NULL argument");
+    if (np > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many panels");
+    HIPCHK(c, hipSetDevice(c->device));
+    // checks, then every panel's place: its first bases in the blobs, its room of m + n columns in the scratch buffer
+    std::vector<uint64_t> p_qoff(np), p_toff(np), p_scr(np);
+    std::vector<uint32_t> kept, cls[9];
+    std::vector<uint8_t> drop(n, 0);
+    uint64_t out_bytes = 0, scr_bytes = 0;
+    uint32_t dropped = 0;
+    for (uint32_t a = 0; a < n; a++) {
+        if (q_off[a] > q_bytes || q_len[a] > q_bytes - q_off[a] || t_off[a] > t_bytes || t_len[a] > t_bytes - t_off[a])
+            return fail(c, DAGCON_ERR_INVALID_ARG, "pair %u runs past its blob", a);
+        if ((uint64_t)q_len[a] + t_len[a] > 0x7FFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "pair %u too long", a);
+        if (panel_begin[a] > panel_begin[a + 1] || panel_begin[a + 1] > np)
+            return fail(c, DAGCON_ERR_INVALID_ARG, "panel_begin is not ascending at pair %u", a);
+        uint64_t st = 0, sq = 0;
+        bool big = false;
+        for (uint64_t p = panel_begin[a]; p < panel_begin[a + 1]; p++) {
+            p_toff[p] = t_off[a] + st; p_qoff[p] = q_off[a] + sq;
+            st += panel_t_len[p]; sq += panel_q_len[p];
+            big |= panel_t_len[p] > DAGCON_PANEL_MAX_SIDE || panel_q_len[p] > DAGCON_PANEL_MAX_SIDE;
+        }
+        if (st != t_len[a] || sq != q_len[a])
+            return fail(c, DAGCON_ERR_INVALID_ARG, "pair %u: its panels hold %llu A and %llu B bases, not %u and %u", a,
+                        (unsigned long long)st, (unsigned long long)sq, t_len[a], q_len[a]);
+        out_bytes = std::max<uint64_t>(out_bytes, out_off[a] + (uint64_t)q_len[a] + t_len[a]);
+        if (big) { drop[a] = 1; dropped++; continue; }
+        kept.push_back(a);
+        for (uint64_t p = panel_begin[a]; p < panel_begin[a + 1]; p++) {
+            p_scr[p] = scr_bytes;
+            scr_bytes += (uint64_t)panel_t_len[p] + panel_q_len[p];
+            const uint32_t m = panel_t_len[p], w = panel_q_len[p];
+            const int ci = w <= 128 ? 0 : w <= 256 ? 1 : 2, ri = m <= 128 ? 0 : m <= 256 ? 1 : 2;
+            cls[ci * 3 + ri].push_back((uint32_t)p);
+        }
+    }
+    DevBuf &dq = c->d_pn[0], &dt = c->d_pn[1], &dpq = c->d_pn[2], &dpt = c->d_pn[3], &dpql = c->d_pn[4], &dptl = c->d_pn[5],
+           &dscr = c->d_pn[6], &dqs = c->d_pn[7], &dts = c->d_pn[8], &dplen = c->d_pn[9], &dpdist = c->d_pn[10],
+           &didx = c->d_pn[11], &dpb = c->d_pn[12], &doo = c->d_pn[13], &dqa = c->d_pn[14], &dta = c->d_pn[15],
+           &dlen = c->d_pn[16], &dkept = c->d_pn[17];
+    hipStream_t s = c->stream;
+    ENSURE(c, dlen, (size_t)n * 4); ENSURE(c, dqa, out_bytes); ENSURE(c, dta, out_bytes);
+    HIPCHK(c, hipMemsetAsync(dlen.p, 0, (size_t)n * 4, s));
+    if (!kept.empty()) {
+        ENSURE(c, dq, q_bytes); ENSURE(c, dt, t_bytes);
+        ENSURE(c, dpq, np * 8); ENSURE(c, dpt, np * 8); ENSURE(c, dpql, np * 4); ENSURE(c, dptl, np * 4); ENSURE(c, dscr, np * 8);
+        ENSURE(c, dqs, scr_bytes); ENSURE(c, dts, scr_bytes); ENSURE(c, dplen, np * 4); ENSURE(c, dpdist, np * 4);
+        ENSURE(c, didx, np * 4); ENSURE(c, dpb, ((size_t)n + 1) * 8); ENSURE(c, doo, (size_t)n * 8); ENSURE(c, dkept, kept.size() * 4);
+        HIPCHK(c, hipMemcpyAsync(dq.p, q_blob, q_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(dt.p, t_blob, t_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(dpq.p, p_qoff.data(), np * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(dpt.p, p_toff.data(), np * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(dpql.p, panel_q_len, np * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(dptl.p, panel_t_len, np * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(dscr.p, p_scr.data(), np * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(dpb.p, panel_begin, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(doo.p, out_off, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(dkept.p, kept.data(), kept.size() * 4, hipMemcpyHostToDevice, s));
+        std::vector<uint32_t> order;
+        order.reserve(np);
+        for (const auto &v : cls) order.insert(order.end(), v.begin(), v.end());
+        HIPCHK(c, hipMemcpyAsync(didx.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, s));
+        DgPanelParams pp;
+        pp.q = (const uint8_t *)dq.p; pp.t = (const uint8_t *)dt.p;
+        pp.q_off = (const uint64_t *)dpq.p; pp.t_off = (const uint64_t *)dpt.p;
+        pp.q_len = (const uint32_t *)dpql.p; pp.t_len = (const uint32_t *)dptl.p;
+        pp.scr_off = (const uint64_t *)dscr.p; pp.qscr = (uint8_t *)dqs.p; pp.tscr = (uint8_t *)dts.p;
+        pp.len = (uint32_t *)dplen.p; pp.dist = (int32_t *)dpdist.p;
+        size_t first = 0;
+        for (int k = 0; k < 9; k++) {
+            if (cls[k].empty()) continue;
+            pp.idx = (const uint32_t *)didx.p + first; pp.n = (uint32_t)cls[k].size();
+            switch (k) {
+                case 0: launch_panels<2, 128>(s, pp); break;
+                case 1: launch_panels<2, 256>(s, pp); break;
+                case 2: launch_panels<2, 512>(s, pp); break;
+                case 3: launch_panels<4, 128>(s, pp); break;
+                case 4: launch_panels<4, 256>(s, pp); break;
+                case 5: launch_panels<4, 512>(s, pp); break;
+                case 6: launch_panels<8, 128>(s, pp); break;
+                case 7: launch_panels<8, 256>(s, pp); break;
+                default: launch_panels<8, 512>(s, pp); break;
+            }
+            HIPCHK(c, hipGetLastError());
+            first += cls[k].size();
+        }
+        hipLaunchKernelGGL(k_align_panel_compact, dim3((uint32_t)kept.size()), dim3(DG_PANEL_COMPACT_THREADS), 0, s,
+                           (const uint64_t *)dpb.p, (const uint64_t *)dscr.p, (const uint32_t *)dptl.p, (const uint32_t *)dpql.p,
+                           (const uint32_t *)dplen.p, (const uint8_t *)dqs.p, (const uint8_t *)dts.p, (const uint64_t *)doo.p,
+                           (uint8_t *)dqa.p, (uint8_t *)dta.p, (uint32_t *)dlen.p, (const uint32_t *)dkept.p);
+        HIPCHK(c, hipGetLastError());
+        if (panel_dist) HIPCHK(c, d2h(c, panel_dist, dpdist.p, np * 4));
+    }
+    HIPCHK(c, d2h(c, aln_len, dlen.p, (size_t)n * 4));
+    if (!kept.empty()) {
+        HIPCHK(c, d2h(c, qaln, dqa.p, out_bytes));
+        HIPCHK(c, d2h(c, taln, dta.p, out_bytes));
+    }
+    for (uint32_t a = 0; a < n; a++) {
+        if ((uint64_t)aln_len[a] > (uint64_t)q_len[a] + t_len[a]) return fail(c, DAGCON_ERR_INTERNAL, "pair %u: alignment longer than its room", a);
+        if (drop[a] && panel_dist) for (uint64_t p = panel_begin[a]; p < panel_begin[a + 1]; p++) panel_dist[p] = -1;
+    }
+    c->align_dropped = dropped;
     return DAGCON_OK;
 }
 

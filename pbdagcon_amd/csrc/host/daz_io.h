@@ -11,8 +11,10 @@
 // (tests/daz_files.py) -- never against a file DALIGNER or DAZZ_DB wrote.
 //
 // The reference then recomputes each overlap's alignment inside the trace-point panels (Compute_Trace_PTS,
-// DazAlnProvider.cpp:349) -- also absent.  dazcon_main.cpp aligns the overlap's two intervals with the device aligner
-// (dagcon_align, the -a stage of pbdagcon) instead: same endpoints, this build's own banded alignment between them.
+// DazAlnProvider.cpp:349) -- also absent.  By default dazcon_main.cpp aligns the overlap's two intervals with the device
+// aligner (dagcon_align, the -a stage of pbdagcon) instead: same endpoints, this build's own banded alignment between
+// them, the trace passed over.  With --trace-panels it keeps the trace (LasReader::next returns it) and aligns inside
+// the panels it gives (dagcon_align_panels, k_align_panels.hip.h: this build's own tie-breaks, parity unpinned too).
 #pragma once
 #include <cstdint>
 #include <cstdio>

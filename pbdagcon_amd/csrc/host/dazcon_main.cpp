@@ -16,7 +16,9 @@
 // with the reference's flags and defaults (dazcon.cpp:122-192).  Round 3: -a <file>.las and -s <file>.db are read in
 // their binary layouts (daz_io.h: PARITY UNPINNED, tested by round trip against this build's own writer), and every
 // overlap of a .las is aligned between its end points by the device aligner (dagcon_align) where the reference runs
-// DALIGNER's Compute_Trace_PTS.  Otherwise -s names a text file that carries what
+// DALIGNER's Compute_Trace_PTS.  --trace-panels does what Compute_Trace_PTS does instead: each overlap aligned inside
+// its trace-point panels (dagcon_align_panels; tie-breaks this build's own, PARITY UNPINNED), an overlap with a panel
+// over DAGCON_PANEL_MAX_SIDE bases end to end as before.  Otherwise -s names a text file that carries what
 // the .db holds (the reads) and -a one that carries what the .las holds after Read_Overlap /
 // Compute_Trace_PTS (overlap records with their trace points, or with alignment strings already
 // decoded); INTEGRATION.md gives the layout:
@@ -53,7 +55,7 @@ namespace {
 struct Opts {
     int threads = 4;
     unsigned min_cov = 6, min_len = 500, trim = 10, max_hits = 85;
-    bool sort_cov = false, proper = false, verbose = false, dump_hits = false, dump_alns = false;
+    bool sort_cov = false, proper = false, verbose = false, dump_hits = false, dump_alns = false, trace_panels = false;
     std::string aln_file, seq_file;
     std::set<int> targets;
     size_t batch_targets = 512;
@@ -74,6 +76,8 @@ void usage(FILE *f) {
             "  -x, --coverage-sort sort hits by coverage\n"
             "  -o, --only-proper-overlaps  use only overlaps that align to the ends\n"
             "  -v, --verbose\n"
+            "  --trace-panels      .las input: align every overlap inside its trace-point panels (dagcon_align_panels)\n"
+            "                      instead of end to end; overlaps with a panel over 512 bases are aligned end to end\n"
             "  targets             limit consensus to these target ids\n"
             "  version 0.3 (dagcon-mi355x)\n");
 }
@@ -113,6 +117,7 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "-v" || a == "--verbose") o.verbose = true;
         else if (a == "--dump-hits") o.dump_hits = true;          // test hook: hit selection only, no GPU
         else if (a == "--dump-alns") o.dump_alns = true;          // test hook: the alignments handed to the consensus, no GPU
+        else if (a == "--trace-panels") o.trace_panels = true;
         else if (a == "--device") { if (!need(&u)) return 1; o.device = (int)u; }
         else if (a == "--batch-targets") { if (!need(&u) || !u) return 1; o.batch_targets = u; }
         else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
@@ -139,6 +144,7 @@ struct Record {
     bool realign = false;              // .las record: aligned between its end points on the device (see daz_io.h)
     std::string tstr, qstr;
     std::vector<int> trace;            // R record: what Compute_Trace_PTS left in path.trace
+    std::vector<uint16_t> tpts;        // .las record with --trace-panels: its trace points (differences, B bases per panel)
 };
 
 // DazAlnProvider.cpp:165-211
@@ -242,7 +248,34 @@ std::string complement_seq(const std::string &s) {        // DAZZ_DB Complement_
     return r;
 }
 
-struct Aln { unsigned start; std::string q, t; bool job = false; int aread = 0, bread = 0; unsigned flags = 0; Path path; };
+struct Aln { unsigned start; std::string q, t; bool job = false; int aread = 0, bread = 0; unsigned flags = 0; Path path; std::vector<uint16_t> tpts; };
+
+// --trace-panels: a .las record's trace as panels of A (DALIGNER's layout): panel 0 is A[abpos, min(aepos, (abpos / tspace
+// + 1) tspace)), the middle ones tspace bases, the last ends at aepos; panel i takes tpts[2 i + 1] bases of B', the
+// B read as the overlap sees it (complemented when COMP(flags)).  False when the trace does not fit the overlap, *err says why.
+bool trace_panels(const Path &p, const std::vector<uint16_t> &tpts, int tspace, std::vector<uint32_t> *alen, std::vector<uint32_t> *blen,
+                  std::string *err) {
+    std::vector<uint32_t> &ends = *alen;
+    ends.clear(); blen->clear();
+    for (int a = p.abpos; a < p.aepos;) {
+        const int e = std::min(p.aepos, (a / tspace + 1) * tspace);
+        ends.push_back((uint32_t)(e - a));
+        a = e;
+    }
+    if (tpts.size() != 2 * ends.size()) {
+        *err = "its trace has " + std::to_string(tpts.size() / 2) + (tpts.size() % 2 ? ".5" : "") + " pairs, its A interval [" +
+               std::to_string(p.abpos) + ", " + std::to_string(p.aepos) + ") " + std::to_string(ends.size()) + " panels of " +
+               std::to_string(tspace);
+        return false;
+    }
+    long long b = 0;
+    for (size_t i = 0; i < ends.size(); i++) { b += tpts[2 * i + 1]; blen->push_back(tpts[2 * i + 1]); }
+    if (b != (long long)p.bepos - p.bbpos) {
+        *err = "its trace's B bases add up to " + std::to_string(b) + ", not bepos - bbpos = " + std::to_string(p.bepos - p.bbpos);
+        return false;
+    }
+    return true;
+}
 struct TargetData { int id; std::string seq; std::vector<Aln> alns; };
 
 }  // namespace
@@ -252,6 +285,10 @@ int main(int argc, char **argv) {
     if (int rc = parse_args(argc, argv, o)) return rc;
     auto ends_with = [](const std::string &x, const char *suf) { const size_t n = strlen(suf); return x.size() >= n && x.compare(x.size() - n, n, suf) == 0; };
     const bool las_in = ends_with(o.aln_file, ".las"), db_in = ends_with(o.seq_file, ".db");
+    if (o.trace_panels && !las_in) {
+        fprintf(stderr, "dazcon: --trace-panels needs a DALIGNER .las file (-a name ending in .las); %s is the text layout\n", o.aln_file.c_str());
+        return 1;
+    }
     // ---- reads (-s) ----
     std::vector<std::string> reads;       // index = 0-based read id
     if (db_in) {
@@ -283,6 +320,7 @@ int main(int argc, char **argv) {
     }
     std::vector<TargetData> out_targets;
     size_t n_jobs = 0;
+    int tspace = 0;                                    // the .las's trace spacing
     Target trg;
     auto finish_target = [&]() -> int {
         if (trg.id < 0) return 0;
@@ -301,7 +339,10 @@ int main(int argc, char **argv) {
                 Aln al;
                 al.start = (unsigned)rec.path.abpos + 1;                                 // :358
                 if (rec.decoded) { al.t = rec.tstr; al.q = rec.qstr; }
-                else if (rec.realign) { al.job = true; al.aread = rec.aread; al.bread = rec.bread; al.flags = rec.flags; al.path = rec.path; n_jobs++; }
+                else if (rec.realign) {
+                    al.job = true; al.aread = rec.aread; al.bread = rec.bread; al.flags = rec.flags; al.path = rec.path; al.tpts = rec.tpts;
+                    n_jobs++;
+                }
                 else {
                     if ((size_t)rec.bread >= reads.size() || reads[(size_t)rec.bread].empty()) {
                         fprintf(stderr, "dazcon: read %d is not in %s\n", rec.bread + 1, o.seq_file.c_str());
@@ -346,8 +387,8 @@ int main(int argc, char **argv) {
         return 0;
     };
     if (las_in) {
-        // Read_Overlap / Read_Trace (DazAlnProvider.cpp:134-140); the trace points are read and passed over: the
-        // alignment between the overlap's end points is the device aligner's (daz_io.h)
+        // Read_Overlap / Read_Trace (DazAlnProvider.cpp:134-140); the trace points are passed over (the alignment between
+        // the overlap's end points is the device aligner's, daz_io.h) unless --trace-panels keeps them for the panels
         daz::LasReader las;
         std::string err;
         if (!las.open(o.aln_file, &err)) { fprintf(stderr, "dazcon: %s\n", err.c_str()); return 1; }
@@ -357,7 +398,18 @@ int main(int argc, char **argv) {
             Record r;
             r.aread = ov.aread; r.bread = ov.bread; r.flags = ov.flags; r.realign = true;
             r.path.abpos = ov.abpos; r.path.aepos = ov.aepos; r.path.bbpos = ov.bbpos; r.path.bepos = ov.bepos; r.path.diffs = ov.diffs;
-            if (int rc = take(std::move(r), "overlap " + std::to_string(las.seen))) return rc;
+            const std::string where = "overlap " + std::to_string(las.seen);
+            if (o.trace_panels) {
+                std::string why;
+                std::vector<uint32_t> pa, pb;
+                if (ov.aepos >= ov.abpos && ov.abpos >= 0 && !trace_panels(r.path, tr, las.tspace, &pa, &pb, &why)) {
+                    fprintf(stderr, "dazcon: %s (A read %d, B read %d): %s\n", where.c_str(), ov.aread + 1, ov.bread + 1, why.c_str());
+                    return 1;
+                }
+                r.tpts = tr;
+            }
+            tspace = las.tspace;
+            if (int rc = take(std::move(r), where)) return rc;
         }
         if (!err.empty()) { fprintf(stderr, "dazcon: %s\n", err.c_str()); return 1; }
         if (int rc = finish_target()) return rc;
@@ -421,40 +473,72 @@ int main(int argc, char **argv) {
     }
     if (n_jobs) {
         // the overlaps of a .las: A[abpos, aepos) against B[bbpos, bepos) (B complemented when COMP(flags), its
-        // coordinates are the complement's: DazAlnProvider.cpp:333-347), global between the end points, in groups of
-        // at most 256 MB of sequence
-        std::vector<Aln *> jobs;
+        // coordinates are the complement's: DazAlnProvider.cpp:333-347), in groups of at most 256 MB of sequence: global
+        // between the end points (dagcon_align), or with --trace-panels inside the trace-point panels
+        // (dagcon_align_panels), where an overlap with a panel over DAGCON_PANEL_MAX_SIDE bases is left over for dagcon_align
+        std::vector<Aln *> jobs, left_over;
         for (TargetData &td : out_targets) for (Aln &al : td.alns) if (al.job) jobs.push_back(&al);
-        size_t j0 = 0;
         uint32_t dropped = 0;
-        while (j0 < jobs.size()) {
-            std::string qb, tb;
-            std::vector<uint64_t> qo, to, oo;
-            std::vector<uint32_t> ql, tl;
-            uint64_t room = 0;
-            size_t j1 = j0;
-            for (; j1 < jobs.size() && qb.size() + tb.size() < (256u << 20); j1++) {
-                const Aln &al = *jobs[j1];
-                const std::string &bs = reads[(size_t)al.bread];
-                const std::string bq = (al.flags & daz::COMP_FLAG) ? complement_seq(bs) : bs;
-                qo.push_back(qb.size()); ql.push_back((uint32_t)(al.path.bepos - al.path.bbpos));
-                qb.append(bq, (size_t)al.path.bbpos, (size_t)(al.path.bepos - al.path.bbpos));
-                to.push_back(tb.size()); tl.push_back((uint32_t)(al.path.aepos - al.path.abpos));
-                tb.append(reads[(size_t)al.aread], (size_t)al.path.abpos, (size_t)(al.path.aepos - al.path.abpos));
-                oo.push_back(room); room += (uint64_t)ql.back() + tl.back();
+        unsigned long long n_panels = 0, over_trace = 0;
+        auto align_jobs = [&](const std::vector<Aln *> &js, bool panels) -> int {
+            size_t j0 = 0;
+            while (j0 < js.size()) {
+                std::string qb, tb;
+                std::vector<uint64_t> qo, to, oo, pbeg{0};
+                std::vector<uint32_t> ql, tl, pa, pq, a_len, b_len;
+                uint64_t room = 0;
+                size_t j1 = j0;
+                for (; j1 < js.size() && qb.size() + tb.size() < (256u << 20); j1++) {
+                    const Aln &al = *js[j1];
+                    const std::string &bs = reads[(size_t)al.bread];
+                    const std::string bq = (al.flags & daz::COMP_FLAG) ? complement_seq(bs) : bs;
+                    qo.push_back(qb.size()); ql.push_back((uint32_t)(al.path.bepos - al.path.bbpos));
+                    qb.append(bq, (size_t)al.path.bbpos, (size_t)(al.path.bepos - al.path.bbpos));
+                    to.push_back(tb.size()); tl.push_back((uint32_t)(al.path.aepos - al.path.abpos));
+                    tb.append(reads[(size_t)al.aread], (size_t)al.path.abpos, (size_t)(al.path.aepos - al.path.abpos));
+                    oo.push_back(room); room += (uint64_t)ql.back() + tl.back();
+                    if (panels) {
+                        std::string why;
+                        trace_panels(al.path, al.tpts, tspace, &a_len, &b_len, &why);     // (checked when the record was read)
+                        pa.insert(pa.end(), a_len.begin(), a_len.end()); pq.insert(pq.end(), b_len.begin(), b_len.end());
+                        pbeg.push_back(pa.size());
+                    }
+                }
+                std::string qa((size_t)room + 1, '\0'), ta((size_t)room + 1, '\0');
+                std::vector<uint32_t> alen(j1 - j0, 0);
+                std::vector<int32_t> dist(pa.size() + 1, 0);
+                const uint32_t nb = (uint32_t)(j1 - j0);
+                rc = panels ? dagcon_align_panels(ctx, nb, qo.data(), ql.data(), to.data(), tl.data(), qb.data(), qb.size(), tb.data(), tb.size(),
+                                                  pbeg.data(), pa.data(), pq.data(), oo.data(), &qa[0], &ta[0], alen.data(), dist.data())
+                            : dagcon_align(ctx, nb, qo.data(), ql.data(), to.data(), tl.data(), qb.data(), qb.size(), tb.data(), tb.size(),
+                                           oo.data(), &qa[0], &ta[0], alen.data());
+                if (rc != DAGCON_OK) { fprintf(stderr, "dazcon: alignment failed (%d): %s\n", rc, dagcon_last_error(ctx)); return 1; }
+                if (!panels) dropped += dagcon_align_dropped(ctx);
+                for (size_t j = j0; j < j1; j++) {
+                    if (panels) {
+                        const uint64_t p0 = pbeg[j - j0], p1 = pbeg[j - j0 + 1];
+                        if (p1 > p0 && dist[p0] < 0) { left_over.push_back(js[j]); continue; }       // a panel too large
+                        // DALIGNER's own path through panel p has tpts[2 p] differences: an optimal one has no more
+                        for (uint64_t p = p0; p < p1; p++) over_trace += dist[p] > (int32_t)js[j]->tpts[2 * (p - p0)];
+                        n_panels += p1 - p0;
+                    }
+                    js[j]->q.assign(qa, (size_t)oo[j - j0], alen[j - j0]);
+                    js[j]->t.assign(ta, (size_t)oo[j - j0], alen[j - j0]);
+                }
+                j0 = j1;
             }
-            std::string qa((size_t)room + 1, '\0'), ta((size_t)room + 1, '\0');
-            std::vector<uint32_t> alen(j1 - j0, 0);
-            rc = dagcon_align(ctx, (uint32_t)(j1 - j0), qo.data(), ql.data(), to.data(), tl.data(), qb.data(), qb.size(), tb.data(), tb.size(),
-                              oo.data(), &qa[0], &ta[0], alen.data());
-            if (rc != DAGCON_OK) { fprintf(stderr, "dazcon: alignment failed (%d): %s\n", rc, dagcon_last_error(ctx)); dagcon_destroy(ctx); return 1; }
-            dropped += dagcon_align_dropped(ctx);
-            for (size_t j = j0; j < j1; j++) {
-                jobs[j]->q.assign(qa, (size_t)oo[j - j0], alen[j - j0]);
-                jobs[j]->t.assign(ta, (size_t)oo[j - j0], alen[j - j0]);
-            }
-            j0 = j1;
+            return 0;
+        };
+        if (align_jobs(jobs, o.trace_panels)) { dagcon_destroy(ctx); return 1; }
+        if (!left_over.empty()) {
+            fprintf(stderr, "dazcon: %zu overlaps have a trace-point panel over %u bases and were aligned end to end\n", left_over.size(),
+                    DAGCON_PANEL_MAX_SIDE);
+            const std::vector<Aln *> again(left_over);
+            if (align_jobs(again, false)) { dagcon_destroy(ctx); return 1; }
         }
+        if (o.trace_panels && o.verbose)
+            fprintf(stderr, "dazcon: %llu of %llu trace-point panels came out with more differences than their trace records "
+                            "(the .las and the database disagree, or the trace layout was misread)\n", over_trace, n_panels);
         if (dropped) fprintf(stderr, "dazcon: warning: %u overlaps could not be aligned inside the widest band and were dropped\n", dropped);
         if (o.dump_alns) {
             for (const TargetData &td : out_targets)

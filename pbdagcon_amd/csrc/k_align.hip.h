@@ -101,6 +101,17 @@ __device__ __forceinline__ int dg_al_dpp(int old, int src) {
 #define DG_DPP_WAVE_SHR1 0x138     // lane l reads lane l - 1
 #define DG_DPP_BCAST15 0x142
 #define DG_DPP_BCAST31 0x143
+// inclusive prefix minimum over the lanes: lane l gets the minimum of x over lanes 0 .. l (k_align_panels.hip.h too)
+__device__ __forceinline__ int dg_al_scan_min(int incl) {
+    int v;
+    v = dg_al_dpp<DG_DPP_ROW_SHR(1), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
+    v = dg_al_dpp<DG_DPP_ROW_SHR(2), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
+    v = dg_al_dpp<DG_DPP_ROW_SHR(4), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
+    v = dg_al_dpp<DG_DPP_ROW_SHR(8), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
+    v = dg_al_dpp<DG_DPP_BCAST15, 0xa>(0x7fffffff, incl); incl = v < incl ? v : incl;
+    v = dg_al_dpp<DG_DPP_BCAST31, 0xc>(0x7fffffff, incl); incl = v < incl ? v : incl;
+    return incl;
+}
 
 template <int C>
 __global__ __launch_bounds__(64) void k_align_band(DgAlignParams p) {
@@ -225,13 +236,7 @@ __global__ __launch_bounds__(64) void k_align_band(DgAlignParams p) {
             lm = x < lm ? x : lm;
         }
         // exclusive prefix minimum over the lanes in front
-        int incl = lm, v;
-        v = dg_al_dpp<DG_DPP_ROW_SHR(1), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
-        v = dg_al_dpp<DG_DPP_ROW_SHR(2), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
-        v = dg_al_dpp<DG_DPP_ROW_SHR(4), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
-        v = dg_al_dpp<DG_DPP_ROW_SHR(8), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
-        v = dg_al_dpp<DG_DPP_BCAST15, 0xa>(0x7fffffff, incl); incl = v < incl ? v : incl;
-        v = dg_al_dpp<DG_DPP_BCAST31, 0xc>(0x7fffffff, incl); incl = v < incl ? v : incl;
+        const int incl = dg_al_scan_min(lm);
         int pm = dg_al_dpp<DG_DPP_WAVE_SHR1, 0xf>(0x7fffffff, incl);
         uint32_t word = 0;
 #pragma unroll
@@ -379,13 +384,7 @@ __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
     // the band moves on to row i: where the previous row's best cell is (its first one) says how far
     auto advance = [&](const uint32_t i) {
         {
-            int mn = P[0] < P[1] ? P[0] : P[1], v;
-            v = dg_al_dpp<DG_DPP_ROW_SHR(1), 0xf>(0x7fffffff, mn); mn = v < mn ? v : mn;
-            v = dg_al_dpp<DG_DPP_ROW_SHR(2), 0xf>(0x7fffffff, mn); mn = v < mn ? v : mn;
-            v = dg_al_dpp<DG_DPP_ROW_SHR(4), 0xf>(0x7fffffff, mn); mn = v < mn ? v : mn;
-            v = dg_al_dpp<DG_DPP_ROW_SHR(8), 0xf>(0x7fffffff, mn); mn = v < mn ? v : mn;
-            v = dg_al_dpp<DG_DPP_BCAST15, 0xa>(0x7fffffff, mn); mn = v < mn ? v : mn;
-            v = dg_al_dpp<DG_DPP_BCAST31, 0xc>(0x7fffffff, mn); mn = v < mn ? v : mn;
+            const int mn = dg_al_scan_min(P[0] < P[1] ? P[0] : P[1]);
             const int best = __builtin_amdgcn_readlane(mn, 63);
             if (best >= DG_AL_LIM) { lost = true; return; }
             const unsigned long long b0 = __ballot(P[0] == best), b1 = __ballot(P[1] == best);
@@ -444,13 +443,7 @@ __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
             const int x = best - DG_AL_DEL * (kb + c);
             lm = x < lm ? x : lm;
         }
-        int incl = lm, v;
-        v = dg_al_dpp<DG_DPP_ROW_SHR(1), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
-        v = dg_al_dpp<DG_DPP_ROW_SHR(2), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
-        v = dg_al_dpp<DG_DPP_ROW_SHR(4), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
-        v = dg_al_dpp<DG_DPP_ROW_SHR(8), 0xf>(0x7fffffff, incl); incl = v < incl ? v : incl;
-        v = dg_al_dpp<DG_DPP_BCAST15, 0xa>(0x7fffffff, incl); incl = v < incl ? v : incl;
-        v = dg_al_dpp<DG_DPP_BCAST31, 0xc>(0x7fffffff, incl); incl = v < incl ? v : incl;
+        const int incl = dg_al_scan_min(lm);
         int pm = dg_al_dpp<DG_DPP_WAVE_SHR1, 0xf>(0x7fffffff, incl);
         uint32_t word = 0;
 #pragma unroll

@@ -19,11 +19,6 @@
 #include "dagcon_dev.h"
 #include "k_build.hip.h"
 #include "k_merge.hip.h"
-#ifdef DG_EXPERIMENTS
-#include "experiments/k_align2.hip.h"        // the following band with two pairs per wave: exact, 86 ms against 60
-#include "experiments/k_emit2.hip.h"         // addAln with a thread per column: exact, and 15.6 ms of build against 12.4
-#include "experiments/k_merge_tile.hip.h"     // dropped experiments: `make experiments` only, never in the shipped library
-#endif
 #include "k_merge_q.hip.h"
 #include "k_bestpath.hip.h"
 #include "k_align.hip.h"
@@ -98,18 +93,10 @@ struct Ctx {
 
     // host copy of the filtered batch
     uint32_t T = 0, A = 0;
-    int emit2 = 0;                                 // addAln with a thread per column (k_emit2.hip.h; DAGCON_EMIT2)
-    uint32_t max_len = 0, bs_stride = 0;
-    DevBuf d_matK, d_bbstart;
     int bp_lane = 1, bl_stk = -1;                  // full-span bestPath: a row of eight lanes per piece (k_bp_sweep_l; DAGCON_BP_LANE=0: a wave per piece, k_bp_sweep; 2: rows whatever the batch size); DAGCON_BP_LANE_STACK: test knob
-    int bp_fused = 1;                              // partial-span bestPath: one (A, B) sweep + vertex-parallel kernels (DAGCON_BP_FUSED=0: three sweeps)
     uint32_t align_dropped = 0;                    // records of the last dagcon_align / dagcon_consensus_pre the band could not align
-    int emit_scan = 1;                             // k_emit takes the prefix over the reads itself (DAGCON_EMIT_SCAN=0: k_groups, as for deeper targets)
-    int nf2 = 1;                                   // k_norm_finish2 (a wave per chunk) instead of k_norm_finish (DAGCON_NF2=0)
     int poison = 0;                                // DAGCON_POISON (tests): arenas nobody clears are filled with 0xEE bytes before every run (bits 1, 2, 4); 8: every buffer the kernels fill
-    int align2 = 0;                                // (make experiments) k_align_adapt2: two pairs per wave, DAGCON_ALIGN2=1
     int fold = 1;                                  // duplicate insertion chains folded by k_emit (DAGCON_FOLD=0: never)
-    int list_q = 0;                                // (make experiments) partial-span worklist by rows, k_merge_list_q: DAGCON_MERGE_LIST_Q=1
     int merge_q = 1, use_q = 0;                    // k_merge_q: eight segments per wave (DAGCON_MERGE_Q=0: never); this batch
     uint32_t max_k = 0, max_tlen = 0;
     uint64_t sum_len = 0, sum_bb = 0, mat_cells = 0, blob_bytes = 0;
@@ -136,7 +123,7 @@ struct Ctx {
     DevBuf d_node_base, d_n_nodes, d_pool_base, d_pool_size, d_pool_top, d_t_nins;
     DevBuf d_matA, d_matD, d_matC, d_cov, d_gcount, d_gbase, d_bid;
     DevBuf d_nodes, d_best, d_queue, d_score, d_cns_tmp, d_bp_tt, d_score_b;
-    DevBuf d_pool, d_stk, d_cuts, d_cuts_bp, d_bp_stat, d_bp_len, d_nextcut, d_tile_list, d_rd, d_pro_state, d_sh_cnt, d_seg_done, d_wl_first, d_queue0, d_bp_end, d_bp_ab, d_defer, d_cns_tmp0;
+    DevBuf d_pool, d_stk, d_cuts, d_cuts_bp, d_bp_stat, d_bp_len, d_worklist, d_rd, d_pro_state, d_sh_cnt, d_seg_done, d_wl_first, d_queue0, d_bp_end, d_bp_ab, d_defer, d_cns_tmp0;
     DevBuf d_al[14];                                // dagcon_align: blobs, offsets, outputs, directions, launch order, widths
     DevBuf d_pn[18];                                // dagcon_align_panels: blobs, panels, scratch, outputs, launch order
     DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
@@ -146,9 +133,7 @@ struct Ctx {
     uint32_t sh_log = 16;                           // slots per segment behind enter's / exit's list (x2 on DG_E_LOG_OVF)
     bool full_span = false;                         // (nearly) every alignment of the batch covers its whole target
     uint32_t gcuts = 1;                             // partial-span cuts: prologue + worklist + epilogue (DAGCON_GCUTS=0: off)
-    uint32_t tile_pos = 0, tile_words = 0, tile_ny = 0, tile_list_cap = 0, list_grid = 8192;   // LDS tiles (tile_pos 0: off)
-    double ins_per_pos = -1.0;                      // inserted vertices per backbone position, from the last run
-    uint64_t expected_workers = 0;                  // merge workers the batch will probably run (prefetch on / off)
+    uint32_t worklist_cap = 0, list_grid = 8192;    // partial-span worklist: entries, and the waves of k_merge_list
 
     DgStatus h_st;
     dagcon_timings tm;
@@ -230,17 +215,16 @@ int ensure_arenas(Ctx *c) {
     ENSURE(c, c->d_queue, c->node_cap * 4);
     ENSURE(c, c->d_score, c->node_cap * 8);
     ENSURE(c, c->d_bp_tt, c->node_cap * 4);
-    if (c->gcuts && c->bp_fused) ENSURE(c, c->d_score_b, c->node_cap * 4);
+    if (c->gcuts) ENSURE(c, c->d_score_b, c->node_cap * 4);
     ENSURE(c, c->d_cns_tmp, c->node_cap);
     ENSURE(c, c->d_pool, c->pool_cap * 4);
-    ENSURE(c, c->d_stk, std::max<uint64_t>((uint64_t)c->T * std::max(c->bp_max, c->seg_max), (c->tile_pos || c->gcuts) ? c->list_grid : 0) * c->stk_words * 4);
-    if (c->tile_pos) ENSURE(c, c->d_nextcut, c->sum_bb * 4);
-    if (c->tile_pos || c->gcuts) ENSURE(c, c->d_tile_list, (4ull + 3ull * c->tile_list_cap) * 4);
+    ENSURE(c, c->d_stk, std::max<uint64_t>((uint64_t)c->T * std::max(c->bp_max, c->seg_max), c->gcuts ? c->list_grid : 0) * c->stk_words * 4);
     if (c->gcuts) {
+        ENSURE(c, c->d_worklist, (4ull + 3ull * c->worklist_cap) * 4);
         ENSURE(c, c->d_rd, (uint64_t)c->A * 16 + 16);
         ENSURE(c, c->d_pro_state, (uint64_t)c->T * 16 + 16);
         ENSURE(c, c->d_sh_cnt, (uint64_t)c->T * (2 + 2 * DG_SH_MAX) * 4 + 16);
-        ENSURE(c, c->d_seg_done, (uint64_t)c->tile_list_cap * (DG_SH_MAX + 1) * 4 + 16);
+        ENSURE(c, c->d_seg_done, (uint64_t)c->worklist_cap * (DG_SH_MAX + 1) * 4 + 16);
         ENSURE(c, c->d_wl_first, (uint64_t)c->T * 4 + 16);
         ENSURE(c, c->d_queue0, c->node_cap * 4);
         ENSURE(c, c->d_bp_end, (uint64_t)c->T * c->bp_max * 4 + 16);
@@ -303,19 +287,11 @@ void fill_params(Ctx *c, DgParams &p) {
     p.cns_tmp = (uint8_t *)c->d_cns_tmp.p; p.node_cap = c->node_cap;
     p.pool = (uint32_t *)c->d_pool.p; p.pool_cap = c->pool_cap;
     p.stk = (int32_t *)c->d_stk.p; p.stk_words = c->stk_words; p.growth_pct = c->growth_pct;
-    // the prefetch wave pays while the chip has idle wave slots; past ~1.5 workers per SIMD the
-    // workers hide each other's latency and it only takes issue slots from them
-#ifdef DG_EXPERIMENTS
-    { const char *e = getenv("DAGCON_PF_AHEAD"); p.pf_ahead = e ? (uint32_t)atoi(e) : (c->expected_workers >= 4096 ? 0u : 48u); }
-#else
-    p.pf_ahead = 0;
-#endif
-    p.emit2 = c->emit2 ? 1u : 0u; p.matK = (uint8_t *)c->d_matK.p; p.bbstart = (uint32_t *)c->d_bbstart.p; p.bs_stride = c->bs_stride;
-    p.bp_fused = c->bp_fused ? 1u : 0u; p.score_b = (float *)c->d_score_b.p;
+    p.score_b = (float *)c->d_score_b.p;
     // (rows pay where there are pieces enough to fill the chip with them, eight to a wave: 64 targets x 50 kb x 60x, 16,384
     // pieces: 2.9 ms by rows against 2.3 by waves; configs[1], 147,000 pieces: 3.8 against 4.7.  DAGCON_BP_LANE=2: always)
     p.bp_lane = c->bp_lane >= 2 || (c->bp_lane && (uint64_t)c->T * c->bp_max >= 32768ull) ? 1u : 0u; p.bl_stk = c->bl_stk >= 0 && c->bl_stk < DG_BL_STK ? (uint32_t)c->bl_stk : (uint32_t)DG_BL_STK;
-    p.emit_scan = (c->emit_scan && c->max_k <= 64u && !c->emit2) ? 1u : 0u;
+    p.emit_scan = c->max_k <= 64u ? 1u : 0u;
     p.fold = (c->fold && !(c->opts.flags & DAGCON_FLAG_STOP_AFTER_BUILD)) ? 1u : 0u;
     p.q_kmax = c->use_q && !c->opts.max_segments && !c->seg_env && c->max_k > DQ_KMAX ? DQ_KMAX : 0u;
     p.bp_seg_min = (c->seg_min + 2u) / 3u;
@@ -326,8 +302,7 @@ void fill_params(Ctx *c, DgParams &p) {
     p.queue0 = (int32_t *)c->d_queue0.p; p.bp_end = (uint32_t *)c->d_bp_end.p; p.bp_ab = (float *)c->d_bp_ab.p;
     p.defer = (uint32_t *)c->d_defer.p; p.cns_tmp0 = (uint8_t *)c->d_cns_tmp0.p;
     p.seg_done = (uint32_t *)c->d_seg_done.p; p.wl_first = (uint32_t *)c->d_wl_first.p;
-    p.nextcut = (uint32_t *)c->d_nextcut.p; p.tile_pos = c->tile_pos; p.tile_words = c->tile_words;
-    p.tile_list = (uint32_t *)c->d_tile_list.p; p.tile_list_cap = c->tile_list_cap;
+    p.worklist = (uint32_t *)c->d_worklist.p; p.worklist_cap = c->worklist_cap;
     p.cns = (uint8_t *)c->d_cns.p; p.cns_cap = c->cns_cap;
     p.cns_off = (uint64_t *)c->d_cns_off.p; p.cns_len = (uint32_t *)c->d_cns_len.p;
     p.seg_first = (uint64_t *)c->d_seg_first.p; p.n_seg = (uint32_t *)c->d_n_seg.p;
@@ -344,8 +319,7 @@ void launch_normalize(Ctx *c, const DgParams &p) {
     hipLaunchKernelGGL((k_norm_chunk<DG_NW, 64, false>), dim3((c->n_chunks + 63) / 64), dim3(64), 0, s, p);
     hipLaunchKernelGGL((k_norm_chunk<DG_NW_BIG, 32, true>), dim3((c->n_chunks + 31) / 32), dim3(32), 0, s, p);
     hipLaunchKernelGGL(k_norm_scan, dim3((c->A + 63) / 64), dim3(64), 0, s, p);
-    if (c->nf2) hipLaunchKernelGGL(k_norm_finish2, dim3((c->n_chunks + 3) / 4), dim3(256), 0, s, p);    // a wave per chunk
-    else hipLaunchKernelGGL(k_norm_finish, dim3((c->n_chunks + 63) / 64), dim3(64), 0, s, p);          // a lane per chunk (DAGCON_NF2=0)
+    hipLaunchKernelGGL(k_norm_finish2, dim3((c->n_chunks + 3) / 4), dim3(256), 0, s, p);    // a wave per chunk
     hipLaunchKernelGGL(k_normalize_slow, dim3((c->A + 63) / 64), dim3(64), 0, s, p);
 }
 
@@ -362,9 +336,9 @@ int launch_all(Ctx *c) {
                           &c->d_ch_tb, &c->d_ch_flag, &c->d_ch_src, &c->d_ch_out, &c->d_ch_adv, &c->d_n_lb, &c->d_norm_tmp, &c->d_ckpt,
                           &c->d_node_base, &c->d_n_nodes, &c->d_pool_base, &c->d_pool_size, &c->d_pool_top, &c->d_t_nins, &c->d_cov, &c->d_gcount,
                           &c->d_gbase, &c->d_bid, &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_stk, &c->d_cuts,
-                          &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_nextcut, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_wl_first,
+                          &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_wl_first,
                           &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns, &c->d_cns_off, &c->d_seg_first,
-                          &c->d_seg_r0, &c->d_seg_r1, &c->d_tile_list, &c->d_seg_done};
+                          &c->d_seg_r0, &c->d_seg_r1, &c->d_worklist, &c->d_seg_done};
         for (DevBuf *b : work)
             if (b->p && b->cap) HIPCHK(c, hipMemsetAsync(b->p, 0xEE, b->cap, s));
     }
@@ -392,13 +366,6 @@ int launch_all(Ctx *c) {
         if (p.emit_scan) hipLaunchKernelGGL(k_gsum, dim3(c->T, (c->max_tlen + 2 + 255) / 256), dim3(256), 0, s, p);
         else hipLaunchKernelGGL(k_groups, dim3(c->T, (c->max_tlen + 2 + 31) / 32), dim3(256), 0, s, p);
         hipLaunchKernelGGL(k_gscan, dim3(c->T), dim3(1024), 0, s, p);
-#ifdef DG_EXPERIMENTS
-        if (c->A > 0 && c->emit2) {
-            hipLaunchKernelGGL(k_blockscan, dim3(c->A), dim3(64), 0, s, p);
-            hipLaunchKernelGGL(k_emit2, dim3((c->bs_stride + 3u) / 4u, c->A), dim3(256), 0, s, p);
-            if (p.fold) hipLaunchKernelGGL(k_dedupe, dim3(c->T, rows4), dim3(256), 0, s, p);
-        } else
-#endif
         if (c->A > 0)
             hipLaunchKernelGGL(k_emit, dim3(c->T, (c->max_k + DG_ERPW - 1) / DG_ERPW, ((c->max_tlen + 2) >> c->emit_shift) + 1),
                                dim3(64), 0, s, p);
@@ -409,58 +376,37 @@ int launch_all(Ctx *c) {
     }
     HIPCHK(c, hipEventRecord(c->ev[2], s));
     if (c->T > 0 && !(c->opts.flags & DAGCON_FLAG_STOP_AFTER_BUILD)) {
-        if (!c->gcuts || c->tile_pos) hipLaunchKernelGGL(k_cuts, dim3(c->T), dim3(64), 0, s, p);      // (k_cuts2 makes its own, bestPath's too)
-        if (c->gcuts && !c->tile_pos) {
-            // partial-span cuts: enter and what hangs on it first, then the segments as a worklist, exit last
-            HIPCHK(c, hipMemsetAsync(c->d_tile_list.p, 0, 16, s));
-            HIPCHK(c, hipMemsetAsync(c->d_seg_done.p, 0, (size_t)c->tile_list_cap * (DG_SH_MAX + 1) * 4, s));
+        if (c->gcuts) {
+            // partial-span cuts (k_cuts2 makes its own, bestPath's too): enter and what hangs on it first, then the
+            // segments as a worklist, exit last
+            HIPCHK(c, hipMemsetAsync(c->d_worklist.p, 0, 16, s));
+            HIPCHK(c, hipMemsetAsync(c->d_seg_done.p, 0, (size_t)c->worklist_cap * (DG_SH_MAX + 1) * 4, s));
             hipLaunchKernelGGL(k_merge_pro, dim3(c->T), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_cuts2, dim3(c->T), dim3(64), 0, s, p);
-            // the worklist, a wave per entry (make experiments: eight entries per wave, one per row of eight lanes, k_merge_list_q)
-#ifdef DG_EXPERIMENTS
-            if (c->merge_q && c->list_q && c->max_k <= DQ_KMAX && (uint64_t)c->T * c->seg_max >= DQ_ROWS) {
-                const uint64_t grid = std::min<uint64_t>(1024ull * DQ_WAVES, (uint64_t)c->T * c->seg_max / DQ_ROWS);
-                hipLaunchKernelGGL(k_merge_list_q, dim3((uint32_t)grid), dim3(64), 0, s, p);
-            } else
-#endif
+            // the worklist, a wave per entry
             hipLaunchKernelGGL(k_merge_list, dim3(c->list_grid), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_merge_fin, dim3(c->T), dim3(64), 0, s, p);
+        } else {
+            hipLaunchKernelGGL(k_cuts, dim3(c->T), dim3(64), 0, s, p);
+            if (c->use_q) {
+                hipLaunchKernelGGL(k_merge_q, dim3((c->T * c->seg_max + DQ_ROWS - 1u) / DQ_ROWS), dim3(64), 0, s, p);
+                // (the few deep targets of a shallow batch: the same cuts, a wave per segment)
+                if (p.q_kmax) hipLaunchKernelGGL(k_merge, dim3(c->T * c->seg_max), dim3(64), 0, s, p);
+            } else hipLaunchKernelGGL(k_merge, dim3(c->T * c->seg_max), dim3(64), 0, s, p);
         }
-#ifdef DG_EXPERIMENTS
-        else if (c->tile_pos) {
-            HIPCHK(c, hipMemsetAsync(c->d_tile_list.p, 0, 16, s));
-            HIPCHK(c, hipFuncSetAttribute((const void *)k_merge_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(c->tile_words * 4)));
-            hipLaunchKernelGGL(k_cutmap, dim3(c->T), dim3(1024), 0, s, p);
-            hipLaunchKernelGGL(k_merge_tile, dim3(c->T, c->tile_ny), dim3(DG_T_LANES), c->tile_words * 4, s, p);
-            hipLaunchKernelGGL(k_merge_list, dim3(c->list_grid), dim3(64), 0, s, p);
-        } else if (p.pf_ahead) hipLaunchKernelGGL(k_merge<true>, dim3(c->T * c->seg_max), dim3(128), 0, s, p);
-#endif
-        else if (c->use_q) {
-            hipLaunchKernelGGL(k_merge_q, dim3((c->T * c->seg_max + DQ_ROWS - 1u) / DQ_ROWS), dim3(64), 0, s, p);
-            // (the few deep targets of a shallow batch: the same cuts, a wave per segment)
-            if (p.q_kmax) hipLaunchKernelGGL(k_merge<false>, dim3(c->T * c->seg_max), dim3(64), 0, s, p);
-        }
-        else hipLaunchKernelGGL(k_merge<false>, dim3(c->T * c->seg_max), dim3(64), 0, s, p);
     }
     HIPCHK(c, hipEventRecord(c->ev[3], s));
     if (c->T > 0 && !(c->opts.flags & (DAGCON_FLAG_STOP_AFTER_BUILD | DAGCON_FLAG_STOP_AFTER_MERGE))) {
         hipLaunchKernelGGL(k_bp_terms, dim3(c->T, 16), dim3(256), 0, s, p);
-        if (c->gcuts && !c->tile_pos) {
-            // partial-span pileups: the pieces of k_cuts2, three sweeps (A, B, absolute), see dg_bp_sweep
+        if (c->gcuts) {
+            // partial-span pileups, on the pieces of k_cuts2: one sweep for (A, B), then vertex-parallel kernels for the
+            // absolute scores and the choices; k_bp_sweep_abs_g sweeps whole the targets the pieces do not take
             hipLaunchKernelGGL(k_bp_xtree, dim3(c->T), dim3(64), 0, s, p);
-            if (p.bp_fused) {
-                // one sweep for (A, B), then vertex-parallel kernels for the absolute scores and the choices
-                hipLaunchKernelGGL(k_bp_sweep_ab, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
-                hipLaunchKernelGGL(k_bp_comb, dim3(c->T), dim3(64), 0, s, p);
-                hipLaunchKernelGGL(k_bp_abs, dim3(c->T * c->bp_max), dim3(256), 0, s, p);
-                hipLaunchKernelGGL(k_bp_choose, dim3(c->T * c->bp_max), dim3(256), 0, s, p);
-            } else {
-                hipLaunchKernelGGL(k_bp_sweep_g<0>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
-                hipLaunchKernelGGL(k_bp_reset_def, dim3(c->T), dim3(64), 0, s, p);
-                hipLaunchKernelGGL(k_bp_sweep_g<1>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
-                hipLaunchKernelGGL(k_bp_comb, dim3(c->T), dim3(64), 0, s, p);
-            }
-            hipLaunchKernelGGL(k_bp_sweep_g<2>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);     // (fused: whole-target sweeps only)
+            hipLaunchKernelGGL(k_bp_sweep_ab, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
+            hipLaunchKernelGGL(k_bp_comb, dim3(c->T), dim3(64), 0, s, p);
+            hipLaunchKernelGGL(k_bp_abs, dim3(c->T * c->bp_max), dim3(256), 0, s, p);
+            hipLaunchKernelGGL(k_bp_choose, dim3(c->T * c->bp_max), dim3(256), 0, s, p);
+            hipLaunchKernelGGL(k_bp_sweep_abs_g, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_bp_defer, dim3(c->T), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_bp_walk_g, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
         } else {
@@ -518,17 +464,9 @@ int dagcon_create(const dagcon_opts *opts, dagcon_ctx **out) {
         if (v >= 1 && v <= 64) c->seg_env = (uint32_t)v;
     }
     if (const char *e = getenv("DAGCON_FOLD")) c->fold = atoi(e) != 0;
-    if (const char *e = getenv("DAGCON_ALIGN2")) c->align2 = atoi(e) != 0;
     if (const char *e = getenv("DAGCON_POISON")) c->poison = atoi(e);
-    if (const char *e = getenv("DAGCON_NF2")) c->nf2 = atoi(e) != 0;
-    if (const char *e = getenv("DAGCON_EMIT_SCAN")) c->emit_scan = atoi(e) != 0;
-    if (const char *e = getenv("DAGCON_BP_FUSED")) c->bp_fused = atoi(e) != 0;
     if (const char *e = getenv("DAGCON_BP_LANE")) c->bp_lane = atoi(e);
     if (const char *e = getenv("DAGCON_BP_LANE_STACK")) c->bl_stk = atoi(e);
-#ifdef DG_EXPERIMENTS
-    if (const char *e = getenv("DAGCON_EMIT2")) c->emit2 = atoi(e) != 0;
-#endif
-    if (const char *e = getenv("DAGCON_MERGE_LIST_Q")) c->list_q = atoi(e) != 0;
     if (const char *e = getenv("DAGCON_MERGE_Q")) c->merge_q = atoi(e) != 0;     // eight segments per wave (k_merge_q.hip.h)
     memset(&c->tm, 0, sizeof c->tm);
     memset(&c->h_st, 0, sizeof c->h_st);
@@ -555,7 +493,7 @@ void dagcon_destroy(dagcon_ctx *ctx) {
                      &c->d_n_ins, &c->d_n_del, &c->d_norm, &c->d_node_base, &c->d_n_nodes,
                      &c->d_pool_base, &c->d_pool_size, &c->d_pool_top, &c->d_t_nins, &c->d_matA, &c->d_matD,
                      &c->d_matC, &c->d_cov, &c->d_gcount, &c->d_gbase, &c->d_bid, &c->d_nodes,
-                     &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_score_b, &c->d_matK, &c->d_bbstart, &c->d_pool, &c->d_stk, &c->d_cuts, &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_nextcut, &c->d_tile_list, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_seg_done, &c->d_wl_first, &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns,
+                     &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_score_b, &c->d_pool, &c->d_stk, &c->d_cuts, &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_worklist, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_seg_done, &c->d_wl_first, &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns,
                      &c->d_cns_off, &c->d_cns_len, &c->d_seg_first, &c->d_n_seg, &c->d_seg_r0, &c->d_seg_r1,
                      &c->d_st};
     for (DevBuf *b : all) free_buf(*b);
@@ -588,7 +526,6 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->h_bbv_base.assign(T, 0);
     c->h_bb_off.assign(T, 0);
     c->h_aln_len.clear(); c->h_aln_start.clear(); c->h_aln_tgt.clear(); c->h_aln_off.clear();
-    c->max_len = 0;
     c->max_k = 0; c->max_tlen = 0; c->sum_len = 0; c->sum_bb = 0; c->mat_cells = 0;
     c->have_bb = b->backbone != nullptr;
     uint64_t bb_bytes = 0, n_whole = 0;
@@ -613,7 +550,6 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
             c->h_aln_off.push_back(b->aln_off[a]);
             c->h_aln_tgt.push_back(t);
             c->sum_len += len;
-            c->max_len = std::max(c->max_len, len);
             // (a read that spans the target begins at its first base and has a column per target base; necessary, not
             // sufficient -- a read that ends early and inserts a lot passes too: the batch is then exact all the same, with
             // fewer cuts than it could have)
@@ -663,38 +599,11 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
         const uint32_t base = std::max(256u, fit);
         if (c->stk_words < base || (uint64_t)c->stk_words * pieces > (1024ull << 20)) c->stk_words = base;
     }
-    if (c->gcuts) c->tile_list_cap = std::max<uint32_t>(c->tile_list_cap, (uint32_t)std::min<uint64_t>((uint64_t)T * c->seg_max + 64, 0x0FFFFFFFull));
-#ifdef DG_EXPERIMENTS
-    // LDS tiles for mergeNodes: positions per tile from the LDS budget and the expected size of a
-    // position's share of the graph (exact after the first run of a shape)
-    {
-        // (opt-in: exact, but at configs[1] the lanes' dependent LDS chains at two waves per CU take 128 ms
-        // where the wave-per-segment kernel takes 22: DESIGN.md, "tried and dropped")
-        int on = 0;
-        if (const char *e = getenv("DAGCON_TILES")) on = atoi(e);
-        uint32_t kb = 80;
-        if (const char *e = getenv("DAGCON_TILE_KB")) { const int v = atoi(e); if (v >= 16 && v <= 160) kb = (uint32_t)v; }
-        c->tile_pos = 0;
-        if (on && T && c->max_k >= 1 && c->seg_max != 1) {
-            c->tile_words = kb * 256u;
-            const double ipp = c->ins_per_pos >= 0 ? c->ins_per_pos : (double)c->sum_len / 10.0 / (double)std::max<uint64_t>(c->sum_bb, 1);
-            const double wpp = 9.5 * (1.0 + ipp) + 3.0 * ipp + 3.0 * dg_capb(c->max_k);
-            const double room = ((double)c->tile_words - 1200.0) * 0.9;
-            uint32_t G = (uint32_t)std::max(8.0, room / wpp);
-            if (const char *e = getenv("DAGCON_TILE_POS")) { const int v = atoi(e); if (v >= 2) G = (uint32_t)v; }
-            c->tile_pos = G;
-            c->tile_ny = (c->max_tlen + 2 + G - 1) / G;
-            c->tile_list_cap = std::max<uint32_t>(c->tile_list_cap, (uint32_t)std::min<uint64_t>((uint64_t)T * c->tile_ny + 16, 0x0FFFFFFFull));
-        }
-    }
-#endif
+    if (c->gcuts) c->worklist_cap = std::max<uint32_t>(c->worklist_cap, (uint32_t)std::min<uint64_t>((uint64_t)T * c->seg_max + 64, 0x0FFFFFFFull));
     c->h_aln_begin[T] = c->h_aln_len.size();
     if (c->h_aln_len.size() > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many alignments");
     c->A = (uint32_t)c->h_aln_len.size();
     c->blob_bytes = b->blob_bytes;
-    // cut vertices need every read to span them: with full-span reads a target is swept in seg_max
-    // pieces, with partial spans in a few
-    c->expected_workers = c->full_span ? (uint64_t)T * c->seg_max : (uint64_t)T * 3;
     // windows of DG_NCH input columns: the units of the chunked normalizeGaps
     c->h_ch_base.assign((size_t)c->A + 1, 0);
     c->h_ch_aln.clear();
@@ -768,13 +677,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     ENSURE(c, c->d_node_base, (size_t)T * 8); ENSURE(c, c->d_n_nodes, T4);
     ENSURE(c, c->d_pool_base, (size_t)T * 8); ENSURE(c, c->d_pool_size, T4); ENSURE(c, c->d_pool_top, T4);
     ENSURE(c, c->d_t_nins, T4); ENSURE(c, c->d_tfail, T4 + 4);
-    if (c->emit2) {
-        // cells as [read][position] rows (k_emit2.hip.h); the chains' keys; backbone position per 64-column block
-        ENSURE(c, c->d_matA, c->matc_cells * 4 + 256); ENSURE(c, c->d_matD, c->matc_cells * 4 + 256);
-        ENSURE(c, c->d_matK, c->matc_cells + 256);
-        c->bs_stride = (uint32_t)((2ull * c->max_len + 63ull) / 64ull + 1ull);
-        ENSURE(c, c->d_bbstart, (uint64_t)std::max<uint32_t>(c->A, 1u) * c->bs_stride * 4);
-    } else { ENSURE(c, c->d_matA, c->mat_cells * 4); ENSURE(c, c->d_matD, c->mat_cells * 4); }
+    ENSURE(c, c->d_matA, c->mat_cells * 4); ENSURE(c, c->d_matD, c->mat_cells * 4);
     ENSURE(c, c->d_matC, c->matc_cells * 4 + 256);
     ENSURE(c, c->d_cov, c->sum_bb * 4); ENSURE(c, c->d_gcount, c->sum_bb * 4);
     ENSURE(c, c->d_gbase, c->sum_bb * 4); ENSURE(c, c->d_bid, c->sum_bb * 4);
@@ -831,11 +734,11 @@ int dagcon_run(dagcon_ctx *ctx) {
                 // (partial-span batches: the merge's worklist -- (target, first vertex, last vertex) triples -- behind it)
                 uint32_t nl = 0;
                 std::vector<uint32_t> wl;
-                if (c->gcuts && c->d_tile_list.p) {
-                    (void)hipMemcpy(&nl, c->d_tile_list.p, 4, hipMemcpyDeviceToHost);
-                    if (nl > c->tile_list_cap) nl = c->tile_list_cap;
+                if (c->gcuts && c->d_worklist.p) {
+                    (void)hipMemcpy(&nl, c->d_worklist.p, 4, hipMemcpyDeviceToHost);
+                    if (nl > c->worklist_cap) nl = c->worklist_cap;
                     wl.resize(3 * (size_t)nl);
-                    if (nl) (void)hipMemcpy(wl.data(), (uint32_t *)c->d_tile_list.p + 4, wl.size() * 4, hipMemcpyDeviceToHost);
+                    if (nl) (void)hipMemcpy(wl.data(), (uint32_t *)c->d_worklist.p + 4, wl.size() * 4, hipMemcpyDeviceToHost);
                 }
                 fwrite(&nl, 4, 1, f);
                 if (nl) fwrite(wl.data(), 4, wl.size(), f);
@@ -885,7 +788,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         if (f & DG_E_POOL_OVF) c->pool_cap = c->h_st.pool_need + 1024;
         if (f & DG_E_POOL_TGT) c->growth_pct *= 3;
         if (f & DG_E_STACK) c->stk_words *= 4;
-        if (f & DG_E_LIST_OVF) c->tile_list_cap *= 4;
+        if (f & DG_E_LIST_OVF) c->worklist_cap *= 4;
         if (f & DG_E_LOG_OVF) c->sh_log *= 2;
         if (f & DG_E_OUT_OVF) {
             c->cns_cap = std::max<uint64_t>(c->cns_cap, c->h_st.cns_top + 1024);
@@ -966,7 +869,6 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     c->tm.n_columns = c->h_st.n_columns;
     c->tm.n_nodes = c->h_st.node_need;
     c->tm.merge_segments = c->h_st.n_mseg;
-    if (c->sum_bb && c->h_st.node_need >= c->sum_bb) c->ins_per_pos = (double)(c->h_st.node_need - c->sum_bb) / (double)c->sum_bb;
     res->n_targets = T;
     res->n_segments = c->r_range0.size();
     res->seg_begin = c->r_seg_begin.data();
@@ -1191,10 +1093,6 @@ static int align_device(Ctx *c, uint32_t n, const uint64_t *q_off, const uint32_
             HIPCHK(c, hipMemcpyAsync(ddo.p, dir_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
             HIPCHK(c, hipMemcpyAsync((uint32_t *)didx.p + first, ad.data() + first, cnt * 4, hipMemcpyHostToDevice, s));
             ap.idx = (const uint32_t *)didx.p + first; ap.n = (uint32_t)cnt; ap.first_pass = 1u;
-#ifdef DG_EXPERIMENTS
-            if (c->align2) hipLaunchKernelGGL(k_align_adapt2, dim3((uint32_t)((cnt + 1) / 2)), dim3(64), 0, s, ap);      // two pairs per wave
-            else
-#endif
             hipLaunchKernelGGL(k_align_adapt, dim3((uint32_t)cnt), dim3(64), 0, s, ap);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(s));

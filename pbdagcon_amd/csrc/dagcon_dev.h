@@ -36,7 +36,7 @@
 #define DG_E_OUT_OVF     0x100u  // output arena too small
 #define DG_E_TOO_BIG     0x200u  // a target has more than 2^25-2 vertices
 #define DG_E_LOG_OVF     0x800u  // a segment appended more entries to enter's / exit's list than its slots hold (rerun with more)
-#define DG_E_LIST_OVF    0x400u  // more tiles handed to k_merge_list than its list holds (rerun with a longer one)
+#define DG_E_LIST_OVF    0x400u  // more segments handed to k_merge_list than its worklist holds (rerun with a longer one)
 
 // failures of one target (its input, or an invariant of its graph): recorded in DgParams::tfail,
 // the batch goes on; everything else is a capacity problem of the whole batch (grow and re-run)
@@ -146,10 +146,6 @@ struct DgParams {
     int32_t *cov;                  // coverage (AlnGraphBoost.cpp:76,87)
     // ---- matrices [position][read] ----
     uint32_t *matA, *matD;         // arrival / departure
-    uint8_t *matK;                 // (p.emit2) [read][position], a byte: key of the short insertion chain a match column closes (k_dedupe)
-    uint32_t *bbstart;             // (p.emit2) [A][bs_stride]: backbone position at the start of every 64-column block (k_blockscan)
-    uint32_t bs_stride;
-    uint32_t emit2;                // 1: addAln with a thread per column (k_emit2.hip.h): matA / matD are [read][position] like matC
     uint32_t *matC;                // [read][position] (row stride matc_stride): insertion run length in front of
                                    // the position, then its exclusive prefix over reads
     const uint64_t *matc_base;     // [T] offset of the target's K rows
@@ -159,8 +155,7 @@ struct DgParams {
     int32_t *best, *queue;
     float2 *score;                 // (best-path score, 1 = final)
     float *bp_tt;                  // per vertex: what an edge into it subtracts (k_bp_terms)
-    float *score_b;                // per vertex (p.gcuts, p.bp_fused): B, best path to exit that does not pass the piece's upper cut
-    uint32_t bp_fused;             // 1: partial-span bestPath as one (A, B) sweep + vertex-parallel kernels (k_bp_sweep_ab)
+    float *score_b;                // per vertex (p.gcuts): B, best path to exit that does not pass the piece's upper cut
     uint32_t bp_seg_min;           // k_cuts2: shortest bestPath piece, in backbone positions (see fill_params)
     uint32_t bp_lane;              // 1: full-span bestPath with a lane per piece (k_bp_sweep_l); k_bp_sweep then takes the pieces it gave up
     uint32_t bl_stk;               // k_bp_sweep_l: entries of a lane's evaluation stack (<= DG_BL_STK; a test knob below that)
@@ -171,7 +166,6 @@ struct DgParams {
     int32_t *stk;                  // per-target scratch, stk_words each
     uint32_t stk_words;
     uint32_t growth_pct;           // pool growth region as % of the initial adjacency words
-    uint32_t pf_ahead;             // vertices the prefetch wave runs ahead of the sweep (0 = off)
     uint32_t emit_scan;            // 1 (every target has at most 64 reads): matC keeps the insertion run lengths, k_gsum adds them up
                                    // per position (gcount) and k_emit takes the prefix over the reads itself (DPP): no k_groups
     uint32_t fold;                 // 1: k_emit folds duplicate insertion chains as it builds (dg_emit_fold); 0 with
@@ -196,15 +190,11 @@ struct DgParams {
                                    // the prologue visits beyond that segment: a stretch of `queue` would be too short)
     uint32_t *pro_state;           // [T][4]: queue head, queue tail of the prologue, vertices it visited, 1 = no cuts allowed
     uint32_t *sh_cnt;              // [T][2 + 2 * DG_SH_MAX]: shared out-lists n, entries of in[exit], then n x (vertex, entries of its out-list)
-    uint32_t *seg_done;            // [tile_list_cap][DG_SH_MAX + 1]: slots of its stretches a worklist entry has used (last: in[exit])
+    uint32_t *seg_done;            // [worklist_cap][DG_SH_MAX + 1]: slots of its stretches a worklist entry has used (last: in[exit])
     uint32_t sh_log;               // slots a segment has behind either shared list
+    uint32_t *worklist;            // [0] entries (k_cuts2), [2] ticket cursor (k_merge_list), then (target, first, last) triples
+    uint32_t worklist_cap;
     uint32_t *wl_first;            // [T]: worklist index of the target's first segment
-    // ---- LDS tiles (k_cutmap, k_merge_tile, k_merge_list) ----
-    uint32_t *nextcut;             // [bbv_base + p]: smallest cut position >= p (k_cutmap)
-    uint32_t tile_pos;             // backbone positions per tile (0: tiles are not used)
-    uint32_t tile_words;           // LDS words of a tile's image
-    uint32_t *tile_list;           // [0] entries, [1] tiles that gave up, then (target, first, last) triples
-    uint32_t tile_list_cap;
     // ---- outputs ----
     uint8_t *cns;
     uint64_t cns_cap;

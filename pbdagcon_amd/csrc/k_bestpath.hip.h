@@ -992,28 +992,18 @@ __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
 
 // ====================================================================================
 // bestPath on the pieces of k_cuts2 (partial-span pileups, p.gcuts): see dg_bp_sweep.
-//   k_bp_sweep_g<0>  A of every piece but the last (cut worth 0, exit -inf); the last piece, which ends
-//                    in the exit vertex, gets its absolute scores at once
-//   k_bp_sweep_g<1>  B of every piece but the last (cut -inf, exit 0)
-//   k_bp_comb        per target: the absolute score of every cut, from the last one down:
-//                    score[c_k] = max(A_k + score[c_k+1], B_k); the exactness bound; deferred vertices reset
-//   k_bp_sweep_g<2>  the absolute scores and first-maximum choices of every piece but the last
-//                    (a target that failed the bound, or has too many deferred vertices: one sweep, as a whole)
-//   k_bp_defer       the deferred vertices nobody asked for (enter is the last of them)
-//   k_bp_walk_g      the best-edge walk in pieces: from every cut to the next cut or to exit, and from
-//                    enter to the first cut it meets;  k_bp_join chains the pieces that are on the path
+//   k_bp_xtree        the tree of vertices that lead to exit and nowhere else: absolute scores at once
+//   k_bp_sweep_ab     one sweep per piece for A (cut worth 0, exit -inf) and B (cut -inf, exit 0) of every vertex;
+//                     the last piece, which ends in the exit vertex, gets its absolute scores and choices at once
+//   k_bp_comb         per target: the absolute score of every cut, from the last one down:
+//                     score[c_k] = max(A_k + score[c_k+1], B_k); the exactness bound; deferred vertices reset
+//   k_bp_abs          the absolute score of every vertex of the other pieces: max(A + score[upper cut], B)
+//   k_bp_choose       their first-maximum choices, each from its own out-list
+//   k_bp_sweep_abs_g  a target that failed the bound, has too many deferred vertices or is one piece: one sweep, whole
+//   k_bp_defer        the deferred vertices nobody asked for (enter is the last of them)
+//   k_bp_walk_g       the best-edge walk in pieces: from every cut to the next cut or to exit, and from
+//                     enter to the first cut it meets;  k_bp_join chains the pieces that are on the path
 // ====================================================================================
-
-__global__ __launch_bounds__(64) void k_bp_reset_def(DgParams p) {
-    const uint32_t t = blockIdx.x;
-    if (dg_failed(p) || dg_tskip(p, t)) return;
-    const uint32_t *dl = p.defer + (uint64_t)t * (DG_DEFER_MAX + 1u);
-    const uint32_t n = dl[0];
-    if (n == DG_BP_ONE) return;
-    const uint64_t nb = p.node_base[t];
-    for (uint32_t i = threadIdx.x; i < n; i += 64)
-        if (p.score[nb + dl[1 + i]].y != 2.0f) { p.score[nb + dl[1 + i]] = make_float2(0.0f, 0.0f); p.best[nb + dl[1 + i]] = -1; }
-}
 
 // the tree of vertices that lead to exit and nowhere else (see dg_bp_sweep): absolute scores, final flag 2.0
 __global__ __launch_bounds__(64) void k_bp_xtree(DgParams p) {
@@ -1046,8 +1036,9 @@ __global__ __launch_bounds__(64) void k_bp_xtree(DgParams p) {
     }
 }
 
-template <int PASS>
-__global__ __launch_bounds__(64) void k_bp_sweep_g(DgParams p) {
+// the targets that k_bp_sweep_ab's pieces do not take, in one piece as the reference does it (every vertex in the
+// stream, the deferred ones too)
+__global__ __launch_bounds__(64) void k_bp_sweep_abs_g(DgParams p) {
     const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
     if (dg_failed(p) || dg_tskip(p, t)) return;
     const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
@@ -1059,52 +1050,23 @@ __global__ __launch_bounds__(64) void k_bp_sweep_g(DgParams p) {
     const int N = (int)p.n_nodes[t];
     float2 *score = p.score + nb;
     const bool one = p.defer[(uint64_t)t * (DG_DEFER_MAX + 1u)] == DG_BP_ONE || nseg <= 1;
+    if (!one || seg != 0) return;
     float amax = 0.0f;
     bool bad = false, stuck = false;
-    if (one) {
-        // in one piece, as the reference does it (every vertex in the stream, the deferred ones too)
-        if (PASS != 2 || seg != 0) return;
-        for (int i = lane; i < N; i += 64) score[i] = make_float2(0.0f, 0.0f);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        dg_bp_sweep(S, p.nodes + nb, p.best + nb, score, p.pool + p.pool_base[t], p.bp_tt + nb, N - 1, 0, -1,
-                    p.stk + (uint64_t)blockIdx.x * p.stk_words, (int)p.stk_words, lane, amax, bad, stuck);
-    } else {
-        if (p.bp_fused) return;                                // (k_bp_sweep_ab / k_bp_abs / k_bp_choose did the pieces)
-        const bool last = seg + 1 == nseg;
-        if (last && PASS != 0) return;
-        const int c_bot = (int)crow[1 + seg];
-        const int c_top = last ? -1 : (int)crow[2 + seg];
-        const int v_top = last ? N - 1 : c_top - 1;
-        if (PASS != 0) {
-            for (int i = c_bot + lane; i <= v_top; i += 64) if (score[i].y != 2.0f) score[i] = make_float2(0.0f, 0.0f);   // (the pass before left its own)
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        }
-        float *ab = p.bp_ab + 4ull * blockIdx.x;
-        const float ctv = PASS == 0 ? 0.0f : PASS == 1 ? DG_BP_NINF : ab[2];
-        const float xv = PASS == 0 && !last ? DG_BP_NINF : 0.0f;   // (the last piece ends in exit: its scores are absolute at once)
-        dg_bp_sweep(S, p.nodes + nb, p.best + nb, score, p.pool + p.pool_base[t], p.bp_tt + nb, v_top, c_bot, c_top,
-                    p.stk + (uint64_t)blockIdx.x * p.stk_words, (int)p.stk_words, lane, amax, bad, stuck,
-                    ctv, last ? -1 : N - 1, xv, true);
-        if (!bad) {
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            const float a = score[c_bot].x;                    // (piece 0 begins with enter, which is deferred: not used)
-            if (lane == 0) {
-                if (PASS == 0) { ab[0] = a; ab[3] = amax; }
-                else if (PASS == 1) { ab[1] = a; ab[3] = fmaxf(ab[3], amax); }
-                else ab[3] = fmaxf(ab[3], amax);
-            }
-        }
-    }
+    for (int i = lane; i < N; i += 64) score[i] = make_float2(0.0f, 0.0f);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    dg_bp_sweep(S, p.nodes + nb, p.best + nb, score, p.pool + p.pool_base[t], p.bp_tt + nb, N - 1, 0, -1,
+                p.stk + (uint64_t)blockIdx.x * p.stk_words, (int)p.stk_words, lane, amax, bad, stuck);
     if (bad && lane == 0) { if (stuck) dg_fail_target(p, t, DG_E_INTERNAL); else { dg_fail(p, DG_E_STACK); p.st->bad_target = t; } }
 }
 
-// ---- the pieces in ONE sweep (p.bp_fused) -------------------------------------------------------------------------
+// ---- the pieces in ONE sweep ----------------------------------------------------------------------------------------
 // A and B of every vertex come out of the same pass (dg_bp_sweep<true>): they are the same recurrence on the same edges
 // with different boundary values, and nothing is decided in it.  k_bp_comb turns the pieces' (A, B) into the absolute
-// score of every cut as before; then the absolute score of every vertex is an elementwise max(A + score[cut], B)
-// (k_bp_abs) and its first-maximum choice a loop over its own out-list (k_bp_choose): vertex-parallel kernels instead of
-// a second and a third sequential sweep.  Exact for the reason the three-sweep form is (all values multiples of 0.5
-// below 2^22: k_bp_comb's bound); k_bp_choose checks it on the way -- the maximum it finds must BE the vertex's
+// score of every cut; then the absolute score of every vertex is an elementwise max(A + score[cut], B) (k_bp_abs) and
+// its first-maximum choice a loop over its own out-list (k_bp_choose): vertex-parallel kernels instead of a second and a
+// third sequential sweep.  Exact (all values are multiples of 0.5 below 2^22: k_bp_comb's bound); k_bp_choose checks it
+// on the way -- the maximum it finds must BE the vertex's
 // absolute score, else the target is swept again in one piece.
 __global__ __launch_bounds__(64) void k_bp_sweep_ab(DgParams p) {
     const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
@@ -1112,7 +1074,7 @@ __global__ __launch_bounds__(64) void k_bp_sweep_ab(DgParams p) {
     const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
     const uint32_t nseg = crow[0];
     if (seg >= nseg) return;
-    if (p.defer[(uint64_t)t * (DG_DEFER_MAX + 1u)] == DG_BP_ONE || nseg <= 1) return;       // k_bp_sweep_g<2> has it, whole
+    if (p.defer[(uint64_t)t * (DG_DEFER_MAX + 1u)] == DG_BP_ONE || nseg <= 1) return;       // k_bp_sweep_abs_g has it, whole
     const int lane = threadIdx.x;
     const uint64_t nb = p.node_base[t];
     __shared__ DgBpShared S;

@@ -131,7 +131,7 @@ __device__ inline void dg_finish_alignment(const DgParams &p, uint32_t a, uint16
 }
 
 // ---------------------------------------------------------------------------
-// Chunked normalizeGaps: k_norm_chunk -> k_norm_scan -> k_norm_finish.
+// Chunked normalizeGaps: k_norm_chunk -> k_norm_scan -> k_norm_finish2.
 //
 // The gap push only ever changes columns to the right of the one it is working on, so the
 // rewrite of an alignment can be cut at any column k that no earlier step has touched when
@@ -144,7 +144,7 @@ __device__ inline void dg_finish_alignment(const DgParams &p, uint32_t a, uint16
 // the re-run region), and the swallowed chunk's own result is dropped by k_norm_scan.
 //   k_norm_chunk   lane per chunk: the streaming push loop (dg_norm_run) on [k0, k1)
 //   k_norm_scan    lane per alignment: offsets of the chunks, trimAln (:219-242)
-//   k_norm_finish  lane per chunk: columns to their final place; what dg_finish_alignment
+//   k_norm_finish2 wave per chunk: columns to their final place; what dg_finish_alignment
 //                  does, on the chunk's share of the trimmed window
 // ---------------------------------------------------------------------------
 #ifndef DG_NCH
@@ -411,100 +411,6 @@ __device__ __forceinline__ uint4 dg_funnel_cols(const uint4 A, const uint4 B, co
     return r;
 }
 
-__global__ __launch_bounds__(64) void k_norm_finish(DgParams p) {
-    // neighbouring chunks are ~1 KB of input (4 KB of scratch) apart: lanes of a wave take chunks
-    // a whole grid apart instead, or their lines fight for the same few L1 sets and L2 channels
-    const uint32_t g = threadIdx.x * gridDim.x + blockIdx.x;
-    if (g >= p.n_chunks) return;
-    if (dg_failed(p)) return;
-    const uint32_t a = p.ch_aln[g];
-    if (dg_askip(p, a)) return;
-    const uint32_t o = p.ch_out[g];
-    if (o == DG_CH_NONE) return;
-    const uint32_t hi = p.n_hi[a];
-    if (hi == DG_REDO) return;
-    const uint32_t lo = p.n_lo[a], start = p.n_start[a], lb = p.n_lb[a];
-    const uint32_t w = p.ch_w[g], adv0 = p.ch_adv[g];
-    const uint16_t *src = p.norm_tmp + p.ch_src[g];                  // 16-byte aligned
-    const uint4 *src4 = reinterpret_cast<const uint4 *>(src);
-    uint16_t *dst = p.norm + p.norm_off[a] + o;                       // norm_off is a multiple of 8 columns
-    // what addAln will do with the window (see dg_finish_alignment)
-    const bool graph = !(p.flags & DG_F_A1_ONLY);
-    uint32_t t_idx = 0, r = 0;
-    uint32_t *Cm = nullptr;
-    if (graph) {
-        t_idx = p.aln_tgt[a];
-        if (p.tactive[t_idx]) {
-            const uint64_t ab = p.aln_begin[t_idx];
-            r = (uint32_t)(a - ab);
-            Cm = p.matC + p.matc_base[t_idx] + (uint64_t)r * p.matc_stride[t_idx];   // the read's row
-        }
-    }
-    const uint32_t tlen = graph ? p.tlen[t_idx] : 0xFFFFFFFFu;
-    uint32_t *ck = p.ckpt + p.ck_base[a];
-    const uint32_t ck_mask = (1u << p.emit_shift) - 1u;
-    // target bases between the trimmed start and this chunk (a chunk in front of lo has none)
-    uint32_t adv = adv0 > lb ? adv0 - lb : 0u;
-    uint32_t n_ins = 0, n_del = 0, run = 0;
-    bool conf = start >= 1 && !((uint64_t)start - 1 + adv > (uint64_t)tlen && adv > 0);
-    // the chunk's share of the trimmed window, as chunk-relative column numbers
-    const uint32_t f0 = lo > o ? lo - o : 0u;
-    const uint32_t f1 = hi > o ? (hi - o < w ? hi - o : w) : 0u;
-    const bool any = f1 > f0;
-    const uint32_t fspan = any ? f1 - f0 : 0u;
-
-    // columns go to their final place as aligned 16-byte stores: h single columns up to the
-    // destination's next 16-byte line, then blocks funnelled out of two source vectors
-    const uint32_t h0 = (8u - (o & 7u)) & 7u;
-    const uint32_t h = h0 < w ? h0 : w;
-    const uint32_t nb = (w - h) / 8u;
-    for (uint32_t x = 0; x < h; x++) dst[x] = src[x];
-    uint4 *dst4 = reinterpret_cast<uint4 *>(dst + h);
-    const uint32_t nvec = (w + 7u) / 8u;
-    uint4 prev = make_uint4(0, 0, 0, 0);
-    // a whole 128-byte line of the chunk (8 vectors) is requested at once: taking it 16 bytes at
-    // a time, with every lane on a line of its own, each line came in from L2 eight times
-    uint4 lin[8];
-    for (uint32_t v = 0; v < nvec; v++) {
-        if ((v & 7u) == 0) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) lin[k] = v + k < nvec ? src4[v + k] : make_uint4(0, 0, 0, 0);
-        }
-        uint4 cur = lin[0];
-#pragma unroll
-        for (int k = 1; k < 8; k++) if ((v & 7u) == (uint32_t)k) cur = lin[k];
-        if (v >= 1 && v - 1 < nb) dst4[v - 1] = dg_funnel_cols(prev, cur, h);
-        prev = cur;
-        if (8u * v + 8u <= f0 || 8u * v >= f1) continue;         // nothing of the window in this vector
-        const uint32_t w4[4] = {cur.x, cur.y, cur.z, cur.w};
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint16_t c = (uint16_t)((k & 1) ? w4[k >> 1] >> 16 : w4[k >> 1] & 0xffffu);
-            if (8u * v + (uint32_t)k - f0 >= fspan) continue;
-            const uint8_t qb = DG_Q(c), tb = DG_T(c);
-            if (qb == tb || qb == DG_GAP) {
-                // (the first column of a chunk inside the window: the chunk in front records it,
-                // it may end in the insertion run that belongs to this position)
-                if (Cm && conf && ((start + adv) & ck_mask) == 0 && start + adv <= tlen + 1 && !(8u * v + (uint32_t)k == 0 && o > lo))
-                    ck[(start + adv) >> p.emit_shift] = o + 8u * v + (uint32_t)k - run;
-                if (run) { if (Cm && conf && start + adv <= tlen + 1) Cm[start + adv] = run; run = 0; }
-                adv++; n_del += (qb != tb);
-                if ((uint64_t)start - 1 + adv > (uint64_t)tlen) conf = false;
-            } else if (tb == DG_GAP) { n_ins++; run++; }
-        }
-    }
-    if (nvec >= 1 && nb == nvec) dst4[nb - 1] = dg_funnel_cols(prev, make_uint4(0, 0, 0, 0), h);   // h == 0, w % 8 == 0
-    for (uint32_t x = h + 8u * nb; x < w; x++) dst[x] = src[x];
-    // the column after the chunk is a match (the next chunk's first) or the end of the window;
-    // a trailing insertion run of the read belongs to the position after its last one
-    if (any && Cm && conf && ((start + adv) & ck_mask) == 0 && start + adv <= tlen + 1 && (o + f1 < hi || run))
-        ck[(start + adv) >> p.emit_shift] = o + f1 - run;
-    if (run && Cm && conf && start + adv <= tlen + 1) Cm[start + adv] = run;
-    if (n_ins) atomicAdd(&p.n_ins[a], n_ins);
-    if (n_del) atomicAdd(&p.n_del[a], n_del);
-    if (graph && any && !conf) dg_fail_aln(p, a, DG_E_NONCONF);
-}
-
 // exclusive prefix sum over the lanes of a wave: four DPP row shifts inside the rows of 16 lanes, two row broadcasts
 // across them (lanes without a source add 0); no LDS
 __device__ __forceinline__ uint32_t dg_wave_excl(const uint32_t v, const int lane) {
@@ -520,18 +426,16 @@ __device__ __forceinline__ uint32_t dg_wave_excl(const uint32_t v, const int lan
 }
 
 // ---------------------------------------------------------------------------
-// k_norm_finish2: what k_norm_finish does, a WAVE per chunk (round 3).  With a lane per chunk every lane streams lines
-// of its own, a whole grid apart: 16-byte accesses that share nothing, half a million chunks in flight, their partly
-// written lines (matC cells above all: 4 bytes here, 4 bytes there along a row) pushed out of the L2s before the next
-// store to them arrives -- 4.7 GB of traffic for a 0.9 GB copy.  Here the 64 lanes take consecutive 16-byte pieces of ONE
-// chunk (8 columns each, 512 per pass): the copy is coalesced loads and funnelled, aligned, coalesced stores; how
-// many target bases lie in front of a lane's columns is a prefix sum over the lanes, how long the insertion run in
-// front of them is a segmented one (reset at every lane that holds a match / deletion column); then every lane walks its
-// own 8 columns as k_norm_finish walks them all.
+// k_norm_finish2: columns to their final place, and what dg_finish_alignment does on the chunk's share of the trimmed
+// window, a WAVE per chunk (round 3; a lane per chunk before it).  With a lane per chunk every lane streams lines of its
+// own, a whole grid apart: 16-byte accesses that share nothing, half a million chunks in flight, their partly written
+// lines (matC cells above all: 4 bytes here, 4 bytes there along a row) pushed out of the L2s before the next store to
+// them arrives -- 4.7 GB of traffic for a 0.9 GB copy.  Here the 64 lanes take consecutive 16-byte pieces of ONE chunk
+// (8 columns each, 512 per pass): the copy is coalesced loads and funnelled, aligned, coalesced stores; how many target
+// bases lie in front of a lane's columns is a prefix sum over the lanes, how long the insertion run in front of them is
+// a segmented one (reset at every lane that holds a match / deletion column); then every lane walks its own 8 columns
+// as dg_finish_alignment walks them all.
 // ---------------------------------------------------------------------------
-#ifndef DG_NF2_V
-#define DG_NF2_V 1            // (2: one pass per chunk instead of two, and no faster: 6.0 against 5.9 ms of normalize)
-#endif
 __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
     const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (g >= p.n_chunks) return;
@@ -563,8 +467,8 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
     const uint32_t f1 = hi > o ? (hi - o < w ? hi - o : w) : 0u;
     const bool any = f1 > f0;
     const uint32_t fspan = any ? f1 - f0 : 0u;
-    // conformity as k_norm_finish keeps it: true while start - 1 + (target bases so far) <= tlen
-#define DG_NF2_CONF(A) (start >= 1u && ((A) == 0u || (uint64_t)start - 1u + (A) <= (uint64_t)tlen))
+    // conformity as dg_finish_alignment keeps it: true while start - 1 + (target bases so far) <= tlen
+#define DG_FIN_CONF(A) (start >= 1u && ((A) == 0u || (uint64_t)start - 1u + (A) <= (uint64_t)tlen))
     const uint32_t h0 = (8u - (o & 7u)) & 7u;
     const uint32_t h = h0 < w ? h0 : w;
     const uint32_t nb = (w - h) / 8u, nvec = (w + 7u) / 8u;
@@ -573,22 +477,19 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
     { const uint32_t x = h + 8u * nb + (uint32_t)lane; if (lane < 8 && x < w) dst[x] = src[x]; }
     uint4 *dst4 = reinterpret_cast<uint4 *>(dst + h);
     uint32_t adv_tile = adv_init, run_tile = 0, n_ins = 0, n_del = 0;
-    // a lane takes DG_NF2_V consecutive 16-byte pieces: a chunk of 512 input columns is ~550 columns here, one pass of 1024
-    constexpr uint32_t NV = DG_NF2_V, NC = 8u * NV;
-    for (uint32_t v0 = 0; v0 < nvec; v0 += 64u * NV) {
-        const uint32_t vl = v0 + NV * (uint32_t)lane;                // the lane's first piece
-        uint4 pc[NV + 1];
-#pragma unroll
-        for (uint32_t j = 0; j <= NV; j++) pc[j] = vl + j < nvec ? src4[vl + j] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-        for (uint32_t j = 0; j < NV; j++) if (vl + j < nb) dst4[vl + j] = dg_funnel_cols(pc[j], pc[j + 1], h);
+    // a lane takes one 16-byte piece per pass: a chunk of 512 input columns is ~550 columns here, two passes of 512
+    // (two pieces per lane and one pass: no faster, 6.0 against 5.9 ms of normalize)
+    for (uint32_t v0 = 0; v0 < nvec; v0 += 64u) {
+        const uint32_t vl = v0 + (uint32_t)lane;                     // the lane's piece
+        const uint4 pc = vl < nvec ? src4[vl] : make_uint4(0, 0, 0, 0);
+        const uint4 pn = vl + 1 < nvec ? src4[vl + 1] : make_uint4(0, 0, 0, 0);     // (the funnel takes columns from the next)
+        if (vl < nb) dst4[vl] = dg_funnel_cols(pc, pn, h);
         if (!any || 8u * v0 >= f1) continue;                          // (uniform) nothing of the window from here on
         // ---- the lane's columns: classes, inside the trimmed window only ----
         uint32_t advm = 0, insm = 0, delm = 0;                        // bit k: column k advances the cursor / is an insertion / a deletion
 #pragma unroll
-        for (uint32_t k = 0; k < NC; k++) {
-            const uint4 q4 = pc[k >> 3];
-            const uint32_t wd = ((k >> 1) & 3u) == 0 ? q4.x : ((k >> 1) & 3u) == 1 ? q4.y : ((k >> 1) & 3u) == 2 ? q4.z : q4.w;
+        for (uint32_t k = 0; k < 8u; k++) {
+            const uint32_t wd = ((k >> 1) & 3u) == 0 ? pc.x : ((k >> 1) & 3u) == 1 ? pc.y : ((k >> 1) & 3u) == 2 ? pc.z : pc.w;
             const uint16_t c = (uint16_t)((k & 1u) ? wd >> 16 : wd & 0xffffu);
             const bool inw = 8u * vl + k < 8u * nvec && 8u * vl + k - f0 < fspan;
             const uint8_t qb = DG_Q(c), tb = DG_T(c);
@@ -617,13 +518,13 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
         const uint32_t lf = (uint32_t)__builtin_amdgcn_readlane((int)sf, 63), lv = (uint32_t)__builtin_amdgcn_readlane((int)sv, 63);
         run_tile = lf ? lv : lv + run_tile;
         adv_tile += (uint32_t)__builtin_amdgcn_readlane((int)(adv_lane - adv_tile + nadv), 63);
-        // ---- the lane walks its columns (k_norm_finish's loop body) ----
+        // ---- the lane walks its columns (dg_finish_alignment's loop) ----
         uint32_t adv = adv_lane;
         if (Cm && (advm | insm)) {
 #pragma unroll
-            for (uint32_t k = 0; k < NC; k++) {
+            for (uint32_t k = 0; k < 8u; k++) {
                 if ((advm >> k) & 1u) {
-                    const bool conf = DG_NF2_CONF(adv);
+                    const bool conf = DG_FIN_CONF(adv);
                     const uint32_t x = 8u * vl + k;
                     // (the first column of a chunk inside the window: the chunk in front records it,
                     // it may end in the insertion run that belongs to this position)
@@ -640,7 +541,7 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
     // a trailing insertion run of the read belongs to the position after its last one
     {
         const uint32_t adv = adv_tile, run = run_tile;
-        const bool conf = DG_NF2_CONF(adv);
+        const bool conf = DG_FIN_CONF(adv);
         if (lane == 0) {
             if (any && Cm && conf && ((start + adv) & ck_mask) == 0 && start + adv <= tlen + 1 && (o + f1 < hi || run))
                 ck[(start + adv) >> p.emit_shift] = o + f1 - run;
@@ -653,7 +554,7 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
         const uint32_t ti = dg_wave_excl(n_ins, lane) + n_ins, td = dg_wave_excl(n_del, lane) + n_del;
         if (lane == 63) { if (ti) atomicAdd(&p.n_ins[a], ti); if (td) atomicAdd(&p.n_del[a], td); }
     }
-#undef DG_NF2_CONF
+#undef DG_FIN_CONF
 }
 
 // The same algorithm with the whole expanded alignment in HBM: raw mode and
@@ -925,7 +826,7 @@ __global__ __launch_bounds__(1024) void k_gscan(DgParams p) {
 // k_emit: addAln.  One wave per (target, group of 64 reads, stretch of 1 << emit_shift
 // backbone positions), one lane per read.
 //
-// A lane enters its stretch at the column k_norm_finish recorded for the stretch's first
+// A lane enters its stretch at the column k_norm_finish2 recorded for the stretch's first
 // position (or at the read's start) and finds the vertex in front of it by looking back
 // over the deletion columns; it writes the arrival side of every vertex of the stretch and
 // the departure side of every vertex it created (`own`): for the last one it looks ahead,
@@ -1364,9 +1265,8 @@ __global__ __launch_bounds__(256) void k_lists(DgParams p) {
     const uint64_t nb = p.node_base[t];
     const uint64_t bv = p.bbv_base[t];
     uint32_t *pool = p.pool + p.pool_base[t];
-    // cells of read r at position pos: [position][read] from k_emit, [read][position] (rows as matC's) from k_emit2
-    const uint32_t *Am0 = p.matA + (p.emit2 ? p.matc_base[t] : p.mat_base[t]), *Dm0 = p.matD + (p.emit2 ? p.matc_base[t] : p.mat_base[t]);
-    const uint32_t rstep = p.emit2 ? p.matc_stride[t] : 1u;
+    // cells of read r at position pos: [position][read] (k_emit)
+    const uint32_t *Am0 = p.matA + p.mat_base[t], *Dm0 = p.matD + p.mat_base[t];
     const uint32_t capb = dg_capb(K);
     const uint32_t fixed0 = 3u * p.t_nins[t];
     // a wave takes DG_LPW consecutive positions: the set-up above is paid once for them
@@ -1374,8 +1274,8 @@ __global__ __launch_bounds__(256) void k_lists(DgParams p) {
     const uint32_t pos = (blockIdx.y * 4 + wave) * DG_LPW + pi;
     if (pos >= blen + 2) return;
     const uint32_t v = p.bid[bv + pos];
-    const uint32_t *Am = Am0 + (p.emit2 ? (uint64_t)pos : (uint64_t)pos * K);
-    const uint32_t *Dm = Dm0 + (p.emit2 ? (uint64_t)pos : (uint64_t)pos * K);
+    const uint32_t *Am = Am0 + (uint64_t)pos * K;
+    const uint32_t *Dm = Dm0 + (uint64_t)pos * K;
     const uint32_t fixed = fixed0 + pos * 3u * capb;
     uint32_t out_off = fixed, in_off = fixed + 2u * capb;
     uint32_t out_cap = capb, in_cap = capb;
@@ -1393,7 +1293,7 @@ __global__ __launch_bounds__(256) void k_lists(DgParams p) {
             // its own with no comparing; only the other backbone vertices (deletion jumps, the exit,
             // the enter) are grouped by peeling.  Entries go straight to the pool in the order of
             // their first read. ----
-            const uint32_t cell = (uint32_t)lane < K ? row[(uint64_t)lane * rstep] : 0u;
+            const uint32_t cell = (uint32_t)lane < K ? row[lane] : 0u;
             // departure: neighbour id + 1 (0 = none) and, above bit 25, the reads k_emit folded into this one's chain
             int32_t val = (int32_t)DG_CELL_ID(cell);
             const int32_t extra = (int32_t)(cell >> 25);
@@ -1451,7 +1351,7 @@ __global__ __launch_bounds__(256) void k_lists(DgParams p) {
         bool in_lds = false;
         for (uint32_t r0 = 0; r0 < K; r0 += DG_WAVE) {
             const uint32_t r = r0 + lane;
-            const uint32_t cell = r < K ? row[(uint64_t)r * rstep] : 0u;
+            const uint32_t cell = r < K ? row[r] : 0u;
             int32_t val = (int32_t)DG_CELL_ID(cell);           // neighbour id + 1, 0 = none
             const int32_t extra = dir == 0 ? (int32_t)(cell >> 25) : 0;       // reads folded into this one's chain (k_emit)
             if (dir == 1) {

@@ -392,45 +392,6 @@ __device__ inline void dgg_merge_out(DgGraph &g, int n) {
 }
 
 // ============================================================================
-// Prefetch wave.  The sweeps of stages (b) and (c) are dependent pointer chases:
-// what they cost is the latency of each access, and a first touch of a cache
-// line is an HBM miss.  Vertex ids are in backbone-position order, so the sweep
-// moves through the vertex records and their lists monotonically; a second
-// wave of the same workgroup (same CU, same L1) runs ahead of the worker and
-// touches the records and list heads it is about to need.  It only loads; it
-// never changes what the worker computes.
-// ============================================================================
-#define DG_PROG_DONE 0x7fffffff
-#define DG_PF_AHEAD 256
-#define DG_PF_CHUNK 64
-
-__device__ inline void dg_prefetch_wave(const DgNode *nd, const uint32_t *pool, uint32_t pool_size,
-                                        int lo, int N, int *s_prog, int lane, int dir, int ahead) {
-    if (ahead <= 0) return;
-    int next = dir > 0 ? lo : N - 1;
-    unsigned spins = 0;
-    uint32_t sink = 0;
-    for (;;) {
-        const int cur = __hip_atomic_load(s_prog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (cur == DG_PROG_DONE) break;
-        const bool work = dir > 0 ? (next < N && next < cur + ahead) : (next >= lo && next > cur - ahead);
-        if (!work) {
-            if ((dir > 0 ? next >= N : next < lo) || ++spins > 400000000u) break;
-            __builtin_amdgcn_s_sleep(4);
-            continue;
-        }
-        const int v = next + dir * lane;
-        if (v >= lo && v < N) {
-            const uint4 h2 = *(reinterpret_cast<const uint4 *>(&nd[v]) + 1);
-            if (h2.x < pool_size) sink ^= pool[h2.x];
-            if (h2.y < pool_size) sink ^= pool[h2.y];
-        }
-        next += dir * DG_PF_CHUNK;
-    }
-    asm volatile("" ::"v"(sink));
-}
-
-// ============================================================================
 // Wave-cooperative merge.  Everything below is executed by all 64 lanes with
 // wave-uniform control flow; a lane holds one list entry.
 // ============================================================================
@@ -813,7 +774,7 @@ __global__ __launch_bounds__(64) void k_cuts(DgParams p) {
             }
             if (found) { if (lane == 0) out[1 + nseg] = found; nseg++; }
         }
-        if (lane == 0) { out[0] = nseg; if (which == 0 && !p.tile_pos && !p.gcuts) atomicAdd(&p.st->n_mseg, nseg); }
+        if (lane == 0) { out[0] = nseg; if (which == 0 && !p.gcuts) atomicAdd(&p.st->n_mseg, nseg); }
     }
 }
 
@@ -821,11 +782,8 @@ __global__ __launch_bounds__(64) void k_cuts(DgParams p) {
 #define DG_IN_STACK 48
 #define DG_QRING 256
 
-// PF: a second wave runs ahead of the worker and pulls the records and lists it is about to
-// need into L2 (pays when the chip has idle wave slots: few targets x segments in flight)
-#define DG_PROG_SET(x) __hip_atomic_store(&s_prog, (x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-// One segment [c_start, c_end] of target t, swept by the calling wave (PF: by the first wave of the
-// block, the second prefetches).  c_end = 0x7fffffff: the segment runs to the exit vertex.
+// One segment [c_start, c_end] of target t, swept by the calling wave.  c_end = 0x7fffffff: the segment
+// runs to the exit vertex.
 // mode DG_MM_WORKER: a segment between two cuts (with p.gcuts: enter / exit shared, exit not visited, the
 //                      segment that starts at enter resumes where the prologue stopped);
 //      DG_MM_PROLOGUE: from enter, every visit up to FIFO level `lvl_stop` (the enter visit and the
@@ -836,7 +794,7 @@ __global__ __launch_bounds__(64) void k_cuts(DgParams p) {
 #define DG_MM_PROLOGUE 1
 #define DG_MM_FINISH 2
 // GC: compiled for p.gcuts (the full-span path, k_merge, carries none of the checks for shared lists)
-template <bool PF, bool GC = false>
+template <bool GC = false>
 __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32_t t, const int c_start, const int c_end,
                                                  int32_t *stk_base, const int mode = DG_MM_WORKER, const uint32_t me = 0,
                                                  const uint32_t wlo = 0, const int lvl_stop = 0) {
@@ -845,15 +803,6 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
     const uint32_t NT = p.n_nodes[t];
     const bool has_end = c_end != 0x7fffffff;
     const int c_hi = has_end ? c_end : (int)NT - 1;
-    __shared__ int s_prog;
-    if (PF) {
-        if (threadIdx.x == 0) s_prog = c_start;
-        __syncthreads();
-    }
-    if (PF && threadIdx.x >= 64) {                       // wave 1: prefetcher
-        dg_prefetch_wave(p.nodes + nb, p.pool + p.pool_base[t], p.pool_size[t], c_start, c_hi + 1, &s_prog, lane, +1, (int)p.pf_ahead);
-        return;
-    }
     DgGraph g;
     const bool own_q = GC && p.gcuts && c_start == 0 && mode != DG_MM_FINISH;     // (see DgParams::queue0)
     g.nd = p.nodes + nb; g.queue = own_q ? p.queue0 + nb : p.queue + nb + c_start;          // the segment's own stretch of the queue
@@ -879,7 +828,6 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
     int lvl = 0;
     uint32_t lvl_end = 1;
     int failed = 0;
-    int prog = c_start;
     int u_next = 0;
     bool have_next = false;
     DgNode nu_next;                 // record of u_next, requested before the previous visit's stores
@@ -907,7 +855,6 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
         unsigned long long ts_pre = 0, ts_in = 0, acc_grp = 0, n_grp_in = 0, n_grp_out = 0;
         const unsigned long long ts0 = clock64();
 #endif
-        if (PF && u > prog + 15) { prog = u; if (lane == 0) DG_PROG_SET(u); }
         if (mode != DG_MM_PROLOGUE && (u < c_start || u > c_hi)) {    // cannot happen (see k_cuts): refuse rather than race
             dgw_fail(g, DG_E_INTERNAL, lane);
             break;
@@ -1160,7 +1107,6 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
         { unsigned long long now = clock64(); if (merged || scalar) { c_slow += now - t_prev; n_slow++; n_scalar += scalar; c_a += ts_pre - ts0; c_b += ts_in - ts_pre; c_c += now - ts_in; c_grp += acc_grp; ng_in += n_grp_in; ng_out += n_grp_out; } else { c_fast += now - t_prev; n_fast++; c_odd += now - t_prev; n_odd++; } t_prev = now; }
 #endif
     }
-    if (PF && lane == 0) DG_PROG_SET(DG_PROG_DONE);
     if (mode == DG_MM_PROLOGUE && lane == 0) {
         p.pro_state[4u * t] = qh; p.pro_state[4u * t + 1u] = qt; p.pro_state[4u * t + 2u] = qh;
     }
@@ -1170,8 +1116,7 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
 }
 
 // mergeNodes (AlnGraphBoost.cpp:129-160): one wave per (target, segment of p.cuts)
-template <bool PF>
-__global__ __launch_bounds__(PF ? 128 : 64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_merge(DgParams p) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_merge(DgParams p) {
     const uint32_t t = blockIdx.x / p.seg_max, seg = blockIdx.x % p.seg_max;
     if (dg_failed(p) || dg_tskip(p, t)) return;
     // (a batch that k_merge_q sweeps leaves its deep targets to this kernel: DgParams::q_kmax)
@@ -1181,10 +1126,10 @@ __global__ __launch_bounds__(PF ? 128 : 64) __attribute__((amdgpu_waves_per_eu(8
     if (seg >= nseg) return;
     const int c_start = (int)crow[1 + seg];
     const int c_end = seg + 1 < nseg ? (int)crow[2 + seg] : 0x7fffffff;     // the next segment's cut vertex
-    dg_merge_segment<PF>(p, t, c_start, c_end, p.stk + (uint64_t)blockIdx.x * p.stk_words);
+    dg_merge_segment(p, t, c_start, c_end, p.stk + (uint64_t)blockIdx.x * p.stk_words);
 }
 
-// A worklist of segments (p.tile_list: [0] = entries, [2] = ticket cursor, then (target, first vertex,
+// A worklist of segments (p.worklist: [0] = entries, [2] = ticket cursor, then (target, first vertex,
 // last vertex or DG_NOSEG_END) triples, a target's segments in a row and in order): one wave per
 // entry.  Entries are taken by ticket, so a worker that waits for the earlier segments of its target
 #define DG_NOSEG_END 0xFFFFFFFFu
@@ -1193,22 +1138,22 @@ __global__ __launch_bounds__(PF ? 128 : 64) __attribute__((amdgpu_waves_per_eu(8
 #endif
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DG_ML_WAVES, DG_ML_WAVES))) void k_merge_list(DgParams p) {
     if (dg_failed(p)) return;
-    const uint32_t n = p.tile_list[0] < p.tile_list_cap ? p.tile_list[0] : p.tile_list_cap;
+    const uint32_t n = p.worklist[0] < p.worklist_cap ? p.worklist[0] : p.worklist_cap;
     for (;;) {
         uint32_t i = 0;
-        if (threadIdx.x == 0) i = atomicAdd(&p.tile_list[2], 1u);
+        if (threadIdx.x == 0) i = atomicAdd(&p.worklist[2], 1u);
         i = (uint32_t)__builtin_amdgcn_readfirstlane((int)i);
         if (i >= n) break;
-        const uint32_t t = p.tile_list[4 + 3 * i];
-        const int c_start = (int)p.tile_list[5 + 3 * i];
-        const uint32_t ce = p.tile_list[6 + 3 * i];
+        const uint32_t t = p.worklist[4 + 3 * i];
+        const int c_start = (int)p.worklist[5 + 3 * i];
+        const uint32_t ce = p.worklist[6 + 3 * i];
         if (dg_tskip(p, t)) continue;
-        dg_merge_segment<false, true>(p, t, c_start, ce == DG_NOSEG_END ? 0x7fffffff : (int)ce, p.stk + (uint64_t)blockIdx.x * p.stk_words,
+        dg_merge_segment<true>(p, t, c_start, ce == DG_NOSEG_END ? 0x7fffffff : (int)ce, p.stk + (uint64_t)blockIdx.x * p.stk_words,
                                       DG_MM_WORKER, i, p.gcuts ? p.wl_first[t] : 0u);
         if (threadIdx.x == 0) atomicAdd(&p.st->n_mseg, 1u);
         DG_WAVE_FENCE();
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && p.tile_list[0] > p.tile_list_cap) dg_fail(p, DG_E_LIST_OVF);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && p.worklist[0] > p.worklist_cap) dg_fail(p, DG_E_LIST_OVF);
 }
 
 // ---- mergeNodes for pileups of partial-span reads: prologue, cuts, epilogue ------------------------
@@ -1256,7 +1201,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     for (int o = 32; o; o >>= 1) { const uint32_t x = __shfl_xor(maxlead, o); maxlead = x > maxlead ? x : maxlead; }
     if (lane == 0) p.pro_state[4u * t + 3u] = 0u;
     DG_WAVE_FENCE();
-    dg_merge_segment<false, true>(p, t, 0, 0x7fffffff, p.stk + (uint64_t)blockIdx.x * p.stk_words, DG_MM_PROLOGUE, 0, 0, (int)maxlead + 1);
+    dg_merge_segment<true>(p, t, 0, 0x7fffffff, p.stk + (uint64_t)blockIdx.x * p.stk_words, DG_MM_PROLOGUE, 0, 0, (int)maxlead + 1);
 }
 
 // cuts for k_merge_list: up to p.seg_max pieces per target, conditions (1) - (4) above
@@ -1446,17 +1391,17 @@ __global__ __launch_bounds__(64) void k_cuts2(DgParams p) {
     // the target's segments, in a row and in order
     __shared__ uint32_t s_base;
     if (lane == 0) {
-        s_base = atomicAdd(&p.tile_list[0], nseg);
+        s_base = atomicAdd(&p.worklist[0], nseg);
         p.wl_first[t] = s_base;
     }
     __syncthreads();
     const uint32_t base = s_base;
     for (uint32_t s = lane; s < nseg; s += 64) {
         const uint32_t i = base + s;
-        if (i < p.tile_list_cap) {
-            p.tile_list[4 + 3 * i] = t;
-            p.tile_list[5 + 3 * i] = skip ? 0u : s_cut[s];
-            p.tile_list[6 + 3 * i] = s + 1 < nseg ? s_cut[s + 1] : DG_NOSEG_END;
+        if (i < p.worklist_cap) {
+            p.worklist[4 + 3 * i] = t;
+            p.worklist[5 + 3 * i] = skip ? 0u : s_cut[s];
+            p.worklist[6 + 3 * i] = s + 1 < nseg ? s_cut[s + 1] : DG_NOSEG_END;
         }
     }
 }
@@ -1498,7 +1443,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     }
     DG_WAVE_FENCE();
     if (!(p.pro_state[4u * t + 3u] & 1u))                 // (a tiny target: the prologue came as far as exit)
-        dg_merge_segment<false, true>(p, t, (int)NT - 1, 0x7fffffff, p.stk + (uint64_t)blockIdx.x * p.stk_words, DG_MM_FINISH);
+        dg_merge_segment<true>(p, t, (int)NT - 1, 0x7fffffff, p.stk + (uint64_t)blockIdx.x * p.stk_words, DG_MM_FINISH);
     DG_WAVE_FENCE();
     // what bestPath's segment sweeps must leave alone (DG_NF_DEFER, see dg_bp_sweep): enter, the vertices the
     // prologue visited that have a successor in another segment than their own id, and their ancestors

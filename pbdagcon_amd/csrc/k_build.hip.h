@@ -9,7 +9,7 @@
 //   k_emit       a2  addAln (AlnGraphBoost.cpp:64-107): one lane per alignment walks its columns;
 //                    plain stores only (arrival / departure cells, inserted vertex records)
 //   k_lists      a2  backbone vertices (AlnGraphBoost.cpp:16-62), addEdge dedupe (:109-127) + coverage / weight / base:
-//                    one wave per backbone position turns its arrival / departure row into
+//                    one wave per DG_LPW backbone positions turns each one's arrival / departure rows into
 //                    ordered adjacency lists (ballot / popcount peeling)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1231,7 +1231,7 @@ __global__ __launch_bounds__(64) void k_emit(DgParams p) {
 }
 
 // ---------------------------------------------------------------------------
-// k_lists: one wave per backbone position.
+// k_lists: one wave per DG_LPW backbone positions.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ int dg_lds_find(volatile int32_t *vals, int n, int x, int lane) {
     for (int b = 0; b < n; b += DG_WAVE) {
@@ -1246,10 +1246,151 @@ __device__ __forceinline__ int dg_lds_find(volatile int32_t *vals, int n, int x,
 __device__ __forceinline__ uint32_t dg_pool_alloc(const DgParams &p, uint32_t t, uint32_t words, int lane) {
     uint32_t off = 0;
     if (lane == 0) {
+        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);   // (formed here on the rare path: no per-target address lives through the caller's loop)
         off = atomicAdd(&p.pool_top[t], words);
         if ((uint64_t)off + words > p.pool_size[t]) { dg_fail(p, DG_E_POOL_TGT); p.st->bad_target = t; off = 0xFFFFFFFFu; }
     }
     return (uint32_t)__builtin_amdgcn_readlane((int)off, 0);
+}
+
+// One row of K <= 64 cells (one read per lane) -> the entries of one list.  Entry 0 is the constructor's neighbour
+// (`chain`, the id + 1 of the adjacent backbone vertex); a neighbour in [ulo, uhi) is an inserted vertex of the adjacent
+// group, which belongs to one read only, so it is an entry of its own with no comparing; only the other backbone vertices
+// (deletion jumps, the exit, the enter) are grouped by peeling.  Returns the lanes that hold the first read of an entry
+// after entry 0; `cnt` is the entry's count on that lane (departures: 1 + extra, peeled: reads + extra), `cm` the reads
+// of entry 0.
+__device__ __forceinline__ unsigned long long dg_list_row(int32_t val, int32_t extra, int32_t chain, int32_t ulo, int32_t uhi,
+                                                          int lane, int32_t &cnt, unsigned long long &cm) {
+    cm = __ballot(val == chain);
+    const bool uniq = val >= ulo && val < uhi;
+    unsigned long long firsts = __ballot(uniq);
+    cnt = 1 + extra;
+    unsigned long long rem = __ballot(val != 0 && !uniq) & ~cm;
+    while (rem) {
+        const int first = __ffsll((long long)rem) - 1;
+        const int32_t x = __builtin_amdgcn_readlane(val, first);
+        const unsigned long long same = __ballot(val == x);
+        rem &= ~same;
+        if (lane == first) cnt = __popcll(same) + extra;
+        firsts |= 1ull << first;
+    }
+    return firsts;
+}
+
+// k_lists for K <= 64 reads: the wave's DG_LPW positions in turn with wave-uniform control, both rows of a position side
+// by side, the next position's row loads issued ahead of this one's ballots (hipcc still waits for all of them at the
+// first ballot: the other waves hide the latency).  What the positions share is fetched once, a position per lane (ids,
+// group bases); what a position makes of its rows is wave-uniform and lands in the lane of that position, whose vertex
+// record and coverage word go out once for the whole wave.
+__device__ __forceinline__ void dg_lists_wave(const DgParams &p, uint32_t t, uint32_t pos0, uint32_t blen, uint32_t K,
+                                              int lane) {
+    const uint32_t npos = min(DG_LPW, blen + 2 - pos0);
+    const uint64_t nb = p.node_base[t];
+    const uint64_t bv = p.bbv_base[t];
+    const uint32_t capb = dg_capb(K);
+    const uint32_t fixed0 = 3u * p.t_nins[t];
+    uint32_t *pool = p.pool + p.pool_base[t];
+#define DG_LPOOL(OFF) (*reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(pool) + (((uint32_t)(OFF)) << 2)))
+    // lane l: bid[pos0 - 1 + l] for l < LPW + 2 (the wave's vertices and the one on either side), gbase[pos0 + l] for l <= LPW
+    const uint32_t qb = pos0 - 1u + (uint32_t)lane;           // (wraps at pos0 = 0, lane 0: no vertex in front of enter)
+    const uint32_t bidl = (lane < (int)DG_LPW + 2 && qb <= blen + 1) ? p.bid[bv + qb] : 0u;
+    const uint32_t gbl = (lane <= (int)DG_LPW && pos0 + lane <= blen + 1) ? p.gbase[bv + pos0 + lane] : 0u;
+    // cells of read r at position pos: [position][read] (k_emit); every row 0 .. blen + 1 exists
+    const uint32_t rb = (uint32_t)lane << 2;
+    const bool rl = (uint32_t)lane < K;
+    const uint32_t *Ar = p.matA + p.mat_base[t] + (uint64_t)pos0 * K, *Dr = p.matD + p.mat_base[t] + (uint64_t)pos0 * K;
+#define DG_LROW(R) (rl ? *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(R) + rb) : 0u)
+    uint32_t dcell = DG_LROW(Dr), acell = DG_LROW(Ar);
+    // the records' variable words, in the lane of their position (the rest follows from the position);
+    // a list that moved to the growth region overwrites its position's default offset and capacity
+    const uint32_t lpos = pos0 + (uint32_t)lane;
+    uint32_t r_lens = 0;                                       // out_len | in_len << 16
+    uint32_t r_cov = 0;                                        // n_cov | n_match << 8 | last_base << 16
+    uint32_t r_out = fixed0 + lpos * 3u * capb, r_in = r_out + 2u * capb;
+    uint32_t r_caps = capb | capb << 16;
+    uint32_t pi = 0;
+    for (; pi < npos; pi++) {
+        const uint32_t pos = pos0 + pi;
+        const uint32_t dep = dcell, arr = acell;
+        if (pi + 1 < npos) {
+            Ar += K; Dr += K;
+            dcell = DG_LROW(Dr); acell = DG_LROW(Ar);
+        }
+        const bool mine = (uint32_t)lane == pi;
+        const int32_t v1 = __builtin_amdgcn_readlane((int)bidl, pi + 1) + 1;     // this vertex's id + 1
+        uint32_t out_len = 0, in_len = 0;
+        if (pos <= blen) {
+            // out list from the departures: neighbour id + 1 (0 = none) and, above bit 25, the reads k_emit folded into this one's chain
+            const int32_t val = (int32_t)DG_CELL_ID(dep), extra = (int32_t)(dep >> 25);
+            const int32_t chain = __builtin_amdgcn_readlane((int)bidl, pi + 2) + 1;
+            const int32_t ulo = __builtin_amdgcn_readlane((int)gbl, pi + 1) + 1;
+            int32_t cnt;
+            unsigned long long cm;
+            const unsigned long long firsts = dg_list_row(val, extra, chain, ulo, chain, lane, cnt, cm);
+            const uint32_t n = 1u + (uint32_t)__popcll(firsts);
+            uint32_t off = fixed0 + pos * 3u * capb;
+            if (n > capb) {                                     // rare: move to the growth region
+                const uint32_t cap = n + 2u;
+                off = dg_pool_alloc(p, t, 2u * cap, lane);
+                if (off == 0xFFFFFFFFu) break;
+                if (mine) { r_out = off; r_caps = (r_caps & 0xFFFF0000u) | cap; }
+            }
+            const uint32_t idx = 1u + (uint32_t)__popcll(firsts & ((1ull << lane) - 1ull));
+            if (lane == 0) { DG_LPOOL(off) = (uint32_t)(chain - 1); DG_LPOOL(off + 1) = (uint32_t)__popcll(cm); }
+            if ((firsts >> lane) & 1ull) { DG_LPOOL(off + 2 * idx) = (uint32_t)(val - 1); DG_LPOOL(off + 2 * idx + 1) = (uint32_t)cnt; }
+            out_len = n;
+        }
+        if (pos >= 1) {
+            // in list from the arrivals, and the coverage of the position
+            const uint32_t idf = DG_CELL_ID(arr);
+            if (pos <= blen) {
+                const unsigned long long covered = __ballot(arr != 0u);
+                const uint32_t n_cov = (uint32_t)__popcll(covered);
+                const uint32_t n_match = (uint32_t)__popcll(__ballot(arr != 0u && idf != DG_CELL_DEL));
+                const uint32_t last_base = covered ? DG_CELL_BASE((uint32_t)__builtin_amdgcn_readlane((int)arr, 63 - __clzll((long long)covered))) : 0u;
+                if (mine) r_cov = n_cov | n_match << 8 | last_base << 16;
+            }
+            const int32_t val = (arr != 0u && idf != DG_CELL_DEL && idf != DG_CELL_DUP) ? (int32_t)idf : 0;
+            const int32_t chain = __builtin_amdgcn_readlane((int)bidl, pi) + 1;
+            const int32_t ulo = __builtin_amdgcn_readlane((int)gbl, pi) + 1;
+            int32_t cnt;
+            unsigned long long cm;
+            const unsigned long long firsts = dg_list_row(val, 0, chain, ulo, v1, lane, cnt, cm);
+            const uint32_t n = 1u + (uint32_t)__popcll(firsts);
+            uint32_t off = fixed0 + pos * 3u * capb + 2u * capb;
+            if (n > capb) {
+                const uint32_t cap = n + 2u;
+                off = dg_pool_alloc(p, t, cap, lane);
+                if (off == 0xFFFFFFFFu) break;
+                if (mine) { r_in = off; r_caps = (r_caps & 0xFFFFu) | cap << 16; }
+            }
+            const uint32_t idx = 1u + (uint32_t)__popcll(firsts & ((1ull << lane) - 1ull));
+            if (lane == 0) DG_LPOOL(off) = (uint32_t)(chain - 1);
+            if ((firsts >> lane) & 1ull) DG_LPOOL(off + idx) = (uint32_t)(val - 1);
+            in_len = n;
+        }
+        if (mine) r_lens = out_len | in_len << 16;
+    }
+    // the whole record of each backbone vertex the wave finished (AlnGraphBoost.cpp:16-62 + what addAln made of it), lane
+    // by position; a growth-region allocation that failed ends the wave at its position (pi), as it ends the kernel
+    const uint32_t v = __shfl_down(bidl, 1);                   // bid[lpos]
+    if ((uint32_t)lane < pi) {
+        const bool inner = lpos >= 1 && lpos <= blen;
+        const uint32_t n_cov = r_cov & 0xFFu, n_match = (r_cov >> 8) & 0xFFu;
+        uint32_t base;
+        if (lpos == 0) base = '^';
+        else if (lpos == blen + 1) base = '$';
+        else if (n_cov) base = r_cov >> 16;                     // last read to cover the position (:79,:90)
+        else base = p.bb ? p.bb[p.bb_off[t] + (lpos - 1)] : (uint8_t)'N';
+        uint4 *rec = reinterpret_cast<uint4 *>(p.nodes + nb + v);
+        rec[0] = make_uint4(r_lens, base | DG_NF_BACKBONE << 8,
+                            inner ? 1u + n_match : 0u,          // weight (:81)
+                            r_lens >> 16);                      // pending = in_len
+        rec[1] = make_uint4(r_out, r_in, r_caps, inner ? lpos : 0u);   // bbpos: _bbMap's absent key (enter, exit) reads as 0
+        p.cov[bv + lpos] = inner ? (int32_t)n_cov : 0;          // :76,:87
+    }
+#undef DG_LROW
+#undef DG_LPOOL
 }
 
 __global__ __launch_bounds__(256) void k_lists(DgParams p) {
@@ -1259,17 +1400,20 @@ __global__ __launch_bounds__(256) void k_lists(DgParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t blen = p.tlen[t];
     const uint32_t K = (uint32_t)(p.aln_begin[t + 1] - p.aln_begin[t]);
+    // a wave takes DG_LPW consecutive positions: the set-up is paid once for them.  (The deep path comes first in the
+    // source: in the other order hipcc needs 106 SGPRs for the kernel and the occupancy drops from 8 to 7.)
+    if (K > DG_WAVE) {
+    // ---- more than a wave of reads: a position at a time; the list under construction has entry i on lane i while it
+    // fits a wave, spilled to LDS beyond that ----
     const uint32_t stride = p.max_k + 2;
     volatile int32_t *vals = s_tmp + (size_t)wave * 2 * stride;
     volatile int32_t *cnts = vals + stride;
     const uint64_t nb = p.node_base[t];
     const uint64_t bv = p.bbv_base[t];
     uint32_t *pool = p.pool + p.pool_base[t];
-    // cells of read r at position pos: [position][read] (k_emit)
     const uint32_t *Am0 = p.matA + p.mat_base[t], *Dm0 = p.matD + p.mat_base[t];
     const uint32_t capb = dg_capb(K);
     const uint32_t fixed0 = 3u * p.t_nins[t];
-    // a wave takes DG_LPW consecutive positions: the set-up above is paid once for them
     for (uint32_t pi = 0; pi < DG_LPW; pi++) {
     const uint32_t pos = (blockIdx.y * 4 + wave) * DG_LPW + pi;
     if (pos >= blen + 2) return;
@@ -1287,64 +1431,6 @@ __global__ __launch_bounds__(256) void k_lists(DgParams p) {
         if (dir == 0 && pos == blen + 1) continue;
         if (dir == 1 && pos == 0) continue;
         const uint32_t *row = dir == 0 ? Dm : Am;
-        if (K <= DG_WAVE) {
-            // ---- one read per lane.  Entry 0 is the constructor's neighbour; a neighbour that is an
-            // inserted vertex of the adjacent group belongs to one read only, so it is an entry of
-            // its own with no comparing; only the other backbone vertices (deletion jumps, the exit,
-            // the enter) are grouped by peeling.  Entries go straight to the pool in the order of
-            // their first read. ----
-            const uint32_t cell = (uint32_t)lane < K ? row[lane] : 0u;
-            // departure: neighbour id + 1 (0 = none) and, above bit 25, the reads k_emit folded into this one's chain
-            int32_t val = (int32_t)DG_CELL_ID(cell);
-            const int32_t extra = (int32_t)(cell >> 25);
-            if (dir == 1) {
-                const uint32_t idf = DG_CELL_ID(cell);
-                const unsigned long long covered = __ballot(cell != 0u);
-                if (pos <= blen) {
-                    n_cov += (uint32_t)__popcll(covered);
-                    n_match += (uint32_t)__popcll(__ballot(cell != 0u && idf != DG_CELL_DEL));
-                    if (covered) last_base = DG_CELL_BASE((uint32_t)__builtin_amdgcn_readlane((int)cell, 63 - __clzll((long long)covered)));
-                }
-                val = (cell != 0u && idf != DG_CELL_DEL && idf != DG_CELL_DUP) ? (int32_t)idf : 0;
-            }
-            const uint32_t gp = dir == 0 ? pos + 1 : pos;
-            const int32_t chain = (int32_t)p.bid[bv + (dir == 0 ? pos + 1 : pos - 1)] + 1;
-            const int32_t ulo = (int32_t)p.gbase[bv + gp] + 1, uhi = (int32_t)p.bid[bv + gp] + 1;
-            const unsigned long long cm = __ballot(val == chain);
-            const bool uniq = val >= ulo && val < uhi;
-            unsigned long long firsts = __ballot(uniq);
-            int32_t cnt = dir == 0 ? 1 + extra : 1;
-            unsigned long long rem = __ballot(val != 0 && !uniq) & ~cm;
-            while (rem) {
-                const int first = __ffsll((long long)rem) - 1;
-                const int32_t x = __builtin_amdgcn_readlane(val, first);
-                const unsigned long long same = __ballot(val == x);
-                rem &= ~same;
-                if (lane == first) cnt = __popcll(same) + (dir == 0 ? extra : 0);
-                firsts |= 1ull << first;
-            }
-            const uint32_t n = 1u + (uint32_t)__popcll(firsts);
-            uint32_t off = dir == 0 ? out_off : in_off;
-            if (n > capb) {                                     // rare: move to the growth region
-                const uint32_t cap = n + 2u;
-                off = dg_pool_alloc(p, t, dir == 0 ? 2u * cap : cap, lane);
-                if (off == 0xFFFFFFFFu) return;
-                if (dir == 0) { out_off = off; out_cap = cap; } else { in_off = off; in_cap = cap; }
-            }
-            const uint32_t idx = 1u + (uint32_t)__popcll(firsts & ((1ull << lane) - 1ull));
-            if (dir == 0) {
-                if (lane == 0) { pool[off] = (uint32_t)(chain - 1); pool[off + 1] = (uint32_t)__popcll(cm); }
-                if ((firsts >> lane) & 1ull) { pool[off + 2 * idx] = (uint32_t)(val - 1); pool[off + 2 * idx + 1] = (uint32_t)cnt; }
-                out_len = n;
-            } else {
-                if (lane == 0) pool[off] = (uint32_t)(chain - 1);
-                if ((firsts >> lane) & 1ull) pool[off + idx] = (uint32_t)(val - 1);
-                in_len = n;
-            }
-            continue;
-        }
-        // ---- more than a wave of reads: the list under construction has entry i on lane i while it
-        // fits a wave, spilled to LDS beyond that ----
         int n = 1;
         int32_t lv = dir == 0 ? (int32_t)p.bid[bv + pos + 1] : (int32_t)p.bid[bv + pos - 1];
         int32_t lc = 0;
@@ -1442,4 +1528,8 @@ __global__ __launch_bounds__(256) void k_lists(DgParams p) {
         p.nodes[nb + v] = nd;
     }
     }
+    return;
+    }
+    const uint32_t pos0 = (blockIdx.y * 4 + (uint32_t)__builtin_amdgcn_readfirstlane(wave)) * DG_LPW;   // (uniform)
+    if (pos0 < blen + 2) dg_lists_wave(p, t, pos0, blen, K, lane);
 }

@@ -58,8 +58,10 @@ typedef enum dagcon_status {
 #define DAGCON_FLAG_STOP_AFTER_MERGE 4u /* debug: stop after mergeNodes */
 #define DAGCON_FLAG_DEBUG_RESWEEP 16u   /* debug: treat the segmented bestPath sweep as inexact, so that
                                            every target takes the one-piece re-sweep (tests only) */
+#define DAGCON_FLAG_LOCAL_ALIGN 32u    /* dagcon_align / dagcon_consensus_pre align local ends (see dagcon_align):
+                                          read ends that do not align stay out of the alignment */
 #define DAGCON_FLAGS_ALL (DAGCON_FLAG_RAW_ALIGNMENTS | DAGCON_FLAG_STOP_AFTER_BUILD | \
-                          DAGCON_FLAG_STOP_AFTER_MERGE | DAGCON_FLAG_DEBUG_RESWEEP)
+                          DAGCON_FLAG_STOP_AFTER_MERGE | DAGCON_FLAG_DEBUG_RESWEEP | DAGCON_FLAG_LOCAL_ALIGN)
                                         /* dagcon_create refuses any other bit (DAGCON_ERR_UNSUPPORTED) */
 
 /* Mirrors ProgramOpts (src/cpp/ProgramOpts.hpp:8-36) for this path. */
@@ -195,11 +197,27 @@ int dagcon_normalize(dagcon_ctx *ctx, uint32_t n, const uint32_t *aln_start,
  * UNALIGNED sequences, as the .pre format carries them (Alignment.cpp:82-112), on the device.
  * Pair a is q_blob[q_off[a] .. +q_len[a]) against t_blob[t_off[a] .. +t_len[a]).  The aligned strings
  * (equal lengths, '-' for gaps) are written to qaln / taln at out_off[a] (room for q_len[a] + t_len[a]
- * columns each), their length to aln_len[a].  The alignment is global: in the terms of
+ * columns each), their length to aln_len[a].  By default the alignment is global: in the terms of
  * SimpleAligner.cpp:52-53 GenomicTBegin() = 0 and GenomicTEnd() = t_len[a]; the caller applies
  * SimpleAligner.cpp:51-62 (start / end / reverse complement) itself.
  * blasr_libcpp is not in the reference tree: this stage is pinned to the reference only by its one
  * known-answer test (test/cpp/SimpleAlignerTest.cpp:8-21); everything else is parity-unpinned.
+ *
+ * Local ends (a context created with DAGCON_FLAG_LOCAL_ALIGN), the reference's SDPAlign(..., Local) in this
+ * build's own definition, pinned by the same one known-answer test (which it reproduces with ends 0, 61, 0, 61)
+ * and unpinned beyond it.  Same scores, same bands and passes; only the ends change:
+ *   - every cell is computed as above (diagonal, insertion, deletion, each only when strictly better); a score
+ *     above 0 becomes 0 with "the alignment starts here", so do all cells of row 0;
+ *   - the alignment ends at the cell with the smallest score over all rows of the band, a tie going to the larger
+ *     i, then the larger j; no cell below 0: no local alignment;
+ *   - it runs back from there to a start cell, giving the half-open ends q[q_begin, q_end) and t[t_begin, t_end)
+ *     (dagcon_align_ends); the aligned strings cover only those, as CreateAlignmentStrings does;
+ *   - a pass stands unless its path comes within 8 cells of an edge of its band or it finds no local alignment;
+ *     a pair the last pass finds none for comes back with length 0 and ends 0, 0, 0, 0 and counts in
+ *     dagcon_align_dropped.
+ * The band is centred as for the global alignment (on j = i * t_len / q_len), so the local ends are found inside it:
+ * flanks that move the aligned core off that diagonal by more than the band's half-width put it out of reach, as
+ * they do for the global alignment.
  */
 int dagcon_align(dagcon_ctx *ctx, uint32_t n, const uint64_t *q_off, const uint32_t *q_len,
                  const uint64_t *t_off, const uint32_t *t_len, const char *q_blob, uint64_t q_bytes,
@@ -236,7 +254,12 @@ int dagcon_align_panels(dagcon_ctx *ctx, uint32_t n,
  * re-aligned as by dagcon_align, start / end / strand handled as SimpleAligner.cpp:51-62 does (start = tstart,
  * end = start + t_len; '-': start = tlen - end and both strings reverse-complemented; start += 1), then
  * filtered, normalised, trimmed and threaded as by dagcon_consensus.  The aligned strings stay on the device.
- * Same parity statement as dagcon_align.
+ * Same parity statement as dagcon_align.  With DAGCON_FLAG_LOCAL_ALIGN: start = tstart + t_begin, end =
+ * tstart + t_end, then the same '-' and += 1 steps.  This reads SimpleAligner.cpp:53's GenomicTEnd() as the aligned
+ * target span (t_end - t_begin) added to the start :52 already moved, a reading blasr's Alignment (not in the tree)
+ * cannot confirm; for global alignments and for the known-answer test it agrees with reading it as an absolute end.
+ * A '-' record then lies on the forward backbone exactly where its aligned target bases do.  Records without a
+ * local alignment (length 0) fall to the min_len filter.
  */
 typedef struct dagcon_pre_batch {
     uint32_t n_targets;
@@ -286,10 +309,18 @@ int dagcon_debug_counters(dagcon_ctx *ctx, unsigned long long *out8);
 /* Records of the last dagcon_align / dagcon_consensus_pre on this context whose corners the widest band could not
  * connect (sequences of very different lengths, indels of hundreds of bases): their alignment has length 0 and the
  * min_len filter then drops them, where the reference's SDPAlign + GuidedAlign (SimpleAligner.cpp:35-48) always
- * returns something.  After dagcon_align_panels: the pairs it did not align because a panel was larger than
+ * returns something.  On a DAGCON_FLAG_LOCAL_ALIGN context: the pairs without a local alignment in the widest band
+ * (no cell scores below 0).  After dagcon_align_panels: the pairs it did not align because a panel was larger than
  * DAGCON_PANEL_MAX_SIDE (length 0 as well).  The calls succeed; a caller that cares asks here (the pbdagcon host
  * warns on stderr, dazcon --trace-panels aligns those pairs again with dagcon_align). */
 uint32_t dagcon_align_dropped(dagcon_ctx *ctx);
+
+/* The ends of the last dagcon_align / dagcon_consensus_pre on this context, pair by pair: the aligned strings cover
+ * q[q_begin, q_end) and t[t_begin, t_end) of the pair's own sequences.  n must be that call's pair count
+ * (DAGCON_ERR_INVALID_ARG otherwise).  Without DAGCON_FLAG_LOCAL_ALIGN: 0, q_len, 0, t_len for aligned pairs; both
+ * modes: 0, 0, 0, 0 for pairs left unaligned. */
+int dagcon_align_ends(dagcon_ctx *ctx, uint32_t n, uint32_t *q_begin, uint32_t *q_end, uint32_t *t_begin,
+                      uint32_t *t_end);
 
 /* Host arithmetic only (no device, no context): the pieces dagcon_upload would cut the merge and bestPath
  * sweeps of a batch of this shape into -- out4 = {pieces per target (merge), shortest stretch worth a

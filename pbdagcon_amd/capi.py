@@ -23,6 +23,7 @@ FLAG_RAW_ALIGNMENTS = 1
 FLAG_STOP_AFTER_BUILD = 2
 FLAG_STOP_AFTER_MERGE = 4
 FLAG_DEBUG_RESWEEP = 16
+FLAG_LOCAL_ALIGN = 32
 MAX_COVERAGE = 4094
 
 EXPORTS = [
@@ -31,6 +32,7 @@ EXPORTS = [
     "dagcon_fetch", "dagcon_get_timings", "dagcon_normalize", "dagcon_debug_graph",
     "dagcon_debug_counters", "dagcon_host_alloc", "dagcon_host_free", "dagcon_align",
     "dagcon_consensus_pre", "dagcon_debug_plan", "dagcon_align_dropped", "dagcon_align_panels",
+    "dagcon_align_ends",
 ]
 ABI_VERSION = 2
 
@@ -122,6 +124,7 @@ def load() -> C.CDLL:
                                       vp, vp, vp, vp, vp]
     L.dagcon_align_dropped.argtypes = [vp]
     L.dagcon_align_dropped.restype = C.c_uint32
+    L.dagcon_align_ends.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
     L.dagcon_host_free.restype = None
@@ -221,6 +224,7 @@ class Context:
         self._keep = None
         self._pinned = []
         self.target_status = None      # per-target dagcon_status of the last fetch (ABI 2)
+        self._align_n = 0              # pairs of the last align / consensus_pre (align_ends)
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
@@ -336,6 +340,7 @@ class Context:
     def align(self, pairs):
         """pairs = [(qseq, tseq)] of unaligned sequences -> [(qaln, taln)] (the -a stage, SimpleAligner.cpp:25-63)."""
         n = len(pairs)
+        self._align_n = n
         if n == 0:
             return []
         ql = np.array([len(q) for q, _ in pairs], dtype=np.uint32)
@@ -387,6 +392,15 @@ class Context:
                 for a in range(n)]
         return alns, [dist[int(pb[a]):int(pb[a + 1])].tolist() for a in range(n)]
 
+    def align_ends(self):
+        """[(q_begin, q_end, t_begin, t_end)] of the last align / consensus_pre (dagcon_align_ends): the aligned strings
+        cover q[q_begin:q_end] and t[t_begin:t_end].  Local with FLAG_LOCAL_ALIGN, else the whole of both."""
+        n = self._align_n
+        e = np.zeros((4, max(n, 1)), np.uint32)
+        self._chk(self.L.dagcon_align_ends(self.h, n, e[0].ctypes.data, e[1].ctypes.data, e[2].ctypes.data,
+                                           e[3].ctypes.data))
+        return [tuple(int(x) for x in e[:, a]) for a in range(n)]
+
     def align_dropped(self):
         """Pairs the last align / align_panels / consensus_pre left unaligned (dagcon_align_dropped)."""
         return int(self.L.dagcon_align_dropped(self.h))
@@ -396,6 +410,7 @@ class Context:
         -> per target [(range0, range1, seq_bytes)] (dagcon_consensus_pre: main.cpp:117-145 with -a)."""
         recs = [r for _, rs in targets for r in rs]
         n = len(recs)
+        self._align_n = n
         tlen = np.array([t for t, _ in targets], dtype=np.uint32)
         begin = np.zeros(len(targets) + 1, np.uint64)
         begin[1:] = np.cumsum([len(rs) for _, rs in targets], dtype=np.uint64)

@@ -95,6 +95,8 @@ struct Ctx {
     uint32_t T = 0, A = 0;
     int bp_lane = 1, bl_stk = -1;                  // full-span bestPath: a row of eight lanes per piece (k_bp_sweep_l; DAGCON_BP_LANE=0: a wave per piece, k_bp_sweep; 2: rows whatever the batch size); DAGCON_BP_LANE_STACK: test knob
     uint32_t align_dropped = 0;                    // records of the last dagcon_align / dagcon_consensus_pre the band could not align
+    uint32_t align_n = 0;                          // pairs of the last dagcon_align / dagcon_consensus_pre
+    std::vector<uint32_t> h_ends;                  // their ends (dagcon_align_ends): q_begin, q_end, t_begin, t_end per pair
     int poison = 0;                                // DAGCON_POISON (tests): arenas nobody clears are filled with 0xEE bytes before every run (bits 1, 2, 4); 8: every buffer the kernels fill
     int fold = 1;                                  // duplicate insertion chains folded by k_emit (DAGCON_FOLD=0: never)
     int merge_q = 1, use_q = 0;                    // k_merge_q: eight segments per wave (DAGCON_MERGE_Q=0: never); this batch
@@ -124,7 +126,7 @@ struct Ctx {
     DevBuf d_matA, d_matD, d_matC, d_cov, d_gcount, d_gbase, d_bid;
     DevBuf d_nodes, d_best, d_queue, d_score, d_cns_tmp, d_bp_tt, d_score_b;
     DevBuf d_pool, d_stk, d_cuts, d_cuts_bp, d_bp_stat, d_bp_len, d_worklist, d_rd, d_pro_state, d_sh_cnt, d_seg_done, d_wl_first, d_queue0, d_bp_end, d_bp_ab, d_defer, d_cns_tmp0;
-    DevBuf d_al[14];                                // dagcon_align: blobs, offsets, outputs, directions, launch order, widths
+    DevBuf d_al[15];                                // dagcon_align: blobs, offsets, outputs, directions, launch order, widths, ends
     DevBuf d_pn[18];                                // dagcon_align_panels: blobs, panels, scratch, outputs, launch order
     DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
 
@@ -1011,11 +1013,28 @@ int dagcon_normalize(dagcon_ctx *ctx, uint32_t n, const uint32_t *aln_start, con
     return r;
 }
 
-// the -a stage on the device: aligned strings left in c->d_al[7] / [8] at out_off[a], their lengths in aln_len (host)
+extern "C++" {
+template <bool LOCAL>
+static void launch_align_band(uint32_t cells, uint32_t nk, hipStream_t s, const DgAlignParams &ap) {
+    switch (cells) {
+        case 2: hipLaunchKernelGGL((k_align_band<2, LOCAL>), dim3(nk), dim3(64), 0, s, ap); break;
+        case 4: hipLaunchKernelGGL((k_align_band<4, LOCAL>), dim3(nk), dim3(64), 0, s, ap); break;
+        case 6: hipLaunchKernelGGL((k_align_band<6, LOCAL>), dim3(nk), dim3(64), 0, s, ap); break;
+        case 8: hipLaunchKernelGGL((k_align_band<8, LOCAL>), dim3(nk), dim3(64), 0, s, ap); break;
+        case 12: hipLaunchKernelGGL((k_align_band<12, LOCAL>), dim3(nk), dim3(64), 0, s, ap); break;
+        default: hipLaunchKernelGGL((k_align_band<16, LOCAL>), dim3(nk), dim3(64), 0, s, ap); break;
+    }
+}
+}
+
+// the -a stage on the device: aligned strings left in c->d_al[7] / [8] at out_off[a], their lengths in aln_len (host),
+// the ends of every pair in c->h_ends (DAGCON_FLAG_LOCAL_ALIGN: the local-end instances of the kernels)
 static int align_device(Ctx *c, uint32_t n, const uint64_t *q_off, const uint32_t *q_len,
                         const uint64_t *t_off, const uint32_t *t_len, const char *q_blob, uint64_t q_bytes,
                         const char *t_blob, uint64_t t_bytes, const uint64_t *out_off, uint32_t *aln_len, uint64_t *out_bytes_ret) {
     HIPCHK(c, hipSetDevice(c->device));
+    const bool local = (c->opts.flags & DAGCON_FLAG_LOCAL_ALIGN) != 0;
+    c->align_n = 0;
     uint64_t out_bytes = 0;
     std::vector<uint64_t> dir_off(n);
     for (uint32_t a = 0; a < n; a++) {
@@ -1030,6 +1049,8 @@ static int align_device(Ctx *c, uint32_t n, const uint64_t *q_off, const uint32_
     ENSURE(c, dqo, (size_t)n * 8); ENSURE(c, dto, (size_t)n * 8); ENSURE(c, dql, (size_t)n * 4); ENSURE(c, dtl, (size_t)n * 4);
     ENSURE(c, doo, (size_t)n * 8); ENSURE(c, dqa, out_bytes); ENSURE(c, dta, out_bytes); ENSURE(c, dlen, (size_t)n * 4);
     ENSURE(c, ddo, (size_t)n * 8);
+    DevBuf &dend = c->d_al[14];
+    if (local) ENSURE(c, dend, (size_t)n * 16);
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(dq.p, q_blob, q_bytes, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(dt.p, t_blob, t_bytes, hipMemcpyHostToDevice, s));
@@ -1066,6 +1087,7 @@ static int align_device(Ctx *c, uint32_t n, const uint64_t *q_off, const uint32_
     ap.q_len = (const uint32_t *)dql.p; ap.t_len = (const uint32_t *)dtl.p;
     ap.out_off = (const uint64_t *)doo.p; ap.qaln = (uint8_t *)dqa.p; ap.taln = (uint8_t *)dta.p;
     ap.aln_len = (uint32_t *)dlen.p; ap.dir_off = (const uint64_t *)ddo.p; ap.halfw = (const uint32_t *)dhw.p;
+    ap.ends = local ? (uint32_t *)dend.p : nullptr;
     // the band that follows the alignment first (k_align_adapt): every pair long enough for a static band wider than it
     {
         std::vector<uint32_t> ad, rest;
@@ -1093,7 +1115,8 @@ static int align_device(Ctx *c, uint32_t n, const uint64_t *q_off, const uint32_
             HIPCHK(c, hipMemcpyAsync(ddo.p, dir_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
             HIPCHK(c, hipMemcpyAsync((uint32_t *)didx.p + first, ad.data() + first, cnt * 4, hipMemcpyHostToDevice, s));
             ap.idx = (const uint32_t *)didx.p + first; ap.n = (uint32_t)cnt; ap.first_pass = 1u;
-            hipLaunchKernelGGL(k_align_adapt, dim3((uint32_t)cnt), dim3(64), 0, s, ap);
+            if (local) hipLaunchKernelGGL(k_align_adapt<true>, dim3((uint32_t)cnt), dim3(64), 0, s, ap);
+            else hipLaunchKernelGGL(k_align_adapt<false>, dim3((uint32_t)cnt), dim3(64), 0, s, ap);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(s));
             if (t_dbg) {
@@ -1148,14 +1171,8 @@ static int align_device(Ctx *c, uint32_t n, const uint64_t *q_off, const uint32_
                                      [&](uint32_t x, uint32_t y) { return q_len[x] > q_len[y]; });
                     HIPCHK(c, hipMemcpyAsync((uint32_t *)didx.p + first + k0, order.data() + first + k0, (size_t)nk * 4, hipMemcpyHostToDevice, s));
                     ap.idx = (const uint32_t *)didx.p + first + k0; ap.n = nk; ap.first_pass = fin ? 0u : 1u;
-                    switch (kinds[k]) {
-                        case 2: hipLaunchKernelGGL(k_align_band<2>, dim3(nk), dim3(64), 0, s, ap); break;
-                        case 4: hipLaunchKernelGGL(k_align_band<4>, dim3(nk), dim3(64), 0, s, ap); break;
-                        case 6: hipLaunchKernelGGL(k_align_band<6>, dim3(nk), dim3(64), 0, s, ap); break;
-                        case 8: hipLaunchKernelGGL(k_align_band<8>, dim3(nk), dim3(64), 0, s, ap); break;
-                        case 12: hipLaunchKernelGGL(k_align_band<12>, dim3(nk), dim3(64), 0, s, ap); break;
-                        default: hipLaunchKernelGGL(k_align_band<16>, dim3(nk), dim3(64), 0, s, ap); break;
-                    }
+                    if (local) launch_align_band<true>(kinds[k], nk, s, ap);
+                    else launch_align_band<false>(kinds[k], nk, s, ap);
                     HIPCHK(c, hipGetLastError());
                 }
             }
@@ -1183,6 +1200,15 @@ static int align_device(Ctx *c, uint32_t n, const uint64_t *q_off, const uint32_
         // length 0, and the record then falls to the min_len filter -- the reference's SDPAlign always returns something
         dropped += aln_len[a] == 0 && (q_len[a] || t_len[a]);
     }
+    c->h_ends.resize((size_t)n * 4);
+    if (local) HIPCHK(c, d2h(c, c->h_ends.data(), dend.p, (size_t)n * 16));    // (16 B a pair; the strings stay)
+    else
+        for (uint32_t a = 0; a < n; a++) {                // global: the whole of both, or nothing
+            const bool ok = aln_len[a] != 0;
+            uint32_t *e = &c->h_ends[(size_t)a * 4];
+            e[0] = 0; e[1] = ok ? q_len[a] : 0u; e[2] = 0; e[3] = ok ? t_len[a] : 0u;
+        }
+    c->align_n = n;
     c->align_dropped = dropped;                   // (the call succeeds: dagcon_align_dropped reports them)
     *out_bytes_ret = out_bytes;
     return DAGCON_OK;
@@ -1194,6 +1220,7 @@ int dagcon_align(dagcon_ctx *ctx, uint32_t n, const uint64_t *q_off, const uint3
                  uint32_t *aln_len) {
     if (!ctx) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    c->align_n = 0;
     if (n == 0) return DAGCON_OK;
     if (!q_off || !q_len || !t_off || !t_len || !q_blob || !t_blob || !out_off || !qaln || !taln || !aln_len)
         return fail(c, DAGCON_ERR_INVALID_ARG, "NULL argument");
@@ -1202,6 +1229,18 @@ int dagcon_align(dagcon_ctx *ctx, uint32_t n, const uint64_t *q_off, const uint3
     if (r != DAGCON_OK) return r;
     HIPCHK(c, d2h(c, qaln, c->d_al[7].p, out_bytes));
     HIPCHK(c, d2h(c, taln, c->d_al[8].p, out_bytes));
+    return DAGCON_OK;
+}
+
+int dagcon_align_ends(dagcon_ctx *ctx, uint32_t n, uint32_t *q_begin, uint32_t *q_end, uint32_t *t_begin, uint32_t *t_end) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (n != c->align_n) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_align_ends: %u pairs asked, the last alignment had %u", n, c->align_n);
+    if (n && (!q_begin || !q_end || !t_begin || !t_end)) return fail(c, DAGCON_ERR_INVALID_ARG, "NULL argument");
+    for (uint32_t a = 0; a < n; a++) {
+        const uint32_t *e = &c->h_ends[(size_t)a * 4];
+        q_begin[a] = e[0]; q_end[a] = e[1]; t_begin[a] = e[2]; t_end[a] = e[3];
+    }
     return DAGCON_OK;
 }
 
@@ -1345,6 +1384,7 @@ int dagcon_consensus_pre(dagcon_ctx *ctx, const dagcon_pre_batch *b, dagcon_resu
     const uint32_t n = (uint32_t)n64;
     if (n && (!b->tstart || !b->strand || !b->q_off || !b->q_len || !b->t_off || !b->t_len || !b->q_blob || !b->t_blob))
         return fail(c, DAGCON_ERR_INVALID_ARG, "record arrays are NULL");
+    c->align_n = 0;
     std::vector<uint64_t> out_off(n);
     std::vector<uint32_t> alen(n, 0), start(n);
     uint64_t tot = 0;
@@ -1355,13 +1395,16 @@ int dagcon_consensus_pre(dagcon_ctx *ctx, const dagcon_pre_batch *b, dagcon_resu
                              out_off.data(), alen.data(), &out_bytes);
         if (r != DAGCON_OK) return r;
     }
-    // SimpleAligner.cpp:51-62 (the alignment is global: GenomicTBegin() = 0, GenomicTEnd() = |tseq|)
+    // SimpleAligner.cpp:51-62: start = tstart + GenomicTBegin(), end = start + the aligned target span (global:
+    // GenomicTBegin() = 0, the span |tseq|; DAGCON_FLAG_LOCAL_ALIGN: t_begin, t_end - t_begin)
+    const bool local = (c->opts.flags & DAGCON_FLAG_LOCAL_ALIGN) != 0;
     std::vector<uint32_t> rc_list;
     for (uint32_t g = 0; g < T; g++) {
         if (b->rec_begin[g + 1] < b->rec_begin[g] || b->rec_begin[g + 1] > n64) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin not monotone at target %u", g);
         for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
             uint32_t st = b->tstart[a];
-            const uint32_t en = st + b->t_len[a];
+            uint32_t en = st + b->t_len[a];
+            if (local) { en = st + c->h_ends[a * 4 + 3]; st += c->h_ends[a * 4 + 2]; }
             if (b->strand[a] == '-') { st = b->tlen[g] - en; if (alen[a]) rc_list.push_back((uint32_t)a); }
             start[a] = st + 1u;
         }

@@ -15,7 +15,8 @@
 //     itself is the GPU's), -j 1 does not deadlock (Q2);
 //   * -a (.pre input, every record re-aligned first: main.cpp:127-128, 243-246) runs this build's own
 //     banded aligner on the GPU (dagcon_align): blasr_libcpp is absent, the stage is pinned to the
-//     reference by its one known-answer test only (test/cpp/SimpleAlignerTest.cpp:8-21);
+//     reference by its one known-answer test only (test/cpp/SimpleAlignerTest.cpp:8-21); global by
+//     default, local ends with --local (DAGCON_FLAG_LOCAL_ALIGN, the reference's SDPAlign(..., Local));
 //   * blank lines are skipped (the reference duplicates the previous record, Q9);
 //   * a missing input file is an error on stderr, exit 1 (the reference is silent, Q11).
 #include <algorithm>
@@ -43,6 +44,7 @@ namespace {
 struct Opts {
     unsigned threads = 4, min_cov = 6, min_len = 500, trim = 50;
     bool align = false, verbose = false, dump = false;
+    bool local = false;                // --local (with -a): the first alignment of every record has local ends
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
     int pinned = -1;                   // --pinned 0|1: page-locked blobs (-1: when the input is several batches long)
     unsigned contexts = 0;             // --contexts N: consensus workers per GPU (0: two when the input is several batches long)
@@ -56,7 +58,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -64,8 +66,11 @@ void usage(FILE *f) {
             "  -m, --min-length    minimum alignment / consensus length (default 500)\n"
             "  -t, --trim          trim alignments on either side (default 50)\n"
             "  -a, --align         input is .pre (qid tid strand tlen tstart tend qseq tseq): align the sequences first\n"
-            "                      (this build's own banded GLOBAL aligner on the GPU; the reference's blasr SDPAlign(Local) +\n"
-            "                      GuidedAlign is not in its tree: parity unpinned beyond its one SimpleAligner known-answer test)\n"
+            "                      (this build's own banded aligner on the GPU, global unless --local; the reference's blasr\n"
+            "                      SDPAlign(Local) + GuidedAlign is not in its tree: parity unpinned beyond its one SimpleAligner\n"
+            "                      known-answer test)\n"
+            "  --local             with -a: align local ends, so read ends that do not align stay out of the graph (the record\n"
+            "                      starts at tstart + the first aligned target base); --polish rounds stay global\n"
             "  -v, --verbose       per-target progress on stderr\n"
             "  --polish N          with -a: N more rounds, each with the previous round's consensus as the backbone the reads\n"
             "                      are re-aligned to (README.md:14-15 of the reference: 'the new consensus can be used as a new\n"
@@ -100,6 +105,7 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "-m" || a == "--min-length") { if (!need(&o.min_len)) return 2; }
         else if (a == "-t" || a == "--trim") { if (!need(&o.trim)) return 2; }
         else if (a == "-a" || a == "--align") o.align = true;
+        else if (a == "--local") o.local = true;
         else if (a == "-v" || a == "--verbose") o.verbose = true;
         else if (a == "--dump-parsed") o.dump = true;            // test hook: parser only, no GPU
         else if (a == "--slab-bytes") { unsigned v = 0; if (!need(&v)) return 2; o.slab_bytes = v; }   // test hook
@@ -128,6 +134,7 @@ int parse_args(int argc, char **argv, Opts &o) {
             o.input = a;
         } else { fprintf(stderr, "PARSE ERROR: unknown argument %s\n", a.c_str()); return 2; }
     }
+    if (o.local && !o.align) { fprintf(stderr, "PARSE ERROR: --local needs -a\n"); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
     return 0;
 }
@@ -198,8 +205,9 @@ std::mutex g_tmu;
 double g_t_upload = 0, g_t_run = 0, g_t_fetch = 0;
 double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// one batch through the device; the records go to b.out (main.cpp:141-143), warnings to stderr
-int flush(dagcon_ctx *ctx, Batch &b, const Opts &o, Blob *scratch) {
+// one batch through the device; the records go to b.out (main.cpp:141-143), warnings to stderr.  actx: the context
+// of the first alignment with --polish (a local one with --local: the rounds stay global on ctx)
+int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scratch) {
     if (b.ids.empty()) return 0;
     if (b.begin.back() != b.start.size()) b.begin.push_back(b.start.size());
     dagcon_batch db;
@@ -211,6 +219,7 @@ int flush(dagcon_ctx *ctx, Batch &b, const Opts &o, Blob *scratch) {
     // -a: SimpleAligner on every record first (main.cpp:127-128)
     std::vector<uint64_t> ooff;
     std::vector<uint32_t> alen, nstart;
+    std::vector<uint32_t> e_qb, e_qe, e_tb, e_te;       // -a --polish: the ends of the first alignments
     char *qa = nullptr, *ta = nullptr;                  // -a: the aligned strings, in the worker's page-locked scratch
     dagcon_results r;
     int rc = DAGCON_OK;
@@ -243,22 +252,27 @@ int flush(dagcon_ctx *ctx, Batch &b, const Opts &o, Blob *scratch) {
         if (!scratch[0].resize(tot + 1, ctx) || !scratch[1].resize(tot + 1, ctx)) { fprintf(stderr, "pbdagcon: out of memory\n"); return 1; }
         qa = scratch[0].data(); ta = scratch[1].data();
         const double ta1 = wall();
-        int rc = dagcon_align(ctx, (uint32_t)A, b.off.data(), b.len.data(), b.off2.data(), b.len2.data(), b.q.data(), b.q.size(),
+        int rc = dagcon_align(actx, (uint32_t)A, b.off.data(), b.len.data(), b.off2.data(), b.len2.data(), b.q.data(), b.q.size(),
                               b.t.data(), b.t.size(), ooff.data(), &qa[0], &ta[0], alen.data());
+        if (rc == DAGCON_OK) {
+            e_qb.resize(A); e_qe.resize(A); e_tb.resize(A); e_te.resize(A);
+            rc = dagcon_align_ends(actx, (uint32_t)A, e_qb.data(), e_qe.data(), e_tb.data(), e_te.data());
+        }
         const double ta2 = wall();
         if (g_timing) fprintf(stderr, "pbdagcon timing: -a batch of %zu records: buffers %.3f  dagcon_align %.3f\n", A, ta1 - ta0, ta2 - ta1);
         if (rc != DAGCON_OK) {
-            fprintf(stderr, "pbdagcon: alignment failed (%d): %s\n", rc, dagcon_last_error(ctx));
+            fprintf(stderr, "pbdagcon: alignment failed (%d): %s\n", rc, dagcon_last_error(actx));
             return 1;
         }
-        if (const uint32_t nd = dagcon_align_dropped(ctx))
+        if (const uint32_t nd = dagcon_align_dropped(actx))
             fprintf(stderr, "pbdagcon: warning: %u of %zu records could not be aligned inside the widest band and were dropped\n", nd, A);
         size_t g = 0;
         for (size_t a = 0; a < A; a++) {
             while (b.begin[g + 1] <= a) g++;
-            // SimpleAligner.cpp:51-62 (the alignment is global: GenomicTBegin() = 0, GenomicTEnd() = |tseq|)
-            uint32_t start = b.start[a];
-            const uint32_t end = start + b.len2[a];
+            // SimpleAligner.cpp:51-62: start = tstart + GenomicTBegin(), end = start + the aligned target span (global:
+            // 0 and |tseq|; --local: t_begin and t_end - t_begin, as dagcon_consensus_pre)
+            uint32_t start = b.start[a] + (o.local ? e_tb[a] : 0u);
+            const uint32_t end = o.local ? b.start[a] + e_te[a] : start + b.len2[a];
             if (b.strand[a] == '-') {
                 start = b.tlen[g] - end;
                 std::string tmp(alen[a], 0);
@@ -302,6 +316,8 @@ int flush(dagcon_ctx *ctx, Batch &b, const Opts &o, Blob *scratch) {
         const uint32_t T = db.n_targets;
         const uint32_t pad = 64;
         std::vector<uint32_t> cur_start(A), cur_len(A), cur_qbase(A, 0);   // qbase: the read's base the current alignment begins with
+        if (o.local)                                     // (the read's first aligned base, in the target's orientation)
+            for (size_t a = 0; a < A; a++) cur_qbase[a] = b.strand[a] == '-' ? b.len[a] - e_qe[a] : e_qb[a];
         std::vector<uint64_t> cur_off(A);
         std::string cur_q(qa, db.blob_bytes + 1), cur_t(ta, db.blob_bytes + 1);     // the reads' last alignments, per record
         for (size_t a = 0; a < A; a++) { cur_start[a] = db.aln_start[a]; cur_off[a] = db.aln_off[a]; cur_len[a] = db.aln_len[a]; }
@@ -474,8 +490,15 @@ int main(int argc, char **argv) {
             dopt.min_cov = o.min_cov; dopt.min_len = o.min_len; dopt.trim = o.trim;
             dopt.min_weight = (int32_t)o.min_cov;          // main.cpp:261,279 (quirk Q1)
             dopt.device = worker_dev[w];
+            dopt.flags = o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u;
             const double tc0 = now();
             int rc = dagcon_create(&dopt, &ctx);
+            dagcon_ctx *actx = ctx;                         // --local --polish: the first alignment on a local context of its own
+            if (rc == DAGCON_OK && o.local && o.polish) {
+                dopt.flags = DAGCON_FLAG_LOCAL_ALIGN;
+                rc = dagcon_create(&dopt, &actx);
+                if (rc != DAGCON_OK) { dagcon_destroy(ctx); ctx = nullptr; }
+            }
             if (w == 0) t_create = now() - tc0;
             if (rc != DAGCON_OK) {
                 fprintf(stderr, "pbdagcon: no usable MI355X as device %d (dagcon_create = %d); there is no CPU fallback\n", worker_dev[w], rc);
@@ -495,7 +518,7 @@ int main(int argc, char **argv) {
                     b = work.front(); work.erase(work.begin());
                 }
                 const double tf0 = now();
-                const int st = flush(ctx, *b, o, scratch);
+                const int st = flush(ctx, actx, *b, o, scratch);
                 const double tf = now() - tf0;
                 {
                     std::unique_lock<std::mutex> lk(mu);
@@ -527,6 +550,7 @@ int main(int argc, char **argv) {
                 if (pin_ctx == ctx) pin_ctx = nullptr;
             }
             scratch[0].release(); scratch[1].release();
+            if (actx != ctx) dagcon_destroy(actx);
             dagcon_destroy(ctx);
         });
     }

@@ -12,6 +12,11 @@
 // stand when the path keeps away from their edges: a band that follows the alignment (k_align_adapt), then a static
 // one (dg_align_halfwidth_first).  The tests hold a bit-exact CPU twin of all of it.
 //
+// LOCAL instances (DAGCON_FLAG_LOCAL_ALIGN, include/dagcon.h; SDPAlign(..., Local) in this build's own definition): a
+// score above 0 becomes 0 with direction code 3 ("starts here"; all of row 0 too), the alignment ends at the cell with
+// the smallest score of the band (ties: the later row, then the later cell) and runs back to a code 3; the four ends
+// go to p.ends.  The LOCAL = false instances compute what the global kernels did (same resource report).
+//
 // One wave per alignment, the band of a row in REGISTERS: B = 2 W + 1 cells right-aligned on 64 lanes x C
 // cells (C = 2 .. 16, one kernel instance per C), lane l owning cells l C .. l C + C - 1 with their previous-row
 // scores and their target characters.  When the band's centre moves on by one column, scores and characters
@@ -87,6 +92,7 @@ struct DgAlignParams {
     const uint32_t *halfw;         // per alignment: half-width of the band of this pass
     uint32_t first_pass;           // 1: a path near an edge of the band gives DG_AL_RETRY instead of an alignment
     uint32_t n;
+    uint32_t *ends;                // LOCAL instances: per alignment q_begin, q_end, t_begin, t_end (4 words)
 };
 
 template <int CTRL, int ROW_MASK>
@@ -113,7 +119,7 @@ __device__ __forceinline__ int dg_al_scan_min(int incl) {
     return incl;
 }
 
-template <int C>
+template <int C, bool LOCAL>
 __global__ __launch_bounds__(64) void k_align_band(DgAlignParams p) {
     typedef typename std::conditional<(C <= 8), uint16_t, uint32_t>::type DirT;      // 2 bits per cell
     __shared__ DirT s_dir[DG_AL_ROWS * 64];
@@ -126,6 +132,13 @@ __global__ __launch_bounds__(64) void k_align_band(DgAlignParams p) {
     const uint32_t n = p.q_len[a], m = p.t_len[a];
     const uint8_t *q = p.q + p.q_off[a], *t = p.t + p.t_off[a];
     uint8_t *qo = p.qaln + p.out_off[a], *to = p.taln + p.out_off[a];
+    if constexpr (LOCAL) {
+        if (n == 0 || m == 0) {                             // no cell scores below 0: no local alignment
+            if (lane < 4) p.ends[4ull * a + (uint32_t)lane] = 0u;
+            if (lane == 0) p.aln_len[a] = 0u;
+            return;
+        }
+    }
     if (n == 0 || m == 0) {
         // all gaps, in order: query columns first
         for (uint32_t i = lane; i < n; i += 64) { qo[i] = q[i]; to[i] = '-'; }
@@ -222,7 +235,7 @@ __global__ __launch_bounds__(64) void k_align_band(DgAlignParams p) {
             const int j = jl + c;
             const bool valid = (!EDGE || (uint32_t)j <= m) && kb + c >= off;
             int best;
-            if constexpr (FIRST) best = j == 0 ? 0 : DG_AL_BIG;
+            if constexpr (FIRST) best = !LOCAL && j == 0 ? 0 : DG_AL_BIG;     // (LOCAL: all of row 0 starts)
             else {
                 const int dg = (c == 0 ? left : P[c - 1]) + (T[c] == qc ? DG_AL_MATCH : DG_AL_MISMATCH);
                 const int up = P[c] + DG_AL_INS;
@@ -247,40 +260,81 @@ __global__ __launch_bounds__(64) void k_align_band(DgAlignParams p) {
             // deletion (left) wins only when strictly better than diagonal / insertion
             const bool del = j > 0 && pm < x;
             int sc = del ? pm + DG_AL_DEL * (kb + c) : A[c];
-            const uint32_t d = del ? 2u : (dbits >> c) & 1u;
+            uint32_t d = del ? 2u : (dbits >> c) & 1u;
+            if constexpr (LOCAL) {
+                // above 0: the alignment starts here.  Exact after the running minimum: min(0, min(A, S + 5)) =
+                // min(0, min(A, min(0, S) + 5)), and a clamped cell never feeds a deletion that scores <= 0
+                const bool st = sc > 0;
+                sc = st ? 0 : sc;
+                d = st ? 3u : d;
+            }
             pm = x < pm ? x : pm;
             P[c] = valid ? sc : DG_AL_BIG;
             word |= d << (2 * c);
         }
         dirs[(uint64_t)i * 64ull + (uint64_t)lane] = (DirT)word;
     };
+    // LOCAL: the end cell so far: the smallest score, a later row, then a later cell winning a tie.  Wave-uniform, kept
+    // in lanes 0 / 1 / 2 of one VGPR (score, row, cell): the wide instances have no SGPR to spare for them
+    int bst = 0;
+    auto track = [&](const uint32_t i) {
+        int lmin = P[0];
+#pragma unroll
+        for (int c = 1; c < C; c++) lmin = P[c] < lmin ? P[c] : lmin;
+        const int mn = __builtin_amdgcn_readlane(dg_al_scan_min(lmin), 63);
+        if (mn < 0 && mn <= __builtin_amdgcn_readlane(bst, 0)) {
+            const int L = 63 - __clzll((long long)__ballot(lmin == mn));          // the last lane that has it
+            int hc = 0;
+#pragma unroll
+            for (int c = 0; c < C; c++) hc = P[c] == mn ? c : hc;
+            const int k = L * C + __builtin_amdgcn_readlane(hc, L);
+            bst = lane == 0 ? mn : lane == 1 ? (int)i : lane == 2 ? k : bst;
+        }
+    };
     row(0u, std::true_type{}, std::true_type{});
     for (uint32_t i = 1; i <= n; i++) {
         advance(i);
         if (ci >= W && ci + W <= (int)m) row(i, std::false_type{}, std::false_type{});
         else row(i, std::false_type{}, std::true_type{});
+        if constexpr (LOCAL) track(i);
     }
-    // (n, m) is cell k = W of the last row
-    const int kend = W + off;
-    int fin = DG_AL_BIG;
+    if constexpr (LOCAL) {
+        if (__builtin_amdgcn_readlane(bst, 0) >= 0) {       // no cell below 0: no local alignment in this band
+            if (lane < 4) p.ends[4ull * a + (uint32_t)lane] = 0u;
+            if (lane == 0) p.aln_len[a] = p.first_pass ? DG_AL_RETRY : 0u;
+            return;
+        }
+    } else {
+        // (n, m) is cell k = W of the last row
+        const int kend = W + off;
+        int fin = DG_AL_BIG;
 #pragma unroll
-    for (int c = 0; c < C; c++) if (kend % C == c) fin = P[c];
-    fin = __builtin_amdgcn_readlane(fin, kend / C);
-    if (fin >= DG_AL_LIM) {                                 // the band does not connect (0, 0) with (n, m)
-        if (lane == 0) p.aln_len[a] = p.first_pass ? DG_AL_RETRY : 0u;
-        return;
+        for (int c = 0; c < C; c++) if (kend % C == c) fin = P[c];
+        fin = __builtin_amdgcn_readlane(fin, kend / C);
+        if (fin >= DG_AL_LIM) {                             // the band does not connect (0, 0) with (n, m)
+            if (lane == 0) p.aln_len[a] = p.first_pass ? DG_AL_RETRY : 0u;
+            return;
+        }
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 
-    // ---- walk back from (n, m): uniform, directions through LDS, one code per step ----
+    // ---- walk back from (n, m) (LOCAL: from the end cell, to a code 3): uniform, directions through LDS, one code
+    // per step ----
     uint32_t i = n, j = m, len = 0;
     int wci = (int)m;                                       // c_i of the row the walk is on
     uint32_t wnum = 0;
-    int r0 = (int)n + 1;                                    // rows [r0, ..] are staged
+    if constexpr (LOCAL) {
+        i = (uint32_t)__builtin_amdgcn_readlane(bst, 1);
+        const uint64_t im = (uint64_t)i * m;
+        wci = (int)(im / n); wnum = (uint32_t)(im - (uint64_t)wci * n);
+        j = (uint32_t)(wci - W + __builtin_amdgcn_readlane(bst, 2) - off);
+    }
+    const uint32_t ie = i, je = j;                          // where the alignment ends
+    int r0 = LOCAL ? (int)i + 1 : (int)n + 1;               // rows [r0, ..] are staged
     int codes = 0;
     const uint32_t cap = n + m;
     bool bad = false, near_edge = false;
-    while (i > 0 || j > 0) {
+    while (LOCAL || i > 0 || j > 0) {                      // (LOCAL: to a code 3; every cell of row 0 is one)
         if ((int)i < r0) {
             __syncthreads();
             r0 = (int)i >= DG_AL_ROWS - 1 ? (int)i - (DG_AL_ROWS - 1) : 0;
@@ -292,7 +346,7 @@ __global__ __launch_bounds__(64) void k_align_band(DgAlignParams p) {
         near_edge |= k - off < DG_AL_MARGIN || k - off > B - 1 - DG_AL_MARGIN;
         const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_dir[((int)i - r0) * 64 + k / C]);
         const uint32_t d = (w >> (2 * (k % C))) & 3u;
-        if (d == 3u) { bad = true; break; }
+        if (d == 3u) { if constexpr (!LOCAL) bad = true; break; }
         codes = (uint32_t)lane == (len & 63u) ? (int)d : codes;
         len++;
         if ((len & 63u) == 0) path[len - 64u + (uint32_t)lane] = (uint8_t)codes;
@@ -307,13 +361,20 @@ __global__ __launch_bounds__(64) void k_align_band(DgAlignParams p) {
             j--;
         }
     }
-    if (bad) { if (lane == 0) p.aln_len[a] = p.first_pass ? DG_AL_RETRY : 0u; return; }
+    if (bad) {
+        if constexpr (LOCAL) { if (lane < 4) p.ends[4ull * a + (uint32_t)lane] = 0u; }
+        if (lane == 0) p.aln_len[a] = p.first_pass ? DG_AL_RETRY : 0u;
+        return;
+    }
     if (near_edge && p.first_pass) { if (lane == 0) p.aln_len[a] = DG_AL_RETRY; return; }
+    if constexpr (LOCAL) {
+        if (lane < 4) p.ends[4ull * a + (uint32_t)lane] = lane == 0 ? i : lane == 1 ? ie : lane == 2 ? j : je;
+    }
     if ((uint32_t)lane < (len & 63u)) path[(len & ~63u) + (uint32_t)lane] = (uint8_t)codes;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __syncthreads();
     // ---- the characters, 64 steps at a time: step s consumed q[i_s - 1] and / or t[j_s - 1] ----
-    uint32_t iq = n, jt = m;
+    uint32_t iq = LOCAL ? ie : n, jt = LOCAL ? je : m;
     for (uint32_t s0 = 0; s0 < len; s0 += 64) {
         const uint32_t s = s0 + (uint32_t)lane;
         const bool on = s < len;
@@ -343,6 +404,7 @@ __global__ __launch_bounds__(64) void k_align_band(DgAlignParams p) {
 __host__ __device__ inline uint64_t dg_align_rows_adapt(uint32_t qlen, uint32_t tlen) {
     return (((uint64_t)qlen + 1ull) * 64ull + 255ull) / 256ull + ((uint64_t)qlen + tlen + 255ull) / 256ull + 1ull;
 }
+template <bool LOCAL>
 __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
     constexpr int C = 2, W = DG_AL_WA, B = 2 * W + 1, off = 64 * C - B;
     __shared__ uint8_t s_dir[DG_AL_ROWS * 64];
@@ -352,6 +414,13 @@ __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
     const uint32_t n = p.q_len[a], m = p.t_len[a];
     const uint8_t *q = p.q + p.q_off[a], *t = p.t + p.t_off[a];
     uint8_t *qo = p.qaln + p.out_off[a], *to = p.taln + p.out_off[a];
+    if constexpr (LOCAL) {
+        if (n == 0 || m == 0) {
+            if (lane < 4) p.ends[4ull * a + (uint32_t)lane] = 0u;
+            if (lane == 0) p.aln_len[a] = 0u;
+            return;
+        }
+    }
     if (n == 0 || m == 0) {
         for (uint32_t i = lane; i < n; i += 64) { qo[i] = q[i]; to[i] = '-'; }
         for (uint32_t j = lane; j < m; j += 64) { qo[n + j] = '-'; to[n + j] = t[j]; }
@@ -381,6 +450,14 @@ __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
     bool lost = false;
     const int kb = lane * C;
     uint32_t shift = 0;
+    // LOCAL: the end cell so far (wave-uniform): score, row, cell, the row's lo; a later row, then a later cell wins a tie
+    int bs = 0, bi = 0, bk = 0, blo = 0;
+    auto track = [&](const uint32_t i, const int best, const unsigned long long b0, const unsigned long long b1) {
+        if (best < 0 && best <= bs) {
+            const int h0 = b0 ? 2 * (63 - __clzll((long long)b0)) : -1, h1 = b1 ? 2 * (63 - __clzll((long long)b1)) + 1 : -1;
+            bs = best; bi = (int)i; bk = h0 > h1 ? h0 : h1; blo = lo;
+        }
+    };
     // the band moves on to row i: where the previous row's best cell is (its first one) says how far
     auto advance = [&](const uint32_t i) {
         {
@@ -388,6 +465,7 @@ __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
             const int best = __builtin_amdgcn_readlane(mn, 63);
             if (best >= DG_AL_LIM) { lost = true; return; }
             const unsigned long long b0 = __ballot(P[0] == best), b1 = __ballot(P[1] == best);
+            if constexpr (LOCAL) track(i - 1u, best, b0, b1);
             const int k0 = b0 ? 2 * (__ffsll((long long)b0) - 1) : 1 << 20, k1 = b1 ? 2 * (__ffsll((long long)b1) - 1) + 1 : 1 << 20;
             const int am = (k0 < k1 ? k0 : k1) - off;
             int sft = am + 1 - W;
@@ -430,7 +508,7 @@ __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
             const int j = jl + c;
             const bool valid = (!EDGE || (uint32_t)j <= m) && kb + c >= off;
             int best;
-            if constexpr (FIRST) best = j == 0 ? 0 : DG_AL_BIG;
+            if constexpr (FIRST) best = !LOCAL && j == 0 ? 0 : DG_AL_BIG;     // (LOCAL: all of row 0 starts)
             else {
                 const int dg = (c == 0 ? left : P[c - 1]) + (T[c] == qc ? DG_AL_MATCH : DG_AL_MISMATCH);
                 const int up = P[c] + DG_AL_INS;
@@ -452,8 +530,13 @@ __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
             const bool valid = (!EDGE || (uint32_t)j <= m) && kb + c >= off;
             const int x = A[c] - DG_AL_DEL * (kb + c);
             const bool del = j > 0 && pm < x;
-            const int sc = del ? pm + DG_AL_DEL * (kb + c) : A[c];
-            const uint32_t d = del ? 2u : (dbits >> c) & 1u;
+            int sc = del ? pm + DG_AL_DEL * (kb + c) : A[c];
+            uint32_t d = del ? 2u : (dbits >> c) & 1u;
+            if constexpr (LOCAL) {                          // (as in k_align_band)
+                const bool st = sc > 0;
+                sc = st ? 0 : sc;
+                d = st ? 3u : d;
+            }
             pm = x < pm ? x : pm;
             P[c] = valid ? sc : DG_AL_BIG;
             word |= d << (2 * c);
@@ -468,22 +551,32 @@ __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
         if (lo >= 0 && lo + B - 1 <= (int)m) row(i, std::false_type{}, std::false_type{});
         else row(i, std::false_type{}, std::true_type{});
     }
-    // (n, m) must be a reachable cell of the last row
-    const int kend = (int)m - lo + off;
-    bool fail = lost || kend < off || kend >= 64 * C;
-    if (!fail) {
-        int fin = (kend & 1) ? P[1] : P[0];
-        fin = __builtin_amdgcn_readlane(fin, kend / C);
-        fail = fin >= DG_AL_LIM;
+    bool fail;
+    if constexpr (LOCAL) {
+        // the last row (every row has a valid cell: the band never leaves t); no cell below 0: no local alignment
+        const int best = __builtin_amdgcn_readlane(dg_al_scan_min(P[0] < P[1] ? P[0] : P[1]), 63);
+        track(n, best, __ballot(P[0] == best), __ballot(P[1] == best));
+        fail = lost || bs >= 0;
+    } else {
+        // (n, m) must be a reachable cell of the last row
+        const int kend = (int)m - lo + off;
+        fail = lost || kend < off || kend >= 64 * C;
+        if (!fail) {
+            int fin = (kend & 1) ? P[1] : P[0];
+            fin = __builtin_amdgcn_readlane(fin, kend / C);
+            fail = fin >= DG_AL_LIM;
+        }
     }
     if (fail) { if (lane == 0) p.aln_len[a] = DG_AL_RETRY; return; }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    // ---- walk back (uniform), rows of directions through LDS ----
+    // ---- walk back (uniform), rows of directions through LDS; LOCAL: from the end cell to a code 3 ----
     uint32_t i = n, j = m, len = 0;
-    int r0 = (int)n + 1, codes = 0;
+    if constexpr (LOCAL) { i = (uint32_t)bi; lo = blo; j = (uint32_t)(blo + bk - off); }
+    const uint32_t ie = i, je = j;
+    int r0 = LOCAL ? (int)i + 1 : (int)n + 1, codes = 0;
     const uint32_t cap = n + m;
     bool bad = false;
-    while (i > 0 || j > 0) {
+    while (LOCAL || i > 0 || j > 0) {                      // (LOCAL: to a code 3; every cell of row 0 is one)
         if ((int)i < r0) {
             __syncthreads();
             r0 = (int)i >= DG_AL_ROWS - 1 ? (int)i - (DG_AL_ROWS - 1) : 0;
@@ -494,7 +587,7 @@ __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
         if (k < off + DG_AL_MARGIN || k > off + B - 1 - DG_AL_MARGIN || len >= cap) { bad = true; break; }
         const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_dir[((int)i - r0) * 64 + k / C]);
         const uint32_t d = (w >> (2 * (k % C))) & 3u;
-        if (d == 3u) { bad = true; break; }
+        if (d == 3u) { if constexpr (!LOCAL) bad = true; break; }
         codes = (uint32_t)lane == (len & 63u) ? (int)d : codes;
         len++;
         if ((len & 63u) == 0) path[len - 64u + (uint32_t)lane] = (uint8_t)codes;
@@ -509,10 +602,13 @@ __global__ __launch_bounds__(64) void k_align_adapt(DgAlignParams p) {
         }
     }
     if (bad) { if (lane == 0) p.aln_len[a] = DG_AL_RETRY; return; }
+    if constexpr (LOCAL) {
+        if (lane < 4) p.ends[4ull * a + (uint32_t)lane] = lane == 0 ? i : lane == 1 ? ie : lane == 2 ? j : je;
+    }
     if ((uint32_t)lane < (len & 63u)) path[(len & ~63u) + (uint32_t)lane] = (uint8_t)codes;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __syncthreads();
-    uint32_t iq = n, jt = m;
+    uint32_t iq = LOCAL ? ie : n, jt = LOCAL ? je : m;
     for (uint32_t s0 = 0; s0 < len; s0 += 64) {
         const uint32_t s = s0 + (uint32_t)lane;
         const bool on = s < len;

@@ -322,6 +322,33 @@ uint32_t dagcon_align_dropped(dagcon_ctx *ctx);
 int dagcon_align_ends(dagcon_ctx *ctx, uint32_t n, uint32_t *q_begin, uint32_t *q_end, uint32_t *t_begin,
                       uint32_t *t_end);
 
+/*
+ * q-sense's read placement (the step q-sense.py has blasr do): for n_pairs (query q, target t) pairs over a set of
+ * sequences, each pair's strand, its support on each strand and the span of t that q covers, by k-mer votes binned
+ * by diagonal.  This build's own definition, parity unpinned: the reference delegates this to blasr.  Sequence s is
+ * blob[seq_off[s] .. + seq_len[s]); pair a is q = pair_q[a] against t = pair_t[a].  Exact integer arithmetic
+ * (tests/place_twin.py reproduces it bit for bit):
+ *   - codes: A/a 0, C/c 1, G/g 2, T/t 3, any other byte invalid.  The k-mer at position i of x is valid if its k bytes
+ *     are; its value packs 2 bits a base, the first base in the most significant bits.  8 <= k <= 16 (12 is the
+ *     default of qsense).  rc(x) reverses x and complements A<->T, C<->G;
+ *   - repeat mask: a k-mer value that occurs more than max_occ times in t is ignored (1 <= max_occ <= 8; qsense: 4);
+ *   - votes: for strand '+' x = q, for '-' x = rc(q).  Every (i, j) where x's k-mer at i equals t's unmasked k-mer at
+ *     j is one vote on diagonal d = j - i, in bin(d) = floor((d + |q|) / 64) (never negative);
+ *   - support: V_s is the largest vote count of any bin of strand s (votes_fwd: V_+, votes_rev: V_-), B_s the smallest
+ *     bin that reaches it.  strand is '+' if V_+ >= V_-, else '-'; when both are 0 it is '.' and t0 = t1 = 0;
+ *   - span: with the chosen strand's bin B, a vote is consistent if |bin(d) - B| <= R, R = 2 + ceil(|q| / 512); its
+ *     quarter is floor(4 i / |q|).  B_head is the most frequent bin among consistent votes of quarter 0, a tie going
+ *     to the smaller bin, B if there are none; B_tail likewise for quarter 3.  t0 = clamp(64 B_head + 32 - |q|, 0, |t|)
+ *     and t1 = clamp(64 B_tail + 32, 0, |t|): the bin centres as the diagonal at q's first base and just past its last.
+ * Size limit: |q|, |t| <= 65,536 (DAGCON_PLACE_MAX_LEN) for every sequence a pair names, else DAGCON_ERR_UNSUPPORTED
+ * (q-sense is "not optimized for larger templates"); DAGCON_ERR_INVALID_ARG for k or max_occ out of range or a
+ * sequence past the blob.  Outputs are [n_pairs] arrays.
+ */
+#define DAGCON_PLACE_MAX_LEN 65536u
+int dagcon_place(dagcon_ctx *ctx, const uint64_t *seq_off, const uint32_t *seq_len, const char *blob, uint64_t bytes,
+                 uint32_t n_pairs, const uint32_t *pair_q, const uint32_t *pair_t, uint32_t k, uint32_t max_occ,
+                 uint32_t *votes_fwd, uint32_t *votes_rev, char *strand, uint32_t *t0, uint32_t *t1);
+
 /* Host arithmetic only (no device, no context): the pieces dagcon_upload would cut the merge and bestPath
  * sweeps of a batch of this shape into -- out4 = {pieces per target (merge), shortest stretch worth a
  * piece, 1 when the four-segments-per-wave merge kernel takes the batch, pieces per target (bestPath)}.

@@ -25,6 +25,7 @@ FLAG_STOP_AFTER_MERGE = 4
 FLAG_DEBUG_RESWEEP = 16
 FLAG_LOCAL_ALIGN = 32
 MAX_COVERAGE = 4094
+PLACE_MAX_LEN = 65536
 
 EXPORTS = [
     "dagcon_abi_version", "dagcon_default_opts", "dagcon_create", "dagcon_destroy",
@@ -32,7 +33,7 @@ EXPORTS = [
     "dagcon_fetch", "dagcon_get_timings", "dagcon_normalize", "dagcon_debug_graph",
     "dagcon_debug_counters", "dagcon_host_alloc", "dagcon_host_free", "dagcon_align",
     "dagcon_consensus_pre", "dagcon_debug_plan", "dagcon_align_dropped", "dagcon_align_panels",
-    "dagcon_align_ends",
+    "dagcon_align_ends", "dagcon_place",
 ]
 ABI_VERSION = 2
 
@@ -125,6 +126,8 @@ def load() -> C.CDLL:
     L.dagcon_align_dropped.argtypes = [vp]
     L.dagcon_align_dropped.restype = C.c_uint32
     L.dagcon_align_ends.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
+    L.dagcon_place.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32,
+                               vp, vp, vp, vp, vp]
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
     L.dagcon_host_free.restype = None
@@ -400,6 +403,27 @@ class Context:
         self._chk(self.L.dagcon_align_ends(self.h, n, e[0].ctypes.data, e[1].ctypes.data, e[2].ctypes.data,
                                            e[3].ctypes.data))
         return [tuple(int(x) for x in e[:, a]) for a in range(n)]
+
+    def place(self, seqs, pairs, k=12, max_occ=4):
+        """seqs = [bytes], pairs = [(q, t)] indices into seqs -> dict of numpy arrays over the pairs (dagcon_place):
+        votes_fwd, votes_rev (uint32), strand (bytes: b'+', b'-' or b'.' per pair), t0, t1 (uint32)."""
+        n = len(pairs)
+        ln = np.array([len(s) for s in seqs] or [0], dtype=np.uint32)
+        off = np.zeros(max(len(seqs), 1), np.uint64)
+        if len(seqs) > 1:
+            off[1:] = np.cumsum(ln[:-1], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(seqs) or b"\0", dtype=np.uint8)
+        pr = np.array(pairs, dtype=np.uint32).reshape(-1, 2) if n else np.zeros((0, 2), np.uint32)
+        pq, pt = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        out = {name: np.zeros(max(n, 1), np.uint32) for name in ("votes_fwd", "votes_rev", "t0", "t1")}
+        strand = np.zeros(max(n, 1), np.uint8)
+        self._chk(self.L.dagcon_place(self.h, off.ctypes.data, ln.ctypes.data, blob.ctypes.data,
+                                      sum(len(s) for s in seqs), n, pq.ctypes.data, pt.ctypes.data, k, max_occ,
+                                      out["votes_fwd"].ctypes.data, out["votes_rev"].ctypes.data, strand.ctypes.data,
+                                      out["t0"].ctypes.data, out["t1"].ctypes.data))
+        res = {name: a[:n] for name, a in out.items()}
+        res["strand"] = strand[:n].tobytes()
+        return res
 
     def align_dropped(self):
         """Pairs the last align / align_panels / consensus_pre left unaligned (dagcon_align_dropped)."""

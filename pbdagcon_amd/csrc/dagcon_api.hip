@@ -23,6 +23,7 @@
 #include "k_bestpath.hip.h"
 #include "k_align.hip.h"
 #include "k_align_panels.hip.h"
+#include "k_place.hip.h"
 
 namespace {
 
@@ -128,6 +129,7 @@ struct Ctx {
     DevBuf d_pool, d_stk, d_cuts, d_cuts_bp, d_bp_stat, d_bp_len, d_worklist, d_rd, d_pro_state, d_sh_cnt, d_seg_done, d_wl_first, d_queue0, d_bp_end, d_bp_ab, d_defer, d_cns_tmp0;
     DevBuf d_al[15];                                // dagcon_align: blobs, offsets, outputs, directions, launch order, widths, ends
     DevBuf d_pn[18];                                // dagcon_align_panels: blobs, panels, scratch, outputs, launch order
+    DevBuf d_pl[14];                                // dagcon_place: blob, sequences, tables, pairs, outputs
     DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
 
     uint64_t norm_cap = 0, node_cap = 0, pool_cap = 0, cns_cap = 0, seg_cap = 0;
@@ -501,6 +503,7 @@ void dagcon_destroy(dagcon_ctx *ctx) {
     for (DevBuf *b : all) free_buf(*b);
     for (DevBuf &b : c->d_al) free_buf(b);
     for (DevBuf &b : c->d_pn) free_buf(b);
+    for (DevBuf &b : c->d_pl) free_buf(b);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1369,6 +1372,117 @@ int dagcon_align_panels(dagcon_ctx *ctx, uint32_t n, const uint64_t *q_off, cons
         if (drop[a] && panel_dist) for (uint64_t p = panel_begin[a]; p < panel_begin[a + 1]; p++) panel_dist[p] = -1;
     }
     c->align_dropped = dropped;
+    return DAGCON_OK;
+}
+
+// dagcon_place (k_place.hip.h).  Pairs are taken in target order; the distinct targets are cut into groups whose tables
+// fit in DG_PLACE_SLOT_BUDGET slots, and each group is one memset, one k_place_index and one k_place_vote launch.
+#define DG_PLACE_SLOT_BUDGET (8u << 20)     // 256 MB of tables at a time
+int dagcon_place(dagcon_ctx *ctx, const uint64_t *seq_off, const uint32_t *seq_len, const char *blob, uint64_t bytes,
+                 uint32_t n_pairs, const uint32_t *pair_q, const uint32_t *pair_t, uint32_t k, uint32_t max_occ,
+                 uint32_t *votes_fwd, uint32_t *votes_rev, char *strand, uint32_t *t0, uint32_t *t1) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (n_pairs == 0) return DAGCON_OK;
+    if (!seq_off || !seq_len || !blob || !pair_q || !pair_t || !votes_fwd || !votes_rev || !strand || !t0 || !t1)
+        return fail(c, DAGCON_ERR_INVALID_ARG, "NULL argument");
+    if (k < 8 || k > DG_PLACE_KMAX) return fail(c, DAGCON_ERR_INVALID_ARG, "k = %u is outside 8 .. 16", k);
+    if (max_occ < 1 || max_occ > DG_PLACE_MAX_OCC) return fail(c, DAGCON_ERR_INVALID_ARG, "max_occ = %u is outside 1 .. 8", max_occ);
+    uint64_t n_seq = 0;
+    for (uint32_t a = 0; a < n_pairs; a++) {
+        for (const uint32_t s : {pair_q[a], pair_t[a]}) {
+            if (seq_off[s] > bytes || seq_len[s] > bytes - seq_off[s])
+                return fail(c, DAGCON_ERR_INVALID_ARG, "pair %u: sequence %u runs past the blob", a, s);
+            if (seq_len[s] > DG_PLACE_MAX_LEN)
+                return fail(c, DAGCON_ERR_UNSUPPORTED, "pair %u: sequence %u has %u bases, more than %u", a, s, seq_len[s], DG_PLACE_MAX_LEN);
+            n_seq = std::max<uint64_t>(n_seq, (uint64_t)s + 1);
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // pairs in target order (counting sort), a table per distinct target, groups of tables
+    std::vector<uint32_t> first(n_seq + 1, 0);
+    for (uint32_t a = 0; a < n_pairs; a++) first[pair_t[a] + 1]++;
+    for (uint64_t s = 0; s < n_seq; s++) first[s + 1] += first[s];
+    std::vector<uint32_t> pid(n_pairs), pq(n_pairs), pt(n_pairs), ptab(n_pairs);
+    {
+        std::vector<uint32_t> fill(first.begin(), first.end() - 1);
+        for (uint32_t a = 0; a < n_pairs; a++) pid[fill[pair_t[a]]++] = a;
+    }
+    std::vector<uint32_t> tab_seq, tab_mask;
+    std::vector<uint64_t> tab_base;                 // counted from its group's first slot
+    struct Group { uint32_t tab0, tab1, pair0, pair1, nb; uint64_t slots; };
+    std::vector<Group> groups;
+    Group g{0, 0, 0, 0, 1, 0};
+    uint64_t max_slots = 0;
+    for (uint64_t s = 0; s < n_seq; s++) {
+        if (first[s] == first[s + 1]) continue;
+        const uint32_t lt = seq_len[s];
+        const uint64_t nk = lt >= k ? lt - k + 1 : 0;
+        uint64_t slots = 64;
+        while (slots < 2 * nk) slots <<= 1;
+        if (g.slots + slots > DG_PLACE_SLOT_BUDGET && g.tab1 > g.tab0) {
+            groups.push_back(g);
+            max_slots = std::max(max_slots, g.slots);
+            g = Group{g.tab1, g.tab1, g.pair1, g.pair1, 1, 0};
+        }
+        const uint32_t tb = (uint32_t)tab_seq.size();
+        tab_seq.push_back((uint32_t)s); tab_base.push_back(g.slots); tab_mask.push_back((uint32_t)(slots - 1));
+        g.slots += slots;
+        g.tab1 = tb + 1;
+        for (uint32_t x = first[s]; x < first[s + 1]; x++) {
+            const uint32_t a = pid[x];
+            pq[x] = pair_q[a]; pt[x] = pair_t[a]; ptab[x] = tb - g.tab0;
+            const uint32_t lq = seq_len[pair_q[a]];
+            if (lq >= k && lt >= k) g.nb = std::max(g.nb, ((lt - k + lq) >> DG_PLACE_BIN_SHIFT) + 1);
+        }
+        g.pair1 = first[s + 1];
+    }
+    groups.push_back(g);
+    max_slots = std::max(max_slots, g.slots);
+
+    DevBuf &dblob = c->d_pl[0], &doff = c->d_pl[1], &dlen = c->d_pl[2], &dtseq = c->d_pl[3], &dtbase = c->d_pl[4],
+           &dtmask = c->d_pl[5], &dslots = c->d_pl[6], &dpq = c->d_pl[7], &dpt = c->d_pl[8], &dptab = c->d_pl[9],
+           &dpid = c->d_pl[10], &dvotes = c->d_pl[11], &dspan = c->d_pl[12], &dstrand = c->d_pl[13];
+    hipStream_t st = c->stream;
+    const uint32_t n_tab = (uint32_t)tab_seq.size();
+    ENSURE(c, dblob, bytes); ENSURE(c, doff, n_seq * 8); ENSURE(c, dlen, n_seq * 4);
+    ENSURE(c, dtseq, (size_t)n_tab * 4); ENSURE(c, dtbase, (size_t)n_tab * 8); ENSURE(c, dtmask, (size_t)n_tab * 4);
+    ENSURE(c, dslots, max_slots * sizeof(DgPlaceSlot));
+    ENSURE(c, dpq, (size_t)n_pairs * 4); ENSURE(c, dpt, (size_t)n_pairs * 4); ENSURE(c, dptab, (size_t)n_pairs * 4);
+    ENSURE(c, dpid, (size_t)n_pairs * 4); ENSURE(c, dvotes, (size_t)n_pairs * 8); ENSURE(c, dspan, (size_t)n_pairs * 8);
+    ENSURE(c, dstrand, n_pairs);
+    if (bytes) HIPCHK(c, hipMemcpyAsync(dblob.p, blob, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(doff.p, seq_off, n_seq * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dlen.p, seq_len, n_seq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dtseq.p, tab_seq.data(), (size_t)n_tab * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dtbase.p, tab_base.data(), (size_t)n_tab * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dtmask.p, tab_mask.data(), (size_t)n_tab * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dpq.p, pq.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dpt.p, pt.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dptab.p, ptab.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dpid.p, pid.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, st));
+    DgPlaceParams pp;
+    pp.blob = (const uint8_t *)dblob.p; pp.seq_off = (const uint64_t *)doff.p; pp.seq_len = (const uint32_t *)dlen.p;
+    pp.slots = (DgPlaceSlot *)dslots.p;
+    pp.votes_fwd = (uint32_t *)dvotes.p; pp.votes_rev = (uint32_t *)dvotes.p + n_pairs;
+    pp.t0 = (uint32_t *)dspan.p; pp.t1 = (uint32_t *)dspan.p + n_pairs; pp.strand = (uint8_t *)dstrand.p;
+    pp.k = k; pp.max_occ = max_occ;
+    for (const Group &gr : groups) {
+        HIPCHK(c, hipMemsetAsync(dslots.p, 0, gr.slots * sizeof(DgPlaceSlot), st));
+        pp.tab_seq = (const uint32_t *)dtseq.p + gr.tab0; pp.tab_base = (const uint64_t *)dtbase.p + gr.tab0;
+        pp.tab_mask = (const uint32_t *)dtmask.p + gr.tab0;
+        pp.pq = (const uint32_t *)dpq.p + gr.pair0; pp.pt = (const uint32_t *)dpt.p + gr.pair0;
+        pp.ptab = (const uint32_t *)dptab.p + gr.pair0; pp.pid = (const uint32_t *)dpid.p + gr.pair0;
+        hipLaunchKernelGGL(k_place_index, dim3(gr.tab1 - gr.tab0), dim3(DG_PLACE_THREADS), 0, st, pp);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_place_vote, dim3(gr.pair1 - gr.pair0), dim3(DG_PLACE_THREADS), (size_t)6 * gr.nb * 4, st, pp);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, d2h(c, votes_fwd, dvotes.p, (size_t)n_pairs * 4));
+    HIPCHK(c, d2h(c, votes_rev, (const uint32_t *)dvotes.p + n_pairs, (size_t)n_pairs * 4));
+    HIPCHK(c, d2h(c, t0, dspan.p, (size_t)n_pairs * 4));
+    HIPCHK(c, d2h(c, t1, (const uint32_t *)dspan.p + n_pairs, (size_t)n_pairs * 4));
+    HIPCHK(c, d2h(c, strand, dstrand.p, n_pairs));
     return DAGCON_OK;
 }
 

@@ -60,8 +60,10 @@ typedef enum dagcon_status {
                                            every target takes the one-piece re-sweep (tests only) */
 #define DAGCON_FLAG_LOCAL_ALIGN 32u    /* dagcon_align / dagcon_consensus_pre align local ends (see dagcon_align):
                                           read ends that do not align stay out of the alignment */
+#define DAGCON_FLAG_BASE_SUPPORT 64u  /* keep the support of every consensus base: dagcon_fetch_support */
 #define DAGCON_FLAGS_ALL (DAGCON_FLAG_RAW_ALIGNMENTS | DAGCON_FLAG_STOP_AFTER_BUILD | \
-                          DAGCON_FLAG_STOP_AFTER_MERGE | DAGCON_FLAG_DEBUG_RESWEEP | DAGCON_FLAG_LOCAL_ALIGN)
+                          DAGCON_FLAG_STOP_AFTER_MERGE | DAGCON_FLAG_DEBUG_RESWEEP | DAGCON_FLAG_LOCAL_ALIGN | \
+                          DAGCON_FLAG_BASE_SUPPORT)
                                         /* dagcon_create refuses any other bit (DAGCON_ERR_UNSUPPORTED) */
 
 /* Mirrors ProgramOpts (src/cpp/ProgramOpts.hpp:8-36) for this path. */
@@ -133,6 +135,28 @@ typedef struct dagcon_results {
     uint32_t n_failed;            /* targets whose status is not DAGCON_OK */
 } dagcon_results;
 
+/*
+ * Per-base support of the consensus (a context created with DAGCON_FLAG_BASE_SUPPORT).  The reference has no such
+ * output: this is this build's own definition, PARITY UNPINNED.  Entry i describes seq_blob[i] of the results, so
+ * segment s has [seq_off[s], seq_off[s] + seq_len[s]) of both arrays; n == seq_bytes, and a failed target, which has
+ * no segments, has no entries.  For the best-path vertex v a consensus base comes from (AlnGraphBoost.cpp:375-459):
+ *   weight[i]  v's node weight after mergeNodes (the value consensus compares with minWeight);
+ *   depth[i]   the coverage of _bbMap[v], the backbone vertex whose coverage bestPath charges for v.
+ * With K the target's alignment count (<= DAGCON_MAX_COVERAGE): depth <= K, weight <= K + 1.  addAln adds 1 to a
+ * coverage per read that consumes the position and 1 to a weight per read that passes through the vertex, once per read;
+ * a backbone vertex starts at weight 1 (AlnGraphBoost.cpp:32,54).  mergeNodes unites siblings that every one of their
+ * reads goes through next (or came from) only, so no read passes through two of them, and adds their weights; a merged
+ * vertex holds at most one backbone vertex.  A target where either value would exceed 65,535 fails with
+ * DAGCON_ERR_INTERNAL; no value wraps.  The arrays are owned by the context, valid as long as the results of the same fetch.
+ * dagcon_fetch_support is valid after dagcon_fetch, dagcon_consensus or dagcon_consensus_pre on such a context, and
+ * returns DAGCON_ERR_STATE otherwise: without the flag, before a fetch, or under DAGCON_FLAG_STOP_AFTER_BUILD / _MERGE.
+ */
+typedef struct dagcon_support {
+    uint64_t n;                  /* == dagcon_results.seq_bytes */
+    const uint16_t *weight;      /* [n] */
+    const uint16_t *depth;       /* [n] */
+} dagcon_support;
+
 /* Per-stage device time of the last dagcon_run, from HIP events on the
  * context's stream (milliseconds), plus the algorithmic byte count SURVEY.md
  * section 8(d) defines. */
@@ -169,6 +193,7 @@ int dagcon_run(dagcon_ctx *ctx);                               /* enqueue all ke
 int dagcon_sync(dagcon_ctx *ctx);                              /* wait for the stream */
 int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *results);    /* sync + status check + D2H */
 int dagcon_get_timings(dagcon_ctx *ctx, dagcon_timings *out);  /* after dagcon_sync / dagcon_fetch */
+int dagcon_fetch_support(dagcon_ctx *ctx, dagcon_support *out); /* DAGCON_FLAG_BASE_SUPPORT: see dagcon_support */
 
 /*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses

@@ -24,6 +24,7 @@ FLAG_STOP_AFTER_BUILD = 2
 FLAG_STOP_AFTER_MERGE = 4
 FLAG_DEBUG_RESWEEP = 16
 FLAG_LOCAL_ALIGN = 32
+FLAG_BASE_SUPPORT = 64
 MAX_COVERAGE = 4094
 PLACE_MAX_LEN = 65536
 
@@ -33,7 +34,7 @@ EXPORTS = [
     "dagcon_fetch", "dagcon_get_timings", "dagcon_normalize", "dagcon_debug_graph",
     "dagcon_debug_counters", "dagcon_host_alloc", "dagcon_host_free", "dagcon_align",
     "dagcon_consensus_pre", "dagcon_debug_plan", "dagcon_align_dropped", "dagcon_align_panels",
-    "dagcon_align_ends", "dagcon_place",
+    "dagcon_align_ends", "dagcon_place", "dagcon_fetch_support",
 ]
 ABI_VERSION = 2
 
@@ -71,6 +72,10 @@ class Results(C.Structure):
                 ("seq_len", C.POINTER(C.c_uint32)), ("seq_blob", C.c_void_p),
                 ("seq_bytes", C.c_uint64), ("target_status", C.POINTER(C.c_int32)),
                 ("n_failed", C.c_uint32)]
+
+
+class Support(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("weight", C.POINTER(C.c_uint16)), ("depth", C.POINTER(C.c_uint16))]
 
 
 class Timings(C.Structure):
@@ -117,6 +122,7 @@ def load() -> C.CDLL:
     L.dagcon_sync.argtypes = [vp]
     L.dagcon_fetch.argtypes = [vp, C.POINTER(Results)]
     L.dagcon_get_timings.argtypes = [vp, C.POINTER(Timings)]
+    L.dagcon_fetch_support.argtypes = [vp, C.POINTER(Support)]
     L.dagcon_normalize.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32,
                                    C.c_uint32, vp, vp, vp, vp, vp]
     L.dagcon_debug_graph.argtypes = [vp, C.c_uint32, C.POINTER(GraphDump)]
@@ -228,6 +234,7 @@ class Context:
         self._pinned = []
         self.target_status = None      # per-target dagcon_status of the last fetch (ABI 2)
         self._align_n = 0              # pairs of the last align / consensus_pre (align_ends)
+        self._segs = None              # (seg_begin, seq_off, seq_len) of the last results (base_support)
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
@@ -287,8 +294,38 @@ class Context:
     def fetch(self, strict=True):
         r = Results()
         self._chk(self.L.dagcon_fetch(self.h, C.byref(r)))
+        out = self._keep_segs(r)
         self._status(r, strict)
+        return out
+
+    def _keep_segs(self, r):
+        """_results_to_py, remembering where each segment's bases are (base_support)."""
+        S = int(r.n_segments)
+        self._segs = (np.ctypeslib.as_array(r.seg_begin, shape=(r.n_targets + 1,)).copy(),
+                      np.ctypeslib.as_array(r.seq_off, shape=(S,)).copy() if S else np.zeros(0, np.uint64),
+                      np.ctypeslib.as_array(r.seq_len, shape=(S,)).copy() if S else np.zeros(0, np.uint32))
         return _results_to_py(r)
+
+    def fetch_support_raw(self):
+        """dagcon_fetch_support: (weight, depth) uint16 arrays over the whole seq_blob of the last results (copies)."""
+        s = Support()
+        self._chk(self.L.dagcon_fetch_support(self.h, C.byref(s)))
+        n = int(s.n)
+        if n == 0:
+            return np.zeros(0, np.uint16), np.zeros(0, np.uint16)
+        return np.ctypeslib.as_array(s.weight, shape=(n,)).copy(), np.ctypeslib.as_array(s.depth, shape=(n,)).copy()
+
+    def base_support(self):
+        """Per target, one (weight, depth) pair of uint16 arrays per segment, aligned with that segment's seq
+        (FLAG_BASE_SUPPORT; after consensus, fetch or consensus_pre).  weight: the node weight of the best-path vertex
+        the base comes from; depth: the coverage of its backbone vertex (include/dagcon.h, dagcon_support)."""
+        w, d = self.fetch_support_raw()
+        sb, so, sl = self._segs
+        out = []
+        for t in range(sb.size - 1):
+            out.append([(w[int(so[s]):int(so[s]) + int(sl[s])], d[int(so[s]):int(so[s]) + int(sl[s])])
+                        for s in range(int(sb[t]), int(sb[t + 1]))])
+        return out
 
     def fetch_raw(self):
         """dagcon_fetch without the conversion to Python objects: the returned struct points into
@@ -307,8 +344,9 @@ class Context:
         b = batch.c_struct()
         r = Results()
         self._chk(self.L.dagcon_consensus(self.h, C.byref(b), C.byref(r)))
+        out = self._keep_segs(r)
         self._status(r, strict)
-        return _results_to_py(r)
+        return out
 
     def timings(self) -> dict:
         t = Timings()
@@ -453,8 +491,9 @@ class Context:
         r = Results()
         self.L.dagcon_consensus_pre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk(self.L.dagcon_consensus_pre(self.h, C.byref(pb), C.byref(r)))
+        out = self._keep_segs(r)
         self._status(r, strict)
-        return _results_to_py(r)
+        return out
 
     def debug_counters(self):
         a = (C.c_ulonglong * 16)()

@@ -131,6 +131,7 @@ struct Ctx {
     DevBuf d_pn[18];                                // dagcon_align_panels: blobs, panels, scratch, outputs, launch order
     DevBuf d_pl[14];                                // dagcon_place: blob, sequences, tables, pairs, outputs
     DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
+    DevBuf d_sup_tmp, d_sup_tmp0, d_sup;           // DAGCON_FLAG_BASE_SUPPORT: walk scratch (4 B per vertex), output (2 x 2 B per base)
 
     uint64_t norm_cap = 0, node_cap = 0, pool_cap = 0, cns_cap = 0, seg_cap = 0;
     uint32_t stk_words = 4096, growth_pct = 100, seg_max = 8, bp_max = 16, seg_env = 0, seg_min = 768;    // (scratch per target and segment: grown x4 and re-run on DG_E_STACK)
@@ -149,6 +150,10 @@ struct Ctx {
     std::vector<int32_t> r_status;
     char *r_blob = nullptr;             // page-locked: the consensus blob comes back at PCIe speed
     size_t r_blob_cap = 0;
+    uint16_t *r_sup = nullptr;          // page-locked, DAGCON_FLAG_BASE_SUPPORT: [seq_bytes] weights, then [seq_bytes] depths
+    size_t r_sup_cap = 0;               // (entries of each half)
+    uint64_t r_sup_n = 0;
+    bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
 
     // debug dump storage
     std::vector<uint8_t> g_base, g_deleted, g_backbone;
@@ -241,6 +246,11 @@ int ensure_arenas(Ctx *c) {
     ENSURE(c, c->d_bp_stat, (uint64_t)c->T * c->bp_max * 8);
     ENSURE(c, c->d_bp_len, (uint64_t)c->T * c->bp_max * 4);
     ENSURE(c, c->d_cns, c->cns_cap);
+    if (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT) {
+        ENSURE(c, c->d_sup_tmp, c->node_cap * 4);
+        if (c->gcuts) ENSURE(c, c->d_sup_tmp0, c->node_cap * 4);
+        ENSURE(c, c->d_sup, c->cns_cap * 4);
+    }
     ENSURE(c, c->d_seg_r0, c->seg_cap * 4);
     ENSURE(c, c->d_seg_r1, c->seg_cap * 4);
     return DAGCON_OK;
@@ -313,6 +323,10 @@ void fill_params(Ctx *c, DgParams &p) {
     p.seg_r0 = (int32_t *)c->d_seg_r0.p; p.seg_r1 = (int32_t *)c->d_seg_r1.p;
     p.seg_cap = c->seg_cap;
     p.st = (DgStatus *)c->d_st.p;
+    if (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT) {
+        p.sup_tmp = (uint32_t *)c->d_sup_tmp.p; p.sup_tmp0 = (uint32_t *)c->d_sup_tmp0.p;
+        p.sup_w = (uint16_t *)c->d_sup.p; p.sup_d = p.sup_w + c->cns_cap;
+    }
 }
 
 // stage a1: count, chunked normalizeGaps + trimAln, and the sequential kernel for what is left
@@ -342,7 +356,7 @@ int launch_all(Ctx *c) {
                           &c->d_gbase, &c->d_bid, &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_stk, &c->d_cuts,
                           &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_wl_first,
                           &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns, &c->d_cns_off, &c->d_seg_first,
-                          &c->d_seg_r0, &c->d_seg_r1, &c->d_worklist, &c->d_seg_done};
+                          &c->d_seg_r0, &c->d_seg_r1, &c->d_worklist, &c->d_seg_done, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup};
         for (DevBuf *b : work)
             if (b->p && b->cap) HIPCHK(c, hipMemsetAsync(b->p, 0xEE, b->cap, s));
     }
@@ -401,6 +415,7 @@ int launch_all(Ctx *c) {
     }
     HIPCHK(c, hipEventRecord(c->ev[3], s));
     if (c->T > 0 && !(c->opts.flags & (DAGCON_FLAG_STOP_AFTER_BUILD | DAGCON_FLAG_STOP_AFTER_MERGE))) {
+        const bool sup = (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT) != 0;   // the walks and the join with per-base support
         hipLaunchKernelGGL(k_bp_terms, dim3(c->T, 16), dim3(256), 0, s, p);
         if (c->gcuts) {
             // partial-span pileups, on the pieces of k_cuts2: one sweep for (A, B), then vertex-parallel kernels for the
@@ -412,16 +427,21 @@ int launch_all(Ctx *c) {
             hipLaunchKernelGGL(k_bp_choose, dim3(c->T * c->bp_max), dim3(256), 0, s, p);
             hipLaunchKernelGGL(k_bp_sweep_abs_g, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_bp_defer, dim3(c->T), dim3(64), 0, s, p);
-            hipLaunchKernelGGL(k_bp_walk_g, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
+            if (sup) hipLaunchKernelGGL(k_bp_walk_g<true>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
+            else hipLaunchKernelGGL(k_bp_walk_g<false>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
         } else {
             // a lane per piece first; the wave-per-piece sweep then takes the pieces a lane gave up (deep recursion)
             if (p.bp_lane) hipLaunchKernelGGL(k_bp_sweep_l, dim3((c->T * c->bp_max + 7u) / 8u), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_bp_sweep, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_bp_check, dim3(c->T), dim3(64), 0, s, p);
-            if (p.bp_lane) hipLaunchKernelGGL(k_bp_walk_r, dim3((c->T * c->bp_max + 7u) / 8u), dim3(64), 0, s, p);
-            else hipLaunchKernelGGL(k_bp_walk, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
+            if (p.bp_lane) {
+                if (sup) hipLaunchKernelGGL(k_bp_walk_r<true>, dim3((c->T * c->bp_max + 7u) / 8u), dim3(64), 0, s, p);
+                else hipLaunchKernelGGL(k_bp_walk_r<false>, dim3((c->T * c->bp_max + 7u) / 8u), dim3(64), 0, s, p);
+            } else if (sup) hipLaunchKernelGGL(k_bp_walk<true>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
+            else hipLaunchKernelGGL(k_bp_walk<false>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
         }
-        hipLaunchKernelGGL(k_bp_join, dim3(c->T), dim3(64), 0, s, p);
+        if (sup) hipLaunchKernelGGL(k_bp_join<true>, dim3(c->T), dim3(64), 0, s, p);
+        else hipLaunchKernelGGL(k_bp_join<false>, dim3(c->T), dim3(64), 0, s, p);
     }
     HIPCHK(c, hipEventRecord(c->ev[4], s));
     HIPCHK(c, hipGetLastError());
@@ -491,6 +511,7 @@ void dagcon_destroy(dagcon_ctx *ctx) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->r_blob) (void)hipHostFree(c->r_blob);
+    if (c->r_sup) (void)hipHostFree(c->r_sup);
     DevBuf *all[] = {&c->d_q, &c->d_t, &c->d_aln_off, &c->d_aln_len, &c->d_aln_start, &c->d_aln_tgt,
                      &c->d_tlen, &c->d_aln_begin, &c->d_tactive, &c->d_tfail, &c->d_bb, &c->d_bb_off, &c->d_mat_base, &c->d_matc_base, &c->d_matc_stride,
                      &c->d_bbv_base, &c->d_nmis, &c->d_norm_off, &c->d_n_lo, &c->d_n_hi, &c->d_n_start, &c->d_ch_aln, &c->d_ch_base, &c->d_ch_k0, &c->d_ch_next, &c->d_ch_w, &c->d_ch_tb, &c->d_ch_flag, &c->d_ch_src, &c->d_ch_out, &c->d_ch_adv, &c->d_n_lb, &c->d_norm_tmp, &c->d_ckpt, &c->d_ck_base,
@@ -499,7 +520,7 @@ void dagcon_destroy(dagcon_ctx *ctx) {
                      &c->d_matC, &c->d_cov, &c->d_gcount, &c->d_gbase, &c->d_bid, &c->d_nodes,
                      &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_score_b, &c->d_pool, &c->d_stk, &c->d_cuts, &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_worklist, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_seg_done, &c->d_wl_first, &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns,
                      &c->d_cns_off, &c->d_cns_len, &c->d_seg_first, &c->d_n_seg, &c->d_seg_r0, &c->d_seg_r1,
-                     &c->d_st};
+                     &c->d_st, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup};
     for (DevBuf *b : all) free_buf(*b);
     for (DevBuf &b : c->d_al) free_buf(b);
     for (DevBuf &b : c->d_pn) free_buf(b);
@@ -514,6 +535,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
+    c->sup_valid = false;
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->aln_begin)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/aln_begin is NULL");
     const uint64_t A_all = T ? b->aln_begin[T] : 0;
@@ -852,6 +874,23 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         }
         if (nb) HIPCHK(c, d2h(c, c->r_blob, c->d_cns.p, nb));
     }
+    c->sup_valid = false;
+    if (full && (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT)) {
+        // the support, weights then depths (the device keeps them apart: no host pass over them)
+        if (c->r_sup_cap < nb + 1) {
+            if (c->r_sup) (void)hipHostFree(c->r_sup);
+            c->r_sup = nullptr; c->r_sup_cap = 0;
+            const size_t want = (size_t)(nb + 1) + (size_t)(nb / 8) + 4096;
+            HIPCHK(c, hipHostMalloc((void **)&c->r_sup, want * 4, hipHostMallocDefault));
+            c->r_sup_cap = want;
+        }
+        if (nb) {
+            HIPCHK(c, hipMemcpyAsync(c->r_sup, c->d_sup.p, nb * 2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, d2h(c, c->r_sup + nb, (const uint16_t *)c->d_sup.p + c->cns_cap, nb * 2));
+        }
+        c->r_sup_n = nb;
+        c->sup_valid = true;
+    }
     c->r_seg_begin.assign(T + 1, 0);
     c->r_range0.clear(); c->r_range1.clear(); c->r_seq_off.clear(); c->r_seq_len.clear();
     uint64_t bases = 0;
@@ -882,6 +921,19 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     res->seq_blob = c->r_blob; res->seq_bytes = nb;
     res->target_status = c->r_status.data(); res->n_failed = n_failed;
     c->fetched = true;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_support(dagcon_ctx *ctx, dagcon_support *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!(c->opts.flags & DAGCON_FLAG_BASE_SUPPORT))
+        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_support on a context created without DAGCON_FLAG_BASE_SUPPORT");
+    if (!c->sup_valid)
+        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_support without the results of a consensus (no fetch yet, or stopped before bestPath)");
+    out->n = c->r_sup_n;
+    out->weight = c->r_sup;
+    out->depth = c->r_sup + c->r_sup_n;
     return DAGCON_OK;
 }
 

@@ -205,6 +205,11 @@ struct DgParams {
     int32_t *seg_r0, *seg_r1;
     uint64_t seg_cap;
     DgStatus *st;
+    // ---- per-base support (DAGCON_FLAG_BASE_SUPPORT only; NULL otherwise).  Last, so that every field above keeps its
+    // offset and the flag-off kernels their code ----
+    uint32_t *sup_tmp;             // [node_cap] parallel to cns_tmp: weight | depth << 16 of each path base of a walk piece
+    uint32_t *sup_tmp0;            // [node_cap] (p.gcuts) parallel to cns_tmp0
+    uint16_t *sup_w, *sup_d;       // [cns_cap] each, parallel to cns: weight and depth of each kept consensus base
 };
 
 // slots a backbone vertex gets for each of its two lists before it has to move to the

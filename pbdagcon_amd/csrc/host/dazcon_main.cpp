@@ -49,6 +49,7 @@
 
 #include "../../../include/dagcon.h"
 #include "daz_io.h"
+#include "fastq.h"
 
 namespace {
 
@@ -56,6 +57,7 @@ struct Opts {
     int threads = 4;
     unsigned min_cov = 6, min_len = 500, trim = 10, max_hits = 85;
     bool sort_cov = false, proper = false, verbose = false, dump_hits = false, dump_alns = false, trace_panels = false;
+    bool fastq = false;                            // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::string aln_file, seq_file;
     std::set<int> targets;
     size_t batch_targets = 512;
@@ -64,7 +66,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: dazcon -a <overlaps> -s <reads> [-j <int>] [-c <uint>] [-l <uint>] [-t <uint>] [-m <uint>] [-x] [-o] [-v] [targets ...]\n"
+            "USAGE: dazcon -a <overlaps> -s <reads> [-j <int>] [-c <uint>] [-l <uint>] [-t <uint>] [-m <uint>] [-x] [-o] [-v] [--fastq] [targets ...]\n"
             "  PBI consensus module (DAGCon over daligner-style overlaps); the consensus runs on an MI355X.\n"
             "  -a, --align-file    overlaps: a DALIGNER .las file (name ends in .las), or the text layout of INTEGRATION.md\n"
             "  -s, --seq-file      reads: a DAZZ_DB database (name ends in .db; its .idx / .bps beside it), or the text layout\n"
@@ -78,6 +80,11 @@ void usage(FILE *f) {
             "  -v, --verbose\n"
             "  --trace-panels      .las input: align every overlap inside its trace-point panels (dagcon_align_panels)\n"
             "                      instead of end to end; overlaps with a panel over 512 bases are aligned end to end\n"
+            "  --fastq             write FASTQ (@id/well/r0_r1, sequence, +, qualities) instead of FASTA, same records, same order.\n"
+            "                      The quality of a base is this build's own definition: a Laplace-smoothed fraction of the\n"
+            "                      reads at its position that do not pass through its consensus vertex, with w = the vertex's\n"
+            "                      weight, c = max(its backbone position's coverage, w), x = c - w + 1:\n"
+            "                      Q = floor(10 log10((c + 2) / x)), in exact integer arithmetic, printed as 33 + Q\n"
             "  targets             limit consensus to these target ids\n"
             "  version 0.3 (dagcon-mi355x)\n");
 }
@@ -118,6 +125,7 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--dump-hits") o.dump_hits = true;          // test hook: hit selection only, no GPU
         else if (a == "--dump-alns") o.dump_alns = true;          // test hook: the alignments handed to the consensus, no GPU
         else if (a == "--trace-panels") o.trace_panels = true;
+        else if (a == "--fastq") o.fastq = true;
         else if (a == "--device") { if (!need(&u)) return 1; o.device = (int)u; }
         else if (a == "--batch-targets") { if (!need(&u) || !u) return 1; o.batch_targets = u; }
         else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
@@ -466,6 +474,7 @@ int main(int argc, char **argv) {
     dopt.min_cov = o.min_cov; dopt.min_len = o.min_len; dopt.trim = o.trim;
     dopt.min_weight = (int32_t)o.min_cov;          // dazcon.cpp:89
     dopt.device = o.device;
+    if (o.fastq) dopt.flags |= DAGCON_FLAG_BASE_SUPPORT;
     int rc = dagcon_create(&dopt, &ctx);
     if (rc != DAGCON_OK) {
         fprintf(stderr, "dazcon: no usable MI355X as device %d (dagcon_create = %d); there is no CPU fallback\n", o.device, rc);
@@ -574,13 +583,31 @@ int main(int argc, char **argv) {
         dagcon_results r;
         rc = dagcon_consensus(ctx, &db, &r);
         if (rc != DAGCON_OK) { fprintf(stderr, "dazcon: consensus failed (%d): %s\n", rc, dagcon_last_error(ctx)); status = 1; break; }
+        dagcon_support sup;
+        memset(&sup, 0, sizeof sup);
+        if (o.fastq && (rc = dagcon_fetch_support(ctx, &sup)) != DAGCON_OK) {
+            fprintf(stderr, "dazcon: per-base support failed (%d): %s\n", rc, dagcon_last_error(ctx)); status = 1; break;
+        }
+        std::string rec;
         for (uint32_t g = 0; g < r.n_targets; g++) {
             const TargetData &td = out_targets[t0 + g];
             if (o.verbose) fprintf(stderr, "(0) calling: %d Alignments: %zu\n", td.id, td.alns.size());
             if (r.target_status[g] != DAGCON_OK)
                 fprintf(stderr, "dazcon: warning: target %d skipped (non-conforming alignment or internal error %d)\n", td.id, r.target_status[g]);
             for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
-                // dazcon.cpp:92-97  ">%s/%d/%d_%d\n%s\n"
+                // dazcon.cpp:92-97  ">%s/%d/%d_%d\n%s\n"; --fastq: '@' for '>', then + and qualities
+                if (o.fastq) {
+                    char name[96];
+                    snprintf(name, sizeof name, "%d/%d/%d_%d", td.id, fake_well_counter, r.range0[s], r.range1[s]);
+                    rec.clear();
+                    if (!dg_append_fastq(rec, name, r.seq_blob + r.seq_off[s], r.seq_len[s], sup.weight + r.seq_off[s],
+                                         sup.depth + r.seq_off[s])) {
+                        fprintf(stderr, "dazcon: target %d: per-base support out of range\n", td.id); status = 1; break;
+                    }
+                    fwrite(rec.data(), 1, rec.size(), stdout);
+                    ++fake_well_counter;
+                    continue;
+                }
                 printf(">%d/%d/%d_%d\n", td.id, fake_well_counter, r.range0[s], r.range1[s]);
                 fwrite(r.seq_blob + r.seq_off[s], 1, r.seq_len[s], stdout);
                 fputc('\n', stdout);

@@ -38,6 +38,7 @@
 #include <unistd.h>
 
 #include "../../../include/dagcon.h"
+#include "fastq.h"
 
 namespace {
 
@@ -45,6 +46,7 @@ struct Opts {
     unsigned threads = 4, min_cov = 6, min_len = 500, trim = 50;
     bool align = false, verbose = false, dump = false;
     bool local = false;                // --local (with -a): the first alignment of every record has local ends
+    bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
     int pinned = -1;                   // --pinned 0|1: page-locked blobs (-1: when the input is several batches long)
     unsigned contexts = 0;             // --contexts N: consensus workers per GPU (0: two when the input is several batches long)
@@ -58,7 +60,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -71,6 +73,12 @@ void usage(FILE *f) {
             "                      known-answer test)\n"
             "  --local             with -a: align local ends, so read ends that do not align stay out of the graph (the record\n"
             "                      starts at tstart + the first aligned target base); --polish rounds stay global\n"
+            "  --fastq             write FASTQ (@id/r0_r1, sequence, +, qualities) instead of FASTA; the same records in the\n"
+            "                      same order.  The quality of a base is this build's own definition: a Laplace-smoothed\n"
+            "                      fraction of the reads at its position that do not pass through its consensus vertex,\n"
+            "                      with w = the vertex's weight, c = max(its backbone position's coverage, w), x = c - w + 1:\n"
+            "                      Q = floor(10 log10((c + 2) / x)), in exact integer arithmetic, printed as 33 + Q\n"
+            "                      (with --polish: the support of the last round)\n"
             "  -v, --verbose       per-target progress on stderr\n"
             "  --polish N          with -a: N more rounds, each with the previous round's consensus as the backbone the reads\n"
             "                      are re-aligned to (README.md:14-15 of the reference: 'the new consensus can be used as a new\n"
@@ -106,6 +114,7 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "-t" || a == "--trim") { if (!need(&o.trim)) return 2; }
         else if (a == "-a" || a == "--align") o.align = true;
         else if (a == "--local") o.local = true;
+        else if (a == "--fastq") o.fastq = true;
         else if (a == "-v" || a == "--verbose") o.verbose = true;
         else if (a == "--dump-parsed") o.dump = true;            // test hook: parser only, no GPU
         else if (a == "--slab-bytes") { unsigned v = 0; if (!need(&v)) return 2; o.slab_bytes = v; }   // test hook
@@ -402,6 +411,12 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
             if (rc != DAGCON_OK) { fprintf(stderr, "pbdagcon: consensus failed (%d): %s\n", rc, dagcon_last_error(ctx)); return 1; }
         }
     }
+    dagcon_support sup;
+    memset(&sup, 0, sizeof sup);
+    if (o.fastq && (rc = dagcon_fetch_support(ctx, &sup)) != DAGCON_OK) {
+        fprintf(stderr, "pbdagcon: per-base support failed (%d): %s\n", rc, dagcon_last_error(ctx));
+        return 1;
+    }
     char head[64];
     for (uint32_t g = 0; g < r.n_targets; g++) {
         if (o.verbose)
@@ -414,7 +429,16 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
                     r.target_status[g] == DAGCON_ERR_NONCONFORMING ? "an alignment leaves the backbone or holds a non-printable byte"
                     : r.target_status[g] == DAGCON_ERR_UNSUPPORTED ? "too large" : "internal error");
         for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
-            // main.cpp:141-143  ">%s/%d_%d\n%s\n"
+            // main.cpp:141-143  ">%s/%d_%d\n%s\n"; --fastq: '@' for '>' (src/cpp/pbdagcon_wf.sh:20-22), then + and qualities
+            if (o.fastq) {
+                snprintf(head, sizeof head, "/%d_%d", r.range0[s], r.range1[s]);
+                if (!dg_append_fastq(b.out, b.ids[g] + head, r.seq_blob + r.seq_off[s], r.seq_len[s], sup.weight + r.seq_off[s],
+                                     sup.depth + r.seq_off[s])) {
+                    fprintf(stderr, "pbdagcon: target %s: per-base support out of range\n", b.ids[g].c_str());
+                    return 1;
+                }
+                continue;
+            }
             b.out += '>'; b.out += b.ids[g];
             snprintf(head, sizeof head, "/%d_%d\n", r.range0[s], r.range1[s]);
             b.out += head;
@@ -490,12 +514,12 @@ int main(int argc, char **argv) {
             dopt.min_cov = o.min_cov; dopt.min_len = o.min_len; dopt.trim = o.trim;
             dopt.min_weight = (int32_t)o.min_cov;          // main.cpp:261,279 (quirk Q1)
             dopt.device = worker_dev[w];
-            dopt.flags = o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u;
+            dopt.flags = (o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u) | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u);
             const double tc0 = now();
             int rc = dagcon_create(&dopt, &ctx);
             dagcon_ctx *actx = ctx;                         // --local --polish: the first alignment on a local context of its own
             if (rc == DAGCON_OK && o.local && o.polish) {
-                dopt.flags = DAGCON_FLAG_LOCAL_ALIGN;
+                dopt.flags = DAGCON_FLAG_LOCAL_ALIGN;           // (aligns only: the support comes from ctx's last round)
                 rc = dagcon_create(&dopt, &actx);
                 if (rc != DAGCON_OK) { dagcon_destroy(ctx); ctx = nullptr; }
             }

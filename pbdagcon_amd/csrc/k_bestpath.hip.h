@@ -38,6 +38,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <type_traits>
 #include "dagcon_dev.h"
 
 // what an edge needs to know about its target t: -10 applies (backbone && weight == 1, :404-405),
@@ -97,6 +98,17 @@ struct DgWalkShared {
     unsigned char wbuf[64];              // consensus bases of the walk, flushed 64 at a time
     int wtag[DG_WR], wbest[DG_WR], wbase[DG_WR], wweight[DG_WR];   // the walk's staging ring
 };
+struct DgWalkSharedS : DgWalkShared {  // SUP walks (DAGCON_FLAG_BASE_SUPPORT); their ring's wbase is base | bbpos << 8
+    uint32_t sw[64], sb[64];             // weight and bbpos (_bbMap) of the path bases in wbuf, flushed with it
+};
+
+// Per-base support (SUP instances): a path base's scratch word is weight | depth << 16, depth = coverage[_bbMap[v]] (the
+// lookup k_bp_terms makes).  Both are at most the target's alignment count (<= DAGCON_MAX_COVERAGE; see dagcon.h), so a
+// value over 65535 is a broken invariant: the target fails, the value is never wrapped.
+__device__ __forceinline__ bool dg_sup_put(uint32_t *dst, uint32_t w, int32_t d) {
+    *dst = (w & 0xffffu) | ((uint32_t)d << 16);
+    return w > 0xffffu || (uint32_t)d > 0xffffu;
+}
 
 // Scores the vertices v_top .. v_bot (descending ids) of one target.  c_top >= 0: the
 // vertex every path of this stretch ends in (the next cut, see k_cuts); it counts as
@@ -774,6 +786,7 @@ __global__ __launch_bounds__(64) void k_bp_check(DgParams p) {
 // The best path passes through every cut vertex, so its stretch from one cut to the next is
 // walked by its own wave.  A segment leaves one byte per path vertex in its own stretch of
 // the scratch (ids of a segment are contiguous): the base, bit 7 = weight >= minWeight.
+template <bool SUP = false>
 __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
     const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
     if (dg_failed(p) || dg_tskip(p, t)) return;
@@ -782,7 +795,7 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
     if (seg >= nseg) return;
     const int lane = threadIdx.x;
     const uint64_t nb = p.node_base[t];
-    __shared__ DgWalkShared W;
+    __shared__ typename std::conditional<SUP, DgWalkSharedS, DgWalkShared>::type W;
     const DgNode *nd = p.nodes + nb;
     const int32_t *best = p.best + nb;
     const int N = (int)p.n_nodes[t];
@@ -795,6 +808,14 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
     int v = c0, cs = c0 >> 6, idx = 0;
     uint32_t steps = 0;
     bool bad = false;
+    // SUP: a flushed row's depths are gathered when it is flushed and stored at the next flush (or at the end), so that
+    // no load of the support waits on the walk's chain
+    const int32_t *cov = SUP ? p.cov + p.bbv_base[t] : nullptr;
+    uint32_t *stmp = SUP ? p.sup_tmp + nb + c0 : nullptr;
+    uint32_t pw = 0;
+    int32_t pdep = 0;
+    int prow = -1;
+    bool sbad = false;
     for (;;) {
         if (v == c1) break;                                  // the next segment starts here
         while (64 * cs < N && 64 * cs < v + 192) {           // (best, base, weight) of 64 ids ahead
@@ -804,25 +825,35 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
                 const int b = best[id];
                 const int xw = id & (DG_WR - 1);
                 W.wtag[xw] = id; W.wbest[xw] = b; W.wbase[xw] = (int)(h.y & 0xffu); W.wweight[xw] = (int)h.z;
+                if constexpr (SUP) W.wbase[xw] = (int)(h.y & 0xffu) | (nd[id].bbpos << 8);     // (bbpos < 2^18)
             }
             cs++;
         }
         const int xw = v & (DG_WR - 1);
-        int nxt, w;
+        int nxt, w, bbp = 0;
         uint8_t base;
         const int wt = W.wtag[xw], wb = W.wbest[xw], wa = W.wbase[xw], ww = W.wweight[xw];
         if (__builtin_amdgcn_readfirstlane(wt) == v) {
             nxt = __builtin_amdgcn_readfirstlane(wb); base = (uint8_t)__builtin_amdgcn_readfirstlane(wa);
             w = __builtin_amdgcn_readfirstlane(ww);
+            if constexpr (SUP) bbp = __builtin_amdgcn_readfirstlane(wa) >> 8;
         } else {
             const uint4 h = *reinterpret_cast<const uint4 *>(&nd[v]);
             nxt = __builtin_amdgcn_readfirstlane(best[v]);
             base = (uint8_t)__builtin_amdgcn_readfirstlane((int)(h.y & 0xffu));
             w = __builtin_amdgcn_readfirstlane((int)h.z);
+            if constexpr (SUP) bbp = __builtin_amdgcn_readfirstlane(nd[v].bbpos);
         }
         if (!(base == eb || base == xb)) {
             if (lane == 0) W.wbuf[idx & 63] = (unsigned char)(base | (w >= minw ? 0x80u : 0u));
-            if ((idx & 63) == 63) tmp[(idx & ~63) + lane] = W.wbuf[lane];
+            if constexpr (SUP) { if (lane == 0) { W.sw[idx & 63] = (uint32_t)w; W.sb[idx & 63] = (uint32_t)bbp; } }
+            if ((idx & 63) == 63) {
+                tmp[(idx & ~63) + lane] = W.wbuf[lane];
+                if constexpr (SUP) {
+                    if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
+                    pw = W.sw[lane]; pdep = cov[W.sb[lane]]; prow = idx & ~63;
+                }
+            }
             idx++;
         }
         if (nxt < 0) break;
@@ -830,6 +861,11 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
         if (++steps > (uint32_t)N) { bad = true; break; }
     }
     if (lane < (idx & 63)) tmp[(idx & ~63) + lane] = W.wbuf[lane];     // the last, partial row
+    if constexpr (SUP) {
+        if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
+        if (lane < (idx & 63)) sbad |= dg_sup_put(stmp + (idx & ~63) + lane, W.sw[lane], cov[W.sb[lane]]);
+        if (__ballot(sbad)) bad = true;
+    }
     if (lane == 0) {
         if (bad) dg_fail_target(p, t, DG_E_INTERNAL);
         p.bp_len[blockIdx.x] = (uint32_t)idx;
@@ -839,6 +875,9 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
 // ---- the same walk with a row of eight lanes per (target, segment): eight pieces per wave (round 3; where k_bp_sweep_l
 // runs).  A step is one dependent round trip -- best[v], the vertex's base and weight: three words, fetched by lanes
 // 0 .. 2 in one load -- so what counts is how many walks are in flight; the bytes leave one at a time.
+// SUP: lane 3 fetches the vertex's bbpos in the same load; the depth it gathers with it is stored one step later, behind
+// the next step's own load (loads return in order), so it never waits on the walk's chain.
+template <bool SUP = false>
 __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
     if (dg_failed(p)) return;
     const int l = threadIdx.x & (DG_BRW - 1);
@@ -859,15 +898,26 @@ __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
     uint8_t *tmp = p.cns_tmp + nb + c0;
     int v = c0, idx = 0, steps = 0, bad = 0;
     int go = v != c1 ? 1 : 0;
+    const int32_t *cov = SUP ? p.cov + p.bbv_base[t] : nullptr;
+    uint32_t *stmp = SUP ? p.sup_tmp + nb + c0 : nullptr;
+    int pend = -1;                                           // SUP: the path base whose support is still to be stored
+    uint32_t pw = 0;
+    int32_t pdep = 0;
+    bool sbad = false;
     while (go) {
         const char *a = l == 1 ? reinterpret_cast<const char *>(&nd[v]) + 4 : l == 2 ? reinterpret_cast<const char *>(&nd[v]) + 8
-                                                                            : reinterpret_cast<const char *>(&best[v]);
+                      : (SUP && l == 3) ? reinterpret_cast<const char *>(&nd[v]) + 28 : reinterpret_cast<const char *>(&best[v]);
         const uint32_t g = *reinterpret_cast<const uint32_t *>(a);
         const int nxt = __shfl((int)g, 0, DG_BRW);
         const uint32_t base = (uint32_t)__shfl((int)g, 1, DG_BRW) & 0xffu;
         const int w = __shfl((int)g, 2, DG_BRW);
+        if constexpr (SUP) {
+            if (pend >= 0 && l == 3) sbad |= dg_sup_put(stmp + pend, pw, pdep);
+            pend = -1;
+        }
         if (!(base == eb || base == xb)) {
             if (l == 0) tmp[idx] = (uint8_t)(base | (w >= minw ? 0x80u : 0u));
+            if constexpr (SUP) { pend = idx; pw = (uint32_t)w; if (l == 3) pdep = cov[(int)g]; }
             idx++;
         }
         if (nxt < 0) go = 0;
@@ -877,6 +927,10 @@ __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
             else if (++steps > N) { bad = 1; go = 0; }
         }
     }
+    if constexpr (SUP) {
+        if (pend >= 0 && l == 3) sbad |= dg_sup_put(stmp + pend, pw, pdep);
+        if (__shfl((int)sbad, 3, DG_BRW)) bad = 1;
+    }
     if (l == 0) {
         if (bad) dg_fail_target(p, t, DG_E_INTERNAL);
         p.bp_len[piece] = (uint32_t)idx;
@@ -884,6 +938,8 @@ __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
 }
 
 // ---- consensus segmentation (:327-373) and output, one wave per target ------------
+// SUP: the support words of the kept bases go out beside them, weight and depth apart (p.sup_w / p.sup_d at cns_off[t])
+template <bool SUP = false>
 __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
     const uint32_t t = blockIdx.x;
     if (dg_failed(p) || dg_tskip(p, t)) return;
@@ -982,6 +1038,17 @@ __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
         const uint32_t g0s = s_off[s], len = s_off[s + 1] - s_off[s];
         const uint8_t *src = (p.gcuts && s == 0) ? p.cns_tmp0 + nb : tmp + s_c0[s];
         for (uint32_t j = lane; j < len && g0s + j < keep; j += 64) out[g0s + j] = (uint8_t)(src[j] & 0x7fu);
+    }
+    if constexpr (SUP) {
+        for (uint32_t s = 0; s < nseg; s++) {
+            const uint32_t g0s = s_off[s], len = s_off[s + 1] - s_off[s];
+            const uint32_t *src = (p.gcuts && s == 0) ? p.sup_tmp0 + nb : p.sup_tmp + nb + s_c0[s];
+            for (uint32_t j = lane; j < len && g0s + j < keep; j += 64) {
+                const uint32_t x = src[j];
+                p.sup_w[co + g0s + j] = (uint16_t)(x & 0xffffu);
+                p.sup_d[co + g0s + j] = (uint16_t)(x >> 16);
+            }
+        }
     }
     for (uint32_t i = lane; i < nout; i += 64) {
         p.seg_r0[so + i] = segs[2 * i];
@@ -1239,6 +1306,7 @@ __global__ __launch_bounds__(64) void k_bp_defer(DgParams p) {
     if (left) dg_fail_target(p, t, DG_E_INTERNAL);
 }
 
+template <bool SUP = false>
 __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
     const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
     if (dg_failed(p) || dg_tskip(p, t)) return;
@@ -1247,7 +1315,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
     if (seg >= nseg) return;
     const int lane = threadIdx.x;
     const uint64_t nb = p.node_base[t];
-    __shared__ DgWalkShared W;
+    __shared__ typename std::conditional<SUP, DgWalkSharedS, DgWalkShared>::type W;
     const DgNode *nd = p.nodes + nb;
     const int32_t *best = p.best + nb;
     const int N = (int)p.n_nodes[t];
@@ -1261,6 +1329,12 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
     int v = c0, cs = c0 >> 6, idx = 0;
     uint32_t steps = 0, endk = 0;                          // endk: piece 0: cut index reached (DG_BP_ONE: exit); others: 1 = the next cut
     bool bad = false;
+    const int32_t *cov = SUP ? p.cov + p.bbv_base[t] : nullptr;    // (SUP: as in k_bp_walk)
+    uint32_t *stmp = SUP ? (seg == 0 ? p.sup_tmp0 + nb : p.sup_tmp + nb + c0) : nullptr;
+    uint32_t pw = 0;
+    int32_t pdep = 0;
+    int prow = -1;
+    bool sbad = false;
     if (seg == 0) endk = DG_BP_ONE;
     for (;;) {
         if (seg != 0) { if (v == c1) { endk = 1; break; } }
@@ -1276,25 +1350,35 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
                 const int b = best[id];
                 const int xw = id & (DG_WR - 1);
                 W.wtag[xw] = id; W.wbest[xw] = b; W.wbase[xw] = (int)(h.y & 0xffu); W.wweight[xw] = (int)h.z;
+                if constexpr (SUP) W.wbase[xw] = (int)(h.y & 0xffu) | (nd[id].bbpos << 8);     // (bbpos < 2^18)
             }
             cs++;
         }
         const int xw = v & (DG_WR - 1);
-        int nxt, w;
+        int nxt, w, bbp = 0;
         uint8_t base;
         const int wt = W.wtag[xw], wb = W.wbest[xw], wa = W.wbase[xw], ww = W.wweight[xw];
         if (__builtin_amdgcn_readfirstlane(wt) == v) {
             nxt = __builtin_amdgcn_readfirstlane(wb); base = (uint8_t)__builtin_amdgcn_readfirstlane(wa);
             w = __builtin_amdgcn_readfirstlane(ww);
+            if constexpr (SUP) bbp = __builtin_amdgcn_readfirstlane(wa) >> 8;
         } else {
             const uint4 h = *reinterpret_cast<const uint4 *>(&nd[v]);
             nxt = __builtin_amdgcn_readfirstlane(best[v]);
             base = (uint8_t)__builtin_amdgcn_readfirstlane((int)(h.y & 0xffu));
             w = __builtin_amdgcn_readfirstlane((int)h.z);
+            if constexpr (SUP) bbp = __builtin_amdgcn_readfirstlane(nd[v].bbpos);
         }
         if (!(base == eb || base == xb)) {
             if (lane == 0) W.wbuf[idx & 63] = (unsigned char)(base | (w >= minw ? 0x80u : 0u));
-            if ((idx & 63) == 63) tmp[(idx & ~63) + lane] = W.wbuf[lane];
+            if constexpr (SUP) { if (lane == 0) { W.sw[idx & 63] = (uint32_t)w; W.sb[idx & 63] = (uint32_t)bbp; } }
+            if ((idx & 63) == 63) {
+                tmp[(idx & ~63) + lane] = W.wbuf[lane];
+                if constexpr (SUP) {
+                    if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
+                    pw = W.sw[lane]; pdep = cov[W.sb[lane]]; prow = idx & ~63;
+                }
+            }
             idx++;
         }
         if (nxt < 0) break;
@@ -1302,6 +1386,11 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
         if (++steps > (uint32_t)N) { bad = true; break; }
     }
     if (lane < (idx & 63)) tmp[(idx & ~63) + lane] = W.wbuf[lane];     // the last, partial row
+    if constexpr (SUP) {
+        if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
+        if (lane < (idx & 63)) sbad |= dg_sup_put(stmp + (idx & ~63) + lane, W.sw[lane], cov[W.sb[lane]]);
+        if (__ballot(sbad)) bad = true;
+    }
     if (lane == 0) {
         if (bad) dg_fail_target(p, t, DG_E_INTERNAL);
         p.bp_len[blockIdx.x] = (uint32_t)idx;

@@ -304,6 +304,47 @@ typedef struct dagcon_pre_batch {
 int dagcon_consensus_pre(dagcon_ctx *ctx, const dagcon_pre_batch *batch, dagcon_results *results);
 
 /*
+ * Alignments as current aligners write them (SAM): one ungapped read, a position and a CIGAR per record, against
+ * target bases that are held once per target.  The records are expanded into the pair of gapped strings of
+ * dagcon_batch on the device and then take the path of dagcon_consensus: the result is, byte for byte, that of
+ * dagcon_consensus on the expanded strings.  The strings never exist on the host.  Expansion of one record, with
+ * q its read bases, t its target's bases, qi = 0 and ti = pos - 1:
+ *   M, =, X of length L:  L columns (q[qi++], t[ti++]);
+ *   I:                    L columns (q[qi++], '-');
+ *   D:                    L columns ('-', t[ti++]);
+ *   S:                    qi += L, no column;        H, P: nothing.
+ * Bytes are copied verbatim (case, N, anything else).  aln_start = pos, aln_len = the number of columns.
+ * A record is non-conforming when an op code is above 8 or is N (3), an op has length 0, the ops do not consume
+ * exactly q_len read bases, pos == 0, pos - 1 + the target bases consumed > tlen, or one of its three totals
+ * (columns, read bases, target bases) does not fit 32 bits.  Its target gets target_status =
+ * DAGCON_ERR_NONCONFORMING and no segments whatever its coverage; the rest of the batch is complete and exact, as
+ * dagcon_consensus confines a failure.  A sequence that runs past its blob (t_off + tlen > t_bytes, q_off + q_len >
+ * q_bytes) or a rec_begin / op_begin that is not monotone is DAGCON_ERR_INVALID_ARG for the call, found on the host
+ * before anything is launched.  After the expansion everything is dagcon_consensus: min_cov counts the records of a
+ * target, min_len the columns of a record, then normalizeGaps, trimAln, an 'N' backbone filled in by the reads
+ * (t_blob feeds the tstr side only; consensus on the real backbone is not offered here).  All flags keep their
+ * meaning (RAW_ALIGNMENTS, STOP_AFTER_*, BASE_SUPPORT with dagcon_fetch_support); LOCAL_ALIGN is ignored as
+ * dagcon_consensus ignores it.
+ */
+typedef struct dagcon_cigar_batch {
+    uint32_t n_targets;
+    const uint32_t *tlen;        /* [n_targets] */
+    const uint64_t *t_off;       /* [n_targets] target bases: t_blob[t_off .. + tlen) */
+    const char *t_blob;
+    uint64_t t_bytes;
+    const uint64_t *rec_begin;   /* [n_targets + 1] records of target g, in addAln order */
+    const uint32_t *pos;         /* [n_rec] 1-based leftmost target base (SAM POS) = Alignment::start */
+    const uint64_t *q_off;       /* [n_rec] read bases as SAM SEQ has them (target orientation) */
+    const uint32_t *q_len;
+    const char *q_blob;
+    uint64_t q_bytes;
+    const uint64_t *op_begin;    /* [n_rec + 1] into ops */
+    const uint32_t *ops;         /* BAM encoding: len << 4 | op, op 0..8 = M I D N S H P = X */
+} dagcon_cigar_batch;
+int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *batch);   /* then dagcon_run / _sync / _fetch as ever */
+int dagcon_consensus_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, dagcon_results *results);
+
+/*
  * Debug / parity aid: adjacency of one target's graph as left by the last
  * dagcon_run (after mergeNodes), in list order.  Vertex ids are in backbone
  * position order: the inserted vertices whose _bbMap is p (in read, column

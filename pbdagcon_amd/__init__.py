@@ -1,6 +1,7 @@
 """pbdagcon_amd -- MI355X-native DAGCon consensus (the pbdagcon hot path).
 
-    capi        ctypes binding of include/dagcon.h (libdagcon_hip.so, HIP/gfx950)
+    capi        ctypes binding of include/dagcon.h (libdagcon_hip.so, HIP/gfx950):
+                Context, HostBatch, HostCigarBatch / CigarBatch (SAM-style input), ...
     consensus   host-side mirror of the reference interface (Alignment,
                 normalizeGaps, trimAln, AlnGraphBoost, CnsResult)
     synth       deterministic synthetic pileups

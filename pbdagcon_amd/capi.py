@@ -34,7 +34,7 @@ EXPORTS = [
     "dagcon_fetch", "dagcon_get_timings", "dagcon_normalize", "dagcon_debug_graph",
     "dagcon_debug_counters", "dagcon_host_alloc", "dagcon_host_free", "dagcon_align",
     "dagcon_consensus_pre", "dagcon_debug_plan", "dagcon_align_dropped", "dagcon_align_panels",
-    "dagcon_align_ends", "dagcon_place", "dagcon_fetch_support",
+    "dagcon_align_ends", "dagcon_place", "dagcon_fetch_support", "dagcon_upload_cigar", "dagcon_consensus_cigar",
 ]
 ABI_VERSION = 2
 
@@ -63,6 +63,13 @@ class PreBatch(C.Structure):
                 ("tstart", C.c_void_p), ("strand", C.c_void_p), ("q_off", C.c_void_p), ("q_len", C.c_void_p),
                 ("t_off", C.c_void_p), ("t_len", C.c_void_p), ("q_blob", C.c_void_p), ("q_bytes", C.c_uint64),
                 ("t_blob", C.c_void_p), ("t_bytes", C.c_uint64)]
+
+
+class CigarBatch(C.Structure):
+    _fields_ = [("n_targets", C.c_uint32), ("tlen", C.c_void_p), ("t_off", C.c_void_p), ("t_blob", C.c_void_p),
+                ("t_bytes", C.c_uint64), ("rec_begin", C.c_void_p), ("pos", C.c_void_p), ("q_off", C.c_void_p),
+                ("q_len", C.c_void_p), ("q_blob", C.c_void_p), ("q_bytes", C.c_uint64), ("op_begin", C.c_void_p),
+                ("ops", C.c_void_p)]
 
 
 class Results(C.Structure):
@@ -134,6 +141,8 @@ def load() -> C.CDLL:
     L.dagcon_align_ends.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
     L.dagcon_place.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32,
                                vp, vp, vp, vp, vp]
+    L.dagcon_upload_cigar.argtypes = [vp, C.POINTER(CigarBatch)]
+    L.dagcon_consensus_cigar.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Results)]
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
     L.dagcon_host_free.restype = None
@@ -213,6 +222,78 @@ class HostBatch:
                          self.aln_len[idx], self.qstr, self.tstr,
                          self.backbone, None if self.backbone_off is None else self.backbone_off[targets],
                          None if self.ids is None else [self.ids[t] for t in targets])
+
+
+CIGAR_OPS = b"MIDNSHP=X"      # BAM op codes 0..8
+
+
+class HostCigarBatch:
+    """numpy view of a dagcon_cigar_batch: per record a position, an ungapped read and BAM-encoded CIGAR ops
+    (len << 4 | op), per target its bases once."""
+
+    def __init__(self, tlen, t_off, t_blob, rec_begin, pos, q_off, q_len, q_blob, op_begin, ops, ids=None):
+        def u8(x):
+            return np.ascontiguousarray(np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else x,
+                                        dtype=np.uint8)
+        self.tlen = np.ascontiguousarray(tlen, dtype=np.uint32)
+        self.t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        self.t_blob = u8(t_blob)
+        self.rec_begin = np.ascontiguousarray(rec_begin, dtype=np.uint64)
+        self.pos = np.ascontiguousarray(pos, dtype=np.uint32)
+        self.q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        self.q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+        self.q_blob = u8(q_blob)
+        self.op_begin = np.ascontiguousarray(op_begin, dtype=np.uint64)
+        self.ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        self.ids = ids
+
+    @classmethod
+    def from_records(cls, targets, ids=None):
+        """targets = [(target bases, [(pos, read bases, [(op char or code, length)])])]."""
+        tlen, t_off, rec_begin, pos, q_off, q_len, op_begin, ops = [], [], [0], [], [], [], [0], []
+        tb, qb = [], []
+        tp = qp = 0
+        for tseq, recs in targets:
+            tlen.append(len(tseq)); t_off.append(tp); tb.append(tseq); tp += len(tseq)
+            for ps, q, cig in recs:
+                pos.append(ps); q_off.append(qp); q_len.append(len(q)); qb.append(q); qp += len(q)
+                for op, ln in cig:
+                    code = op if isinstance(op, int) else CIGAR_OPS.index(op.encode() if isinstance(op, str) else op)
+                    ops.append((int(ln) << 4) | code)
+                op_begin.append(len(ops))
+            rec_begin.append(len(pos))
+        return cls(tlen, t_off, b"".join(tb), rec_begin, pos, q_off, q_len, b"".join(qb), op_begin, ops, ids)
+
+    @property
+    def n_targets(self):
+        return int(self.tlen.size)
+
+    @property
+    def n_records(self):
+        return int(self.pos.size)
+
+    @property
+    def nbytes(self):
+        """Bytes the call carries to the device: both blobs, the ops and the per-record / per-target arrays."""
+        return int(sum(a.nbytes for a in (self.tlen, self.t_off, self.t_blob, self.rec_begin, self.pos, self.q_off,
+                                          self.q_len, self.q_blob, self.op_begin, self.ops)))
+
+    def c_struct(self) -> CigarBatch:
+        b = CigarBatch()
+        b.n_targets = self.n_targets
+        b.tlen = self.tlen.ctypes.data
+        b.t_off = self.t_off.ctypes.data
+        b.t_blob = self.t_blob.ctypes.data
+        b.t_bytes = self.t_blob.size
+        b.rec_begin = self.rec_begin.ctypes.data
+        b.pos = self.pos.ctypes.data
+        b.q_off = self.q_off.ctypes.data
+        b.q_len = self.q_len.ctypes.data
+        b.q_blob = self.q_blob.ctypes.data
+        b.q_bytes = self.q_blob.size
+        b.op_begin = self.op_begin.ctypes.data
+        b.ops = self.ops.ctypes.data
+        return b
 
 
 class Context:
@@ -344,6 +425,22 @@ class Context:
         b = batch.c_struct()
         r = Results()
         self._chk(self.L.dagcon_consensus(self.h, C.byref(b), C.byref(r)))
+        out = self._keep_segs(r)
+        self._status(r, strict)
+        return out
+
+    def upload_cigar(self, batch: HostCigarBatch):
+        """dagcon_upload_cigar: then run / sync / fetch as after upload."""
+        self._keep = batch
+        b = batch.c_struct()
+        self._chk(self.L.dagcon_upload_cigar(self.h, C.byref(b)))
+
+    def consensus_cigar(self, batch: HostCigarBatch, strict=True):
+        """Per target: [(range0, range1, seq_bytes)], from (position, read, CIGAR) records expanded on the device."""
+        self._keep = batch
+        b = batch.c_struct()
+        r = Results()
+        self._chk(self.L.dagcon_consensus_cigar(self.h, C.byref(b), C.byref(r)))
         out = self._keep_segs(r)
         self._status(r, strict)
         return out

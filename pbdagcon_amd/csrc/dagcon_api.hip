@@ -24,6 +24,7 @@
 #include "k_align.hip.h"
 #include "k_align_panels.hip.h"
 #include "k_place.hip.h"
+#include "k_cigar.hip.h"
 
 namespace {
 
@@ -130,6 +131,9 @@ struct Ctx {
     DevBuf d_al[15];                                // dagcon_align: blobs, offsets, outputs, directions, launch order, widths, ends
     DevBuf d_pn[18];                                // dagcon_align_panels: blobs, panels, scratch, outputs, launch order
     DevBuf d_pl[14];                                // dagcon_place: blob, sequences, tables, pairs, outputs
+    DevBuf d_cg[11];                                // dagcon_upload_cigar: ops, op / tile begins, totals, checkpoints, blobs, offsets
+    std::vector<uint8_t> h_cig_bad;                 // dagcon_upload_cigar: targets with a non-conforming record (empty: another upload)
+    std::string cig_err;                            // the first of them, for dagcon_last_error
     DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
     DevBuf d_sup_tmp, d_sup_tmp0, d_sup;           // DAGCON_FLAG_BASE_SUPPORT: walk scratch (4 B per vertex), output (2 x 2 B per base)
 
@@ -525,6 +529,7 @@ void dagcon_destroy(dagcon_ctx *ctx) {
     for (DevBuf &b : c->d_al) free_buf(b);
     for (DevBuf &b : c->d_pn) free_buf(b);
     for (DevBuf &b : c->d_pl) free_buf(b);
+    for (DevBuf &b : c->d_cg) free_buf(b);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -536,6 +541,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
     c->sup_valid = false;
+    c->h_cig_bad.clear();
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->aln_begin)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/aln_begin is NULL");
     const uint64_t A_all = T ? b->aln_begin[T] : 0;
@@ -663,7 +669,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     // inputs -> HBM
     ENSURE(c, c->d_q, b->blob_bytes);
     ENSURE(c, c->d_t, b->blob_bytes);
-    if (b->blob_bytes) {
+    if (b->blob_bytes && !(dev_q == c->d_q.p && dev_t == c->d_t.p)) {     // (dagcon_upload_cigar expands into d_q / d_t themselves)
         HIPCHK(c, hipMemcpyAsync(c->d_q.p, dev_q ? dev_q : b->qstr, b->blob_bytes, dev_q ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_t.p, dev_t ? dev_t : b->tstr, b->blob_bytes, dev_t ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     }
@@ -850,6 +856,12 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
             else if (f & DG_E_TOO_BIG) fail(c, code, "target %u too large (more than 2^25 - 3 vertices or 2^30 pool words)", t);
             else fail(c, code, "device invariant violated in target %u", t);
         }
+    }
+    // dagcon_upload_cigar: a target with a non-conforming record had none of its records expanded
+    for (uint32_t t = 0; t < T && !c->h_cig_bad.empty(); t++) {
+        if (!c->h_cig_bad[t] || c->r_status[t] != DAGCON_OK) continue;
+        c->r_status[t] = DAGCON_ERR_NONCONFORMING;
+        if (!n_failed++) c->err = c->cig_err;
     }
     const uint64_t nseg = c->h_st.seg_top, nb = c->h_st.cns_top;
     c->r_cns_off.assign(T, 0); c->r_cns_len.assign(T, 0); c->r_seg_first.assign(T, 0); c->r_n_seg.assign(T, 0);
@@ -1590,6 +1602,129 @@ int dagcon_consensus_pre(dagcon_ctx *ctx, const dagcon_pre_batch *b, dagcon_resu
     db.aln_start = start.data(); db.aln_off = out_off.data(); db.aln_len = alen.data();
     db.blob_bytes = n ? out_bytes : 0;
     int r = upload_impl(ctx, &db, n ? c->d_al[7].p : nullptr, n ? c->d_al[8].p : nullptr);
+    if (r != DAGCON_OK) return r;
+    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
+    return dagcon_fetch(ctx, results);
+}
+
+// SAM-style input: position + ungapped read + CIGAR per record, target bases once per target.  k_cigar_scan sizes
+// every record, the host plans the string blobs as for any batch, k_cigar_expand writes them into d_q / d_t, and
+// upload_impl takes them from there (the door dagcon_consensus_pre uses)
+int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
+    if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    c->uploaded = c->ran = c->fetched = false;
+    c->sup_valid = false;
+    const uint32_t T = b->n_targets;
+    if (T && (!b->tlen || !b->rec_begin || !b->t_off)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
+    const uint64_t n64 = T ? b->rec_begin[T] : 0;
+    if (n64 > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many records");
+    const uint32_t n = (uint32_t)n64;
+    if (n && (!b->pos || !b->q_off || !b->q_len || !b->op_begin)) return fail(c, DAGCON_ERR_INVALID_ARG, "record arrays are NULL");
+    if (T && b->rec_begin[0] != 0) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin does not start at 0");
+    for (uint32_t g = 0; g < T; g++) {
+        if (b->rec_begin[g + 1] < b->rec_begin[g] || b->rec_begin[g + 1] > n64) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin not monotone at target %u", g);
+        if (b->t_off[g] > b->t_bytes || b->tlen[g] > b->t_bytes - b->t_off[g]) return fail(c, DAGCON_ERR_INVALID_ARG, "target %u runs past t_blob", g);
+        if (b->tlen[g] && !b->t_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "t_blob is NULL");
+    }
+    std::vector<uint64_t> tile_begin((size_t)n + 1, 0);
+    for (uint32_t a = 0; a < n; a++) {
+        if (b->op_begin[a + 1] < b->op_begin[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "op_begin not monotone at record %u", a);
+        if (b->q_off[a] > b->q_bytes || b->q_len[a] > b->q_bytes - b->q_off[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "record %u runs past q_blob", a);
+        if (b->q_len[a] && !b->q_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "q_blob is NULL");
+        tile_begin[a + 1] = tile_begin[a] + (b->op_begin[a + 1] - b->op_begin[a] + 63u) / 64u;
+    }
+    const uint64_t n_ops = n ? b->op_begin[n] - b->op_begin[0] : 0, n_tiles = tile_begin[n];
+    if (n_ops && !b->ops) return fail(c, DAGCON_ERR_INVALID_ARG, "ops is NULL");
+    if (n_tiles > 0x7FFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many CIGAR ops");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DevBuf &d_ops = c->d_cg[0], &d_opb = c->d_cg[1], &d_tileb = c->d_cg[2], &d_tot = c->d_cg[3], &d_ck = c->d_cg[4],
+           &d_qb = c->d_cg[5], &d_tb = c->d_cg[6], &d_qoff = c->d_cg[7], &d_tbase = c->d_cg[8], &d_out = c->d_cg[9];
+    // op_begin as the caller has it, less its first entry (ops are uploaded from there)
+    std::vector<uint64_t> opb((size_t)n + 1, 0);
+    for (uint32_t a = 0; a <= n && n; a++) opb[a] = b->op_begin[a] - b->op_begin[0];
+    ENSURE(c, d_ops, n_ops * 4); ENSURE(c, d_tot, (size_t)n * 16); ENSURE(c, d_ck, n_tiles * 16);
+    ENSURE(c, d_qb, b->q_bytes); ENSURE(c, d_tb, b->t_bytes); ENSURE(c, d_qoff, (size_t)n * 8);
+    if (n_ops) HIPCHK(c, hipMemcpyAsync(d_ops.p, b->ops + b->op_begin[0], n_ops * 4, hipMemcpyHostToDevice, s));
+    if (b->q_bytes && b->q_blob) HIPCHK(c, hipMemcpyAsync(d_qb.p, b->q_blob, b->q_bytes, hipMemcpyHostToDevice, s));
+    if (b->t_bytes && b->t_blob) HIPCHK(c, hipMemcpyAsync(d_tb.p, b->t_blob, b->t_bytes, hipMemcpyHostToDevice, s));
+    if (n) HIPCHK(c, hipMemcpyAsync(d_qoff.p, b->q_off, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    int r;
+    if ((r = upload_vec(c, d_opb, opb))) return r;
+    if ((r = upload_vec(c, d_tileb, tile_begin))) return r;
+    DgCigarParams p;
+    memset(&p, 0, sizeof p);
+    p.ops = (const uint32_t *)d_ops.p; p.op_begin = (const uint64_t *)d_opb.p; p.tile_begin = (const uint64_t *)d_tileb.p;
+    p.n = n; p.n_tiles = (uint32_t)n_tiles;
+    p.totals = (uint4 *)d_tot.p; p.ckpt = (uint4 *)d_ck.p;
+    std::vector<uint32_t> tot((size_t)n * 4);
+    if (n) {
+        hipLaunchKernelGGL(k_cigar_scan, dim3((n + 3u) / 4u), dim3(256), 0, s, p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, d2h(c, tot.data(), d_tot.p, (size_t)n * 16));
+    }
+    // what every record is: the targets with a non-conforming one lose all their records
+    std::vector<uint8_t> bad(T, 0);
+    std::string first_err;
+    for (uint32_t g = 0; g < T; g++)
+        for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
+            const uint32_t nq = tot[a * 4 + 1], nt = tot[a * 4 + 2], fl = tot[a * 4 + 3];
+            const char *why = (fl & DG_CG_BAD_OP) ? "an op code above 8 or N"
+                            : (fl & DG_CG_ZERO_LEN) ? "an op of length 0"
+                            : (fl & DG_CG_OVERFLOW) ? "a total past 32 bits"
+                            : b->pos[a] == 0 ? "pos is 0"
+                            : nq != b->q_len[a] ? "the ops do not consume exactly q_len read bases"
+                            : (uint64_t)b->pos[a] - 1u + nt > b->tlen[g] ? "target bases past tlen" : nullptr;
+            if (!why) continue;
+            if (first_err.empty()) {
+                char buf[256];
+                snprintf(buf, sizeof buf, "target %u: record %llu is non-conforming (%s)", g, (unsigned long long)a, why);
+                first_err = buf;
+            }
+            bad[g] = 1;
+        }
+    // the batch upload_impl sees: the records of the other targets, strings planned as dagcon_consensus_pre plans them
+    // (a target below min_cov is skipped whatever it holds: it goes in without records, and nothing of it is expanded)
+    std::vector<uint64_t> beg2((size_t)T + 1, 0), off2, out_off((size_t)n, DG_CG_SKIP), t_base((size_t)n, 0);
+    std::vector<uint32_t> start2, len2;
+    uint64_t bytes = 0;
+    for (uint32_t g = 0; g < T; g++) {
+        beg2[g] = start2.size();
+        const uint64_t k = b->rec_begin[g + 1] - b->rec_begin[g];
+        if (bad[g] || k == 0 || k < c->opts.min_cov) continue;
+        for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
+            out_off[a] = bytes; t_base[a] = b->t_off[g] + b->pos[a] - 1u;
+            start2.push_back(b->pos[a]); off2.push_back(bytes); len2.push_back(tot[a * 4]);
+            bytes += ((uint64_t)tot[a * 4] + 15ull) & ~15ull;
+        }
+    }
+    beg2[T] = start2.size();
+    ENSURE(c, c->d_q, bytes); ENSURE(c, c->d_t, bytes);
+    if ((r = upload_vec(c, d_tbase, t_base))) return r;
+    if ((r = upload_vec(c, d_out, out_off))) return r;
+    if (n_tiles && bytes) {
+        p.q = (const uint8_t *)d_qb.p; p.t = (const uint8_t *)d_tb.p;
+        p.q_off = (const uint64_t *)d_qoff.p; p.t_base = (const uint64_t *)d_tbase.p; p.out_off = (const uint64_t *)d_out.p;
+        p.out_q = (uint8_t *)c->d_q.p; p.out_t = (uint8_t *)c->d_t.p;
+        hipLaunchKernelGGL(k_cigar_expand, dim3((uint32_t)n_tiles), dim3(64), 0, s, p);
+        HIPCHK(c, hipGetLastError());
+    }
+    dagcon_batch db;
+    memset(&db, 0, sizeof db);
+    db.n_targets = T; db.tlen = b->tlen; db.aln_begin = beg2.data();
+    db.aln_start = start2.data(); db.aln_off = off2.data(); db.aln_len = len2.data();
+    db.blob_bytes = bytes;
+    r = upload_impl(ctx, &db, c->d_q.p, c->d_t.p);                 // (synchronises the stream: the locals above may go)
+    if (r != DAGCON_OK) { (void)hipStreamSynchronize(s); return r; }
+    c->h_cig_bad = bad;
+    c->cig_err = first_err;
+    return DAGCON_OK;
+}
+
+int dagcon_consensus_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, dagcon_results *results) {
+    if (!results) return DAGCON_ERR_INVALID_ARG;
+    int r = dagcon_upload_cigar(ctx, batch);
     if (r != DAGCON_OK) return r;
     if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
     return dagcon_fetch(ctx, results);

@@ -17,6 +17,8 @@
 //     banded aligner on the GPU (dagcon_align): blasr_libcpp is absent, the stage is pinned to the
 //     reference by its one known-answer test only (test/cpp/SimpleAlignerTest.cpp:8-21); global by
 //     default, local ends with --local (DAGCON_FLAG_LOCAL_ALIGN, the reference's SDPAlign(..., Local));
+//   * --sam --ref: SAM text (one ungapped read, a position and a CIGAR per record) against a FASTA of the targets; the
+//     gapped strings are made on the GPU (dagcon_consensus_cigar), never on the host (sam.h);
 //   * blank lines are skipped (the reference duplicates the previous record, Q9);
 //   * a missing input file is an error on stderr, exit 1 (the reference is silent, Q11).
 #include <algorithm>
@@ -30,6 +32,7 @@
 #include <string>
 #include <chrono>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include <fcntl.h>
@@ -39,6 +42,7 @@
 
 #include "../../../include/dagcon.h"
 #include "fastq.h"
+#include "sam.h"
 
 namespace {
 
@@ -46,6 +50,8 @@ struct Opts {
     unsigned threads = 4, min_cov = 6, min_len = 500, trim = 50;
     bool align = false, verbose = false, dump = false;
     bool local = false;                // --local (with -a): the first alignment of every record has local ends
+    bool sam = false;                  // --sam: SAM text, the targets' bases from --ref (dagcon_consensus_cigar)
+    std::string ref;                   // --ref FASTA
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
     int pinned = -1;                   // --pinned 0|1: page-locked blobs (-1: when the input is several batches long)
@@ -60,7 +66,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam --ref <fasta>] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -73,6 +79,13 @@ void usage(FILE *f) {
             "                      known-answer test)\n"
             "  --local             with -a: align local ends, so read ends that do not align stay out of the graph (the record\n"
             "                      starts at tstart + the first aligned target base); --polish rounds stay global\n"
+            "  --sam               input is SAM text, records of one RNAME consecutive (a coordinate-sorted SAM is): FLAG, RNAME,\n"
+            "                      POS, CIGAR and SEQ are used, the target's bases come from --ref; records with FLAG 0x4 or\n"
+            "                      0x100, or RNAME, CIGAR or SEQ '*', are skipped (counted with -v).  The gapped strings are made\n"
+            "                      on the GPU; the output is that of the .m5 input with the same alignments.  Not with -a,\n"
+            "                      --local or --polish.  BAM, PAF and MD:Z-only input (no FASTA) are not read\n"
+            "  --ref FASTA         with --sam (required): the target sequences, by the name up to the first blank; an @SQ line\n"
+            "                      whose LN differs from the sequence of its SN is an error\n"
             "  --fastq             write FASTQ (@id/r0_r1, sequence, +, qualities) instead of FASTA; the same records in the\n"
             "                      same order.  The quality of a base is this build's own definition: a Laplace-smoothed\n"
             "                      fraction of the reads at its position that do not pass through its consensus vertex,\n"
@@ -87,7 +100,7 @@ void usage(FILE *f) {
             "                      targets dealt round-robin, records still printed in input order\n"
             "  --contexts N        consensus workers (thread + context) per GPU, 1..4: a batch's upload and formatting run\n"
             "                      beside another batch's kernels (default: 2 for inputs of several batches, else 1)\n"
-            "  <input>             BLASR -m 5 file (.pre with -a) sorted by target, or - for stdin\n"
+            "  <input>             BLASR -m 5 file (.pre with -a, SAM with --sam) sorted by target, or - for stdin\n"
             "  version 0.3 (dagcon-mi355x)\n");
 }
 
@@ -115,6 +128,11 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "-a" || a == "--align") o.align = true;
         else if (a == "--local") o.local = true;
         else if (a == "--fastq") o.fastq = true;
+        else if (a == "--sam") o.sam = true;
+        else if (a == "--ref") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --ref needs a FASTA file\n"); return 2; }
+            o.ref = argv[++i];
+        }
         else if (a == "-v" || a == "--verbose") o.verbose = true;
         else if (a == "--dump-parsed") o.dump = true;            // test hook: parser only, no GPU
         else if (a == "--slab-bytes") { unsigned v = 0; if (!need(&v)) return 2; o.slab_bytes = v; }   // test hook
@@ -144,6 +162,9 @@ int parse_args(int argc, char **argv, Opts &o) {
         } else { fprintf(stderr, "PARSE ERROR: unknown argument %s\n", a.c_str()); return 2; }
     }
     if (o.local && !o.align) { fprintf(stderr, "PARSE ERROR: --local needs -a\n"); return 2; }
+    if (o.sam && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --sam does not go with -a, --local or --polish\n"); return 2; }
+    if (o.sam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --sam needs --ref <fasta>\n"); return 2; }
+    if (!o.sam && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam\n"); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
     return 0;
 }
@@ -203,10 +224,13 @@ struct Batch {
     std::vector<uint32_t> tlen, start, len, len2;          // len2 / off2: the target sequence of a .pre record
     std::vector<uint64_t> begin{0}, off, off2;
     std::vector<char> strand;
+    std::vector<uint64_t> toff, opb{0};                    // --sam: the target's bases in t (per target); first op of each record
+    std::vector<const char *> tsrc;                        // --sam: where the target's bases come from (per target)
+    std::vector<uint32_t> ops;                             // --sam: BAM-encoded CIGAR ops of all records
     Blob q, t;
     unsigned long long seq = 0;        // position in the input: records are printed in this order
     std::string out;                   // the batch's FASTA records
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); q.n = 0; t.n = 0; out.clear(); }
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); q.n = 0; t.n = 0; out.clear(); }
 };
 
 bool g_timing = false;                                    // PBDAGCON_TIMING
@@ -233,7 +257,19 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
     dagcon_results r;
     int rc = DAGCON_OK;
     bool have_results = false;
-    if (o.align && !o.polish) {
+    if (o.sam) {
+        // position + read + CIGAR per record, the target's bases once: expanded on the device
+        dagcon_cigar_batch cb;
+        memset(&cb, 0, sizeof cb);
+        cb.n_targets = db.n_targets; cb.tlen = b.tlen.data(); cb.t_off = b.toff.data();
+        cb.t_blob = b.t.data(); cb.t_bytes = b.t.size(); cb.rec_begin = b.begin.data();
+        cb.pos = b.start.data(); cb.q_off = b.off.data(); cb.q_len = b.len.data();
+        cb.q_blob = b.q.data(); cb.q_bytes = b.q.size(); cb.op_begin = b.opb.data(); cb.ops = b.ops.data();
+        const double ta0 = wall();
+        rc = dagcon_consensus_cigar(ctx, &cb, &r);
+        if (g_timing) fprintf(stderr, "pbdagcon timing: --sam batch of %zu records: dagcon_consensus_cigar %.3f\n", b.start.size(), wall() - ta0);
+        have_results = true;
+    } else if (o.align && !o.polish) {
         // main.cpp:117-145 with -a in one call: the aligned strings stay on the device
         const size_t A = b.start.size();
         dagcon_pre_batch pb;
@@ -426,7 +462,8 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
         // AlnGraphBoost.cpp:71-72): warn, go on with the rest
         if (r.target_status[g] != DAGCON_OK)
             fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(),
-                    r.target_status[g] == DAGCON_ERR_NONCONFORMING ? "an alignment leaves the backbone or holds a non-printable byte"
+                    r.target_status[g] == DAGCON_ERR_NONCONFORMING && o.sam ? "a record's CIGAR does not fit its SEQ or its target, or holds N or a length of 0"
+                    : r.target_status[g] == DAGCON_ERR_NONCONFORMING ? "an alignment leaves the backbone or holds a non-printable byte"
                     : r.target_status[g] == DAGCON_ERR_UNSUPPORTED ? "too large" : "internal error");
         for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
             // main.cpp:141-143  ">%s/%d_%d\n%s\n"; --fastq: '@' for '>' (src/cpp/pbdagcon_wf.sh:20-22), then + and qualities
@@ -482,6 +519,16 @@ int main(int argc, char **argv) {
             data = (const char *)map;
         }
         close(fd);
+    }
+
+    // ---- --sam: the targets' bases, and the header's @SQ lines against them ----
+    DgRefSeqs ref;
+    if (o.sam) {
+        std::string err;
+        if (!dg_read_fasta(o.ref, ref, err) || !dg_sam_check_header(data, size, ref, err)) {
+            fprintf(stderr, "pbdagcon: %s\n", err.c_str());
+            return 1;
+        }
     }
 
     // ---- consensus workers: one thread + context per GPU (the reference starts its N consensus
@@ -611,8 +658,12 @@ int main(int argc, char **argv) {
         const char *id, *name, *q, *t;
         uint32_t idl, namel, len, tlen, start, tl;   // tl: length of the target sequence (.pre); len: of the query string
         char strand;
+        const char *cg; uint32_t cgl, nops;          // --sam: the CIGAR field and its number of ops (t: the target's bases in --ref)
+        unsigned long long line;                     // --sam: line of the input
     };
-    struct Part { std::vector<Rec> recs; int err = 0; unsigned long long err_rec = 0; int err_nf = 0; };
+    struct Part { std::vector<Rec> recs; int err = 0; unsigned long long err_rec = 0; int err_nf = 0; unsigned long long lines = 0, skipped = 0; };
+    unsigned long long n_lines_before = 0, n_skipped = 0;
+    std::unordered_set<std::string> seen_targets;         // --sam: a target whose records come back after another's is an error
     const unsigned nthr = std::max(1u, std::min(o.threads, 64u));
     // the text is taken a slab at a time, so that the first batch reaches the GPU before the
     // whole file has been indexed; the records of a slab's last (possibly unfinished) target
@@ -638,7 +689,7 @@ int main(int argc, char **argv) {
         }
         auto index = [&](unsigned k) {
             Part &pt = parts[k];
-            pt.recs.clear(); pt.err = 0;
+            pt.recs.clear(); pt.err = 0; pt.lines = 0; pt.skipped = 0;
             size_t pos = cut[k];
             const size_t stop = cut[k + 1];
             while (pos < stop) {
@@ -647,6 +698,40 @@ int main(int argc, char **argv) {
                 size_t ll = nl ? (size_t)(nl - line) : size - pos;
                 pos += ll + (nl ? 1 : 0);
                 if (ll && line[ll - 1] == '\r') ll--;
+                pt.lines++;
+                if (o.sam) {
+                    // QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL, tab-separated; header lines skipped
+                    if (ll == 0 || line[0] == '@') continue;
+                    const char *sf[10];
+                    size_t sl[10];
+                    int snf = 0;
+                    for (size_t i = 0; snf < 10; snf++) {
+                        const char *tab = (const char *)memchr(line + i, '\t', ll - i);
+                        const size_t j = tab ? (size_t)(tab - line) : ll;
+                        sf[snf] = line + i; sl[snf] = j - i;
+                        if (!tab) { snf++; break; }
+                        i = j + 1;
+                    }
+                    if (snf < 10) { pt.err = 1; pt.err_rec = pt.lines; pt.err_nf = snf; return; }
+                    const uint32_t flag = tok_u32(sf[1], sl[1]);
+                    auto star = [&](int x) { return sl[x] == 1 && sf[x][0] == '*'; };
+                    if ((flag & (DG_SAM_UNMAPPED | DG_SAM_SECONDARY)) || star(2) || star(5) || star(9)) { pt.skipped++; continue; }
+                    const long nops = dg_cigar_ops(sf[5], sl[5], nullptr);
+                    if (nops < 0) { pt.err = 3; pt.err_rec = pt.lines; return; }
+                    const DgRefSeqs::Span *sp = ref.find(sf[2], sl[2]);
+                    if (!sp) { pt.err = 4; pt.err_rec = pt.lines; return; }
+                    Rec r;
+                    r.id = sf[2]; r.idl = (uint32_t)sl[2];
+                    r.name = sf[0]; r.namel = (uint32_t)sl[0];
+                    r.q = sf[9]; r.len = (uint32_t)sl[9];
+                    r.t = ref.bases.data() + sp->off; r.tlen = sp->len; r.tl = 0;
+                    r.start = tok_u32(sf[3], sl[3]);             // SAM POS is 1-based, as Alignment::start
+                    r.strand = (flag & DG_SAM_REVERSE) ? '-' : '+';   // (SEQ is in the target's orientation either way)
+                    r.cg = sf[5]; r.cgl = (uint32_t)sl[5]; r.nops = (uint32_t)nops;
+                    r.line = pt.lines;
+                    pt.recs.push_back(r);
+                    continue;
+                }
                 const char *f[19];
                 size_t fl[19];
                 int nf = 0;
@@ -694,6 +779,19 @@ int main(int argc, char **argv) {
         recs.clear();
         for (const Rec &r : carry) recs.push_back(&r);
         for (unsigned k = 0; k < nthr; k++) {
+            if (o.sam) {                                       // line numbers of the whole input
+                for (Rec &r : parts[k].recs) r.line += n_lines_before;
+                n_skipped += parts[k].skipped;
+                if (parts[k].err) {
+                    const unsigned long long ln = n_lines_before + parts[k].err_rec;
+                    if (parts[k].err == 1) fprintf(stderr, "pbdagcon: format error: line %llu has %d fields, 11 expected\n", ln, parts[k].err_nf);
+                    else if (parts[k].err == 3) fprintf(stderr, "pbdagcon: format error: line %llu: malformed CIGAR\n", ln);
+                    else fprintf(stderr, "pbdagcon: line %llu: RNAME is not a sequence of %s\n", ln, o.ref.c_str());
+                    for (const Rec &r : parts[k].recs) recs.push_back(&r);
+                    had_error = true; break;
+                }
+                n_lines_before += parts[k].lines;
+            }
             for (const Rec &r : parts[k].recs) recs.push_back(&r);
             n_rec_before += parts[k].recs.size();
             if (parts[k].err == 1) {
@@ -711,11 +809,17 @@ int main(int argc, char **argv) {
         dagcon_ctx *pin = nullptr;
         if (want_pin) { std::lock_guard<std::mutex> lk(mu); pin = pin_ctx; }
         if (!b.q.resize(bytes, pin) || !b.t.resize(bytes2, pin)) { fprintf(stderr, "pbdagcon: out of memory\n"); exit(1); }
+        if (o.sam) b.ops.resize(b.opb.back());
         auto work = [&](unsigned k) {
+            if (o.sam)                                            // the targets' bases, once each
+                for (size_t g = k; g < b.tsrc.size(); g += nthr) memcpy(b.t.data() + b.toff[g], b.tsrc[g], b.tlen[g]);
             for (size_t x = r0 + k; x < r1; x += nthr) {
                 const Rec &r = *recs[x];
                 char *dq = b.q.data() + b.off[x - r0], *dt = b.t.data() + b.off2[x - r0];
-                if (o.align) {                                    // .pre: sequences as they are (Alignment.cpp:112)
+                if (o.sam) {                                      // SEQ as it is; the CIGAR as BAM-encoded ops
+                    memcpy(dq, r.q, r.len);
+                    dg_cigar_ops(r.cg, r.cgl, b.ops.data() + b.opb[x - r0]);
+                } else if (o.align) {                                    // .pre: sequences as they are (Alignment.cpp:112)
                     memcpy(dq, r.q, r.len);
                     memcpy(dt, r.t, r.tl);
                 } else if (r.strand == '-') {                            // Alignment.cpp:69-75: start is NOT flipped (Q6)
@@ -769,6 +873,12 @@ int main(int argc, char **argv) {
                             const size_t o0 = b.off[y - rb];
                             size_t g = 0;
                             while (b.begin[g + 1] <= y - rb) g++;
+                            if (o.sam) {                       // RNAME, its length in --ref, POS, strand, QNAME, SEQ, CIGAR (from the ops)
+                                printf("%.*s\t%u\t%u\t%c\t%.*s\t%.*s\t%s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
+                                       (int)r.namel, r.name, (int)r.len, b.q.data() + o0,
+                                       dg_cigar_text(b.ops.data() + b.opb[y - rb], b.opb[y - rb + 1] - b.opb[y - rb]).c_str());
+                                continue;
+                            }
                             printf("%.*s\t%u\t%u\t%c\t%.*s\t%.*s\t%.*s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
                                    (int)r.namel, r.name, (int)r.len, b.q.data() + o0, (int)r.tl, b.t.data() + b.off2[y - rb]);
                         }
@@ -780,10 +890,18 @@ int main(int argc, char **argv) {
             }
             const Rec &r = *recs[x];
             if (new_target) {
+                if (o.sam && !seen_targets.emplace(r.id, r.idl).second) {
+                    fprintf(stderr, "pbdagcon: line %llu: records of %.*s come back after another target's; the records of one RNAME "
+                            "must be consecutive (sort the SAM by coordinate)\n", r.line, (int)r.idl, r.id);
+                    had_error = true;
+                    break;
+                }
                 if (x > rb) b.begin.push_back(b.start.size());
                 b.ids.emplace_back(r.id, r.idl);
                 b.tlen.push_back(r.tlen);
+                if (o.sam) { b.toff.push_back(bytes2); b.tsrc.push_back(r.t); bytes2 += r.tlen; }
             }
+            if (o.sam) b.opb.push_back(b.opb.back() + r.nops);
             b.start.push_back(r.start);
             b.off.push_back(bytes); b.off2.push_back(bytes2);
             b.len.push_back(r.len); b.len2.push_back(r.tl);
@@ -818,6 +936,8 @@ int main(int argc, char **argv) {
         if (eof) slab_pos = size;
     }
     if (had_error) status = 1;
+    if (o.sam && o.verbose)
+        fprintf(stderr, "pbdagcon: %llu SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')\n", n_skipped);
     t_parse_end = now();
 #undef b
     if (!o.dump) {

@@ -1,0 +1,152 @@
+// k_cigar.hip.h -- dagcon_upload_cigar: alignments given as (position, ungapped read, CIGAR) against target bases held
+// once are expanded into the pair of gapped strings dagcon_upload takes, on the device (include/dagcon.h has the rule).
+// The strings never exist on the host.
+//
+// k_cigar_scan: one wave per record.  The record's ops are taken 64 at a time (a tile); every lane turns its op into
+// three increments -- columns, read bases, target bases -- and an inclusive wave prefix sum (DPP, 64-bit: a tile of
+// 64 ops of 2^28 - 1 does not fit 32 bits) plus a carry across tiles gives the tile's checkpoint (columns, read
+// bases, target bases in front of it, and the record it belongs to: the map the expansion is launched over) and, at
+// the end, the record's three totals and its flags.  No lane loops over a record's ops one by one.
+//
+// k_cigar_expand: one wave per tile.  The tile's columns are one contiguous range of the record's strings: the wave
+// recomputes the tile's prefix sums (32 bits are enough here: only records whose totals fit are expanded), leaves
+// per op the end of its columns, its first read / target base and its code in LDS, and walks the range 64 columns at
+// a time; a lane finds the op of its column by a binary search over the 64 ends and stores one byte of each string.
+// A wave's stores are contiguous 64-byte runs; the reads of q and t are gathers that move forward with the columns.
+// Only plain vector loads and stores.
+//
+// Out-of-bounds safety: the host expands a record only when the scan's totals say that its ops consume exactly q_len
+// read bases and stay inside the target, after it has checked q_off + q_len and t_off + tlen against the blobs; the
+// expansion recomputes the same sums from the same device copy of the ops, so every index it forms lies inside
+// [0, q_len), [pos - 1, tlen) and [0, columns).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define DG_CG_BAD_OP 1u       // an op code above 8, or N (3)
+#define DG_CG_ZERO_LEN 2u     // an op of length 0
+#define DG_CG_OVERFLOW 4u     // a total past 2^32 - 1
+#define DG_CG_SKIP (~0ull)    // out_off of a record that is not expanded
+
+// BAM op codes: M 0, I 1, D 2, N 3, S 4, H 5, P 6, = 7, X 8
+#define DG_CG_COL_MASK 0x187u   // M I D = X make columns
+#define DG_CG_Q_MASK 0x193u     // M I S = X consume read bases
+#define DG_CG_T_MASK 0x185u     // M D = X consume target bases
+
+struct DgCigarParams {
+    const uint32_t *ops;
+    const uint64_t *op_begin;      // [n + 1]
+    const uint64_t *tile_begin;    // [n + 1]: first tile (64 ops) of each record
+    uint32_t n;                    // records
+    uint32_t n_tiles;
+    uint4 *totals;                 // [n] columns, read bases, target bases, DG_CG_* flags
+    uint4 *ckpt;                   // [n_tiles] columns, read bases, target bases in front of the tile; its record
+    // expansion
+    const uint8_t *q, *t;          // the blobs
+    const uint64_t *q_off;         // [n]
+    const uint64_t *t_base;        // [n] t_off of the record's target + pos - 1
+    const uint64_t *out_off;       // [n] DG_CG_SKIP: leave the record alone
+    uint8_t *out_q, *out_t;
+};
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint64_t dg_cg_dpp64(uint64_t x) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)x, CTRL, ROW_MASK, 0xf, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(x >> 32), CTRL, ROW_MASK, 0xf, false);
+    return ((uint64_t)hi << 32) | lo;
+}
+// inclusive prefix sum over the 64 lanes (the scheme of dg_al_scan_min: four shifts inside a row, two row broadcasts)
+__device__ __forceinline__ uint64_t dg_cg_scan64(uint64_t incl) {
+    incl += dg_cg_dpp64<0x111, 0xf>(incl);     // row_shr:1
+    incl += dg_cg_dpp64<0x112, 0xf>(incl);     // row_shr:2
+    incl += dg_cg_dpp64<0x114, 0xf>(incl);     // row_shr:4
+    incl += dg_cg_dpp64<0x118, 0xf>(incl);     // row_shr:8
+    incl += dg_cg_dpp64<0x142, 0xa>(incl);     // row_bcast:15 into rows 1 and 3
+    incl += dg_cg_dpp64<0x143, 0xc>(incl);     // row_bcast:31 into rows 2 and 3
+    return incl;
+}
+__device__ __forceinline__ uint32_t dg_cg_scan32(uint32_t incl) {
+    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, false);
+    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, false);
+    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, false);
+    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xf, 0xf, false);
+    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xa, 0xf, false);
+    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xc, 0xf, false);
+    return incl;
+}
+__device__ __forceinline__ uint64_t dg_cg_last64(uint64_t x) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, 63);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), 63);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// a wave per record (four to a workgroup)
+__global__ __launch_bounds__(256) void k_cigar_scan(DgCigarParams p) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6);      // wave-uniform
+    if (r >= p.n) return;
+    const uint64_t ob = p.op_begin[r], oe = p.op_begin[r + 1];
+    const uint64_t tile0 = p.tile_begin[r];
+    uint64_t c_col = 0, c_q = 0, c_t = 0;                         // carried across tiles
+    uint32_t flags = 0;
+    uint64_t tile = 0;
+    for (uint64_t o = ob; o < oe; o += 64, tile++) {
+        const bool have = o + lane < oe;
+        const uint32_t op = have ? p.ops[o + lane] : 0u;
+        const uint32_t code = op & 15u, len = op >> 4;
+        const uint32_t bit = 1u << code;
+        const bool bad = have && (code > 8u || code == 3u), zero = have && len == 0u;
+        if (__ballot(bad)) flags |= DG_CG_BAD_OP;
+        if (__ballot(zero)) flags |= DG_CG_ZERO_LEN;
+        const uint64_t s_col = dg_cg_scan64((have && (bit & DG_CG_COL_MASK)) ? len : 0u);
+        const uint64_t s_q = dg_cg_scan64((have && (bit & DG_CG_Q_MASK)) ? len : 0u);
+        const uint64_t s_t = dg_cg_scan64((have && (bit & DG_CG_T_MASK)) ? len : 0u);
+        if (lane == 0) p.ckpt[tile0 + tile] = make_uint4((uint32_t)c_col, (uint32_t)c_q, (uint32_t)c_t, r);
+        c_col += dg_cg_last64(s_col); c_q += dg_cg_last64(s_q); c_t += dg_cg_last64(s_t);
+    }
+    if ((c_col | c_q | c_t) >> 32) flags |= DG_CG_OVERFLOW;
+    if (lane == 0) p.totals[r] = make_uint4((uint32_t)c_col, (uint32_t)c_q, (uint32_t)c_t, flags);
+}
+
+// a wave per tile of 64 ops
+__global__ __launch_bounds__(64) void k_cigar_expand(DgCigarParams p) {
+    __shared__ uint32_t s_end[64], s_q0[64], s_t0[64], s_code[64];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t tile = blockIdx.x;
+    if (tile >= p.n_tiles) return;
+    const uint4 ck = p.ckpt[tile];
+    const uint32_t r = ck.w;
+    const uint64_t out = p.out_off[r];
+    if (out == DG_CG_SKIP) return;                                // (wave-uniform: nobody reaches the barrier)
+    const uint64_t o = p.op_begin[r] + (uint64_t)(tile - p.tile_begin[r]) * 64u, oe = p.op_begin[r + 1];
+    const bool have = o + lane < oe;
+    const uint32_t op = have ? p.ops[o + lane] : 0u;
+    const uint32_t code = op & 15u, len = op >> 4;
+    const uint32_t bit = have ? 1u << code : 0u;
+    const uint32_t i_col = (bit & DG_CG_COL_MASK) ? len : 0u;
+    const uint32_t i_q = (bit & DG_CG_Q_MASK) ? len : 0u;
+    const uint32_t i_t = (bit & DG_CG_T_MASK) ? len : 0u;
+    const uint32_t e_col = dg_cg_scan32(i_col);
+    const uint32_t e_q = dg_cg_scan32(i_q), e_t = dg_cg_scan32(i_t);
+    s_end[lane] = e_col;
+    s_q0[lane] = ck.y + e_q - i_q;                                // the op's first read base
+    s_t0[lane] = ck.z + e_t - i_t;                                // its first target base, from pos - 1
+    s_code[lane] = code;
+    __syncthreads();
+    const uint32_t n_col = (uint32_t)__builtin_amdgcn_readlane((int)e_col, 63);
+    const uint8_t *q = p.q + p.q_off[r];
+    const uint8_t *t = p.t + p.t_base[r];
+    uint8_t *oq = p.out_q + out + ck.x, *ot = p.out_t + out + ck.x;
+    for (uint32_t c = lane; c < n_col; c += 64u) {
+        // the first op whose columns end past c
+        uint32_t lo = 0;
+#pragma unroll
+        for (uint32_t step = 32u; step; step >>= 1)
+            if (s_end[lo + step - 1u] <= c) lo += step;
+        const uint32_t first = lo ? s_end[lo - 1u] : 0u;          // (an op without columns ends where it begins: never found)
+        const uint32_t k = c - first;
+        const uint32_t b = 1u << s_code[lo];
+        oq[c] = (b & DG_CG_Q_MASK) ? q[s_q0[lo] + k] : (uint8_t)'-';
+        ot[c] = (b & DG_CG_T_MASK) ? t[s_t0[lo] + k] : (uint8_t)'-';
+    }
+}

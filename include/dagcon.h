@@ -61,9 +61,10 @@ typedef enum dagcon_status {
 #define DAGCON_FLAG_LOCAL_ALIGN 32u    /* dagcon_align / dagcon_consensus_pre align local ends (see dagcon_align):
                                           read ends that do not align stay out of the alignment */
 #define DAGCON_FLAG_BASE_SUPPORT 64u  /* keep the support of every consensus base: dagcon_fetch_support */
+#define DAGCON_FLAG_BASE_POS 256u     /* keep the target position of every consensus base: dagcon_fetch_positions */
 #define DAGCON_FLAGS_ALL (DAGCON_FLAG_RAW_ALIGNMENTS | DAGCON_FLAG_STOP_AFTER_BUILD | \
                           DAGCON_FLAG_STOP_AFTER_MERGE | DAGCON_FLAG_DEBUG_RESWEEP | DAGCON_FLAG_LOCAL_ALIGN | \
-                          DAGCON_FLAG_BASE_SUPPORT)
+                          DAGCON_FLAG_BASE_SUPPORT | DAGCON_FLAG_BASE_POS)
                                         /* dagcon_create refuses any other bit (DAGCON_ERR_UNSUPPORTED) */
 
 /* Mirrors ProgramOpts (src/cpp/ProgramOpts.hpp:8-36) for this path. */
@@ -194,6 +195,19 @@ int dagcon_sync(dagcon_ctx *ctx);                              /* wait for the s
 int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *results);    /* sync + status check + D2H */
 int dagcon_get_timings(dagcon_ctx *ctx, dagcon_timings *out);  /* after dagcon_sync / dagcon_fetch */
 int dagcon_fetch_support(dagcon_ctx *ctx, dagcon_support *out); /* DAGCON_FLAG_BASE_SUPPORT: see dagcon_support */
+
+/*
+ * Per-base target position of the consensus (a context created with DAGCON_FLAG_BASE_POS; independent of
+ * DAGCON_FLAG_BASE_SUPPORT, either alone or both).  (*pos)[i] describes seq_blob[i]; *n == seq_bytes.  It is _bbMap[v] of
+ * the best-path vertex v the base comes from, as a vertex index of the reference: p in 1 .. tlen is target base p
+ * (AlnGraphBoost.cpp:34,57); an inserted vertex has the position of the next target base, up to tlen + 1 (:101); after
+ * mergeNodes a survivor keeps its own value.  The values need NOT be monotone along a segment: a merged insertion can
+ * carry a position above that of the backbone vertex that follows it.  This is what lets a caller join the results of
+ * neighbouring windows of one long target at a target coordinate (range0 / range1 only index the consensus string, Q5).
+ * Lifetime and state rules of dagcon_fetch_support: DAGCON_ERR_STATE without the flag, before a fetch, or under
+ * DAGCON_FLAG_STOP_AFTER_BUILD / _MERGE; the array is owned by the context, valid as long as the results of the same fetch.
+ */
+int dagcon_fetch_positions(dagcon_ctx *ctx, const uint32_t **pos, uint64_t *n);
 
 /*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses
@@ -343,6 +357,38 @@ typedef struct dagcon_cigar_batch {
 } dagcon_cigar_batch;
 int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *batch);   /* then dagcon_run / _sync / _fetch as ever */
 int dagcon_consensus_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, dagcon_results *results);
+
+/*
+ * The same input with its targets cut into windows, for targets of any length and depth (a contig and the reads mapped
+ * to it): every window is one target of the pipeline, results.n_targets == n_windows, tlen = end - begin, and the
+ * records are cut to the windows they cross on the device.  This build's own definition.  A record covers target bases
+ * [s, e), s = pos - 1, e = s + the target bases its ops consume.  For a window [a, b), A = max(a, s), B = min(b, e):
+ *   - A >= B: the record has no piece in the window;
+ *   - F(x) is the index of the first column of the record's expansion (the rule above) that consumes target base x,
+ *     F(s) := 0 and F(e) := the number of columns, so a record's own leading and trailing insertions stay with it;
+ *   - the piece is columns [F(A), F(B)) with aln_start = A - a + 1: insertions in front of a cut at A > s are left out,
+ *     insertions in front of B < e are kept, so windows that tile a target partition a record's columns;
+ *   - pieces of a window keep the order of their records (addAln order).
+ * After the cut everything is dagcon_consensus: min_cov counts a window's pieces, min_len a piece's columns, then
+ * normalizeGaps, trimAln and an 'N' backbone; all flags keep their meaning.  Per window the result is, byte for byte,
+ * that of dagcon_consensus on the piece strings.  With DAGCON_FLAG_BASE_POS a caller joins neighbouring windows at a
+ * target coordinate (position + begin); pbdagcon --sam --window does (csrc/host/windows.h).
+ * Conformance as for dagcon_consensus_cigar; a non-conforming record fails every window it has a piece in
+ * (target_status DAGCON_ERR_NONCONFORMING), the other windows are complete.  The span of a non-conforming record is
+ * s = max(pos, 1) - 1 and e = s + its target-base total (32 bits), then s <= tlen - 1 and s + 1 <= e <= tlen.
+ * DAGCON_ERR_INVALID_ARG before any launch: end <= begin, end > tlen, a target index out of range, windows out of order.
+ * A window longer than the tlen limit of dagcon_consensus or with more than DAGCON_MAX_COVERAGE pieces:
+ * DAGCON_ERR_UNSUPPORTED for the call, as there.
+ */
+typedef struct dagcon_windows {
+    uint32_t n_windows;
+    const uint32_t *target;   /* [n_windows] index into the cigar batch's targets, ascending */
+    const uint32_t *begin;    /* [n_windows] 0-based, half-open [begin, end) in target bases; */
+    const uint32_t *end;      /*             ascending begin within a target; windows may overlap */
+} dagcon_windows;
+int dagcon_upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows);
+int dagcon_consensus_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows,
+                                   dagcon_results *results);
 
 /*
  * Debug / parity aid: adjacency of one target's graph as left by the last

@@ -25,6 +25,7 @@ FLAG_STOP_AFTER_MERGE = 4
 FLAG_DEBUG_RESWEEP = 16
 FLAG_LOCAL_ALIGN = 32
 FLAG_BASE_SUPPORT = 64
+FLAG_BASE_POS = 256
 MAX_COVERAGE = 4094
 PLACE_MAX_LEN = 65536
 
@@ -35,6 +36,7 @@ EXPORTS = [
     "dagcon_debug_counters", "dagcon_host_alloc", "dagcon_host_free", "dagcon_align",
     "dagcon_consensus_pre", "dagcon_debug_plan", "dagcon_align_dropped", "dagcon_align_panels",
     "dagcon_align_ends", "dagcon_place", "dagcon_fetch_support", "dagcon_upload_cigar", "dagcon_consensus_cigar",
+    "dagcon_fetch_positions", "dagcon_upload_cigar_windows", "dagcon_consensus_cigar_windows",
 ]
 ABI_VERSION = 2
 
@@ -70,6 +72,10 @@ class CigarBatch(C.Structure):
                 ("t_bytes", C.c_uint64), ("rec_begin", C.c_void_p), ("pos", C.c_void_p), ("q_off", C.c_void_p),
                 ("q_len", C.c_void_p), ("q_blob", C.c_void_p), ("q_bytes", C.c_uint64), ("op_begin", C.c_void_p),
                 ("ops", C.c_void_p)]
+
+
+class Windows(C.Structure):
+    _fields_ = [("n_windows", C.c_uint32), ("target", C.c_void_p), ("begin", C.c_void_p), ("end", C.c_void_p)]
 
 
 class Results(C.Structure):
@@ -143,6 +149,9 @@ def load() -> C.CDLL:
                                vp, vp, vp, vp, vp]
     L.dagcon_upload_cigar.argtypes = [vp, C.POINTER(CigarBatch)]
     L.dagcon_consensus_cigar.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Results)]
+    L.dagcon_fetch_positions.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint64)]
+    L.dagcon_upload_cigar_windows.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows)]
+    L.dagcon_consensus_cigar_windows.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(Results)]
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
     L.dagcon_host_free.restype = None
@@ -296,6 +305,39 @@ class HostCigarBatch:
         return b
 
 
+class HostWindows:
+    """numpy view of a dagcon_windows: per window its target (index into the cigar batch) and [begin, end) in target
+    bases; targets ascending, begins ascending inside a target, windows may overlap."""
+
+    def __init__(self, target, begin, end):
+        self.target = np.ascontiguousarray(target, dtype=np.uint32)
+        self.begin = np.ascontiguousarray(begin, dtype=np.uint32)
+        self.end = np.ascontiguousarray(end, dtype=np.uint32)
+        if not (self.target.size == self.begin.size == self.end.size):
+            raise ValueError("target, begin and end must have one entry per window")
+
+    @classmethod
+    def tiled(cls, tlens, window, overlap=0):
+        """Window i of a target has the core [i W, min((i + 1) W, tlen)) and runs as the core widened by `overlap`
+        on both sides, clipped to the target (what pbdagcon --sam --window does)."""
+        tg, bg, en = [], [], []
+        for g, tl in enumerate(tlens):
+            tl = int(tl)
+            for i in range(max(1, -(-tl // window)) if tl else 0):
+                tg.append(g); bg.append(max(0, i * window - overlap)); en.append(min(tl, (i + 1) * window + overlap))
+        return cls(tg, bg, en)
+
+    @property
+    def n_windows(self):
+        return int(self.target.size)
+
+    def c_struct(self) -> Windows:
+        w = Windows()
+        w.n_windows = self.n_windows
+        w.target, w.begin, w.end = self.target.ctypes.data, self.begin.ctypes.data, self.end.ctypes.data
+        return w
+
+
 class Context:
     """dagcon_ctx handle.  One per GPU; single-owner."""
 
@@ -408,6 +450,23 @@ class Context:
                         for s in range(int(sb[t]), int(sb[t + 1]))])
         return out
 
+    def fetch_positions_raw(self):
+        """dagcon_fetch_positions: a uint32 array over the whole seq_blob of the last results (a copy)."""
+        ptr, n = C.POINTER(C.c_uint32)(), C.c_uint64()
+        self._chk(self.L.dagcon_fetch_positions(self.h, C.byref(ptr), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, np.uint32)
+        return np.ctypeslib.as_array(ptr, shape=(int(n.value),)).copy()
+
+    def base_positions(self):
+        """Per target, one uint32 array per segment, aligned with that segment's seq (FLAG_BASE_POS; after consensus,
+        fetch or consensus_pre): _bbMap of the best-path vertex each base comes from -- target base p for a backbone
+        vertex, the next target base for an inserted one (include/dagcon.h, dagcon_fetch_positions)."""
+        pos = self.fetch_positions_raw()
+        sb, so, sl = self._segs
+        return [[pos[int(so[s]):int(so[s]) + int(sl[s])] for s in range(int(sb[t]), int(sb[t + 1]))]
+                for t in range(sb.size - 1)]
+
     def fetch_raw(self):
         """dagcon_fetch without the conversion to Python objects: the returned struct points into
         host memory the context owns until its next fetch (dagcon_run does not touch it), so a
@@ -441,6 +500,22 @@ class Context:
         b = batch.c_struct()
         r = Results()
         self._chk(self.L.dagcon_consensus_cigar(self.h, C.byref(b), C.byref(r)))
+        out = self._keep_segs(r)
+        self._status(r, strict)
+        return out
+
+    def upload_cigar_windows(self, batch: HostCigarBatch, windows: HostWindows):
+        """dagcon_upload_cigar_windows: then run / sync / fetch as after upload (one result target per window)."""
+        self._keep = (batch, windows)
+        b, w = batch.c_struct(), windows.c_struct()
+        self._chk(self.L.dagcon_upload_cigar_windows(self.h, C.byref(b), C.byref(w)))
+
+    def consensus_cigar_windows(self, batch: HostCigarBatch, windows: HostWindows, strict=True):
+        """Per window: [(range0, range1, seq_bytes)], the records cut to the windows on the device."""
+        self._keep = (batch, windows)
+        b, w = batch.c_struct(), windows.c_struct()
+        r = Results()
+        self._chk(self.L.dagcon_consensus_cigar_windows(self.h, C.byref(b), C.byref(w), C.byref(r)))
         out = self._keep_segs(r)
         self._status(r, strict)
         return out

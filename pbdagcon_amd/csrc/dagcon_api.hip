@@ -131,10 +131,11 @@ struct Ctx {
     DevBuf d_al[15];                                // dagcon_align: blobs, offsets, outputs, directions, launch order, widths, ends
     DevBuf d_pn[18];                                // dagcon_align_panels: blobs, panels, scratch, outputs, launch order
     DevBuf d_pl[14];                                // dagcon_place: blob, sequences, tables, pairs, outputs
-    DevBuf d_cg[11];                                // dagcon_upload_cigar: ops, op / tile begins, totals, checkpoints, blobs, offsets
+    DevBuf d_cg[16];                                // dagcon_upload_cigar: ops, op / tile begins, totals, checkpoints, blobs, offsets
     std::vector<uint8_t> h_cig_bad;                 // dagcon_upload_cigar: targets with a non-conforming record (empty: another upload)
     std::string cig_err;                            // the first of them, for dagcon_last_error
     DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
+    DevBuf d_pos_tmp, d_pos_tmp0, d_pos;           // DAGCON_FLAG_BASE_POS: walk scratch (4 B per vertex), output (4 B per base)
     DevBuf d_sup_tmp, d_sup_tmp0, d_sup;           // DAGCON_FLAG_BASE_SUPPORT: walk scratch (4 B per vertex), output (2 x 2 B per base)
 
     uint64_t norm_cap = 0, node_cap = 0, pool_cap = 0, cns_cap = 0, seg_cap = 0;
@@ -157,6 +158,8 @@ struct Ctx {
     uint16_t *r_sup = nullptr;          // page-locked, DAGCON_FLAG_BASE_SUPPORT: [seq_bytes] weights, then [seq_bytes] depths
     size_t r_sup_cap = 0;               // (entries of each half)
     uint64_t r_sup_n = 0;
+    std::vector<uint32_t> r_pos;        // DAGCON_FLAG_BASE_POS: [seq_bytes] _bbMap of every consensus base
+    bool pos_valid = false;
     bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
 
     // debug dump storage
@@ -255,6 +258,11 @@ int ensure_arenas(Ctx *c) {
         if (c->gcuts) ENSURE(c, c->d_sup_tmp0, c->node_cap * 4);
         ENSURE(c, c->d_sup, c->cns_cap * 4);
     }
+    if (c->opts.flags & DAGCON_FLAG_BASE_POS) {
+        ENSURE(c, c->d_pos_tmp, c->node_cap * 4);
+        if (c->gcuts) ENSURE(c, c->d_pos_tmp0, c->node_cap * 4);
+        ENSURE(c, c->d_pos, c->cns_cap * 4);
+    }
     ENSURE(c, c->d_seg_r0, c->seg_cap * 4);
     ENSURE(c, c->d_seg_r1, c->seg_cap * 4);
     return DAGCON_OK;
@@ -331,6 +339,9 @@ void fill_params(Ctx *c, DgParams &p) {
         p.sup_tmp = (uint32_t *)c->d_sup_tmp.p; p.sup_tmp0 = (uint32_t *)c->d_sup_tmp0.p;
         p.sup_w = (uint16_t *)c->d_sup.p; p.sup_d = p.sup_w + c->cns_cap;
     }
+    if (c->opts.flags & DAGCON_FLAG_BASE_POS) {
+        p.pos_tmp = (uint32_t *)c->d_pos_tmp.p; p.pos_tmp0 = (uint32_t *)c->d_pos_tmp0.p; p.pos_out = (uint32_t *)c->d_pos.p;
+    }
 }
 
 // stage a1: count, chunked normalizeGaps + trimAln, and the sequential kernel for what is left
@@ -360,7 +371,7 @@ int launch_all(Ctx *c) {
                           &c->d_gbase, &c->d_bid, &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_stk, &c->d_cuts,
                           &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_wl_first,
                           &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns, &c->d_cns_off, &c->d_seg_first,
-                          &c->d_seg_r0, &c->d_seg_r1, &c->d_worklist, &c->d_seg_done, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup};
+                          &c->d_seg_r0, &c->d_seg_r1, &c->d_worklist, &c->d_seg_done, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup, &c->d_pos_tmp, &c->d_pos_tmp0, &c->d_pos};
         for (DevBuf *b : work)
             if (b->p && b->cap) HIPCHK(c, hipMemsetAsync(b->p, 0xEE, b->cap, s));
     }
@@ -420,6 +431,15 @@ int launch_all(Ctx *c) {
     HIPCHK(c, hipEventRecord(c->ev[3], s));
     if (c->T > 0 && !(c->opts.flags & (DAGCON_FLAG_STOP_AFTER_BUILD | DAGCON_FLAG_STOP_AFTER_MERGE))) {
         const bool sup = (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT) != 0;   // the walks and the join with per-base support
+        const bool pos = (c->opts.flags & DAGCON_FLAG_BASE_POS) != 0;       // ... and with per-base target positions
+        // (neither flag: the <false, false> instances, the code of the kernels before either existed)
+#define DG_BP_LAUNCH(K, GRID)                                                                          \
+        do {                                                                                           \
+            if (sup && pos) hipLaunchKernelGGL((K<true, true>), GRID, dim3(64), 0, s, p);              \
+            else if (sup) hipLaunchKernelGGL((K<true, false>), GRID, dim3(64), 0, s, p);               \
+            else if (pos) hipLaunchKernelGGL((K<false, true>), GRID, dim3(64), 0, s, p);               \
+            else hipLaunchKernelGGL((K<false, false>), GRID, dim3(64), 0, s, p);                       \
+        } while (0)
         hipLaunchKernelGGL(k_bp_terms, dim3(c->T, 16), dim3(256), 0, s, p);
         if (c->gcuts) {
             // partial-span pileups, on the pieces of k_cuts2: one sweep for (A, B), then vertex-parallel kernels for the
@@ -431,21 +451,17 @@ int launch_all(Ctx *c) {
             hipLaunchKernelGGL(k_bp_choose, dim3(c->T * c->bp_max), dim3(256), 0, s, p);
             hipLaunchKernelGGL(k_bp_sweep_abs_g, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_bp_defer, dim3(c->T), dim3(64), 0, s, p);
-            if (sup) hipLaunchKernelGGL(k_bp_walk_g<true>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
-            else hipLaunchKernelGGL(k_bp_walk_g<false>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
+            DG_BP_LAUNCH(k_bp_walk_g, dim3(c->T * c->bp_max));
         } else {
             // a lane per piece first; the wave-per-piece sweep then takes the pieces a lane gave up (deep recursion)
             if (p.bp_lane) hipLaunchKernelGGL(k_bp_sweep_l, dim3((c->T * c->bp_max + 7u) / 8u), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_bp_sweep, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_bp_check, dim3(c->T), dim3(64), 0, s, p);
-            if (p.bp_lane) {
-                if (sup) hipLaunchKernelGGL(k_bp_walk_r<true>, dim3((c->T * c->bp_max + 7u) / 8u), dim3(64), 0, s, p);
-                else hipLaunchKernelGGL(k_bp_walk_r<false>, dim3((c->T * c->bp_max + 7u) / 8u), dim3(64), 0, s, p);
-            } else if (sup) hipLaunchKernelGGL(k_bp_walk<true>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
-            else hipLaunchKernelGGL(k_bp_walk<false>, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
+            if (p.bp_lane) DG_BP_LAUNCH(k_bp_walk_r, dim3((c->T * c->bp_max + 7u) / 8u));
+            else DG_BP_LAUNCH(k_bp_walk, dim3(c->T * c->bp_max));
         }
-        if (sup) hipLaunchKernelGGL(k_bp_join<true>, dim3(c->T), dim3(64), 0, s, p);
-        else hipLaunchKernelGGL(k_bp_join<false>, dim3(c->T), dim3(64), 0, s, p);
+        DG_BP_LAUNCH(k_bp_join, dim3(c->T));
+#undef DG_BP_LAUNCH
     }
     HIPCHK(c, hipEventRecord(c->ev[4], s));
     HIPCHK(c, hipGetLastError());
@@ -524,7 +540,7 @@ void dagcon_destroy(dagcon_ctx *ctx) {
                      &c->d_matC, &c->d_cov, &c->d_gcount, &c->d_gbase, &c->d_bid, &c->d_nodes,
                      &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_score_b, &c->d_pool, &c->d_stk, &c->d_cuts, &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_worklist, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_seg_done, &c->d_wl_first, &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns,
                      &c->d_cns_off, &c->d_cns_len, &c->d_seg_first, &c->d_n_seg, &c->d_seg_r0, &c->d_seg_r1,
-                     &c->d_st, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup};
+                     &c->d_st, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup, &c->d_pos_tmp, &c->d_pos_tmp0, &c->d_pos};
     for (DevBuf *b : all) free_buf(*b);
     for (DevBuf &b : c->d_al) free_buf(b);
     for (DevBuf &b : c->d_pn) free_buf(b);
@@ -540,7 +556,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
-    c->sup_valid = false;
+    c->sup_valid = c->pos_valid = false;
     c->h_cig_bad.clear();
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->aln_begin)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/aln_begin is NULL");
@@ -886,7 +902,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         }
         if (nb) HIPCHK(c, d2h(c, c->r_blob, c->d_cns.p, nb));
     }
-    c->sup_valid = false;
+    c->sup_valid = c->pos_valid = false;
     if (full && (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT)) {
         // the support, weights then depths (the device keeps them apart: no host pass over them)
         if (c->r_sup_cap < nb + 1) {
@@ -902,6 +918,11 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         }
         c->r_sup_n = nb;
         c->sup_valid = true;
+    }
+    if (full && (c->opts.flags & DAGCON_FLAG_BASE_POS)) {
+        c->r_pos.resize(nb + 1);
+        if (nb) HIPCHK(c, d2h(c, c->r_pos.data(), c->d_pos.p, nb * 4));
+        c->pos_valid = true;
     }
     c->r_seg_begin.assign(T + 1, 0);
     c->r_range0.clear(); c->r_range1.clear(); c->r_seq_off.clear(); c->r_seq_len.clear();
@@ -946,6 +967,18 @@ int dagcon_fetch_support(dagcon_ctx *ctx, dagcon_support *out) {
     out->n = c->r_sup_n;
     out->weight = c->r_sup;
     out->depth = c->r_sup + c->r_sup_n;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_positions(dagcon_ctx *ctx, const uint32_t **pos, uint64_t *n) {
+    if (!ctx || !pos || !n) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!(c->opts.flags & DAGCON_FLAG_BASE_POS))
+        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_positions on a context created without DAGCON_FLAG_BASE_POS");
+    if (!c->pos_valid)
+        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_positions without the results of a consensus (no fetch yet, or stopped before bestPath)");
+    *pos = c->r_pos.data();
+    *n = c->r_pos.size() - 1;
     return DAGCON_OK;
 }
 
@@ -1607,14 +1640,12 @@ int dagcon_consensus_pre(dagcon_ctx *ctx, const dagcon_pre_batch *b, dagcon_resu
     return dagcon_fetch(ctx, results);
 }
 
-// SAM-style input: position + ungapped read + CIGAR per record, target bases once per target.  k_cigar_scan sizes
-// every record, the host plans the string blobs as for any batch, k_cigar_expand writes them into d_q / d_t, and
-// upload_impl takes them from there (the door dagcon_consensus_pre uses)
-int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
-    if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    c->uploaded = c->ran = c->fetched = false;
-    c->sup_valid = false;
+}  // extern "C"
+namespace {
+// what dagcon_upload_cigar and dagcon_upload_cigar_windows share: the checks of the batch, its upload, k_cigar_scan and
+// the totals back on the host (tot: columns, read bases, target bases, DG_CG_* flags per record); p is left ready for
+// an expansion but for its offsets
+int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, DgCigarParams &p, std::vector<uint64_t> &tile_begin, std::vector<uint32_t> &tot) {
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->rec_begin || !b->t_off)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
     const uint64_t n64 = T ? b->rec_begin[T] : 0;
@@ -1627,7 +1658,7 @@ int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
         if (b->t_off[g] > b->t_bytes || b->tlen[g] > b->t_bytes - b->t_off[g]) return fail(c, DAGCON_ERR_INVALID_ARG, "target %u runs past t_blob", g);
         if (b->tlen[g] && !b->t_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "t_blob is NULL");
     }
-    std::vector<uint64_t> tile_begin((size_t)n + 1, 0);
+    tile_begin.assign((size_t)n + 1, 0);
     for (uint32_t a = 0; a < n; a++) {
         if (b->op_begin[a + 1] < b->op_begin[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "op_begin not monotone at record %u", a);
         if (b->q_off[a] > b->q_bytes || b->q_len[a] > b->q_bytes - b->q_off[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "record %u runs past q_blob", a);
@@ -1640,7 +1671,7 @@ int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     DevBuf &d_ops = c->d_cg[0], &d_opb = c->d_cg[1], &d_tileb = c->d_cg[2], &d_tot = c->d_cg[3], &d_ck = c->d_cg[4],
-           &d_qb = c->d_cg[5], &d_tb = c->d_cg[6], &d_qoff = c->d_cg[7], &d_tbase = c->d_cg[8], &d_out = c->d_cg[9];
+           &d_qb = c->d_cg[5], &d_tb = c->d_cg[6], &d_qoff = c->d_cg[7];
     // op_begin as the caller has it, less its first entry (ops are uploaded from there)
     std::vector<uint64_t> opb((size_t)n + 1, 0);
     for (uint32_t a = 0; a <= n && n; a++) opb[a] = b->op_begin[a] - b->op_begin[0];
@@ -1653,29 +1684,57 @@ int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
     int r;
     if ((r = upload_vec(c, d_opb, opb))) return r;
     if ((r = upload_vec(c, d_tileb, tile_begin))) return r;
-    DgCigarParams p;
     memset(&p, 0, sizeof p);
     p.ops = (const uint32_t *)d_ops.p; p.op_begin = (const uint64_t *)d_opb.p; p.tile_begin = (const uint64_t *)d_tileb.p;
     p.n = n; p.n_tiles = (uint32_t)n_tiles;
     p.totals = (uint4 *)d_tot.p; p.ckpt = (uint4 *)d_ck.p;
-    std::vector<uint32_t> tot((size_t)n * 4);
+    p.q = (const uint8_t *)d_qb.p; p.t = (const uint8_t *)d_tb.p; p.q_off = (const uint64_t *)d_qoff.p;
+    tot.assign((size_t)n * 4, 0);
     if (n) {
         hipLaunchKernelGGL(k_cigar_scan, dim3((n + 3u) / 4u), dim3(256), 0, s, p);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, d2h(c, tot.data(), d_tot.p, (size_t)n * 16));
     }
+    return DAGCON_OK;
+}
+
+// why a record is non-conforming (include/dagcon.h), nullptr if it conforms
+const char *cigar_why(const dagcon_cigar_batch *b, const std::vector<uint32_t> &tot, uint32_t g, uint64_t a) {
+    const uint32_t nq = tot[a * 4 + 1], nt = tot[a * 4 + 2], fl = tot[a * 4 + 3];
+    return (fl & DG_CG_BAD_OP) ? "an op code above 8 or N"
+         : (fl & DG_CG_ZERO_LEN) ? "an op of length 0"
+         : (fl & DG_CG_OVERFLOW) ? "a total past 32 bits"
+         : b->pos[a] == 0 ? "pos is 0"
+         : nq != b->q_len[a] ? "the ops do not consume exactly q_len read bases"
+         : (uint64_t)b->pos[a] - 1u + nt > b->tlen[g] ? "target bases past tlen" : nullptr;
+}
+}  // namespace
+extern "C" {
+
+// SAM-style input: position + ungapped read + CIGAR per record, target bases once per target.  k_cigar_scan sizes
+// every record, the host plans the string blobs as for any batch, k_cigar_expand writes them into d_q / d_t, and
+// upload_impl takes them from there (the door dagcon_consensus_pre uses)
+int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
+    if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    c->uploaded = c->ran = c->fetched = false;
+    c->sup_valid = c->pos_valid = false;
+    const uint32_t T = b->n_targets;
+    const uint32_t n = T && b->rec_begin ? (uint32_t)b->rec_begin[T] : 0u;
+    DgCigarParams p;
+    std::vector<uint64_t> tile_begin;
+    std::vector<uint32_t> tot;
+    int r = cigar_scan(c, b, p, tile_begin, tot);
+    if (r != DAGCON_OK) return r;
+    const uint64_t n_tiles = tile_begin[n];
+    hipStream_t s = c->stream;
+    DevBuf &d_tbase = c->d_cg[8], &d_out = c->d_cg[9];
     // what every record is: the targets with a non-conforming one lose all their records
     std::vector<uint8_t> bad(T, 0);
     std::string first_err;
     for (uint32_t g = 0; g < T; g++)
         for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
-            const uint32_t nq = tot[a * 4 + 1], nt = tot[a * 4 + 2], fl = tot[a * 4 + 3];
-            const char *why = (fl & DG_CG_BAD_OP) ? "an op code above 8 or N"
-                            : (fl & DG_CG_ZERO_LEN) ? "an op of length 0"
-                            : (fl & DG_CG_OVERFLOW) ? "a total past 32 bits"
-                            : b->pos[a] == 0 ? "pos is 0"
-                            : nq != b->q_len[a] ? "the ops do not consume exactly q_len read bases"
-                            : (uint64_t)b->pos[a] - 1u + nt > b->tlen[g] ? "target bases past tlen" : nullptr;
+            const char *why = cigar_why(b, tot, g, a);
             if (!why) continue;
             if (first_err.empty()) {
                 char buf[256];
@@ -1704,8 +1763,7 @@ int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
     if ((r = upload_vec(c, d_tbase, t_base))) return r;
     if ((r = upload_vec(c, d_out, out_off))) return r;
     if (n_tiles && bytes) {
-        p.q = (const uint8_t *)d_qb.p; p.t = (const uint8_t *)d_tb.p;
-        p.q_off = (const uint64_t *)d_qoff.p; p.t_base = (const uint64_t *)d_tbase.p; p.out_off = (const uint64_t *)d_out.p;
+        p.t_base = (const uint64_t *)d_tbase.p; p.out_off = (const uint64_t *)d_out.p;
         p.out_q = (uint8_t *)c->d_q.p; p.out_t = (uint8_t *)c->d_t.p;
         hipLaunchKernelGGL(k_cigar_expand, dim3((uint32_t)n_tiles), dim3(64), 0, s, p);
         HIPCHK(c, hipGetLastError());
@@ -1720,6 +1778,147 @@ int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
     c->h_cig_bad = bad;
     c->cig_err = first_err;
     return DAGCON_OK;
+}
+
+// The same input with every target cut into windows, each window a target of the pipeline (include/dagcon.h has the
+// cut).  After the scan's totals the host knows every record's [s, e) and lists the (record, window) pieces; k_cigar_cut
+// turns each piece's two target coordinates into columns and tiles, the host plans the output from those, and
+// k_cigar_expand_cut writes every piece from the one device copy of the record's ops and bases.
+int dagcon_upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
+    if (!ctx || !b || !wn) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    c->uploaded = c->ran = c->fetched = false;
+    c->sup_valid = c->pos_valid = false;
+    const uint32_t T = b->n_targets, W = wn->n_windows;
+    if (W && (!wn->target || !wn->begin || !wn->end)) return fail(c, DAGCON_ERR_INVALID_ARG, "window arrays are NULL");
+    if (T && !b->tlen) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
+    for (uint32_t w = 0; w < W; w++) {
+        const uint32_t g = wn->target[w];
+        if (g >= T) return fail(c, DAGCON_ERR_INVALID_ARG, "window %u: target %u out of range", w, g);
+        if (wn->end[w] <= wn->begin[w] || wn->end[w] > b->tlen[g])
+            return fail(c, DAGCON_ERR_INVALID_ARG, "window %u: [%u, %u) is empty or runs past tlen %u", w, wn->begin[w], wn->end[w], b->tlen[g]);
+        if (w && (g < wn->target[w - 1] || (g == wn->target[w - 1] && wn->begin[w] < wn->begin[w - 1])))
+            return fail(c, DAGCON_ERR_INVALID_ARG, "window %u is out of order (targets ascending, begins ascending inside a target)", w);
+    }
+    const uint32_t n = T && b->rec_begin ? (uint32_t)b->rec_begin[T] : 0u;
+    DgCigarParams p;
+    std::vector<uint64_t> tile_begin;
+    std::vector<uint32_t> tot;
+    int r = cigar_scan(c, b, p, tile_begin, tot);
+    if (r != DAGCON_OK) return r;
+    hipStream_t s = c->stream;
+    DevBuf &d_tbase = c->d_cg[8], &d_piece = c->d_cg[10], &d_cut = c->d_cg[11], &d_wpiece = c->d_cg[12], &d_wbegin = c->d_cg[13],
+           &d_pout = c->d_cg[14];
+    // every record's [s, e) in target bases.  A non-conforming record has whatever span its pos and its target-base
+    // total give, clipped to the target and at least one base long: it fails the windows that span meets
+    std::vector<uint32_t> rs((size_t)n), re((size_t)n);
+    std::vector<uint8_t> rbad((size_t)n, 0);
+    std::vector<uint64_t> t_base((size_t)n, 0);
+    std::string first_err;
+    for (uint32_t g = 0; g < T; g++)
+        for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
+            const char *why = cigar_why(b, tot, g, a);
+            const uint64_t tl = b->tlen[g];
+            uint64_t s0 = b->pos[a] ? b->pos[a] - 1u : 0u, e0 = s0 + tot[a * 4 + 2];
+            if (why) {
+                rbad[a] = 1;
+                if (tl && s0 > tl - 1) s0 = tl - 1;
+                if (e0 < s0 + 1) e0 = s0 + 1;
+                if (e0 > tl) e0 = tl;
+                if (first_err.empty()) {
+                    char buf[256];
+                    snprintf(buf, sizeof buf, "target %u: record %llu is non-conforming (%s)", g, (unsigned long long)a, why);
+                    first_err = buf;
+                }
+            }
+            rs[a] = (uint32_t)s0; re[a] = (uint32_t)e0;
+            t_base[a] = b->t_off[g] + s0;
+        }
+    // the pieces, window by window, records in their own order (addAln order); a window with a non-conforming piece, or
+    // with fewer pieces than min_cov, keeps none
+    std::vector<uint8_t> bad(W, 0);
+    std::vector<uint64_t> beg2((size_t)W + 1, 0);
+    std::vector<uint32_t> piece;                                   // x4: record, a_rel, b_rel, window
+    for (uint32_t w = 0; w < W; w++) {
+        const uint32_t g = wn->target[w], wa = wn->begin[w], wb = wn->end[w];
+        const size_t first = piece.size();
+        for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
+            const uint32_t A = std::max(wa, rs[a]), B = std::min(wb, re[a]);
+            if (A >= B) continue;
+            if (rbad[a]) { bad[w] = 1; continue; }
+            piece.push_back((uint32_t)a); piece.push_back(A - rs[a]); piece.push_back(B - rs[a]); piece.push_back(w);
+        }
+        const size_t k = (piece.size() - first) / 4;
+        if (bad[w] || k < c->opts.min_cov) piece.resize(first);
+    }
+    const uint64_t np64 = piece.size() / 4;
+    if (np64 > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many alignments");
+    const uint32_t np = (uint32_t)np64;
+    DgCigarCutParams cw;
+    memset(&cw, 0, sizeof cw);
+    std::vector<uint32_t> cut((size_t)np * 4);
+    if (np) {
+        if ((r = upload_vec(c, d_piece, piece))) return r;
+        ENSURE(c, d_cut, (size_t)np * 16);
+        cw.piece = (const uint4 *)d_piece.p; cw.cut = (uint4 *)d_cut.p; cw.n_pieces = np;
+        hipLaunchKernelGGL(k_cigar_cut, dim3((np + 3u) / 4u), dim3(256), 0, s, p, cw);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, d2h(c, cut.data(), d_cut.p, (size_t)np * 16));
+    }
+    // the output plan: nothing the device said is used before it has been checked against the record's own sizes
+    std::vector<uint64_t> off2((size_t)np), pout((size_t)np);
+    std::vector<uint32_t> start2((size_t)np), len2((size_t)np), wbegin((size_t)np), wpiece;
+    uint64_t bytes = 0;
+    uint32_t cur = 0;
+    for (uint32_t i = 0; i < np; i++) {
+        const uint32_t a = piece[i * 4], w = piece[i * 4 + 3];
+        const uint32_t ca = cut[i * 4], cb = cut[i * 4 + 1], ta = cut[i * 4 + 2], tb = cut[i * 4 + 3];
+        const uint64_t ntile = tile_begin[a + 1] - tile_begin[a];
+        if (ca > cb || cb > tot[a * 4] || ta > tb || tb >= ntile)
+            return fail(c, DAGCON_ERR_INTERNAL, "k_cigar_cut: piece %u of record %u has columns [%u, %u), tiles [%u, %u] of %llu", i, a, ca, cb, ta, tb, (unsigned long long)ntile);
+        while (cur < w) beg2[++cur] = i;
+        off2[i] = pout[i] = bytes;
+        len2[i] = cb - ca;
+        start2[i] = rs[a] + piece[i * 4 + 1] - wn->begin[w] + 1u;
+        bytes += ((uint64_t)(cb - ca) + 15ull) & ~15ull;
+        if (wpiece.size() + (tb - ta + 1u) > 0x7FFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many CIGAR ops");
+        wbegin[i] = (uint32_t)wpiece.size();
+        wpiece.insert(wpiece.end(), tb - ta + 1u, i);
+    }
+    while (cur < W) beg2[++cur] = np;
+    ENSURE(c, c->d_q, bytes); ENSURE(c, c->d_t, bytes);
+    if (np && bytes) {
+        if ((r = upload_vec(c, d_tbase, t_base))) return r;
+        if ((r = upload_vec(c, d_wpiece, wpiece))) return r;
+        if ((r = upload_vec(c, d_wbegin, wbegin))) return r;
+        if ((r = upload_vec(c, d_pout, pout))) return r;
+        p.t_base = (const uint64_t *)d_tbase.p;
+        p.out_q = (uint8_t *)c->d_q.p; p.out_t = (uint8_t *)c->d_t.p;
+        cw.wave_piece = (const uint32_t *)d_wpiece.p; cw.wave_begin = (const uint32_t *)d_wbegin.p;
+        cw.piece_out = (const uint64_t *)d_pout.p; cw.n_waves = (uint32_t)wpiece.size();
+        hipLaunchKernelGGL(k_cigar_expand_cut, dim3(cw.n_waves), dim3(64), 0, s, p, cw);
+        HIPCHK(c, hipGetLastError());
+    }
+    std::vector<uint32_t> wlen(W);
+    for (uint32_t w = 0; w < W; w++) wlen[w] = wn->end[w] - wn->begin[w];
+    dagcon_batch db;
+    memset(&db, 0, sizeof db);
+    db.n_targets = W; db.tlen = wlen.data(); db.aln_begin = beg2.data();
+    db.aln_start = start2.data(); db.aln_off = off2.data(); db.aln_len = len2.data();
+    db.blob_bytes = bytes;
+    r = upload_impl(ctx, &db, c->d_q.p, c->d_t.p);                 // (synchronises the stream: the locals above may go)
+    if (r != DAGCON_OK) { (void)hipStreamSynchronize(s); return r; }
+    c->h_cig_bad = bad;
+    c->cig_err = first_err;
+    return DAGCON_OK;
+}
+
+int dagcon_consensus_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, dagcon_results *results) {
+    if (!results) return DAGCON_ERR_INVALID_ARG;
+    int r = dagcon_upload_cigar_windows(ctx, batch, windows);
+    if (r != DAGCON_OK) return r;
+    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
+    return dagcon_fetch(ctx, results);
 }
 
 int dagcon_consensus_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, dagcon_results *results) {

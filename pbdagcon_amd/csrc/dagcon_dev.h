@@ -210,6 +210,10 @@ struct DgParams {
     uint32_t *sup_tmp;             // [node_cap] parallel to cns_tmp: weight | depth << 16 of each path base of a walk piece
     uint32_t *sup_tmp0;            // [node_cap] (p.gcuts) parallel to cns_tmp0
     uint16_t *sup_w, *sup_d;       // [cns_cap] each, parallel to cns: weight and depth of each kept consensus base
+    // ---- per-base target position (DAGCON_FLAG_BASE_POS only; NULL otherwise) ----
+    uint32_t *pos_tmp;             // [node_cap] parallel to cns_tmp: _bbMap of each path base of a walk piece
+    uint32_t *pos_tmp0;            // [node_cap] (p.gcuts) parallel to cns_tmp0
+    uint32_t *pos_out;             // [cns_cap] parallel to cns: _bbMap of each kept consensus base
 };
 
 // slots a backbone vertex gets for each of its two lists before it has to move to the

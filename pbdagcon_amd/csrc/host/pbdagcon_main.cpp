@@ -43,6 +43,7 @@
 #include "../../../include/dagcon.h"
 #include "fastq.h"
 #include "sam.h"
+#include "windows.h"
 
 namespace {
 
@@ -52,6 +53,8 @@ struct Opts {
     bool local = false;                // --local (with -a): the first alignment of every record has local ends
     bool sam = false;                  // --sam: SAM text, the targets' bases from --ref (dagcon_consensus_cigar)
     std::string ref;                   // --ref FASTA
+    unsigned window = 0, overlap = 1000;   // --window W [--overlap O] (with --sam): targets cut into windows (windows.h)
+    bool overlap_set = false;
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
     int pinned = -1;                   // --pinned 0|1: page-locked blobs (-1: when the input is several batches long)
@@ -66,7 +69,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam --ref <fasta>] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam --ref <fasta> [--window W [--overlap O]]] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -86,6 +89,14 @@ void usage(FILE *f) {
             "                      --local or --polish.  BAM, PAF and MD:Z-only input (no FASTA) are not read\n"
             "  --ref FASTA         with --sam (required): the target sequences, by the name up to the first blank; an @SQ line\n"
             "                      whose LN differs from the sequence of its SN is an error\n"
+            "  --window W          with --sam: targets of any length and depth.  Every target is cut into windows with cores of W\n"
+            "                      bases, each run with --overlap more bases on either side; the records are cut to the windows\n"
+            "                      on the GPU and the windows' consensus is joined at target coordinates.  Records of one RNAME\n"
+            "                      must then be ascending in POS (a coordinate-sorted SAM).  In this mode only, a record is named\n"
+            "                      >RNAME/t0_t1 with t0, t1 TARGET coordinates (0-based start, end) of its first and last base,\n"
+            "                      not indexes into the consensus string; a break in the consensus starts a new record\n"
+            "  --overlap O         with --window: bases a window is widened by on either side (default 1000); at least\n"
+            "                      --trim + 64, so that trimming at a window's ends does not thin the coverage inside its core\n"
             "  --fastq             write FASTQ (@id/r0_r1, sequence, +, qualities) instead of FASTA; the same records in the\n"
             "                      same order.  The quality of a base is this build's own definition: a Laplace-smoothed\n"
             "                      fraction of the reads at its position that do not pass through its consensus vertex,\n"
@@ -129,6 +140,8 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--local") o.local = true;
         else if (a == "--fastq") o.fastq = true;
         else if (a == "--sam") o.sam = true;
+        else if (a == "--window") { if (!need(&o.window) || !o.window) { fprintf(stderr, "PARSE ERROR: --window takes a positive number of bases\n"); return 2; } }
+        else if (a == "--overlap") { if (!need(&o.overlap)) return 2; o.overlap_set = true; }
         else if (a == "--ref") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --ref needs a FASTA file\n"); return 2; }
             o.ref = argv[++i];
@@ -165,6 +178,9 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (o.sam && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --sam does not go with -a, --local or --polish\n"); return 2; }
     if (o.sam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --sam needs --ref <fasta>\n"); return 2; }
     if (!o.sam && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam\n"); return 2; }
+    if (o.window && (!o.sam || o.align || o.polish)) { fprintf(stderr, "PARSE ERROR: --window needs --sam and does not go with -a or --polish\n"); return 2; }
+    if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
+    if (o.window && (uint64_t)o.overlap < (uint64_t)o.trim + 64) { fprintf(stderr, "PARSE ERROR: --overlap must be at least --trim + 64 (%u)\n", o.trim + 64); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
     return 0;
 }
@@ -529,6 +545,11 @@ int main(int argc, char **argv) {
             fprintf(stderr, "pbdagcon: %s\n", err.c_str());
             return 1;
         }
+    }
+
+    if (o.window && !o.dump) {
+        DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0]};
+        return dg_run_sam_windows(wo, data, size, ref);
     }
 
     // ---- consensus workers: one thread + context per GPU (the reference starts its N consensus

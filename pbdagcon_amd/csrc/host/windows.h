@@ -1,0 +1,250 @@
+// windows.h -- `pbdagcon --sam --ref F --window W [--overlap O]`: targets of any length and depth.
+//
+// Window i of a target has the core [iW, min((i + 1)W, tlen)) and is run as [max(0, iW - O), min(tlen, (i + 1)W + O));
+// a target of at most W bases is one window.  Windows go to the device in groups of about --batch-targets
+// (dagcon_consensus_cigar_windows on a DAGCON_FLAG_BASE_POS context, with DAGCON_FLAG_BASE_SUPPORT for --fastq); a group
+// gets only the records whose [s, e) meets it, which the host knows from the ops it has parsed.  Records of one RNAME
+// must be consecutive and ascending in POS, as in a coordinate-sorted SAM.
+//
+// The stitch (DgStitch; tests/window_twin.py: stitch is its numpy twin).  With g = pos + window begin the 1-based
+// target position of a consensus base (dagcon_fetch_positions): of a window's segment the bases from the first one
+// with g > core begin up to, not including, the first one from there on with g > core end are kept -- first crossings
+// only, nothing assumes that g is monotone; a segment whose kept part is empty is ignored.  A segment was cut at its
+// core begin when bases lie in front of the kept part, at its core end when bases lie behind it.  A kept part that was
+// cut at its core begin continues the piece before it when that piece ends with the kept part just before it, comes
+// from the window just before, and was cut at its core end; in every other case there is a break.  Joined pieces
+// shorter than -m are dropped.  A record is >RNAME/t0_t1 with t0 = g of the first base - 1 and t1 = g of the last:
+// target coordinates (in this mode only; everywhere else the name holds indexes into the consensus string, quirk Q5).
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../../include/dagcon.h"
+#include "fastq.h"
+#include "sam.h"
+
+struct DgStitchPiece {
+    long long t0 = 0, t1 = 0;
+    std::string seq;
+    std::vector<uint16_t> weight, depth;                   // --fastq: sliced as the bases are
+};
+
+// the pieces of one target, fed window by window in order
+struct DgStitch {
+    std::vector<DgStitchPiece> pieces;
+    long long open_w = -1;                                 // window of the last piece, if it was cut at its core end
+    void reset() { pieces.clear(); open_w = -1; }
+    // one segment of window wi = [begin, ..), core [c0, c1); weight / depth may be NULL
+    void add(long long wi, uint32_t begin, uint32_t c0, uint32_t c1, const char *seq, const uint32_t *pos, uint32_t n,
+             const uint16_t *weight, const uint16_t *depth) {
+        uint32_t i0 = 0;
+        while (i0 < n && (uint64_t)pos[i0] + begin <= c0) i0++;
+        if (i0 == n) return;
+        uint32_t i1 = i0;
+        while (i1 < n && (uint64_t)pos[i1] + begin <= c1) i1++;
+        if (i1 <= i0) return;
+        const long long last_g = (long long)pos[i1 - 1] + begin;
+        if (i0 > 0 && open_w >= 0 && open_w == wi - 1 && !pieces.empty()) {
+            DgStitchPiece &p = pieces.back();
+            p.t1 = last_g;
+            p.seq.append(seq + i0, i1 - i0);
+            if (weight) { p.weight.insert(p.weight.end(), weight + i0, weight + i1); p.depth.insert(p.depth.end(), depth + i0, depth + i1); }
+        } else {
+            pieces.emplace_back();
+            DgStitchPiece &p = pieces.back();
+            p.t0 = (long long)pos[i0] + begin - 1; p.t1 = last_g;
+            p.seq.assign(seq + i0, i1 - i0);
+            if (weight) { p.weight.assign(weight + i0, weight + i1); p.depth.assign(depth + i0, depth + i1); }
+        }
+        open_w = i1 < n ? wi : -1;
+    }
+};
+
+struct DgWinOpts {
+    unsigned min_cov, min_len, trim, window, overlap;
+    size_t batch_targets;
+    bool fastq, verbose;
+    int device;
+};
+
+// the whole run; the process's exit status
+inline int dg_run_sam_windows(const DgWinOpts &o, const char *data, size_t size, const DgRefSeqs &ref) {
+    struct Rec { uint32_t pos, s, e, q_len; const char *q; uint64_t op0; uint32_t nops; };
+    struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; };
+    std::vector<Tgt> tgts;
+    std::vector<uint32_t> ops;
+    std::unordered_map<std::string, int> seen;
+    unsigned long long lineno = 0, skipped = 0;
+    // ---- parse: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL ----
+    for (size_t p = 0; p < size;) {
+        const char *line = data + p;
+        const char *nl = (const char *)memchr(line, '\n', size - p);
+        size_t ll = nl ? (size_t)(nl - line) : size - p;
+        p += ll + (nl ? 1 : 0);
+        lineno++;
+        if (ll && line[ll - 1] == '\r') ll--;
+        if (ll == 0 || line[0] == '@') continue;
+        const char *f[11]; size_t fl[11]; int nf = 0;
+        for (size_t i = 0; nf < 11;) {
+            const char *tab = (const char *)memchr(line + i, '\t', ll - i);
+            const size_t j = tab ? (size_t)(tab - line) : ll;
+            f[nf] = line + i; fl[nf] = j - i; nf++;
+            if (!tab) break;
+            i = j + 1;
+        }
+        if (nf < 10) { fprintf(stderr, "pbdagcon: line %llu: a SAM record has 11 fields, this one has fewer than 10 fields\n", lineno); return 1; }
+        auto star = [&](int k) { return fl[k] == 1 && f[k][0] == '*'; };
+        uint64_t flag = 0, pos = 0;
+        for (size_t i = 0; i < fl[1] && f[1][i] >= '0' && f[1][i] <= '9'; i++) flag = flag * 10 + (uint64_t)(f[1][i] - '0');
+        for (size_t i = 0; i < fl[3] && f[3][i] >= '0' && f[3][i] <= '9' && pos < (1ull << 40); i++) pos = pos * 10 + (uint64_t)(f[3][i] - '0');
+        if ((flag & (DG_SAM_UNMAPPED | DG_SAM_SECONDARY)) || star(2) || star(5) || star(9)) { skipped++; continue; }
+        const std::string rname(f[2], fl[2]);
+        if (tgts.empty() || tgts.back().name != rname) {
+            const DgRefSeqs::Span *sp = ref.find(f[2], fl[2]);
+            if (!sp) { fprintf(stderr, "pbdagcon: line %llu: RNAME %s is not a sequence of --ref\n", lineno, rname.c_str()); return 1; }
+            if (!seen.emplace(rname, 1).second) { fprintf(stderr, "pbdagcon: line %llu: records of RNAME %s come back after another target's (records of one RNAME must be consecutive)\n", lineno, rname.c_str()); return 1; }
+            tgts.emplace_back();
+            tgts.back().name = rname; tgts.back().sp = *sp;
+        }
+        Tgt &t = tgts.back();
+        const long k = dg_cigar_ops(f[5], fl[5], nullptr);
+        if (k < 0) { fprintf(stderr, "pbdagcon: line %llu: malformed CIGAR %.*s\n", lineno, (int)std::min<size_t>(fl[5], 60), f[5]); return 1; }
+        Rec r;
+        r.pos = pos > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pos;
+        if (!t.recs.empty() && r.pos < t.recs.back().pos) { fprintf(stderr, "pbdagcon: line %llu: POS %u of RNAME %s is below that of the record before it (--window needs records ascending in POS, as in a coordinate-sorted SAM)\n", lineno, r.pos, rname.c_str()); return 1; }
+        r.q = f[9]; r.q_len = (uint32_t)fl[9]; r.op0 = ops.size(); r.nops = (uint32_t)k;
+        ops.resize(ops.size() + (size_t)k);
+        dg_cigar_ops(f[5], fl[5], ops.data() + r.op0);
+        // [s, e) by the rule of include/dagcon.h (a non-conforming record: clipped into the target, at least one base)
+        uint64_t nt = 0;
+        for (long i = 0; i < k; i++) { const uint32_t op = ops[r.op0 + i]; if ((1u << (op & 15u)) & 0x185u) nt += op >> 4; }
+        const uint64_t tl = t.sp.len;
+        uint64_t s0 = r.pos ? r.pos - 1u : 0u, e0 = s0 + (nt & 0xFFFFFFFFull);
+        if (tl && s0 > tl - 1) s0 = tl - 1;
+        if (e0 < s0 + 1) e0 = s0 + 1;
+        if (e0 > tl) e0 = tl;
+        r.s = (uint32_t)s0; r.e = (uint32_t)e0;
+        t.max_span = std::max(t.max_span, r.e > r.s ? r.e - r.s : 0u);
+        t.recs.push_back(r);
+    }
+    if (o.verbose && skipped) fprintf(stderr, "pbdagcon: %llu SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')\n", skipped);
+    // ---- the windows of every target, in target order ----
+    struct Win { uint32_t tgt, idx, begin, end, c0, c1; };
+    std::vector<Win> wins;
+    for (uint32_t g = 0; g < tgts.size(); g++) {
+        const uint64_t tl = tgts[g].sp.len;
+        if (!tl) continue;
+        const uint64_t nw = (tl + o.window - 1) / o.window;
+        for (uint64_t i = 0; i < nw; i++) {
+            const uint64_t c0 = i * o.window, c1 = std::min<uint64_t>((i + 1) * o.window, tl);
+            wins.push_back(Win{g, (uint32_t)i, (uint32_t)(c0 > o.overlap ? c0 - o.overlap : 0), (uint32_t)std::min<uint64_t>(tl, (i + 1) * (uint64_t)o.window + o.overlap), (uint32_t)c0, (uint32_t)c1});
+        }
+    }
+    dagcon_ctx *ctx = nullptr;
+    dagcon_opts dopt;
+    dagcon_default_opts(&dopt);
+    dopt.min_cov = o.min_cov; dopt.min_len = o.min_len; dopt.trim = o.trim;
+    dopt.min_weight = (int32_t)o.min_cov;
+    dopt.device = o.device;
+    dopt.flags = DAGCON_FLAG_BASE_POS | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u);
+    int rc = dagcon_create(&dopt, &ctx);
+    if (rc != DAGCON_OK) {
+        fprintf(stderr, "pbdagcon: no usable MI355X as device %d (dagcon_create = %d); there is no CPU fallback\n", o.device, rc);
+        return 1;
+    }
+    int status = 0;
+    DgStitch st;
+    std::string out;
+    long long cur_tgt = -1;
+    auto flush_target = [&]() {
+        if (cur_tgt < 0) return true;
+        for (const DgStitchPiece &p : st.pieces) {
+            if (p.seq.size() < o.min_len) continue;
+            char head[64];
+            snprintf(head, sizeof head, "/%lld_%lld", p.t0, p.t1);
+            if (o.fastq) {
+                if (!dg_append_fastq(out, tgts[(size_t)cur_tgt].name + head, p.seq.data(), (uint32_t)p.seq.size(), p.weight.data(), p.depth.data())) return false;
+            } else {
+                out += '>'; out += tgts[(size_t)cur_tgt].name; out += head; out += '\n'; out += p.seq; out += '\n';
+            }
+        }
+        fwrite(out.data(), 1, out.size(), stdout);
+        out.clear();
+        st.reset();
+        return true;
+    };
+    // ---- groups of windows ----
+    for (size_t w0 = 0; w0 < wins.size() && status == 0;) {
+        const size_t w1 = std::min(wins.size(), w0 + std::max<size_t>(1, o.batch_targets));
+        // the batch: the targets the group touches, each with the records that meet the group's stretch of it
+        std::vector<uint32_t> b_tlen, b_pos, b_qlen, b_ops, w_t, w_b, w_e;
+        std::vector<uint64_t> b_toff, b_rec{0}, b_qoff, b_opb{0};
+        std::string qblob;
+        for (size_t a = w0; a < w1;) {
+            size_t z = a;
+            while (z < w1 && wins[z].tgt == wins[a].tgt) z++;
+            const Tgt &t = tgts[wins[a].tgt];
+            const uint32_t lo = wins[a].begin, hi = wins[z - 1].end;
+            const uint32_t bt = (uint32_t)b_tlen.size();
+            b_tlen.push_back(t.sp.len); b_toff.push_back(t.sp.off);
+            // records are ascending in s: none that starts more than the longest span in front of lo reaches it
+            const uint32_t from = lo > t.max_span ? lo - t.max_span : 0u;
+            auto it = std::lower_bound(t.recs.begin(), t.recs.end(), from, [](const Rec &r, uint32_t v) { return r.s < v; });
+            for (; it != t.recs.end() && it->s < hi; ++it) {
+                if (it->e <= lo) continue;
+                b_pos.push_back(it->pos); b_qoff.push_back(qblob.size()); b_qlen.push_back(it->q_len);
+                qblob.append(it->q, it->q_len);
+                b_ops.insert(b_ops.end(), ops.begin() + (long)it->op0, ops.begin() + (long)(it->op0 + it->nops));
+                b_opb.push_back(b_ops.size());
+            }
+            b_rec.push_back(b_pos.size());
+            for (size_t k = a; k < z; k++) { w_t.push_back(bt); w_b.push_back(wins[k].begin); w_e.push_back(wins[k].end); }
+            a = z;
+        }
+        dagcon_cigar_batch cb;
+        memset(&cb, 0, sizeof cb);
+        cb.n_targets = (uint32_t)b_tlen.size(); cb.tlen = b_tlen.data(); cb.t_off = b_toff.data();
+        cb.t_blob = ref.bases.data(); cb.t_bytes = ref.bases.size();
+        cb.rec_begin = b_rec.data(); cb.pos = b_pos.data(); cb.q_off = b_qoff.data(); cb.q_len = b_qlen.data();
+        cb.q_blob = qblob.data(); cb.q_bytes = qblob.size(); cb.op_begin = b_opb.data(); cb.ops = b_ops.data();
+        dagcon_windows dw;
+        dw.n_windows = (uint32_t)w_t.size(); dw.target = w_t.data(); dw.begin = w_b.data(); dw.end = w_e.data();
+        dagcon_results r;
+        rc = dagcon_consensus_cigar_windows(ctx, &cb, &dw, &r);
+        const uint32_t *pos = nullptr;
+        uint64_t npos = 0;
+        dagcon_support sup;
+        memset(&sup, 0, sizeof sup);
+        if (rc == DAGCON_OK) rc = dagcon_fetch_positions(ctx, &pos, &npos);
+        if (rc == DAGCON_OK && o.fastq) rc = dagcon_fetch_support(ctx, &sup);
+        if (rc != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); status = 1; break; }
+        for (size_t k = w0; k < w1; k++) {
+            const Win &w = wins[k];
+            if ((long long)w.tgt != cur_tgt) {
+                if (!flush_target()) { status = 1; break; }
+                cur_tgt = w.tgt;
+            }
+            const size_t g = k - w0;
+            if (r.target_status[g] != DAGCON_OK)
+                fprintf(stderr, "pbdagcon: warning: %s window [%u, %u) skipped (%s)\n", tgts[w.tgt].name.c_str(), w.begin, w.end,
+                        r.target_status[g] == DAGCON_ERR_NONCONFORMING ? "a record's CIGAR does not fit its SEQ or its target, or holds N or a length of 0"
+                        : r.target_status[g] == DAGCON_ERR_UNSUPPORTED ? "too large" : "internal error");
+            if (o.verbose) fprintf(stderr, "pbdagcon: %s window %u [%u, %u): %llu segments\n", tgts[w.tgt].name.c_str(), w.idx, w.begin, w.end,
+                                   (unsigned long long)(r.seg_begin[g + 1] - r.seg_begin[g]));
+            for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
+                const uint64_t off = r.seq_off[s];
+                st.add(w.idx, w.begin, w.c0, w.c1, r.seq_blob + off, pos + off, r.seq_len[s],
+                       o.fastq ? sup.weight + off : nullptr, o.fastq ? sup.depth + off : nullptr);
+            }
+        }
+        w0 = w1;
+    }
+    if (status == 0 && !flush_target()) status = 1;
+    fflush(stdout);
+    dagcon_destroy(ctx);
+    return status;
+}

@@ -786,8 +786,9 @@ __global__ __launch_bounds__(64) void k_bp_check(DgParams p) {
 // The best path passes through every cut vertex, so its stretch from one cut to the next is
 // walked by its own wave.  A segment leaves one byte per path vertex in its own stretch of
 // the scratch (ids of a segment are contiguous): the base, bit 7 = weight >= minWeight.
-template <bool SUP = false>
+template <bool SUP = false, bool POS = false>
 __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
+    constexpr bool SB = SUP || POS;                          // the walk carries _bbMap of its path bases
     const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
     if (dg_failed(p) || dg_tskip(p, t)) return;
     const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
@@ -795,7 +796,7 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
     if (seg >= nseg) return;
     const int lane = threadIdx.x;
     const uint64_t nb = p.node_base[t];
-    __shared__ typename std::conditional<SUP, DgWalkSharedS, DgWalkShared>::type W;
+    __shared__ typename std::conditional<SB, DgWalkSharedS, DgWalkShared>::type W;
     const DgNode *nd = p.nodes + nb;
     const int32_t *best = p.best + nb;
     const int N = (int)p.n_nodes[t];
@@ -812,6 +813,7 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
     // no load of the support waits on the walk's chain
     const int32_t *cov = SUP ? p.cov + p.bbv_base[t] : nullptr;
     uint32_t *stmp = SUP ? p.sup_tmp + nb + c0 : nullptr;
+    uint32_t *ptmp = POS ? p.pos_tmp + nb + c0 : nullptr;     // POS: _bbMap itself, a second scratch word per path base
     uint32_t pw = 0;
     int32_t pdep = 0;
     int prow = -1;
@@ -825,7 +827,7 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
                 const int b = best[id];
                 const int xw = id & (DG_WR - 1);
                 W.wtag[xw] = id; W.wbest[xw] = b; W.wbase[xw] = (int)(h.y & 0xffu); W.wweight[xw] = (int)h.z;
-                if constexpr (SUP) W.wbase[xw] = (int)(h.y & 0xffu) | (nd[id].bbpos << 8);     // (bbpos < 2^18)
+                if constexpr (SB) W.wbase[xw] = (int)(h.y & 0xffu) | (nd[id].bbpos << 8);     // (bbpos < 2^18)
             }
             cs++;
         }
@@ -836,23 +838,24 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
         if (__builtin_amdgcn_readfirstlane(wt) == v) {
             nxt = __builtin_amdgcn_readfirstlane(wb); base = (uint8_t)__builtin_amdgcn_readfirstlane(wa);
             w = __builtin_amdgcn_readfirstlane(ww);
-            if constexpr (SUP) bbp = __builtin_amdgcn_readfirstlane(wa) >> 8;
+            if constexpr (SB) bbp = __builtin_amdgcn_readfirstlane(wa) >> 8;
         } else {
             const uint4 h = *reinterpret_cast<const uint4 *>(&nd[v]);
             nxt = __builtin_amdgcn_readfirstlane(best[v]);
             base = (uint8_t)__builtin_amdgcn_readfirstlane((int)(h.y & 0xffu));
             w = __builtin_amdgcn_readfirstlane((int)h.z);
-            if constexpr (SUP) bbp = __builtin_amdgcn_readfirstlane(nd[v].bbpos);
+            if constexpr (SB) bbp = __builtin_amdgcn_readfirstlane(nd[v].bbpos);
         }
         if (!(base == eb || base == xb)) {
             if (lane == 0) W.wbuf[idx & 63] = (unsigned char)(base | (w >= minw ? 0x80u : 0u));
-            if constexpr (SUP) { if (lane == 0) { W.sw[idx & 63] = (uint32_t)w; W.sb[idx & 63] = (uint32_t)bbp; } }
+            if constexpr (SB) { if (lane == 0) { W.sw[idx & 63] = (uint32_t)w; W.sb[idx & 63] = (uint32_t)bbp; } }
             if ((idx & 63) == 63) {
                 tmp[(idx & ~63) + lane] = W.wbuf[lane];
                 if constexpr (SUP) {
                     if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
                     pw = W.sw[lane]; pdep = cov[W.sb[lane]]; prow = idx & ~63;
                 }
+                if constexpr (POS) ptmp[(idx & ~63) + lane] = W.sb[lane];
             }
             idx++;
         }
@@ -866,6 +869,7 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
         if (lane < (idx & 63)) sbad |= dg_sup_put(stmp + (idx & ~63) + lane, W.sw[lane], cov[W.sb[lane]]);
         if (__ballot(sbad)) bad = true;
     }
+    if constexpr (POS) { if (lane < (idx & 63)) ptmp[(idx & ~63) + lane] = W.sb[lane]; }
     if (lane == 0) {
         if (bad) dg_fail_target(p, t, DG_E_INTERNAL);
         p.bp_len[blockIdx.x] = (uint32_t)idx;
@@ -877,7 +881,7 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
 // 0 .. 2 in one load -- so what counts is how many walks are in flight; the bytes leave one at a time.
 // SUP: lane 3 fetches the vertex's bbpos in the same load; the depth it gathers with it is stored one step later, behind
 // the next step's own load (loads return in order), so it never waits on the walk's chain.
-template <bool SUP = false>
+template <bool SUP = false, bool POS = false>
 __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
     if (dg_failed(p)) return;
     const int l = threadIdx.x & (DG_BRW - 1);
@@ -900,13 +904,14 @@ __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
     int go = v != c1 ? 1 : 0;
     const int32_t *cov = SUP ? p.cov + p.bbv_base[t] : nullptr;
     uint32_t *stmp = SUP ? p.sup_tmp + nb + c0 : nullptr;
+    uint32_t *ptmp = POS ? p.pos_tmp + nb + c0 : nullptr;     // POS: lane 3 stores the _bbMap it has loaded
     int pend = -1;                                           // SUP: the path base whose support is still to be stored
     uint32_t pw = 0;
     int32_t pdep = 0;
     bool sbad = false;
     while (go) {
         const char *a = l == 1 ? reinterpret_cast<const char *>(&nd[v]) + 4 : l == 2 ? reinterpret_cast<const char *>(&nd[v]) + 8
-                      : (SUP && l == 3) ? reinterpret_cast<const char *>(&nd[v]) + 28 : reinterpret_cast<const char *>(&best[v]);
+                      : ((SUP || POS) && l == 3) ? reinterpret_cast<const char *>(&nd[v]) + 28 : reinterpret_cast<const char *>(&best[v]);
         const uint32_t g = *reinterpret_cast<const uint32_t *>(a);
         const int nxt = __shfl((int)g, 0, DG_BRW);
         const uint32_t base = (uint32_t)__shfl((int)g, 1, DG_BRW) & 0xffu;
@@ -918,6 +923,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
         if (!(base == eb || base == xb)) {
             if (l == 0) tmp[idx] = (uint8_t)(base | (w >= minw ? 0x80u : 0u));
             if constexpr (SUP) { pend = idx; pw = (uint32_t)w; if (l == 3) pdep = cov[(int)g]; }
+            if constexpr (POS) { if (l == 3) ptmp[idx] = g; }
             idx++;
         }
         if (nxt < 0) go = 0;
@@ -939,7 +945,8 @@ __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
 
 // ---- consensus segmentation (:327-373) and output, one wave per target ------------
 // SUP: the support words of the kept bases go out beside them, weight and depth apart (p.sup_w / p.sup_d at cns_off[t])
-template <bool SUP = false>
+// POS: and the _bbMap of each (p.pos_out at cns_off[t])
+template <bool SUP = false, bool POS = false>
 __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
     const uint32_t t = blockIdx.x;
     if (dg_failed(p) || dg_tskip(p, t)) return;
@@ -1048,6 +1055,13 @@ __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
                 p.sup_w[co + g0s + j] = (uint16_t)(x & 0xffffu);
                 p.sup_d[co + g0s + j] = (uint16_t)(x >> 16);
             }
+        }
+    }
+    if constexpr (POS) {
+        for (uint32_t s = 0; s < nseg; s++) {
+            const uint32_t g0s = s_off[s], len = s_off[s + 1] - s_off[s];
+            const uint32_t *src = (p.gcuts && s == 0) ? p.pos_tmp0 + nb : p.pos_tmp + nb + s_c0[s];
+            for (uint32_t j = lane; j < len && g0s + j < keep; j += 64) p.pos_out[co + g0s + j] = src[j];
         }
     }
     for (uint32_t i = lane; i < nout; i += 64) {
@@ -1306,8 +1320,9 @@ __global__ __launch_bounds__(64) void k_bp_defer(DgParams p) {
     if (left) dg_fail_target(p, t, DG_E_INTERNAL);
 }
 
-template <bool SUP = false>
+template <bool SUP = false, bool POS = false>
 __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
+    constexpr bool SB = SUP || POS;
     const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
     if (dg_failed(p) || dg_tskip(p, t)) return;
     const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
@@ -1315,7 +1330,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
     if (seg >= nseg) return;
     const int lane = threadIdx.x;
     const uint64_t nb = p.node_base[t];
-    __shared__ typename std::conditional<SUP, DgWalkSharedS, DgWalkShared>::type W;
+    __shared__ typename std::conditional<SB, DgWalkSharedS, DgWalkShared>::type W;
     const DgNode *nd = p.nodes + nb;
     const int32_t *best = p.best + nb;
     const int N = (int)p.n_nodes[t];
@@ -1331,6 +1346,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
     bool bad = false;
     const int32_t *cov = SUP ? p.cov + p.bbv_base[t] : nullptr;    // (SUP: as in k_bp_walk)
     uint32_t *stmp = SUP ? (seg == 0 ? p.sup_tmp0 + nb : p.sup_tmp + nb + c0) : nullptr;
+    uint32_t *ptmp = POS ? (seg == 0 ? p.pos_tmp0 + nb : p.pos_tmp + nb + c0) : nullptr;
     uint32_t pw = 0;
     int32_t pdep = 0;
     int prow = -1;
@@ -1350,7 +1366,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
                 const int b = best[id];
                 const int xw = id & (DG_WR - 1);
                 W.wtag[xw] = id; W.wbest[xw] = b; W.wbase[xw] = (int)(h.y & 0xffu); W.wweight[xw] = (int)h.z;
-                if constexpr (SUP) W.wbase[xw] = (int)(h.y & 0xffu) | (nd[id].bbpos << 8);     // (bbpos < 2^18)
+                if constexpr (SB) W.wbase[xw] = (int)(h.y & 0xffu) | (nd[id].bbpos << 8);     // (bbpos < 2^18)
             }
             cs++;
         }
@@ -1361,23 +1377,24 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
         if (__builtin_amdgcn_readfirstlane(wt) == v) {
             nxt = __builtin_amdgcn_readfirstlane(wb); base = (uint8_t)__builtin_amdgcn_readfirstlane(wa);
             w = __builtin_amdgcn_readfirstlane(ww);
-            if constexpr (SUP) bbp = __builtin_amdgcn_readfirstlane(wa) >> 8;
+            if constexpr (SB) bbp = __builtin_amdgcn_readfirstlane(wa) >> 8;
         } else {
             const uint4 h = *reinterpret_cast<const uint4 *>(&nd[v]);
             nxt = __builtin_amdgcn_readfirstlane(best[v]);
             base = (uint8_t)__builtin_amdgcn_readfirstlane((int)(h.y & 0xffu));
             w = __builtin_amdgcn_readfirstlane((int)h.z);
-            if constexpr (SUP) bbp = __builtin_amdgcn_readfirstlane(nd[v].bbpos);
+            if constexpr (SB) bbp = __builtin_amdgcn_readfirstlane(nd[v].bbpos);
         }
         if (!(base == eb || base == xb)) {
             if (lane == 0) W.wbuf[idx & 63] = (unsigned char)(base | (w >= minw ? 0x80u : 0u));
-            if constexpr (SUP) { if (lane == 0) { W.sw[idx & 63] = (uint32_t)w; W.sb[idx & 63] = (uint32_t)bbp; } }
+            if constexpr (SB) { if (lane == 0) { W.sw[idx & 63] = (uint32_t)w; W.sb[idx & 63] = (uint32_t)bbp; } }
             if ((idx & 63) == 63) {
                 tmp[(idx & ~63) + lane] = W.wbuf[lane];
                 if constexpr (SUP) {
                     if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
                     pw = W.sw[lane]; pdep = cov[W.sb[lane]]; prow = idx & ~63;
                 }
+                if constexpr (POS) ptmp[(idx & ~63) + lane] = W.sb[lane];
             }
             idx++;
         }
@@ -1391,6 +1408,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
         if (lane < (idx & 63)) sbad |= dg_sup_put(stmp + (idx & ~63) + lane, W.sw[lane], cov[W.sb[lane]]);
         if (__ballot(sbad)) bad = true;
     }
+    if constexpr (POS) { if (lane < (idx & 63)) ptmp[(idx & ~63) + lane] = W.sb[lane]; }
     if (lane == 0) {
         if (bad) dg_fail_target(p, t, DG_E_INTERNAL);
         p.bp_len[blockIdx.x] = (uint32_t)idx;

@@ -150,3 +150,131 @@ __global__ __launch_bounds__(64) void k_cigar_expand(DgCigarParams p) {
         ot[c] = (b & DG_CG_T_MASK) ? t[s_t0[lo] + k] : (uint8_t)'-';
     }
 }
+
+// ---- records cut to windows (dagcon_upload_cigar_windows; include/dagcon.h has the rule) ----------------------------
+// A piece is one (record, window) pair: the record's columns [F(A), F(B)), F(x) the first column that consumes target
+// base x, F(s) = 0 and F(e) = the record's column count.  The host lists the pieces from the scan's totals (it knows
+// s = pos - 1 and e = s + target bases) and gives each the two bounds relative to s: 0 <= a_rel < b_rel <= target bases.
+//
+// k_cigar_cut: a wave per piece.  For a bound x strictly inside the record, the tile that consumes base x is the last
+// one whose checkpoint has at most x target bases in front (ckpt[].z is monotone over a record's tiles): a 64-ary
+// search, every lane one checkpoint per round and a ballot.  Then one 64-lane load of that tile's ops, the prefix sums
+// of k_cigar_expand, and a ballot for the op whose target bases hold x; the column follows from that lane's sums.
+// No lane walks ops one by one.  Output per piece: F(A), F(B), the tile of F(A), the tile of F(B) (record-relative).
+//
+// k_cigar_expand_cut: a wave per (piece, tile), k_cigar_expand's table and search on the columns of the tile that lie
+// inside [F(A), F(B)), written at the piece's own offset less F(A).  A record that crosses k windows is expanded k
+// times from the one copy of its ops and bases.
+//
+// Out-of-bounds safety: pieces are listed only for conforming records (their sums fit 32 bits, consume q_len read bases
+// and stay inside the target).  The host takes k_cigar_cut's four words back and refuses anything but
+// F(A) <= F(B) <= columns and first tile <= last tile < the record's tiles before it plans the output: a piece's room
+// is F(B) - F(A) bytes rounded up to 16, and the expansion writes column c only when F(A) <= c < F(B), at c - F(A).
+// Its reads are those of k_cigar_expand: inside [0, q_len) and [pos - 1, pos - 1 + target bases).
+#define DG_CG_NO_COL 0xFFFFFFFFu   // k_cigar_cut found no op for a bound (the host fails the call: never expanded)
+
+struct DgCigarCutParams {
+    const uint4 *piece;            // [n_pieces] record, a_rel, b_rel, -
+    uint4 *cut;                    // [n_pieces] F(A), F(B), tile of F(A), tile of F(B)
+    uint32_t n_pieces;
+    // expansion
+    const uint32_t *wave_piece;    // [n_waves] the piece of each wave
+    const uint32_t *wave_begin;    // [n_pieces] the piece's first wave
+    const uint64_t *piece_out;     // [n_pieces] where the piece's strings go
+    uint32_t n_waves;
+};
+
+// the column and the tile of bound x (0 < x < the record's target bases); wave-uniform in and out
+__device__ __forceinline__ void dg_cg_find(const DgCigarParams &p, uint32_t r, uint64_t tile0, uint32_t ntile, uint32_t x,
+                                           uint32_t lane, uint32_t &col, uint32_t &tile) {
+    uint32_t lo = 0, n = ntile;
+    for (;;) {                                                    // z of tile lo is at most x throughout
+        const uint32_t stride = (n + 63u) / 64u;
+        const bool le = lane * stride < n && p.ckpt[tile0 + lo + lane * stride].z <= x;
+        uint32_t cnt = (uint32_t)__popcll(__ballot(le));
+        if (cnt == 0) cnt = 1;
+        const uint32_t end = lo + n;
+        lo += (cnt - 1u) * stride;
+        n = end - lo < stride ? end - lo : stride;
+        if (stride <= 1u) break;
+    }
+    tile = lo;
+    const uint4 ck = p.ckpt[tile0 + lo];
+    const uint64_t o = p.op_begin[r] + (uint64_t)lo * 64u, oe = p.op_begin[r + 1];
+    const bool have = o + lane < oe;
+    const uint32_t op = have ? p.ops[o + lane] : 0u;
+    const uint32_t code = op & 15u, len = op >> 4;
+    const uint32_t bit = have ? 1u << code : 0u;
+    const uint32_t i_col = (bit & DG_CG_COL_MASK) ? len : 0u;
+    const uint32_t i_t = (bit & DG_CG_T_MASK) ? len : 0u;
+    const uint32_t e_col = dg_cg_scan32(i_col), e_t = dg_cg_scan32(i_t);
+    const uint32_t t0 = ck.z + e_t - i_t;                         // the op's first target base
+    const unsigned long long hit = __ballot(i_t != 0u && t0 <= x && x - t0 < i_t);
+    const uint32_t mine = ck.x + e_col - i_col + (x - t0);        // (an op with target bases has a column for each)
+    col = hit ? (uint32_t)__shfl((int)mine, __ffsll((long long)hit) - 1) : DG_CG_NO_COL;
+}
+
+// a wave per piece (four to a workgroup)
+__global__ __launch_bounds__(256) void k_cigar_cut(DgCigarParams p, DgCigarCutParams w) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t pc = blockIdx.x * 4u + (threadIdx.x >> 6);     // wave-uniform
+    if (pc >= w.n_pieces) return;
+    const uint4 pi = w.piece[pc];
+    const uint32_t r = pi.x;
+    const uint4 tot = p.totals[r];
+    const uint64_t tile0 = p.tile_begin[r];
+    const uint32_t ntile = (uint32_t)(p.tile_begin[r + 1] - tile0);
+    uint32_t ca = 0, ta = 0, cb = tot.x, tb = ntile ? ntile - 1u : 0u;
+    if (ntile) {
+        if (pi.y != 0u && pi.y < tot.z) dg_cg_find(p, r, tile0, ntile, pi.y, lane, ca, ta);
+        if (pi.z < tot.z) dg_cg_find(p, r, tile0, ntile, pi.z, lane, cb, tb);
+    }
+    if (lane == 0) w.cut[pc] = make_uint4(ca, cb, ta, tb);
+}
+
+// a wave per (piece, tile of 64 ops)
+__global__ __launch_bounds__(64) void k_cigar_expand_cut(DgCigarParams p, DgCigarCutParams w) {
+    __shared__ uint32_t s_end[64], s_q0[64], s_t0[64], s_code[64];
+    const uint32_t lane = threadIdx.x;
+    if (blockIdx.x >= w.n_waves) return;
+    const uint32_t pc = w.wave_piece[blockIdx.x];
+    const uint32_t r = w.piece[pc].x;
+    const uint4 cut = w.cut[pc];
+    const uint32_t k = cut.z + (blockIdx.x - w.wave_begin[pc]);   // the record's k-th tile
+    const uint4 ck = p.ckpt[p.tile_begin[r] + k];
+    const uint64_t o = p.op_begin[r] + (uint64_t)k * 64u, oe = p.op_begin[r + 1];
+    const bool have = o + lane < oe;
+    const uint32_t op = have ? p.ops[o + lane] : 0u;
+    const uint32_t code = op & 15u, len = op >> 4;
+    const uint32_t bit = have ? 1u << code : 0u;
+    const uint32_t i_col = (bit & DG_CG_COL_MASK) ? len : 0u;
+    const uint32_t i_q = (bit & DG_CG_Q_MASK) ? len : 0u;
+    const uint32_t i_t = (bit & DG_CG_T_MASK) ? len : 0u;
+    const uint32_t e_col = dg_cg_scan32(i_col);
+    const uint32_t e_q = dg_cg_scan32(i_q), e_t = dg_cg_scan32(i_t);
+    s_end[lane] = e_col;
+    s_q0[lane] = ck.y + e_q - i_q;
+    s_t0[lane] = ck.z + e_t - i_t;
+    s_code[lane] = code;
+    __syncthreads();
+    const uint32_t n_col = (uint32_t)__builtin_amdgcn_readlane((int)e_col, 63);
+    // the tile's columns are [ck.x, ck.x + n_col) of the record: those inside [F(A), F(B)), tile-relative
+    const uint32_t c_lo = cut.x > ck.x ? cut.x - ck.x : 0u;
+    const uint32_t c_hi = cut.y > ck.x ? (cut.y - ck.x < n_col ? cut.y - ck.x : n_col) : 0u;
+    const uint8_t *q = p.q + p.q_off[r];
+    const uint8_t *t = p.t + p.t_base[r];
+    const uint64_t out = w.piece_out[pc];
+    uint8_t *oq = p.out_q + out, *ot = p.out_t + out;
+    for (uint32_t c = c_lo + lane; c < c_hi; c += 64u) {
+        uint32_t lo = 0;
+#pragma unroll
+        for (uint32_t step = 32u; step; step >>= 1)
+            if (s_end[lo + step - 1u] <= c) lo += step;
+        const uint32_t first = lo ? s_end[lo - 1u] : 0u;
+        const uint32_t kk = c - first;
+        const uint32_t b = 1u << s_code[lo];
+        const uint32_t at = ck.x + c - cut.x;                     // (ck.x + c >= F(A): c >= c_lo)
+        oq[at] = (b & DG_CG_Q_MASK) ? q[s_q0[lo] + kk] : (uint8_t)'-';
+        ot[at] = (b & DG_CG_T_MASK) ? t[s_t0[lo] + kk] : (uint8_t)'-';
+    }
+}

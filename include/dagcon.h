@@ -391,6 +391,23 @@ int dagcon_consensus_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *ba
                                    dagcon_results *results);
 
 /*
+ * dagcon_cigar_batch with q_blob in BAM's 4-bit encoding, as a BAM record's seq field has it: q_off[r] is the BYTE
+ * offset of record r's first base (every record starts on a byte, as in a BAM record), q_len[r] still counts bases,
+ * q_bytes is the size of the packed blob.  Base i of a record is nibble i from q_off: byte i >> 1, the high nibble for
+ * even i, decoded by BAM's table "=ACMGRSVTWYHKDBN" on the device (code 0 is the byte '=', copied like any other byte,
+ * as the SAM line printed from the record would carry it).  windows may be NULL (then: dagcon_upload_cigar /
+ * dagcon_consensus_cigar, else dagcon_upload_cigar_windows / dagcon_consensus_cigar_windows).  t_blob stays one byte a
+ * base.  The result is, byte for byte, that of the unpacked call on the same batch with every read decoded to one
+ * byte a base by the table: segments, target_status, dagcon_fetch_support, dagcon_fetch_positions, the counts in the
+ * timings.  Conformance, confinement of a failure, flags and limits are those of the unpacked calls; the only new
+ * refusal is DAGCON_ERR_INVALID_ARG, before any launch, for q_off + (q_len + 1) / 2 > q_bytes.  Letter case is not
+ * representable (BAM has none).  The unused low nibble of an odd-length record is ignored, whatever it holds.
+ */
+int dagcon_upload_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows);
+int dagcon_consensus_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows,
+                                  dagcon_results *results);
+
+/*
  * Debug / parity aid: adjacency of one target's graph as left by the last
  * dagcon_run (after mergeNodes), in list order.  Vertex ids are in backbone
  * position order: the inserted vertices whose _bbMap is p (in read, column

@@ -37,6 +37,7 @@ EXPORTS = [
     "dagcon_consensus_pre", "dagcon_debug_plan", "dagcon_align_dropped", "dagcon_align_panels",
     "dagcon_align_ends", "dagcon_place", "dagcon_fetch_support", "dagcon_upload_cigar", "dagcon_consensus_cigar",
     "dagcon_fetch_positions", "dagcon_upload_cigar_windows", "dagcon_consensus_cigar_windows",
+    "dagcon_upload_cigar_packed", "dagcon_consensus_cigar_packed",
 ]
 ABI_VERSION = 2
 
@@ -152,6 +153,8 @@ def load() -> C.CDLL:
     L.dagcon_fetch_positions.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint64)]
     L.dagcon_upload_cigar_windows.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows)]
     L.dagcon_consensus_cigar_windows.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(Results)]
+    L.dagcon_upload_cigar_packed.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows)]
+    L.dagcon_consensus_cigar_packed.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(Results)]
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
     L.dagcon_host_free.restype = None
@@ -234,6 +237,7 @@ class HostBatch:
 
 
 CIGAR_OPS = b"MIDNSHP=X"      # BAM op codes 0..8
+BAM_NT16 = b"=ACMGRSVTWYHKDBN"     # BAM's 4-bit base codes 0..15
 
 
 class HostCigarBatch:
@@ -255,6 +259,37 @@ class HostCigarBatch:
         self.op_begin = np.ascontiguousarray(op_begin, dtype=np.uint64)
         self.ops = np.ascontiguousarray(ops, dtype=np.uint32)
         self.ids = ids
+
+    is_packed = False
+
+    def packed(self) -> "HostCigarBatch":
+        """The packed twin (dagcon_upload_cigar_packed): the reads in BAM's 4-bit encoding, two bases a byte, high
+        nibble first, every record on a byte of its own.  A base outside =ACMGRSVTWYHKDBN (lower case too) raises
+        ValueError."""
+        if self.is_packed:
+            return self
+        code = np.full(256, 255, dtype=np.uint8)
+        code[np.frombuffer(BAM_NT16, dtype=np.uint8)] = np.arange(16, dtype=np.uint8)
+        n = self.q_len.astype(np.int64)
+        nb = (n + 1) // 2
+        p_off = np.zeros(n.size, dtype=np.uint64)
+        if n.size:
+            p_off[1:] = np.cumsum(nb)[:-1]
+        # nibble slots of the packed blob, two a byte; the slot of base i of record r is 2 * p_off[r] + i
+        rec = np.repeat(np.arange(n.size), n)
+        i = np.arange(int(n.sum()), dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
+        src = self.q_blob[self.q_off.astype(np.int64)[rec] + i]
+        c = code[src]
+        if (c == 255).any():
+            bad = int(src[c == 255][0])
+            raise ValueError(f"read base {bytes([bad])!r} is not one of {BAM_NT16.decode()}")
+        slots = np.zeros(2 * int(nb.sum()), dtype=np.uint8)
+        slots[2 * p_off.astype(np.int64)[rec] + i] = c
+        blob = (slots[0::2] << 4) | slots[1::2]
+        out = HostCigarBatch(self.tlen, self.t_off, self.t_blob, self.rec_begin, self.pos, p_off, self.q_len, blob,
+                             self.op_begin, self.ops, self.ids)
+        out.is_packed = True
+        return out
 
     @classmethod
     def from_records(cls, targets, ids=None):
@@ -492,6 +527,9 @@ class Context:
         """dagcon_upload_cigar: then run / sync / fetch as after upload."""
         self._keep = batch
         b = batch.c_struct()
+        if batch.is_packed:
+            self._chk(self.L.dagcon_upload_cigar_packed(self.h, C.byref(b), None))
+            return
         self._chk(self.L.dagcon_upload_cigar(self.h, C.byref(b)))
 
     def consensus_cigar(self, batch: HostCigarBatch, strict=True):
@@ -499,7 +537,10 @@ class Context:
         self._keep = batch
         b = batch.c_struct()
         r = Results()
-        self._chk(self.L.dagcon_consensus_cigar(self.h, C.byref(b), C.byref(r)))
+        if batch.is_packed:
+            self._chk(self.L.dagcon_consensus_cigar_packed(self.h, C.byref(b), None, C.byref(r)))
+        else:
+            self._chk(self.L.dagcon_consensus_cigar(self.h, C.byref(b), C.byref(r)))
         out = self._keep_segs(r)
         self._status(r, strict)
         return out
@@ -508,6 +549,9 @@ class Context:
         """dagcon_upload_cigar_windows: then run / sync / fetch as after upload (one result target per window)."""
         self._keep = (batch, windows)
         b, w = batch.c_struct(), windows.c_struct()
+        if batch.is_packed:
+            self._chk(self.L.dagcon_upload_cigar_packed(self.h, C.byref(b), C.byref(w)))
+            return
         self._chk(self.L.dagcon_upload_cigar_windows(self.h, C.byref(b), C.byref(w)))
 
     def consensus_cigar_windows(self, batch: HostCigarBatch, windows: HostWindows, strict=True):
@@ -515,7 +559,10 @@ class Context:
         self._keep = (batch, windows)
         b, w = batch.c_struct(), windows.c_struct()
         r = Results()
-        self._chk(self.L.dagcon_consensus_cigar_windows(self.h, C.byref(b), C.byref(w), C.byref(r)))
+        if batch.is_packed:
+            self._chk(self.L.dagcon_consensus_cigar_packed(self.h, C.byref(b), C.byref(w), C.byref(r)))
+        else:
+            self._chk(self.L.dagcon_consensus_cigar_windows(self.h, C.byref(b), C.byref(w), C.byref(r)))
         out = self._keep_segs(r)
         self._status(r, strict)
         return out

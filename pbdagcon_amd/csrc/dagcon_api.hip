@@ -1644,8 +1644,9 @@ int dagcon_consensus_pre(dagcon_ctx *ctx, const dagcon_pre_batch *b, dagcon_resu
 namespace {
 // what dagcon_upload_cigar and dagcon_upload_cigar_windows share: the checks of the batch, its upload, k_cigar_scan and
 // the totals back on the host (tot: columns, read bases, target bases, DG_CG_* flags per record); p is left ready for
-// an expansion but for its offsets
-int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, DgCigarParams &p, std::vector<uint64_t> &tile_begin, std::vector<uint32_t> &tot) {
+// an expansion but for its offsets.  packed: q_blob holds two bases a byte (dagcon_upload_cigar_packed), a record
+// takes (q_len + 1) / 2 bytes of it from q_off
+int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, bool packed, DgCigarParams &p, std::vector<uint64_t> &tile_begin, std::vector<uint32_t> &tot) {
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->rec_begin || !b->t_off)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
     const uint64_t n64 = T ? b->rec_begin[T] : 0;
@@ -1661,7 +1662,8 @@ int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, DgCigarParams &p, std::vecto
     tile_begin.assign((size_t)n + 1, 0);
     for (uint32_t a = 0; a < n; a++) {
         if (b->op_begin[a + 1] < b->op_begin[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "op_begin not monotone at record %u", a);
-        if (b->q_off[a] > b->q_bytes || b->q_len[a] > b->q_bytes - b->q_off[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "record %u runs past q_blob", a);
+        const uint64_t qb = packed ? ((uint64_t)b->q_len[a] + 1u) / 2u : b->q_len[a];
+        if (b->q_off[a] > b->q_bytes || qb > b->q_bytes - b->q_off[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "record %u runs past q_blob", a);
         if (b->q_len[a] && !b->q_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "q_blob is NULL");
         tile_begin[a + 1] = tile_begin[a] + (b->op_begin[a + 1] - b->op_begin[a] + 63u) / 64u;
     }
@@ -1714,7 +1716,9 @@ extern "C" {
 // SAM-style input: position + ungapped read + CIGAR per record, target bases once per target.  k_cigar_scan sizes
 // every record, the host plans the string blobs as for any batch, k_cigar_expand writes them into d_q / d_t, and
 // upload_impl takes them from there (the door dagcon_consensus_pre uses)
-int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
+}  // extern "C"
+namespace {
+int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed) {
     if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
@@ -1724,7 +1728,7 @@ int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
     DgCigarParams p;
     std::vector<uint64_t> tile_begin;
     std::vector<uint32_t> tot;
-    int r = cigar_scan(c, b, p, tile_begin, tot);
+    int r = cigar_scan(c, b, packed, p, tile_begin, tot);
     if (r != DAGCON_OK) return r;
     const uint64_t n_tiles = tile_begin[n];
     hipStream_t s = c->stream;
@@ -1765,7 +1769,8 @@ int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
     if (n_tiles && bytes) {
         p.t_base = (const uint64_t *)d_tbase.p; p.out_off = (const uint64_t *)d_out.p;
         p.out_q = (uint8_t *)c->d_q.p; p.out_t = (uint8_t *)c->d_t.p;
-        hipLaunchKernelGGL(k_cigar_expand, dim3((uint32_t)n_tiles), dim3(64), 0, s, p);
+        if (packed) hipLaunchKernelGGL(k_cigar_expand_packed, dim3((uint32_t)n_tiles), dim3(64), 0, s, p);
+        else hipLaunchKernelGGL(k_cigar_expand, dim3((uint32_t)n_tiles), dim3(64), 0, s, p);
         HIPCHK(c, hipGetLastError());
     }
     dagcon_batch db;
@@ -1784,7 +1789,7 @@ int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) {
 // cut).  After the scan's totals the host knows every record's [s, e) and lists the (record, window) pieces; k_cigar_cut
 // turns each piece's two target coordinates into columns and tiles, the host plans the output from those, and
 // k_cigar_expand_cut writes every piece from the one device copy of the record's ops and bases.
-int dagcon_upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
+int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, bool packed) {
     if (!ctx || !b || !wn) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
@@ -1804,7 +1809,7 @@ int dagcon_upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, co
     DgCigarParams p;
     std::vector<uint64_t> tile_begin;
     std::vector<uint32_t> tot;
-    int r = cigar_scan(c, b, p, tile_begin, tot);
+    int r = cigar_scan(c, b, packed, p, tile_begin, tot);
     if (r != DAGCON_OK) return r;
     hipStream_t s = c->stream;
     DevBuf &d_tbase = c->d_cg[8], &d_piece = c->d_cg[10], &d_cut = c->d_cg[11], &d_wpiece = c->d_cg[12], &d_wbegin = c->d_cg[13],
@@ -1896,7 +1901,8 @@ int dagcon_upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, co
         p.out_q = (uint8_t *)c->d_q.p; p.out_t = (uint8_t *)c->d_t.p;
         cw.wave_piece = (const uint32_t *)d_wpiece.p; cw.wave_begin = (const uint32_t *)d_wbegin.p;
         cw.piece_out = (const uint64_t *)d_pout.p; cw.n_waves = (uint32_t)wpiece.size();
-        hipLaunchKernelGGL(k_cigar_expand_cut, dim3(cw.n_waves), dim3(64), 0, s, p, cw);
+        if (packed) hipLaunchKernelGGL(k_cigar_expand_cut_packed, dim3(cw.n_waves), dim3(64), 0, s, p, cw);
+        else hipLaunchKernelGGL(k_cigar_expand_cut, dim3(cw.n_waves), dim3(64), 0, s, p, cw);
         HIPCHK(c, hipGetLastError());
     }
     std::vector<uint32_t> wlen(W);
@@ -1911,6 +1917,25 @@ int dagcon_upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, co
     c->h_cig_bad = bad;
     c->cig_err = first_err;
     return DAGCON_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) { return upload_cigar(ctx, b, false); }
+int dagcon_upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
+    return upload_cigar_windows(ctx, b, wn, false);
+}
+// q_blob as a BAM record's seq field has it, two bases a byte (k_cigar.hip.h); windows may be NULL
+int dagcon_upload_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
+    return wn ? upload_cigar_windows(ctx, b, wn, true) : upload_cigar(ctx, b, true);
+}
+int dagcon_consensus_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, dagcon_results *results) {
+    if (!results) return DAGCON_ERR_INVALID_ARG;
+    int r = dagcon_upload_cigar_packed(ctx, batch, windows);
+    if (r != DAGCON_OK) return r;
+    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
+    return dagcon_fetch(ctx, results);
 }
 
 int dagcon_consensus_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, dagcon_results *results) {

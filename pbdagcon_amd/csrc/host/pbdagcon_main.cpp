@@ -19,6 +19,8 @@
 //     default, local ends with --local (DAGCON_FLAG_LOCAL_ALIGN, the reference's SDPAlign(..., Local));
 //   * --sam --ref: SAM text (one ungapped read, a position and a CIGAR per record) against a FASTA of the targets; the
 //     gapped strings are made on the GPU (dagcon_consensus_cigar), never on the host (sam.h);
+//   * --bam --ref: the same from BAM (bam.h: BGZF, inflate and the records); the CIGAR ops and the 4-bit SEQ go to the
+//     GPU as they lie in the file (dagcon_consensus_cigar_packed), the output is that of --sam on the same records;
 //   * blank lines are skipped (the reference duplicates the previous record, Q9);
 //   * a missing input file is an error on stderr, exit 1 (the reference is silent, Q11).
 #include <algorithm>
@@ -41,6 +43,7 @@
 #include <unistd.h>
 
 #include "../../../include/dagcon.h"
+#include "bam.h"
 #include "fastq.h"
 #include "sam.h"
 #include "windows.h"
@@ -52,6 +55,7 @@ struct Opts {
     bool align = false, verbose = false, dump = false;
     bool local = false;                // --local (with -a): the first alignment of every record has local ends
     bool sam = false;                  // --sam: SAM text, the targets' bases from --ref (dagcon_consensus_cigar)
+    bool bam = false;                  // --bam: the same records from BAM (bam.h); sam is set too, and the reads stay 4-bit
     std::string ref;                   // --ref FASTA
     unsigned window = 0, overlap = 1000;   // --window W [--overlap O] (with --sam): targets cut into windows (windows.h)
     bool overlap_set = false;
@@ -69,7 +73,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam --ref <fasta> [--window W [--overlap O]]] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> [--window W [--overlap O]]] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -86,10 +90,17 @@ void usage(FILE *f) {
             "                      POS, CIGAR and SEQ are used, the target's bases come from --ref; records with FLAG 0x4 or\n"
             "                      0x100, or RNAME, CIGAR or SEQ '*', are skipped (counted with -v).  The gapped strings are made\n"
             "                      on the GPU; the output is that of the .m5 input with the same alignments.  Not with -a,\n"
-            "                      --local or --polish.  BAM, PAF and MD:Z-only input (no FASTA) are not read\n"
-            "  --ref FASTA         with --sam (required): the target sequences, by the name up to the first blank; an @SQ line\n"
+            "                      --local or --polish.  PAF and MD:Z-only input (no FASTA) are not read\n"
+            "  --bam               input is BAM: everything --sam does, from the same records in a BAM file (BGZF inflated on the\n"
+            "                      -j threads by this build's own decoder, CRC32 and ISIZE of every member checked).  refID, pos,\n"
+            "                      flag, read_name, the CIGAR (from the CG tag when it has more than 65,535 ops) and seq are used;\n"
+            "                      records with FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ are skipped (counted with -v);\n"
+            "                      errors name the record's ordinal in the file.  The CIGAR ops and the 4-bit bases go to the GPU\n"
+            "                      as they lie in the file.  Indexes, CRAM and QUAL are not read.  Parity unpinned: tested on\n"
+            "                      files from this build's own BAM writer only\n"
+            "  --ref FASTA         with --sam or --bam (required): the target sequences, by the name up to the first blank; an @SQ line\n"
             "                      whose LN differs from the sequence of its SN is an error\n"
-            "  --window W          with --sam: targets of any length and depth.  Every target is cut into windows with cores of W\n"
+            "  --window W          with --sam or --bam: targets of any length and depth.  Every target is cut into windows with cores of W\n"
             "                      bases, each run with --overlap more bases on either side; the records are cut to the windows\n"
             "                      on the GPU and the windows' consensus is joined at target coordinates.  Records of one RNAME\n"
             "                      must then be ascending in POS (a coordinate-sorted SAM).  In this mode only, a record is named\n"
@@ -111,7 +122,7 @@ void usage(FILE *f) {
             "                      targets dealt round-robin, records still printed in input order\n"
             "  --contexts N        consensus workers (thread + context) per GPU, 1..4: a batch's upload and formatting run\n"
             "                      beside another batch's kernels (default: 2 for inputs of several batches, else 1)\n"
-            "  <input>             BLASR -m 5 file (.pre with -a, SAM with --sam) sorted by target, or - for stdin\n"
+            "  <input>             BLASR -m 5 file (.pre with -a, SAM with --sam, BAM with --bam) sorted by target, or - for stdin\n"
             "  version 0.3 (dagcon-mi355x)\n");
 }
 
@@ -140,6 +151,7 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--local") o.local = true;
         else if (a == "--fastq") o.fastq = true;
         else if (a == "--sam") o.sam = true;
+        else if (a == "--bam") o.bam = true;
         else if (a == "--window") { if (!need(&o.window) || !o.window) { fprintf(stderr, "PARSE ERROR: --window takes a positive number of bases\n"); return 2; } }
         else if (a == "--overlap") { if (!need(&o.overlap)) return 2; o.overlap_set = true; }
         else if (a == "--ref") {
@@ -175,10 +187,14 @@ int parse_args(int argc, char **argv, Opts &o) {
         } else { fprintf(stderr, "PARSE ERROR: unknown argument %s\n", a.c_str()); return 2; }
     }
     if (o.local && !o.align) { fprintf(stderr, "PARSE ERROR: --local needs -a\n"); return 2; }
+    if (o.bam && o.sam) { fprintf(stderr, "PARSE ERROR: --bam and --sam do not go together\n"); return 2; }
+    if (o.bam && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --bam does not go with -a, --local or --polish\n"); return 2; }
+    if (o.bam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --bam needs --ref <fasta>\n"); return 2; }
+    if (o.bam) o.sam = true;                               // from here on sam means: records with a CIGAR, from either format
     if (o.sam && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --sam does not go with -a, --local or --polish\n"); return 2; }
     if (o.sam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --sam needs --ref <fasta>\n"); return 2; }
-    if (!o.sam && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam\n"); return 2; }
-    if (o.window && (!o.sam || o.align || o.polish)) { fprintf(stderr, "PARSE ERROR: --window needs --sam and does not go with -a or --polish\n"); return 2; }
+    if (!o.sam && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam or --bam\n"); return 2; }
+    if (o.window && (!o.sam || o.align || o.polish)) { fprintf(stderr, "PARSE ERROR: --window needs --sam or --bam and does not go with -a or --polish\n"); return 2; }
     if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
     if (o.window && (uint64_t)o.overlap < (uint64_t)o.trim + 64) { fprintf(stderr, "PARSE ERROR: --overlap must be at least --trim + 64 (%u)\n", o.trim + 64); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
@@ -282,8 +298,8 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
         cb.pos = b.start.data(); cb.q_off = b.off.data(); cb.q_len = b.len.data();
         cb.q_blob = b.q.data(); cb.q_bytes = b.q.size(); cb.op_begin = b.opb.data(); cb.ops = b.ops.data();
         const double ta0 = wall();
-        rc = dagcon_consensus_cigar(ctx, &cb, &r);
-        if (g_timing) fprintf(stderr, "pbdagcon timing: --sam batch of %zu records: dagcon_consensus_cigar %.3f\n", b.start.size(), wall() - ta0);
+        rc = o.bam ? dagcon_consensus_cigar_packed(ctx, &cb, nullptr, &r) : dagcon_consensus_cigar(ctx, &cb, &r);
+        if (g_timing) fprintf(stderr, "pbdagcon timing: %s batch of %zu records: dagcon_consensus_cigar%s %.3f\n", o.bam ? "--bam" : "--sam", b.start.size(), o.bam ? "_packed" : "", wall() - ta0);
         have_results = true;
     } else if (o.align && !o.polish) {
         // main.cpp:117-145 with -a in one call: the aligned strings stay on the device
@@ -541,15 +557,37 @@ int main(int argc, char **argv) {
     DgRefSeqs ref;
     if (o.sam) {
         std::string err;
-        if (!dg_read_fasta(o.ref, ref, err) || !dg_sam_check_header(data, size, ref, err)) {
+        if (!dg_read_fasta(o.ref, ref, err) || (!o.bam && !dg_sam_check_header(data, size, ref, err))) {
             fprintf(stderr, "pbdagcon: %s\n", err.c_str());
             return 1;
         }
     }
+    // ---- --bam: the file inflated (the -j threads), its header's references against --ref.  From here on data / size
+    // are the inflated records; the compressed file is finished with ----
+    DgBamReader bam;
+    size_t bam_first = 0;                                  // where the first record lies
+    if (o.bam) {
+        std::string err;
+        if (!bam.open((const uint8_t *)data, size, o.threads, err) || !dg_bam_check_refs(bam, ref, err)) {
+            fprintf(stderr, "pbdagcon: %s\n", err.c_str());
+            return 1;
+        }
+        const DgBgzfStats &bs = bam.stats;
+        if (o.verbose && !bs.eof_member) fprintf(stderr, "pbdagcon: note: the BAM file does not end with the empty BGZF member (it may be incomplete)\n");
+        if (timing)
+            fprintf(stderr, "pbdagcon timing: --bam inflate: %zu members, %.1f MB -> %.1f MB in %.3f on %u threads (%.1f MB/s of inflated bytes per thread)\n",
+                    bs.members, bs.file_bytes / 1e6, bs.inflated_bytes / 1e6, bs.wall, bs.threads, bs.busy > 0 ? bs.inflated_bytes / 1e6 / bs.busy : 0.0);
+        if (map) { munmap(map, size); map = nullptr; }
+        slurp.clear(); slurp.shrink_to_fit();
+        data = (const char *)bam.u.data(); size = bam.u.size();
+        bam_first = bam.at;
+    }
 
     if (o.window && !o.dump) {
         DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0]};
-        return dg_run_sam_windows(wo, data, size, ref);
+        if (o.bam) { DgBamSource src(bam, ref); return dg_run_windows(wo, src, ref); }
+        DgSamSource src(data, size, ref);
+        return dg_run_windows(wo, src, ref);
     }
 
     // ---- consensus workers: one thread + context per GPU (the reference starts its N consensus
@@ -679,8 +717,9 @@ int main(int argc, char **argv) {
         const char *id, *name, *q, *t;
         uint32_t idl, namel, len, tlen, start, tl;   // tl: length of the target sequence (.pre); len: of the query string
         char strand;
-        const char *cg; uint32_t cgl, nops;          // --sam: the CIGAR field and its number of ops (t: the target's bases in --ref)
-        unsigned long long line;                     // --sam: line of the input
+        const char *cg; uint32_t cgl, nops;          // --sam: the CIGAR field and its number of ops (t: the target's bases in --ref);
+                                                     // --bam: the ops themselves, q the 4-bit seq field, len its bases
+        unsigned long long line;                     // --sam: line of the input; --bam: ordinal of the record
     };
     struct Part { std::vector<Rec> recs; int err = 0; unsigned long long err_rec = 0; int err_nf = 0; unsigned long long lines = 0, skipped = 0; };
     unsigned long long n_lines_before = 0, n_skipped = 0;
@@ -690,14 +729,47 @@ int main(int argc, char **argv) {
     // whole file has been indexed; the records of a slab's last (possibly unfinished) target
     // are carried into the next slab
     const size_t slab_bytes = o.slab_bytes ? o.slab_bytes : std::max<size_t>(o.batch_bytes, 256u << 20);
-    size_t slab_pos = 0, unmapped = 0;
+    size_t slab_pos = bam_first, unmapped = 0;
+    const char *unit = o.bam ? "record" : "line";          // what an error names
     unsigned long long n_rec_before = 0;
     bool had_error = false;
     int status = 0;
     std::vector<Rec> carry;
     std::vector<Part> parts(nthr);
     std::vector<const Rec *> recs;
+    // --bam: the records up to s1 (the reader stops behind the first one that ends there or later); one thread, there is
+    // no per-base work in it
+    auto index_bam = [&](size_t s1) {
+        Part &pt = parts[0];
+        pt.recs.clear();
+        recs.clear();
+        for (const Rec &r : carry) recs.push_back(&r);
+        DgBamRec br;
+        std::string err;
+        while (bam.at < s1) {
+            const int rc = bam.next(br, err);
+            if (rc == 0) break;
+            if (rc < 0) { fprintf(stderr, "pbdagcon: format error: %s\n", err.c_str()); had_error = true; break; }
+            const std::string &rn = bam.refs[(size_t)br.ref_id].name;
+            const DgRefSeqs::Span *sp = ref.find(rn.data(), rn.size());
+            if (!sp) { fprintf(stderr, "pbdagcon: record %llu: RNAME is not a sequence of %s\n", br.ordinal, o.ref.c_str()); had_error = true; break; }
+            Rec r;
+            r.id = rn.data(); r.idl = (uint32_t)rn.size();
+            r.name = br.name; r.namel = br.name_len;
+            r.q = (const char *)br.seq; r.len = br.l_seq;
+            r.t = ref.bases.data() + sp->off; r.tlen = sp->len; r.tl = 0;
+            r.start = br.pos;
+            r.strand = (br.flag & DG_SAM_REVERSE) ? '-' : '+';
+            r.cg = (const char *)br.ops; r.cgl = br.n_ops * 4u; r.nops = br.n_ops;
+            r.line = br.ordinal;
+            pt.recs.push_back(r);
+        }
+        n_skipped = bam.n_skipped;
+        for (const Rec &r : pt.recs) recs.push_back(&r);
+        n_rec_before += pt.recs.size();
+    };
     auto index_slab = [&](size_t s0, size_t s1) {
+        if (o.bam) { index_bam(s1); return; }
         std::vector<size_t> cut(nthr + 1, s1);
         cut[0] = s0;
         for (unsigned k = 1; k < nthr; k++) {
@@ -837,7 +909,10 @@ int main(int argc, char **argv) {
             for (size_t x = r0 + k; x < r1; x += nthr) {
                 const Rec &r = *recs[x];
                 char *dq = b.q.data() + b.off[x - r0], *dt = b.t.data() + b.off2[x - r0];
-                if (o.sam) {                                      // SEQ as it is; the CIGAR as BAM-encoded ops
+                if (o.bam) {                                      // the seq field and the ops as they lie in the record
+                    memcpy(dq, r.q, ((size_t)r.len + 1) / 2);
+                    memcpy(b.ops.data() + b.opb[x - r0], r.cg, r.cgl);
+                } else if (o.sam) {                               // SEQ as it is; the CIGAR as BAM-encoded ops
                     memcpy(dq, r.q, r.len);
                     dg_cigar_ops(r.cg, r.cgl, b.ops.data() + b.opb[x - r0]);
                 } else if (o.align) {                                    // .pre: sequences as they are (Alignment.cpp:112)
@@ -863,12 +938,12 @@ int main(int argc, char **argv) {
 #define b (*bp)
     while (status == 0 && !had_error && (slab_pos < size || !carry.empty())) {
         size_t s1 = std::min(size, slab_pos + slab_bytes);
-        if (s1 < size) {                                   // a slab ends at a line end
+        if (s1 < size && !o.bam) {                         // a slab ends at a line end
             const char *nl = (const char *)memchr(data + s1, '\n', size - s1);
             s1 = nl ? (size_t)(nl - data) + 1 : size;
         }
         { const double t0 = now(); index_slab(slab_pos, s1); t_index += now() - t0; }
-        slab_pos = s1;
+        slab_pos = o.bam ? (bam.at >= size ? size : std::max(bam.at, slab_pos)) : s1;   // (--bam: behind the last record taken)
         const bool eof = slab_pos >= size || had_error;
         // all but the last target of the slab (it may go on in the next one)
         size_t n_use = recs.size();
@@ -894,6 +969,14 @@ int main(int argc, char **argv) {
                             const size_t o0 = b.off[y - rb];
                             size_t g = 0;
                             while (b.begin[g + 1] <= y - rb) g++;
+                            if (o.bam) {                       // what --sam prints for the SAM text of the record (SEQ decoded for printing only)
+                                std::string seq(r.len, 0);
+                                for (uint32_t i = 0; i < r.len; i++) seq[i] = dg_bam_base((const uint8_t *)b.q.data() + o0, i);
+                                printf("%.*s\t%u\t%u\t%c\t%.*s\t%s\t%s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
+                                       (int)r.namel, r.name, seq.c_str(),
+                                       dg_cigar_text(b.ops.data() + b.opb[y - rb], b.opb[y - rb + 1] - b.opb[y - rb]).c_str());
+                                continue;
+                            }
                             if (o.sam) {                       // RNAME, its length in --ref, POS, strand, QNAME, SEQ, CIGAR (from the ops)
                                 printf("%.*s\t%u\t%u\t%c\t%.*s\t%.*s\t%s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
                                        (int)r.namel, r.name, (int)r.len, b.q.data() + o0,
@@ -912,8 +995,8 @@ int main(int argc, char **argv) {
             const Rec &r = *recs[x];
             if (new_target) {
                 if (o.sam && !seen_targets.emplace(r.id, r.idl).second) {
-                    fprintf(stderr, "pbdagcon: line %llu: records of %.*s come back after another target's; the records of one RNAME "
-                            "must be consecutive (sort the SAM by coordinate)\n", r.line, (int)r.idl, r.id);
+                    fprintf(stderr, "pbdagcon: %s %llu: records of %.*s come back after another target's; the records of one RNAME "
+                            "must be consecutive (sort the %s by coordinate)\n", unit, r.line, (int)r.idl, r.id, o.bam ? "BAM" : "SAM");
                     had_error = true;
                     break;
                 }
@@ -927,7 +1010,7 @@ int main(int argc, char **argv) {
             b.off.push_back(bytes); b.off2.push_back(bytes2);
             b.len.push_back(r.len); b.len2.push_back(r.tl);
             b.strand.push_back(r.strand);
-            bytes += r.len; bytes2 += r.tl;
+            bytes += o.bam ? ((size_t)r.len + 1) / 2 : r.len; bytes2 += r.tl;
         }
         // the unfinished target's records wait for the next slab
         std::vector<Rec> next_carry;
@@ -957,7 +1040,9 @@ int main(int argc, char **argv) {
         if (eof) slab_pos = size;
     }
     if (had_error) status = 1;
-    if (o.sam && o.verbose)
+    if (o.bam && o.verbose)
+        fprintf(stderr, "pbdagcon: %llu BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)\n", n_skipped);
+    else if (o.sam && o.verbose)
         fprintf(stderr, "pbdagcon: %llu SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')\n", n_skipped);
     t_parse_end = now();
 #undef b

@@ -1,10 +1,12 @@
-// windows.h -- `pbdagcon --sam --ref F --window W [--overlap O]`: targets of any length and depth.
+// windows.h -- `pbdagcon --sam|--bam --ref F --window W [--overlap O]`: targets of any length and depth.
 //
 // Window i of a target has the core [iW, min((i + 1)W, tlen)) and is run as [max(0, iW - O), min(tlen, (i + 1)W + O));
 // a target of at most W bases is one window.  Windows go to the device in groups of about --batch-targets
 // (dagcon_consensus_cigar_windows on a DAGCON_FLAG_BASE_POS context, with DAGCON_FLAG_BASE_SUPPORT for --fastq); a group
 // gets only the records whose [s, e) meets it, which the host knows from the ops it has parsed.  Records of one RNAME
-// must be consecutive and ascending in POS, as in a coordinate-sorted SAM.
+// must be consecutive and ascending in POS, as in a coordinate-sorted SAM.  The records come from a source (DgSamSource:
+// SAM text; DgBamSource: bam.h's reader, whose reads stay in BAM's 4-bit encoding all the way to the device); grouping,
+// batching and the stitch do not know which.
 //
 // The stitch (DgStitch; tests/window_twin.py: stitch is its numpy twin).  With g = pos + window begin the 1-based
 // target position of a consensus base (dagcon_fetch_positions): of a window's segment the bases from the first one
@@ -24,6 +26,7 @@
 #include <vector>
 
 #include "../../../include/dagcon.h"
+#include "bam.h"
 #include "fastq.h"
 #include "sam.h"
 
@@ -71,54 +74,114 @@ struct DgWinOpts {
     int device;
 };
 
+// One alignment record as the window driver takes it: the target by name, POS, the read bases (one a byte, or two a
+// byte when the source is packed) and the CIGAR as BAM-encoded ops, appended to `ops` by the source.
+struct DgAlnRec {
+    const char *rname; size_t rname_len;
+    uint32_t pos;
+    const char *q; uint32_t q_len;                         // q_len counts bases
+    uint32_t nops;                                         // the record's ops are the last nops of `ops`
+    unsigned long long where;                              // the line (SAM) or the record's ordinal (BAM): what an error names
+};
+
+// SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
+struct DgSamSource {
+    static constexpr bool packed = false;
+    static constexpr const char *unit = "line";
+    static constexpr const char *skipped_what = "SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')";
+    const char *data; size_t size, p = 0;
+    unsigned long long lineno = 0, skipped = 0;
+    DgSamSource(const char *d, size_t n, const DgRefSeqs &) : data(d), size(n) {}
+    // 1: a record; 0: the end; -1: an error (printed)
+    int next(DgAlnRec &r, std::vector<uint32_t> &ops) {
+        while (p < size) {
+            const char *line = data + p;
+            const char *nl = (const char *)memchr(line, '\n', size - p);
+            size_t ll = nl ? (size_t)(nl - line) : size - p;
+            p += ll + (nl ? 1 : 0);
+            lineno++;
+            if (ll && line[ll - 1] == '\r') ll--;
+            if (ll == 0 || line[0] == '@') continue;
+            const char *f[11]; size_t fl[11]; int nf = 0;
+            for (size_t i = 0; nf < 11;) {
+                const char *tab = (const char *)memchr(line + i, '\t', ll - i);
+                const size_t j = tab ? (size_t)(tab - line) : ll;
+                f[nf] = line + i; fl[nf] = j - i; nf++;
+                if (!tab) break;
+                i = j + 1;
+            }
+            if (nf < 10) { fprintf(stderr, "pbdagcon: line %llu: a SAM record has 11 fields, this one has fewer than 10 fields\n", lineno); return -1; }
+            auto star = [&](int k) { return fl[k] == 1 && f[k][0] == '*'; };
+            uint64_t flag = 0, pos = 0;
+            for (size_t i = 0; i < fl[1] && f[1][i] >= '0' && f[1][i] <= '9'; i++) flag = flag * 10 + (uint64_t)(f[1][i] - '0');
+            for (size_t i = 0; i < fl[3] && f[3][i] >= '0' && f[3][i] <= '9' && pos < (1ull << 40); i++) pos = pos * 10 + (uint64_t)(f[3][i] - '0');
+            if ((flag & (DG_SAM_UNMAPPED | DG_SAM_SECONDARY)) || star(2) || star(5) || star(9)) { skipped++; continue; }
+            const long k = dg_cigar_ops(f[5], fl[5], nullptr);
+            if (k < 0) { fprintf(stderr, "pbdagcon: line %llu: malformed CIGAR %.*s\n", lineno, (int)std::min<size_t>(fl[5], 60), f[5]); return -1; }
+            r.rname = f[2]; r.rname_len = fl[2];
+            r.pos = pos > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pos;
+            r.q = f[9]; r.q_len = (uint32_t)fl[9]; r.nops = (uint32_t)k;
+            r.where = lineno;
+            ops.resize(ops.size() + (size_t)k);
+            dg_cigar_ops(f[5], fl[5], ops.data() + ops.size() - (size_t)k);
+            return 1;
+        }
+        return 0;
+    }
+};
+
+// BAM records (bam.h); the header's references were checked against --ref when the file was opened
+struct DgBamSource {
+    static constexpr bool packed = true;
+    static constexpr const char *unit = "record";
+    static constexpr const char *skipped_what = "BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)";
+    DgBamReader &bam;
+    unsigned long long skipped = 0;
+    DgBamSource(DgBamReader &b, const DgRefSeqs &) : bam(b) {}
+    int next(DgAlnRec &r, std::vector<uint32_t> &ops) {
+        DgBamRec br;
+        std::string err;
+        const int rc = bam.next(br, err);
+        skipped = bam.n_skipped;
+        if (rc < 0) fprintf(stderr, "pbdagcon: format error: %s\n", err.c_str());
+        if (rc <= 0) return rc;
+        const std::string &rn = bam.refs[(size_t)br.ref_id].name;
+        r.rname = rn.data(); r.rname_len = rn.size();
+        r.pos = br.pos;
+        r.q = (const char *)br.seq; r.q_len = br.l_seq; r.nops = br.n_ops;
+        r.where = br.ordinal;
+        ops.resize(ops.size() + br.n_ops);
+        memcpy(ops.data() + ops.size() - br.n_ops, br.ops, (size_t)br.n_ops * 4);
+        return 1;
+    }
+};
+
 // the whole run; the process's exit status
-inline int dg_run_sam_windows(const DgWinOpts &o, const char *data, size_t size, const DgRefSeqs &ref) {
+template <class Source>
+inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref) {
     struct Rec { uint32_t pos, s, e, q_len; const char *q; uint64_t op0; uint32_t nops; };
     struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; };
     std::vector<Tgt> tgts;
     std::vector<uint32_t> ops;
     std::unordered_map<std::string, int> seen;
-    unsigned long long lineno = 0, skipped = 0;
-    // ---- parse: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL ----
-    for (size_t p = 0; p < size;) {
-        const char *line = data + p;
-        const char *nl = (const char *)memchr(line, '\n', size - p);
-        size_t ll = nl ? (size_t)(nl - line) : size - p;
-        p += ll + (nl ? 1 : 0);
-        lineno++;
-        if (ll && line[ll - 1] == '\r') ll--;
-        if (ll == 0 || line[0] == '@') continue;
-        const char *f[11]; size_t fl[11]; int nf = 0;
-        for (size_t i = 0; nf < 11;) {
-            const char *tab = (const char *)memchr(line + i, '\t', ll - i);
-            const size_t j = tab ? (size_t)(tab - line) : ll;
-            f[nf] = line + i; fl[nf] = j - i; nf++;
-            if (!tab) break;
-            i = j + 1;
-        }
-        if (nf < 10) { fprintf(stderr, "pbdagcon: line %llu: a SAM record has 11 fields, this one has fewer than 10 fields\n", lineno); return 1; }
-        auto star = [&](int k) { return fl[k] == 1 && f[k][0] == '*'; };
-        uint64_t flag = 0, pos = 0;
-        for (size_t i = 0; i < fl[1] && f[1][i] >= '0' && f[1][i] <= '9'; i++) flag = flag * 10 + (uint64_t)(f[1][i] - '0');
-        for (size_t i = 0; i < fl[3] && f[3][i] >= '0' && f[3][i] <= '9' && pos < (1ull << 40); i++) pos = pos * 10 + (uint64_t)(f[3][i] - '0');
-        if ((flag & (DG_SAM_UNMAPPED | DG_SAM_SECONDARY)) || star(2) || star(5) || star(9)) { skipped++; continue; }
-        const std::string rname(f[2], fl[2]);
+    // ---- the records, grouped by target ----
+    DgAlnRec ar{};
+    for (int have; (have = src.next(ar, ops)) != 0;) {
+        if (have < 0) return 1;
+        const std::string rname(ar.rname, ar.rname_len);
         if (tgts.empty() || tgts.back().name != rname) {
-            const DgRefSeqs::Span *sp = ref.find(f[2], fl[2]);
-            if (!sp) { fprintf(stderr, "pbdagcon: line %llu: RNAME %s is not a sequence of --ref\n", lineno, rname.c_str()); return 1; }
-            if (!seen.emplace(rname, 1).second) { fprintf(stderr, "pbdagcon: line %llu: records of RNAME %s come back after another target's (records of one RNAME must be consecutive)\n", lineno, rname.c_str()); return 1; }
+            const DgRefSeqs::Span *sp = ref.find(ar.rname, ar.rname_len);
+            if (!sp) { fprintf(stderr, "pbdagcon: %s %llu: RNAME %s is not a sequence of --ref\n", Source::unit, ar.where, rname.c_str()); return 1; }
+            if (!seen.emplace(rname, 1).second) { fprintf(stderr, "pbdagcon: %s %llu: records of RNAME %s come back after another target's (records of one RNAME must be consecutive)\n", Source::unit, ar.where, rname.c_str()); return 1; }
             tgts.emplace_back();
             tgts.back().name = rname; tgts.back().sp = *sp;
         }
         Tgt &t = tgts.back();
-        const long k = dg_cigar_ops(f[5], fl[5], nullptr);
-        if (k < 0) { fprintf(stderr, "pbdagcon: line %llu: malformed CIGAR %.*s\n", lineno, (int)std::min<size_t>(fl[5], 60), f[5]); return 1; }
         Rec r;
-        r.pos = pos > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pos;
-        if (!t.recs.empty() && r.pos < t.recs.back().pos) { fprintf(stderr, "pbdagcon: line %llu: POS %u of RNAME %s is below that of the record before it (--window needs records ascending in POS, as in a coordinate-sorted SAM)\n", lineno, r.pos, rname.c_str()); return 1; }
-        r.q = f[9]; r.q_len = (uint32_t)fl[9]; r.op0 = ops.size(); r.nops = (uint32_t)k;
-        ops.resize(ops.size() + (size_t)k);
-        dg_cigar_ops(f[5], fl[5], ops.data() + r.op0);
+        r.pos = ar.pos;
+        if (!t.recs.empty() && r.pos < t.recs.back().pos) { fprintf(stderr, "pbdagcon: %s %llu: POS %u of RNAME %s is below that of the record before it (--window needs records ascending in POS, as in a coordinate-sorted SAM)\n", Source::unit, ar.where, r.pos, rname.c_str()); return 1; }
+        r.q = ar.q; r.q_len = ar.q_len; r.op0 = ops.size() - ar.nops; r.nops = ar.nops;
+        const long k = (long)ar.nops;
         // [s, e) by the rule of include/dagcon.h (a non-conforming record: clipped into the target, at least one base)
         uint64_t nt = 0;
         for (long i = 0; i < k; i++) { const uint32_t op = ops[r.op0 + i]; if ((1u << (op & 15u)) & 0x185u) nt += op >> 4; }
@@ -131,7 +194,7 @@ inline int dg_run_sam_windows(const DgWinOpts &o, const char *data, size_t size,
         t.max_span = std::max(t.max_span, r.e > r.s ? r.e - r.s : 0u);
         t.recs.push_back(r);
     }
-    if (o.verbose && skipped) fprintf(stderr, "pbdagcon: %llu SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')\n", skipped);
+    if (o.verbose && src.skipped) fprintf(stderr, "pbdagcon: %llu %s\n", src.skipped, Source::skipped_what);
     // ---- the windows of every target, in target order ----
     struct Win { uint32_t tgt, idx, begin, end, c0, c1; };
     std::vector<Win> wins;
@@ -197,7 +260,7 @@ inline int dg_run_sam_windows(const DgWinOpts &o, const char *data, size_t size,
             for (; it != t.recs.end() && it->s < hi; ++it) {
                 if (it->e <= lo) continue;
                 b_pos.push_back(it->pos); b_qoff.push_back(qblob.size()); b_qlen.push_back(it->q_len);
-                qblob.append(it->q, it->q_len);
+                qblob.append(it->q, Source::packed ? ((size_t)it->q_len + 1) / 2 : it->q_len);
                 b_ops.insert(b_ops.end(), ops.begin() + (long)it->op0, ops.begin() + (long)(it->op0 + it->nops));
                 b_opb.push_back(b_ops.size());
             }
@@ -214,7 +277,7 @@ inline int dg_run_sam_windows(const DgWinOpts &o, const char *data, size_t size,
         dagcon_windows dw;
         dw.n_windows = (uint32_t)w_t.size(); dw.target = w_t.data(); dw.begin = w_b.data(); dw.end = w_e.data();
         dagcon_results r;
-        rc = dagcon_consensus_cigar_windows(ctx, &cb, &dw, &r);
+        rc = Source::packed ? dagcon_consensus_cigar_packed(ctx, &cb, &dw, &r) : dagcon_consensus_cigar_windows(ctx, &cb, &dw, &r);
         const uint32_t *pos = nullptr;
         uint64_t npos = 0;
         dagcon_support sup;

@@ -19,6 +19,16 @@
 // read bases and stay inside the target, after it has checked q_off + q_len and t_off + tlen against the blobs; the
 // expansion recomputes the same sums from the same device copy of the ops, so every index it forms lies inside
 // [0, q_len), [pos - 1, tlen) and [0, columns).
+//
+// Packed read bases (dagcon_upload_cigar_packed; k_cigar_expand_packed, k_cigar_expand_cut_packed): q holds BAM's seq
+// field as it lies, two bases a byte.  Read base i of a record is nibble i of q + q_off[r]: byte i >> 1, the high
+// nibble for even i, decoded by BAM's table =ACMGRSVTWYHKDBN (dg_cg_nt16: the 16 letters are two 64-bit immediates and
+// a shift, no table in memory).  A record starts on a byte; the first base an op uses falls on either nibble (a soft
+// clip of odd length), so every lane takes its own byte and its own nibble.  The packed kernels are the unpacked ones
+// but for that one load (one body, PACKED a template parameter); scan and cut read no bases and serve both.
+// Out-of-bounds safety, packed: the host admits a record only after q_off + (q_len + 1) / 2 <= q_bytes (in 64 bits)
+// and, as above, after the scan's totals say that its ops consume exactly q_len read bases; a base index i formed here
+// is then below q_len, and the byte index i >> 1 below (q_len + 1) / 2.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -108,8 +118,21 @@ __global__ __launch_bounds__(256) void k_cigar_scan(DgCigarParams p) {
     if (lane == 0) p.totals[r] = make_uint4((uint32_t)c_col, (uint32_t)c_q, (uint32_t)c_t, flags);
 }
 
+// BAM's 4-bit base codes: "=ACMGRSV" and "TWYHKDBN", first letter in the lowest byte
+__device__ __forceinline__ uint8_t dg_cg_nt16(uint32_t code) {
+    const uint64_t w = (code & 8u) ? 0x4E42444B48595754ull : 0x565352474D43413Dull;
+    return (uint8_t)(w >> ((code & 7u) * 8u));
+}
+// read base i of a record whose bases begin at q
+template <bool PACKED>
+__device__ __forceinline__ uint8_t dg_cg_qbase(const uint8_t *q, uint32_t i) {
+    if constexpr (PACKED) return dg_cg_nt16(((uint32_t)q[i >> 1] >> ((~i & 1u) * 4u)) & 15u);
+    else return q[i];
+}
+
 // a wave per tile of 64 ops
-__global__ __launch_bounds__(64) void k_cigar_expand(DgCigarParams p) {
+template <bool PACKED>
+__device__ __forceinline__ void dg_cg_expand(const DgCigarParams &p) {
     __shared__ uint32_t s_end[64], s_q0[64], s_t0[64], s_code[64];
     const uint32_t lane = threadIdx.x;
     const uint32_t tile = blockIdx.x;
@@ -146,10 +169,12 @@ __global__ __launch_bounds__(64) void k_cigar_expand(DgCigarParams p) {
         const uint32_t first = lo ? s_end[lo - 1u] : 0u;          // (an op without columns ends where it begins: never found)
         const uint32_t k = c - first;
         const uint32_t b = 1u << s_code[lo];
-        oq[c] = (b & DG_CG_Q_MASK) ? q[s_q0[lo] + k] : (uint8_t)'-';
+        oq[c] = (b & DG_CG_Q_MASK) ? dg_cg_qbase<PACKED>(q, s_q0[lo] + k) : (uint8_t)'-';
         ot[c] = (b & DG_CG_T_MASK) ? t[s_t0[lo] + k] : (uint8_t)'-';
     }
 }
+__global__ __launch_bounds__(64) void k_cigar_expand(DgCigarParams p) { dg_cg_expand<false>(p); }
+__global__ __launch_bounds__(64) void k_cigar_expand_packed(DgCigarParams p) { dg_cg_expand<true>(p); }
 
 // ---- records cut to windows (dagcon_upload_cigar_windows; include/dagcon.h has the rule) ----------------------------
 // A piece is one (record, window) pair: the record's columns [F(A), F(B)), F(x) the first column that consumes target
@@ -233,7 +258,8 @@ __global__ __launch_bounds__(256) void k_cigar_cut(DgCigarParams p, DgCigarCutPa
 }
 
 // a wave per (piece, tile of 64 ops)
-__global__ __launch_bounds__(64) void k_cigar_expand_cut(DgCigarParams p, DgCigarCutParams w) {
+template <bool PACKED>
+__device__ __forceinline__ void dg_cg_expand_cut(const DgCigarParams &p, const DgCigarCutParams &w) {
     __shared__ uint32_t s_end[64], s_q0[64], s_t0[64], s_code[64];
     const uint32_t lane = threadIdx.x;
     if (blockIdx.x >= w.n_waves) return;
@@ -274,7 +300,9 @@ __global__ __launch_bounds__(64) void k_cigar_expand_cut(DgCigarParams p, DgCiga
         const uint32_t kk = c - first;
         const uint32_t b = 1u << s_code[lo];
         const uint32_t at = ck.x + c - cut.x;                     // (ck.x + c >= F(A): c >= c_lo)
-        oq[at] = (b & DG_CG_Q_MASK) ? q[s_q0[lo] + kk] : (uint8_t)'-';
+        oq[at] = (b & DG_CG_Q_MASK) ? dg_cg_qbase<PACKED>(q, s_q0[lo] + kk) : (uint8_t)'-';
         ot[at] = (b & DG_CG_T_MASK) ? t[s_t0[lo] + kk] : (uint8_t)'-';
     }
 }
+__global__ __launch_bounds__(64) void k_cigar_expand_cut(DgCigarParams p, DgCigarCutParams w) { dg_cg_expand_cut<false>(p, w); }
+__global__ __launch_bounds__(64) void k_cigar_expand_cut_packed(DgCigarParams p, DgCigarCutParams w) { dg_cg_expand_cut<true>(p, w); }

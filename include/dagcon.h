@@ -348,7 +348,8 @@ typedef struct dagcon_cigar_batch {
     uint64_t t_bytes;
     const uint64_t *rec_begin;   /* [n_targets + 1] records of target g, in addAln order */
     const uint32_t *pos;         /* [n_rec] 1-based leftmost target base (SAM POS) = Alignment::start */
-    const uint64_t *q_off;       /* [n_rec] read bases as SAM SEQ has them (target orientation) */
+    const uint64_t *q_off;       /* [n_rec] read bases as SAM SEQ has them (target orientation); the ranges of several */
+                                 /*         records may overlap or coincide (one read, many alignments)               */
     const uint32_t *q_len;
     const char *q_blob;
     uint64_t q_bytes;
@@ -406,6 +407,26 @@ int dagcon_consensus_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *ba
 int dagcon_upload_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows);
 int dagcon_consensus_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows,
                                   dagcon_results *results);
+
+/*
+ * dagcon_cigar_batch with the read bases as a reads file has them and one strand flag per record (PAF: a line names a
+ * slice [qs, qe) of a read that lies once in another file, and for a '-' line the CIGAR is written against the
+ * reverse complement of that slice).  q_blob[q_off[r] .. + q_len[r]) is the slice as the file has it, one byte a base
+ * (there is no packed form: a reads file is text).  For a record with reverse[r] != 0, read base i of the expansion
+ * rule above is comp(q_blob[q_off[r] + q_len[r] - 1 - i]), formed on the device; comp swaps A<->T, C<->G, a<->t, c<->g
+ * and leaves every other byte as it is.  (Alignment.cpp:15-26 complements upper case only; reads files carry
+ * soft-masked lower case, and the reference reads no PAF: this rule is this build's own, parity unpinned.)
+ * Several records may name overlapping or equal ranges of q_blob, on either strand.
+ * windows may be NULL (then: dagcon_upload_cigar / dagcon_consensus_cigar, else the _windows calls).  reverse == NULL
+ * is the unstranded call.  The result is, byte for byte, that of the unstranded call on the same batch with every
+ * reverse record's bases replaced by their reverse complement: segments, target_status, dagcon_fetch_support,
+ * dagcon_fetch_positions, the counts in the timings.  Conformance, confinement of a failure, flags, limits and the
+ * DAGCON_ERR_INVALID_ARG checks are those of the unstranded calls.
+ */
+int dagcon_upload_cigar_strand(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows /* or NULL */,
+                               const uint8_t *reverse /* [n_rec], or NULL */);
+int dagcon_consensus_cigar_strand(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows,
+                                  const uint8_t *reverse, dagcon_results *results);
 
 /*
  * Debug / parity aid: adjacency of one target's graph as left by the last

@@ -38,6 +38,7 @@ EXPORTS = [
     "dagcon_align_ends", "dagcon_place", "dagcon_fetch_support", "dagcon_upload_cigar", "dagcon_consensus_cigar",
     "dagcon_fetch_positions", "dagcon_upload_cigar_windows", "dagcon_consensus_cigar_windows",
     "dagcon_upload_cigar_packed", "dagcon_consensus_cigar_packed",
+    "dagcon_upload_cigar_strand", "dagcon_consensus_cigar_strand",
 ]
 ABI_VERSION = 2
 
@@ -155,6 +156,8 @@ def load() -> C.CDLL:
     L.dagcon_consensus_cigar_windows.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(Results)]
     L.dagcon_upload_cigar_packed.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows)]
     L.dagcon_consensus_cigar_packed.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(Results)]
+    L.dagcon_upload_cigar_strand.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), vp]
+    L.dagcon_consensus_cigar_strand.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), vp, C.POINTER(Results)]
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
     L.dagcon_host_free.restype = None
@@ -242,9 +245,11 @@ BAM_NT16 = b"=ACMGRSVTWYHKDBN"     # BAM's 4-bit base codes 0..15
 
 class HostCigarBatch:
     """numpy view of a dagcon_cigar_batch: per record a position, an ungapped read and BAM-encoded CIGAR ops
-    (len << 4 | op), per target its bases once."""
+    (len << 4 | op), per target its bases once.  reverse (optional, one byte per record): the stranded calls
+    (dagcon_upload_cigar_strand) -- q_blob holds the reads as the reads file has them and the device reads the bases of
+    a record with reverse != 0 backwards and complemented."""
 
-    def __init__(self, tlen, t_off, t_blob, rec_begin, pos, q_off, q_len, q_blob, op_begin, ops, ids=None):
+    def __init__(self, tlen, t_off, t_blob, rec_begin, pos, q_off, q_len, q_blob, op_begin, ops, ids=None, reverse=None):
         def u8(x):
             return np.ascontiguousarray(np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else x,
                                         dtype=np.uint8)
@@ -259,6 +264,9 @@ class HostCigarBatch:
         self.op_begin = np.ascontiguousarray(op_begin, dtype=np.uint64)
         self.ops = np.ascontiguousarray(ops, dtype=np.uint32)
         self.ids = ids
+        self.reverse = None if reverse is None else np.ascontiguousarray(np.asarray(reverse) != 0, dtype=np.uint8)
+        if self.reverse is not None and self.reverse.shape != self.pos.shape:
+            raise ValueError("reverse needs one entry per record")
 
     is_packed = False
 
@@ -268,6 +276,8 @@ class HostCigarBatch:
         ValueError."""
         if self.is_packed:
             return self
+        if self.reverse is not None:
+            raise ValueError("a batch with reverse has no packed form (dagcon_upload_cigar_strand takes one byte a base)")
         code = np.full(256, 255, dtype=np.uint8)
         code[np.frombuffer(BAM_NT16, dtype=np.uint8)] = np.arange(16, dtype=np.uint8)
         n = self.q_len.astype(np.int64)
@@ -527,6 +537,9 @@ class Context:
         """dagcon_upload_cigar: then run / sync / fetch as after upload."""
         self._keep = batch
         b = batch.c_struct()
+        if batch.reverse is not None:
+            self._chk(self.L.dagcon_upload_cigar_strand(self.h, C.byref(b), None, batch.reverse.ctypes.data))
+            return
         if batch.is_packed:
             self._chk(self.L.dagcon_upload_cigar_packed(self.h, C.byref(b), None))
             return
@@ -537,7 +550,9 @@ class Context:
         self._keep = batch
         b = batch.c_struct()
         r = Results()
-        if batch.is_packed:
+        if batch.reverse is not None:
+            self._chk(self.L.dagcon_consensus_cigar_strand(self.h, C.byref(b), None, batch.reverse.ctypes.data, C.byref(r)))
+        elif batch.is_packed:
             self._chk(self.L.dagcon_consensus_cigar_packed(self.h, C.byref(b), None, C.byref(r)))
         else:
             self._chk(self.L.dagcon_consensus_cigar(self.h, C.byref(b), C.byref(r)))
@@ -549,6 +564,9 @@ class Context:
         """dagcon_upload_cigar_windows: then run / sync / fetch as after upload (one result target per window)."""
         self._keep = (batch, windows)
         b, w = batch.c_struct(), windows.c_struct()
+        if batch.reverse is not None:
+            self._chk(self.L.dagcon_upload_cigar_strand(self.h, C.byref(b), C.byref(w), batch.reverse.ctypes.data))
+            return
         if batch.is_packed:
             self._chk(self.L.dagcon_upload_cigar_packed(self.h, C.byref(b), C.byref(w)))
             return
@@ -559,7 +577,9 @@ class Context:
         self._keep = (batch, windows)
         b, w = batch.c_struct(), windows.c_struct()
         r = Results()
-        if batch.is_packed:
+        if batch.reverse is not None:
+            self._chk(self.L.dagcon_consensus_cigar_strand(self.h, C.byref(b), C.byref(w), batch.reverse.ctypes.data, C.byref(r)))
+        elif batch.is_packed:
             self._chk(self.L.dagcon_consensus_cigar_packed(self.h, C.byref(b), C.byref(w), C.byref(r)))
         else:
             self._chk(self.L.dagcon_consensus_cigar_windows(self.h, C.byref(b), C.byref(w), C.byref(r)))

@@ -131,7 +131,7 @@ struct Ctx {
     DevBuf d_al[15];                                // dagcon_align: blobs, offsets, outputs, directions, launch order, widths, ends
     DevBuf d_pn[18];                                // dagcon_align_panels: blobs, panels, scratch, outputs, launch order
     DevBuf d_pl[14];                                // dagcon_place: blob, sequences, tables, pairs, outputs
-    DevBuf d_cg[16];                                // dagcon_upload_cigar: ops, op / tile begins, totals, checkpoints, blobs, offsets
+    DevBuf d_cg[18];                                // dagcon_upload_cigar: ops, op / tile begins, totals, checkpoints, blobs, offsets
     std::vector<uint8_t> h_cig_bad;                 // dagcon_upload_cigar: targets with a non-conforming record (empty: another upload)
     std::string cig_err;                            // the first of them, for dagcon_last_error
     DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
@@ -1710,6 +1710,18 @@ const char *cigar_why(const dagcon_cigar_batch *b, const std::vector<uint32_t> &
          : nq != b->q_len[a] ? "the ops do not consume exactly q_len read bases"
          : (uint64_t)b->pos[a] - 1u + nt > b->tlen[g] ? "target bases past tlen" : nullptr;
 }
+
+// the strand kernels' own arguments (dagcon_upload_cigar_strand): one flag and q_len per record
+int cigar_strand(Ctx *c, const dagcon_cigar_batch *b, uint32_t n, const uint8_t *reverse, DgCigarStrand &st) {
+    DevBuf &d_rev = c->d_cg[15], &d_qlen = c->d_cg[16];
+    ENSURE(c, d_rev, (size_t)n); ENSURE(c, d_qlen, (size_t)n * 4);
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(d_rev.p, reverse, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_qlen.p, b->q_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    st.rev = (const uint8_t *)d_rev.p; st.q_len = (const uint32_t *)d_qlen.p;
+    return DAGCON_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -1718,7 +1730,7 @@ extern "C" {
 // upload_impl takes them from there (the door dagcon_consensus_pre uses)
 }  // extern "C"
 namespace {
-int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed) {
+int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed, const uint8_t *reverse = nullptr) {
     if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
@@ -1769,7 +1781,11 @@ int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed) {
     if (n_tiles && bytes) {
         p.t_base = (const uint64_t *)d_tbase.p; p.out_off = (const uint64_t *)d_out.p;
         p.out_q = (uint8_t *)c->d_q.p; p.out_t = (uint8_t *)c->d_t.p;
-        if (packed) hipLaunchKernelGGL(k_cigar_expand_packed, dim3((uint32_t)n_tiles), dim3(64), 0, s, p);
+        if (reverse) {
+            DgCigarStrand st;
+            if ((r = cigar_strand(c, b, n, reverse, st))) return r;
+            hipLaunchKernelGGL(k_cigar_expand_strand, dim3((uint32_t)n_tiles), dim3(64), 0, s, p, st);
+        } else if (packed) hipLaunchKernelGGL(k_cigar_expand_packed, dim3((uint32_t)n_tiles), dim3(64), 0, s, p);
         else hipLaunchKernelGGL(k_cigar_expand, dim3((uint32_t)n_tiles), dim3(64), 0, s, p);
         HIPCHK(c, hipGetLastError());
     }
@@ -1789,7 +1805,7 @@ int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed) {
 // cut).  After the scan's totals the host knows every record's [s, e) and lists the (record, window) pieces; k_cigar_cut
 // turns each piece's two target coordinates into columns and tiles, the host plans the output from those, and
 // k_cigar_expand_cut writes every piece from the one device copy of the record's ops and bases.
-int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, bool packed) {
+int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, bool packed, const uint8_t *reverse = nullptr) {
     if (!ctx || !b || !wn) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
@@ -1901,7 +1917,11 @@ int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dag
         p.out_q = (uint8_t *)c->d_q.p; p.out_t = (uint8_t *)c->d_t.p;
         cw.wave_piece = (const uint32_t *)d_wpiece.p; cw.wave_begin = (const uint32_t *)d_wbegin.p;
         cw.piece_out = (const uint64_t *)d_pout.p; cw.n_waves = (uint32_t)wpiece.size();
-        if (packed) hipLaunchKernelGGL(k_cigar_expand_cut_packed, dim3(cw.n_waves), dim3(64), 0, s, p, cw);
+        if (reverse) {
+            DgCigarStrand st;
+            if ((r = cigar_strand(c, b, n, reverse, st))) return r;
+            hipLaunchKernelGGL(k_cigar_expand_cut_strand, dim3(cw.n_waves), dim3(64), 0, s, p, cw, st);
+        } else if (packed) hipLaunchKernelGGL(k_cigar_expand_cut_packed, dim3(cw.n_waves), dim3(64), 0, s, p, cw);
         else hipLaunchKernelGGL(k_cigar_expand_cut, dim3(cw.n_waves), dim3(64), 0, s, p, cw);
         HIPCHK(c, hipGetLastError());
     }
@@ -1933,6 +1953,20 @@ int dagcon_upload_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *b, con
 int dagcon_consensus_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, dagcon_results *results) {
     if (!results) return DAGCON_ERR_INVALID_ARG;
     int r = dagcon_upload_cigar_packed(ctx, batch, windows);
+    if (r != DAGCON_OK) return r;
+    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
+    return dagcon_fetch(ctx, results);
+}
+
+// q_blob as the reads file has it, reverse[r] != 0: the ops are written against the reverse complement (k_cigar.hip.h);
+// windows and reverse may be NULL
+int dagcon_upload_cigar_strand(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, const uint8_t *reverse) {
+    return wn ? upload_cigar_windows(ctx, b, wn, false, reverse) : upload_cigar(ctx, b, false, reverse);
+}
+int dagcon_consensus_cigar_strand(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, const uint8_t *reverse,
+                                  dagcon_results *results) {
+    if (!results) return DAGCON_ERR_INVALID_ARG;
+    int r = dagcon_upload_cigar_strand(ctx, batch, windows, reverse);
     if (r != DAGCON_OK) return r;
     if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
     return dagcon_fetch(ctx, results);

@@ -1,0 +1,240 @@
+// paf.h -- what `pbdagcon --paf --ref --reads` needs of PAF text and of a reads file.
+//
+// A PAF line (minimap2 -c) does not carry the read: qname qlen qs qe strand tname tlen ts te nmatch alen mapq and then
+// tags name a slice [qs, qe) of a read that lies once in another file, and for a '-' line the cg:Z: CIGAR is written
+// against the reverse complement of that slice.  A record of the pipeline is then: pos = ts + 1, q_len = qe - qs, the
+// read bases the slice AS THE READS FILE HAS IT (a pointer into DgPafInput::reads; whoever fills a batch copies it with
+// memcpy), reverse = (strand == '-'): the device reads the slice backwards and complemented
+// (dagcon_upload_cigar_strand in include/dagcon.h).  No base is touched here; dg_paf_revcomp serves --dump-parsed only.
+//
+// minimap2 orders PAF by query, so the reader groups: targets come in --ref order, a target's records in file order
+// (that order is addAln order: it is semantics).  tp:A:S lines are skipped as secondary SAM records are; lines without
+// cg:Z: are skipped and counted (aligning them is not built).  A cg that does not consume exactly te - ts target bases
+// takes its target out, with a warning that names the line, as the library takes out the target of a record whose cg
+// does not consume exactly qe - qs read bases (DAGCON_ERR_NONCONFORMING).  cs:Z:, MD:Z:, QUAL and gzip are not read.
+// Line ends are LF (a CR in front of it is dropped, as sam.h drops it).
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+#include "sam.h"
+
+// the complement of include/dagcon.h: A<->T, C<->G in either case, every other byte as it is
+inline char dg_paf_comp(char c) {
+    switch (c) {
+        case 'A': return 'T'; case 'T': return 'A'; case 'C': return 'G'; case 'G': return 'C';
+        case 'a': return 't'; case 't': return 'a'; case 'c': return 'g'; case 'g': return 'c';
+        default: return c;
+    }
+}
+// for printing only (--dump-parsed)
+inline std::string dg_paf_revcomp(const char *s, size_t n) {
+    std::string out(n, 0);
+    for (size_t i = 0; i < n; i++) out[i] = dg_paf_comp(s[n - 1 - i]);
+    return out;
+}
+
+// reads a four-line FASTQ file: the names (first word of the @ line) and the bases; QUAL is not read
+inline bool dg_read_fastq(const std::string &path, DgRefSeqs &reads, std::string &err) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) { err = "error opening file: " + path; return false; }
+    std::string text;
+    char buf[1 << 16];
+    size_t n;
+    while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
+    fclose(f);
+    reads.bases.reserve(text.size() / 2);
+    size_t pos = 0;
+    unsigned long long lineno = 0;
+    const char *ln[4]; size_t ll[4];
+    while (pos < text.size()) {
+        int k = 0;
+        for (; k < 4 && pos < text.size(); k++) {
+            ln[k] = text.data() + pos;
+            const char *nl = (const char *)memchr(ln[k], '\n', text.size() - pos);
+            ll[k] = nl ? (size_t)(nl - ln[k]) : text.size() - pos;
+            pos += ll[k] + (nl ? 1 : 0);
+            lineno++;
+            if (ll[k] && ln[k][ll[k] - 1] == '\r') ll[k]--;
+            if (k == 0 && ll[0] == 0) { k = -1; continue; }       // blank lines between records
+        }
+        if (k == 0) break;
+        if (k < 4 || ll[0] < 1 || ln[0][0] != '@' || ll[2] < 1 || ln[2][0] != '+') {
+            err = path + ": line " + std::to_string(lineno) + ": not a four-line FASTQ record (@name, bases, +, qualities)";
+            return false;
+        }
+        size_t e = 1;
+        while (e < ll[0] && ln[0][e] != ' ' && ln[0][e] != '\t') e++;
+        const std::string name(ln[0] + 1, e - 1);
+        if (ll[1] > 0xFFFFFFFFull) { err = "sequence " + name + " is too long"; return false; }
+        if (!reads.by_name.emplace(name, DgRefSeqs::Span{reads.bases.size(), (uint32_t)ll[1]}).second) {
+            err = "sequence " + name + " occurs twice in " + path;
+            return false;
+        }
+        reads.bases.append(ln[1], ll[1]);
+    }
+    return true;
+}
+
+// the reads file: FASTA (multi-line) or four-line FASTQ, told apart by the first byte
+inline bool dg_read_reads(const std::string &path, DgRefSeqs &reads, std::string &err) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) { err = "error opening file: " + path; return false; }
+    const int c = fgetc(f);
+    fclose(f);
+    if (c == EOF) return true;
+    if (c == '>') return dg_read_fasta(path, reads, err);
+    if (c == '@') return dg_read_fastq(path, reads, err);
+    err = path + " is neither FASTA ('>') nor FASTQ ('@'); gzip is not read";
+    return false;
+}
+
+struct DgPafRec {
+    const char *tname; uint32_t tname_len;                 // in the PAF text
+    const char *qname; uint32_t qname_len;
+    uint32_t pos;                                          // ts + 1
+    const char *q; uint32_t q_len;                         // the slice [qs, qe) as the reads file has it
+    const char *read; uint32_t read_len, qs;               // the whole read (--dump-parsed)
+    bool reverse;
+    const char *cg; uint32_t cg_len, nops;                 // the text behind cg:Z:
+    DgRefSeqs::Span tspan;                                 // the target in --ref
+    unsigned long long line;
+};
+
+struct DgPafInput {
+    DgRefSeqs reads;
+    std::vector<DgPafRec> recs;                            // grouped: targets in --ref order, file order inside a target
+    unsigned long long n_secondary = 0, n_nocg = 0;
+
+    static bool num(const char *s, size_t n, uint64_t &v) {
+        v = 0;
+        if (!n) return false;
+        for (size_t i = 0; i < n; i++) {
+            if (s[i] < '0' || s[i] > '9') return false;
+            v = v * 10 + (uint64_t)(s[i] - '0');
+            if (v > 0xFFFFFFFFull) return false;
+        }
+        return true;
+    }
+
+    // parses the whole text; false with a message in err (it names the line).  Warnings go to stderr
+    bool parse(const char *data, size_t size, const DgRefSeqs &ref, std::string &err) {
+        size_t p = 0;
+        unsigned long long lineno = 0;
+        std::unordered_set<std::string> dropped;           // targets taken out by a cg that does not fit [ts, te)
+        auto fail = [&](const std::string &what) { err = "line " + std::to_string(lineno) + ": " + what; return false; };
+        while (p < size) {
+            const char *line = data + p;
+            const char *nl = (const char *)memchr(line, '\n', size - p);
+            size_t ll = nl ? (size_t)(nl - line) : size - p;
+            p += ll + (nl ? 1 : 0);
+            lineno++;
+            if (ll && line[ll - 1] == '\r') ll--;
+            if (ll == 0) continue;
+            const char *f[12]; size_t fl[12]; int nf = 0;
+            size_t i = 0;
+            bool more = false;                             // tags follow field 12
+            for (; nf < 12;) {
+                const char *tab = (const char *)memchr(line + i, '\t', ll - i);
+                const size_t j = tab ? (size_t)(tab - line) : ll;
+                f[nf] = line + i; fl[nf] = j - i; nf++;
+                i = j + 1;
+                if (!tab) break;
+                more = nf == 12;
+            }
+            if (nf < 12) return fail("a PAF line has 12 fields and then tags, this one has " + std::to_string(nf) + " fields");
+            const char *cg = nullptr; size_t cgl = 0;
+            bool secondary = false;
+            while (more && i <= ll) {
+                const char *tab = (const char *)memchr(line + i, '\t', ll - i);
+                const size_t j = tab ? (size_t)(tab - line) : ll;
+                if (j - i >= 5 && memcmp(line + i, "cg:Z:", 5) == 0) { cg = line + i + 5; cgl = j - i - 5; }
+                if (j - i == 6 && memcmp(line + i, "tp:A:S", 6) == 0) secondary = true;
+                if (!tab) break;
+                i = j + 1;
+            }
+            if (secondary) { n_secondary++; continue; }
+            if (!cg) { n_nocg++; continue; }
+            if (fl[4] != 1 || (f[4][0] != '+' && f[4][0] != '-')) return fail("strand is '" + std::string(f[4], std::min<size_t>(fl[4], 20)) + "', not + or -");
+            uint64_t qlen, qs, qe, tlen, ts, te;
+            if (!num(f[1], fl[1], qlen) || !num(f[2], fl[2], qs) || !num(f[3], fl[3], qe) || !num(f[6], fl[6], tlen) ||
+                !num(f[7], fl[7], ts) || !num(f[8], fl[8], te))
+                return fail("a length or a coordinate is not an unsigned 32-bit number");
+            if (qs >= qe || qe > qlen) return fail("query slice [" + std::to_string(qs) + ", " + std::to_string(qe) + ") is empty or runs past the query length " + std::to_string(qlen));
+            if (ts > te || te > tlen) return fail("target range [" + std::to_string(ts) + ", " + std::to_string(te) + ") is reversed or runs past the target length " + std::to_string(tlen));
+            const DgRefSeqs::Span *rd = reads.find(f[0], fl[0]);
+            if (!rd) return fail("query " + std::string(f[0], fl[0]) + " is not a sequence of --reads");
+            const DgRefSeqs::Span *tg = ref.find(f[5], fl[5]);
+            if (!tg) return fail("target " + std::string(f[5], fl[5]) + " is not a sequence of --ref");
+            if (qlen != rd->len) return fail("query " + std::string(f[0], fl[0]) + " has length " + std::to_string(qlen) + " here but " + std::to_string(rd->len) + " bases in --reads");
+            if (tlen != tg->len) return fail("target " + std::string(f[5], fl[5]) + " has length " + std::to_string(tlen) + " here but " + std::to_string(tg->len) + " bases in --ref");
+            // the CIGAR through sam.h's parser; the target bases it consumes against te - ts
+            std::vector<uint32_t> ops;
+            const long k = dg_cigar_ops(cg, cgl, nullptr);
+            if (k < 0) return fail("malformed cg:Z: " + std::string(cg, std::min<size_t>(cgl, 60)));
+            ops.resize((size_t)k);
+            dg_cigar_ops(cg, cgl, ops.data());
+            uint64_t nt = 0;
+            for (uint32_t op : ops) if ((1u << (op & 15u)) & 0x185u) nt += op >> 4;    // M D = X
+            const std::string tname(f[5], fl[5]);
+            if (nt != te - ts) {
+                fprintf(stderr, "pbdagcon: warning: target %s skipped (line %llu: cg:Z: consumes %llu target bases, te - ts is %llu)\n",
+                        tname.c_str(), lineno, (unsigned long long)nt, (unsigned long long)(te - ts));
+                dropped.insert(tname);
+                continue;
+            }
+            DgPafRec r;
+            r.tname = f[5]; r.tname_len = (uint32_t)fl[5];
+            r.qname = f[0]; r.qname_len = (uint32_t)fl[0];
+            r.pos = (uint32_t)ts + 1u;
+            r.read = reads.bases.data() + rd->off; r.read_len = rd->len; r.qs = (uint32_t)qs;
+            r.q = r.read + qs; r.q_len = (uint32_t)(qe - qs);
+            r.reverse = f[4][0] == '-';
+            r.cg = cg; r.cg_len = (uint32_t)cgl; r.nops = (uint32_t)k;
+            r.tspan = *tg;
+            r.line = lineno;
+            recs.push_back(r);
+        }
+        if (!dropped.empty())
+            recs.erase(std::remove_if(recs.begin(), recs.end(), [&](const DgPafRec &r) { return dropped.count(std::string(r.tname, r.tname_len)) != 0; }), recs.end());
+        // --ref order: a sequence's offset into the FASTA's bases ascends with its place in the file (the name breaks the
+        // tie of empty sequences); stable, so a target's records stay in file order
+        std::stable_sort(recs.begin(), recs.end(), [](const DgPafRec &a, const DgPafRec &b) {
+            if (a.tspan.off != b.tspan.off) return a.tspan.off < b.tspan.off;
+            const int c = memcmp(a.tname, b.tname, std::min(a.tname_len, b.tname_len));
+            return c ? c < 0 : a.tname_len < b.tname_len;
+        });
+        if (n_nocg) fprintf(stderr, "pbdagcon: %llu PAF lines without a cg:Z: tag skipped (run minimap2 with -c)\n", n_nocg);
+        return true;
+    }
+};
+
+// the grouped records as windows.h's driver takes them
+struct DgPafSource {
+    static constexpr bool packed = false;
+    static constexpr bool stranded = true;
+    static constexpr const char *unit = "line";
+    static constexpr const char *skipped_what = "PAF lines skipped (tp:A:S)";
+    const DgPafInput &in;
+    size_t at = 0;
+    unsigned long long skipped;
+    DgPafSource(const DgPafInput &i, const DgRefSeqs &) : in(i), skipped(i.n_secondary) {}
+    template <class AlnRec>
+    int next(AlnRec &r, std::vector<uint32_t> &ops) {
+        if (at >= in.recs.size()) return 0;
+        const DgPafRec &p = in.recs[at++];
+        r.rname = p.tname; r.rname_len = p.tname_len;
+        r.pos = p.pos;
+        r.q = p.q; r.q_len = p.q_len; r.nops = p.nops;
+        r.reverse = p.reverse;
+        r.where = p.line;
+        ops.resize(ops.size() + p.nops);
+        dg_cigar_ops(p.cg, p.cg_len, ops.data() + ops.size() - p.nops);
+        return 1;
+    }
+};

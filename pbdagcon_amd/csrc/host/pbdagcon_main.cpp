@@ -21,6 +21,10 @@
 //     gapped strings are made on the GPU (dagcon_consensus_cigar), never on the host (sam.h);
 //   * --bam --ref: the same from BAM (bam.h: BGZF, inflate and the records); the CIGAR ops and the 4-bit SEQ go to the
 //     GPU as they lie in the file (dagcon_consensus_cigar_packed), the output is that of --sam on the same records;
+//   * --paf --ref --reads: PAF lines with a cg:Z: CIGAR (minimap2 -c), the reads from a FASTA / FASTQ file (paf.h); a line's
+//     slice of its read goes to the GPU as the reads file has it, with one strand flag per record, and the GPU reads a
+//     '-' record's bases backwards and complemented (dagcon_consensus_cigar_strand); the output is that of --sam on the
+//     same alignments;
 //   * blank lines are skipped (the reference duplicates the previous record, Q9);
 //   * a missing input file is an error on stderr, exit 1 (the reference is silent, Q11).
 #include <algorithm>
@@ -45,6 +49,7 @@
 #include "../../../include/dagcon.h"
 #include "bam.h"
 #include "fastq.h"
+#include "paf.h"
 #include "sam.h"
 #include "windows.h"
 
@@ -56,7 +61,10 @@ struct Opts {
     bool local = false;                // --local (with -a): the first alignment of every record has local ends
     bool sam = false;                  // --sam: SAM text, the targets' bases from --ref (dagcon_consensus_cigar)
     bool bam = false;                  // --bam: the same records from BAM (bam.h); sam is set too, and the reads stay 4-bit
+    bool paf = false;                  // --paf: PAF lines with cg:Z: (paf.h), the reads from --reads; sam is set too, and the
+                                       // strand of a record is applied on the device
     std::string ref;                   // --ref FASTA
+    std::string reads;                 // --reads FASTA / FASTQ (with --paf)
     unsigned window = 0, overlap = 1000;   // --window W [--overlap O] (with --sam): targets cut into windows (windows.h)
     bool overlap_set = false;
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
@@ -73,7 +81,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> [--window W [--overlap O]]] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --paf --ref <fasta> --reads <fasta|fastq> [--window W [--overlap O]]] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -90,7 +98,7 @@ void usage(FILE *f) {
             "                      POS, CIGAR and SEQ are used, the target's bases come from --ref; records with FLAG 0x4 or\n"
             "                      0x100, or RNAME, CIGAR or SEQ '*', are skipped (counted with -v).  The gapped strings are made\n"
             "                      on the GPU; the output is that of the .m5 input with the same alignments.  Not with -a,\n"
-            "                      --local or --polish.  PAF and MD:Z-only input (no FASTA) are not read\n"
+            "                      --local or --polish.  MD:Z-only input (no FASTA) is not read\n"
             "  --bam               input is BAM: everything --sam does, from the same records in a BAM file (BGZF inflated on the\n"
             "                      -j threads by this build's own decoder, CRC32 and ISIZE of every member checked).  refID, pos,\n"
             "                      flag, read_name, the CIGAR (from the CG tag when it has more than 65,535 ops) and seq are used;\n"
@@ -98,9 +106,20 @@ void usage(FILE *f) {
             "                      errors name the record's ordinal in the file.  The CIGAR ops and the 4-bit bases go to the GPU\n"
             "                      as they lie in the file.  Indexes, CRAM and QUAL are not read.  Parity unpinned: tested on\n"
             "                      files from this build's own BAM writer only\n"
-            "  --ref FASTA         with --sam or --bam (required): the target sequences, by the name up to the first blank; an @SQ line\n"
+            "  --paf               input is PAF with cg:Z: tags (minimap2 -c): everything --sam does, from qname qlen qs qe strand\n"
+            "                      tname tlen ts te and the cg tag; the read bases come from --reads, the target's from --ref.\n"
+            "                      A line's slice [qs, qe) of its read goes to the GPU as the reads file has it, and the GPU\n"
+            "                      reads a '-' line's bases backwards and complemented (A<->T, C<->G, lower case too: this\n"
+            "                      build's own rule, parity unpinned).  Lines are grouped by target: targets in --ref order,\n"
+            "                      a target's lines in file order (with --window: ascending in ts).  tp:A:S lines are skipped\n"
+            "                      (counted with -v); lines without cg:Z: are skipped and their count is printed.  A line\n"
+            "                      whose lengths disagree with the files, or that names an unknown sequence, is an error.\n"
+            "                      Not with --sam, --bam, -a, --local or --polish.  cs:Z:, MD:Z:, QUAL and gzip are not read\n"
+            "  --reads FILE        with --paf (required): the reads, FASTA (multi-line) or four-line FASTQ by the first byte,\n"
+            "                      named by the first word of the header; a name that occurs twice is an error\n"
+            "  --ref FASTA         with --sam, --bam or --paf (required): the target sequences, by the name up to the first blank; an @SQ line\n"
             "                      whose LN differs from the sequence of its SN is an error\n"
-            "  --window W          with --sam or --bam: targets of any length and depth.  Every target is cut into windows with cores of W\n"
+            "  --window W          with --sam, --bam or --paf: targets of any length and depth.  Every target is cut into windows with cores of W\n"
             "                      bases, each run with --overlap more bases on either side; the records are cut to the windows\n"
             "                      on the GPU and the windows' consensus is joined at target coordinates.  Records of one RNAME\n"
             "                      must then be ascending in POS (a coordinate-sorted SAM).  In this mode only, a record is named\n"
@@ -122,7 +141,7 @@ void usage(FILE *f) {
             "                      targets dealt round-robin, records still printed in input order\n"
             "  --contexts N        consensus workers (thread + context) per GPU, 1..4: a batch's upload and formatting run\n"
             "                      beside another batch's kernels (default: 2 for inputs of several batches, else 1)\n"
-            "  <input>             BLASR -m 5 file (.pre with -a, SAM with --sam, BAM with --bam) sorted by target, or - for stdin\n"
+            "  <input>             BLASR -m 5 file (.pre with -a, SAM with --sam, BAM with --bam, PAF with --paf) sorted by target, or - for stdin\n"
             "  version 0.3 (dagcon-mi355x)\n");
 }
 
@@ -152,6 +171,11 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--fastq") o.fastq = true;
         else if (a == "--sam") o.sam = true;
         else if (a == "--bam") o.bam = true;
+        else if (a == "--paf") o.paf = true;
+        else if (a == "--reads") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --reads needs a FASTA or FASTQ file\n"); return 2; }
+            o.reads = argv[++i];
+        }
         else if (a == "--window") { if (!need(&o.window) || !o.window) { fprintf(stderr, "PARSE ERROR: --window takes a positive number of bases\n"); return 2; } }
         else if (a == "--overlap") { if (!need(&o.overlap)) return 2; o.overlap_set = true; }
         else if (a == "--ref") {
@@ -187,14 +211,20 @@ int parse_args(int argc, char **argv, Opts &o) {
         } else { fprintf(stderr, "PARSE ERROR: unknown argument %s\n", a.c_str()); return 2; }
     }
     if (o.local && !o.align) { fprintf(stderr, "PARSE ERROR: --local needs -a\n"); return 2; }
+    if (o.paf && (o.sam || o.bam)) { fprintf(stderr, "PARSE ERROR: --paf does not go with --sam or --bam\n"); return 2; }
+    if (o.paf && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --paf does not go with -a, --local or --polish\n"); return 2; }
+    if (o.paf && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --paf needs --ref <fasta>\n"); return 2; }
+    if (o.paf && o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --paf needs --reads <fasta|fastq>\n"); return 2; }
+    if (!o.paf && !o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --reads needs --paf\n"); return 2; }
+    if (o.paf) o.sam = true;                               // (records with a CIGAR, as below)
     if (o.bam && o.sam) { fprintf(stderr, "PARSE ERROR: --bam and --sam do not go together\n"); return 2; }
     if (o.bam && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --bam does not go with -a, --local or --polish\n"); return 2; }
     if (o.bam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --bam needs --ref <fasta>\n"); return 2; }
     if (o.bam) o.sam = true;                               // from here on sam means: records with a CIGAR, from either format
     if (o.sam && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --sam does not go with -a, --local or --polish\n"); return 2; }
     if (o.sam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --sam needs --ref <fasta>\n"); return 2; }
-    if (!o.sam && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam or --bam\n"); return 2; }
-    if (o.window && (!o.sam || o.align || o.polish)) { fprintf(stderr, "PARSE ERROR: --window needs --sam or --bam and does not go with -a or --polish\n"); return 2; }
+    if (!o.sam && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam, --bam or --paf\n"); return 2; }
+    if (o.window && (!o.sam || o.align || o.polish)) { fprintf(stderr, "PARSE ERROR: --window needs --sam, --bam or --paf and does not go with -a or --polish\n"); return 2; }
     if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
     if (o.window && (uint64_t)o.overlap < (uint64_t)o.trim + 64) { fprintf(stderr, "PARSE ERROR: --overlap must be at least --trim + 64 (%u)\n", o.trim + 64); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
@@ -297,9 +327,12 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
         cb.t_blob = b.t.data(); cb.t_bytes = b.t.size(); cb.rec_begin = b.begin.data();
         cb.pos = b.start.data(); cb.q_off = b.off.data(); cb.q_len = b.len.data();
         cb.q_blob = b.q.data(); cb.q_bytes = b.q.size(); cb.op_begin = b.opb.data(); cb.ops = b.ops.data();
+        std::vector<uint8_t> rev;                           // --paf: one strand flag per record, applied on the device
+        if (o.paf) { rev.resize(b.strand.size() + 1); for (size_t a = 0; a < b.strand.size(); a++) rev[a] = b.strand[a] == '-'; }
         const double ta0 = wall();
-        rc = o.bam ? dagcon_consensus_cigar_packed(ctx, &cb, nullptr, &r) : dagcon_consensus_cigar(ctx, &cb, &r);
-        if (g_timing) fprintf(stderr, "pbdagcon timing: %s batch of %zu records: dagcon_consensus_cigar%s %.3f\n", o.bam ? "--bam" : "--sam", b.start.size(), o.bam ? "_packed" : "", wall() - ta0);
+        rc = o.paf ? dagcon_consensus_cigar_strand(ctx, &cb, nullptr, rev.data(), &r)
+           : o.bam ? dagcon_consensus_cigar_packed(ctx, &cb, nullptr, &r) : dagcon_consensus_cigar(ctx, &cb, &r);
+        if (g_timing) fprintf(stderr, "pbdagcon timing: %s batch of %zu records: dagcon_consensus_cigar%s %.3f\n", o.paf ? "--paf" : o.bam ? "--bam" : "--sam", b.start.size(), o.paf ? "_strand" : o.bam ? "_packed" : "", wall() - ta0);
         have_results = true;
     } else if (o.align && !o.polish) {
         // main.cpp:117-145 with -a in one call: the aligned strings stay on the device
@@ -557,7 +590,7 @@ int main(int argc, char **argv) {
     DgRefSeqs ref;
     if (o.sam) {
         std::string err;
-        if (!dg_read_fasta(o.ref, ref, err) || (!o.bam && !dg_sam_check_header(data, size, ref, err))) {
+        if (!dg_read_fasta(o.ref, ref, err) || (!o.bam && !o.paf && !dg_sam_check_header(data, size, ref, err))) {
             fprintf(stderr, "pbdagcon: %s\n", err.c_str());
             return 1;
         }
@@ -583,9 +616,20 @@ int main(int argc, char **argv) {
         bam_first = bam.at;
     }
 
+    // ---- --paf: the reads, and every line parsed, checked and grouped by target (targets in --ref order) ----
+    DgPafInput paf;
+    if (o.paf) {
+        std::string err;
+        if (!dg_read_reads(o.reads, paf.reads, err) || !paf.parse(data, size, ref, err)) {
+            fprintf(stderr, "pbdagcon: %s\n", err.c_str());
+            return 1;
+        }
+    }
+
     if (o.window && !o.dump) {
         DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0]};
         if (o.bam) { DgBamSource src(bam, ref); return dg_run_windows(wo, src, ref); }
+        if (o.paf) { DgPafSource src(paf, ref); return dg_run_windows(wo, src, ref); }
         DgSamSource src(data, size, ref);
         return dg_run_windows(wo, src, ref);
     }
@@ -720,6 +764,7 @@ int main(int argc, char **argv) {
         const char *cg; uint32_t cgl, nops;          // --sam: the CIGAR field and its number of ops (t: the target's bases in --ref);
                                                      // --bam: the ops themselves, q the 4-bit seq field, len its bases
         unsigned long long line;                     // --sam: line of the input; --bam: ordinal of the record
+        const char *read; uint32_t read_len, qs;     // --paf: the whole read and where the slice q begins in it (--dump-parsed)
     };
     struct Part { std::vector<Rec> recs; int err = 0; unsigned long long err_rec = 0; int err_nf = 0; unsigned long long lines = 0, skipped = 0; };
     unsigned long long n_lines_before = 0, n_skipped = 0;
@@ -768,8 +813,31 @@ int main(int argc, char **argv) {
         for (const Rec &r : pt.recs) recs.push_back(&r);
         n_rec_before += pt.recs.size();
     };
+    // --paf: the grouped records, all at once (paf.h has parsed and checked the lines)
+    auto index_paf = [&]() {
+        Part &pt = parts[0];
+        pt.recs.clear();
+        recs.clear();
+        for (const DgPafRec &p : paf.recs) {
+            Rec r;
+            r.id = p.tname; r.idl = p.tname_len;
+            r.name = p.qname; r.namel = p.qname_len;
+            r.q = p.q; r.len = p.q_len;
+            r.t = ref.bases.data() + p.tspan.off; r.tlen = p.tspan.len; r.tl = 0;
+            r.start = p.pos;
+            r.strand = p.reverse ? '-' : '+';
+            r.cg = p.cg; r.cgl = p.cg_len; r.nops = p.nops;
+            r.line = p.line;
+            r.read = p.read; r.read_len = p.read_len; r.qs = p.qs;
+            pt.recs.push_back(r);
+        }
+        n_skipped = paf.n_secondary;
+        for (const Rec &r : pt.recs) recs.push_back(&r);
+        n_rec_before += pt.recs.size();
+    };
     auto index_slab = [&](size_t s0, size_t s1) {
         if (o.bam) { index_bam(s1); return; }
+        if (o.paf) { index_paf(); return; }
         std::vector<size_t> cut(nthr + 1, s1);
         cut[0] = s0;
         for (unsigned k = 1; k < nthr; k++) {
@@ -937,7 +1005,7 @@ int main(int argc, char **argv) {
     if (!bp) status = 1;
 #define b (*bp)
     while (status == 0 && !had_error && (slab_pos < size || !carry.empty())) {
-        size_t s1 = std::min(size, slab_pos + slab_bytes);
+        size_t s1 = o.paf ? size : std::min(size, slab_pos + slab_bytes);   // (--paf: the lines were grouped as a whole)
         if (s1 < size && !o.bam) {                         // a slab ends at a line end
             const char *nl = (const char *)memchr(data + s1, '\n', size - s1);
             s1 = nl ? (size_t)(nl - data) + 1 : size;
@@ -975,6 +1043,18 @@ int main(int argc, char **argv) {
                                 printf("%.*s\t%u\t%u\t%c\t%.*s\t%s\t%s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
                                        (int)r.namel, r.name, seq.c_str(),
                                        dg_cigar_text(b.ops.data() + b.opb[y - rb], b.opb[y - rb + 1] - b.opb[y - rb]).c_str());
+                                continue;
+                            }
+                            if (o.paf) {
+                                // what --sam prints for the equivalent SAM record: SEQ the whole read in the target's
+                                // orientation (reverse-complemented for printing only), soft clips qs and qlen - qe around
+                                // the cg ops, swapped for '-'
+                                const uint32_t c0 = r.strand == '-' ? r.read_len - r.qs - r.len : r.qs, c1 = r.read_len - r.len - c0;
+                                const std::string seq = r.strand == '-' ? dg_paf_revcomp(r.read, r.read_len) : std::string(r.read, r.read_len);
+                                printf("%.*s\t%u\t%u\t%c\t%.*s\t%s\t%s%s%s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
+                                       (int)r.namel, r.name, seq.c_str(), c0 ? (std::to_string(c0) + "S").c_str() : "",
+                                       dg_cigar_text(b.ops.data() + b.opb[y - rb], b.opb[y - rb + 1] - b.opb[y - rb]).c_str(),
+                                       c1 ? (std::to_string(c1) + "S").c_str() : "");
                                 continue;
                             }
                             if (o.sam) {                       // RNAME, its length in --ref, POS, strand, QNAME, SEQ, CIGAR (from the ops)
@@ -1040,7 +1120,9 @@ int main(int argc, char **argv) {
         if (eof) slab_pos = size;
     }
     if (had_error) status = 1;
-    if (o.bam && o.verbose)
+    if (o.paf && o.verbose)
+        fprintf(stderr, "pbdagcon: %llu PAF lines skipped (tp:A:S)\n", n_skipped);
+    else if (o.bam && o.verbose)
         fprintf(stderr, "pbdagcon: %llu BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)\n", n_skipped);
     else if (o.sam && o.verbose)
         fprintf(stderr, "pbdagcon: %llu SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')\n", n_skipped);

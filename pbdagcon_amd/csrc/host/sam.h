@@ -1,6 +1,6 @@
 // sam.h -- what `pbdagcon --sam --ref` needs of SAM and FASTA text: the reference sequences by name, CIGAR text to
 // BAM-encoded ops (len << 4 | op, op 0..8 = M I D N S H P = X: dagcon_cigar_batch in include/dagcon.h), the @SQ lines
-// of the header against the FASTA.  Text only (BAM: bam.h); PAF and MD:Z-only input are not read.  Line ends are LF (a CR in
+// of the header against the FASTA.  Text only (BAM: bam.h; PAF: paf.h); MD:Z-only input is not read.  Line ends are LF (a CR in
 // front of it is dropped with the line's last field, as the .m5 parser drops it).
 #pragma once
 #include <cstdint>

@@ -1,12 +1,13 @@
-// windows.h -- `pbdagcon --sam|--bam --ref F --window W [--overlap O]`: targets of any length and depth.
+// windows.h -- `pbdagcon --sam|--bam|--paf --ref F --window W [--overlap O]`: targets of any length and depth.
 //
 // Window i of a target has the core [iW, min((i + 1)W, tlen)) and is run as [max(0, iW - O), min(tlen, (i + 1)W + O));
 // a target of at most W bases is one window.  Windows go to the device in groups of about --batch-targets
 // (dagcon_consensus_cigar_windows on a DAGCON_FLAG_BASE_POS context, with DAGCON_FLAG_BASE_SUPPORT for --fastq); a group
 // gets only the records whose [s, e) meets it, which the host knows from the ops it has parsed.  Records of one RNAME
 // must be consecutive and ascending in POS, as in a coordinate-sorted SAM.  The records come from a source (DgSamSource:
-// SAM text; DgBamSource: bam.h's reader, whose reads stay in BAM's 4-bit encoding all the way to the device); grouping,
-// batching and the stitch do not know which.
+// SAM text; DgBamSource: bam.h's reader, whose reads stay in BAM's 4-bit encoding all the way to the device; DgPafSource in
+// paf.h: PAF lines grouped by target, whose reads stay as the reads file has them, with a strand flag per record that
+// the device applies); grouping, batching and the stitch do not know which.
 //
 // The stitch (DgStitch; tests/window_twin.py: stitch is its numpy twin).  With g = pos + window begin the 1-based
 // target position of a consensus base (dagcon_fetch_positions): of a window's segment the bases from the first one
@@ -81,12 +82,15 @@ struct DgAlnRec {
     uint32_t pos;
     const char *q; uint32_t q_len;                         // q_len counts bases
     uint32_t nops;                                         // the record's ops are the last nops of `ops`
+    bool reverse;                                          // stranded sources only: the ops are written against the reverse
+                                                           // complement of q (dagcon_upload_cigar_strand)
     unsigned long long where;                              // the line (SAM) or the record's ordinal (BAM): what an error names
 };
 
 // SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
 struct DgSamSource {
     static constexpr bool packed = false;
+    static constexpr bool stranded = false;
     static constexpr const char *unit = "line";
     static constexpr const char *skipped_what = "SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')";
     const char *data; size_t size, p = 0;
@@ -133,6 +137,7 @@ struct DgSamSource {
 // BAM records (bam.h); the header's references were checked against --ref when the file was opened
 struct DgBamSource {
     static constexpr bool packed = true;
+    static constexpr bool stranded = false;
     static constexpr const char *unit = "record";
     static constexpr const char *skipped_what = "BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)";
     DgBamReader &bam;
@@ -159,7 +164,7 @@ struct DgBamSource {
 // the whole run; the process's exit status
 template <class Source>
 inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref) {
-    struct Rec { uint32_t pos, s, e, q_len; const char *q; uint64_t op0; uint32_t nops; };
+    struct Rec { uint32_t pos, s, e, q_len; const char *q; uint64_t op0; uint32_t nops; bool reverse; };
     struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; };
     std::vector<Tgt> tgts;
     std::vector<uint32_t> ops;
@@ -181,6 +186,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         r.pos = ar.pos;
         if (!t.recs.empty() && r.pos < t.recs.back().pos) { fprintf(stderr, "pbdagcon: %s %llu: POS %u of RNAME %s is below that of the record before it (--window needs records ascending in POS, as in a coordinate-sorted SAM)\n", Source::unit, ar.where, r.pos, rname.c_str()); return 1; }
         r.q = ar.q; r.q_len = ar.q_len; r.op0 = ops.size() - ar.nops; r.nops = ar.nops;
+        r.reverse = Source::stranded && ar.reverse;
         const long k = (long)ar.nops;
         // [s, e) by the rule of include/dagcon.h (a non-conforming record: clipped into the target, at least one base)
         uint64_t nt = 0;
@@ -247,6 +253,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         std::vector<uint32_t> b_tlen, b_pos, b_qlen, b_ops, w_t, w_b, w_e;
         std::vector<uint64_t> b_toff, b_rec{0}, b_qoff, b_opb{0};
         std::string qblob;
+        std::vector<uint8_t> b_rev;                            // stranded sources: one flag per record
         for (size_t a = w0; a < w1;) {
             size_t z = a;
             while (z < w1 && wins[z].tgt == wins[a].tgt) z++;
@@ -263,6 +270,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
                 qblob.append(it->q, Source::packed ? ((size_t)it->q_len + 1) / 2 : it->q_len);
                 b_ops.insert(b_ops.end(), ops.begin() + (long)it->op0, ops.begin() + (long)(it->op0 + it->nops));
                 b_opb.push_back(b_ops.size());
+                if (Source::stranded) b_rev.push_back(it->reverse ? 1 : 0);
             }
             b_rec.push_back(b_pos.size());
             for (size_t k = a; k < z; k++) { w_t.push_back(bt); w_b.push_back(wins[k].begin); w_e.push_back(wins[k].end); }
@@ -277,7 +285,9 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         dagcon_windows dw;
         dw.n_windows = (uint32_t)w_t.size(); dw.target = w_t.data(); dw.begin = w_b.data(); dw.end = w_e.data();
         dagcon_results r;
-        rc = Source::packed ? dagcon_consensus_cigar_packed(ctx, &cb, &dw, &r) : dagcon_consensus_cigar_windows(ctx, &cb, &dw, &r);
+        rc = Source::packed ? dagcon_consensus_cigar_packed(ctx, &cb, &dw, &r)
+           : Source::stranded ? dagcon_consensus_cigar_strand(ctx, &cb, &dw, b_rev.data(), &r)
+                              : dagcon_consensus_cigar_windows(ctx, &cb, &dw, &r);
         const uint32_t *pos = nullptr;
         uint64_t npos = 0;
         dagcon_support sup;

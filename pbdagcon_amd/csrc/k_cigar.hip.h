@@ -29,6 +29,18 @@
 // Out-of-bounds safety, packed: the host admits a record only after q_off + (q_len + 1) / 2 <= q_bytes (in 64 bits)
 // and, as above, after the scan's totals say that its ops consume exactly q_len read bases; a base index i formed here
 // is then below q_len, and the byte index i >> 1 below (q_len + 1) / 2.
+//
+// Read strand (dagcon_upload_cigar_strand; k_cigar_expand_strand, k_cigar_expand_cut_strand): q holds a record's bases as
+// the reads file has them and rev one byte per record; for rev[r] != 0 the ops are written against the reverse
+// complement, so read base i is comp(q[q_len - 1 - i]).  A wave works on one record, so the flag is wave-uniform: it is
+// loaded once per wave (a scalar load) next to the record's q_len, which is its read-base total (ckpt and totals hold
+// it only per tile; the host passes q_len[]).  comp swaps A<->T, C<->G in either case and keeps every other byte: four
+// compares on the byte with its case bit cleared and an XOR by the pair's difference (A^T = 0x15, C^G = 0x04), no table
+// in memory.  The strand kernels are the unpacked ones but for that index and those few ALU ops (one body, STRAND a
+// template parameter); scan and cut read no bases and serve all.
+// Out-of-bounds safety, strand: as above a base index i formed here is below q_len, the q_len the host checked against
+// the blob and passes to the kernel unchanged; 0 <= i < q_len implies 0 <= q_len - 1 - i < q_len, so the mirrored
+// index stays inside the same q_off .. + q_len range.  rev and q_len have one entry per record, and r < n.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -129,10 +141,28 @@ __device__ __forceinline__ uint8_t dg_cg_qbase(const uint8_t *q, uint32_t i) {
     if constexpr (PACKED) return dg_cg_nt16(((uint32_t)q[i >> 1] >> ((~i & 1u) * 4u)) & 15u);
     else return q[i];
 }
+// the complement: A<->T, C<->G, a<->t, c<->g, any other byte as it is
+__device__ __forceinline__ uint8_t dg_cg_comp(uint8_t b) {
+    const uint32_t u = b & 0xDFu;                                  // case bit cleared (only letters compare equal below)
+    const uint32_t x = (u == 'A' || u == 'T') ? 0x15u : (u == 'C' || u == 'G') ? 0x04u : 0u;
+    return (uint8_t)(b ^ x);
+}
+// what the strand kernels know of a record beyond DgCigarParams (kernel arguments of their own: the struct, and with it
+// the four kernels without strand, stay as they are)
+struct DgCigarStrand {
+    const uint8_t *rev;            // [n] != 0: the ops are written against the reverse complement of the bases
+    const uint32_t *q_len;         // [n]
+};
+// read base i of a record of the strand kernels: last = q_len - 1 for a reverse record (wave-uniform), else unused
+__device__ __forceinline__ uint8_t dg_cg_qbase_strand(const uint8_t *q, uint32_t i, bool rev, uint32_t last) {
+    const uint8_t b = q[rev ? last - i : i];
+    return rev ? dg_cg_comp(b) : b;
+}
 
 // a wave per tile of 64 ops
-template <bool PACKED>
-__device__ __forceinline__ void dg_cg_expand(const DgCigarParams &p) {
+template <bool PACKED, bool STRAND>
+__device__ __forceinline__ void dg_cg_expand(const DgCigarParams &p, const DgCigarStrand &st) {
+    static_assert(!(PACKED && STRAND), "packed bases carry no strand");
     __shared__ uint32_t s_end[64], s_q0[64], s_t0[64], s_code[64];
     const uint32_t lane = threadIdx.x;
     const uint32_t tile = blockIdx.x;
@@ -160,6 +190,12 @@ __device__ __forceinline__ void dg_cg_expand(const DgCigarParams &p) {
     const uint8_t *q = p.q + p.q_off[r];
     const uint8_t *t = p.t + p.t_base[r];
     uint8_t *oq = p.out_q + out + ck.x, *ot = p.out_t + out + ck.x;
+    bool rev = false;
+    uint32_t last = 0;
+    if constexpr (STRAND) {                                       // (r is wave-uniform: scalar loads, once per wave)
+        rev = st.rev[r] != 0;
+        last = st.q_len[r] - 1u;                                  // (read only for a base index below q_len >= 1)
+    }
     for (uint32_t c = lane; c < n_col; c += 64u) {
         // the first op whose columns end past c
         uint32_t lo = 0;
@@ -169,12 +205,14 @@ __device__ __forceinline__ void dg_cg_expand(const DgCigarParams &p) {
         const uint32_t first = lo ? s_end[lo - 1u] : 0u;          // (an op without columns ends where it begins: never found)
         const uint32_t k = c - first;
         const uint32_t b = 1u << s_code[lo];
-        oq[c] = (b & DG_CG_Q_MASK) ? dg_cg_qbase<PACKED>(q, s_q0[lo] + k) : (uint8_t)'-';
+        if constexpr (STRAND) oq[c] = (b & DG_CG_Q_MASK) ? dg_cg_qbase_strand(q, s_q0[lo] + k, rev, last) : (uint8_t)'-';
+        else oq[c] = (b & DG_CG_Q_MASK) ? dg_cg_qbase<PACKED>(q, s_q0[lo] + k) : (uint8_t)'-';
         ot[c] = (b & DG_CG_T_MASK) ? t[s_t0[lo] + k] : (uint8_t)'-';
     }
 }
-__global__ __launch_bounds__(64) void k_cigar_expand(DgCigarParams p) { dg_cg_expand<false>(p); }
-__global__ __launch_bounds__(64) void k_cigar_expand_packed(DgCigarParams p) { dg_cg_expand<true>(p); }
+__global__ __launch_bounds__(64) void k_cigar_expand(DgCigarParams p) { dg_cg_expand<false, false>(p, DgCigarStrand{}); }
+__global__ __launch_bounds__(64) void k_cigar_expand_packed(DgCigarParams p) { dg_cg_expand<true, false>(p, DgCigarStrand{}); }
+__global__ __launch_bounds__(64) void k_cigar_expand_strand(DgCigarParams p, DgCigarStrand st) { dg_cg_expand<false, true>(p, st); }
 
 // ---- records cut to windows (dagcon_upload_cigar_windows; include/dagcon.h has the rule) ----------------------------
 // A piece is one (record, window) pair: the record's columns [F(A), F(B)), F(x) the first column that consumes target
@@ -258,8 +296,9 @@ __global__ __launch_bounds__(256) void k_cigar_cut(DgCigarParams p, DgCigarCutPa
 }
 
 // a wave per (piece, tile of 64 ops)
-template <bool PACKED>
-__device__ __forceinline__ void dg_cg_expand_cut(const DgCigarParams &p, const DgCigarCutParams &w) {
+template <bool PACKED, bool STRAND>
+__device__ __forceinline__ void dg_cg_expand_cut(const DgCigarParams &p, const DgCigarCutParams &w, const DgCigarStrand &st) {
+    static_assert(!(PACKED && STRAND), "packed bases carry no strand");
     __shared__ uint32_t s_end[64], s_q0[64], s_t0[64], s_code[64];
     const uint32_t lane = threadIdx.x;
     if (blockIdx.x >= w.n_waves) return;
@@ -291,6 +330,12 @@ __device__ __forceinline__ void dg_cg_expand_cut(const DgCigarParams &p, const D
     const uint8_t *t = p.t + p.t_base[r];
     const uint64_t out = w.piece_out[pc];
     uint8_t *oq = p.out_q + out, *ot = p.out_t + out;
+    bool rev = false;
+    uint32_t last = 0;
+    if constexpr (STRAND) {                                       // (as in dg_cg_expand)
+        rev = st.rev[r] != 0;
+        last = st.q_len[r] - 1u;
+    }
     for (uint32_t c = c_lo + lane; c < c_hi; c += 64u) {
         uint32_t lo = 0;
 #pragma unroll
@@ -300,9 +345,13 @@ __device__ __forceinline__ void dg_cg_expand_cut(const DgCigarParams &p, const D
         const uint32_t kk = c - first;
         const uint32_t b = 1u << s_code[lo];
         const uint32_t at = ck.x + c - cut.x;                     // (ck.x + c >= F(A): c >= c_lo)
-        oq[at] = (b & DG_CG_Q_MASK) ? dg_cg_qbase<PACKED>(q, s_q0[lo] + kk) : (uint8_t)'-';
+        if constexpr (STRAND) oq[at] = (b & DG_CG_Q_MASK) ? dg_cg_qbase_strand(q, s_q0[lo] + kk, rev, last) : (uint8_t)'-';
+        else oq[at] = (b & DG_CG_Q_MASK) ? dg_cg_qbase<PACKED>(q, s_q0[lo] + kk) : (uint8_t)'-';
         ot[at] = (b & DG_CG_T_MASK) ? t[s_t0[lo] + kk] : (uint8_t)'-';
     }
 }
-__global__ __launch_bounds__(64) void k_cigar_expand_cut(DgCigarParams p, DgCigarCutParams w) { dg_cg_expand_cut<false>(p, w); }
-__global__ __launch_bounds__(64) void k_cigar_expand_cut_packed(DgCigarParams p, DgCigarCutParams w) { dg_cg_expand_cut<true>(p, w); }
+__global__ __launch_bounds__(64) void k_cigar_expand_cut(DgCigarParams p, DgCigarCutParams w) { dg_cg_expand_cut<false, false>(p, w, DgCigarStrand{}); }
+__global__ __launch_bounds__(64) void k_cigar_expand_cut_packed(DgCigarParams p, DgCigarCutParams w) { dg_cg_expand_cut<true, false>(p, w, DgCigarStrand{}); }
+__global__ __launch_bounds__(64) void k_cigar_expand_cut_strand(DgCigarParams p, DgCigarCutParams w, DgCigarStrand st) {
+    dg_cg_expand_cut<false, true>(p, w, st);
+}

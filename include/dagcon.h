@@ -429,6 +429,56 @@ int dagcon_consensus_cigar_strand(dagcon_ctx *ctx, const dagcon_cigar_batch *bat
                                   const uint8_t *reverse, dagcon_results *results);
 
 /*
+ * Alignments as minimap2 --cs writes them (PAF cs:Z:): the tag's text and the target are the whole alignment, there are
+ * no read bases to hand over.  cs_blob[cs_off[r] .. + cs_len[r]) is the text behind "cs:Z:" as the file has it; it goes
+ * to the device raw and is decoded there into the ops and the read bases of a dagcon_cigar_batch record (k_cs.hip.h),
+ * which then take the path of dagcon_consensus_cigar (windows == NULL) or dagcon_consensus_cigar_windows.  Neither the
+ * ops nor the read exist on the host.  The text is in target orientation: a '-' PAF line needs nothing done to it.
+ * Decode rule (this build's own: the reference reads no PAF, parity unpinned):
+ *   - a byte of  : * + - = ~  starts an op wherever it stands; the op's body runs to the next such byte or to the end
+ *     of the text (tokenising is context-free);
+ *   - :n     n = 1..9 decimal digits, 1 <= n < 2^28:  op '=' of length n, read bases = the target's bytes at those
+ *            positions, verbatim (a soft-masked target passes through);
+ *   - =SEQ   one or more ASCII letters:  op '=' of length |SEQ|, read bases SEQ upper-cased;
+ *   - *tq    exactly two ASCII letters:  op 'X' of length 1, read base q upper-cased;
+ *   - +SEQ   one or more ASCII letters:  op 'I' of length |SEQ|, read bases SEQ upper-cased;
+ *   - -SEQ   one or more ASCII letters:  op 'D' of length |SEQ|, no read bases.
+ *   Upper-cased: a..z lose the case bit, upper case stays.  The t of *tq and the body of -SEQ are not compared with
+ *   the target: the target side always comes from t_blob, as in dagcon_consensus_cigar.  Neighbouring ops are not
+ *   merged.
+ * The result is, byte for byte, that of dagcon_consensus_cigar (or _windows) on the batch with these ops and these read
+ * bases: segments, target_status, dagcon_fetch_support, dagcon_fetch_positions, the counts in the timings.
+ * A record is non-conforming (target_status DAGCON_ERR_NONCONFORMING for its target, or for every window it touches;
+ * the rest of the batch is complete and exact) when its text breaks the grammar -- a ~ op, a non-empty text whose
+ * first byte starts no op, an empty body, a non-letter or a non-digit in a body, :0, more than 9 digits or a number of
+ * 2^28 or more, a * body that is not two letters -- or when its read-base total != q_len, its target-base total !=
+ * t_span (when t_span is given), or anything holds that makes a CIGAR record non-conforming (pos == 0, pos - 1 + target
+ * bases > tlen, a total past 32 bits).  With windows, the span of a non-conforming record is that of the CIGAR calls
+ * with its decoded target-base total; a record whose text breaks the grammar has no decoded totals: its total is
+ * t_span when that is given, else 0 (the one base at pos).
+ * DAGCON_ERR_INVALID_ARG before any launch: cs_off + cs_len > cs_bytes, t_off + tlen > t_bytes, a rec_begin that is not
+ * monotone.  Windows errors, limits and flags are those of the CIGAR calls.
+ */
+typedef struct dagcon_cs_batch {
+    uint32_t n_targets;
+    const uint32_t *tlen;        /* [n_targets] */
+    const uint64_t *t_off;       /* [n_targets] target bases: t_blob[t_off .. + tlen) */
+    const char *t_blob;
+    uint64_t t_bytes;
+    const uint64_t *rec_begin;   /* [n_targets + 1] records of target g, in addAln order */
+    const uint32_t *pos;         /* [n_rec] 1-based leftmost target base (PAF ts + 1) */
+    const uint32_t *q_len;       /* [n_rec] read bases the record claims (PAF qe - qs) */
+    const uint32_t *t_span;      /* [n_rec] target bases it claims (PAF te - ts), or NULL: not checked */
+    const uint64_t *cs_off;      /* [n_rec] the text behind "cs:Z:": cs_blob[cs_off .. + cs_len) */
+    const uint32_t *cs_len;
+    const char *cs_blob;
+    uint64_t cs_bytes;
+} dagcon_cs_batch;
+int dagcon_upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *batch, const dagcon_windows *windows /* or NULL */);
+int dagcon_consensus_cs(dagcon_ctx *ctx, const dagcon_cs_batch *batch, const dagcon_windows *windows /* or NULL */,
+                        dagcon_results *results);
+
+/*
  * Debug / parity aid: adjacency of one target's graph as left by the last
  * dagcon_run (after mergeNodes), in list order.  Vertex ids are in backbone
  * position order: the inserted vertices whose _bbMap is p (in read, column

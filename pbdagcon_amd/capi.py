@@ -39,6 +39,7 @@ EXPORTS = [
     "dagcon_fetch_positions", "dagcon_upload_cigar_windows", "dagcon_consensus_cigar_windows",
     "dagcon_upload_cigar_packed", "dagcon_consensus_cigar_packed",
     "dagcon_upload_cigar_strand", "dagcon_consensus_cigar_strand",
+    "dagcon_upload_cs", "dagcon_consensus_cs",
 ]
 ABI_VERSION = 2
 
@@ -74,6 +75,13 @@ class CigarBatch(C.Structure):
                 ("t_bytes", C.c_uint64), ("rec_begin", C.c_void_p), ("pos", C.c_void_p), ("q_off", C.c_void_p),
                 ("q_len", C.c_void_p), ("q_blob", C.c_void_p), ("q_bytes", C.c_uint64), ("op_begin", C.c_void_p),
                 ("ops", C.c_void_p)]
+
+
+class CsBatch(C.Structure):
+    _fields_ = [("n_targets", C.c_uint32), ("tlen", C.c_void_p), ("t_off", C.c_void_p), ("t_blob", C.c_void_p),
+                ("t_bytes", C.c_uint64), ("rec_begin", C.c_void_p), ("pos", C.c_void_p), ("q_len", C.c_void_p),
+                ("t_span", C.c_void_p), ("cs_off", C.c_void_p), ("cs_len", C.c_void_p), ("cs_blob", C.c_void_p),
+                ("cs_bytes", C.c_uint64)]
 
 
 class Windows(C.Structure):
@@ -157,6 +165,8 @@ def load() -> C.CDLL:
     L.dagcon_upload_cigar_packed.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows)]
     L.dagcon_consensus_cigar_packed.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(Results)]
     L.dagcon_upload_cigar_strand.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), vp]
+    L.dagcon_upload_cs.argtypes = [vp, C.POINTER(CsBatch), C.POINTER(Windows)]
+    L.dagcon_consensus_cs.argtypes = [vp, C.POINTER(CsBatch), C.POINTER(Windows), C.POINTER(Results)]
     L.dagcon_consensus_cigar_strand.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), vp, C.POINTER(Results)]
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
@@ -347,6 +357,77 @@ class HostCigarBatch:
         b.q_bytes = self.q_blob.size
         b.op_begin = self.op_begin.ctypes.data
         b.ops = self.ops.ctypes.data
+        return b
+
+
+class HostCsBatch:
+    """numpy view of a dagcon_cs_batch: per record a position, the read and target lengths it claims and the text
+    behind a PAF line's cs:Z: tag as the file has it, per target its bases once.  There are no read bases: the device
+    decodes the text against the target (dagcon_upload_cs)."""
+
+    def __init__(self, tlen, t_off, t_blob, rec_begin, pos, q_len, cs_off, cs_len, cs_blob, t_span=None, ids=None):
+        def u8(x):
+            return np.ascontiguousarray(np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else x,
+                                        dtype=np.uint8)
+        self.tlen = np.ascontiguousarray(tlen, dtype=np.uint32)
+        self.t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        self.t_blob = u8(t_blob)
+        self.rec_begin = np.ascontiguousarray(rec_begin, dtype=np.uint64)
+        self.pos = np.ascontiguousarray(pos, dtype=np.uint32)
+        self.q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+        self.cs_off = np.ascontiguousarray(cs_off, dtype=np.uint64)
+        self.cs_len = np.ascontiguousarray(cs_len, dtype=np.uint32)
+        self.cs_blob = u8(cs_blob)
+        self.t_span = None if t_span is None else np.ascontiguousarray(t_span, dtype=np.uint32)
+        self.ids = ids
+        if self.t_span is not None and self.t_span.shape != self.pos.shape:
+            raise ValueError("t_span needs one entry per record")
+
+    @classmethod
+    def from_records(cls, targets, with_span=True, ids=None):
+        """targets = [(target bases, [(pos, q_len, t_span, cs text)])]."""
+        tlen, t_off, rec_begin, pos, q_len, t_span, cs_off, cs_len = [], [], [0], [], [], [], [], []
+        tb, cb = [], []
+        tp = cp = 0
+        for tseq, recs in targets:
+            tlen.append(len(tseq)); t_off.append(tp); tb.append(tseq); tp += len(tseq)
+            for ps, ql, ts, cs in recs:
+                cs = cs.encode() if isinstance(cs, str) else cs
+                pos.append(ps); q_len.append(ql); t_span.append(ts); cs_off.append(cp); cs_len.append(len(cs))
+                cb.append(cs); cp += len(cs)
+            rec_begin.append(len(pos))
+        return cls(tlen, t_off, b"".join(tb), rec_begin, pos, q_len, cs_off, cs_len, b"".join(cb),
+                   t_span if with_span else None, ids)
+
+    @property
+    def n_targets(self):
+        return int(self.tlen.size)
+
+    @property
+    def n_records(self):
+        return int(self.pos.size)
+
+    @property
+    def nbytes(self):
+        """Bytes the call carries to the device: the text, the targets and the per-record / per-target arrays."""
+        arrs = [self.tlen, self.t_off, self.t_blob, self.rec_begin, self.pos, self.q_len, self.cs_off, self.cs_len, self.cs_blob]
+        return int(sum(a.nbytes for a in arrs) + (self.t_span.nbytes if self.t_span is not None else 0))
+
+    def c_struct(self) -> CsBatch:
+        b = CsBatch()
+        b.n_targets = self.n_targets
+        b.tlen = self.tlen.ctypes.data
+        b.t_off = self.t_off.ctypes.data
+        b.t_blob = self.t_blob.ctypes.data
+        b.t_bytes = self.t_blob.size
+        b.rec_begin = self.rec_begin.ctypes.data
+        b.pos = self.pos.ctypes.data
+        b.q_len = self.q_len.ctypes.data
+        b.t_span = None if self.t_span is None else self.t_span.ctypes.data
+        b.cs_off = self.cs_off.ctypes.data
+        b.cs_len = self.cs_len.ctypes.data
+        b.cs_blob = self.cs_blob.ctypes.data
+        b.cs_bytes = self.cs_blob.size
         return b
 
 
@@ -583,6 +664,24 @@ class Context:
             self._chk(self.L.dagcon_consensus_cigar_packed(self.h, C.byref(b), C.byref(w), C.byref(r)))
         else:
             self._chk(self.L.dagcon_consensus_cigar_windows(self.h, C.byref(b), C.byref(w), C.byref(r)))
+        out = self._keep_segs(r)
+        self._status(r, strict)
+        return out
+
+    def upload_cs(self, batch: HostCsBatch, windows: HostWindows = None):
+        """dagcon_upload_cs: then run / sync / fetch as after upload (with windows: one result target per window)."""
+        self._keep = (batch, windows)
+        b = batch.c_struct()
+        w = windows.c_struct() if windows is not None else None
+        self._chk(self.L.dagcon_upload_cs(self.h, C.byref(b), C.byref(w) if w is not None else None))
+
+    def consensus_cs(self, batch: HostCsBatch, windows: HostWindows = None, strict=True):
+        """Per target (per window with windows): [(range0, range1, seq_bytes)], from cs:Z: text decoded on the device."""
+        self._keep = (batch, windows)
+        b = batch.c_struct()
+        w = windows.c_struct() if windows is not None else None
+        r = Results()
+        self._chk(self.L.dagcon_consensus_cs(self.h, C.byref(b), C.byref(w) if w is not None else None, C.byref(r)))
         out = self._keep_segs(r)
         self._status(r, strict)
         return out

@@ -25,6 +25,7 @@
 #include "k_align_panels.hip.h"
 #include "k_place.hip.h"
 #include "k_cigar.hip.h"
+#include "k_cs.hip.h"
 
 namespace {
 
@@ -131,6 +132,7 @@ struct Ctx {
     DevBuf d_al[15];                                // dagcon_align: blobs, offsets, outputs, directions, launch order, widths, ends
     DevBuf d_pn[18];                                // dagcon_align_panels: blobs, panels, scratch, outputs, launch order
     DevBuf d_pl[14];                                // dagcon_place: blob, sequences, tables, pairs, outputs
+    DevBuf d_cs[10];                                // dagcon_upload_cs: the text, its offsets, the scan's totals, what k_cs_write takes
     DevBuf d_cg[18];                                // dagcon_upload_cigar: ops, op / tile begins, totals, checkpoints, blobs, offsets
     std::vector<uint8_t> h_cig_bad;                 // dagcon_upload_cigar: targets with a non-conforming record (empty: another upload)
     std::string cig_err;                            // the first of them, for dagcon_last_error
@@ -546,6 +548,7 @@ void dagcon_destroy(dagcon_ctx *ctx) {
     for (DevBuf &b : c->d_pn) free_buf(b);
     for (DevBuf &b : c->d_pl) free_buf(b);
     for (DevBuf &b : c->d_cg) free_buf(b);
+    for (DevBuf &b : c->d_cs) free_buf(b);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1645,8 +1648,16 @@ namespace {
 // what dagcon_upload_cigar and dagcon_upload_cigar_windows share: the checks of the batch, its upload, k_cigar_scan and
 // the totals back on the host (tot: columns, read bases, target bases, DG_CG_* flags per record); p is left ready for
 // an expansion but for its offsets.  packed: q_blob holds two bases a byte (dagcon_upload_cigar_packed), a record
-// takes (q_len + 1) / 2 bytes of it from q_off
-int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, bool packed, DgCigarParams &p, std::vector<uint64_t> &tile_begin, std::vector<uint32_t> &tot) {
+// takes (q_len + 1) / 2 bytes of it from q_off.  cs (dagcon_upload_cs): the ops, the reads and the targets are on the
+// device already (d_cg[0], [5], [6], made by k_cs_write), b->ops and b->q_blob are NULL and b->q_off is the host's
+// prefix sum of q_len; the scan's totals must then be those of k_cs_scan for every conforming record, and the caller
+// gets k_cs_scan's (they hold the spans of the records that are not)
+struct CsDecoded {
+    std::vector<const char *> why;                                 // per record: nullptr: conforming
+    std::vector<uint32_t> tot;                                     // per record, as tot below
+};
+int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, bool packed, DgCigarParams &p, std::vector<uint64_t> &tile_begin, std::vector<uint32_t> &tot,
+               const CsDecoded *cs = nullptr) {
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->rec_begin || !b->t_off)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
     const uint64_t n64 = T ? b->rec_begin[T] : 0;
@@ -1664,11 +1675,11 @@ int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, bool packed, DgCigarParams &
         if (b->op_begin[a + 1] < b->op_begin[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "op_begin not monotone at record %u", a);
         const uint64_t qb = packed ? ((uint64_t)b->q_len[a] + 1u) / 2u : b->q_len[a];
         if (b->q_off[a] > b->q_bytes || qb > b->q_bytes - b->q_off[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "record %u runs past q_blob", a);
-        if (b->q_len[a] && !b->q_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "q_blob is NULL");
+        if (b->q_len[a] && !b->q_blob && !cs) return fail(c, DAGCON_ERR_INVALID_ARG, "q_blob is NULL");
         tile_begin[a + 1] = tile_begin[a] + (b->op_begin[a + 1] - b->op_begin[a] + 63u) / 64u;
     }
     const uint64_t n_ops = n ? b->op_begin[n] - b->op_begin[0] : 0, n_tiles = tile_begin[n];
-    if (n_ops && !b->ops) return fail(c, DAGCON_ERR_INVALID_ARG, "ops is NULL");
+    if (n_ops && !b->ops && !cs) return fail(c, DAGCON_ERR_INVALID_ARG, "ops is NULL");
     if (n_tiles > 0x7FFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many CIGAR ops");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
@@ -1679,9 +1690,9 @@ int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, bool packed, DgCigarParams &
     for (uint32_t a = 0; a <= n && n; a++) opb[a] = b->op_begin[a] - b->op_begin[0];
     ENSURE(c, d_ops, n_ops * 4); ENSURE(c, d_tot, (size_t)n * 16); ENSURE(c, d_ck, n_tiles * 16);
     ENSURE(c, d_qb, b->q_bytes); ENSURE(c, d_tb, b->t_bytes); ENSURE(c, d_qoff, (size_t)n * 8);
-    if (n_ops) HIPCHK(c, hipMemcpyAsync(d_ops.p, b->ops + b->op_begin[0], n_ops * 4, hipMemcpyHostToDevice, s));
+    if (n_ops && !cs) HIPCHK(c, hipMemcpyAsync(d_ops.p, b->ops + b->op_begin[0], n_ops * 4, hipMemcpyHostToDevice, s));
     if (b->q_bytes && b->q_blob) HIPCHK(c, hipMemcpyAsync(d_qb.p, b->q_blob, b->q_bytes, hipMemcpyHostToDevice, s));
-    if (b->t_bytes && b->t_blob) HIPCHK(c, hipMemcpyAsync(d_tb.p, b->t_blob, b->t_bytes, hipMemcpyHostToDevice, s));
+    if (b->t_bytes && b->t_blob && !cs) HIPCHK(c, hipMemcpyAsync(d_tb.p, b->t_blob, b->t_bytes, hipMemcpyHostToDevice, s));
     if (n) HIPCHK(c, hipMemcpyAsync(d_qoff.p, b->q_off, (size_t)n * 8, hipMemcpyHostToDevice, s));
     int r;
     if ((r = upload_vec(c, d_opb, opb))) return r;
@@ -1697,11 +1708,19 @@ int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, bool packed, DgCigarParams &
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, d2h(c, tot.data(), d_tot.p, (size_t)n * 16));
     }
+    if (cs) {
+        for (uint32_t a = 0; a < n; a++)
+            if (!cs->why[a] && memcmp(&tot[(size_t)a * 4], &cs->tot[(size_t)a * 4], 16) != 0)
+                return fail(c, DAGCON_ERR_INTERNAL, "k_cs_write: the ops of record %u sum to %u columns, %u read bases, %u target bases, flags %u; k_cs_scan said %u, %u, %u", a,
+                            tot[(size_t)a * 4], tot[(size_t)a * 4 + 1], tot[(size_t)a * 4 + 2], tot[(size_t)a * 4 + 3], cs->tot[(size_t)a * 4], cs->tot[(size_t)a * 4 + 1], cs->tot[(size_t)a * 4 + 2]);
+        tot = cs->tot;
+    }
     return DAGCON_OK;
 }
 
 // why a record is non-conforming (include/dagcon.h), nullptr if it conforms
-const char *cigar_why(const dagcon_cigar_batch *b, const std::vector<uint32_t> &tot, uint32_t g, uint64_t a) {
+const char *cigar_why(const dagcon_cigar_batch *b, const std::vector<uint32_t> &tot, uint32_t g, uint64_t a, const CsDecoded *cs = nullptr) {
+    if (cs) return cs->why[a];
     const uint32_t nq = tot[a * 4 + 1], nt = tot[a * 4 + 2], fl = tot[a * 4 + 3];
     return (fl & DG_CG_BAD_OP) ? "an op code above 8 or N"
          : (fl & DG_CG_ZERO_LEN) ? "an op of length 0"
@@ -1730,7 +1749,7 @@ extern "C" {
 // upload_impl takes them from there (the door dagcon_consensus_pre uses)
 }  // extern "C"
 namespace {
-int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed, const uint8_t *reverse = nullptr) {
+int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed, const uint8_t *reverse = nullptr, const CsDecoded *cs = nullptr) {
     if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
@@ -1740,7 +1759,7 @@ int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed, cons
     DgCigarParams p;
     std::vector<uint64_t> tile_begin;
     std::vector<uint32_t> tot;
-    int r = cigar_scan(c, b, packed, p, tile_begin, tot);
+    int r = cigar_scan(c, b, packed, p, tile_begin, tot, cs);
     if (r != DAGCON_OK) return r;
     const uint64_t n_tiles = tile_begin[n];
     hipStream_t s = c->stream;
@@ -1750,7 +1769,7 @@ int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed, cons
     std::string first_err;
     for (uint32_t g = 0; g < T; g++)
         for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
-            const char *why = cigar_why(b, tot, g, a);
+            const char *why = cigar_why(b, tot, g, a, cs);
             if (!why) continue;
             if (first_err.empty()) {
                 char buf[256];
@@ -1805,7 +1824,8 @@ int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed, cons
 // cut).  After the scan's totals the host knows every record's [s, e) and lists the (record, window) pieces; k_cigar_cut
 // turns each piece's two target coordinates into columns and tiles, the host plans the output from those, and
 // k_cigar_expand_cut writes every piece from the one device copy of the record's ops and bases.
-int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, bool packed, const uint8_t *reverse = nullptr) {
+int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, bool packed, const uint8_t *reverse = nullptr,
+                         const CsDecoded *cs = nullptr) {
     if (!ctx || !b || !wn) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
@@ -1825,7 +1845,7 @@ int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dag
     DgCigarParams p;
     std::vector<uint64_t> tile_begin;
     std::vector<uint32_t> tot;
-    int r = cigar_scan(c, b, packed, p, tile_begin, tot);
+    int r = cigar_scan(c, b, packed, p, tile_begin, tot, cs);
     if (r != DAGCON_OK) return r;
     hipStream_t s = c->stream;
     DevBuf &d_tbase = c->d_cg[8], &d_piece = c->d_cg[10], &d_cut = c->d_cg[11], &d_wpiece = c->d_cg[12], &d_wbegin = c->d_cg[13],
@@ -1838,7 +1858,7 @@ int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dag
     std::string first_err;
     for (uint32_t g = 0; g < T; g++)
         for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
-            const char *why = cigar_why(b, tot, g, a);
+            const char *why = cigar_why(b, tot, g, a, cs);
             const uint64_t tl = b->tlen[g];
             uint64_t s0 = b->pos[a] ? b->pos[a] - 1u : 0u, e0 = s0 + tot[a * 4 + 2];
             if (why) {
@@ -1939,8 +1959,118 @@ int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dag
     return DAGCON_OK;
 }
 
+// minimap2's cs:Z: text per record, the target's bases once per target (include/dagcon.h has the rule).  k_cs_scan sizes
+// and judges every record from the raw text; the host lays the conforming records' ops out without gaps and gives every
+// record its q_len bytes of the read buffer; k_cs_write fills both on the device; from there the batch is a
+// dagcon_cigar_batch whose ops, reads and targets are device-resident (upload_cigar / upload_cigar_windows with cs)
+int upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *wn) {
+    if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    c->uploaded = c->ran = c->fetched = false;
+    c->sup_valid = c->pos_valid = false;
+    const uint32_t T = b->n_targets;
+    if (T && (!b->tlen || !b->rec_begin || !b->t_off)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
+    const uint64_t n64 = T ? b->rec_begin[T] : 0;
+    if (n64 > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many records");
+    const uint32_t n = (uint32_t)n64;
+    if (n && (!b->pos || !b->q_len || !b->cs_off || !b->cs_len)) return fail(c, DAGCON_ERR_INVALID_ARG, "record arrays are NULL");
+    if (T && b->rec_begin[0] != 0) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin does not start at 0");
+    for (uint32_t g = 0; g < T; g++) {
+        if (b->rec_begin[g + 1] < b->rec_begin[g] || b->rec_begin[g + 1] > n64) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin not monotone at target %u", g);
+        if (b->t_off[g] > b->t_bytes || b->tlen[g] > b->t_bytes - b->t_off[g]) return fail(c, DAGCON_ERR_INVALID_ARG, "target %u runs past t_blob", g);
+        if (b->tlen[g] && !b->t_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "t_blob is NULL");
+    }
+    std::vector<uint64_t> q_off((size_t)n + 1, 0);
+    for (uint32_t a = 0; a < n; a++) {
+        if (b->cs_off[a] > b->cs_bytes || b->cs_len[a] > b->cs_bytes - b->cs_off[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "record %u runs past cs_blob", a);
+        if (b->cs_len[a] && !b->cs_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "cs_blob is NULL");
+        q_off[a + 1] = q_off[a] + b->q_len[a];
+    }
+    const uint64_t q_bytes = q_off[n];
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DevBuf &d_txt = c->d_cs[0], &d_csoff = c->d_cs[1], &d_cslen = c->d_cs[2], &d_tot = c->d_cs[3], &d_nops = c->d_cs[4], &d_opb = c->d_cs[5],
+           &d_tbase = c->d_cs[6], &d_troom = c->d_cs[7], &d_qoff = c->d_cs[8], &d_qlen = c->d_cs[9];
+    DevBuf &d_ops = c->d_cg[0], &d_qb = c->d_cg[5], &d_tb = c->d_cg[6];     // where cigar_scan looks for them
+    ENSURE(c, d_txt, b->cs_bytes); ENSURE(c, d_csoff, (size_t)n * 8); ENSURE(c, d_cslen, (size_t)n * 4);
+    ENSURE(c, d_tot, (size_t)n * 16); ENSURE(c, d_nops, (size_t)n * 4); ENSURE(c, d_tb, b->t_bytes); ENSURE(c, d_qb, q_bytes);
+    if (b->cs_bytes && b->cs_blob) HIPCHK(c, hipMemcpyAsync(d_txt.p, b->cs_blob, b->cs_bytes, hipMemcpyHostToDevice, s));
+    if (b->t_bytes && b->t_blob) HIPCHK(c, hipMemcpyAsync(d_tb.p, b->t_blob, b->t_bytes, hipMemcpyHostToDevice, s));
+    DgCsParams p;
+    memset(&p, 0, sizeof p);
+    CsDecoded cs;
+    cs.why.assign((size_t)n, nullptr);
+    cs.tot.assign((size_t)n * 4, 0);
+    std::vector<uint32_t> nops((size_t)n, 0);
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(d_csoff.p, b->cs_off, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(d_cslen.p, b->cs_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        p.cs = (const uint8_t *)d_txt.p; p.cs_off = (const uint64_t *)d_csoff.p; p.cs_len = (const uint32_t *)d_cslen.p; p.n = n;
+        p.totals = (uint4 *)d_tot.p; p.n_ops = (uint32_t *)d_nops.p;
+        hipLaunchKernelGGL(k_cs_scan, dim3((n + 3u) / 4u), dim3(256), 0, s, p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, d2h(c, cs.tot.data(), d_tot.p, (size_t)n * 16));
+        HIPCHK(c, d2h(c, nops.data(), d_nops.p, (size_t)n * 4));
+    }
+    // what every record is; the ops of the conforming ones back to back, a read of q_len bytes each
+    std::vector<uint64_t> opb((size_t)n + 1, 0), t_base((size_t)n, 0);
+    std::vector<uint32_t> t_room((size_t)n, 0);
+    for (uint32_t g = 0; g < T; g++)
+        for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
+            uint32_t *tt = &cs.tot[a * 4];
+            const uint32_t nq = tt[1], nt = tt[2], fl = tt[3];
+            const uint32_t pos = b->pos[a], tl = b->tlen[g];
+            const char *why = (fl & DG_CS_BAD_OP) ? "cs: a ~ op, or a first byte that starts no op"
+                            : (fl & DG_CS_BAD_BODY) ? "cs: an op's body is empty, holds a byte that is no letter (no digit for :), is :0, has more than 9 digits or is 2^28 or more, or a * body is not two letters"
+                            : (fl & DG_CG_OVERFLOW) ? "a total past 32 bits"
+                            : pos == 0 ? "pos is 0"
+                            : nq != b->q_len[a] ? "the cs ops do not produce exactly q_len read bases"
+                            : (b->t_span && nt != b->t_span[a]) ? "the cs ops do not consume exactly t_span target bases"
+                            : (uint64_t)pos - 1u + nt > tl ? "target bases past tlen" : nullptr;
+            if (!why && nops[a] > b->cs_len[a] / 2u)
+                return fail(c, DAGCON_ERR_INTERNAL, "k_cs_scan: record %llu has %u ops in %u bytes of text", (unsigned long long)a, nops[a], b->cs_len[a]);
+            cs.why[a] = why;
+            if (fl & (DG_CS_BAD_OP | DG_CS_BAD_BODY)) { tt[0] = 0; tt[1] = 0; tt[2] = b->t_span ? b->t_span[a] : 0u; }   // (no decoded totals: include/dagcon.h)
+            opb[a + 1] = opb[a] + (why ? 0u : nops[a]);
+            if (pos >= 1u && pos - 1u <= tl) { t_room[a] = tl - (pos - 1u); t_base[a] = b->t_off[g] + pos - 1u; }
+        }
+    const uint64_t n_ops = opb[n];
+    ENSURE(c, d_ops, n_ops * 4);
+    int r;
+    if (n_ops) {
+        if ((r = upload_vec(c, d_opb, opb))) return r;
+        if ((r = upload_vec(c, d_tbase, t_base))) return r;
+        if ((r = upload_vec(c, d_troom, t_room))) return r;
+        if ((r = upload_vec(c, d_qoff, q_off))) return r;
+        ENSURE(c, d_qlen, (size_t)n * 4);
+        HIPCHK(c, hipMemcpyAsync(d_qlen.p, b->q_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        p.op_begin = (const uint64_t *)d_opb.p; p.ops = (uint32_t *)d_ops.p;
+        p.t = (const uint8_t *)d_tb.p; p.t_base = (const uint64_t *)d_tbase.p; p.t_room = (const uint32_t *)d_troom.p;
+        p.q_off = (const uint64_t *)d_qoff.p; p.q_len = (const uint32_t *)d_qlen.p; p.q = (uint8_t *)d_qb.p;
+        hipLaunchKernelGGL(k_cs_write, dim3((n + 3u) / 4u), dim3(256), 0, s, p);
+        HIPCHK(c, hipGetLastError());
+    }
+    dagcon_cigar_batch cb;
+    memset(&cb, 0, sizeof cb);
+    cb.n_targets = T; cb.tlen = b->tlen; cb.t_off = b->t_off; cb.t_blob = b->t_blob; cb.t_bytes = b->t_bytes;
+    cb.rec_begin = b->rec_begin; cb.pos = b->pos; cb.q_off = q_off.data(); cb.q_len = b->q_len; cb.q_bytes = q_bytes;
+    cb.op_begin = opb.data();
+    r = wn ? upload_cigar_windows(ctx, &cb, wn, false, nullptr, &cs) : upload_cigar(ctx, &cb, false, nullptr, &cs);
+    if (r != DAGCON_OK) (void)hipStreamSynchronize(s);            // (the locals above may go)
+    return r;
+}
+
 }  // namespace
 extern "C" {
+
+int dagcon_upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *wn) { return upload_cs(ctx, b, wn); }
+int dagcon_consensus_cs(dagcon_ctx *ctx, const dagcon_cs_batch *batch, const dagcon_windows *windows, dagcon_results *results) {
+    if (!results) return DAGCON_ERR_INVALID_ARG;
+    int r = dagcon_upload_cs(ctx, batch, windows);
+    if (r != DAGCON_OK) return r;
+    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
+    return dagcon_fetch(ctx, results);
+}
 
 int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) { return upload_cigar(ctx, b, false); }
 int dagcon_upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn) {

@@ -1,4 +1,4 @@
-// paf.h -- what `pbdagcon --paf --ref --reads` needs of PAF text and of a reads file.
+// paf.h -- what `pbdagcon --paf --ref --reads` and `pbdagcon --paf --cs --ref` need of PAF text and of a reads file.
 //
 // A PAF line (minimap2 -c) does not carry the read: qname qlen qs qe strand tname tlen ts te nmatch alen mapq and then
 // tags name a slice [qs, qe) of a read that lies once in another file, and for a '-' line the cg:Z: CIGAR is written
@@ -11,8 +11,15 @@
 // (that order is addAln order: it is semantics).  tp:A:S lines are skipped as secondary SAM records are; lines without
 // cg:Z: are skipped and counted (aligning them is not built).  A cg that does not consume exactly te - ts target bases
 // takes its target out, with a warning that names the line, as the library takes out the target of a record whose cg
-// does not consume exactly qe - qs read bases (DAGCON_ERR_NONCONFORMING).  cs:Z:, MD:Z:, QUAL and gzip are not read.
+// does not consume exactly qe - qs read bases (DAGCON_ERR_NONCONFORMING).  MD:Z:, QUAL and gzip are not read.
 // Line ends are LF (a CR in front of it is dropped, as sam.h drops it).
+//
+// --cs (minimap2 --cs, with or without -c): the text behind cs:Z: and the target are the whole alignment, so there is no
+// reads file and the query name is not looked up; qlen, qs and qe are checked among themselves.  A record is then
+// pos = ts + 1, q_len = qe - qs, t_span = te - ts and the text, found by its tab and not looked into: the device decodes
+// it (dagcon_upload_cs in include/dagcon.h) and takes out the target of a record whose text does not give exactly q_len
+// read bases and t_span target bases.  The text is in the target's orientation: the strand is carried for printing only.
+// Lines without cs:Z: are skipped and counted.  dg_cs_decode serves --dump-parsed only.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -37,6 +44,46 @@ inline std::string dg_paf_revcomp(const char *s, size_t n) {
     std::string out(n, 0);
     for (size_t i = 0; i < n; i++) out[i] = dg_paf_comp(s[n - 1 - i]);
     return out;
+}
+
+// for printing only (--dump-parsed): the read and the ops of a cs text by the rule of include/dagcon.h, against the target's
+// bases t[0, tlen) from pos; false when the text breaks the grammar or runs past the target
+inline bool dg_cs_decode(const char *cs, size_t n, const char *t, size_t tlen, uint32_t pos, std::string &read, std::vector<uint32_t> &ops) {
+    auto isop = [](char c) { return c == ':' || c == '*' || c == '+' || c == '-' || c == '=' || c == '~'; };
+    auto letter = [](char c) { return (unsigned)((c & 0xDF) - 'A') < 26u; };
+    auto upper = [](char c) { return (char)(c >= 'a' && c <= 'z' ? c - 32 : c); };
+    read.clear(); ops.clear();
+    if (pos == 0) return false;
+    size_t ti = pos - 1u;
+    for (size_t i = 0; i < n;) {
+        const char op = cs[i];
+        if (!isop(op) || op == '~') return false;
+        size_t j = i + 1;
+        while (j < n && !isop(cs[j])) j++;
+        const size_t len = j - i - 1;
+        if (len == 0) return false;
+        if (op == ':') {
+            uint64_t v = 0;
+            if (len > 9) return false;
+            for (size_t k = i + 1; k < j; k++) { if (cs[k] < '0' || cs[k] > '9') return false; v = v * 10 + (uint64_t)(cs[k] - '0'); }
+            if (v == 0 || v >= (1u << 28) || ti + v > tlen) return false;
+            read.append(t + ti, (size_t)v); ti += (size_t)v;
+            ops.push_back((uint32_t)v << 4 | 7u);
+        } else {
+            for (size_t k = i + 1; k < j; k++) if (!letter(cs[k])) return false;
+            if (op == '*') {
+                if (len != 2) return false;
+                read += upper(cs[i + 2]); ti += 1;
+                ops.push_back(1u << 4 | 8u);
+            } else {
+                if (op != '-') for (size_t k = i + 1; k < j; k++) read += upper(cs[k]);
+                if (op != '+') ti += len;
+                ops.push_back((uint32_t)len << 4 | (op == '=' ? 7u : op == '+' ? 1u : 2u));
+            }
+        }
+        i = j;
+    }
+    return ti <= tlen;
 }
 
 // reads a four-line FASTQ file: the names (first word of the @ line) and the bases; QUAL is not read
@@ -101,13 +148,15 @@ struct DgPafRec {
     const char *q; uint32_t q_len;                         // the slice [qs, qe) as the reads file has it
     const char *read; uint32_t read_len, qs;               // the whole read (--dump-parsed)
     bool reverse;
-    const char *cg; uint32_t cg_len, nops;                 // the text behind cg:Z:
+    const char *cg; uint32_t cg_len, nops;                 // the text behind cg:Z: (--cs: behind cs:Z:, nops 0)
+    uint32_t t_span;                                       // te - ts
     DgRefSeqs::Span tspan;                                 // the target in --ref
     unsigned long long line;
 };
 
 struct DgPafInput {
     DgRefSeqs reads;
+    bool cs = false;                                       // --cs: the cs:Z: tag instead of cg:Z: and a reads file
     std::vector<DgPafRec> recs;                            // grouped: targets in --ref order, file order inside a target
     unsigned long long n_secondary = 0, n_nocg = 0;
 
@@ -153,7 +202,7 @@ struct DgPafInput {
             while (more && i <= ll) {
                 const char *tab = (const char *)memchr(line + i, '\t', ll - i);
                 const size_t j = tab ? (size_t)(tab - line) : ll;
-                if (j - i >= 5 && memcmp(line + i, "cg:Z:", 5) == 0) { cg = line + i + 5; cgl = j - i - 5; }
+                if (j - i >= 5 && memcmp(line + i, cs ? "cs:Z:" : "cg:Z:", 5) == 0) { cg = line + i + 5; cgl = j - i - 5; }
                 if (j - i == 6 && memcmp(line + i, "tp:A:S", 6) == 0) secondary = true;
                 if (!tab) break;
                 i = j + 1;
@@ -167,12 +216,28 @@ struct DgPafInput {
                 return fail("a length or a coordinate is not an unsigned 32-bit number");
             if (qs >= qe || qe > qlen) return fail("query slice [" + std::to_string(qs) + ", " + std::to_string(qe) + ") is empty or runs past the query length " + std::to_string(qlen));
             if (ts > te || te > tlen) return fail("target range [" + std::to_string(ts) + ", " + std::to_string(te) + ") is reversed or runs past the target length " + std::to_string(tlen));
-            const DgRefSeqs::Span *rd = reads.find(f[0], fl[0]);
-            if (!rd) return fail("query " + std::string(f[0], fl[0]) + " is not a sequence of --reads");
+            const DgRefSeqs::Span *rd = cs ? nullptr : reads.find(f[0], fl[0]);
+            if (!rd && !cs) return fail("query " + std::string(f[0], fl[0]) + " is not a sequence of --reads");
             const DgRefSeqs::Span *tg = ref.find(f[5], fl[5]);
             if (!tg) return fail("target " + std::string(f[5], fl[5]) + " is not a sequence of --ref");
-            if (qlen != rd->len) return fail("query " + std::string(f[0], fl[0]) + " has length " + std::to_string(qlen) + " here but " + std::to_string(rd->len) + " bases in --reads");
+            if (!cs && qlen != rd->len) return fail("query " + std::string(f[0], fl[0]) + " has length " + std::to_string(qlen) + " here but " + std::to_string(rd->len) + " bases in --reads");
             if (tlen != tg->len) return fail("target " + std::string(f[5], fl[5]) + " has length " + std::to_string(tlen) + " here but " + std::to_string(tg->len) + " bases in --ref");
+            if (cs) {                                      // the text is not looked into: the device decodes and judges it
+                if (cgl > 0xFFFFFFFFull) return fail("the cs:Z: tag is too long");
+                DgPafRec r;
+                r.tname = f[5]; r.tname_len = (uint32_t)fl[5];
+                r.qname = f[0]; r.qname_len = (uint32_t)fl[0];
+                r.pos = (uint32_t)ts + 1u;
+                r.read = nullptr; r.read_len = 0; r.qs = (uint32_t)qs;
+                r.q = nullptr; r.q_len = (uint32_t)(qe - qs);
+                r.reverse = f[4][0] == '-';
+                r.cg = cg; r.cg_len = (uint32_t)cgl; r.nops = 0;
+                r.t_span = (uint32_t)(te - ts);
+                r.tspan = *tg;
+                r.line = lineno;
+                recs.push_back(r);
+                continue;
+            }
             // the CIGAR through sam.h's parser; the target bases it consumes against te - ts
             std::vector<uint32_t> ops;
             const long k = dg_cigar_ops(cg, cgl, nullptr);
@@ -196,6 +261,7 @@ struct DgPafInput {
             r.q = r.read + qs; r.q_len = (uint32_t)(qe - qs);
             r.reverse = f[4][0] == '-';
             r.cg = cg; r.cg_len = (uint32_t)cgl; r.nops = (uint32_t)k;
+            r.t_span = (uint32_t)(te - ts);
             r.tspan = *tg;
             r.line = lineno;
             recs.push_back(r);
@@ -209,7 +275,8 @@ struct DgPafInput {
             const int c = memcmp(a.tname, b.tname, std::min(a.tname_len, b.tname_len));
             return c ? c < 0 : a.tname_len < b.tname_len;
         });
-        if (n_nocg) fprintf(stderr, "pbdagcon: %llu PAF lines without a cg:Z: tag skipped (run minimap2 with -c)\n", n_nocg);
+        if (n_nocg && cs) fprintf(stderr, "pbdagcon: %llu PAF lines without a cs:Z: tag skipped (run minimap2 with --cs)\n", n_nocg);
+        else if (n_nocg) fprintf(stderr, "pbdagcon: %llu PAF lines without a cg:Z: tag skipped (run minimap2 with -c)\n", n_nocg);
         return true;
     }
 };
@@ -218,6 +285,7 @@ struct DgPafInput {
 struct DgPafSource {
     static constexpr bool packed = false;
     static constexpr bool stranded = true;
+    static constexpr bool cs = false;
     static constexpr const char *unit = "line";
     static constexpr const char *skipped_what = "PAF lines skipped (tp:A:S)";
     const DgPafInput &in;
@@ -235,6 +303,31 @@ struct DgPafSource {
         r.where = p.line;
         ops.resize(ops.size() + p.nops);
         dg_cigar_ops(p.cg, p.cg_len, ops.data() + ops.size() - p.nops);
+        return 1;
+    }
+};
+
+// the same for --cs: q is the record's cs text (cs_len bytes), q_len the read bases it claims, no ops
+struct DgPafCsSource {
+    static constexpr bool packed = false;
+    static constexpr bool stranded = false;
+    static constexpr bool cs = true;
+    static constexpr const char *unit = "line";
+    static constexpr const char *skipped_what = "PAF lines skipped (tp:A:S)";
+    const DgPafInput &in;
+    size_t at = 0;
+    unsigned long long skipped;
+    DgPafCsSource(const DgPafInput &i, const DgRefSeqs &) : in(i), skipped(i.n_secondary) {}
+    template <class AlnRec>
+    int next(AlnRec &r, std::vector<uint32_t> &) {
+        if (at >= in.recs.size()) return 0;
+        const DgPafRec &p = in.recs[at++];
+        r.rname = p.tname; r.rname_len = p.tname_len;
+        r.pos = p.pos;
+        r.q = p.cg; r.q_len = p.q_len; r.nops = 0;
+        r.cs_len = p.cg_len; r.t_span = p.t_span;
+        r.reverse = false;
+        r.where = p.line;
         return 1;
     }
 };

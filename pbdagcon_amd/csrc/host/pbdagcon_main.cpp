@@ -21,6 +21,8 @@
 //     gapped strings are made on the GPU (dagcon_consensus_cigar), never on the host (sam.h);
 //   * --bam --ref: the same from BAM (bam.h: BGZF, inflate and the records); the CIGAR ops and the 4-bit SEQ go to the
 //     GPU as they lie in the file (dagcon_consensus_cigar_packed), the output is that of --sam on the same records;
+//   * --paf --cs --ref: PAF lines with a cs:Z: tag (minimap2 --cs) and no reads file: the tag's text goes to the device as it
+//     lies in the file and is decoded there (dagcon_consensus_cs); the host finds the tag by its tab and reads no base
 //   * --paf --ref --reads: PAF lines with a cg:Z: CIGAR (minimap2 -c), the reads from a FASTA / FASTQ file (paf.h); a line's
 //     slice of its read goes to the GPU as the reads file has it, with one strand flag per record, and the GPU reads a
 //     '-' record's bases backwards and complemented (dagcon_consensus_cigar_strand); the output is that of --sam on the
@@ -65,6 +67,7 @@ struct Opts {
                                        // strand of a record is applied on the device
     std::string ref;                   // --ref FASTA
     std::string reads;                 // --reads FASTA / FASTQ (with --paf)
+    bool cs = false;                   // --cs (with --paf): the lines' cs:Z: text instead of cg:Z: and --reads, decoded on the device
     unsigned window = 0, overlap = 1000;   // --window W [--overlap O] (with --sam): targets cut into windows (windows.h)
     bool overlap_set = false;
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
@@ -81,7 +84,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --paf --ref <fasta> --reads <fasta|fastq> [--window W [--overlap O]]] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]]] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -114,7 +117,16 @@ void usage(FILE *f) {
             "                      a target's lines in file order (with --window: ascending in ts).  tp:A:S lines are skipped\n"
             "                      (counted with -v); lines without cg:Z: are skipped and their count is printed.  A line\n"
             "                      whose lengths disagree with the files, or that names an unknown sequence, is an error.\n"
-            "                      Not with --sam, --bam, -a, --local or --polish.  cs:Z:, MD:Z:, QUAL and gzip are not read\n"
+            "                      Not with --sam, --bam, -a, --local or --polish.  MD:Z:, QUAL and gzip are not read\n"
+            "  --cs                with --paf, instead of --reads: the lines carry cs:Z: tags (minimap2 --cs, short or long form,\n"
+            "                      with or without -c).  A cs:Z: tag and the target are the whole alignment: there is no reads\n"
+            "                      file, the query name is not looked up, and a '-' line needs nothing done to it.  The tag's\n"
+            "                      text goes to the GPU as it lies in the file and is decoded there (:n copies the target's\n"
+            "                      bytes, =SEQ *tq +SEQ give upper-cased read bases, -SEQ none; ~ is not taken: this build's own\n"
+            "                      rule, parity unpinned).  A line whose text does not give qe - qs read bases and te - ts target\n"
+            "                      bases, or breaks the grammar, takes its target (with --window: the windows it touches) out\n"
+            "                      with a warning.  Lines without cs:Z: are skipped and their count is printed.  Everything\n"
+            "                      else is as with --paf --reads.  Not with --reads, --sam, --bam, -a, --local or --polish\n"
             "  --reads FILE        with --paf (required): the reads, FASTA (multi-line) or four-line FASTQ by the first byte,\n"
             "                      named by the first word of the header; a name that occurs twice is an error\n"
             "  --ref FASTA         with --sam, --bam or --paf (required): the target sequences, by the name up to the first blank; an @SQ line\n"
@@ -172,6 +184,7 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--sam") o.sam = true;
         else if (a == "--bam") o.bam = true;
         else if (a == "--paf") o.paf = true;
+        else if (a == "--cs") o.cs = true;
         else if (a == "--reads") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --reads needs a FASTA or FASTQ file\n"); return 2; }
             o.reads = argv[++i];
@@ -211,10 +224,13 @@ int parse_args(int argc, char **argv, Opts &o) {
         } else { fprintf(stderr, "PARSE ERROR: unknown argument %s\n", a.c_str()); return 2; }
     }
     if (o.local && !o.align) { fprintf(stderr, "PARSE ERROR: --local needs -a\n"); return 2; }
+    if (o.cs && !o.paf) { fprintf(stderr, "PARSE ERROR: --cs needs --paf\n"); return 2; }
+    if (o.cs && !o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --cs does not go with --reads (a cs:Z: tag and --ref are the whole alignment)\n"); return 2; }
+    if (o.cs && (o.sam || o.bam || o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --cs does not go with --sam, --bam, -a, --local or --polish\n"); return 2; }
     if (o.paf && (o.sam || o.bam)) { fprintf(stderr, "PARSE ERROR: --paf does not go with --sam or --bam\n"); return 2; }
     if (o.paf && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --paf does not go with -a, --local or --polish\n"); return 2; }
     if (o.paf && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --paf needs --ref <fasta>\n"); return 2; }
-    if (o.paf && o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --paf needs --reads <fasta|fastq>\n"); return 2; }
+    if (o.paf && !o.cs && o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --paf needs --reads <fasta|fastq>\n"); return 2; }
     if (!o.paf && !o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --reads needs --paf\n"); return 2; }
     if (o.paf) o.sam = true;                               // (records with a CIGAR, as below)
     if (o.bam && o.sam) { fprintf(stderr, "PARSE ERROR: --bam and --sam do not go together\n"); return 2; }
@@ -286,13 +302,14 @@ struct Batch {
     std::vector<uint32_t> tlen, start, len, len2;          // len2 / off2: the target sequence of a .pre record
     std::vector<uint64_t> begin{0}, off, off2;
     std::vector<char> strand;
+    std::vector<uint32_t> tspan;                           // --cs: te - ts of each record (len: qe - qs; off / len2: its text in q)
     std::vector<uint64_t> toff, opb{0};                    // --sam: the target's bases in t (per target); first op of each record
     std::vector<const char *> tsrc;                        // --sam: where the target's bases come from (per target)
     std::vector<uint32_t> ops;                             // --sam: BAM-encoded CIGAR ops of all records
     Blob q, t;
     unsigned long long seq = 0;        // position in the input: records are printed in this order
     std::string out;                   // the batch's FASTA records
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); q.n = 0; t.n = 0; out.clear(); }
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); tspan.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); q.n = 0; t.n = 0; out.clear(); }
 };
 
 bool g_timing = false;                                    // PBDAGCON_TIMING
@@ -319,7 +336,19 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
     dagcon_results r;
     int rc = DAGCON_OK;
     bool have_results = false;
-    if (o.sam) {
+    if (o.cs) {
+        // position + cs text per record, the target's bases once: decoded and expanded on the device
+        dagcon_cs_batch sb;
+        memset(&sb, 0, sizeof sb);
+        sb.n_targets = db.n_targets; sb.tlen = b.tlen.data(); sb.t_off = b.toff.data();
+        sb.t_blob = b.t.data(); sb.t_bytes = b.t.size(); sb.rec_begin = b.begin.data();
+        sb.pos = b.start.data(); sb.q_len = b.len.data(); sb.t_span = b.tspan.data();
+        sb.cs_off = b.off.data(); sb.cs_len = b.len2.data(); sb.cs_blob = b.q.data(); sb.cs_bytes = b.q.size();
+        const double ta0 = wall();
+        rc = dagcon_consensus_cs(ctx, &sb, nullptr, &r);
+        if (g_timing) fprintf(stderr, "pbdagcon timing: --paf --cs batch of %zu records: dagcon_consensus_cs %.3f\n", b.start.size(), wall() - ta0);
+        have_results = true;
+    } else if (o.sam) {
         // position + read + CIGAR per record, the target's bases once: expanded on the device
         dagcon_cigar_batch cb;
         memset(&cb, 0, sizeof cb);
@@ -527,7 +556,8 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
         // AlnGraphBoost.cpp:71-72): warn, go on with the rest
         if (r.target_status[g] != DAGCON_OK)
             fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(),
-                    r.target_status[g] == DAGCON_ERR_NONCONFORMING && o.sam ? "a record's CIGAR does not fit its SEQ or its target, or holds N or a length of 0"
+                    r.target_status[g] == DAGCON_ERR_NONCONFORMING && o.cs ? "a line's cs:Z: text breaks the grammar or does not fit its qe - qs, its te - ts or its target"
+                    : r.target_status[g] == DAGCON_ERR_NONCONFORMING && o.sam ? "a record's CIGAR does not fit its SEQ or its target, or holds N or a length of 0"
                     : r.target_status[g] == DAGCON_ERR_NONCONFORMING ? "an alignment leaves the backbone or holds a non-printable byte"
                     : r.target_status[g] == DAGCON_ERR_UNSUPPORTED ? "too large" : "internal error");
         for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
@@ -620,7 +650,8 @@ int main(int argc, char **argv) {
     DgPafInput paf;
     if (o.paf) {
         std::string err;
-        if (!dg_read_reads(o.reads, paf.reads, err) || !paf.parse(data, size, ref, err)) {
+        paf.cs = o.cs;
+        if ((!o.cs && !dg_read_reads(o.reads, paf.reads, err)) || !paf.parse(data, size, ref, err)) {
             fprintf(stderr, "pbdagcon: %s\n", err.c_str());
             return 1;
         }
@@ -629,6 +660,7 @@ int main(int argc, char **argv) {
     if (o.window && !o.dump) {
         DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0]};
         if (o.bam) { DgBamSource src(bam, ref); return dg_run_windows(wo, src, ref); }
+        if (o.cs) { DgPafCsSource src(paf, ref); return dg_run_windows(wo, src, ref); }
         if (o.paf) { DgPafSource src(paf, ref); return dg_run_windows(wo, src, ref); }
         DgSamSource src(data, size, ref);
         return dg_run_windows(wo, src, ref);
@@ -765,6 +797,7 @@ int main(int argc, char **argv) {
                                                      // --bam: the ops themselves, q the 4-bit seq field, len its bases
         unsigned long long line;                     // --sam: line of the input; --bam: ordinal of the record
         const char *read; uint32_t read_len, qs;     // --paf: the whole read and where the slice q begins in it (--dump-parsed)
+        uint32_t tspan;                              // --paf --cs: te - ts (cg / cgl: the cs text, q none, len = qe - qs)
     };
     struct Part { std::vector<Rec> recs; int err = 0; unsigned long long err_rec = 0; int err_nf = 0; unsigned long long lines = 0, skipped = 0; };
     unsigned long long n_lines_before = 0, n_skipped = 0;
@@ -829,6 +862,7 @@ int main(int argc, char **argv) {
             r.cg = p.cg; r.cgl = p.cg_len; r.nops = p.nops;
             r.line = p.line;
             r.read = p.read; r.read_len = p.read_len; r.qs = p.qs;
+            r.tspan = p.t_span;
             pt.recs.push_back(r);
         }
         n_skipped = paf.n_secondary;
@@ -977,7 +1011,9 @@ int main(int argc, char **argv) {
             for (size_t x = r0 + k; x < r1; x += nthr) {
                 const Rec &r = *recs[x];
                 char *dq = b.q.data() + b.off[x - r0], *dt = b.t.data() + b.off2[x - r0];
-                if (o.bam) {                                      // the seq field and the ops as they lie in the record
+                if (o.cs) {                                       // the text behind cs:Z: as it lies in the line
+                    memcpy(dq, r.cg, r.cgl);
+                } else if (o.bam) {                                      // the seq field and the ops as they lie in the record
                     memcpy(dq, r.q, ((size_t)r.len + 1) / 2);
                     memcpy(b.ops.data() + b.opb[x - r0], r.cg, r.cgl);
                 } else if (o.sam) {                               // SEQ as it is; the CIGAR as BAM-encoded ops
@@ -1045,6 +1081,16 @@ int main(int argc, char **argv) {
                                        dg_cigar_text(b.ops.data() + b.opb[y - rb], b.opb[y - rb + 1] - b.opb[y - rb]).c_str());
                                 continue;
                             }
+                            if (o.cs) {
+                                // what --sam prints for the equivalent SAM record: SEQ the decoded read, the CIGAR the decoded
+                                // = X I D ops (decoded on the host for printing only)
+                                std::string seq;
+                                std::vector<uint32_t> dops;
+                                if (!dg_cs_decode(b.q.data() + o0, r.cgl, r.t, r.tlen, r.start, seq, dops)) { seq = "*"; dops.clear(); }
+                                printf("%.*s\t%u\t%u\t%c\t%.*s\t%s\t%s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
+                                       (int)r.namel, r.name, seq.c_str(), dg_cigar_text(dops.data(), dops.size()).c_str());
+                                continue;
+                            }
                             if (o.paf) {
                                 // what --sam prints for the equivalent SAM record: SEQ the whole read in the target's
                                 // orientation (reverse-complemented for printing only), soft clips qs and qlen - qe around
@@ -1088,9 +1134,10 @@ int main(int argc, char **argv) {
             if (o.sam) b.opb.push_back(b.opb.back() + r.nops);
             b.start.push_back(r.start);
             b.off.push_back(bytes); b.off2.push_back(bytes2);
-            b.len.push_back(r.len); b.len2.push_back(r.tl);
+            b.len.push_back(r.len); b.len2.push_back(o.cs ? r.cgl : r.tl);
             b.strand.push_back(r.strand);
-            bytes += o.bam ? ((size_t)r.len + 1) / 2 : r.len; bytes2 += r.tl;
+            if (o.cs) b.tspan.push_back(r.tspan);
+            bytes += o.cs ? r.cgl : o.bam ? ((size_t)r.len + 1) / 2 : r.len; bytes2 += r.tl;
         }
         // the unfinished target's records wait for the next slab
         std::vector<Rec> next_carry;

@@ -1,4 +1,4 @@
-// windows.h -- `pbdagcon --sam|--bam|--paf --ref F --window W [--overlap O]`: targets of any length and depth.
+// windows.h -- `pbdagcon --sam|--bam|--paf [--cs] --ref F --window W [--overlap O]`: targets of any length and depth.
 //
 // Window i of a target has the core [iW, min((i + 1)W, tlen)) and is run as [max(0, iW - O), min(tlen, (i + 1)W + O));
 // a target of at most W bases is one window.  Windows go to the device in groups of about --batch-targets
@@ -7,7 +7,8 @@
 // must be consecutive and ascending in POS, as in a coordinate-sorted SAM.  The records come from a source (DgSamSource:
 // SAM text; DgBamSource: bam.h's reader, whose reads stay in BAM's 4-bit encoding all the way to the device; DgPafSource in
 // paf.h: PAF lines grouped by target, whose reads stay as the reads file has them, with a strand flag per record that
-// the device applies); grouping, batching and the stitch do not know which.
+// the device applies; DgPafCsSource in paf.h: PAF lines with cs:Z: text and no reads at all, whose [s, e) is the line's own
+// [ts, te) and whose text goes to dagcon_consensus_cs as it is); grouping, batching and the stitch do not know which.
 //
 // The stitch (DgStitch; tests/window_twin.py: stitch is its numpy twin).  With g = pos + window begin the 1-based
 // target position of a consensus base (dagcon_fetch_positions): of a window's segment the bases from the first one
@@ -84,6 +85,7 @@ struct DgAlnRec {
     uint32_t nops;                                         // the record's ops are the last nops of `ops`
     bool reverse;                                          // stranded sources only: the ops are written against the reverse
                                                            // complement of q (dagcon_upload_cigar_strand)
+    uint32_t cs_len, t_span;                               // cs sources only: q is cs text of cs_len bytes; the target bases claimed
     unsigned long long where;                              // the line (SAM) or the record's ordinal (BAM): what an error names
 };
 
@@ -91,6 +93,7 @@ struct DgAlnRec {
 struct DgSamSource {
     static constexpr bool packed = false;
     static constexpr bool stranded = false;
+    static constexpr bool cs = false;
     static constexpr const char *unit = "line";
     static constexpr const char *skipped_what = "SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')";
     const char *data; size_t size, p = 0;
@@ -138,6 +141,7 @@ struct DgSamSource {
 struct DgBamSource {
     static constexpr bool packed = true;
     static constexpr bool stranded = false;
+    static constexpr bool cs = false;
     static constexpr const char *unit = "record";
     static constexpr const char *skipped_what = "BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)";
     DgBamReader &bam;
@@ -164,7 +168,7 @@ struct DgBamSource {
 // the whole run; the process's exit status
 template <class Source>
 inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref) {
-    struct Rec { uint32_t pos, s, e, q_len; const char *q; uint64_t op0; uint32_t nops; bool reverse; };
+    struct Rec { uint32_t pos, s, e, q_len; const char *q; uint64_t op0; uint32_t nops; bool reverse; uint32_t cs_len, t_span; };
     struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; };
     std::vector<Tgt> tgts;
     std::vector<uint32_t> ops;
@@ -187,10 +191,12 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         if (!t.recs.empty() && r.pos < t.recs.back().pos) { fprintf(stderr, "pbdagcon: %s %llu: POS %u of RNAME %s is below that of the record before it (--window needs records ascending in POS, as in a coordinate-sorted SAM)\n", Source::unit, ar.where, r.pos, rname.c_str()); return 1; }
         r.q = ar.q; r.q_len = ar.q_len; r.op0 = ops.size() - ar.nops; r.nops = ar.nops;
         r.reverse = Source::stranded && ar.reverse;
+        r.cs_len = Source::cs ? ar.cs_len : 0u; r.t_span = Source::cs ? ar.t_span : 0u;
         const long k = (long)ar.nops;
         // [s, e) by the rule of include/dagcon.h (a non-conforming record: clipped into the target, at least one base)
         uint64_t nt = 0;
         for (long i = 0; i < k; i++) { const uint32_t op = ops[r.op0 + i]; if ((1u << (op & 15u)) & 0x185u) nt += op >> 4; }
+        if (Source::cs) nt = ar.t_span;                        // (the device holds the text to it)
         const uint64_t tl = t.sp.len;
         uint64_t s0 = r.pos ? r.pos - 1u : 0u, e0 = s0 + (nt & 0xFFFFFFFFull);
         if (tl && s0 > tl - 1) s0 = tl - 1;
@@ -254,6 +260,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         std::vector<uint64_t> b_toff, b_rec{0}, b_qoff, b_opb{0};
         std::string qblob;
         std::vector<uint8_t> b_rev;                            // stranded sources: one flag per record
+        std::vector<uint32_t> b_cslen, b_tspan;                // cs sources: qblob holds the texts
         for (size_t a = w0; a < w1;) {
             size_t z = a;
             while (z < w1 && wins[z].tgt == wins[a].tgt) z++;
@@ -267,7 +274,8 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             for (; it != t.recs.end() && it->s < hi; ++it) {
                 if (it->e <= lo) continue;
                 b_pos.push_back(it->pos); b_qoff.push_back(qblob.size()); b_qlen.push_back(it->q_len);
-                qblob.append(it->q, Source::packed ? ((size_t)it->q_len + 1) / 2 : it->q_len);
+                qblob.append(it->q, Source::cs ? it->cs_len : Source::packed ? ((size_t)it->q_len + 1) / 2 : it->q_len);
+                if (Source::cs) { b_cslen.push_back(it->cs_len); b_tspan.push_back(it->t_span); }
                 b_ops.insert(b_ops.end(), ops.begin() + (long)it->op0, ops.begin() + (long)(it->op0 + it->nops));
                 b_opb.push_back(b_ops.size());
                 if (Source::stranded) b_rev.push_back(it->reverse ? 1 : 0);
@@ -285,6 +293,14 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         dagcon_windows dw;
         dw.n_windows = (uint32_t)w_t.size(); dw.target = w_t.data(); dw.begin = w_b.data(); dw.end = w_e.data();
         dagcon_results r;
+        if (Source::cs) {
+            dagcon_cs_batch sb;
+            memset(&sb, 0, sizeof sb);
+            sb.n_targets = cb.n_targets; sb.tlen = cb.tlen; sb.t_off = cb.t_off; sb.t_blob = cb.t_blob; sb.t_bytes = cb.t_bytes;
+            sb.rec_begin = cb.rec_begin; sb.pos = cb.pos; sb.q_len = cb.q_len; sb.t_span = b_tspan.data();
+            sb.cs_off = b_qoff.data(); sb.cs_len = b_cslen.data(); sb.cs_blob = qblob.data(); sb.cs_bytes = qblob.size();
+            rc = dagcon_consensus_cs(ctx, &sb, &dw, &r);
+        } else
         rc = Source::packed ? dagcon_consensus_cigar_packed(ctx, &cb, &dw, &r)
            : Source::stranded ? dagcon_consensus_cigar_strand(ctx, &cb, &dw, b_rev.data(), &r)
                               : dagcon_consensus_cigar_windows(ctx, &cb, &dw, &r);

@@ -614,77 +614,58 @@ class Context:
         self._status(r, strict)
         return out
 
+    def _intake(self, batch, windows, keep, consensus, strict=True):
+        """The one way into the record intake.  The entry point follows from the batch (cs text; CIGAR records stranded,
+        packed or plain), from windows (None: whole targets) and from consensus (False: upload only, then run / sync /
+        fetch as after upload; True: the results, per target or per window [(range0, range1, seq_bytes)])."""
+        self._keep = keep
+        b = batch.c_struct()
+        w = windows.c_struct() if windows is not None else None
+        args = [self.h, C.byref(b), C.byref(w) if w is not None else None]
+        if isinstance(batch, HostCsBatch):
+            kind = "cs"
+        elif batch.reverse is not None:
+            kind = "cigar_strand"
+            args.append(batch.reverse.ctypes.data)
+        elif batch.is_packed:
+            kind = "cigar_packed"
+        elif w is not None:
+            kind = "cigar_windows"
+        else:
+            kind = "cigar"
+            args.pop()                 # (the one entry point without a windows parameter)
+        if not consensus:
+            self._chk(getattr(self.L, "dagcon_upload_" + kind)(*args))
+            return None
+        r = Results()
+        self._chk(getattr(self.L, "dagcon_consensus_" + kind)(*args, C.byref(r)))
+        out = self._keep_segs(r)
+        self._status(r, strict)
+        return out
+
     def upload_cigar(self, batch: HostCigarBatch):
         """dagcon_upload_cigar: then run / sync / fetch as after upload."""
-        self._keep = batch
-        b = batch.c_struct()
-        if batch.reverse is not None:
-            self._chk(self.L.dagcon_upload_cigar_strand(self.h, C.byref(b), None, batch.reverse.ctypes.data))
-            return
-        if batch.is_packed:
-            self._chk(self.L.dagcon_upload_cigar_packed(self.h, C.byref(b), None))
-            return
-        self._chk(self.L.dagcon_upload_cigar(self.h, C.byref(b)))
+        self._intake(batch, None, batch, False)
 
     def consensus_cigar(self, batch: HostCigarBatch, strict=True):
         """Per target: [(range0, range1, seq_bytes)], from (position, read, CIGAR) records expanded on the device."""
-        self._keep = batch
-        b = batch.c_struct()
-        r = Results()
-        if batch.reverse is not None:
-            self._chk(self.L.dagcon_consensus_cigar_strand(self.h, C.byref(b), None, batch.reverse.ctypes.data, C.byref(r)))
-        elif batch.is_packed:
-            self._chk(self.L.dagcon_consensus_cigar_packed(self.h, C.byref(b), None, C.byref(r)))
-        else:
-            self._chk(self.L.dagcon_consensus_cigar(self.h, C.byref(b), C.byref(r)))
-        out = self._keep_segs(r)
-        self._status(r, strict)
-        return out
+        return self._intake(batch, None, batch, True, strict)
 
     def upload_cigar_windows(self, batch: HostCigarBatch, windows: HostWindows):
         """dagcon_upload_cigar_windows: then run / sync / fetch as after upload (one result target per window)."""
-        self._keep = (batch, windows)
-        b, w = batch.c_struct(), windows.c_struct()
-        if batch.reverse is not None:
-            self._chk(self.L.dagcon_upload_cigar_strand(self.h, C.byref(b), C.byref(w), batch.reverse.ctypes.data))
-            return
-        if batch.is_packed:
-            self._chk(self.L.dagcon_upload_cigar_packed(self.h, C.byref(b), C.byref(w)))
-            return
-        self._chk(self.L.dagcon_upload_cigar_windows(self.h, C.byref(b), C.byref(w)))
+        self._intake(batch, windows, (batch, windows), False)
 
     def consensus_cigar_windows(self, batch: HostCigarBatch, windows: HostWindows, strict=True):
         """Per window: [(range0, range1, seq_bytes)], the records cut to the windows on the device."""
-        self._keep = (batch, windows)
-        b, w = batch.c_struct(), windows.c_struct()
-        r = Results()
-        if batch.reverse is not None:
-            self._chk(self.L.dagcon_consensus_cigar_strand(self.h, C.byref(b), C.byref(w), batch.reverse.ctypes.data, C.byref(r)))
-        elif batch.is_packed:
-            self._chk(self.L.dagcon_consensus_cigar_packed(self.h, C.byref(b), C.byref(w), C.byref(r)))
-        else:
-            self._chk(self.L.dagcon_consensus_cigar_windows(self.h, C.byref(b), C.byref(w), C.byref(r)))
-        out = self._keep_segs(r)
-        self._status(r, strict)
-        return out
+        return self._intake(batch, windows, (batch, windows), True, strict)
 
     def upload_cs(self, batch: HostCsBatch, windows: HostWindows = None):
         """dagcon_upload_cs: then run / sync / fetch as after upload (with windows: one result target per window)."""
-        self._keep = (batch, windows)
-        b = batch.c_struct()
-        w = windows.c_struct() if windows is not None else None
-        self._chk(self.L.dagcon_upload_cs(self.h, C.byref(b), C.byref(w) if w is not None else None))
+        self._intake(batch, windows, (batch, windows), False)
 
     def consensus_cs(self, batch: HostCsBatch, windows: HostWindows = None, strict=True):
         """Per target (per window with windows): [(range0, range1, seq_bytes)], from cs:Z: text decoded on the device."""
-        self._keep = (batch, windows)
-        b = batch.c_struct()
-        w = windows.c_struct() if windows is not None else None
-        r = Results()
-        self._chk(self.L.dagcon_consensus_cs(self.h, C.byref(b), C.byref(w) if w is not None else None, C.byref(r)))
-        out = self._keep_segs(r)
-        self._status(r, strict)
-        return out
+        return self._intake(batch, windows, (batch, windows), True, strict)
 
     def timings(self) -> dict:
         t = Timings()

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <string>
 #include <chrono>
+#include <array>
 #include <vector>
 
 #include "../../include/dagcon.h"
@@ -33,6 +34,25 @@ struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
 };
+
+// the device buffers of the record intake, by name; all() is what dagcon_destroy frees
+struct CigarBufs {
+    DevBuf ops, op_begin, tile_begin, totals, ckpt;                // the records' ops, k_cigar_scan's output
+    DevBuf q, t, q_off, t_base;                                    // the blobs and where each record's bases begin
+    DevBuf out_off;                                                // whole targets: where each record's strings go
+    DevBuf piece, cut, wave_piece, wave_begin, piece_out;          // windows: DgCigarCutParams
+    DevBuf rev, q_len;                                             // DgCigarStrand
+    std::array<DevBuf *, 17> all() {
+        return {&ops, &op_begin, &tile_begin, &totals, &ckpt, &q, &t, &q_off, &t_base, &out_off, &piece, &cut, &wave_piece, &wave_begin, &piece_out, &rev, &q_len};
+    }
+};
+static_assert(sizeof(CigarBufs) == 17 * sizeof(DevBuf), "CigarBufs::all() must name every member");
+// dagcon_upload_cs: the text and what k_cs_scan / k_cs_write take besides CigarBufs::ops, q and t, which k_cs_write fills
+struct CsBufs {
+    DevBuf text, cs_off, cs_len, totals, n_ops, op_begin, t_base, t_room, q_off, q_len;
+    std::array<DevBuf *, 10> all() { return {&text, &cs_off, &cs_len, &totals, &n_ops, &op_begin, &t_base, &t_room, &q_off, &q_len}; }
+};
+static_assert(sizeof(CsBufs) == 10 * sizeof(DevBuf), "CsBufs::all() must name every member");
 
 // ---- how many pieces the merge / bestPath sweeps of a batch are cut into (host arithmetic only: exported as
 // dagcon_debug_plan so that a CPU test can sweep it; every grid size derived from it is > 0) ----
@@ -132,8 +152,8 @@ struct Ctx {
     DevBuf d_al[15];                                // dagcon_align: blobs, offsets, outputs, directions, launch order, widths, ends
     DevBuf d_pn[18];                                // dagcon_align_panels: blobs, panels, scratch, outputs, launch order
     DevBuf d_pl[14];                                // dagcon_place: blob, sequences, tables, pairs, outputs
-    DevBuf d_cs[10];                                // dagcon_upload_cs: the text, its offsets, the scan's totals, what k_cs_write takes
-    DevBuf d_cg[18];                                // dagcon_upload_cigar: ops, op / tile begins, totals, checkpoints, blobs, offsets
+    CsBufs cs;                                      // dagcon_upload_cs
+    CigarBufs cg;                                   // dagcon_upload_cigar and its kin
     std::vector<uint8_t> h_cig_bad;                 // dagcon_upload_cigar: targets with a non-conforming record (empty: another upload)
     std::string cig_err;                            // the first of them, for dagcon_last_error
     DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
@@ -547,8 +567,8 @@ void dagcon_destroy(dagcon_ctx *ctx) {
     for (DevBuf &b : c->d_al) free_buf(b);
     for (DevBuf &b : c->d_pn) free_buf(b);
     for (DevBuf &b : c->d_pl) free_buf(b);
-    for (DevBuf &b : c->d_cg) free_buf(b);
-    for (DevBuf &b : c->d_cs) free_buf(b);
+    for (DevBuf *b : c->cg.all()) free_buf(*b);
+    for (DevBuf *b : c->cs.all()) free_buf(*b);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1645,31 +1665,80 @@ int dagcon_consensus_pre(dagcon_ctx *ctx, const dagcon_pre_batch *b, dagcon_resu
 
 }  // extern "C"
 namespace {
-// what dagcon_upload_cigar and dagcon_upload_cigar_windows share: the checks of the batch, its upload, k_cigar_scan and
-// the totals back on the host (tot: columns, read bases, target bases, DG_CG_* flags per record); p is left ready for
-// an expansion but for its offsets.  packed: q_blob holds two bases a byte (dagcon_upload_cigar_packed), a record
-// takes (q_len + 1) / 2 bytes of it from q_off.  cs (dagcon_upload_cs): the ops, the reads and the targets are on the
-// device already (d_cg[0], [5], [6], made by k_cs_write), b->ops and b->q_blob are NULL and b->q_off is the host's
-// prefix sum of q_len; the scan's totals must then be those of k_cs_scan for every conforming record, and the caller
-// gets k_cs_scan's (they hold the spans of the records that are not)
+// ---- record intake: dagcon_upload_cigar, _windows, _packed, _strand and dagcon_upload_cs ------------------------------
+// One path, upload_records: reset, scan, judge, plan, expand, hand-over.  Whole targets and windows differ in the plan
+// alone (plan_whole / plan_windows); the input kinds differ in what cigar_scan uploads and in the kernel cigar_expand
+// picks, both read off a RecordSource.
+
+// what dagcon_upload_cs leaves for the path: every record judged and sized from its text
 struct CsDecoded {
     std::vector<const char *> why;                                 // per record: nullptr: conforming
-    std::vector<uint32_t> tot;                                     // per record, as tot below
+    std::vector<uint32_t> tot;                                     // per record, as CigarScan::tot
 };
-int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, bool packed, DgCigarParams &p, std::vector<uint64_t> &tile_begin, std::vector<uint32_t> &tot,
-               const CsDecoded *cs = nullptr) {
-    const uint32_t T = b->n_targets;
-    if (T && (!b->tlen || !b->rec_begin || !b->t_off)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
-    const uint64_t n64 = T ? b->rec_begin[T] : 0;
+
+// Where a batch's read bases and ops come from: a kind and what that kind alone carries; no other pairing can be built.
+//   PLAIN / PACKED  q_blob holds one base a byte / two (a record takes (q_len + 1) / 2 bytes from q_off)
+//   STRANDED        one base a byte and a flag per record: != 0, the ops are written against the reverse complement
+//   DECODED         dagcon_upload_cs: ops, reads and targets are on the device already (CigarBufs::ops, q, t, made by
+//                   k_cs_write), b->ops and b->q_blob are NULL, b->q_off is the host's prefix sum of q_len; the scan's totals
+//                   must be k_cs_scan's for every conforming record, and the path goes on with k_cs_scan's
+class RecordSource {
+  public:
+    enum Kind { PLAIN, PACKED, STRANDED, DECODED };
+    static RecordSource plain() { return RecordSource(PLAIN, nullptr); }
+    static RecordSource packed() { return RecordSource(PACKED, nullptr); }
+    static RecordSource stranded(const uint8_t *reverse) { return reverse ? RecordSource(STRANDED, reverse) : plain(); }
+    static RecordSource decoded(const CsDecoded &cs) { return RecordSource(DECODED, &cs); }
+    Kind kind() const { return kind_; }
+    const uint8_t *reverse() const { return kind_ == STRANDED ? static_cast<const uint8_t *>(carried_) : nullptr; }
+    const CsDecoded *cs() const { return kind_ == DECODED ? static_cast<const CsDecoded *>(carried_) : nullptr; }
+
+  private:
+    RecordSource(Kind k, const void *carried) : kind_(k), carried_(carried) {}
+    Kind kind_;
+    const void *carried_;
+};
+
+// reset: what any upload does to the context's state first
+Ctx *intake_reset(dagcon_ctx *ctx) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    c->uploaded = c->ran = c->fetched = false;
+    c->sup_valid = c->pos_valid = false;
+    return c;
+}
+
+// the checks a dagcon_cigar_batch and a dagcon_cs_batch share: the targets, their records' ranges, and the record count
+int check_targets(Ctx *c, uint32_t T, const uint32_t *tlen, const uint64_t *t_off, const uint64_t *rec_begin, const char *t_blob, uint64_t t_bytes,
+                  bool have_record_arrays, uint32_t &n) {
+    if (T && (!tlen || !rec_begin || !t_off)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
+    const uint64_t n64 = T ? rec_begin[T] : 0;
     if (n64 > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many records");
-    const uint32_t n = (uint32_t)n64;
-    if (n && (!b->pos || !b->q_off || !b->q_len || !b->op_begin)) return fail(c, DAGCON_ERR_INVALID_ARG, "record arrays are NULL");
-    if (T && b->rec_begin[0] != 0) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin does not start at 0");
+    n = (uint32_t)n64;
+    if (n && !have_record_arrays) return fail(c, DAGCON_ERR_INVALID_ARG, "record arrays are NULL");
+    if (T && rec_begin[0] != 0) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin does not start at 0");
     for (uint32_t g = 0; g < T; g++) {
-        if (b->rec_begin[g + 1] < b->rec_begin[g] || b->rec_begin[g + 1] > n64) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin not monotone at target %u", g);
-        if (b->t_off[g] > b->t_bytes || b->tlen[g] > b->t_bytes - b->t_off[g]) return fail(c, DAGCON_ERR_INVALID_ARG, "target %u runs past t_blob", g);
-        if (b->tlen[g] && !b->t_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "t_blob is NULL");
+        if (rec_begin[g + 1] < rec_begin[g] || rec_begin[g + 1] > n64) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin not monotone at target %u", g);
+        if (t_off[g] > t_bytes || tlen[g] > t_bytes - t_off[g]) return fail(c, DAGCON_ERR_INVALID_ARG, "target %u runs past t_blob", g);
+        if (tlen[g] && !t_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "t_blob is NULL");
     }
+    return DAGCON_OK;
+}
+
+// scan: the checks of the batch, its upload, k_cigar_scan and the totals back on the host; p is left ready for an
+// expansion but for what the plan decides (t_base, the offsets)
+struct CigarScan {
+    uint32_t n = 0;                                                // records
+    DgCigarParams p;
+    std::vector<uint64_t> tile_begin;                              // [n + 1]
+    std::vector<uint32_t> tot;                                     // per record: columns, read bases, target bases, DG_CG_* flags
+};
+int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, const RecordSource &src, CigarScan &sc) {
+    const CsDecoded *cs = src.cs();
+    const bool packed = src.kind() == RecordSource::PACKED;
+    uint32_t n = 0;
+    int r = check_targets(c, b->n_targets, b->tlen, b->t_off, b->rec_begin, b->t_blob, b->t_bytes, b->pos && b->q_off && b->q_len && b->op_begin, n);
+    if (r != DAGCON_OK) return r;
+    std::vector<uint64_t> &tile_begin = sc.tile_begin;
     tile_begin.assign((size_t)n + 1, 0);
     for (uint32_t a = 0; a < n; a++) {
         if (b->op_begin[a + 1] < b->op_begin[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "op_begin not monotone at record %u", a);
@@ -1683,30 +1752,30 @@ int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, bool packed, DgCigarParams &
     if (n_tiles > 0x7FFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many CIGAR ops");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    DevBuf &d_ops = c->d_cg[0], &d_opb = c->d_cg[1], &d_tileb = c->d_cg[2], &d_tot = c->d_cg[3], &d_ck = c->d_cg[4],
-           &d_qb = c->d_cg[5], &d_tb = c->d_cg[6], &d_qoff = c->d_cg[7];
+    CigarBufs &d = c->cg;
     // op_begin as the caller has it, less its first entry (ops are uploaded from there)
     std::vector<uint64_t> opb((size_t)n + 1, 0);
     for (uint32_t a = 0; a <= n && n; a++) opb[a] = b->op_begin[a] - b->op_begin[0];
-    ENSURE(c, d_ops, n_ops * 4); ENSURE(c, d_tot, (size_t)n * 16); ENSURE(c, d_ck, n_tiles * 16);
-    ENSURE(c, d_qb, b->q_bytes); ENSURE(c, d_tb, b->t_bytes); ENSURE(c, d_qoff, (size_t)n * 8);
-    if (n_ops && !cs) HIPCHK(c, hipMemcpyAsync(d_ops.p, b->ops + b->op_begin[0], n_ops * 4, hipMemcpyHostToDevice, s));
-    if (b->q_bytes && b->q_blob) HIPCHK(c, hipMemcpyAsync(d_qb.p, b->q_blob, b->q_bytes, hipMemcpyHostToDevice, s));
-    if (b->t_bytes && b->t_blob && !cs) HIPCHK(c, hipMemcpyAsync(d_tb.p, b->t_blob, b->t_bytes, hipMemcpyHostToDevice, s));
-    if (n) HIPCHK(c, hipMemcpyAsync(d_qoff.p, b->q_off, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    int r;
-    if ((r = upload_vec(c, d_opb, opb))) return r;
-    if ((r = upload_vec(c, d_tileb, tile_begin))) return r;
+    ENSURE(c, d.ops, n_ops * 4); ENSURE(c, d.totals, (size_t)n * 16); ENSURE(c, d.ckpt, n_tiles * 16);
+    ENSURE(c, d.q, b->q_bytes); ENSURE(c, d.t, b->t_bytes); ENSURE(c, d.q_off, (size_t)n * 8);
+    if (n_ops && !cs) HIPCHK(c, hipMemcpyAsync(d.ops.p, b->ops + b->op_begin[0], n_ops * 4, hipMemcpyHostToDevice, s));
+    if (b->q_bytes && b->q_blob) HIPCHK(c, hipMemcpyAsync(d.q.p, b->q_blob, b->q_bytes, hipMemcpyHostToDevice, s));
+    if (b->t_bytes && b->t_blob && !cs) HIPCHK(c, hipMemcpyAsync(d.t.p, b->t_blob, b->t_bytes, hipMemcpyHostToDevice, s));
+    if (n) HIPCHK(c, hipMemcpyAsync(d.q_off.p, b->q_off, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    if ((r = upload_vec(c, d.op_begin, opb))) return r;
+    if ((r = upload_vec(c, d.tile_begin, tile_begin))) return r;
+    DgCigarParams &p = sc.p;
     memset(&p, 0, sizeof p);
-    p.ops = (const uint32_t *)d_ops.p; p.op_begin = (const uint64_t *)d_opb.p; p.tile_begin = (const uint64_t *)d_tileb.p;
+    p.ops = (const uint32_t *)d.ops.p; p.op_begin = (const uint64_t *)d.op_begin.p; p.tile_begin = (const uint64_t *)d.tile_begin.p;
     p.n = n; p.n_tiles = (uint32_t)n_tiles;
-    p.totals = (uint4 *)d_tot.p; p.ckpt = (uint4 *)d_ck.p;
-    p.q = (const uint8_t *)d_qb.p; p.t = (const uint8_t *)d_tb.p; p.q_off = (const uint64_t *)d_qoff.p;
+    p.totals = (uint4 *)d.totals.p; p.ckpt = (uint4 *)d.ckpt.p;
+    p.q = (const uint8_t *)d.q.p; p.t = (const uint8_t *)d.t.p; p.q_off = (const uint64_t *)d.q_off.p;
+    std::vector<uint32_t> &tot = sc.tot;
     tot.assign((size_t)n * 4, 0);
     if (n) {
         hipLaunchKernelGGL(k_cigar_scan, dim3((n + 3u) / 4u), dim3(256), 0, s, p);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, d2h(c, tot.data(), d_tot.p, (size_t)n * 16));
+        HIPCHK(c, d2h(c, tot.data(), d.totals.p, (size_t)n * 16));
     }
     if (cs) {
         for (uint32_t a = 0; a < n; a++)
@@ -1715,121 +1784,81 @@ int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, bool packed, DgCigarParams &
                             tot[(size_t)a * 4], tot[(size_t)a * 4 + 1], tot[(size_t)a * 4 + 2], tot[(size_t)a * 4 + 3], cs->tot[(size_t)a * 4], cs->tot[(size_t)a * 4 + 1], cs->tot[(size_t)a * 4 + 2]);
         tot = cs->tot;
     }
+    sc.n = n;
     return DAGCON_OK;
 }
 
-// why a record is non-conforming (include/dagcon.h), nullptr if it conforms
-const char *cigar_why(const dagcon_cigar_batch *b, const std::vector<uint32_t> &tot, uint32_t g, uint64_t a, const CsDecoded *cs = nullptr) {
-    if (cs) return cs->why[a];
-    const uint32_t nq = tot[a * 4 + 1], nt = tot[a * 4 + 2], fl = tot[a * 4 + 3];
-    return (fl & DG_CG_BAD_OP) ? "an op code above 8 or N"
-         : (fl & DG_CG_ZERO_LEN) ? "an op of length 0"
-         : (fl & DG_CG_OVERFLOW) ? "a total past 32 bits"
-         : b->pos[a] == 0 ? "pos is 0"
-         : nq != b->q_len[a] ? "the ops do not consume exactly q_len read bases"
-         : (uint64_t)b->pos[a] - 1u + nt > b->tlen[g] ? "target bases past tlen" : nullptr;
-}
-
-// the strand kernels' own arguments (dagcon_upload_cigar_strand): one flag and q_len per record
-int cigar_strand(Ctx *c, const dagcon_cigar_batch *b, uint32_t n, const uint8_t *reverse, DgCigarStrand &st) {
-    DevBuf &d_rev = c->d_cg[15], &d_qlen = c->d_cg[16];
-    ENSURE(c, d_rev, (size_t)n); ENSURE(c, d_qlen, (size_t)n * 4);
-    if (n) {
-        HIPCHK(c, hipMemcpyAsync(d_rev.p, reverse, (size_t)n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_qlen.p, b->q_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    st.rev = (const uint8_t *)d_rev.p; st.q_len = (const uint32_t *)d_qlen.p;
-    return DAGCON_OK;
-}
-}  // namespace
-extern "C" {
-
-// SAM-style input: position + ungapped read + CIGAR per record, target bases once per target.  k_cigar_scan sizes
-// every record, the host plans the string blobs as for any batch, k_cigar_expand writes them into d_q / d_t, and
-// upload_impl takes them from there (the door dagcon_consensus_pre uses)
-}  // extern "C"
-namespace {
-int upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b, bool packed, const uint8_t *reverse = nullptr, const CsDecoded *cs = nullptr) {
-    if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    c->uploaded = c->ran = c->fetched = false;
-    c->sup_valid = c->pos_valid = false;
-    const uint32_t T = b->n_targets;
-    const uint32_t n = T && b->rec_begin ? (uint32_t)b->rec_begin[T] : 0u;
-    DgCigarParams p;
-    std::vector<uint64_t> tile_begin;
-    std::vector<uint32_t> tot;
-    int r = cigar_scan(c, b, packed, p, tile_begin, tot, cs);
-    if (r != DAGCON_OK) return r;
-    const uint64_t n_tiles = tile_begin[n];
-    hipStream_t s = c->stream;
-    DevBuf &d_tbase = c->d_cg[8], &d_out = c->d_cg[9];
-    // what every record is: the targets with a non-conforming one lose all their records
-    std::vector<uint8_t> bad(T, 0);
+// judge: why each record is non-conforming (include/dagcon.h; nullptr: it conforms), and the text of the first that is
+struct CigarVerdict {
+    std::vector<const char *> why;                                 // [n]
     std::string first_err;
-    for (uint32_t g = 0; g < T; g++)
+};
+CigarVerdict cigar_judge(const dagcon_cigar_batch *b, const RecordSource &src, const CigarScan &sc) {
+    CigarVerdict v;
+    v.why.assign((size_t)sc.n, nullptr);
+    for (uint32_t g = 0; g < b->n_targets; g++)
         for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
-            const char *why = cigar_why(b, tot, g, a, cs);
-            if (!why) continue;
-            if (first_err.empty()) {
+            const uint32_t nq = sc.tot[a * 4 + 1], nt = sc.tot[a * 4 + 2], fl = sc.tot[a * 4 + 3];
+            const char *why = src.cs() ? src.cs()->why[a]
+                            : (fl & DG_CG_BAD_OP) ? "an op code above 8 or N"
+                            : (fl & DG_CG_ZERO_LEN) ? "an op of length 0"
+                            : (fl & DG_CG_OVERFLOW) ? "a total past 32 bits"
+                            : b->pos[a] == 0 ? "pos is 0"
+                            : nq != b->q_len[a] ? "the ops do not consume exactly q_len read bases"
+                            : (uint64_t)b->pos[a] - 1u + nt > b->tlen[g] ? "target bases past tlen" : nullptr;
+            v.why[a] = why;
+            if (why && v.first_err.empty()) {
                 char buf[256];
                 snprintf(buf, sizeof buf, "target %u: record %llu is non-conforming (%s)", g, (unsigned long long)a, why);
-                first_err = buf;
+                v.first_err = buf;
             }
-            bad[g] = 1;
         }
-    // the batch upload_impl sees: the records of the other targets, strings planned as dagcon_consensus_pre plans them
-    // (a target below min_cov is skipped whatever it holds: it goes in without records, and nothing of it is expanded)
-    std::vector<uint64_t> beg2((size_t)T + 1, 0), off2, out_off((size_t)n, DG_CG_SKIP), t_base((size_t)n, 0);
-    std::vector<uint32_t> start2, len2;
-    uint64_t bytes = 0;
+    return v;
+}
+
+// plan: what upload_impl is to see (a dagcon_batch of strings, planned as dagcon_consensus_pre plans them), where the
+// expansion writes them (set in sc.p, and cw for pieces), and how many waves it takes (0: nothing to expand)
+struct CigarPlan {
+    std::vector<uint8_t> bad;                                      // per target of the pipeline: it holds a non-conforming record
+    std::vector<uint32_t> tlen;                                    // windows: the pipeline's targets (whole: the batch's own)
+    std::vector<uint64_t> beg, off;                                // aln_begin, aln_off
+    std::vector<uint32_t> start, len;                              // aln_start, aln_len
+    uint64_t bytes = 0;                                            // of each string blob
+    bool pieces = false;                                           // the expansion is k_cigar_expand_cut's, over cw
+    DgCigarCutParams cw;
+    uint32_t waves = 0;
+};
+
+// whole targets: one record, one string; the targets with a non-conforming record lose all their records (a target below
+// min_cov is skipped whatever it holds: it goes in without records, and nothing of it is expanded)
+int plan_whole(Ctx *c, const dagcon_cigar_batch *b, CigarScan &sc, const CigarVerdict &v, CigarPlan &pl) {
+    const uint32_t T = b->n_targets, n = sc.n;
+    pl.bad.assign(T, 0);
+    for (uint32_t g = 0; g < T; g++)
+        for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++)
+            if (v.why[a]) pl.bad[g] = 1;
+    std::vector<uint64_t> out_off((size_t)n, DG_CG_SKIP), t_base((size_t)n, 0);
+    pl.beg.assign((size_t)T + 1, 0);
     for (uint32_t g = 0; g < T; g++) {
-        beg2[g] = start2.size();
+        pl.beg[g] = pl.start.size();
         const uint64_t k = b->rec_begin[g + 1] - b->rec_begin[g];
-        if (bad[g] || k == 0 || k < c->opts.min_cov) continue;
+        if (pl.bad[g] || k == 0 || k < c->opts.min_cov) continue;
         for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
-            out_off[a] = bytes; t_base[a] = b->t_off[g] + b->pos[a] - 1u;
-            start2.push_back(b->pos[a]); off2.push_back(bytes); len2.push_back(tot[a * 4]);
-            bytes += ((uint64_t)tot[a * 4] + 15ull) & ~15ull;
+            out_off[a] = pl.bytes; t_base[a] = b->t_off[g] + b->pos[a] - 1u;
+            pl.start.push_back(b->pos[a]); pl.off.push_back(pl.bytes); pl.len.push_back(sc.tot[a * 4]);
+            pl.bytes += ((uint64_t)sc.tot[a * 4] + 15ull) & ~15ull;
         }
     }
-    beg2[T] = start2.size();
-    ENSURE(c, c->d_q, bytes); ENSURE(c, c->d_t, bytes);
-    if ((r = upload_vec(c, d_tbase, t_base))) return r;
-    if ((r = upload_vec(c, d_out, out_off))) return r;
-    if (n_tiles && bytes) {
-        p.t_base = (const uint64_t *)d_tbase.p; p.out_off = (const uint64_t *)d_out.p;
-        p.out_q = (uint8_t *)c->d_q.p; p.out_t = (uint8_t *)c->d_t.p;
-        if (reverse) {
-            DgCigarStrand st;
-            if ((r = cigar_strand(c, b, n, reverse, st))) return r;
-            hipLaunchKernelGGL(k_cigar_expand_strand, dim3((uint32_t)n_tiles), dim3(64), 0, s, p, st);
-        } else if (packed) hipLaunchKernelGGL(k_cigar_expand_packed, dim3((uint32_t)n_tiles), dim3(64), 0, s, p);
-        else hipLaunchKernelGGL(k_cigar_expand, dim3((uint32_t)n_tiles), dim3(64), 0, s, p);
-        HIPCHK(c, hipGetLastError());
-    }
-    dagcon_batch db;
-    memset(&db, 0, sizeof db);
-    db.n_targets = T; db.tlen = b->tlen; db.aln_begin = beg2.data();
-    db.aln_start = start2.data(); db.aln_off = off2.data(); db.aln_len = len2.data();
-    db.blob_bytes = bytes;
-    r = upload_impl(ctx, &db, c->d_q.p, c->d_t.p);                 // (synchronises the stream: the locals above may go)
-    if (r != DAGCON_OK) { (void)hipStreamSynchronize(s); return r; }
-    c->h_cig_bad = bad;
-    c->cig_err = first_err;
+    pl.beg[T] = pl.start.size();
+    int r;
+    if ((r = upload_vec(c, c->cg.t_base, t_base))) return r;
+    if ((r = upload_vec(c, c->cg.out_off, out_off))) return r;
+    sc.p.t_base = (const uint64_t *)c->cg.t_base.p; sc.p.out_off = (const uint64_t *)c->cg.out_off.p;
+    pl.waves = pl.bytes ? sc.p.n_tiles : 0u;
     return DAGCON_OK;
 }
 
-// The same input with every target cut into windows, each window a target of the pipeline (include/dagcon.h has the
-// cut).  After the scan's totals the host knows every record's [s, e) and lists the (record, window) pieces; k_cigar_cut
-// turns each piece's two target coordinates into columns and tiles, the host plans the output from those, and
-// k_cigar_expand_cut writes every piece from the one device copy of the record's ops and bases.
-int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, bool packed, const uint8_t *reverse = nullptr,
-                         const CsDecoded *cs = nullptr) {
-    if (!ctx || !b || !wn) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    c->uploaded = c->ran = c->fetched = false;
-    c->sup_valid = c->pos_valid = false;
+int check_windows(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
     const uint32_t T = b->n_targets, W = wn->n_windows;
     if (W && (!wn->target || !wn->begin || !wn->end)) return fail(c, DAGCON_ERR_INVALID_ARG, "window arrays are NULL");
     if (T && !b->tlen) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
@@ -1841,44 +1870,37 @@ int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dag
         if (w && (g < wn->target[w - 1] || (g == wn->target[w - 1] && wn->begin[w] < wn->begin[w - 1])))
             return fail(c, DAGCON_ERR_INVALID_ARG, "window %u is out of order (targets ascending, begins ascending inside a target)", w);
     }
-    const uint32_t n = T && b->rec_begin ? (uint32_t)b->rec_begin[T] : 0u;
-    DgCigarParams p;
-    std::vector<uint64_t> tile_begin;
-    std::vector<uint32_t> tot;
-    int r = cigar_scan(c, b, packed, p, tile_begin, tot, cs);
-    if (r != DAGCON_OK) return r;
-    hipStream_t s = c->stream;
-    DevBuf &d_tbase = c->d_cg[8], &d_piece = c->d_cg[10], &d_cut = c->d_cg[11], &d_wpiece = c->d_cg[12], &d_wbegin = c->d_cg[13],
-           &d_pout = c->d_cg[14];
+    return DAGCON_OK;
+}
+
+// windows: every target cut into windows, each window a target of the pipeline (include/dagcon.h has the cut).  After
+// the scan's totals the host knows every record's [s, e) and lists the (record, window) pieces; k_cigar_cut turns each
+// piece's two target coordinates into columns and tiles, the host plans the output from those, and k_cigar_expand_cut
+// writes every piece from the one device copy of the record's ops and bases.
+int plan_windows(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn, CigarScan &sc, const CigarVerdict &v, CigarPlan &pl) {
+    const uint32_t T = b->n_targets, W = wn->n_windows, n = sc.n;
+    const std::vector<uint32_t> &tot = sc.tot;
+    CigarBufs &d = c->cg;
     // every record's [s, e) in target bases.  A non-conforming record has whatever span its pos and its target-base
     // total give, clipped to the target and at least one base long: it fails the windows that span meets
     std::vector<uint32_t> rs((size_t)n), re((size_t)n);
-    std::vector<uint8_t> rbad((size_t)n, 0);
     std::vector<uint64_t> t_base((size_t)n, 0);
-    std::string first_err;
     for (uint32_t g = 0; g < T; g++)
         for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
-            const char *why = cigar_why(b, tot, g, a, cs);
             const uint64_t tl = b->tlen[g];
             uint64_t s0 = b->pos[a] ? b->pos[a] - 1u : 0u, e0 = s0 + tot[a * 4 + 2];
-            if (why) {
-                rbad[a] = 1;
+            if (v.why[a]) {
                 if (tl && s0 > tl - 1) s0 = tl - 1;
                 if (e0 < s0 + 1) e0 = s0 + 1;
                 if (e0 > tl) e0 = tl;
-                if (first_err.empty()) {
-                    char buf[256];
-                    snprintf(buf, sizeof buf, "target %u: record %llu is non-conforming (%s)", g, (unsigned long long)a, why);
-                    first_err = buf;
-                }
             }
             rs[a] = (uint32_t)s0; re[a] = (uint32_t)e0;
             t_base[a] = b->t_off[g] + s0;
         }
     // the pieces, window by window, records in their own order (addAln order); a window with a non-conforming piece, or
     // with fewer pieces than min_cov, keeps none
-    std::vector<uint8_t> bad(W, 0);
-    std::vector<uint64_t> beg2((size_t)W + 1, 0);
+    pl.bad.assign(W, 0);
+    pl.beg.assign((size_t)W + 1, 0);
     std::vector<uint32_t> piece;                                   // x4: record, a_rel, b_rel, window
     for (uint32_t w = 0; w < W; w++) {
         const uint32_t g = wn->target[w], wa = wn->begin[w], wb = wn->end[w];
@@ -1886,100 +1908,143 @@ int upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dag
         for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
             const uint32_t A = std::max(wa, rs[a]), B = std::min(wb, re[a]);
             if (A >= B) continue;
-            if (rbad[a]) { bad[w] = 1; continue; }
+            if (v.why[a]) { pl.bad[w] = 1; continue; }
             piece.push_back((uint32_t)a); piece.push_back(A - rs[a]); piece.push_back(B - rs[a]); piece.push_back(w);
         }
         const size_t k = (piece.size() - first) / 4;
-        if (bad[w] || k < c->opts.min_cov) piece.resize(first);
+        if (pl.bad[w] || k < c->opts.min_cov) piece.resize(first);
     }
     const uint64_t np64 = piece.size() / 4;
     if (np64 > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many alignments");
     const uint32_t np = (uint32_t)np64;
-    DgCigarCutParams cw;
+    DgCigarCutParams &cw = pl.cw;
     memset(&cw, 0, sizeof cw);
+    pl.pieces = true;
     std::vector<uint32_t> cut((size_t)np * 4);
+    int r;
     if (np) {
-        if ((r = upload_vec(c, d_piece, piece))) return r;
-        ENSURE(c, d_cut, (size_t)np * 16);
-        cw.piece = (const uint4 *)d_piece.p; cw.cut = (uint4 *)d_cut.p; cw.n_pieces = np;
-        hipLaunchKernelGGL(k_cigar_cut, dim3((np + 3u) / 4u), dim3(256), 0, s, p, cw);
+        if ((r = upload_vec(c, d.piece, piece))) return r;
+        ENSURE(c, d.cut, (size_t)np * 16);
+        cw.piece = (const uint4 *)d.piece.p; cw.cut = (uint4 *)d.cut.p; cw.n_pieces = np;
+        hipLaunchKernelGGL(k_cigar_cut, dim3((np + 3u) / 4u), dim3(256), 0, c->stream, sc.p, cw);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, d2h(c, cut.data(), d_cut.p, (size_t)np * 16));
+        HIPCHK(c, d2h(c, cut.data(), d.cut.p, (size_t)np * 16));
     }
     // the output plan: nothing the device said is used before it has been checked against the record's own sizes
-    std::vector<uint64_t> off2((size_t)np), pout((size_t)np);
-    std::vector<uint32_t> start2((size_t)np), len2((size_t)np), wbegin((size_t)np), wpiece;
-    uint64_t bytes = 0;
+    std::vector<uint64_t> pout((size_t)np);
+    std::vector<uint32_t> wbegin((size_t)np), wpiece;
+    pl.off.resize(np); pl.start.resize(np); pl.len.resize(np);
     uint32_t cur = 0;
     for (uint32_t i = 0; i < np; i++) {
         const uint32_t a = piece[i * 4], w = piece[i * 4 + 3];
         const uint32_t ca = cut[i * 4], cb = cut[i * 4 + 1], ta = cut[i * 4 + 2], tb = cut[i * 4 + 3];
-        const uint64_t ntile = tile_begin[a + 1] - tile_begin[a];
+        const uint64_t ntile = sc.tile_begin[a + 1] - sc.tile_begin[a];
         if (ca > cb || cb > tot[a * 4] || ta > tb || tb >= ntile)
             return fail(c, DAGCON_ERR_INTERNAL, "k_cigar_cut: piece %u of record %u has columns [%u, %u), tiles [%u, %u] of %llu", i, a, ca, cb, ta, tb, (unsigned long long)ntile);
-        while (cur < w) beg2[++cur] = i;
-        off2[i] = pout[i] = bytes;
-        len2[i] = cb - ca;
-        start2[i] = rs[a] + piece[i * 4 + 1] - wn->begin[w] + 1u;
-        bytes += ((uint64_t)(cb - ca) + 15ull) & ~15ull;
+        while (cur < w) pl.beg[++cur] = i;
+        pl.off[i] = pout[i] = pl.bytes;
+        pl.len[i] = cb - ca;
+        pl.start[i] = rs[a] + piece[i * 4 + 1] - wn->begin[w] + 1u;
+        pl.bytes += ((uint64_t)(cb - ca) + 15ull) & ~15ull;
         if (wpiece.size() + (tb - ta + 1u) > 0x7FFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many CIGAR ops");
         wbegin[i] = (uint32_t)wpiece.size();
         wpiece.insert(wpiece.end(), tb - ta + 1u, i);
     }
-    while (cur < W) beg2[++cur] = np;
-    ENSURE(c, c->d_q, bytes); ENSURE(c, c->d_t, bytes);
-    if (np && bytes) {
-        if ((r = upload_vec(c, d_tbase, t_base))) return r;
-        if ((r = upload_vec(c, d_wpiece, wpiece))) return r;
-        if ((r = upload_vec(c, d_wbegin, wbegin))) return r;
-        if ((r = upload_vec(c, d_pout, pout))) return r;
-        p.t_base = (const uint64_t *)d_tbase.p;
-        p.out_q = (uint8_t *)c->d_q.p; p.out_t = (uint8_t *)c->d_t.p;
-        cw.wave_piece = (const uint32_t *)d_wpiece.p; cw.wave_begin = (const uint32_t *)d_wbegin.p;
-        cw.piece_out = (const uint64_t *)d_pout.p; cw.n_waves = (uint32_t)wpiece.size();
-        if (reverse) {
-            DgCigarStrand st;
-            if ((r = cigar_strand(c, b, n, reverse, st))) return r;
-            hipLaunchKernelGGL(k_cigar_expand_cut_strand, dim3(cw.n_waves), dim3(64), 0, s, p, cw, st);
-        } else if (packed) hipLaunchKernelGGL(k_cigar_expand_cut_packed, dim3(cw.n_waves), dim3(64), 0, s, p, cw);
-        else hipLaunchKernelGGL(k_cigar_expand_cut, dim3(cw.n_waves), dim3(64), 0, s, p, cw);
-        HIPCHK(c, hipGetLastError());
+    while (cur < W) pl.beg[++cur] = np;
+    pl.tlen.resize(W);
+    for (uint32_t w = 0; w < W; w++) pl.tlen[w] = wn->end[w] - wn->begin[w];
+    if (np && pl.bytes) {
+        if ((r = upload_vec(c, d.t_base, t_base))) return r;
+        if ((r = upload_vec(c, d.wave_piece, wpiece))) return r;
+        if ((r = upload_vec(c, d.wave_begin, wbegin))) return r;
+        if ((r = upload_vec(c, d.piece_out, pout))) return r;
+        sc.p.t_base = (const uint64_t *)d.t_base.p;
+        cw.wave_piece = (const uint32_t *)d.wave_piece.p; cw.wave_begin = (const uint32_t *)d.wave_begin.p;
+        cw.piece_out = (const uint64_t *)d.piece_out.p; cw.n_waves = (uint32_t)wpiece.size();
+        pl.waves = cw.n_waves;
     }
-    std::vector<uint32_t> wlen(W);
-    for (uint32_t w = 0; w < W; w++) wlen[w] = wn->end[w] - wn->begin[w];
+    return DAGCON_OK;
+}
+
+// expand: the strings into d_q / d_t, a wave per tile (of a record, or of a piece), by the kernel of the source's kind
+int cigar_expand(Ctx *c, const dagcon_cigar_batch *b, const RecordSource &src, CigarScan &sc, const CigarPlan &pl) {
+    ENSURE(c, c->d_q, pl.bytes); ENSURE(c, c->d_t, pl.bytes);
+    if (!pl.waves) return DAGCON_OK;
+    DgCigarParams &p = sc.p;
+    p.out_q = (uint8_t *)c->d_q.p; p.out_t = (uint8_t *)c->d_t.p;
+    const dim3 grid(pl.waves), block(64);
+    hipStream_t s = c->stream;
+    switch (src.kind()) {
+    case RecordSource::STRANDED: {
+        // the strand kernels' own arguments: one flag and q_len per record
+        DgCigarStrand st;
+        ENSURE(c, c->cg.rev, (size_t)sc.n); ENSURE(c, c->cg.q_len, (size_t)sc.n * 4);
+        if (sc.n) {
+            HIPCHK(c, hipMemcpyAsync(c->cg.rev.p, src.reverse(), (size_t)sc.n, hipMemcpyHostToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(c->cg.q_len.p, b->q_len, (size_t)sc.n * 4, hipMemcpyHostToDevice, s));
+        }
+        st.rev = (const uint8_t *)c->cg.rev.p; st.q_len = (const uint32_t *)c->cg.q_len.p;
+        if (pl.pieces) hipLaunchKernelGGL(k_cigar_expand_cut_strand, grid, block, 0, s, p, pl.cw, st);
+        else hipLaunchKernelGGL(k_cigar_expand_strand, grid, block, 0, s, p, st);
+        break;
+    }
+    case RecordSource::PACKED:
+        if (pl.pieces) hipLaunchKernelGGL(k_cigar_expand_cut_packed, grid, block, 0, s, p, pl.cw);
+        else hipLaunchKernelGGL(k_cigar_expand_packed, grid, block, 0, s, p);
+        break;
+    case RecordSource::PLAIN:
+    case RecordSource::DECODED:
+        if (pl.pieces) hipLaunchKernelGGL(k_cigar_expand_cut, grid, block, 0, s, p, pl.cw);
+        else hipLaunchKernelGGL(k_cigar_expand, grid, block, 0, s, p);
+        break;
+    }
+    HIPCHK(c, hipGetLastError());
+    return DAGCON_OK;
+}
+
+// hand-over: the planned strings go in by the door dagcon_consensus_pre uses; the context remembers which of the
+// pipeline's targets fail for a record, and why
+int cigar_hand_over(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const CigarPlan &pl, const CigarVerdict &v) {
     dagcon_batch db;
     memset(&db, 0, sizeof db);
-    db.n_targets = W; db.tlen = wlen.data(); db.aln_begin = beg2.data();
-    db.aln_start = start2.data(); db.aln_off = off2.data(); db.aln_len = len2.data();
-    db.blob_bytes = bytes;
-    r = upload_impl(ctx, &db, c->d_q.p, c->d_t.p);                 // (synchronises the stream: the locals above may go)
-    if (r != DAGCON_OK) { (void)hipStreamSynchronize(s); return r; }
-    c->h_cig_bad = bad;
-    c->cig_err = first_err;
+    db.n_targets = (uint32_t)pl.bad.size(); db.tlen = pl.pieces ? pl.tlen.data() : b->tlen; db.aln_begin = pl.beg.data();
+    db.aln_start = pl.start.data(); db.aln_off = pl.off.data(); db.aln_len = pl.len.data();
+    db.blob_bytes = pl.bytes;
+    const int r = upload_impl(ctx, &db, c->d_q.p, c->d_t.p);       // (synchronises the stream: the caller's locals may go)
+    if (r != DAGCON_OK) { (void)hipStreamSynchronize(c->stream); return r; }
+    c->h_cig_bad = pl.bad;
+    c->cig_err = v.first_err;
     return DAGCON_OK;
+}
+
+// SAM-style input: position + ungapped read + CIGAR per record, target bases once per target.  k_cigar_scan sizes every
+// record, the host plans the string blobs as for any batch, the expansion writes them into d_q / d_t, and upload_impl
+// takes them from there.  wn NULL: whole targets.  The strings never exist on the host.
+int upload_records(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, const RecordSource &src) {
+    if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = intake_reset(ctx);
+    int r;
+    if (wn && (r = check_windows(c, b, wn))) return r;
+    CigarScan sc;
+    if ((r = cigar_scan(c, b, src, sc))) return r;
+    const CigarVerdict v = cigar_judge(b, src, sc);
+    CigarPlan pl;
+    if ((r = wn ? plan_windows(c, b, wn, sc, v, pl) : plan_whole(c, b, sc, v, pl))) return r;
+    if ((r = cigar_expand(c, b, src, sc, pl))) return r;
+    return cigar_hand_over(ctx, c, b, pl, v);
 }
 
 // minimap2's cs:Z: text per record, the target's bases once per target (include/dagcon.h has the rule).  k_cs_scan sizes
 // and judges every record from the raw text; the host lays the conforming records' ops out without gaps and gives every
 // record its q_len bytes of the read buffer; k_cs_write fills both on the device; from there the batch is a
-// dagcon_cigar_batch whose ops, reads and targets are device-resident (upload_cigar / upload_cigar_windows with cs)
+// dagcon_cigar_batch whose ops, reads and targets are device-resident (upload_records with RecordSource::decoded)
 int upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *wn) {
     if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    c->uploaded = c->ran = c->fetched = false;
-    c->sup_valid = c->pos_valid = false;
+    Ctx *c = intake_reset(ctx);
     const uint32_t T = b->n_targets;
-    if (T && (!b->tlen || !b->rec_begin || !b->t_off)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
-    const uint64_t n64 = T ? b->rec_begin[T] : 0;
-    if (n64 > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many records");
-    const uint32_t n = (uint32_t)n64;
-    if (n && (!b->pos || !b->q_len || !b->cs_off || !b->cs_len)) return fail(c, DAGCON_ERR_INVALID_ARG, "record arrays are NULL");
-    if (T && b->rec_begin[0] != 0) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin does not start at 0");
-    for (uint32_t g = 0; g < T; g++) {
-        if (b->rec_begin[g + 1] < b->rec_begin[g] || b->rec_begin[g + 1] > n64) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin not monotone at target %u", g);
-        if (b->t_off[g] > b->t_bytes || b->tlen[g] > b->t_bytes - b->t_off[g]) return fail(c, DAGCON_ERR_INVALID_ARG, "target %u runs past t_blob", g);
-        if (b->tlen[g] && !b->t_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "t_blob is NULL");
-    }
+    uint32_t n = 0;
+    int r = check_targets(c, T, b->tlen, b->t_off, b->rec_begin, b->t_blob, b->t_bytes, b->pos && b->q_len && b->cs_off && b->cs_len, n);
+    if (r != DAGCON_OK) return r;
     std::vector<uint64_t> q_off((size_t)n + 1, 0);
     for (uint32_t a = 0; a < n; a++) {
         if (b->cs_off[a] > b->cs_bytes || b->cs_len[a] > b->cs_bytes - b->cs_off[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "record %u runs past cs_blob", a);
@@ -1989,13 +2054,12 @@ int upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *w
     const uint64_t q_bytes = q_off[n];
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    DevBuf &d_txt = c->d_cs[0], &d_csoff = c->d_cs[1], &d_cslen = c->d_cs[2], &d_tot = c->d_cs[3], &d_nops = c->d_cs[4], &d_opb = c->d_cs[5],
-           &d_tbase = c->d_cs[6], &d_troom = c->d_cs[7], &d_qoff = c->d_cs[8], &d_qlen = c->d_cs[9];
-    DevBuf &d_ops = c->d_cg[0], &d_qb = c->d_cg[5], &d_tb = c->d_cg[6];     // where cigar_scan looks for them
-    ENSURE(c, d_txt, b->cs_bytes); ENSURE(c, d_csoff, (size_t)n * 8); ENSURE(c, d_cslen, (size_t)n * 4);
-    ENSURE(c, d_tot, (size_t)n * 16); ENSURE(c, d_nops, (size_t)n * 4); ENSURE(c, d_tb, b->t_bytes); ENSURE(c, d_qb, q_bytes);
-    if (b->cs_bytes && b->cs_blob) HIPCHK(c, hipMemcpyAsync(d_txt.p, b->cs_blob, b->cs_bytes, hipMemcpyHostToDevice, s));
-    if (b->t_bytes && b->t_blob) HIPCHK(c, hipMemcpyAsync(d_tb.p, b->t_blob, b->t_bytes, hipMemcpyHostToDevice, s));
+    CsBufs &d = c->cs;
+    CigarBufs &cg = c->cg;                                         // ops, q and t: what k_cs_write makes for cigar_scan
+    ENSURE(c, d.text, b->cs_bytes); ENSURE(c, d.cs_off, (size_t)n * 8); ENSURE(c, d.cs_len, (size_t)n * 4);
+    ENSURE(c, d.totals, (size_t)n * 16); ENSURE(c, d.n_ops, (size_t)n * 4); ENSURE(c, cg.t, b->t_bytes); ENSURE(c, cg.q, q_bytes);
+    if (b->cs_bytes && b->cs_blob) HIPCHK(c, hipMemcpyAsync(d.text.p, b->cs_blob, b->cs_bytes, hipMemcpyHostToDevice, s));
+    if (b->t_bytes && b->t_blob) HIPCHK(c, hipMemcpyAsync(cg.t.p, b->t_blob, b->t_bytes, hipMemcpyHostToDevice, s));
     DgCsParams p;
     memset(&p, 0, sizeof p);
     CsDecoded cs;
@@ -2003,14 +2067,14 @@ int upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *w
     cs.tot.assign((size_t)n * 4, 0);
     std::vector<uint32_t> nops((size_t)n, 0);
     if (n) {
-        HIPCHK(c, hipMemcpyAsync(d_csoff.p, b->cs_off, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(d_cslen.p, b->cs_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        p.cs = (const uint8_t *)d_txt.p; p.cs_off = (const uint64_t *)d_csoff.p; p.cs_len = (const uint32_t *)d_cslen.p; p.n = n;
-        p.totals = (uint4 *)d_tot.p; p.n_ops = (uint32_t *)d_nops.p;
+        HIPCHK(c, hipMemcpyAsync(d.cs_off.p, b->cs_off, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(d.cs_len.p, b->cs_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        p.cs = (const uint8_t *)d.text.p; p.cs_off = (const uint64_t *)d.cs_off.p; p.cs_len = (const uint32_t *)d.cs_len.p; p.n = n;
+        p.totals = (uint4 *)d.totals.p; p.n_ops = (uint32_t *)d.n_ops.p;
         hipLaunchKernelGGL(k_cs_scan, dim3((n + 3u) / 4u), dim3(256), 0, s, p);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, d2h(c, cs.tot.data(), d_tot.p, (size_t)n * 16));
-        HIPCHK(c, d2h(c, nops.data(), d_nops.p, (size_t)n * 4));
+        HIPCHK(c, d2h(c, cs.tot.data(), d.totals.p, (size_t)n * 16));
+        HIPCHK(c, d2h(c, nops.data(), d.n_ops.p, (size_t)n * 4));
     }
     // what every record is; the ops of the conforming ones back to back, a read of q_len bytes each
     std::vector<uint64_t> opb((size_t)n + 1, 0), t_base((size_t)n, 0);
@@ -2035,18 +2099,17 @@ int upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *w
             if (pos >= 1u && pos - 1u <= tl) { t_room[a] = tl - (pos - 1u); t_base[a] = b->t_off[g] + pos - 1u; }
         }
     const uint64_t n_ops = opb[n];
-    ENSURE(c, d_ops, n_ops * 4);
-    int r;
+    ENSURE(c, cg.ops, n_ops * 4);
     if (n_ops) {
-        if ((r = upload_vec(c, d_opb, opb))) return r;
-        if ((r = upload_vec(c, d_tbase, t_base))) return r;
-        if ((r = upload_vec(c, d_troom, t_room))) return r;
-        if ((r = upload_vec(c, d_qoff, q_off))) return r;
-        ENSURE(c, d_qlen, (size_t)n * 4);
-        HIPCHK(c, hipMemcpyAsync(d_qlen.p, b->q_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        p.op_begin = (const uint64_t *)d_opb.p; p.ops = (uint32_t *)d_ops.p;
-        p.t = (const uint8_t *)d_tb.p; p.t_base = (const uint64_t *)d_tbase.p; p.t_room = (const uint32_t *)d_troom.p;
-        p.q_off = (const uint64_t *)d_qoff.p; p.q_len = (const uint32_t *)d_qlen.p; p.q = (uint8_t *)d_qb.p;
+        if ((r = upload_vec(c, d.op_begin, opb))) return r;
+        if ((r = upload_vec(c, d.t_base, t_base))) return r;
+        if ((r = upload_vec(c, d.t_room, t_room))) return r;
+        if ((r = upload_vec(c, d.q_off, q_off))) return r;
+        ENSURE(c, d.q_len, (size_t)n * 4);
+        HIPCHK(c, hipMemcpyAsync(d.q_len.p, b->q_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        p.op_begin = (const uint64_t *)d.op_begin.p; p.ops = (uint32_t *)cg.ops.p;
+        p.t = (const uint8_t *)cg.t.p; p.t_base = (const uint64_t *)d.t_base.p; p.t_room = (const uint32_t *)d.t_room.p;
+        p.q_off = (const uint64_t *)d.q_off.p; p.q_len = (const uint32_t *)d.q_len.p; p.q = (uint8_t *)cg.q.p;
         hipLaunchKernelGGL(k_cs_write, dim3((n + 3u) / 4u), dim3(256), 0, s, p);
         HIPCHK(c, hipGetLastError());
     }
@@ -2055,67 +2118,53 @@ int upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *w
     cb.n_targets = T; cb.tlen = b->tlen; cb.t_off = b->t_off; cb.t_blob = b->t_blob; cb.t_bytes = b->t_bytes;
     cb.rec_begin = b->rec_begin; cb.pos = b->pos; cb.q_off = q_off.data(); cb.q_len = b->q_len; cb.q_bytes = q_bytes;
     cb.op_begin = opb.data();
-    r = wn ? upload_cigar_windows(ctx, &cb, wn, false, nullptr, &cs) : upload_cigar(ctx, &cb, false, nullptr, &cs);
+    r = upload_records(ctx, &cb, wn, RecordSource::decoded(cs));
     if (r != DAGCON_OK) (void)hipStreamSynchronize(s);            // (the locals above may go)
     return r;
 }
 
+// what every dagcon_consensus_* of this intake is: upload, run, fetch
+template <typename Upload>
+int upload_run_fetch(dagcon_ctx *ctx, dagcon_results *results, Upload upload) {
+    if (!results) return DAGCON_ERR_INVALID_ARG;
+    int r = upload();
+    if (r != DAGCON_OK) return r;
+    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
+    return dagcon_fetch(ctx, results);
+}
 }  // namespace
 extern "C" {
 
 int dagcon_upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *wn) { return upload_cs(ctx, b, wn); }
-int dagcon_consensus_cs(dagcon_ctx *ctx, const dagcon_cs_batch *batch, const dagcon_windows *windows, dagcon_results *results) {
-    if (!results) return DAGCON_ERR_INVALID_ARG;
-    int r = dagcon_upload_cs(ctx, batch, windows);
-    if (r != DAGCON_OK) return r;
-    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
-    return dagcon_fetch(ctx, results);
-}
-
-int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) { return upload_cigar(ctx, b, false); }
+int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) { return upload_records(ctx, b, nullptr, RecordSource::plain()); }
 int dagcon_upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
-    return upload_cigar_windows(ctx, b, wn, false);
+    return wn ? upload_records(ctx, b, wn, RecordSource::plain()) : DAGCON_ERR_INVALID_ARG;
 }
 // q_blob as a BAM record's seq field has it, two bases a byte (k_cigar.hip.h); windows may be NULL
 int dagcon_upload_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
-    return wn ? upload_cigar_windows(ctx, b, wn, true) : upload_cigar(ctx, b, true);
+    return upload_records(ctx, b, wn, RecordSource::packed());
 }
-int dagcon_consensus_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, dagcon_results *results) {
-    if (!results) return DAGCON_ERR_INVALID_ARG;
-    int r = dagcon_upload_cigar_packed(ctx, batch, windows);
-    if (r != DAGCON_OK) return r;
-    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
-    return dagcon_fetch(ctx, results);
-}
-
 // q_blob as the reads file has it, reverse[r] != 0: the ops are written against the reverse complement (k_cigar.hip.h);
 // windows and reverse may be NULL
 int dagcon_upload_cigar_strand(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, const uint8_t *reverse) {
-    return wn ? upload_cigar_windows(ctx, b, wn, false, reverse) : upload_cigar(ctx, b, false, reverse);
+    return upload_records(ctx, b, wn, RecordSource::stranded(reverse));
+}
+
+int dagcon_consensus_cs(dagcon_ctx *ctx, const dagcon_cs_batch *batch, const dagcon_windows *windows, dagcon_results *results) {
+    return upload_run_fetch(ctx, results, [&] { return dagcon_upload_cs(ctx, batch, windows); });
+}
+int dagcon_consensus_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, dagcon_results *results) {
+    return upload_run_fetch(ctx, results, [&] { return dagcon_upload_cigar(ctx, batch); });
+}
+int dagcon_consensus_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, dagcon_results *results) {
+    return upload_run_fetch(ctx, results, [&] { return dagcon_upload_cigar_windows(ctx, batch, windows); });
+}
+int dagcon_consensus_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, dagcon_results *results) {
+    return upload_run_fetch(ctx, results, [&] { return dagcon_upload_cigar_packed(ctx, batch, windows); });
 }
 int dagcon_consensus_cigar_strand(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, const uint8_t *reverse,
                                   dagcon_results *results) {
-    if (!results) return DAGCON_ERR_INVALID_ARG;
-    int r = dagcon_upload_cigar_strand(ctx, batch, windows, reverse);
-    if (r != DAGCON_OK) return r;
-    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
-    return dagcon_fetch(ctx, results);
-}
-
-int dagcon_consensus_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, dagcon_results *results) {
-    if (!results) return DAGCON_ERR_INVALID_ARG;
-    int r = dagcon_upload_cigar_windows(ctx, batch, windows);
-    if (r != DAGCON_OK) return r;
-    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
-    return dagcon_fetch(ctx, results);
-}
-
-int dagcon_consensus_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, dagcon_results *results) {
-    if (!results) return DAGCON_ERR_INVALID_ARG;
-    int r = dagcon_upload_cigar(ctx, batch);
-    if (r != DAGCON_OK) return r;
-    if ((r = dagcon_run(ctx)) != DAGCON_OK) return r;
-    return dagcon_fetch(ctx, results);
+    return upload_run_fetch(ctx, results, [&] { return dagcon_upload_cigar_strand(ctx, batch, windows, reverse); });
 }
 
 int dagcon_host_alloc(dagcon_ctx *ctx, size_t bytes, void **out) {

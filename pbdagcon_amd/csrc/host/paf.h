@@ -29,6 +29,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "intake.h"
 #include "sam.h"
 
 // the complement of include/dagcon.h: A<->T, C<->G in either case, every other byte as it is
@@ -281,53 +282,36 @@ struct DgPafInput {
     }
 };
 
-// the grouped records as windows.h's driver takes them
-struct DgPafSource {
-    static constexpr bool packed = false;
-    static constexpr bool stranded = true;
-    static constexpr bool cs = false;
+// the grouped records as windows.h's driver takes them, the one place a DgPafRec becomes its record.  DG_REC_STRANDED:
+// the read's slice, a strand flag and the cg:Z: ops; DG_REC_CS: q is the record's cs text (cs_len bytes), q_len the read
+// bases it claims, no ops
+template <DgRecordKind K>
+struct DgPafSourceOf {
+    static constexpr DgRecordKind kind = K;
     static constexpr const char *unit = "line";
     static constexpr const char *skipped_what = "PAF lines skipped (tp:A:S)";
     const DgPafInput &in;
     size_t at = 0;
     unsigned long long skipped;
-    DgPafSource(const DgPafInput &i, const DgRefSeqs &) : in(i), skipped(i.n_secondary) {}
+    DgPafSourceOf(const DgPafInput &i, const DgRefSeqs &) : in(i), skipped(i.n_secondary) {}
     template <class AlnRec>
     int next(AlnRec &r, std::vector<uint32_t> &ops) {
         if (at >= in.recs.size()) return 0;
         const DgPafRec &p = in.recs[at++];
         r.rname = p.tname; r.rname_len = p.tname_len;
         r.pos = p.pos;
-        r.q = p.q; r.q_len = p.q_len; r.nops = p.nops;
-        r.reverse = p.reverse;
+        r.q_len = p.q_len;
         r.where = p.line;
+        if (K == DG_REC_CS) {
+            r.q = p.cg; r.nops = 0; r.reverse = false;
+            r.cs_len = p.cg_len; r.t_span = p.t_span;
+            return 1;
+        }
+        r.q = p.q; r.nops = p.nops; r.reverse = p.reverse;
         ops.resize(ops.size() + p.nops);
         dg_cigar_ops(p.cg, p.cg_len, ops.data() + ops.size() - p.nops);
         return 1;
     }
 };
-
-// the same for --cs: q is the record's cs text (cs_len bytes), q_len the read bases it claims, no ops
-struct DgPafCsSource {
-    static constexpr bool packed = false;
-    static constexpr bool stranded = false;
-    static constexpr bool cs = true;
-    static constexpr const char *unit = "line";
-    static constexpr const char *skipped_what = "PAF lines skipped (tp:A:S)";
-    const DgPafInput &in;
-    size_t at = 0;
-    unsigned long long skipped;
-    DgPafCsSource(const DgPafInput &i, const DgRefSeqs &) : in(i), skipped(i.n_secondary) {}
-    template <class AlnRec>
-    int next(AlnRec &r, std::vector<uint32_t> &) {
-        if (at >= in.recs.size()) return 0;
-        const DgPafRec &p = in.recs[at++];
-        r.rname = p.tname; r.rname_len = p.tname_len;
-        r.pos = p.pos;
-        r.q = p.cg; r.q_len = p.q_len; r.nops = 0;
-        r.cs_len = p.cg_len; r.t_span = p.t_span;
-        r.reverse = false;
-        r.where = p.line;
-        return 1;
-    }
-};
+using DgPafSource = DgPafSourceOf<DG_REC_STRANDED>;
+using DgPafCsSource = DgPafSourceOf<DG_REC_CS>;

@@ -336,32 +336,21 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
     dagcon_results r;
     int rc = DAGCON_OK;
     bool have_results = false;
-    if (o.cs) {
-        // position + cs text per record, the target's bases once: decoded and expanded on the device
-        dagcon_cs_batch sb;
-        memset(&sb, 0, sizeof sb);
-        sb.n_targets = db.n_targets; sb.tlen = b.tlen.data(); sb.t_off = b.toff.data();
-        sb.t_blob = b.t.data(); sb.t_bytes = b.t.size(); sb.rec_begin = b.begin.data();
-        sb.pos = b.start.data(); sb.q_len = b.len.data(); sb.t_span = b.tspan.data();
-        sb.cs_off = b.off.data(); sb.cs_len = b.len2.data(); sb.cs_blob = b.q.data(); sb.cs_bytes = b.q.size();
-        const double ta0 = wall();
-        rc = dagcon_consensus_cs(ctx, &sb, nullptr, &r);
-        if (g_timing) fprintf(stderr, "pbdagcon timing: --paf --cs batch of %zu records: dagcon_consensus_cs %.3f\n", b.start.size(), wall() - ta0);
-        have_results = true;
-    } else if (o.sam) {
-        // position + read + CIGAR per record, the target's bases once: expanded on the device
-        dagcon_cigar_batch cb;
-        memset(&cb, 0, sizeof cb);
-        cb.n_targets = db.n_targets; cb.tlen = b.tlen.data(); cb.t_off = b.toff.data();
-        cb.t_blob = b.t.data(); cb.t_bytes = b.t.size(); cb.rec_begin = b.begin.data();
-        cb.pos = b.start.data(); cb.q_off = b.off.data(); cb.q_len = b.len.data();
-        cb.q_blob = b.q.data(); cb.q_bytes = b.q.size(); cb.op_begin = b.opb.data(); cb.ops = b.ops.data();
+    if (o.sam) {
+        // position + read + CIGAR (--cs: cs text) per record, the target's bases once: expanded on the device
+        const DgRecordKind kind = o.cs ? DG_REC_CS : o.paf ? DG_REC_STRANDED : o.bam ? DG_REC_PACKED : DG_REC_PLAIN;
         std::vector<uint8_t> rev;                           // --paf: one strand flag per record, applied on the device
-        if (o.paf) { rev.resize(b.strand.size() + 1); for (size_t a = 0; a < b.strand.size(); a++) rev[a] = b.strand[a] == '-'; }
+        if (kind == DG_REC_STRANDED) { rev.resize(b.strand.size() + 1); for (size_t a = 0; a < b.strand.size(); a++) rev[a] = b.strand[a] == '-'; }
+        DgRecordArrays ra{};
+        ra.cb.n_targets = db.n_targets; ra.cb.tlen = b.tlen.data(); ra.cb.t_off = b.toff.data();
+        ra.cb.t_blob = b.t.data(); ra.cb.t_bytes = b.t.size(); ra.cb.rec_begin = b.begin.data();
+        ra.cb.pos = b.start.data(); ra.cb.q_off = b.off.data(); ra.cb.q_len = b.len.data();
+        ra.cb.q_blob = b.q.data(); ra.cb.q_bytes = b.q.size(); ra.cb.op_begin = b.opb.data(); ra.cb.ops = b.ops.data();
+        ra.reverse = rev.data(); ra.cs_len = b.len2.data(); ra.t_span = b.tspan.data();
         const double ta0 = wall();
-        rc = o.paf ? dagcon_consensus_cigar_strand(ctx, &cb, nullptr, rev.data(), &r)
-           : o.bam ? dagcon_consensus_cigar_packed(ctx, &cb, nullptr, &r) : dagcon_consensus_cigar(ctx, &cb, &r);
-        if (g_timing) fprintf(stderr, "pbdagcon timing: %s batch of %zu records: dagcon_consensus_cigar%s %.3f\n", o.paf ? "--paf" : o.bam ? "--bam" : "--sam", b.start.size(), o.paf ? "_strand" : o.bam ? "_packed" : "", wall() - ta0);
+        rc = dg_consensus_records(ctx, kind, ra, nullptr, &r);
+        if (g_timing && o.cs) fprintf(stderr, "pbdagcon timing: --paf --cs batch of %zu records: dagcon_consensus_cs %.3f\n", b.start.size(), wall() - ta0);
+        else if (g_timing) fprintf(stderr, "pbdagcon timing: %s batch of %zu records: dagcon_consensus_cigar%s %.3f\n", o.paf ? "--paf" : o.bam ? "--bam" : "--sam", b.start.size(), o.paf ? "_strand" : o.bam ? "_packed" : "", wall() - ta0);
         have_results = true;
     } else if (o.align && !o.polish) {
         // main.cpp:117-145 with -a in one call: the aligned strings stay on the device
@@ -556,8 +545,7 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
         // AlnGraphBoost.cpp:71-72): warn, go on with the rest
         if (r.target_status[g] != DAGCON_OK)
             fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(),
-                    r.target_status[g] == DAGCON_ERR_NONCONFORMING && o.cs ? "a line's cs:Z: text breaks the grammar or does not fit its qe - qs, its te - ts or its target"
-                    : r.target_status[g] == DAGCON_ERR_NONCONFORMING && o.sam ? "a record's CIGAR does not fit its SEQ or its target, or holds N or a length of 0"
+                    r.target_status[g] == DAGCON_ERR_NONCONFORMING && o.sam ? dg_nonconforming_text(o.cs)
                     : r.target_status[g] == DAGCON_ERR_NONCONFORMING ? "an alignment leaves the backbone or holds a non-printable byte"
                     : r.target_status[g] == DAGCON_ERR_UNSUPPORTED ? "too large" : "internal error");
         for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
@@ -896,23 +884,15 @@ int main(int argc, char **argv) {
                 pt.lines++;
                 if (o.sam) {
                     // QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL, tab-separated; header lines skipped
-                    if (ll == 0 || line[0] == '@') continue;
-                    const char *sf[10];
-                    size_t sl[10];
-                    int snf = 0;
-                    for (size_t i = 0; snf < 10; snf++) {
-                        const char *tab = (const char *)memchr(line + i, '\t', ll - i);
-                        const size_t j = tab ? (size_t)(tab - line) : ll;
-                        sf[snf] = line + i; sl[snf] = j - i;
-                        if (!tab) { snf++; break; }
-                        i = j + 1;
-                    }
-                    if (snf < 10) { pt.err = 1; pt.err_rec = pt.lines; pt.err_nf = snf; return; }
-                    const uint32_t flag = tok_u32(sf[1], sl[1]);
-                    auto star = [&](int x) { return sl[x] == 1 && sf[x][0] == '*'; };
-                    if ((flag & (DG_SAM_UNMAPPED | DG_SAM_SECONDARY)) || star(2) || star(5) || star(9)) { pt.skipped++; continue; }
-                    const long nops = dg_cigar_ops(sf[5], sl[5], nullptr);
-                    if (nops < 0) { pt.err = 3; pt.err_rec = pt.lines; return; }
+                    DgSamLine sm;
+                    const DgSamWhat what = dg_sam_split(line, ll, sm, tok_u32);
+                    if (what == DG_SAM_NO_RECORD) continue;
+                    if (what == DG_SAM_SKIPPED) { pt.skipped++; continue; }
+                    if (what == DG_SAM_FEW_FIELDS) { pt.err = 1; pt.err_rec = pt.lines; pt.err_nf = sm.nf; return; }
+                    if (what == DG_SAM_BAD_CIGAR) { pt.err = 3; pt.err_rec = pt.lines; return; }
+                    const char *const *sf = sm.f; const size_t *sl = sm.fl;
+                    const uint32_t flag = sm.flag;
+                    const long nops = sm.nops;
                     const DgRefSeqs::Span *sp = ref.find(sf[2], sl[2]);
                     if (!sp) { pt.err = 4; pt.err_rec = pt.lines; return; }
                     Rec r;

@@ -97,6 +97,35 @@ inline long dg_cigar_ops(const char *s, size_t n, uint32_t *out) {
     return k;
 }
 
+// One line of SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ [QUAL ...], tab-separated.  The one splitter
+// of the host: fields 0..9, the rule that keeps a record out (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*') and the
+// number of the CIGAR's ops.  flag_of(field, length) reads FLAG the caller's way; every caller words its own errors.
+struct DgSamLine {
+    const char *f[10]; size_t fl[10];
+    int nf;                                                // fields found, at most 10
+    uint32_t flag;
+    long nops;                                             // DG_SAM_RECORD only
+};
+enum DgSamWhat { DG_SAM_RECORD, DG_SAM_NO_RECORD /* empty, or a header line */, DG_SAM_SKIPPED, DG_SAM_FEW_FIELDS, DG_SAM_BAD_CIGAR };
+template <class FlagOf>
+inline DgSamWhat dg_sam_split(const char *line, size_t ll, DgSamLine &s, FlagOf flag_of) {
+    s.nf = 0;
+    if (ll == 0 || line[0] == '@') return DG_SAM_NO_RECORD;
+    for (size_t i = 0; s.nf < 10;) {
+        const char *tab = (const char *)memchr(line + i, '\t', ll - i);
+        const size_t j = tab ? (size_t)(tab - line) : ll;
+        s.f[s.nf] = line + i; s.fl[s.nf] = j - i; s.nf++;
+        if (!tab) break;
+        i = j + 1;
+    }
+    if (s.nf < 10) return DG_SAM_FEW_FIELDS;
+    s.flag = (uint32_t)flag_of(s.f[1], s.fl[1]);
+    auto star = [&](int k) { return s.fl[k] == 1 && s.f[k][0] == '*'; };
+    if ((s.flag & (DG_SAM_UNMAPPED | DG_SAM_SECONDARY)) || star(2) || star(5) || star(9)) return DG_SAM_SKIPPED;
+    s.nops = dg_cigar_ops(s.f[5], s.fl[5], nullptr);
+    return s.nops < 0 ? DG_SAM_BAD_CIGAR : DG_SAM_RECORD;
+}
+
 // the CIGAR text of BAM-encoded ops (--dump-parsed)
 inline std::string dg_cigar_text(const uint32_t *ops, size_t n) {
     std::string s;

@@ -30,6 +30,7 @@
 #include "../../../include/dagcon.h"
 #include "bam.h"
 #include "fastq.h"
+#include "intake.h"
 #include "sam.h"
 
 struct DgStitchPiece {
@@ -91,9 +92,7 @@ struct DgAlnRec {
 
 // SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
 struct DgSamSource {
-    static constexpr bool packed = false;
-    static constexpr bool stranded = false;
-    static constexpr bool cs = false;
+    static constexpr DgRecordKind kind = DG_REC_PLAIN;
     static constexpr const char *unit = "line";
     static constexpr const char *skipped_what = "SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')";
     const char *data; size_t size, p = 0;
@@ -108,23 +107,18 @@ struct DgSamSource {
             p += ll + (nl ? 1 : 0);
             lineno++;
             if (ll && line[ll - 1] == '\r') ll--;
-            if (ll == 0 || line[0] == '@') continue;
-            const char *f[11]; size_t fl[11]; int nf = 0;
-            for (size_t i = 0; nf < 11;) {
-                const char *tab = (const char *)memchr(line + i, '\t', ll - i);
-                const size_t j = tab ? (size_t)(tab - line) : ll;
-                f[nf] = line + i; fl[nf] = j - i; nf++;
-                if (!tab) break;
-                i = j + 1;
+            DgSamLine sl;
+            uint64_t pos = 0;
+            switch (dg_sam_split(line, ll, sl, [](const char *f, size_t n) { uint64_t v = 0; for (size_t i = 0; i < n && f[i] >= '0' && f[i] <= '9'; i++) v = v * 10 + (uint64_t)(f[i] - '0'); return v; })) {
+                case DG_SAM_NO_RECORD: continue;
+                case DG_SAM_SKIPPED: skipped++; continue;
+                case DG_SAM_FEW_FIELDS: fprintf(stderr, "pbdagcon: line %llu: a SAM record has 11 fields, this one has fewer than 10 fields\n", lineno); return -1;
+                case DG_SAM_BAD_CIGAR: fprintf(stderr, "pbdagcon: line %llu: malformed CIGAR %.*s\n", lineno, (int)std::min<size_t>(sl.fl[5], 60), sl.f[5]); return -1;
+                case DG_SAM_RECORD: break;
             }
-            if (nf < 10) { fprintf(stderr, "pbdagcon: line %llu: a SAM record has 11 fields, this one has fewer than 10 fields\n", lineno); return -1; }
-            auto star = [&](int k) { return fl[k] == 1 && f[k][0] == '*'; };
-            uint64_t flag = 0, pos = 0;
-            for (size_t i = 0; i < fl[1] && f[1][i] >= '0' && f[1][i] <= '9'; i++) flag = flag * 10 + (uint64_t)(f[1][i] - '0');
+            const char *const *f = sl.f; const size_t *fl = sl.fl;
+            const long k = sl.nops;
             for (size_t i = 0; i < fl[3] && f[3][i] >= '0' && f[3][i] <= '9' && pos < (1ull << 40); i++) pos = pos * 10 + (uint64_t)(f[3][i] - '0');
-            if ((flag & (DG_SAM_UNMAPPED | DG_SAM_SECONDARY)) || star(2) || star(5) || star(9)) { skipped++; continue; }
-            const long k = dg_cigar_ops(f[5], fl[5], nullptr);
-            if (k < 0) { fprintf(stderr, "pbdagcon: line %llu: malformed CIGAR %.*s\n", lineno, (int)std::min<size_t>(fl[5], 60), f[5]); return -1; }
             r.rname = f[2]; r.rname_len = fl[2];
             r.pos = pos > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pos;
             r.q = f[9]; r.q_len = (uint32_t)fl[9]; r.nops = (uint32_t)k;
@@ -139,9 +133,7 @@ struct DgSamSource {
 
 // BAM records (bam.h); the header's references were checked against --ref when the file was opened
 struct DgBamSource {
-    static constexpr bool packed = true;
-    static constexpr bool stranded = false;
-    static constexpr bool cs = false;
+    static constexpr DgRecordKind kind = DG_REC_PACKED;
     static constexpr const char *unit = "record";
     static constexpr const char *skipped_what = "BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)";
     DgBamReader &bam;
@@ -190,13 +182,13 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         r.pos = ar.pos;
         if (!t.recs.empty() && r.pos < t.recs.back().pos) { fprintf(stderr, "pbdagcon: %s %llu: POS %u of RNAME %s is below that of the record before it (--window needs records ascending in POS, as in a coordinate-sorted SAM)\n", Source::unit, ar.where, r.pos, rname.c_str()); return 1; }
         r.q = ar.q; r.q_len = ar.q_len; r.op0 = ops.size() - ar.nops; r.nops = ar.nops;
-        r.reverse = Source::stranded && ar.reverse;
-        r.cs_len = Source::cs ? ar.cs_len : 0u; r.t_span = Source::cs ? ar.t_span : 0u;
+        r.reverse = (Source::kind == DG_REC_STRANDED) && ar.reverse;
+        r.cs_len = (Source::kind == DG_REC_CS) ? ar.cs_len : 0u; r.t_span = (Source::kind == DG_REC_CS) ? ar.t_span : 0u;
         const long k = (long)ar.nops;
         // [s, e) by the rule of include/dagcon.h (a non-conforming record: clipped into the target, at least one base)
         uint64_t nt = 0;
         for (long i = 0; i < k; i++) { const uint32_t op = ops[r.op0 + i]; if ((1u << (op & 15u)) & 0x185u) nt += op >> 4; }
-        if (Source::cs) nt = ar.t_span;                        // (the device holds the text to it)
+        if ((Source::kind == DG_REC_CS)) nt = ar.t_span;                        // (the device holds the text to it)
         const uint64_t tl = t.sp.len;
         uint64_t s0 = r.pos ? r.pos - 1u : 0u, e0 = s0 + (nt & 0xFFFFFFFFull);
         if (tl && s0 > tl - 1) s0 = tl - 1;
@@ -274,36 +266,26 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             for (; it != t.recs.end() && it->s < hi; ++it) {
                 if (it->e <= lo) continue;
                 b_pos.push_back(it->pos); b_qoff.push_back(qblob.size()); b_qlen.push_back(it->q_len);
-                qblob.append(it->q, Source::cs ? it->cs_len : Source::packed ? ((size_t)it->q_len + 1) / 2 : it->q_len);
-                if (Source::cs) { b_cslen.push_back(it->cs_len); b_tspan.push_back(it->t_span); }
+                qblob.append(it->q, (Source::kind == DG_REC_CS) ? it->cs_len : (Source::kind == DG_REC_PACKED) ? ((size_t)it->q_len + 1) / 2 : it->q_len);
+                if ((Source::kind == DG_REC_CS)) { b_cslen.push_back(it->cs_len); b_tspan.push_back(it->t_span); }
                 b_ops.insert(b_ops.end(), ops.begin() + (long)it->op0, ops.begin() + (long)(it->op0 + it->nops));
                 b_opb.push_back(b_ops.size());
-                if (Source::stranded) b_rev.push_back(it->reverse ? 1 : 0);
+                if ((Source::kind == DG_REC_STRANDED)) b_rev.push_back(it->reverse ? 1 : 0);
             }
             b_rec.push_back(b_pos.size());
             for (size_t k = a; k < z; k++) { w_t.push_back(bt); w_b.push_back(wins[k].begin); w_e.push_back(wins[k].end); }
             a = z;
         }
-        dagcon_cigar_batch cb;
-        memset(&cb, 0, sizeof cb);
-        cb.n_targets = (uint32_t)b_tlen.size(); cb.tlen = b_tlen.data(); cb.t_off = b_toff.data();
-        cb.t_blob = ref.bases.data(); cb.t_bytes = ref.bases.size();
-        cb.rec_begin = b_rec.data(); cb.pos = b_pos.data(); cb.q_off = b_qoff.data(); cb.q_len = b_qlen.data();
-        cb.q_blob = qblob.data(); cb.q_bytes = qblob.size(); cb.op_begin = b_opb.data(); cb.ops = b_ops.data();
+        DgRecordArrays ra{};
+        ra.cb.n_targets = (uint32_t)b_tlen.size(); ra.cb.tlen = b_tlen.data(); ra.cb.t_off = b_toff.data();
+        ra.cb.t_blob = ref.bases.data(); ra.cb.t_bytes = ref.bases.size();
+        ra.cb.rec_begin = b_rec.data(); ra.cb.pos = b_pos.data(); ra.cb.q_off = b_qoff.data(); ra.cb.q_len = b_qlen.data();
+        ra.cb.q_blob = qblob.data(); ra.cb.q_bytes = qblob.size(); ra.cb.op_begin = b_opb.data(); ra.cb.ops = b_ops.data();
+        ra.reverse = b_rev.data(); ra.cs_len = b_cslen.data(); ra.t_span = b_tspan.data();
         dagcon_windows dw;
         dw.n_windows = (uint32_t)w_t.size(); dw.target = w_t.data(); dw.begin = w_b.data(); dw.end = w_e.data();
         dagcon_results r;
-        if (Source::cs) {
-            dagcon_cs_batch sb;
-            memset(&sb, 0, sizeof sb);
-            sb.n_targets = cb.n_targets; sb.tlen = cb.tlen; sb.t_off = cb.t_off; sb.t_blob = cb.t_blob; sb.t_bytes = cb.t_bytes;
-            sb.rec_begin = cb.rec_begin; sb.pos = cb.pos; sb.q_len = cb.q_len; sb.t_span = b_tspan.data();
-            sb.cs_off = b_qoff.data(); sb.cs_len = b_cslen.data(); sb.cs_blob = qblob.data(); sb.cs_bytes = qblob.size();
-            rc = dagcon_consensus_cs(ctx, &sb, &dw, &r);
-        } else
-        rc = Source::packed ? dagcon_consensus_cigar_packed(ctx, &cb, &dw, &r)
-           : Source::stranded ? dagcon_consensus_cigar_strand(ctx, &cb, &dw, b_rev.data(), &r)
-                              : dagcon_consensus_cigar_windows(ctx, &cb, &dw, &r);
+        rc = dg_consensus_records(ctx, Source::kind, ra, &dw, &r);
         const uint32_t *pos = nullptr;
         uint64_t npos = 0;
         dagcon_support sup;
@@ -320,7 +302,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             const size_t g = k - w0;
             if (r.target_status[g] != DAGCON_OK)
                 fprintf(stderr, "pbdagcon: warning: %s window [%u, %u) skipped (%s)\n", tgts[w.tgt].name.c_str(), w.begin, w.end,
-                        r.target_status[g] == DAGCON_ERR_NONCONFORMING ? "a record's CIGAR does not fit its SEQ or its target, or holds N or a length of 0"
+                        r.target_status[g] == DAGCON_ERR_NONCONFORMING ? dg_nonconforming_text(false)
                         : r.target_status[g] == DAGCON_ERR_UNSUPPORTED ? "too large" : "internal error");
             if (o.verbose) fprintf(stderr, "pbdagcon: %s window %u [%u, %u): %llu segments\n", tgts[w.tgt].name.c_str(), w.idx, w.begin, w.end,
                                    (unsigned long long)(r.seg_begin[g + 1] - r.seg_begin[g]));

@@ -159,56 +159,87 @@ __device__ __forceinline__ uint8_t dg_cg_qbase_strand(const uint8_t *q, uint32_t
     return rev ? dg_cg_comp(b) : b;
 }
 
-// a wave per tile of 64 ops
+// The one definition of "a tile's ops, decoded and summed": lane l of the wave takes op l of the k-th tile of record r
+// (nothing past the record's last op), turns it into its three increments and takes their inclusive prefix sums over
+// the wave.  What a caller leaves unused (dg_cg_find: the read bases) costs nothing: the body is inlined
+struct DgCgTile {
+    uint32_t code;                 // BAM op code (0 for a lane past the record's ops: no increments)
+    uint32_t i_col, i_q, i_t;      // the op's columns, read bases, target bases
+    uint32_t e_col, e_q, e_t;      // the same summed over lanes 0 .. l
+};
+__device__ __forceinline__ DgCgTile dg_cg_tile(const DgCigarParams &p, uint32_t r, uint64_t k, uint32_t lane) {
+    const uint64_t o = p.op_begin[r] + k * 64u, oe = p.op_begin[r + 1];
+    const bool have = o + lane < oe;
+    const uint32_t op = have ? p.ops[o + lane] : 0u;
+    const uint32_t len = op >> 4;
+    DgCgTile t;
+    t.code = op & 15u;
+    const uint32_t bit = have ? 1u << t.code : 0u;
+    t.i_col = (bit & DG_CG_COL_MASK) ? len : 0u;
+    t.i_q = (bit & DG_CG_Q_MASK) ? len : 0u;
+    t.i_t = (bit & DG_CG_T_MASK) ? len : 0u;
+    t.e_col = dg_cg_scan32(t.i_col);
+    t.e_q = dg_cg_scan32(t.i_q); t.e_t = dg_cg_scan32(t.i_t);
+    return t;
+}
+
+// The one expand body: a wave writes the columns of the k-th tile of record r (ck its checkpoint) that lie inside the
+// record's columns [c0, c1), column c at oq / ot + c - c0.  k_cigar_expand asks for all of a record (c0 = 0, c1 past any
+// column), k_cigar_expand_cut for a piece ([F(A), F(B)) below).
+// Out-of-bounds safety, for every caller: r is a conforming record (above), so the sums recomputed here from the same
+// device copy of the ops are the scan's: a read-base index lies inside [0, q_len), a target-base index inside
+// [pos - 1, pos - 1 + target bases), a tile's columns inside [0, columns); a store goes to c - c0 with c0 <= c < c1 and
+// c < columns, so inside the min(c1, columns) - c0 bytes the host gave the caller at oq / ot.
 template <bool PACKED, bool STRAND>
-__device__ __forceinline__ void dg_cg_expand(const DgCigarParams &p, const DgCigarStrand &st) {
+__device__ __forceinline__ void dg_cg_expand_tile(const DgCigarParams &p, const DgCigarStrand &st, uint32_t r, uint64_t k, const uint4 ck,
+                                                  uint32_t c0, uint32_t c1, uint8_t *oq, uint8_t *ot) {
     static_assert(!(PACKED && STRAND), "packed bases carry no strand");
     __shared__ uint32_t s_end[64], s_q0[64], s_t0[64], s_code[64];
     const uint32_t lane = threadIdx.x;
-    const uint32_t tile = blockIdx.x;
-    if (tile >= p.n_tiles) return;
-    const uint4 ck = p.ckpt[tile];
-    const uint32_t r = ck.w;
-    const uint64_t out = p.out_off[r];
-    if (out == DG_CG_SKIP) return;                                // (wave-uniform: nobody reaches the barrier)
-    const uint64_t o = p.op_begin[r] + (uint64_t)(tile - p.tile_begin[r]) * 64u, oe = p.op_begin[r + 1];
-    const bool have = o + lane < oe;
-    const uint32_t op = have ? p.ops[o + lane] : 0u;
-    const uint32_t code = op & 15u, len = op >> 4;
-    const uint32_t bit = have ? 1u << code : 0u;
-    const uint32_t i_col = (bit & DG_CG_COL_MASK) ? len : 0u;
-    const uint32_t i_q = (bit & DG_CG_Q_MASK) ? len : 0u;
-    const uint32_t i_t = (bit & DG_CG_T_MASK) ? len : 0u;
-    const uint32_t e_col = dg_cg_scan32(i_col);
-    const uint32_t e_q = dg_cg_scan32(i_q), e_t = dg_cg_scan32(i_t);
-    s_end[lane] = e_col;
-    s_q0[lane] = ck.y + e_q - i_q;                                // the op's first read base
-    s_t0[lane] = ck.z + e_t - i_t;                                // its first target base, from pos - 1
-    s_code[lane] = code;
+    const DgCgTile tl = dg_cg_tile(p, r, k, lane);
+    s_end[lane] = tl.e_col;
+    s_q0[lane] = ck.y + tl.e_q - tl.i_q;                          // the op's first read base
+    s_t0[lane] = ck.z + tl.e_t - tl.i_t;                          // its first target base, from pos - 1
+    s_code[lane] = tl.code;
     __syncthreads();
-    const uint32_t n_col = (uint32_t)__builtin_amdgcn_readlane((int)e_col, 63);
+    const uint32_t n_col = (uint32_t)__builtin_amdgcn_readlane((int)tl.e_col, 63);
+    // the tile's columns are [ck.x, ck.x + n_col) of the record: those inside [c0, c1), tile-relative
+    const uint32_t c_lo = c0 > ck.x ? c0 - ck.x : 0u;
+    const uint32_t c_hi = c1 > ck.x ? (c1 - ck.x < n_col ? c1 - ck.x : n_col) : 0u;
     const uint8_t *q = p.q + p.q_off[r];
     const uint8_t *t = p.t + p.t_base[r];
-    uint8_t *oq = p.out_q + out + ck.x, *ot = p.out_t + out + ck.x;
     bool rev = false;
     uint32_t last = 0;
     if constexpr (STRAND) {                                       // (r is wave-uniform: scalar loads, once per wave)
         rev = st.rev[r] != 0;
         last = st.q_len[r] - 1u;                                  // (read only for a base index below q_len >= 1)
     }
-    for (uint32_t c = lane; c < n_col; c += 64u) {
+    for (uint32_t c = c_lo + lane; c < c_hi; c += 64u) {
         // the first op whose columns end past c
         uint32_t lo = 0;
 #pragma unroll
         for (uint32_t step = 32u; step; step >>= 1)
             if (s_end[lo + step - 1u] <= c) lo += step;
         const uint32_t first = lo ? s_end[lo - 1u] : 0u;          // (an op without columns ends where it begins: never found)
-        const uint32_t k = c - first;
+        const uint32_t kk = c - first;
         const uint32_t b = 1u << s_code[lo];
-        if constexpr (STRAND) oq[c] = (b & DG_CG_Q_MASK) ? dg_cg_qbase_strand(q, s_q0[lo] + k, rev, last) : (uint8_t)'-';
-        else oq[c] = (b & DG_CG_Q_MASK) ? dg_cg_qbase<PACKED>(q, s_q0[lo] + k) : (uint8_t)'-';
-        ot[c] = (b & DG_CG_T_MASK) ? t[s_t0[lo] + k] : (uint8_t)'-';
+        const uint32_t at = ck.x + c - c0;                        // (ck.x + c >= c0: c >= c_lo)
+        if constexpr (STRAND) oq[at] = (b & DG_CG_Q_MASK) ? dg_cg_qbase_strand(q, s_q0[lo] + kk, rev, last) : (uint8_t)'-';
+        else oq[at] = (b & DG_CG_Q_MASK) ? dg_cg_qbase<PACKED>(q, s_q0[lo] + kk) : (uint8_t)'-';
+        ot[at] = (b & DG_CG_T_MASK) ? t[s_t0[lo] + kk] : (uint8_t)'-';
     }
+}
+
+// a wave per tile of 64 ops: all of the tile's columns, at the record's own offset
+template <bool PACKED, bool STRAND>
+__device__ __forceinline__ void dg_cg_expand(const DgCigarParams &p, const DgCigarStrand &st) {
+    const uint32_t tile = blockIdx.x;
+    if (tile >= p.n_tiles) return;
+    const uint4 ck = p.ckpt[tile];
+    const uint32_t r = ck.w;
+    const uint64_t out = p.out_off[r];
+    if (out == DG_CG_SKIP) return;                                // (wave-uniform: nobody reaches the barrier)
+    dg_cg_expand_tile<PACKED, STRAND>(p, st, r, tile - p.tile_begin[r], ck, 0u, ~0u, p.out_q + out, p.out_t + out);
 }
 __global__ __launch_bounds__(64) void k_cigar_expand(DgCigarParams p) { dg_cg_expand<false, false>(p, DgCigarStrand{}); }
 __global__ __launch_bounds__(64) void k_cigar_expand_packed(DgCigarParams p) { dg_cg_expand<true, false>(p, DgCigarStrand{}); }
@@ -263,17 +294,10 @@ __device__ __forceinline__ void dg_cg_find(const DgCigarParams &p, uint32_t r, u
     }
     tile = lo;
     const uint4 ck = p.ckpt[tile0 + lo];
-    const uint64_t o = p.op_begin[r] + (uint64_t)lo * 64u, oe = p.op_begin[r + 1];
-    const bool have = o + lane < oe;
-    const uint32_t op = have ? p.ops[o + lane] : 0u;
-    const uint32_t code = op & 15u, len = op >> 4;
-    const uint32_t bit = have ? 1u << code : 0u;
-    const uint32_t i_col = (bit & DG_CG_COL_MASK) ? len : 0u;
-    const uint32_t i_t = (bit & DG_CG_T_MASK) ? len : 0u;
-    const uint32_t e_col = dg_cg_scan32(i_col), e_t = dg_cg_scan32(i_t);
-    const uint32_t t0 = ck.z + e_t - i_t;                         // the op's first target base
-    const unsigned long long hit = __ballot(i_t != 0u && t0 <= x && x - t0 < i_t);
-    const uint32_t mine = ck.x + e_col - i_col + (x - t0);        // (an op with target bases has a column for each)
+    const DgCgTile tl = dg_cg_tile(p, r, lo, lane);
+    const uint32_t t0 = ck.z + tl.e_t - tl.i_t;                   // the op's first target base
+    const unsigned long long hit = __ballot(tl.i_t != 0u && t0 <= x && x - t0 < tl.i_t);
+    const uint32_t mine = ck.x + tl.e_col - tl.i_col + (x - t0);        // (an op with target bases has a column for each)
     col = hit ? (uint32_t)__shfl((int)mine, __ffsll((long long)hit) - 1) : DG_CG_NO_COL;
 }
 
@@ -295,60 +319,16 @@ __global__ __launch_bounds__(256) void k_cigar_cut(DgCigarParams p, DgCigarCutPa
     if (lane == 0) w.cut[pc] = make_uint4(ca, cb, ta, tb);
 }
 
-// a wave per (piece, tile of 64 ops)
+// a wave per (piece, tile of 64 ops): the tile's columns inside [F(A), F(B)), at the piece's own offset
 template <bool PACKED, bool STRAND>
 __device__ __forceinline__ void dg_cg_expand_cut(const DgCigarParams &p, const DgCigarCutParams &w, const DgCigarStrand &st) {
-    static_assert(!(PACKED && STRAND), "packed bases carry no strand");
-    __shared__ uint32_t s_end[64], s_q0[64], s_t0[64], s_code[64];
-    const uint32_t lane = threadIdx.x;
     if (blockIdx.x >= w.n_waves) return;
     const uint32_t pc = w.wave_piece[blockIdx.x];
     const uint32_t r = w.piece[pc].x;
     const uint4 cut = w.cut[pc];
     const uint32_t k = cut.z + (blockIdx.x - w.wave_begin[pc]);   // the record's k-th tile
-    const uint4 ck = p.ckpt[p.tile_begin[r] + k];
-    const uint64_t o = p.op_begin[r] + (uint64_t)k * 64u, oe = p.op_begin[r + 1];
-    const bool have = o + lane < oe;
-    const uint32_t op = have ? p.ops[o + lane] : 0u;
-    const uint32_t code = op & 15u, len = op >> 4;
-    const uint32_t bit = have ? 1u << code : 0u;
-    const uint32_t i_col = (bit & DG_CG_COL_MASK) ? len : 0u;
-    const uint32_t i_q = (bit & DG_CG_Q_MASK) ? len : 0u;
-    const uint32_t i_t = (bit & DG_CG_T_MASK) ? len : 0u;
-    const uint32_t e_col = dg_cg_scan32(i_col);
-    const uint32_t e_q = dg_cg_scan32(i_q), e_t = dg_cg_scan32(i_t);
-    s_end[lane] = e_col;
-    s_q0[lane] = ck.y + e_q - i_q;
-    s_t0[lane] = ck.z + e_t - i_t;
-    s_code[lane] = code;
-    __syncthreads();
-    const uint32_t n_col = (uint32_t)__builtin_amdgcn_readlane((int)e_col, 63);
-    // the tile's columns are [ck.x, ck.x + n_col) of the record: those inside [F(A), F(B)), tile-relative
-    const uint32_t c_lo = cut.x > ck.x ? cut.x - ck.x : 0u;
-    const uint32_t c_hi = cut.y > ck.x ? (cut.y - ck.x < n_col ? cut.y - ck.x : n_col) : 0u;
-    const uint8_t *q = p.q + p.q_off[r];
-    const uint8_t *t = p.t + p.t_base[r];
     const uint64_t out = w.piece_out[pc];
-    uint8_t *oq = p.out_q + out, *ot = p.out_t + out;
-    bool rev = false;
-    uint32_t last = 0;
-    if constexpr (STRAND) {                                       // (as in dg_cg_expand)
-        rev = st.rev[r] != 0;
-        last = st.q_len[r] - 1u;
-    }
-    for (uint32_t c = c_lo + lane; c < c_hi; c += 64u) {
-        uint32_t lo = 0;
-#pragma unroll
-        for (uint32_t step = 32u; step; step >>= 1)
-            if (s_end[lo + step - 1u] <= c) lo += step;
-        const uint32_t first = lo ? s_end[lo - 1u] : 0u;
-        const uint32_t kk = c - first;
-        const uint32_t b = 1u << s_code[lo];
-        const uint32_t at = ck.x + c - cut.x;                     // (ck.x + c >= F(A): c >= c_lo)
-        if constexpr (STRAND) oq[at] = (b & DG_CG_Q_MASK) ? dg_cg_qbase_strand(q, s_q0[lo] + kk, rev, last) : (uint8_t)'-';
-        else oq[at] = (b & DG_CG_Q_MASK) ? dg_cg_qbase<PACKED>(q, s_q0[lo] + kk) : (uint8_t)'-';
-        ot[at] = (b & DG_CG_T_MASK) ? t[s_t0[lo] + kk] : (uint8_t)'-';
-    }
+    dg_cg_expand_tile<PACKED, STRAND>(p, st, r, k, p.ckpt[p.tile_begin[r] + k], cut.x, cut.y, p.out_q + out, p.out_t + out);
 }
 __global__ __launch_bounds__(64) void k_cigar_expand_cut(DgCigarParams p, DgCigarCutParams w) { dg_cg_expand_cut<false, false>(p, w, DgCigarStrand{}); }
 __global__ __launch_bounds__(64) void k_cigar_expand_cut_packed(DgCigarParams p, DgCigarCutParams w) { dg_cg_expand_cut<true, false>(p, w, DgCigarStrand{}); }

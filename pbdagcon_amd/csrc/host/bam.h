@@ -22,7 +22,7 @@
 #include <thread>
 #include <vector>
 
-#include "sam.h"
+#include "intake.h"
 
 // ---- CRC32 (RFC 1952, polynomial 0xEDB88320 reflected), a byte at a time ---------------------------------------------
 struct DgCrcTable {
@@ -438,4 +438,17 @@ inline bool dg_bam_check_refs(const DgBamReader &bam, const DgRefSeqs &ref, std:
         return false;
     }
     return true;
+}
+
+// a record of the reader as the pipeline's record, the one place a DgBamRec becomes one: SEQ and the ops stay as they lie in the file
+inline void dg_bam_rec(const DgBamReader &bam, const DgBamRec &br, const DgRefSeqs &ref, DgAlnRec &r) {
+    const std::string &rn = bam.refs[(size_t)br.ref_id].name;
+    r = DgAlnRec{};
+    r.rname = rn.data(); r.rname_len = (uint32_t)rn.size(); r.target = ref.find(rn.data(), rn.size());
+    r.qname = br.name; r.qname_len = br.name_len;
+    r.pos = br.pos;
+    r.q = (const char *)br.seq; r.q_len = br.l_seq;
+    r.bam_ops = br.ops; r.nops = br.n_ops;
+    r.reverse = (br.flag & DG_SAM_REVERSE) != 0;
+    r.where = br.ordinal;
 }

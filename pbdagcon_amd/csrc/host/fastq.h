@@ -11,6 +11,7 @@
 // tests/support_twin.py is its Python twin.
 #pragma once
 #include <cstdint>
+#include <cstdio>
 #include <string>
 
 #include "../../../include/dagcon.h"
@@ -38,6 +39,23 @@ inline bool dg_append_fastq(std::string &out, const std::string &name, const cha
         if (q < 0) return false;
         out += (char)(33 + q);
     }
+    out += '\n';
+    return true;
+}
+
+// one result record of pbdagcon, ">%s/%d_%d\n%s\n" (main.cpp:141-143), or with fastq '@' for '>' (src/cpp/pbdagcon_wf.sh:20-22),
+// then + and the qualities.  False, with a message, when a quality cannot be computed.
+inline bool dg_append_result(std::string &out, bool fastq, const std::string &id, long long r0, long long r1, const char *seq,
+                             uint32_t len, const uint16_t *weight, const uint16_t *depth) {
+    char head[64];
+    snprintf(head, sizeof head, "/%lld_%lld", r0, r1);
+    if (fastq) {
+        if (dg_append_fastq(out, id + head, seq, len, weight, depth)) return true;
+        fprintf(stderr, "pbdagcon: target %s: per-base support out of range\n", id.c_str());
+        return false;
+    }
+    out += '>'; out += id; out += head; out += '\n';
+    out.append(seq, len);
     out += '\n';
     return true;
 }

@@ -1,11 +1,13 @@
-// intake.h -- where the command-line hosts hand alignment records to the library: one description of a batch's arrays
-// for every kind of input, one call that fills the library's struct and picks the entry point (whole targets or windows),
-// and the text of the warning for a target or window that a record fails.
+// intake.h -- where the command-line hosts hand alignment records to the library: the one record every format becomes (DgAlnRec),
+// one description per kind of input (dg_kind: what the messages say; dg_blob_bytes, dg_blob, dg_rec_ops: what of a record goes to the
+// device), a batch's arrays, the call that picks the entry point, the warning texts, and the one place a context is made.
 #pragma once
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 
 #include "../../../include/dagcon.h"
+#include "sam.h"
 
 enum DgRecordKind {
     DG_REC_PLAIN,       // --sam: one base a byte                          dagcon_consensus_cigar / _cigar_windows
@@ -13,6 +15,64 @@ enum DgRecordKind {
     DG_REC_STRANDED,    // --paf: one base a byte, a flag per record       dagcon_consensus_cigar_strand
     DG_REC_CS           // --paf --cs: no bases, cs:Z: text per record     dagcon_consensus_cs
 };
+
+// what the messages of a kind say
+struct DgKindDesc {
+    const char *flag, *entry;                              // the command line's flags and the library's entry point (timing lines)
+    const char *unit;                                      // what DgAlnRec::where counts: what an error names
+    const char *format;                                    // the file format a user is told to sort
+    const char *skipped_what;                              // behind the number of records left out
+    const char *nonconforming;                             // why DAGCON_ERR_NONCONFORMING came back for a target or a window
+};
+#define DG_CIGAR_UNFIT "a record's CIGAR does not fit its SEQ or its target, or holds N or a length of 0"
+inline const DgKindDesc &dg_kind(DgRecordKind k) {
+    static const DgKindDesc d[4] = {
+        {"--sam", "dagcon_consensus_cigar", "line", "SAM", "SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')", DG_CIGAR_UNFIT},
+        {"--bam", "dagcon_consensus_cigar_packed", "record", "BAM", "BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)", DG_CIGAR_UNFIT},
+        {"--paf", "dagcon_consensus_cigar_strand", "line", "SAM", "PAF lines skipped (tp:A:S)", DG_CIGAR_UNFIT},
+        {"--paf --cs", "dagcon_consensus_cs", "line", "SAM", "PAF lines skipped (tp:A:S)",
+         "a line's cs:Z: text breaks the grammar or does not fit its qe - qs, its te - ts or its target"}};
+    return d[k];
+}
+
+// One alignment record, whatever it was read from (dg_sam_rec below, dg_bam_rec in bam.h, dg_paf_rec in paf.h).  Nothing
+// is copied: every pointer points into the input, the --ref bases or the reads.
+struct DgAlnRec {
+    const char *rname; uint32_t rname_len;                 // the target's name
+    const DgRefSeqs::Span *target;                         // its bases in --ref; NULL: --ref has no such sequence (the caller words the error)
+    const char *qname; uint32_t qname_len;                 // the read's name (--dump-parsed)
+    uint32_t pos;                                          // 1-based, SAM POS
+    const char *q; uint32_t q_len;                         // the read bases, one a byte (packed: two a byte; cs: none); q_len counts bases
+    const char *cigar; uint32_t cigar_len;                 // plain, stranded: the CIGAR text
+    const uint8_t *bam_ops;                                // packed: the ops as they lie in the record (not aligned)
+    uint32_t nops;                                         // ops of cigar / bam_ops (cs: 0)
+    const char *cs; uint32_t cs_len, t_span;               // cs: the text behind cs:Z: and the target bases the line claims (te - ts)
+    bool reverse;                                          // the record's strand is '-' (stranded: the ops are written against the reverse
+                                                           // complement of q, dagcon_upload_cigar_strand; every other kind: for printing)
+    const char *read; uint32_t read_len, qs;               // stranded: the whole read and where q begins in it (--dump-parsed)
+    unsigned long long where;                              // the line or the record's ordinal (dg_kind().unit): what an error names
+};
+
+// bytes of a record in a batch's q blob, and where they come from
+inline size_t dg_blob_bytes(DgRecordKind k, const DgAlnRec &r) { return k == DG_REC_CS ? r.cs_len : k == DG_REC_PACKED ? ((size_t)r.q_len + 1) / 2 : r.q_len; }
+inline const char *dg_blob(DgRecordKind k, const DgAlnRec &r) { return k == DG_REC_CS ? r.cs : r.q; }
+// the record's nops BAM-encoded ops to dst
+inline void dg_rec_ops(DgRecordKind k, const DgAlnRec &r, uint32_t *dst) {
+    if (k == DG_REC_PACKED) memcpy(dst, r.bam_ops, (size_t)r.nops * 4);
+    else if (k != DG_REC_CS) dg_cigar_ops(r.cigar, r.cigar_len, dst);
+}
+
+// a split SAM line (DG_SAM_RECORD) as a record; pos: POS as the caller reads it
+inline void dg_sam_rec(const DgSamLine &l, uint32_t pos, unsigned long long lineno, const DgRefSeqs &ref, DgAlnRec &r) {
+    r = DgAlnRec{};
+    r.rname = l.f[2]; r.rname_len = (uint32_t)l.fl[2]; r.target = ref.find(l.f[2], l.fl[2]);
+    r.qname = l.f[0]; r.qname_len = (uint32_t)l.fl[0];
+    r.pos = pos;                                           // 1-based, as Alignment::start
+    r.q = l.f[9]; r.q_len = (uint32_t)l.fl[9];             // (SEQ is in the target's orientation either way)
+    r.cigar = l.f[5]; r.cigar_len = (uint32_t)l.fl[5]; r.nops = (uint32_t)l.nops;
+    r.reverse = (l.flag & DG_SAM_REVERSE) != 0;
+    r.where = lineno;
+}
 
 // the arrays of a batch: a dagcon_cigar_batch (DG_REC_CS: q_off / q_blob / q_bytes are the cs texts, op_begin / ops unused)
 // and what the stranded and the cs kinds add to it
@@ -38,8 +98,19 @@ inline int dg_consensus_records(dagcon_ctx *ctx, DgRecordKind kind, const DgReco
          : windows ? dagcon_consensus_cigar_windows(ctx, &cb, windows, r) : dagcon_consensus_cigar(ctx, &cb, r);
 }
 
-// why DAGCON_ERR_NONCONFORMING came back for a target or a window of record input
-inline const char *dg_nonconforming_text(bool cs_text) {
-    return cs_text ? "a line's cs:Z: text breaks the grammar or does not fit its qe - qs, its te - ts or its target"
-                   : "a record's CIGAR does not fit its SEQ or its target, or holds N or a length of 0";
+// why a target or a window was skipped: its status as a warning's text
+inline const char *dg_status_text(int status, const char *nonconforming) {
+    return status == DAGCON_ERR_NONCONFORMING ? nonconforming : status == DAGCON_ERR_UNSUPPORTED ? "too large" : "internal error";
+}
+
+// a context for the command line's options; a failure is reported here (there is no CPU fallback)
+inline int dg_create(unsigned min_cov, unsigned min_len, unsigned trim, int device, uint32_t flags, dagcon_ctx **ctx) {
+    dagcon_opts dopt;
+    dagcon_default_opts(&dopt);
+    dopt.min_cov = min_cov; dopt.min_len = min_len; dopt.trim = trim;
+    dopt.min_weight = (int32_t)min_cov;                    // main.cpp:261,279 (quirk Q1)
+    dopt.device = device; dopt.flags = flags;
+    const int rc = dagcon_create(&dopt, ctx);
+    if (rc != DAGCON_OK) fprintf(stderr, "pbdagcon: no usable MI355X as device %d (dagcon_create = %d); there is no CPU fallback\n", device, rc);
+    return rc;
 }

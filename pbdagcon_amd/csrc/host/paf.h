@@ -89,13 +89,8 @@ inline bool dg_cs_decode(const char *cs, size_t n, const char *t, size_t tlen, u
 
 // reads a four-line FASTQ file: the names (first word of the @ line) and the bases; QUAL is not read
 inline bool dg_read_fastq(const std::string &path, DgRefSeqs &reads, std::string &err) {
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) { err = "error opening file: " + path; return false; }
     std::string text;
-    char buf[1 << 16];
-    size_t n;
-    while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
-    fclose(f);
+    if (!dg_slurp(path, text, err)) return false;
     reads.bases.reserve(text.size() / 2);
     size_t pos = 0;
     unsigned long long lineno = 0;
@@ -104,11 +99,8 @@ inline bool dg_read_fastq(const std::string &path, DgRefSeqs &reads, std::string
         int k = 0;
         for (; k < 4 && pos < text.size(); k++) {
             ln[k] = text.data() + pos;
-            const char *nl = (const char *)memchr(ln[k], '\n', text.size() - pos);
-            ll[k] = nl ? (size_t)(nl - ln[k]) : text.size() - pos;
-            pos += ll[k] + (nl ? 1 : 0);
+            ll[k] = dg_line(text.data(), text.size(), pos);
             lineno++;
-            if (ll[k] && ln[k][ll[k] - 1] == '\r') ll[k]--;
             if (k == 0 && ll[0] == 0) { k = -1; continue; }       // blank lines between records
         }
         if (k == 0) break;
@@ -180,11 +172,8 @@ struct DgPafInput {
         auto fail = [&](const std::string &what) { err = "line " + std::to_string(lineno) + ": " + what; return false; };
         while (p < size) {
             const char *line = data + p;
-            const char *nl = (const char *)memchr(line, '\n', size - p);
-            size_t ll = nl ? (size_t)(nl - line) : size - p;
-            p += ll + (nl ? 1 : 0);
+            const size_t ll = dg_line(data, size, p);
             lineno++;
-            if (ll && line[ll - 1] == '\r') ll--;
             if (ll == 0) continue;
             const char *f[12]; size_t fl[12]; int nf = 0;
             size_t i = 0;
@@ -223,19 +212,19 @@ struct DgPafInput {
             if (!tg) return fail("target " + std::string(f[5], fl[5]) + " is not a sequence of --ref");
             if (!cs && qlen != rd->len) return fail("query " + std::string(f[0], fl[0]) + " has length " + std::to_string(qlen) + " here but " + std::to_string(rd->len) + " bases in --reads");
             if (tlen != tg->len) return fail("target " + std::string(f[5], fl[5]) + " has length " + std::to_string(tlen) + " here but " + std::to_string(tg->len) + " bases in --ref");
+            DgPafRec r;
+            r.tname = f[5]; r.tname_len = (uint32_t)fl[5];
+            r.qname = f[0]; r.qname_len = (uint32_t)fl[0];
+            r.pos = (uint32_t)ts + 1u;
+            r.read = nullptr; r.read_len = 0; r.qs = (uint32_t)qs;
+            r.q = nullptr; r.q_len = (uint32_t)(qe - qs);
+            r.reverse = f[4][0] == '-';
+            r.cg = cg; r.cg_len = (uint32_t)cgl; r.nops = 0;
+            r.t_span = (uint32_t)(te - ts);
+            r.tspan = *tg;
+            r.line = lineno;
             if (cs) {                                      // the text is not looked into: the device decodes and judges it
                 if (cgl > 0xFFFFFFFFull) return fail("the cs:Z: tag is too long");
-                DgPafRec r;
-                r.tname = f[5]; r.tname_len = (uint32_t)fl[5];
-                r.qname = f[0]; r.qname_len = (uint32_t)fl[0];
-                r.pos = (uint32_t)ts + 1u;
-                r.read = nullptr; r.read_len = 0; r.qs = (uint32_t)qs;
-                r.q = nullptr; r.q_len = (uint32_t)(qe - qs);
-                r.reverse = f[4][0] == '-';
-                r.cg = cg; r.cg_len = (uint32_t)cgl; r.nops = 0;
-                r.t_span = (uint32_t)(te - ts);
-                r.tspan = *tg;
-                r.line = lineno;
                 recs.push_back(r);
                 continue;
             }
@@ -254,17 +243,8 @@ struct DgPafInput {
                 dropped.insert(tname);
                 continue;
             }
-            DgPafRec r;
-            r.tname = f[5]; r.tname_len = (uint32_t)fl[5];
-            r.qname = f[0]; r.qname_len = (uint32_t)fl[0];
-            r.pos = (uint32_t)ts + 1u;
-            r.read = reads.bases.data() + rd->off; r.read_len = rd->len; r.qs = (uint32_t)qs;
-            r.q = r.read + qs; r.q_len = (uint32_t)(qe - qs);
-            r.reverse = f[4][0] == '-';
-            r.cg = cg; r.cg_len = (uint32_t)cgl; r.nops = (uint32_t)k;
-            r.t_span = (uint32_t)(te - ts);
-            r.tspan = *tg;
-            r.line = lineno;
+            r.read = reads.bases.data() + rd->off; r.read_len = rd->len;
+            r.q = r.read + qs; r.nops = (uint32_t)k;
             recs.push_back(r);
         }
         if (!dropped.empty())
@@ -282,34 +262,31 @@ struct DgPafInput {
     }
 };
 
-// the grouped records as windows.h's driver takes them, the one place a DgPafRec becomes its record.  DG_REC_STRANDED:
-// the read's slice, a strand flag and the cg:Z: ops; DG_REC_CS: q is the record's cs text (cs_len bytes), q_len the read
-// bases it claims, no ops
+// a parsed line as the pipeline's record, the one place a DgPafRec becomes one.  cg:Z: lines: the read's slice as the
+// reads file has it, the strand and the CIGAR text; cs:Z: lines: the text, q_len the read bases it claims, no bases, no ops
+inline void dg_paf_rec(const DgPafRec &p, bool cs, DgAlnRec &r) {
+    r = DgAlnRec{};
+    r.rname = p.tname; r.rname_len = p.tname_len; r.target = &p.tspan;
+    r.qname = p.qname; r.qname_len = p.qname_len;
+    r.pos = p.pos; r.q_len = p.q_len;
+    r.reverse = p.reverse;
+    r.where = p.line;
+    if (cs) { r.cs = p.cg; r.cs_len = p.cg_len; r.t_span = p.t_span; return; }
+    r.q = p.q; r.read = p.read; r.read_len = p.read_len; r.qs = p.qs;
+    r.cigar = p.cg; r.cigar_len = p.cg_len; r.nops = p.nops;
+}
+
+// the grouped records as windows.h's driver takes them
 template <DgRecordKind K>
 struct DgPafSourceOf {
     static constexpr DgRecordKind kind = K;
-    static constexpr const char *unit = "line";
-    static constexpr const char *skipped_what = "PAF lines skipped (tp:A:S)";
     const DgPafInput &in;
     size_t at = 0;
     unsigned long long skipped;
-    DgPafSourceOf(const DgPafInput &i, const DgRefSeqs &) : in(i), skipped(i.n_secondary) {}
-    template <class AlnRec>
-    int next(AlnRec &r, std::vector<uint32_t> &ops) {
+    DgPafSourceOf(const DgPafInput &i) : in(i), skipped(i.n_secondary) {}
+    int next(DgAlnRec &r) {
         if (at >= in.recs.size()) return 0;
-        const DgPafRec &p = in.recs[at++];
-        r.rname = p.tname; r.rname_len = p.tname_len;
-        r.pos = p.pos;
-        r.q_len = p.q_len;
-        r.where = p.line;
-        if (K == DG_REC_CS) {
-            r.q = p.cg; r.nops = 0; r.reverse = false;
-            r.cs_len = p.cg_len; r.t_span = p.t_span;
-            return 1;
-        }
-        r.q = p.q; r.nops = p.nops; r.reverse = p.reverse;
-        ops.resize(ops.size() + p.nops);
-        dg_cigar_ops(p.cg, p.cg_len, ops.data() + ops.size() - p.nops);
+        dg_paf_rec(in.recs[at++], K == DG_REC_CS, r);
         return 1;
     }
 };

@@ -17,16 +17,9 @@
 //     banded aligner on the GPU (dagcon_align): blasr_libcpp is absent, the stage is pinned to the
 //     reference by its one known-answer test only (test/cpp/SimpleAlignerTest.cpp:8-21); global by
 //     default, local ends with --local (DAGCON_FLAG_LOCAL_ALIGN, the reference's SDPAlign(..., Local));
-//   * --sam --ref: SAM text (one ungapped read, a position and a CIGAR per record) against a FASTA of the targets; the
-//     gapped strings are made on the GPU (dagcon_consensus_cigar), never on the host (sam.h);
-//   * --bam --ref: the same from BAM (bam.h: BGZF, inflate and the records); the CIGAR ops and the 4-bit SEQ go to the
-//     GPU as they lie in the file (dagcon_consensus_cigar_packed), the output is that of --sam on the same records;
-//   * --paf --cs --ref: PAF lines with a cs:Z: tag (minimap2 --cs) and no reads file: the tag's text goes to the device as it
-//     lies in the file and is decoded there (dagcon_consensus_cs); the host finds the tag by its tab and reads no base
-//   * --paf --ref --reads: PAF lines with a cg:Z: CIGAR (minimap2 -c), the reads from a FASTA / FASTQ file (paf.h); a line's
-//     slice of its read goes to the GPU as the reads file has it, with one strand flag per record, and the GPU reads a
-//     '-' record's bases backwards and complemented (dagcon_consensus_cigar_strand); the output is that of --sam on the
-//     same alignments;
+//   * --sam, --bam, --paf --reads and --paf --cs, all with --ref: alignment records (a position, a CIGAR or cs:Z: text and the
+//     ungapped read, or no read at all) against a FASTA of the targets; what each format gives is in sam.h, bam.h and paf.h, the one
+//     record they all become and the per-kind description in intake.h.  The gapped strings are made on the GPU, never on the host;
 //   * blank lines are skipped (the reference duplicates the previous record, Q9);
 //   * a missing input file is an error on stderr, exit 1 (the reference is silent, Q11).
 #include <algorithm>
@@ -57,18 +50,15 @@
 
 namespace {
 
+enum Mode { MODE_M5, MODE_PRE, MODE_RECORDS };             // BLASR -m 5 text; .pre text (-a); alignment records of o.kind
+
 struct Opts {
     unsigned threads = 4, min_cov = 6, min_len = 500, trim = 50;
-    bool align = false, verbose = false, dump = false;
-    bool local = false;                // --local (with -a): the first alignment of every record has local ends
-    bool sam = false;                  // --sam: SAM text, the targets' bases from --ref (dagcon_consensus_cigar)
-    bool bam = false;                  // --bam: the same records from BAM (bam.h); sam is set too, and the reads stay 4-bit
-    bool paf = false;                  // --paf: PAF lines with cg:Z: (paf.h), the reads from --reads; sam is set too, and the
-                                       // strand of a record is applied on the device
-    std::string ref;                   // --ref FASTA
-    std::string reads;                 // --reads FASTA / FASTQ (with --paf)
-    bool cs = false;                   // --cs (with --paf): the lines' cs:Z: text instead of cg:Z: and --reads, decoded on the device
-    unsigned window = 0, overlap = 1000;   // --window W [--overlap O] (with --sam): targets cut into windows (windows.h)
+    Mode mode = MODE_M5;                // what the input is, decided once by parse_args
+    DgRecordKind kind = DG_REC_PLAIN;   // MODE_RECORDS: --sam, --bam, --paf or --paf --cs (intake.h)
+    bool verbose = false, dump = false, local = false;   // local: --local (with -a), the first alignment of every record has local ends
+    std::string ref, reads;            // --ref FASTA (MODE_RECORDS); --reads FASTA / FASTQ (with --paf)
+    unsigned window = 0, overlap = 1000;   // --window W [--overlap O] (MODE_RECORDS): targets cut into windows (windows.h)
     bool overlap_set = false;
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
@@ -76,11 +66,11 @@ struct Opts {
     unsigned contexts = 0;             // --contexts N: consensus workers per GPU (0: two when the input is several batches long)
     unsigned polish = 0;               // --polish N (with -a): N more rounds with the consensus as the new backbone
     size_t batch_targets = 512;        // parsing and the GPU still overlap on mid-size inputs; 256 left the GPU a third less efficient (4,000 targets: 0.79 -> 0.67 s)
-    size_t batch_bytes = 512ull << 20;  // (of strings: 80 targets of 50 kb x 60x fill the chip; what a context holds, and has to
-                                       // allocate on its first batch, grows with it)
+    size_t batch_bytes = 512ull << 20;  // (of strings: 80 targets of 50 kb x 60x fill the chip; what a context holds, and has to allocate on its first batch, grows with it)
     size_t slab_bytes = 0;             // test hook: text indexed per round (0 = automatic)
     std::string input;
 };
+
 
 void usage(FILE *f) {
     fprintf(f,
@@ -167,6 +157,7 @@ bool parse_uint(const char *s, unsigned *out) {
 }
 
 int parse_args(int argc, char **argv, Opts &o) {
+    bool align = false, sam = false, bam = false, paf = false, cs = false;   // -a, --sam, --bam, --paf, --cs as typed
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](unsigned *dst) {
@@ -178,13 +169,13 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "-c" || a == "--min-coverage") { if (!need(&o.min_cov)) return 2; }
         else if (a == "-m" || a == "--min-length") { if (!need(&o.min_len)) return 2; }
         else if (a == "-t" || a == "--trim") { if (!need(&o.trim)) return 2; }
-        else if (a == "-a" || a == "--align") o.align = true;
+        else if (a == "-a" || a == "--align") align = true;
         else if (a == "--local") o.local = true;
         else if (a == "--fastq") o.fastq = true;
-        else if (a == "--sam") o.sam = true;
-        else if (a == "--bam") o.bam = true;
-        else if (a == "--paf") o.paf = true;
-        else if (a == "--cs") o.cs = true;
+        else if (a == "--sam") sam = true;
+        else if (a == "--bam") bam = true;
+        else if (a == "--paf") paf = true;
+        else if (a == "--cs") cs = true;
         else if (a == "--reads") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --reads needs a FASTA or FASTQ file\n"); return 2; }
             o.reads = argv[++i];
@@ -223,27 +214,28 @@ int parse_args(int argc, char **argv, Opts &o) {
             o.input = a;
         } else { fprintf(stderr, "PARSE ERROR: unknown argument %s\n", a.c_str()); return 2; }
     }
-    if (o.local && !o.align) { fprintf(stderr, "PARSE ERROR: --local needs -a\n"); return 2; }
-    if (o.cs && !o.paf) { fprintf(stderr, "PARSE ERROR: --cs needs --paf\n"); return 2; }
-    if (o.cs && !o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --cs does not go with --reads (a cs:Z: tag and --ref are the whole alignment)\n"); return 2; }
-    if (o.cs && (o.sam || o.bam || o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --cs does not go with --sam, --bam, -a, --local or --polish\n"); return 2; }
-    if (o.paf && (o.sam || o.bam)) { fprintf(stderr, "PARSE ERROR: --paf does not go with --sam or --bam\n"); return 2; }
-    if (o.paf && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --paf does not go with -a, --local or --polish\n"); return 2; }
-    if (o.paf && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --paf needs --ref <fasta>\n"); return 2; }
-    if (o.paf && !o.cs && o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --paf needs --reads <fasta|fastq>\n"); return 2; }
-    if (!o.paf && !o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --reads needs --paf\n"); return 2; }
-    if (o.paf) o.sam = true;                               // (records with a CIGAR, as below)
-    if (o.bam && o.sam) { fprintf(stderr, "PARSE ERROR: --bam and --sam do not go together\n"); return 2; }
-    if (o.bam && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --bam does not go with -a, --local or --polish\n"); return 2; }
-    if (o.bam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --bam needs --ref <fasta>\n"); return 2; }
-    if (o.bam) o.sam = true;                               // from here on sam means: records with a CIGAR, from either format
-    if (o.sam && (o.align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --sam does not go with -a, --local or --polish\n"); return 2; }
-    if (o.sam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --sam needs --ref <fasta>\n"); return 2; }
-    if (!o.sam && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam, --bam or --paf\n"); return 2; }
-    if (o.window && (!o.sam || o.align || o.polish)) { fprintf(stderr, "PARSE ERROR: --window needs --sam, --bam or --paf and does not go with -a or --polish\n"); return 2; }
+    if (o.local && !align) { fprintf(stderr, "PARSE ERROR: --local needs -a\n"); return 2; }
+    if (cs && !paf) { fprintf(stderr, "PARSE ERROR: --cs needs --paf\n"); return 2; }
+    if (cs && !o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --cs does not go with --reads (a cs:Z: tag and --ref are the whole alignment)\n"); return 2; }
+    if (cs && (sam || bam || align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --cs does not go with --sam, --bam, -a, --local or --polish\n"); return 2; }
+    if (paf && (sam || bam)) { fprintf(stderr, "PARSE ERROR: --paf does not go with --sam or --bam\n"); return 2; }
+    if (paf && (align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --paf does not go with -a, --local or --polish\n"); return 2; }
+    if (paf && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --paf needs --ref <fasta>\n"); return 2; }
+    if (paf && !cs && o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --paf needs --reads <fasta|fastq>\n"); return 2; }
+    if (!paf && !o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --reads needs --paf\n"); return 2; }
+    if (bam && sam) { fprintf(stderr, "PARSE ERROR: --bam and --sam do not go together\n"); return 2; }
+    if (bam && (align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --bam does not go with -a, --local or --polish\n"); return 2; }
+    if (bam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --bam needs --ref <fasta>\n"); return 2; }
+    const bool records = sam || bam || paf;
+    if (sam && (align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --sam does not go with -a, --local or --polish\n"); return 2; }
+    if (sam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --sam needs --ref <fasta>\n"); return 2; }
+    if (!records && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam, --bam or --paf\n"); return 2; }
+    if (o.window && (!records || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --window needs --sam, --bam or --paf and does not go with -a or --polish\n"); return 2; }
     if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
     if (o.window && (uint64_t)o.overlap < (uint64_t)o.trim + 64) { fprintf(stderr, "PARSE ERROR: --overlap must be at least --trim + 64 (%u)\n", o.trim + 64); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
+    o.mode = records ? MODE_RECORDS : align ? MODE_PRE : MODE_M5;
+    o.kind = cs ? DG_REC_CS : paf ? DG_REC_STRANDED : bam ? DG_REC_PACKED : DG_REC_PLAIN;
     return 0;
 }
 
@@ -269,6 +261,15 @@ uint32_t tok_u32(const char *s, size_t n) {
     if (!any) return 0;
     if (over) return 0xFFFFFFFFu;
     return neg ? (uint32_t)(0u - (uint32_t)v) : (uint32_t)v;
+}
+
+// f(0) here and f(1) .. f(n - 1) on threads of their own
+template <class F>
+void on_threads(unsigned n, F f) {
+    std::vector<std::thread> th;
+    for (unsigned k = 1; k < n; k++) th.emplace_back(f, k);
+    f(0);
+    for (auto &x : th) x.join();
 }
 
 // string blob of a batch: page-locked (dagcon_host_alloc) when a context offers it, else malloc
@@ -297,123 +298,72 @@ struct Blob {
     size_t size() const { return n; }
 };
 
+// The targets of one trip to the device.  .m5 / .pre: off2 / len2 are a record's target string in t.  Records: t holds each
+// target's bases once (toff; tsrc: where they come from), ops every record's ops (from opb), cs_len / tspan what the cs kind adds
 struct Batch {
     std::vector<std::string> ids;
-    std::vector<uint32_t> tlen, start, len, len2;          // len2 / off2: the target sequence of a .pre record
+    std::vector<uint32_t> tlen, start, len, len2;
     std::vector<uint64_t> begin{0}, off, off2;
     std::vector<char> strand;
-    std::vector<uint32_t> tspan;                           // --cs: te - ts of each record (len: qe - qs; off / len2: its text in q)
-    std::vector<uint64_t> toff, opb{0};                    // --sam: the target's bases in t (per target); first op of each record
-    std::vector<const char *> tsrc;                        // --sam: where the target's bases come from (per target)
-    std::vector<uint32_t> ops;                             // --sam: BAM-encoded CIGAR ops of all records
+    std::vector<uint64_t> toff, opb{0};
+    std::vector<const char *> tsrc;
+    std::vector<uint32_t> ops, cs_len, tspan;
+    std::vector<uint8_t> reverse;
     Blob q, t;
     unsigned long long seq = 0;        // position in the input: records are printed in this order
     std::string out;                   // the batch's FASTA records
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); tspan.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); q.n = 0; t.n = 0; out.clear(); }
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); q.n = 0; t.n = 0; out.clear(); }
 };
 
-bool g_timing = false;                                    // PBDAGCON_TIMING
+bool g_timing = false;                                    // PBDAGCON_TIMING=1: where the wall time of the run went, on stderr (seconds)
 std::mutex g_tmu;
 double g_t_upload = 0, g_t_run = 0, g_t_fetch = 0;
 double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// one batch through the device; the records go to b.out (main.cpp:141-143), warnings to stderr.  actx: the context
-// of the first alignment with --polish (a local one with --local: the rounds stay global on ctx)
-int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scratch) {
-    if (b.ids.empty()) return 0;
-    if (b.begin.back() != b.start.size()) b.begin.push_back(b.start.size());
+// ---- one batch through the device, by mode ---------------------------------------------------------------------------
+
+// false, with the library's message, when a call failed
+bool ok(dagcon_ctx *ctx, int rc, const char *what) {
+    if (rc != DAGCON_OK) fprintf(stderr, "pbdagcon: %s failed (%d): %s\n", what, rc, dagcon_last_error(ctx));
+    return rc == DAGCON_OK;
+}
+
+// the records of the results to b.out (main.cpp:141-143), warnings to stderr
+int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_results &r) {
+    dagcon_support sup;
+    memset(&sup, 0, sizeof sup);
+    if (o.fastq && !ok(ctx, dagcon_fetch_support(ctx, &sup), "per-base support")) return 1;
+    const char *nonconforming = o.mode == MODE_RECORDS ? dg_kind(o.kind).nonconforming : "an alignment leaves the backbone or holds a non-printable byte";
+    for (uint32_t g = 0; g < r.n_targets; g++) {
+        if (o.verbose)
+            fprintf(stderr, "Consensus calling: %s Alignments: %llu\n", b.ids[g].c_str(),
+                    (unsigned long long)(b.begin[g + 1] - b.begin[g]));
+        // a failure is confined to its target (the reference's assert hits one worker's one target,
+        // AlnGraphBoost.cpp:71-72): warn, go on with the rest
+        if (r.target_status[g] != DAGCON_OK)
+            fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(), dg_status_text(r.target_status[g], nonconforming));
+        for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++)
+            if (!dg_append_result(b.out, o.fastq, b.ids[g], r.range0[s], r.range1[s], r.seq_blob + r.seq_off[s], r.seq_len[s],
+                                  o.fastq ? sup.weight + r.seq_off[s] : nullptr, o.fastq ? sup.depth + r.seq_off[s] : nullptr)) return 1;
+    }
+    return 0;
+}
+
+// the batch's own strings as the library's batch
+dagcon_batch strings_batch(Batch &b) {
     dagcon_batch db;
     memset(&db, 0, sizeof db);
     db.n_targets = (uint32_t)b.ids.size();
     db.tlen = b.tlen.data(); db.aln_begin = b.begin.data();
     db.aln_start = b.start.data(); db.aln_off = b.off.data(); db.aln_len = b.len.data();
     db.qstr = b.q.data(); db.tstr = b.t.data(); db.blob_bytes = b.q.size();
-    // -a: SimpleAligner on every record first (main.cpp:127-128)
-    std::vector<uint64_t> ooff;
-    std::vector<uint32_t> alen, nstart;
-    std::vector<uint32_t> e_qb, e_qe, e_tb, e_te;       // -a --polish: the ends of the first alignments
-    char *qa = nullptr, *ta = nullptr;                  // -a: the aligned strings, in the worker's page-locked scratch
-    dagcon_results r;
-    int rc = DAGCON_OK;
-    bool have_results = false;
-    if (o.sam) {
-        // position + read + CIGAR (--cs: cs text) per record, the target's bases once: expanded on the device
-        const DgRecordKind kind = o.cs ? DG_REC_CS : o.paf ? DG_REC_STRANDED : o.bam ? DG_REC_PACKED : DG_REC_PLAIN;
-        std::vector<uint8_t> rev;                           // --paf: one strand flag per record, applied on the device
-        if (kind == DG_REC_STRANDED) { rev.resize(b.strand.size() + 1); for (size_t a = 0; a < b.strand.size(); a++) rev[a] = b.strand[a] == '-'; }
-        DgRecordArrays ra{};
-        ra.cb.n_targets = db.n_targets; ra.cb.tlen = b.tlen.data(); ra.cb.t_off = b.toff.data();
-        ra.cb.t_blob = b.t.data(); ra.cb.t_bytes = b.t.size(); ra.cb.rec_begin = b.begin.data();
-        ra.cb.pos = b.start.data(); ra.cb.q_off = b.off.data(); ra.cb.q_len = b.len.data();
-        ra.cb.q_blob = b.q.data(); ra.cb.q_bytes = b.q.size(); ra.cb.op_begin = b.opb.data(); ra.cb.ops = b.ops.data();
-        ra.reverse = rev.data(); ra.cs_len = b.len2.data(); ra.t_span = b.tspan.data();
-        const double ta0 = wall();
-        rc = dg_consensus_records(ctx, kind, ra, nullptr, &r);
-        if (g_timing && o.cs) fprintf(stderr, "pbdagcon timing: --paf --cs batch of %zu records: dagcon_consensus_cs %.3f\n", b.start.size(), wall() - ta0);
-        else if (g_timing) fprintf(stderr, "pbdagcon timing: %s batch of %zu records: dagcon_consensus_cigar%s %.3f\n", o.paf ? "--paf" : o.bam ? "--bam" : "--sam", b.start.size(), o.paf ? "_strand" : o.bam ? "_packed" : "", wall() - ta0);
-        have_results = true;
-    } else if (o.align && !o.polish) {
-        // main.cpp:117-145 with -a in one call: the aligned strings stay on the device
-        const size_t A = b.start.size();
-        dagcon_pre_batch pb;
-        memset(&pb, 0, sizeof pb);
-        pb.n_targets = db.n_targets; pb.tlen = b.tlen.data(); pb.rec_begin = b.begin.data();
-        pb.tstart = b.start.data(); pb.strand = b.strand.data();
-        pb.q_off = b.off.data(); pb.q_len = b.len.data(); pb.t_off = b.off2.data(); pb.t_len = b.len2.data();
-        pb.q_blob = b.q.data(); pb.q_bytes = b.q.size(); pb.t_blob = b.t.data(); pb.t_bytes = b.t.size();
-        const double ta0 = wall();
-        rc = dagcon_consensus_pre(ctx, &pb, &r);
-        if (g_timing) fprintf(stderr, "pbdagcon timing: -a batch of %zu records: dagcon_consensus_pre %.3f\n", A, wall() - ta0);
-        if (rc != DAGCON_OK) {
-            fprintf(stderr, "pbdagcon: alignment / consensus failed (%d): %s\n", rc, dagcon_last_error(ctx));
-            return 1;
-        }
-        if (const uint32_t nd = dagcon_align_dropped(ctx))
-            fprintf(stderr, "pbdagcon: warning: %u of %zu records could not be aligned inside the widest band and were dropped\n", nd, A);
-        have_results = true;
-    } else if (o.align) {
-        const double ta0 = wall();
-        const size_t A = b.start.size();
-        ooff.resize(A); alen.assign(A, 0); nstart.resize(A);
-        uint64_t tot = 0;
-        for (size_t a = 0; a < A; a++) { ooff[a] = tot; tot += (uint64_t)b.len[a] + b.len2[a]; }
-        if (!scratch[0].resize(tot + 1, ctx) || !scratch[1].resize(tot + 1, ctx)) { fprintf(stderr, "pbdagcon: out of memory\n"); return 1; }
-        qa = scratch[0].data(); ta = scratch[1].data();
-        const double ta1 = wall();
-        int rc = dagcon_align(actx, (uint32_t)A, b.off.data(), b.len.data(), b.off2.data(), b.len2.data(), b.q.data(), b.q.size(),
-                              b.t.data(), b.t.size(), ooff.data(), &qa[0], &ta[0], alen.data());
-        if (rc == DAGCON_OK) {
-            e_qb.resize(A); e_qe.resize(A); e_tb.resize(A); e_te.resize(A);
-            rc = dagcon_align_ends(actx, (uint32_t)A, e_qb.data(), e_qe.data(), e_tb.data(), e_te.data());
-        }
-        const double ta2 = wall();
-        if (g_timing) fprintf(stderr, "pbdagcon timing: -a batch of %zu records: buffers %.3f  dagcon_align %.3f\n", A, ta1 - ta0, ta2 - ta1);
-        if (rc != DAGCON_OK) {
-            fprintf(stderr, "pbdagcon: alignment failed (%d): %s\n", rc, dagcon_last_error(actx));
-            return 1;
-        }
-        if (const uint32_t nd = dagcon_align_dropped(actx))
-            fprintf(stderr, "pbdagcon: warning: %u of %zu records could not be aligned inside the widest band and were dropped\n", nd, A);
-        size_t g = 0;
-        for (size_t a = 0; a < A; a++) {
-            while (b.begin[g + 1] <= a) g++;
-            // SimpleAligner.cpp:51-62: start = tstart + GenomicTBegin(), end = start + the aligned target span (global:
-            // 0 and |tseq|; --local: t_begin and t_end - t_begin, as dagcon_consensus_pre)
-            uint32_t start = b.start[a] + (o.local ? e_tb[a] : 0u);
-            const uint32_t end = o.local ? b.start[a] + e_te[a] : start + b.len2[a];
-            if (b.strand[a] == '-') {
-                start = b.tlen[g] - end;
-                std::string tmp(alen[a], 0);
-                revcomp_into(&tmp[0], &qa[ooff[a]], alen[a]); memcpy(&qa[ooff[a]], tmp.data(), alen[a]);
-                revcomp_into(&tmp[0], &ta[ooff[a]], alen[a]); memcpy(&ta[ooff[a]], tmp.data(), alen[a]);
-            }
-            nstart[a] = start + 1;
-        }
-        db.aln_start = nstart.data(); db.aln_off = ooff.data(); db.aln_len = alen.data();
-        db.qstr = qa; db.tstr = ta; db.blob_bytes = tot;
-    }
-    if (have_results) {
-    } else if (g_timing) {                                // the three steps of dagcon_consensus, timed apart
+    return db;
+}
+
+// dagcon_consensus; with PBDAGCON_TIMING its three steps, timed apart
+bool consensus_strings(dagcon_ctx *ctx, const dagcon_batch &db, dagcon_results &r) {
+    int rc;
+    if (g_timing) {
         const double t0 = wall();
         rc = dagcon_upload(ctx, &db);
         const double t1 = wall();
@@ -425,10 +375,89 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
         std::lock_guard<std::mutex> lk(g_tmu);
         g_t_upload += t1 - t0; g_t_run += t2 - t1; g_t_fetch += t3 - t2;
     } else rc = dagcon_consensus(ctx, &db, &r);
-    if (rc != DAGCON_OK) {
-        fprintf(stderr, "pbdagcon: consensus failed (%d): %s\n", rc, dagcon_last_error(ctx));
-        return 1;
+    return ok(ctx, rc, "consensus");
+}
+
+// plain .m5: the strings as they were parsed
+int run_m5(dagcon_ctx *ctx, Batch &b, const Opts &o) {
+    dagcon_results r;
+    return consensus_strings(ctx, strings_batch(b), r) ? append_results(ctx, b, o, r) : 1;
+}
+
+// position + read + CIGAR (cs kind: cs text) per record, the target's bases once: expanded on the device
+int run_records(dagcon_ctx *ctx, Batch &b, const Opts &o) {
+    DgRecordArrays ra{};
+    ra.cb.n_targets = (uint32_t)b.ids.size(); ra.cb.tlen = b.tlen.data(); ra.cb.t_off = b.toff.data();
+    ra.cb.t_blob = b.t.data(); ra.cb.t_bytes = b.t.size(); ra.cb.rec_begin = b.begin.data();
+    ra.cb.pos = b.start.data(); ra.cb.q_off = b.off.data(); ra.cb.q_len = b.len.data();
+    ra.cb.q_blob = b.q.data(); ra.cb.q_bytes = b.q.size(); ra.cb.op_begin = b.opb.data(); ra.cb.ops = b.ops.data();
+    ra.reverse = o.kind == DG_REC_STRANDED ? b.reverse.data() : nullptr; ra.cs_len = b.cs_len.data(); ra.t_span = b.tspan.data();
+    dagcon_results r;
+    const double t0 = wall();
+    const int rc = dg_consensus_records(ctx, o.kind, ra, nullptr, &r);
+    if (g_timing) fprintf(stderr, "pbdagcon timing: %s batch of %zu records: %s %.3f\n", dg_kind(o.kind).flag, b.start.size(), dg_kind(o.kind).entry, wall() - t0);
+    return ok(ctx, rc, "consensus") ? append_results(ctx, b, o, r) : 1;
+}
+
+void warn_dropped(dagcon_ctx *ctx, size_t n_records) {
+    if (const uint32_t nd = dagcon_align_dropped(ctx)) fprintf(stderr, "pbdagcon: warning: %u of %zu records could not be aligned inside the widest band and were dropped\n", nd, n_records);
+}
+
+// -a: SimpleAligner on every record first (main.cpp:117-145), in one call: the aligned strings stay on the device
+int run_pre(dagcon_ctx *ctx, Batch &b, const Opts &o) {
+    dagcon_pre_batch pb;
+    memset(&pb, 0, sizeof pb);
+    pb.n_targets = (uint32_t)b.ids.size(); pb.tlen = b.tlen.data(); pb.rec_begin = b.begin.data();
+    pb.tstart = b.start.data(); pb.strand = b.strand.data();
+    pb.q_off = b.off.data(); pb.q_len = b.len.data(); pb.t_off = b.off2.data(); pb.t_len = b.len2.data();
+    pb.q_blob = b.q.data(); pb.q_bytes = b.q.size(); pb.t_blob = b.t.data(); pb.t_bytes = b.t.size();
+    dagcon_results r;
+    const double t0 = wall();
+    const int rc = dagcon_consensus_pre(ctx, &pb, &r);
+    if (g_timing) fprintf(stderr, "pbdagcon timing: -a batch of %zu records: dagcon_consensus_pre %.3f\n", b.start.size(), wall() - t0);
+    if (!ok(ctx, rc, "alignment / consensus")) return 1;
+    warn_dropped(ctx, b.start.size());
+    return append_results(ctx, b, o, r);
+}
+
+// -a --polish N: the alignments come back to the host (the worker's page-locked scratch), round 0's consensus is made from them as
+// from .m5 strings, then the rounds.  actx: the context of the first alignment (a local one with --local: the rounds stay global on ctx)
+int run_pre_polish(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scratch) {
+    const double ta0 = wall();
+    const size_t A = b.start.size();
+    std::vector<uint64_t> ooff(A);
+    std::vector<uint32_t> alen(A, 0), nstart(A);
+    std::vector<uint32_t> e_qb(A), e_qe(A), e_tb(A), e_te(A);       // the ends of the first alignments
+    uint64_t total = 0;
+    for (size_t a = 0; a < A; a++) { ooff[a] = total; total += (uint64_t)b.len[a] + b.len2[a]; }
+    if (!scratch[0].resize(total + 1, ctx) || !scratch[1].resize(total + 1, ctx)) { fprintf(stderr, "pbdagcon: out of memory\n"); return 1; }
+    char *qa = scratch[0].data(), *ta = scratch[1].data();          // the aligned strings
+    const double ta1 = wall();
+    int rc = dagcon_align(actx, (uint32_t)A, b.off.data(), b.len.data(), b.off2.data(), b.len2.data(), b.q.data(), b.q.size(),
+                          b.t.data(), b.t.size(), ooff.data(), &qa[0], &ta[0], alen.data());
+    if (rc == DAGCON_OK) rc = dagcon_align_ends(actx, (uint32_t)A, e_qb.data(), e_qe.data(), e_tb.data(), e_te.data());
+    if (g_timing) fprintf(stderr, "pbdagcon timing: -a batch of %zu records: buffers %.3f  dagcon_align %.3f\n", A, ta1 - ta0, wall() - ta1);
+    if (!ok(actx, rc, "alignment")) return 1;
+    warn_dropped(actx, A);
+    for (size_t a = 0, g = 0; a < A; a++) {
+        while (b.begin[g + 1] <= a) g++;
+        // SimpleAligner.cpp:51-62: start = tstart + GenomicTBegin(), end = start + the aligned target span (global:
+        // 0 and |tseq|; --local: t_begin and t_end - t_begin, as dagcon_consensus_pre)
+        uint32_t start = b.start[a] + (o.local ? e_tb[a] : 0u);
+        const uint32_t end = o.local ? b.start[a] + e_te[a] : start + b.len2[a];
+        if (b.strand[a] == '-') {
+            start = b.tlen[g] - end;
+            std::string tmp(alen[a], 0);
+            revcomp_into(&tmp[0], &qa[ooff[a]], alen[a]); memcpy(&qa[ooff[a]], tmp.data(), alen[a]);
+            revcomp_into(&tmp[0], &ta[ooff[a]], alen[a]); memcpy(&ta[ooff[a]], tmp.data(), alen[a]);
+        }
+        nstart[a] = start + 1;
     }
+    dagcon_batch db = strings_batch(b);
+    db.aln_start = nstart.data(); db.aln_off = ooff.data(); db.aln_len = alen.data();
+    db.qstr = qa; db.tstr = ta; db.blob_bytes = total;
+    dagcon_results r;
+    if (!consensus_strings(ctx, db, r)) return 1;
     // --polish: the consensus becomes the backbone, the reads are aligned to it again, N times.  The
     // reference names this use (README.md:14-15) and leaves it to the caller; nothing of it is in its
     // C++ sources, so there is no reference behaviour to match: the steps are this build's own
@@ -439,134 +468,608 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
     // clipped to what lies over that stretch (plus a margin) and the stretch of the new backbone it covers is
     // estimated; (3) dagcon_align, global over the two pieces, backbone bases in front of / behind the read
     // stripped; (4) real-backbone consensus as dazcon.cpp:76 does.
-    if (o.align && o.polish) {
-        const size_t A = b.start.size();
-        const uint32_t T = db.n_targets;
-        const uint32_t pad = 64;
-        std::vector<uint32_t> cur_start(A), cur_len(A), cur_qbase(A, 0);   // qbase: the read's base the current alignment begins with
-        if (o.local)                                     // (the read's first aligned base, in the target's orientation)
-            for (size_t a = 0; a < A; a++) cur_qbase[a] = b.strand[a] == '-' ? b.len[a] - e_qe[a] : e_qb[a];
-        std::vector<uint64_t> cur_off(A);
-        std::string cur_q(qa, db.blob_bytes + 1), cur_t(ta, db.blob_bytes + 1);     // the reads' last alignments, per record
-        for (size_t a = 0; a < A; a++) { cur_start[a] = db.aln_start[a]; cur_off[a] = db.aln_off[a]; cur_len[a] = db.aln_len[a]; }
-        std::vector<uint64_t> p_qoff(A), p_toff(A), p_ooff(A), p_begin, p_bboff;
-        std::vector<uint32_t> p_qlen(A), p_tlen(A), p_alen(A), p_tl, w0(A);
-        std::string p_q, p_t, p_qa, p_ta, p_bb, fwd;
-        std::vector<uint32_t> k_start, k_len; std::vector<uint64_t> k_off;
-        for (unsigned round = 1; round <= o.polish; round++) {
-            std::vector<std::string> bb(T);
-            std::vector<int32_t> r0(T, 0), r1(T, 0);
-            for (uint32_t g = 0; g < T; g++) {
-                uint32_t best = 0;                           // (the first of the longest ones, as AlnGraphBoost.cpp:309,319 breaks ties)
-                for (uint64_t sg = r.seg_begin[g]; sg < r.seg_begin[g + 1]; sg++)
-                    if (r.seq_len[sg] > best) { best = r.seq_len[sg]; bb[g].assign(r.seq_blob + r.seq_off[sg], r.seq_len[sg]); r0[g] = r.range0[sg]; r1[g] = r.range1[sg]; }
+    const uint32_t T = db.n_targets;
+    const uint32_t pad = 64;
+    std::vector<uint32_t> cur_start(A), cur_len(A), cur_qbase(A, 0);   // qbase: the read's base the current alignment begins with
+    if (o.local)                                     // (the read's first aligned base, in the target's orientation)
+        for (size_t a = 0; a < A; a++) cur_qbase[a] = b.strand[a] == '-' ? b.len[a] - e_qe[a] : e_qb[a];
+    std::vector<uint64_t> cur_off(A);
+    std::string cur_q(qa, db.blob_bytes + 1), cur_t(ta, db.blob_bytes + 1);     // the reads' last alignments, per record
+    for (size_t a = 0; a < A; a++) { cur_start[a] = db.aln_start[a]; cur_off[a] = db.aln_off[a]; cur_len[a] = db.aln_len[a]; }
+    std::vector<uint64_t> p_qoff(A), p_toff(A), p_ooff(A), p_begin, p_bboff;
+    std::vector<uint32_t> p_qlen(A), p_tlen(A), p_alen(A), p_tl, w0(A);
+    std::string p_q, p_t, p_qa, p_ta, p_bb, fwd;
+    std::vector<uint32_t> k_start, k_len; std::vector<uint64_t> k_off;
+    for (unsigned round = 1; round <= o.polish; round++) {
+        std::vector<std::string> bb(T);
+        std::vector<int32_t> r0(T, 0), r1(T, 0);
+        for (uint32_t g = 0; g < T; g++) {
+            uint32_t best = 0;                           // (the first of the longest ones, as AlnGraphBoost.cpp:309,319 breaks ties)
+            for (uint64_t sg = r.seg_begin[g]; sg < r.seg_begin[g + 1]; sg++)
+                if (r.seq_len[sg] > best) { best = r.seq_len[sg]; bb[g].assign(r.seq_blob + r.seq_off[sg], r.seq_len[sg]); r0[g] = r.range0[sg]; r1[g] = r.range1[sg]; }
+        }
+        p_q.clear(); p_t.clear();
+        uint64_t tot = 0;
+        size_t g = 0;
+        for (size_t a = 0; a < A; a++) {
+            while (b.begin[g + 1] <= a) g++;
+            const std::string &B = bb[g];
+            p_qoff[a] = p_q.size(); p_toff[a] = p_t.size(); p_ooff[a] = tot; p_qlen[a] = 0; p_tlen[a] = 0; w0[a] = 0;
+            if (B.empty() || cur_len[a] == 0) { cur_len[a] = 0; continue; }     // (no consensus, or nothing left of the read)
+            // the new backbone lies over [lo_t, hi_t) of the previous one, margins included (0-based)
+            const int64_t org = (int64_t)o.trim + r0[g];
+            const int64_t lo_t = org - pad, hi_t = (int64_t)o.trim + r1[g] + pad;
+            int64_t tpos = (int64_t)cur_start[a] - 1;
+            uint32_t qpos = 0, qlo = 0, qhi = 0;
+            int64_t t_first = -1, t_last = -1;
+            for (uint32_t i = 0; i < cur_len[a]; i++) {
+                const char qc = cur_q[cur_off[a] + i], tc = cur_t[cur_off[a] + i];
+                const bool in = tpos >= lo_t && tpos < hi_t;
+                if (qc != '-') { if (tpos < lo_t) qlo = qpos + 1; if (in) qhi = qpos + 1; qpos++; }
+                if (in && tc != '-') { if (t_first < 0) t_first = tpos; t_last = tpos; }
+                if (tc != '-') tpos++;
             }
-            p_q.clear(); p_t.clear();
-            uint64_t tot = 0;
-            size_t g = 0;
-            for (size_t a = 0; a < A; a++) {
-                while (b.begin[g + 1] <= a) g++;
-                const std::string &B = bb[g];
-                p_qoff[a] = p_q.size(); p_toff[a] = p_t.size(); p_ooff[a] = tot; p_qlen[a] = 0; p_tlen[a] = 0; w0[a] = 0;
-                if (B.empty() || cur_len[a] == 0) { cur_len[a] = 0; continue; }     // (no consensus, or nothing left of the read)
-                // the new backbone lies over [lo_t, hi_t) of the previous one, margins included (0-based)
-                const int64_t org = (int64_t)o.trim + r0[g];
-                const int64_t lo_t = org - pad, hi_t = (int64_t)o.trim + r1[g] + pad;
-                int64_t tpos = (int64_t)cur_start[a] - 1;
-                uint32_t qpos = 0, qlo = 0, qhi = 0;
-                int64_t t_first = -1, t_last = -1;
-                for (uint32_t i = 0; i < cur_len[a]; i++) {
-                    const char qc = cur_q[cur_off[a] + i], tc = cur_t[cur_off[a] + i];
-                    const bool in = tpos >= lo_t && tpos < hi_t;
-                    if (qc != '-') { if (tpos < lo_t) qlo = qpos + 1; if (in) qhi = qpos + 1; qpos++; }
-                    if (in && tc != '-') { if (t_first < 0) t_first = tpos; t_last = tpos; }
-                    if (tc != '-') tpos++;
+            if (qhi <= qlo || t_first < 0) { cur_len[a] = 0; continue; }
+            const int64_t a0 = std::max<int64_t>(0, std::min<int64_t>(t_first - org - pad, (int64_t)B.size()));
+            const int64_t a1 = std::max<int64_t>(a0, std::min<int64_t>(t_last + 1 - org + pad, (int64_t)B.size()));
+            w0[a] = (uint32_t)a0; p_tlen[a] = (uint32_t)(a1 - a0);
+            p_t.append(B, (size_t)a0, (size_t)(a1 - a0));
+            // the read in the target's orientation, clipped
+            fwd.resize(b.len[a]);
+            if (b.strand[a] == '-') revcomp_into(&fwd[0], b.q.data() + b.off[a], b.len[a]);
+            else memcpy(&fwd[0], b.q.data() + b.off[a], b.len[a]);
+            p_qlen[a] = qhi - qlo;
+            p_q.append(fwd, cur_qbase[a] + qlo, qhi - qlo);
+            cur_qbase[a] += qlo;
+            tot += (uint64_t)p_qlen[a] + p_tlen[a];
+        }
+        p_qa.assign(tot + 1, 0); p_ta.assign(tot + 1, 0);
+        if (p_q.empty()) p_q.push_back(0);
+        if (p_t.empty()) p_t.push_back(0);
+        rc = dagcon_align(ctx, (uint32_t)A, p_qoff.data(), p_qlen.data(), p_toff.data(), p_tlen.data(), p_q.data(), p_q.size(),
+                          p_t.data(), p_t.size(), p_ooff.data(), &p_qa[0], &p_ta[0], p_alen.data());
+        if (rc != DAGCON_OK) { fprintf(stderr, "pbdagcon: alignment failed (%d): %s\n", rc, dagcon_last_error(ctx)); return 1; }
+        // global over the two pieces: backbone bases in front of / behind the read are not part of its alignment
+        k_start.clear(); k_off.clear(); k_len.clear();
+        p_begin.assign(1, 0);
+        g = 0;
+        for (size_t a = 0; a < A; a++) {
+            while (b.begin[g + 1] <= a) { g++; p_begin.push_back(k_start.size()); }
+            if (cur_len[a] == 0) continue;
+            uint32_t n = p_alen[a], lead = 0;
+            uint64_t off = p_ooff[a];
+            while (n && p_qa[off] == '-') { off++; n--; lead++; }
+            while (n && p_qa[off + n - 1] == '-') n--;
+            cur_start[a] = w0[a] + lead + 1u; cur_off[a] = off; cur_len[a] = n;
+            if (n) { k_start.push_back(cur_start[a]); k_off.push_back(off); k_len.push_back(n); }
+        }
+        while (p_begin.size() < (size_t)T + 1) p_begin.push_back(k_start.size());
+        cur_q.swap(p_qa); cur_t.swap(p_ta);            // (the next round clips against these)
+        p_tl.assign(T, 0); p_bboff.assign(T, 0); p_bb.clear();
+        for (uint32_t t2 = 0; t2 < T; t2++) { p_tl[t2] = (uint32_t)bb[t2].size(); p_bboff[t2] = p_bb.size(); p_bb += bb[t2]; }
+        if (p_bb.empty()) p_bb.push_back('N');
+        memset(&db, 0, sizeof db);
+        db.n_targets = T; db.tlen = p_tl.data(); db.aln_begin = p_begin.data();
+        db.aln_start = k_start.data(); db.aln_off = k_off.data(); db.aln_len = k_len.data();
+        db.qstr = cur_q.data(); db.tstr = cur_t.data(); db.blob_bytes = cur_q.size();
+        db.backbone = p_bb.data(); db.backbone_off = p_bboff.data();
+        rc = dagcon_consensus(ctx, &db, &r);
+        if (rc != DAGCON_OK) { fprintf(stderr, "pbdagcon: consensus failed (%d): %s\n", rc, dagcon_last_error(ctx)); return 1; }
+    }
+    return append_results(ctx, b, o, r);
+}
+
+int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scratch) {
+    if (b.ids.empty()) return 0;
+    return o.mode == MODE_RECORDS ? run_records(ctx, b, o) : o.mode == MODE_M5 ? run_m5(ctx, b, o)
+         : o.polish ? run_pre_polish(ctx, actx, b, o, scratch) : run_pre(ctx, b, o);
+}
+
+// ---- consensus workers: one thread + context per GPU and --contexts (the reference starts its N consensus workers itself too,
+// main.cpp:251-274); batches are taken in input order from one queue, their records are printed in input order by whoever completes
+// the next one in line.  Two contexts per GPU: one batch's copy, host preparation and formatting go on beside the other's kernels ----
+struct Workers {
+    const Opts &o;
+    std::vector<int> dev;                                   // the device of every worker
+    std::vector<Batch> bufs;                                // one more than workers: the parser fills one while the others are on GPUs
+    std::mutex mu; std::condition_variable cv;
+    std::vector<Batch *> free_list, work, done;             // work: FIFO; done: completed, waiting for their turn to print
+    unsigned long long next_seq = 0, print_seq = 0;
+    bool stop = false; int status = 0;
+    dagcon_ctx *pin_ctx = nullptr;                          // first context up: page-locked blobs come from it
+    std::vector<std::thread> threads;
+    double t_create = 0, t_flush = 0, t_print = 0, t_wait = 0;
+
+    Workers(const Opts &opts, size_t input_bytes) : o(opts) {
+        const unsigned per_dev = o.contexts ? o.contexts : (input_bytes > 512ull << 20 ? 2u : 1u);
+        for (unsigned k = 0; k < per_dev; k++) for (int d : o.devices) dev.push_back(d);
+        bufs = std::vector<Batch>(dev.size() + 1);
+        for (auto &x : bufs) free_list.push_back(&x);
+    }
+    void start() { for (size_t w = 0; w < dev.size(); w++) threads.emplace_back([this, w] { run(w); }); }
+
+    void run(size_t w) {
+        dagcon_ctx *ctx = nullptr;
+        const double tc0 = wall();
+        int rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], (o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u) | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u), &ctx);
+        dagcon_ctx *actx = ctx;                             // --local --polish: the first alignment on a local context of its own
+        if (rc == DAGCON_OK && o.local && o.polish) {       // (aligns only: the support comes from ctx's last round)
+            rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], DAGCON_FLAG_LOCAL_ALIGN, &actx);
+            if (rc != DAGCON_OK) { dagcon_destroy(ctx); ctx = nullptr; }
+        }
+        if (w == 0) t_create = wall() - tc0;
+        if (rc != DAGCON_OK) {
+            std::lock_guard<std::mutex> lk(mu);
+            status = 1;
+            cv.notify_all();
+            return;
+        }
+        { std::lock_guard<std::mutex> lk(mu); if (!pin_ctx) pin_ctx = ctx; }
+        Blob scratch[2];
+        for (;;) {
+            Batch *b = nullptr;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return !work.empty() || stop; });
+                if (work.empty()) break;
+                b = work.front(); work.erase(work.begin());
+            }
+            const double tf0 = wall();
+            const int st = flush(ctx, actx, *b, o, scratch);
+            const double tf = wall() - tf0;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                t_flush += tf;
+                if (st) status = st;
+                done.push_back(b);
+                // print what is next in line (this batch and any that were waiting on it)
+                for (size_t i = 0; i < done.size();) {
+                    if (done[i]->seq != print_seq) { i++; continue; }
+                    Batch *d = done[i];
+                    done.erase(done.begin() + i);
+                    { const double tp0 = wall(); fwrite(d->out.data(), 1, d->out.size(), stdout); t_print += wall() - tp0; }
+                    d->clear();
+                    free_list.push_back(d);
+                    print_seq++;
+                    i = 0;
                 }
-                if (qhi <= qlo || t_first < 0) { cur_len[a] = 0; continue; }
-                const int64_t a0 = std::max<int64_t>(0, std::min<int64_t>(t_first - org - pad, (int64_t)B.size()));
-                const int64_t a1 = std::max<int64_t>(a0, std::min<int64_t>(t_last + 1 - org + pad, (int64_t)B.size()));
-                w0[a] = (uint32_t)a0; p_tlen[a] = (uint32_t)(a1 - a0);
-                p_t.append(B, (size_t)a0, (size_t)(a1 - a0));
-                // the read in the target's orientation, clipped
-                fwd.resize(b.len[a]);
-                if (b.strand[a] == '-') revcomp_into(&fwd[0], b.q.data() + b.off[a], b.len[a]);
-                else memcpy(&fwd[0], b.q.data() + b.off[a], b.len[a]);
-                p_qlen[a] = qhi - qlo;
-                p_q.append(fwd, cur_qbase[a] + qlo, qhi - qlo);
-                cur_qbase[a] += qlo;
-                tot += (uint64_t)p_qlen[a] + p_tlen[a];
             }
-            p_qa.assign(tot + 1, 0); p_ta.assign(tot + 1, 0);
-            if (p_q.empty()) p_q.push_back(0);
-            if (p_t.empty()) p_t.push_back(0);
-            rc = dagcon_align(ctx, (uint32_t)A, p_qoff.data(), p_qlen.data(), p_toff.data(), p_tlen.data(), p_q.data(), p_q.size(),
-                              p_t.data(), p_t.size(), p_ooff.data(), &p_qa[0], &p_ta[0], p_alen.data());
-            if (rc != DAGCON_OK) { fprintf(stderr, "pbdagcon: alignment failed (%d): %s\n", rc, dagcon_last_error(ctx)); return 1; }
-            // global over the two pieces: backbone bases in front of / behind the read are not part of its alignment
-            k_start.clear(); k_off.clear(); k_len.clear();
-            p_begin.assign(1, 0);
-            g = 0;
-            for (size_t a = 0; a < A; a++) {
-                while (b.begin[g + 1] <= a) { g++; p_begin.push_back(k_start.size()); }
-                if (cur_len[a] == 0) continue;
-                uint32_t n = p_alen[a], lead = 0;
-                uint64_t off = p_ooff[a];
-                while (n && p_qa[off] == '-') { off++; n--; lead++; }
-                while (n && p_qa[off + n - 1] == '-') n--;
-                cur_start[a] = w0[a] + lead + 1u; cur_off[a] = off; cur_len[a] = n;
-                if (n) { k_start.push_back(cur_start[a]); k_off.push_back(off); k_len.push_back(n); }
+            cv.notify_all();
+        }
+        // (blobs that were page-locked through this context are released before it goes)
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            for (auto &x : bufs) { if (x.q.owner == ctx) x.q.release(); if (x.t.owner == ctx) x.t.release(); }
+            if (pin_ctx == ctx) pin_ctx = nullptr;
+        }
+        scratch[0].release(); scratch[1].release();
+        if (actx != ctx) dagcon_destroy(actx);
+        dagcon_destroy(ctx);
+    }
+    dagcon_ctx *pin() { std::lock_guard<std::mutex> lk(mu); return pin_ctx; }
+    // a free batch buffer for the parser (waits for a worker to finish one); NULL: a worker gave up
+    Batch *acquire() {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !free_list.empty() || status; });
+        if (free_list.empty()) return nullptr;
+        Batch *b = free_list.back(); free_list.pop_back();
+        return b;
+    }
+    // hands the filled batch to the workers and takes the next free buffer; the status so far
+    int submit(Batch *&b) {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            if (status) return status;
+            b->seq = next_seq++;
+            work.push_back(b);
+        }
+        cv.notify_all();
+        const double tw0 = wall();
+        b = acquire();
+        t_wait += wall() - tw0;
+        return b ? 0 : 1;
+    }
+    // every submitted batch printed (or a worker gave up), every worker gone: each destroys its context, so the device
+    // memory goes back in order and the next process's large hipMalloc does not wait for it
+    int drain() {
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return print_seq == next_seq || status; });
+            stop = true;
+        }
+        cv.notify_all();
+        for (auto &w : threads) w.join();
+        return status;
+    }
+};
+
+// ---- the input ---------------------------------------------------------------------------------------------------------
+struct Input {
+    const char *data = nullptr; size_t size = 0;
+    std::string slurp;                 // stdin
+    void *map = nullptr;               // a file
+    size_t unmapped = 0;               // pages of map dropped so far
+    unsigned nthr = 1;                 // host threads of every stage (-j)
+
+    // mmap a file, or slurp stdin
+    bool open(const std::string &path) {
+        if (path == "-") {
+            char buf[1 << 16];
+            size_t n;
+            while ((n = fread(buf, 1, sizeof buf, stdin)) > 0) slurp.append(buf, n);
+            data = slurp.data(); size = slurp.size();
+            return true;
+        }
+        int fd = ::open(path.c_str(), O_RDONLY);
+        if (fd < 0) { fprintf(stderr, "pbdagcon: error opening file: %s\n", path.c_str()); return false; }
+        struct stat st;
+        if (fstat(fd, &st) != 0) { close(fd); return false; }
+        size = (size_t)st.st_size;
+        if (size) {
+            map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (map == MAP_FAILED) { fprintf(stderr, "pbdagcon: mmap failed\n"); close(fd); return false; }
+            data = (const char *)map;
+        }
+        close(fd);
+        return true;
+    }
+    // the text is finished with (--bam: the inflated records take its place)
+    void replace(const char *d, size_t n) {
+        if (map) { munmap(map, size); map = nullptr; }
+        slurp.clear(); slurp.shrink_to_fit();
+        data = d; size = n;
+    }
+    // where the line that holds byte p ends (p itself at the end of the input)
+    size_t line_end(size_t p) const {
+        if (p >= size) return size;
+        const char *nl = (const char *)memchr(data + p, '\n', size - p);
+        return nl ? (size_t)(nl - data) + 1 : size;
+    }
+    // The text in front of `dead` is finished with: its page-table entries go now, while the GPU works, instead of all at once at
+    // the end (0.3 s for 26 GB of text).  MADV_DONTNEED takes the address-space lock shared (munmap takes it exclusively and would
+    // stall the workers' page faults and the driver's pinning): the threads drop a share of the range each
+    void drop_pages(size_t dead) {
+        const size_t upto = dead & ~(size_t)((2u << 20) - 1);
+        if (!map || upto <= unmapped) return;
+        const size_t n2m = (upto - unmapped) >> 21;
+        on_threads(nthr, [&](unsigned k) {
+            const size_t a = unmapped + ((n2m * k / nthr) << 21), e = unmapped + ((n2m * (k + 1) / nthr) << 21);
+            if (e > a) madvise((char *)map + a, e - a, MADV_DONTNEED);
+        });
+        unmapped = upto;
+    }
+};
+
+// ---- parse (Alignment.cpp:44-80) and group by target id (BlasrM5AlnProvider.cpp:34-55) ----
+// 1. index: the -j threads split the text at line starts and record where every field of every record is (nothing is
+//    copied);
+// 2. in file order: records are grouped into targets and targets into batches;
+// 3. per batch the same threads copy (or reverse-complement) the strings into the blobs.
+// The text is taken a slab at a time, so that the first batch reaches the GPU before the whole file has been indexed;
+// the records of a slab's last (possibly unfinished) target are carried into the next slab.
+
+// what one thread found in its piece of a slab
+template <class R>
+struct Part { std::vector<R> recs; int err = 0; unsigned long long err_rec = 0; int err_nf = 0; unsigned long long lines = 0, skipped = 0; };
+
+// what the two indexers share: the slab's records in file order (the carried ones first), up to the first malformed one
+template <class R>
+struct Indexer {
+    Input &in;
+    std::vector<R> carry;
+    std::vector<Part<R>> parts;
+    std::vector<const R *> recs;
+    bool had_error = false;
+    unsigned long long n_rec_before = 0;
+    double t_index = 0, t_fill = 0;                        // PBDAGCON_TIMING
+    explicit Indexer(Input &i) : in(i), parts(i.nthr) {}
+    void begin() { recs.clear(); for (const R &r : carry) recs.push_back(&r); }
+    void take(const Part<R> &p) { for (const R &r : p.recs) recs.push_back(&r); n_rec_before += p.recs.size(); }
+    // [s0, s1) cut at line starts into a piece per thread; thread k has line(part k, text, length) parse every line of
+    // its piece, until it returns false
+    template <class Line>
+    void index_lines(size_t s0, size_t s1, Line line) {
+        const unsigned nthr = in.nthr;
+        std::vector<size_t> cut(nthr + 1, s1);
+        cut[0] = s0;
+        for (unsigned k = 1; k < nthr; k++) {
+            size_t p0 = std::max(cut[k - 1], s0 + (size_t)((unsigned long long)(s1 - s0) * k / nthr));
+            if (p0 > s0 && p0 < s1) p0 = std::min(in.line_end(p0 - 1), s1);
+            cut[k] = std::min(p0, s1);
+        }
+        on_threads(nthr, [&](unsigned k) {
+            Part<R> &pt = parts[k];
+            pt.recs.clear(); pt.err = 0; pt.lines = 0; pt.skipped = 0;
+            for (size_t pos = cut[k]; pos < cut[k + 1];) {
+                const char *text = in.data + pos;
+                const size_t ll = dg_line(in.data, in.size, pos);
+                pt.lines++;
+                if (!line(pt, text, ll)) return;
             }
-            while (p_begin.size() < (size_t)T + 1) p_begin.push_back(k_start.size());
-            cur_q.swap(p_qa); cur_t.swap(p_ta);            // (the next round clips against these)
-            p_tl.assign(T, 0); p_bboff.assign(T, 0); p_bb.clear();
-            for (uint32_t t2 = 0; t2 < T; t2++) { p_tl[t2] = (uint32_t)bb[t2].size(); p_bboff[t2] = p_bb.size(); p_bb += bb[t2]; }
-            if (p_bb.empty()) p_bb.push_back('N');
-            memset(&db, 0, sizeof db);
-            db.n_targets = T; db.tlen = p_tl.data(); db.aln_begin = p_begin.data();
-            db.aln_start = k_start.data(); db.aln_off = k_off.data(); db.aln_len = k_len.data();
-            db.qstr = cur_q.data(); db.tstr = cur_t.data(); db.blob_bytes = cur_q.size();
-            db.backbone = p_bb.data(); db.backbone_off = p_bboff.data();
-            rc = dagcon_consensus(ctx, &db, &r);
-            if (rc != DAGCON_OK) { fprintf(stderr, "pbdagcon: consensus failed (%d): %s\n", rc, dagcon_last_error(ctx)); return 1; }
+        });
+    }
+};
+
+// a record of .m5 or .pre text
+struct Rec {
+    const char *rname, *qname, *q, *t;                     // target and query name, as DgAlnRec calls them
+    uint32_t rname_len, qname_len, len, tl, tlen, start;   // len, tl: of the query and the target string; tlen: of the target
+    char strand;
+};
+
+struct TextIndexer : Indexer<Rec> {
+    const Opts &o;
+    TextIndexer(Input &i, const Opts &opts) : Indexer<Rec>(i), o(opts) {}
+
+    static bool parse_line(Mode mode, Part<Rec> &pt, const char *line, size_t ll) {
+        const char *f[19];
+        size_t fl[19], i = 0;
+        int nf = 0;
+        while (i < ll && nf < 19) {
+            while (i < ll && line[i] == ' ') i++;
+            if (i >= ll) break;
+            const char *sp = (const char *)memchr(line + i, ' ', ll - i);   // fields 16..18 are ~tlen chars each
+            const size_t j = sp ? (size_t)(sp - line) : ll;
+            f[nf] = line + i; fl[nf] = j - i; nf++;
+            i = j;
+        }
+        if (nf == 0) return true;                       // blank line
+        Rec r;
+        if (mode == MODE_PRE) {
+            // Alignment.cpp:82-112 parsePre: qid tid strand tlen tstart tend qseq tseq
+            if (nf < 8) { pt.err = 1; pt.err_rec = pt.recs.size() + 1; pt.err_nf = nf; return false; }
+            r.rname = f[1]; r.rname_len = (uint32_t)fl[1];
+            r.qname = f[0]; r.qname_len = (uint32_t)fl[0];
+            r.strand = f[2][0];
+            r.tlen = tok_u32(f[3], fl[3]);
+            r.start = tok_u32(f[4], fl[4]);             // (SimpleAligner.cpp:61 adds the 1)
+            r.q = f[6]; r.len = (uint32_t)fl[6];
+            r.t = f[7]; r.tl = (uint32_t)fl[7];
+        } else {
+            if (nf < 19) { pt.err = 1; pt.err_rec = pt.recs.size() + 1; pt.err_nf = nf; return false; }
+            if (fl[16] != fl[18]) { pt.err = 2; pt.err_rec = pt.recs.size() + 1; return false; }
+            r.rname = f[5]; r.rname_len = (uint32_t)fl[5];
+            r.qname = f[0]; r.qname_len = (uint32_t)fl[0];
+            r.q = f[16]; r.t = f[18]; r.len = (uint32_t)fl[16]; r.tl = r.len;
+            r.tlen = tok_u32(f[6], fl[6]);
+            r.start = tok_u32(f[7], fl[7]) + 1;             // Alignment.cpp:65-66
+            r.strand = f[9][0];
+        }
+        pt.recs.push_back(r);
+        return true;
+    }
+    // indexes the slab that begins at s0; where the next one begins
+    size_t index(size_t s0, size_t slab_bytes) {
+        const size_t s1 = in.line_end(std::min(in.size, s0 + slab_bytes));   // a slab ends at a line end
+        index_lines(s0, s1, [this](Part<Rec> &pt, const char *text, size_t ll) { return parse_line(o.mode, pt, text, ll); });
+        begin();
+        for (const Part<Rec> &pt : parts) {
+            take(pt);
+            if (pt.err == 1) fprintf(stderr, "pbdagcon: format error: record %llu has %d fields, %d expected\n", n_rec_before + 1, pt.err_nf, o.mode == MODE_PRE ? 8 : 19);
+            if (pt.err == 2) fprintf(stderr, "pbdagcon: format error: record %llu: query and target strings differ in length\n", n_rec_before + 1);
+            if (pt.err) { had_error = true; break; }
+        }
+        return s1;
+    }
+    bool add_target(Batch &b, const Rec &r, size_t &) { b.ids.emplace_back(r.rname, r.rname_len); b.tlen.push_back(r.tlen); return true; }
+    void add_record(Batch &b, const Rec &r, size_t &bytes, size_t &bytes2) {
+        b.start.push_back(r.start); b.len.push_back(r.len); b.len2.push_back(r.tl);
+        b.off.push_back(bytes); b.off2.push_back(bytes2);
+        b.strand.push_back(r.strand);
+        bytes += r.len; bytes2 += r.tl;                     // (-a: the t strings count too)
+    }
+    // copies the strings of records [r0, r1) into batch b, whose offsets are set already
+    void fill(Batch &b, size_t r0, size_t r1) {
+        on_threads(in.nthr, [&](unsigned k) {
+            for (size_t x = r0 + k; x < r1; x += in.nthr) {
+                const Rec &r = *recs[x];
+                char *dq = b.q.data() + b.off[x - r0], *dt = b.t.data() + b.off2[x - r0];
+                if (o.mode == MODE_M5 && r.strand == '-') {     // Alignment.cpp:69-75: start is NOT flipped (Q6)
+                    revcomp_into(dq, r.q, r.len);
+                    revcomp_into(dt, r.t, r.len);
+                } else {                                        // (.pre: sequences as they are, Alignment.cpp:112)
+                    memcpy(dq, r.q, r.len);
+                    memcpy(dt, r.t, r.tl);
+                }
+            }
+        });
+    }
+    // --dump-parsed: the batch as it would go to the device
+    void dump(Batch &b, size_t r0, size_t r1) {
+        for (size_t y = r0, g = 0; y < r1; y++) {
+            const Rec &r = *recs[y];
+            while (b.begin[g + 1] <= y - r0) g++;
+            printf("%.*s\t%u\t%u\t%c\t%.*s\t%.*s\t%.*s\n", (int)r.rname_len, r.rname, b.tlen[g], r.start, r.strand,
+                   (int)r.qname_len, r.qname, (int)r.len, b.q.data() + b.off[y - r0], (int)r.tl, b.t.data() + b.off2[y - r0]);
         }
     }
-    dagcon_support sup;
-    memset(&sup, 0, sizeof sup);
-    if (o.fastq && (rc = dagcon_fetch_support(ctx, &sup)) != DAGCON_OK) {
-        fprintf(stderr, "pbdagcon: per-base support failed (%d): %s\n", rc, dagcon_last_error(ctx));
-        return 1;
-    }
-    char head[64];
-    for (uint32_t g = 0; g < r.n_targets; g++) {
-        if (o.verbose)
-            fprintf(stderr, "Consensus calling: %s Alignments: %llu\n", b.ids[g].c_str(),
-                    (unsigned long long)(b.begin[g + 1] - b.begin[g]));
-        // a failure is confined to its target (the reference's assert hits one worker's one target,
-        // AlnGraphBoost.cpp:71-72): warn, go on with the rest
-        if (r.target_status[g] != DAGCON_OK)
-            fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(),
-                    r.target_status[g] == DAGCON_ERR_NONCONFORMING && o.sam ? dg_nonconforming_text(o.cs)
-                    : r.target_status[g] == DAGCON_ERR_NONCONFORMING ? "an alignment leaves the backbone or holds a non-printable byte"
-                    : r.target_status[g] == DAGCON_ERR_UNSUPPORTED ? "too large" : "internal error");
-        for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
-            // main.cpp:141-143  ">%s/%d_%d\n%s\n"; --fastq: '@' for '>' (src/cpp/pbdagcon_wf.sh:20-22), then + and qualities
-            if (o.fastq) {
-                snprintf(head, sizeof head, "/%d_%d", r.range0[s], r.range1[s]);
-                if (!dg_append_fastq(b.out, b.ids[g] + head, r.seq_blob + r.seq_off[s], r.seq_len[s], sup.weight + r.seq_off[s],
-                                     sup.depth + r.seq_off[s])) {
-                    fprintf(stderr, "pbdagcon: target %s: per-base support out of range\n", b.ids[g].c_str());
-                    return 1;
-                }
-                continue;
+    void report_skipped() {}
+};
+
+// records of a DgRecordKind: --sam text is indexed like .m5 text, on the -j threads; --bam by one thread that stops at
+// the slab's end (there is no per-base work in it); --paf all at once (paf.h has parsed, checked and grouped the lines)
+struct RecordIndexer : Indexer<DgAlnRec> {
+    const Opts &o; const DgKindDesc &kd; const DgRefSeqs &ref;
+    DgBamReader &bam;
+    const DgPafInput &paf;
+    unsigned long long n_lines_before = 0, n_skipped = 0;
+    std::unordered_set<std::string> seen_targets;         // a target whose records come back after another's is an error
+
+    RecordIndexer(Input &i, const Opts &opts, const DgRefSeqs &rf, DgBamReader &bm, const DgPafInput &pf)
+        : Indexer<DgAlnRec>(i), o(opts), kd(dg_kind(opts.kind)), ref(rf), bam(bm), paf(pf) {}
+
+    size_t index(size_t s0, size_t slab_bytes) {
+        if (o.kind == DG_REC_PLAIN) return index_sam(s0, in.line_end(std::min(in.size, s0 + slab_bytes)));
+        begin();
+        Part<DgAlnRec> &pt = parts[0];
+        pt.recs.clear();
+        if (o.kind == DG_REC_PACKED) {
+            const size_t s1 = std::min(in.size, s0 + slab_bytes);
+            DgBamRec br; DgAlnRec r; std::string err;
+            while (bam.at < s1) {                          // (the reader stops behind the first record that ends at s1 or later)
+                const int rc = bam.next(br, err);
+                if (rc == 0) break;
+                if (rc < 0) { fprintf(stderr, "pbdagcon: format error: %s\n", err.c_str()); had_error = true; break; }
+                dg_bam_rec(bam, br, ref, r);
+                if (!r.target) { fprintf(stderr, "pbdagcon: record %llu: RNAME is not a sequence of %s\n", br.ordinal, o.ref.c_str()); had_error = true; break; }
+                pt.recs.push_back(r);
             }
-            b.out += '>'; b.out += b.ids[g];
-            snprintf(head, sizeof head, "/%d_%d\n", r.range0[s], r.range1[s]);
-            b.out += head;
-            b.out.append(r.seq_blob + r.seq_off[s], r.seq_len[s]);
-            b.out += '\n';
+            n_skipped = bam.n_skipped;
+            take(pt);
+            return bam.at >= in.size ? in.size : std::max(bam.at, s0);   // behind the last record taken
+        }
+        pt.recs.resize(paf.recs.size());
+        for (size_t k = 0; k < paf.recs.size(); k++) dg_paf_rec(paf.recs[k], o.kind == DG_REC_CS, pt.recs[k]);
+        n_skipped = paf.n_secondary;
+        take(pt);
+        return in.size;
+    }
+    // QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL, tab-separated; header lines skipped
+    size_t index_sam(size_t s0, size_t s1) {
+        index_lines(s0, s1, [this](Part<DgAlnRec> &pt, const char *text, size_t ll) {
+            DgSamLine sm;
+            const DgSamWhat what = dg_sam_split(text, ll, sm, tok_u32);
+            if (what == DG_SAM_NO_RECORD) return true;
+            if (what == DG_SAM_SKIPPED) { pt.skipped++; return true; }
+            pt.err_rec = pt.lines;
+            if (what == DG_SAM_FEW_FIELDS) { pt.err = 1; pt.err_nf = sm.nf; return false; }
+            if (what == DG_SAM_BAD_CIGAR) { pt.err = 3; return false; }
+            DgAlnRec r;
+            dg_sam_rec(sm, tok_u32(sm.f[3], sm.fl[3]), pt.lines, ref, r);
+            if (!r.target) { pt.err = 4; return false; }
+            pt.recs.push_back(r);
+            return true;
+        });
+        begin();
+        for (Part<DgAlnRec> &pt : parts) {
+            for (DgAlnRec &r : pt.recs) r.where += n_lines_before;      // line numbers of the whole input
+            n_skipped += pt.skipped;
+            take(pt);
+            if (pt.err) {
+                const unsigned long long ln = n_lines_before + pt.err_rec;
+                if (pt.err == 1) fprintf(stderr, "pbdagcon: format error: line %llu has %d fields, 11 expected\n", ln, pt.err_nf);
+                else if (pt.err == 3) fprintf(stderr, "pbdagcon: format error: line %llu: malformed CIGAR\n", ln);
+                else fprintf(stderr, "pbdagcon: line %llu: RNAME is not a sequence of %s\n", ln, o.ref.c_str());
+                had_error = true; break;
+            }
+            n_lines_before += pt.lines;
+        }
+        return s1;
+    }
+    bool add_target(Batch &b, const DgAlnRec &r, size_t &bytes2) {
+        if (!seen_targets.emplace(r.rname, r.rname_len).second) {
+            fprintf(stderr, "pbdagcon: %s %llu: records of %.*s come back after another target's; the records of one RNAME "
+                    "must be consecutive (sort the %s by coordinate)\n", kd.unit, r.where, (int)r.rname_len, r.rname, kd.format);
+            return false;
+        }
+        b.ids.emplace_back(r.rname, r.rname_len);
+        b.tlen.push_back(r.target->len);
+        b.toff.push_back(bytes2); b.tsrc.push_back(ref.bases.data() + r.target->off); bytes2 += r.target->len;
+        return true;
+    }
+    void add_record(Batch &b, const DgAlnRec &r, size_t &bytes, size_t &) {
+        b.opb.push_back(b.opb.back() + r.nops);
+        b.start.push_back(r.pos);
+        b.off.push_back(bytes); b.len.push_back(r.q_len);
+        b.reverse.push_back(r.reverse ? 1 : 0);
+        if (o.kind == DG_REC_CS) { b.cs_len.push_back(r.cs_len); b.tspan.push_back(r.t_span); }
+        bytes += dg_blob_bytes(o.kind, r);
+    }
+    // the targets' bases, once each; of every record its bytes of the q blob as they lie in the input and its ops
+    void fill(Batch &b, size_t r0, size_t r1) {
+        b.ops.resize(b.opb.back());
+        on_threads(in.nthr, [&](unsigned k) {
+            for (size_t g = k; g < b.tsrc.size(); g += in.nthr) memcpy(b.t.data() + b.toff[g], b.tsrc[g], b.tlen[g]);
+            for (size_t x = r0 + k; x < r1; x += in.nthr) {
+                const DgAlnRec &r = *recs[x];
+                memcpy(b.q.data() + b.off[x - r0], dg_blob(o.kind, r), dg_blob_bytes(o.kind, r));
+                dg_rec_ops(o.kind, r, b.ops.data() + b.opb[x - r0]);
+            }
+        });
+    }
+    // --dump-parsed: what --sam prints for the SAM record of the same alignment -- RNAME, its length in --ref, POS, strand, QNAME,
+    // SEQ, CIGAR (from the batch's ops) -- with SEQ and CIGAR made for printing only where the kind has neither: --bam: SEQ decoded;
+    // --paf: SEQ the whole read in the target's orientation, soft clips qs and qlen - qe around the cg ops, swapped for '-'; --cs:
+    // SEQ the decoded read, the CIGAR the decoded = X I D ops
+    void dump(Batch &b, size_t r0, size_t r1) {
+        for (size_t y = r0; y < r1; y++) {
+            const DgAlnRec &r = *recs[y];
+            const char *q = b.q.data() + b.off[y - r0];
+            std::string seq(q, o.kind == DG_REC_PLAIN ? r.q_len : 0);
+            std::string cigar = dg_cigar_text(b.ops.data() + b.opb[y - r0], b.opb[y - r0 + 1] - b.opb[y - r0]);
+            if (o.kind == DG_REC_PACKED) {
+                for (uint32_t i = 0; i < r.q_len; i++) seq += dg_bam_base((const uint8_t *)q, i);
+            } else if (o.kind == DG_REC_STRANDED) {
+                const uint32_t c0 = r.reverse ? r.read_len - r.qs - r.q_len : r.qs, c1 = r.read_len - r.q_len - c0;
+                seq = r.reverse ? dg_paf_revcomp(r.read, r.read_len) : std::string(r.read, r.read_len);
+                cigar = (c0 ? std::to_string(c0) + "S" : "") + cigar + (c1 ? std::to_string(c1) + "S" : "");
+            } else if (o.kind == DG_REC_CS) {
+                std::vector<uint32_t> dops;
+                if (!dg_cs_decode(q, r.cs_len, ref.bases.data() + r.target->off, r.target->len, r.pos, seq, dops)) { seq = "*"; dops.clear(); }
+                cigar = dg_cigar_text(dops.data(), dops.size());
+            }
+            printf("%.*s\t%u\t%u\t%c\t%.*s\t%s\t%s\n", (int)r.rname_len, r.rname, r.target->len, r.pos, r.reverse ? '-' : '+',
+                   (int)r.qname_len, r.qname, seq.c_str(), cigar.c_str());
         }
     }
-    return 0;
+    void report_skipped() { if (o.verbose) fprintf(stderr, "pbdagcon: %llu %s\n", n_skipped, kd.skipped_what); }
+};
+
+// per slab: index -> group into batches -> fill -> submit (or dump); the status
+template <class Ix>
+int parse_input(Ix &ix, size_t first, const Opts &o, Workers &wk) {
+    Input &in = ix.in;
+    const size_t slab_bytes = o.slab_bytes ? o.slab_bytes : std::max<size_t>(o.batch_bytes, 256u << 20);
+    const bool want_pin = o.pinned == 1 || (o.pinned < 0 && in.size > 2 * o.batch_bytes);
+    auto same_target = [](const auto &x, const auto &y) { return x.rname_len == y.rname_len && memcmp(x.rname, y.rname, x.rname_len) == 0; };
+    int status = 0;
+    Batch *b = o.dump ? &wk.bufs[0] : wk.acquire();
+    if (!b) status = 1;
+    size_t slab_pos = first;
+    while (status == 0 && !ix.had_error && (slab_pos < in.size || !ix.carry.empty())) {
+        { const double t0 = wall(); slab_pos = ix.index(slab_pos, slab_bytes); ix.t_index += wall() - t0; }
+        const auto &recs = ix.recs;
+        const bool eof = slab_pos >= in.size || ix.had_error;
+        // all but the last target of the slab (it may go on in the next one)
+        size_t n_use = recs.size();
+        if (!eof) while (n_use > 0 && same_target(*recs[n_use - 1], *recs.back())) n_use--;
+        size_t rb = 0, bytes = 0, bytes2 = 0;            // first record of the batch being formed; bytes of its q and t blobs
+        for (size_t x = 0; x <= n_use && status == 0; x++) {
+            const bool last = x == n_use;
+            const bool new_target = !last && (x == rb || !same_target(*recs[x], *recs[x - 1]));
+            // a batch is closed when it is full, and at the end of the slab's usable records once it
+            // holds something (at the end of the input whatever it holds)
+            if (last || (new_target && x > rb && (b->ids.size() >= o.batch_targets || bytes + bytes2 >= o.batch_bytes))) {
+                if (x > rb) {
+                    b->begin.push_back(b->start.size());
+                    const double t0 = wall();
+                    dagcon_ctx *pin = want_pin ? wk.pin() : nullptr;
+                    if (!b->q.resize(bytes, pin) || !b->t.resize(bytes2, pin)) { fprintf(stderr, "pbdagcon: out of memory\n"); exit(1); }
+                    ix.fill(*b, rb, x);
+                    ix.t_fill += wall() - t0;
+                    if (o.dump) { ix.dump(*b, rb, x); b->clear(); }
+                    else status = wk.submit(b);
+                }
+                rb = x; bytes = 0; bytes2 = 0;
+                if (last || status) break;
+            }
+            if (new_target) {
+                if (x > rb) b->begin.push_back(b->start.size());
+                if (!ix.add_target(*b, *recs[x], bytes2)) { ix.had_error = true; break; }
+            }
+            ix.add_record(*b, *recs[x], bytes, bytes2);
+        }
+        // the unfinished target's records wait for the next slab
+        decltype(ix.carry) next_carry;
+        for (size_t x = n_use; x < recs.size(); x++) next_carry.push_back(*recs[x]);
+        ix.carry.swap(next_carry);
+        // the text in front of the first carried record is finished with
+        in.drop_pages(ix.carry.empty() ? slab_pos : (size_t)(ix.carry[0].qname - in.data));    // (a line begins with its query name)
+        if (eof && ix.carry.empty()) break;
+        if (eof) slab_pos = in.size;
+    }
+    ix.report_skipped();
+    return ix.had_error ? 1 : status;
 }
 
 }  // namespace
@@ -574,620 +1077,78 @@ int flush(dagcon_ctx *ctx, dagcon_ctx *actx, Batch &b, const Opts &o, Blob *scra
 int main(int argc, char **argv) {
     Opts o;
     if (int rc = parse_args(argc, argv, o)) return rc;
-    // PBDAGCON_TIMING=1: where the wall time of the run went, on stderr (seconds)
-    const bool timing = getenv("PBDAGCON_TIMING") != nullptr;
-    g_timing = timing;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_main = now();
-    double t_index = 0, t_fill = 0, t_wait = 0, t_create = 0, t_flush = 0, t_print = 0, t_parse_end = 0, t_joined = 0;
-    // ---- input: mmap a file, or slurp stdin ----
-    const char *data = nullptr;
-    size_t size = 0;
-    std::string slurp;
-    void *map = nullptr;
-    if (o.input == "-") {
-        char buf[1 << 16];
-        size_t n;
-        while ((n = fread(buf, 1, sizeof buf, stdin)) > 0) slurp.append(buf, n);
-        data = slurp.data(); size = slurp.size();
-    } else {
-        int fd = open(o.input.c_str(), O_RDONLY);
-        if (fd < 0) { fprintf(stderr, "pbdagcon: error opening file: %s\n", o.input.c_str()); return 1; }
-        struct stat st;
-        if (fstat(fd, &st) != 0) { close(fd); return 1; }
-        size = (size_t)st.st_size;
-        if (size) {
-            map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (map == MAP_FAILED) { fprintf(stderr, "pbdagcon: mmap failed\n"); close(fd); return 1; }
-            data = (const char *)map;
-        }
-        close(fd);
-    }
-
-    // ---- --sam: the targets' bases, and the header's @SQ lines against them ----
-    DgRefSeqs ref;
-    if (o.sam) {
+    g_timing = getenv("PBDAGCON_TIMING") != nullptr;
+    const double t_main = wall();
+    Input in;
+    in.nthr = std::max(1u, std::min(o.threads, 64u));
+    if (!in.open(o.input)) return 1;
+    // ---- records: the targets' bases (--sam: and the header's @SQ lines against them); --bam: the file inflated (the -j threads), its
+    // header's references against --ref, from here on the input is the inflated records; --paf: the reads, and every line parsed,
+    // checked and grouped by target (targets in --ref order) ----
+    DgRefSeqs ref; DgBamReader bam; DgPafInput paf;
+    size_t first = 0;                                      // where the first record lies
+    if (o.mode == MODE_RECORDS) {
         std::string err;
-        if (!dg_read_fasta(o.ref, ref, err) || (!o.bam && !o.paf && !dg_sam_check_header(data, size, ref, err))) {
-            fprintf(stderr, "pbdagcon: %s\n", err.c_str());
-            return 1;
-        }
+        bool good = dg_read_fasta(o.ref, ref, err);
+        if (good && o.kind == DG_REC_PLAIN) good = dg_sam_check_header(in.data, in.size, ref, err);
+        if (good && o.kind == DG_REC_PACKED) good = bam.open((const uint8_t *)in.data, in.size, o.threads, err) && dg_bam_check_refs(bam, ref, err);
+        paf.cs = o.kind == DG_REC_CS;
+        if (good && o.kind == DG_REC_STRANDED) good = dg_read_reads(o.reads, paf.reads, err);
+        if (good && (o.kind == DG_REC_STRANDED || o.kind == DG_REC_CS)) good = paf.parse(in.data, in.size, ref, err);
+        if (!good) { fprintf(stderr, "pbdagcon: %s\n", err.c_str()); return 1; }
     }
-    // ---- --bam: the file inflated (the -j threads), its header's references against --ref.  From here on data / size
-    // are the inflated records; the compressed file is finished with ----
-    DgBamReader bam;
-    size_t bam_first = 0;                                  // where the first record lies
-    if (o.bam) {
-        std::string err;
-        if (!bam.open((const uint8_t *)data, size, o.threads, err) || !dg_bam_check_refs(bam, ref, err)) {
-            fprintf(stderr, "pbdagcon: %s\n", err.c_str());
-            return 1;
-        }
+    if (o.mode == MODE_RECORDS && o.kind == DG_REC_PACKED) {
         const DgBgzfStats &bs = bam.stats;
         if (o.verbose && !bs.eof_member) fprintf(stderr, "pbdagcon: note: the BAM file does not end with the empty BGZF member (it may be incomplete)\n");
-        if (timing)
+        if (g_timing)
             fprintf(stderr, "pbdagcon timing: --bam inflate: %zu members, %.1f MB -> %.1f MB in %.3f on %u threads (%.1f MB/s of inflated bytes per thread)\n",
                     bs.members, bs.file_bytes / 1e6, bs.inflated_bytes / 1e6, bs.wall, bs.threads, bs.busy > 0 ? bs.inflated_bytes / 1e6 / bs.busy : 0.0);
-        if (map) { munmap(map, size); map = nullptr; }
-        slurp.clear(); slurp.shrink_to_fit();
-        data = (const char *)bam.u.data(); size = bam.u.size();
-        bam_first = bam.at;
+        in.replace((const char *)bam.u.data(), bam.u.size());
+        first = bam.at;
     }
 
-    // ---- --paf: the reads, and every line parsed, checked and grouped by target (targets in --ref order) ----
-    DgPafInput paf;
-    if (o.paf) {
-        std::string err;
-        paf.cs = o.cs;
-        if ((!o.cs && !dg_read_reads(o.reads, paf.reads, err)) || !paf.parse(data, size, ref, err)) {
-            fprintf(stderr, "pbdagcon: %s\n", err.c_str());
-            return 1;
-        }
-    }
-
+    // ---- --window: the window driver takes the records from here (windows.h) ----
     if (o.window && !o.dump) {
         DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0]};
-        if (o.bam) { DgBamSource src(bam, ref); return dg_run_windows(wo, src, ref); }
-        if (o.cs) { DgPafCsSource src(paf, ref); return dg_run_windows(wo, src, ref); }
-        if (o.paf) { DgPafSource src(paf, ref); return dg_run_windows(wo, src, ref); }
-        DgSamSource src(data, size, ref);
+        if (o.kind == DG_REC_PACKED) { DgBamSource src(bam, ref); return dg_run_windows(wo, src, ref); }
+        if (o.kind == DG_REC_CS) { DgPafCsSource src(paf); return dg_run_windows(wo, src, ref); }
+        if (o.kind == DG_REC_STRANDED) { DgPafSource src(paf); return dg_run_windows(wo, src, ref); }
+        DgSamSource src(in.data, in.size, ref);
         return dg_run_windows(wo, src, ref);
     }
 
-    // ---- consensus workers: one thread + context per GPU (the reference starts its N consensus
-    // workers itself too, main.cpp:251-274); batches are taken in input order from one queue, their
-    // records are printed in input order by whoever completes the next one in line ----
-    // (two contexts per GPU: one batch's host-to-device copy, host preparation and record formatting go on
-    // beside the other's kernels)
-    const unsigned per_dev = o.contexts ? o.contexts : (size > 512ull << 20 ? 2u : 1u);
-    std::vector<int> worker_dev;
-    for (unsigned k = 0; k < per_dev; k++) for (int d : o.devices) worker_dev.push_back(d);
-    const size_t ndev = worker_dev.size();
-    const size_t nbuf = ndev + 1;                          // the parser fills one while the others are on GPUs
-    std::vector<Batch> bufs(nbuf);
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<Batch *> free_list, work;                   // work: FIFO
-    for (auto &x : bufs) free_list.push_back(&x);
-    std::vector<Batch *> done;                              // completed, waiting for their turn to print
-    unsigned long long next_seq = 0, print_seq = 0;
-    bool stop = false;
-    int worker_status = 0;
-    dagcon_ctx *pin_ctx = nullptr;                          // first context up: page-locked blobs come from it
-    bool want_pin = o.pinned == 1 || (o.pinned < 0 && size > 2 * o.batch_bytes);
-    std::vector<std::thread> workers;
+    // ---- whole targets: the workers start (context creation hides behind the parsing of the first batch), the input
+    // is parsed into batches slab by slab, the workers drain ----
+    Workers wk(o, in.size);
+    if (!o.dump) wk.start();
+    RecordIndexer rix(in, o, ref, bam, paf);
+    TextIndexer tix(in, o);
+    int status = o.mode == MODE_RECORDS ? parse_input(rix, first, o, wk) : parse_input(tix, first, o, wk);
+    const double t_index = rix.t_index + tix.t_index, t_fill = rix.t_fill + tix.t_fill;
+    const double t_parse_end = wall();
+    bool fast_exit = false;
     if (!o.dump) {
-        for (size_t w = 0; w < ndev; w++) workers.emplace_back([&, w] {
-            dagcon_ctx *ctx = nullptr;
-            dagcon_opts dopt;
-            dagcon_default_opts(&dopt);
-            dopt.min_cov = o.min_cov; dopt.min_len = o.min_len; dopt.trim = o.trim;
-            dopt.min_weight = (int32_t)o.min_cov;          // main.cpp:261,279 (quirk Q1)
-            dopt.device = worker_dev[w];
-            dopt.flags = (o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u) | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u);
-            const double tc0 = now();
-            int rc = dagcon_create(&dopt, &ctx);
-            dagcon_ctx *actx = ctx;                         // --local --polish: the first alignment on a local context of its own
-            if (rc == DAGCON_OK && o.local && o.polish) {
-                dopt.flags = DAGCON_FLAG_LOCAL_ALIGN;           // (aligns only: the support comes from ctx's last round)
-                rc = dagcon_create(&dopt, &actx);
-                if (rc != DAGCON_OK) { dagcon_destroy(ctx); ctx = nullptr; }
-            }
-            if (w == 0) t_create = now() - tc0;
-            if (rc != DAGCON_OK) {
-                fprintf(stderr, "pbdagcon: no usable MI355X as device %d (dagcon_create = %d); there is no CPU fallback\n", worker_dev[w], rc);
-                std::lock_guard<std::mutex> lk(mu);
-                worker_status = 1;
-                cv.notify_all();
-                return;
-            }
-            { std::lock_guard<std::mutex> lk(mu); if (!pin_ctx) pin_ctx = ctx; }
-            Blob scratch[2];
-            for (;;) {
-                Batch *b = nullptr;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return !work.empty() || stop; });
-                    if (work.empty()) break;
-                    b = work.front(); work.erase(work.begin());
-                }
-                const double tf0 = now();
-                const int st = flush(ctx, actx, *b, o, scratch);
-                const double tf = now() - tf0;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    t_flush += tf;
-                    if (st) worker_status = st;
-                    done.push_back(b);
-                    // print what is next in line (this batch and any that were waiting on it)
-                    for (bool again = true; again;) {
-                        again = false;
-                        for (size_t i = 0; i < done.size(); i++) {
-                            if (done[i]->seq != print_seq) continue;
-                            Batch *d = done[i];
-                            done.erase(done.begin() + i);
-                            { const double tp0 = now(); fwrite(d->out.data(), 1, d->out.size(), stdout); t_print += now() - tp0; }
-                            d->clear();
-                            free_list.push_back(d);
-                            print_seq++;
-                            again = true;
-                            break;
-                        }
-                    }
-                }
-                cv.notify_all();
-            }
-            // (blobs that were page-locked through this context are released before it goes)
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                for (auto &x : bufs) { if (x.q.owner == ctx) x.q.release(); if (x.t.owner == ctx) x.t.release(); }
-                if (pin_ctx == ctx) pin_ctx = nullptr;
-            }
-            scratch[0].release(); scratch[1].release();
-            if (actx != ctx) dagcon_destroy(actx);
-            dagcon_destroy(ctx);
-        });
-    }
-    Batch *bp = nullptr;
-    // a free batch buffer for the parser (waits for a worker to finish one)
-    auto acquire = [&]() -> Batch * {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return !free_list.empty() || worker_status; });
-        if (free_list.empty()) return nullptr;
-        Batch *b = free_list.back(); free_list.pop_back();
-        return b;
-    };
-    // hands the filled batch to the workers and takes the next free buffer
-    auto submit = [&]() -> int {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (worker_status) return worker_status;
-            bp->seq = next_seq++;
-            work.push_back(bp);
-        }
-        cv.notify_all();
-        const double tw0 = now();
-        bp = acquire();
-        t_wait += now() - tw0;
-        return bp ? 0 : 1;
-    };
-
-    // ---- parse (Alignment.cpp:44-80) and group by target id (BlasrM5AlnProvider.cpp:34-55) ----
-    // 1. index: o.threads threads split the text at line starts and record where every field of
-    //    every record is (nothing is copied);
-    // 2. in file order: records are grouped into targets and targets into batches;
-    // 3. per batch the same threads copy (or reverse-complement) the strings into the blobs.
-    struct Rec {
-        const char *id, *name, *q, *t;
-        uint32_t idl, namel, len, tlen, start, tl;   // tl: length of the target sequence (.pre); len: of the query string
-        char strand;
-        const char *cg; uint32_t cgl, nops;          // --sam: the CIGAR field and its number of ops (t: the target's bases in --ref);
-                                                     // --bam: the ops themselves, q the 4-bit seq field, len its bases
-        unsigned long long line;                     // --sam: line of the input; --bam: ordinal of the record
-        const char *read; uint32_t read_len, qs;     // --paf: the whole read and where the slice q begins in it (--dump-parsed)
-        uint32_t tspan;                              // --paf --cs: te - ts (cg / cgl: the cs text, q none, len = qe - qs)
-    };
-    struct Part { std::vector<Rec> recs; int err = 0; unsigned long long err_rec = 0; int err_nf = 0; unsigned long long lines = 0, skipped = 0; };
-    unsigned long long n_lines_before = 0, n_skipped = 0;
-    std::unordered_set<std::string> seen_targets;         // --sam: a target whose records come back after another's is an error
-    const unsigned nthr = std::max(1u, std::min(o.threads, 64u));
-    // the text is taken a slab at a time, so that the first batch reaches the GPU before the
-    // whole file has been indexed; the records of a slab's last (possibly unfinished) target
-    // are carried into the next slab
-    const size_t slab_bytes = o.slab_bytes ? o.slab_bytes : std::max<size_t>(o.batch_bytes, 256u << 20);
-    size_t slab_pos = bam_first, unmapped = 0;
-    const char *unit = o.bam ? "record" : "line";          // what an error names
-    unsigned long long n_rec_before = 0;
-    bool had_error = false;
-    int status = 0;
-    std::vector<Rec> carry;
-    std::vector<Part> parts(nthr);
-    std::vector<const Rec *> recs;
-    // --bam: the records up to s1 (the reader stops behind the first one that ends there or later); one thread, there is
-    // no per-base work in it
-    auto index_bam = [&](size_t s1) {
-        Part &pt = parts[0];
-        pt.recs.clear();
-        recs.clear();
-        for (const Rec &r : carry) recs.push_back(&r);
-        DgBamRec br;
-        std::string err;
-        while (bam.at < s1) {
-            const int rc = bam.next(br, err);
-            if (rc == 0) break;
-            if (rc < 0) { fprintf(stderr, "pbdagcon: format error: %s\n", err.c_str()); had_error = true; break; }
-            const std::string &rn = bam.refs[(size_t)br.ref_id].name;
-            const DgRefSeqs::Span *sp = ref.find(rn.data(), rn.size());
-            if (!sp) { fprintf(stderr, "pbdagcon: record %llu: RNAME is not a sequence of %s\n", br.ordinal, o.ref.c_str()); had_error = true; break; }
-            Rec r;
-            r.id = rn.data(); r.idl = (uint32_t)rn.size();
-            r.name = br.name; r.namel = br.name_len;
-            r.q = (const char *)br.seq; r.len = br.l_seq;
-            r.t = ref.bases.data() + sp->off; r.tlen = sp->len; r.tl = 0;
-            r.start = br.pos;
-            r.strand = (br.flag & DG_SAM_REVERSE) ? '-' : '+';
-            r.cg = (const char *)br.ops; r.cgl = br.n_ops * 4u; r.nops = br.n_ops;
-            r.line = br.ordinal;
-            pt.recs.push_back(r);
-        }
-        n_skipped = bam.n_skipped;
-        for (const Rec &r : pt.recs) recs.push_back(&r);
-        n_rec_before += pt.recs.size();
-    };
-    // --paf: the grouped records, all at once (paf.h has parsed and checked the lines)
-    auto index_paf = [&]() {
-        Part &pt = parts[0];
-        pt.recs.clear();
-        recs.clear();
-        for (const DgPafRec &p : paf.recs) {
-            Rec r;
-            r.id = p.tname; r.idl = p.tname_len;
-            r.name = p.qname; r.namel = p.qname_len;
-            r.q = p.q; r.len = p.q_len;
-            r.t = ref.bases.data() + p.tspan.off; r.tlen = p.tspan.len; r.tl = 0;
-            r.start = p.pos;
-            r.strand = p.reverse ? '-' : '+';
-            r.cg = p.cg; r.cgl = p.cg_len; r.nops = p.nops;
-            r.line = p.line;
-            r.read = p.read; r.read_len = p.read_len; r.qs = p.qs;
-            r.tspan = p.t_span;
-            pt.recs.push_back(r);
-        }
-        n_skipped = paf.n_secondary;
-        for (const Rec &r : pt.recs) recs.push_back(&r);
-        n_rec_before += pt.recs.size();
-    };
-    auto index_slab = [&](size_t s0, size_t s1) {
-        if (o.bam) { index_bam(s1); return; }
-        if (o.paf) { index_paf(); return; }
-        std::vector<size_t> cut(nthr + 1, s1);
-        cut[0] = s0;
-        for (unsigned k = 1; k < nthr; k++) {
-            size_t p0 = std::max(cut[k - 1], s0 + (size_t)((unsigned long long)(s1 - s0) * k / nthr));
-            if (p0 > s0 && p0 < s1) {
-                const char *nl = (const char *)memchr(data + p0 - 1, '\n', s1 - (p0 - 1));
-                p0 = nl ? (size_t)(nl - data) + 1 : s1;
-            }
-            cut[k] = std::min(p0, s1);
-        }
-        auto index = [&](unsigned k) {
-            Part &pt = parts[k];
-            pt.recs.clear(); pt.err = 0; pt.lines = 0; pt.skipped = 0;
-            size_t pos = cut[k];
-            const size_t stop = cut[k + 1];
-            while (pos < stop) {
-                const char *line = data + pos;
-                const char *nl = (const char *)memchr(line, '\n', size - pos);
-                size_t ll = nl ? (size_t)(nl - line) : size - pos;
-                pos += ll + (nl ? 1 : 0);
-                if (ll && line[ll - 1] == '\r') ll--;
-                pt.lines++;
-                if (o.sam) {
-                    // QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL, tab-separated; header lines skipped
-                    DgSamLine sm;
-                    const DgSamWhat what = dg_sam_split(line, ll, sm, tok_u32);
-                    if (what == DG_SAM_NO_RECORD) continue;
-                    if (what == DG_SAM_SKIPPED) { pt.skipped++; continue; }
-                    if (what == DG_SAM_FEW_FIELDS) { pt.err = 1; pt.err_rec = pt.lines; pt.err_nf = sm.nf; return; }
-                    if (what == DG_SAM_BAD_CIGAR) { pt.err = 3; pt.err_rec = pt.lines; return; }
-                    const char *const *sf = sm.f; const size_t *sl = sm.fl;
-                    const uint32_t flag = sm.flag;
-                    const long nops = sm.nops;
-                    const DgRefSeqs::Span *sp = ref.find(sf[2], sl[2]);
-                    if (!sp) { pt.err = 4; pt.err_rec = pt.lines; return; }
-                    Rec r;
-                    r.id = sf[2]; r.idl = (uint32_t)sl[2];
-                    r.name = sf[0]; r.namel = (uint32_t)sl[0];
-                    r.q = sf[9]; r.len = (uint32_t)sl[9];
-                    r.t = ref.bases.data() + sp->off; r.tlen = sp->len; r.tl = 0;
-                    r.start = tok_u32(sf[3], sl[3]);             // SAM POS is 1-based, as Alignment::start
-                    r.strand = (flag & DG_SAM_REVERSE) ? '-' : '+';   // (SEQ is in the target's orientation either way)
-                    r.cg = sf[5]; r.cgl = (uint32_t)sl[5]; r.nops = (uint32_t)nops;
-                    r.line = pt.lines;
-                    pt.recs.push_back(r);
-                    continue;
-                }
-                const char *f[19];
-                size_t fl[19];
-                int nf = 0;
-                size_t i = 0;
-                while (i < ll && nf < 19) {
-                    while (i < ll && line[i] == ' ') i++;
-                    if (i >= ll) break;
-                    const char *sp = (const char *)memchr(line + i, ' ', ll - i);   // fields 16..18 are ~tlen chars each
-                    const size_t j = sp ? (size_t)(sp - line) : ll;
-                    f[nf] = line + i; fl[nf] = j - i; nf++;
-                    i = j;
-                }
-                if (nf == 0) continue;                          // blank line
-                if (o.align) {
-                    // Alignment.cpp:82-112 parsePre: qid tid strand tlen tstart tend qseq tseq
-                    if (nf < 8) { pt.err = 1; pt.err_rec = pt.recs.size() + 1; pt.err_nf = nf; return; }
-                    Rec r;
-                    r.id = f[1]; r.idl = (uint32_t)fl[1];
-                    r.name = f[0]; r.namel = (uint32_t)fl[0];
-                    r.strand = f[2][0];
-                    r.tlen = tok_u32(f[3], fl[3]);
-                    r.start = tok_u32(f[4], fl[4]);             // (SimpleAligner.cpp:61 adds the 1)
-                    r.q = f[6]; r.len = (uint32_t)fl[6];
-                    r.t = f[7]; r.tl = (uint32_t)fl[7];
-                    pt.recs.push_back(r);
-                    continue;
-                }
-                if (nf < 19) { pt.err = 1; pt.err_rec = pt.recs.size() + 1; pt.err_nf = nf; return; }
-                if (fl[16] != fl[18]) { pt.err = 2; pt.err_rec = pt.recs.size() + 1; return; }
-                Rec r;
-                r.id = f[5]; r.idl = (uint32_t)fl[5];
-                r.name = f[0]; r.namel = (uint32_t)fl[0];
-                r.q = f[16]; r.t = f[18]; r.len = (uint32_t)fl[16]; r.tl = r.len;
-                r.tlen = tok_u32(f[6], fl[6]);
-                r.start = tok_u32(f[7], fl[7]) + 1;             // Alignment.cpp:65-66
-                r.strand = f[9][0];
-                pt.recs.push_back(r);
-            }
-        };
-        std::vector<std::thread> th;
-        for (unsigned k = 1; k < nthr; k++) th.emplace_back(index, k);
-        index(0);
-        for (auto &x : th) x.join();
-        // records in file order, up to the first malformed one
-        recs.clear();
-        for (const Rec &r : carry) recs.push_back(&r);
-        for (unsigned k = 0; k < nthr; k++) {
-            if (o.sam) {                                       // line numbers of the whole input
-                for (Rec &r : parts[k].recs) r.line += n_lines_before;
-                n_skipped += parts[k].skipped;
-                if (parts[k].err) {
-                    const unsigned long long ln = n_lines_before + parts[k].err_rec;
-                    if (parts[k].err == 1) fprintf(stderr, "pbdagcon: format error: line %llu has %d fields, 11 expected\n", ln, parts[k].err_nf);
-                    else if (parts[k].err == 3) fprintf(stderr, "pbdagcon: format error: line %llu: malformed CIGAR\n", ln);
-                    else fprintf(stderr, "pbdagcon: line %llu: RNAME is not a sequence of %s\n", ln, o.ref.c_str());
-                    for (const Rec &r : parts[k].recs) recs.push_back(&r);
-                    had_error = true; break;
-                }
-                n_lines_before += parts[k].lines;
-            }
-            for (const Rec &r : parts[k].recs) recs.push_back(&r);
-            n_rec_before += parts[k].recs.size();
-            if (parts[k].err == 1) {
-                fprintf(stderr, "pbdagcon: format error: record %llu has %d fields, %d expected\n", n_rec_before + 1, parts[k].err_nf, o.align ? 8 : 19);
-                had_error = true; break;
-            }
-            if (parts[k].err == 2) {
-                fprintf(stderr, "pbdagcon: format error: record %llu: query and target strings differ in length\n", n_rec_before + 1);
-                had_error = true; break;
-            }
-        }
-    };
-    // copies the strings of records [r0, r1) into batch b, whose offsets are set already
-    auto fill_strings = [&](Batch &b, size_t r0, size_t r1, size_t bytes, size_t bytes2) {
-        dagcon_ctx *pin = nullptr;
-        if (want_pin) { std::lock_guard<std::mutex> lk(mu); pin = pin_ctx; }
-        if (!b.q.resize(bytes, pin) || !b.t.resize(bytes2, pin)) { fprintf(stderr, "pbdagcon: out of memory\n"); exit(1); }
-        if (o.sam) b.ops.resize(b.opb.back());
-        auto work = [&](unsigned k) {
-            if (o.sam)                                            // the targets' bases, once each
-                for (size_t g = k; g < b.tsrc.size(); g += nthr) memcpy(b.t.data() + b.toff[g], b.tsrc[g], b.tlen[g]);
-            for (size_t x = r0 + k; x < r1; x += nthr) {
-                const Rec &r = *recs[x];
-                char *dq = b.q.data() + b.off[x - r0], *dt = b.t.data() + b.off2[x - r0];
-                if (o.cs) {                                       // the text behind cs:Z: as it lies in the line
-                    memcpy(dq, r.cg, r.cgl);
-                } else if (o.bam) {                                      // the seq field and the ops as they lie in the record
-                    memcpy(dq, r.q, ((size_t)r.len + 1) / 2);
-                    memcpy(b.ops.data() + b.opb[x - r0], r.cg, r.cgl);
-                } else if (o.sam) {                               // SEQ as it is; the CIGAR as BAM-encoded ops
-                    memcpy(dq, r.q, r.len);
-                    dg_cigar_ops(r.cg, r.cgl, b.ops.data() + b.opb[x - r0]);
-                } else if (o.align) {                                    // .pre: sequences as they are (Alignment.cpp:112)
-                    memcpy(dq, r.q, r.len);
-                    memcpy(dt, r.t, r.tl);
-                } else if (r.strand == '-') {                            // Alignment.cpp:69-75: start is NOT flipped (Q6)
-                    revcomp_into(dq, r.q, r.len);
-                    revcomp_into(dt, r.t, r.len);
-                } else {
-                    memcpy(dq, r.q, r.len);
-                    memcpy(dt, r.t, r.len);
-                }
-            }
-        };
-        std::vector<std::thread> th;
-        for (unsigned k = 1; k < nthr; k++) th.emplace_back(work, k);
-        work(0);
-        for (auto &x : th) x.join();
-    };
-    bp = &bufs[0];
-    if (!o.dump) bp = acquire();
-    if (!bp) status = 1;
-#define b (*bp)
-    while (status == 0 && !had_error && (slab_pos < size || !carry.empty())) {
-        size_t s1 = o.paf ? size : std::min(size, slab_pos + slab_bytes);   // (--paf: the lines were grouped as a whole)
-        if (s1 < size && !o.bam) {                         // a slab ends at a line end
-            const char *nl = (const char *)memchr(data + s1, '\n', size - s1);
-            s1 = nl ? (size_t)(nl - data) + 1 : size;
-        }
-        { const double t0 = now(); index_slab(slab_pos, s1); t_index += now() - t0; }
-        slab_pos = o.bam ? (bam.at >= size ? size : std::max(bam.at, slab_pos)) : s1;   // (--bam: behind the last record taken)
-        const bool eof = slab_pos >= size || had_error;
-        // all but the last target of the slab (it may go on in the next one)
-        size_t n_use = recs.size();
-        if (!eof) {
-            while (n_use > 0 && recs[n_use - 1]->idl == recs.back()->idl &&
-                   memcmp(recs[n_use - 1]->id, recs.back()->id, recs.back()->idl) == 0) n_use--;
-        }
-        size_t rb = 0;                                   // first record of the batch being formed
-        size_t bytes = 0, bytes2 = 0;
-        for (size_t x = 0; x <= n_use && status == 0; x++) {
-            const bool last = x == n_use;
-            const bool new_target = !last && (x == rb || recs[x]->idl != recs[x - 1]->idl ||
-                                              memcmp(recs[x]->id, recs[x - 1]->id, recs[x]->idl) != 0);
-            // a batch is closed when it is full, and at the end of the slab's usable records once it
-            // holds something (at the end of the input whatever it holds)
-            if (last || (new_target && x > rb && (b.ids.size() >= o.batch_targets || bytes + bytes2 >= o.batch_bytes))) {   // (-a: the t strings count too)
-                if (x > rb) {
-                    b.begin.push_back(b.start.size());
-                    { const double t0 = now(); fill_strings(b, rb, x, bytes, bytes2); t_fill += now() - t0; }
-                    if (o.dump) {
-                        for (size_t y = rb; y < x; y++) {
-                            const Rec &r = *recs[y];
-                            const size_t o0 = b.off[y - rb];
-                            size_t g = 0;
-                            while (b.begin[g + 1] <= y - rb) g++;
-                            if (o.bam) {                       // what --sam prints for the SAM text of the record (SEQ decoded for printing only)
-                                std::string seq(r.len, 0);
-                                for (uint32_t i = 0; i < r.len; i++) seq[i] = dg_bam_base((const uint8_t *)b.q.data() + o0, i);
-                                printf("%.*s\t%u\t%u\t%c\t%.*s\t%s\t%s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
-                                       (int)r.namel, r.name, seq.c_str(),
-                                       dg_cigar_text(b.ops.data() + b.opb[y - rb], b.opb[y - rb + 1] - b.opb[y - rb]).c_str());
-                                continue;
-                            }
-                            if (o.cs) {
-                                // what --sam prints for the equivalent SAM record: SEQ the decoded read, the CIGAR the decoded
-                                // = X I D ops (decoded on the host for printing only)
-                                std::string seq;
-                                std::vector<uint32_t> dops;
-                                if (!dg_cs_decode(b.q.data() + o0, r.cgl, r.t, r.tlen, r.start, seq, dops)) { seq = "*"; dops.clear(); }
-                                printf("%.*s\t%u\t%u\t%c\t%.*s\t%s\t%s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
-                                       (int)r.namel, r.name, seq.c_str(), dg_cigar_text(dops.data(), dops.size()).c_str());
-                                continue;
-                            }
-                            if (o.paf) {
-                                // what --sam prints for the equivalent SAM record: SEQ the whole read in the target's
-                                // orientation (reverse-complemented for printing only), soft clips qs and qlen - qe around
-                                // the cg ops, swapped for '-'
-                                const uint32_t c0 = r.strand == '-' ? r.read_len - r.qs - r.len : r.qs, c1 = r.read_len - r.len - c0;
-                                const std::string seq = r.strand == '-' ? dg_paf_revcomp(r.read, r.read_len) : std::string(r.read, r.read_len);
-                                printf("%.*s\t%u\t%u\t%c\t%.*s\t%s\t%s%s%s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
-                                       (int)r.namel, r.name, seq.c_str(), c0 ? (std::to_string(c0) + "S").c_str() : "",
-                                       dg_cigar_text(b.ops.data() + b.opb[y - rb], b.opb[y - rb + 1] - b.opb[y - rb]).c_str(),
-                                       c1 ? (std::to_string(c1) + "S").c_str() : "");
-                                continue;
-                            }
-                            if (o.sam) {                       // RNAME, its length in --ref, POS, strand, QNAME, SEQ, CIGAR (from the ops)
-                                printf("%.*s\t%u\t%u\t%c\t%.*s\t%.*s\t%s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
-                                       (int)r.namel, r.name, (int)r.len, b.q.data() + o0,
-                                       dg_cigar_text(b.ops.data() + b.opb[y - rb], b.opb[y - rb + 1] - b.opb[y - rb]).c_str());
-                                continue;
-                            }
-                            printf("%.*s\t%u\t%u\t%c\t%.*s\t%.*s\t%.*s\n", (int)r.idl, r.id, b.tlen[g], r.start, r.strand,
-                                   (int)r.namel, r.name, (int)r.len, b.q.data() + o0, (int)r.tl, b.t.data() + b.off2[y - rb]);
-                        }
-                        b.clear();
-                    } else status = submit();
-                }
-                rb = x; bytes = 0; bytes2 = 0;
-                if (last || status) break;
-            }
-            const Rec &r = *recs[x];
-            if (new_target) {
-                if (o.sam && !seen_targets.emplace(r.id, r.idl).second) {
-                    fprintf(stderr, "pbdagcon: %s %llu: records of %.*s come back after another target's; the records of one RNAME "
-                            "must be consecutive (sort the %s by coordinate)\n", unit, r.line, (int)r.idl, r.id, o.bam ? "BAM" : "SAM");
-                    had_error = true;
-                    break;
-                }
-                if (x > rb) b.begin.push_back(b.start.size());
-                b.ids.emplace_back(r.id, r.idl);
-                b.tlen.push_back(r.tlen);
-                if (o.sam) { b.toff.push_back(bytes2); b.tsrc.push_back(r.t); bytes2 += r.tlen; }
-            }
-            if (o.sam) b.opb.push_back(b.opb.back() + r.nops);
-            b.start.push_back(r.start);
-            b.off.push_back(bytes); b.off2.push_back(bytes2);
-            b.len.push_back(r.len); b.len2.push_back(o.cs ? r.cgl : r.tl);
-            b.strand.push_back(r.strand);
-            if (o.cs) b.tspan.push_back(r.tspan);
-            bytes += o.cs ? r.cgl : o.bam ? ((size_t)r.len + 1) / 2 : r.len; bytes2 += r.tl;
-        }
-        // the unfinished target's records wait for the next slab
-        std::vector<Rec> next_carry;
-        for (size_t x = n_use; x < recs.size(); x++) next_carry.push_back(*recs[x]);
-        carry.swap(next_carry);
-        // the text in front of the first carried record is finished with: its page-table entries go now, while the
-        // GPU works, instead of all at once at the end (0.3 s for 26 GB of text)
-        if (map) {
-            const size_t dead = carry.empty() ? slab_pos : (size_t)(carry[0].name - data);
-            const size_t upto = dead & ~(size_t)((2u << 20) - 1);
-            if (upto > unmapped) {
-                // MADV_DONTNEED takes the address-space lock shared (munmap takes it exclusively and would stall the
-                // workers' page faults and the driver's pinning): the threads drop a share of the range each
-                const size_t n2m = (upto - unmapped) >> 21;
-                auto drop = [&](unsigned k) {
-                    const size_t a = unmapped + ((n2m * k / nthr) << 21), e = unmapped + ((n2m * (k + 1) / nthr) << 21);
-                    if (e > a) madvise((char *)map + a, e - a, MADV_DONTNEED);
-                };
-                std::vector<std::thread> th;
-                for (unsigned k = 1; k < nthr; k++) th.emplace_back(drop, k);
-                drop(0);
-                for (auto &x : th) x.join();
-                unmapped = upto;
-            }
-        }
-        if (eof && carry.empty()) break;
-        if (eof) slab_pos = size;
-    }
-    if (had_error) status = 1;
-    if (o.paf && o.verbose)
-        fprintf(stderr, "pbdagcon: %llu PAF lines skipped (tp:A:S)\n", n_skipped);
-    else if (o.bam && o.verbose)
-        fprintf(stderr, "pbdagcon: %llu BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)\n", n_skipped);
-    else if (o.sam && o.verbose)
-        fprintf(stderr, "pbdagcon: %llu SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')\n", n_skipped);
-    t_parse_end = now();
-#undef b
-    if (!o.dump) {
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            // every submitted batch printed (or a worker gave up)
-            cv.wait(lk, [&] { return print_seq == next_seq || worker_status; });
-            stop = true;
-            if (worker_status && !status) status = worker_status;
-        }
-        cv.notify_all();
-        for (auto &w : workers) w.join();          // (every worker destroys its context: the device memory goes back in order,
-                                                   // so that the next process's large hipMalloc does not wait for it)
+        const int ws = wk.drain();
+        if (ws && !status) status = ws;
         // Every record is printed and the GPU is released: what is left is host-side tidying -- page-locked blobs, the
         // mapping of the input, the HIP runtime's own exit handlers (0.1 - 0.3 s at 1,000 targets) -- which the kernel
         // does for a process that ends, at once.  PBDAGCON_TEARDOWN=1 keeps the orderly way.
-        if (!getenv("PBDAGCON_TEARDOWN") && !status) {
-            fflush(stdout);
-            if (timing)
-                fprintf(stderr, "pbdagcon timing: total %.3f = parse loop %.3f (index %.3f  fill %.3f  wait-for-buffer %.3f) + drain %.3f, no host teardown | "
-                        "worker 0: create %.3f; all workers: flush %.3f (upload %.3f  run %.3f  fetch %.3f)  print %.3f\n",
-                        now() - t_main, t_parse_end - t_main, t_index, t_fill, t_wait, now() - t_parse_end, t_create, t_flush,
-                        g_t_upload, g_t_run, g_t_fetch, t_print);
-            fflush(stderr);
-            _exit(0);
-        }
+        fast_exit = !getenv("PBDAGCON_TEARDOWN") && !status;
     }
-    t_joined = now();
-    for (auto &x : bufs) { x.q.release(); x.t.release(); }
-    if (map) munmap(map, size);
+    const double t_joined = wall();
+    if (!fast_exit) {
+        for (auto &x : wk.bufs) { x.q.release(); x.t.release(); }
+        if (in.map) munmap(in.map, in.size);
+    }
     fflush(stdout);
-    if (timing)
-        fprintf(stderr, "pbdagcon timing: total %.3f = parse loop %.3f (index %.3f  fill %.3f  wait-for-buffer %.3f) + drain %.3f + teardown %.3f | "
+    if (g_timing) {
+        char teardown[64] = ", no host teardown";
+        if (!fast_exit) snprintf(teardown, sizeof teardown, " + teardown %.3f", wall() - t_joined);
+        fprintf(stderr, "pbdagcon timing: total %.3f = parse loop %.3f (index %.3f  fill %.3f  wait-for-buffer %.3f) + drain %.3f%s | "
                 "worker 0: create %.3f; all workers: flush %.3f (upload %.3f  run %.3f  fetch %.3f)  print %.3f\n",
-                now() - t_main, t_parse_end - t_main, t_index, t_fill, t_wait, t_joined - t_parse_end, now() - t_joined, t_create, t_flush,
-                g_t_upload, g_t_run, g_t_fetch, t_print);
+                wall() - t_main, t_parse_end - t_main, t_index, t_fill, wk.t_wait, t_joined - t_parse_end, teardown, wk.t_create, wk.t_flush,
+                g_t_upload, g_t_run, g_t_fetch, wk.t_print);
+    }
+    if (fast_exit) { fflush(stderr); _exit(0); }
     return status;
 }

@@ -25,15 +25,30 @@ struct DgRefSeqs {
     }
 };
 
-// reads a FASTA file; false with a message in err
-inline bool dg_read_fasta(const std::string &path, DgRefSeqs &ref, std::string &err) {
+// a whole file; false with a message in err
+inline bool dg_slurp(const std::string &path, std::string &text, std::string &err) {
     FILE *f = fopen(path.c_str(), "rb");
     if (!f) { err = "error opening file: " + path; return false; }
-    std::string text;
     char buf[1 << 16];
     size_t n;
     while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
     fclose(f);
+    return true;
+}
+
+// the line of text that begins at pos: its length without the LF and a CR in front of it; pos moves behind the line
+inline size_t dg_line(const char *data, size_t size, size_t &pos) {
+    const char *line = data + pos;
+    const char *nl = (const char *)memchr(line, '\n', size - pos);
+    const size_t ll = nl ? (size_t)(nl - line) : size - pos;
+    pos += ll + (nl ? 1 : 0);
+    return ll && line[ll - 1] == '\r' ? ll - 1 : ll;
+}
+
+// reads a FASTA file; false with a message in err
+inline bool dg_read_fasta(const std::string &path, DgRefSeqs &ref, std::string &err) {
+    std::string text;
+    if (!dg_slurp(path, text, err)) return false;
     ref.bases.reserve(text.size());
     std::string name;
     uint64_t begin = 0;
@@ -48,10 +63,7 @@ inline bool dg_read_fasta(const std::string &path, DgRefSeqs &ref, std::string &
     size_t pos = 0;
     while (pos < text.size()) {
         const char *line = text.data() + pos;
-        const char *nl = (const char *)memchr(line, '\n', text.size() - pos);
-        size_t ll = nl ? (size_t)(nl - line) : text.size() - pos;
-        pos += ll + (nl ? 1 : 0);
-        if (ll && line[ll - 1] == '\r') ll--;
+        const size_t ll = dg_line(text.data(), text.size(), pos);
         if (ll == 0) continue;
         if (line[0] == '>') {
             if (!close_rec()) return false;
@@ -139,11 +151,8 @@ inline bool dg_sam_check_header(const char *data, size_t size, const DgRefSeqs &
     unsigned long long lineno = 0;
     while (pos < size && data[pos] == '@') {
         const char *line = data + pos;
-        const char *nl = (const char *)memchr(line, '\n', size - pos);
-        size_t ll = nl ? (size_t)(nl - line) : size - pos;
-        pos += ll + (nl ? 1 : 0);
+        const size_t ll = dg_line(data, size, pos);
         lineno++;
-        if (ll && line[ll - 1] == '\r') ll--;
         if (ll < 4 || memcmp(line, "@SQ\t", 4) != 0) continue;
         const char *sn = nullptr, *ln = nullptr;
         size_t snl = 0, lnl = 0;

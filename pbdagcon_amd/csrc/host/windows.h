@@ -4,11 +4,9 @@
 // a target of at most W bases is one window.  Windows go to the device in groups of about --batch-targets
 // (dagcon_consensus_cigar_windows on a DAGCON_FLAG_BASE_POS context, with DAGCON_FLAG_BASE_SUPPORT for --fastq); a group
 // gets only the records whose [s, e) meets it, which the host knows from the ops it has parsed.  Records of one RNAME
-// must be consecutive and ascending in POS, as in a coordinate-sorted SAM.  The records come from a source (DgSamSource:
-// SAM text; DgBamSource: bam.h's reader, whose reads stay in BAM's 4-bit encoding all the way to the device; DgPafSource in
-// paf.h: PAF lines grouped by target, whose reads stay as the reads file has them, with a strand flag per record that
-// the device applies; DgPafCsSource in paf.h: PAF lines with cs:Z: text and no reads at all, whose [s, e) is the line's own
-// [ts, te) and whose text goes to dagcon_consensus_cs as it is); grouping, batching and the stitch do not know which.
+// must be consecutive and ascending in POS, as in a coordinate-sorted SAM.  The records come from a source of DgAlnRecs
+// (DgSamSource, DgBamSource; DgPafSource and DgPafCsSource in paf.h; a cs record's [s, e) is the line's own [ts, te)) and go
+// to the device as intake.h says for the source's kind; grouping, batching and the stitch do not know which.
 //
 // The stitch (DgStitch; tests/window_twin.py: stitch is its numpy twin).  With g = pos + window begin the 1-based
 // target position of a consensus base (dagcon_fetch_positions): of a window's segment the bases from the first one
@@ -77,54 +75,31 @@ struct DgWinOpts {
     int device;
 };
 
-// One alignment record as the window driver takes it: the target by name, POS, the read bases (one a byte, or two a
-// byte when the source is packed) and the CIGAR as BAM-encoded ops, appended to `ops` by the source.
-struct DgAlnRec {
-    const char *rname; size_t rname_len;
-    uint32_t pos;
-    const char *q; uint32_t q_len;                         // q_len counts bases
-    uint32_t nops;                                         // the record's ops are the last nops of `ops`
-    bool reverse;                                          // stranded sources only: the ops are written against the reverse
-                                                           // complement of q (dagcon_upload_cigar_strand)
-    uint32_t cs_len, t_span;                               // cs sources only: q is cs text of cs_len bytes; the target bases claimed
-    unsigned long long where;                              // the line (SAM) or the record's ordinal (BAM): what an error names
-};
-
 // SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
 struct DgSamSource {
     static constexpr DgRecordKind kind = DG_REC_PLAIN;
-    static constexpr const char *unit = "line";
-    static constexpr const char *skipped_what = "SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')";
     const char *data; size_t size, p = 0;
+    const DgRefSeqs &ref;
     unsigned long long lineno = 0, skipped = 0;
-    DgSamSource(const char *d, size_t n, const DgRefSeqs &) : data(d), size(n) {}
+    DgSamSource(const char *d, size_t n, const DgRefSeqs &rf) : data(d), size(n), ref(rf) {}
     // 1: a record; 0: the end; -1: an error (printed)
-    int next(DgAlnRec &r, std::vector<uint32_t> &ops) {
+    int next(DgAlnRec &r) {
         while (p < size) {
             const char *line = data + p;
-            const char *nl = (const char *)memchr(line, '\n', size - p);
-            size_t ll = nl ? (size_t)(nl - line) : size - p;
-            p += ll + (nl ? 1 : 0);
+            const size_t ll = dg_line(data, size, p);
             lineno++;
-            if (ll && line[ll - 1] == '\r') ll--;
             DgSamLine sl;
-            uint64_t pos = 0;
-            switch (dg_sam_split(line, ll, sl, [](const char *f, size_t n) { uint64_t v = 0; for (size_t i = 0; i < n && f[i] >= '0' && f[i] <= '9'; i++) v = v * 10 + (uint64_t)(f[i] - '0'); return v; })) {
+            // the leading digits of a field; POS stops at 2^40 and is clamped to 32 bits
+            auto digits = [](const char *f, size_t n, bool stop) { uint64_t v = 0; for (size_t i = 0; i < n && f[i] >= '0' && f[i] <= '9' && !(stop && v >= (1ull << 40)); i++) v = v * 10 + (uint64_t)(f[i] - '0'); return v; };
+            switch (dg_sam_split(line, ll, sl, [&](const char *f, size_t n) { return digits(f, n, false); })) {
                 case DG_SAM_NO_RECORD: continue;
                 case DG_SAM_SKIPPED: skipped++; continue;
                 case DG_SAM_FEW_FIELDS: fprintf(stderr, "pbdagcon: line %llu: a SAM record has 11 fields, this one has fewer than 10 fields\n", lineno); return -1;
                 case DG_SAM_BAD_CIGAR: fprintf(stderr, "pbdagcon: line %llu: malformed CIGAR %.*s\n", lineno, (int)std::min<size_t>(sl.fl[5], 60), sl.f[5]); return -1;
                 case DG_SAM_RECORD: break;
             }
-            const char *const *f = sl.f; const size_t *fl = sl.fl;
-            const long k = sl.nops;
-            for (size_t i = 0; i < fl[3] && f[3][i] >= '0' && f[3][i] <= '9' && pos < (1ull << 40); i++) pos = pos * 10 + (uint64_t)(f[3][i] - '0');
-            r.rname = f[2]; r.rname_len = fl[2];
-            r.pos = pos > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pos;
-            r.q = f[9]; r.q_len = (uint32_t)fl[9]; r.nops = (uint32_t)k;
-            r.where = lineno;
-            ops.resize(ops.size() + (size_t)k);
-            dg_cigar_ops(f[5], fl[5], ops.data() + ops.size() - (size_t)k);
+            const uint64_t pos = digits(sl.f[3], sl.fl[3], true);
+            dg_sam_rec(sl, pos > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pos, lineno, ref, r);
             return 1;
         }
         return 0;
@@ -134,56 +109,50 @@ struct DgSamSource {
 // BAM records (bam.h); the header's references were checked against --ref when the file was opened
 struct DgBamSource {
     static constexpr DgRecordKind kind = DG_REC_PACKED;
-    static constexpr const char *unit = "record";
-    static constexpr const char *skipped_what = "BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)";
     DgBamReader &bam;
+    const DgRefSeqs &ref;
     unsigned long long skipped = 0;
-    DgBamSource(DgBamReader &b, const DgRefSeqs &) : bam(b) {}
-    int next(DgAlnRec &r, std::vector<uint32_t> &ops) {
+    DgBamSource(DgBamReader &b, const DgRefSeqs &rf) : bam(b), ref(rf) {}
+    int next(DgAlnRec &r) {
         DgBamRec br;
         std::string err;
         const int rc = bam.next(br, err);
         skipped = bam.n_skipped;
         if (rc < 0) fprintf(stderr, "pbdagcon: format error: %s\n", err.c_str());
-        if (rc <= 0) return rc;
-        const std::string &rn = bam.refs[(size_t)br.ref_id].name;
-        r.rname = rn.data(); r.rname_len = rn.size();
-        r.pos = br.pos;
-        r.q = (const char *)br.seq; r.q_len = br.l_seq; r.nops = br.n_ops;
-        r.where = br.ordinal;
-        ops.resize(ops.size() + br.n_ops);
-        memcpy(ops.data() + ops.size() - br.n_ops, br.ops, (size_t)br.n_ops * 4);
-        return 1;
+        if (rc > 0) dg_bam_rec(bam, br, ref, r);
+        return rc;
     }
 };
 
 // the whole run; the process's exit status
 template <class Source>
 inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref) {
-    struct Rec { uint32_t pos, s, e, q_len; const char *q; uint64_t op0; uint32_t nops; bool reverse; uint32_t cs_len, t_span; };
+    struct Rec { uint32_t pos, s, e, q_len; const char *q; size_t q_bytes; uint64_t op0; uint32_t nops; bool reverse; uint32_t t_span; };   // q, q_bytes: its bytes of the q blob
     struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; };
     std::vector<Tgt> tgts;
     std::vector<uint32_t> ops;
     std::unordered_map<std::string, int> seen;
     // ---- the records, grouped by target ----
+    const DgKindDesc &kd = dg_kind(Source::kind);
     DgAlnRec ar{};
-    for (int have; (have = src.next(ar, ops)) != 0;) {
+    for (int have; (have = src.next(ar)) != 0;) {
         if (have < 0) return 1;
+        ops.resize(ops.size() + ar.nops);
+        dg_rec_ops(Source::kind, ar, ops.data() + ops.size() - ar.nops);
         const std::string rname(ar.rname, ar.rname_len);
         if (tgts.empty() || tgts.back().name != rname) {
-            const DgRefSeqs::Span *sp = ref.find(ar.rname, ar.rname_len);
-            if (!sp) { fprintf(stderr, "pbdagcon: %s %llu: RNAME %s is not a sequence of --ref\n", Source::unit, ar.where, rname.c_str()); return 1; }
-            if (!seen.emplace(rname, 1).second) { fprintf(stderr, "pbdagcon: %s %llu: records of RNAME %s come back after another target's (records of one RNAME must be consecutive)\n", Source::unit, ar.where, rname.c_str()); return 1; }
+            if (!ar.target) { fprintf(stderr, "pbdagcon: %s %llu: RNAME %s is not a sequence of --ref\n", kd.unit, ar.where, rname.c_str()); return 1; }
+            if (!seen.emplace(rname, 1).second) { fprintf(stderr, "pbdagcon: %s %llu: records of RNAME %s come back after another target's (records of one RNAME must be consecutive)\n", kd.unit, ar.where, rname.c_str()); return 1; }
             tgts.emplace_back();
-            tgts.back().name = rname; tgts.back().sp = *sp;
+            tgts.back().name = rname; tgts.back().sp = *ar.target;
         }
         Tgt &t = tgts.back();
         Rec r;
         r.pos = ar.pos;
-        if (!t.recs.empty() && r.pos < t.recs.back().pos) { fprintf(stderr, "pbdagcon: %s %llu: POS %u of RNAME %s is below that of the record before it (--window needs records ascending in POS, as in a coordinate-sorted SAM)\n", Source::unit, ar.where, r.pos, rname.c_str()); return 1; }
-        r.q = ar.q; r.q_len = ar.q_len; r.op0 = ops.size() - ar.nops; r.nops = ar.nops;
+        if (!t.recs.empty() && r.pos < t.recs.back().pos) { fprintf(stderr, "pbdagcon: %s %llu: POS %u of RNAME %s is below that of the record before it (--window needs records ascending in POS, as in a coordinate-sorted SAM)\n", kd.unit, ar.where, r.pos, rname.c_str()); return 1; }
+        r.q = dg_blob(Source::kind, ar); r.q_len = ar.q_len; r.q_bytes = dg_blob_bytes(Source::kind, ar); r.op0 = ops.size() - ar.nops; r.nops = ar.nops;
         r.reverse = (Source::kind == DG_REC_STRANDED) && ar.reverse;
-        r.cs_len = (Source::kind == DG_REC_CS) ? ar.cs_len : 0u; r.t_span = (Source::kind == DG_REC_CS) ? ar.t_span : 0u;
+        r.t_span = ar.t_span;
         const long k = (long)ar.nops;
         // [s, e) by the rule of include/dagcon.h (a non-conforming record: clipped into the target, at least one base)
         uint64_t nt = 0;
@@ -198,7 +167,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         t.max_span = std::max(t.max_span, r.e > r.s ? r.e - r.s : 0u);
         t.recs.push_back(r);
     }
-    if (o.verbose && src.skipped) fprintf(stderr, "pbdagcon: %llu %s\n", src.skipped, Source::skipped_what);
+    if (o.verbose && src.skipped) fprintf(stderr, "pbdagcon: %llu %s\n", src.skipped, kd.skipped_what);
     // ---- the windows of every target, in target order ----
     struct Win { uint32_t tgt, idx, begin, end, c0, c1; };
     std::vector<Win> wins;
@@ -212,33 +181,16 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         }
     }
     dagcon_ctx *ctx = nullptr;
-    dagcon_opts dopt;
-    dagcon_default_opts(&dopt);
-    dopt.min_cov = o.min_cov; dopt.min_len = o.min_len; dopt.trim = o.trim;
-    dopt.min_weight = (int32_t)o.min_cov;
-    dopt.device = o.device;
-    dopt.flags = DAGCON_FLAG_BASE_POS | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u);
-    int rc = dagcon_create(&dopt, &ctx);
-    if (rc != DAGCON_OK) {
-        fprintf(stderr, "pbdagcon: no usable MI355X as device %d (dagcon_create = %d); there is no CPU fallback\n", o.device, rc);
-        return 1;
-    }
+    int rc = dg_create(o.min_cov, o.min_len, o.trim, o.device, DAGCON_FLAG_BASE_POS | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u), &ctx);
+    if (rc != DAGCON_OK) return 1;
     int status = 0;
     DgStitch st;
     std::string out;
     long long cur_tgt = -1;
     auto flush_target = [&]() {
         if (cur_tgt < 0) return true;
-        for (const DgStitchPiece &p : st.pieces) {
-            if (p.seq.size() < o.min_len) continue;
-            char head[64];
-            snprintf(head, sizeof head, "/%lld_%lld", p.t0, p.t1);
-            if (o.fastq) {
-                if (!dg_append_fastq(out, tgts[(size_t)cur_tgt].name + head, p.seq.data(), (uint32_t)p.seq.size(), p.weight.data(), p.depth.data())) return false;
-            } else {
-                out += '>'; out += tgts[(size_t)cur_tgt].name; out += head; out += '\n'; out += p.seq; out += '\n';
-            }
-        }
+        for (const DgStitchPiece &p : st.pieces)
+            if (p.seq.size() >= o.min_len && !dg_append_result(out, o.fastq, tgts[(size_t)cur_tgt].name, p.t0, p.t1, p.seq.data(), (uint32_t)p.seq.size(), p.weight.data(), p.depth.data())) return false;
         fwrite(out.data(), 1, out.size(), stdout);
         out.clear();
         st.reset();
@@ -266,8 +218,8 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             for (; it != t.recs.end() && it->s < hi; ++it) {
                 if (it->e <= lo) continue;
                 b_pos.push_back(it->pos); b_qoff.push_back(qblob.size()); b_qlen.push_back(it->q_len);
-                qblob.append(it->q, (Source::kind == DG_REC_CS) ? it->cs_len : (Source::kind == DG_REC_PACKED) ? ((size_t)it->q_len + 1) / 2 : it->q_len);
-                if ((Source::kind == DG_REC_CS)) { b_cslen.push_back(it->cs_len); b_tspan.push_back(it->t_span); }
+                qblob.append(it->q, it->q_bytes);
+                if ((Source::kind == DG_REC_CS)) { b_cslen.push_back((uint32_t)it->q_bytes); b_tspan.push_back(it->t_span); }
                 b_ops.insert(b_ops.end(), ops.begin() + (long)it->op0, ops.begin() + (long)(it->op0 + it->nops));
                 b_opb.push_back(b_ops.size());
                 if ((Source::kind == DG_REC_STRANDED)) b_rev.push_back(it->reverse ? 1 : 0);
@@ -302,8 +254,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             const size_t g = k - w0;
             if (r.target_status[g] != DAGCON_OK)
                 fprintf(stderr, "pbdagcon: warning: %s window [%u, %u) skipped (%s)\n", tgts[w.tgt].name.c_str(), w.begin, w.end,
-                        r.target_status[g] == DAGCON_ERR_NONCONFORMING ? dg_nonconforming_text(false)
-                        : r.target_status[g] == DAGCON_ERR_UNSUPPORTED ? "too large" : "internal error");
+                        dg_status_text(r.target_status[g], DG_CIGAR_UNFIT));
             if (o.verbose) fprintf(stderr, "pbdagcon: %s window %u [%u, %u): %llu segments\n", tgts[w.tgt].name.c_str(), w.idx, w.begin, w.end,
                                    (unsigned long long)(r.seg_begin[g + 1] - r.seg_begin[g]));
             for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {

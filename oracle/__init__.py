@@ -200,6 +200,30 @@ def banded_align(q: bytes, t: bytes):
     return qa.raw[:n], ta.raw[:n]
 
 
+STAGE_NONE, STAGE_FOLLOWING, STAGE_FIRST, STAGE_FULL = 0, 1, 2, 3
+
+
+def banded_align_stage(q: bytes, t: bytes):
+    """banded_align and the pass of its cascade that produced the answer: (qaln, taln, stage), stage one of STAGE_*
+    (the band that follows the alignment, the first static band, the full band, or none: no band connects the
+    corners).  OG_NO_ADAPTIVE is honoured as in banded_align."""
+    L = lib()
+    L.og_banded_align_stage.restype = C.c_size_t
+    L.og_banded_align_stage.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_char_p, C.c_char_p,
+                                        C.POINTER(C.c_int)]
+    qa, ta = C.create_string_buffer(len(q) + len(t) + 1), C.create_string_buffer(len(q) + len(t) + 1)
+    stage = C.c_int(-1)
+    n = L.og_banded_align_stage(q, len(q), t, len(t), qa, ta, C.byref(stage))
+    return qa.raw[:n], ta.raw[:n], stage.value
+
+
+def align_halfwidth_first(qlen: int, tlen: int) -> int:
+    L = lib()
+    L.og_align_halfwidth_first.restype = C.c_uint32
+    L.og_align_halfwidth_first.argtypes = [C.c_uint32, C.c_uint32]
+    return L.og_align_halfwidth_first(qlen, tlen)
+
+
 def align_halfwidth(qlen: int, tlen: int) -> int:
     L = lib()
     L.og_align_halfwidth.restype = C.c_uint32

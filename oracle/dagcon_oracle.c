@@ -379,12 +379,14 @@ static size_t og_adaptive_align(const char *q, uint32_t n, const char *t, uint32
     return *fallback ? 0 : len;
 }
 
-size_t og_banded_align(const char *q, uint32_t n, const char *t, uint32_t m, char *qaln, char *taln) {
+/* the cascade of og_banded_align; *stage: the pass whose answer stands (OG_STAGE_*) */
+static size_t og_banded_align_cascade(const char *q, uint32_t n, const char *t, uint32_t m, char *qaln, char *taln, int *stage) {
     if (n == 0 || m == 0) {
         size_t k = 0;
         for (uint32_t i = 0; i < n; i++) { qaln[k] = q[i]; taln[k] = '-'; k++; }
         for (uint32_t j = 0; j < m; j++) { qaln[k] = '-'; taln[k] = t[j]; k++; }
         qaln[k] = taln[k] = 0;
+        *stage = OG_STAGE_FIRST;                                /* (no band at all: all gaps) */
         return k;
     }
     const uint32_t w1 = og_align_halfwidth_first(n, m), w2 = og_align_halfwidth(n, m);
@@ -392,12 +394,23 @@ size_t og_banded_align(const char *q, uint32_t n, const char *t, uint32_t m, cha
     if (w1 > OG_AL_WA && !getenv("OG_NO_ADAPTIVE")) {          /* (a static band that narrow already: nothing to gain) */
         int fb = 0;
         const size_t la = og_adaptive_align(q, n, t, m, qaln, taln, &fb);
-        if (!fb) return la;
+        if (!fb) { *stage = OG_STAGE_FOLLOWING; return la; }
     }
     size_t len = og_banded_align_w(q, n, t, m, w1, qaln, taln, &touched);
+    *stage = OG_STAGE_FIRST;
     /* near an edge, or no path at all inside the narrow band: the full band decides */
-    if (w1 < w2 && (touched || len == 0)) len = og_banded_align_w(q, n, t, m, w2, qaln, taln, &touched);
+    if (w1 < w2 && (touched || len == 0)) { len = og_banded_align_w(q, n, t, m, w2, qaln, taln, &touched); *stage = OG_STAGE_FULL; }
+    if (len == 0) *stage = OG_STAGE_NONE;
     return len;
+}
+
+size_t og_banded_align(const char *q, uint32_t n, const char *t, uint32_t m, char *qaln, char *taln) {
+    int stage;
+    return og_banded_align_cascade(q, n, t, m, qaln, taln, &stage);
+}
+
+size_t og_banded_align_stage(const char *q, uint32_t n, const char *t, uint32_t m, char *qaln, char *taln, int *stage) {
+    return og_banded_align_cascade(q, n, t, m, qaln, taln, stage);
 }
 
 /* SimpleAligner.cpp:51-62 */

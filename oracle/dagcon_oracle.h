@@ -73,6 +73,14 @@ int og_parse_pre(const char *line, size_t len, og_parsed *out, uint32_t *end_out
 uint32_t og_align_halfwidth(uint32_t qlen, uint32_t tlen);
 uint32_t og_align_halfwidth_first(uint32_t qlen, uint32_t tlen);   /* the band tried first (see og_banded_align) */
 size_t og_banded_align(const char *q, uint32_t qlen, const char *t, uint32_t tlen, char *qaln, char *taln);
+/* og_banded_align, and which pass of its cascade produced the answer (OG_NO_ADAPTIVE honoured as there): the band that
+ * follows the alignment, the first static band (also: a pair with an empty side, which no band sees, and a pair whose
+ * first band is the full one already), the full band, or none: no band connects the corners (length 0). */
+#define OG_STAGE_NONE 0
+#define OG_STAGE_FOLLOWING 1
+#define OG_STAGE_FIRST 2
+#define OG_STAGE_FULL 3
+size_t og_banded_align_stage(const char *q, uint32_t qlen, const char *t, uint32_t tlen, char *qaln, char *taln, int *stage);
 /* SimpleAligner.cpp:51-62: what align() does to start / end / strings once the aligner has
  * produced (queryStr, targetStr, GenomicTBegin = 0, GenomicTEnd = tlen of the record's tstr).
  * qaln / taln are rewritten in place (reverse-complemented for the '-' strand). */

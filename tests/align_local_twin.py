@@ -150,22 +150,29 @@ def following_band(q, t):
     return None if touched else (qa, ta, ends)
 
 
-def align(q: bytes, t: bytes, static_only: bool = False):
+STAGE_NONE, STAGE_FOLLOWING, STAGE_FIRST, STAGE_FULL = 0, 1, 2, 3     # oracle.STAGE_*: the pass whose answer stands
+
+
+def align(q: bytes, t: bytes, static_only: bool = False, stage: bool = False):
     """The pass structure of dagcon_align in local mode -> (qaln, taln, (q_begin, q_end, t_begin, t_end)); a pair
-    without a local alignment -> (b"", b"", (0, 0, 0, 0)).  static_only: DAGCON_ALIGN_STATIC=1."""
+    without a local alignment -> (b"", b"", (0, 0, 0, 0)).  static_only: DAGCON_ALIGN_STATIC=1.  stage: a fourth
+    element says which pass produced the answer (STAGE_*: the following band, the first static band, the full band;
+    none when no pass finds a local alignment)."""
     n, m = len(q), len(t)
     none = (b"", b"", (0, 0, 0, 0))
     if n == 0 or m == 0:
-        return none
+        return none + (STAGE_NONE,) if stage else none
     w1, w2 = halfwidth_first(n, m), halfwidth(n, m)
     if w1 > WA and not static_only:
         r = following_band(q, t)
         if r is not None:
-            return r
-    r = static_band(q, t, w1)
+            return r + (STAGE_FOLLOWING,) if stage else r
+    r, st = static_band(q, t, w1), STAGE_FIRST
     if w1 < w2 and (r is None or r[3]):
-        r = static_band(q, t, w2)
-    return none if r is None else r[:3]
+        r, st = static_band(q, t, w2), STAGE_FULL
+    if r is None:
+        return none + (STAGE_NONE,) if stage else none
+    return r[:3] + (st,) if stage else r[:3]
 
 
 def full_matrix(q: bytes, t: bytes):

@@ -378,8 +378,8 @@ int dagcon_consensus_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, dag
  * (target_status DAGCON_ERR_NONCONFORMING), the other windows are complete.  The span of a non-conforming record is
  * s = max(pos, 1) - 1 and e = s + its target-base total (32 bits), then s <= tlen - 1 and s + 1 <= e <= tlen.
  * DAGCON_ERR_INVALID_ARG before any launch: end <= begin, end > tlen, a target index out of range, windows out of order.
- * A window longer than the tlen limit of dagcon_consensus or with more than DAGCON_MAX_COVERAGE pieces:
- * DAGCON_ERR_UNSUPPORTED for the call, as there.
+ * A window longer than the tlen limit of dagcon_consensus or with more than DAGCON_MAX_COVERAGE pieces (after the pick
+ * of dagcon_set_record_filter, when a filter is set): DAGCON_ERR_UNSUPPORTED for the call, as there.
  */
 typedef struct dagcon_windows {
     uint32_t n_windows;
@@ -477,6 +477,54 @@ typedef struct dagcon_cs_batch {
 int dagcon_upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *batch, const dagcon_windows *windows /* or NULL */);
 int dagcon_consensus_cs(dagcon_ctx *ctx, const dagcon_cs_batch *batch, const dagcon_windows *windows /* or NULL */,
                         dagcon_results *results);
+
+/*
+ * Picking the records (off by default).  The record calls above take every record the aligner wrote; with a filter set
+ * on the context they rate every record on the device and leave some out before anything is built.  This build's own
+ * rule, PARITY UNPINNED (the reference picks reads upstream, in m4topre.py and dazcon -m).  For a conforming record, over
+ * the columns of its expansion (the rule of dagcon_cigar_batch):
+ *   match     columns of an M, = or X op whose read byte and target byte are equal after clearing bit 0x20 of both.  The
+ *             read byte is the one the expansion writes: decoded from its nibble for packed input, complemented for a
+ *             reverse record, the decoded read for cs.  One rule for the three ops: an = or X op is not trusted, the
+ *             bases decide.  BAM's '=' base is the byte '=' and matches only '=';
+ *   mismatch  the other M / = / X columns;
+ *   ins, del  the bases of I ops, of D ops.  S, H and P count nowhere: match + mismatch + ins + del == the columns.
+ * err = mismatch + ins + del.  A record passes max_error_ppm iff err * 1000000 <= max_error_ppm * columns, in 64-bit
+ * integers; a record of 0 columns passes.  Then max_depth D (0: off), on a target's records that passed -- with windows,
+ * on each window's pieces of such records: if more than D remain, the D with the largest match stay, a tie going to the
+ * lower record index, and those that stay keep their own order (addAln order).  With windows the key is still the
+ * RECORD's match, not the piece's: a record that agrees well overall wins a window it crosses badly.  The cap is taken
+ * on every target and window, also on one that then fails or falls below min_cov.  min_cov counts what both steps
+ * leave.  The result is, byte for byte, that of the same call without a filter on the batch without the records left
+ * out (for a depth cap with windows: window by window): segments, target_status, dagcon_fetch_support,
+ * dagcon_fetch_positions, the counts in the timings.  A non-conforming record has no counts and fails its target, or
+ * the windows its span meets, exactly as without a filter.  A target or window that the filter brings to at most
+ * DAGCON_MAX_COVERAGE records is not refused.
+ * The filter holds for every later dagcon_upload_cigar* / dagcon_consensus_cigar* / _packed / _strand / dagcon_upload_cs /
+ * dagcon_consensus_cs call on the context, whole targets and windows; dagcon_consensus, dagcon_consensus_pre and
+ * dagcon_align ignore it.  NULL switches it off.  {1000000, 0} is legal: nothing is left out, the counts are there.
+ * DAGCON_ERR_INVALID_ARG: max_error_ppm > 1000000 or max_depth > DAGCON_MAX_COVERAGE (the filter stays as it was).
+ * Without a filter neither kernel of the rating runs.
+ */
+typedef struct dagcon_record_filter {
+    uint32_t max_error_ppm;      /* 1000000: keep all */
+    uint32_t max_depth;          /* 0: off */
+} dagcon_record_filter;
+int dagcon_set_record_filter(dagcon_ctx *ctx, const dagcon_record_filter *f);   /* NULL: off (the default) */
+
+/* What the last record upload under a filter found, record by record (n == rec_begin[n_targets]).  Valid after such an
+ * upload (or dagcon_consensus_cigar* / _cs) while the filter is set; DAGCON_ERR_STATE otherwise: no filter, no such
+ * upload since the filter was set, or another kind of upload since.  The arrays are owned by the context until the next
+ * upload. */
+#define DAGCON_FATE_MAX_ERROR 1u      /* over max_error_ppm */
+#define DAGCON_FATE_MAX_DEPTH 2u      /* left out of at least one target or window by max_depth */
+#define DAGCON_FATE_NONCONFORMING 4u  /* non-conforming: its four counts are 0 */
+typedef struct dagcon_record_stats {
+    uint64_t n;
+    const uint32_t *match, *mismatch, *ins, *del;   /* [n] */
+    const uint8_t *fate;                            /* [n] DAGCON_FATE_* bits */
+} dagcon_record_stats;
+int dagcon_fetch_record_stats(dagcon_ctx *ctx, dagcon_record_stats *out);
 
 /*
  * Debug / parity aid: adjacency of one target's graph as left by the last

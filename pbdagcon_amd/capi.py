@@ -40,6 +40,7 @@ EXPORTS = [
     "dagcon_upload_cigar_packed", "dagcon_consensus_cigar_packed",
     "dagcon_upload_cigar_strand", "dagcon_consensus_cigar_strand",
     "dagcon_upload_cs", "dagcon_consensus_cs",
+    "dagcon_set_record_filter", "dagcon_fetch_record_stats",
 ]
 ABI_VERSION = 2
 
@@ -99,6 +100,19 @@ class Results(C.Structure):
 
 class Support(C.Structure):
     _fields_ = [("n", C.c_uint64), ("weight", C.POINTER(C.c_uint16)), ("depth", C.POINTER(C.c_uint16))]
+
+
+class RecordFilter(C.Structure):
+    """dagcon_record_filter: max_error_ppm 1000000 keeps every record, max_depth 0 is off."""
+    _fields_ = [("max_error_ppm", C.c_uint32), ("max_depth", C.c_uint32)]
+
+
+class RecordStats(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("match", C.POINTER(C.c_uint32)), ("mismatch", C.POINTER(C.c_uint32)),
+                ("ins", C.POINTER(C.c_uint32)), ("del_", C.POINTER(C.c_uint32)), ("fate", C.POINTER(C.c_uint8))]
+
+
+FATE_MAX_ERROR, FATE_MAX_DEPTH, FATE_NONCONFORMING = 1, 2, 4
 
 
 class Timings(C.Structure):
@@ -168,6 +182,8 @@ def load() -> C.CDLL:
     L.dagcon_upload_cs.argtypes = [vp, C.POINTER(CsBatch), C.POINTER(Windows)]
     L.dagcon_consensus_cs.argtypes = [vp, C.POINTER(CsBatch), C.POINTER(Windows), C.POINTER(Results)]
     L.dagcon_consensus_cigar_strand.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), vp, C.POINTER(Results)]
+    L.dagcon_set_record_filter.argtypes = [vp, C.POINTER(RecordFilter)]
+    L.dagcon_fetch_record_stats.argtypes = [vp, C.POINTER(RecordStats)]
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
     L.dagcon_host_free.restype = None
@@ -666,6 +682,28 @@ class Context:
     def consensus_cs(self, batch: HostCsBatch, windows: HostWindows = None, strict=True):
         """Per target (per window with windows): [(range0, range1, seq_bytes)], from cs:Z: text decoded on the device."""
         return self._intake(batch, windows, (batch, windows), True, strict)
+
+    def set_record_filter(self, max_error_ppm=1000000, max_depth=0):
+        """dagcon_set_record_filter for every later record call (CIGAR, packed, stranded, cs; whole targets and windows):
+        records above max_error_ppm are left out, then at most max_depth per target or window stay (include/dagcon.h
+        has the rule).  The defaults leave nothing out and only make record_stats available; None for both: off."""
+        if max_error_ppm is None and max_depth is None:
+            self._chk(self.L.dagcon_set_record_filter(self.h, None))
+            return
+        f = RecordFilter(max_error_ppm, max_depth)
+        self._chk(self.L.dagcon_set_record_filter(self.h, C.byref(f)))
+
+    def record_stats(self) -> dict:
+        """dagcon_fetch_record_stats: match, mismatch, ins, del (uint32) and fate (uint8, FATE_* bits), one entry per
+        record of the last record upload under a filter (copies)."""
+        st = RecordStats()
+        self._chk(self.L.dagcon_fetch_record_stats(self.h, C.byref(st)))
+        n = int(st.n)
+
+        def arr(ptr, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return {"match": arr(st.match, np.uint32), "mismatch": arr(st.mismatch, np.uint32), "ins": arr(st.ins, np.uint32),
+                "del": arr(st.del_, np.uint32), "fate": arr(st.fate, np.uint8)}
 
     def timings(self) -> dict:
         t = Timings()

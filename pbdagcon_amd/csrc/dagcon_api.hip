@@ -26,6 +26,7 @@
 #include "k_align_panels.hip.h"
 #include "k_place.hip.h"
 #include "k_cigar.hip.h"
+#include "k_rate.hip.h"
 #include "k_cs.hip.h"
 
 namespace {
@@ -42,11 +43,13 @@ struct CigarBufs {
     DevBuf out_off;                                                // whole targets: where each record's strings go
     DevBuf piece, cut, wave_piece, wave_begin, piece_out;          // windows: DgCigarCutParams
     DevBuf rev, q_len;                                             // DgCigarStrand
-    std::array<DevBuf *, 17> all() {
-        return {&ops, &op_begin, &tile_begin, &totals, &ckpt, &q, &t, &q_off, &t_base, &out_off, &piece, &cut, &wave_piece, &wave_begin, &piece_out, &rev, &q_len};
+    DevBuf rate_base, tile_rate, rate;                             // DgCigarRate (a record filter is set)
+    std::array<DevBuf *, 20> all() {
+        return {&ops, &op_begin, &tile_begin, &totals, &ckpt, &q, &t, &q_off, &t_base, &out_off, &piece, &cut, &wave_piece, &wave_begin, &piece_out, &rev, &q_len,
+                &rate_base, &tile_rate, &rate};
     }
 };
-static_assert(sizeof(CigarBufs) == 17 * sizeof(DevBuf), "CigarBufs::all() must name every member");
+static_assert(sizeof(CigarBufs) == 20 * sizeof(DevBuf), "CigarBufs::all() must name every member");
 // dagcon_upload_cs: the text and what k_cs_scan / k_cs_write take besides CigarBufs::ops, q and t, which k_cs_write fills
 struct CsBufs {
     DevBuf text, cs_off, cs_len, totals, n_ops, op_begin, t_base, t_room, q_off, q_len;
@@ -156,6 +159,11 @@ struct Ctx {
     CigarBufs cg;                                   // dagcon_upload_cigar and its kin
     std::vector<uint8_t> h_cig_bad;                 // dagcon_upload_cigar: targets with a non-conforming record (empty: another upload)
     std::string cig_err;                            // the first of them, for dagcon_last_error
+    bool filter_on = false;                         // dagcon_set_record_filter: the record intake rates and picks its records
+    dagcon_record_filter filter = {1000000u, 0u};
+    bool rs_valid = false;                          // the record stats below are those of the last upload (dagcon_fetch_record_stats)
+    std::vector<uint32_t> rs_match, rs_mismatch, rs_ins, rs_del;
+    std::vector<uint8_t> rs_fate;
     DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
     DevBuf d_pos_tmp, d_pos_tmp0, d_pos;           // DAGCON_FLAG_BASE_POS: walk scratch (4 B per vertex), output (4 B per base)
     DevBuf d_sup_tmp, d_sup_tmp0, d_sup;           // DAGCON_FLAG_BASE_SUPPORT: walk scratch (4 B per vertex), output (2 x 2 B per base)
@@ -581,6 +589,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->uploaded = c->ran = c->fetched = false;
     c->sup_valid = c->pos_valid = false;
     c->h_cig_bad.clear();
+    c->rs_valid = false;
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->aln_begin)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/aln_begin is NULL");
     const uint64_t A_all = T ? b->aln_begin[T] : 0;
@@ -1666,9 +1675,9 @@ int dagcon_consensus_pre(dagcon_ctx *ctx, const dagcon_pre_batch *b, dagcon_resu
 }  // extern "C"
 namespace {
 // ---- record intake: dagcon_upload_cigar, _windows, _packed, _strand and dagcon_upload_cs ------------------------------
-// One path, upload_records: reset, scan, judge, plan, expand, hand-over.  Whole targets and windows differ in the plan
-// alone (plan_whole / plan_windows); the input kinds differ in what cigar_scan uploads and in the kernel cigar_expand
-// picks, both read off a RecordSource.
+// One path, upload_records: reset, scan, judge, rate, pick, plan, expand, hand-over.  Whole targets and windows differ in
+// the plan alone (plan_whole / plan_windows); the input kinds differ in what cigar_scan uploads and in the kernels
+// cigar_rate and cigar_expand pick, both read off a RecordSource.  rate runs only when a record filter is set.
 
 // what dagcon_upload_cs leaves for the path: every record judged and sized from its text
 struct CsDecoded {
@@ -1731,6 +1740,7 @@ struct CigarScan {
     DgCigarParams p;
     std::vector<uint64_t> tile_begin;                              // [n + 1]
     std::vector<uint32_t> tot;                                     // per record: columns, read bases, target bases, DG_CG_* flags
+    DgCigarStrand st = {nullptr, nullptr};                         // cigar_strand: the strand kernels' own arguments
 };
 int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, const RecordSource &src, CigarScan &sc) {
     const CsDecoded *cs = src.cs();
@@ -1816,6 +1826,96 @@ CigarVerdict cigar_judge(const dagcon_cigar_batch *b, const RecordSource &src, c
     return v;
 }
 
+// the strand kernels' own arguments, one flag and q_len per record: uploaded once, by whichever stage asks first
+int cigar_strand(Ctx *c, const dagcon_cigar_batch *b, const RecordSource &src, CigarScan &sc) {
+    if (src.kind() != RecordSource::STRANDED || sc.st.rev) return DAGCON_OK;
+    ENSURE(c, c->cg.rev, (size_t)sc.n); ENSURE(c, c->cg.q_len, (size_t)sc.n * 4);
+    if (sc.n) {
+        HIPCHK(c, hipMemcpyAsync(c->cg.rev.p, src.reverse(), (size_t)sc.n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->cg.q_len.p, b->q_len, (size_t)sc.n * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    sc.st.rev = (const uint8_t *)c->cg.rev.p; sc.st.q_len = (const uint32_t *)c->cg.q_len.p;
+    return DAGCON_OK;
+}
+
+// rate and pick (dagcon_set_record_filter; include/dagcon.h has the rule): which records the plan is to see.  Without a
+// filter every record is kept and nothing is launched.
+struct CigarPick {
+    std::vector<uint8_t> keep;                                     // [n] 0: over max_error (a non-conforming record stays: it fails its target as ever)
+    uint32_t max_depth = 0;                                        // 0: off
+    std::vector<uint32_t> rate;                                    // [n] x4 match, mismatch, ins, del (a filter is set)
+    std::vector<uint8_t> fate;                                     // [n] DAGCON_FATE_* (a filter is set)
+};
+
+// rate: k_cigar_rate over the tiles of the conforming records, k_cigar_rate_sum over the records, the counts back on the
+// host and checked against the scan's column totals before anything is decided from them
+int cigar_rate(Ctx *c, const dagcon_cigar_batch *b, const RecordSource &src, CigarScan &sc, const CigarVerdict &v, CigarPick &pk) {
+    const uint32_t n = sc.n;
+    pk.rate.assign((size_t)n * 4, 0);
+    if (!n) return DAGCON_OK;
+    std::vector<uint64_t> base((size_t)n, DG_CG_SKIP);
+    for (uint32_t g = 0; g < b->n_targets; g++)
+        for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++)
+            if (!v.why[a]) base[a] = b->t_off[g] + b->pos[a] - 1u;
+    CigarBufs &d = c->cg;
+    int r;
+    if ((r = upload_vec(c, d.rate_base, base))) return r;
+    if ((r = cigar_strand(c, b, src, sc))) return r;
+    ENSURE(c, d.tile_rate, (size_t)sc.p.n_tiles * 16); ENSURE(c, d.rate, (size_t)n * 16);
+    DgCigarRate rt;
+    rt.base = (const uint64_t *)d.rate_base.p; rt.tile_rate = (uint4 *)d.tile_rate.p; rt.rate = (uint4 *)d.rate.p;
+    hipStream_t s = c->stream;
+    if (sc.p.n_tiles) {
+        const dim3 grid(sc.p.n_tiles), block(64);
+        switch (src.kind()) {
+        case RecordSource::STRANDED: hipLaunchKernelGGL(k_cigar_rate_strand, grid, block, 0, s, sc.p, rt, sc.st); break;
+        case RecordSource::PACKED: hipLaunchKernelGGL(k_cigar_rate_packed, grid, block, 0, s, sc.p, rt); break;
+        case RecordSource::PLAIN:
+        case RecordSource::DECODED: hipLaunchKernelGGL(k_cigar_rate, grid, block, 0, s, sc.p, rt); break;
+        }
+        HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_cigar_rate_sum, dim3((n + 3u) / 4u), dim3(256), 0, s, sc.p, rt);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, d2h(c, pk.rate.data(), d.rate.p, (size_t)n * 16));
+    for (uint32_t a = 0; a < n; a++) {
+        const uint32_t *k = &pk.rate[(size_t)a * 4];
+        const uint64_t sum = (uint64_t)k[0] + k[1] + k[2] + k[3];
+        if (sum != (v.why[a] ? 0u : sc.tot[(size_t)a * 4]))
+            return fail(c, DAGCON_ERR_INTERNAL, "k_cigar_rate: record %u has %u + %u + %u + %u of %u columns", a, k[0], k[1], k[2], k[3], sc.tot[(size_t)a * 4]);
+    }
+    return DAGCON_OK;
+}
+
+// pick, first step: the error threshold, record by record
+void cigar_pick(const dagcon_record_filter &f, const CigarVerdict &v, CigarPick &pk) {
+    const size_t n = v.why.size();
+    pk.fate.assign(n, 0);
+    pk.max_depth = f.max_depth;
+    for (size_t a = 0; a < n; a++) {
+        if (v.why[a]) { pk.fate[a] = DAGCON_FATE_NONCONFORMING; continue; }
+        const uint32_t *k = &pk.rate[a * 4];
+        const uint64_t err = (uint64_t)k[1] + k[2] + k[3], col = err + k[0];
+        if (err * 1000000ull > (uint64_t)f.max_error_ppm * col) { pk.fate[a] = DAGCON_FATE_MAX_ERROR; pk.keep[a] = 0; }
+    }
+}
+
+// pick, second step: the depth cap on one target's or one window's records, recs in their own order.  More than
+// max_depth: the max_depth with the largest match stay (a tie goes to the lower record index), in their own order;
+// take[i] says whether recs[i] does.  Empty: all stay
+std::vector<uint8_t> cap_depth(CigarPick &pk, const std::vector<uint32_t> &recs) {
+    std::vector<uint8_t> take;
+    if (!pk.max_depth || recs.size() <= pk.max_depth) return take;
+    std::vector<uint32_t> by_match(recs.size());
+    for (uint32_t i = 0; i < by_match.size(); i++) by_match[i] = i;
+    std::stable_sort(by_match.begin(), by_match.end(), [&](uint32_t x, uint32_t y) { return pk.rate[(size_t)recs[x] * 4] > pk.rate[(size_t)recs[y] * 4]; });
+    take.assign(recs.size(), 0);
+    for (uint32_t i = 0; i < pk.max_depth; i++) take[by_match[i]] = 1;
+    for (size_t i = 0; i < recs.size(); i++)
+        if (!take[i]) pk.fate[recs[i]] |= DAGCON_FATE_MAX_DEPTH;
+    return take;
+}
+
 // plan: what upload_impl is to see (a dagcon_batch of strings, planned as dagcon_consensus_pre plans them), where the
 // expansion writes them (set in sc.p, and cw for pieces), and how many waves it takes (0: nothing to expand)
 struct CigarPlan {
@@ -1830,8 +1930,9 @@ struct CigarPlan {
 };
 
 // whole targets: one record, one string; the targets with a non-conforming record lose all their records (a target below
-// min_cov is skipped whatever it holds: it goes in without records, and nothing of it is expanded)
-int plan_whole(Ctx *c, const dagcon_cigar_batch *b, CigarScan &sc, const CigarVerdict &v, CigarPlan &pl) {
+// min_cov is skipped whatever it holds: it goes in without records, and nothing of it is expanded).  min_cov counts the
+// records the pick left
+int plan_whole(Ctx *c, const dagcon_cigar_batch *b, CigarScan &sc, const CigarVerdict &v, CigarPick &pk, CigarPlan &pl) {
     const uint32_t T = b->n_targets, n = sc.n;
     pl.bad.assign(T, 0);
     for (uint32_t g = 0; g < T; g++)
@@ -1839,11 +1940,22 @@ int plan_whole(Ctx *c, const dagcon_cigar_batch *b, CigarScan &sc, const CigarVe
             if (v.why[a]) pl.bad[g] = 1;
     std::vector<uint64_t> out_off((size_t)n, DG_CG_SKIP), t_base((size_t)n, 0);
     pl.beg.assign((size_t)T + 1, 0);
+    std::vector<uint32_t> recs;
     for (uint32_t g = 0; g < T; g++) {
         pl.beg[g] = pl.start.size();
-        const uint64_t k = b->rec_begin[g + 1] - b->rec_begin[g];
+        recs.clear();
+        for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++)
+            if (pk.keep[a] && !v.why[a]) recs.push_back((uint32_t)a);
+        const std::vector<uint8_t> take = cap_depth(pk, recs);
+        if (!take.empty()) {
+            size_t to = 0;
+            for (size_t i = 0; i < recs.size(); i++)
+                if (take[i]) recs[to++] = recs[i];
+            recs.resize(to);
+        }
+        const uint64_t k = recs.size();
         if (pl.bad[g] || k == 0 || k < c->opts.min_cov) continue;
-        for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
+        for (const uint32_t a : recs) {
             out_off[a] = pl.bytes; t_base[a] = b->t_off[g] + b->pos[a] - 1u;
             pl.start.push_back(b->pos[a]); pl.off.push_back(pl.bytes); pl.len.push_back(sc.tot[a * 4]);
             pl.bytes += ((uint64_t)sc.tot[a * 4] + 15ull) & ~15ull;
@@ -1877,7 +1989,7 @@ int check_windows(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn)
 // the scan's totals the host knows every record's [s, e) and lists the (record, window) pieces; k_cigar_cut turns each
 // piece's two target coordinates into columns and tiles, the host plans the output from those, and k_cigar_expand_cut
 // writes every piece from the one device copy of the record's ops and bases.
-int plan_windows(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn, CigarScan &sc, const CigarVerdict &v, CigarPlan &pl) {
+int plan_windows(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn, CigarScan &sc, const CigarVerdict &v, CigarPick &pk, CigarPlan &pl) {
     const uint32_t T = b->n_targets, W = wn->n_windows, n = sc.n;
     const std::vector<uint32_t> &tot = sc.tot;
     CigarBufs &d = c->cg;
@@ -1898,8 +2010,9 @@ int plan_windows(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn, 
             t_base[a] = b->t_off[g] + s0;
         }
     // the pieces, window by window, records in their own order (addAln order); a window with a non-conforming piece, or
-    // with fewer pieces than min_cov, keeps none
+    // with fewer pieces than min_cov after the pick, keeps none
     pl.bad.assign(W, 0);
+    std::vector<uint32_t> recs;
     pl.beg.assign((size_t)W + 1, 0);
     std::vector<uint32_t> piece;                                   // x4: record, a_rel, b_rel, window
     for (uint32_t w = 0; w < W; w++) {
@@ -1909,9 +2022,20 @@ int plan_windows(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn, 
             const uint32_t A = std::max(wa, rs[a]), B = std::min(wb, re[a]);
             if (A >= B) continue;
             if (v.why[a]) { pl.bad[w] = 1; continue; }
+            if (!pk.keep[a]) continue;
             piece.push_back((uint32_t)a); piece.push_back(A - rs[a]); piece.push_back(B - rs[a]); piece.push_back(w);
         }
-        const size_t k = (piece.size() - first) / 4;
+        size_t k = (piece.size() - first) / 4;
+        recs.resize(k);
+        for (size_t i = 0; i < k; i++) recs[i] = piece[first + i * 4];
+        const std::vector<uint8_t> take = cap_depth(pk, recs);
+        if (!take.empty()) {                                       // the pieces that stay, moved up in their own order
+            size_t to = first;
+            for (size_t i = 0; i < k; i++)
+                if (take[i]) { std::copy_n(&piece[first + i * 4], 4, &piece[to]); to += 4; }
+            piece.resize(to);
+            k = (to - first) / 4;
+        }
         if (pl.bad[w] || k < c->opts.min_cov) piece.resize(first);
     }
     const uint64_t np64 = piece.size() / 4;
@@ -1976,16 +2100,10 @@ int cigar_expand(Ctx *c, const dagcon_cigar_batch *b, const RecordSource &src, C
     hipStream_t s = c->stream;
     switch (src.kind()) {
     case RecordSource::STRANDED: {
-        // the strand kernels' own arguments: one flag and q_len per record
-        DgCigarStrand st;
-        ENSURE(c, c->cg.rev, (size_t)sc.n); ENSURE(c, c->cg.q_len, (size_t)sc.n * 4);
-        if (sc.n) {
-            HIPCHK(c, hipMemcpyAsync(c->cg.rev.p, src.reverse(), (size_t)sc.n, hipMemcpyHostToDevice, s));
-            HIPCHK(c, hipMemcpyAsync(c->cg.q_len.p, b->q_len, (size_t)sc.n * 4, hipMemcpyHostToDevice, s));
-        }
-        st.rev = (const uint8_t *)c->cg.rev.p; st.q_len = (const uint32_t *)c->cg.q_len.p;
-        if (pl.pieces) hipLaunchKernelGGL(k_cigar_expand_cut_strand, grid, block, 0, s, p, pl.cw, st);
-        else hipLaunchKernelGGL(k_cigar_expand_strand, grid, block, 0, s, p, st);
+        const int r = cigar_strand(c, b, src, sc);
+        if (r != DAGCON_OK) return r;
+        if (pl.pieces) hipLaunchKernelGGL(k_cigar_expand_cut_strand, grid, block, 0, s, p, pl.cw, sc.st);
+        else hipLaunchKernelGGL(k_cigar_expand_strand, grid, block, 0, s, p, sc.st);
         break;
     }
     case RecordSource::PACKED:
@@ -2004,7 +2122,7 @@ int cigar_expand(Ctx *c, const dagcon_cigar_batch *b, const RecordSource &src, C
 
 // hand-over: the planned strings go in by the door dagcon_consensus_pre uses; the context remembers which of the
 // pipeline's targets fail for a record, and why
-int cigar_hand_over(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const CigarPlan &pl, const CigarVerdict &v) {
+int cigar_hand_over(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const CigarPlan &pl, const CigarVerdict &v, const CigarPick &pk) {
     dagcon_batch db;
     memset(&db, 0, sizeof db);
     db.n_targets = (uint32_t)pl.bad.size(); db.tlen = pl.pieces ? pl.tlen.data() : b->tlen; db.aln_begin = pl.beg.data();
@@ -2014,6 +2132,16 @@ int cigar_hand_over(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const 
     if (r != DAGCON_OK) { (void)hipStreamSynchronize(c->stream); return r; }
     c->h_cig_bad = pl.bad;
     c->cig_err = v.first_err;
+    if (c->filter_on) {                                            // dagcon_fetch_record_stats: one array per count
+        const size_t n = pk.fate.size();
+        c->rs_match.resize(n); c->rs_mismatch.resize(n); c->rs_ins.resize(n); c->rs_del.resize(n);
+        for (size_t a = 0; a < n; a++) {
+            c->rs_match[a] = pk.rate[a * 4]; c->rs_mismatch[a] = pk.rate[a * 4 + 1];
+            c->rs_ins[a] = pk.rate[a * 4 + 2]; c->rs_del[a] = pk.rate[a * 4 + 3];
+        }
+        c->rs_fate = pk.fate;
+        c->rs_valid = true;
+    }
     return DAGCON_OK;
 }
 
@@ -2028,10 +2156,16 @@ int upload_records(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_wi
     CigarScan sc;
     if ((r = cigar_scan(c, b, src, sc))) return r;
     const CigarVerdict v = cigar_judge(b, src, sc);
+    CigarPick pk;
+    pk.keep.assign((size_t)sc.n, 1);
+    if (c->filter_on) {
+        if ((r = cigar_rate(c, b, src, sc, v, pk))) return r;
+        cigar_pick(c->filter, v, pk);
+    }
     CigarPlan pl;
-    if ((r = wn ? plan_windows(c, b, wn, sc, v, pl) : plan_whole(c, b, sc, v, pl))) return r;
+    if ((r = wn ? plan_windows(c, b, wn, sc, v, pk, pl) : plan_whole(c, b, sc, v, pk, pl))) return r;
     if ((r = cigar_expand(c, b, src, sc, pl))) return r;
-    return cigar_hand_over(ctx, c, b, pl, v);
+    return cigar_hand_over(ctx, c, b, pl, v, pk);
 }
 
 // minimap2's cs:Z: text per record, the target's bases once per target (include/dagcon.h has the rule).  k_cs_scan sizes
@@ -2135,6 +2269,25 @@ int upload_run_fetch(dagcon_ctx *ctx, dagcon_results *results, Upload upload) {
 }  // namespace
 extern "C" {
 
+int dagcon_set_record_filter(dagcon_ctx *ctx, const dagcon_record_filter *f) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (f && f->max_error_ppm > 1000000u) return fail(c, DAGCON_ERR_INVALID_ARG, "max_error_ppm %u is above 1000000", f->max_error_ppm);
+    if (f && f->max_depth > DAGCON_MAX_COVERAGE) return fail(c, DAGCON_ERR_INVALID_ARG, "max_depth %u is above %u", f->max_depth, DAGCON_MAX_COVERAGE);
+    c->filter_on = f != nullptr;
+    if (f) c->filter = *f;
+    c->rs_valid = false;                                           // (the stats belong to an upload under the filter that is set)
+    return DAGCON_OK;
+}
+int dagcon_fetch_record_stats(dagcon_ctx *ctx, dagcon_record_stats *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->filter_on || !c->rs_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_record_stats: no record upload under a record filter");
+    out->n = c->rs_fate.size();
+    out->match = c->rs_match.data(); out->mismatch = c->rs_mismatch.data(); out->ins = c->rs_ins.data(); out->del = c->rs_del.data();
+    out->fate = c->rs_fate.data();
+    return DAGCON_OK;
+}
 int dagcon_upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *wn) { return upload_cs(ctx, b, wn); }
 int dagcon_upload_cigar(dagcon_ctx *ctx, const dagcon_cigar_batch *b) { return upload_records(ctx, b, nullptr, RecordSource::plain()); }
 int dagcon_upload_cigar_windows(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn) {

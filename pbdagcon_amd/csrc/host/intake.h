@@ -1,10 +1,12 @@
 // intake.h -- where the command-line hosts hand alignment records to the library: the one record every format becomes (DgAlnRec),
 // one description per kind of input (dg_kind: what the messages say; dg_blob_bytes, dg_blob, dg_rec_ops: what of a record goes to the
-// device), a batch's arrays, the call that picks the entry point, the warning texts, and the one place a context is made.
+// device), a batch's arrays, the call that picks the entry point, the warning texts, and the one place a context is made and
+// given --max-error / --max-depth (DgPick).
 #pragma once
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <string>
 
 #include "../../../include/dagcon.h"
 #include "sam.h"
@@ -103,14 +105,60 @@ inline const char *dg_status_text(int status, const char *nonconforming) {
     return status == DAGCON_ERR_NONCONFORMING ? nonconforming : status == DAGCON_ERR_UNSUPPORTED ? "too large" : "internal error";
 }
 
-// a context for the command line's options; a failure is reported here (there is no CPU fallback)
-inline int dg_create(unsigned min_cov, unsigned min_len, unsigned trim, int device, uint32_t flags, dagcon_ctx **ctx) {
+// --max-error F / --max-depth N: the records are picked on the device (dagcon_set_record_filter; include/dagcon.h has the rule)
+struct DgPick {
+    uint32_t max_error_ppm = 1000000u, max_depth = 0;
+    bool error_set = false, depth_set = false;
+    bool on() const { return error_set || depth_set; }
+    // the flags as a timing line names them
+    std::string text() const {
+        char buf[96] = "";
+        int k = 0;
+        if (error_set) k += snprintf(buf + k, sizeof buf - k, " --max-error %u.%06u", max_error_ppm / 1000000u, max_error_ppm % 1000000u);
+        if (depth_set) snprintf(buf + k, sizeof buf - k, " --max-depth %u", max_depth);
+        return buf;
+    }
+};
+// --max-error's text as parts per million, without floating point: 0 or 1, then optionally a point and one to six digits;
+// at most 1.  "0.15" is exactly 150000
+inline bool dg_parse_ppm(const char *s, uint32_t *ppm) {
+    if (s[0] != '0' && s[0] != '1') return false;
+    uint32_t v = (uint32_t)(s[0] - '0') * 1000000u;
+    const char *p = s + 1;
+    if (*p == '.') {
+        uint32_t scale = 100000u, digits = 0;
+        for (p++; *p >= '0' && *p <= '9' && digits < 6; p++, digits++, scale /= 10u) v += (uint32_t)(*p - '0') * scale;
+        if (!digits) return false;
+    }
+    if (*p || v > 1000000u) return false;
+    *ppm = v;
+    return true;
+}
+// what the pick did to the records of the last call on ctx, one DAGCON_FATE_* byte per record; NULL: no filter is set
+inline const uint8_t *dg_record_fates(dagcon_ctx *ctx, uint64_t *n) {
+    dagcon_record_stats st;
+    if (dagcon_fetch_record_stats(ctx, &st) != DAGCON_OK) return nullptr;
+    *n = st.n;
+    return st.fate;
+}
+inline void dg_report_pick(const DgPick &pick, unsigned long long over_error, unsigned long long over_depth) {
+    if (pick.on()) fprintf(stderr, "pbdagcon: records left out: %llu by --max-error, %llu by --max-depth\n", over_error, over_depth);
+}
+
+// a context for the command line's options, with the record filter --max-error / --max-depth ask for (pick NULL: none);
+// a failure is reported here (there is no CPU fallback)
+inline int dg_create(unsigned min_cov, unsigned min_len, unsigned trim, int device, uint32_t flags, const DgPick *pick, dagcon_ctx **ctx) {
     dagcon_opts dopt;
     dagcon_default_opts(&dopt);
     dopt.min_cov = min_cov; dopt.min_len = min_len; dopt.trim = trim;
     dopt.min_weight = (int32_t)min_cov;                    // main.cpp:261,279 (quirk Q1)
     dopt.device = device; dopt.flags = flags;
     const int rc = dagcon_create(&dopt, ctx);
-    if (rc != DAGCON_OK) fprintf(stderr, "pbdagcon: no usable MI355X as device %d (dagcon_create = %d); there is no CPU fallback\n", device, rc);
+    if (rc != DAGCON_OK) { fprintf(stderr, "pbdagcon: no usable MI355X as device %d (dagcon_create = %d); there is no CPU fallback\n", device, rc); return rc; }
+    if (pick && pick->on()) {
+        const dagcon_record_filter f = {pick->max_error_ppm, pick->max_depth};
+        const int rf = dagcon_set_record_filter(*ctx, &f);
+        if (rf != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(*ctx)); dagcon_destroy(*ctx); *ctx = nullptr; return rf; }
+    }
     return rc;
 }

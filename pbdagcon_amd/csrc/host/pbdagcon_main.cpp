@@ -60,6 +60,7 @@ struct Opts {
     std::string ref, reads;            // --ref FASTA (MODE_RECORDS); --reads FASTA / FASTQ (with --paf)
     unsigned window = 0, overlap = 1000;   // --window W [--overlap O] (MODE_RECORDS): targets cut into windows (windows.h)
     bool overlap_set = false;
+    DgPick pick;                       // --max-error F, --max-depth N (MODE_RECORDS): the records are picked on the device
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
     int pinned = -1;                   // --pinned 0|1: page-locked blobs (-1: when the input is several batches long)
@@ -74,7 +75,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]]] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N]] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -129,6 +130,15 @@ void usage(FILE *f) {
             "                      not indexes into the consensus string; a break in the consensus starts a new record\n"
             "  --overlap O         with --window: bases a window is widened by on either side (default 1000); at least\n"
             "                      --trim + 64, so that trimming at a window's ends does not thin the coverage inside its core\n"
+            "  --max-error F       with --sam, --bam or --paf: leave out the records whose read disagrees with the target in more\n"
+            "                      than the fraction F of the alignment's columns (mismatches + inserted + deleted bases; = and X\n"
+            "                      ops are not trusted, the bases are compared, case ignored).  F is decimal text in [0, 1] with\n"
+            "                      at most six places, e.g. 0.15.  Counted on the GPU from the records as they lie there; this\n"
+            "                      build's own rule, parity unpinned\n"
+            "  --max-depth N       with --sam, --bam or --paf: of the records --max-error leaves, at most N per target (with --window:\n"
+            "                      per window) go into the graph, those with the most matching columns, in their own order; 1..4094.\n"
+            "                      -c counts what is left.  With it a target or window of any depth can be run.  Both flags end\n"
+            "                      with one line on stderr that counts the records each left out\n"
             "  --fastq             write FASTQ (@id/r0_r1, sequence, +, qualities) instead of FASTA; the same records in the\n"
             "                      same order.  The quality of a base is this build's own definition: a Laplace-smoothed\n"
             "                      fraction of the reads at its position that do not pass through its consensus vertex,\n"
@@ -181,6 +191,14 @@ int parse_args(int argc, char **argv, Opts &o) {
             o.reads = argv[++i];
         }
         else if (a == "--window") { if (!need(&o.window) || !o.window) { fprintf(stderr, "PARSE ERROR: --window takes a positive number of bases\n"); return 2; } }
+        else if (a == "--max-error") {
+            if (i + 1 >= argc || !dg_parse_ppm(argv[i + 1], &o.pick.max_error_ppm)) { fprintf(stderr, "PARSE ERROR: --max-error takes a fraction in [0, 1] with at most six decimal places\n"); return 2; }
+            i++; o.pick.error_set = true;
+        }
+        else if (a == "--max-depth") {
+            if (!need(&o.pick.max_depth) || !o.pick.max_depth || o.pick.max_depth > DAGCON_MAX_COVERAGE) { fprintf(stderr, "PARSE ERROR: --max-depth takes 1..%u\n", DAGCON_MAX_COVERAGE); return 2; }
+            o.pick.depth_set = true;
+        }
         else if (a == "--overlap") { if (!need(&o.overlap)) return 2; o.overlap_set = true; }
         else if (a == "--ref") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --ref needs a FASTA file\n"); return 2; }
@@ -231,6 +249,7 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (sam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --sam needs --ref <fasta>\n"); return 2; }
     if (!records && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam, --bam or --paf\n"); return 2; }
     if (o.window && (!records || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --window needs --sam, --bam or --paf and does not go with -a or --polish\n"); return 2; }
+    if (o.pick.on() && !records) { fprintf(stderr, "PARSE ERROR: --max-error and --max-depth need --sam, --bam or --paf\n"); return 2; }
     if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
     if (o.window && (uint64_t)o.overlap < (uint64_t)o.trim + 64) { fprintf(stderr, "PARSE ERROR: --overlap must be at least --trim + 64 (%u)\n", o.trim + 64); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
@@ -315,6 +334,7 @@ struct Batch {
     void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); q.n = 0; t.n = 0; out.clear(); }
 };
 
+unsigned long long g_over_error = 0, g_over_depth = 0;     // records --max-error / --max-depth left out, all batches (under g_tmu)
 bool g_timing = false;                                    // PBDAGCON_TIMING=1: where the wall time of the run went, on stderr (seconds)
 std::mutex g_tmu;
 double g_t_upload = 0, g_t_run = 0, g_t_fetch = 0;
@@ -395,8 +415,16 @@ int run_records(dagcon_ctx *ctx, Batch &b, const Opts &o) {
     dagcon_results r;
     const double t0 = wall();
     const int rc = dg_consensus_records(ctx, o.kind, ra, nullptr, &r);
-    if (g_timing) fprintf(stderr, "pbdagcon timing: %s batch of %zu records: %s %.3f\n", dg_kind(o.kind).flag, b.start.size(), dg_kind(o.kind).entry, wall() - t0);
-    return ok(ctx, rc, "consensus") ? append_results(ctx, b, o, r) : 1;
+    if (g_timing) fprintf(stderr, "pbdagcon timing: %s%s batch of %zu records: %s %.3f\n", dg_kind(o.kind).flag, o.pick.text().c_str(), b.start.size(), dg_kind(o.kind).entry, wall() - t0);
+    if (!ok(ctx, rc, "consensus")) return 1;
+    uint64_t n_fate = 0;
+    if (const uint8_t *fate = dg_record_fates(ctx, &n_fate)) {
+        unsigned long long over_error = 0, over_depth = 0;
+        for (uint64_t i = 0; i < n_fate; i++) { over_error += (fate[i] & DAGCON_FATE_MAX_ERROR) != 0; over_depth += (fate[i] & DAGCON_FATE_MAX_DEPTH) != 0; }
+        std::lock_guard<std::mutex> lk(g_tmu);
+        g_over_error += over_error; g_over_depth += over_depth;
+    }
+    return append_results(ctx, b, o, r);
 }
 
 void warn_dropped(dagcon_ctx *ctx, size_t n_records) {
@@ -591,10 +619,10 @@ struct Workers {
     void run(size_t w) {
         dagcon_ctx *ctx = nullptr;
         const double tc0 = wall();
-        int rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], (o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u) | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u), &ctx);
+        int rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], (o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u) | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u), &o.pick, &ctx);
         dagcon_ctx *actx = ctx;                             // --local --polish: the first alignment on a local context of its own
         if (rc == DAGCON_OK && o.local && o.polish) {       // (aligns only: the support comes from ctx's last round)
-            rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], DAGCON_FLAG_LOCAL_ALIGN, &actx);
+            rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], DAGCON_FLAG_LOCAL_ALIGN, nullptr, &actx);
             if (rc != DAGCON_OK) { dagcon_destroy(ctx); ctx = nullptr; }
         }
         if (w == 0) t_create = wall() - tc0;
@@ -1077,6 +1105,7 @@ int parse_input(Ix &ix, size_t first, const Opts &o, Workers &wk) {
 int main(int argc, char **argv) {
     Opts o;
     if (int rc = parse_args(argc, argv, o)) return rc;
+    if (o.dump && o.pick.on()) fprintf(stderr, "pbdagcon: record filter: max_error_ppm %u max_depth %u\n", o.pick.max_error_ppm, o.pick.max_depth);
     g_timing = getenv("PBDAGCON_TIMING") != nullptr;
     const double t_main = wall();
     Input in;
@@ -1109,7 +1138,7 @@ int main(int argc, char **argv) {
 
     // ---- --window: the window driver takes the records from here (windows.h) ----
     if (o.window && !o.dump) {
-        DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0]};
+        DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0], o.pick};
         if (o.kind == DG_REC_PACKED) { DgBamSource src(bam, ref); return dg_run_windows(wo, src, ref); }
         if (o.kind == DG_REC_CS) { DgPafCsSource src(paf); return dg_run_windows(wo, src, ref); }
         if (o.kind == DG_REC_STRANDED) { DgPafSource src(paf); return dg_run_windows(wo, src, ref); }
@@ -1136,6 +1165,7 @@ int main(int argc, char **argv) {
         fast_exit = !getenv("PBDAGCON_TEARDOWN") && !status;
     }
     const double t_joined = wall();
+    if (!o.dump) dg_report_pick(o.pick, g_over_error, g_over_depth);
     if (!fast_exit) {
         for (auto &x : wk.bufs) { x.q.release(); x.t.release(); }
         if (in.map) munmap(in.map, in.size);

@@ -1,4 +1,7 @@
-// windows.h -- `pbdagcon --sam|--bam|--paf [--cs] --ref F --window W [--overlap O]`: targets of any length and depth.
+// windows.h -- `pbdagcon --sam|--bam|--paf [--cs] --ref F --window W [--overlap O]`: targets of any length; of any depth
+// with --max-depth N, which keeps at most N pieces per window (picked on the device, include/dagcon.h).  Without it a
+// window holds at most DAGCON_MAX_COVERAGE (4,094) pieces that pass -m: one piece more and the run ends with the
+// library's "too large" error.
 //
 // Window i of a target has the core [iW, min((i + 1)W, tlen)) and is run as [max(0, iW - O), min(tlen, (i + 1)W + O));
 // a target of at most W bases is one window.  Windows go to the device in groups of about --batch-targets
@@ -73,6 +76,7 @@ struct DgWinOpts {
     size_t batch_targets;
     bool fastq, verbose;
     int device;
+    DgPick pick;                                           // --max-error / --max-depth
 };
 
 // SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
@@ -128,7 +132,7 @@ struct DgBamSource {
 template <class Source>
 inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref) {
     struct Rec { uint32_t pos, s, e, q_len; const char *q; size_t q_bytes; uint64_t op0; uint32_t nops; bool reverse; uint32_t t_span; };   // q, q_bytes: its bytes of the q blob
-    struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; };
+    struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; std::vector<uint8_t> fate; };   // fate: DAGCON_FATE_* per record, over all groups
     std::vector<Tgt> tgts;
     std::vector<uint32_t> ops;
     std::unordered_map<std::string, int> seen;
@@ -181,8 +185,9 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         }
     }
     dagcon_ctx *ctx = nullptr;
-    int rc = dg_create(o.min_cov, o.min_len, o.trim, o.device, DAGCON_FLAG_BASE_POS | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u), &ctx);
+    int rc = dg_create(o.min_cov, o.min_len, o.trim, o.device, DAGCON_FLAG_BASE_POS | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u), &o.pick, &ctx);
     if (rc != DAGCON_OK) return 1;
+    for (Tgt &t : tgts) t.fate.assign(t.recs.size(), 0);
     int status = 0;
     DgStitch st;
     std::string out;
@@ -205,10 +210,11 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         std::string qblob;
         std::vector<uint8_t> b_rev;                            // stranded sources: one flag per record
         std::vector<uint32_t> b_cslen, b_tspan;                // cs sources: qblob holds the texts
+        std::vector<uint8_t *> b_fate;                         // where each record's fate is kept (a record goes out with every group it meets)
         for (size_t a = w0; a < w1;) {
             size_t z = a;
             while (z < w1 && wins[z].tgt == wins[a].tgt) z++;
-            const Tgt &t = tgts[wins[a].tgt];
+            Tgt &t = tgts[wins[a].tgt];
             const uint32_t lo = wins[a].begin, hi = wins[z - 1].end;
             const uint32_t bt = (uint32_t)b_tlen.size();
             b_tlen.push_back(t.sp.len); b_toff.push_back(t.sp.off);
@@ -217,6 +223,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             auto it = std::lower_bound(t.recs.begin(), t.recs.end(), from, [](const Rec &r, uint32_t v) { return r.s < v; });
             for (; it != t.recs.end() && it->s < hi; ++it) {
                 if (it->e <= lo) continue;
+                b_fate.push_back(&t.fate[(size_t)(it - t.recs.begin())]);
                 b_pos.push_back(it->pos); b_qoff.push_back(qblob.size()); b_qlen.push_back(it->q_len);
                 qblob.append(it->q, it->q_bytes);
                 if ((Source::kind == DG_REC_CS)) { b_cslen.push_back((uint32_t)it->q_bytes); b_tspan.push_back(it->t_span); }
@@ -245,6 +252,9 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         if (rc == DAGCON_OK) rc = dagcon_fetch_positions(ctx, &pos, &npos);
         if (rc == DAGCON_OK && o.fastq) rc = dagcon_fetch_support(ctx, &sup);
         if (rc != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); status = 1; break; }
+        uint64_t n_fate = 0;
+        if (const uint8_t *fate = dg_record_fates(ctx, &n_fate))
+            for (uint64_t i = 0; i < n_fate && i < b_fate.size(); i++) *b_fate[i] |= fate[i];
         for (size_t k = w0; k < w1; k++) {
             const Win &w = wins[k];
             if ((long long)w.tgt != cur_tgt) {
@@ -266,6 +276,10 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         w0 = w1;
     }
     if (status == 0 && !flush_target()) status = 1;
+    unsigned long long over_error = 0, over_depth = 0;
+    for (const Tgt &t : tgts)
+        for (const uint8_t f : t.fate) { over_error += (f & DAGCON_FATE_MAX_ERROR) != 0; over_depth += (f & DAGCON_FATE_MAX_DEPTH) != 0; }
+    dg_report_pick(o.pick, over_error, over_depth);
     fflush(stdout);
     dagcon_destroy(ctx);
     return status;

@@ -109,6 +109,19 @@ static DgPlan dg_plan_pieces(const DgPlanIn &in) {
     return pl;
 }
 
+// The words the host reads back after every run, as ranges of ONE device buffer (each 16-byte aligned): what a run starts
+// from zero first -- DgStatus, tfail[T + 1], cns_len[T], n_seg[T]: one memset -- then cns_off[T] and seg_first[T].  The whole
+// block comes back in one copy into `host`, its page-locked mirror (dagcon_fetch reads the mirror in place).
+struct StatBlock {
+    DevBuf dev;
+    char *host = nullptr;
+    size_t host_cap = 0;
+    size_t o_tfail = 0, o_cns_len = 0, o_n_seg = 0, o_cns_off = 0, o_seg_first = 0;     // (DgStatus at 0)
+    size_t zero_bytes = 0, bytes = 0;
+    template <typename X> X *d(size_t off) const { return reinterpret_cast<X *>(static_cast<char *>(dev.p) + off); }
+    template <typename X> const X *h(size_t off) const { return reinterpret_cast<const X *>(host + off); }
+};
+
 struct Ctx {
     dagcon_opts opts;
     int device = 0;
@@ -133,6 +146,7 @@ struct Ctx {
     std::vector<uint64_t> h_aln_begin, h_aln_off, h_mat_base, h_bbv_base, h_bb_off, h_matc_base;
     std::vector<uint32_t> h_matc_stride;
     uint64_t matc_cells = 0;
+    bool wide_cells = false;                        // this upload met an insertion run of more than 255 columns: 32-bit matC cells
     std::vector<uint8_t> h_tactive;
     std::vector<uint32_t> h_ch_base, h_ch_aln;      // chunk tables of k_norm_*
     std::vector<uint64_t> h_norm_off;               // column buffer of each alignment
@@ -143,7 +157,7 @@ struct Ctx {
     uint64_t tmp_main = 0, tmp_cap = 0;
 
     // device buffers
-    DevBuf d_tfail, d_q, d_t, d_aln_off, d_aln_len, d_aln_start, d_aln_tgt, d_tlen, d_aln_begin, d_tactive,
+    DevBuf d_q, d_t, d_aln_off, d_aln_len, d_aln_start, d_aln_tgt, d_tlen, d_aln_begin, d_tactive,
         d_bb, d_bb_off, d_mat_base, d_bbv_base, d_matc_base, d_matc_stride;
     DevBuf d_nmis, d_norm_off, d_n_lo, d_n_hi, d_n_start, d_n_ins, d_n_del, d_norm;
     DevBuf d_ch_aln, d_ch_base, d_ch_k0, d_ch_next, d_ch_w, d_ch_tb, d_ch_flag, d_ch_src, d_ch_out, d_ch_adv,
@@ -164,7 +178,9 @@ struct Ctx {
     bool rs_valid = false;                          // the record stats below are those of the last upload (dagcon_fetch_record_stats)
     std::vector<uint32_t> rs_match, rs_mismatch, rs_ins, rs_del;
     std::vector<uint8_t> rs_fate;
-    DevBuf d_cns, d_cns_off, d_cns_len, d_seg_first, d_n_seg, d_seg_r0, d_seg_r1, d_st;
+    DevBuf d_cns;
+    StatBlock sb;                                   // DgStatus, tfail, cns_len, n_seg, cns_off, seg_first
+    DevBuf d_seg;                                   // seg_r0[seg_cap], then seg_r1 at seg_stride() entries
     DevBuf d_pos_tmp, d_pos_tmp0, d_pos;           // DAGCON_FLAG_BASE_POS: walk scratch (4 B per vertex), output (4 B per base)
     DevBuf d_sup_tmp, d_sup_tmp0, d_sup;           // DAGCON_FLAG_BASE_SUPPORT: walk scratch (4 B per vertex), output (2 x 2 B per base)
 
@@ -179,9 +195,11 @@ struct Ctx {
     dagcon_timings tm;
 
     // results (host)
-    std::vector<uint64_t> r_seg_begin, r_seq_off, r_cns_off, r_seg_first;
-    std::vector<int32_t> r_range0, r_range1, r_tmp0, r_tmp1;
-    std::vector<uint32_t> r_seq_len, r_cns_len, r_n_seg, r_tfail;
+    std::vector<uint64_t> r_seg_begin, r_seq_off;
+    std::vector<int32_t> r_range0, r_range1;
+    std::vector<uint32_t> r_seq_len;
+    int32_t *r_seg = nullptr;           // page-locked, grown with the segment arena: seg_r0's first seg_top entries, then seg_r1's
+    size_t r_seg_cap = 0;               // (entries of each half)
     std::vector<int32_t> r_status;
     char *r_blob = nullptr;             // page-locked: the consensus blob comes back at PCIe speed
     size_t r_blob_cap = 0;
@@ -254,6 +272,34 @@ void free_buf(DevBuf &b) {
     b.p = nullptr; b.cap = 0;
 }
 
+size_t seg_stride(const Ctx *c) { return ((size_t)c->seg_cap + 3) & ~(size_t)3; }      // entries between seg_r0 and seg_r1 (16-byte aligned)
+
+// bytes of a matC cell: a byte where the cells stay run lengths (p.emit_scan) and no run of this upload has outgrown it
+bool matc_wide(const Ctx *c) { return c->max_k > 64u || c->wide_cells; }
+size_t matc_bytes(const Ctx *c) { return (size_t)c->matc_cells * (matc_wide(c) ? 4u : 1u); }
+
+// the status block of a batch of T targets and its mirror
+int ensure_stat(Ctx *c, uint32_t T) {
+    StatBlock &b = c->sb;
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    b.o_tfail = up16(sizeof(DgStatus));
+    b.o_cns_len = b.o_tfail + up16(((size_t)T + 1) * 4);
+    b.o_n_seg = b.o_cns_len + up16((size_t)T * 4);
+    b.zero_bytes = b.o_n_seg + up16((size_t)T * 4);
+    b.o_cns_off = b.zero_bytes;
+    b.o_seg_first = b.o_cns_off + up16((size_t)T * 8);
+    b.bytes = b.o_seg_first + up16((size_t)T * 8);
+    ENSURE(c, b.dev, b.bytes);
+    if (b.host_cap < b.bytes) {
+        if (b.host) (void)hipHostFree(b.host);
+        b.host = nullptr; b.host_cap = 0;
+        const size_t want = b.bytes + b.bytes / 8 + 4096;
+        HIPCHK(c, hipHostMalloc((void **)&b.host, want, hipHostMallocDefault));
+        b.host_cap = want;
+    }
+    return DAGCON_OK;
+}
+
 int ensure_arenas(Ctx *c) {
     ENSURE(c, c->d_norm, c->norm_cap * sizeof(uint16_t));
     ENSURE(c, c->d_nodes, c->node_cap * sizeof(DgNode));
@@ -293,8 +339,15 @@ int ensure_arenas(Ctx *c) {
         if (c->gcuts) ENSURE(c, c->d_pos_tmp0, c->node_cap * 4);
         ENSURE(c, c->d_pos, c->cns_cap * 4);
     }
-    ENSURE(c, c->d_seg_r0, c->seg_cap * 4);
-    ENSURE(c, c->d_seg_r1, c->seg_cap * 4);
+    ENSURE(c, c->d_seg, 2 * seg_stride(c) * 4);
+    if (c->r_seg_cap < c->seg_cap) {
+        if (c->r_seg) (void)hipHostFree(c->r_seg);
+        c->r_seg = nullptr; c->r_seg_cap = 0;
+        const size_t want = (size_t)c->seg_cap + (size_t)(c->seg_cap / 8) + 1024;
+        HIPCHK(c, hipHostMalloc((void **)&c->r_seg, 2 * want * 4, hipHostMallocDefault));
+        c->r_seg_cap = want;
+    }
+    ENSURE(c, c->d_matC, matc_bytes(c) + 256);          // (grows for the re-run with 32-bit cells)
     return DAGCON_OK;
 }
 
@@ -307,7 +360,7 @@ void fill_params(Ctx *c, DgParams &p) {
     p.aln_tgt = (const uint32_t *)c->d_aln_tgt.p;
     p.tlen = (const uint32_t *)c->d_tlen.p;
     p.aln_begin = (const uint64_t *)c->d_aln_begin.p;
-    p.tactive = (const uint8_t *)c->d_tactive.p; p.tfail = (uint32_t *)c->d_tfail.p;
+    p.tactive = (const uint8_t *)c->d_tactive.p; p.tfail = c->sb.d<uint32_t>(c->sb.o_tfail);
     p.bb = c->have_bb ? (const uint8_t *)c->d_bb.p : nullptr;
     p.bb_off = (const uint64_t *)c->d_bb_off.p;
     p.mat_base = (const uint64_t *)c->d_mat_base.p;
@@ -335,7 +388,7 @@ void fill_params(Ctx *c, DgParams &p) {
     p.node_base = (uint64_t *)c->d_node_base.p; p.n_nodes = (uint32_t *)c->d_n_nodes.p;
     p.pool_base = (uint64_t *)c->d_pool_base.p; p.pool_size = (uint32_t *)c->d_pool_size.p;
     p.pool_top = (uint32_t *)c->d_pool_top.p; p.t_nins = (uint32_t *)c->d_t_nins.p;
-    p.matA = (uint32_t *)c->d_matA.p; p.matD = (uint32_t *)c->d_matD.p; p.matC = (uint32_t *)c->d_matC.p;
+    p.matA = (uint32_t *)c->d_matA.p; p.matD = (uint32_t *)c->d_matD.p; p.matC = c->d_matC.p;
     p.cov = (int32_t *)c->d_cov.p; p.gcount = (uint32_t *)c->d_gcount.p;
     p.gbase = (uint32_t *)c->d_gbase.p; p.bid = (uint32_t *)c->d_bid.p;
     p.nodes = (DgNode *)c->d_nodes.p; p.best = (int32_t *)c->d_best.p;
@@ -360,11 +413,11 @@ void fill_params(Ctx *c, DgParams &p) {
     p.seg_done = (uint32_t *)c->d_seg_done.p; p.wl_first = (uint32_t *)c->d_wl_first.p;
     p.worklist = (uint32_t *)c->d_worklist.p; p.worklist_cap = c->worklist_cap;
     p.cns = (uint8_t *)c->d_cns.p; p.cns_cap = c->cns_cap;
-    p.cns_off = (uint64_t *)c->d_cns_off.p; p.cns_len = (uint32_t *)c->d_cns_len.p;
-    p.seg_first = (uint64_t *)c->d_seg_first.p; p.n_seg = (uint32_t *)c->d_n_seg.p;
-    p.seg_r0 = (int32_t *)c->d_seg_r0.p; p.seg_r1 = (int32_t *)c->d_seg_r1.p;
+    p.cns_off = c->sb.d<uint64_t>(c->sb.o_cns_off); p.cns_len = c->sb.d<uint32_t>(c->sb.o_cns_len);
+    p.seg_first = c->sb.d<uint64_t>(c->sb.o_seg_first); p.n_seg = c->sb.d<uint32_t>(c->sb.o_n_seg);
+    p.seg_r0 = (int32_t *)c->d_seg.p; p.seg_r1 = p.seg_r0 + seg_stride(c);
     p.seg_cap = c->seg_cap;
-    p.st = (DgStatus *)c->d_st.p;
+    p.st = c->sb.d<DgStatus>(0);
     if (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT) {
         p.sup_tmp = (uint32_t *)c->d_sup_tmp.p; p.sup_tmp0 = (uint32_t *)c->d_sup_tmp0.p;
         p.sup_w = (uint16_t *)c->d_sup.p; p.sup_d = p.sup_w + c->cns_cap;
@@ -375,15 +428,21 @@ void fill_params(Ctx *c, DgParams &p) {
 }
 
 // stage a1: count, chunked normalizeGaps + trimAln, and the sequential kernel for what is left
-void launch_normalize(Ctx *c, const DgParams &p) {
+// (wide: the matC writers' 32-bit instances)
+void launch_normalize(Ctx *c, const DgParams &p, const bool wide) {
     hipStream_t s = c->stream;
     if (c->A == 0) return;
     (void)hipMemsetAsync(c->d_ckpt.p, 0xFF, c->n_ckpt * 4, s);
     hipLaunchKernelGGL((k_norm_chunk<DG_NW, 64, false>), dim3((c->n_chunks + 63) / 64), dim3(64), 0, s, p);
     hipLaunchKernelGGL((k_norm_chunk<DG_NW_BIG, 32, true>), dim3((c->n_chunks + 31) / 32), dim3(32), 0, s, p);
     hipLaunchKernelGGL(k_norm_scan, dim3((c->A + 63) / 64), dim3(64), 0, s, p);
-    hipLaunchKernelGGL(k_norm_finish2, dim3((c->n_chunks + 3) / 4), dim3(256), 0, s, p);    // a wave per chunk
-    hipLaunchKernelGGL(k_normalize_slow, dim3((c->A + 63) / 64), dim3(64), 0, s, p);
+    if (wide) {
+        hipLaunchKernelGGL(k_norm_finish2<uint32_t>, dim3((c->n_chunks + 3) / 4), dim3(256), 0, s, p);    // a wave per chunk
+        hipLaunchKernelGGL(k_normalize_slow<uint32_t>, dim3((c->A + 63) / 64), dim3(64), 0, s, p);
+    } else {
+        hipLaunchKernelGGL(k_norm_finish2<uint8_t>, dim3((c->n_chunks + 3) / 4), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(k_normalize_slow<uint8_t>, dim3((c->A + 63) / 64), dim3(64), 0, s, p);
+    }
 }
 
 int launch_all(Ctx *c) {
@@ -392,6 +451,7 @@ int launch_all(Ctx *c) {
     DgParams p;
     fill_params(c, p);
     hipStream_t s = c->stream;
+    const bool wide = matc_wide(c);                       // (!p.emit_scan, or a run of this upload outgrew a byte)
     if (c->poison & 8) {
         // every buffer the kernels themselves fill (nothing the host uploaded), before the memsets below: whoever reads an
         // entry of them that THIS run has not written finds 0xEE bytes, in a fresh process as in one that re-uses its memory
@@ -400,16 +460,15 @@ int launch_all(Ctx *c) {
                           &c->d_node_base, &c->d_n_nodes, &c->d_pool_base, &c->d_pool_size, &c->d_pool_top, &c->d_t_nins, &c->d_cov, &c->d_gcount,
                           &c->d_gbase, &c->d_bid, &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_stk, &c->d_cuts,
                           &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_wl_first,
-                          &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns, &c->d_cns_off, &c->d_seg_first,
-                          &c->d_seg_r0, &c->d_seg_r1, &c->d_worklist, &c->d_seg_done, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup, &c->d_pos_tmp, &c->d_pos_tmp0, &c->d_pos};
+                          &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns,
+                          &c->d_seg, &c->d_worklist, &c->d_seg_done, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup, &c->d_pos_tmp, &c->d_pos_tmp0, &c->d_pos};
         for (DevBuf *b : work)
             if (b->p && b->cap) HIPCHK(c, hipMemsetAsync(b->p, 0xEE, b->cap, s));
+        // (cns_off and seg_first: the part of the status block that is not cleared below)
+        if (c->sb.bytes > c->sb.zero_bytes) HIPCHK(c, hipMemsetAsync(c->sb.d<char>(c->sb.zero_bytes), 0xEE, c->sb.bytes - c->sb.zero_bytes, s));
     }
-    HIPCHK(c, hipMemsetAsync(c->d_st.p, 0, sizeof(DgStatus), s));
-    HIPCHK(c, hipMemsetAsync(c->d_tfail.p, 0, (size_t)c->T * 4 + 4, s));
-    HIPCHK(c, hipMemsetAsync(c->d_cns_len.p, 0, (size_t)c->T * 4, s));
-    HIPCHK(c, hipMemsetAsync(c->d_n_seg.p, 0, (size_t)c->T * 4, s));
-    if (c->matc_cells) HIPCHK(c, hipMemsetAsync(c->d_matC.p, 0, c->matc_cells * 4, s));
+    HIPCHK(c, hipMemsetAsync(c->sb.dev.p, 0, c->sb.zero_bytes, s));      // DgStatus, tfail, cns_len, n_seg
+    if (c->matc_cells) HIPCHK(c, hipMemsetAsync(c->d_matC.p, 0, matc_bytes(c), s));
     if (c->poison) {
         // what no kernel is supposed to read before it has been written in THIS run: a process that re-uses its
         // arenas (another context's freed memory, the batch before) finds old cells there, not the zeros of a fresh one
@@ -419,19 +478,22 @@ int launch_all(Ctx *c) {
         if ((c->poison & 4) && c->d_norm.p) HIPCHK(c, hipMemsetAsync(c->d_norm.p, 0xEE, c->d_norm.cap, s));
     }
     HIPCHK(c, hipEventRecord(c->ev[0], s));
-    launch_normalize(c, p);
+    launch_normalize(c, p, wide);
     HIPCHK(c, hipEventRecord(c->ev[1], s));
     // (matA / matD are not cleared: k_emit writes every cell of every row)
     hipLaunchKernelGGL(k_carve, dim3(1), dim3(1024), 0, s, p);
     if (c->T > 0) {
         const uint32_t rows4 = (c->max_tlen + 2 + 4 * DG_LPW - 1) / (4 * DG_LPW);   // 4 waves x DG_LPW positions per block
         if (c->gcuts && c->A > 0) hipLaunchKernelGGL(k_readspan, dim3((c->A + 63) / 64), dim3(64), 0, s, p);   // (before matC becomes prefix sums)
-        if (p.emit_scan) hipLaunchKernelGGL(k_gsum, dim3(c->T, (c->max_tlen + 2 + 255) / 256), dim3(256), 0, s, p);
+        if (p.emit_scan && wide) hipLaunchKernelGGL(k_gsum<uint32_t>, dim3(c->T, (c->max_tlen + 2 + 255) / 256), dim3(256), 0, s, p);
+        else if (p.emit_scan) hipLaunchKernelGGL(k_gsum<uint8_t>, dim3(c->T, (c->max_tlen + 2 + 1023) / 1024), dim3(256), 0, s, p);
         else hipLaunchKernelGGL(k_groups, dim3(c->T, (c->max_tlen + 2 + 31) / 32), dim3(256), 0, s, p);
         hipLaunchKernelGGL(k_gscan, dim3(c->T), dim3(1024), 0, s, p);
-        if (c->A > 0)
-            hipLaunchKernelGGL(k_emit, dim3(c->T, (c->max_k + DG_ERPW - 1) / DG_ERPW, ((c->max_tlen + 2) >> c->emit_shift) + 1),
-                               dim3(64), 0, s, p);
+        if (c->A > 0) {
+            const dim3 eg(c->T, (c->max_k + DG_ERPW - 1) / DG_ERPW, ((c->max_tlen + 2) >> c->emit_shift) + 1);
+            if (wide) hipLaunchKernelGGL(k_emit<uint32_t>, eg, dim3(64), 0, s, p);
+            else hipLaunchKernelGGL(k_emit<uint8_t>, eg, dim3(64), 0, s, p);
+        }
         const size_t lds = (size_t)4 * 2 * (c->max_k + 2) * sizeof(int32_t);
         if (lds > 65536)
             HIPCHK(c, hipFuncSetAttribute((const void *)k_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -550,7 +612,7 @@ int dagcon_create(const dagcon_opts *opts, dagcon_ctx **out) {
     }
     for (auto &e : c->ev)
         if (hipEventCreate(&e) != hipSuccess) { delete c; return DAGCON_ERR_HIP; }
-    if (ensure(c, c->d_st, sizeof(DgStatus)) != DAGCON_OK) { delete c; return DAGCON_ERR_WORKSPACE; }
+    if (ensure_stat(c, 0) != DAGCON_OK) { dagcon_destroy(reinterpret_cast<dagcon_ctx *>(c)); return DAGCON_ERR_WORKSPACE; }
     *out = reinterpret_cast<dagcon_ctx *>(c);
     return DAGCON_OK;
 }
@@ -562,15 +624,16 @@ void dagcon_destroy(dagcon_ctx *ctx) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->r_blob) (void)hipHostFree(c->r_blob);
     if (c->r_sup) (void)hipHostFree(c->r_sup);
+    if (c->r_seg) (void)hipHostFree(c->r_seg);
+    if (c->sb.host) (void)hipHostFree(c->sb.host);
     DevBuf *all[] = {&c->d_q, &c->d_t, &c->d_aln_off, &c->d_aln_len, &c->d_aln_start, &c->d_aln_tgt,
-                     &c->d_tlen, &c->d_aln_begin, &c->d_tactive, &c->d_tfail, &c->d_bb, &c->d_bb_off, &c->d_mat_base, &c->d_matc_base, &c->d_matc_stride,
+                     &c->d_tlen, &c->d_aln_begin, &c->d_tactive, &c->sb.dev, &c->d_bb, &c->d_bb_off, &c->d_mat_base, &c->d_matc_base, &c->d_matc_stride,
                      &c->d_bbv_base, &c->d_nmis, &c->d_norm_off, &c->d_n_lo, &c->d_n_hi, &c->d_n_start, &c->d_ch_aln, &c->d_ch_base, &c->d_ch_k0, &c->d_ch_next, &c->d_ch_w, &c->d_ch_tb, &c->d_ch_flag, &c->d_ch_src, &c->d_ch_out, &c->d_ch_adv, &c->d_n_lb, &c->d_norm_tmp, &c->d_ckpt, &c->d_ck_base,
                      &c->d_n_ins, &c->d_n_del, &c->d_norm, &c->d_node_base, &c->d_n_nodes,
                      &c->d_pool_base, &c->d_pool_size, &c->d_pool_top, &c->d_t_nins, &c->d_matA, &c->d_matD,
                      &c->d_matC, &c->d_cov, &c->d_gcount, &c->d_gbase, &c->d_bid, &c->d_nodes,
                      &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_score_b, &c->d_pool, &c->d_stk, &c->d_cuts, &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_worklist, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_seg_done, &c->d_wl_first, &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns,
-                     &c->d_cns_off, &c->d_cns_len, &c->d_seg_first, &c->d_n_seg, &c->d_seg_r0, &c->d_seg_r1,
-                     &c->d_st, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup, &c->d_pos_tmp, &c->d_pos_tmp0, &c->d_pos};
+                     &c->d_seg, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup, &c->d_pos_tmp, &c->d_pos_tmp0, &c->d_pos};
     for (DevBuf *b : all) free_buf(*b);
     for (DevBuf &b : c->d_al) free_buf(b);
     for (DevBuf &b : c->d_pn) free_buf(b);
@@ -590,6 +653,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->sup_valid = c->pos_valid = false;
     c->h_cig_bad.clear();
     c->rs_valid = false;
+    c->wide_cells = false;                             // (one batch with a very long insertion run does not slow the ones after it)
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->aln_begin)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/aln_begin is NULL");
     const uint64_t A_all = T ? b->aln_begin[T] : 0;
@@ -757,13 +821,11 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     }
     ENSURE(c, c->d_node_base, (size_t)T * 8); ENSURE(c, c->d_n_nodes, T4);
     ENSURE(c, c->d_pool_base, (size_t)T * 8); ENSURE(c, c->d_pool_size, T4); ENSURE(c, c->d_pool_top, T4);
-    ENSURE(c, c->d_t_nins, T4); ENSURE(c, c->d_tfail, T4 + 4);
+    ENSURE(c, c->d_t_nins, T4);
     ENSURE(c, c->d_matA, c->mat_cells * 4); ENSURE(c, c->d_matD, c->mat_cells * 4);
-    ENSURE(c, c->d_matC, c->matc_cells * 4 + 256);
     ENSURE(c, c->d_cov, c->sum_bb * 4); ENSURE(c, c->d_gcount, c->sum_bb * 4);
     ENSURE(c, c->d_gbase, c->sum_bb * 4); ENSURE(c, c->d_bid, c->sum_bb * 4);
-    ENSURE(c, c->d_cns_off, (size_t)T * 8); ENSURE(c, c->d_cns_len, T4);
-    ENSURE(c, c->d_seg_first, (size_t)T * 8); ENSURE(c, c->d_n_seg, T4);
+    if ((r = ensure_stat(c, T))) return r;
 
     // first guesses for the data-dependent arenas; a run that finds them too
     // small records the exact need on the device and is repeated once.
@@ -847,7 +909,7 @@ static hipError_t d2h(Ctx *c, void *dst, const void *src, size_t bytes) {
 
 static int read_status(Ctx *c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, d2h(c, &c->h_st, c->d_st.p, sizeof(DgStatus)));
+    HIPCHK(c, d2h(c, &c->h_st, c->sb.dev.p, sizeof(DgStatus)));
     return DAGCON_OK;
 }
 
@@ -857,8 +919,11 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     if (!c->ran) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch before dagcon_run");
     HIPCHK(c, hipSetDevice(c->device));
     int r;
+    const StatBlock &sb = c->sb;
     for (int attempt = 0;; attempt++) {
-        if ((r = read_status(c))) return r;
+        // round 1: the whole status block in one copy -- the status, and with it everything whose size the host knows
+        HIPCHK(c, d2h(c, sb.host, sb.dev.p, sb.bytes));
+        memcpy(&c->h_st, sb.host, sizeof(DgStatus));
         const uint32_t f = c->h_st.err_flags;
         if (f == 0) break;
         if (f & DG_E_TARGET_MASK)       // (target-level failures never set the batch flag: see DgParams::tfail)
@@ -871,6 +936,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         if (f & DG_E_STACK) c->stk_words *= 4;
         if (f & DG_E_LIST_OVF) c->worklist_cap *= 4;
         if (f & DG_E_LOG_OVF) c->sh_log *= 2;
+        if (f & DG_E_RUN_WIDE) c->wide_cells = true;       // (until the next upload)
         if (f & DG_E_OUT_OVF) {
             c->cns_cap = std::max<uint64_t>(c->cns_cap, c->h_st.cns_top + 1024);
             c->seg_cap = std::max<uint64_t>(c->seg_cap, c->h_st.seg_top + 1024);
@@ -888,12 +954,13 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
 
     const uint32_t T = c->T;
     // per-target outcome (ABI 2): a failure is confined to its target
-    c->r_tfail.assign(T, 0); c->r_status.assign(T, DAGCON_OK);
-    if (T) HIPCHK(c, d2h(c, c->r_tfail.data(), c->d_tfail.p, (size_t)T * 4));
+    const uint32_t *m_tfail = sb.h<uint32_t>(sb.o_tfail), *m_n_seg = sb.h<uint32_t>(sb.o_n_seg);
+    const uint64_t *m_cns_off = sb.h<uint64_t>(sb.o_cns_off), *m_seg_first = sb.h<uint64_t>(sb.o_seg_first);
+    c->r_status.assign(T, DAGCON_OK);
     uint32_t n_failed = 0;
     c->err.clear();
     for (uint32_t t = 0; t < T; t++) {
-        const uint32_t f = c->r_tfail[t];
+        const uint32_t f = m_tfail[t];
         if (!f) continue;
         const int code = (f & (DG_E_BADCHAR | DG_E_NONCONF)) ? DAGCON_ERR_NONCONFORMING
                        : (f & DG_E_TOO_BIG) ? DAGCON_ERR_UNSUPPORTED : DAGCON_ERR_INTERNAL;
@@ -912,8 +979,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         if (!n_failed++) c->err = c->cig_err;
     }
     const uint64_t nseg = c->h_st.seg_top, nb = c->h_st.cns_top;
-    c->r_cns_off.assign(T, 0); c->r_cns_len.assign(T, 0); c->r_seg_first.assign(T, 0); c->r_n_seg.assign(T, 0);
-    c->r_tmp0.assign(nseg, 0); c->r_tmp1.assign(nseg, 0);
+    if (nseg > c->r_seg_cap || nseg > c->seg_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu segments in an arena of %llu", (unsigned long long)nseg, (unsigned long long)c->seg_cap);
     if (c->r_blob_cap < nb + 1) {
         if (c->r_blob) (void)hipHostFree(c->r_blob);
         c->r_blob = nullptr; c->r_blob_cap = 0;
@@ -923,50 +989,47 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     }
     c->r_blob[nb] = 0;
     const bool full = !(c->opts.flags & (DAGCON_FLAG_STOP_AFTER_BUILD | DAGCON_FLAG_STOP_AFTER_MERGE));
-    if (T && full) {
-        HIPCHK(c, d2h(c, c->r_cns_off.data(), c->d_cns_off.p, (size_t)T * 8));
-        HIPCHK(c, d2h(c, c->r_cns_len.data(), c->d_cns_len.p, (size_t)T * 4));
-        HIPCHK(c, d2h(c, c->r_seg_first.data(), c->d_seg_first.p, (size_t)T * 8));
-        HIPCHK(c, d2h(c, c->r_n_seg.data(), c->d_n_seg.p, (size_t)T * 4));
-        if (nseg) {
-            HIPCHK(c, d2h(c, c->r_tmp0.data(), c->d_seg_r0.p, nseg * 4));
-            HIPCHK(c, d2h(c, c->r_tmp1.data(), c->d_seg_r1.p, nseg * 4));
-        }
-        if (nb) HIPCHK(c, d2h(c, c->r_blob, c->d_cns.p, nb));
-    }
+    const bool want_sup = full && (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT), want_pos = full && (c->opts.flags & DAGCON_FLAG_BASE_POS);
     c->sup_valid = c->pos_valid = false;
-    if (full && (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT)) {
-        // the support, weights then depths (the device keeps them apart: no host pass over them)
-        if (c->r_sup_cap < nb + 1) {
-            if (c->r_sup) (void)hipHostFree(c->r_sup);
-            c->r_sup = nullptr; c->r_sup_cap = 0;
-            const size_t want = (size_t)(nb + 1) + (size_t)(nb / 8) + 4096;
-            HIPCHK(c, hipHostMalloc((void **)&c->r_sup, want * 4, hipHostMallocDefault));
-            c->r_sup_cap = want;
-        }
-        if (nb) {
-            HIPCHK(c, hipMemcpyAsync(c->r_sup, c->d_sup.p, nb * 2, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, d2h(c, c->r_sup + nb, (const uint16_t *)c->d_sup.p + c->cns_cap, nb * 2));
-        }
-        c->r_sup_n = nb;
-        c->sup_valid = true;
+    if (want_sup && c->r_sup_cap < nb + 1) {
+        if (c->r_sup) (void)hipHostFree(c->r_sup);
+        c->r_sup = nullptr; c->r_sup_cap = 0;
+        const size_t want = (size_t)(nb + 1) + (size_t)(nb / 8) + 4096;
+        HIPCHK(c, hipHostMalloc((void **)&c->r_sup, want * 4, hipHostMallocDefault));
+        c->r_sup_cap = want;
     }
-    if (full && (c->opts.flags & DAGCON_FLAG_BASE_POS)) {
-        c->r_pos.resize(nb + 1);
-        if (nb) HIPCHK(c, d2h(c, c->r_pos.data(), c->d_pos.p, nb * 4));
-        c->pos_valid = true;
+    if (want_pos) c->r_pos.resize(nb + 1);
+    // round 2: what the status sizes -- the segments' ranges (the first seg_top entries of either array), the blob, the
+    // support (weights then depths: the device keeps them apart, no host pass over them) and the positions -- enqueued
+    // together, one wait
+    int32_t *m_r0 = c->r_seg, *m_r1 = c->r_seg + nseg;
+    bool queued = false;
+    if (T && full && nseg) {
+        HIPCHK(c, hipMemcpyAsync(m_r0, c->d_seg.p, nseg * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(m_r1, (const int32_t *)c->d_seg.p + seg_stride(c), nseg * 4, hipMemcpyDeviceToHost, c->stream));
+        queued = true;
     }
+    if (T && full && nb) { HIPCHK(c, hipMemcpyAsync(c->r_blob, c->d_cns.p, nb, hipMemcpyDeviceToHost, c->stream)); queued = true; }
+    if (want_sup && nb) {
+        HIPCHK(c, hipMemcpyAsync(c->r_sup, c->d_sup.p, nb * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->r_sup + nb, (const uint16_t *)c->d_sup.p + c->cns_cap, nb * 2, hipMemcpyDeviceToHost, c->stream));
+        queued = true;
+    }
+    if (want_pos && nb) { HIPCHK(c, hipMemcpyAsync(c->r_pos.data(), c->d_pos.p, nb * 4, hipMemcpyDeviceToHost, c->stream)); queued = true; }
+    if (queued) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (want_sup) { c->r_sup_n = nb; c->sup_valid = true; }
+    if (want_pos) c->pos_valid = true;
     c->r_seg_begin.assign(T + 1, 0);
     c->r_range0.clear(); c->r_range1.clear(); c->r_seq_off.clear(); c->r_seq_len.clear();
     uint64_t bases = 0;
     for (uint32_t t = 0; t < T; t++) {
         c->r_seg_begin[t] = c->r_range0.size();
-        if (!full || !c->h_tactive[t] || c->r_tfail[t]) continue;
-        for (uint32_t i = 0; i < c->r_n_seg[t]; i++) {
-            const uint64_t s = c->r_seg_first[t] + i;
-            const int32_t r0 = c->r_tmp0[s], r1 = c->r_tmp1[s];
+        if (!full || !c->h_tactive[t] || m_tfail[t]) continue;
+        for (uint32_t i = 0; i < m_n_seg[t]; i++) {
+            const uint64_t s = m_seg_first[t] + i;
+            const int32_t r0 = m_r0[s], r1 = m_r1[s];
             c->r_range0.push_back(r0); c->r_range1.push_back(r1);
-            c->r_seq_off.push_back(c->r_cns_off[t] + (uint64_t)r0);
+            c->r_seq_off.push_back(m_cns_off[t] + (uint64_t)r0);
             c->r_seq_len.push_back((uint32_t)(r1 - r0));
             bases += (uint64_t)(r1 - r0);
         }
@@ -1021,7 +1084,7 @@ int dagcon_debug_counters(dagcon_ctx *ctx, unsigned long long *out8) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     DgStatus st;
-    HIPCHK(c, d2h(c, &st, c->d_st.p, sizeof st));
+    HIPCHK(c, d2h(c, &st, c->sb.dev.p, sizeof st));
     for (int i = 0; i < 16; i++) out8[i] = st.dbg[i];
     return DAGCON_OK;
 }
@@ -1087,9 +1150,8 @@ static int normalize_impl(Ctx *c, dagcon_ctx *ctx, uint32_t n, const uint32_t *a
         DgParams p;
         fill_params(c, p);
         p.flags |= DG_F_A1_ONLY;
-        HIPCHK(c, hipMemsetAsync(c->d_st.p, 0, sizeof(DgStatus), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_tfail.p, 0, (size_t)c->T * 4 + 4, c->stream));
-        launch_normalize(c, p);
+        HIPCHK(c, hipMemsetAsync(c->sb.dev.p, 0, c->sb.zero_bytes, c->stream));     // DgStatus and tfail among them
+        launch_normalize(c, p, true);                      // (no graph follows: nothing is written to matC)
         HIPCHK(c, hipGetLastError());
         if ((r = read_status(c))) return r;
         if ((c->h_st.err_flags & DG_E_NORM_OVF) && attempt < 3) {

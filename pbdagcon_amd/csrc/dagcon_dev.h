@@ -37,6 +37,7 @@
 #define DG_E_TOO_BIG     0x200u  // a target has more than 2^25-2 vertices
 #define DG_E_LOG_OVF     0x800u  // a segment appended more entries to enter's / exit's list than its slots hold (rerun with more)
 #define DG_E_LIST_OVF    0x400u  // more segments handed to k_merge_list than its worklist holds (rerun with a longer one)
+#define DG_E_RUN_WIDE    0x1000u // an insertion run longer than 255 columns met byte-wide matC cells (rerun with 32-bit cells)
 
 // failures of one target (its input, or an invariant of its graph): recorded in DgParams::tfail,
 // the batch goes on; everything else is a capacity problem of the whole batch (grow and re-run)
@@ -146,10 +147,12 @@ struct DgParams {
     int32_t *cov;                  // coverage (AlnGraphBoost.cpp:76,87)
     // ---- matrices [position][read] ----
     uint32_t *matA, *matD;         // arrival / departure
-    uint32_t *matC;                // [read][position] (row stride matc_stride): insertion run length in front of
-                                   // the position, then its exclusive prefix over reads
-    const uint64_t *matc_base;     // [T] offset of the target's K rows
-    const uint32_t *matc_stride;   // [T] (tlen + 2) rounded up to a multiple of 4 cells
+    void *matC;                    // [read][position] (row stride matc_stride): insertion run length in front of
+                                   // the position, then (k_groups) its exclusive prefix over reads.  Cells are uint8_t
+                                   // where p.emit_scan keeps the run lengths themselves (the kernels' <uint8_t>
+                                   // instances; a run of more than 255 columns raises DG_E_RUN_WIDE), uint32_t otherwise
+    const uint64_t *matc_base;     // [T] offset of the target's K rows, in cells
+    const uint32_t *matc_stride;   // [T] (tlen + 2) rounded up to a multiple of 8 cells
     // ---- vertex arena ----
     DgNode *nodes;
     int32_t *best, *queue;

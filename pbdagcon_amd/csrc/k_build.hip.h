@@ -62,8 +62,19 @@ __device__ __forceinline__ void dg_fail_aln(const DgParams &p, uint32_t a, uint3
 #define DG_NW_BIG 512u        // window of the second pass, for the chunks whose look-ahead outgrew the first
 #define DG_REDO 0xFFFFFFFFu   // n_hi marker: redo on the slow path
 
+// a matC cell: the length of a read's insertion run.  Byte cells hold up to 255: a longer run is not stored (nothing is
+// truncated) and the batch is flagged, dagcon_fetch then runs it again with 32-bit cells.
+template <typename CT>
+__device__ __forceinline__ void dg_store_run(const DgParams &p, CT *cell, const uint32_t run) {
+    if constexpr (sizeof(CT) == 1) {
+        if (run > 255u) { dg_fail(p, DG_E_RUN_WIDE); return; }
+    }
+    *cell = (CT)run;
+}
+
 // trimAln, column counts, conformity, insertion runs: what follows normalizeGaps for
-// both kernels.  buf holds the m final columns.
+// both kernels.  buf holds the m final columns.  CT: the matC cell type.
+template <typename CT>
 __device__ inline void dg_finish_alignment(const DgParams &p, uint32_t a, uint16_t *buf, uint32_t m) {
     // Alignment.cpp:219-242 trimAln (a no-op for trim == 0)
     const uint32_t trim = p.trim;
@@ -81,13 +92,13 @@ __device__ inline void dg_finish_alignment(const DgParams &p, uint32_t a, uint16
     // length per (position, read) numbers the inserted vertices
     const bool graph = !(p.flags & DG_F_A1_ONLY);
     uint32_t t_idx = 0, r = 0;
-    uint32_t *Cm = nullptr;
+    CT *Cm = nullptr;
     if (graph) {
         t_idx = p.aln_tgt[a];
         if (p.tactive[t_idx]) {
             const uint64_t ab = p.aln_begin[t_idx];
             r = (uint32_t)(a - ab);
-            Cm = p.matC + p.matc_base[t_idx] + (uint64_t)r * p.matc_stride[t_idx];   // the read's row
+            Cm = static_cast<CT *>(p.matC) + p.matc_base[t_idx] + (uint64_t)r * p.matc_stride[t_idx];   // the read's row
         }
     }
     const uint32_t tlen = graph ? p.tlen[t_idx] : 0xFFFFFFFFu;
@@ -101,7 +112,7 @@ __device__ inline void dg_finish_alignment(const DgParams &p, uint32_t a, uint16
         if (qb_ == tb_ || qb_ == DG_GAP) {                                                \
             if (Cm && conf && ((start + adv) & ((1u << p.emit_shift) - 1u)) == 0 && start + adv <= tlen + 1) \
                 ck[(start + adv) >> p.emit_shift] = ci_ - run;                            \
-            if (run) { if (Cm && conf && start + adv <= tlen + 1) Cm[start + adv] = run; run = 0; } \
+            if (run) { if (Cm && conf && start + adv <= tlen + 1) dg_store_run(p, Cm + (start + adv), run); run = 0; } \
             adv++; n_del += (qb_ != tb_);                                                 \
             if ((uint64_t)start - 1 + adv > (uint64_t)tlen) conf = false;                 \
         } else if (tb_ == DG_GAP) { n_ins++; run++; }                                     \
@@ -122,7 +133,7 @@ __device__ inline void dg_finish_alignment(const DgParams &p, uint32_t a, uint16
     while (i < hi) { const uint16_t c = buf[i]; DG_FIN_COL(c, i); i++; }
     if (run && Cm && conf && ((start + adv) & ((1u << p.emit_shift) - 1u)) == 0 && start + adv <= tlen + 1)
         ck[(start + adv) >> p.emit_shift] = hi - run;     // a trailing insertion run: the position after the read's last
-    if (run && Cm && conf && start + adv <= tlen + 1) Cm[start + adv] = run;
+    if (run && Cm && conf && start + adv <= tlen + 1) dg_store_run(p, Cm + (start + adv), run);
 #undef DG_FIN_COL
     p.n_lo[a] = lo; p.n_hi[a] = hi; p.n_start[a] = start;
     p.n_ins[a] = n_ins; p.n_del[a] = n_del;
@@ -434,8 +445,10 @@ __device__ __forceinline__ uint32_t dg_wave_excl(const uint32_t v, const int lan
 // (8 columns each, 512 per pass): the copy is coalesced loads and funnelled, aligned, coalesced stores; how many target
 // bases lie in front of a lane's columns is a prefix sum over the lanes, how long the insertion run in front of them is
 // a segmented one (reset at every lane that holds a match / deletion column); then every lane walks its own 8 columns
-// as dg_finish_alignment walks them all.
+// as dg_finish_alignment walks them all.  CT: the matC cell type (byte cells put four times as many of a row's runs into
+// a line).
 // ---------------------------------------------------------------------------
+template <typename CT>
 __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
     const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (g >= p.n_chunks) return;
@@ -454,10 +467,10 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
     uint16_t *dst = p.norm + p.norm_off[a] + o;                       // norm_off is a multiple of 8 columns
     const bool graph = !(p.flags & DG_F_A1_ONLY);
     uint32_t t_idx = 0;
-    uint32_t *Cm = nullptr;
+    CT *Cm = nullptr;
     if (graph) {
         t_idx = p.aln_tgt[a];
-        if (p.tactive[t_idx]) Cm = p.matC + p.matc_base[t_idx] + (uint64_t)(a - p.aln_begin[t_idx]) * p.matc_stride[t_idx];   // the read's row
+        if (p.tactive[t_idx]) Cm = static_cast<CT *>(p.matC) + p.matc_base[t_idx] + (uint64_t)(a - p.aln_begin[t_idx]) * p.matc_stride[t_idx];   // the read's row
     }
     const uint32_t tlen = graph ? p.tlen[t_idx] : 0xFFFFFFFFu;
     uint32_t *ck = p.ckpt + p.ck_base[a];
@@ -530,7 +543,7 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
                     // it may end in the insertion run that belongs to this position)
                     if (conf && ((start + adv) & ck_mask) == 0 && start + adv <= tlen + 1 && !(x == 0 && o > lo))
                         ck[(start + adv) >> p.emit_shift] = o + x - run;
-                    if (run && conf && start + adv <= tlen + 1) Cm[start + adv] = run;
+                    if (run && conf && start + adv <= tlen + 1) dg_store_run(p, Cm + (start + adv), run);
                     run = 0;
                     adv++;
                 } else if ((insm >> k) & 1u) run++;
@@ -545,7 +558,7 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
         if (lane == 0) {
             if (any && Cm && conf && ((start + adv) & ck_mask) == 0 && start + adv <= tlen + 1 && (o + f1 < hi || run))
                 ck[(start + adv) >> p.emit_shift] = o + f1 - run;
-            if (run && Cm && conf && start + adv <= tlen + 1) Cm[start + adv] = run;
+            if (run && Cm && conf && start + adv <= tlen + 1) dg_store_run(p, Cm + (start + adv), run);
             if (graph && any && !conf) dg_fail_aln(p, a, DG_E_NONCONF);
         }
     }
@@ -559,6 +572,7 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
 
 // The same algorithm with the whole expanded alignment in HBM: raw mode and
 // alignments whose look-ahead outgrew the LDS window.
+template <typename CT>
 __global__ __launch_bounds__(64) void k_normalize_slow(DgParams p) {
     const uint32_t a = blockIdx.x * 64 + threadIdx.x;
     if (a >= p.A) return;
@@ -613,7 +627,7 @@ __global__ __launch_bounds__(64) void k_normalize_slow(DgParams p) {
         }
         m = w;
     }
-    dg_finish_alignment(p, a, buf, m);
+    dg_finish_alignment<CT>(p, a, buf, m);
 }
 
 // ---------------------------------------------------------------------------
@@ -750,7 +764,7 @@ __global__ __launch_bounds__(256) void k_groups(DgParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t blen = p.tlen[t];
     const uint32_t K = (uint32_t)(p.aln_begin[t + 1] - p.aln_begin[t]);
-    uint32_t *col0 = p.matC + p.matc_base[t];
+    uint32_t *col0 = static_cast<uint32_t *>(p.matC) + p.matc_base[t];      // (always 32-bit cells: the prefix is taken in place)
     const uint32_t cstride = p.matc_stride[t];              // a multiple of 8: rows start 32-byte aligned
     uint32_t *gcount = p.gcount + p.bbv_base[t];
     // a wave takes 8 consecutive positions: a lane (= a read) loads and stores them as two 16-byte
@@ -901,19 +915,38 @@ __device__ __forceinline__ uint32_t dg_emit_fold(unsigned long long em, const ui
 // ---------------------------------------------------------------------------
 // k_gsum (p.emit_scan): gcount[p] = inserted vertices whose _bbMap is p = the column sum of the reads' run lengths; a
 // thread per position, the reads' rows read side by side (k_groups does the same and the prefix over the reads with it,
-// in place: where every target has at most a wave of reads k_emit takes that prefix itself)
+// in place: where every target has at most a wave of reads k_emit takes that prefix itself).  The kernel is bound by the
+// bytes it reads, so with byte cells (DgGsum::PPT positions per thread) it has a quarter of the work: a thread takes
+// four neighbouring positions with one 32-bit load per row (rows start 8-byte aligned and are padded with cleared cells
+// to a multiple of 8) and adds them up as two words of 16-bit pairs -- 64 reads x 255 stays below 2^16.
 // ---------------------------------------------------------------------------
+template <typename CT> struct DgGsum { static constexpr uint32_t PPT = sizeof(CT) == 1 ? 4u : 1u; };     // positions per thread
+template <typename CT>
 __global__ __launch_bounds__(256) void k_gsum(DgParams p) {
     const uint32_t t = blockIdx.x;
     if (dg_failed(p) || dg_tskip(p, t)) return;
-    const uint32_t pos = blockIdx.y * 256u + threadIdx.x;
-    if (pos >= p.tlen[t] + 2u) return;
+    const uint32_t pos = (blockIdx.y * 256u + threadIdx.x) * DgGsum<CT>::PPT;
+    const uint32_t np = p.tlen[t] + 2u;
+    if (pos >= np) return;
     const uint32_t K = (uint32_t)(p.aln_begin[t + 1] - p.aln_begin[t]);
-    const uint32_t *col = p.matC + p.matc_base[t] + pos;
+    const CT *col = static_cast<const CT *>(p.matC) + p.matc_base[t] + pos;
     const uint32_t stride = p.matc_stride[t];
-    uint32_t sum = 0;
-    for (uint32_t r = 0; r < K; r++) sum += col[(uint64_t)r * stride];
-    p.gcount[p.bbv_base[t] + pos] = sum;
+    uint32_t *gc = p.gcount + p.bbv_base[t] + pos;
+    if constexpr (sizeof(CT) == 1) {
+        uint32_t even = 0, odd = 0;                       // positions (pos, pos + 2) and (pos + 1, pos + 3), 16 bits each
+        for (uint32_t r = 0; r < K; r++) {
+            const uint32_t w = *reinterpret_cast<const uint32_t *>(col + (uint64_t)r * stride);
+            even += w & 0x00FF00FFu; odd += (w >> 8) & 0x00FF00FFu;
+        }
+        const uint32_t s[4] = {even & 0xFFFFu, odd & 0xFFFFu, even >> 16, odd >> 16};
+        // (a target's gcount cells start 16-byte aligned: bbv_base is a multiple of 4)
+        if (pos + 3u < np) *reinterpret_cast<uint4 *>(gc) = make_uint4(s[0], s[1], s[2], s[3]);
+        else for (uint32_t j = 0; pos + j < np; j++) gc[j] = s[j];
+    } else {
+        uint32_t sum = 0;
+        for (uint32_t r = 0; r < K; r++) sum += col[(uint64_t)r * stride];
+        *gc = sum;
+    }
 }
 
 #ifndef DG_EB
@@ -930,7 +963,10 @@ __global__ __launch_bounds__(256) void k_gsum(DgParams p) {
 #endif
 // (LDS, not registers, bounds the waves in flight here: 2 KB of departure cells + the staged columns.  48 / 40 / 32 / 24
 // columns -> 8.4 / 7.4 / 6.4 / 5.4 KB, 86 / 82 / 78 / 74 VGPRs, 5 / 5 / 6 / 6 waves per SIMD: build 10.08 / 9.85 / 9.97 / 10.01 ms)
+// CT: the matC cell type (uint8_t only with p.emit_scan: the cells are then run lengths, never prefixes)
+template <typename CT>
 __global__ __launch_bounds__(64) void k_emit(DgParams p) {
+    static_assert(sizeof(CT) == 4 || DG_EB == 8, "a batch of byte cells is one 8-byte load");
     __shared__ uint32_t s_D[DG_EB * 64];
     __shared__ uint16_t s_col[64 * DG_ECOLS_STRIDE];
     if (dg_failed(p)) return;
@@ -952,7 +988,7 @@ __global__ __launch_bounds__(64) void k_emit(DgParams p) {
     const uint32_t *bid = p.bid + bv, *gbase = p.gbase + bv;
     uint32_t *Am = p.matA + p.mat_base[t];
     uint32_t *Dm = p.matD + p.mat_base[t];
-    const uint32_t *Cm = p.matC + p.matc_base[t] + (uint64_t)(idle ? 0 : r) * p.matc_stride[t];   // the read's row
+    const CT *Cm = static_cast<const CT *>(p.matC) + p.matc_base[t] + (uint64_t)(idle ? 0 : r) * p.matc_stride[t];   // the read's row
     uint32_t *pool = p.pool + p.pool_base[t];
     DgNode *ndt = p.nodes + nb;
     // pool words / vertex records / matrix cells: uniform base + 32-bit byte offset (see k_merge)
@@ -1071,13 +1107,19 @@ __global__ __launch_bounds__(64) void k_emit(DgParams p) {
                 const uint4 v = gp[k];
                 gbv[4 * k] = v.x; gbv[4 * k + 1] = v.y; gbv[4 * k + 2] = v.z; gbv[4 * k + 3] = v.w;
             }
-            // (the row is padded to a multiple of 8 cells and pos0 is a multiple of 4: whole
-            // 16-byte pieces; what lies past the exit position is not used)
-            const uint4 *cp = reinterpret_cast<const uint4 *>(Cm + pos0);
+            // (the row is padded to a multiple of 8 cells and pos0 is a multiple of 8: whole
+            // 16-byte pieces, or one 8-byte piece of byte cells; what lies past the exit position is not used)
+            if constexpr (sizeof(CT) == 1) {
+                const uint2 v = *reinterpret_cast<const uint2 *>(Cm + pos0);
 #pragma unroll
-            for (int k = 0; k < DG_EB / 4; k++) {
-                const uint4 v = cp[k];
-                cmv[4 * k] = v.x; cmv[4 * k + 1] = v.y; cmv[4 * k + 2] = v.z; cmv[4 * k + 3] = v.w;
+                for (int k = 0; k < 8; k++) cmv[k] = ((k < 4 ? v.x : v.y) >> (8 * (k & 3))) & 0xFFu;
+            } else {
+                const uint4 *cp = reinterpret_cast<const uint4 *>(Cm + pos0);
+#pragma unroll
+                for (int k = 0; k < DG_EB / 4; k++) {
+                    const uint4 v = cp[k];
+                    cmv[4 * k] = v.x; cmv[4 * k + 1] = v.y; cmv[4 * k + 2] = v.z; cmv[4 * k + 3] = v.w;
+                }
             }
         }
         if (p.emit_scan) {

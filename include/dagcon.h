@@ -210,6 +210,55 @@ int dagcon_fetch_support(dagcon_ctx *ctx, dagcon_support *out); /* DAGCON_FLAG_B
 int dagcon_fetch_positions(dagcon_ctx *ctx, const uint32_t **pos, uint64_t *n);
 
 /*
+ * Edits: where the consensus differs from its target (off by default; a context switch like dagcon_set_record_filter,
+ * on a context created with DAGCON_FLAG_BASE_POS).  The reference has no such output: this is this build's own
+ * definition, PARITY UNPINNED.  The device derives the list from the best path itself, nothing is aligned: a consensus
+ * base comes from a backbone vertex (a target base kept) or from an inserted vertex (a base added), and a target
+ * position that lies between two consecutive backbone bases of the path and is neither is a base dropped.
+ * Segment s of the results lies on a target of a record upload (with windows: on a window, and every position below
+ * is relative to the window, whose bases are t_blob[t_off + begin ..]).  Its bases are i = 0 .. n - 1; those from a
+ * backbone vertex are j_0 < .. < j_m with the 1-based target positions P (dagcon_fetch_positions), which rise strictly.
+ *   - span: seg_t0 = P(j_0) - 1, seg_t1 = P(j_m), 0-based half-open [t0, t1); a segment without a backbone base has
+ *     t0 = t1 = (the position of its first base) - 1;
+ *   - one raw edit per pair of consecutive backbone bases j_a, j_b with inserted bases between them (j_b - j_a > 1) or
+ *     target bases skipped (P(j_b) - P(j_a) > 1): it replaces target bases [P(j_a), P(j_b) - 1) (0-based) by the
+ *     consensus bases (j_a, j_b);
+ *   - the inserted bases in front of j_0 are an insertion at t0, those behind j_m an insertion at t1, a segment
+ *     without a backbone base is one insertion at t0;
+ *   - trim: equal leading bytes of the replaced target bytes and the replacing bytes are taken off both (exact bytes,
+ *     case counts) and both starts advance, then equal trailing bytes; an edit with nothing left on either side is
+ *     dropped.
+ * Edits of segment s are e in [edit_begin[s], edit_begin[s + 1]), in ascending target order and disjoint: target
+ * bases [t_pos, t_pos + t_len) become seq_blob[c_off, c_off + c_len).  c_off is defined also when c_len == 0: the index
+ * of the consensus base the deletion stands in front of (seq_off[s] + seq_len[s] cannot occur: a segment's last edit
+ * with c_len == 0 lies in front of j_m).  Where a target's bases lie in seq_blob is not fixed from run to run (seq_off
+ * says where), so c_off is reproducible as c_off - seq_off[s], not as a number.
+ * INVARIANT: walking the target's bases [seg_t0, seg_t1) and replacing [t_pos, t_pos + t_len) by seq_blob[c_off,
+ * c_off + c_len) for every edit of s yields the segment's sequence exactly.  It rests on: the byte of a backbone base
+ * is its target byte (an 'N' backbone is filled from tstr, which the record intake copies from t_blob).  That holds
+ * for every backbone vertex a read passes through, so for every base a min_weight of 2 or more lets out.
+ * dagcon_set_edits: DAGCON_ERR_STATE on a context without DAGCON_FLAG_BASE_POS.  The switch holds for every later
+ * dagcon_upload_cigar* / _packed / _strand / dagcon_upload_cs (and the dagcon_consensus_* of those); with it off no
+ * kernel, buffer or copy differs from a context that never heard of it.  With it on, three more kernels run behind the
+ * consensus (csrc/k_edits.hip.h), the edit arrays come back in the fetch's second round, and the 4 bytes a base of
+ * dagcon_fetch_positions are copied only when that is called.
+ * dagcon_fetch_edits is valid after a fetch that followed such an upload with the switch on; DAGCON_ERR_STATE
+ * otherwise: switch off, dagcon_consensus / dagcon_consensus_pre (no single target on the device), before a fetch, or
+ * under DAGCON_FLAG_STOP_AFTER_BUILD / _MERGE.  A failed target has no segments and no edits.  The arrays are owned by
+ * the context, valid as long as the results of the same fetch (as dagcon_support).
+ */
+typedef struct dagcon_edits {
+    uint64_t n_segments, n;              /* n_segments == dagcon_results.n_segments */
+    const uint32_t *seg_t0, *seg_t1;     /* [n_segments] */
+    const uint64_t *edit_begin;          /* [n_segments + 1] */
+    const uint32_t *t_pos, *t_len;       /* [n] */
+    const uint64_t *c_off;               /* [n] into seq_blob */
+    const uint32_t *c_len;               /* [n] */
+} dagcon_edits;
+int dagcon_set_edits(dagcon_ctx *ctx, int on);
+int dagcon_fetch_edits(dagcon_ctx *ctx, dagcon_edits *out);
+
+/*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses
  * alignment records straight into such a buffer gets its dagcon_upload at link speed instead of
  * through the driver's staging copies.  Optional: any host memory is accepted by dagcon_upload.

@@ -41,6 +41,7 @@ EXPORTS = [
     "dagcon_upload_cigar_strand", "dagcon_consensus_cigar_strand",
     "dagcon_upload_cs", "dagcon_consensus_cs",
     "dagcon_set_record_filter", "dagcon_fetch_record_stats",
+    "dagcon_set_edits", "dagcon_fetch_edits",
 ]
 ABI_VERSION = 2
 
@@ -115,6 +116,14 @@ class RecordStats(C.Structure):
 FATE_MAX_ERROR, FATE_MAX_DEPTH, FATE_NONCONFORMING = 1, 2, 4
 
 
+class Edits(C.Structure):
+    """dagcon_edits: per segment its target span and its edits (include/dagcon.h has the definition)."""
+    _fields_ = [("n_segments", C.c_uint64), ("n", C.c_uint64), ("seg_t0", C.POINTER(C.c_uint32)),
+                ("seg_t1", C.POINTER(C.c_uint32)), ("edit_begin", C.POINTER(C.c_uint64)),
+                ("t_pos", C.POINTER(C.c_uint32)), ("t_len", C.POINTER(C.c_uint32)),
+                ("c_off", C.POINTER(C.c_uint64)), ("c_len", C.POINTER(C.c_uint32))]
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_normalize", C.c_float), ("ms_build", C.c_float),
                 ("ms_merge", C.c_float), ("ms_bestpath", C.c_float),
@@ -184,6 +193,8 @@ def load() -> C.CDLL:
     L.dagcon_consensus_cigar_strand.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), vp, C.POINTER(Results)]
     L.dagcon_set_record_filter.argtypes = [vp, C.POINTER(RecordFilter)]
     L.dagcon_fetch_record_stats.argtypes = [vp, C.POINTER(RecordStats)]
+    L.dagcon_set_edits.argtypes = [vp, C.c_int]
+    L.dagcon_fetch_edits.argtypes = [vp, C.POINTER(Edits)]
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
     L.dagcon_host_free.restype = None
@@ -704,6 +715,24 @@ class Context:
             return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
         return {"match": arr(st.match, np.uint32), "mismatch": arr(st.mismatch, np.uint32), "ins": arr(st.ins, np.uint32),
                 "del": arr(st.del_, np.uint32), "fate": arr(st.fate, np.uint8)}
+
+    def set_edits(self, on=True):
+        """dagcon_set_edits for every later record call (a FLAG_BASE_POS context): the device lists where each segment
+        differs from its target (edits())."""
+        self._chk(self.L.dagcon_set_edits(self.h, 1 if on else 0))
+
+    def edits(self) -> dict:
+        """dagcon_fetch_edits (copies): seg_t0, seg_t1 (uint32, one per segment of the last results, in their order),
+        edit_begin (uint64, one more), and per edit t_pos, t_len, c_len (uint32) and c_off (uint64, into seq_blob)."""
+        e = Edits()
+        self._chk(self.L.dagcon_fetch_edits(self.h, C.byref(e)))
+        S, n = int(e.n_segments), int(e.n)
+
+        def arr(ptr, k, dt):
+            return np.ctypeslib.as_array(ptr, shape=(k,)).copy() if k else np.zeros(0, dt)
+        return {"seg_t0": arr(e.seg_t0, S, np.uint32), "seg_t1": arr(e.seg_t1, S, np.uint32),
+                "edit_begin": arr(e.edit_begin, S + 1, np.uint64), "t_pos": arr(e.t_pos, n, np.uint32),
+                "t_len": arr(e.t_len, n, np.uint32), "c_off": arr(e.c_off, n, np.uint64), "c_len": arr(e.c_len, n, np.uint32)}
 
     def timings(self) -> dict:
         t = Timings()

@@ -28,6 +28,7 @@
 #include "k_cigar.hip.h"
 #include "k_rate.hip.h"
 #include "k_cs.hip.h"
+#include "k_edits.hip.h"
 
 namespace {
 
@@ -117,6 +118,7 @@ struct StatBlock {
     char *host = nullptr;
     size_t host_cap = 0;
     size_t o_tfail = 0, o_cns_len = 0, o_n_seg = 0, o_cns_off = 0, o_seg_first = 0;     // (DgStatus at 0)
+    size_t o_ed_top = 0;                            // edits of the batch, behind seg_first (a batch with edits on only; 0: none)
     size_t zero_bytes = 0, bytes = 0;
     template <typename X> X *d(size_t off) const { return reinterpret_cast<X *>(static_cast<char *>(dev.p) + off); }
     template <typename X> const X *h(size_t off) const { return reinterpret_cast<const X *>(host + off); }
@@ -183,6 +185,13 @@ struct Ctx {
     DevBuf d_seg;                                   // seg_r0[seg_cap], then seg_r1 at seg_stride() entries
     DevBuf d_pos_tmp, d_pos_tmp0, d_pos;           // DAGCON_FLAG_BASE_POS: walk scratch (4 B per vertex), output (4 B per base)
     DevBuf d_sup_tmp, d_sup_tmp0, d_sup;           // DAGCON_FLAG_BASE_SUPPORT: walk scratch (4 B per vertex), output (2 x 2 B per base)
+    // dagcon_set_edits: the switch; whether the batch on the device is a record upload made under it; its buffers
+    // (a DgEdSeg per segment, a DgEdit per edit, where each target's bases begin in cg.t)
+    bool edits_on = false, ed_batch = false;
+    DevBuf d_ed_seg, d_ed_out, d_ed_tbase;
+    std::vector<uint64_t> h_ed_tbase;
+    uint64_t ed_cap = 0;
+    long ed_cap_env = 0;                            // DAGCON_EDITS_CAP (tests): first size of the edit arena, so that the re-run is met
 
     uint64_t norm_cap = 0, node_cap = 0, pool_cap = 0, cns_cap = 0, seg_cap = 0;
     uint32_t stk_words = 4096, growth_pct = 100, seg_max = 8, bp_max = 16, seg_env = 0, seg_min = 768;    // (scratch per target and segment: grown x4 and re-run on DG_E_STACK)
@@ -208,6 +217,13 @@ struct Ctx {
     uint64_t r_sup_n = 0;
     std::vector<uint32_t> r_pos;        // DAGCON_FLAG_BASE_POS: [seq_bytes] _bbMap of every consensus base
     bool pos_valid = false;
+    bool pos_pending = false;           // edits on: the positions stay on the device until dagcon_fetch_positions asks for them
+    uint64_t r_nb = 0;                  // seq_bytes of the last fetch
+    char *r_ed = nullptr;               // page-locked: the DgEdSeg records of the last fetch, then its DgEdit records
+    size_t r_ed_cap = 0;
+    bool ed_valid = false;              // the arrays below are those of the last fetch (dagcon_fetch_edits)
+    std::vector<uint32_t> e_t0, e_t1, e_tpos, e_tlen, e_clen;
+    std::vector<uint64_t> e_begin, e_coff;
     bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
 
     // debug dump storage
@@ -289,6 +305,8 @@ int ensure_stat(Ctx *c, uint32_t T) {
     b.o_cns_off = b.zero_bytes;
     b.o_seg_first = b.o_cns_off + up16((size_t)T * 8);
     b.bytes = b.o_seg_first + up16((size_t)T * 8);
+    b.o_ed_top = 0;
+    if (c->ed_batch) { b.o_ed_top = b.bytes; b.bytes += 16; }
     ENSURE(c, b.dev, b.bytes);
     if (b.host_cap < b.bytes) {
         if (b.host) (void)hipHostFree(b.host);
@@ -338,6 +356,10 @@ int ensure_arenas(Ctx *c) {
         ENSURE(c, c->d_pos_tmp, c->node_cap * 4);
         if (c->gcuts) ENSURE(c, c->d_pos_tmp0, c->node_cap * 4);
         ENSURE(c, c->d_pos, c->cns_cap * 4);
+    }
+    if (c->ed_batch) {
+        ENSURE(c, c->d_ed_seg, c->seg_cap * sizeof(DgEdSeg));
+        ENSURE(c, c->d_ed_out, c->ed_cap * sizeof(DgEdit));
     }
     ENSURE(c, c->d_seg, 2 * seg_stride(c) * 4);
     if (c->r_seg_cap < c->seg_cap) {
@@ -425,6 +447,11 @@ void fill_params(Ctx *c, DgParams &p) {
     if (c->opts.flags & DAGCON_FLAG_BASE_POS) {
         p.pos_tmp = (uint32_t *)c->d_pos_tmp.p; p.pos_tmp0 = (uint32_t *)c->d_pos_tmp0.p; p.pos_out = (uint32_t *)c->d_pos.p;
     }
+    if (c->ed_batch) {
+        p.ed_seg = (DgEdSeg *)c->d_ed_seg.p; p.ed_out = (DgEdit *)c->d_ed_out.p; p.ed_cap = c->ed_cap;
+        p.ed_top = c->sb.d<unsigned long long>(c->sb.o_ed_top);
+        p.ed_t = (const uint8_t *)c->cg.t.p; p.ed_tbase = (const uint64_t *)c->d_ed_tbase.p;
+    }
 }
 
 // stage a1: count, chunked normalizeGaps + trimAln, and the sequential kernel for what is left
@@ -461,7 +488,8 @@ int launch_all(Ctx *c) {
                           &c->d_gbase, &c->d_bid, &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_stk, &c->d_cuts,
                           &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_wl_first,
                           &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns,
-                          &c->d_seg, &c->d_worklist, &c->d_seg_done, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup, &c->d_pos_tmp, &c->d_pos_tmp0, &c->d_pos};
+                          &c->d_seg, &c->d_worklist, &c->d_seg_done, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup, &c->d_pos_tmp, &c->d_pos_tmp0, &c->d_pos,
+                          &c->d_ed_seg, &c->d_ed_out};
         for (DevBuf *b : work)
             if (b->p && b->cap) HIPCHK(c, hipMemsetAsync(b->p, 0xEE, b->cap, s));
         // (cns_off and seg_first: the part of the status block that is not cleared below)
@@ -554,6 +582,13 @@ int launch_all(Ctx *c) {
         }
         DG_BP_LAUNCH(k_bp_join, dim3(c->T));
 #undef DG_BP_LAUNCH
+        if (c->ed_batch) {
+            // the edits (k_edits.hip.h): count, place, write; a wave per segment of the arena (seg_top is the device's)
+            const dim3 eg((uint32_t)((c->seg_cap + 3) / 4));
+            hipLaunchKernelGGL(k_ed_scan_seg<false>, eg, dim3(256), 0, s, p);
+            hipLaunchKernelGGL(k_ed_scan, dim3(1), dim3(1024), 0, s, p);
+            hipLaunchKernelGGL(k_ed_scan_seg<true>, eg, dim3(256), 0, s, p);
+        }
     }
     HIPCHK(c, hipEventRecord(c->ev[4], s));
     HIPCHK(c, hipGetLastError());
@@ -604,6 +639,7 @@ int dagcon_create(const dagcon_opts *opts, dagcon_ctx **out) {
     if (const char *e = getenv("DAGCON_BP_LANE")) c->bp_lane = atoi(e);
     if (const char *e = getenv("DAGCON_BP_LANE_STACK")) c->bl_stk = atoi(e);
     if (const char *e = getenv("DAGCON_MERGE_Q")) c->merge_q = atoi(e) != 0;     // eight segments per wave (k_merge_q.hip.h)
+    if (const char *e = getenv("DAGCON_EDITS_CAP")) c->ed_cap_env = atol(e);
     memset(&c->tm, 0, sizeof c->tm);
     memset(&c->h_st, 0, sizeof c->h_st);
     if (hipSetDevice(c->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -625,6 +661,7 @@ void dagcon_destroy(dagcon_ctx *ctx) {
     if (c->r_blob) (void)hipHostFree(c->r_blob);
     if (c->r_sup) (void)hipHostFree(c->r_sup);
     if (c->r_seg) (void)hipHostFree(c->r_seg);
+    if (c->r_ed) (void)hipHostFree(c->r_ed);
     if (c->sb.host) (void)hipHostFree(c->sb.host);
     DevBuf *all[] = {&c->d_q, &c->d_t, &c->d_aln_off, &c->d_aln_len, &c->d_aln_start, &c->d_aln_tgt,
                      &c->d_tlen, &c->d_aln_begin, &c->d_tactive, &c->sb.dev, &c->d_bb, &c->d_bb_off, &c->d_mat_base, &c->d_matc_base, &c->d_matc_stride,
@@ -633,7 +670,8 @@ void dagcon_destroy(dagcon_ctx *ctx) {
                      &c->d_pool_base, &c->d_pool_size, &c->d_pool_top, &c->d_t_nins, &c->d_matA, &c->d_matD,
                      &c->d_matC, &c->d_cov, &c->d_gcount, &c->d_gbase, &c->d_bid, &c->d_nodes,
                      &c->d_best, &c->d_queue, &c->d_score, &c->d_cns_tmp, &c->d_bp_tt, &c->d_score_b, &c->d_pool, &c->d_stk, &c->d_cuts, &c->d_cuts_bp, &c->d_bp_stat, &c->d_bp_len, &c->d_worklist, &c->d_rd, &c->d_pro_state, &c->d_sh_cnt, &c->d_seg_done, &c->d_wl_first, &c->d_queue0, &c->d_bp_end, &c->d_bp_ab, &c->d_defer, &c->d_cns_tmp0, &c->d_cns,
-                     &c->d_seg, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup, &c->d_pos_tmp, &c->d_pos_tmp0, &c->d_pos};
+                     &c->d_seg, &c->d_sup_tmp, &c->d_sup_tmp0, &c->d_sup, &c->d_pos_tmp, &c->d_pos_tmp0, &c->d_pos,
+                     &c->d_ed_seg, &c->d_ed_out, &c->d_ed_tbase};
     for (DevBuf *b : all) free_buf(*b);
     for (DevBuf &b : c->d_al) free_buf(b);
     for (DevBuf &b : c->d_pn) free_buf(b);
@@ -651,6 +689,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
     c->sup_valid = c->pos_valid = false;
+    c->ed_batch = c->ed_valid = c->pos_pending = false;     // (a record upload with edits on says so after the hand-over)
     c->h_cig_bad.clear();
     c->rs_valid = false;
     c->wide_cells = false;                             // (one batch with a very long insertion run does not slow the ones after it)
@@ -850,6 +889,7 @@ int dagcon_run(dagcon_ctx *ctx) {
     int r = launch_all(c);
     if (r != DAGCON_OK) return r;
     c->ran = true; c->fetched = false;
+    c->ed_valid = c->pos_pending = false;
     // debugging aid (tools/bp_pieces.py): DAGCON_DUMP=<target>:<path> leaves that target's merged graph, its bestPath cuts,
     // scores and choices in a file -- N, bp_max, pool words, then cuts row, records, pool, (score, final) pairs, best[]
     if (const char *e = getenv("DAGCON_DUMP")) {
@@ -937,6 +977,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         if (f & DG_E_LIST_OVF) c->worklist_cap *= 4;
         if (f & DG_E_LOG_OVF) c->sh_log *= 2;
         if (f & DG_E_RUN_WIDE) c->wide_cells = true;       // (until the next upload)
+        if ((f & DG_E_ED_OVF) && sb.o_ed_top) c->ed_cap = *sb.h<uint64_t>(sb.o_ed_top) + 1024;
         if (f & DG_E_OUT_OVF) {
             c->cns_cap = std::max<uint64_t>(c->cns_cap, c->h_st.cns_top + 1024);
             c->seg_cap = std::max<uint64_t>(c->seg_cap, c->h_st.seg_top + 1024);
@@ -990,7 +1031,21 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     c->r_blob[nb] = 0;
     const bool full = !(c->opts.flags & (DAGCON_FLAG_STOP_AFTER_BUILD | DAGCON_FLAG_STOP_AFTER_MERGE));
     const bool want_sup = full && (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT), want_pos = full && (c->opts.flags & DAGCON_FLAG_BASE_POS);
+    // edits on: the edits come instead of the positions, which stay on the device for dagcon_fetch_positions to ask for
+    const bool want_ed = full && c->ed_batch, lazy_pos = want_pos && want_ed;
+    const uint64_t n_ed = want_ed && T ? *sb.h<uint64_t>(sb.o_ed_top) : 0;
+    if (n_ed > c->ed_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu edits in an arena of %llu", (unsigned long long)n_ed, (unsigned long long)c->ed_cap);
     c->sup_valid = c->pos_valid = false;
+    c->ed_valid = c->pos_pending = false;
+    c->r_nb = nb;
+    const size_t ed_seg_bytes = (size_t)nseg * sizeof(DgEdSeg), ed_bytes = ed_seg_bytes + (size_t)n_ed * sizeof(DgEdit);
+    if (want_ed && c->r_ed_cap < ed_bytes + 1) {
+        if (c->r_ed) (void)hipHostFree(c->r_ed);
+        c->r_ed = nullptr; c->r_ed_cap = 0;
+        const size_t want = ed_bytes + ed_bytes / 8 + 4096;
+        HIPCHK(c, hipHostMalloc((void **)&c->r_ed, want, hipHostMallocDefault));
+        c->r_ed_cap = want;
+    }
     if (want_sup && c->r_sup_cap < nb + 1) {
         if (c->r_sup) (void)hipHostFree(c->r_sup);
         c->r_sup = nullptr; c->r_sup_cap = 0;
@@ -998,7 +1053,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         HIPCHK(c, hipHostMalloc((void **)&c->r_sup, want * 4, hipHostMallocDefault));
         c->r_sup_cap = want;
     }
-    if (want_pos) c->r_pos.resize(nb + 1);
+    if (want_pos && !lazy_pos) c->r_pos.resize(nb + 1);
     // round 2: what the status sizes -- the segments' ranges (the first seg_top entries of either array), the blob, the
     // support (weights then depths: the device keeps them apart, no host pass over them) and the positions -- enqueued
     // together, one wait
@@ -1015,10 +1070,22 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         HIPCHK(c, hipMemcpyAsync(c->r_sup + nb, (const uint16_t *)c->d_sup.p + c->cns_cap, nb * 2, hipMemcpyDeviceToHost, c->stream));
         queued = true;
     }
-    if (want_pos && nb) { HIPCHK(c, hipMemcpyAsync(c->r_pos.data(), c->d_pos.p, nb * 4, hipMemcpyDeviceToHost, c->stream)); queued = true; }
+    if (want_pos && !lazy_pos && nb) { HIPCHK(c, hipMemcpyAsync(c->r_pos.data(), c->d_pos.p, nb * 4, hipMemcpyDeviceToHost, c->stream)); queued = true; }
+    if (want_ed && T && nseg) {
+        HIPCHK(c, hipMemcpyAsync(c->r_ed, c->d_ed_seg.p, ed_seg_bytes, hipMemcpyDeviceToHost, c->stream));
+        if (n_ed) HIPCHK(c, hipMemcpyAsync(c->r_ed + ed_seg_bytes, c->d_ed_out.p, (size_t)n_ed * sizeof(DgEdit), hipMemcpyDeviceToHost, c->stream));
+        queued = true;
+    }
     if (queued) HIPCHK(c, hipStreamSynchronize(c->stream));
     if (want_sup) { c->r_sup_n = nb; c->sup_valid = true; }
-    if (want_pos) c->pos_valid = true;
+    if (want_pos && !lazy_pos) c->pos_valid = true;
+    c->pos_pending = lazy_pos;
+    const DgEdSeg *m_es = reinterpret_cast<const DgEdSeg *>(c->r_ed);
+    const DgEdit *m_ed = reinterpret_cast<const DgEdit *>(c->r_ed + ed_seg_bytes);
+    if (want_ed) {
+        c->e_t0.clear(); c->e_t1.clear(); c->e_begin.clear();
+        c->e_tpos.clear(); c->e_tlen.clear(); c->e_clen.clear(); c->e_coff.clear();
+    }
     c->r_seg_begin.assign(T + 1, 0);
     c->r_range0.clear(); c->r_range1.clear(); c->r_seq_off.clear(); c->r_seq_len.clear();
     uint64_t bases = 0;
@@ -1032,8 +1099,21 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
             c->r_seq_off.push_back(m_cns_off[t] + (uint64_t)r0);
             c->r_seq_len.push_back((uint32_t)(r1 - r0));
             bases += (uint64_t)(r1 - r0);
+            if (want_ed) {
+                // the segment's record and its edits, from the device's order into the host's
+                const DgEdSeg &es = m_es[s];
+                if (es.tgt != t || es.off > n_ed || es.cnt > n_ed - es.off)
+                    return fail(c, DAGCON_ERR_INTERNAL, "k_ed_scan: segment %llu of target %u has edits [%llu, + %u) of %llu, target %u",
+                                (unsigned long long)s, t, (unsigned long long)es.off, es.cnt, (unsigned long long)n_ed, es.tgt);
+                c->e_t0.push_back(es.t0); c->e_t1.push_back(es.t1); c->e_begin.push_back(c->e_tpos.size());
+                for (uint32_t k = 0; k < es.cnt; k++) {
+                    const DgEdit &e = m_ed[es.off + k];
+                    c->e_tpos.push_back(e.t_pos); c->e_tlen.push_back(e.t_len); c->e_coff.push_back(e.c_off); c->e_clen.push_back(e.c_len);
+                }
+            }
         }
     }
+    if (want_ed) { c->e_begin.push_back(c->e_tpos.size()); c->ed_valid = true; }
     c->r_seg_begin[T] = c->r_range0.size();
     c->tm.consensus_bases = bases;
     c->tm.algorithmic_bytes = 2ull * c->sum_len + bases;
@@ -1070,10 +1150,39 @@ int dagcon_fetch_positions(dagcon_ctx *ctx, const uint32_t **pos, uint64_t *n) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (!(c->opts.flags & DAGCON_FLAG_BASE_POS))
         return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_positions on a context created without DAGCON_FLAG_BASE_POS");
+    if (c->pos_pending) {
+        // edits on: the copy dagcon_fetch left out; the kind bit the edit kernels read stays on the device
+        HIPCHK(c, hipSetDevice(c->device));
+        c->r_pos.resize(c->r_nb + 1);
+        if (c->r_nb) HIPCHK(c, d2h(c, c->r_pos.data(), c->d_pos.p, c->r_nb * 4));
+        for (uint64_t i = 0; i < c->r_nb; i++) c->r_pos[i] &= ~DG_POS_BB;
+        c->pos_pending = false; c->pos_valid = true;
+    }
     if (!c->pos_valid)
         return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_positions without the results of a consensus (no fetch yet, or stopped before bestPath)");
     *pos = c->r_pos.data();
     *n = c->r_pos.size() - 1;
+    return DAGCON_OK;
+}
+
+int dagcon_set_edits(dagcon_ctx *ctx, int on) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!(c->opts.flags & DAGCON_FLAG_BASE_POS))
+        return fail(c, DAGCON_ERR_STATE, "dagcon_set_edits on a context created without DAGCON_FLAG_BASE_POS");
+    c->edits_on = on != 0;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_edits(dagcon_ctx *ctx, dagcon_edits *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->edits_on || !c->ed_valid)
+        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_edits without the results of a record upload made with dagcon_set_edits on (edits off, "
+                                         "another kind of upload, no fetch yet, or stopped before bestPath)");
+    out->n_segments = c->e_t0.size(); out->n = c->e_tpos.size();
+    out->seg_t0 = c->e_t0.data(); out->seg_t1 = c->e_t1.data(); out->edit_begin = c->e_begin.data();
+    out->t_pos = c->e_tpos.data(); out->t_len = c->e_tlen.data(); out->c_off = c->e_coff.data(); out->c_len = c->e_clen.data();
     return DAGCON_OK;
 }
 
@@ -1775,6 +1884,7 @@ Ctx *intake_reset(dagcon_ctx *ctx) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->uploaded = c->ran = c->fetched = false;
     c->sup_valid = c->pos_valid = false;
+    c->ed_batch = c->ed_valid = c->pos_pending = false;
     return c;
 }
 
@@ -2207,6 +2317,23 @@ int cigar_hand_over(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const 
     return DAGCON_OK;
 }
 
+// dagcon_set_edits: the batch the hand-over left is one whose edits the run is to report.  Each of the pipeline's targets
+// gets the place of its first base in cg.t (a window's: its target's, plus its begin), the status block a word for the
+// edit count, the arena a first size (grown by the re-run when DG_E_ED_OVF says so)
+int edits_arm(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
+    const uint32_t T = c->T;
+    c->h_ed_tbase.assign(T, 0);
+    for (uint32_t t = 0; t < T; t++) c->h_ed_tbase[t] = wn ? b->t_off[wn->target[t]] + wn->begin[t] : b->t_off[t];
+    c->ed_batch = true;
+    c->ed_cap = c->ed_cap_env > 0 ? (uint64_t)c->ed_cap_env : std::max<uint64_t>(c->ed_cap, c->sum_bb / 8 + 1024);
+    int r;
+    if ((r = upload_vec(c, c->d_ed_tbase, c->h_ed_tbase))) return r;
+    if ((r = ensure_stat(c, T))) return r;
+    if ((r = ensure_arenas(c))) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DAGCON_OK;
+}
+
 // SAM-style input: position + ungapped read + CIGAR per record, target bases once per target.  k_cigar_scan sizes every
 // record, the host plans the string blobs as for any batch, the expansion writes them into d_q / d_t, and upload_impl
 // takes them from there.  wn NULL: whole targets.  The strings never exist on the host.
@@ -2227,7 +2354,8 @@ int upload_records(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_wi
     CigarPlan pl;
     if ((r = wn ? plan_windows(c, b, wn, sc, v, pk, pl) : plan_whole(c, b, sc, v, pk, pl))) return r;
     if ((r = cigar_expand(c, b, src, sc, pl))) return r;
-    return cigar_hand_over(ctx, c, b, pl, v, pk);
+    if ((r = cigar_hand_over(ctx, c, b, pl, v, pk))) return r;
+    return c->edits_on ? edits_arm(c, b, wn) : DAGCON_OK;
 }
 
 // minimap2's cs:Z: text per record, the target's bases once per target (include/dagcon.h has the rule).  k_cs_scan sizes

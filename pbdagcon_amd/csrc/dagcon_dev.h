@@ -38,6 +38,7 @@
 #define DG_E_LOG_OVF     0x800u  // a segment appended more entries to enter's / exit's list than its slots hold (rerun with more)
 #define DG_E_LIST_OVF    0x400u  // more segments handed to k_merge_list than its worklist holds (rerun with a longer one)
 #define DG_E_RUN_WIDE    0x1000u // an insertion run longer than 255 columns met byte-wide matC cells (rerun with 32-bit cells)
+#define DG_E_ED_OVF      0x2000u // edit arena too small (dagcon_set_edits; rerun with *DgParams::ed_top)
 
 // failures of one target (its input, or an invariant of its graph): recorded in DgParams::tfail,
 // the batch goes on; everything else is a capacity problem of the whole batch (grow and re-run)
@@ -217,6 +218,28 @@ struct DgParams {
     uint32_t *pos_tmp;             // [node_cap] parallel to cns_tmp: _bbMap of each path base of a walk piece
     uint32_t *pos_tmp0;            // [node_cap] (p.gcuts) parallel to cns_tmp0
     uint32_t *pos_out;             // [cns_cap] parallel to cns: _bbMap of each kept consensus base
+    // Bit 31 of a pos_tmp / pos_tmp0 word (DG_POS_BB) says that the base's vertex is a backbone vertex: the walks set it,
+    // k_bp_join clears it on the way to pos_out unless the edit kernels are to read it there (ed_seg != NULL)
+    // ---- edits (dagcon_set_edits on a record upload; NULL / 0 otherwise): k_edits.hip.h ----
+    struct DgEdSeg *ed_seg;        // [seg_cap] one record per segment, in the order of seg_r0 / seg_r1
+    struct DgEdit *ed_out;         // [ed_cap] the edits, segments in host order (target, then segment)
+    uint64_t ed_cap;
+    unsigned long long *ed_top;    // edits of the batch (k_ed_scan; in the status block)
+    const uint8_t *ed_t;           // the record intake's target blob
+    const uint64_t *ed_tbase;      // [T] where a target's (a window's) first base lies in it
+};
+#define DG_POS_BB 0x80000000u
+
+struct __attribute__((aligned(16))) DgEdSeg {
+    uint32_t tgt;                  // the segment's target (k_bp_join)
+    uint32_t cnt;                  // its edits, after the trim (k_ed_scan_seg<false>)
+    uint32_t t0, t1;               // its target span [t0, t1)
+    unsigned long long off;        // its first edit in ed_out (k_ed_scan)
+    unsigned long long pad;
+};
+struct DgEdit {
+    unsigned long long c_off;      // into cns
+    uint32_t t_pos, t_len, c_len, pad;
 };
 
 // slots a backbone vertex gets for each of its two lists before it has to move to the

@@ -61,6 +61,7 @@ struct Opts {
     unsigned window = 0, overlap = 1000;   // --window W [--overlap O] (MODE_RECORDS): targets cut into windows (windows.h)
     bool overlap_set = false;
     DgPick pick;                       // --max-error F, --max-depth N (MODE_RECORDS): the records are picked on the device
+    std::string edits;                 // --edits FILE (MODE_RECORDS): where every record differs from its target
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
     int pinned = -1;                   // --pinned 0|1: page-locked blobs (-1: when the input is several batches long)
@@ -75,7 +76,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N]] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE]] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -139,6 +140,13 @@ void usage(FILE *f) {
             "                      per window) go into the graph, those with the most matching columns, in their own order; 1..4094.\n"
             "                      -c counts what is left.  With it a target or window of any depth can be run.  Both flags end\n"
             "                      with one line on stderr that counts the records each left out\n"
+            "  --edits FILE        with --sam, --bam or --paf, with or without --window: FILE lists where every record\n"
+            "                      differs from its target.  A line '#piece RNAME t0 t1' per record, in output order, with the\n"
+            "                      target span [t0, t1) the record covers, then one line per edit: RNAME, begin, end (0-based,\n"
+            "                      half-open target coordinates), REF, ALT, tab-separated, '-' for an empty side.  The edits\n"
+            "                      applied to ref[t0:t1] give the record's sequence.  The list comes from the GPU, read off\n"
+            "                      the best path itself, nothing is aligned again; stdout does not change.  This build's own\n"
+            "                      rule, parity unpinned\n"
             "  --fastq             write FASTQ (@id/r0_r1, sequence, +, qualities) instead of FASTA; the same records in the\n"
             "                      same order.  The quality of a base is this build's own definition: a Laplace-smoothed\n"
             "                      fraction of the reads at its position that do not pass through its consensus vertex,\n"
@@ -189,6 +197,10 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--reads") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --reads needs a FASTA or FASTQ file\n"); return 2; }
             o.reads = argv[++i];
+        }
+        else if (a == "--edits") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --edits needs a file name\n"); return 2; }
+            o.edits = argv[++i];
         }
         else if (a == "--window") { if (!need(&o.window) || !o.window) { fprintf(stderr, "PARSE ERROR: --window takes a positive number of bases\n"); return 2; } }
         else if (a == "--max-error") {
@@ -250,6 +262,8 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (!records && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam, --bam or --paf\n"); return 2; }
     if (o.window && (!records || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --window needs --sam, --bam or --paf and does not go with -a or --polish\n"); return 2; }
     if (o.pick.on() && !records) { fprintf(stderr, "PARSE ERROR: --max-error and --max-depth need --sam, --bam or --paf\n"); return 2; }
+    if (!o.edits.empty() && !records) { fprintf(stderr, "PARSE ERROR: --edits needs --sam, --bam or --paf\n"); return 2; }
+    if (!o.edits.empty() && o.dump) { fprintf(stderr, "PARSE ERROR: --edits does not go with --dump-parsed (nothing is run, the file would not be written)\n"); return 2; }
     if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
     if (o.window && (uint64_t)o.overlap < (uint64_t)o.trim + 64) { fprintf(stderr, "PARSE ERROR: --overlap must be at least --trim + 64 (%u)\n", o.trim + 64); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
@@ -331,9 +345,13 @@ struct Batch {
     Blob q, t;
     unsigned long long seq = 0;        // position in the input: records are printed in this order
     std::string out;                   // the batch's FASTA records
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); q.n = 0; t.n = 0; out.clear(); }
+    std::string edits;                 // --edits: the batch's lines of that file
+    unsigned long long n_edits = 0;
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; }
 };
 
+FILE *g_edits = nullptr;                                  // --edits FILE, written batch by batch in output order
+unsigned long long g_n_edits = 0;
 unsigned long long g_over_error = 0, g_over_depth = 0;     // records --max-error / --max-depth left out, all batches (under g_tmu)
 bool g_timing = false;                                    // PBDAGCON_TIMING=1: where the wall time of the run went, on stderr (seconds)
 std::mutex g_tmu;
@@ -353,6 +371,9 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
     dagcon_support sup;
     memset(&sup, 0, sizeof sup);
     if (o.fastq && !ok(ctx, dagcon_fetch_support(ctx, &sup), "per-base support")) return 1;
+    dagcon_edits ed;
+    memset(&ed, 0, sizeof ed);
+    if (!o.edits.empty() && !ok(ctx, dagcon_fetch_edits(ctx, &ed), "edits")) return 1;
     const char *nonconforming = o.mode == MODE_RECORDS ? dg_kind(o.kind).nonconforming : "an alignment leaves the backbone or holds a non-printable byte";
     for (uint32_t g = 0; g < r.n_targets; g++) {
         if (o.verbose)
@@ -362,9 +383,25 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
         // AlnGraphBoost.cpp:71-72): warn, go on with the rest
         if (r.target_status[g] != DAGCON_OK)
             fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(), dg_status_text(r.target_status[g], nonconforming));
-        for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++)
+        for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
             if (!dg_append_result(b.out, o.fastq, b.ids[g], r.range0[s], r.range1[s], r.seq_blob + r.seq_off[s], r.seq_len[s],
                                   o.fastq ? sup.weight + r.seq_off[s] : nullptr, o.fastq ? sup.depth + r.seq_off[s] : nullptr)) return 1;
+            if (o.edits.empty()) continue;
+            // the record's span and edits (include/dagcon.h, dagcon_edits): REF from the target's bases, ALT from the record's
+            char head[64];
+            snprintf(head, sizeof head, " %u %u\n", ed.seg_t0[s], ed.seg_t1[s]);
+            b.edits += "#piece "; b.edits += b.ids[g]; b.edits += head;
+            const char *tb = b.t.data() + b.toff[g];
+            for (uint64_t e = ed.edit_begin[s]; e < ed.edit_begin[s + 1]; e++) {
+                snprintf(head, sizeof head, "\t%u\t%u\t", ed.t_pos[e], ed.t_pos[e] + ed.t_len[e]);
+                b.edits += b.ids[g]; b.edits += head;
+                if (ed.t_len[e]) b.edits.append(tb + ed.t_pos[e], ed.t_len[e]); else b.edits += '-';
+                b.edits += '\t';
+                if (ed.c_len[e]) b.edits.append(r.seq_blob + ed.c_off[e], ed.c_len[e]); else b.edits += '-';
+                b.edits += '\n';
+            }
+            b.n_edits += ed.edit_begin[s + 1] - ed.edit_begin[s];
+        }
     }
     return 0;
 }
@@ -619,7 +656,11 @@ struct Workers {
     void run(size_t w) {
         dagcon_ctx *ctx = nullptr;
         const double tc0 = wall();
-        int rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], (o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u) | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u), &o.pick, &ctx);
+        int rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], (o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u) | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u) | (o.edits.empty() ? 0u : DAGCON_FLAG_BASE_POS), &o.pick, &ctx);
+        if (rc == DAGCON_OK && !o.edits.empty() && (rc = dagcon_set_edits(ctx, 1)) != DAGCON_OK) {
+            fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx));
+            dagcon_destroy(ctx); ctx = nullptr;
+        }
         dagcon_ctx *actx = ctx;                             // --local --polish: the first alignment on a local context of its own
         if (rc == DAGCON_OK && o.local && o.polish) {       // (aligns only: the support comes from ctx's last round)
             rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], DAGCON_FLAG_LOCAL_ALIGN, nullptr, &actx);
@@ -656,6 +697,7 @@ struct Workers {
                     Batch *d = done[i];
                     done.erase(done.begin() + i);
                     { const double tp0 = wall(); fwrite(d->out.data(), 1, d->out.size(), stdout); t_print += wall() - tp0; }
+                    if (g_edits) { fwrite(d->edits.data(), 1, d->edits.size(), g_edits); g_n_edits += d->n_edits; }
                     d->clear();
                     free_list.push_back(d);
                     print_seq++;
@@ -1138,7 +1180,7 @@ int main(int argc, char **argv) {
 
     // ---- --window: the window driver takes the records from here (windows.h) ----
     if (o.window && !o.dump) {
-        DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0], o.pick};
+        DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0], o.pick, o.edits.empty() ? nullptr : o.edits.c_str()};
         if (o.kind == DG_REC_PACKED) { DgBamSource src(bam, ref); return dg_run_windows(wo, src, ref); }
         if (o.kind == DG_REC_CS) { DgPafCsSource src(paf); return dg_run_windows(wo, src, ref); }
         if (o.kind == DG_REC_STRANDED) { DgPafSource src(paf); return dg_run_windows(wo, src, ref); }
@@ -1148,6 +1190,7 @@ int main(int argc, char **argv) {
 
     // ---- whole targets: the workers start (context creation hides behind the parsing of the first batch), the input
     // is parsed into batches slab by slab, the workers drain ----
+    if (!o.edits.empty() && !o.dump && !(g_edits = fopen(o.edits.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.edits.c_str()); return 1; }
     Workers wk(o, in.size);
     if (!o.dump) wk.start();
     RecordIndexer rix(in, o, ref, bam, paf);
@@ -1166,6 +1209,10 @@ int main(int argc, char **argv) {
     }
     const double t_joined = wall();
     if (!o.dump) dg_report_pick(o.pick, g_over_error, g_over_depth);
+    if (g_edits) {
+        if (fclose(g_edits) != 0) { fprintf(stderr, "pbdagcon: error writing %s\n", o.edits.c_str()); status = 1; fast_exit = false; }
+        if (o.verbose) fprintf(stderr, "pbdagcon: %llu edits written to %s\n", g_n_edits, o.edits.c_str());
+    }
     if (!fast_exit) {
         for (auto &x : wk.bufs) { x.q.release(); x.t.release(); }
         if (in.map) munmap(in.map, in.size);

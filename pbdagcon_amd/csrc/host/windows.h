@@ -20,6 +20,26 @@
 // from the window just before, and was cut at its core end; in every other case there is a break.  Joined pieces
 // shorter than -m are dropped.  A record is >RNAME/t0_t1 with t0 = g of the first base - 1 and t1 = g of the last:
 // target coordinates (in this mode only; everywhere else the name holds indexes into the consensus string, quirk Q5).
+//
+// The edits of a piece (--edits FILE; tests/edits_twin.py: stitch_edits is the twin).  A segment's edits (include/dagcon.h,
+// dagcon_edits; t_pos + window begin) cut it into blocks in target order: a stretch of bases equal to their target bases,
+// then an edit, and so on.  Of the kept part [i0, i1) of a segment:
+//   - a stretch of equal bases is clipped to [i0, i1) and its target bases with it;
+//   - an edit's inserted bases go where the stitch puts them: those inside [i0, i1) are kept, so a run that a cut splits
+//     is split with it;
+//   - an edit's target bases go with the base behind the edit (the first base behind its inserted bases): they are the
+//     piece's when that base is in [i0, i1).  The part of a run in front of a cut is a plain insertion where the edit
+//     begins; the edit's target bases stand in front of whatever is kept behind the cut.
+// A piece that starts at a break begins at the target base of its first kept base: an edit's target bases directly in
+// front of it (a leading deletion) are not the piece's, and inserted bases it begins with are an insertion at its begin.
+// A kept part that continues a piece begins where that piece ended: target bases between that end and the part's first
+// block are deleted by the joined piece (where the two windows agree that is the part's own leading deletion, or
+// nothing), and a block that reaches back over that end -- the windows disagree -- gives the bases it holds twice as an
+// insertion there.  The same clamp keeps a piece behind a break from beginning in front of the end of the piece before
+// it, so the pieces of a target never overlap.  Edits that come to touch in target and piece are one edit; the trim of
+// include/dagcon.h is not applied again.  The span [e0, e1) these edits refer to is written on the #piece line: it is
+// the record's t0_t1 except where the first or last kept base is an inserted base (its g is that of the target base
+// behind it) or a window disagrees with the one before it.  Per piece: ref[e0, e1) with the edits applied is the piece.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -34,20 +54,76 @@
 #include "intake.h"
 #include "sam.h"
 
+struct DgPieceEdit { long long t_pos, t_len, c_off, c_len; };   // target [t_pos, t_pos + t_len) -> seq[c_off, c_off + c_len)
+
 struct DgStitchPiece {
     long long t0 = 0, t1 = 0;
     std::string seq;
     std::vector<uint16_t> weight, depth;                   // --fastq: sliced as the bases are
+    long long e0 = 0, e1 = 0;                              // --edits: the target span the edits apply to
+    std::vector<DgPieceEdit> edits;
+};
+
+// one segment's edits as dagcon_fetch_edits hands them out (positions relative to the window)
+struct DgSegEdits {
+    uint32_t t0; uint64_t n;
+    const uint32_t *t_pos, *t_len; const uint64_t *c_off; const uint32_t *c_len;
+    uint64_t c_base;                                       // the segment's seq_off
 };
 
 // the pieces of one target, fed window by window in order
 struct DgStitch {
     std::vector<DgStitchPiece> pieces;
     long long open_w = -1;                                 // window of the last piece, if it was cut at its core end
-    void reset() { pieces.clear(); open_w = -1; }
-    // one segment of window wi = [begin, ..), core [c0, c1); weight / depth may be NULL
+    long long last_end = 0;                                // --edits: where the last piece's span ends
+    void reset() { pieces.clear(); open_w = -1; last_end = 0; }
+    // the edits of the kept part [i0, i1) of a segment, which is already the tail of the last piece (the rule above)
+    void add_edits(bool cont, uint32_t begin, uint32_t i0, uint32_t i1, uint32_t n, const DgSegEdits &ed) {
+        DgStitchPiece &p = pieces.back();
+        const long long shift = (long long)p.seq.size() - i1;          // segment index + shift = index in p.seq
+        long long at = 0;
+        bool first = true;
+        auto put = [&](long long tb, long long tl, long long cb, long long cl) {
+            if (!tl && !cl) return;
+            if (!p.edits.empty()) {
+                DgPieceEdit &l = p.edits.back();
+                if (l.t_pos + l.t_len == tb && l.c_off + l.c_len == cb) { l.t_len += tl; l.c_len += cl; return; }
+            }
+            p.edits.push_back(DgPieceEdit{tb, tl, cb, cl});
+        };
+        // a block clipped to the kept part: target [tb, te), segment bases [cb, ce); equal: the bases are their target's
+        auto block = [&](bool equal, long long tb, long long te, long long cb, long long ce) {
+            cb += shift; ce += shift;
+            if (first) {
+                first = false;
+                if (cont) at = p.e1; else p.e0 = at = std::max(equal ? tb : te, last_end);
+            }
+            if (!equal) { const long long e = std::max(te, at); put(at, e - at, cb, ce - cb); at = e; return; }
+            if (te <= at) { put(at, 0, cb, ce - cb); return; }
+            if (tb < at) { put(at, 0, cb, at - tb); cb += at - tb; tb = at; }
+            if (tb > at) put(at, tb - at, cb, 0);
+            at = te;
+        };
+        auto equal_run = [&](long long c_lo, long long c_hi, long long t_lo) {
+            const long long cb = std::max<long long>(c_lo, i0), ce = std::min<long long>(c_hi, i1);
+            if (cb < ce) block(true, t_lo + (cb - c_lo), t_lo + (ce - c_lo), cb, ce);
+        };
+        long long c = 0, t = (long long)ed.t0 + begin;
+        for (uint64_t k = 0; k < ed.n; k++) {
+            const long long tp = (long long)ed.t_pos[k] + begin, tl = ed.t_len[k], co = (long long)(ed.c_off[k] - ed.c_base), cl = ed.c_len[k];
+            equal_run(c, co, t);
+            const long long behind = co + cl, cb = std::max<long long>(co, i0), ce = std::min<long long>(behind, i1);
+            const bool takes = behind >= i0 && behind < i1;            // the edit's target bases are this part's
+            if (cb < ce) block(false, tp, takes ? tp + tl : tp, cb, ce);
+            else if (takes && tl) block(false, tp, tp + tl, behind, behind);
+            c = behind; t = tp + tl;
+        }
+        equal_run(c, n, t);
+        p.e1 = last_end = at;
+    }
+    // one segment of window wi = [begin, ..), core [c0, c1); weight / depth may be NULL; ed: NULL without --edits
     void add(long long wi, uint32_t begin, uint32_t c0, uint32_t c1, const char *seq, const uint32_t *pos, uint32_t n,
-             const uint16_t *weight, const uint16_t *depth) {
+             const uint16_t *weight, const uint16_t *depth, const DgSegEdits *ed = nullptr) {
         uint32_t i0 = 0;
         while (i0 < n && (uint64_t)pos[i0] + begin <= c0) i0++;
         if (i0 == n) return;
@@ -55,7 +131,8 @@ struct DgStitch {
         while (i1 < n && (uint64_t)pos[i1] + begin <= c1) i1++;
         if (i1 <= i0) return;
         const long long last_g = (long long)pos[i1 - 1] + begin;
-        if (i0 > 0 && open_w >= 0 && open_w == wi - 1 && !pieces.empty()) {
+        const bool cont = i0 > 0 && open_w >= 0 && open_w == wi - 1 && !pieces.empty();
+        if (cont) {
             DgStitchPiece &p = pieces.back();
             p.t1 = last_g;
             p.seq.append(seq + i0, i1 - i0);
@@ -67,6 +144,7 @@ struct DgStitch {
             p.seq.assign(seq + i0, i1 - i0);
             if (weight) { p.weight.assign(weight + i0, weight + i1); p.depth.assign(depth + i0, depth + i1); }
         }
+        if (ed) add_edits(cont, begin, i0, i1, n, *ed);
         open_w = i1 < n ? wi : -1;
     }
 };
@@ -77,6 +155,7 @@ struct DgWinOpts {
     bool fastq, verbose;
     int device;
     DgPick pick;                                           // --max-error / --max-depth
+    const char *edits;                                     // --edits FILE, or NULL
 };
 
 // SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
@@ -187,6 +266,12 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
     dagcon_ctx *ctx = nullptr;
     int rc = dg_create(o.min_cov, o.min_len, o.trim, o.device, DAGCON_FLAG_BASE_POS | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u), &o.pick, &ctx);
     if (rc != DAGCON_OK) return 1;
+    FILE *ef = nullptr;
+    unsigned long long n_edits = 0;
+    if (o.edits) {
+        if ((rc = dagcon_set_edits(ctx, 1)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); return 1; }
+        if (!(ef = fopen(o.edits, "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.edits); dagcon_destroy(ctx); return 1; }
+    }
     for (Tgt &t : tgts) t.fate.assign(t.recs.size(), 0);
     int status = 0;
     DgStitch st;
@@ -198,6 +283,25 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             if (p.seq.size() >= o.min_len && !dg_append_result(out, o.fastq, tgts[(size_t)cur_tgt].name, p.t0, p.t1, p.seq.data(), (uint32_t)p.seq.size(), p.weight.data(), p.depth.data())) return false;
         fwrite(out.data(), 1, out.size(), stdout);
         out.clear();
+        if (ef) {
+            // a #piece line with the span its edits apply to, then the edits: REF from --ref, ALT from the piece
+            const Tgt &t = tgts[(size_t)cur_tgt];
+            const char *tb = ref.bases.data() + t.sp.off;
+            for (const DgStitchPiece &p : st.pieces) {
+                if (p.seq.size() < o.min_len) continue;
+                out += "#piece " + t.name + " " + std::to_string(p.e0) + " " + std::to_string(p.e1) + "\n";
+                for (const DgPieceEdit &e : p.edits) {
+                    out += t.name + "\t" + std::to_string(e.t_pos) + "\t" + std::to_string(e.t_pos + e.t_len) + "\t";
+                    if (e.t_len) out.append(tb + e.t_pos, (size_t)e.t_len); else out += '-';
+                    out += '\t';
+                    if (e.c_len) out.append(p.seq.data() + e.c_off, (size_t)e.c_len); else out += '-';
+                    out += '\n';
+                }
+                n_edits += p.edits.size();
+            }
+            fwrite(out.data(), 1, out.size(), ef);
+            out.clear();
+        }
         st.reset();
         return true;
     };
@@ -251,6 +355,9 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         memset(&sup, 0, sizeof sup);
         if (rc == DAGCON_OK) rc = dagcon_fetch_positions(ctx, &pos, &npos);
         if (rc == DAGCON_OK && o.fastq) rc = dagcon_fetch_support(ctx, &sup);
+        dagcon_edits ed;
+        memset(&ed, 0, sizeof ed);
+        if (rc == DAGCON_OK && ef) rc = dagcon_fetch_edits(ctx, &ed);
         if (rc != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); status = 1; break; }
         uint64_t n_fate = 0;
         if (const uint8_t *fate = dg_record_fates(ctx, &n_fate))
@@ -269,8 +376,13 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
                                    (unsigned long long)(r.seg_begin[g + 1] - r.seg_begin[g]));
             for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
                 const uint64_t off = r.seq_off[s];
+                DgSegEdits se{};
+                if (ef) {
+                    const uint64_t e0 = ed.edit_begin[s];
+                    se = DgSegEdits{ed.seg_t0[s], ed.edit_begin[s + 1] - e0, ed.t_pos + e0, ed.t_len + e0, ed.c_off + e0, ed.c_len + e0, off};
+                }
                 st.add(w.idx, w.begin, w.c0, w.c1, r.seq_blob + off, pos + off, r.seq_len[s],
-                       o.fastq ? sup.weight + off : nullptr, o.fastq ? sup.depth + off : nullptr);
+                       o.fastq ? sup.weight + off : nullptr, o.fastq ? sup.depth + off : nullptr, ef ? &se : nullptr);
             }
         }
         w0 = w1;
@@ -281,6 +393,10 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         for (const uint8_t f : t.fate) { over_error += (f & DAGCON_FATE_MAX_ERROR) != 0; over_depth += (f & DAGCON_FATE_MAX_DEPTH) != 0; }
     dg_report_pick(o.pick, over_error, over_depth);
     fflush(stdout);
+    if (ef) {
+        if (fclose(ef) != 0) { fprintf(stderr, "pbdagcon: error writing %s\n", o.edits); status = 1; }
+        if (o.verbose) fprintf(stderr, "pbdagcon: %llu edits written to %s\n", n_edits, o.edits);
+    }
     dagcon_destroy(ctx);
     return status;
 }

@@ -782,6 +782,11 @@ __global__ __launch_bounds__(64) void k_bp_check(DgParams p) {
     if (bad && lane == 0) { if (stuck) dg_fail_target(p, t, DG_E_INTERNAL); else { dg_fail(p, DG_E_STACK); p.st->bad_target = t; } }
 }
 
+// POS walks: a path base's _bbMap travels through W.sb with its vertex's kind in bit 22 (_bbMap < 2^18); it leaves for
+// pos_tmp as _bbMap | DG_POS_BB for a backbone vertex.  The SUP-only instances keep the plain value (mask of all ones)
+#define DG_WALK_BBM(POS) ((POS) ? 0x3fffffu : 0xffffffffu)
+__device__ __forceinline__ uint32_t dg_pos_word(uint32_t sb) { return (sb & 0x3fffffu) | ((sb >> 22) << 31); }
+
 // ---- the best-edge walk (:443-456), one wave per (target, segment) ----------------
 // The best path passes through every cut vertex, so its stretch from one cut to the next is
 // walked by its own wave.  A segment leaves one byte per path vertex in its own stretch of
@@ -813,7 +818,7 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
     // no load of the support waits on the walk's chain
     const int32_t *cov = SUP ? p.cov + p.bbv_base[t] : nullptr;
     uint32_t *stmp = SUP ? p.sup_tmp + nb + c0 : nullptr;
-    uint32_t *ptmp = POS ? p.pos_tmp + nb + c0 : nullptr;     // POS: _bbMap itself, a second scratch word per path base
+    uint32_t *ptmp = POS ? p.pos_tmp + nb + c0 : nullptr;     // POS: _bbMap itself, a second scratch word per path base; DG_POS_BB: a backbone vertex
     uint32_t pw = 0;
     int32_t pdep = 0;
     int prow = -1;
@@ -828,6 +833,7 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
                 const int xw = id & (DG_WR - 1);
                 W.wtag[xw] = id; W.wbest[xw] = b; W.wbase[xw] = (int)(h.y & 0xffu); W.wweight[xw] = (int)h.z;
                 if constexpr (SB) W.wbase[xw] = (int)(h.y & 0xffu) | (nd[id].bbpos << 8);     // (bbpos < 2^18)
+                if constexpr (POS) W.wbase[xw] |= (int)(((h.y >> 8) & DG_NF_BACKBONE) << 30);  // the vertex's kind rides above it
             }
             cs++;
         }
@@ -845,6 +851,7 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
             base = (uint8_t)__builtin_amdgcn_readfirstlane((int)(h.y & 0xffu));
             w = __builtin_amdgcn_readfirstlane((int)h.z);
             if constexpr (SB) bbp = __builtin_amdgcn_readfirstlane(nd[v].bbpos);
+            if constexpr (POS) bbp |= __builtin_amdgcn_readfirstlane((int)(((h.y >> 8) & DG_NF_BACKBONE) << 22));
         }
         if (!(base == eb || base == xb)) {
             if (lane == 0) W.wbuf[idx & 63] = (unsigned char)(base | (w >= minw ? 0x80u : 0u));
@@ -853,9 +860,9 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
                 tmp[(idx & ~63) + lane] = W.wbuf[lane];
                 if constexpr (SUP) {
                     if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
-                    pw = W.sw[lane]; pdep = cov[W.sb[lane]]; prow = idx & ~63;
+                    pw = W.sw[lane]; pdep = cov[W.sb[lane] & DG_WALK_BBM(POS)]; prow = idx & ~63;
                 }
-                if constexpr (POS) ptmp[(idx & ~63) + lane] = W.sb[lane];
+                if constexpr (POS) ptmp[(idx & ~63) + lane] = dg_pos_word(W.sb[lane]);
             }
             idx++;
         }
@@ -866,10 +873,10 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
     if (lane < (idx & 63)) tmp[(idx & ~63) + lane] = W.wbuf[lane];     // the last, partial row
     if constexpr (SUP) {
         if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
-        if (lane < (idx & 63)) sbad |= dg_sup_put(stmp + (idx & ~63) + lane, W.sw[lane], cov[W.sb[lane]]);
+        if (lane < (idx & 63)) sbad |= dg_sup_put(stmp + (idx & ~63) + lane, W.sw[lane], cov[W.sb[lane] & DG_WALK_BBM(POS)]);
         if (__ballot(sbad)) bad = true;
     }
-    if constexpr (POS) { if (lane < (idx & 63)) ptmp[(idx & ~63) + lane] = W.sb[lane]; }
+    if constexpr (POS) { if (lane < (idx & 63)) ptmp[(idx & ~63) + lane] = dg_pos_word(W.sb[lane]); }
     if (lane == 0) {
         if (bad) dg_fail_target(p, t, DG_E_INTERNAL);
         p.bp_len[blockIdx.x] = (uint32_t)idx;
@@ -904,7 +911,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
     int go = v != c1 ? 1 : 0;
     const int32_t *cov = SUP ? p.cov + p.bbv_base[t] : nullptr;
     uint32_t *stmp = SUP ? p.sup_tmp + nb + c0 : nullptr;
-    uint32_t *ptmp = POS ? p.pos_tmp + nb + c0 : nullptr;     // POS: lane 3 stores the _bbMap it has loaded
+    uint32_t *ptmp = POS ? p.pos_tmp + nb + c0 : nullptr;     // POS: lane 3 stores the _bbMap it has loaded, DG_POS_BB from lane 1's flags
     int pend = -1;                                           // SUP: the path base whose support is still to be stored
     uint32_t pw = 0;
     int32_t pdep = 0;
@@ -914,7 +921,8 @@ __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
                       : ((SUP || POS) && l == 3) ? reinterpret_cast<const char *>(&nd[v]) + 28 : reinterpret_cast<const char *>(&best[v]);
         const uint32_t g = *reinterpret_cast<const uint32_t *>(a);
         const int nxt = __shfl((int)g, 0, DG_BRW);
-        const uint32_t base = (uint32_t)__shfl((int)g, 1, DG_BRW) & 0xffu;
+        const uint32_t hy = (uint32_t)__shfl((int)g, 1, DG_BRW);    // base | flags << 8
+        const uint32_t base = hy & 0xffu;
         const int w = __shfl((int)g, 2, DG_BRW);
         if constexpr (SUP) {
             if (pend >= 0 && l == 3) sbad |= dg_sup_put(stmp + pend, pw, pdep);
@@ -923,7 +931,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
         if (!(base == eb || base == xb)) {
             if (l == 0) tmp[idx] = (uint8_t)(base | (w >= minw ? 0x80u : 0u));
             if constexpr (SUP) { pend = idx; pw = (uint32_t)w; if (l == 3) pdep = cov[(int)g]; }
-            if constexpr (POS) { if (l == 3) ptmp[idx] = g; }
+            if constexpr (POS) { if (l == 3) ptmp[idx] = g | (((hy >> 8) & DG_NF_BACKBONE) << 31); }
             idx++;
         }
         if (nxt < 0) go = 0;
@@ -1061,8 +1069,10 @@ __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
         for (uint32_t s = 0; s < nseg; s++) {
             const uint32_t g0s = s_off[s], len = s_off[s + 1] - s_off[s];
             const uint32_t *src = (p.gcuts && s == 0) ? p.pos_tmp0 + nb : p.pos_tmp + nb + s_c0[s];
-            for (uint32_t j = lane; j < len && g0s + j < keep; j += 64) p.pos_out[co + g0s + j] = src[j];
+            for (uint32_t j = lane; j < len && g0s + j < keep; j += 64) p.pos_out[co + g0s + j] = p.ed_seg ? src[j] : src[j] & ~DG_POS_BB;
         }
+        // (edits: which target a segment belongs to, for the wave that scans it)
+        if (p.ed_seg) for (uint32_t i = lane; i < nout; i += 64) p.ed_seg[so + i].tgt = t;
     }
     for (uint32_t i = lane; i < nout; i += 64) {
         p.seg_r0[so + i] = segs[2 * i];
@@ -1367,6 +1377,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
                 const int xw = id & (DG_WR - 1);
                 W.wtag[xw] = id; W.wbest[xw] = b; W.wbase[xw] = (int)(h.y & 0xffu); W.wweight[xw] = (int)h.z;
                 if constexpr (SB) W.wbase[xw] = (int)(h.y & 0xffu) | (nd[id].bbpos << 8);     // (bbpos < 2^18)
+                if constexpr (POS) W.wbase[xw] |= (int)(((h.y >> 8) & DG_NF_BACKBONE) << 30);  // the vertex's kind rides above it
             }
             cs++;
         }
@@ -1384,6 +1395,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
             base = (uint8_t)__builtin_amdgcn_readfirstlane((int)(h.y & 0xffu));
             w = __builtin_amdgcn_readfirstlane((int)h.z);
             if constexpr (SB) bbp = __builtin_amdgcn_readfirstlane(nd[v].bbpos);
+            if constexpr (POS) bbp |= __builtin_amdgcn_readfirstlane((int)(((h.y >> 8) & DG_NF_BACKBONE) << 22));
         }
         if (!(base == eb || base == xb)) {
             if (lane == 0) W.wbuf[idx & 63] = (unsigned char)(base | (w >= minw ? 0x80u : 0u));
@@ -1392,9 +1404,9 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
                 tmp[(idx & ~63) + lane] = W.wbuf[lane];
                 if constexpr (SUP) {
                     if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
-                    pw = W.sw[lane]; pdep = cov[W.sb[lane]]; prow = idx & ~63;
+                    pw = W.sw[lane]; pdep = cov[W.sb[lane] & DG_WALK_BBM(POS)]; prow = idx & ~63;
                 }
-                if constexpr (POS) ptmp[(idx & ~63) + lane] = W.sb[lane];
+                if constexpr (POS) ptmp[(idx & ~63) + lane] = dg_pos_word(W.sb[lane]);
             }
             idx++;
         }
@@ -1405,10 +1417,10 @@ __global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
     if (lane < (idx & 63)) tmp[(idx & ~63) + lane] = W.wbuf[lane];     // the last, partial row
     if constexpr (SUP) {
         if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
-        if (lane < (idx & 63)) sbad |= dg_sup_put(stmp + (idx & ~63) + lane, W.sw[lane], cov[W.sb[lane]]);
+        if (lane < (idx & 63)) sbad |= dg_sup_put(stmp + (idx & ~63) + lane, W.sw[lane], cov[W.sb[lane] & DG_WALK_BBM(POS)]);
         if (__ballot(sbad)) bad = true;
     }
-    if constexpr (POS) { if (lane < (idx & 63)) ptmp[(idx & ~63) + lane] = W.sb[lane]; }
+    if constexpr (POS) { if (lane < (idx & 63)) ptmp[(idx & ~63) + lane] = dg_pos_word(W.sb[lane]); }
     if (lane == 0) {
         if (bad) dg_fail_target(p, t, DG_E_INTERNAL);
         p.bp_len[blockIdx.x] = (uint32_t)idx;

@@ -1,7 +1,9 @@
 // k_build.hip.h -- stage (a): alignment strings -> alignment DAG in HBM.
 //
-//   k_norm_*     a1  normalizeGaps (Alignment.cpp:131-217) + trimAln (:219-242) in chunks of ~1 k
-//                    input columns, one lane per chunk; also records the insertion run length
+//   k_norm_*     a1  normalizeGaps (Alignment.cpp:131-217) + trimAln (:219-242) in chunks of ~512
+//                    input columns, one lane per chunk (the run loops are in k_norm_run.hip.h: the first
+//                    pass visits only the columns that hold a gap, the second pass every column of the
+//                    few chunks the first could not serve); also records the insertion run length
 //                    per (position, read).  k_normalize_slow: whole alignments, sequential.
 //   k_carve      a2  exact vertex / pool needs per target, exclusive scans -> arena offsets
 //   k_groups     a2  per backbone position: exclusive scan of insertion run lengths over reads
@@ -14,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dagcon_dev.h"
+#include "k_norm_run.hip.h"
 
 #define DG_WAVE 64
 #ifndef DG_LPW
@@ -47,16 +50,20 @@ __device__ __forceinline__ void dg_fail_aln(const DgParams &p, uint32_t a, uint3
 // ---------------------------------------------------------------------------
 // normalizeGaps.  Columns are uint16: low byte = query char, high byte = target char.
 //
+// (DG_COL / DG_Q / DG_T and the run loops themselves: k_norm_run.hip.h, which a host compiler takes too.)
+//
 // The rewrite streams: 16 input columns per 16-byte load, expanded into a per-lane LDS
-// window; the push loop (Alignment.cpp:165-198) runs on the window with its two monotone
-// look-ahead cursors and pauses when a look-ahead reaches the end of the window (its steps
-// are idempotent, see dg_norm_run); finished columns leave 8 at a time.  An alignment whose
-// look-ahead outgrows the window (a gap run of ~100 columns) is flagged and redone by
+// window; the push (Alignment.cpp:165-198) runs on the window and pauses when a look-ahead
+// reaches the end of the window (a paused step has written nothing that a repeat would not
+// write again); finished columns leave 8 at a time.
+//   first pass   64-column window, dg_norm_run_gc: two 64-bit masks over the window (target
+//                is a gap / query is a gap) name the columns that hold a gap and, by a
+//                find-first-set, each one's partner; columns with two bases are never visited
+//   second pass  512-column window, dg_norm_run<512>: every column in turn, two monotone
+//                look-ahead cursors; for the chunks whose look-ahead outgrew the first window
+// An alignment whose look-ahead outgrows the second window too is flagged and redone by
 // k_normalize_slow, the same algorithm on HBM.
 // ---------------------------------------------------------------------------
-#define DG_COL(qb, tb) ((uint16_t)((uint16_t)(qb) | ((uint16_t)(tb) << 8)))
-#define DG_Q(c) ((uint8_t)((c) & 0xff))
-#define DG_T(c) ((uint8_t)((c) >> 8))
 #define DG_NW 64u             // LDS window of the first pass: columns per lane (power of two); the lane
                               // row is NW + 2 uint16 = an odd number of dwords, so lanes spread over banks
 #define DG_NW_BIG 512u        // window of the second pass, for the chunks whose look-ahead outgrew the first
@@ -153,159 +160,18 @@ __device__ inline void dg_finish_alignment(const DgParams &p, uint32_t a, uint16
 // has not written past it.  By induction from chunk 0 all chunks are then exact.  A chunk
 // that did write past its end is run again with the next chunk taken in (its output goes to
 // the re-run region), and the swallowed chunk's own result is dropped by k_norm_scan.
-//   k_norm_chunk   lane per chunk: the streaming push loop (dg_norm_run) on [k0, k1)
+//   k_norm_chunk   lane per chunk: the streaming push (dg_norm_run_gc / dg_norm_run) on [k0, k1)
 //   k_norm_scan    lane per alignment: offsets of the chunks, trimAln (:219-242)
 //   k_norm_finish2 wave per chunk: columns to their final place; what dg_finish_alignment
 //                  does, on the chunk's share of the trimmed window
 // ---------------------------------------------------------------------------
-#ifndef DG_NCH
-#define DG_NCH 512u            // input columns per window (1024: +1.4 ms at configs[1], 256: the same, 128: +1.3 ms)
-#endif
-#define DG_CH_NONE 0xFFFFFFFFu
-
-__device__ __forceinline__ bool dg_match_col(uint8_t qb, uint8_t tb) { return qb == tb && qb != DG_GAP && qb != '.'; }
-
-// column a chunk starts at inside window c of the alignment, DG_CH_NONE if there is none
-__device__ inline uint32_t dg_chunk_start(const uint8_t *q, const uint8_t *t, uint32_t len, uint32_t c) {
-    if (c == 0) return 0;
-    const uint64_t w0 = (uint64_t)c * DG_NCH;
-    if (w0 >= len) return DG_CH_NONE;
-    const uint32_t hi = (uint64_t)len < w0 + DG_NCH ? len : (uint32_t)(w0 + DG_NCH);
-    for (uint32_t k = (uint32_t)w0; k < hi; k++) {
-        const uint8_t b = q[k];
-        if (dg_match_col(b, t[k]) && b != q[k - 1] && dg_match_col(q[k - 1], t[k - 1]) && dg_match_col(q[k - 2], t[k - 2]))
-            return k;
-    }
-    return DG_CH_NONE;
-}
-
-struct DgChunkRun { uint32_t w, tb; bool dirty, overflow, badchar; };
-
-// normalizeGaps (Alignment.cpp:142-214) on the input columns [k0, k1) of an alignment, started
-// cold; the look-ahead may read (and, reported as `dirty`, write) beyond k1.
-template <uint32_t NW>
-__device__ inline DgChunkRun dg_norm_run(const uint8_t *q, const uint8_t *t, const uint32_t len, const uint32_t k0,
-                                         const uint32_t k1, uint16_t *win, uint16_t *out) {
-#define DG_W(x) win[(x) & (NW - 1u)]
-    DgChunkRun r;
-    r.w = 0; r.tb = 0; r.dirty = false; r.overflow = false; r.badchar = false;
-    if (k0 >= k1) return r;
-    uint32_t badw = 0;                                     // bit 7 of a byte set: a byte outside 33..126 was read
-    uint32_t ip = k0, e = 0, i = 0, w = 0, tb = 0, jt = 0, jq = 0;
-    uint32_t e_end = 0xFFFFFFFFu;                          // window index of input column k1, once known
-    // finished columns collect in a 128-bit shift register and leave 8 at a time (out is
-    // 16-byte aligned): one store request instead of eight
-    uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
-    // (flags that differ from lane to lane are kept as integers in vector registers, not as booleans: see k_emit)
-    uint32_t in_done = 0, dirty = 0, overflow = 0;
-    for (;;) {
-        asm volatile("" : "+v"(in_done), "+v"(dirty));
-        // ---- refill: Alignment.cpp:142-159 on the next (up to) 16 input columns ----
-        if (!in_done && (e - i) + 32u > NW) { overflow = 1; break; }
-        if (!in_done) {
-            uint32_t take = len - ip;
-            if (take > 16u) take = 16u;
-            if (ip < k1 && take > k1 - ip) take = k1 - ip;  // land on the chunk's end exactly
-#define DG_EXPAND(QB, TB)                                                      \
-            do {                                                               \
-                uint8_t qb_ = (QB), tb_ = (TB);                                \
-                if (qb_ == '.') qb_ = DG_GAP;                                  \
-                if (tb_ == '.') tb_ = DG_GAP;                                  \
-                /* a mismatch becomes (-, t) (q, -): no branch -- the second slot is written whatever the column is */ \
-                /* (the next column overwrites it; the refill has 32 free slots for its 16 columns) */                   \
-                const bool mm_ = qb_ != tb_ && qb_ != DG_GAP && tb_ != DG_GAP; \
-                DG_W(e) = mm_ ? DG_COL(DG_GAP, tb_) : DG_COL(qb_, tb_);        \
-                DG_W(e + 1u) = DG_COL(qb_, DG_GAP);                            \
-                e += mm_ ? 2u : 1u;                                            \
-            } while (0)
-            if (take == 16u && (((uintptr_t)(q + ip)) & 15u) == 0) {
-                // the common case, unrolled: bytes come out of the two 16-byte registers with
-                // constant shifts
-                const uint4 qv = *reinterpret_cast<const uint4 *>(q + ip);
-                const uint4 tv = *reinterpret_cast<const uint4 *>(t + ip);
-                const uint32_t qw[4] = {qv.x, qv.y, qv.z, qv.w}, tw[4] = {tv.x, tv.y, tv.z, tv.w};
-                // every byte has to be printable ASCII (33..126): four at a time
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    badw |= ((qw[k] - 0x21212121u) & ~qw[k]) | ((qw[k] + 0x01010101u) | qw[k]);
-                    badw |= ((tw[k] - 0x21212121u) & ~tw[k]) | ((tw[k] + 0x01010101u) | tw[k]);
-                }
-#pragma unroll
-                for (int k = 0; k < 16; k++)
-                    DG_EXPAND((uint8_t)(qw[k >> 2] >> (8 * (k & 3))), (uint8_t)(tw[k >> 2] >> (8 * (k & 3))));
-            } else {
-                // head (up to the next 16-byte boundary) and tail: byte loads
-                const uint32_t to_align = (uint32_t)((16u - (((uintptr_t)(q + ip)) & 15u)) & 15u);
-                if (to_align && take > to_align) take = to_align;
-                for (uint32_t k = 0; k < take; k++) {
-                    const uint8_t qb0 = q[ip + k], tb0 = t[ip + k];
-                    if (qb0 < 33 || qb0 > 126 || tb0 < 33 || tb0 > 126) badw = 0x80u;
-                    DG_EXPAND(qb0, tb0);
-                }
-            }
-#undef DG_EXPAND
-            ip += take;
-            if (ip == k1) e_end = e;
-            if (ip == len) in_done = 1;
-        }
-        // ---- Alignment.cpp:165-198 push gaps to the right, as far as the window reaches.
-        // jt / jq only move forward (a column left of a cursor is never turned back into
-        // a base).  A step that runs out of window stores what it has done to column i
-        // and is restarted after the refill: the t-pass of a restarted step either finds
-        // its column already filled or repeats the same fruitless look-up. ----
-        while (i < e && i < e_end) {
-            if (i + 1 == e && !in_done) break;
-            const uint16_t c = DG_W(i);
-            uint8_t qi = DG_Q(c), ti = DG_T(c);
-            uint32_t more = 0;
-            if (i + 1 < e) {
-                if (ti == DG_GAP) {
-                    if (jt <= i) jt = i + 1;
-                    while (jt < e && DG_T(DG_W(jt)) == DG_GAP) jt++;
-                    if (jt < e) {
-                        const uint16_t cj = DG_W(jt);
-                        if (DG_T(cj) == qi) { ti = qi; DG_W(jt) = DG_COL(DG_Q(cj), DG_GAP); dirty |= (uint32_t)(jt >= e_end); }
-                    } else if (!in_done) more = 2;
-                }
-                if (!more && qi == DG_GAP) {
-                    if (jq <= i) jq = i + 1;
-                    while (jq < e && DG_Q(DG_W(jq)) == DG_GAP) jq++;
-                    if (jq < e) {
-                        const uint16_t cj = DG_W(jq);
-                        if (DG_Q(cj) == ti) { qi = ti; DG_W(jq) = DG_COL(DG_GAP, DG_T(cj)); dirty |= (uint32_t)(jq >= e_end); }
-                    } else if (!in_done) more = 2;
-                }
-            }
-            if (more) { DG_W(i) = DG_COL(qi, ti); break; }
-            if (qi != DG_GAP || ti != DG_GAP) {                                // :209-214
-                o0 = (o0 >> 16) | (o1 << 16); o1 = (o1 >> 16) | (o2 << 16); o2 = (o2 >> 16) | (o3 << 16);
-                o3 = (o3 >> 16) | ((uint32_t)DG_COL(qi, ti) << 16);
-                w++;
-                tb += (ti != DG_GAP);
-                if ((w & 7u) == 0) *reinterpret_cast<uint4 *>(out + w - 8) = make_uint4(o0, o1, o2, o3);
-            }
-            i++;
-        }
-        if (i == e_end) break;
-    }
-#undef DG_W
-    // the last, partial group: its columns sit at the top of the register
-    for (uint32_t k = w & 7u, x = w - (w & 7u); k > 0; k--, x++) {
-        const uint32_t sh = 8u - k;                        // column x is sh places from the bottom
-        const uint32_t word = sh >> 1;
-        const uint32_t v = word == 0 ? o0 : word == 1 ? o1 : word == 2 ? o2 : o3;
-        out[x] = (uint16_t)((sh & 1u) ? v >> 16 : v & 0xffffu);
-    }
-    r.w = w; r.tb = tb; r.dirty = dirty != 0; r.overflow = overflow != 0; r.badchar = (badw & 0x80808080u) != 0;
-    return r;
-}
-
 // NW = 64 keeps the LDS footprint of the first pass at 8 KB per wave (the kernel is bound by waves in
-// flight); a chunk whose look-ahead outgrows that window (a gap run of ~30 columns) is done again
+// flight); a chunk whose look-ahead outgrows that window (a gap run of more than 25 columns) is done again
 // by the second pass (RETRY: LANES = 32 lanes per block, a 512-column window each), and only what
-// outgrows that one too sends its alignment to k_normalize_slow.
+// outgrows that one too sends its alignment to k_normalize_slow.  The first pass asks for 5 waves per
+// SIMD (96 VGPRs), what its LDS allows; the second pass has one wave per SIMD either way.
 template <uint32_t NW, uint32_t LANES, bool RETRY>
-__global__ __launch_bounds__(LANES) void k_norm_chunk(DgParams p) {
+__global__ __launch_bounds__(LANES, RETRY ? 1 : 5) void k_norm_chunk(DgParams p) {
     __shared__ uint16_t s_win[LANES * (NW + 2u)];
     // neighbouring chunks are ~1 KB of input (4 KB of scratch) apart: lanes of a wave take chunks
     // a whole grid apart instead, or their lines fight for the same few L1 sets and L2 channels
@@ -337,7 +203,8 @@ __global__ __launch_bounds__(LANES) void k_norm_chunk(DgParams p) {
                     const uint32_t s = dg_chunk_start(q, t, len, cn);
                     if (s != DG_CH_NONE) { k1 = s; break; }
                 }
-                r = dg_norm_run<NW>(q, t, len, k0, k1, win, p.norm_tmp + src);
+                if constexpr (NW == DG_NW) r = dg_norm_run_gc(q, t, len, k0, k1, win, p.norm_tmp + src);
+                else r = dg_norm_run<NW>(q, t, len, k0, k1, win, p.norm_tmp + src);
                 if (r.badchar) dg_fail_aln(p, a, DG_E_BADCHAR);
                 if (r.overflow) { flag = RETRY ? 1u : 2u; break; }
                 if (!r.dirty) break;

@@ -1,0 +1,282 @@
+// api_ctx.h -- the context: owning buffers, the named buffer sets, the status block, Ctx, errors, ensure() and upload()
+// (one translation unit with dagcon_api.hip, which includes it once).
+namespace {
+
+struct Ctx;
+
+// a device buffer and its owner: grown by ensure(), freed with the context
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+    template <class X> X *as() const { return static_cast<X *>(p); }
+};
+
+// a page-locked host buffer and its owner (cap in bytes): what comes back from the device at PCIe speed
+struct PinBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    int reserve(Ctx *c, size_t bytes);              // (at least bytes; what it held is gone when it grows)
+    template <class X> X *as() const { return static_cast<X *>(p); }
+};
+
+// the device buffers of the record intake, by name
+struct CigarBufs {
+    DevBuf ops, op_begin, tile_begin, totals, ckpt;                // the records' ops, k_cigar_scan's output
+    DevBuf q, t, q_off, t_base;                                    // the blobs and where each record's bases begin
+    DevBuf out_off;                                                // whole targets: where each record's strings go
+    DevBuf piece, cut, wave_piece, wave_begin, piece_out;          // windows: DgCigarCutParams
+    DevBuf rev, q_len;                                             // DgCigarStrand
+    DevBuf rate_base, tile_rate, rate;                             // DgCigarRate (a record filter is set)
+};
+// dagcon_upload_cs: the text and what k_cs_scan / k_cs_write take besides CigarBufs::ops, q and t, which k_cs_write fills
+struct CsBufs {
+    DevBuf text, cs_off, cs_len, totals, n_ops, op_begin, t_base, t_room, q_off, q_len;
+};
+// dagcon_align (align_device): blobs, offsets, outputs, directions, launch order, widths, ends; qaln / taln at out_off are
+// what dagcon_consensus_pre hands to the pipeline
+struct AlignBufs {
+    DevBuf q, t, q_off, t_off, q_len, t_len, out_off, qaln, taln, len, dirs, dir_off, idx, halfw, ends;
+};
+// dagcon_align_panels: blobs, panels (p_*), scratch, per-panel outputs, launch order, then the pairs' side
+struct PanelBufs {
+    DevBuf q, t, p_q_off, p_t_off, p_q_len, p_t_len, scr_off, qscr, tscr, p_len, p_dist, idx, panel_begin, out_off, qaln, taln, len, kept;
+};
+// dagcon_place: blob, sequences, tables, pairs, outputs
+struct PlaceBufs {
+    DevBuf blob, seq_off, seq_len, tab_seq, tab_base, tab_mask, slots, pq, pt, ptab, pid, votes, span, strand;
+};
+
+// The buffers of a batch on its way through the pipeline, by who writes them.
+// InBufs: what the host uploads per batch (upload_impl, edits_arm; q / t also by the record intake's expansion)
+struct InBufs {
+    DevBuf q, t, aln_off, aln_len, aln_start, aln_tgt, tlen, aln_begin, tactive, bb, bb_off, mat_base, bbv_base, matc_base, matc_stride;
+    DevBuf norm_off, ch_aln, ch_base, ck_base;
+    DevBuf ed_tbase;                                // dagcon_set_edits: where each target's bases begin in cg.t
+};
+// RunBufs: what the kernels of a run fill and nobody clears.  all() is the set DAGCON_POISON & 8 fills with 0xEE bytes
+// before every run (launch_all): a new member goes into it, and the static_assert below says so
+struct RunBufs {
+    DevBuf nmis, n_lo, n_hi, n_start, n_ins, n_del;
+    DevBuf ch_k0, ch_next, ch_w, ch_tb, ch_flag, ch_src, ch_out, ch_adv, n_lb, norm_tmp, ckpt;
+    DevBuf node_base, n_nodes, pool_base, pool_size, pool_top, t_nins;
+    DevBuf cov, gcount, gbase, bid;
+    DevBuf best, queue, score, cns_tmp, bp_tt;
+    DevBuf stk, cuts, cuts_bp, bp_stat, bp_len, rd, pro_state, sh_cnt, wl_first, queue0, bp_end, bp_ab, defer, cns_tmp0;
+    DevBuf cns;
+    DevBuf seg;                                     // seg_r0[seg_cap], then seg_r1 at seg_stride() entries
+    DevBuf worklist, seg_done;
+    DevBuf sup_tmp, sup_tmp0, sup;                  // DAGCON_FLAG_BASE_SUPPORT: walk scratch (4 B per vertex), output (2 x 2 B per base)
+    DevBuf pos_tmp, pos_tmp0, pos;                  // DAGCON_FLAG_BASE_POS: walk scratch (4 B per vertex), output (4 B per base)
+    DevBuf ed_seg, ed_out;                          // dagcon_set_edits: a DgEdSeg per segment, a DgEdit per edit
+    std::array<DevBuf *, 58> all() {
+        return {&nmis, &n_lo, &n_hi, &n_start, &n_ins, &n_del, &ch_k0, &ch_next, &ch_w, &ch_tb, &ch_flag, &ch_src, &ch_out, &ch_adv, &n_lb, &norm_tmp, &ckpt,
+                &node_base, &n_nodes, &pool_base, &pool_size, &pool_top, &t_nins, &cov, &gcount, &gbase, &bid, &best, &queue, &score, &cns_tmp, &bp_tt,
+                &stk, &cuts, &cuts_bp, &bp_stat, &bp_len, &rd, &pro_state, &sh_cnt, &wl_first, &queue0, &bp_end, &bp_ab, &defer, &cns_tmp0, &cns,
+                &seg, &worklist, &seg_done, &sup_tmp, &sup_tmp0, &sup, &pos_tmp, &pos_tmp0, &pos, &ed_seg, &ed_out};
+    }
+};
+static_assert(sizeof(RunBufs) == 58 * sizeof(DevBuf), "RunBufs::all() must name every member");
+// ArenaBufs: the arenas with a treatment of their own -- matC is cleared before every run, the others are filled under
+// DAGCON_POISON bits 1 (matA, matD), 2 (nodes, pool) and 4 (score_b, norm)
+struct ArenaBufs {
+    DevBuf matA, matD, matC, nodes, pool, score_b, norm;
+};
+
+// The words the host reads back after every run, as ranges of ONE device buffer (each 16-byte aligned): what a run starts
+// from zero first -- DgStatus, tfail[T + 1], cns_len[T], n_seg[T]: one memset -- then cns_off[T] and seg_first[T].  The whole
+// block comes back in one copy into `host`, its page-locked mirror (dagcon_fetch reads the mirror in place).
+struct StatBlock {
+    DevBuf dev;
+    PinBuf host;
+    size_t o_tfail = 0, o_cns_len = 0, o_n_seg = 0, o_cns_off = 0, o_seg_first = 0;     // (DgStatus at 0)
+    size_t o_ed_top = 0;                            // edits of the batch, behind seg_first (a batch with edits on only; 0: none)
+    size_t zero_bytes = 0, bytes = 0;
+    template <typename X> X *d(size_t off) const { return reinterpret_cast<X *>(static_cast<char *>(dev.p) + off); }
+    template <typename X> const X *h(size_t off) const { return reinterpret_cast<const X *>(host.as<char>() + off); }
+};
+
+struct Ctx {
+    dagcon_opts opts;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::string err;
+    bool uploaded = false, ran = false, fetched = false;
+
+    // host copy of the filtered batch
+    uint32_t T = 0, A = 0;
+    int bp_lane = 1, bl_stk = -1;                  // full-span bestPath: a row of eight lanes per piece (k_bp_sweep_l; DAGCON_BP_LANE=0: a wave per piece, k_bp_sweep; 2: rows whatever the batch size); DAGCON_BP_LANE_STACK: test knob
+    uint32_t align_dropped = 0;                    // records of the last dagcon_align / dagcon_consensus_pre the band could not align
+    uint32_t align_n = 0;                          // pairs of the last dagcon_align / dagcon_consensus_pre
+    std::vector<uint32_t> h_ends;                  // their ends (dagcon_align_ends): q_begin, q_end, t_begin, t_end per pair
+    int poison = 0;                                // DAGCON_POISON (tests): arenas nobody clears are filled with 0xEE bytes before every run (bits 1, 2, 4); 8: every buffer the kernels fill
+    int fold = 1;                                  // duplicate insertion chains folded by k_emit (DAGCON_FOLD=0: never)
+    int merge_q = 1, use_q = 0;                    // k_merge_q: eight segments per wave (DAGCON_MERGE_Q=0: never); this batch
+    uint32_t max_k = 0, max_tlen = 0;
+    uint64_t sum_len = 0, sum_bb = 0, mat_cells = 0, blob_bytes = 0;
+    bool have_bb = false;
+    std::vector<uint32_t> h_tlen, h_aln_len, h_aln_start, h_aln_tgt;
+    std::vector<uint64_t> h_aln_begin, h_aln_off, h_mat_base, h_bbv_base, h_bb_off, h_matc_base;
+    std::vector<uint32_t> h_matc_stride;
+    uint64_t matc_cells = 0;
+    bool wide_cells = false;                        // this upload met an insertion run of more than 255 columns: 32-bit matC cells
+    std::vector<uint8_t> h_tactive;
+    std::vector<uint32_t> h_ch_base, h_ch_aln;      // chunk tables of k_norm_*
+    std::vector<uint64_t> h_norm_off;               // column buffer of each alignment
+    std::vector<uint32_t> h_ck_base;                // first k_emit checkpoint of each alignment
+    uint64_t n_ckpt = 0;
+    uint32_t emit_shift = 9;                        // 512 backbone positions per k_emit wave
+    uint32_t n_chunks = 0;
+    uint64_t tmp_main = 0, tmp_cap = 0;
+
+    // device buffers (each frees itself with the context)
+    InBufs in;
+    RunBufs run;
+    ArenaBufs arena;
+    AlignBufs al;                                   // dagcon_align
+    PanelBufs pn;                                   // dagcon_align_panels
+    PlaceBufs pl;                                   // dagcon_place
+    CsBufs cs;                                      // dagcon_upload_cs
+    CigarBufs cg;                                   // dagcon_upload_cigar and its kin
+    std::vector<uint8_t> h_cig_bad;                 // dagcon_upload_cigar: targets with a non-conforming record (empty: another upload)
+    std::string cig_err;                            // the first of them, for dagcon_last_error
+    bool filter_on = false;                         // dagcon_set_record_filter: the record intake rates and picks its records
+    dagcon_record_filter filter = {1000000u, 0u};
+    bool rs_valid = false;                          // the record stats below are those of the last upload (dagcon_fetch_record_stats)
+    std::vector<uint32_t> rs_match, rs_mismatch, rs_ins, rs_del;
+    std::vector<uint8_t> rs_fate;
+    StatBlock sb;                                   // DgStatus, tfail, cns_len, n_seg, cns_off, seg_first
+    // dagcon_set_edits: the switch; whether the batch on the device is a record upload made under it (its buffers:
+    // run.ed_seg, run.ed_out, in.ed_tbase)
+    bool edits_on = false, ed_batch = false;
+    std::vector<uint64_t> h_ed_tbase;
+    uint64_t ed_cap = 0;
+    long ed_cap_env = 0;                            // DAGCON_EDITS_CAP (tests): first size of the edit arena, so that the re-run is met
+
+    uint64_t norm_cap = 0, node_cap = 0, pool_cap = 0, cns_cap = 0, seg_cap = 0;
+    uint32_t stk_words = 4096, growth_pct = 100, seg_max = 8, bp_max = 16, seg_env = 0, seg_min = 768;    // (scratch per target and segment: grown x4 and re-run on DG_E_STACK)
+    uint32_t sh_log = 16;                           // slots per segment behind enter's / exit's list (x2 on DG_E_LOG_OVF)
+    bool full_span = false;                         // (nearly) every alignment of the batch covers its whole target
+    uint32_t gcuts = 1;                             // partial-span cuts: prologue + worklist + epilogue (DAGCON_GCUTS=0: off)
+    uint32_t worklist_cap = 0, list_grid = 8192;    // partial-span worklist: entries, and the waves of k_merge_list
+
+    DgStatus h_st;
+    dagcon_timings tm;
+
+    // results (host)
+    std::vector<uint64_t> r_seg_begin, r_seq_off;
+    std::vector<int32_t> r_range0, r_range1;
+    std::vector<uint32_t> r_seq_len;
+    PinBuf r_seg;                       // int32_t, grown with the segment arena: seg_r0's first seg_top entries, then seg_r1's
+    std::vector<int32_t> r_status;
+    PinBuf r_blob;                      // char: the consensus blob
+    PinBuf r_sup;                       // uint16_t, DAGCON_FLAG_BASE_SUPPORT: [seq_bytes] weights, then [seq_bytes] depths
+    uint64_t r_sup_n = 0;
+    std::vector<uint32_t> r_pos;        // DAGCON_FLAG_BASE_POS: [seq_bytes] _bbMap of every consensus base
+    bool pos_valid = false;
+    bool pos_pending = false;           // edits on: the positions stay on the device until dagcon_fetch_positions asks for them
+    uint64_t r_nb = 0;                  // seq_bytes of the last fetch
+    PinBuf r_ed;                        // the DgEdSeg records of the last fetch, then its DgEdit records
+    bool ed_valid = false;              // the arrays below are those of the last fetch (dagcon_fetch_edits)
+    std::vector<uint32_t> e_t0, e_t1, e_tpos, e_tlen, e_clen;
+    std::vector<uint64_t> e_begin, e_coff;
+    bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
+
+    // debug dump storage
+    std::vector<uint8_t> g_base, g_deleted, g_backbone;
+    std::vector<int32_t> g_weight, g_cov, g_bbpos, g_out_dst, g_out_cnt, g_in_src;
+    std::vector<uint32_t> g_out_begin, g_in_begin;
+
+    // (the body runs before the members free themselves: nothing of this context is in flight any more when they do)
+    ~Ctx() {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+int fail(Ctx *c, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (c) c->err = buf;
+    return code;
+}
+
+#define HIPCHK(c, call)                                                                    \
+    do {                                                                                   \
+        hipError_t _e = (call);                                                            \
+        if (_e != hipSuccess)                                                              \
+            return fail((c), DAGCON_ERR_HIP, "%s failed: %s (%s:%d)", #call,               \
+                        hipGetErrorString(_e), __FILE__, __LINE__);                        \
+    } while (0)
+
+int ensure(Ctx *c, DevBuf &b, size_t bytes) {
+    if (bytes == 0) bytes = 16;
+    if (b.cap >= bytes) return DAGCON_OK;
+    b.release();
+    size_t want = bytes + bytes / 16 + 256;
+    const bool dbg = getenv("DAGCON_ALLOC_TIMING") != nullptr;
+    const double t0 = dbg ? std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() : 0;
+    hipError_t e = hipMalloc(&b.p, want);
+    if (dbg) {
+        const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0;
+        if (dt > 0.005) fprintf(stderr, "dagcon: hipMalloc(%.1f MB) took %.1f ms\n", want / 1e6, dt * 1e3);
+    }
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        return fail(c, DAGCON_ERR_WORKSPACE, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
+    }
+    b.cap = want;
+    return DAGCON_OK;
+}
+
+#define ENSURE(c, buf, bytes)                                \
+    do {                                                     \
+        int _r = ensure((c), (buf), (size_t)(bytes));        \
+        if (_r != DAGCON_OK) return _r;                      \
+    } while (0)
+
+// room for n entries, then the host's n entries on their way there on the context's stream (n == 0: no copy)
+template <typename X>
+int upload(Ctx *c, DevBuf &b, const X *host, size_t n) {
+    ENSURE(c, b, n * sizeof(X));
+    if (n) HIPCHK(c, hipMemcpyAsync(b.p, host, n * sizeof(X), hipMemcpyHostToDevice, c->stream));
+    return DAGCON_OK;
+}
+template <typename X>
+int upload(Ctx *c, DevBuf &b, const std::vector<X> &v) { return upload(c, b, v.data(), v.size()); }
+
+#define UPLOAD(c, buf, ...)                                  \
+    do {                                                     \
+        int _r = upload((c), (buf), __VA_ARGS__);            \
+        if (_r != DAGCON_OK) return _r;                      \
+    } while (0)
+
+// one headroom for every page-locked buffer, in bytes: not below any of the five it replaces (the largest was the
+// support's, 4 x (n + n / 8 + 4096))
+int PinBuf::reserve(Ctx *c, size_t bytes) {
+    if (cap >= bytes) return DAGCON_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    const size_t want = bytes + bytes / 8 + 16384;
+    HIPCHK(c, hipHostMalloc(&p, want, hipHostMallocDefault));
+    cap = want;
+    return DAGCON_OK;
+}
+}  // namespace

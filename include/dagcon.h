@@ -528,6 +528,60 @@ int dagcon_consensus_cs(dagcon_ctx *ctx, const dagcon_cs_batch *batch, const dag
                         dagcon_results *results);
 
 /*
+ * SAM / BAM records without target bases: a dagcon_cigar_batch (plain reads, or BAM-packed with packed != 0; there is no
+ * stranded form) plus one MD:Z text per record.  With CIGAR and SEQ the tag spells every target base a record touches --
+ * matches are the read's own bases, mismatches and deleted bases are letters of the text -- so the targets are rebuilt
+ * on the device (k_md.hip.h) and the batch then takes the path of dagcon_consensus_cigar / _windows / _packed.
+ * batch->t_blob is not read and may be NULL; tlen, t_off and t_bytes lay out a target blob T of t_bytes bytes that the
+ * device makes.  md_blob[md_off[r] .. + md_len[r]) is the text behind "MD:Z:" as the file has it.
+ * This build's own rule (the reference reads no SAM, parity unpinned):
+ * Grammar: a text must match [0-9]+(([A-Za-z]|\^[A-Za-z]+)[0-9]+)* in full.
+ *   - A number has 1 to 9 digits and a value below 2^28; 0 and leading zeros are fine.  A number n covers n target bases
+ *     as matches.
+ *   - A lone letter covers one target base and spells it (a mismatch).
+ *   - The letters behind ^ each cover and spell one target base (deleted bases).  They run to the next digit, so ^AC0G is
+ *     a deletion of 2 and then a mismatch.
+ *   - Letters are stored verbatim; no case is changed.  Offset k of a covered base counts from the record's pos - 1.
+ * A record is non-conforming when its text breaks the grammar (an empty text, a first byte that is no digit, ^ followed by
+ * a digit or by the end, two letters in a row outside a deletion, any other byte, 10 digits, a value of 2^28 or more),
+ * when the bases its text covers do not equal the target bases its CIGAR consumes, or when anything makes it
+ * non-conforming for dagcon_consensus_cigar.  It fails its target, or with windows the windows its span meets, exactly as
+ * there.  MD and CIGAR are not cross-checked beyond that total: a D op whose bases the text counts as matches deletes
+ * whatever T holds there, and a letter under an M op is simply that position's target base.
+ * T, from every conforming record of the batch, before dagcon_set_record_filter picks (a record the filter later drops
+ * still contributes):
+ *   1. a position spelled by a letter of any record holds that letter;
+ *   2. otherwise a position under an M / = / X column of any record holds that column's read base, the byte the
+ *      expansion would write (decoded from its nibble when the reads are packed);
+ *   3. every other byte of the blob is 'N'.
+ * There is a conflict when two records spell different letters at one position, or when two records give different read
+ * bases at one position no record spells.  Then every record of that target becomes non-conforming ("its target's MD
+ * tags disagree"; fate DAGCON_FATE_NONCONFORMING, counts 0): the target fails, or the windows those records meet; the
+ * rest of the batch is exact.  A match under one record and a letter from another at the same position is no conflict:
+ * the letter wins (step 1).  Whether a conflict exists does not depend on the order the device stores in, so the outcome
+ * is deterministic.  The bytes of a failed target in T are unspecified.
+ * The result is, byte for byte, that of dagcon_consensus_cigar / _windows / _packed on the same batch with t_blob = T:
+ * segments, target_status, dagcon_fetch_support, dagcon_fetch_positions, dagcon_fetch_edits, dagcon_fetch_record_stats
+ * and the counts in the timings.
+ * DAGCON_ERR_INVALID_ARG before any launch: md NULL while the batch has records, md_off + md_len > md_bytes, target
+ * ranges that are not ascending and disjoint (t_off[g] + tlen[g] <= t_off[g + 1]: two targets must not share bytes the
+ * device writes), and everything the CIGAR calls refuse.
+ * dagcon_fetch_md_targets gives T (t_bytes bytes, owned by the context) after such an upload until the next upload of any
+ * kind; DAGCON_ERR_STATE otherwise.
+ */
+typedef struct dagcon_md_tags {
+    const uint64_t *md_off;      /* [n_rec] the text behind "MD:Z:": md_blob[md_off .. + md_len) */
+    const uint32_t *md_len;
+    const char *md_blob;
+    uint64_t md_bytes;
+} dagcon_md_tags;
+int dagcon_upload_cigar_md(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows /* or NULL */,
+                           const dagcon_md_tags *md, int packed);
+int dagcon_consensus_cigar_md(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows /* or NULL */,
+                              const dagcon_md_tags *md, int packed, dagcon_results *results);
+int dagcon_fetch_md_targets(dagcon_ctx *ctx, const char **t_blob, uint64_t *t_bytes);
+
+/*
  * Picking the records (off by default).  The record calls above take every record the aligner wrote; with a filter set
  * on the context they rate every record on the device and leave some out before anything is built.  This build's own
  * rule, PARITY UNPINNED (the reference picks reads upstream, in m4topre.py and dazcon -m).  For a conforming record, over

@@ -42,6 +42,7 @@ EXPORTS = [
     "dagcon_upload_cs", "dagcon_consensus_cs",
     "dagcon_set_record_filter", "dagcon_fetch_record_stats",
     "dagcon_set_edits", "dagcon_fetch_edits",
+    "dagcon_upload_cigar_md", "dagcon_consensus_cigar_md", "dagcon_fetch_md_targets",
 ]
 ABI_VERSION = 2
 
@@ -84,6 +85,11 @@ class CsBatch(C.Structure):
                 ("t_bytes", C.c_uint64), ("rec_begin", C.c_void_p), ("pos", C.c_void_p), ("q_len", C.c_void_p),
                 ("t_span", C.c_void_p), ("cs_off", C.c_void_p), ("cs_len", C.c_void_p), ("cs_blob", C.c_void_p),
                 ("cs_bytes", C.c_uint64)]
+
+
+class MdTags(C.Structure):
+    """dagcon_md_tags: one MD:Z text per record of a dagcon_cigar_batch."""
+    _fields_ = [("md_off", C.c_void_p), ("md_len", C.c_void_p), ("md_blob", C.c_void_p), ("md_bytes", C.c_uint64)]
 
 
 class Windows(C.Structure):
@@ -195,6 +201,10 @@ def load() -> C.CDLL:
     L.dagcon_fetch_record_stats.argtypes = [vp, C.POINTER(RecordStats)]
     L.dagcon_set_edits.argtypes = [vp, C.c_int]
     L.dagcon_fetch_edits.argtypes = [vp, C.POINTER(Edits)]
+    L.dagcon_upload_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int]
+    L.dagcon_consensus_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int,
+                                            C.POINTER(Results)]
+    L.dagcon_fetch_md_targets.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.dagcon_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.dagcon_host_free.argtypes = [vp, vp]
     L.dagcon_host_free.restype = None
@@ -284,7 +294,8 @@ class HostCigarBatch:
     """numpy view of a dagcon_cigar_batch: per record a position, an ungapped read and BAM-encoded CIGAR ops
     (len << 4 | op), per target its bases once.  reverse (optional, one byte per record): the stranded calls
     (dagcon_upload_cigar_strand) -- q_blob holds the reads as the reads file has them and the device reads the bases of
-    a record with reverse != 0 backwards and complemented."""
+    a record with reverse != 0 backwards and complemented.  t_blob None: a batch without target bases, for the MD calls
+    (dagcon_upload_cigar_md), t_bytes the end of the last target."""
 
     def __init__(self, tlen, t_off, t_blob, rec_begin, pos, q_off, q_len, q_blob, op_begin, ops, ids=None, reverse=None):
         def u8(x):
@@ -292,7 +303,7 @@ class HostCigarBatch:
                                         dtype=np.uint8)
         self.tlen = np.ascontiguousarray(tlen, dtype=np.uint32)
         self.t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
-        self.t_blob = u8(t_blob)
+        self.t_blob = None if t_blob is None else u8(t_blob)
         self.rec_begin = np.ascontiguousarray(rec_begin, dtype=np.uint64)
         self.pos = np.ascontiguousarray(pos, dtype=np.uint32)
         self.q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
@@ -364,18 +375,24 @@ class HostCigarBatch:
         return int(self.pos.size)
 
     @property
+    def t_bytes(self):
+        if self.t_blob is not None:
+            return int(self.t_blob.size)
+        return int((self.t_off + self.tlen).max()) if self.tlen.size else 0
+
+    @property
     def nbytes(self):
         """Bytes the call carries to the device: both blobs, the ops and the per-record / per-target arrays."""
         return int(sum(a.nbytes for a in (self.tlen, self.t_off, self.t_blob, self.rec_begin, self.pos, self.q_off,
-                                          self.q_len, self.q_blob, self.op_begin, self.ops)))
+                                          self.q_len, self.q_blob, self.op_begin, self.ops) if a is not None))
 
     def c_struct(self) -> CigarBatch:
         b = CigarBatch()
         b.n_targets = self.n_targets
         b.tlen = self.tlen.ctypes.data
         b.t_off = self.t_off.ctypes.data
-        b.t_blob = self.t_blob.ctypes.data
-        b.t_bytes = self.t_blob.size
+        b.t_blob = None if self.t_blob is None else self.t_blob.ctypes.data
+        b.t_bytes = self.t_bytes
         b.rec_begin = self.rec_begin.ctypes.data
         b.pos = self.pos.ctypes.data
         b.q_off = self.q_off.ctypes.data
@@ -456,6 +473,42 @@ class HostCsBatch:
         b.cs_blob = self.cs_blob.ctypes.data
         b.cs_bytes = self.cs_blob.size
         return b
+
+
+class HostMdTags:
+    """numpy view of a dagcon_md_tags: the text behind each record's MD:Z: tag as the file has it, back to back."""
+
+    def __init__(self, md_off, md_len, md_blob):
+        self.md_off = np.ascontiguousarray(md_off, dtype=np.uint64)
+        self.md_len = np.ascontiguousarray(md_len, dtype=np.uint32)
+        self.md_blob = np.ascontiguousarray(np.frombuffer(md_blob, dtype=np.uint8)
+                                            if isinstance(md_blob, (bytes, bytearray)) else md_blob, dtype=np.uint8)
+        if self.md_off.shape != self.md_len.shape:
+            raise ValueError("md_off and md_len need one entry per record")
+
+    @classmethod
+    def from_texts(cls, texts):
+        """texts: one bytes / str per record, in record order."""
+        texts = [t.encode() if isinstance(t, str) else bytes(t) for t in texts]
+        ln = np.asarray([len(t) for t in texts], dtype=np.uint32)
+        off = np.zeros(len(texts), dtype=np.uint64)
+        if len(texts):
+            off[1:] = np.cumsum(ln.astype(np.uint64))[:-1]
+        return cls(off, ln, b"".join(texts))
+
+    @property
+    def n_records(self):
+        return int(self.md_off.size)
+
+    @property
+    def nbytes(self):
+        return int(self.md_off.nbytes + self.md_len.nbytes + self.md_blob.nbytes)
+
+    def c_struct(self) -> MdTags:
+        m = MdTags()
+        m.md_off, m.md_len, m.md_blob = self.md_off.ctypes.data, self.md_len.ctypes.data, self.md_blob.ctypes.data
+        m.md_bytes = self.md_blob.size
+        return m
 
 
 class HostWindows:
@@ -693,6 +746,41 @@ class Context:
     def consensus_cs(self, batch: HostCsBatch, windows: HostWindows = None, strict=True):
         """Per target (per window with windows): [(range0, range1, seq_bytes)], from cs:Z: text decoded on the device."""
         return self._intake(batch, windows, (batch, windows), True, strict)
+
+    def _intake_md(self, batch, md, windows, consensus, strict=True):
+        self._keep = (batch, md, windows)
+        b = batch.c_struct()
+        m = md.c_struct() if md is not None else None
+        w = windows.c_struct() if windows is not None else None
+        args = [self.h, C.byref(b), C.byref(w) if w is not None else None, C.byref(m) if m is not None else None,
+                1 if batch.is_packed else 0]
+        if not consensus:
+            self._chk(self.L.dagcon_upload_cigar_md(*args))
+            return None
+        r = Results()
+        self._chk(self.L.dagcon_consensus_cigar_md(*args, C.byref(r)))
+        out = self._keep_segs(r)
+        self._status(r, strict)
+        return out
+
+    def upload_cigar_md(self, batch: HostCigarBatch, md: "HostMdTags", windows: HostWindows = None):
+        """dagcon_upload_cigar_md: then run / sync / fetch as after upload.  batch.t_blob is not read (None is fine);
+        a HostCigarBatch.packed() batch selects the packed form."""
+        self._intake_md(batch, md, windows, False)
+
+    def consensus_cigar_md(self, batch: HostCigarBatch, md: "HostMdTags", windows: HostWindows = None, strict=True):
+        """Per target (per window with windows): [(range0, range1, seq_bytes)], the targets rebuilt on the device from
+        the records' MD:Z texts."""
+        return self._intake_md(batch, md, windows, True, strict)
+
+    def md_targets(self):
+        """dagcon_fetch_md_targets: the target blob the last upload_cigar_md / consensus_cigar_md rebuilt, a uint8 array
+        of t_bytes bytes (a copy)."""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.dagcon_fetch_md_targets(self.h, C.byref(ptr), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, np.uint8)
+        return np.ctypeslib.as_array((C.c_uint8 * int(n.value)).from_address(ptr.value)).copy()
 
     def set_record_filter(self, max_error_ppm=1000000, max_depth=0):
         """dagcon_set_record_filter for every later record call (CIGAR, packed, stranded, cs; whole targets and windows):

@@ -44,6 +44,10 @@ struct CigarBufs {
 struct CsBufs {
     DevBuf text, cs_off, cs_len, totals, n_ops, op_begin, t_base, t_room, q_off, q_len;
 };
+// dagcon_upload_cigar_md: the MD texts and what the k_md_* kernels take besides CigarBufs::t, which they fill
+struct MdBufs {
+    DevBuf text, md_off, md_len, totals, t_base, nt, tgt, mark, conflict;
+};
 // dagcon_align (align_device): blobs, offsets, outputs, directions, launch order, widths, ends; qaln / taln at out_off are
 // what dagcon_consensus_pre hands to the pipeline
 struct AlignBufs {
@@ -150,6 +154,10 @@ struct Ctx {
     PlaceBufs pl;                                   // dagcon_place
     CsBufs cs;                                      // dagcon_upload_cs
     CigarBufs cg;                                   // dagcon_upload_cigar and its kin
+    MdBufs md;                                      // dagcon_upload_cigar_md
+    bool md_valid = false, md_fetched = false;      // cg.t holds the targets such an upload rebuilt; h_md_t holds them too (dagcon_fetch_md_targets)
+    uint64_t md_bytes = 0;
+    std::vector<char> h_md_t;
     std::vector<uint8_t> h_cig_bad;                 // dagcon_upload_cigar: targets with a non-conforming record (empty: another upload)
     std::string cig_err;                            // the first of them, for dagcon_last_error
     bool filter_on = false;                         // dagcon_set_record_filter: the record intake rates and picks its records

@@ -1,8 +1,9 @@
-// api_records.hip.h -- the record intake (SAM, BAM, PAF, cs:Z:), its filter, the callers' page-locked memory, debugging aids
+// api_records.hip.h -- the record intake (SAM, BAM, PAF, cs:Z:, MD:Z:), its filter, the callers' page-locked memory, debugging aids
 // (one translation unit with dagcon_api.hip, which includes it once).
 namespace {
-// ---- record intake: dagcon_upload_cigar, _windows, _packed, _strand and dagcon_upload_cs ------------------------------
-// One path, upload_records: reset, scan, judge, rate, pick, plan, expand, hand-over.  Whole targets and windows differ in
+// ---- record intake: dagcon_upload_cigar, _windows, _packed, _strand, dagcon_upload_cs and dagcon_upload_cigar_md -------
+// One path, upload_records: reset, scan, judge, then records_finish: rate, pick, plan, expand, hand-over (upload_md makes
+// the targets between the scan and a judgement of its own, and joins at records_finish).  Whole targets and windows differ in
 // the plan alone (plan_whole / plan_windows); the input kinds differ in what cigar_scan uploads and in the kernels
 // cigar_rate and cigar_expand pick, both read off a RecordSource.  rate runs only when a record filter is set.
 
@@ -18,6 +19,8 @@ struct CsDecoded {
 //   DECODED         dagcon_upload_cs: ops, reads and targets are on the device already (CigarBufs::ops, q, t, made by
 //                   k_cs_write), b->ops and b->q_blob are NULL, b->q_off is the host's prefix sum of q_len; the scan's totals
 //                   must be k_cs_scan's for every conforming record, and the path goes on with k_cs_scan's
+//   rebuilt()       PLAIN or PACKED from dagcon_upload_cigar_md: the targets are made on the device (CigarBufs::t, by the
+//                   k_md_* kernels); b->t_blob is not read and may be NULL
 class RecordSource {
   public:
     enum Kind { PLAIN, PACKED, STRANDED, DECODED };
@@ -25,7 +28,9 @@ class RecordSource {
     static RecordSource packed() { return RecordSource(PACKED, nullptr); }
     static RecordSource stranded(const uint8_t *reverse) { return reverse ? RecordSource(STRANDED, reverse) : plain(); }
     static RecordSource decoded(const CsDecoded &cs) { return RecordSource(DECODED, &cs); }
+    static RecordSource rebuilt(bool packed) { RecordSource s(packed ? PACKED : PLAIN, nullptr); s.rebuilt_ = true; return s; }
     Kind kind() const { return kind_; }
+    bool rebuilt() const { return rebuilt_; }
     const uint8_t *reverse() const { return kind_ == STRANDED ? static_cast<const uint8_t *>(carried_) : nullptr; }
     const CsDecoded *cs() const { return kind_ == DECODED ? static_cast<const CsDecoded *>(carried_) : nullptr; }
 
@@ -33,6 +38,7 @@ class RecordSource {
     RecordSource(Kind k, const void *carried) : kind_(k), carried_(carried) {}
     Kind kind_;
     const void *carried_;
+    bool rebuilt_ = false;
 };
 
 // reset: what any upload does to the context's state first
@@ -41,12 +47,13 @@ Ctx *intake_reset(dagcon_ctx *ctx) {
     c->uploaded = c->ran = c->fetched = false;
     c->sup_valid = c->pos_valid = false;
     c->ed_batch = c->ed_valid = c->pos_pending = false;
+    c->md_valid = c->md_fetched = false;
     return c;
 }
 
 // the checks a dagcon_cigar_batch and a dagcon_cs_batch share: the targets, their records' ranges, and the record count
 int check_targets(Ctx *c, uint32_t T, const uint32_t *tlen, const uint64_t *t_off, const uint64_t *rec_begin, const char *t_blob, uint64_t t_bytes,
-                  bool have_record_arrays, uint32_t &n) {
+                  bool have_record_arrays, uint32_t &n, bool need_t_blob = true) {
     if (T && (!tlen || !rec_begin || !t_off)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
     const uint64_t n64 = T ? rec_begin[T] : 0;
     if (n64 > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "too many records");
@@ -56,7 +63,7 @@ int check_targets(Ctx *c, uint32_t T, const uint32_t *tlen, const uint64_t *t_of
     for (uint32_t g = 0; g < T; g++) {
         if (rec_begin[g + 1] < rec_begin[g] || rec_begin[g + 1] > n64) return fail(c, DAGCON_ERR_INVALID_ARG, "rec_begin not monotone at target %u", g);
         if (t_off[g] > t_bytes || tlen[g] > t_bytes - t_off[g]) return fail(c, DAGCON_ERR_INVALID_ARG, "target %u runs past t_blob", g);
-        if (tlen[g] && !t_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "t_blob is NULL");
+        if (tlen[g] && !t_blob && need_t_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "t_blob is NULL");
     }
     return DAGCON_OK;
 }
@@ -74,7 +81,7 @@ int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, const RecordSource &src, Cig
     const CsDecoded *cs = src.cs();
     const bool packed = src.kind() == RecordSource::PACKED;
     uint32_t n = 0;
-    int r = check_targets(c, b->n_targets, b->tlen, b->t_off, b->rec_begin, b->t_blob, b->t_bytes, b->pos && b->q_off && b->q_len && b->op_begin, n);
+    int r = check_targets(c, b->n_targets, b->tlen, b->t_off, b->rec_begin, b->t_blob, b->t_bytes, b->pos && b->q_off && b->q_len && b->op_begin, n, !src.rebuilt());
     if (r != DAGCON_OK) return r;
     std::vector<uint64_t> &tile_begin = sc.tile_begin;
     tile_begin.assign((size_t)n + 1, 0);
@@ -98,7 +105,7 @@ int cigar_scan(Ctx *c, const dagcon_cigar_batch *b, const RecordSource &src, Cig
     ENSURE(c, d.q, b->q_bytes); ENSURE(c, d.t, b->t_bytes);
     if (n_ops && !cs) HIPCHK(c, hipMemcpyAsync(d.ops.p, b->ops + b->op_begin[0], n_ops * 4, hipMemcpyHostToDevice, s));
     if (b->q_bytes && b->q_blob) HIPCHK(c, hipMemcpyAsync(d.q.p, b->q_blob, b->q_bytes, hipMemcpyHostToDevice, s));
-    if (b->t_bytes && b->t_blob && !cs) HIPCHK(c, hipMemcpyAsync(d.t.p, b->t_blob, b->t_bytes, hipMemcpyHostToDevice, s));
+    if (b->t_bytes && b->t_blob && !cs && !src.rebuilt()) HIPCHK(c, hipMemcpyAsync(d.t.p, b->t_blob, b->t_bytes, hipMemcpyHostToDevice, s));
     UPLOAD(c, d.q_off, b->q_off, n);
     UPLOAD(c, d.op_begin, opb);
     UPLOAD(c, d.tile_begin, tile_begin);
@@ -131,7 +138,8 @@ struct CigarVerdict {
     std::vector<const char *> why;                                 // [n]
     std::string first_err;
 };
-CigarVerdict cigar_judge(const dagcon_cigar_batch *b, const RecordSource &src, const CigarScan &sc) {
+// (more: per record what its MD text adds to the reasons below, dagcon_upload_cigar_md; nullptr: nothing)
+CigarVerdict cigar_judge(const dagcon_cigar_batch *b, const RecordSource &src, const CigarScan &sc, const std::vector<const char *> *more = nullptr) {
     CigarVerdict v;
     v.why.assign((size_t)sc.n, nullptr);
     for (uint32_t g = 0; g < b->n_targets; g++)
@@ -143,7 +151,8 @@ CigarVerdict cigar_judge(const dagcon_cigar_batch *b, const RecordSource &src, c
                             : (fl & DG_CG_OVERFLOW) ? "a total past 32 bits"
                             : b->pos[a] == 0 ? "pos is 0"
                             : nq != b->q_len[a] ? "the ops do not consume exactly q_len read bases"
-                            : (uint64_t)b->pos[a] - 1u + nt > b->tlen[g] ? "target bases past tlen" : nullptr;
+                            : (uint64_t)b->pos[a] - 1u + nt > b->tlen[g] ? "target bases past tlen"
+                            : more ? (*more)[a] : nullptr;
             v.why[a] = why;
             if (why && v.first_err.empty()) {
                 char buf[256];
@@ -484,17 +493,9 @@ int edits_arm(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
     return DAGCON_OK;
 }
 
-// SAM-style input: position + ungapped read + CIGAR per record, target bases once per target.  k_cigar_scan sizes every
-// record, the host plans the string blobs as for any batch, the expansion writes them into d_q / d_t, and upload_impl
-// takes them from there.  wn NULL: whole targets.  The strings never exist on the host.
-int upload_records(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, const RecordSource &src) {
-    if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = intake_reset(ctx);
+// what follows the scan and the judgement of every record intake: rate, pick, plan, expand, hand-over
+int records_finish(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn, const RecordSource &src, CigarScan &sc, const CigarVerdict &v) {
     int r;
-    if (wn && (r = check_windows(c, b, wn))) return r;
-    CigarScan sc;
-    if ((r = cigar_scan(c, b, src, sc))) return r;
-    const CigarVerdict v = cigar_judge(b, src, sc);
     CigarPick pk;
     pk.keep.assign((size_t)sc.n, 1);
     if (c->filter_on) {
@@ -506,6 +507,19 @@ int upload_records(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_wi
     if ((r = cigar_expand(c, b, src, sc, pl))) return r;
     if ((r = cigar_hand_over(ctx, c, b, pl, v, pk))) return r;
     return c->edits_on ? edits_arm(c, b, wn) : DAGCON_OK;
+}
+
+// SAM-style input: position + ungapped read + CIGAR per record, target bases once per target.  k_cigar_scan sizes every
+// record, the host plans the string blobs as for any batch, the expansion writes them into d_q / d_t, and upload_impl
+// takes them from there.  wn NULL: whole targets.  The strings never exist on the host.
+int upload_records(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, const RecordSource &src) {
+    if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = intake_reset(ctx);
+    int r;
+    if (wn && (r = check_windows(c, b, wn))) return r;
+    CigarScan sc;
+    if ((r = cigar_scan(c, b, src, sc))) return r;
+    return records_finish(ctx, c, b, wn, src, sc, cigar_judge(b, src, sc));
 }
 
 // minimap2's cs:Z: text per record, the target's bases once per target (include/dagcon.h has the rule).  k_cs_scan sizes
@@ -595,6 +609,112 @@ int upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *w
     return r;
 }
 
+const char *const MD_DISAGREE = "its target's MD tags disagree";
+
+// SAM / BAM records with one MD:Z text each and no target bases (include/dagcon.h has the rule).  The targets are rebuilt
+// in cg.t before the intake above runs on them: T is set to 'N', k_cigar_scan and k_md_scan size every record, the host
+// judges them, k_md_write / k_md_check store and compare the letters of the conforming ones, k_md_fill / k_md_fill_check
+// their read bases under M / = / X at positions no letter spells; a target whose tags disagree loses all its records.
+int upload_md_records(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn, const dagcon_md_tags *md, bool packed) {
+    int r;
+    if (wn && (r = check_windows(c, b, wn))) return r;
+    const uint32_t T = b->n_targets;
+    uint32_t n = 0;
+    if ((r = check_targets(c, T, b->tlen, b->t_off, b->rec_begin, nullptr, b->t_bytes, b->pos && b->q_off && b->q_len && b->op_begin, n, false))) return r;
+    if (n && (!md || !md->md_off || !md->md_len)) return fail(c, DAGCON_ERR_INVALID_ARG, "md is NULL");
+    for (uint32_t g = 0; g + 1 < T; g++)
+        if (b->t_off[g] + b->tlen[g] > b->t_off[g + 1])
+            return fail(c, DAGCON_ERR_INVALID_ARG, "targets %u and %u are not ascending and disjoint in the target blob", g, g + 1);
+    for (uint32_t a = 0; a < n; a++) {
+        if (md->md_off[a] > md->md_bytes || md->md_len[a] > md->md_bytes - md->md_off[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "record %u runs past md_blob", a);
+        if (md->md_len[a] && !md->md_blob) return fail(c, DAGCON_ERR_INVALID_ARG, "md_blob is NULL");
+    }
+    const uint64_t md_bytes = n ? md->md_bytes : 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    MdBufs &d = c->md;
+    CigarBufs &cg = c->cg;
+    ENSURE(c, cg.t, b->t_bytes); ENSURE(c, d.mark, b->t_bytes); ENSURE(c, d.conflict, T);
+    if (b->t_bytes) {
+        HIPCHK(c, hipMemsetAsync(cg.t.p, 'N', b->t_bytes, s));
+        HIPCHK(c, hipMemsetAsync(d.mark.p, 0, b->t_bytes, s));
+    }
+    if (T) HIPCHK(c, hipMemsetAsync(d.conflict.p, 0, T, s));
+    const RecordSource src = RecordSource::rebuilt(packed);
+    CigarScan sc;
+    if ((r = cigar_scan(c, b, src, sc))) return r;
+    ENSURE(c, d.text, md_bytes); ENSURE(c, d.totals, (size_t)n * 16);
+    std::vector<const char *> more((size_t)n, nullptr);
+    if (!n) return records_finish(ctx, c, b, wn, src, sc, cigar_judge(b, src, sc));
+    if (md_bytes && md->md_blob) HIPCHK(c, hipMemcpyAsync(d.text.p, md->md_blob, md_bytes, hipMemcpyHostToDevice, s));
+    UPLOAD(c, d.md_off, md->md_off, n); UPLOAD(c, d.md_len, md->md_len, n);
+    DgMdParams p;
+    memset(&p, 0, sizeof p);
+    p.md = d.text.as<const uint8_t>(); p.md_off = d.md_off.as<const uint64_t>(); p.md_len = d.md_len.as<const uint32_t>(); p.n = n;
+    p.totals = d.totals.as<uint4>();
+    const dim3 rec_grid((n + 3u) / 4u), rec_block(256);
+    hipLaunchKernelGGL(k_md_scan, rec_grid, rec_block, 0, s, p);
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint32_t> mtot((size_t)n * 4, 0);
+    HIPCHK(c, d2h(c, mtot.data(), d.totals.p, (size_t)n * 16));
+    for (uint32_t a = 0; a < n; a++) {
+        const uint32_t covered = mtot[(size_t)a * 4], fl = mtot[(size_t)a * 4 + 2];
+        more[a] = (fl & DG_MD_BAD) ? "MD: the text is empty, does not begin and end with a number, holds a byte that is no digit, letter or ^, a ^ that follows no number or "
+                                     "has no letter behind it, two letters in a row outside a deletion, more than 9 digits or a number of 2^28 or more"
+                : (fl & DG_CG_OVERFLOW) ? "MD: the bases covered do not fit 32 bits"
+                : covered != sc.tot[(size_t)a * 4 + 2] ? "MD: the text does not cover exactly the target bases the CIGAR consumes" : nullptr;
+    }
+    CigarVerdict v = cigar_judge(b, src, sc, &more);
+    // the conforming records: where each begins in T, how far it goes, whose it is
+    std::vector<uint64_t> t_base((size_t)n, DG_CG_SKIP);
+    std::vector<uint32_t> nt((size_t)n, 0), tgt((size_t)n, 0);
+    bool any = false;
+    for (uint32_t g = 0; g < T; g++)
+        for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) {
+            tgt[a] = g;
+            if (v.why[a]) continue;
+            t_base[a] = b->t_off[g] + b->pos[a] - 1u; nt[a] = sc.tot[a * 4 + 2];
+            any = true;
+        }
+    if (any) {
+        UPLOAD(c, d.t_base, t_base); UPLOAD(c, d.nt, nt); UPLOAD(c, d.tgt, tgt);
+        p.t = cg.t.as<uint8_t>(); p.mark = d.mark.as<uint8_t>(); p.t_base = d.t_base.as<const uint64_t>(); p.nt = d.nt.as<const uint32_t>();
+        p.tgt = d.tgt.as<const uint32_t>(); p.conflict = d.conflict.as<uint8_t>();
+        hipLaunchKernelGGL(k_md_write, rec_grid, rec_block, 0, s, p);
+        hipLaunchKernelGGL(k_md_check, rec_grid, rec_block, 0, s, p);
+        if (sc.p.n_tiles) {
+            const dim3 grid(sc.p.n_tiles), block(64);
+            if (packed) {
+                hipLaunchKernelGGL(k_md_fill_packed, grid, block, 0, s, sc.p, p);
+                hipLaunchKernelGGL(k_md_fill_check_packed, grid, block, 0, s, sc.p, p);
+            } else {
+                hipLaunchKernelGGL(k_md_fill, grid, block, 0, s, sc.p, p);
+                hipLaunchKernelGGL(k_md_fill_check, grid, block, 0, s, sc.p, p);
+            }
+        }
+        HIPCHK(c, hipGetLastError());
+        std::vector<uint8_t> conflict(T, 0);
+        HIPCHK(c, d2h(c, conflict.data(), d.conflict.p, T));
+        bool again = false;
+        for (uint32_t g = 0; g < T; g++)
+            if (conflict[g]) {
+                for (uint64_t a = b->rec_begin[g]; a < b->rec_begin[g + 1]; a++) more[a] = MD_DISAGREE;
+                again = true;
+            }
+        if (again) v = cigar_judge(b, src, sc, &more);
+    }
+    return records_finish(ctx, c, b, wn, src, sc, v);
+}
+int upload_md(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, const dagcon_md_tags *md, bool packed) {
+    if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = intake_reset(ctx);
+    const int r = upload_md_records(ctx, c, b, wn, md, packed);
+    if (r != DAGCON_OK) { (void)hipStreamSynchronize(c->stream); return r; }    // (the locals above may go)
+    c->md_valid = true;                                            // (cg.t holds the targets until the next upload)
+    c->md_bytes = b->t_bytes;
+    return DAGCON_OK;
+}
+
 // what every dagcon_consensus_* of this intake is: upload, run, fetch
 template <typename Upload>
 int upload_run_fetch(dagcon_ctx *ctx, dagcon_results *results, Upload upload) {
@@ -656,6 +776,29 @@ int dagcon_consensus_cigar_packed(dagcon_ctx *ctx, const dagcon_cigar_batch *bat
 int dagcon_consensus_cigar_strand(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, const uint8_t *reverse,
                                   dagcon_results *results) {
     return upload_run_fetch(ctx, results, [&] { return dagcon_upload_cigar_strand(ctx, batch, windows, reverse); });
+}
+
+int dagcon_upload_cigar_md(dagcon_ctx *ctx, const dagcon_cigar_batch *b, const dagcon_windows *wn, const dagcon_md_tags *md, int packed) {
+    return upload_md(ctx, b, wn, md, packed != 0);
+}
+int dagcon_consensus_cigar_md(dagcon_ctx *ctx, const dagcon_cigar_batch *batch, const dagcon_windows *windows, const dagcon_md_tags *md, int packed,
+                              dagcon_results *results) {
+    return upload_run_fetch(ctx, results, [&] { return dagcon_upload_cigar_md(ctx, batch, windows, md, packed); });
+}
+// the targets the last dagcon_upload_cigar_md rebuilt: copied from the device when first asked for
+int dagcon_fetch_md_targets(dagcon_ctx *ctx, const char **t_blob, uint64_t *t_bytes) {
+    if (!ctx || !t_blob || !t_bytes) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->md_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_md_targets: the last upload was not a dagcon_upload_cigar_md");
+    if (!c->md_fetched) {
+        c->h_md_t.resize(c->md_bytes + 1);
+        HIPCHK(c, hipSetDevice(c->device));
+        if (c->md_bytes) HIPCHK(c, d2h(c, c->h_md_t.data(), c->cg.t.p, c->md_bytes));
+        c->h_md_t[c->md_bytes] = 0;
+        c->md_fetched = true;
+    }
+    *t_blob = c->h_md_t.data(); *t_bytes = c->md_bytes;
+    return DAGCON_OK;
 }
 
 int dagcon_host_alloc(dagcon_ctx *ctx, size_t bytes, void **out) {

@@ -410,6 +410,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->ed_batch = c->ed_valid = c->pos_pending = false;     // (a record upload with edits on says so after the hand-over)
     c->h_cig_bad.clear();
     c->rs_valid = false;
+    c->md_valid = c->md_fetched = false;
     c->wide_cells = false;                             // (one batch with a very long insertion run does not slow the ones after it)
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->aln_begin)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/aln_begin is NULL");

@@ -29,6 +29,7 @@
 #include "k_cigar.hip.h"
 #include "k_rate.hip.h"
 #include "k_cs.hip.h"
+#include "k_md.hip.h"
 #include "k_edits.hip.h"
 #include "api_ctx.h"
 #include "api_run.hip.h"

@@ -323,7 +323,41 @@ struct DgBamRec {
     const uint8_t *ops;                // n_ops little-endian 32-bit words, len << 4 | op (not aligned: memcpy)
     uint32_t n_ops;
     unsigned long long ordinal;        // 1-based, counting every record of the file
+    const uint8_t *aux, *aux_end;      // the optional fields behind QUAL
 };
+
+// The one walker over a record's optional fields [t, end): the value of the first field tagged c0 c1 whose type is ty, or
+// NULL (also when a field runs past the record).  ty 'Z' / 'H': the text, n its length without the NUL; ty 'B': the
+// subtype byte (sub, when given, is the subtype asked for), then the 32-bit count, then the elements, n the count; any
+// other type: the value, n its width.
+inline const uint8_t *dg_bam_aux(const uint8_t *t, const uint8_t *end, char c0, char c1, uint8_t ty_want, size_t &n, uint8_t sub = 0) {
+    auto width = [](uint8_t y) -> size_t { return y == 'c' || y == 'C' || y == 'A' ? 1 : y == 's' || y == 'S' ? 2 : y == 'i' || y == 'I' || y == 'f' ? 4 : 0; };
+    while (end - t >= 3) {
+        const bool hit = t[0] == (uint8_t)c0 && t[1] == (uint8_t)c1 && t[2] == ty_want;
+        const uint8_t ty = t[2];
+        t += 3;
+        size_t sz = 0;
+        if (ty == 'Z' || ty == 'H') {
+            const void *z = memchr(t, 0, (size_t)(end - t));
+            if (!z) return nullptr;
+            sz = (size_t)((const uint8_t *)z - t) + 1;
+            if (hit) { n = sz - 1; return t; }
+        } else if (ty == 'B') {
+            if (end - t < 5) return nullptr;
+            const size_t w = width(t[0]);
+            const uint64_t cnt = (uint32_t)(t[1] | (uint32_t)t[2] << 8 | (uint32_t)t[3] << 16 | (uint32_t)t[4] << 24);
+            if (!w || cnt * w > (uint64_t)(end - t - 5)) return nullptr;
+            if (hit && (!sub || t[0] == sub)) { n = (size_t)cnt; return t; }
+            sz = 5 + (size_t)(cnt * w);
+        } else {
+            sz = width(ty);
+            if (!sz || sz > (size_t)(end - t)) return nullptr;
+            if (hit) { n = sz; return t; }
+        }
+        t += sz;
+    }
+    return nullptr;
+}
 
 // the letter of a 4-bit base code, for printing (--dump-parsed); the device decodes for itself (k_cigar.hip.h)
 inline char dg_bam_base(const uint8_t *seq, uint32_t i) { return "=ACMGRSVTWYHKDBN"[(seq[i >> 1] >> ((~i & 1u) * 4u)) & 15u]; }
@@ -392,34 +426,15 @@ struct DgBamReader {
             r.ops = b + 32 + l_name; r.n_ops = n_cig;
             r.seq = r.ops + 4ull * n_cig;
             r.ordinal = ord;
+            r.aux = b + need; r.aux_end = end;
             if ((flag & (0x4u | 0x100u)) || r.ref_id < 0 || n_cig == 0 || l_seq == 0) { n_skipped++; continue; }
             if ((uint64_t)r.ref_id >= refs.size()) { err = where + " (" + std::string(r.name, r.name_len) + "): refID " + std::to_string(r.ref_id) + " but the header has " + std::to_string(refs.size()) + " references"; return -1; }
             // more than 65,535 ops: <l_seq>S<ref_len>N in the record, the real ops in the CG:B,I tag
             if (n_cig == 2 && u32(r.ops) == (((uint32_t)l_seq << 4) | 4u) && (u32(r.ops + 4) & 15u) == 3u) {
-                const uint8_t *t = b + need;
-                bool found = false;
-                while (end - t >= 3) {
-                    const uint8_t c0 = t[0], c1 = t[1], ty = t[2];
-                    t += 3;
-                    size_t sz = 0;
-                    auto width = [](uint8_t y) -> size_t { return y == 'c' || y == 'C' || y == 'A' ? 1 : y == 's' || y == 'S' ? 2 : y == 'i' || y == 'I' || y == 'f' ? 4 : 0; };
-                    if (ty == 'Z' || ty == 'H') {
-                        const void *z = memchr(t, 0, (size_t)(end - t));
-                        if (!z) { t = end; break; }
-                        sz = (size_t)((const uint8_t *)z - t) + 1;
-                    } else if (ty == 'B') {
-                        if (end - t < 5) { t = end; break; }
-                        const size_t w = width(t[0]);
-                        const uint64_t cnt = u32(t + 1);
-                        if (!w || cnt * w > (uint64_t)(end - t - 5)) { t = end; break; }
-                        if (c0 == 'C' && c1 == 'G' && t[0] == 'I') { r.ops = t + 5; r.n_ops = (uint32_t)cnt; found = true; break; }
-                        sz = 5 + (size_t)(cnt * w);
-                    } else {
-                        sz = width(ty);
-                        if (!sz || sz > (size_t)(end - t)) { t = end; break; }
-                    }
-                    t += sz;
-                }
+                size_t cnt = 0;
+                const uint8_t *cg = dg_bam_aux(r.aux, r.aux_end, 'C', 'G', 'B', cnt, 'I');
+                const bool found = cg != nullptr;
+                if (found) { r.ops = cg + 5; r.n_ops = (uint32_t)cnt; }
                 if (!found || r.n_ops == 0) { err = where + " (" + std::string(r.name, r.name_len) + "): its CIGAR is the placeholder " + std::to_string(l_seq) + "S" + std::to_string(u32(b + 32 + l_name + 4) >> 4) + "N of a record with more than 65,535 ops, but it has no CG:B,I tag"; return -1; }
             }
             return 1;
@@ -441,7 +456,8 @@ inline bool dg_bam_check_refs(const DgBamReader &bam, const DgRefSeqs &ref, std:
 }
 
 // a record of the reader as the pipeline's record, the one place a DgBamRec becomes one: SEQ and the ops stay as they lie in the file
-inline void dg_bam_rec(const DgBamReader &bam, const DgBamRec &br, const DgRefSeqs &ref, DgAlnRec &r) {
+// (want_md: the md kinds look for the MD:Z field; a record without it is skipped by the caller)
+inline void dg_bam_rec(const DgBamReader &bam, const DgBamRec &br, const DgRefSeqs &ref, DgAlnRec &r, bool want_md = false) {
     const std::string &rn = bam.refs[(size_t)br.ref_id].name;
     r = DgAlnRec{};
     r.rname = rn.data(); r.rname_len = (uint32_t)rn.size(); r.target = ref.find(rn.data(), rn.size());
@@ -451,4 +467,14 @@ inline void dg_bam_rec(const DgBamReader &bam, const DgBamRec &br, const DgRefSe
     r.bam_ops = br.ops; r.nops = br.n_ops;
     r.reverse = (br.flag & DG_SAM_REVERSE) != 0;
     r.where = br.ordinal;
+    size_t n = 0;
+    const uint8_t *md = want_md ? dg_bam_aux(br.aux, br.aux_end, 'M', 'D', 'Z', n) : nullptr;
+    if (md) { r.md = (const char *)md; r.md_len = (uint32_t)n; }
+}
+
+// --md: the targets are the header's references, names and lengths only (ref.bases stays empty, a span's off is unused)
+inline bool dg_bam_header_refs(const DgBamReader &bam, DgRefSeqs &ref, std::string &err) {
+    for (const DgBamReader::Ref &r : bam.refs)
+        if (!ref.by_name.emplace(r.name, DgRefSeqs::Span{0, r.len}).second) { err = "BAM header: reference " + r.name + " occurs twice"; return false; }
+    return true;
 }

@@ -15,8 +15,13 @@ enum DgRecordKind {
     DG_REC_PLAIN,       // --sam: one base a byte                          dagcon_consensus_cigar / _cigar_windows
     DG_REC_PACKED,      // --bam: two bases a byte                         dagcon_consensus_cigar_packed
     DG_REC_STRANDED,    // --paf: one base a byte, a flag per record       dagcon_consensus_cigar_strand
-    DG_REC_CS           // --paf --cs: no bases, cs:Z: text per record     dagcon_consensus_cs
+    DG_REC_CS,          // --paf --cs: no bases, cs:Z: text per record     dagcon_consensus_cs
+    DG_REC_PLAIN_MD,    // --sam --md: one base a byte, MD:Z: text per record, no --ref       dagcon_consensus_cigar_md
+    DG_REC_PACKED_MD    // --bam --md: two bases a byte, MD:Z: text per record, no --ref      dagcon_consensus_cigar_md (packed)
 };
+constexpr bool dg_kind_md(DgRecordKind k) { return k == DG_REC_PLAIN_MD || k == DG_REC_PACKED_MD; }
+constexpr bool dg_kind_sam(DgRecordKind k) { return k == DG_REC_PLAIN || k == DG_REC_PLAIN_MD; }       // SAM text
+constexpr bool dg_kind_bam(DgRecordKind k) { return k == DG_REC_PACKED || k == DG_REC_PACKED_MD; }     // BAM records, packed bases
 
 // what the messages of a kind say
 struct DgKindDesc {
@@ -27,13 +32,16 @@ struct DgKindDesc {
     const char *nonconforming;                             // why DAGCON_ERR_NONCONFORMING came back for a target or a window
 };
 #define DG_CIGAR_UNFIT "a record's CIGAR does not fit its SEQ or its target, or holds N or a length of 0"
+#define DG_MD_UNFIT "a record's CIGAR does not fit its SEQ or its target, its MD:Z: text breaks the grammar or does not cover the target bases of its CIGAR, or the MD:Z: texts of the target disagree"
 inline const DgKindDesc &dg_kind(DgRecordKind k) {
-    static const DgKindDesc d[4] = {
+    static const DgKindDesc d[6] = {
         {"--sam", "dagcon_consensus_cigar", "line", "SAM", "SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')", DG_CIGAR_UNFIT},
         {"--bam", "dagcon_consensus_cigar_packed", "record", "BAM", "BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)", DG_CIGAR_UNFIT},
         {"--paf", "dagcon_consensus_cigar_strand", "line", "SAM", "PAF lines skipped (tp:A:S)", DG_CIGAR_UNFIT},
         {"--paf --cs", "dagcon_consensus_cs", "line", "SAM", "PAF lines skipped (tp:A:S)",
-         "a line's cs:Z: text breaks the grammar or does not fit its qe - qs, its te - ts or its target"}};
+         "a line's cs:Z: text breaks the grammar or does not fit its qe - qs, its te - ts or its target"},
+        {"--sam --md", "dagcon_consensus_cigar_md", "line", "SAM", "SAM records skipped (FLAG 0x4 or 0x100, or RNAME, CIGAR or SEQ '*')", DG_MD_UNFIT},
+        {"--bam --md", "dagcon_consensus_cigar_md", "record", "BAM", "BAM records skipped (FLAG 0x4 or 0x100, refID < 0, no CIGAR or no SEQ)", DG_MD_UNFIT}};
     return d[k];
 }
 
@@ -49,6 +57,7 @@ struct DgAlnRec {
     const uint8_t *bam_ops;                                // packed: the ops as they lie in the record (not aligned)
     uint32_t nops;                                         // ops of cigar / bam_ops (cs: 0)
     const char *cs; uint32_t cs_len, t_span;               // cs: the text behind cs:Z: and the target bases the line claims (te - ts)
+    const char *md; uint32_t md_len;                       // md kinds: the text behind MD:Z:
     bool reverse;                                          // the record's strand is '-' (stranded: the ops are written against the reverse
                                                            // complement of q, dagcon_upload_cigar_strand; every other kind: for printing)
     const char *read; uint32_t read_len, qs;               // stranded: the whole read and where q begins in it (--dump-parsed)
@@ -56,16 +65,16 @@ struct DgAlnRec {
 };
 
 // bytes of a record in a batch's q blob, and where they come from
-inline size_t dg_blob_bytes(DgRecordKind k, const DgAlnRec &r) { return k == DG_REC_CS ? r.cs_len : k == DG_REC_PACKED ? ((size_t)r.q_len + 1) / 2 : r.q_len; }
+inline size_t dg_blob_bytes(DgRecordKind k, const DgAlnRec &r) { return k == DG_REC_CS ? r.cs_len : dg_kind_bam(k) ? ((size_t)r.q_len + 1) / 2 : r.q_len; }
 inline const char *dg_blob(DgRecordKind k, const DgAlnRec &r) { return k == DG_REC_CS ? r.cs : r.q; }
 // the record's nops BAM-encoded ops to dst
 inline void dg_rec_ops(DgRecordKind k, const DgAlnRec &r, uint32_t *dst) {
-    if (k == DG_REC_PACKED) memcpy(dst, r.bam_ops, (size_t)r.nops * 4);
+    if (dg_kind_bam(k)) memcpy(dst, r.bam_ops, (size_t)r.nops * 4);
     else if (k != DG_REC_CS) dg_cigar_ops(r.cigar, r.cigar_len, dst);
 }
 
-// a split SAM line (DG_SAM_RECORD) as a record; pos: POS as the caller reads it
-inline void dg_sam_rec(const DgSamLine &l, uint32_t pos, unsigned long long lineno, const DgRefSeqs &ref, DgAlnRec &r) {
+// a split SAM line (DG_SAM_RECORD) as a record; pos: POS as the caller reads it; want_md: the md kinds look for the tag
+inline void dg_sam_rec(const DgSamLine &l, uint32_t pos, unsigned long long lineno, const DgRefSeqs &ref, DgAlnRec &r, bool want_md = false) {
     r = DgAlnRec{};
     r.rname = l.f[2]; r.rname_len = (uint32_t)l.fl[2]; r.target = ref.find(l.f[2], l.fl[2]);
     r.qname = l.f[0]; r.qname_len = (uint32_t)l.fl[0];
@@ -74,6 +83,7 @@ inline void dg_sam_rec(const DgSamLine &l, uint32_t pos, unsigned long long line
     r.cigar = l.f[5]; r.cigar_len = (uint32_t)l.fl[5]; r.nops = (uint32_t)l.nops;
     r.reverse = (l.flag & DG_SAM_REVERSE) != 0;
     r.where = lineno;
+    if (want_md && !dg_sam_md(l, r.md, r.md_len)) r.md = nullptr;     // (a record without the tag is skipped by the caller)
 }
 
 // the arrays of a batch: a dagcon_cigar_batch (DG_REC_CS: q_off / q_blob / q_bytes are the cs texts, op_begin / ops unused)
@@ -82,6 +92,7 @@ struct DgRecordArrays {
     dagcon_cigar_batch cb;
     const uint8_t *reverse;                                        // DG_REC_STRANDED
     const uint32_t *cs_len, *t_span;                               // DG_REC_CS
+    dagcon_md_tags md;                                             // the md kinds (cb.t_blob is then not read)
 };
 
 // windows NULL: whole targets
@@ -95,6 +106,7 @@ inline int dg_consensus_records(dagcon_ctx *ctx, DgRecordKind kind, const DgReco
         sb.cs_off = cb.q_off; sb.cs_len = a.cs_len; sb.cs_blob = cb.q_blob; sb.cs_bytes = cb.q_bytes;
         return dagcon_consensus_cs(ctx, &sb, windows, r);
     }
+    if (dg_kind_md(kind)) return dagcon_consensus_cigar_md(ctx, &cb, windows, &a.md, kind == DG_REC_PACKED_MD, r);
     return kind == DG_REC_PACKED ? dagcon_consensus_cigar_packed(ctx, &cb, windows, r)
          : kind == DG_REC_STRANDED ? dagcon_consensus_cigar_strand(ctx, &cb, windows, a.reverse, r)
          : windows ? dagcon_consensus_cigar_windows(ctx, &cb, windows, r) : dagcon_consensus_cigar(ctx, &cb, r);
@@ -140,6 +152,10 @@ inline const uint8_t *dg_record_fates(dagcon_ctx *ctx, uint64_t *n) {
     if (dagcon_fetch_record_stats(ctx, &st) != DAGCON_OK) return nullptr;
     *n = st.n;
     return st.fate;
+}
+// --md: the records left out for want of the tag, one line
+inline void dg_report_no_md(DgRecordKind k, unsigned long long n) {
+    if (n) fprintf(stderr, "pbdagcon: %llu %s records without an MD:Z: tag skipped (samtools calmd or minimap2 --MD write it)\n", n, dg_kind_sam(k) ? "SAM" : "BAM");
 }
 inline void dg_report_pick(const DgPick &pick, unsigned long long over_error, unsigned long long over_depth) {
     if (pick.on()) fprintf(stderr, "pbdagcon: records left out: %llu by --max-error, %llu by --max-depth\n", over_error, over_depth);

@@ -20,6 +20,8 @@
 //   * --sam, --bam, --paf --reads and --paf --cs, all with --ref: alignment records (a position, a CIGAR or cs:Z: text and the
 //     ungapped read, or no read at all) against a FASTA of the targets; what each format gives is in sam.h, bam.h and paf.h, the one
 //     record they all become and the per-kind description in intake.h.  The gapped strings are made on the GPU, never on the host;
+//   * --sam --md and --bam --md need no --ref: the targets' names and lengths come from the header, every record's MD:Z: text goes
+//     to the GPU, which rebuilds the target bases from CIGAR, SEQ and that text (include/dagcon.h, dagcon_md_tags);
 //   * blank lines are skipped (the reference duplicates the previous record, Q9);
 //   * a missing input file is an error on stderr, exit 1 (the reference is silent, Q11).
 #include <algorithm>
@@ -55,7 +57,7 @@ enum Mode { MODE_M5, MODE_PRE, MODE_RECORDS };             // BLASR -m 5 text; .
 struct Opts {
     unsigned threads = 4, min_cov = 6, min_len = 500, trim = 50;
     Mode mode = MODE_M5;                // what the input is, decided once by parse_args
-    DgRecordKind kind = DG_REC_PLAIN;   // MODE_RECORDS: --sam, --bam, --paf or --paf --cs (intake.h)
+    DgRecordKind kind = DG_REC_PLAIN;   // MODE_RECORDS: --sam, --bam, --paf, --paf --cs, --sam --md or --bam --md (intake.h)
     bool verbose = false, dump = false, local = false;   // local: --local (with -a), the first alignment of every record has local ends
     std::string ref, reads;            // --ref FASTA (MODE_RECORDS); --reads FASTA / FASTQ (with --paf)
     unsigned window = 0, overlap = 1000;   // --window W [--overlap O] (MODE_RECORDS): targets cut into windows (windows.h)
@@ -76,7 +78,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE]] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE]] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -93,7 +95,7 @@ void usage(FILE *f) {
             "                      POS, CIGAR and SEQ are used, the target's bases come from --ref; records with FLAG 0x4 or\n"
             "                      0x100, or RNAME, CIGAR or SEQ '*', are skipped (counted with -v).  The gapped strings are made\n"
             "                      on the GPU; the output is that of the .m5 input with the same alignments.  Not with -a,\n"
-            "                      --local or --polish.  MD:Z-only input (no FASTA) is not read\n"
+            "                      --local or --polish.  Without a FASTA: --md\n"
             "  --bam               input is BAM: everything --sam does, from the same records in a BAM file (BGZF inflated on the\n"
             "                      -j threads by this build's own decoder, CRC32 and ISIZE of every member checked).  refID, pos,\n"
             "                      flag, read_name, the CIGAR (from the CG tag when it has more than 65,535 ops) and seq are used;\n"
@@ -119,6 +121,19 @@ void usage(FILE *f) {
             "                      bases, or breaks the grammar, takes its target (with --window: the windows it touches) out\n"
             "                      with a warning.  Lines without cs:Z: are skipped and their count is printed.  Everything\n"
             "                      else is as with --paf --reads.  Not with --reads, --sam, --bam, -a, --local or --polish\n"
+            "  --md                with --sam or --bam, instead of --ref: no FASTA is needed.  Every record carries an MD:Z: tag\n"
+            "                      (BWA always writes it; minimap2 --MD and samtools calmd add it), which with CIGAR and SEQ\n"
+            "                      spells every target base the record touches.  The tag's text goes to the GPU as it lies in\n"
+            "                      the file, and the GPU rebuilds the targets: a base a letter of any record spells (a mismatch,\n"
+            "                      a deleted base) is that letter, otherwise the read base of a record that matches there, N\n"
+            "                      where no record reaches.  Target names and lengths come from the @SQ lines (--bam: the file's\n"
+            "                      reference list); a record whose RNAME has none is an error.  The text must match\n"
+            "                      [0-9]+(([A-Za-z]|^[A-Za-z]+)[0-9]+)* with numbers of at most 9 digits below 2^28 and cover\n"
+            "                      exactly the target bases of the CIGAR, else the record takes its target (with --window: the\n"
+            "                      windows it touches) out with a warning; so do all records of a target whose tags disagree\n"
+            "                      about a base.  Records without the tag are skipped and their count is printed.  --window,\n"
+            "                      --fastq, --edits (REF is the rebuilt target), --max-error and --max-depth work as with --ref.\n"
+            "                      This build's own rule, parity unpinned.  Not with --ref, --paf, -a, --local or --polish\n"
             "  --reads FILE        with --paf (required): the reads, FASTA (multi-line) or four-line FASTQ by the first byte,\n"
             "                      named by the first word of the header; a name that occurs twice is an error\n"
             "  --ref FASTA         with --sam, --bam or --paf (required): the target sequences, by the name up to the first blank; an @SQ line\n"
@@ -175,7 +190,7 @@ bool parse_uint(const char *s, unsigned *out) {
 }
 
 int parse_args(int argc, char **argv, Opts &o) {
-    bool align = false, sam = false, bam = false, paf = false, cs = false;   // -a, --sam, --bam, --paf, --cs as typed
+    bool align = false, sam = false, bam = false, paf = false, cs = false, md = false;   // -a, --sam, --bam, --paf, --cs, --md as typed
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](unsigned *dst) {
@@ -194,6 +209,7 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--bam") bam = true;
         else if (a == "--paf") paf = true;
         else if (a == "--cs") cs = true;
+        else if (a == "--md") md = true;
         else if (a == "--reads") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --reads needs a FASTA or FASTQ file\n"); return 2; }
             o.reads = argv[++i];
@@ -245,6 +261,9 @@ int parse_args(int argc, char **argv, Opts &o) {
         } else { fprintf(stderr, "PARSE ERROR: unknown argument %s\n", a.c_str()); return 2; }
     }
     if (o.local && !align) { fprintf(stderr, "PARSE ERROR: --local needs -a\n"); return 2; }
+    if (md && !sam && !bam) { fprintf(stderr, "PARSE ERROR: --md needs --sam or --bam\n"); return 2; }
+    if (md && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --md does not go with --ref (the MD:Z: tags stand in for the FASTA)\n"); return 2; }
+    if (md && (paf || align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --md does not go with --paf, -a, --local or --polish\n"); return 2; }
     if (cs && !paf) { fprintf(stderr, "PARSE ERROR: --cs needs --paf\n"); return 2; }
     if (cs && !o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --cs does not go with --reads (a cs:Z: tag and --ref are the whole alignment)\n"); return 2; }
     if (cs && (sam || bam || align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --cs does not go with --sam, --bam, -a, --local or --polish\n"); return 2; }
@@ -255,10 +274,10 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (!paf && !o.reads.empty()) { fprintf(stderr, "PARSE ERROR: --reads needs --paf\n"); return 2; }
     if (bam && sam) { fprintf(stderr, "PARSE ERROR: --bam and --sam do not go together\n"); return 2; }
     if (bam && (align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --bam does not go with -a, --local or --polish\n"); return 2; }
-    if (bam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --bam needs --ref <fasta>\n"); return 2; }
+    if (bam && o.ref.empty() && !md) { fprintf(stderr, "PARSE ERROR: --bam needs --ref <fasta>\n"); return 2; }
     const bool records = sam || bam || paf;
     if (sam && (align || o.local || o.polish)) { fprintf(stderr, "PARSE ERROR: --sam does not go with -a, --local or --polish\n"); return 2; }
-    if (sam && o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --sam needs --ref <fasta>\n"); return 2; }
+    if (sam && o.ref.empty() && !md) { fprintf(stderr, "PARSE ERROR: --sam needs --ref <fasta>\n"); return 2; }
     if (!records && !o.ref.empty()) { fprintf(stderr, "PARSE ERROR: --ref needs --sam, --bam or --paf\n"); return 2; }
     if (o.window && (!records || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --window needs --sam, --bam or --paf and does not go with -a or --polish\n"); return 2; }
     if (o.pick.on() && !records) { fprintf(stderr, "PARSE ERROR: --max-error and --max-depth need --sam, --bam or --paf\n"); return 2; }
@@ -268,7 +287,7 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (o.window && (uint64_t)o.overlap < (uint64_t)o.trim + 64) { fprintf(stderr, "PARSE ERROR: --overlap must be at least --trim + 64 (%u)\n", o.trim + 64); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
     o.mode = records ? MODE_RECORDS : align ? MODE_PRE : MODE_M5;
-    o.kind = cs ? DG_REC_CS : paf ? DG_REC_STRANDED : bam ? DG_REC_PACKED : DG_REC_PLAIN;
+    o.kind = cs ? DG_REC_CS : paf ? DG_REC_STRANDED : bam ? (md ? DG_REC_PACKED_MD : DG_REC_PACKED) : md ? DG_REC_PLAIN_MD : DG_REC_PLAIN;
     return 0;
 }
 
@@ -342,12 +361,15 @@ struct Batch {
     std::vector<const char *> tsrc;
     std::vector<uint32_t> ops, cs_len, tspan;
     std::vector<uint8_t> reverse;
+    std::vector<uint64_t> md_off;      // md kinds: every record's MD:Z: text in md
+    std::vector<uint32_t> md_len;
+    std::string md;
     Blob q, t;
     unsigned long long seq = 0;        // position in the input: records are printed in this order
     std::string out;                   // the batch's FASTA records
     std::string edits;                 // --edits: the batch's lines of that file
     unsigned long long n_edits = 0;
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; }
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; }
 };
 
 FILE *g_edits = nullptr;                                  // --edits FILE, written batch by batch in output order
@@ -449,11 +471,21 @@ int run_records(dagcon_ctx *ctx, Batch &b, const Opts &o) {
     ra.cb.pos = b.start.data(); ra.cb.q_off = b.off.data(); ra.cb.q_len = b.len.data();
     ra.cb.q_blob = b.q.data(); ra.cb.q_bytes = b.q.size(); ra.cb.op_begin = b.opb.data(); ra.cb.ops = b.ops.data();
     ra.reverse = o.kind == DG_REC_STRANDED ? b.reverse.data() : nullptr; ra.cs_len = b.cs_len.data(); ra.t_span = b.tspan.data();
+    if (dg_kind_md(o.kind)) {                               // (b.t is not read: the device makes the targets)
+        ra.cb.t_blob = nullptr;
+        ra.md.md_off = b.md_off.data(); ra.md.md_len = b.md_len.data(); ra.md.md_blob = b.md.data(); ra.md.md_bytes = b.md.size();
+    }
     dagcon_results r;
     const double t0 = wall();
     const int rc = dg_consensus_records(ctx, o.kind, ra, nullptr, &r);
     if (g_timing) fprintf(stderr, "pbdagcon timing: %s%s batch of %zu records: %s %.3f\n", dg_kind(o.kind).flag, o.pick.text().c_str(), b.start.size(), dg_kind(o.kind).entry, wall() - t0);
     if (!ok(ctx, rc, "consensus")) return 1;
+    if (dg_kind_md(o.kind) && !o.edits.empty()) {           // REF of the edits: the targets as the device rebuilt them, in b.t's layout
+        const char *tb = nullptr;
+        uint64_t tn = 0;
+        if (!ok(ctx, dagcon_fetch_md_targets(ctx, &tb, &tn), "rebuilt targets")) return 1;
+        memcpy(b.t.data(), tb, std::min<uint64_t>(tn, b.t.size()));
+    }
     uint64_t n_fate = 0;
     if (const uint8_t *fate = dg_record_fates(ctx, &n_fate)) {
         unsigned long long over_error = 0, over_depth = 0;
@@ -820,7 +852,7 @@ struct Input {
 
 // what one thread found in its piece of a slab
 template <class R>
-struct Part { std::vector<R> recs; int err = 0; unsigned long long err_rec = 0; int err_nf = 0; unsigned long long lines = 0, skipped = 0; };
+struct Part { std::vector<R> recs; int err = 0; unsigned long long err_rec = 0; int err_nf = 0; unsigned long long lines = 0, skipped = 0, no_md = 0; };
 
 // what the two indexers share: the slab's records in file order (the carried ones first), up to the first malformed one
 template <class R>
@@ -849,7 +881,7 @@ struct Indexer {
         }
         on_threads(nthr, [&](unsigned k) {
             Part<R> &pt = parts[k];
-            pt.recs.clear(); pt.err = 0; pt.lines = 0; pt.skipped = 0;
+            pt.recs.clear(); pt.err = 0; pt.lines = 0; pt.skipped = 0; pt.no_md = 0;
             for (size_t pos = cut[k]; pos < cut[k + 1];) {
                 const char *text = in.data + pos;
                 const size_t ll = dg_line(in.data, in.size, pos);
@@ -962,26 +994,27 @@ struct RecordIndexer : Indexer<DgAlnRec> {
     const Opts &o; const DgKindDesc &kd; const DgRefSeqs &ref;
     DgBamReader &bam;
     const DgPafInput &paf;
-    unsigned long long n_lines_before = 0, n_skipped = 0;
+    unsigned long long n_lines_before = 0, n_skipped = 0, n_no_md = 0;
     std::unordered_set<std::string> seen_targets;         // a target whose records come back after another's is an error
 
     RecordIndexer(Input &i, const Opts &opts, const DgRefSeqs &rf, DgBamReader &bm, const DgPafInput &pf)
         : Indexer<DgAlnRec>(i), o(opts), kd(dg_kind(opts.kind)), ref(rf), bam(bm), paf(pf) {}
 
     size_t index(size_t s0, size_t slab_bytes) {
-        if (o.kind == DG_REC_PLAIN) return index_sam(s0, in.line_end(std::min(in.size, s0 + slab_bytes)));
+        if (dg_kind_sam(o.kind)) return index_sam(s0, in.line_end(std::min(in.size, s0 + slab_bytes)));
         begin();
         Part<DgAlnRec> &pt = parts[0];
         pt.recs.clear();
-        if (o.kind == DG_REC_PACKED) {
+        if (dg_kind_bam(o.kind)) {
             const size_t s1 = std::min(in.size, s0 + slab_bytes);
             DgBamRec br; DgAlnRec r; std::string err;
             while (bam.at < s1) {                          // (the reader stops behind the first record that ends at s1 or later)
                 const int rc = bam.next(br, err);
                 if (rc == 0) break;
                 if (rc < 0) { fprintf(stderr, "pbdagcon: format error: %s\n", err.c_str()); had_error = true; break; }
-                dg_bam_rec(bam, br, ref, r);
+                dg_bam_rec(bam, br, ref, r, dg_kind_md(o.kind));
                 if (!r.target) { fprintf(stderr, "pbdagcon: record %llu: RNAME is not a sequence of %s\n", br.ordinal, o.ref.c_str()); had_error = true; break; }
+                if (dg_kind_md(o.kind) && !r.md) { n_no_md++; continue; }
                 pt.recs.push_back(r);
             }
             n_skipped = bam.n_skipped;
@@ -1005,20 +1038,22 @@ struct RecordIndexer : Indexer<DgAlnRec> {
             if (what == DG_SAM_FEW_FIELDS) { pt.err = 1; pt.err_nf = sm.nf; return false; }
             if (what == DG_SAM_BAD_CIGAR) { pt.err = 3; return false; }
             DgAlnRec r;
-            dg_sam_rec(sm, tok_u32(sm.f[3], sm.fl[3]), pt.lines, ref, r);
+            dg_sam_rec(sm, tok_u32(sm.f[3], sm.fl[3]), pt.lines, ref, r, dg_kind_md(o.kind));
             if (!r.target) { pt.err = 4; return false; }
+            if (dg_kind_md(o.kind) && !r.md) { pt.no_md++; return true; }
             pt.recs.push_back(r);
             return true;
         });
         begin();
         for (Part<DgAlnRec> &pt : parts) {
             for (DgAlnRec &r : pt.recs) r.where += n_lines_before;      // line numbers of the whole input
-            n_skipped += pt.skipped;
+            n_skipped += pt.skipped; n_no_md += pt.no_md;
             take(pt);
             if (pt.err) {
                 const unsigned long long ln = n_lines_before + pt.err_rec;
                 if (pt.err == 1) fprintf(stderr, "pbdagcon: format error: line %llu has %d fields, 11 expected\n", ln, pt.err_nf);
                 else if (pt.err == 3) fprintf(stderr, "pbdagcon: format error: line %llu: malformed CIGAR\n", ln);
+                else if (dg_kind_md(o.kind)) fprintf(stderr, "pbdagcon: line %llu: RNAME has no @SQ line in the header (--md takes the targets' names and lengths from there)\n", ln);
                 else fprintf(stderr, "pbdagcon: line %llu: RNAME is not a sequence of %s\n", ln, o.ref.c_str());
                 had_error = true; break;
             }
@@ -1034,7 +1069,7 @@ struct RecordIndexer : Indexer<DgAlnRec> {
         }
         b.ids.emplace_back(r.rname, r.rname_len);
         b.tlen.push_back(r.target->len);
-        b.toff.push_back(bytes2); b.tsrc.push_back(ref.bases.data() + r.target->off); bytes2 += r.target->len;
+        b.toff.push_back(bytes2); b.tsrc.push_back(dg_kind_md(o.kind) ? nullptr : ref.bases.data() + r.target->off); bytes2 += r.target->len;
         return true;
     }
     void add_record(Batch &b, const DgAlnRec &r, size_t &bytes, size_t &) {
@@ -1043,13 +1078,14 @@ struct RecordIndexer : Indexer<DgAlnRec> {
         b.off.push_back(bytes); b.len.push_back(r.q_len);
         b.reverse.push_back(r.reverse ? 1 : 0);
         if (o.kind == DG_REC_CS) { b.cs_len.push_back(r.cs_len); b.tspan.push_back(r.t_span); }
+        if (dg_kind_md(o.kind)) { b.md_off.push_back(b.md.size()); b.md_len.push_back(r.md_len); b.md.append(r.md, r.md_len); }
         bytes += dg_blob_bytes(o.kind, r);
     }
     // the targets' bases, once each; of every record its bytes of the q blob as they lie in the input and its ops
     void fill(Batch &b, size_t r0, size_t r1) {
         b.ops.resize(b.opb.back());
         on_threads(in.nthr, [&](unsigned k) {
-            for (size_t g = k; g < b.tsrc.size(); g += in.nthr) memcpy(b.t.data() + b.toff[g], b.tsrc[g], b.tlen[g]);
+            for (size_t g = k; g < b.tsrc.size(); g += in.nthr) if (b.tsrc[g]) memcpy(b.t.data() + b.toff[g], b.tsrc[g], b.tlen[g]);
             for (size_t x = r0 + k; x < r1; x += in.nthr) {
                 const DgAlnRec &r = *recs[x];
                 memcpy(b.q.data() + b.off[x - r0], dg_blob(o.kind, r), dg_blob_bytes(o.kind, r));
@@ -1065,9 +1101,9 @@ struct RecordIndexer : Indexer<DgAlnRec> {
         for (size_t y = r0; y < r1; y++) {
             const DgAlnRec &r = *recs[y];
             const char *q = b.q.data() + b.off[y - r0];
-            std::string seq(q, o.kind == DG_REC_PLAIN ? r.q_len : 0);
+            std::string seq(q, dg_kind_sam(o.kind) ? r.q_len : 0);
             std::string cigar = dg_cigar_text(b.ops.data() + b.opb[y - r0], b.opb[y - r0 + 1] - b.opb[y - r0]);
-            if (o.kind == DG_REC_PACKED) {
+            if (dg_kind_bam(o.kind)) {
                 for (uint32_t i = 0; i < r.q_len; i++) seq += dg_bam_base((const uint8_t *)q, i);
             } else if (o.kind == DG_REC_STRANDED) {
                 const uint32_t c0 = r.reverse ? r.read_len - r.qs - r.q_len : r.qs, c1 = r.read_len - r.q_len - c0;
@@ -1078,11 +1114,16 @@ struct RecordIndexer : Indexer<DgAlnRec> {
                 if (!dg_cs_decode(q, r.cs_len, ref.bases.data() + r.target->off, r.target->len, r.pos, seq, dops)) { seq = "*"; dops.clear(); }
                 cigar = dg_cigar_text(dops.data(), dops.size());
             }
-            printf("%.*s\t%u\t%u\t%c\t%.*s\t%s\t%s\n", (int)r.rname_len, r.rname, r.target->len, r.pos, r.reverse ? '-' : '+',
+            printf("%.*s\t%u\t%u\t%c\t%.*s\t%s\t%s", (int)r.rname_len, r.rname, r.target->len, r.pos, r.reverse ? '-' : '+',
                    (int)r.qname_len, r.qname, seq.c_str(), cigar.c_str());
+            if (dg_kind_md(o.kind)) printf("\t%.*s", (int)b.md_len[y - r0], b.md.data() + b.md_off[y - r0]);   // (the text as the batch carries it)
+            putchar('\n');
         }
     }
-    void report_skipped() { if (o.verbose) fprintf(stderr, "pbdagcon: %llu %s\n", n_skipped, kd.skipped_what); }
+    void report_skipped() {
+        if (o.verbose) fprintf(stderr, "pbdagcon: %llu %s\n", n_skipped, kd.skipped_what);
+        dg_report_no_md(o.kind, n_no_md);
+    }
 };
 
 // per slab: index -> group into batches -> fill -> submit (or dump); the status
@@ -1160,15 +1201,18 @@ int main(int argc, char **argv) {
     size_t first = 0;                                      // where the first record lies
     if (o.mode == MODE_RECORDS) {
         std::string err;
-        bool good = dg_read_fasta(o.ref, ref, err);
+        bool good = dg_kind_md(o.kind) || dg_read_fasta(o.ref, ref, err);
         if (good && o.kind == DG_REC_PLAIN) good = dg_sam_check_header(in.data, in.size, ref, err);
-        if (good && o.kind == DG_REC_PACKED) good = bam.open((const uint8_t *)in.data, in.size, o.threads, err) && dg_bam_check_refs(bam, ref, err);
+        if (good && o.kind == DG_REC_PLAIN_MD) good = dg_sam_header_refs(in.data, in.size, ref, err);
+        if (good && dg_kind_bam(o.kind)) good = bam.open((const uint8_t *)in.data, in.size, o.threads, err);
+        if (good && o.kind == DG_REC_PACKED) good = dg_bam_check_refs(bam, ref, err);
+        if (good && o.kind == DG_REC_PACKED_MD) good = dg_bam_header_refs(bam, ref, err);
         paf.cs = o.kind == DG_REC_CS;
         if (good && o.kind == DG_REC_STRANDED) good = dg_read_reads(o.reads, paf.reads, err);
         if (good && (o.kind == DG_REC_STRANDED || o.kind == DG_REC_CS)) good = paf.parse(in.data, in.size, ref, err);
         if (!good) { fprintf(stderr, "pbdagcon: %s\n", err.c_str()); return 1; }
     }
-    if (o.mode == MODE_RECORDS && o.kind == DG_REC_PACKED) {
+    if (o.mode == MODE_RECORDS && dg_kind_bam(o.kind)) {
         const DgBgzfStats &bs = bam.stats;
         if (o.verbose && !bs.eof_member) fprintf(stderr, "pbdagcon: note: the BAM file does not end with the empty BGZF member (it may be incomplete)\n");
         if (g_timing)
@@ -1182,6 +1226,8 @@ int main(int argc, char **argv) {
     if (o.window && !o.dump) {
         DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0], o.pick, o.edits.empty() ? nullptr : o.edits.c_str()};
         if (o.kind == DG_REC_PACKED) { DgBamSource src(bam, ref); return dg_run_windows(wo, src, ref); }
+        if (o.kind == DG_REC_PACKED_MD) { DgBamMdSource src(bam, ref); return dg_run_windows(wo, src, ref); }
+        if (o.kind == DG_REC_PLAIN_MD) { DgSamMdSource src(in.data, in.size, ref); return dg_run_windows(wo, src, ref); }
         if (o.kind == DG_REC_CS) { DgPafCsSource src(paf); return dg_run_windows(wo, src, ref); }
         if (o.kind == DG_REC_STRANDED) { DgPafSource src(paf); return dg_run_windows(wo, src, ref); }
         DgSamSource src(in.data, in.size, ref);

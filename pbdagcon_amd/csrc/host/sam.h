@@ -1,7 +1,11 @@
 // sam.h -- what `pbdagcon --sam --ref` needs of SAM and FASTA text: the reference sequences by name, CIGAR text to
 // BAM-encoded ops (len << 4 | op, op 0..8 = M I D N S H P = X: dagcon_cigar_batch in include/dagcon.h), the @SQ lines
-// of the header against the FASTA.  Text only (BAM: bam.h; PAF: paf.h); MD:Z-only input is not read.  Line ends are LF (a CR in
-// front of it is dropped with the line's last field, as the .m5 parser drops it).
+// of the header against the FASTA.  Text only (BAM: bam.h; PAF: paf.h).  Line ends are LF (a CR in front of it is dropped
+// with the line's last field, as the .m5 parser drops it).
+// `pbdagcon --sam --md` needs no FASTA: the targets' names and lengths come from the @SQ lines (dg_sam_header_refs), every
+// record's MD:Z: text (dg_sam_md: the first optional field that begins MD:Z:) goes to the device as it lies in the line,
+// and the device rebuilds the target bases from CIGAR, SEQ and that text (include/dagcon.h, dagcon_md_tags; this build's
+// own rule, parity unpinned).  Records without the tag are skipped and counted.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -114,6 +118,7 @@ inline long dg_cigar_ops(const char *s, size_t n, uint32_t *out) {
 // number of the CIGAR's ops.  flag_of(field, length) reads FLAG the caller's way; every caller words its own errors.
 struct DgSamLine {
     const char *f[10]; size_t fl[10];
+    const char *rest; size_t rest_len;                     // what follows SEQ's tab: QUAL and the optional fields
     int nf;                                                // fields found, at most 10
     uint32_t flag;
     long nops;                                             // DG_SAM_RECORD only
@@ -122,6 +127,7 @@ enum DgSamWhat { DG_SAM_RECORD, DG_SAM_NO_RECORD /* empty, or a header line */, 
 template <class FlagOf>
 inline DgSamWhat dg_sam_split(const char *line, size_t ll, DgSamLine &s, FlagOf flag_of) {
     s.nf = 0;
+    s.rest = line + ll; s.rest_len = 0;
     if (ll == 0 || line[0] == '@') return DG_SAM_NO_RECORD;
     for (size_t i = 0; s.nf < 10;) {
         const char *tab = (const char *)memchr(line + i, '\t', ll - i);
@@ -129,6 +135,7 @@ inline DgSamWhat dg_sam_split(const char *line, size_t ll, DgSamLine &s, FlagOf 
         s.f[s.nf] = line + i; s.fl[s.nf] = j - i; s.nf++;
         if (!tab) break;
         i = j + 1;
+        if (s.nf == 10) { s.rest = line + i; s.rest_len = ll - i; }
     }
     if (s.nf < 10) return DG_SAM_FEW_FIELDS;
     s.flag = (uint32_t)flag_of(s.f[1], s.fl[1]);
@@ -136,6 +143,19 @@ inline DgSamWhat dg_sam_split(const char *line, size_t ll, DgSamLine &s, FlagOf 
     if ((s.flag & (DG_SAM_UNMAPPED | DG_SAM_SECONDARY)) || star(2) || star(5) || star(9)) return DG_SAM_SKIPPED;
     s.nops = dg_cigar_ops(s.f[5], s.fl[5], nullptr);
     return s.nops < 0 ? DG_SAM_BAD_CIGAR : DG_SAM_RECORD;
+}
+
+// the text behind the first optional field of a split line that begins MD:Z: (the fields behind QUAL); false: there is none
+inline bool dg_sam_md(const DgSamLine &s, const char *&md, uint32_t &md_len) {
+    const char *p = s.rest, *end = s.rest + s.rest_len;
+    for (int field = 0; p < end; field++) {
+        const char *tab = (const char *)memchr(p, '\t', (size_t)(end - p));
+        const char *e = tab ? tab : end;
+        if (field >= 1 && e - p >= 5 && memcmp(p, "MD:Z:", 5) == 0) { md = p + 5; md_len = (uint32_t)(e - p - 5); return true; }
+        if (!tab) break;
+        p = tab + 1;
+    }
+    return false;
 }
 
 // the CIGAR text of BAM-encoded ops (--dump-parsed)
@@ -176,6 +196,36 @@ inline bool dg_sam_check_header(const char *data, size_t size, const DgRefSeqs &
                   " but the --ref sequence of that name has " + std::to_string(sp->len) + " bases";
             return false;
         }
+    }
+    return true;
+}
+
+// --md: the targets are the header's @SQ lines, names and lengths only (ref.bases stays empty, a span's off is unused);
+// false with a message in err for an @SQ without SN or LN, an LN that is no number below 2^32, or a name that occurs twice
+inline bool dg_sam_header_refs(const char *data, size_t size, DgRefSeqs &ref, std::string &err) {
+    size_t pos = 0;
+    unsigned long long lineno = 0;
+    while (pos < size && data[pos] == '@') {
+        const char *line = data + pos;
+        const size_t ll = dg_line(data, size, pos);
+        lineno++;
+        if (ll < 4 || memcmp(line, "@SQ\t", 4) != 0) continue;
+        const char *sn = nullptr, *ln = nullptr;
+        size_t snl = 0, lnl = 0;
+        for (size_t i = 4; i < ll;) {
+            const char *tab = (const char *)memchr(line + i, '\t', ll - i);
+            const size_t j = tab ? (size_t)(tab - line) : ll;
+            if (j - i >= 3 && line[i + 2] == ':') {
+                if (line[i] == 'S' && line[i + 1] == 'N') { sn = line + i + 3; snl = j - i - 3; }
+                if (line[i] == 'L' && line[i + 1] == 'N') { ln = line + i + 3; lnl = j - i - 3; }
+            }
+            i = j + 1;
+        }
+        uint64_t v = 0;
+        size_t k = 0;
+        for (; ln && k < lnl && ln[k] >= '0' && ln[k] <= '9' && v < (1ull << 40); k++) v = v * 10 + (uint64_t)(ln[k] - '0');
+        if (!sn || !ln || !lnl || k < lnl || v > 0xFFFFFFFFull) { err = "line " + std::to_string(lineno) + ": an @SQ line needs SN and a numeric LN below 2^32"; return false; }
+        if (!ref.by_name.emplace(std::string(sn, snl), DgRefSeqs::Span{0, (uint32_t)v}).second) { err = "line " + std::to_string(lineno) + ": @SQ SN:" + std::string(sn, snl) + " occurs twice"; return false; }
     }
     return true;
 }

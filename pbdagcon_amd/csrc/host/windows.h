@@ -10,6 +10,9 @@
 // must be consecutive and ascending in POS, as in a coordinate-sorted SAM.  The records come from a source of DgAlnRecs
 // (DgSamSource, DgBamSource; DgPafSource and DgPafCsSource in paf.h; a cs record's [s, e) is the line's own [ts, te)) and go
 // to the device as intake.h says for the source's kind; grouping, batching and the stitch do not know which.
+// The md kinds (--sam --md, --bam --md) have no --ref: a group's targets are laid out back to back in a blob the device
+// rebuilds (dagcon_consensus_cigar_md), and --edits takes its REF column from dagcon_fetch_md_targets, group by group (every
+// record that covers a base of a group's windows is in the group, so a group's stretch of a target is the whole run's).
 //
 // The stitch (DgStitch; tests/window_twin.py: stitch is its numpy twin).  With g = pos + window begin the 1-based
 // target position of a consensus base (dagcon_fetch_positions): of a window's segment the bases from the first one
@@ -159,12 +162,13 @@ struct DgWinOpts {
 };
 
 // SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
-struct DgSamSource {
-    static constexpr DgRecordKind kind = DG_REC_PLAIN;
+template <bool MD>
+struct DgSamSourceT {
+    static constexpr DgRecordKind kind = MD ? DG_REC_PLAIN_MD : DG_REC_PLAIN;
     const char *data; size_t size, p = 0;
     const DgRefSeqs &ref;
-    unsigned long long lineno = 0, skipped = 0;
-    DgSamSource(const char *d, size_t n, const DgRefSeqs &rf) : data(d), size(n), ref(rf) {}
+    unsigned long long lineno = 0, skipped = 0, no_md = 0;
+    DgSamSourceT(const char *d, size_t n, const DgRefSeqs &rf) : data(d), size(n), ref(rf) {}
     // 1: a record; 0: the end; -1: an error (printed)
     int next(DgAlnRec &r) {
         while (p < size) {
@@ -182,36 +186,50 @@ struct DgSamSource {
                 case DG_SAM_RECORD: break;
             }
             const uint64_t pos = digits(sl.f[3], sl.fl[3], true);
-            dg_sam_rec(sl, pos > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pos, lineno, ref, r);
+            dg_sam_rec(sl, pos > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pos, lineno, ref, r, MD);
+            if (MD && !r.md) { no_md++; continue; }
             return 1;
         }
         return 0;
     }
 };
+using DgSamSource = DgSamSourceT<false>;
+using DgSamMdSource = DgSamSourceT<true>;
 
 // BAM records (bam.h); the header's references were checked against --ref when the file was opened
-struct DgBamSource {
-    static constexpr DgRecordKind kind = DG_REC_PACKED;
+template <bool MD>
+struct DgBamSourceT {
+    static constexpr DgRecordKind kind = MD ? DG_REC_PACKED_MD : DG_REC_PACKED;
     DgBamReader &bam;
     const DgRefSeqs &ref;
-    unsigned long long skipped = 0;
-    DgBamSource(DgBamReader &b, const DgRefSeqs &rf) : bam(b), ref(rf) {}
+    unsigned long long skipped = 0, no_md = 0;
+    DgBamSourceT(DgBamReader &b, const DgRefSeqs &rf) : bam(b), ref(rf) {}
     int next(DgAlnRec &r) {
-        DgBamRec br;
-        std::string err;
-        const int rc = bam.next(br, err);
-        skipped = bam.n_skipped;
-        if (rc < 0) fprintf(stderr, "pbdagcon: format error: %s\n", err.c_str());
-        if (rc > 0) dg_bam_rec(bam, br, ref, r);
-        return rc;
+        for (;;) {
+            DgBamRec br;
+            std::string err;
+            const int rc = bam.next(br, err);
+            skipped = bam.n_skipped;
+            if (rc < 0) fprintf(stderr, "pbdagcon: format error: %s\n", err.c_str());
+            if (rc > 0) dg_bam_rec(bam, br, ref, r, MD);
+            if (MD && rc > 0 && !r.md) { no_md++; continue; }
+            return rc;
+        }
     }
 };
+using DgBamSource = DgBamSourceT<false>;
+using DgBamMdSource = DgBamSourceT<true>;
+
+// the records a source left out for want of an MD:Z: tag (the md sources count them)
+template <class Source> auto dg_source_no_md(const Source &s, int) -> decltype(s.no_md) { return s.no_md; }
+template <class Source> unsigned long long dg_source_no_md(const Source &, long) { return 0; }
 
 // the whole run; the process's exit status
 template <class Source>
 inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref) {
-    struct Rec { uint32_t pos, s, e, q_len; const char *q; size_t q_bytes; uint64_t op0; uint32_t nops; bool reverse; uint32_t t_span; };   // q, q_bytes: its bytes of the q blob
-    struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; std::vector<uint8_t> fate; };   // fate: DAGCON_FATE_* per record, over all groups
+    struct Rec { uint32_t pos, s, e, q_len; const char *q; size_t q_bytes; uint64_t op0; uint32_t nops; bool reverse; uint32_t t_span; const char *md; uint32_t md_len; };   // q, q_bytes: its bytes of the q blob
+    struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; std::vector<uint8_t> fate; std::string rebuilt; };   // fate: DAGCON_FATE_* per record, over all groups; rebuilt: md kinds with --edits, the target as the device made it
+    constexpr bool MD = dg_kind_md(Source::kind);
     std::vector<Tgt> tgts;
     std::vector<uint32_t> ops;
     std::unordered_map<std::string, int> seen;
@@ -224,7 +242,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         dg_rec_ops(Source::kind, ar, ops.data() + ops.size() - ar.nops);
         const std::string rname(ar.rname, ar.rname_len);
         if (tgts.empty() || tgts.back().name != rname) {
-            if (!ar.target) { fprintf(stderr, "pbdagcon: %s %llu: RNAME %s is not a sequence of --ref\n", kd.unit, ar.where, rname.c_str()); return 1; }
+            if (!ar.target) { fprintf(stderr, MD ? "pbdagcon: %s %llu: RNAME %s has no @SQ line / reference in the header\n" : "pbdagcon: %s %llu: RNAME %s is not a sequence of --ref\n", kd.unit, ar.where, rname.c_str()); return 1; }
             if (!seen.emplace(rname, 1).second) { fprintf(stderr, "pbdagcon: %s %llu: records of RNAME %s come back after another target's (records of one RNAME must be consecutive)\n", kd.unit, ar.where, rname.c_str()); return 1; }
             tgts.emplace_back();
             tgts.back().name = rname; tgts.back().sp = *ar.target;
@@ -236,6 +254,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         r.q = dg_blob(Source::kind, ar); r.q_len = ar.q_len; r.q_bytes = dg_blob_bytes(Source::kind, ar); r.op0 = ops.size() - ar.nops; r.nops = ar.nops;
         r.reverse = (Source::kind == DG_REC_STRANDED) && ar.reverse;
         r.t_span = ar.t_span;
+        r.md = ar.md; r.md_len = ar.md_len;
         const long k = (long)ar.nops;
         // [s, e) by the rule of include/dagcon.h (a non-conforming record: clipped into the target, at least one base)
         uint64_t nt = 0;
@@ -251,6 +270,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         t.recs.push_back(r);
     }
     if (o.verbose && src.skipped) fprintf(stderr, "pbdagcon: %llu %s\n", src.skipped, kd.skipped_what);
+    dg_report_no_md(Source::kind, dg_source_no_md(src, 0));
     // ---- the windows of every target, in target order ----
     struct Win { uint32_t tgt, idx, begin, end, c0, c1; };
     std::vector<Win> wins;
@@ -285,8 +305,8 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         out.clear();
         if (ef) {
             // a #piece line with the span its edits apply to, then the edits: REF from --ref, ALT from the piece
-            const Tgt &t = tgts[(size_t)cur_tgt];
-            const char *tb = ref.bases.data() + t.sp.off;
+            Tgt &t = tgts[(size_t)cur_tgt];
+            const char *tb = MD ? t.rebuilt.data() : ref.bases.data() + t.sp.off;
             for (const DgStitchPiece &p : st.pieces) {
                 if (p.seq.size() < o.min_len) continue;
                 out += "#piece " + t.name + " " + std::to_string(p.e0) + " " + std::to_string(p.e1) + "\n";
@@ -301,6 +321,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             }
             fwrite(out.data(), 1, out.size(), ef);
             out.clear();
+            std::string().swap(t.rebuilt);
         }
         st.reset();
         return true;
@@ -315,13 +336,20 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         std::vector<uint8_t> b_rev;                            // stranded sources: one flag per record
         std::vector<uint32_t> b_cslen, b_tspan;                // cs sources: qblob holds the texts
         std::vector<uint8_t *> b_fate;                         // where each record's fate is kept (a record goes out with every group it meets)
+        std::vector<uint64_t> b_mdoff;                         // md sources: the texts, back to back in mdblob
+        std::vector<uint32_t> b_mdlen;
+        std::string mdblob;
+        uint64_t t_bytes = 0;                                  // md sources: the group's targets back to back
+        struct Stretch { Tgt *t; uint64_t off; uint32_t lo, hi; };
+        std::vector<Stretch> stretches;                        // md sources with --edits: what of each target the group rebuilds
         for (size_t a = w0; a < w1;) {
             size_t z = a;
             while (z < w1 && wins[z].tgt == wins[a].tgt) z++;
             Tgt &t = tgts[wins[a].tgt];
             const uint32_t lo = wins[a].begin, hi = wins[z - 1].end;
             const uint32_t bt = (uint32_t)b_tlen.size();
-            b_tlen.push_back(t.sp.len); b_toff.push_back(t.sp.off);
+            b_tlen.push_back(t.sp.len); b_toff.push_back(MD ? t_bytes : t.sp.off);
+            if (MD) { if (ef) stretches.push_back(Stretch{&t, t_bytes, lo, hi}); t_bytes += t.sp.len; }
             // records are ascending in s: none that starts more than the longest span in front of lo reaches it
             const uint32_t from = lo > t.max_span ? lo - t.max_span : 0u;
             auto it = std::lower_bound(t.recs.begin(), t.recs.end(), from, [](const Rec &r, uint32_t v) { return r.s < v; });
@@ -334,6 +362,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
                 b_ops.insert(b_ops.end(), ops.begin() + (long)it->op0, ops.begin() + (long)(it->op0 + it->nops));
                 b_opb.push_back(b_ops.size());
                 if ((Source::kind == DG_REC_STRANDED)) b_rev.push_back(it->reverse ? 1 : 0);
+                if (MD) { b_mdoff.push_back(mdblob.size()); b_mdlen.push_back(it->md_len); mdblob.append(it->md, it->md_len); }
             }
             b_rec.push_back(b_pos.size());
             for (size_t k = a; k < z; k++) { w_t.push_back(bt); w_b.push_back(wins[k].begin); w_e.push_back(wins[k].end); }
@@ -341,7 +370,8 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         }
         DgRecordArrays ra{};
         ra.cb.n_targets = (uint32_t)b_tlen.size(); ra.cb.tlen = b_tlen.data(); ra.cb.t_off = b_toff.data();
-        ra.cb.t_blob = ref.bases.data(); ra.cb.t_bytes = ref.bases.size();
+        ra.cb.t_blob = MD ? nullptr : ref.bases.data(); ra.cb.t_bytes = MD ? t_bytes : ref.bases.size();
+        ra.md.md_off = b_mdoff.data(); ra.md.md_len = b_mdlen.data(); ra.md.md_blob = mdblob.data(); ra.md.md_bytes = mdblob.size();
         ra.cb.rec_begin = b_rec.data(); ra.cb.pos = b_pos.data(); ra.cb.q_off = b_qoff.data(); ra.cb.q_len = b_qlen.data();
         ra.cb.q_blob = qblob.data(); ra.cb.q_bytes = qblob.size(); ra.cb.op_begin = b_opb.data(); ra.cb.ops = b_ops.data();
         ra.reverse = b_rev.data(); ra.cs_len = b_cslen.data(); ra.t_span = b_tspan.data();
@@ -358,6 +388,16 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         dagcon_edits ed;
         memset(&ed, 0, sizeof ed);
         if (rc == DAGCON_OK && ef) rc = dagcon_fetch_edits(ctx, &ed);
+        if (rc == DAGCON_OK && ef && MD) {                     // REF of the edits: the group's stretch of every target, as the device rebuilt it
+            const char *tb = nullptr;
+            uint64_t tn = 0;
+            rc = dagcon_fetch_md_targets(ctx, &tb, &tn);
+            for (size_t k = 0; rc == DAGCON_OK && k < stretches.size(); k++) {
+                const Stretch &x = stretches[k];
+                if (x.t->rebuilt.empty()) x.t->rebuilt.assign(x.t->sp.len, 'N');
+                memcpy(&x.t->rebuilt[x.lo], tb + x.off + x.lo, x.hi - x.lo);
+            }
+        }
         if (rc != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); status = 1; break; }
         uint64_t n_fate = 0;
         if (const uint8_t *fate = dg_record_fates(ctx, &n_fate))
@@ -371,7 +411,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             const size_t g = k - w0;
             if (r.target_status[g] != DAGCON_OK)
                 fprintf(stderr, "pbdagcon: warning: %s window [%u, %u) skipped (%s)\n", tgts[w.tgt].name.c_str(), w.begin, w.end,
-                        dg_status_text(r.target_status[g], DG_CIGAR_UNFIT));
+                        dg_status_text(r.target_status[g], MD ? kd.nonconforming : DG_CIGAR_UNFIT));
             if (o.verbose) fprintf(stderr, "pbdagcon: %s window %u [%u, %u): %llu segments\n", tgts[w.tgt].name.c_str(), w.idx, w.begin, w.end,
                                    (unsigned long long)(r.seg_begin[g + 1] - r.seg_begin[g]));
             for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {

@@ -259,6 +259,56 @@ int dagcon_set_edits(dagcon_ctx *ctx, int on);
 int dagcon_fetch_edits(dagcon_ctx *ctx, dagcon_edits *out);
 
 /*
+ * Read support per edit: how many alignments stand behind each edit of dagcon_edits (off by default; a second switch
+ * behind dagcon_set_edits).  This is this build's own rule, PARITY UNPINNED: the reference has no such output.
+ * DAGCON_FLAG_BASE_SUPPORT cannot answer the question: it has a weight only for vertices on the best path, a deletion
+ * has no base to carry a weight, and the target's own allele is not on the path.
+ * Everything is relative to a target of the pipeline: a target of the batch, or with windows a window.
+ *   - T[0, tlen) are its bytes as the record intake left them.
+ *   - A segment has span [t0, t1) and consensus bytes S.
+ *   - Its edits are e_0 .. e_{m-1}, ascending, as (t_pos, t_len, c, c_len) with c relative to S.
+ *   - x ~ y means the two bytes are equal after clearing bit 0x20 in both.
+ * 1. Window of an edit.  Start with L = t_pos, R = t_pos + t_len.  Clamps: lo = t_pos + t_len of the edit before it, or
+ *    t0 for the first edit; hi = t_pos of the edit behind it, or t1 for the last edit.  Only a pure insertion or a pure
+ *    deletion is extended, that is an edit where exactly one of t_len, c_len is 0.  Let u be the k bytes of the
+ *    non-empty side.  Left: while L > lo and T[L-1] ~ u[(k-1-j) mod k], with j the steps taken so far, do L--.  Right:
+ *    while R < hi and T[R] ~ u[j mod k], do R++.  So the window covers every place the same indel could have been
+ *    written in a repeat.  L and R are non-decreasing along the segment.
+ * 2. Groups.  Edit i > 0 joins the group of edit i-1 iff L_i <= R_{i-1}: the windows touch or overlap.  A group's
+ *    window is [gL, gR) = [L of its first edit, R of its last edit).  Its ref allele is T[gL, gR).  Its alt allele is
+ *    S[cL, cR), with cL = c_first - (t_pos_first - gL) and cR = c_last + c_len_last + (gR - t_pos_last - t_len_last).
+ *    The edits invariant makes the bytes between edits identical on both sides.  Two groups of a segment are separated
+ *    by at least one target base.
+ * 3. The alignments counted are the target's alignments of at least min_len columns, as the graph took them: after
+ *    normalizeGaps and trimAln, and non-empty.  Alignment a has columns (q, t).  Its first target base is s0 (its
+ *    start after the trim, 0-based).  It covers [s0, e0).  A column's coordinate tc is s0 plus the target-base columns
+ *    in front of it.
+ *    Spanning: the alignment spans the group iff both hold: gL > 0 ? s0 <= gL-1 : s0 == 0, and
+ *    gR < tlen ? e0-1 >= gR : e0 == tlen.
+ *    Allele: the alignment's allele is its q bytes other than the gap, taken from the columns with tc >= gL and
+ *    (tc < gR, or tc == gR with a gap in t).  Insertions at either end of the window belong to it.
+ *    Flanks: the flanks are good iff the column holding target base gL-1 has a read base ~ its target base, and
+ *    likewise for the column of base gR.  A flank exists when gL > 0 (left flank) or gR < tlen (right flank).  A flank
+ *    that does not exist asks nothing.
+ *    Class: alt: the flanks are good and the allele ~ the alt allele (same length, byte by byte).  ref: otherwise, the
+ *    flanks are good and the allele ~ the ref allele.  other: every remaining spanning alignment.  Alt is tested first.
+ * 4. Output is per edit, n == dagcon_edits.n, in the same order.  Every edit of a group carries the group's values:
+ *    w_begin = gL, w_end = gR, span: the spanning alignments, alt: those in class alt, ref: those in class ref.
+ *    alt + ref <= span <= the target's alignment count.  A failed target has no entries.
+ * dagcon_set_edit_support: DAGCON_ERR_STATE unless dagcon_set_edits is on; turning edits off turns this off.  With the
+ * switch off no kernel, buffer, launch or copy differs; with it on three more kernels run behind the edit kernels
+ * (csrc/k_evidence.hip.h) and the arrays come back in the fetch's second round beside the edit records.
+ * dagcon_fetch_edit_support is valid exactly when dagcon_fetch_edits is and the switch was on at the upload;
+ * DAGCON_ERR_STATE otherwise.  The arrays are owned by the context, valid as long as the results of the same fetch.
+ */
+typedef struct dagcon_edit_support {
+    uint64_t n;                                          /* == dagcon_edits.n */
+    const uint32_t *w_begin, *w_end, *span, *alt, *ref;  /* [n] */
+} dagcon_edit_support;
+int dagcon_set_edit_support(dagcon_ctx *ctx, int on);
+int dagcon_fetch_edit_support(dagcon_ctx *ctx, dagcon_edit_support *out);
+
+/*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses
  * alignment records straight into such a buffer gets its dagcon_upload at link speed instead of
  * through the driver's staging copies.  Optional: any host memory is accepted by dagcon_upload.

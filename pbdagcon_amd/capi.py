@@ -42,6 +42,7 @@ EXPORTS = [
     "dagcon_upload_cs", "dagcon_consensus_cs",
     "dagcon_set_record_filter", "dagcon_fetch_record_stats",
     "dagcon_set_edits", "dagcon_fetch_edits",
+    "dagcon_set_edit_support", "dagcon_fetch_edit_support",
     "dagcon_upload_cigar_md", "dagcon_consensus_cigar_md", "dagcon_fetch_md_targets",
 ]
 ABI_VERSION = 2
@@ -120,6 +121,12 @@ class RecordStats(C.Structure):
 
 
 FATE_MAX_ERROR, FATE_MAX_DEPTH, FATE_NONCONFORMING = 1, 2, 4
+
+
+class EditSupport(C.Structure):
+    """dagcon_edit_support: per edit its group's window and the alignments behind it (include/dagcon.h has the rule)."""
+    _fields_ = [("n", C.c_uint64), ("w_begin", C.POINTER(C.c_uint32)), ("w_end", C.POINTER(C.c_uint32)),
+                ("span", C.POINTER(C.c_uint32)), ("alt", C.POINTER(C.c_uint32)), ("ref", C.POINTER(C.c_uint32))]
 
 
 class Edits(C.Structure):
@@ -201,6 +208,8 @@ def load() -> C.CDLL:
     L.dagcon_fetch_record_stats.argtypes = [vp, C.POINTER(RecordStats)]
     L.dagcon_set_edits.argtypes = [vp, C.c_int]
     L.dagcon_fetch_edits.argtypes = [vp, C.POINTER(Edits)]
+    L.dagcon_set_edit_support.argtypes = [vp, C.c_int]
+    L.dagcon_fetch_edit_support.argtypes = [vp, C.POINTER(EditSupport)]
     L.dagcon_upload_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int]
     L.dagcon_consensus_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int,
                                             C.POINTER(Results)]
@@ -808,6 +817,19 @@ class Context:
         """dagcon_set_edits for every later record call (a FLAG_BASE_POS context): the device lists where each segment
         differs from its target (edits())."""
         self._chk(self.L.dagcon_set_edits(self.h, 1 if on else 0))
+
+    def set_edit_support(self, on=True):
+        """dagcon_set_edit_support for every later record call (set_edits must be on): the device counts, per edit, the
+        alignments that span its window and those that carry the consensus' or the target's allele (edit_support())."""
+        self._chk(self.L.dagcon_set_edit_support(self.h, 1 if on else 0))
+
+    def edit_support(self) -> dict:
+        """dagcon_fetch_edit_support (copies): w_begin, w_end, span, alt, ref (uint32, one per edit of edits())."""
+        e = EditSupport()
+        self._chk(self.L.dagcon_fetch_edit_support(self.h, C.byref(e)))
+        n = int(e.n)
+        return {k: (np.ctypeslib.as_array(getattr(e, k), shape=(n,)).copy() if n else np.zeros(0, np.uint32))
+                for k in ("w_begin", "w_end", "span", "alt", "ref")}
 
     def edits(self) -> dict:
         """dagcon_fetch_edits (copies): seg_t0, seg_t1 (uint32, one per segment of the last results, in their order),

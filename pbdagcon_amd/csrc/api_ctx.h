@@ -84,14 +84,15 @@ struct RunBufs {
     DevBuf sup_tmp, sup_tmp0, sup;                  // DAGCON_FLAG_BASE_SUPPORT: walk scratch (4 B per vertex), output (2 x 2 B per base)
     DevBuf pos_tmp, pos_tmp0, pos;                  // DAGCON_FLAG_BASE_POS: walk scratch (4 B per vertex), output (4 B per base)
     DevBuf ed_seg, ed_out;                          // dagcon_set_edits: a DgEdSeg per segment, a DgEdit per edit
-    std::array<DevBuf *, 58> all() {
+    DevBuf evid;                                    // dagcon_set_edit_support: a DgEvid per edit
+    std::array<DevBuf *, 59> all() {
         return {&nmis, &n_lo, &n_hi, &n_start, &n_ins, &n_del, &ch_k0, &ch_next, &ch_w, &ch_tb, &ch_flag, &ch_src, &ch_out, &ch_adv, &n_lb, &norm_tmp, &ckpt,
                 &node_base, &n_nodes, &pool_base, &pool_size, &pool_top, &t_nins, &cov, &gcount, &gbase, &bid, &best, &queue, &score, &cns_tmp, &bp_tt,
                 &stk, &cuts, &cuts_bp, &bp_stat, &bp_len, &rd, &pro_state, &sh_cnt, &wl_first, &queue0, &bp_end, &bp_ab, &defer, &cns_tmp0, &cns,
-                &seg, &worklist, &seg_done, &sup_tmp, &sup_tmp0, &sup, &pos_tmp, &pos_tmp0, &pos, &ed_seg, &ed_out};
+                &seg, &worklist, &seg_done, &sup_tmp, &sup_tmp0, &sup, &pos_tmp, &pos_tmp0, &pos, &ed_seg, &ed_out, &evid};
     }
 };
-static_assert(sizeof(RunBufs) == 58 * sizeof(DevBuf), "RunBufs::all() must name every member");
+static_assert(sizeof(RunBufs) == 59 * sizeof(DevBuf), "RunBufs::all() must name every member");
 // ArenaBufs: the arenas with a treatment of their own -- matC is cleared before every run, the others are filled under
 // DAGCON_POISON bits 1 (matA, matD), 2 (nodes, pool) and 4 (score_b, norm)
 struct ArenaBufs {
@@ -169,6 +170,8 @@ struct Ctx {
     // dagcon_set_edits: the switch; whether the batch on the device is a record upload made under it (its buffers:
     // run.ed_seg, run.ed_out, in.ed_tbase)
     bool edits_on = false, ed_batch = false;
+    // dagcon_set_edit_support: the switch (on only while edits_on is); whether the batch on the device was armed under it
+    bool evid_on = false, evid_batch = false;
     std::vector<uint64_t> h_ed_tbase;
     uint64_t ed_cap = 0;
     long ed_cap_env = 0;                            // DAGCON_EDITS_CAP (tests): first size of the edit arena, so that the re-run is met
@@ -200,6 +203,8 @@ struct Ctx {
     bool ed_valid = false;              // the arrays below are those of the last fetch (dagcon_fetch_edits)
     std::vector<uint32_t> e_t0, e_t1, e_tpos, e_tlen, e_clen;
     std::vector<uint64_t> e_begin, e_coff;
+    bool evid_valid = false;              // the arrays below are those of the last fetch (dagcon_fetch_edit_support)
+    std::vector<uint32_t> v_begin, v_end, v_span, v_alt, v_ref;
     bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
 
     // debug dump storage

@@ -47,6 +47,7 @@ Ctx *intake_reset(dagcon_ctx *ctx) {
     c->uploaded = c->ran = c->fetched = false;
     c->sup_valid = c->pos_valid = false;
     c->ed_batch = c->ed_valid = c->pos_pending = false;
+    c->evid_batch = c->evid_valid = false;
     c->md_valid = c->md_fetched = false;
     return c;
 }
@@ -484,6 +485,7 @@ int edits_arm(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
     c->h_ed_tbase.assign(T, 0);
     for (uint32_t t = 0; t < T; t++) c->h_ed_tbase[t] = wn ? b->t_off[wn->target[t]] + wn->begin[t] : b->t_off[t];
     c->ed_batch = true;
+    c->evid_batch = c->evid_on;
     c->ed_cap = c->ed_cap_env > 0 ? (uint64_t)c->ed_cap_env : std::max<uint64_t>(c->ed_cap, c->sum_bb / 8 + 1024);
     int r;
     UPLOAD(c, c->in.ed_tbase, c->h_ed_tbase);

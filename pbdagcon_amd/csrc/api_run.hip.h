@@ -119,6 +119,7 @@ int ensure_arenas(Ctx *c) {
     if (c->ed_batch) {
         ENSURE(c, c->run.ed_seg, c->seg_cap * sizeof(DgEdSeg));
         ENSURE(c, c->run.ed_out, c->ed_cap * sizeof(DgEdit));
+        if (c->evid_batch) ENSURE(c, c->run.evid, c->ed_cap * sizeof(DgEvid));
     }
     ENSURE(c, c->run.seg, 2 * seg_stride(c) * 4);
     if (int r = c->r_seg.reserve(c, 2 * (size_t)c->seg_cap * 4)) return r;
@@ -204,6 +205,7 @@ void fill_params(Ctx *c, DgParams &p) {
         p.ed_seg = c->run.ed_seg.as<DgEdSeg>(); p.ed_out = c->run.ed_out.as<DgEdit>(); p.ed_cap = c->ed_cap;
         p.ed_top = c->sb.d<unsigned long long>(c->sb.o_ed_top);
         p.ed_t = c->cg.t.as<const uint8_t>(); p.ed_tbase = c->in.ed_tbase.as<const uint64_t>();
+        if (c->evid_batch) p.evid = c->run.evid.as<DgEvid>();
     }
 }
 
@@ -333,6 +335,12 @@ int launch_all(Ctx *c) {
             hipLaunchKernelGGL(k_ed_scan_seg<false>, eg, dim3(256), 0, s, p);
             hipLaunchKernelGGL(k_ed_scan, dim3(1), dim3(1024), 0, s, p);
             hipLaunchKernelGGL(k_ed_scan_seg<true>, eg, dim3(256), 0, s, p);
+            if (c->evid_batch) {
+                // read support per edit (k_evidence.hip.h): windows and groups per segment, a wave per alignment, the copy
+                hipLaunchKernelGGL(k_ev_windows, eg, dim3(256), 0, s, p);
+                if (c->A > 0) hipLaunchKernelGGL(k_ev_count, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
+                hipLaunchKernelGGL(k_ev_spread, eg, dim3(256), 0, s, p);
+            }
         }
     }
     HIPCHK(c, hipEventRecord(c->ev[4], s));
@@ -408,6 +416,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->uploaded = c->ran = c->fetched = false;
     c->sup_valid = c->pos_valid = false;
     c->ed_batch = c->ed_valid = c->pos_pending = false;     // (a record upload with edits on says so after the hand-over)
+    c->evid_batch = c->evid_valid = false;
     c->h_cig_bad.clear();
     c->rs_valid = false;
     c->md_valid = c->md_fetched = false;
@@ -610,6 +619,7 @@ int dagcon_run(dagcon_ctx *ctx) {
     if (r != DAGCON_OK) return r;
     c->ran = true; c->fetched = false;
     c->ed_valid = c->pos_pending = false;
+    c->evid_valid = false;
     if (const char *e = getenv("DAGCON_DUMP")) return dump_target(c, e);
     return DAGCON_OK;
 }
@@ -719,9 +729,12 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     if (n_ed > c->ed_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu edits in an arena of %llu", (unsigned long long)n_ed, (unsigned long long)c->ed_cap);
     c->sup_valid = c->pos_valid = false;
     c->ed_valid = c->pos_pending = false;
+    c->evid_valid = false;
     c->r_nb = nb;
+    const bool want_evid = want_ed && c->evid_batch;
     const size_t ed_seg_bytes = (size_t)nseg * sizeof(DgEdSeg), ed_bytes = ed_seg_bytes + (size_t)n_ed * sizeof(DgEdit);
-    if (want_ed && (r = c->r_ed.reserve(c, ed_bytes + 1))) return r;
+    const size_t evid_bytes = want_evid ? (size_t)n_ed * sizeof(DgEvid) : 0;        // (behind the edit records; both 8-byte aligned)
+    if (want_ed && (r = c->r_ed.reserve(c, ed_bytes + evid_bytes + 1))) return r;
     if (want_sup && (r = c->r_sup.reserve(c, 2 * (size_t)(nb + 1) * 2))) return r;     // (two halves of nb + 1 entries)
     char *const m_edb = c->r_ed.as<char>();
     uint16_t *const m_sup = c->r_sup.as<uint16_t>();
@@ -746,6 +759,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     if (want_ed && T && nseg) {
         HIPCHK(c, hipMemcpyAsync(m_edb, c->run.ed_seg.p, ed_seg_bytes, hipMemcpyDeviceToHost, c->stream));
         if (n_ed) HIPCHK(c, hipMemcpyAsync(m_edb + ed_seg_bytes, c->run.ed_out.p, (size_t)n_ed * sizeof(DgEdit), hipMemcpyDeviceToHost, c->stream));
+        if (evid_bytes) HIPCHK(c, hipMemcpyAsync(m_edb + ed_bytes, c->run.evid.p, evid_bytes, hipMemcpyDeviceToHost, c->stream));
         queued = true;
     }
     if (queued) HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -754,6 +768,8 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     c->pos_pending = lazy_pos;
     const DgEdSeg *m_es = reinterpret_cast<const DgEdSeg *>(m_edb);
     const DgEdit *m_ed = reinterpret_cast<const DgEdit *>(m_edb + ed_seg_bytes);
+    const DgEvid *m_evid = reinterpret_cast<const DgEvid *>(m_edb + ed_bytes);
+    if (want_evid) { c->v_begin.clear(); c->v_end.clear(); c->v_span.clear(); c->v_alt.clear(); c->v_ref.clear(); }
     if (want_ed) {
         c->e_t0.clear(); c->e_t1.clear(); c->e_begin.clear();
         c->e_tpos.clear(); c->e_tlen.clear(); c->e_clen.clear(); c->e_coff.clear();
@@ -781,11 +797,17 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
                 for (uint32_t k = 0; k < es.cnt; k++) {
                     const DgEdit &e = m_ed[es.off + k];
                     c->e_tpos.push_back(e.t_pos); c->e_tlen.push_back(e.t_len); c->e_coff.push_back(e.c_off); c->e_clen.push_back(e.c_len);
+                    if (want_evid) {
+                        const DgEvid &v = m_evid[es.off + k];
+                        c->v_begin.push_back(v.gL); c->v_end.push_back(v.gR);
+                        c->v_span.push_back(v.span); c->v_alt.push_back(v.alt); c->v_ref.push_back(v.ref);
+                    }
                 }
             }
         }
     }
     if (want_ed) { c->e_begin.push_back(c->e_tpos.size()); c->ed_valid = true; }
+    c->evid_valid = want_evid;
     c->r_seg_begin[T] = c->r_range0.size();
     c->tm.consensus_bases = bases;
     c->tm.algorithmic_bytes = 2ull * c->sum_len + bases;
@@ -843,6 +865,27 @@ int dagcon_set_edits(dagcon_ctx *ctx, int on) {
     if (!(c->opts.flags & DAGCON_FLAG_BASE_POS))
         return fail(c, DAGCON_ERR_STATE, "dagcon_set_edits on a context created without DAGCON_FLAG_BASE_POS");
     c->edits_on = on != 0;
+    if (!c->edits_on) c->evid_on = false;
+    return DAGCON_OK;
+}
+
+int dagcon_set_edit_support(dagcon_ctx *ctx, int on) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->edits_on) return fail(c, DAGCON_ERR_STATE, "dagcon_set_edit_support without dagcon_set_edits on");
+    c->evid_on = on != 0;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_edit_support(dagcon_ctx *ctx, dagcon_edit_support *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->edits_on || !c->ed_valid || !c->evid_valid)
+        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_edit_support without the results of a record upload made with dagcon_set_edit_support "
+                                         "on (switch off at the upload, edits off, another kind of upload, no fetch yet, or stopped before bestPath)");
+    out->n = c->v_begin.size();
+    out->w_begin = c->v_begin.data(); out->w_end = c->v_end.data();
+    out->span = c->v_span.data(); out->alt = c->v_alt.data(); out->ref = c->v_ref.data();
     return DAGCON_OK;
 }
 

@@ -227,6 +227,8 @@ struct DgParams {
     unsigned long long *ed_top;    // edits of the batch (k_ed_scan; in the status block)
     const uint8_t *ed_t;           // the record intake's target blob
     const uint64_t *ed_tbase;      // [T] where a target's (a window's) first base lies in it
+    // ---- read support per edit (dagcon_set_edit_support; NULL otherwise): k_evidence.hip.h ----
+    struct DgEvid *evid;           // [ed_cap] parallel to ed_out
 };
 #define DG_POS_BB 0x80000000u
 
@@ -240,6 +242,15 @@ struct __attribute__((aligned(16))) DgEdSeg {
 struct DgEdit {
     unsigned long long c_off;      // into cns
     uint32_t t_pos, t_len, c_len, pad;
+};
+
+// one per edit: its group's window, alt allele and counts (k_evidence.hip.h)
+struct DgEvid {
+    unsigned long long c_lo;       // where the group's alt allele begins, into cns
+    uint32_t gL, gR;               // the group's window [gL, gR)
+    uint32_t alt_len;              // bytes of the alt allele
+    uint32_t back;                 // edits back to the group's first edit (0: this is it, and the counts are added here)
+    uint32_t span, alt, ref, pad;
 };
 
 // slots a backbone vertex gets for each of its two lists before it has to move to the

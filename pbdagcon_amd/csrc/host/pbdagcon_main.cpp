@@ -49,6 +49,7 @@
 #include "paf.h"
 #include "sam.h"
 #include "windows.h"
+#include "vcf.h"
 
 namespace {
 
@@ -64,6 +65,8 @@ struct Opts {
     bool overlap_set = false;
     DgPick pick;                       // --max-error F, --max-depth N (MODE_RECORDS): the records are picked on the device
     std::string edits;                 // --edits FILE (MODE_RECORDS): where every record differs from its target
+    std::string vcf;                   // --vcf FILE (MODE_RECORDS, whole targets): the edits as VCF with the reads behind each
+    bool want_edits() const { return !edits.empty() || !vcf.empty(); }
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
     int pinned = -1;                   // --pinned 0|1: page-locked blobs (-1: when the input is several batches long)
@@ -78,7 +81,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE]] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -162,6 +165,13 @@ void usage(FILE *f) {
             "                      applied to ref[t0:t1] give the record's sequence.  The list comes from the GPU, read off\n"
             "                      the best path itself, nothing is aligned again; stdout does not change.  This build's own\n"
             "                      rule, parity unpinned\n"
+            "  --vcf FILE          with --sam, --bam or --paf (--ref or --md; not with --window): FILE lists the edits of --edits\n"
+            "                      as VCFv4.2, one line per edit in output order: RNAME POS . REF ALT . . DP=span;AD=ref,alt;\n"
+            "                      WIN=first-last.  DP counts the alignments that span the edit's window, AD those among them that\n"
+            "                      carry the target's and the consensus' allele there, WIN is the window (every place the same\n"
+            "                      change could be written in a repeat).  A pure insertion or deletion is anchored on the base in\n"
+            "                      front of it (at position 1: behind it).  Counted on the GPU from the alignments as the graph\n"
+            "                      took them; stdout and --edits do not change.  This build's own rule, parity unpinned\n"
             "  --fastq             write FASTQ (@id/r0_r1, sequence, +, qualities) instead of FASTA; the same records in the\n"
             "                      same order.  The quality of a base is this build's own definition: a Laplace-smoothed\n"
             "                      fraction of the reads at its position that do not pass through its consensus vertex,\n"
@@ -217,6 +227,10 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--edits") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --edits needs a file name\n"); return 2; }
             o.edits = argv[++i];
+        }
+        else if (a == "--vcf") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --vcf needs a file name\n"); return 2; }
+            o.vcf = argv[++i];
         }
         else if (a == "--window") { if (!need(&o.window) || !o.window) { fprintf(stderr, "PARSE ERROR: --window takes a positive number of bases\n"); return 2; } }
         else if (a == "--max-error") {
@@ -283,6 +297,9 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (o.pick.on() && !records) { fprintf(stderr, "PARSE ERROR: --max-error and --max-depth need --sam, --bam or --paf\n"); return 2; }
     if (!o.edits.empty() && !records) { fprintf(stderr, "PARSE ERROR: --edits needs --sam, --bam or --paf\n"); return 2; }
     if (!o.edits.empty() && o.dump) { fprintf(stderr, "PARSE ERROR: --edits does not go with --dump-parsed (nothing is run, the file would not be written)\n"); return 2; }
+    if (!o.vcf.empty() && !records) { fprintf(stderr, "PARSE ERROR: --vcf needs --sam, --bam or --paf\n"); return 2; }
+    if (!o.vcf.empty() && o.dump) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --dump-parsed (nothing is run, the file would not be written)\n"); return 2; }
+    if (!o.vcf.empty() && o.window) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --window (the stitch splits and fuses edits: a fused edit has no single count)\n"); return 2; }
     if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
     if (o.window && (uint64_t)o.overlap < (uint64_t)o.trim + 64) { fprintf(stderr, "PARSE ERROR: --overlap must be at least --trim + 64 (%u)\n", o.trim + 64); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
@@ -369,11 +386,17 @@ struct Batch {
     std::string out;                   // the batch's FASTA records
     std::string edits;                 // --edits: the batch's lines of that file
     unsigned long long n_edits = 0;
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; }
+    std::string vcf, contigs;          // --vcf: the batch's lines of that file, and its targets' ##contig lines
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); }
 };
 
 FILE *g_edits = nullptr;                                  // --edits FILE, written batch by batch in output order
 unsigned long long g_n_edits = 0;
+// --vcf FILE, opened before the workers start.  The header names every target, so the lines go to an unnamed temporary
+// file batch by batch, in output order, and only the ##contig lines are kept; the end of the run writes header and lines
+FILE *g_vcf = nullptr, *g_vcf_lines = nullptr;
+std::string g_vcf_contigs;
+bool g_vcf_bad = false;
 unsigned long long g_over_error = 0, g_over_depth = 0;     // records --max-error / --max-depth left out, all batches (under g_tmu)
 bool g_timing = false;                                    // PBDAGCON_TIMING=1: where the wall time of the run went, on stderr (seconds)
 std::mutex g_tmu;
@@ -395,7 +418,10 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
     if (o.fastq && !ok(ctx, dagcon_fetch_support(ctx, &sup), "per-base support")) return 1;
     dagcon_edits ed;
     memset(&ed, 0, sizeof ed);
-    if (!o.edits.empty() && !ok(ctx, dagcon_fetch_edits(ctx, &ed), "edits")) return 1;
+    if (o.want_edits() && !ok(ctx, dagcon_fetch_edits(ctx, &ed), "edits")) return 1;
+    dagcon_edit_support es;
+    memset(&es, 0, sizeof es);
+    if (!o.vcf.empty() && !ok(ctx, dagcon_fetch_edit_support(ctx, &es), "edit support")) return 1;
     const char *nonconforming = o.mode == MODE_RECORDS ? dg_kind(o.kind).nonconforming : "an alignment leaves the backbone or holds a non-printable byte";
     for (uint32_t g = 0; g < r.n_targets; g++) {
         if (o.verbose)
@@ -403,11 +429,16 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
                     (unsigned long long)(b.begin[g + 1] - b.begin[g]));
         // a failure is confined to its target (the reference's assert hits one worker's one target,
         // AlnGraphBoost.cpp:71-72): warn, go on with the rest
+        if (!o.vcf.empty()) dg_vcf_contig(b.contigs, b.ids[g], b.tlen[g]);
         if (r.target_status[g] != DAGCON_OK)
             fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(), dg_status_text(r.target_status[g], nonconforming));
         for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
             if (!dg_append_result(b.out, o.fastq, b.ids[g], r.range0[s], r.range1[s], r.seq_blob + r.seq_off[s], r.seq_len[s],
                                   o.fastq ? sup.weight + r.seq_off[s] : nullptr, o.fastq ? sup.depth + r.seq_off[s] : nullptr)) return 1;
+            if (!o.vcf.empty())
+                for (uint64_t e = ed.edit_begin[s]; e < ed.edit_begin[s + 1]; e++)
+                    dg_vcf_line(b.vcf, b.ids[g], b.t.data() + b.toff[g], b.tlen[g], ed.t_pos[e], ed.t_len[e], r.seq_blob + ed.c_off[e], ed.c_len[e],
+                                es.span[e], es.ref[e], es.alt[e], es.w_begin[e], es.w_end[e]);
             if (o.edits.empty()) continue;
             // the record's span and edits (include/dagcon.h, dagcon_edits): REF from the target's bases, ALT from the record's
             char head[64];
@@ -480,7 +511,7 @@ int run_records(dagcon_ctx *ctx, Batch &b, const Opts &o) {
     const int rc = dg_consensus_records(ctx, o.kind, ra, nullptr, &r);
     if (g_timing) fprintf(stderr, "pbdagcon timing: %s%s batch of %zu records: %s %.3f\n", dg_kind(o.kind).flag, o.pick.text().c_str(), b.start.size(), dg_kind(o.kind).entry, wall() - t0);
     if (!ok(ctx, rc, "consensus")) return 1;
-    if (dg_kind_md(o.kind) && !o.edits.empty()) {           // REF of the edits: the targets as the device rebuilt them, in b.t's layout
+    if (dg_kind_md(o.kind) && o.want_edits()) {           // REF of the edits: the targets as the device rebuilt them, in b.t's layout
         const char *tb = nullptr;
         uint64_t tn = 0;
         if (!ok(ctx, dagcon_fetch_md_targets(ctx, &tb, &tn), "rebuilt targets")) return 1;
@@ -688,8 +719,8 @@ struct Workers {
     void run(size_t w) {
         dagcon_ctx *ctx = nullptr;
         const double tc0 = wall();
-        int rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], (o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u) | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u) | (o.edits.empty() ? 0u : DAGCON_FLAG_BASE_POS), &o.pick, &ctx);
-        if (rc == DAGCON_OK && !o.edits.empty() && (rc = dagcon_set_edits(ctx, 1)) != DAGCON_OK) {
+        int rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], (o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u) | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u) | (o.want_edits() ? DAGCON_FLAG_BASE_POS : 0u), &o.pick, &ctx);
+        if (rc == DAGCON_OK && o.want_edits() && ((rc = dagcon_set_edits(ctx, 1)) != DAGCON_OK || (!o.vcf.empty() && (rc = dagcon_set_edit_support(ctx, 1)) != DAGCON_OK))) {
             fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx));
             dagcon_destroy(ctx); ctx = nullptr;
         }
@@ -730,6 +761,7 @@ struct Workers {
                     done.erase(done.begin() + i);
                     { const double tp0 = wall(); fwrite(d->out.data(), 1, d->out.size(), stdout); t_print += wall() - tp0; }
                     if (g_edits) { fwrite(d->edits.data(), 1, d->edits.size(), g_edits); g_n_edits += d->n_edits; }
+                    if (g_vcf) { g_vcf_contigs += d->contigs; if (fwrite(d->vcf.data(), 1, d->vcf.size(), g_vcf_lines) != d->vcf.size()) g_vcf_bad = true; }
                     d->clear();
                     free_list.push_back(d);
                     print_seq++;
@@ -1237,6 +1269,7 @@ int main(int argc, char **argv) {
     // ---- whole targets: the workers start (context creation hides behind the parsing of the first batch), the input
     // is parsed into batches slab by slab, the workers drain ----
     if (!o.edits.empty() && !o.dump && !(g_edits = fopen(o.edits.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.edits.c_str()); return 1; }
+    if (!o.vcf.empty() && !o.dump && (!(g_vcf = fopen(o.vcf.c_str(), "w")) || !(g_vcf_lines = tmpfile()))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.vcf.c_str()); return 1; }
     Workers wk(o, in.size);
     if (!o.dump) wk.start();
     RecordIndexer rix(in, o, ref, bam, paf);
@@ -1258,6 +1291,17 @@ int main(int argc, char **argv) {
     if (g_edits) {
         if (fclose(g_edits) != 0) { fprintf(stderr, "pbdagcon: error writing %s\n", o.edits.c_str()); status = 1; fast_exit = false; }
         if (o.verbose) fprintf(stderr, "pbdagcon: %llu edits written to %s\n", g_n_edits, o.edits.c_str());
+    }
+    if (g_vcf) {
+        std::string head;
+        dg_vcf_header(head); head += g_vcf_contigs; dg_vcf_columns(head);
+        bool wrote = !g_vcf_bad && fwrite(head.data(), 1, head.size(), g_vcf) == head.size();
+        rewind(g_vcf_lines);
+        char buf[65536];
+        for (size_t k; wrote && (k = fread(buf, 1, sizeof buf, g_vcf_lines)) > 0;) wrote = fwrite(buf, 1, k, g_vcf) == k;
+        wrote = wrote && !ferror(g_vcf_lines);
+        fclose(g_vcf_lines);
+        if (fclose(g_vcf) != 0 || !wrote) { fprintf(stderr, "pbdagcon: error writing %s\n", o.vcf.c_str()); status = 1; fast_exit = false; }
     }
     if (!fast_exit) {
         for (auto &x : wk.bufs) { x.q.release(); x.t.release(); }

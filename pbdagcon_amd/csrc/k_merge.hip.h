@@ -10,7 +10,7 @@
 //   * a visit gathers the records of all in- (then out-) neighbours of the
 //     dequeued vertex at once, one list entry per lane, and picks the next merge
 //     group with ballots (smallest base shared by >= 2 eligible neighbours);
-//   * a group is merged cooperatively (dgw_merge_in_group / dgw_merge_out_group):
+//   * a group is merged cooperatively (dg_merge_in_group / dg_merge_out_group):
 //     the victims' edges are flattened onto lanes, deduplicated in first-
 //     occurrence order with ballot / popcount, and every list that changes is
 //     rewritten by one compaction; after a group the vertex is re-evaluated
@@ -429,48 +429,74 @@ __device__ __forceinline__ int dg_wave_incl_scan(int v, int lane) {
     }
     return v;
 }
-__device__ __forceinline__ int dg_wave_sum_masked(int v, unsigned long long m) {
+// ---- the merge rule, once, over a group of lanes --------------------------------
+// A group is the set of lanes that holds one list, an entry per lane: the wave here (DgWave), a row of DQ_W
+// lanes in k_merge_q (DgRow, k_merge_q.hip.h).  A group policy G gives: mask (a bit per lane of the group),
+// W (its lanes), ballot (over the group), rl (the value a lane of the group holds; the lane is group-uniform),
+// ffs / popc on a mask, lt (the bits below a lane).  `lane` is the caller's lane within its group.
+// row_text: three statements below have two places, or two spellings, that mean the same (marked "row_text"); the
+// wave kernels keep the one they were tuned with and k_merge_q the other.  All five kernels sit at a pinned occupancy
+// with spilled scalar registers, and the other choice moves their register allocation: the wave kernels by -38 .. +6
+// instructions, k_merge_q by +20 and 0.5 ms of 10.7 at configs[1] (profiles/merge_lanes/).  Nothing else may hang on it.
+struct DgWave {
+    typedef unsigned long long mask;
+    static constexpr int W = 64;
+    static constexpr bool row_text = false;
+    static __device__ __forceinline__ mask ballot(bool p) { return __ballot(p); }
+    static __device__ __forceinline__ int rl(int v, int l) { return DG_RL(v, l); }
+    static __device__ __forceinline__ int ffs(mask m) { return __ffsll((long long)m); }
+    static __device__ __forceinline__ int popc(mask m) { return __popcll(m); }
+    static __device__ __forceinline__ mask lt(int lane) { return DG_LT(lane); }
+};
+
+template <class G>
+__device__ __forceinline__ int dg_sum_masked(int v, typename G::mask m) {
     int acc = 0;
     while (m) {
-        const int f = __ffsll((long long)m) - 1;
-        acc += DG_RL(v, f);
-        m &= m - 1ull;
+        const int f = G::ffs(m) - 1;
+        acc += G::rl(v, f);
+        m &= m - 1;
     }
     return acc;
 }
 
 // smallest base > last that at least two candidate lanes share; returns the
 // base (or 256) and the mask of its lanes
-__device__ __forceinline__ int dg_pick_group(unsigned long long cand, int base, int last, int lane,
-                                             unsigned long long *mask) {
+template <class G>
+__device__ __forceinline__ int dg_pick_group(typename G::mask cand, int base, int last, int lane,
+                                             typename G::mask *mask) {
+    typedef typename G::mask gmask;
     int best = 256;
-    unsigned long long bm = 0;
+    gmask bm = 0;
     // candidates carry their base, every other lane a value no base equals: one compare per round
-    const int key = ((cand >> lane) & 1ull) ? base : -1 - lane;
+    const int key = ((cand >> lane) & 1) ? base : -1 - lane;
     while (cand) {
-        const int f = __ffsll((long long)cand) - 1;
-        const int b = DG_RL(key, f);
-        const unsigned long long same = __ballot(key == b);
-        if (b > last && b < best && __popcll(same) >= 2) { best = b; bm = same; }
+        const int f = G::ffs(cand) - 1;
+        const int b = G::rl(key, f);
+        const gmask same = G::ballot(key == b);
+        if (b > last && b < best && G::popc(same) >= 2) { best = b; bm = same; }
         cand &= ~same;
     }
     *mask = bm;
     return best;
 }
 
-__device__ __forceinline__ uint32_t dg_wave_alloc(DgGraph &g, uint32_t words, int lane) {
+template <class G>
+__device__ __forceinline__ uint32_t dg_group_alloc(DgGraph &g, uint32_t words, int lane) {
     uint32_t off = 0;
     if (lane == 0) { DgGraph gs = g; off = dgg_alloc(gs, words); }
-    off = (uint32_t)DG_RL(off, 0);
+    off = (uint32_t)G::rl((int)off, 0);
     if (off == 0xFFFFFFFFu) g.err = true;                // every lane: keeps control flow uniform
     return off;
 }
 
 // Removes from in[v] every source held (in `vid`) by a lane of vm (stable), then
 // appends `app` when app >= 0.  pend_delta is added to v's pending counter.
-// Requires in_len(v) <= 64.
-__device__ inline void dgw_in_rewrite(DgGraph &g, int v, int vid, unsigned long long vm, int app,
-                                      int pend_delta, int lane) {
+// Requires in_len(v) <= G::W.
+template <class G>
+__device__ inline void dg_in_rewrite(DgGraph &g, int v, int vid, typename G::mask vm, int app,
+                                     int pend_delta, int lane) {
+    typedef typename G::mask gmask;
     const uint4 h = dg_lo16(&DG_NV(g, v)), h2 = dg_hi16(&DG_NV(g, v));
     const int len = DG_H_INLEN(h);
     uint32_t off = DG_H2_INOFF(h2);
@@ -478,15 +504,15 @@ __device__ inline void dgw_in_rewrite(DgGraph &g, int v, int vid, unsigned long 
     int e = -1;
     if (lane < len) e = (int)DG_PW(g, off + lane);
     bool rm = false;
-    for (unsigned long long m = vm; m; m &= m - 1ull) rm |= (e == DG_RL(vid, __ffsll((long long)m) - 1));
+    for (gmask m = vm; m; m &= m - 1) rm |= (e == G::rl(vid, G::ffs(m) - 1));
     const bool keep = lane < len && !rm;
-    const unsigned long long km = __ballot(keep);
-    int nlen = __popcll(km);
-    const int nidx = __popcll(km & DG_LT(lane));
+    const gmask km = G::ballot(keep);
+    int nlen = G::popc(km);
+    const int nidx = G::popc(km & G::lt(lane));
     if (app >= 0 && nlen + 1 > cap) {
         uint32_t ncap = 2u * (uint32_t)(nlen + 1);
         if (ncap < 4) ncap = 4;
-        const uint32_t noff = dg_wave_alloc(g, ncap, lane);
+        const uint32_t noff = dg_group_alloc<G>(g, ncap, lane);
         if (noff == 0xFFFFFFFFu) return;
         off = noff; cap = (int)ncap;
     }
@@ -500,82 +526,88 @@ __device__ inline void dgw_in_rewrite(DgGraph &g, int v, int vid, unsigned long 
 }
 
 // ---- mergeOutNodes, one group (AlnGraphBoost.cpp:229-266) ---------------------
-// Lanes 32..63 hold u's out entries: d (target), cnt, h (first half of the
-// target's record).  M = lanes of the group (survivor = lowest lane).
-// Returns false, with nothing modified, when a list involved is longer than a wave.
-__device__ inline bool dgw_merge_out_group(DgGraph &g, int u, const DgNode &nu, unsigned long long M,
-                                           int d, int &cnt, uint4 h, bool valid_out, int lane) {
-    const int an_lane = __ffsll((long long)M) - 1;
-    const unsigned long long vm = M & ~(1ull << an_lane);
-    const int an = DG_RL(d, an_lane);
-    const bool member = (M >> lane) & 1ull;
+// The caller has all of u's out entries in lanes of its lane group, in list order by rising lane (anywhere in the
+// group: other lanes may hold something else) and marked by valid_out: d (target), cnt, h (first half of the
+// target's record); u_out_off is where the list lies in the pool.  M = lanes of the merge group (survivor = lowest lane).
+// Returns false, with nothing modified, when a list involved is longer than the lane group.
+template <class G>
+__device__ inline bool dg_merge_out_group(DgGraph &g, int u, uint32_t u_out_off, typename G::mask M,
+                                          int d, int &cnt, uint4 h, bool valid_out, int lane) {
+    typedef typename G::mask gmask;
+    const int an_lane = G::ffs(M) - 1;
+    const gmask vm = M & ~((gmask)1 << an_lane);
+    const int an = G::rl(d, an_lane);
+    const bool member = (M >> lane) & 1;
     uint4 h2 = make_uint4(0, 0, 0, 0);
     if (member) h2 = dg_hi16(&DG_NV(g, d));
     // members' out entries flattened onto lanes 0..L-1: survivor's first, then victims in order
     int L = 0, src = -1, e = 0;
     uint32_t src_off = 0;
     {
-        unsigned long long mm = M;
+        gmask mm = M;
         while (mm) {
-            const int ml = __ffsll((long long)mm) - 1;
-            mm &= mm - 1ull;
-            const int mlen = DG_RL(DG_H_OUTLEN(h), ml);
-            const uint32_t moff = (uint32_t)DG_RL(DG_H2_OUTOFF(h2), ml);
+            const int ml = G::ffs(mm) - 1;
+            mm &= mm - 1;
+            const int mlen = G::rl(DG_H_OUTLEN(h), ml);
+            const uint32_t moff = (uint32_t)G::rl((int)DG_H2_OUTOFF(h2), ml);
             if (lane >= L && lane < L + mlen) { src = ml; e = lane - L; src_off = moff; }
             L += mlen;
         }
     }
-    if (L > 64) return false;
+    if (L > G::W) return false;
     const bool fl = lane < L;
     int n2 = -1, c2 = 0;
     if (fl) { n2 = (int)DG_PW(g, src_off + 2 * e); c2 = (int)DG_PW(g, src_off + 2 * e + 1); }
     const bool vic_entry = fl && src != an_lane;
     uint4 hn2 = make_uint4(0, 0, 0, 0);
     if (vic_entry) hn2 = dg_lo16(&DG_NV(g, n2));
-    if (__ballot(vic_entry && DG_H_INLEN(hn2) > 64)) return false;
-    if (g.sh && __ballot(vic_entry && ((hn2.y >> 8) & DG_NF_SHARED))) return false;      // in[exit] is shared: literal path
+    if (G::ballot(vic_entry && DG_H_INLEN(hn2) > G::W)) return false;
+    if (g.sh && G::ballot(vic_entry && ((hn2.y >> 8) & DG_NF_SHARED))) return false;      // in[exit] is shared: literal path
 
     // ---- nothing has been modified up to here ----
     // :236-243 count(u->an) += counts of u->victims, weight[an] += weights
-    const int add_cnt = dg_wave_sum_masked(cnt, vm);
-    const int add_w = dg_wave_sum_masked(DG_H_WEIGHT(h), vm);
+    const int add_cnt = dg_sum_masked<G>(cnt, vm);
+    const int add_w = dg_sum_masked<G>(DG_H_WEIGHT(h), vm);
     // :246-265 fold the victims' out edges into the survivor's, first occurrence order
-    unsigned long long rem = __ballot(fl), first_m = 0;
+    gmask rem = G::ballot(fl), first_m = 0;
+    gmask vics = 0;                                       // lanes that hold a victim's entry (row_text: taken here)
+    if constexpr (G::row_text) vics = G::ballot(vic_entry);
     int newcnt = c2;
     while (rem) {
-        const int f = __ffsll((long long)rem) - 1;
-        const int x = DG_RL(n2, f);
-        const unsigned long long same = __ballot(fl && n2 == x);
+        const int f = G::ffs(rem) - 1;
+        const int x = G::rl(n2, f);
+        const gmask same = G::ballot(fl && n2 == x);
         rem &= ~same;
-        first_m |= 1ull << f;
-        const int tot = dg_wave_sum_masked(c2, same);
+        first_m |= (gmask)1 << f;
+        const int tot = dg_sum_masked<G>(c2, same);
         if (lane == f) newcnt = tot;
-        const unsigned long long vsame = same & __ballot(vic_entry);
-        const int nv = __popcll(vsame);
+        if constexpr (!G::row_text) vics = G::ballot(vic_entry);
+        const gmask vsame = same & vics;
+        const int nv = G::popc(vsame);
         if (nv) {
-            const bool is_new = (vsame >> f) & 1ull;       // survivor had no edge to x
-            dgw_in_rewrite(g, x, d, vm, is_new ? an : -1, -(nv - (is_new ? 1 : 0)), lane);
+            const bool is_new = (vsame >> f) & 1;          // survivor had no edge to x
+            dg_in_rewrite<G>(g, x, d, vm, is_new ? an : -1, -(nv - (is_new ? 1 : 0)), lane);
             if (g.err) return true;
         }
     }
     // survivor's new out list
     {
-        const int nlen = __popcll(first_m);
-        uint32_t off = (uint32_t)DG_RL(DG_H2_OUTOFF(h2), an_lane);
-        int cap = DG_RL(DG_H2_OUTCAP(h2), an_lane);
+        const int nlen = G::popc(first_m);
+        uint32_t off = (uint32_t)G::rl((int)DG_H2_OUTOFF(h2), an_lane);
+        int cap = G::rl(DG_H2_OUTCAP(h2), an_lane);
         if (nlen > cap) {
             uint32_t ncap = 2u * (uint32_t)(nlen + 1);
             if (ncap < 4) ncap = 4;
-            const uint32_t noff = dg_wave_alloc(g, 2u * ncap, lane);
+            const uint32_t noff = dg_group_alloc<G>(g, 2u * ncap, lane);
             if (noff == 0xFFFFFFFFu) return true;
             off = noff; cap = (int)ncap;
         }
-        if ((first_m >> lane) & 1ull) {
-            const int idx = __popcll(first_m & DG_LT(lane));
+        if ((first_m >> lane) & 1) {
+            const int idx = G::popc(first_m & G::lt(lane));
             DG_PW(g, off + 2 * idx) = (uint32_t)n2;
             DG_PW(g, off + 2 * idx + 1) = (uint32_t)newcnt;
         }
-        const int an_w = DG_RL(DG_H_WEIGHT(h), an_lane);
+        const int an_w = G::rl(DG_H_WEIGHT(h), an_lane);
         if (lane == 0) {
             DgNode *a = &DG_NV(g, an);
             a->out_len = (uint16_t)nlen; a->out_off = off; a->out_cap = (uint16_t)cap;
@@ -584,18 +616,18 @@ __device__ inline bool dgw_merge_out_group(DgGraph &g, int u, const DgNode &nu, 
     }
     // u's out list without the victims (stable), survivor's edge count updated
     {
-        const bool keep = valid_out && !((vm >> lane) & 1ull);
-        const unsigned long long km = __ballot(keep);
+        const bool keep = valid_out && !((vm >> lane) & 1);
+        const gmask km = G::ballot(keep);
         if (keep) {
-            const int idx = __popcll(km & DG_LT(lane));
-            DG_PW(g, nu.out_off + 2 * idx) = (uint32_t)d;
+            const int idx = G::popc(km & G::lt(lane));
+            DG_PW(g, u_out_off + 2 * idx) = (uint32_t)d;
             if (lane == an_lane) cnt += add_cnt;
-            DG_PW(g, nu.out_off + 2 * idx + 1) = (uint32_t)cnt;
+            DG_PW(g, u_out_off + 2 * idx + 1) = (uint32_t)cnt;
         }
-        if (lane == 0) DG_NV(g, u).out_len = (uint16_t)__popcll(km);
+        if (lane == 0) DG_NV(g, u).out_len = (uint16_t)G::popc(km);
     }
     // AlnGraphBoost.cpp:269-273 for every victim
-    if ((vm >> lane) & 1ull) {
+    if ((vm >> lane) & 1) {
         DgNode *vn = &DG_NV(g, d);
         vn->out_len = 0; vn->in_len = 0; vn->flags |= DG_NF_DELETED;
     }
@@ -603,17 +635,20 @@ __device__ inline bool dgw_merge_out_group(DgGraph &g, int u, const DgNode &nu, 
 }
 
 // ---- mergeInNodes, one group (AlnGraphBoost.cpp:176-212) ----------------------
-// Lanes 0..31 hold n's in entries: s (source), h (first half of its record).
-// M = lanes of the group (survivor = lowest lane).  *an_out = survivor.
-// Returns false, with nothing modified, when a list involved is longer than a wave.
-__device__ inline bool dgw_merge_in_group(DgGraph &g, int n, const DgNode &nn, unsigned long long M,
-                                          int s, uint4 h, bool valid_in, int lane, int *an_out) {
-    const int an_lane = __ffsll((long long)M) - 1;
-    const unsigned long long vm = M & ~(1ull << an_lane);
-    const int an = DG_RL(s, an_lane);
+// The caller has all of n's in entries in lanes of its lane group, in list order by rising lane and marked by
+// valid_in: s (source), h (first half of its record); n_in_off is where the list lies in the pool.
+// M = lanes of the merge group (survivor = lowest lane).  *an_out = survivor.
+// Returns false, with nothing modified, when a list involved is longer than the lane group.
+template <class G>
+__device__ inline bool dg_merge_in_group(DgGraph &g, int n, uint32_t n_in_off, typename G::mask M,
+                                         int s, uint4 h, bool valid_in, int lane, int *an_out) {
+    typedef typename G::mask gmask;
+    const int an_lane = G::ffs(M) - 1;
+    const gmask vm = M & ~((gmask)1 << an_lane);
+    const int an = G::rl(s, an_lane);
     *an_out = an;
-    const bool member = (M >> lane) & 1ull;
-    const bool victim = (vm >> lane) & 1ull;
+    const bool member = (M >> lane) & 1;
+    const bool victim = (vm >> lane) & 1;
     uint4 h2 = make_uint4(0, 0, 0, 0);
     if (member) h2 = dg_hi16(&DG_NV(g, s));
     int c0 = 0;
@@ -622,61 +657,63 @@ __device__ inline bool dgw_merge_in_group(DgGraph &g, int n, const DgNode &nn, u
     int L = 0, e = 0;
     uint32_t src_off = 0;
     {
-        unsigned long long mm = vm;
+        gmask mm = vm;
         while (mm) {
-            const int ml = __ffsll((long long)mm) - 1;
-            mm &= mm - 1ull;
-            const int mlen = DG_RL(DG_H_INLEN(h), ml);
-            const uint32_t moff = (uint32_t)DG_RL(DG_H2_INOFF(h2), ml);
+            const int ml = G::ffs(mm) - 1;
+            mm &= mm - 1;
+            const int mlen = G::rl(DG_H_INLEN(h), ml);
+            const uint32_t moff = (uint32_t)G::rl((int)DG_H2_INOFF(h2), ml);
             if (lane >= L && lane < L + mlen) { e = lane - L; src_off = moff; }
             L += mlen;
         }
     }
-    if (L > 64) return false;
+    if (L > G::W) return false;
     const bool fl = lane < L;
     int n1 = -1;
     if (fl) n1 = (int)DG_PW(g, src_off + e);
     uint4 hn1 = make_uint4(0, 0, 0, 0);
     if (fl) hn1 = dg_lo16(&DG_NV(g, n1));
-    if (__ballot(fl && DG_H_OUTLEN(hn1) > 64)) return false;
-    if (g.sh && __ballot(fl && ((hn1.y >> 8) & DG_NF_SHARED))) return false;    // a shared out-list: literal path
+    if (G::ballot(fl && DG_H_OUTLEN(hn1) > G::W)) return false;
+    if (g.sh && G::ballot(fl && ((hn1.y >> 8) & DG_NF_SHARED))) return false;    // a shared out-list: literal path
+    int a_in_len = 0;                                     // in_len of the survivor (row_text: read here)
+    if constexpr (G::row_text) a_in_len = G::rl(DG_H_INLEN(h), an_lane);
 
     // ---- nothing has been modified up to here ----
     // :183-190 survivor's out edge count and weight
-    const int add_cnt = dg_wave_sum_masked(c0, vm);
-    const int add_w = dg_wave_sum_masked(DG_H_WEIGHT(h), vm);
+    const int add_cnt = dg_sum_masked<G>(c0, vm);
+    const int add_w = dg_sum_masked<G>(DG_H_WEIGHT(h), vm);
     if (lane == an_lane) {
         DG_PW(g, DG_H2_OUTOFF(h2) + 1) = (uint32_t)(c0 + add_cnt);
         DG_NV(g, an).weight = DG_H_WEIGHT(h) + add_w;
     }
     // :193-212 re-point the victims' in edges to the survivor, in order
-    uint32_t a_in_off = (uint32_t)DG_RL(DG_H2_INOFF(h2), an_lane);
-    int a_in_cap = DG_RL(DG_H2_INCAP(h2), an_lane);
-    int a_in_len = DG_RL(DG_H_INLEN(h), an_lane);
+    uint32_t a_in_off = (uint32_t)G::rl((int)DG_H2_INOFF(h2), an_lane);
+    int a_in_cap = G::rl(DG_H2_INCAP(h2), an_lane);
+    if constexpr (!G::row_text) a_in_len = G::rl(DG_H_INLEN(h), an_lane);
     bool a_dirty = false;
-    unsigned long long rem = __ballot(fl);
+    gmask rem = G::ballot(fl);
     while (rem) {
-        const int f = __ffsll((long long)rem) - 1;
-        const int x = DG_RL(n1, f);
-        rem &= ~__ballot(fl && n1 == x);
+        const int f = G::ffs(rem) - 1;
+        const int x = G::rl(n1, f);
+        rem &= ~G::ballot(fl && n1 == x);
         // out[x]: drop the entries that point at victims, fold their counts into x->an
         const uint4 hx2 = dg_hi16(&DG_NV(g, x));
-        const int xlen = DG_RL(DG_H_OUTLEN(hn1), f);
+        const int xlen = G::rl(DG_H_OUTLEN(hn1), f);
         const uint32_t xoff = DG_H2_OUTOFF(hx2);
         int dst = -1, c = 0;
         if (lane < xlen) { dst = (int)DG_PW(g, xoff + 2 * lane); c = (int)DG_PW(g, xoff + 2 * lane + 1); }
         bool isv = false;
-        for (unsigned long long m = vm; m; m &= m - 1ull) isv |= (dst == DG_RL(s, __ffsll((long long)m) - 1));
-        const unsigned long long vmask = __ballot(lane < xlen && isv);
-        const int csum = dg_wave_sum_masked(c, vmask);
-        const unsigned long long apos = __ballot(lane < xlen && dst == an);
+        for (gmask m = vm; m; m &= m - 1) isv |= (dst == G::rl(s, G::ffs(m) - 1));
+        const gmask vmask = G::ballot(lane < xlen && isv);
+        const int csum = dg_sum_masked<G>(c, vmask);
+        const gmask apos = G::ballot(lane < xlen && dst == an);
         const bool keep = lane < xlen && !isv;
-        const unsigned long long km = __ballot(keep);
-        int nlen = __popcll(km);
+        const gmask km = G::ballot(keep);
+        int nlen = G::popc(km);
         if (keep) {
-            const int idx = __popcll(km & DG_LT(lane));
+            const int idx = G::popc(km & G::lt(lane));
             DG_PW(g, xoff + 2 * idx) = (uint32_t)dst;
-            DG_PW(g, xoff + 2 * idx + 1) = (uint32_t)(((apos >> lane) & 1ull) ? c + csum : c);
+            DG_PW(g, xoff + 2 * idx + 1) = (uint32_t)(((apos >> lane) & 1) ? c + csum : c);
         }
         if (!apos) {
             // new edge x->an: END of out[x] (room is there: at least one entry was dropped)
@@ -686,10 +723,11 @@ __device__ inline bool dgw_merge_in_group(DgGraph &g, int n, const DgNode &nn, u
             if (a_in_len + 1 > a_in_cap) {
                 uint32_t ncap = 2u * (uint32_t)(a_in_len + 1);
                 if (ncap < 4) ncap = 4;
-                const uint32_t noff = dg_wave_alloc(g, ncap, lane);
+                const uint32_t noff = dg_group_alloc<G>(g, ncap, lane);
                 if (noff == 0xFFFFFFFFu) return true;
-                if (lane < a_in_len) DG_PW(g, noff + lane) = DG_PW(g, a_in_off + lane);
-                for (int i = 64 + lane; i < a_in_len; i += 64) DG_PW(g, noff + i) = DG_PW(g, a_in_off + i);
+                int i = lane;                             // in[an] to its new place (row_text: one loop)
+                if constexpr (!G::row_text) { if (lane < a_in_len) DG_PW(g, noff + lane) = DG_PW(g, a_in_off + lane); i += G::W; }
+                for (; i < a_in_len; i += G::W) DG_PW(g, noff + i) = DG_PW(g, a_in_off + i);
                 a_in_off = noff; a_in_cap = (int)ncap;
             }
             if (lane == 0) DG_PW(g, a_in_off + a_in_len) = (uint32_t)x;
@@ -705,9 +743,9 @@ __device__ inline bool dgw_merge_in_group(DgGraph &g, int n, const DgNode &nn, u
     // in[n] without the victims (stable)
     {
         const bool keep = valid_in && !victim;
-        const unsigned long long km = __ballot(keep);
-        if (keep) DG_PW(g, nn.in_off + __popcll(km & DG_LT(lane))) = (uint32_t)s;
-        if (lane == 0) DG_NV(g, n).in_len = (uint16_t)__popcll(km);
+        const gmask km = G::ballot(keep);
+        if (keep) DG_PW(g, n_in_off + G::popc(km & G::lt(lane))) = (uint32_t)s;
+        if (lane == 0) DG_NV(g, n).in_len = (uint16_t)G::popc(km);
     }
     if (victim) {
         DgNode *vn = &DG_NV(g, s);
@@ -905,7 +943,7 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
                 const unsigned long long c_in = cand & 0xffffffffull;
                 unsigned long long M = 0;
                 bool in_work = false;
-                if (__popcll(c_in) >= 2) in_work = dg_pick_group(c_in, DG_H_BASE(h), -1, lane, &M) != 256;
+                if (__popcll(c_in) >= 2) in_work = dg_pick_group<DgWave>(c_in, DG_H_BASE(h), -1, lane, &M) != 256;
                 if (!in_work && in_only) break;           // nothing to merge in front of the cut: segment done
                 if (!in_work) {
                     // mergeOutNodes(u) on the resident out entries (lanes 32..63), group by group
@@ -915,12 +953,12 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
                     for (;;) {
                         const unsigned long long c_out = __ballot(live && DG_H_INLEN(h) == 1);
                         int b = 256;
-                        if (__popcll(c_out) >= 2) b = dg_pick_group(c_out, DG_H_BASE(h), last_out, lane, &M);
+                        if (__popcll(c_out) >= 2) b = dg_pick_group<DgWave>(c_out, DG_H_BASE(h), last_out, lane, &M);
                         if (b == 256) break;
 #ifdef DG_STAMPS
                         const unsigned long long tg0 = clock64();
 #endif
-                        const bool okg = dgw_merge_out_group(g, u, nu, M, nbr, cnt, h, live, lane);
+                        const bool okg = dg_merge_out_group<DgWave>(g, u, nu.out_off, M, nbr, cnt, h, live, lane);
 #ifdef DG_STAMPS
                         c_grp += clock64() - tg0; ng_out++;
 #endif
@@ -994,7 +1032,7 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
             const unsigned long long cand = __ballot(valid && DG_H_OUTLEN(h) == 1 && !(sh && ((h.y >> 8) & DG_NF_SHARED)));
             unsigned long long M = 0;
             int b = 256;
-            if (__popcll(cand) >= 2) b = dg_pick_group(cand, DG_H_BASE(h), fr_last, lane, &M);
+            if (__popcll(cand) >= 2) b = dg_pick_group<DgWave>(cand, DG_H_BASE(h), fr_last, lane, &M);
             if (b == 256) {                               // frame done: pop
                 sp--;
                 if (sp > 0) { fr_n = s_stk[2 * (sp - 1)]; fr_last = s_stk[2 * (sp - 1) + 1]; }
@@ -1005,7 +1043,7 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
 #ifdef DG_STAMPS
             const unsigned long long tg0 = clock64();
 #endif
-            if (!dgw_merge_in_group(g, fr_n, nn, M, s, h, valid, lane, &an)) { scalar = true; break; }
+            if (!dg_merge_in_group<DgWave>(g, fr_n, nn.in_off, M, s, h, valid, lane, &an)) { scalar = true; break; }
 #ifdef DG_STAMPS
             acc_grp += clock64() - tg0; n_grp_in++;
 #endif
@@ -1048,15 +1086,15 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
                 const unsigned long long cand = __ballot(valid && DG_H_INLEN(h) == 1 && d != X);
                 unsigned long long M = 0;
                 int b = 256;
-                if (__popcll(cand) >= 2) b = dg_pick_group(cand, DG_H_BASE(h), last_out, lane, &M);
+                if (__popcll(cand) >= 2) b = dg_pick_group<DgWave>(cand, DG_H_BASE(h), last_out, lane, &M);
                 if (b != 256) {
 #ifdef DG_STAMPS
                     const unsigned long long tg0 = clock64();
-                    const bool okg = dgw_merge_out_group(g, u, nu, M, d, cnt, h, valid, lane);
+                    const bool okg = dg_merge_out_group<DgWave>(g, u, nu.out_off, M, d, cnt, h, valid, lane);
                     acc_grp += clock64() - tg0; n_grp_out++;
                     if (okg) {
 #else
-                    if (dgw_merge_out_group(g, u, nu, M, d, cnt, h, valid, lane)) {
+                    if (dg_merge_out_group<DgWave>(g, u, nu.out_off, M, d, cnt, h, valid, lane)) {
 #endif
                         merged = true;
                         last_out = b;

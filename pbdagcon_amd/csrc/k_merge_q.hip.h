@@ -10,7 +10,9 @@
 // single-lane path (dgg_*), as lists longer than a wave do in k_merge.
 //
 // Exactness is inherited: every row runs exactly the sweep of dg_merge_segment on its own segment, and segments
-// touch disjoint state (the cut argument above k_cuts).  Full-span pileups only (p.gcuts == 0).
+// touch disjoint state (the cut argument above k_cuts).  The merge of a group is not written again here: it is
+// k_merge.hip.h's dg_merge_in_group / dg_merge_out_group, instantiated for a row (DgRow) where k_merge instantiates
+// them for the wave (DgWave).  Full-span pileups only (p.gcuts == 0).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dagcon_dev.h"
@@ -46,283 +48,17 @@ __device__ __forceinline__ void dq_fail(DgGraph &g, uint32_t bit, int lane) {
     }
     g.err = true;
 }
-__device__ __forceinline__ int dq_sum_masked(int v, qmask m) {
-    int acc = 0;
-    while (m) {
-        const int f = __ffs((int)m) - 1;
-        acc += dq_rl(v, f);
-        m &= m - 1u;
-    }
-    return acc;
-}
-// smallest base > last that at least two candidate lanes share; returns the base (or 256) and the mask of its lanes
-__device__ __forceinline__ int dq_pick_group(qmask cand, int base, int last, int lane, qmask *mask) {
-    int best = 256;
-    qmask bm = 0;
-    const int key = ((cand >> lane) & 1u) ? base : -1 - lane;
-    while (cand) {
-        const int f = __ffs((int)cand) - 1;
-        const int b = dq_rl(key, f);
-        const qmask same = dq_ballot(key == b);
-        if (b > last && b < best && __popc(same) >= 2) { best = b; bm = same; }
-        cand &= ~same;
-    }
-    *mask = bm;
-    return best;
-}
-__device__ __forceinline__ uint32_t dq_alloc(DgGraph &g, uint32_t words, int lane) {
-    uint32_t off = 0;
-    if (lane == 0) { DgGraph gs = g; off = dgg_alloc(gs, words); }
-    off = (uint32_t)dq_rl((int)off, 0);
-    if (off == 0xFFFFFFFFu) g.err = true;
-    return off;
-}
-
-// Removes from in[v] every source held (in `vid`) by a lane of vm (stable), then appends `app` when app >= 0.
-// pend_delta is added to v's pending counter.  Requires in_len(v) <= DQ_W.
-__device__ inline void dq_in_rewrite(DgGraph &g, int v, int vid, qmask vm, int app, int pend_delta, int lane) {
-    const uint4 h = dg_lo16(&DG_NV(g, v)), h2 = dg_hi16(&DG_NV(g, v));
-    const int len = DG_H_INLEN(h);
-    uint32_t off = DG_H2_INOFF(h2);
-    int cap = DG_H2_INCAP(h2);
-    int e = -1;
-    if (lane < len) e = (int)DG_PW(g, off + lane);
-    bool rm = false;
-    for (qmask m = vm; m; m &= m - 1u) rm |= (e == dq_rl(vid, __ffs((int)m) - 1));
-    const bool keep = lane < len && !rm;
-    const qmask km = dq_ballot(keep);
-    int nlen = __popc(km);
-    const int nidx = __popc(km & DQ_LT(lane));
-    if (app >= 0 && nlen + 1 > cap) {
-        uint32_t ncap = 2u * (uint32_t)(nlen + 1);
-        if (ncap < 4) ncap = 4;
-        const uint32_t noff = dq_alloc(g, ncap, lane);
-        if (noff == 0xFFFFFFFFu) return;
-        off = noff; cap = (int)ncap;
-    }
-    if (keep) DG_PW(g, off + nidx) = (uint32_t)e;
-    if (app >= 0) { if (lane == 0) DG_PW(g, off + nlen) = (uint32_t)app; nlen++; }
-    if (lane == 0) {
-        DgNode *n = &DG_NV(g, v);
-        n->in_len = (uint16_t)nlen; n->in_off = off; n->in_cap = (uint16_t)cap;
-        if (pend_delta) n->pending = DG_H_PEND(h) + pend_delta;
-    }
-}
-
-// ---- mergeOutNodes, one group (AlnGraphBoost.cpp:229-266); as dgw_merge_out_group, on a row ----------
-// Lanes of M hold out entries of u: d (target), cnt, h (first half of the target's record); survivor = lowest lane.
-// Returns false, with nothing modified, when a list involved is longer than a row.
-__device__ inline bool dq_merge_out_group(DgGraph &g, int u, uint32_t u_out_off, qmask M, int d, int &cnt, uint4 h,
-                                          bool valid_out, qmask out_lanes, int lane) {
-    const int an_lane = __ffs((int)M) - 1;
-    const qmask vm = M & ~(1u << an_lane);
-    const int an = dq_rl(d, an_lane);
-    const bool member = (M >> lane) & 1u;
-    uint4 h2 = make_uint4(0, 0, 0, 0);
-    if (member) h2 = dg_hi16(&DG_NV(g, d));
-    // members' out entries flattened onto lanes 0..L-1: survivor's first, then victims in order
-    int L = 0, src = -1, e = 0;
-    uint32_t src_off = 0;
-    {
-        qmask mm = M;
-        while (mm) {
-            const int ml = __ffs((int)mm) - 1;
-            mm &= mm - 1u;
-            const int mlen = dq_rl(DG_H_OUTLEN(h), ml);
-            const uint32_t moff = (uint32_t)dq_rl((int)DG_H2_OUTOFF(h2), ml);
-            if (lane >= L && lane < L + mlen) { src = ml; e = lane - L; src_off = moff; }
-            L += mlen;
-        }
-    }
-    if (L > DQ_W) return false;
-    const bool fl = lane < L;
-    int n2 = -1, c2 = 0;
-    if (fl) { n2 = (int)DG_PW(g, src_off + 2 * e); c2 = (int)DG_PW(g, src_off + 2 * e + 1); }
-    const bool vic_entry = fl && src != an_lane;
-    uint4 hn2 = make_uint4(0, 0, 0, 0);
-    if (vic_entry) hn2 = dg_lo16(&DG_NV(g, n2));
-    if (dq_ballot(vic_entry && DG_H_INLEN(hn2) > DQ_W)) return false;
-    if (g.sh && dq_ballot(vic_entry && ((hn2.y >> 8) & DG_NF_SHARED))) return false;      // in[exit] is shared: literal path
-
-    // ---- nothing has been modified up to here ----
-    const int add_cnt = dq_sum_masked(cnt, vm);
-    const int add_w = dq_sum_masked(DG_H_WEIGHT(h), vm);
-    // :246-265 fold the victims' out edges into the survivor's, first occurrence order
-    qmask rem = dq_ballot(fl), first_m = 0;
-    const qmask vics = dq_ballot(vic_entry);
-    int newcnt = c2;
-    while (rem) {
-        const int f = __ffs((int)rem) - 1;
-        const int x = dq_rl(n2, f);
-        const qmask same = dq_ballot(fl && n2 == x);
-        rem &= ~same;
-        first_m |= 1u << f;
-        const int tot = dq_sum_masked(c2, same);
-        if (lane == f) newcnt = tot;
-        const qmask vsame = same & vics;
-        const int nv = __popc(vsame);
-        if (nv) {
-            const bool is_new = (vsame >> f) & 1u;         // survivor had no edge to x
-            dq_in_rewrite(g, x, d, vm, is_new ? an : -1, -(nv - (is_new ? 1 : 0)), lane);
-            if (g.err) return true;
-        }
-    }
-    // survivor's new out list
-    {
-        const int nlen = __popc(first_m);
-        uint32_t off = (uint32_t)dq_rl((int)DG_H2_OUTOFF(h2), an_lane);
-        int cap = dq_rl(DG_H2_OUTCAP(h2), an_lane);
-        if (nlen > cap) {
-            uint32_t ncap = 2u * (uint32_t)(nlen + 1);
-            if (ncap < 4) ncap = 4;
-            const uint32_t noff = dq_alloc(g, 2u * ncap, lane);
-            if (noff == 0xFFFFFFFFu) return true;
-            off = noff; cap = (int)ncap;
-        }
-        if ((first_m >> lane) & 1u) {
-            const int idx = __popc(first_m & DQ_LT(lane));
-            DG_PW(g, off + 2 * idx) = (uint32_t)n2;
-            DG_PW(g, off + 2 * idx + 1) = (uint32_t)newcnt;
-        }
-        const int an_w = dq_rl(DG_H_WEIGHT(h), an_lane);
-        if (lane == 0) {
-            DgNode *a = &DG_NV(g, an);
-            a->out_len = (uint16_t)nlen; a->out_off = off; a->out_cap = (uint16_t)cap;
-            a->weight = an_w + add_w;
-        }
-    }
-    // u's out list without the victims (stable), survivor's edge count updated.  out_lanes: the lanes that hold
-    // u's out entries, in list order
-    {
-        const bool keep = valid_out && !((vm >> lane) & 1u);
-        const qmask km = dq_ballot(keep);
-        if (keep) {
-            const int idx = __popc(km & DQ_LT(lane));
-            DG_PW(g, u_out_off + 2 * idx) = (uint32_t)d;
-            if (lane == an_lane) cnt += add_cnt;
-            DG_PW(g, u_out_off + 2 * idx + 1) = (uint32_t)cnt;
-        }
-        if (lane == 0) DG_NV(g, u).out_len = (uint16_t)__popc(km);
-    }
-    (void)out_lanes;
-    // AlnGraphBoost.cpp:269-273 for every victim
-    if ((vm >> lane) & 1u) {
-        DgNode *vn = &DG_NV(g, d);
-        vn->out_len = 0; vn->in_len = 0; vn->flags |= DG_NF_DELETED;
-    }
-    return true;
-}
-
-// ---- mergeInNodes, one group (AlnGraphBoost.cpp:176-212); as dgw_merge_in_group, on a row ---------------
-// Lanes 0.. hold n's in entries: s (source), h (first half of its record).  *an_out = survivor.
-__device__ inline bool dq_merge_in_group(DgGraph &g, int n, uint32_t n_in_off, qmask M, int s, uint4 h, bool valid_in,
-                                         int lane, int *an_out) {
-    const int an_lane = __ffs((int)M) - 1;
-    const qmask vm = M & ~(1u << an_lane);
-    const int an = dq_rl(s, an_lane);
-    *an_out = an;
-    const bool member = (M >> lane) & 1u;
-    const bool victim = (vm >> lane) & 1u;
-    uint4 h2 = make_uint4(0, 0, 0, 0);
-    if (member) h2 = dg_hi16(&DG_NV(g, s));
-    int c0 = 0;
-    if (member) c0 = (int)DG_PW(g, DG_H2_OUTOFF(h2) + 1);     // count of its single out edge (-> n)
-    // victims' in entries flattened onto lanes 0..L-1, victims in order
-    int L = 0, e = 0;
-    uint32_t src_off = 0;
-    {
-        qmask mm = vm;
-        while (mm) {
-            const int ml = __ffs((int)mm) - 1;
-            mm &= mm - 1u;
-            const int mlen = dq_rl(DG_H_INLEN(h), ml);
-            const uint32_t moff = (uint32_t)dq_rl((int)DG_H2_INOFF(h2), ml);
-            if (lane >= L && lane < L + mlen) { e = lane - L; src_off = moff; }
-            L += mlen;
-        }
-    }
-    if (L > DQ_W) return false;
-    const bool fl = lane < L;
-    int n1 = -1;
-    if (fl) n1 = (int)DG_PW(g, src_off + e);
-    uint4 hn1 = make_uint4(0, 0, 0, 0);
-    if (fl) hn1 = dg_lo16(&DG_NV(g, n1));
-    if (dq_ballot(fl && DG_H_OUTLEN(hn1) > DQ_W)) return false;
-    if (g.sh && dq_ballot(fl && ((hn1.y >> 8) & DG_NF_SHARED))) return false;            // a shared out-list: literal path
-    const int a_in_len0 = dq_rl(DG_H_INLEN(h), an_lane);
-
-    // ---- nothing has been modified up to here ----
-    const int add_cnt = dq_sum_masked(c0, vm);
-    const int add_w = dq_sum_masked(DG_H_WEIGHT(h), vm);
-    if (lane == an_lane) {
-        DG_PW(g, DG_H2_OUTOFF(h2) + 1) = (uint32_t)(c0 + add_cnt);
-        DG_NV(g, an).weight = DG_H_WEIGHT(h) + add_w;
-    }
-    // :193-212 re-point the victims' in edges to the survivor, in order
-    uint32_t a_in_off = (uint32_t)dq_rl((int)DG_H2_INOFF(h2), an_lane);
-    int a_in_cap = dq_rl(DG_H2_INCAP(h2), an_lane);
-    int a_in_len = a_in_len0;
-    bool a_dirty = false;
-    qmask rem = dq_ballot(fl);
-    while (rem) {
-        const int f = __ffs((int)rem) - 1;
-        const int x = dq_rl(n1, f);
-        rem &= ~dq_ballot(fl && n1 == x);
-        // out[x]: drop the entries that point at victims, fold their counts into x->an
-        const uint4 hx2 = dg_hi16(&DG_NV(g, x));
-        const int xlen = dq_rl(DG_H_OUTLEN(hn1), f);
-        const uint32_t xoff = DG_H2_OUTOFF(hx2);
-        int dst = -1, c = 0;
-        if (lane < xlen) { dst = (int)DG_PW(g, xoff + 2 * lane); c = (int)DG_PW(g, xoff + 2 * lane + 1); }
-        bool isv = false;
-        for (qmask m = vm; m; m &= m - 1u) isv |= (dst == dq_rl(s, __ffs((int)m) - 1));
-        const qmask vmask = dq_ballot(lane < xlen && isv);
-        const int csum = dq_sum_masked(c, vmask);
-        const qmask apos = dq_ballot(lane < xlen && dst == an);
-        const bool keep = lane < xlen && !isv;
-        const qmask km = dq_ballot(keep);
-        int nlen = __popc(km);
-        if (keep) {
-            const int idx = __popc(km & DQ_LT(lane));
-            DG_PW(g, xoff + 2 * idx) = (uint32_t)dst;
-            DG_PW(g, xoff + 2 * idx + 1) = (uint32_t)(((apos >> lane) & 1u) ? c + csum : c);
-        }
-        if (!apos) {
-            // new edge x->an: END of out[x] (room is there: at least one entry was dropped)
-            if (lane == 0) { DG_PW(g, xoff + 2 * nlen) = (uint32_t)an; DG_PW(g, xoff + 2 * nlen + 1) = (uint32_t)csum; }
-            nlen++;
-            // ... and END of in[an]
-            if (a_in_len + 1 > a_in_cap) {
-                uint32_t ncap = 2u * (uint32_t)(a_in_len + 1);
-                if (ncap < 4) ncap = 4;
-                const uint32_t noff = dq_alloc(g, ncap, lane);
-                if (noff == 0xFFFFFFFFu) return true;
-                for (int i = lane; i < a_in_len; i += DQ_W) DG_PW(g, noff + i) = DG_PW(g, a_in_off + i);
-                a_in_off = noff; a_in_cap = (int)ncap;
-            }
-            if (lane == 0) DG_PW(g, a_in_off + a_in_len) = (uint32_t)x;
-            a_in_len++;
-            a_dirty = true;
-        }
-        if (lane == 0) DG_NV(g, x).out_len = (uint16_t)nlen;
-    }
-    if (a_dirty && lane == 0) {
-        DgNode *a = &DG_NV(g, an);
-        a->in_len = (uint16_t)a_in_len; a->in_off = a_in_off; a->in_cap = (uint16_t)a_in_cap;
-    }
-    // in[n] without the victims (stable)
-    {
-        const bool keep = valid_in && !victim;
-        const qmask km = dq_ballot(keep);
-        if (keep) DG_PW(g, n_in_off + __popc(km & DQ_LT(lane))) = (uint32_t)s;
-        if (lane == 0) DG_NV(g, n).in_len = (uint16_t)__popc(km);
-    }
-    if (victim) {
-        DgNode *vn = &DG_NV(g, s);
-        vn->out_len = 0; vn->in_len = 0; vn->flags |= DG_NF_DELETED;
-    }
-    return true;
-}
+// the row as a lane group of the merge rule (dg_merge_in_group / dg_merge_out_group, k_merge.hip.h)
+struct DgRow {
+    typedef qmask mask;
+    static constexpr int W = DQ_W;
+    static constexpr bool row_text = true;
+    static __device__ __forceinline__ mask ballot(bool p) { return dq_ballot(p); }
+    static __device__ __forceinline__ int rl(int v, int l) { return dq_rl(v, l); }
+    static __device__ __forceinline__ int ffs(mask m) { return __ffs((int)m); }
+    static __device__ __forceinline__ int popc(mask m) { return __popc(m); }
+    static __device__ __forceinline__ mask lt(int lane) { return DQ_LT(lane); }
+};
 
 #define DQ_IN_STACK 48
 // what a row is doing (dq_merge_segment)
@@ -447,7 +183,7 @@ __device__ __forceinline__ void dq_merge_segment(const DgParams &p, const uint32
             const qmask cand = dq_ballot(valid && DG_H_OUTLEN(h) == 1);
             qmask M = 0;
             int b = 256;
-            if (__popc(cand) >= 2) b = dq_pick_group(cand, DG_H_BASE(h), fr_last, lane, &M);
+            if (__popc(cand) >= 2) b = dg_pick_group<DgRow>(cand, DG_H_BASE(h), fr_last, lane, &M);
             if (b == 256) {                               // frame done: pop
                 sp--;
                 if (sp > 0) { fr_n = s_stk[2 * (sp - 1)]; fr_last = s_stk[2 * (sp - 1) + 1]; }
@@ -455,7 +191,7 @@ __device__ __forceinline__ void dq_merge_segment(const DgParams &p, const uint32
             }
             if (sp >= DQ_IN_STACK) { scalar = true; break; }
             int an = -1;
-            if (!dq_merge_in_group(g, fr_n, DG_H2_INOFF(nh), M, s, h, valid, lane, &an)) { scalar = true; break; }
+            if (!dg_merge_in_group<DgRow>(g, fr_n, DG_H2_INOFF(nh), M, s, h, valid, lane, &an)) { scalar = true; break; }
             if (g.err) break;
             fr_last = b;
             if (lane == 0) { s_stk[2 * (sp - 1)] = fr_n; s_stk[2 * (sp - 1) + 1] = fr_last; }
@@ -490,9 +226,9 @@ __device__ __forceinline__ void dq_merge_segment(const DgParams &p, const uint32
                 const qmask cand = dq_ballot(valid && DG_H_INLEN(h) == 1 && d != X);
                 qmask M = 0;
                 int b = 256;
-                if (__popc(cand) >= 2) b = dq_pick_group(cand, DG_H_BASE(h), last_out, lane, &M);
+                if (__popc(cand) >= 2) b = dg_pick_group<DgRow>(cand, DG_H_BASE(h), last_out, lane, &M);
                 if (b != 256) {
-                    if (dq_merge_out_group(g, u, DG_H2_OUTOFF(uh), M, d, cnt, h, valid, DQ_ALL, lane)) {
+                    if (dg_merge_out_group<DgRow>(g, u, DG_H2_OUTOFF(uh), M, d, cnt, h, valid, lane)) {
                         last_out = b;
                         continue;                         // re-read u's list, look for the next group
                     }
@@ -540,7 +276,7 @@ __device__ __forceinline__ void dq_merge_segment(const DgParams &p, const uint32
     }
 }
 
-// mergeNodes, four (target, segment of p.cuts) pairs per wave: row r of block b sweeps pair 4 b + r.  (Rows that take
+// mergeNodes, DQ_ROWS = 8 (target, segment of p.cuts) pairs per wave: row r of block b sweeps pair DQ_ROWS b + r.  (Rows that take
 // their pairs off a ticket counter, one after the other, were 2 - 3 ms slower at configs[1] than this grid with the
 // number of pieces chosen so that the waves fill the chip a whole number of times: dagcon_upload.)
 #ifndef DQ_WAVES

@@ -120,10 +120,15 @@ def _oracle_graph(batch, t, min_len, trim, merge):
     return g.adjacency(), o2d
 
 
-def _check_graphs(ctx, batch, trim, merge, targets=None):
+def _check_graphs(ctx, batch, trim, merge, targets=None, oracle_graphs=None):
+    """The device graph of every target against the oracle's (oracle_graphs[t]: the value of
+    _oracle_graph for target t, where a caller checks several runs against it).  Returns the
+    device graphs it read."""
+    read = []
     for t in (range(batch.n_targets) if targets is None else targets):
         got = ctx.debug_graph(t)
-        exp, o2d = _oracle_graph(batch, t, 0, trim, merge)
+        read.append(got)
+        exp, o2d = oracle_graphs[t] if oracle_graphs is not None else _oracle_graph(batch, t, 0, trim, merge)
         assert len(got) == len(exp) == len(o2d), f"target {t}: vertex count"
         assert sorted(o2d) == list(range(len(got)))
         blen = int(batch.tlen[t])
@@ -138,6 +143,7 @@ def _check_graphs(ctx, batch, trim, merge, targets=None):
                 assert g["coverage"] == ec, f"target {t} vertex {o}: coverage"
             assert g["out"] == [(o2d[d], c) for d, c in eoe], f"target {t} vertex {o}: out list"
             assert g["inn"] == [o2d[s] for s, _ in eie], f"target {t} vertex {o}: in list"
+    return read
 
 
 @pytest.mark.parametrize("merge", [False, True])
@@ -256,6 +262,58 @@ def test_segments_on_adversarial_little_pileups(gpu_ctx_factory, seed):
             assert (g["base"], g["weight"]) == (eb, ew)
             assert g["out"] == [(o2d[d], c) for d, c in eoe], f"target {t} vertex {o}: out list"
             assert g["inn"] == [o2d[s] for s, _ in eie], f"target {t} vertex {o}: in list"
+
+
+def _full_span_pileups(seed, n=60):
+    """n full-span little pileups on tiny alphabets: two of every three 2 - 9 reads deep, the
+    third 12 - 20 deep."""
+    rng = np.random.default_rng(seed)
+    targets = []
+    for i in range(n):
+        tl = int(rng.integers(20, 160))
+        depth = int(rng.integers(12, 21)) if i % 3 == 2 else int(rng.integers(2, 10))
+        alns, bb = random_target(rng, tl, depth, alphabet=[b"AC", b"ACGT", b"A"][(i // 3) % 3],
+                                 sub=float(rng.uniform(0, 0.1)), ins=float(rng.uniform(0, 0.25)),
+                                 dele=float(rng.uniform(0, 0.12)), full_span=True)
+        targets.append((tl, alns, bb))
+    return targets
+
+
+def test_merge_rule_on_rows_and_on_waves(gpu_ctx_factory, monkeypatch):
+    """One text of the merge of a group (dg_merge_in_group / dg_merge_out_group), two
+    instances: a row of 8 lanes in k_merge_q, the wave in k_merge.  Full-span pileups cut every
+    few bases take k_merge_q; with DAGCON_MERGE_Q=0 the same cuts are swept by k_merge.  Both
+    leave the oracle's merged graph, vertex by vertex and in adjacency order, hence the same
+    graph, and then the oracle's consensus.  At 12 - 20 reads a vertex's lists outgrow a row
+    but not a wave: there the row instance refuses (nothing modified) and the literal path
+    finishes the visit, while the wave instance merges in parallel.
+
+    The seed was chosen on the CPU with oracle/pymodel.py's AlnGraph, its merge_in and
+    merge_out counting the groups of two or more that they merge and the length of the list
+    they were found in.  Seed 22: 16 of the 40 shallow and 14 of the 20 deep targets have groups
+    on the in side and on the out side; the shallow targets have 78 in and 576 out groups in
+    lists of at most 8 entries (and 27 out groups in lists a little longer), the deep ones 167
+    in and 847 out groups in lists of at most 8 and 5 in and 180 out groups in lists of 9 - 64;
+    no list with a group is longer than a wave."""
+    targets = _full_span_pileups(22)
+    batch = batch_from_targets(targets)
+    n = batch.n_targets
+    kw = dict(min_cov=0, min_len=0, trim=0, min_weight=0, max_segments=16, min_segment_len=4)
+    oracle_graphs = [_oracle_graph(batch, t, 0, 0, True) for t in range(n)]
+    exp = oracle_batch(batch, 0, 0, 0, 0)
+    graphs = {}
+    monkeypatch.delenv("DAGCON_MERGE_Q", raising=False)
+    for q in ("unset", "0"):                  # k_merge_q (max_segments on a full-span batch selects it), then k_merge
+        if q == "0":
+            monkeypatch.setenv("DAGCON_MERGE_Q", q)
+        ctx = gpu_ctx_factory(flags=capi.FLAG_STOP_AFTER_MERGE, **kw)
+        ctx.consensus(batch)
+        assert ctx.timings()["merge_segments"] > 3 * n, f"DAGCON_MERGE_Q={q}"     # the cuts were really used
+        graphs[q] = _check_graphs(ctx, batch, 0, True, oracle_graphs=oracle_graphs)
+        ctx = gpu_ctx_factory(**kw)
+        assert ctx.consensus(batch) == exp, f"DAGCON_MERGE_Q={q}"
+        assert ctx.timings()["merge_segments"] > 3 * n
+    assert graphs["unset"] == graphs["0"]
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])

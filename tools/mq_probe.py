@@ -1,4 +1,4 @@
-"""configs[1] and other full-span shapes: k_merge (a wave per segment) against k_merge_q (four segments per wave)."""
+"""configs[1] and other full-span shapes: k_merge (a wave per segment) against k_merge_q (eight segments per wave)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

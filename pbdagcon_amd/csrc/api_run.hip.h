@@ -269,10 +269,17 @@ int launch_all(Ctx *c) {
             if (wide) hipLaunchKernelGGL(k_emit<uint32_t>, eg, dim3(64), 0, s, p);
             else hipLaunchKernelGGL(k_emit<uint8_t>, eg, dim3(64), 0, s, p);
         }
-        const size_t lds = (size_t)4 * 2 * (c->max_k + 2) * sizeof(int32_t);
-        if (lds > 65536)
-            HIPCHK(c, hipFuncSetAttribute((const void *)k_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_lists, dim3(c->T, rows4), dim3(256), lds, s, p);
+        // targets of up to 64 reads: a lane per position, a wave's 64 rows in LDS (33,280 bytes a block at the most)
+        const size_t lds_lanes = (size_t)DG_LL_WAVES * DG_WAVE * (std::min<uint32_t>(c->max_k, DG_WAVE) | 1u) * sizeof(uint32_t);
+        hipLaunchKernelGGL(k_lists_lanes, dim3(c->T, (c->max_tlen + 2 + DG_LL_WAVES * DG_WAVE - 1) / (DG_LL_WAVES * DG_WAVE)),
+                           dim3(DG_LL_WAVES * DG_WAVE), lds_lanes, s, p);
+        if (c->max_k > DG_WAVE) {
+            // (the deep targets of the batch: a wave per position)
+            const size_t lds = (size_t)4 * 2 * (c->max_k + 2) * sizeof(int32_t);
+            if (lds > 65536)
+                HIPCHK(c, hipFuncSetAttribute((const void *)k_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k_lists, dim3(c->T, rows4), dim3(256), lds, s, p);
+        }
     }
     HIPCHK(c, hipEventRecord(c->ev[2], s));
     if (c->T > 0 && !(c->opts.flags & DAGCON_FLAG_STOP_AFTER_BUILD)) {

@@ -10,9 +10,10 @@
 //   k_gscan      a2  per target: exclusive scan over positions -> position-ordered vertex ids
 //   k_emit       a2  addAln (AlnGraphBoost.cpp:64-107): one lane per alignment walks its columns;
 //                    plain stores only (arrival / departure cells, inserted vertex records)
-//   k_lists      a2  backbone vertices (AlnGraphBoost.cpp:16-62), addEdge dedupe (:109-127) + coverage / weight / base:
-//                    one wave per DG_LPW backbone positions turns each one's arrival / departure rows into
-//                    ordered adjacency lists (ballot / popcount peeling)
+//   k_lists*     a2  backbone vertices (AlnGraphBoost.cpp:16-62), addEdge dedupe (:109-127) + coverage / weight / base:
+//                    each position's arrival / departure rows become ordered adjacency lists.  k_lists_lanes (targets
+//                    of up to 64 reads): a lane per position scans its rows out of LDS (k_lists_row.hip.h); k_lists
+//                    (deeper targets): one wave per DG_LPW positions, ballot / popcount peeling
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dagcon_dev.h"
@@ -20,7 +21,7 @@
 
 #define DG_WAVE 64
 #ifndef DG_LPW
-#define DG_LPW 8u             // positions per wave of k_lists / k_groups
+#define DG_LPW 8u             // positions per wave of k_lists
 #endif
 
 __device__ __forceinline__ bool dg_failed(const DgParams &p) {
@@ -1140,8 +1141,9 @@ __global__ __launch_bounds__(64) void k_emit(DgParams p) {
 }
 
 // ---------------------------------------------------------------------------
-// k_lists: one wave per DG_LPW backbone positions.
+// k_lists_lanes (K <= 64 reads: a lane per backbone position) and k_lists (deeper targets: a wave per position).
 // ---------------------------------------------------------------------------
+#include "k_lists_row.hip.h"
 __device__ __forceinline__ int dg_lds_find(volatile int32_t *vals, int n, int x, int lane) {
     for (int b = 0; b < n; b += DG_WAVE) {
         int i = b + lane;
@@ -1186,120 +1188,213 @@ __device__ __forceinline__ unsigned long long dg_list_row(int32_t val, int32_t e
     return firsts;
 }
 
-// k_lists for K <= 64 reads: the wave's DG_LPW positions in turn with wave-uniform control, both rows of a position side
-// by side, the next position's row loads issued ahead of this one's ballots (hipcc still waits for all of them at the
-// first ballot: the other waves hide the latency).  What the positions share is fetched once, a position per lane (ids,
-// group bases); what a position makes of its rows is wave-uniform and lands in the lane of that position, whose vertex
-// record and coverage word go out once for the whole wave.
-__device__ __forceinline__ void dg_lists_wave(const DgParams &p, uint32_t t, uint32_t pos0, uint32_t blen, uint32_t K,
+// One position with the reads on the lanes (K <= 64), wave-uniform control, both rows side by side: the routine
+// k_lists_lanes falls back on for the rows its lanes cannot list.  `dep` / `arr`: the lane's cell of either row; v1: this
+// vertex's id + 1; chain / ulo of either side as in dg_list_row.  What it makes of the rows is wave-uniform and comes
+// back in `r`; false: a growth-region allocation failed.
+struct DgPosLists { uint32_t o_len, o_off, o_cap, i_len, i_off, i_cap, cov; };
+
+__device__ __forceinline__ bool dg_lists_pos(const DgParams &p, uint32_t t, uint32_t *pool, uint32_t pos, uint32_t blen,
+                                             uint32_t capb, uint32_t fixed0, int lane, bool do_out, bool do_in,
+                                             uint32_t dep, uint32_t arr, int32_t v1, int32_t chain_o, int32_t ulo_o,
+                                             int32_t chain_i, int32_t ulo_i, DgPosLists &r) {
+#define DG_LPOOL(OFF) (*reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(pool) + (((uint32_t)(OFF)) << 2)))
+    if (do_out) {
+        // out list from the departures: neighbour id + 1 (0 = none) and, above bit 25, the reads k_emit folded into this one's chain
+        const int32_t val = (int32_t)DG_CELL_ID(dep), extra = (int32_t)(dep >> 25);
+        int32_t cnt;
+        unsigned long long cm;
+        const unsigned long long firsts = dg_list_row(val, extra, chain_o, ulo_o, chain_o, lane, cnt, cm);
+        const uint32_t n = 1u + (uint32_t)__popcll(firsts);
+        uint32_t off = fixed0 + pos * 3u * capb, cap = capb;
+        if (n > capb) {                                     // rare: move to the growth region
+            cap = n + 2u;
+            off = dg_pool_alloc(p, t, 2u * cap, lane);
+            if (off == 0xFFFFFFFFu) return false;
+        }
+        const uint32_t idx = 1u + (uint32_t)__popcll(firsts & ((1ull << lane) - 1ull));
+        if (lane == 0) { DG_LPOOL(off) = (uint32_t)(chain_o - 1); DG_LPOOL(off + 1) = (uint32_t)__popcll(cm); }
+        if ((firsts >> lane) & 1ull) { DG_LPOOL(off + 2 * idx) = (uint32_t)(val - 1); DG_LPOOL(off + 2 * idx + 1) = (uint32_t)cnt; }
+        r.o_len = n; r.o_off = off; r.o_cap = cap;
+    }
+    if (do_in) {
+        // in list from the arrivals, and the coverage of the position
+        const uint32_t idf = DG_CELL_ID(arr);
+        r.cov = 0;
+        if (pos <= blen) {
+            const unsigned long long covered = __ballot(arr != 0u);
+            const uint32_t n_cov = (uint32_t)__popcll(covered);
+            const uint32_t n_match = (uint32_t)__popcll(__ballot(arr != 0u && idf != DG_CELL_DEL));
+            const uint32_t last_base = covered ? DG_CELL_BASE((uint32_t)__builtin_amdgcn_readlane((int)arr, 63 - __clzll((long long)covered))) : 0u;
+            r.cov = n_cov | n_match << 8 | last_base << 16;
+        }
+        const int32_t val = (arr != 0u && idf != DG_CELL_DEL && idf != DG_CELL_DUP) ? (int32_t)idf : 0;
+        int32_t cnt;
+        unsigned long long cm;
+        const unsigned long long firsts = dg_list_row(val, 0, chain_i, ulo_i, v1, lane, cnt, cm);
+        const uint32_t n = 1u + (uint32_t)__popcll(firsts);
+        uint32_t off = fixed0 + pos * 3u * capb + 2u * capb, cap = capb;
+        if (n > capb) {
+            cap = n + 2u;
+            off = dg_pool_alloc(p, t, cap, lane);
+            if (off == 0xFFFFFFFFu) return false;
+        }
+        const uint32_t idx = 1u + (uint32_t)__popcll(firsts & ((1ull << lane) - 1ull));
+        if (lane == 0) DG_LPOOL(off) = (uint32_t)(chain_i - 1);
+        if ((firsts >> lane) & 1ull) DG_LPOOL(off + idx) = (uint32_t)(val - 1);
+        r.i_len = n; r.i_off = off; r.i_cap = cap;
+    }
+#undef DG_LPOOL
+    return true;
+}
+
+// a lane's growth-region allocation (dg_pool_alloc's rule, a lane at a time); 0xFFFFFFFF: the pool of the target is full
+__device__ __forceinline__ uint32_t dg_pool_alloc_lane(const DgParams &p, uint32_t t, uint32_t words) {
+    const uint32_t off = atomicAdd(&p.pool_top[t], words);
+    if ((uint64_t)off + words > p.pool_size[t]) { dg_fail(p, DG_E_POOL_TGT); p.st->bad_target = t; return 0xFFFFFFFFu; }
+    return off;
+}
+
+// the wave's block of rows (nrows x K words, contiguous in HBM) -> LDS with row stride S, loaded coalesced
+__device__ __forceinline__ void dg_stage_rows(uint32_t *rows, const uint32_t *blk, uint32_t nrows, uint32_t K, uint32_t S,
                                               int lane) {
-    const uint32_t npos = min(DG_LPW, blen + 2 - pos0);
+    if (K == 0) return;
+    const uint32_t total = nrows * K, q = DG_WAVE / K, rm = DG_WAVE % K;
+    uint32_t row = (uint32_t)lane / K, col = (uint32_t)lane % K;
+#pragma unroll 4
+    for (uint32_t i = (uint32_t)lane; i < total; i += DG_WAVE) {
+        rows[row * S + col] = blk[i];
+        row += q; col += rm;
+        if (col >= K) { col -= K; row++; }
+    }
+}
+
+#define DG_LL_WAVES 2u         // waves per block of k_lists_lanes (each holds 64 rows of up to 65 words in LDS)
+
+// k_lists for K <= 64 reads: a lane per backbone position, a wave per 64 consecutive positions of one target.  The
+// departure rows of the 64 positions are one contiguous block of matD: it goes to LDS coalesced (odd row stride: lane p
+// reading word p * S + r meets no bank conflict) and every lane scans its own row once (dg_lane_row), staging the
+// entries in place; the lists go out entry by entry, the arrival rows follow through the same LDS.  A row with more
+// distinct backbone neighbours than the lane's table (enter's departures and exit's arrivals under partial spans,
+// many deletion-run lengths at one position) is left to dg_lists_pos, a position at a time, after the lanes are done.
+__global__ __launch_bounds__(64 * DG_LL_WAVES) void k_lists_lanes(DgParams p) {
+    extern __shared__ uint32_t s_rows[];    // per wave: 64 rows of (min(max_k, 64) | 1) words
+    const uint32_t t = blockIdx.x;
+    if (dg_failed(p) || dg_tskip(p, t)) return;
+    const uint32_t K = (uint32_t)(p.aln_begin[t + 1] - p.aln_begin[t]);
+    if (K > DG_WAVE) return;                                  // k_lists
+    const uint32_t blen = p.tlen[t];
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t pos0 = (blockIdx.y * DG_LL_WAVES + wave) * DG_WAVE;
+    if (pos0 >= blen + 2) return;
+    const uint32_t nrows = min((uint32_t)DG_WAVE, blen + 2 - pos0);
+    const uint32_t S = K | 1u;
+    uint32_t *rows = s_rows + wave * DG_WAVE * (min(p.max_k, (uint32_t)DG_WAVE) | 1u);
+    uint32_t *row = rows + (uint32_t)lane * S;
     const uint64_t nb = p.node_base[t];
     const uint64_t bv = p.bbv_base[t];
     const uint32_t capb = dg_capb(K);
     const uint32_t fixed0 = 3u * p.t_nins[t];
     uint32_t *pool = p.pool + p.pool_base[t];
-#define DG_LPOOL(OFF) (*reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(pool) + (((uint32_t)(OFF)) << 2)))
-    // lane l: bid[pos0 - 1 + l] for l < LPW + 2 (the wave's vertices and the one on either side), gbase[pos0 + l] for l <= LPW
-    const uint32_t qb = pos0 - 1u + (uint32_t)lane;           // (wraps at pos0 = 0, lane 0: no vertex in front of enter)
-    const uint32_t bidl = (lane < (int)DG_LPW + 2 && qb <= blen + 1) ? p.bid[bv + qb] : 0u;
-    const uint32_t gbl = (lane <= (int)DG_LPW && pos0 + lane <= blen + 1) ? p.gbase[bv + pos0 + lane] : 0u;
-    // cells of read r at position pos: [position][read] (k_emit); every row 0 .. blen + 1 exists
-    const uint32_t rb = (uint32_t)lane << 2;
-    const bool rl = (uint32_t)lane < K;
-    const uint32_t *Ar = p.matA + p.mat_base[t] + (uint64_t)pos0 * K, *Dr = p.matD + p.mat_base[t] + (uint64_t)pos0 * K;
-#define DG_LROW(R) (rl ? *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(R) + rb) : 0u)
-    uint32_t dcell = DG_LROW(Dr), acell = DG_LROW(Ar);
-    // the records' variable words, in the lane of their position (the rest follows from the position);
-    // a list that moved to the growth region overwrites its position's default offset and capacity
-    const uint32_t lpos = pos0 + (uint32_t)lane;
-    uint32_t r_lens = 0;                                       // out_len | in_len << 16
-    uint32_t r_cov = 0;                                        // n_cov | n_match << 8 | last_base << 16
-    uint32_t r_out = fixed0 + lpos * 3u * capb, r_in = r_out + 2u * capb;
-    uint32_t r_caps = capb | capb << 16;
-    uint32_t pi = 0;
-    for (; pi < npos; pi++) {
-        const uint32_t pos = pos0 + pi;
-        const uint32_t dep = dcell, arr = acell;
-        if (pi + 1 < npos) {
-            Ar += K; Dr += K;
-            dcell = DG_LROW(Dr); acell = DG_LROW(Ar);
-        }
-        const bool mine = (uint32_t)lane == pi;
-        const int32_t v1 = __builtin_amdgcn_readlane((int)bidl, pi + 1) + 1;     // this vertex's id + 1
-        uint32_t out_len = 0, in_len = 0;
-        if (pos <= blen) {
-            // out list from the departures: neighbour id + 1 (0 = none) and, above bit 25, the reads k_emit folded into this one's chain
-            const int32_t val = (int32_t)DG_CELL_ID(dep), extra = (int32_t)(dep >> 25);
-            const int32_t chain = __builtin_amdgcn_readlane((int)bidl, pi + 2) + 1;
-            const int32_t ulo = __builtin_amdgcn_readlane((int)gbl, pi + 1) + 1;
-            int32_t cnt;
-            unsigned long long cm;
-            const unsigned long long firsts = dg_list_row(val, extra, chain, ulo, chain, lane, cnt, cm);
-            const uint32_t n = 1u + (uint32_t)__popcll(firsts);
-            uint32_t off = fixed0 + pos * 3u * capb;
-            if (n > capb) {                                     // rare: move to the growth region
-                const uint32_t cap = n + 2u;
-                off = dg_pool_alloc(p, t, 2u * cap, lane);
-                if (off == 0xFFFFFFFFu) break;
-                if (mine) { r_out = off; r_caps = (r_caps & 0xFFFF0000u) | cap; }
+    const uint32_t *Db = p.matD + p.mat_base[t] + (uint64_t)pos0 * K, *Ab = p.matA + p.mat_base[t] + (uint64_t)pos0 * K;
+
+    const uint32_t pos = pos0 + (uint32_t)lane;
+    const bool act = (uint32_t)lane < nrows;                  // pos <= blen + 1
+    const bool do_out = act && pos <= blen, do_in = act && pos >= 1;
+    // ids of this vertex and the one on either side, bases of this and the next insertion group
+    const uint32_t b0 = act ? p.bid[bv + pos] : 0u;
+    const uint32_t bm = do_in ? p.bid[bv + pos - 1] : 0u;
+    const uint32_t bp = do_out ? p.bid[bv + pos + 1] : 0u;
+    const uint32_t g0 = act ? p.gbase[bv + pos] : 0u;
+    const uint32_t g1 = do_out ? p.gbase[bv + pos + 1] : 0u;
+    // the record's variable words; a list that moved to the growth region overwrites its default offset and capacity
+    uint32_t out_len = 0, in_len = 0, r_cov = 0;
+    uint32_t r_out = fixed0 + pos * 3u * capb, r_in = r_out + 2u * capb;
+    uint32_t out_cap = capb, in_cap = capb;
+    bool dead = false;                                        // the pool of the target is full: the host grows it and runs again
+
+    // ---- out lists from the departures ----
+    dg_stage_rows(rows, Db, nrows, K, S, lane);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    DgLaneRow so = {};
+    if (do_out) {
+        so = dg_lane_row<false>(row, K, bp + 1u, g1 + 1u, bp + 1u);
+        if (!so.overflow) {
+            if (so.n > capb) {
+                const uint32_t off = dg_pool_alloc_lane(p, t, 2u * (so.n + 2u));
+                if (off == 0xFFFFFFFFu) dead = true;
+                else { r_out = off; out_cap = so.n + 2u; }
             }
-            const uint32_t idx = 1u + (uint32_t)__popcll(firsts & ((1ull << lane) - 1ull));
-            if (lane == 0) { DG_LPOOL(off) = (uint32_t)(chain - 1); DG_LPOOL(off + 1) = (uint32_t)__popcll(cm); }
-            if ((firsts >> lane) & 1ull) { DG_LPOOL(off + 2 * idx) = (uint32_t)(val - 1); DG_LPOOL(off + 2 * idx + 1) = (uint32_t)cnt; }
-            out_len = n;
+            if (!dead) { pool[r_out] = bp; pool[r_out + 1u] = so.c0; out_len = so.n; }
         }
-        if (pos >= 1) {
-            // in list from the arrivals, and the coverage of the position
-            const uint32_t idf = DG_CELL_ID(arr);
-            if (pos <= blen) {
-                const unsigned long long covered = __ballot(arr != 0u);
-                const uint32_t n_cov = (uint32_t)__popcll(covered);
-                const uint32_t n_match = (uint32_t)__popcll(__ballot(arr != 0u && idf != DG_CELL_DEL));
-                const uint32_t last_base = covered ? DG_CELL_BASE((uint32_t)__builtin_amdgcn_readlane((int)arr, 63 - __clzll((long long)covered))) : 0u;
-                if (mine) r_cov = n_cov | n_match << 8 | last_base << 16;
-            }
-            const int32_t val = (arr != 0u && idf != DG_CELL_DEL && idf != DG_CELL_DUP) ? (int32_t)idf : 0;
-            const int32_t chain = __builtin_amdgcn_readlane((int)bidl, pi) + 1;
-            const int32_t ulo = __builtin_amdgcn_readlane((int)gbl, pi) + 1;
-            int32_t cnt;
-            unsigned long long cm;
-            const unsigned long long firsts = dg_list_row(val, 0, chain, ulo, v1, lane, cnt, cm);
-            const uint32_t n = 1u + (uint32_t)__popcll(firsts);
-            uint32_t off = fixed0 + pos * 3u * capb + 2u * capb;
-            if (n > capb) {
-                const uint32_t cap = n + 2u;
-                off = dg_pool_alloc(p, t, cap, lane);
-                if (off == 0xFFFFFFFFu) break;
-                if (mine) { r_in = off; r_caps = (r_caps & 0xFFFFu) | cap << 16; }
-            }
-            const uint32_t idx = 1u + (uint32_t)__popcll(firsts & ((1ull << lane) - 1ull));
-            if (lane == 0) DG_LPOOL(off) = (uint32_t)(chain - 1);
-            if ((firsts >> lane) & 1ull) DG_LPOOL(off + idx) = (uint32_t)(val - 1);
-            in_len = n;
-        }
-        if (mine) r_lens = out_len | in_len << 16;
     }
-    // the whole record of each backbone vertex the wave finished (AlnGraphBoost.cpp:16-62 + what addAln made of it), lane
-    // by position; a growth-region allocation that failed ends the wave at its position (pi), as it ends the kernel
-    const uint32_t v = __shfl_down(bidl, 1);                   // bid[lpos]
-    if ((uint32_t)lane < pi) {
-        const bool inner = lpos >= 1 && lpos <= blen;
+    for (uint32_t j = 1; __ballot(j < out_len) != 0ull; j++)
+        if (j < out_len) {
+            const uint32_t e = row[j - 1u];
+            pool[r_out + 2u * j] = DG_CELL_ID(e) - 1u;
+            pool[r_out + 2u * j + 1u] = dg_lane_count(so, e);
+        }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+
+    // ---- in lists from the arrivals, and the coverage of the position ----
+    dg_stage_rows(rows, Ab, nrows, K, S, lane);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    DgLaneRow si = {};
+    if (do_in) {
+        si = dg_lane_row<true>(row, K, bm + 1u, g0 + 1u, b0 + 1u);
+        if (pos <= blen) r_cov = si.n_cov | si.n_match << 8 | si.last_base << 16;
+        if (!si.overflow && !dead) {
+            if (si.n > capb) {
+                const uint32_t off = dg_pool_alloc_lane(p, t, si.n + 2u);
+                if (off == 0xFFFFFFFFu) dead = true;
+                else { r_in = off; in_cap = si.n + 2u; }
+            }
+            if (!dead) { pool[r_in] = bm; in_len = si.n; }
+        }
+    }
+    for (uint32_t j = 1; __ballot(j < in_len) != 0ull; j++)
+        if (j < in_len) pool[r_in + j] = DG_CELL_ID(row[j - 1u]) - 1u;
+
+    // ---- the rows that did not fit a lane's table: the reads on the lanes, a position at a time ----
+    const unsigned long long redo_o = __ballot(do_out && so.overflow != 0u), redo_i = __ballot(do_in && si.overflow != 0u);
+    for (unsigned long long rem = redo_o | redo_i; rem; rem &= rem - 1ull) {
+        const int pi = __ffsll((long long)rem) - 1;
+        const bool ro = (redo_o >> pi) & 1ull, ri = (redo_i >> pi) & 1ull;
+        const bool rl = (uint32_t)lane < K;
+        const uint32_t dep = rl && ro ? Db[(uint32_t)pi * K + (uint32_t)lane] : 0u;
+        const uint32_t arr = rl && ri ? Ab[(uint32_t)pi * K + (uint32_t)lane] : 0u;
+        DgPosLists r;
+        const bool ok = dg_lists_pos(p, t, pool, pos0 + (uint32_t)pi, blen, capb, fixed0, lane, ro, ri, dep, arr,
+                                     __builtin_amdgcn_readlane((int)b0, pi) + 1,
+                                     __builtin_amdgcn_readlane((int)bp, pi) + 1, __builtin_amdgcn_readlane((int)g1, pi) + 1,
+                                     __builtin_amdgcn_readlane((int)bm, pi) + 1, __builtin_amdgcn_readlane((int)g0, pi) + 1, r);
+        if (lane == pi) {
+            if (!ok) dead = true;
+            else {
+                if (ro) { out_len = r.o_len; r_out = r.o_off; out_cap = r.o_cap; }
+                if (ri) { in_len = r.i_len; r_in = r.i_off; in_cap = r.i_cap; r_cov = r.cov; }
+            }
+        }
+        if (!ok) break;
+    }
+
+    // the whole record of each backbone vertex (AlnGraphBoost.cpp:16-62 + what addAln made of it), a lane per position
+    if (act && !dead) {
+        const bool inner = pos >= 1 && pos <= blen;
         const uint32_t n_cov = r_cov & 0xFFu, n_match = (r_cov >> 8) & 0xFFu;
         uint32_t base;
-        if (lpos == 0) base = '^';
-        else if (lpos == blen + 1) base = '$';
+        if (pos == 0) base = '^';
+        else if (pos == blen + 1) base = '$';
         else if (n_cov) base = r_cov >> 16;                     // last read to cover the position (:79,:90)
-        else base = p.bb ? p.bb[p.bb_off[t] + (lpos - 1)] : (uint8_t)'N';
-        uint4 *rec = reinterpret_cast<uint4 *>(p.nodes + nb + v);
-        rec[0] = make_uint4(r_lens, base | DG_NF_BACKBONE << 8,
+        else base = p.bb ? p.bb[p.bb_off[t] + (pos - 1)] : (uint8_t)'N';
+        uint4 *rec = reinterpret_cast<uint4 *>(p.nodes + nb + b0);
+        rec[0] = make_uint4(out_len | in_len << 16, base | DG_NF_BACKBONE << 8,
                             inner ? 1u + n_match : 0u,          // weight (:81)
-                            r_lens >> 16);                      // pending = in_len
-        rec[1] = make_uint4(r_out, r_in, r_caps, inner ? lpos : 0u);   // bbpos: _bbMap's absent key (enter, exit) reads as 0
-        p.cov[bv + lpos] = inner ? (int32_t)n_cov : 0;          // :76,:87
+                            in_len);                            // pending = in_len
+        rec[1] = make_uint4(r_out, r_in, out_cap | in_cap << 16, inner ? pos : 0u);   // bbpos: _bbMap's absent key (enter, exit) reads as 0
+        p.cov[bv + pos] = inner ? (int32_t)n_cov : 0;           // :76,:87
     }
-#undef DG_LROW
-#undef DG_LPOOL
 }
 
 __global__ __launch_bounds__(256) void k_lists(DgParams p) {
@@ -1309,11 +1404,9 @@ __global__ __launch_bounds__(256) void k_lists(DgParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t blen = p.tlen[t];
     const uint32_t K = (uint32_t)(p.aln_begin[t + 1] - p.aln_begin[t]);
-    // a wave takes DG_LPW consecutive positions: the set-up is paid once for them.  (The deep path comes first in the
-    // source: in the other order hipcc needs 106 SGPRs for the kernel and the occupancy drops from 8 to 7.)
-    if (K > DG_WAVE) {
-    // ---- more than a wave of reads: a position at a time; the list under construction has entry i on lane i while it
-    // fits a wave, spilled to LDS beyond that ----
+    if (K <= DG_WAVE) return;                                 // k_lists_lanes
+    // more than a wave of reads: a wave takes DG_LPW consecutive positions, one at a time; the list under construction
+    // has entry i on lane i while it fits a wave, spilled to LDS beyond that
     const uint32_t stride = p.max_k + 2;
     volatile int32_t *vals = s_tmp + (size_t)wave * 2 * stride;
     volatile int32_t *cnts = vals + stride;
@@ -1437,8 +1530,4 @@ __global__ __launch_bounds__(256) void k_lists(DgParams p) {
         p.nodes[nb + v] = nd;
     }
     }
-    return;
-    }
-    const uint32_t pos0 = (blockIdx.y * 4 + (uint32_t)__builtin_amdgcn_readfirstlane(wave)) * DG_LPW;   // (uniform)
-    if (pos0 < blen + 2) dg_lists_wave(p, t, pos0, blen, K, lane);
 }

@@ -309,6 +309,58 @@ int dagcon_set_edit_support(dagcon_ctx *ctx, int on);
 int dagcon_fetch_edit_support(dagcon_ctx *ctx, dagcon_edit_support *out);
 
 /*
+ * Pile-up: what the alignments show at every target position, and the positions where a second allele has support (off
+ * by default; a context switch like dagcon_set_record_filter).  This is this build's own rule, PARITY UNPINNED: the
+ * reference has no such output.  DAGCON_FLAG_BASE_SUPPORT gives the weight of the winning vertex and a depth, not the
+ * alternatives; dagcon_edit_support counts only at edits.  It needs neither DAGCON_FLAG_BASE_POS nor the edits, and it
+ * holds for every way in: dagcon_consensus, dagcon_consensus_pre, every record upload, with or without windows.
+ * Everything is relative to a target of the pipeline: a target of the batch, or with windows a window.
+ * 1. The alignments counted are exactly those the graph took: the target's alignments of at least min_len columns,
+ *    after normalizeGaps and trimAln, and non-empty; records that dagcon_set_record_filter leaves out are not among them.
+ *    A target below min_cov has no graph and counts nothing.
+ * 2. Alignment a has columns (q, t), '-' is the gap.  Its first target base after the trim is s0 (0-based).  The
+ *    coordinate tc of a column is s0 plus the columns with t != '-' in front of it.
+ *      t != '-', q == '-'    DEL[tc] += 1
+ *      t != '-', q != '-'    one of A[tc], C[tc], G[tc], T[tc] += 1, by q & 0xDF (letter case does not count); any other
+ *                            byte: N[tc] += 1
+ *      t == '-', q != '-'    an inserted base; it belongs to the target base in front of it, tc - 1.  A run of inserted
+ *                            columns counts its alignment once: INS[tc - 1] += 1 at the run's first column, which is
+ *                            the inserted column whose neighbour in front, in the same alignment, has t != '-'.  Inserted
+ *                            columns in front of the alignment's first target-base column have no such neighbour and
+ *                            count nowhere
+ *      both '-'              nowhere
+ * 3. Layout: eight uint16_t per position, A C G T N DEL INS 0.  depth = A + C + G + T + N + DEL is not stored.
+ *    INS <= depth always: the column in front of a run's first column is a target-base column of the same alignment.
+ *    A count is at most DAGCON_MAX_COVERAGE (4094): 16 bits hold it.  On the device two counters share a 32-bit word
+ *    and an add is one 32-bit atomic add of 1 or 1 << 16; neither half can carry into the other.
+ * 4. A failed target (target_status != DAGCON_OK) has all-zero counts and no sites.
+ * 5. Sites, given min_count and min_frac_ppm: with s2 the second largest of the six counts A C G T N DEL (ties as
+ *    they fall: a 3/3 split has s2 = 3) and m = max(s2, min(INS, depth - INS)), position p is a site iff depth > 0 and
+ *    m >= min_count and m * 1000000 >= min_frac_ppm * depth, in 64-bit integers, no floating point.  With 0 / 0 every
+ *    position with depth is a site.  The sites of a target are listed in ascending position.
+ * dagcon_set_pileup: NULL turns it off; min_frac_ppm > 1000000 is DAGCON_ERR_INVALID_ARG (the switch stays as it was).
+ * The switch and its thresholds are read at the upload (dagcon_upload and every other upload, the dagcon_consensus* calls
+ * among them).  With it off no kernel, buffer, memset, launch or copy differs from a context that never heard of it.
+ * With it on, the counters are cleared and four kernels (csrc/k_pileup.hip.h) run behind the consensus in every
+ * execution of the run, the site list comes back with dagcon_fetch, and the counts, 16 bytes a position, stay on the
+ * device and are copied only when dagcon_fetch_pileup is called.  On a DAGCON_FLAG_RAW_ALIGNMENTS context the column
+ * arena is filled too, with the strings as given: the switch is accepted and the same rule counts on those columns.
+ * dagcon_fetch_pileup / dagcon_fetch_pileup_sites are valid after a dagcon_fetch of an upload made with the switch on;
+ * DAGCON_ERR_STATE otherwise: switch off at the upload, before a fetch, or under DAGCON_FLAG_STOP_AFTER_BUILD / _MERGE.
+ * The arrays are owned by the context, valid as long as the results of the same fetch.
+ */
+typedef struct dagcon_pileup_opts { uint32_t min_count, min_frac_ppm; } dagcon_pileup_opts;
+int dagcon_set_pileup(dagcon_ctx *ctx, const dagcon_pileup_opts *o);   /* NULL: off (the default) */
+typedef struct dagcon_pileup {       /* counts[8 * (pos_begin[t] + p)] .. : A C G T N DEL INS 0 of position p of target t */
+    uint32_t n_targets; const uint64_t *pos_begin; const uint16_t *counts;   /* pos_begin: [n_targets + 1] */
+} dagcon_pileup;
+int dagcon_fetch_pileup(dagcon_ctx *ctx, dagcon_pileup *out);
+typedef struct dagcon_pileup_sites { /* sites of target t: [site_begin[t], site_begin[t + 1]) */
+    uint32_t n_targets; const uint64_t *site_begin; const uint32_t *pos; const uint16_t *counts;   /* counts: eight per site */
+} dagcon_pileup_sites;
+int dagcon_fetch_pileup_sites(dagcon_ctx *ctx, dagcon_pileup_sites *out);
+
+/*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses
  * alignment records straight into such a buffer gets its dagcon_upload at link speed instead of
  * through the driver's staging copies.  Optional: any host memory is accepted by dagcon_upload.

@@ -43,6 +43,7 @@ EXPORTS = [
     "dagcon_set_record_filter", "dagcon_fetch_record_stats",
     "dagcon_set_edits", "dagcon_fetch_edits",
     "dagcon_set_edit_support", "dagcon_fetch_edit_support",
+    "dagcon_set_pileup", "dagcon_fetch_pileup", "dagcon_fetch_pileup_sites",
     "dagcon_upload_cigar_md", "dagcon_consensus_cigar_md", "dagcon_fetch_md_targets",
 ]
 ABI_VERSION = 2
@@ -129,6 +130,23 @@ class EditSupport(C.Structure):
                 ("span", C.POINTER(C.c_uint32)), ("alt", C.POINTER(C.c_uint32)), ("ref", C.POINTER(C.c_uint32))]
 
 
+class PileupOpts(C.Structure):
+    """dagcon_pileup_opts: a position is a site when its second allele has at least min_count alignments and at least
+    min_frac_ppm millionths of the depth (include/dagcon.h has the rule)."""
+    _fields_ = [("min_count", C.c_uint32), ("min_frac_ppm", C.c_uint32)]
+
+
+class Pileup(C.Structure):
+    """dagcon_pileup: eight uint16 per position (A C G T N DEL INS 0), target t's from pos_begin[t]."""
+    _fields_ = [("n_targets", C.c_uint32), ("pos_begin", C.POINTER(C.c_uint64)), ("counts", C.POINTER(C.c_uint16))]
+
+
+class PileupSites(C.Structure):
+    """dagcon_pileup_sites: target t's sites are [site_begin[t], site_begin[t + 1]), eight uint16 per site."""
+    _fields_ = [("n_targets", C.c_uint32), ("site_begin", C.POINTER(C.c_uint64)), ("pos", C.POINTER(C.c_uint32)),
+                ("counts", C.POINTER(C.c_uint16))]
+
+
 class Edits(C.Structure):
     """dagcon_edits: per segment its target span and its edits (include/dagcon.h has the definition)."""
     _fields_ = [("n_segments", C.c_uint64), ("n", C.c_uint64), ("seg_t0", C.POINTER(C.c_uint32)),
@@ -210,6 +228,9 @@ def load() -> C.CDLL:
     L.dagcon_fetch_edits.argtypes = [vp, C.POINTER(Edits)]
     L.dagcon_set_edit_support.argtypes = [vp, C.c_int]
     L.dagcon_fetch_edit_support.argtypes = [vp, C.POINTER(EditSupport)]
+    L.dagcon_set_pileup.argtypes = [vp, C.POINTER(PileupOpts)]
+    L.dagcon_fetch_pileup.argtypes = [vp, C.POINTER(Pileup)]
+    L.dagcon_fetch_pileup_sites.argtypes = [vp, C.POINTER(PileupSites)]
     L.dagcon_upload_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int]
     L.dagcon_consensus_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int,
                                             C.POINTER(Results)]
@@ -830,6 +851,39 @@ class Context:
         n = int(e.n)
         return {k: (np.ctypeslib.as_array(getattr(e, k), shape=(n,)).copy() if n else np.zeros(0, np.uint32))
                 for k in ("w_begin", "w_end", "span", "alt", "ref")}
+
+    def set_pileup(self, min_count=0, min_frac_ppm=0):
+        """dagcon_set_pileup for every later upload, whatever its kind: the device counts per target position what the
+        alignments show there (pileup()) and lists the positions whose second allele has at least min_count alignments
+        and min_frac_ppm millionths of the depth (pileup_sites()).  set_pileup(None): off."""
+        if min_count is None:
+            self._chk(self.L.dagcon_set_pileup(self.h, None))
+            return
+        o = PileupOpts(min_count, min_frac_ppm)
+        self._chk(self.L.dagcon_set_pileup(self.h, C.byref(o)))
+
+    def pileup(self) -> dict:
+        """dagcon_fetch_pileup (copies): pos_begin (uint64, one per target and one more) and counts (uint16,
+        [positions, 8]: A C G T N DEL INS 0; target t's rows are pos_begin[t] .. pos_begin[t + 1])."""
+        pu = Pileup()
+        self._chk(self.L.dagcon_fetch_pileup(self.h, C.byref(pu)))
+        T = int(pu.n_targets)
+        begin = np.ctypeslib.as_array(pu.pos_begin, shape=(T + 1,)).copy()
+        n = int(begin[T])
+        counts = np.ctypeslib.as_array(pu.counts, shape=(n, 8)).copy() if n else np.zeros((0, 8), np.uint16)
+        return {"pos_begin": begin, "counts": counts}
+
+    def pileup_sites(self) -> dict:
+        """dagcon_fetch_pileup_sites (copies): site_begin (uint64, one per target and one more), pos (uint32, per site,
+        relative to its target) and counts (uint16, [sites, 8])."""
+        ps = PileupSites()
+        self._chk(self.L.dagcon_fetch_pileup_sites(self.h, C.byref(ps)))
+        T = int(ps.n_targets)
+        begin = np.ctypeslib.as_array(ps.site_begin, shape=(T + 1,)).copy()
+        n = int(begin[T])
+        return {"site_begin": begin,
+                "pos": np.ctypeslib.as_array(ps.pos, shape=(n,)).copy() if n else np.zeros(0, np.uint32),
+                "counts": np.ctypeslib.as_array(ps.counts, shape=(n, 8)).copy() if n else np.zeros((0, 8), np.uint16)}
 
     def edits(self) -> dict:
         """dagcon_fetch_edits (copies): seg_t0, seg_t1 (uint32, one per segment of the last results, in their order),

@@ -68,6 +68,7 @@ struct InBufs {
     DevBuf q, t, aln_off, aln_len, aln_start, aln_tgt, tlen, aln_begin, tactive, bb, bb_off, mat_base, bbv_base, matc_base, matc_stride;
     DevBuf norm_off, ch_aln, ch_base, ck_base;
     DevBuf ed_tbase;                                // dagcon_set_edits: where each target's bases begin in cg.t
+    DevBuf pile_begin;                              // dagcon_set_pileup: where each target's positions begin in run.pile
 };
 // RunBufs: what the kernels of a run fill and nobody clears.  all() is the set DAGCON_POISON & 8 fills with 0xEE bytes
 // before every run (launch_all): a new member goes into it, and the static_assert below says so
@@ -85,14 +86,15 @@ struct RunBufs {
     DevBuf pos_tmp, pos_tmp0, pos;                  // DAGCON_FLAG_BASE_POS: walk scratch (4 B per vertex), output (4 B per base)
     DevBuf ed_seg, ed_out;                          // dagcon_set_edits: a DgEdSeg per segment, a DgEdit per edit
     DevBuf evid;                                    // dagcon_set_edit_support: a DgEvid per edit
-    std::array<DevBuf *, 59> all() {
+    DevBuf pile, pile_tile, pile_site;              // dagcon_set_pileup: 16 B per position (cleared before every run), 8 B per tile, a DgSite per site
+    std::array<DevBuf *, 62> all() {
         return {&nmis, &n_lo, &n_hi, &n_start, &n_ins, &n_del, &ch_k0, &ch_next, &ch_w, &ch_tb, &ch_flag, &ch_src, &ch_out, &ch_adv, &n_lb, &norm_tmp, &ckpt,
                 &node_base, &n_nodes, &pool_base, &pool_size, &pool_top, &t_nins, &cov, &gcount, &gbase, &bid, &best, &queue, &score, &cns_tmp, &bp_tt,
                 &stk, &cuts, &cuts_bp, &bp_stat, &bp_len, &rd, &pro_state, &sh_cnt, &wl_first, &queue0, &bp_end, &bp_ab, &defer, &cns_tmp0, &cns,
-                &seg, &worklist, &seg_done, &sup_tmp, &sup_tmp0, &sup, &pos_tmp, &pos_tmp0, &pos, &ed_seg, &ed_out, &evid};
+                &seg, &worklist, &seg_done, &sup_tmp, &sup_tmp0, &sup, &pos_tmp, &pos_tmp0, &pos, &ed_seg, &ed_out, &evid, &pile, &pile_tile, &pile_site};
     }
 };
-static_assert(sizeof(RunBufs) == 59 * sizeof(DevBuf), "RunBufs::all() must name every member");
+static_assert(sizeof(RunBufs) == 62 * sizeof(DevBuf), "RunBufs::all() must name every member");
 // ArenaBufs: the arenas with a treatment of their own -- matC is cleared before every run, the others are filled under
 // DAGCON_POISON bits 1 (matA, matD), 2 (nodes, pool) and 4 (score_b, norm)
 struct ArenaBufs {
@@ -107,6 +109,7 @@ struct StatBlock {
     PinBuf host;
     size_t o_tfail = 0, o_cns_len = 0, o_n_seg = 0, o_cns_off = 0, o_seg_first = 0;     // (DgStatus at 0)
     size_t o_ed_top = 0;                            // edits of the batch, behind seg_first (a batch with edits on only; 0: none)
+    size_t o_site_top = 0;                          // sites of the batch, behind that (a batch with the pile-up on only; 0: none)
     size_t zero_bytes = 0, bytes = 0;
     template <typename X> X *d(size_t off) const { return reinterpret_cast<X *>(static_cast<char *>(dev.p) + off); }
     template <typename X> const X *h(size_t off) const { return reinterpret_cast<const X *>(host.as<char>() + off); }
@@ -173,6 +176,12 @@ struct Ctx {
     // dagcon_set_edit_support: the switch (on only while edits_on is); whether the batch on the device was armed under it
     bool evid_on = false, evid_batch = false;
     std::vector<uint64_t> h_ed_tbase;
+    // dagcon_set_pileup: the switch and its thresholds; whether the batch on the device was uploaded under it (its buffers:
+    // in.pile_begin, run.pile, run.pile_tile, run.pile_site), and the thresholds of that upload
+    bool pile_on = false, pile_batch = false;
+    dagcon_pileup_opts pile_opts = {0u, 0u}, pile_batch_opts = {0u, 0u};
+    std::vector<uint64_t> h_pile_begin;             // [T + 1]
+    uint64_t site_cap = 0;
     uint64_t ed_cap = 0;
     long ed_cap_env = 0;                            // DAGCON_EDITS_CAP (tests): first size of the edit arena, so that the re-run is met
 
@@ -205,6 +214,13 @@ struct Ctx {
     std::vector<uint64_t> e_begin, e_coff;
     bool evid_valid = false;              // the arrays below are those of the last fetch (dagcon_fetch_edit_support)
     std::vector<uint32_t> v_begin, v_end, v_span, v_alt, v_ref;
+    bool pile_valid = false;            // the site arrays below are those of the last fetch (dagcon_fetch_pileup_sites)
+    bool pile_fetched = false;          // r_pile holds the counts of the same run (dagcon_fetch_pileup copies them when asked)
+    PinBuf r_site;                      // the DgSite records of the last fetch
+    PinBuf r_pile;                      // uint16_t, eight per position
+    std::vector<uint64_t> s_begin;
+    std::vector<uint32_t> s_pos;
+    std::vector<uint16_t> s_counts;
     bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
 
     // debug dump storage

@@ -48,6 +48,7 @@ Ctx *intake_reset(dagcon_ctx *ctx) {
     c->sup_valid = c->pos_valid = false;
     c->ed_batch = c->ed_valid = c->pos_pending = false;
     c->evid_batch = c->evid_valid = false;
+    c->pile_batch = c->pile_valid = c->pile_fetched = false;
     c->md_valid = c->md_fetched = false;
     return c;
 }

@@ -73,6 +73,8 @@ int ensure_stat(Ctx *c, uint32_t T) {
     b.bytes = b.o_seg_first + up16((size_t)T * 8);
     b.o_ed_top = 0;
     if (c->ed_batch) { b.o_ed_top = b.bytes; b.bytes += 16; }
+    b.o_site_top = 0;
+    if (c->pile_batch) { b.o_site_top = b.bytes; b.bytes += 16; }
     ENSURE(c, b.dev, b.bytes);
     return b.host.reserve(c, b.bytes);
 }
@@ -120,6 +122,12 @@ int ensure_arenas(Ctx *c) {
         ENSURE(c, c->run.ed_seg, c->seg_cap * sizeof(DgEdSeg));
         ENSURE(c, c->run.ed_out, c->ed_cap * sizeof(DgEdit));
         if (c->evid_batch) ENSURE(c, c->run.evid, c->ed_cap * sizeof(DgEvid));
+    }
+    if (c->pile_batch) {
+        const uint64_t pn = c->h_pile_begin.back();
+        ENSURE(c, c->run.pile, pn * 16);
+        ENSURE(c, c->run.pile_tile, (pn + DG_PILE_TILE - 1) / DG_PILE_TILE * 8);
+        ENSURE(c, c->run.pile_site, c->site_cap * sizeof(DgSite));
     }
     ENSURE(c, c->run.seg, 2 * seg_stride(c) * 4);
     if (int r = c->r_seg.reserve(c, 2 * (size_t)c->seg_cap * 4)) return r;
@@ -206,6 +214,13 @@ void fill_params(Ctx *c, DgParams &p) {
         p.ed_top = c->sb.d<unsigned long long>(c->sb.o_ed_top);
         p.ed_t = c->cg.t.as<const uint8_t>(); p.ed_tbase = c->in.ed_tbase.as<const uint64_t>();
         if (c->evid_batch) p.evid = c->run.evid.as<DgEvid>();
+    }
+    if (c->pile_batch) {
+        p.pile = c->run.pile.as<uint32_t>(); p.pile_begin = c->in.pile_begin.as<const uint64_t>(); p.pile_n = c->h_pile_begin.back();
+        p.pile_tile = c->run.pile_tile.as<unsigned long long>();
+        p.pile_site = c->run.pile_site.as<DgSite>(); p.site_cap = c->site_cap;
+        p.site_top = c->sb.d<unsigned long long>(c->sb.o_site_top);
+        p.pile_min_count = c->pile_batch_opts.min_count; p.pile_min_ppm = c->pile_batch_opts.min_frac_ppm;
     }
 }
 
@@ -349,6 +364,16 @@ int launch_all(Ctx *c) {
                 hipLaunchKernelGGL(k_ev_spread, eg, dim3(256), 0, s, p);
             }
         }
+        if (c->pile_batch && p.pile_n) {
+            // the pile-up (k_pileup.hip.h): the counters start from zero in every execution, a re-run included; a wave per
+            // alignment; then the sites: mark and count per tile, one scan, write
+            HIPCHK(c, hipMemsetAsync(c->run.pile.p, 0, p.pile_n * 16, s));
+            if (c->A > 0) hipLaunchKernelGGL(k_pile_count, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
+            const dim3 tg((uint32_t)((p.pile_n + DG_PILE_TILE - 1) / DG_PILE_TILE));
+            hipLaunchKernelGGL(k_pile_sites<false>, tg, dim3(DG_PILE_TILE), 0, s, p);
+            hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(1024), 0, s, p);
+            hipLaunchKernelGGL(k_pile_sites<true>, tg, dim3(DG_PILE_TILE), 0, s, p);
+        }
     }
     HIPCHK(c, hipEventRecord(c->ev[4], s));
     HIPCHK(c, hipGetLastError());
@@ -424,6 +449,8 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->sup_valid = c->pos_valid = false;
     c->ed_batch = c->ed_valid = c->pos_pending = false;     // (a record upload with edits on says so after the hand-over)
     c->evid_batch = c->evid_valid = false;
+    c->pile_batch = c->pile_on; c->pile_batch_opts = c->pile_opts;
+    c->pile_valid = c->pile_fetched = false;
     c->h_cig_bad.clear();
     c->rs_valid = false;
     c->md_valid = c->md_fetched = false;
@@ -579,6 +606,14 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     UPLOAD(c, c->in.ch_aln, c->h_ch_aln);
     UPLOAD(c, c->in.ck_base, c->h_ck_base);
     UPLOAD(c, c->in.norm_off, c->h_norm_off);
+    if (c->pile_batch) {
+        // a target's positions [pile_begin[t], + tlen): every target has them, the ones no graph is built for too (all zero)
+        c->h_pile_begin.assign((size_t)T + 1, 0);
+        for (uint32_t t = 0; t < T; t++) c->h_pile_begin[t + 1] = c->h_pile_begin[t] + b->tlen[t];
+        UPLOAD(c, c->in.pile_begin, c->h_pile_begin);
+        // first guess, as for the edits; a run with more sites records their number and is repeated (DG_E_SITE_OVF)
+        c->site_cap = std::max<uint64_t>(c->site_cap, c->h_pile_begin[T] / 8 + 1024);
+    }
     ENSURE(c, c->run.ckpt, c->n_ckpt * 4);
 
     // work arrays whose size the host knows
@@ -627,6 +662,7 @@ int dagcon_run(dagcon_ctx *ctx) {
     c->ran = true; c->fetched = false;
     c->ed_valid = c->pos_pending = false;
     c->evid_valid = false;
+    c->pile_valid = c->pile_fetched = false;
     if (const char *e = getenv("DAGCON_DUMP")) return dump_target(c, e);
     return DAGCON_OK;
 }
@@ -688,6 +724,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         if (f & DG_E_LOG_OVF) c->sh_log *= 2;
         if (f & DG_E_RUN_WIDE) c->wide_cells = true;       // (until the next upload)
         if ((f & DG_E_ED_OVF) && sb.o_ed_top) c->ed_cap = *sb.h<uint64_t>(sb.o_ed_top) + 1024;
+        if ((f & DG_E_SITE_OVF) && sb.o_site_top) c->site_cap = *sb.h<uint64_t>(sb.o_site_top) + 1024;
         if (f & DG_E_OUT_OVF) {
             c->cns_cap = std::max<uint64_t>(c->cns_cap, c->h_st.cns_top + 1024);
             c->seg_cap = std::max<uint64_t>(c->seg_cap, c->h_st.seg_top + 1024);
@@ -737,7 +774,13 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     c->sup_valid = c->pos_valid = false;
     c->ed_valid = c->pos_pending = false;
     c->evid_valid = false;
+    c->pile_valid = c->pile_fetched = false;
     c->r_nb = nb;
+    // the pile-up's sites come back here; its counts, 16 bytes a position, stay on the device until dagcon_fetch_pileup
+    const bool want_pile = full && c->pile_batch;
+    const uint64_t n_site = want_pile && T && c->h_pile_begin.back() ? *sb.h<uint64_t>(sb.o_site_top) : 0;
+    if (n_site > c->site_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu sites in an arena of %llu", (unsigned long long)n_site, (unsigned long long)c->site_cap);
+    if (want_pile && (r = c->r_site.reserve(c, (size_t)n_site * sizeof(DgSite) + 1))) return r;
     const bool want_evid = want_ed && c->evid_batch;
     const size_t ed_seg_bytes = (size_t)nseg * sizeof(DgEdSeg), ed_bytes = ed_seg_bytes + (size_t)n_ed * sizeof(DgEdit);
     const size_t evid_bytes = want_evid ? (size_t)n_ed * sizeof(DgEvid) : 0;        // (behind the edit records; both 8-byte aligned)
@@ -769,6 +812,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         if (evid_bytes) HIPCHK(c, hipMemcpyAsync(m_edb + ed_bytes, c->run.evid.p, evid_bytes, hipMemcpyDeviceToHost, c->stream));
         queued = true;
     }
+    if (n_site) { HIPCHK(c, hipMemcpyAsync(c->r_site.p, c->run.pile_site.p, (size_t)n_site * sizeof(DgSite), hipMemcpyDeviceToHost, c->stream)); queued = true; }
     if (queued) HIPCHK(c, hipStreamSynchronize(c->stream));
     if (want_sup) { c->r_sup_n = nb; c->sup_valid = true; }
     if (want_pos && !lazy_pos) c->pos_valid = true;
@@ -815,6 +859,26 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     }
     if (want_ed) { c->e_begin.push_back(c->e_tpos.size()); c->ed_valid = true; }
     c->evid_valid = want_evid;
+    if (want_pile) {
+        // the device lists the sites in the order of the positions: a target's are one stretch, the targets ascend.  A
+        // target the host reports as failed has none (one that failed on the device has none there either)
+        const DgSite *m_site = c->r_site.as<const DgSite>();
+        c->s_begin.assign((size_t)T + 1, 0); c->s_pos.clear(); c->s_counts.clear();
+        uint64_t k = 0;
+        for (uint32_t t = 0; t < T; t++) {
+            c->s_begin[t] = c->s_pos.size();
+            for (; k < n_site && m_site[k].tgt == t; k++) {
+                const DgSite &x = m_site[k];
+                if (x.pos >= c->h_tlen[t]) return fail(c, DAGCON_ERR_INTERNAL, "k_pile_sites: site %llu of target %u at position %u of %u", (unsigned long long)k, t, x.pos, c->h_tlen[t]);
+                if (c->r_status[t] != DAGCON_OK) continue;
+                c->s_pos.push_back(x.pos);
+                for (int j = 0; j < 4; j++) { c->s_counts.push_back((uint16_t)(x.w[j] & 0xFFFFu)); c->s_counts.push_back((uint16_t)(x.w[j] >> 16)); }
+            }
+        }
+        if (k != n_site) return fail(c, DAGCON_ERR_INTERNAL, "k_pile_sites: site %llu of %llu is out of order (target %u)", (unsigned long long)k, (unsigned long long)n_site, m_site[k].tgt);
+        c->s_begin[T] = c->s_pos.size();
+        c->pile_valid = true;
+    }
     c->r_seg_begin[T] = c->r_range0.size();
     c->tm.consensus_bases = bases;
     c->tm.algorithmic_bytes = 2ull * c->sum_len + bases;
@@ -893,6 +957,48 @@ int dagcon_fetch_edit_support(dagcon_ctx *ctx, dagcon_edit_support *out) {
     out->n = c->v_begin.size();
     out->w_begin = c->v_begin.data(); out->w_end = c->v_end.data();
     out->span = c->v_span.data(); out->alt = c->v_alt.data(); out->ref = c->v_ref.data();
+    return DAGCON_OK;
+}
+
+int dagcon_set_pileup(dagcon_ctx *ctx, const dagcon_pileup_opts *o) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!o) { c->pile_on = false; return DAGCON_OK; }
+    if (o->min_frac_ppm > 1000000u) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_pileup: min_frac_ppm %u is more than 1000000", o->min_frac_ppm);
+    c->pile_opts = *o;
+    c->pile_on = true;
+    return DAGCON_OK;
+}
+
+static const char *const k_pile_state = "without the results of an upload made with dagcon_set_pileup on (switch off at the upload, no fetch "
+                                        "yet, or stopped before bestPath)";
+
+int dagcon_fetch_pileup_sites(dagcon_ctx *ctx, dagcon_pileup_sites *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->pile_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_pileup_sites %s", k_pile_state);
+    out->n_targets = c->T;
+    out->site_begin = c->s_begin.data(); out->pos = c->s_pos.data(); out->counts = c->s_counts.data();
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_pileup(dagcon_ctx *ctx, dagcon_pileup *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->pile_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_pileup %s", k_pile_state);
+    if (!c->pile_fetched) {
+        // the copy dagcon_fetch left out: 16 bytes a position, only when asked for
+        HIPCHK(c, hipSetDevice(c->device));
+        const uint64_t pn = c->h_pile_begin.back();
+        if (int r = c->r_pile.reserve(c, (size_t)pn * 16 + 16)) return r;
+        if (pn) HIPCHK(c, d2h(c, c->r_pile.p, c->run.pile.p, (size_t)pn * 16));
+        // a failed target: all zero, whatever was counted before it failed
+        for (uint32_t t = 0; t < c->T; t++)
+            if (c->r_status[t] != DAGCON_OK) memset(c->r_pile.as<char>() + 16 * c->h_pile_begin[t], 0, (size_t)16 * c->h_tlen[t]);
+        c->pile_fetched = true;
+    }
+    out->n_targets = c->T;
+    out->pos_begin = c->h_pile_begin.data(); out->counts = c->r_pile.as<uint16_t>();
     return DAGCON_OK;
 }
 

@@ -39,6 +39,7 @@
 #define DG_E_LIST_OVF    0x400u  // more segments handed to k_merge_list than its worklist holds (rerun with a longer one)
 #define DG_E_RUN_WIDE    0x1000u // an insertion run longer than 255 columns met byte-wide matC cells (rerun with 32-bit cells)
 #define DG_E_ED_OVF      0x2000u // edit arena too small (dagcon_set_edits; rerun with *DgParams::ed_top)
+#define DG_E_SITE_OVF    0x4000u // site arena too small (dagcon_set_pileup; rerun with *DgParams::site_top)
 
 // failures of one target (its input, or an invariant of its graph): recorded in DgParams::tfail,
 // the batch goes on; everything else is a capacity problem of the whole batch (grow and re-run)
@@ -229,6 +230,15 @@ struct DgParams {
     const uint64_t *ed_tbase;      // [T] where a target's (a window's) first base lies in it
     // ---- read support per edit (dagcon_set_edit_support; NULL otherwise): k_evidence.hip.h ----
     struct DgEvid *evid;           // [ed_cap] parallel to ed_out
+    // ---- per-position allele counts (dagcon_set_pileup; NULL / 0 otherwise): k_pileup.hip.h ----
+    uint32_t *pile;                // [4 * pile_n] a position's words: A | C << 16, G | T << 16, N | DEL << 16, INS
+    const uint64_t *pile_begin;    // [T + 1] where a target's (a window's) first position lies in it
+    uint64_t pile_n;               // positions of the batch
+    unsigned long long *pile_tile; // [tiles of DG_PILE_TILE positions] sites of the tile, then (k_pile_scan) the sites in front of it
+    struct DgSite *pile_site;      // [site_cap] the sites, in the order of the positions
+    uint64_t site_cap;
+    unsigned long long *site_top;  // sites of the batch (k_pile_scan; in the status block)
+    uint32_t pile_min_count, pile_min_ppm;     // dagcon_pileup_opts
 };
 #define DG_POS_BB 0x80000000u
 
@@ -251,6 +261,12 @@ struct DgEvid {
     uint32_t alt_len;              // bytes of the alt allele
     uint32_t back;                 // edits back to the group's first edit (0: this is it, and the counts are added here)
     uint32_t span, alt, ref, pad;
+};
+
+// one per site: its position in its target and the position's four words (k_pileup.hip.h)
+struct DgSite {
+    uint32_t pos, tgt;
+    uint32_t w[4];
 };
 
 // slots a backbone vertex gets for each of its two lists before it has to move to the

@@ -50,6 +50,7 @@
 #include "sam.h"
 #include "windows.h"
 #include "vcf.h"
+#include "pileup.h"
 
 namespace {
 
@@ -67,6 +68,7 @@ struct Opts {
     std::string edits;                 // --edits FILE (MODE_RECORDS): where every record differs from its target
     std::string vcf;                   // --vcf FILE (MODE_RECORDS, whole targets): the edits as VCF with the reads behind each
     bool want_edits() const { return !edits.empty() || !vcf.empty(); }
+    DgPileOpts pile;                   // --pileup FILE, --sites FILE [--site-min-frac F] [--site-min-count N] (every mode): what the alignments show per position
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
     int pinned = -1;                   // --pinned 0|1: page-locked blobs (-1: when the input is several batches long)
@@ -81,7 +83,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -172,6 +174,17 @@ void usage(FILE *f) {
             "                      change could be written in a repeat).  A pure insertion or deletion is anchored on the base in\n"
             "                      front of it (at position 1: behind it).  Counted on the GPU from the alignments as the graph\n"
             "                      took them; stdout and --edits do not change.  This build's own rule, parity unpinned\n"
+            "  --pileup FILE       every kind of input, with or without --window (not with --polish): FILE lists, for every target\n"
+            "                      position that an alignment covers, what the alignments the graph was built from show there,\n"
+            "                      one line per position in output order: RNAME POS REF DEPTH A C G T N DEL INS, tab-separated.\n"
+            "                      POS is 1-based; REF is the target's base with --sam, --bam and --paf and '.' otherwise;\n"
+            "                      DEPTH = A + C + G + T + N + DEL; INS counts the alignments with inserted bases behind the\n"
+            "                      position.  With --window a position's line comes from the window whose core holds it.\n"
+            "                      Counted on the GPU; stdout does not change.  This build's own rule, parity unpinned\n"
+            "  --sites FILE        the same lines, only for the positions where a second allele has support: with m the\n"
+            "                      second largest of A C G T N DEL, or min(INS, DEPTH - INS) if that is more, a position is\n"
+            "                      listed when m >= N and m >= F x DEPTH.  --site-min-frac F (default 0.2, at most six decimal\n"
+            "                      places) and --site-min-count N (default 2) are this build's own choice.  Goes with --pileup\n"
             "  --fastq             write FASTQ (@id/r0_r1, sequence, +, qualities) instead of FASTA; the same records in the\n"
             "                      same order.  The quality of a base is this build's own definition: a Laplace-smoothed\n"
             "                      fraction of the reads at its position that do not pass through its consensus vertex,\n"
@@ -232,6 +245,19 @@ int parse_args(int argc, char **argv, Opts &o) {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --vcf needs a file name\n"); return 2; }
             o.vcf = argv[++i];
         }
+        else if (a == "--pileup") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --pileup needs a file name\n"); return 2; }
+            o.pile.pileup = argv[++i];
+        }
+        else if (a == "--sites") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --sites needs a file name\n"); return 2; }
+            o.pile.sites = argv[++i];
+        }
+        else if (a == "--site-min-frac") {
+            if (i + 1 >= argc || !dg_parse_ppm(argv[i + 1], &o.pile.min_frac_ppm)) { fprintf(stderr, "PARSE ERROR: --site-min-frac takes a fraction in [0, 1] with at most six decimal places\n"); return 2; }
+            i++; o.pile.frac_set = true;
+        }
+        else if (a == "--site-min-count") { if (!need(&o.pile.min_count)) return 2; o.pile.count_set = true; }
         else if (a == "--window") { if (!need(&o.window) || !o.window) { fprintf(stderr, "PARSE ERROR: --window takes a positive number of bases\n"); return 2; } }
         else if (a == "--max-error") {
             if (i + 1 >= argc || !dg_parse_ppm(argv[i + 1], &o.pick.max_error_ppm)) { fprintf(stderr, "PARSE ERROR: --max-error takes a fraction in [0, 1] with at most six decimal places\n"); return 2; }
@@ -300,6 +326,9 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (!o.vcf.empty() && !records) { fprintf(stderr, "PARSE ERROR: --vcf needs --sam, --bam or --paf\n"); return 2; }
     if (!o.vcf.empty() && o.dump) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --dump-parsed (nothing is run, the file would not be written)\n"); return 2; }
     if (!o.vcf.empty() && o.window) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --window (the stitch splits and fuses edits: a fused edit has no single count)\n"); return 2; }
+    if ((o.pile.frac_set || o.pile.count_set) && o.pile.sites.empty()) { fprintf(stderr, "PARSE ERROR: --site-min-frac and --site-min-count need --sites\n"); return 2; }
+    if (o.pile.on() && o.polish) { fprintf(stderr, "PARSE ERROR: --pileup and --sites do not go with --polish (the backbone changes under the positions)\n"); return 2; }
+    if (o.pile.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --pileup and --sites do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
     if (o.window && (uint64_t)o.overlap < (uint64_t)o.trim + 64) { fprintf(stderr, "PARSE ERROR: --overlap must be at least --trim + 64 (%u)\n", o.trim + 64); return 2; }
     if (o.input.empty()) { fprintf(stderr, "PARSE ERROR: required argument missing: input\n"); usage(stderr); return 2; }
@@ -387,7 +416,8 @@ struct Batch {
     std::string edits;                 // --edits: the batch's lines of that file
     unsigned long long n_edits = 0;
     std::string vcf, contigs;          // --vcf: the batch's lines of that file, and its targets' ##contig lines
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); }
+    std::string pileup, sites;         // --pileup, --sites: the batch's lines of those files
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); }
 };
 
 FILE *g_edits = nullptr;                                  // --edits FILE, written batch by batch in output order
@@ -397,6 +427,8 @@ unsigned long long g_n_edits = 0;
 FILE *g_vcf = nullptr, *g_vcf_lines = nullptr;
 std::string g_vcf_contigs;
 bool g_vcf_bad = false;
+FILE *g_pileup = nullptr, *g_sites = nullptr;              // --pileup FILE, --sites FILE, written batch by batch in output order
+bool g_pile_bad = false;
 unsigned long long g_over_error = 0, g_over_depth = 0;     // records --max-error / --max-depth left out, all batches (under g_tmu)
 bool g_timing = false;                                    // PBDAGCON_TIMING=1: where the wall time of the run went, on stderr (seconds)
 std::mutex g_tmu;
@@ -422,6 +454,12 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
     dagcon_edit_support es;
     memset(&es, 0, sizeof es);
     if (!o.vcf.empty() && !ok(ctx, dagcon_fetch_edit_support(ctx, &es), "edit support")) return 1;
+    dagcon_pileup pu;
+    memset(&pu, 0, sizeof pu);
+    if (!o.pile.pileup.empty() && !ok(ctx, dagcon_fetch_pileup(ctx, &pu), "pile-up")) return 1;
+    dagcon_pileup_sites ps;
+    memset(&ps, 0, sizeof ps);
+    if (!o.pile.sites.empty() && !ok(ctx, dagcon_fetch_pileup_sites(ctx, &ps), "pile-up sites")) return 1;
     const char *nonconforming = o.mode == MODE_RECORDS ? dg_kind(o.kind).nonconforming : "an alignment leaves the backbone or holds a non-printable byte";
     for (uint32_t g = 0; g < r.n_targets; g++) {
         if (o.verbose)
@@ -430,6 +468,12 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
         // a failure is confined to its target (the reference's assert hits one worker's one target,
         // AlnGraphBoost.cpp:71-72): warn, go on with the rest
         if (!o.vcf.empty()) dg_vcf_contig(b.contigs, b.ids[g], b.tlen[g]);
+        if (o.pile.on()) {
+            // REF: the record inputs carry the target's bases (--md: as the device rebuilt them, run_records)
+            const char *tb = o.mode == MODE_RECORDS ? b.t.data() + b.toff[g] : nullptr;
+            if (!o.pile.pileup.empty()) dg_pileup_lines(b.pileup, b.ids[g], pu, g, 0, b.tlen[g], 0, tb);
+            if (!o.pile.sites.empty()) dg_site_lines(b.sites, b.ids[g], ps, g, 0, b.tlen[g], 0, tb);
+        }
         if (r.target_status[g] != DAGCON_OK)
             fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(), dg_status_text(r.target_status[g], nonconforming));
         for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++) {
@@ -511,7 +555,7 @@ int run_records(dagcon_ctx *ctx, Batch &b, const Opts &o) {
     const int rc = dg_consensus_records(ctx, o.kind, ra, nullptr, &r);
     if (g_timing) fprintf(stderr, "pbdagcon timing: %s%s batch of %zu records: %s %.3f\n", dg_kind(o.kind).flag, o.pick.text().c_str(), b.start.size(), dg_kind(o.kind).entry, wall() - t0);
     if (!ok(ctx, rc, "consensus")) return 1;
-    if (dg_kind_md(o.kind) && o.want_edits()) {           // REF of the edits: the targets as the device rebuilt them, in b.t's layout
+    if (dg_kind_md(o.kind) && (o.want_edits() || o.pile.on())) {           // REF of the edits and of the pile-up lines: the targets as the device rebuilt them, in b.t's layout
         const char *tb = nullptr;
         uint64_t tn = 0;
         if (!ok(ctx, dagcon_fetch_md_targets(ctx, &tb, &tn), "rebuilt targets")) return 1;
@@ -724,6 +768,10 @@ struct Workers {
             fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx));
             dagcon_destroy(ctx); ctx = nullptr;
         }
+        if (rc == DAGCON_OK && o.pile.on()) {
+            const dagcon_pileup_opts po = {o.pile.min_count, o.pile.min_frac_ppm};
+            if ((rc = dagcon_set_pileup(ctx, &po)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
+        }
         dagcon_ctx *actx = ctx;                             // --local --polish: the first alignment on a local context of its own
         if (rc == DAGCON_OK && o.local && o.polish) {       // (aligns only: the support comes from ctx's last round)
             rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], DAGCON_FLAG_LOCAL_ALIGN, nullptr, &actx);
@@ -762,6 +810,8 @@ struct Workers {
                     { const double tp0 = wall(); fwrite(d->out.data(), 1, d->out.size(), stdout); t_print += wall() - tp0; }
                     if (g_edits) { fwrite(d->edits.data(), 1, d->edits.size(), g_edits); g_n_edits += d->n_edits; }
                     if (g_vcf) { g_vcf_contigs += d->contigs; if (fwrite(d->vcf.data(), 1, d->vcf.size(), g_vcf_lines) != d->vcf.size()) g_vcf_bad = true; }
+                    if (g_pileup && fwrite(d->pileup.data(), 1, d->pileup.size(), g_pileup) != d->pileup.size()) g_pile_bad = true;
+                    if (g_sites && fwrite(d->sites.data(), 1, d->sites.size(), g_sites) != d->sites.size()) g_pile_bad = true;
                     d->clear();
                     free_list.push_back(d);
                     print_seq++;
@@ -1254,16 +1304,30 @@ int main(int argc, char **argv) {
         first = bam.at;
     }
 
+    // ---- --pileup / --sites: both files are opened before anything runs ----
+    if (!o.pile.pileup.empty() && !(g_pileup = fopen(o.pile.pileup.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.pile.pileup.c_str()); return 1; }
+    if (!o.pile.sites.empty() && !(g_sites = fopen(o.pile.sites.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.pile.sites.c_str()); return 1; }
+    auto close_pile = [&](int status) {
+        for (FILE **f : {&g_pileup, &g_sites}) {
+            if (!*f) continue;
+            const bool bad = fclose(*f) != 0 || g_pile_bad;
+            if (bad) { fprintf(stderr, "pbdagcon: error writing %s\n", (f == &g_pileup ? o.pile.pileup : o.pile.sites).c_str()); status = 1; }
+            *f = nullptr;
+        }
+        return status;
+    };
+
     // ---- --window: the window driver takes the records from here (windows.h) ----
     if (o.window && !o.dump) {
-        DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0], o.pick, o.edits.empty() ? nullptr : o.edits.c_str()};
-        if (o.kind == DG_REC_PACKED) { DgBamSource src(bam, ref); return dg_run_windows(wo, src, ref); }
-        if (o.kind == DG_REC_PACKED_MD) { DgBamMdSource src(bam, ref); return dg_run_windows(wo, src, ref); }
-        if (o.kind == DG_REC_PLAIN_MD) { DgSamMdSource src(in.data, in.size, ref); return dg_run_windows(wo, src, ref); }
-        if (o.kind == DG_REC_CS) { DgPafCsSource src(paf); return dg_run_windows(wo, src, ref); }
-        if (o.kind == DG_REC_STRANDED) { DgPafSource src(paf); return dg_run_windows(wo, src, ref); }
+        DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0], o.pick, o.edits.empty() ? nullptr : o.edits.c_str(),
+                     g_pileup, g_sites, o.pile.min_count, o.pile.min_frac_ppm};
+        if (o.kind == DG_REC_PACKED) { DgBamSource src(bam, ref); return close_pile(dg_run_windows(wo, src, ref)); }
+        if (o.kind == DG_REC_PACKED_MD) { DgBamMdSource src(bam, ref); return close_pile(dg_run_windows(wo, src, ref)); }
+        if (o.kind == DG_REC_PLAIN_MD) { DgSamMdSource src(in.data, in.size, ref); return close_pile(dg_run_windows(wo, src, ref)); }
+        if (o.kind == DG_REC_CS) { DgPafCsSource src(paf); return close_pile(dg_run_windows(wo, src, ref)); }
+        if (o.kind == DG_REC_STRANDED) { DgPafSource src(paf); return close_pile(dg_run_windows(wo, src, ref)); }
         DgSamSource src(in.data, in.size, ref);
-        return dg_run_windows(wo, src, ref);
+        return close_pile(dg_run_windows(wo, src, ref));
     }
 
     // ---- whole targets: the workers start (context creation hides behind the parsing of the first batch), the input
@@ -1291,6 +1355,10 @@ int main(int argc, char **argv) {
     if (g_edits) {
         if (fclose(g_edits) != 0) { fprintf(stderr, "pbdagcon: error writing %s\n", o.edits.c_str()); status = 1; fast_exit = false; }
         if (o.verbose) fprintf(stderr, "pbdagcon: %llu edits written to %s\n", g_n_edits, o.edits.c_str());
+    }
+    if (g_pileup || g_sites) {
+        const int ps = close_pile(0);
+        if (ps) { status = ps; fast_exit = false; }
     }
     if (g_vcf) {
         std::string head;

@@ -43,6 +43,9 @@
 // include/dagcon.h is not applied again.  The span [e0, e1) these edits refer to is written on the #piece line: it is
 // the record's t0_t1 except where the first or last kept base is an inserted base (its g is that of the target base
 // behind it) or a window disagrees with the one before it.  Per piece: ref[e0, e1) with the edits applied is the piece.
+//
+// The pile-up (--pileup FILE, --sites FILE; pileup.h) needs no stitch: the cores tile the target, so the line of target
+// position p is that of position p - begin of the window whose core holds p, written group by group in window order.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -55,6 +58,7 @@
 #include "bam.h"
 #include "fastq.h"
 #include "intake.h"
+#include "pileup.h"
 #include "sam.h"
 
 struct DgPieceEdit { long long t_pos, t_len, c_off, c_len; };   // target [t_pos, t_pos + t_len) -> seq[c_off, c_off + c_len)
@@ -159,6 +163,8 @@ struct DgWinOpts {
     int device;
     DgPick pick;                                           // --max-error / --max-depth
     const char *edits;                                     // --edits FILE, or NULL
+    FILE *pileup = nullptr, *sites = nullptr;              // --pileup / --sites: open files, or NULL (the caller closes them)
+    uint32_t site_min_count = 0, site_min_ppm = 0;
 };
 
 // SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
@@ -292,6 +298,13 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         if ((rc = dagcon_set_edits(ctx, 1)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); return 1; }
         if (!(ef = fopen(o.edits, "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.edits); dagcon_destroy(ctx); return 1; }
     }
+    // --pileup / --sites: a position's line comes from the window whose core holds it
+    const bool pile = o.pileup || o.sites, want_rebuilt = ef || pile;
+    if (pile) {
+        const dagcon_pileup_opts po = {o.site_min_count, o.site_min_ppm};
+        if ((rc = dagcon_set_pileup(ctx, &po)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); if (ef) fclose(ef); dagcon_destroy(ctx); return 1; }
+    }
+    std::string pile_out, site_out;
     for (Tgt &t : tgts) t.fate.assign(t.recs.size(), 0);
     int status = 0;
     DgStitch st;
@@ -321,8 +334,8 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             }
             fwrite(out.data(), 1, out.size(), ef);
             out.clear();
-            std::string().swap(t.rebuilt);
         }
+        std::string().swap(tgts[(size_t)cur_tgt].rebuilt);
         st.reset();
         return true;
     };
@@ -349,7 +362,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             const uint32_t lo = wins[a].begin, hi = wins[z - 1].end;
             const uint32_t bt = (uint32_t)b_tlen.size();
             b_tlen.push_back(t.sp.len); b_toff.push_back(MD ? t_bytes : t.sp.off);
-            if (MD) { if (ef) stretches.push_back(Stretch{&t, t_bytes, lo, hi}); t_bytes += t.sp.len; }
+            if (MD) { if (want_rebuilt) stretches.push_back(Stretch{&t, t_bytes, lo, hi}); t_bytes += t.sp.len; }
             // records are ascending in s: none that starts more than the longest span in front of lo reaches it
             const uint32_t from = lo > t.max_span ? lo - t.max_span : 0u;
             auto it = std::lower_bound(t.recs.begin(), t.recs.end(), from, [](const Rec &r, uint32_t v) { return r.s < v; });
@@ -388,7 +401,13 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         dagcon_edits ed;
         memset(&ed, 0, sizeof ed);
         if (rc == DAGCON_OK && ef) rc = dagcon_fetch_edits(ctx, &ed);
-        if (rc == DAGCON_OK && ef && MD) {                     // REF of the edits: the group's stretch of every target, as the device rebuilt it
+        dagcon_pileup pu;
+        memset(&pu, 0, sizeof pu);
+        if (rc == DAGCON_OK && o.pileup) rc = dagcon_fetch_pileup(ctx, &pu);
+        dagcon_pileup_sites ps;
+        memset(&ps, 0, sizeof ps);
+        if (rc == DAGCON_OK && o.sites) rc = dagcon_fetch_pileup_sites(ctx, &ps);
+        if (rc == DAGCON_OK && want_rebuilt && MD) {           // REF of the edits and of the pile-up lines: the group's stretch of every target, as the device rebuilt it
             const char *tb = nullptr;
             uint64_t tn = 0;
             rc = dagcon_fetch_md_targets(ctx, &tb, &tn);
@@ -409,6 +428,12 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
                 cur_tgt = w.tgt;
             }
             const size_t g = k - w0;
+            if (pile) {
+                const Tgt &t = tgts[w.tgt];
+                const char *tb = MD ? t.rebuilt.data() : ref.bases.data() + t.sp.off;
+                if (o.pileup) dg_pileup_lines(pile_out, t.name, pu, (uint32_t)g, w.c0 - w.begin, w.c1 - w.begin, w.begin, tb);
+                if (o.sites) dg_site_lines(site_out, t.name, ps, (uint32_t)g, w.c0 - w.begin, w.c1 - w.begin, w.begin, tb);
+            }
             if (r.target_status[g] != DAGCON_OK)
                 fprintf(stderr, "pbdagcon: warning: %s window [%u, %u) skipped (%s)\n", tgts[w.tgt].name.c_str(), w.begin, w.end,
                         dg_status_text(r.target_status[g], MD ? kd.nonconforming : DG_CIGAR_UNFIT));
@@ -425,6 +450,9 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
                        o.fastq ? sup.weight + off : nullptr, o.fastq ? sup.depth + off : nullptr, ef ? &se : nullptr);
             }
         }
+        if (o.pileup && fwrite(pile_out.data(), 1, pile_out.size(), o.pileup) != pile_out.size()) { fprintf(stderr, "pbdagcon: error writing the --pileup file\n"); status = 1; }
+        if (o.sites && fwrite(site_out.data(), 1, site_out.size(), o.sites) != site_out.size()) { fprintf(stderr, "pbdagcon: error writing the --sites file\n"); status = 1; }
+        pile_out.clear(); site_out.clear();
         w0 = w1;
     }
     if (status == 0 && !flush_target()) status = 1;

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include "dagcon_dev.h"
 #include "k_norm_run.hip.h"
+#include "k_norm_fin.hip.h"
 
 #define DG_WAVE 64
 #ifndef DG_LPW
@@ -304,21 +305,43 @@ __device__ __forceinline__ uint32_t dg_wave_excl(const uint32_t v, const int lan
     return (uint32_t)incl - v;
 }
 
+// inclusive scan of (reset, value) words over the lanes of a wave with dg_seg_combine, in the form of dg_wave_excl: a
+// select and an add per step (lanes without a source combine with 0, the identity); no LDS
+__device__ __forceinline__ uint32_t dg_wave_seg_incl(uint32_t x) {
+#define DG_SEG_STEP(CTRL, ROWS) x = dg_seg_combine((uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWS, 0xf, false), x)
+    DG_SEG_STEP(0x111, 0xf);      // row_shr:1
+    DG_SEG_STEP(0x112, 0xf);      // row_shr:2
+    DG_SEG_STEP(0x114, 0xf);      // row_shr:4
+    DG_SEG_STEP(0x118, 0xf);      // row_shr:8
+    DG_SEG_STEP(0x142, 0xa);      // row_bcast:15 into rows 1 and 3
+    DG_SEG_STEP(0x143, 0xc);      // row_bcast:31 into rows 2 and 3
+#undef DG_SEG_STEP
+    return x;
+}
+
 // ---------------------------------------------------------------------------
 // k_norm_finish2: columns to their final place, and what dg_finish_alignment does on the chunk's share of the trimmed
 // window, a WAVE per chunk (round 3; a lane per chunk before it).  With a lane per chunk every lane streams lines of its
 // own, a whole grid apart: 16-byte accesses that share nothing, half a million chunks in flight, their partly written
 // lines (matC cells above all: 4 bytes here, 4 bytes there along a row) pushed out of the L2s before the next store to
 // them arrives -- 4.7 GB of traffic for a 0.9 GB copy.  Here the 64 lanes take consecutive 16-byte pieces of ONE chunk
-// (8 columns each, 512 per pass): the copy is coalesced loads and funnelled, aligned, coalesced stores; how many target
-// bases lie in front of a lane's columns is a prefix sum over the lanes, how long the insertion run in front of them is
-// a segmented one (reset at every lane that holds a match / deletion column); then every lane walks its own 8 columns
-// as dg_finish_alignment walks them all.  CT: the matC cell type (byte cells put four times as many of a row's runs into
-// a line).
+// (8 columns each, DG_FIN_NP adjacent pieces a lane): the copy is coalesced loads and funnelled, aligned 16-byte stores.
+//
+// What dg_finish_alignment does column by column happens here by EVENTS (round 8, k_norm_fin.hip.h).  A lane
+// classifies its columns four bytes at a time into three bit masks (advancing / insertion / deletion), cut to the
+// trimmed window by one range mask.  How many target bases lie in front of a lane's columns is a prefix sum over the
+// lanes, how long the insertion run in front of them is a segmented one (reset at every lane that holds an advancing
+// column), both by DPP row shifts and broadcasts.  Then the wave visits only the columns where something is written: the
+// advancing columns that end an insertion run (a matC cell; ~8 % of the columns) in a loop that lasts as long as the
+// lane with the most of them has one left, and the checkpoint columns (one in 1 << emit_shift positions), found by
+// arithmetic on the lane's position.  Position and run length of an event are popcounts of the masks.  CT: the matC cell
+// type (byte cells put four times as many of a row's runs into a line).
 // ---------------------------------------------------------------------------
 template <typename CT>
 __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
-    const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6);
+    // the wave's number, said to be the same in all lanes: what hangs on the chunk alone (its records, the read's and
+    // the target's, the window, the funnel's shift) is then loaded and computed once a wave, on the scalar side
+    const uint32_t g = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (g >= p.n_chunks) return;
     if (dg_failed(p)) return;
     const int lane = threadIdx.x & 63;
@@ -342,14 +365,11 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
     }
     const uint32_t tlen = graph ? p.tlen[t_idx] : 0xFFFFFFFFu;
     uint32_t *ck = p.ckpt + p.ck_base[a];
-    const uint32_t ck_mask = (1u << p.emit_shift) - 1u;
+    const DgFinChunk u = dg_fin_chunk(start, tlen, p.emit_shift, o, lo);
     const uint32_t adv_init = adv0 > lb ? adv0 - lb : 0u;            // target bases between the trimmed start and this chunk
     const uint32_t f0 = lo > o ? lo - o : 0u;
     const uint32_t f1 = hi > o ? (hi - o < w ? hi - o : w) : 0u;
     const bool any = f1 > f0;
-    const uint32_t fspan = any ? f1 - f0 : 0u;
-    // conformity as dg_finish_alignment keeps it: true while start - 1 + (target bases so far) <= tlen
-#define DG_FIN_CONF(A) (start >= 1u && ((A) == 0u || (uint64_t)start - 1u + (A) <= (uint64_t)tlen))
     const uint32_t h0 = (8u - (o & 7u)) & 7u;
     const uint32_t h = h0 < w ? h0 : w;
     const uint32_t nb = (w - h) / 8u, nvec = (w + 7u) / 8u;
@@ -358,63 +378,62 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
     { const uint32_t x = h + 8u * nb + (uint32_t)lane; if (lane < 8 && x < w) dst[x] = src[x]; }
     uint4 *dst4 = reinterpret_cast<uint4 *>(dst + h);
     uint32_t adv_tile = adv_init, run_tile = 0, n_ins = 0, n_del = 0;
-    // a lane takes one 16-byte piece per pass: a chunk of 512 input columns is ~550 columns here, two passes of 512
-    // (two pieces per lane and one pass: no faster, 6.0 against 5.9 ms of normalize)
-    for (uint32_t v0 = 0; v0 < nvec; v0 += 64u) {
-        const uint32_t vl = v0 + (uint32_t)lane;                     // the lane's piece
-        const uint4 pc = vl < nvec ? src4[vl] : make_uint4(0, 0, 0, 0);
-        const uint4 pn = vl + 1 < nvec ? src4[vl + 1] : make_uint4(0, 0, 0, 0);     // (the funnel takes columns from the next)
-        if (vl < nb) dst4[vl] = dg_funnel_cols(pc, pn, h);
+    const bool writes = Cm != nullptr && u.ok;                        // (no position of a non-conforming start is written to)
+    // a chunk of 512 input columns is ~550 columns here: one pass of 64 lanes x DG_FIN_NP pieces x 8 columns; the loop
+    // is for the re-run chunks that took their neighbour in.  (Round 3, while a lane walked every column: "two pieces
+    // per lane and one pass: no faster, 6.0 against 5.9 ms of normalize".  On the event loop two pieces and one pass are
+    // the faster: 3.77 - 3.83 ms of normalize against 3.84 - 3.91 with DG_FIN_NP 1, three alternating runs each.)
+    for (uint32_t v0 = 0; v0 < nvec; v0 += 64u * DG_FIN_NP) {
+        const uint32_t vl = v0 + DG_FIN_NP * (uint32_t)lane;         // the lane's first piece
+        // (the funnel takes columns from the next piece.  A piece behind the chunk's last is that one once more: no
+        // branch, nothing of it is stored -- vl + j < nb -- and the window ends in front of it)
+        uint4 pc[DG_FIN_NP + 1u];
+#pragma unroll
+        for (uint32_t j = 0; j <= DG_FIN_NP; j++) pc[j] = src4[vl + j < nvec ? vl + j : nvec - 1u];
+#pragma unroll
+        for (uint32_t j = 0; j < DG_FIN_NP; j++)
+            if (vl + j < nb) dst4[vl + j] = dg_funnel_cols(pc[j], pc[j + 1u], h);
         if (!any || 8u * v0 >= f1) continue;                          // (uniform) nothing of the window from here on
         // ---- the lane's columns: classes, inside the trimmed window only ----
-        uint32_t advm = 0, insm = 0, delm = 0;                        // bit k: column k advances the cursor / is an insertion / a deletion
+        uint32_t advm = 0, insm = 0, delm = 0;
 #pragma unroll
-        for (uint32_t k = 0; k < 8u; k++) {
-            const uint32_t wd = ((k >> 1) & 3u) == 0 ? pc.x : ((k >> 1) & 3u) == 1 ? pc.y : ((k >> 1) & 3u) == 2 ? pc.z : pc.w;
-            const uint16_t c = (uint16_t)((k & 1u) ? wd >> 16 : wd & 0xffffu);
-            const bool inw = 8u * vl + k < 8u * nvec && 8u * vl + k - f0 < fspan;
-            const uint8_t qb = DG_Q(c), tb = DG_T(c);
-            const bool adv = inw && (qb == tb || qb == DG_GAP);
-            advm |= adv ? 1u << k : 0u;
-            delm |= (adv && qb != tb) ? 1u << k : 0u;
-            insm |= (inw && !adv && tb == DG_GAP) ? 1u << k : 0u;
+        for (uint32_t j = 0; j < DG_FIN_NP; j++) {
+            const DgFinMasks m = dg_fin_piece(pc[j]);
+            advm |= m.advm << (8u * j); insm |= m.insm << (8u * j); delm |= m.delm << (8u * j);
         }
-        const uint32_t nadv = (uint32_t)__popc(advm), nI = (uint32_t)__popc(insm);
-        n_ins += nI; n_del += (uint32_t)__popc(delm);
-        // target bases in front of the lane's columns
-        const uint32_t adv_lane = adv_tile + dg_wave_excl(nadv, lane);
-        // insertion columns since the last advancing column in front of the lane's columns: a scan of (reset, value)
-        // pairs, (f1, v1) then (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2)
-        uint32_t sf = advm ? 1u : 0u;
-        uint32_t sv = advm ? (uint32_t)__popc(insm & ~((2u << (31 - __clz((int)advm))) - 1u)) : nI;      // behind its last advancing column
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t pf = (uint32_t)__shfl_up((int)sf, d), pv = (uint32_t)__shfl_up((int)sv, d);
-            if (lane >= d) { sv = sf ? sv : pv + sv; sf |= pf; }
+        const uint32_t win = dg_fin_window(8u * vl, f0, f1);
+        advm &= win; insm &= win; delm &= win;
+        const uint32_t nadv = (uint32_t)__popc(advm);
+        n_ins += (uint32_t)__popc(insm); n_del += (uint32_t)__popc(delm);
+        // target bases in front of the lane's columns, and the insertion run that arrives at them (the pass's first
+        // lane: what the pass before ended with)
+        const uint32_t adv_rel = dg_wave_excl(nadv, lane);
+        const uint32_t adv_lane = adv_tile + adv_rel;
+        const uint32_t seg = dg_wave_seg_incl(dg_seg_pack(advm, insm));
+        const uint32_t seg_front = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)seg, 0x138, 0xf, 0xf, false);     // wave_shr:1
+        const uint32_t run_in = dg_seg_value(dg_seg_combine(run_tile, seg_front));
+        run_tile = dg_seg_value(dg_seg_combine(run_tile, (uint32_t)__builtin_amdgcn_readlane((int)seg, 63)));
+        adv_tile += (uint32_t)__builtin_amdgcn_readlane((int)(adv_rel + nadv), 63);
+        if (!writes) continue;
+        // ---- insertion runs that end among the lane's columns: a matC cell each ----
+        uint32_t ends = dg_fin_run_ends(advm, insm, run_in);          // (lane-varying state in vector registers: see k_emit)
+        while (__ballot(ends != 0u)) {
+            if (ends) {
+                const uint32_t k = (uint32_t)__builtin_ctz(ends);
+                ends &= ends - 1u;
+                const DgFinEvent e = dg_fin_event(u, advm, insm, run_in, adv_lane, k);
+                if (e.writes) dg_store_run(p, Cm + e.pos, e.run);
+            }
         }
-        // exclusive: what the lane in front ends with (the pass's first lane: what the pass before ended with)
-        uint32_t ef = (uint32_t)__shfl_up((int)sf, 1), ev = (uint32_t)__shfl_up((int)sv, 1);
-        if (lane == 0) { ef = 0; ev = 0; }
-        uint32_t run = ef ? ev : ev + run_tile;
-        const uint32_t lf = (uint32_t)__builtin_amdgcn_readlane((int)sf, 63), lv = (uint32_t)__builtin_amdgcn_readlane((int)sv, 63);
-        run_tile = lf ? lv : lv + run_tile;
-        adv_tile += (uint32_t)__builtin_amdgcn_readlane((int)(adv_lane - adv_tile + nadv), 63);
-        // ---- the lane walks its columns (dg_finish_alignment's loop) ----
-        uint32_t adv = adv_lane;
-        if (Cm && (advm | insm)) {
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; k++) {
-                if ((advm >> k) & 1u) {
-                    const bool conf = DG_FIN_CONF(adv);
-                    const uint32_t x = 8u * vl + k;
-                    // (the first column of a chunk inside the window: the chunk in front records it,
-                    // it may end in the insertion run that belongs to this position)
-                    if (conf && ((start + adv) & ck_mask) == 0 && start + adv <= tlen + 1 && !(x == 0 && o > lo))
-                        ck[(start + adv) >> p.emit_shift] = o + x - run;
-                    if (run && conf && start + adv <= tlen + 1) dg_store_run(p, Cm + (start + adv), run);
-                    run = 0;
-                    adv++;
-                } else if ((insm >> k) & 1u) run++;
+        // ---- checkpoints: rare (one lane in a few passes), so the wave asks first ----
+        uint32_t jc = dg_fin_first_ckpt(u, adv_lane);
+        while (__ballot(jc < nadv)) {
+            if (jc < nadv) {
+                const uint32_t k = dg_fin_nth_adv(advm, jc);
+                const DgFinEvent e = dg_fin_event(u, advm, insm, run_in, adv_lane, k);
+                uint32_t slot, value;
+                if (dg_fin_ckpt(u, e, 8u * vl + k, slot, value)) ck[slot] = value;
+                jc += u.ck_mask + 1u;
             }
         }
     }
@@ -422,9 +441,9 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
     // a trailing insertion run of the read belongs to the position after its last one
     {
         const uint32_t adv = adv_tile, run = run_tile;
-        const bool conf = DG_FIN_CONF(adv);
+        const bool conf = dg_fin_conf(u, adv);
         if (lane == 0) {
-            if (any && Cm && conf && ((start + adv) & ck_mask) == 0 && start + adv <= tlen + 1 && (o + f1 < hi || run))
+            if (any && Cm && conf && ((start + adv) & u.ck_mask) == 0 && start + adv <= tlen + 1 && (o + f1 < hi || run))
                 ck[(start + adv) >> p.emit_shift] = o + f1 - run;
             if (run && Cm && conf && start + adv <= tlen + 1) dg_store_run(p, Cm + (start + adv), run);
             if (graph && any && !conf) dg_fail_aln(p, a, DG_E_NONCONF);
@@ -435,7 +454,6 @@ __global__ __launch_bounds__(256) void k_norm_finish2(DgParams p) {
         const uint32_t ti = dg_wave_excl(n_ins, lane) + n_ins, td = dg_wave_excl(n_del, lane) + n_del;
         if (lane == 63) { if (ti) atomicAdd(&p.n_ins[a], ti); if (td) atomicAdd(&p.n_del[a], td); }
     }
-#undef DG_FIN_CONF
 }
 
 // The same algorithm with the whole expanded alignment in HBM: raw mode and

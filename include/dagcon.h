@@ -361,6 +361,57 @@ typedef struct dagcon_pileup_sites { /* sites of target t: [site_begin[t], site_
 int dagcon_fetch_pileup_sites(dagcon_ctx *ctx, dagcon_pileup_sites *out);
 
 /*
+ * Site reads: which alignment shows which allele at each site of the pile-up, and a split of a target's alignments into
+ * two groups that agree site after site (off by default; a context switch like dagcon_set_pileup, which it needs).  A
+ * heterozygous site and a collapsed repeat copy are carried by the same reads at every site; a systematic error is not.
+ * This is this build's own rule, PARITY UNPINNED: the reference has no such output.  Everything is relative to a target
+ * of the pipeline: a target of the batch, or with windows a window.
+ * 1. The taken alignments are those of rule 1 of the pile-up: at least min_len columns, normalised, trimmed, non-empty,
+ *    of a target with a graph (not below min_cov, not failed), not left out by dagcon_set_record_filter.  They are
+ *    numbered x = 0 .. n_aln - 1 in the order the pipeline holds them: batch order with the others removed.  aln_tgt[x]
+ *    is the target (the window), aln_src[x] the index the caller gave the alignment by: the alignment index of a
+ *    dagcon_batch, the record index of every record batch (with windows: the piece's record) and of a dagcon_pre_batch.
+ * 2. Entries.  Alignment x has an entry at site k (position p of its target) iff it has a column with a target base at
+ *    coordinate p (rule 2 of the pile-up).  An entry holds one byte, code = cls | ins << 3: cls 0..5 for A C G T N DEL by
+ *    exactly the classification of that rule, ins = 1 iff an insertion run of this alignment is counted at p by the
+ *    pile-up's INS rule.  The inserted bases themselves are not compared: two alignments that insert different bases
+ *    behind p carry the same code.  The entries of an alignment are in ascending position, ent_begin[x] .. ent_begin[x + 1];
+ *    ent_site is an index into the arrays of dagcon_fetch_pileup_sites.  For every site the entries' classes add up to
+ *    the site's six counts and their ins bits to its INS.
+ * 3. Signs.  An entry gets M in {+1, 0, -1} from its site's counts, s2 the second largest of the six as in the site rule.
+ *    If min(INS, depth - INS) > s2 the site is an insertion site: M = -1 if ins, else +1.  Otherwise it is a base site:
+ *    k1 is the class with the largest count, ties to the lowest index; k2 the class with the largest count among the
+ *    others, ties to the lowest index, and only if that count is > 0; M = +1 for cls == k1, -1 for cls == k2, else 0.
+ * 4. The split (phase != 0), per target, in integers, nothing in it depends on an order.  The seed is the taken alignment
+ *    with the most entries of M != 0, ties to the lowest x; without one everything of the target stays 0.  sigma[k] =
+ *    M(seed, k) at the seed's entries, 0 elsewhere.  Then exactly `rounds` rounds of two steps:
+ *      h[x]     = sgn(sum over k of M(x, k) * sigma[k])    for every alignment of the target
+ *      sigma[k] = sgn(sum over x of M(x, k) * h[x])        for every site of the target
+ *    with sgn(0) = 0 (the device stops at a round that changes nothing: the answer is the same).  hap[x] is 1 for h = +1,
+ *    2 for h = -1, 0 for unassigned: no informative site, a tie, or more than `rounds` read-overlap hops from the seed.
+ *    phase[k] = sigma[k].  A round carries the labels one hop of overlapping reads further; rounds = 0 means the default,
+ *    8, this build's own choice: a target tiled by reads more than `rounds` hops deep leaves the far reads unassigned.
+ *    More than two groups are not looked for, and windows are labelled each on its own.
+ * 5. A failed target (target_status != DAGCON_OK) has no taken alignments, no entries and no phase.
+ * dagcon_set_site_reads: NULL turns it off; rounds > 64 is DAGCON_ERR_INVALID_ARG (the switch stays as it was).  The
+ * switch is read at the upload and needs dagcon_set_pileup on at the same upload.  With either off at the upload no
+ * kernel, buffer, memset, launch or copy differs from a context that never heard of it, and dagcon_fetch_site_reads is
+ * DAGCON_ERR_STATE; the same before a dagcon_fetch and under DAGCON_FLAG_STOP_AFTER_BUILD / _MERGE.  With both on, the
+ * kernels of csrc/k_site_reads.hip.h run behind the pile-up's in every execution of the run; the entry arena grows by a
+ * re-run (at thresholds 0 / 0 every target-base column is an entry).  The arrays stay on the device and are copied only
+ * when dagcon_fetch_site_reads is called.  They are owned by the context, valid as long as the results of the same fetch.
+ */
+typedef struct dagcon_site_reads_opts { uint32_t phase, rounds; } dagcon_site_reads_opts;   /* rounds 0: the default, 8 */
+int dagcon_set_site_reads(dagcon_ctx *ctx, const dagcon_site_reads_opts *o);   /* NULL: off (the default) */
+typedef struct dagcon_site_reads {
+    uint64_t n_aln; const uint32_t *aln_tgt; const uint64_t *aln_src;      /* the taken alignments */
+    const uint64_t *ent_begin;                                             /* [n_aln + 1] */
+    const uint64_t *ent_site; const uint8_t *ent_code;                     /* ent_site: index into dagcon_pileup_sites' arrays */
+    const uint8_t *hap; const int8_t *phase;                               /* [n_aln], [sites]; NULL when phase was off */
+} dagcon_site_reads;
+int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out);
+
+/*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses
  * alignment records straight into such a buffer gets its dagcon_upload at link speed instead of
  * through the driver's staging copies.  Optional: any host memory is accepted by dagcon_upload.

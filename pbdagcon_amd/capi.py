@@ -44,6 +44,7 @@ EXPORTS = [
     "dagcon_set_edits", "dagcon_fetch_edits",
     "dagcon_set_edit_support", "dagcon_fetch_edit_support",
     "dagcon_set_pileup", "dagcon_fetch_pileup", "dagcon_fetch_pileup_sites",
+    "dagcon_set_site_reads", "dagcon_fetch_site_reads",
     "dagcon_upload_cigar_md", "dagcon_consensus_cigar_md", "dagcon_fetch_md_targets",
 ]
 ABI_VERSION = 2
@@ -147,6 +148,19 @@ class PileupSites(C.Structure):
                 ("counts", C.POINTER(C.c_uint16))]
 
 
+class SiteReadsOpts(C.Structure):
+    """dagcon_site_reads_opts: phase != 0 splits each target's alignments in two; rounds 0 is the default, 8 (include/dagcon.h
+    has the rule)."""
+    _fields_ = [("phase", C.c_uint32), ("rounds", C.c_uint32)]
+
+
+class SiteReads(C.Structure):
+    """dagcon_site_reads: the taken alignments, their entries at the sites of dagcon_pileup_sites, hap and phase."""
+    _fields_ = [("n_aln", C.c_uint64), ("aln_tgt", C.POINTER(C.c_uint32)), ("aln_src", C.POINTER(C.c_uint64)),
+                ("ent_begin", C.POINTER(C.c_uint64)), ("ent_site", C.POINTER(C.c_uint64)), ("ent_code", C.POINTER(C.c_uint8)),
+                ("hap", C.POINTER(C.c_uint8)), ("phase", C.POINTER(C.c_int8))]
+
+
 class Edits(C.Structure):
     """dagcon_edits: per segment its target span and its edits (include/dagcon.h has the definition)."""
     _fields_ = [("n_segments", C.c_uint64), ("n", C.c_uint64), ("seg_t0", C.POINTER(C.c_uint32)),
@@ -231,6 +245,8 @@ def load() -> C.CDLL:
     L.dagcon_set_pileup.argtypes = [vp, C.POINTER(PileupOpts)]
     L.dagcon_fetch_pileup.argtypes = [vp, C.POINTER(Pileup)]
     L.dagcon_fetch_pileup_sites.argtypes = [vp, C.POINTER(PileupSites)]
+    L.dagcon_set_site_reads.argtypes = [vp, C.POINTER(SiteReadsOpts)]
+    L.dagcon_fetch_site_reads.argtypes = [vp, C.POINTER(SiteReads)]
     L.dagcon_upload_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int]
     L.dagcon_consensus_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int,
                                             C.POINTER(Results)]
@@ -884,6 +900,36 @@ class Context:
         return {"site_begin": begin,
                 "pos": np.ctypeslib.as_array(ps.pos, shape=(n,)).copy() if n else np.zeros(0, np.uint32),
                 "counts": np.ctypeslib.as_array(ps.counts, shape=(n, 8)).copy() if n else np.zeros((0, 8), np.uint16)}
+
+    def set_site_reads(self, phase=False, rounds=0):
+        """dagcon_set_site_reads for every later upload made with set_pileup on: the device lists per taken alignment what
+        it shows at each site (site_reads()); phase: it also splits each target's alignments in two, in `rounds` rounds
+        (0: the default, 8).  set_site_reads(None): off."""
+        if phase is None:
+            self._chk(self.L.dagcon_set_site_reads(self.h, None))
+            return
+        o = SiteReadsOpts(1 if phase else 0, rounds)
+        self._chk(self.L.dagcon_set_site_reads(self.h, C.byref(o)))
+
+    def site_reads(self) -> dict:
+        """dagcon_fetch_site_reads (copies): aln_tgt (uint32), aln_src (uint64) per taken alignment; ent_begin (uint64, one
+        more); ent_site (uint64, index into pileup_sites()' arrays) and ent_code (uint8, cls | ins << 3) per entry; hap
+        (uint8 per alignment) and phase (int8 per site), None when phase was off."""
+        sr = SiteReads()
+        self._chk(self.L.dagcon_fetch_site_reads(self.h, C.byref(sr)))
+        ps = PileupSites()
+        self._chk(self.L.dagcon_fetch_pileup_sites(self.h, C.byref(ps)))
+        n = int(sr.n_aln)
+        n_site = int(ps.site_begin[int(ps.n_targets)])
+
+        def arr(ptr, k, dt):
+            return np.ctypeslib.as_array(ptr, shape=(k,)).copy() if k else np.zeros(0, dt)
+        begin = np.ctypeslib.as_array(sr.ent_begin, shape=(n + 1,)).copy()
+        ne = int(begin[n])
+        return {"aln_tgt": arr(sr.aln_tgt, n, np.uint32), "aln_src": arr(sr.aln_src, n, np.uint64), "ent_begin": begin,
+                "ent_site": arr(sr.ent_site, ne, np.uint64), "ent_code": arr(sr.ent_code, ne, np.uint8),
+                "hap": arr(sr.hap, n, np.uint8) if sr.hap else None,
+                "phase": arr(sr.phase, n_site, np.int8) if sr.phase else None}
 
     def edits(self) -> dict:
         """dagcon_fetch_edits (copies): seg_t0, seg_t1 (uint32, one per segment of the last results, in their order),

@@ -87,14 +87,18 @@ struct RunBufs {
     DevBuf ed_seg, ed_out;                          // dagcon_set_edits: a DgEdSeg per segment, a DgEdit per edit
     DevBuf evid;                                    // dagcon_set_edit_support: a DgEvid per edit
     DevBuf pile, pile_tile, pile_site;              // dagcon_set_pileup: 16 B per position (cleared before every run), 8 B per tile, a DgSite per site
-    std::array<DevBuf *, 62> all() {
+    // dagcon_set_site_reads: a bit and a rank word per 64 positions; per alignment its entry count, offset, hap and signed
+    // entries; per entry its site and code; per site its phase, sign rule and a round's sum
+    DevBuf sr_bits, sr_rank, sr_cnt, sr_off, sr_site, sr_code, sr_hap, sr_sigma, sr_kind, sr_acc, sr_nz;
+    std::array<DevBuf *, 73> all() {
         return {&nmis, &n_lo, &n_hi, &n_start, &n_ins, &n_del, &ch_k0, &ch_next, &ch_w, &ch_tb, &ch_flag, &ch_src, &ch_out, &ch_adv, &n_lb, &norm_tmp, &ckpt,
                 &node_base, &n_nodes, &pool_base, &pool_size, &pool_top, &t_nins, &cov, &gcount, &gbase, &bid, &best, &queue, &score, &cns_tmp, &bp_tt,
                 &stk, &cuts, &cuts_bp, &bp_stat, &bp_len, &rd, &pro_state, &sh_cnt, &wl_first, &queue0, &bp_end, &bp_ab, &defer, &cns_tmp0, &cns,
-                &seg, &worklist, &seg_done, &sup_tmp, &sup_tmp0, &sup, &pos_tmp, &pos_tmp0, &pos, &ed_seg, &ed_out, &evid, &pile, &pile_tile, &pile_site};
+                &seg, &worklist, &seg_done, &sup_tmp, &sup_tmp0, &sup, &pos_tmp, &pos_tmp0, &pos, &ed_seg, &ed_out, &evid, &pile, &pile_tile, &pile_site,
+                &sr_bits, &sr_rank, &sr_cnt, &sr_off, &sr_site, &sr_code, &sr_hap, &sr_sigma, &sr_kind, &sr_acc, &sr_nz};
     }
 };
-static_assert(sizeof(RunBufs) == 62 * sizeof(DevBuf), "RunBufs::all() must name every member");
+static_assert(sizeof(RunBufs) == 73 * sizeof(DevBuf), "RunBufs::all() must name every member");
 // ArenaBufs: the arenas with a treatment of their own -- matC is cleared before every run, the others are filled under
 // DAGCON_POISON bits 1 (matA, matD), 2 (nodes, pool) and 4 (score_b, norm)
 struct ArenaBufs {
@@ -110,6 +114,7 @@ struct StatBlock {
     size_t o_tfail = 0, o_cns_len = 0, o_n_seg = 0, o_cns_off = 0, o_seg_first = 0;     // (DgStatus at 0)
     size_t o_ed_top = 0;                            // edits of the batch, behind seg_first (a batch with edits on only; 0: none)
     size_t o_site_top = 0;                          // sites of the batch, behind that (a batch with the pile-up on only; 0: none)
+    size_t o_sr_top = 0;                            // entries of the batch, the second word of the same 16 bytes (dagcon_set_site_reads; 0: none)
     size_t zero_bytes = 0, bytes = 0;
     template <typename X> X *d(size_t off) const { return reinterpret_cast<X *>(static_cast<char *>(dev.p) + off); }
     template <typename X> const X *h(size_t off) const { return reinterpret_cast<const X *>(host.as<char>() + off); }
@@ -181,6 +186,12 @@ struct Ctx {
     bool pile_on = false, pile_batch = false;
     dagcon_pileup_opts pile_opts = {0u, 0u}, pile_batch_opts = {0u, 0u};
     std::vector<uint64_t> h_pile_begin;             // [T + 1]
+    // dagcon_set_site_reads: the switch; whether the batch on the device was uploaded under it (and under the pile-up) and
+    // with which options; per alignment of the device the index the caller knows it by; the entry arena's size
+    bool sr_on = false, sr_batch = false;
+    dagcon_site_reads_opts sr_opts = {0u, 0u}, sr_batch_opts = {0u, 0u};
+    std::vector<uint64_t> h_aln_src;                // [A]
+    uint64_t sr_cap = 0;
     uint64_t site_cap = 0;
     uint64_t ed_cap = 0;
     long ed_cap_env = 0;                            // DAGCON_EDITS_CAP (tests): first size of the edit arena, so that the re-run is met
@@ -218,6 +229,14 @@ struct Ctx {
     bool pile_fetched = false;          // r_pile holds the counts of the same run (dagcon_fetch_pileup copies them when asked)
     PinBuf r_site;                      // the DgSite records of the last fetch
     PinBuf r_pile;                      // uint16_t, eight per position
+    bool sr_valid = false;              // the last fetch was of a batch with dagcon_set_site_reads on: sr_n_ent, sr_n_site, s_dev_begin are its
+    bool sr_fetched = false;            // the arrays below are that run's (dagcon_fetch_site_reads copies them when asked)
+    uint64_t sr_n_ent = 0, sr_n_site = 0;
+    std::vector<uint64_t> s_dev_begin;  // [T + 1] where a target's sites begin in the device's list (s_begin: in the host's)
+    std::vector<uint32_t> x_tgt;
+    std::vector<uint64_t> x_src, x_begin, x_site;
+    std::vector<uint8_t> x_code, x_hap;
+    std::vector<int8_t> x_phase;
     std::vector<uint64_t> s_begin;
     std::vector<uint32_t> s_pos;
     std::vector<uint16_t> s_counts;

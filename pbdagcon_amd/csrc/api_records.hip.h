@@ -49,6 +49,7 @@ Ctx *intake_reset(dagcon_ctx *ctx) {
     c->ed_batch = c->ed_valid = c->pos_pending = false;
     c->evid_batch = c->evid_valid = false;
     c->pile_batch = c->pile_valid = c->pile_fetched = false;
+    c->sr_batch = c->sr_valid = c->sr_fetched = false;
     c->md_valid = c->md_fetched = false;
     return c;
 }
@@ -258,6 +259,7 @@ struct CigarPlan {
     std::vector<uint32_t> tlen;                                    // windows: the pipeline's targets (whole: the batch's own)
     std::vector<uint64_t> beg, off;                                // aln_begin, aln_off
     std::vector<uint32_t> start, len;                              // aln_start, aln_len
+    std::vector<uint32_t> rec;                                     // the record each of them comes from (dagcon_site_reads::aln_src)
     uint64_t bytes = 0;                                            // of each string blob
     bool pieces = false;                                           // the expansion is k_cigar_expand_cut's, over cw
     DgCigarCutParams cw;
@@ -292,7 +294,7 @@ int plan_whole(Ctx *c, const dagcon_cigar_batch *b, CigarScan &sc, const CigarVe
         if (pl.bad[g] || k == 0 || k < c->opts.min_cov) continue;
         for (const uint32_t a : recs) {
             out_off[a] = pl.bytes; t_base[a] = b->t_off[g] + b->pos[a] - 1u;
-            pl.start.push_back(b->pos[a]); pl.off.push_back(pl.bytes); pl.len.push_back(sc.tot[a * 4]);
+            pl.start.push_back(b->pos[a]); pl.off.push_back(pl.bytes); pl.len.push_back(sc.tot[a * 4]); pl.rec.push_back(a);
             pl.bytes += ((uint64_t)sc.tot[a * 4] + 15ull) & ~15ull;
         }
     }
@@ -390,7 +392,7 @@ int plan_windows(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn, 
     // the output plan: nothing the device said is used before it has been checked against the record's own sizes
     std::vector<uint64_t> pout((size_t)np);
     std::vector<uint32_t> wbegin((size_t)np), wpiece;
-    pl.off.resize(np); pl.start.resize(np); pl.len.resize(np);
+    pl.off.resize(np); pl.start.resize(np); pl.len.resize(np); pl.rec.resize(np);
     uint32_t cur = 0;
     for (uint32_t i = 0; i < np; i++) {
         const uint32_t a = piece[i * 4], w = piece[i * 4 + 3];
@@ -399,7 +401,7 @@ int plan_windows(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn, 
         if (ca > cb || cb > tot[a * 4] || ta > tb || tb >= ntile)
             return fail(c, DAGCON_ERR_INTERNAL, "k_cigar_cut: piece %u of record %u has columns [%u, %u), tiles [%u, %u] of %llu", i, a, ca, cb, ta, tb, (unsigned long long)ntile);
         while (cur < w) pl.beg[++cur] = i;
-        pl.off[i] = pout[i] = pl.bytes;
+        pl.off[i] = pout[i] = pl.bytes; pl.rec[i] = a;
         pl.len[i] = cb - ca;
         pl.start[i] = rs[a] + piece[i * 4 + 1] - wn->begin[w] + 1u;
         pl.bytes += ((uint64_t)(cb - ca) + 15ull) & ~15ull;
@@ -464,6 +466,7 @@ int cigar_hand_over(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const 
     const int r = upload_impl(ctx, &db, c->in.q.p, c->in.t.p);       // (synchronises the stream: the caller's locals may go)
     if (r != DAGCON_OK) { (void)hipStreamSynchronize(c->stream); return r; }
     c->h_cig_bad = pl.bad;
+    for (uint64_t &x : c->h_aln_src) x = pl.rec[x];                // (dagcon_set_site_reads: upload_impl left the index into pl's arrays)
     c->cig_err = v.first_err;
     if (c->filter_on) {                                            // dagcon_fetch_record_stats: one array per count
         const size_t n = pk.fate.size();

@@ -74,7 +74,9 @@ int ensure_stat(Ctx *c, uint32_t T) {
     b.o_ed_top = 0;
     if (c->ed_batch) { b.o_ed_top = b.bytes; b.bytes += 16; }
     b.o_site_top = 0;
+    b.o_sr_top = 0;
     if (c->pile_batch) { b.o_site_top = b.bytes; b.bytes += 16; }
+    if (c->sr_batch) b.o_sr_top = b.o_site_top + 8;
     ENSURE(c, b.dev, b.bytes);
     return b.host.reserve(c, b.bytes);
 }
@@ -128,6 +130,17 @@ int ensure_arenas(Ctx *c) {
         ENSURE(c, c->run.pile, pn * 16);
         ENSURE(c, c->run.pile_tile, (pn + DG_PILE_TILE - 1) / DG_PILE_TILE * 8);
         ENSURE(c, c->run.pile_site, c->site_cap * sizeof(DgSite));
+    }
+    if (c->sr_batch) {
+        const uint64_t words = (c->h_pile_begin.back() + 63) / 64;
+        const size_t A4 = (size_t)c->A * 4;
+        ENSURE(c, c->run.sr_bits, words * 8); ENSURE(c, c->run.sr_rank, words * 4);
+        ENSURE(c, c->run.sr_cnt, A4); ENSURE(c, c->run.sr_off, 2 * A4);
+        ENSURE(c, c->run.sr_site, c->sr_cap * 4); ENSURE(c, c->run.sr_code, c->sr_cap);
+        if (c->sr_batch_opts.phase) {
+            ENSURE(c, c->run.sr_hap, (size_t)c->A); ENSURE(c, c->run.sr_nz, A4);
+            ENSURE(c, c->run.sr_sigma, c->site_cap); ENSURE(c, c->run.sr_kind, c->site_cap); ENSURE(c, c->run.sr_acc, c->site_cap * 4);
+        }
     }
     ENSURE(c, c->run.seg, 2 * seg_stride(c) * 4);
     if (int r = c->r_seg.reserve(c, 2 * (size_t)c->seg_cap * 4)) return r;
@@ -221,6 +234,17 @@ void fill_params(Ctx *c, DgParams &p) {
         p.pile_site = c->run.pile_site.as<DgSite>(); p.site_cap = c->site_cap;
         p.site_top = c->sb.d<unsigned long long>(c->sb.o_site_top);
         p.pile_min_count = c->pile_batch_opts.min_count; p.pile_min_ppm = c->pile_batch_opts.min_frac_ppm;
+    }
+    if (c->sr_batch) {
+        p.sr_bits = c->run.sr_bits.as<unsigned long long>(); p.sr_rank = c->run.sr_rank.as<uint32_t>();
+        p.sr_cnt = c->run.sr_cnt.as<uint32_t>(); p.sr_off = c->run.sr_off.as<unsigned long long>();
+        p.sr_site = c->run.sr_site.as<uint32_t>(); p.sr_code = c->run.sr_code.as<uint8_t>(); p.sr_cap = c->sr_cap;
+        p.sr_top = c->sb.d<unsigned long long>(c->sb.o_sr_top);
+        p.sr_phase = c->sr_batch_opts.phase; p.sr_rounds = c->sr_batch_opts.rounds ? c->sr_batch_opts.rounds : 8u;
+        if (p.sr_phase) {
+            p.sr_hap = c->run.sr_hap.as<uint8_t>(); p.sr_nz = c->run.sr_nz.as<uint32_t>();
+            p.sr_sigma = c->run.sr_sigma.as<int8_t>(); p.sr_kind = c->run.sr_kind.as<uint8_t>(); p.sr_acc = c->run.sr_acc.as<int>();
+        }
     }
 }
 
@@ -373,6 +397,15 @@ int launch_all(Ctx *c) {
             hipLaunchKernelGGL(k_pile_sites<false>, tg, dim3(DG_PILE_TILE), 0, s, p);
             hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(1024), 0, s, p);
             hipLaunchKernelGGL(k_pile_sites<true>, tg, dim3(DG_PILE_TILE), 0, s, p);
+            if (c->sr_batch) {
+                // the reads at the sites (k_site_reads.hip.h): a bit per site position, count, scan, write; then the split
+                HIPCHK(c, hipMemsetAsync(c->run.sr_bits.p, 0, (p.pile_n + 63) / 64 * 8, s));
+                hipLaunchKernelGGL(k_sr_mark, dim3((uint32_t)((p.site_cap + 255) / 256)), dim3(256), 0, s, p);
+                if (c->A > 0) hipLaunchKernelGGL(k_sr_walk<false>, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
+                hipLaunchKernelGGL(k_sr_scan, dim3(1), dim3(1024), 0, s, p);
+                if (c->A > 0) hipLaunchKernelGGL(k_sr_walk<true>, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
+                if (p.sr_phase && c->A > 0) hipLaunchKernelGGL(k_sr_split, dim3(c->T), dim3(256), 0, s, p);
+            }
         }
     }
     HIPCHK(c, hipEventRecord(c->ev[4], s));
@@ -451,6 +484,9 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->evid_batch = c->evid_valid = false;
     c->pile_batch = c->pile_on; c->pile_batch_opts = c->pile_opts;
     c->pile_valid = c->pile_fetched = false;
+    c->sr_batch = c->sr_on && c->pile_on; c->sr_batch_opts = c->sr_opts;
+    c->sr_valid = c->sr_fetched = false;
+    c->h_aln_src.clear();
     c->h_cig_bad.clear();
     c->rs_valid = false;
     c->md_valid = c->md_fetched = false;
@@ -495,6 +531,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
             c->h_aln_start.push_back(b->aln_start[a]);
             c->h_aln_off.push_back(b->aln_off[a]);
             c->h_aln_tgt.push_back(t);
+            if (c->sr_batch) c->h_aln_src.push_back(a);
             c->sum_len += len;
             // (a read that spans the target begins at its first base and has a column per target base; necessary, not
             // sufficient -- a read that ends early and inserts a lot passes too: the batch is then exact all the same, with
@@ -613,6 +650,12 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
         UPLOAD(c, c->in.pile_begin, c->h_pile_begin);
         // first guess, as for the edits; a run with more sites records their number and is repeated (DG_E_SITE_OVF)
         c->site_cap = std::max<uint64_t>(c->site_cap, c->h_pile_begin[T] / 8 + 1024);
+        if (c->sr_batch) {
+            // a site index is 32 bits wide in an entry
+            if (c->h_pile_begin[T] > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "dagcon_set_site_reads: more than 2^32 - 16 target positions in a batch");
+            // first guess: one column in 64 an entry; a run with more records their number and is repeated (DG_E_SR_OVF)
+            c->sr_cap = std::max<uint64_t>(c->sr_cap, c->sum_len / 64 + 4096);
+        }
     }
     ENSURE(c, c->run.ckpt, c->n_ckpt * 4);
 
@@ -663,6 +706,7 @@ int dagcon_run(dagcon_ctx *ctx) {
     c->ed_valid = c->pos_pending = false;
     c->evid_valid = false;
     c->pile_valid = c->pile_fetched = false;
+    c->sr_valid = c->sr_fetched = false;
     if (const char *e = getenv("DAGCON_DUMP")) return dump_target(c, e);
     return DAGCON_OK;
 }
@@ -725,6 +769,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         if (f & DG_E_RUN_WIDE) c->wide_cells = true;       // (until the next upload)
         if ((f & DG_E_ED_OVF) && sb.o_ed_top) c->ed_cap = *sb.h<uint64_t>(sb.o_ed_top) + 1024;
         if ((f & DG_E_SITE_OVF) && sb.o_site_top) c->site_cap = *sb.h<uint64_t>(sb.o_site_top) + 1024;
+        if ((f & DG_E_SR_OVF) && sb.o_sr_top) c->sr_cap = *sb.h<uint64_t>(sb.o_sr_top) + 1024;
         if (f & DG_E_OUT_OVF) {
             c->cns_cap = std::max<uint64_t>(c->cns_cap, c->h_st.cns_top + 1024);
             c->seg_cap = std::max<uint64_t>(c->seg_cap, c->h_st.seg_top + 1024);
@@ -775,6 +820,7 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     c->ed_valid = c->pos_pending = false;
     c->evid_valid = false;
     c->pile_valid = c->pile_fetched = false;
+    c->sr_valid = c->sr_fetched = false;
     c->r_nb = nb;
     // the pile-up's sites come back here; its counts, 16 bytes a position, stay on the device until dagcon_fetch_pileup
     const bool want_pile = full && c->pile_batch;
@@ -864,9 +910,11 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         // target the host reports as failed has none (one that failed on the device has none there either)
         const DgSite *m_site = c->r_site.as<const DgSite>();
         c->s_begin.assign((size_t)T + 1, 0); c->s_pos.clear(); c->s_counts.clear();
+        if (c->sr_batch) c->s_dev_begin.assign((size_t)T + 1, n_site);
         uint64_t k = 0;
         for (uint32_t t = 0; t < T; t++) {
             c->s_begin[t] = c->s_pos.size();
+            if (c->sr_batch) c->s_dev_begin[t] = k;
             for (; k < n_site && m_site[k].tgt == t; k++) {
                 const DgSite &x = m_site[k];
                 if (x.pos >= c->h_tlen[t]) return fail(c, DAGCON_ERR_INTERNAL, "k_pile_sites: site %llu of target %u at position %u of %u", (unsigned long long)k, t, x.pos, c->h_tlen[t]);
@@ -878,6 +926,13 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         if (k != n_site) return fail(c, DAGCON_ERR_INTERNAL, "k_pile_sites: site %llu of %llu is out of order (target %u)", (unsigned long long)k, (unsigned long long)n_site, m_site[k].tgt);
         c->s_begin[T] = c->s_pos.size();
         c->pile_valid = true;
+        if (c->sr_batch) {
+            // the entries stay on the device until dagcon_fetch_site_reads; their number came with the status block
+            c->sr_n_site = n_site;
+            c->sr_n_ent = T && c->h_pile_begin.back() ? *sb.h<uint64_t>(sb.o_sr_top) : 0;
+            if (c->sr_n_ent > c->sr_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu site entries in an arena of %llu", (unsigned long long)c->sr_n_ent, (unsigned long long)c->sr_cap);
+            c->sr_valid = true;
+        }
     }
     c->r_seg_begin[T] = c->r_range0.size();
     c->tm.consensus_bases = bases;
@@ -999,6 +1054,73 @@ int dagcon_fetch_pileup(dagcon_ctx *ctx, dagcon_pileup *out) {
     }
     out->n_targets = c->T;
     out->pos_begin = c->h_pile_begin.data(); out->counts = c->r_pile.as<uint16_t>();
+    return DAGCON_OK;
+}
+
+int dagcon_set_site_reads(dagcon_ctx *ctx, const dagcon_site_reads_opts *o) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!o) { c->sr_on = false; return DAGCON_OK; }
+    if (o->rounds > 64u) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_site_reads: %u rounds are more than 64", o->rounds);
+    c->sr_opts = *o;
+    c->sr_on = true;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->sr_valid || !c->pile_valid)
+        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_site_reads without the results of an upload made with dagcon_set_pileup and dagcon_set_site_reads on "
+                                         "(a switch off at the upload, no fetch yet, or stopped before bestPath)");
+    const bool phase = c->sr_batch_opts.phase != 0;
+    if (!c->sr_fetched) {
+        // the copies dagcon_fetch left out, and the device's arrays in the host's terms: the alignments of a failed target
+        // and the ones the graph did not take go, a site's index becomes the one dagcon_fetch_pileup_sites lists it under
+        HIPCHK(c, hipSetDevice(c->device));
+        const uint32_t A = c->A, T = c->T;
+        const uint64_t ne = c->sr_n_ent, ns = c->sr_n_site;
+        const bool ran = T && c->h_pile_begin.back();               // (otherwise launch_all started none of the kernels)
+        std::vector<uint32_t> cnt((size_t)A, 0), site((size_t)ne);
+        std::vector<uint8_t> code((size_t)ne), hap((size_t)A, 0);
+        std::vector<int8_t> sigma((size_t)ns, 0);
+        if (ran && A) HIPCHK(c, d2h(c, cnt.data(), c->run.sr_cnt.p, (size_t)A * 4));
+        if (ne) { HIPCHK(c, d2h(c, site.data(), c->run.sr_site.p, (size_t)ne * 4)); HIPCHK(c, d2h(c, code.data(), c->run.sr_code.p, (size_t)ne)); }
+        if (phase && ran && A) HIPCHK(c, d2h(c, hap.data(), c->run.sr_hap.p, (size_t)A));
+        if (phase && ns) HIPCHK(c, d2h(c, sigma.data(), c->run.sr_sigma.p, (size_t)ns));
+        c->x_tgt.clear(); c->x_src.clear(); c->x_begin.assign(1, 0); c->x_site.clear(); c->x_code.clear(); c->x_hap.clear();
+        uint64_t e = 0;
+        for (uint32_t a = 0; a < A; a++) {
+            const uint32_t t = c->h_aln_tgt[a], n = cnt[a] & ~DG_SR_TAKEN;
+            const uint64_t e0 = e;
+            e += n;
+            if (e > ne) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_walk: the alignments hold more than the %llu entries of the batch (alignment %u)", (unsigned long long)ne, a);
+            if (c->r_status[t] != DAGCON_OK || !(cnt[a] & DG_SR_TAKEN)) continue;
+            const uint64_t d0 = c->s_dev_begin[t], d1 = c->s_dev_begin[t + 1];
+            for (uint64_t j = e0; j < e; j++) {
+                if (site[j] < d0 || site[j] >= d1 || (code[j] & 7u) > 5u || (code[j] >> 4))
+                    return fail(c, DAGCON_ERR_INTERNAL, "k_sr_walk: entry %llu of alignment %u: site %u, code %u (target %u has sites [%llu, %llu))", (unsigned long long)(j - e0), a,
+                                site[j], code[j], t, (unsigned long long)d0, (unsigned long long)d1);
+                c->x_site.push_back(site[j] - d0 + c->s_begin[t]);
+                c->x_code.push_back(code[j]);
+            }
+            c->x_tgt.push_back(t); c->x_src.push_back(c->h_aln_src[a]); c->x_begin.push_back(c->x_site.size());
+            if (hap[a] > 2u) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_split: alignment %u has hap %u", a, hap[a]);
+            c->x_hap.push_back(hap[a]);
+        }
+        if (e != ne) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_walk: the alignments hold %llu entries, the batch %llu", (unsigned long long)e, (unsigned long long)ne);
+        c->x_phase.assign(c->s_pos.size() + 1, 0);
+        for (uint32_t t = 0; t < T && phase; t++) {
+            if (c->r_status[t] != DAGCON_OK) continue;
+            for (uint64_t j = c->s_begin[t]; j < c->s_begin[t + 1]; j++) c->x_phase[j] = sigma[c->s_dev_begin[t] + (j - c->s_begin[t])];
+        }
+        c->x_site.push_back(0); c->x_code.push_back(0); c->x_tgt.push_back(0); c->x_src.push_back(0); c->x_hap.push_back(0);   // (no NULL for an empty array)
+        c->sr_fetched = true;
+    }
+    out->n_aln = c->x_begin.size() - 1;
+    out->aln_tgt = c->x_tgt.data(); out->aln_src = c->x_src.data(); out->ent_begin = c->x_begin.data();
+    out->ent_site = c->x_site.data(); out->ent_code = c->x_code.data();
+    out->hap = phase ? c->x_hap.data() : nullptr; out->phase = phase ? c->x_phase.data() : nullptr;
     return DAGCON_OK;
 }
 

@@ -33,6 +33,7 @@
 #include "k_edits.hip.h"
 #include "k_evidence.hip.h"
 #include "k_pileup.hip.h"
+#include "k_site_reads.hip.h"
 #include "api_ctx.h"
 #include "api_run.hip.h"
 #include "api_align.hip.h"

@@ -40,6 +40,7 @@
 #define DG_E_RUN_WIDE    0x1000u // an insertion run longer than 255 columns met byte-wide matC cells (rerun with 32-bit cells)
 #define DG_E_ED_OVF      0x2000u // edit arena too small (dagcon_set_edits; rerun with *DgParams::ed_top)
 #define DG_E_SITE_OVF    0x4000u // site arena too small (dagcon_set_pileup; rerun with *DgParams::site_top)
+#define DG_E_SR_OVF      0x8000u // entry arena too small (dagcon_set_site_reads; rerun with *DgParams::sr_top)
 
 // failures of one target (its input, or an invariant of its graph): recorded in DgParams::tfail,
 // the batch goes on; everything else is a capacity problem of the whole batch (grow and re-run)
@@ -239,7 +240,23 @@ struct DgParams {
     uint64_t site_cap;
     unsigned long long *site_top;  // sites of the batch (k_pile_scan; in the status block)
     uint32_t pile_min_count, pile_min_ppm;     // dagcon_pileup_opts
+    // ---- per-read alleles at the sites and the two-way split (dagcon_set_site_reads; NULL / 0 otherwise): k_site_reads.hip.h ----
+    unsigned long long *sr_bits;   // [(pile_n + 63) / 64] a bit per position: it is a site (cleared before every run)
+    uint32_t *sr_rank;             // [(pile_n + 63) / 64] the first site of a word that holds one (its index in pile_site)
+    uint32_t *sr_cnt;              // [A] entries of the alignment; DG_SR_TAKEN: the graph took it
+    unsigned long long *sr_off;    // [A] where its entries begin (k_sr_scan)
+    uint32_t *sr_site;             // [sr_cap] an entry's site (index in pile_site)
+    uint8_t *sr_code;              // [sr_cap] an entry's code: cls | ins << 3
+    uint64_t sr_cap;
+    unsigned long long *sr_top;    // entries of the batch (k_sr_scan; in the status block)
+    uint32_t sr_phase, sr_rounds;  // dagcon_site_reads_opts (rounds: the default filled in)
+    uint8_t *sr_hap;               // [A] 0, 1, 2 (phase on)
+    int8_t *sr_sigma;              // [site_cap] a site's phase
+    uint8_t *sr_kind;              // [site_cap] what decides an entry's sign at the site (dg_sr_kind)
+    int *sr_acc;                   // [site_cap] the sum over a site's entries of a round
+    uint32_t *sr_nz;               // [A] entries with a sign
 };
+#define DG_SR_TAKEN 0x80000000u
 #define DG_POS_BB 0x80000000u
 
 struct __attribute__((aligned(16))) DgEdSeg {

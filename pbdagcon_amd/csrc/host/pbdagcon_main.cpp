@@ -36,6 +36,7 @@
 #include <chrono>
 #include <thread>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include <fcntl.h>
@@ -51,6 +52,7 @@
 #include "windows.h"
 #include "vcf.h"
 #include "pileup.h"
+#include "site_reads.h"
 
 namespace {
 
@@ -69,6 +71,8 @@ struct Opts {
     std::string vcf;                   // --vcf FILE (MODE_RECORDS, whole targets): the edits as VCF with the reads behind each
     bool want_edits() const { return !edits.empty() || !vcf.empty(); }
     DgPileOpts pile;                   // --pileup FILE, --sites FILE [--site-min-frac F] [--site-min-count N] (every mode): what the alignments show per position
+    DgSiteReadOpts sr;                 // --site-reads FILE, --haplotag FILE (whole targets, not -a): which read shows which allele at the sites; a two-way split
+    bool want_pile() const { return pile.on() || sr.on(); }   // (the site reads need the pile-up, whether or not its files are asked for)
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
     int pinned = -1;                   // --pinned 0|1: page-locked blobs (-1: when the input is several batches long)
@@ -83,7 +87,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -185,6 +189,19 @@ void usage(FILE *f) {
             "                      second largest of A C G T N DEL, or min(INS, DEPTH - INS) if that is more, a position is\n"
             "                      listed when m >= N and m >= F x DEPTH.  --site-min-frac F (default 0.2, at most six decimal\n"
             "                      places) and --site-min-count N (default 2) are this build's own choice.  Goes with --pileup\n"
+            "  --site-reads FILE   every kind of input (not with --window, -a, --polish): FILE lists which read shows which allele at\n"
+            "                      each position --sites would list (the same thresholds, --site-min-frac and --site-min-count, with\n"
+            "                      or without --sites), one line per read and site: RNAME POS QNAME ALLELE INS, tab-separated, a\n"
+            "                      target's sites ascending, a site's reads in the order of their records.  ALLELE is one of\n"
+            "                      A C G T N *, * for a deleted base; INS is 1 when the read has inserted bases behind the position\n"
+            "                      (which bases is not compared).  Only the alignments the graph was built from are listed.\n"
+            "                      Listed on the GPU; stdout does not change.  This build's own rule, parity unpinned\n"
+            "  --haplotag FILE     the same inputs: FILE has one line per alignment the graph was built from, RNAME QNAME HAP\n"
+            "                      SITES.  The reads of a target are split in two groups that agree site after site: HAP is 1 or\n"
+            "                      2, or 0 where a read has no informative site, ties, or lies more than 8 read overlaps from the\n"
+            "                      read the split starts at; SITES is the number of the read's informative sites.  A heterozygous\n"
+            "                      site or a collapsed repeat copy splits the reads the same way at every site, a systematic error\n"
+            "                      does not.  The names 1 and 2 hold inside one target only.  This build's own rule, parity unpinned\n"
             "  --fastq             write FASTQ (@id/r0_r1, sequence, +, qualities) instead of FASTA; the same records in the\n"
             "                      same order.  The quality of a base is this build's own definition: a Laplace-smoothed\n"
             "                      fraction of the reads at its position that do not pass through its consensus vertex,\n"
@@ -252,6 +269,14 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--sites") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --sites needs a file name\n"); return 2; }
             o.pile.sites = argv[++i];
+        }
+        else if (a == "--site-reads") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --site-reads needs a file name\n"); return 2; }
+            o.sr.site_reads = argv[++i];
+        }
+        else if (a == "--haplotag") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --haplotag needs a file name\n"); return 2; }
+            o.sr.haplotag = argv[++i];
         }
         else if (a == "--site-min-frac") {
             if (i + 1 >= argc || !dg_parse_ppm(argv[i + 1], &o.pile.min_frac_ppm)) { fprintf(stderr, "PARSE ERROR: --site-min-frac takes a fraction in [0, 1] with at most six decimal places\n"); return 2; }
@@ -326,7 +351,9 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (!o.vcf.empty() && !records) { fprintf(stderr, "PARSE ERROR: --vcf needs --sam, --bam or --paf\n"); return 2; }
     if (!o.vcf.empty() && o.dump) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --dump-parsed (nothing is run, the file would not be written)\n"); return 2; }
     if (!o.vcf.empty() && o.window) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --window (the stitch splits and fuses edits: a fused edit has no single count)\n"); return 2; }
-    if ((o.pile.frac_set || o.pile.count_set) && o.pile.sites.empty()) { fprintf(stderr, "PARSE ERROR: --site-min-frac and --site-min-count need --sites\n"); return 2; }
+    if ((o.pile.frac_set || o.pile.count_set) && o.pile.sites.empty() && !o.sr.on()) { fprintf(stderr, "PARSE ERROR: --site-min-frac and --site-min-count need --sites\n"); return 2; }
+    if (o.sr.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
+    if (o.sr.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (o.pile.on() && o.polish) { fprintf(stderr, "PARSE ERROR: --pileup and --sites do not go with --polish (the backbone changes under the positions)\n"); return 2; }
     if (o.pile.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --pileup and --sites do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
@@ -417,7 +444,9 @@ struct Batch {
     unsigned long long n_edits = 0;
     std::string vcf, contigs;          // --vcf: the batch's lines of that file, and its targets' ##contig lines
     std::string pileup, sites;         // --pileup, --sites: the batch's lines of those files
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); }
+    std::vector<std::string> qnames;   // --site-reads, --haplotag: the records' read names (the input's pages may be gone by the time they are written)
+    std::string site_reads, haplotag;  // and the batch's lines of those files
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); }
 };
 
 FILE *g_edits = nullptr;                                  // --edits FILE, written batch by batch in output order
@@ -428,6 +457,7 @@ FILE *g_vcf = nullptr, *g_vcf_lines = nullptr;
 std::string g_vcf_contigs;
 bool g_vcf_bad = false;
 FILE *g_pileup = nullptr, *g_sites = nullptr;              // --pileup FILE, --sites FILE, written batch by batch in output order
+FILE *g_site_reads = nullptr, *g_haplotag = nullptr;       // --site-reads FILE, --haplotag FILE, the same way
 bool g_pile_bad = false;
 unsigned long long g_over_error = 0, g_over_depth = 0;     // records --max-error / --max-depth left out, all batches (under g_tmu)
 bool g_timing = false;                                    // PBDAGCON_TIMING=1: where the wall time of the run went, on stderr (seconds)
@@ -459,7 +489,11 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
     if (!o.pile.pileup.empty() && !ok(ctx, dagcon_fetch_pileup(ctx, &pu), "pile-up")) return 1;
     dagcon_pileup_sites ps;
     memset(&ps, 0, sizeof ps);
-    if (!o.pile.sites.empty() && !ok(ctx, dagcon_fetch_pileup_sites(ctx, &ps), "pile-up sites")) return 1;
+    if ((!o.pile.sites.empty() || o.sr.on()) && !ok(ctx, dagcon_fetch_pileup_sites(ctx, &ps), "pile-up sites")) return 1;
+    dagcon_site_reads sr;
+    memset(&sr, 0, sizeof sr);
+    if (o.sr.on() && !ok(ctx, dagcon_fetch_site_reads(ctx, &sr), "site reads")) return 1;
+    uint64_t sr_x = 0;                                      // (aln_tgt ascends: one walk over the taken alignments)
     const char *nonconforming = o.mode == MODE_RECORDS ? dg_kind(o.kind).nonconforming : "an alignment leaves the backbone or holds a non-printable byte";
     for (uint32_t g = 0; g < r.n_targets; g++) {
         if (o.verbose)
@@ -473,6 +507,11 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
             const char *tb = o.mode == MODE_RECORDS ? b.t.data() + b.toff[g] : nullptr;
             if (!o.pile.pileup.empty()) dg_pileup_lines(b.pileup, b.ids[g], pu, g, 0, b.tlen[g], 0, tb);
             if (!o.pile.sites.empty()) dg_site_lines(b.sites, b.ids[g], ps, g, 0, b.tlen[g], 0, tb);
+        }
+        if (o.sr.on()) {
+            const uint64_t x0 = sr_x;
+            while (sr_x < sr.n_aln && sr.aln_tgt[sr_x] == g) sr_x++;
+            dg_site_read_lines(o.sr.site_reads.empty() ? nullptr : &b.site_reads, o.sr.haplotag.empty() ? nullptr : &b.haplotag, b.ids[g], ps, sr, g, x0, sr_x, b.qnames);
         }
         if (r.target_status[g] != DAGCON_OK)
             fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(), dg_status_text(r.target_status[g], nonconforming));
@@ -768,9 +807,13 @@ struct Workers {
             fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx));
             dagcon_destroy(ctx); ctx = nullptr;
         }
-        if (rc == DAGCON_OK && o.pile.on()) {
+        if (rc == DAGCON_OK && o.want_pile()) {
             const dagcon_pileup_opts po = {o.pile.min_count, o.pile.min_frac_ppm};
             if ((rc = dagcon_set_pileup(ctx, &po)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
+        }
+        if (rc == DAGCON_OK && o.sr.on()) {
+            const dagcon_site_reads_opts so = {o.sr.phase() ? 1u : 0u, 0u};
+            if ((rc = dagcon_set_site_reads(ctx, &so)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
         }
         dagcon_ctx *actx = ctx;                             // --local --polish: the first alignment on a local context of its own
         if (rc == DAGCON_OK && o.local && o.polish) {       // (aligns only: the support comes from ctx's last round)
@@ -812,6 +855,8 @@ struct Workers {
                     if (g_vcf) { g_vcf_contigs += d->contigs; if (fwrite(d->vcf.data(), 1, d->vcf.size(), g_vcf_lines) != d->vcf.size()) g_vcf_bad = true; }
                     if (g_pileup && fwrite(d->pileup.data(), 1, d->pileup.size(), g_pileup) != d->pileup.size()) g_pile_bad = true;
                     if (g_sites && fwrite(d->sites.data(), 1, d->sites.size(), g_sites) != d->sites.size()) g_pile_bad = true;
+                    if (g_site_reads && fwrite(d->site_reads.data(), 1, d->site_reads.size(), g_site_reads) != d->site_reads.size()) g_pile_bad = true;
+                    if (g_haplotag && fwrite(d->haplotag.data(), 1, d->haplotag.size(), g_haplotag) != d->haplotag.size()) g_pile_bad = true;
                     d->clear();
                     free_list.push_back(d);
                     print_seq++;
@@ -1040,6 +1085,7 @@ struct TextIndexer : Indexer<Rec> {
         b.start.push_back(r.start); b.len.push_back(r.len); b.len2.push_back(r.tl);
         b.off.push_back(bytes); b.off2.push_back(bytes2);
         b.strand.push_back(r.strand);
+        if (o.sr.on()) b.qnames.emplace_back(r.qname, r.qname_len);
         bytes += r.len; bytes2 += r.tl;                     // (-a: the t strings count too)
     }
     // copies the strings of records [r0, r1) into batch b, whose offsets are set already
@@ -1159,6 +1205,7 @@ struct RecordIndexer : Indexer<DgAlnRec> {
         b.start.push_back(r.pos);
         b.off.push_back(bytes); b.len.push_back(r.q_len);
         b.reverse.push_back(r.reverse ? 1 : 0);
+        if (o.sr.on()) b.qnames.emplace_back(r.qname, r.qname_len);
         if (o.kind == DG_REC_CS) { b.cs_len.push_back(r.cs_len); b.tspan.push_back(r.t_span); }
         if (dg_kind_md(o.kind)) { b.md_off.push_back(b.md.size()); b.md_len.push_back(r.md_len); b.md.append(r.md, r.md_len); }
         bytes += dg_blob_bytes(o.kind, r);
@@ -1307,12 +1354,15 @@ int main(int argc, char **argv) {
     // ---- --pileup / --sites: both files are opened before anything runs ----
     if (!o.pile.pileup.empty() && !(g_pileup = fopen(o.pile.pileup.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.pile.pileup.c_str()); return 1; }
     if (!o.pile.sites.empty() && !(g_sites = fopen(o.pile.sites.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.pile.sites.c_str()); return 1; }
+    if (!o.sr.site_reads.empty() && !(g_site_reads = fopen(o.sr.site_reads.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.sr.site_reads.c_str()); return 1; }
+    if (!o.sr.haplotag.empty() && !(g_haplotag = fopen(o.sr.haplotag.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.sr.haplotag.c_str()); return 1; }
     auto close_pile = [&](int status) {
-        for (FILE **f : {&g_pileup, &g_sites}) {
-            if (!*f) continue;
-            const bool bad = fclose(*f) != 0 || g_pile_bad;
-            if (bad) { fprintf(stderr, "pbdagcon: error writing %s\n", (f == &g_pileup ? o.pile.pileup : o.pile.sites).c_str()); status = 1; }
-            *f = nullptr;
+        const std::pair<FILE **, const std::string *> files[] = {{&g_pileup, &o.pile.pileup}, {&g_sites, &o.pile.sites}, {&g_site_reads, &o.sr.site_reads}, {&g_haplotag, &o.sr.haplotag}};
+        for (const auto &f : files) {
+            if (!*f.first) continue;
+            const bool bad = fclose(*f.first) != 0 || g_pile_bad;
+            if (bad) { fprintf(stderr, "pbdagcon: error writing %s\n", f.second->c_str()); status = 1; }
+            *f.first = nullptr;
         }
         return status;
     };
@@ -1356,7 +1406,7 @@ int main(int argc, char **argv) {
         if (fclose(g_edits) != 0) { fprintf(stderr, "pbdagcon: error writing %s\n", o.edits.c_str()); status = 1; fast_exit = false; }
         if (o.verbose) fprintf(stderr, "pbdagcon: %llu edits written to %s\n", g_n_edits, o.edits.c_str());
     }
-    if (g_pileup || g_sites) {
+    if (g_pileup || g_sites || g_site_reads || g_haplotag) {
         const int ps = close_pile(0);
         if (ps) { status = ps; fast_exit = false; }
     }

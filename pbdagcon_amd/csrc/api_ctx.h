@@ -112,13 +112,26 @@ struct StatBlock {
     DevBuf dev;
     PinBuf host;
     size_t o_tfail = 0, o_cns_len = 0, o_n_seg = 0, o_cns_off = 0, o_seg_first = 0;     // (DgStatus at 0)
-    size_t o_ed_top = 0;                            // edits of the batch, behind seg_first (a batch with edits on only; 0: none)
-    size_t o_site_top = 0;                          // sites of the batch, behind that (a batch with the pile-up on only; 0: none)
-    size_t o_sr_top = 0;                            // entries of the batch, the second word of the same 16 bytes (dagcon_set_site_reads; 0: none)
-    size_t zero_bytes = 0, bytes = 0;
+    size_t zero_bytes = 0, bytes = 0;               // (behind seg_first: the totals of the growing arenas, GrowArena::o_top)
     template <typename X> X *d(size_t off) const { return reinterpret_cast<X *>(static_cast<char *>(dev.p) + off); }
     template <typename X> const X *h(size_t off) const { return reinterpret_cast<const X *>(host.as<char>() + off); }
 };
+
+// An arena of an optional output whose size only a run tells: the run's scan (k_scan.hip.h) stores the total in a word of
+// the status block and raises `ovf` when it exceeds `cap`; dagcon_fetch then sets cap = total + 1024 and runs the batch
+// again.  Ctx::growing() lists them; ensure_stat (the words' layout), fill_params, the re-run and arena_total walk that list.
+struct GrowArena {
+    const char *what;                               // what it holds, for messages
+    uint32_t ovf;                                   // DG_E_*_OVF
+    bool own_word;                                  // false: its word is the second of the 16 bytes of the arena in front of it
+    unsigned long long *DgParams::*p_top;           // the kernels' names for the word and the capacity
+    uint64_t DgParams::*p_cap;
+    uint64_t cap = 0;                               // entries (first guess at the upload; DAGCON_EDITS_CAP: the edits')
+    size_t o_top = 0;                               // the word's offset in the status block of this batch; 0: the output is off
+};
+struct GrowRef { GrowArena *g; bool on; };          // an arena, and whether the batch on the device was uploaded with its output on
+
+enum class Fresh { FETCH, RUN, UPLOAD };            // what is new when results stop being valid (Ctx::drop_results)
 
 struct Ctx {
     dagcon_opts opts;
@@ -191,9 +204,12 @@ struct Ctx {
     bool sr_on = false, sr_batch = false;
     dagcon_site_reads_opts sr_opts = {0u, 0u}, sr_batch_opts = {0u, 0u};
     std::vector<uint64_t> h_aln_src;                // [A]
-    uint64_t sr_cap = 0;
-    uint64_t site_cap = 0;
-    uint64_t ed_cap = 0;
+    // the growing arenas: run.ed_out (and run.evid beside it), run.pile_site, run.sr_site / sr_code.  The status block
+    // holds 16 bytes for the edits' total, then 16 for the sites', whose second word is the entries'
+    GrowArena ed_arena{"edits", DG_E_ED_OVF, true, &DgParams::ed_top, &DgParams::ed_cap};
+    GrowArena site_arena{"sites", DG_E_SITE_OVF, true, &DgParams::site_top, &DgParams::site_cap};
+    GrowArena sr_arena{"site entries", DG_E_SR_OVF, false, &DgParams::sr_top, &DgParams::sr_cap};
+    std::array<GrowRef, 3> growing() { return {{{&ed_arena, ed_batch}, {&site_arena, pile_batch}, {&sr_arena, sr_batch}}}; }
     long ed_cap_env = 0;                            // DAGCON_EDITS_CAP (tests): first size of the edit arena, so that the re-run is met
 
     uint64_t norm_cap = 0, node_cap = 0, pool_cap = 0, cns_cap = 0, seg_cap = 0;
@@ -241,6 +257,17 @@ struct Ctx {
     std::vector<uint32_t> s_pos;
     std::vector<uint16_t> s_counts;
     bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
+
+    // The one place where results stop being valid.  A fetch drops what the fetch before it left; a run drops that and
+    // `fetched`; an upload drops that and `uploaded`, `ran` and the rebuilt targets.  One exception to upload > run > fetch:
+    // a run alone leaves sup_valid and pos_valid -- r_sup and r_pos are host copies that still hold what the last fetch
+    // brought, and stay readable until the next fetch replaces them.  (The *_batch latches are the upload's own business.)
+    void drop_results(const Fresh lv) {
+        ed_valid = pos_pending = evid_valid = pile_valid = pile_fetched = sr_valid = sr_fetched = false;
+        if (lv != Fresh::RUN) sup_valid = pos_valid = false;
+        if (lv != Fresh::FETCH) fetched = false;
+        if (lv == Fresh::UPLOAD) uploaded = ran = md_valid = md_fetched = false;
+    }
 
     // debug dump storage
     std::vector<uint8_t> g_base, g_deleted, g_backbone;

@@ -44,13 +44,8 @@ class RecordSource {
 // reset: what any upload does to the context's state first
 Ctx *intake_reset(dagcon_ctx *ctx) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    c->uploaded = c->ran = c->fetched = false;
-    c->sup_valid = c->pos_valid = false;
-    c->ed_batch = c->ed_valid = c->pos_pending = false;
-    c->evid_batch = c->evid_valid = false;
-    c->pile_batch = c->pile_valid = c->pile_fetched = false;
-    c->sr_batch = c->sr_valid = c->sr_fetched = false;
-    c->md_valid = c->md_fetched = false;
+    c->drop_results(Fresh::UPLOAD);
+    c->ed_batch = c->evid_batch = c->pile_batch = c->sr_batch = false;     // (upload_impl and edits_arm latch them)
     return c;
 }
 
@@ -490,7 +485,7 @@ int edits_arm(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
     for (uint32_t t = 0; t < T; t++) c->h_ed_tbase[t] = wn ? b->t_off[wn->target[t]] + wn->begin[t] : b->t_off[t];
     c->ed_batch = true;
     c->evid_batch = c->evid_on;
-    c->ed_cap = c->ed_cap_env > 0 ? (uint64_t)c->ed_cap_env : std::max<uint64_t>(c->ed_cap, c->sum_bb / 8 + 1024);
+    c->ed_arena.cap = c->ed_cap_env > 0 ? (uint64_t)c->ed_cap_env : std::max<uint64_t>(c->ed_arena.cap, c->sum_bb / 8 + 1024);
     int r;
     UPLOAD(c, c->in.ed_tbase, c->h_ed_tbase);
     if ((r = ensure_stat(c, T))) return r;

@@ -71,12 +71,13 @@ int ensure_stat(Ctx *c, uint32_t T) {
     b.o_cns_off = b.zero_bytes;
     b.o_seg_first = b.o_cns_off + up16((size_t)T * 8);
     b.bytes = b.o_seg_first + up16((size_t)T * 8);
-    b.o_ed_top = 0;
-    if (c->ed_batch) { b.o_ed_top = b.bytes; b.bytes += 16; }
-    b.o_site_top = 0;
-    b.o_sr_top = 0;
-    if (c->pile_batch) { b.o_site_top = b.bytes; b.bytes += 16; }
-    if (c->sr_batch) b.o_sr_top = b.o_site_top + 8;
+    // the totals of the growing arenas whose output is on: 16 bytes each, or the second word of the arena's in front
+    size_t prev = 0;
+    for (const GrowRef &r : c->growing()) {
+        r.g->o_top = !r.on ? 0 : r.g->own_word ? b.bytes : prev + 8;
+        if (r.on && r.g->own_word) b.bytes += 16;
+        prev = r.g->o_top;
+    }
     ENSURE(c, b.dev, b.bytes);
     return b.host.reserve(c, b.bytes);
 }
@@ -122,24 +123,24 @@ int ensure_arenas(Ctx *c) {
     }
     if (c->ed_batch) {
         ENSURE(c, c->run.ed_seg, c->seg_cap * sizeof(DgEdSeg));
-        ENSURE(c, c->run.ed_out, c->ed_cap * sizeof(DgEdit));
-        if (c->evid_batch) ENSURE(c, c->run.evid, c->ed_cap * sizeof(DgEvid));
+        ENSURE(c, c->run.ed_out, c->ed_arena.cap * sizeof(DgEdit));
+        if (c->evid_batch) ENSURE(c, c->run.evid, c->ed_arena.cap * sizeof(DgEvid));
     }
     if (c->pile_batch) {
         const uint64_t pn = c->h_pile_begin.back();
         ENSURE(c, c->run.pile, pn * 16);
         ENSURE(c, c->run.pile_tile, (pn + DG_PILE_TILE - 1) / DG_PILE_TILE * 8);
-        ENSURE(c, c->run.pile_site, c->site_cap * sizeof(DgSite));
+        ENSURE(c, c->run.pile_site, c->site_arena.cap * sizeof(DgSite));
     }
     if (c->sr_batch) {
         const uint64_t words = (c->h_pile_begin.back() + 63) / 64;
         const size_t A4 = (size_t)c->A * 4;
         ENSURE(c, c->run.sr_bits, words * 8); ENSURE(c, c->run.sr_rank, words * 4);
         ENSURE(c, c->run.sr_cnt, A4); ENSURE(c, c->run.sr_off, 2 * A4);
-        ENSURE(c, c->run.sr_site, c->sr_cap * 4); ENSURE(c, c->run.sr_code, c->sr_cap);
+        ENSURE(c, c->run.sr_site, c->sr_arena.cap * 4); ENSURE(c, c->run.sr_code, c->sr_arena.cap);
         if (c->sr_batch_opts.phase) {
             ENSURE(c, c->run.sr_hap, (size_t)c->A); ENSURE(c, c->run.sr_nz, A4);
-            ENSURE(c, c->run.sr_sigma, c->site_cap); ENSURE(c, c->run.sr_kind, c->site_cap); ENSURE(c, c->run.sr_acc, c->site_cap * 4);
+            ENSURE(c, c->run.sr_sigma, c->site_arena.cap); ENSURE(c, c->run.sr_kind, c->site_arena.cap); ENSURE(c, c->run.sr_acc, c->site_arena.cap * 4);
         }
     }
     ENSURE(c, c->run.seg, 2 * seg_stride(c) * 4);
@@ -222,24 +223,23 @@ void fill_params(Ctx *c, DgParams &p) {
     if (c->opts.flags & DAGCON_FLAG_BASE_POS) {
         p.pos_tmp = c->run.pos_tmp.as<uint32_t>(); p.pos_tmp0 = c->run.pos_tmp0.as<uint32_t>(); p.pos_out = c->run.pos.as<uint32_t>();
     }
+    for (const GrowRef &r : c->growing())                   // ed_top / ed_cap, site_top / site_cap, sr_top / sr_cap
+        if (r.on) { p.*(r.g->p_top) = c->sb.d<unsigned long long>(r.g->o_top); p.*(r.g->p_cap) = r.g->cap; }
     if (c->ed_batch) {
-        p.ed_seg = c->run.ed_seg.as<DgEdSeg>(); p.ed_out = c->run.ed_out.as<DgEdit>(); p.ed_cap = c->ed_cap;
-        p.ed_top = c->sb.d<unsigned long long>(c->sb.o_ed_top);
+        p.ed_seg = c->run.ed_seg.as<DgEdSeg>(); p.ed_out = c->run.ed_out.as<DgEdit>();
         p.ed_t = c->cg.t.as<const uint8_t>(); p.ed_tbase = c->in.ed_tbase.as<const uint64_t>();
         if (c->evid_batch) p.evid = c->run.evid.as<DgEvid>();
     }
     if (c->pile_batch) {
         p.pile = c->run.pile.as<uint32_t>(); p.pile_begin = c->in.pile_begin.as<const uint64_t>(); p.pile_n = c->h_pile_begin.back();
         p.pile_tile = c->run.pile_tile.as<unsigned long long>();
-        p.pile_site = c->run.pile_site.as<DgSite>(); p.site_cap = c->site_cap;
-        p.site_top = c->sb.d<unsigned long long>(c->sb.o_site_top);
+        p.pile_site = c->run.pile_site.as<DgSite>();
         p.pile_min_count = c->pile_batch_opts.min_count; p.pile_min_ppm = c->pile_batch_opts.min_frac_ppm;
     }
     if (c->sr_batch) {
         p.sr_bits = c->run.sr_bits.as<unsigned long long>(); p.sr_rank = c->run.sr_rank.as<uint32_t>();
         p.sr_cnt = c->run.sr_cnt.as<uint32_t>(); p.sr_off = c->run.sr_off.as<unsigned long long>();
-        p.sr_site = c->run.sr_site.as<uint32_t>(); p.sr_code = c->run.sr_code.as<uint8_t>(); p.sr_cap = c->sr_cap;
-        p.sr_top = c->sb.d<unsigned long long>(c->sb.o_sr_top);
+        p.sr_site = c->run.sr_site.as<uint32_t>(); p.sr_code = c->run.sr_code.as<uint8_t>();
         p.sr_phase = c->sr_batch_opts.phase; p.sr_rounds = c->sr_batch_opts.rounds ? c->sr_batch_opts.rounds : 8u;
         if (p.sr_phase) {
             p.sr_hap = c->run.sr_hap.as<uint8_t>(); p.sr_nz = c->run.sr_nz.as<uint32_t>();
@@ -478,18 +478,13 @@ void dagcon_destroy(dagcon_ctx *ctx) { delete reinterpret_cast<Ctx *>(ctx); }
 static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q, const void *dev_t) {
     if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    c->uploaded = c->ran = c->fetched = false;
-    c->sup_valid = c->pos_valid = false;
-    c->ed_batch = c->ed_valid = c->pos_pending = false;     // (a record upload with edits on says so after the hand-over)
-    c->evid_batch = c->evid_valid = false;
+    c->drop_results(Fresh::UPLOAD);
+    c->ed_batch = c->evid_batch = false;                    // (a record upload with edits on says so after the hand-over)
     c->pile_batch = c->pile_on; c->pile_batch_opts = c->pile_opts;
-    c->pile_valid = c->pile_fetched = false;
     c->sr_batch = c->sr_on && c->pile_on; c->sr_batch_opts = c->sr_opts;
-    c->sr_valid = c->sr_fetched = false;
     c->h_aln_src.clear();
     c->h_cig_bad.clear();
     c->rs_valid = false;
-    c->md_valid = c->md_fetched = false;
     c->wide_cells = false;                             // (one batch with a very long insertion run does not slow the ones after it)
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->aln_begin)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/aln_begin is NULL");
@@ -649,12 +644,12 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
         for (uint32_t t = 0; t < T; t++) c->h_pile_begin[t + 1] = c->h_pile_begin[t] + b->tlen[t];
         UPLOAD(c, c->in.pile_begin, c->h_pile_begin);
         // first guess, as for the edits; a run with more sites records their number and is repeated (DG_E_SITE_OVF)
-        c->site_cap = std::max<uint64_t>(c->site_cap, c->h_pile_begin[T] / 8 + 1024);
+        c->site_arena.cap = std::max<uint64_t>(c->site_arena.cap, c->h_pile_begin[T] / 8 + 1024);
         if (c->sr_batch) {
             // a site index is 32 bits wide in an entry
             if (c->h_pile_begin[T] > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "dagcon_set_site_reads: more than 2^32 - 16 target positions in a batch");
             // first guess: one column in 64 an entry; a run with more records their number and is repeated (DG_E_SR_OVF)
-            c->sr_cap = std::max<uint64_t>(c->sr_cap, c->sum_len / 64 + 4096);
+            c->sr_arena.cap = std::max<uint64_t>(c->sr_arena.cap, c->sum_len / 64 + 4096);
         }
     }
     ENSURE(c, c->run.ckpt, c->n_ckpt * 4);
@@ -702,11 +697,8 @@ int dagcon_run(dagcon_ctx *ctx) {
     HIPCHK(c, hipSetDevice(c->device));
     int r = launch_all(c);
     if (r != DAGCON_OK) return r;
-    c->ran = true; c->fetched = false;
-    c->ed_valid = c->pos_pending = false;
-    c->evid_valid = false;
-    c->pile_valid = c->pile_fetched = false;
-    c->sr_valid = c->sr_fetched = false;
+    c->drop_results(Fresh::RUN);
+    c->ran = true;
     if (const char *e = getenv("DAGCON_DUMP")) return dump_target(c, e);
     return DAGCON_OK;
 }
@@ -743,15 +735,13 @@ static int read_status(Ctx *c) {
     return DAGCON_OK;
 }
 
-int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
-    if (!ctx || !res) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->ran) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch before dagcon_run");
-    HIPCHK(c, hipSetDevice(c->device));
-    int r;
+// ---- dagcon_fetch: status and re-runs, outcomes, sizes, the second round of copies, two unpack passes ----
+
+// round 1, until no batch-level flag is left: the whole status block in one copy -- the status, and with it everything whose
+// size the host knows; an arena that was too small is grown to what the device asked for and the batch runs again
+static int fetch_status(Ctx *c) {
     const StatBlock &sb = c->sb;
     for (int attempt = 0;; attempt++) {
-        // round 1: the whole status block in one copy -- the status, and with it everything whose size the host knows
         HIPCHK(c, d2h(c, sb.host.p, sb.dev.p, sb.bytes));
         memcpy(&c->h_st, sb.host.p, sizeof(DgStatus));
         const uint32_t f = c->h_st.err_flags;
@@ -767,22 +757,22 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         if (f & DG_E_LIST_OVF) c->worklist_cap *= 4;
         if (f & DG_E_LOG_OVF) c->sh_log *= 2;
         if (f & DG_E_RUN_WIDE) c->wide_cells = true;       // (until the next upload)
-        if ((f & DG_E_ED_OVF) && sb.o_ed_top) c->ed_cap = *sb.h<uint64_t>(sb.o_ed_top) + 1024;
-        if ((f & DG_E_SITE_OVF) && sb.o_site_top) c->site_cap = *sb.h<uint64_t>(sb.o_site_top) + 1024;
-        if ((f & DG_E_SR_OVF) && sb.o_sr_top) c->sr_cap = *sb.h<uint64_t>(sb.o_sr_top) + 1024;
+        for (const GrowRef &r : c->growing())
+            if ((f & r.g->ovf) && r.g->o_top) r.g->cap = *sb.h<uint64_t>(r.g->o_top) + 1024;
         if (f & DG_E_OUT_OVF) {
             c->cns_cap = std::max<uint64_t>(c->cns_cap, c->h_st.cns_top + 1024);
             c->seg_cap = std::max<uint64_t>(c->seg_cap, c->h_st.seg_top + 1024);
         }
         c->tm.reruns++;
-        if ((r = launch_all(c))) return r;
+        if (int r = launch_all(c)) return r;
     }
-    if ((r = read_timings(c))) return r;
+    return read_timings(c);
+}
 
+// per-target outcome (ABI 2): a failure is confined to its target.  Returns the number of failed targets
+static uint32_t fetch_outcomes(Ctx *c) {
     const uint32_t T = c->T;
-    // per-target outcome (ABI 2): a failure is confined to its target
-    const uint32_t *m_tfail = sb.h<uint32_t>(sb.o_tfail), *m_n_seg = sb.h<uint32_t>(sb.o_n_seg);
-    const uint64_t *m_cns_off = sb.h<uint64_t>(sb.o_cns_off), *m_seg_first = sb.h<uint64_t>(sb.o_seg_first);
+    const uint32_t *m_tfail = c->sb.h<uint32_t>(c->sb.o_tfail);
     c->r_status.assign(T, DAGCON_OK);
     uint32_t n_failed = 0;
     c->err.clear();
@@ -805,67 +795,100 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
         c->r_status[t] = DAGCON_ERR_NONCONFORMING;
         if (!n_failed++) c->err = c->cig_err;
     }
-    const uint64_t nseg = c->h_st.seg_top, nb = c->h_st.cns_top;
-    if (2 * nseg * 4 > c->r_seg.cap || nseg > c->seg_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu segments in an arena of %llu", (unsigned long long)nseg, (unsigned long long)c->seg_cap);
-    if ((r = c->r_blob.reserve(c, nb + 1))) return r;
-    char *const m_blob = c->r_blob.as<char>();
-    m_blob[nb] = 0;
-    const bool full = !(c->opts.flags & (DAGCON_FLAG_STOP_AFTER_BUILD | DAGCON_FLAG_STOP_AFTER_MERGE));
-    const bool want_sup = full && (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT), want_pos = full && (c->opts.flags & DAGCON_FLAG_BASE_POS);
+    return n_failed;
+}
+
+// the total of a growing arena in the status block's mirror; ran false: its scan did not run in this batch
+static int arena_total(Ctx *c, const GrowArena &g, const bool ran, uint64_t &n) {
+    n = ran && g.o_top ? *c->sb.h<uint64_t>(g.o_top) : 0;
+    if (n > g.cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu %s in an arena of %llu", (unsigned long long)n, g.what, (unsigned long long)g.cap);
+    return DAGCON_OK;
+}
+
+// what this fetch brings back and how much of it: decided once from the status block, read by the steps behind it
+struct FetchPlan {
+    bool full, want_sup, want_pos, lazy_pos, want_ed, want_evid, want_pile;
+    uint64_t nseg, nb, n_ed, n_site;
+    size_t ed_seg_bytes, ed_bytes, evid_bytes;      // r_ed: the DgEdSeg records, then the DgEdit records, then the DgEvid records (all 8-byte aligned)
+};
+
+// the sizes, each checked against its arena; the results of the fetch before stop being valid; room for the copies
+static int fetch_plan(Ctx *c, FetchPlan &f) {
+    int r;
+    const uint32_t T = c->T;
+    f.nseg = c->h_st.seg_top; f.nb = c->h_st.cns_top;
+    if (2 * f.nseg * 4 > c->r_seg.cap || f.nseg > c->seg_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu segments in an arena of %llu", (unsigned long long)f.nseg, (unsigned long long)c->seg_cap);
+    if ((r = c->r_blob.reserve(c, f.nb + 1))) return r;
+    c->r_blob.as<char>()[f.nb] = 0;
+    f.full = !(c->opts.flags & (DAGCON_FLAG_STOP_AFTER_BUILD | DAGCON_FLAG_STOP_AFTER_MERGE));
+    f.want_sup = f.full && (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT); f.want_pos = f.full && (c->opts.flags & DAGCON_FLAG_BASE_POS);
     // edits on: the edits come instead of the positions, which stay on the device for dagcon_fetch_positions to ask for
-    const bool want_ed = full && c->ed_batch, lazy_pos = want_pos && want_ed;
-    const uint64_t n_ed = want_ed && T ? *sb.h<uint64_t>(sb.o_ed_top) : 0;
-    if (n_ed > c->ed_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu edits in an arena of %llu", (unsigned long long)n_ed, (unsigned long long)c->ed_cap);
-    c->sup_valid = c->pos_valid = false;
-    c->ed_valid = c->pos_pending = false;
-    c->evid_valid = false;
-    c->pile_valid = c->pile_fetched = false;
-    c->sr_valid = c->sr_fetched = false;
-    c->r_nb = nb;
+    f.want_ed = f.full && c->ed_batch; f.lazy_pos = f.want_pos && f.want_ed;
+    if ((r = arena_total(c, c->ed_arena, f.want_ed && T, f.n_ed))) return r;
+    c->drop_results(Fresh::FETCH);
+    c->r_nb = f.nb;
     // the pile-up's sites come back here; its counts, 16 bytes a position, stay on the device until dagcon_fetch_pileup
-    const bool want_pile = full && c->pile_batch;
-    const uint64_t n_site = want_pile && T && c->h_pile_begin.back() ? *sb.h<uint64_t>(sb.o_site_top) : 0;
-    if (n_site > c->site_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu sites in an arena of %llu", (unsigned long long)n_site, (unsigned long long)c->site_cap);
-    if (want_pile && (r = c->r_site.reserve(c, (size_t)n_site * sizeof(DgSite) + 1))) return r;
-    const bool want_evid = want_ed && c->evid_batch;
-    const size_t ed_seg_bytes = (size_t)nseg * sizeof(DgEdSeg), ed_bytes = ed_seg_bytes + (size_t)n_ed * sizeof(DgEdit);
-    const size_t evid_bytes = want_evid ? (size_t)n_ed * sizeof(DgEvid) : 0;        // (behind the edit records; both 8-byte aligned)
-    if (want_ed && (r = c->r_ed.reserve(c, ed_bytes + evid_bytes + 1))) return r;
-    if (want_sup && (r = c->r_sup.reserve(c, 2 * (size_t)(nb + 1) * 2))) return r;     // (two halves of nb + 1 entries)
-    char *const m_edb = c->r_ed.as<char>();
-    uint16_t *const m_sup = c->r_sup.as<uint16_t>();
-    if (want_pos && !lazy_pos) c->r_pos.resize(nb + 1);
-    // round 2: what the status sizes -- the segments' ranges (the first seg_top entries of either array), the blob, the
-    // support (weights then depths: the device keeps them apart, no host pass over them) and the positions -- enqueued
-    // together, one wait
+    f.want_pile = f.full && c->pile_batch;
+    if ((r = arena_total(c, c->site_arena, f.want_pile && T && c->h_pile_begin.back(), f.n_site))) return r;
+    if (f.want_pile && (r = c->r_site.reserve(c, (size_t)f.n_site * sizeof(DgSite) + 1))) return r;
+    f.want_evid = f.want_ed && c->evid_batch;
+    f.ed_seg_bytes = (size_t)f.nseg * sizeof(DgEdSeg); f.ed_bytes = f.ed_seg_bytes + (size_t)f.n_ed * sizeof(DgEdit);
+    f.evid_bytes = f.want_evid ? (size_t)f.n_ed * sizeof(DgEvid) : 0;
+    if (f.want_ed && (r = c->r_ed.reserve(c, f.ed_bytes + f.evid_bytes + 1))) return r;
+    if (f.want_sup && (r = c->r_sup.reserve(c, 2 * (size_t)(f.nb + 1) * 2))) return r;     // (two halves of nb + 1 entries)
+    if (f.want_pos && !f.lazy_pos) c->r_pos.resize(f.nb + 1);
+    return DAGCON_OK;
+}
+
+// round 2: what the status sizes -- the segments' ranges (the first seg_top entries of either array), the blob, the
+// support (weights then depths: the device keeps them apart, no host pass over them), the positions, the edit records
+// and the sites -- enqueued together, one wait
+static int fetch_copies(Ctx *c, const FetchPlan &f) {
+    const uint32_t T = c->T;
+    const uint64_t nseg = f.nseg, nb = f.nb;
     int32_t *m_r0 = c->r_seg.as<int32_t>(), *m_r1 = m_r0 + nseg;
+    uint16_t *const m_sup = c->r_sup.as<uint16_t>();
+    char *const m_edb = c->r_ed.as<char>();
     bool queued = false;
-    if (T && full && nseg) {
+    if (T && f.full && nseg) {
         HIPCHK(c, hipMemcpyAsync(m_r0, c->run.seg.p, nseg * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(m_r1, c->run.seg.as<const int32_t>() + seg_stride(c), nseg * 4, hipMemcpyDeviceToHost, c->stream));
         queued = true;
     }
-    if (T && full && nb) { HIPCHK(c, hipMemcpyAsync(m_blob, c->run.cns.p, nb, hipMemcpyDeviceToHost, c->stream)); queued = true; }
-    if (want_sup && nb) {
+    if (T && f.full && nb) { HIPCHK(c, hipMemcpyAsync(c->r_blob.p, c->run.cns.p, nb, hipMemcpyDeviceToHost, c->stream)); queued = true; }
+    if (f.want_sup && nb) {
         HIPCHK(c, hipMemcpyAsync(m_sup, c->run.sup.p, nb * 2, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(m_sup + nb, c->run.sup.as<const uint16_t>() + c->cns_cap, nb * 2, hipMemcpyDeviceToHost, c->stream));
         queued = true;
     }
-    if (want_pos && !lazy_pos && nb) { HIPCHK(c, hipMemcpyAsync(c->r_pos.data(), c->run.pos.p, nb * 4, hipMemcpyDeviceToHost, c->stream)); queued = true; }
-    if (want_ed && T && nseg) {
-        HIPCHK(c, hipMemcpyAsync(m_edb, c->run.ed_seg.p, ed_seg_bytes, hipMemcpyDeviceToHost, c->stream));
-        if (n_ed) HIPCHK(c, hipMemcpyAsync(m_edb + ed_seg_bytes, c->run.ed_out.p, (size_t)n_ed * sizeof(DgEdit), hipMemcpyDeviceToHost, c->stream));
-        if (evid_bytes) HIPCHK(c, hipMemcpyAsync(m_edb + ed_bytes, c->run.evid.p, evid_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (f.want_pos && !f.lazy_pos && nb) { HIPCHK(c, hipMemcpyAsync(c->r_pos.data(), c->run.pos.p, nb * 4, hipMemcpyDeviceToHost, c->stream)); queued = true; }
+    if (f.want_ed && T && nseg) {
+        HIPCHK(c, hipMemcpyAsync(m_edb, c->run.ed_seg.p, f.ed_seg_bytes, hipMemcpyDeviceToHost, c->stream));
+        if (f.n_ed) HIPCHK(c, hipMemcpyAsync(m_edb + f.ed_seg_bytes, c->run.ed_out.p, (size_t)f.n_ed * sizeof(DgEdit), hipMemcpyDeviceToHost, c->stream));
+        if (f.evid_bytes) HIPCHK(c, hipMemcpyAsync(m_edb + f.ed_bytes, c->run.evid.p, f.evid_bytes, hipMemcpyDeviceToHost, c->stream));
         queued = true;
     }
-    if (n_site) { HIPCHK(c, hipMemcpyAsync(c->r_site.p, c->run.pile_site.p, (size_t)n_site * sizeof(DgSite), hipMemcpyDeviceToHost, c->stream)); queued = true; }
+    if (f.n_site) { HIPCHK(c, hipMemcpyAsync(c->r_site.p, c->run.pile_site.p, (size_t)f.n_site * sizeof(DgSite), hipMemcpyDeviceToHost, c->stream)); queued = true; }
     if (queued) HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (want_sup) { c->r_sup_n = nb; c->sup_valid = true; }
-    if (want_pos && !lazy_pos) c->pos_valid = true;
-    c->pos_pending = lazy_pos;
+    if (f.want_sup) { c->r_sup_n = nb; c->sup_valid = true; }
+    if (f.want_pos && !f.lazy_pos) c->pos_valid = true;
+    c->pos_pending = f.lazy_pos;
+    return DAGCON_OK;
+}
+
+// the segments of every target that came through, in the host's order; with them each segment's edit record, its edits
+// and their support, from the device's order into the host's.  bases: the consensus bases of the batch
+static int unpack_segments(Ctx *c, const FetchPlan &f, uint64_t &bases) {
+    const StatBlock &sb = c->sb;
+    const uint32_t T = c->T;
+    const uint32_t *m_tfail = sb.h<uint32_t>(sb.o_tfail), *m_n_seg = sb.h<uint32_t>(sb.o_n_seg);
+    const uint64_t *m_cns_off = sb.h<uint64_t>(sb.o_cns_off), *m_seg_first = sb.h<uint64_t>(sb.o_seg_first);
+    const int32_t *m_r0 = c->r_seg.as<int32_t>(), *m_r1 = m_r0 + f.nseg;
+    const char *const m_edb = c->r_ed.as<char>();
     const DgEdSeg *m_es = reinterpret_cast<const DgEdSeg *>(m_edb);
-    const DgEdit *m_ed = reinterpret_cast<const DgEdit *>(m_edb + ed_seg_bytes);
-    const DgEvid *m_evid = reinterpret_cast<const DgEvid *>(m_edb + ed_bytes);
+    const DgEdit *m_ed = reinterpret_cast<const DgEdit *>(m_edb + f.ed_seg_bytes);
+    const DgEvid *m_evid = reinterpret_cast<const DgEvid *>(m_edb + f.ed_bytes);
+    const bool want_ed = f.want_ed, want_evid = f.want_evid;
     if (want_evid) { c->v_begin.clear(); c->v_end.clear(); c->v_span.clear(); c->v_alt.clear(); c->v_ref.clear(); }
     if (want_ed) {
         c->e_t0.clear(); c->e_t1.clear(); c->e_begin.clear();
@@ -873,10 +896,10 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     }
     c->r_seg_begin.assign(T + 1, 0);
     c->r_range0.clear(); c->r_range1.clear(); c->r_seq_off.clear(); c->r_seq_len.clear();
-    uint64_t bases = 0;
+    bases = 0;
     for (uint32_t t = 0; t < T; t++) {
         c->r_seg_begin[t] = c->r_range0.size();
-        if (!full || !c->h_tactive[t] || m_tfail[t]) continue;
+        if (!f.full || !c->h_tactive[t] || m_tfail[t]) continue;
         for (uint32_t i = 0; i < m_n_seg[t]; i++) {
             const uint64_t s = m_seg_first[t] + i;
             const int32_t r0 = m_r0[s], r1 = m_r1[s];
@@ -884,69 +907,87 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
             c->r_seq_off.push_back(m_cns_off[t] + (uint64_t)r0);
             c->r_seq_len.push_back((uint32_t)(r1 - r0));
             bases += (uint64_t)(r1 - r0);
-            if (want_ed) {
-                // the segment's record and its edits, from the device's order into the host's
-                const DgEdSeg &es = m_es[s];
-                if (es.tgt != t || es.off > n_ed || es.cnt > n_ed - es.off)
-                    return fail(c, DAGCON_ERR_INTERNAL, "k_ed_scan: segment %llu of target %u has edits [%llu, + %u) of %llu, target %u",
-                                (unsigned long long)s, t, (unsigned long long)es.off, es.cnt, (unsigned long long)n_ed, es.tgt);
-                c->e_t0.push_back(es.t0); c->e_t1.push_back(es.t1); c->e_begin.push_back(c->e_tpos.size());
-                for (uint32_t k = 0; k < es.cnt; k++) {
-                    const DgEdit &e = m_ed[es.off + k];
-                    c->e_tpos.push_back(e.t_pos); c->e_tlen.push_back(e.t_len); c->e_coff.push_back(e.c_off); c->e_clen.push_back(e.c_len);
-                    if (want_evid) {
-                        const DgEvid &v = m_evid[es.off + k];
-                        c->v_begin.push_back(v.gL); c->v_end.push_back(v.gR);
-                        c->v_span.push_back(v.span); c->v_alt.push_back(v.alt); c->v_ref.push_back(v.ref);
-                    }
+            if (!want_ed) continue;
+            const DgEdSeg &es = m_es[s];
+            if (es.tgt != t || es.off > f.n_ed || es.cnt > f.n_ed - es.off)
+                return fail(c, DAGCON_ERR_INTERNAL, "k_ed_scan: segment %llu of target %u has edits [%llu, + %u) of %llu, target %u",
+                            (unsigned long long)s, t, (unsigned long long)es.off, es.cnt, (unsigned long long)f.n_ed, es.tgt);
+            c->e_t0.push_back(es.t0); c->e_t1.push_back(es.t1); c->e_begin.push_back(c->e_tpos.size());
+            for (uint32_t k = 0; k < es.cnt; k++) {
+                const DgEdit &e = m_ed[es.off + k];
+                c->e_tpos.push_back(e.t_pos); c->e_tlen.push_back(e.t_len); c->e_coff.push_back(e.c_off); c->e_clen.push_back(e.c_len);
+                if (want_evid) {
+                    const DgEvid &v = m_evid[es.off + k];
+                    c->v_begin.push_back(v.gL); c->v_end.push_back(v.gR);
+                    c->v_span.push_back(v.span); c->v_alt.push_back(v.alt); c->v_ref.push_back(v.ref);
                 }
             }
         }
     }
+    c->r_seg_begin[T] = c->r_range0.size();
     if (want_ed) { c->e_begin.push_back(c->e_tpos.size()); c->ed_valid = true; }
     c->evid_valid = want_evid;
-    if (want_pile) {
-        // the device lists the sites in the order of the positions: a target's are one stretch, the targets ascend.  A
-        // target the host reports as failed has none (one that failed on the device has none there either)
-        const DgSite *m_site = c->r_site.as<const DgSite>();
-        c->s_begin.assign((size_t)T + 1, 0); c->s_pos.clear(); c->s_counts.clear();
-        if (c->sr_batch) c->s_dev_begin.assign((size_t)T + 1, n_site);
-        uint64_t k = 0;
-        for (uint32_t t = 0; t < T; t++) {
-            c->s_begin[t] = c->s_pos.size();
-            if (c->sr_batch) c->s_dev_begin[t] = k;
-            for (; k < n_site && m_site[k].tgt == t; k++) {
-                const DgSite &x = m_site[k];
-                if (x.pos >= c->h_tlen[t]) return fail(c, DAGCON_ERR_INTERNAL, "k_pile_sites: site %llu of target %u at position %u of %u", (unsigned long long)k, t, x.pos, c->h_tlen[t]);
-                if (c->r_status[t] != DAGCON_OK) continue;
-                c->s_pos.push_back(x.pos);
-                for (int j = 0; j < 4; j++) { c->s_counts.push_back((uint16_t)(x.w[j] & 0xFFFFu)); c->s_counts.push_back((uint16_t)(x.w[j] >> 16)); }
-            }
-        }
-        if (k != n_site) return fail(c, DAGCON_ERR_INTERNAL, "k_pile_sites: site %llu of %llu is out of order (target %u)", (unsigned long long)k, (unsigned long long)n_site, m_site[k].tgt);
-        c->s_begin[T] = c->s_pos.size();
-        c->pile_valid = true;
-        if (c->sr_batch) {
-            // the entries stay on the device until dagcon_fetch_site_reads; their number came with the status block
-            c->sr_n_site = n_site;
-            c->sr_n_ent = T && c->h_pile_begin.back() ? *sb.h<uint64_t>(sb.o_sr_top) : 0;
-            if (c->sr_n_ent > c->sr_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu site entries in an arena of %llu", (unsigned long long)c->sr_n_ent, (unsigned long long)c->sr_cap);
-            c->sr_valid = true;
+    return DAGCON_OK;
+}
+
+// the pile-up's sites.  The device lists them in the order of the positions: a target's are one stretch, the targets
+// ascend.  A target the host reports as failed has none (one that failed on the device has none there either)
+static int unpack_sites(Ctx *c, const FetchPlan &f) {
+    const uint32_t T = c->T;
+    const uint64_t n_site = f.n_site;
+    const DgSite *m_site = c->r_site.as<const DgSite>();
+    c->s_begin.assign((size_t)T + 1, 0); c->s_pos.clear(); c->s_counts.clear();
+    if (c->sr_batch) c->s_dev_begin.assign((size_t)T + 1, n_site);
+    uint64_t k = 0;
+    for (uint32_t t = 0; t < T; t++) {
+        c->s_begin[t] = c->s_pos.size();
+        if (c->sr_batch) c->s_dev_begin[t] = k;
+        for (; k < n_site && m_site[k].tgt == t; k++) {
+            const DgSite &x = m_site[k];
+            if (x.pos >= c->h_tlen[t]) return fail(c, DAGCON_ERR_INTERNAL, "k_pile_sites: site %llu of target %u at position %u of %u", (unsigned long long)k, t, x.pos, c->h_tlen[t]);
+            if (c->r_status[t] != DAGCON_OK) continue;
+            c->s_pos.push_back(x.pos);
+            for (int j = 0; j < 4; j++) { c->s_counts.push_back((uint16_t)(x.w[j] & 0xFFFFu)); c->s_counts.push_back((uint16_t)(x.w[j] >> 16)); }
         }
     }
-    c->r_seg_begin[T] = c->r_range0.size();
+    if (k != n_site) return fail(c, DAGCON_ERR_INTERNAL, "k_pile_sites: site %llu of %llu is out of order (target %u)", (unsigned long long)k, (unsigned long long)n_site, m_site[k].tgt);
+    c->s_begin[T] = c->s_pos.size();
+    c->pile_valid = true;
+    if (c->sr_batch) {
+        // the entries stay on the device until dagcon_fetch_site_reads; their number came with the status block
+        c->sr_n_site = n_site;
+        if (int r = arena_total(c, c->sr_arena, T && c->h_pile_begin.back(), c->sr_n_ent)) return r;
+        c->sr_valid = true;
+    }
+    return DAGCON_OK;
+}
+
+int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
+    if (!ctx || !res) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->ran) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch before dagcon_run");
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    if ((r = fetch_status(c))) return r;
+    const uint32_t n_failed = fetch_outcomes(c);
+    FetchPlan f;
+    uint64_t bases = 0;
+    if ((r = fetch_plan(c, f))) return r;
+    if ((r = fetch_copies(c, f))) return r;
+    if ((r = unpack_segments(c, f, bases))) return r;
+    if (f.want_pile && (r = unpack_sites(c, f))) return r;
     c->tm.consensus_bases = bases;
     c->tm.algorithmic_bytes = 2ull * c->sum_len + bases;
     c->tm.n_alignments = c->A;
     c->tm.n_columns = c->h_st.n_columns;
     c->tm.n_nodes = c->h_st.node_need;
     c->tm.merge_segments = c->h_st.n_mseg;
-    res->n_targets = T;
+    res->n_targets = c->T;
     res->n_segments = c->r_range0.size();
     res->seg_begin = c->r_seg_begin.data();
     res->range0 = c->r_range0.data(); res->range1 = c->r_range1.data();
     res->seq_off = c->r_seq_off.data(); res->seq_len = c->r_seq_len.data();
-    res->seq_blob = m_blob; res->seq_bytes = nb;
+    res->seq_blob = c->r_blob.as<char>(); res->seq_bytes = f.nb;
     res->target_status = c->r_status.data(); res->n_failed = n_failed;
     c->fetched = true;
     return DAGCON_OK;

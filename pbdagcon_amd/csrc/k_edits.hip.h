@@ -6,9 +6,9 @@
 // between consecutive backbone bases are the edits, and nothing is aligned.
 //
 //   k_ed_scan_seg<false>  a wave per segment: counts the segment's edits after the trim, writes its span [t0, t1)
-//   k_ed_scan             one block: the exclusive prefix of the counts, targets in their own order, then a target's
-//                         segments in theirs (the order the host lists them in); the total; DG_E_ED_OVF when the arena
-//                         is too small (the batch is re-run with a larger one, as for every other arena)
+//   k_ed_scan             one block (k_scan.hip.h, the scan of every growing arena): the exclusive prefix of the counts,
+//                         targets in their own order, then a target's segments in theirs (the order the host lists them
+//                         in); the total; DG_E_ED_OVF when the arena is too small (the batch is re-run with a larger one)
 //   k_ed_scan_seg<true>   the same scan again, every surviving edit stored at its place: the order is that of the
 //                         target, no atomic decides it
 //
@@ -21,6 +21,7 @@
 // k_bp_join wrote it.
 #pragma once
 #include "dagcon_dev.h"
+#include "k_scan.hip.h"
 
 // equal leading bytes off both sides, then equal trailing ones (exact bytes); c is relative to the segment
 __device__ __forceinline__ void dg_ed_trim(const uint8_t *tb, const uint8_t *cb, uint32_t &t_pos, uint32_t &t_len, uint32_t &c, uint32_t &c_len) {
@@ -113,33 +114,22 @@ __global__ __launch_bounds__(256) void k_ed_scan_seg(DgParams p) {
 // host does not list them).  A thread takes a target and goes through its segments one by one, reading and writing
 // 32-byte records: a batch of many targets with a few segments each is what this is shaped for.  One target with
 // thousands of segments runs on one lane here; that case has not been measured (a prefix per segment would be the cure)
-__global__ __launch_bounds__(1024) void k_ed_scan(DgParams p) {
-    if (dg_failed(p)) return;
-    __shared__ unsigned long long s_part[16], s_carry;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0ull;
-    __syncthreads();
-    for (uint32_t t0 = 0; t0 < p.T; t0 += 1024u) {
-        const uint32_t t = t0 + threadIdx.x;
-        const bool live = t < p.T && !dg_tskip(p, t);
-        const uint64_t first = live ? p.seg_first[t] : 0ull;
-        const uint32_t ns = live ? p.n_seg[t] : 0u;
+struct DgEdScanItem {
+    uint64_t first;
+    uint32_t ns;
+    static __device__ __forceinline__ uint64_t n(const DgParams &p) { return p.T; }
+    __device__ __forceinline__ unsigned long long load(const DgParams &p, const uint64_t t) {
+        const bool live = !dg_tskip(p, (uint32_t)t);
+        first = live ? p.seg_first[t] : 0ull;
+        ns = live ? p.n_seg[t] : 0u;
         unsigned long long sum = 0;
         for (uint32_t k = 0; k < ns; k++) sum += p.ed_seg[first + k].cnt;
-        unsigned long long incl = sum;
-        for (int o = 1; o < 64; o <<= 1) { const unsigned long long up = __shfl_up(incl, o); if (lane >= o) incl += up; }
-        if (lane == 63) s_part[wv] = incl;
-        __syncthreads();
-        unsigned long long off = s_carry;
-        for (int k = 0; k < wv; k++) off += s_part[k];
-        off += incl - sum;
+        return sum;
+    }
+    __device__ __forceinline__ void store(const DgParams &p, const uint64_t, unsigned long long off) const {
         for (uint32_t k = 0; k < ns; k++) { p.ed_seg[first + k].off = off; off += p.ed_seg[first + k].cnt; }
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = off;
-        __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        *p.ed_top = s_carry;
-        if (s_carry > p.ed_cap) dg_fail(p, DG_E_ED_OVF);
-    }
-}
+    static constexpr auto top = &DgParams::ed_top; static constexpr auto cap = &DgParams::ed_cap;
+    static constexpr uint32_t ovf = DG_E_ED_OVF;
+};
+__global__ __launch_bounds__(1024) void k_ed_scan(DgParams p) { dg_block_scan<DgEdScanItem>(p); }

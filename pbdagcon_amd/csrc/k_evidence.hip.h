@@ -7,8 +7,8 @@
 //                 highest head lane at or below, one shuffle, a carry across steps).  Backward over the same steps: gR
 //                 and the alt end flow back from the group's tail.  A lane reads in the second loop only what it wrote
 //                 itself in the first.  Leaves one DgEvid per edit, counts zero.
-//   k_ev_count    a wave per alignment: walks its columns 64 a step, the target coordinate of a column from a ballot of
-//                 the target-base columns and a population count, the carry scalar.  The first group it can span is
+//   k_ev_count    a wave per alignment: walks its columns 64 a step (k_walk.hip.h: the alignment's header, the step, the
+//                 target coordinate of a column); the loop is its own.  The first group it can span is
 //                 found by binary search; one group is open at a time (a group
 //                 that touches the one before it, across two adjacent segments, is walked from the step of base gR - 1
 //                 again), its allele index and its "still equal to alt /
@@ -20,6 +20,7 @@
 // Every index is checked before it is used; a violation fails the target with DG_E_INTERNAL.
 #pragma once
 #include "dagcon_dev.h"
+#include "k_walk.hip.h"
 
 // k_cigar_rate's comparison: equal after clearing bit 0x20 in both
 __device__ __forceinline__ bool dg_ev_eq(const uint8_t a, const uint8_t b) { return ((a ^ b) & 0xDFu) == 0u; }
@@ -137,14 +138,13 @@ __global__ __launch_bounds__(256) void k_ev_count(DgParams p) {
     if (a64 >= p.A) return;
     const uint32_t a = (uint32_t)a64;
     const int lane = threadIdx.x & 63;
-    const uint32_t t = p.aln_tgt[a];
-    if (t >= p.T || dg_tskip(p, t)) return;
-    const uint32_t lo = p.n_lo[a], hi = p.n_hi[a];
-    if (hi <= lo) return;                                               // (empty after the trim: the graph did not take it)
-    const uint32_t ns = p.n_seg[t], tlen = p.tlen[t];
+    DgWalk wk;
+    if (dg_walk_open(p, a, lane, wk) != DG_WALK_GO) return;
+    const uint32_t t = wk.t, lo = wk.lo, hi = wk.hi, tlen = wk.tlen, s0 = wk.s0;
+    const uint32_t ns = p.n_seg[t];
     if (!ns) return;
-    const uint64_t first = p.seg_first[t], noff = p.norm_off[a];
-    bool bad = hi == DG_REDO || noff + hi > p.norm_cap || p.n_start[a] < 1u || first + ns > p.seg_cap || first + ns > p.st->seg_top;
+    const uint64_t first = p.seg_first[t];
+    bool bad = first + ns > p.seg_cap || first + ns > p.st->seg_top;
     uint64_t g = 0, ee = 0;
     if (!bad) {
         const DgEdSeg sa = p.ed_seg[first], sz = p.ed_seg[first + ns - 1u];
@@ -153,7 +153,6 @@ __global__ __launch_bounds__(256) void k_ev_count(DgParams p) {
     }
     if (bad) { if (lane == 0) dg_fail_target(p, t, DG_E_INTERNAL); return; }
     if (g == ee) return;
-    const uint32_t s0 = p.n_start[a] - 1u;
     {
         // the first edit whose group begins where this alignment has a left flank (gL >= 1 + s0), or at base 0
         const uint32_t need = s0 ? s0 + 1u : 0u;
@@ -161,7 +160,6 @@ __global__ __launch_bounds__(256) void k_ev_count(DgParams p) {
         while (l < r) { const uint64_t m = l + (r - l) / 2u; if (p.evid[m].gL < need) l = m + 1u; else r = m; }
         g = dg_ev_next_head(p, l, ee);
     }
-    const uint16_t *col = p.norm + noff;
     const uint8_t *tb = p.ed_t + p.ed_tbase[t];
     const unsigned long long lt = (1ull << lane) - 1ull;
     uint32_t tc0 = s0, c0 = lo;
@@ -174,13 +172,10 @@ __global__ __launch_bounds__(256) void k_ev_count(DgParams p) {
     bool eqA = true, eqR = true, lf = false, fresh = true;
     while (c0 < hi && g < ee) {
         bool rewind = false;
-        const uint32_t i = c0 + (uint32_t)lane;
-        const bool v = i < hi;
-        const uint16_t c = v ? col[i] : (uint16_t)(DG_GAP | (DG_GAP << 8));
-        const uint8_t qb = (uint8_t)(c & 0xff), tcb = (uint8_t)(c >> 8);
-        const bool isT = v && tcb != DG_GAP;
-        const unsigned long long mT = __ballot(isT);
-        const uint32_t nT = (uint32_t)__popcll(mT), tc = tc0 + (uint32_t)__popcll(mT & lt);
+        const DgWalkStep s = dg_walk_step(wk, c0, tc0, lane);
+        const bool v = s.v, isT = s.isT;
+        const uint8_t qb = s.qb, tcb = s.tcb;
+        const uint32_t nT = (uint32_t)__popcll(s.mT), tc = s.tc;
         const bool same = isT && dg_ev_eq(qb, tcb);
         while (g < ee) {
             if (fresh) {

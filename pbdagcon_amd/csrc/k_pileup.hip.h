@@ -2,8 +2,8 @@
 // Everything read here is resident after a run: the normalised, trimmed columns the graph was built from (norm) and
 // where each alignment's lie (norm_off, n_lo, n_hi, n_start, aln_tgt).
 //
-//   k_pile_count        a wave per alignment: walks its columns 64 a step, the target coordinate of a column from a
-//                       ballot of the target-base columns and a population count, the carry scalar.  A column with a
+//   k_pile_count        a wave per alignment: walks its columns 64 a step (k_walk.hip.h: the alignment's header, the
+//                       step, the target coordinate of a column).  A column with a
 //                       target base adds 1 to one of the six counters of its position; an inserted column whose
 //                       neighbour in front holds a target base (bit lane - 1 of the same ballot, bit 63 of the step
 //                       before for lane 0) begins a run and adds 1 to INS of that neighbour's position.  A position is
@@ -13,14 +13,16 @@
 //                       words on the stream before every execution.
 //   k_pile_sites<false> a thread per position, a block per tile of 256: marks the sites (the rule in integers), counts
 //                       them per tile.
-//   k_pile_scan         one block: the exclusive prefix over the tiles; the total; DG_E_SITE_OVF when the arena is too
-//                       small (the batch is re-run with a larger one, as for every other arena).
+//   k_pile_scan         one block (k_scan.hip.h): the exclusive prefix over the tiles; the total; DG_E_SITE_OVF when the
+//                       arena is too small (the batch is re-run with a larger one, as for every other arena).
 //   k_pile_sites<true>  the same marks again, every site stored at its place: tile offset, waves in front, lanes in
 //                       front.  The order is that of the positions; no atomic decides it.
 //
 // Every index is checked before it is used; a violation fails the target with DG_E_INTERNAL.
 #pragma once
 #include "dagcon_dev.h"
+#include "k_scan.hip.h"
+#include "k_walk.hip.h"
 
 #define DG_PILE_TILE 256u
 
@@ -30,31 +32,21 @@ __global__ __launch_bounds__(256) void k_pile_count(DgParams p) {
     if (a64 >= p.A) return;
     const uint32_t a = (uint32_t)a64;
     const int lane = threadIdx.x & 63;
-    const uint32_t t = p.aln_tgt[a];
-    if (t >= p.T || dg_tskip(p, t)) return;
-    const uint32_t lo = p.n_lo[a], hi = p.n_hi[a];
-    if (hi <= lo) return;                                               // (empty after the trim: the graph did not take it)
-    const uint32_t tlen = p.tlen[t];
-    const uint64_t noff = p.norm_off[a], pb = p.pile_begin[t];
-    if (hi == DG_REDO || noff + hi > p.norm_cap || p.n_start[a] < 1u || pb > p.pile_n || tlen > p.pile_n - pb) {
-        if (lane == 0) dg_fail_target(p, t, DG_E_INTERNAL);
-        return;
-    }
-    const uint16_t *col = p.norm + noff;
+    DgWalk wk;
+    if (dg_walk_open(p, a, lane, wk) != DG_WALK_GO) return;
+    const uint32_t t = wk.t, tlen = wk.tlen;
+    const uint64_t pb = p.pile_begin[t];
+    if (pb > p.pile_n || tlen > p.pile_n - pb) { if (lane == 0) dg_fail_target(p, t, DG_E_INTERNAL); return; }
     uint32_t *cnt = p.pile + 4ull * pb;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    uint32_t tc0 = p.n_start[a] - 1u;
+    uint32_t tc0 = wk.s0;
     bool carry = false, bad = false;                                    // carry: the column in front of this step holds a target base
-    for (uint32_t c0 = lo; c0 < hi; c0 += 64u) {
-        const uint32_t i = c0 + (uint32_t)lane;
-        const bool v = i < hi;
-        const uint16_t c = v ? col[i] : (uint16_t)(DG_GAP | (DG_GAP << 8));
-        const uint8_t qb = (uint8_t)(c & 0xff), tcb = (uint8_t)(c >> 8);
-        const bool isT = v && tcb != DG_GAP;
-        const unsigned long long mT = __ballot(isT);
-        const uint32_t tc = tc0 + (uint32_t)__popcll(mT & lt);          // target bases in front of this column
+    for (uint32_t c0 = wk.lo; c0 < wk.hi; c0 += 64u) {
+        const DgWalkStep s = dg_walk_step(wk, c0, tc0, lane);
+        const uint8_t qb = s.qb;
+        const unsigned long long mT = s.mT;
+        const uint32_t tc = s.tc;
         const bool prevT = lane ? ((mT >> (lane - 1)) & 1ull) != 0ull : carry;
-        if (isT) {
+        if (s.isT) {
             if (tc >= tlen) bad = true;
             else {
                 uint32_t w = 2u, inc = 1u;                              // N
@@ -68,7 +60,7 @@ __global__ __launch_bounds__(256) void k_pile_count(DgParams p) {
                 }
                 atomicAdd(&cnt[4ull * tc + w], inc);
             }
-        } else if (v && qb != DG_GAP && prevT) {
+        } else if (s.v && qb != DG_GAP && prevT) {
             // the first column of an insertion run: it belongs to the base in front, tc - 1 (prevT: tc >= 1 + the start)
             if (tc == 0u || tc - 1u >= tlen) bad = true;
             else atomicAdd(&cnt[4ull * (tc - 1u) + 3u], 1u);
@@ -132,29 +124,11 @@ __global__ __launch_bounds__(DG_PILE_TILE) void k_pile_sites(DgParams p) {
 }
 
 // the exclusive prefix of the tiles' site counts, one block
-__global__ __launch_bounds__(1024) void k_pile_scan(DgParams p) {
-    if (dg_failed(p)) return;
-    __shared__ unsigned long long s_part[16], s_carry;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0ull;
-    __syncthreads();
-    const uint64_t n_tiles = (p.pile_n + DG_PILE_TILE - 1u) / DG_PILE_TILE;
-    for (uint64_t b0 = 0; b0 < n_tiles; b0 += 1024u) {
-        const uint64_t b = b0 + threadIdx.x;
-        const unsigned long long own = b < n_tiles ? p.pile_tile[b] : 0ull;
-        unsigned long long incl = own;
-        for (int o = 1; o < 64; o <<= 1) { const unsigned long long up = __shfl_up(incl, o); if (lane >= o) incl += up; }
-        if (lane == 63) s_part[wv] = incl;
-        __syncthreads();
-        unsigned long long off = s_carry;
-        for (int k = 0; k < wv; k++) off += s_part[k];
-        if (b < n_tiles) p.pile_tile[b] = off + incl - own;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = off + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *p.site_top = s_carry;
-        if (s_carry > p.site_cap) dg_fail(p, DG_E_SITE_OVF);
-    }
-}
+struct DgPileScanItem {
+    static __device__ __forceinline__ uint64_t n(const DgParams &p) { return (p.pile_n + DG_PILE_TILE - 1u) / DG_PILE_TILE; }
+    __device__ __forceinline__ unsigned long long load(const DgParams &p, const uint64_t b) const { return p.pile_tile[b]; }
+    __device__ __forceinline__ void store(const DgParams &p, const uint64_t b, const unsigned long long off) const { p.pile_tile[b] = off; }
+    static constexpr auto top = &DgParams::site_top; static constexpr auto cap = &DgParams::site_cap;
+    static constexpr uint32_t ovf = DG_E_SITE_OVF;
+};
+__global__ __launch_bounds__(1024) void k_pile_scan(DgParams p) { dg_block_scan<DgPileScanItem>(p); }

@@ -6,11 +6,11 @@
 //                       execution), and the first site of a 64-position word stores its own index in sr_rank of that word.
 //                       The site of a position whose bit is set is then sr_rank[word] + popcount(bits below): no search.
 //                       A word without a site is never asked, so sr_rank needs no clearing.
-//   k_sr_walk<false>    a wave per alignment, k_pile_count's walk: 64 columns a step, the coordinate from a ballot and a
-//                       population count.  A column with a target base whose position has its bit set is an entry; the
+//   k_sr_walk<false>    a wave per alignment, k_pile_count's walk (k_walk.hip.h): 64 columns a step, the coordinate from a
+//                       ballot and a population count.  A column with a target base whose position has its bit set is an entry; the
 //                       wave counts them, sr_cnt[a] (DG_SR_TAKEN: the alignment is one the graph took).  A column whose
 //                       bit is clear costs the walk one test of a word that the 64 lanes share.
-//   k_sr_scan           one block: the exclusive prefix of the alignments' entry counts; the total; DG_E_SR_OVF when the
+//   k_sr_scan           one block (k_scan.hip.h): the exclusive prefix of the alignments' entry counts; the total; DG_E_SR_OVF when the
 //                       arena is too small (the batch is re-run with a larger one).
 //   k_sr_walk<true>     the same walk, every entry stored at its place: the alignment's offset, the entries of the steps
 //                       before, the lanes in front.  The code is cls | ins << 3: cls by k_pile_count's classification, ins
@@ -25,6 +25,8 @@
 // Every index is checked before it is used; a violation fails the target with DG_E_INTERNAL.
 #pragma once
 #include "dagcon_dev.h"
+#include "k_scan.hip.h"
+#include "k_walk.hip.h"
 
 // sites of the batch the kernels may index: *site_top, never more than the arena
 __device__ __forceinline__ unsigned long long dg_sr_nsite(const DgParams &p) {
@@ -70,17 +72,14 @@ __global__ __launch_bounds__(256) void k_sr_walk(DgParams p) {
     if (a64 >= p.A) return;
     const uint32_t a = (uint32_t)a64;
     const int lane = threadIdx.x & 63;
-    const uint32_t t = p.aln_tgt[a];
-    uint32_t lo = 0, hi = 0;
-    bool taken = t < p.T && !dg_tskip(p, t);
-    if (taken) { lo = p.n_lo[a]; hi = p.n_hi[a]; taken = hi > lo; }    // (empty after the trim: the graph did not take it)
-    if (!taken) {
+    DgWalk wk;
+    if (dg_walk_open(p, a, lane, wk) != DG_WALK_GO) {                  // (<false>: every early way out leaves a count of 0)
         if (!WRITE && lane == 0) p.sr_cnt[a] = 0u;
         return;
     }
-    const uint32_t tlen = p.tlen[t];
-    const uint64_t noff = p.norm_off[a], pb = p.pile_begin[t];
-    if (hi == DG_REDO || noff + hi > p.norm_cap || p.n_start[a] < 1u || pb > p.pile_n || tlen > p.pile_n - pb) {
+    const uint32_t t = wk.t, tlen = wk.tlen, hi = wk.hi;
+    const uint64_t pb = p.pile_begin[t];
+    if (pb > p.pile_n || tlen > p.pile_n - pb) {
         if (lane == 0) { dg_fail_target(p, t, DG_E_INTERNAL); if (!WRITE) p.sr_cnt[a] = 0u; }
         return;
     }
@@ -92,30 +91,24 @@ __global__ __launch_bounds__(256) void k_sr_walk(DgParams p) {
         if (at > p.sr_cap || cnt > p.sr_cap - at) { if (lane == 0) dg_fail_target(p, t, DG_E_INTERNAL); return; }
         end = at + cnt;
     }
-    const uint16_t *col = p.norm + noff;
     const unsigned long long lt = (1ull << lane) - 1ull;
-    uint32_t tc0 = p.n_start[a] - 1u, total = 0u;
+    uint32_t tc0 = wk.s0, total = 0u;
     bool bad = false;
-    for (uint32_t c0 = lo; c0 < hi; c0 += 64u) {
-        const uint32_t i = c0 + (uint32_t)lane;
-        const bool v = i < hi;
-        const uint16_t c = v ? col[i] : (uint16_t)(DG_GAP | (DG_GAP << 8));
-        const uint8_t qb = (uint8_t)(c & 0xff), tcb = (uint8_t)(c >> 8);
-        const bool isT = v && tcb != DG_GAP;
-        const unsigned long long mT = __ballot(isT);
-        const uint32_t tc = tc0 + (uint32_t)__popcll(mT & lt);          // target bases in front of this column
+    for (uint32_t c0 = wk.lo; c0 < hi; c0 += 64u) {
+        const DgWalkStep ws = dg_walk_step(wk, c0, tc0, lane);
+        const uint32_t i = ws.i, tc = ws.tc;
         bool ent = false;
         unsigned long long word = 0ull;
         uint64_t g = 0;
-        if (isT) {
+        if (ws.isT) {
             if (tc >= tlen) bad = true;
             else { g = pb + tc; word = p.sr_bits[g >> 6]; ent = ((word >> (g & 63u)) & 1ull) != 0ull; }
         }
         const unsigned long long mE = __ballot(ent);
         if (WRITE && mE) {
             // the column behind: the next lane's, lane 63's from memory
-            uint32_t nx = (uint32_t)__shfl_down((int)c, 1);
-            if (lane == 63) nx = i + 1u < hi ? col[i + 1u] : (uint32_t)(DG_GAP | (DG_GAP << 8));
+            uint32_t nx = (uint32_t)__shfl_down((int)ws.c, 1);
+            if (lane == 63) nx = i + 1u < hi ? wk.col[i + 1u] : (uint32_t)(DG_GAP | (DG_GAP << 8));
             if (ent) {
                 const bool ins = i + 1u < hi && (uint8_t)(nx >> 8) == DG_GAP && (uint8_t)(nx & 0xff) != DG_GAP;
                 const unsigned long long k = (unsigned long long)p.sr_rank[g >> 6] + (unsigned long long)__popcll(word & ((1ull << (g & 63u)) - 1ull));
@@ -124,12 +117,12 @@ __global__ __launch_bounds__(256) void k_sr_walk(DgParams p) {
                 else {
                     const DgSite s = p.pile_site[k];
                     if (s.tgt != t || s.pos != tc) bad = true;
-                    else { p.sr_site[to] = (uint32_t)k; p.sr_code[to] = (uint8_t)(dg_sr_cls(qb) | (ins ? 8u : 0u)); }
+                    else { p.sr_site[to] = (uint32_t)k; p.sr_code[to] = (uint8_t)(dg_sr_cls(ws.qb) | (ins ? 8u : 0u)); }
                 }
             }
         }
         total += (uint32_t)__popcll(mE);
-        tc0 += (uint32_t)__popcll(mT);
+        tc0 += (uint32_t)__popcll(ws.mT);
     }
     const bool any_bad = __ballot(bad) != 0ull;
     if (WRITE && at + total != end) { if (lane == 0) dg_fail_target(p, t, DG_E_INTERNAL); return; }
@@ -138,31 +131,14 @@ __global__ __launch_bounds__(256) void k_sr_walk(DgParams p) {
 }
 
 // the exclusive prefix of the alignments' entry counts, one block
-__global__ __launch_bounds__(1024) void k_sr_scan(DgParams p) {
-    if (dg_failed(p)) return;
-    __shared__ unsigned long long s_part[16], s_carry;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0ull;
-    __syncthreads();
-    for (uint64_t b0 = 0; b0 < p.A; b0 += 1024u) {
-        const uint64_t b = b0 + threadIdx.x;
-        const unsigned long long own = b < p.A ? (unsigned long long)(p.sr_cnt[b] & ~DG_SR_TAKEN) : 0ull;
-        unsigned long long incl = own;
-        for (int o = 1; o < 64; o <<= 1) { const unsigned long long up = __shfl_up(incl, o); if (lane >= o) incl += up; }
-        if (lane == 63) s_part[wv] = incl;
-        __syncthreads();
-        unsigned long long off = s_carry;
-        for (int k = 0; k < wv; k++) off += s_part[k];
-        if (b < p.A) p.sr_off[b] = off + incl - own;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = off + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *p.sr_top = s_carry;
-        if (s_carry > p.sr_cap) dg_fail(p, DG_E_SR_OVF);
-    }
-}
+struct DgSrScanItem {
+    static __device__ __forceinline__ uint64_t n(const DgParams &p) { return p.A; }
+    __device__ __forceinline__ unsigned long long load(const DgParams &p, const uint64_t a) const { return p.sr_cnt[a] & ~DG_SR_TAKEN; }
+    __device__ __forceinline__ void store(const DgParams &p, const uint64_t a, const unsigned long long off) const { p.sr_off[a] = off; }
+    static constexpr auto top = &DgParams::sr_top; static constexpr auto cap = &DgParams::sr_cap;
+    static constexpr uint32_t ovf = DG_E_SR_OVF;
+};
+__global__ __launch_bounds__(1024) void k_sr_scan(DgParams p) { dg_block_scan<DgSrScanItem>(p); }
 
 // what decides an entry's sign at a site: 0x80 an insertion site; otherwise k1 | k2 << 3, k2 == 7: no second class
 __device__ __forceinline__ uint32_t dg_sr_kind(const DgSite &s) {

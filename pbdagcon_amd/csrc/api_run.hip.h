@@ -366,7 +366,7 @@ int launch_all(Ctx *c) {
             hipLaunchKernelGGL(k_bp_defer, dim3(c->T), dim3(64), 0, s, p);
             DG_BP_LAUNCH(k_bp_walk_g, dim3(c->T * c->bp_max));
         } else {
-            // a lane per piece first; the wave-per-piece sweep then takes the pieces a lane gave up (deep recursion)
+            // a row of eight lanes per piece first; the wave-per-piece sweep then takes the pieces a row gave up (deep recursion)
             if (p.bp_lane) hipLaunchKernelGGL(k_bp_sweep_l, dim3((c->T * c->bp_max + 7u) / 8u), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_bp_sweep, dim3(c->T * c->bp_max), dim3(64), 0, s, p);
             hipLaunchKernelGGL(k_bp_check, dim3(c->T), dim3(64), 0, s, p);

@@ -11,27 +11,43 @@
 //     w(e) = (float)count - coverage*0.5f       (the reference's left-to-right order)
 // that does not depend on any score.
 //
-//   k_bp_terms    thread per vertex: the target-side term of w(e), one float per vertex.
-//                 (w(e) itself is formed from it and the edge's count when k_bp_sweep unpacks a
-//                 chunk: the terms are gathered a chunk ahead, like the edges.)
-//   k_bp_sweep    one wave per (target, segment between two cut vertices of k_cuts); what
-//                 is left is the bare recurrence.  Vertex ids
-//                 are in backbone-position order, a topological order except for the few
-//                 edges the merge turned around.  The wave STREAMS the vertices from the
-//                 exit downwards: the records of 64 vertices at a time are requested two
-//                 chunks ahead (plain loads whose latency nobody waits for) and unpacked
-//                 into an LDS ring (edges: target, w); finished scores live in a second
-//                 LDS ring.  A step reads the vertex's edges and its successors' scores
-//                 from LDS, one edge per lane, takes the first maximum and stores it.
-//                 An edge to a vertex that has no score yet (a turned-around edge) puts
-//                 that vertex on a small stack and it is scored first.  Whatever is not
-//                 in the rings (long lists, far-away successors) comes from HBM.
-//   k_bp_check    one wave per target: checks that the segmented sweep was exact, else
-//                 sweeps the target in one piece.
-//   k_bp_walk     one wave per (target, segment): the best-edge walk (:443-456) from one
-//                 cut vertex to the next on LDS-staged (best, base, weight) triples.
-//   k_bp_join     one wave per target: the segmentation (:327-373) over the joined
-//                 pieces, and the output.
+// w(e) is spelled once, dg_bp_edge_w: the exactness argument (same operations, same order)
+// rests on every site forming it alike.
+//
+// The kernels, in launch order (api_run.hip.h).  A piece is a (target, segment between two cut
+// vertices) pair; DgBpPiece / dg_bp_piece_open is how a wave or a block learns which one it has.
+// Both paths begin with
+//   k_bp_terms        thread per vertex: the target-side term of w(e), one float per vertex
+//                     (w(e) is formed from it and the edge's count when a sweep unpacks a chunk).
+// Full-span pileups (cuts of k_cuts; every path crosses every cut, so the pieces are swept
+// concurrently, each relative to its own upper cut):
+//   k_bp_sweep_l      a row of eight lanes per piece, eight pieces a wave (batches of many pieces);
+//                     a row that gives its piece up marks it
+//   k_bp_sweep        a wave per piece: dg_bp_sweep, the streamed recurrence (see there); the
+//                     pieces k_bp_sweep_l marked, or all of them
+//   k_bp_check        a wave per target: the 2^22 bound (dg_bp_exact) on what the pieces left,
+//                     else the target swept whole (dg_bp_sweep_whole)
+//   k_bp_walk_r       the best-edge walk (:443-456) with a row of eight lanes per piece (where
+//                     k_bp_sweep_l ran), or
+//   k_bp_walk         with a wave per piece: dg_bp_walk_wave<SUP, POS, false>
+// Partial-span pileups (p.gcuts, cuts of k_cuts2; a path may leave a piece for exit):
+//   k_bp_xtree        a lane per target: the tree of vertices that lead to exit and nowhere else,
+//                     absolute scores at once
+//   k_bp_sweep_ab     a wave per piece: one sweep for A (cut worth 0, exit -inf) and B (cut -inf,
+//                     exit 0) of every vertex; the last piece, which ends in exit, is absolute
+//   k_bp_comb         a wave per target: the absolute score of every cut from the last one down,
+//                     score[c_k] = max(A_k + score[c_k+1], B_k); the bound; deferred vertices reset
+//   k_bp_abs          a block per piece: absolute scores, max(A + score[upper cut], B)
+//   k_bp_choose       a block per piece: the first-maximum choices (dg_bp_first_max)
+//   k_bp_sweep_abs_g  a target that failed the bound, has too many deferred vertices or is one
+//                     piece: swept whole (dg_bp_sweep_whole)
+//   k_bp_defer        a lane per target: the deferred vertices nobody asked for (enter is the last)
+//   k_bp_walk_g       a wave per piece: dg_bp_walk_wave<SUP, POS, true>, from every cut to the next
+//                     cut or to exit, and from enter to the first cut it meets
+// Both end with
+//   k_bp_join         a wave per target: chains the pieces that are on the path, the segmentation
+//                     (:327-373) over them, and the output.
+// The walks and the join come in four (SUP, POS) instances: per-base support and per-base positions.
 //
 // fp32 throughout; every value is a multiple of 0.5 below 2^23, so the arithmetic is
 // exact (-ffp-contract=off).
@@ -62,6 +78,34 @@ __global__ __launch_bounds__(256) void k_bp_terms(DgParams p) {
         p.score[nb + v] = make_float2(0.0f, 0.0f);     // (score, 1 = final); absent key reads as 0
         p.best[nb + v] = -1;
     }
+}
+
+// w(e) of an edge with `count` reads into a vertex whose term (k_bp_terms) is tt: AlnGraphBoost.cpp:404-408, the one
+// spelling of it.  Every sweep, choice and check adds a score to this value and nothing else.
+__device__ __forceinline__ float dg_bp_edge_w(const float tt, const int count) {
+    return tt == DG_TT_TEN ? -10.0f : (float)count - tt;
+}
+
+// A piece: segment seg of target t, the vertices c_bot .. c_top - 1 between two cuts of its row of p.cuts_bp (crow:
+// the count, then the cuts), or c_bot .. N - 1 for the last piece, which ends in exit (c_top = -1).
+struct DgBpPiece {
+    uint32_t t, seg, nseg;
+    uint64_t nb;
+    int N, c_bot, c_top;
+    const uint32_t *crow;
+};
+// false: nothing to do (the run has failed, the target is skipped, the target has fewer pieces)
+__device__ __forceinline__ bool dg_bp_piece_open(const DgParams &p, const uint32_t piece, DgBpPiece &o) {
+    o.t = piece / p.bp_max; o.seg = piece % p.bp_max;
+    if (dg_failed(p) || dg_tskip(p, o.t)) return false;
+    o.crow = p.cuts_bp + (uint64_t)o.t * (p.bp_max + 2u);
+    o.nseg = o.crow[0];
+    if (o.seg >= o.nseg) return false;
+    o.nb = p.node_base[o.t];
+    o.N = (int)p.n_nodes[o.t];
+    o.c_bot = (int)o.crow[1 + o.seg];
+    o.c_top = o.seg + 1 < o.nseg ? (int)o.crow[2 + o.seg] : -1;
+    return true;
 }
 
 // LDS per sweep wave is what bounds the waves in flight (8 segments x 1000 targets want
@@ -110,6 +154,13 @@ __device__ __forceinline__ bool dg_sup_put(uint32_t *dst, uint32_t w, int32_t d)
     return w > 0xffffu || (uint32_t)d > 0xffffu;
 }
 
+// The streamed recurrence, one wave.  Vertex ids are in backbone-position order, a topological order except for the few
+// edges the merge turned around.  The wave STREAMS the vertices downwards: the records of 64 vertices at a time are
+// requested two chunks ahead (plain loads whose latency nobody waits for) and unpacked into an LDS ring (edges: target,
+// w); finished scores live in a second LDS ring.  A step reads the vertex's edges and its successors' scores from LDS,
+// one edge per lane, takes the first maximum and stores it.  An edge to a vertex that has no score yet (a turned-around
+// edge) puts that vertex on a small stack and it is scored first.  Whatever is not in the rings (long lists, far-away
+// successors) comes from HBM.
 // Scores the vertices v_top .. v_bot (descending ids) of one target.  c_top >= 0: the
 // vertex every path of this stretch ends in (the next cut, see k_cuts); it counts as
 // score 0 and is not evaluated, so the scores are relative to it.  amax = largest
@@ -187,7 +238,7 @@ __device__ __forceinline__ void dg_bp_sweep(DgBpShared &S, const DgNode *nd, int
             if (ol_ <= DG_BOUT) {                                                           \
                 _Pragma("unroll") for (int k_ = 0; k_ < DG_BOUT; k_++) {                    \
                     S.out_dst[x_ * DG_BOUT + k_] = e_dst[k_];                               \
-                    S.out_w[x_ * DG_BOUT + k_] = e_t[k_] == DG_TT_TEN ? -10.0f : (float)e_w[k_] - e_t[k_]; /* :404-408 */ \
+                    S.out_w[x_ * DG_BOUT + k_] = dg_bp_edge_w(e_t[k_], e_w[k_]);                \
                 }                                                                           \
             }                                                                               \
         }                                                                                   \
@@ -362,8 +413,7 @@ __device__ __forceinline__ void dg_bp_sweep(DgBpShared &S, const DgNode *nd, int
                         if (!hbm) { d = S.out_dst[x * DG_BOUT + idx]; w = S.out_w[x * DG_BOUT + idx]; }
                         else {
                             d = (int)pool[out_off + 2 * idx];
-                            const float td = tt[d];
-                            w = td == DG_TT_TEN ? -10.0f : (float)(int)pool[out_off + 2 * idx + 1] - td;   // :404-408
+                            w = dg_bp_edge_w(tt[d], (int)pool[out_off + 2 * idx + 1]);
                         }
                     }
                     const int y = d & (DG_SR - 1);
@@ -488,31 +538,57 @@ __device__ __forceinline__ void dg_bp_sweep(DgBpShared &S, const DgNode *nd, int
 // the segments are swept concurrently, each relative to its own upper cut, and the
 // first-maximum choices (all that the consensus uses) are the reference's as long as
 // the arithmetic is exact, which k_bp_check verifies from the figures left here.
-__global__ __launch_bounds__(64) void k_bp_sweep(DgParams p) {
-    const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
-    if (dg_failed(p) || dg_tskip(p, t)) return;
-    const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
-    const uint32_t nseg = crow[0];
-    if (seg >= nseg) return;
-    const int lane = threadIdx.x;
+// a sweep that came back bad (one lane reports).  stuck: it spent its step budget, the graph is broken and the target
+// is dropped; else its evaluation stack was full: STACK, the host grows the scratch and runs the batch again
+__device__ __forceinline__ void dg_bp_sweep_failed(const DgParams &p, const uint32_t t, const bool stuck) {
+    if (stuck) dg_fail_target(p, t, DG_E_INTERNAL);
+    else { dg_fail(p, DG_E_STACK); p.st->bad_target = t; }
+}
+// target t in one piece, as the reference does it: every vertex in the stream, absolute scores, final choices
+__device__ __forceinline__ void dg_bp_sweep_whole(const DgParams &p, const uint32_t t, DgBpShared &S, int32_t *gstk, const int lane) {
     const uint64_t nb = p.node_base[t];
-    __shared__ DgBpShared S;
     const int N = (int)p.n_nodes[t];
-    const int c_bot = (int)crow[1 + seg];
-    const int c_top = seg + 1 < nseg ? (int)crow[2 + seg] : -1;
+    float2 *score = p.score + nb;
+    for (int i = lane; i < N; i += 64) score[i] = make_float2(0.0f, 0.0f);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    float amax = 0.0f;
+    bool bad = false, stuck = false;
+    dg_bp_sweep(S, p.nodes + nb, p.best + nb, score, p.pool + p.pool_base[t], p.bp_tt + nb, N - 1, 0, -1,
+                gstk, (int)p.stk_words, lane, amax, bad, stuck);
+    if (bad && lane == 0) dg_bp_sweep_failed(p, t, stuck);
+}
+// The 2^22 bound.  Every score is a multiple of 0.5, so fp32 is exact below 2^23.  A vertex of a piece has the absolute
+// score rel + abs(upper cut), and a candidate adds one edge term (|w| <= wmax = max(10, reads)).  If the piece's largest
+// relative value m, the absolute score `above` of its upper cut and wmax together stay below 2^22, the reference's
+// absolute arithmetic and the pieces' relative one are both exact and pick the same first maxima; else the target is
+// swept again in one piece.
+__device__ __forceinline__ float dg_bp_wmax(const DgParams &p, const uint32_t t) {
+    const float K = (float)(uint32_t)(p.aln_begin[t + 1] - p.aln_begin[t]);
+    return K > 10.0f ? K : 10.0f;
+}
+__device__ __forceinline__ bool dg_bp_exact(const float m, const float above, const float wmax) {
+    return m + fabsf(above) + wmax < 4194304.0f;
+}
+
+__global__ __launch_bounds__(64) void k_bp_sweep(DgParams p) {
+    DgBpPiece P;
+    if (!dg_bp_piece_open(p, blockIdx.x, P)) return;
+    const int lane = threadIdx.x;
+    const uint64_t nb = P.nb;
+    __shared__ DgBpShared S;
     // (p.bp_lane: k_bp_sweep_l has been over every piece; what it gave up is marked)
     if (p.bp_lane && !(p.bp_stat[2 * (uint64_t)blockIdx.x] < 0.0f)) return;
     float amax = 0.0f;
     bool bad = false, stuck = false;
-    dg_bp_sweep(S, p.nodes + nb, p.best + nb, p.score + nb, p.pool + p.pool_base[t], p.bp_tt + nb,
-                c_top >= 0 ? c_top - 1 : N - 1, c_bot, c_top,
+    dg_bp_sweep(S, p.nodes + nb, p.best + nb, p.score + nb, p.pool + p.pool_base[P.t], p.bp_tt + nb,
+                P.c_top >= 0 ? P.c_top - 1 : P.N - 1, P.c_bot, P.c_top,
                 p.stk + (uint64_t)blockIdx.x * p.stk_words, (int)p.stk_words, lane, amax, bad, stuck);
-    if (bad) {                                                    // STACK: the host grows the scratch and re-runs
-        if (lane == 0) { if (stuck) dg_fail_target(p, t, DG_E_INTERNAL); else { dg_fail(p, DG_E_STACK); p.st->bad_target = t; } }
+    if (bad) {
+        if (lane == 0) dg_bp_sweep_failed(p, P.t, stuck);
         return;
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    const float a = p.score[nb + c_bot].x;                        // this segment's first vertex, relative to c_top
+    const float a = p.score[nb + P.c_bot].x;                      // this segment's first vertex, relative to c_top
     if (lane == 0) { p.bp_stat[2 * (uint64_t)blockIdx.x] = amax; p.bp_stat[2 * (uint64_t)blockIdx.x + 1] = a; }
 }
 
@@ -558,6 +634,8 @@ __global__ __launch_bounds__(64) void k_bp_sweep_l(DgParams p) {
     const int l = threadIdx.x & (DG_BRW - 1);
     const uint32_t row = threadIdx.x / DG_BRW;
     const uint32_t piece = blockIdx.x * (uint32_t)ROWS + row;
+    // (the row kernels keep this prologue of their own, not dg_bp_piece_open: the last wave's rows reach past the last
+    // target, which has to be seen before dg_tskip reads tactive[t]; and their code is held identical to what it was)
     const uint32_t t = piece / p.bp_max, seg = piece % p.bp_max;
     if (t >= p.T || dg_tskip(p, t)) return;
     const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
@@ -706,7 +784,7 @@ __global__ __launch_bounds__(64) void k_bp_sweep_l(DgParams p) {
                 n = __shfl(d, __ffs((int)miss) - 1, DG_BRW);
                 next = 0;
             } else {
-                const float w = tv == DG_TT_TEN ? -10.0f : (float)cnt - tv;          // :404-408
+                const float w = dg_bp_edge_w(tv, cnt);
                 const float ns = w + sc;
                 float mx = 0.0f;                             // no out edge (the exit vertex): score 0, the map default
                 int bd = -1;
@@ -749,37 +827,22 @@ __global__ __launch_bounds__(64) void k_bp_sweep_l(DgParams p) {
 __global__ __launch_bounds__(64) void k_bp_check(DgParams p) {
     const uint32_t t = blockIdx.x;
     if (dg_failed(p) || dg_tskip(p, t)) return;
-    const int lane = threadIdx.x;
-    const uint64_t nb = p.node_base[t];
-    // Every score is a multiple of 0.5, so fp32 is exact below 2^23.  A vertex of segment i has
-    // the absolute score rel + abs(cut i+1), and a candidate adds one edge term
-    // (|w| <= max(10, reads)); if all of that stays below 2^22 both the reference's absolute
-    // arithmetic and the relative one of k_bp_sweep are exact and pick the same first maxima.
-    // Otherwise the target is swept again in one piece.
+    // piece i's upper cut has the absolute score acc, the sum of the first-vertex scores of the pieces above it
     const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
     const int nseg = (int)crow[0];
     if (nseg <= 1) return;
     bool redo = (p.flags & DG_F_RESWEEP) != 0;
-    const float K = (float)(uint32_t)(p.aln_begin[t + 1] - p.aln_begin[t]);
-    const float wmax = K > 10.0f ? K : 10.0f;
+    const float wmax = dg_bp_wmax(p, t);
     float acc = 0.0f;
     for (int i = nseg - 1; i >= 0; i--) {
         const float m = p.bp_stat[2 * ((uint64_t)t * p.bp_max + i)];
         const float a = p.bp_stat[2 * ((uint64_t)t * p.bp_max + i) + 1];
-        if (!(m + fabsf(acc) + wmax < 4194304.0f)) redo = true;
+        if (!dg_bp_exact(m, acc, wmax)) redo = true;
         acc += a;
     }
     if (!redo) return;
     __shared__ DgBpShared S;
-    const int N = (int)p.n_nodes[t];
-    float2 *score = p.score + nb;
-    for (int i = lane; i < N; i += 64) score[i] = make_float2(0.0f, 0.0f);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    float amax = 0.0f;
-    bool bad = false, stuck = false;
-    dg_bp_sweep(S, p.nodes + nb, p.best + nb, score, p.pool + p.pool_base[t], p.bp_tt + nb, N - 1, 0, -1,
-                p.stk + (uint64_t)t * p.bp_max * p.stk_words, (int)p.stk_words, lane, amax, bad, stuck);
-    if (bad && lane == 0) { if (stuck) dg_fail_target(p, t, DG_E_INTERNAL); else { dg_fail(p, DG_E_STACK); p.st->bad_target = t; } }
+    dg_bp_sweep_whole(p, t, S, p.stk + (uint64_t)t * p.bp_max * p.stk_words, (int)threadIdx.x);
 }
 
 // POS walks: a path base's _bbMap travels through W.sb with its vertex's kind in bit 22 (_bbMap < 2^18); it leaves for
@@ -791,40 +854,52 @@ __device__ __forceinline__ uint32_t dg_pos_word(uint32_t sb) { return (sb & 0x3f
 // The best path passes through every cut vertex, so its stretch from one cut to the next is
 // walked by its own wave.  A segment leaves one byte per path vertex in its own stretch of
 // the scratch (ids of a segment are contiguous): the base, bit 7 = weight >= minWeight.
-template <bool SUP = false, bool POS = false>
-__global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
+// G: the pieces of k_cuts2 (partial-span pileups).  A piece's walk may then end at exit instead of at its next cut, and
+// piece 0 starts at enter, whose best edge leads anywhere: it stops at whichever cut it meets first, says in bp_end which
+// (k_bp_join chains the pieces from there), and has a stretch of scratch of its own (cns_tmp0 / sup_tmp0 / pos_tmp0),
+// since the ids it passes are other pieces'.
+template <bool SUP, bool POS, bool G>
+__device__ __forceinline__ void dg_bp_walk_wave(const DgParams &p) {
     constexpr bool SB = SUP || POS;                          // the walk carries _bbMap of its path bases
-    const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
-    if (dg_failed(p) || dg_tskip(p, t)) return;
-    const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
-    const uint32_t nseg = crow[0];
-    if (seg >= nseg) return;
+    DgBpPiece P;
+    if (!dg_bp_piece_open(p, blockIdx.x, P)) return;
+    const uint32_t t = P.t;
     const int lane = threadIdx.x;
-    const uint64_t nb = p.node_base[t];
+    const uint64_t nb = P.nb;
     __shared__ typename std::conditional<SB, DgWalkSharedS, DgWalkShared>::type W;
     const DgNode *nd = p.nodes + nb;
     const int32_t *best = p.best + nb;
-    const int N = (int)p.n_nodes[t];
+    const int N = P.N;
     for (int i = lane; i < DG_WR; i += 64) W.wtag[i] = -1;
-    const int c0 = (int)crow[1 + seg];
-    const int c1 = seg + 1 < nseg ? (int)crow[2 + seg] : -1;
+    const int c0 = P.c_bot, c1 = P.c_top;
+    const bool first = G && P.seg == 0;                      // the piece from enter
     const uint8_t eb = nd[0].base, xb = nd[N - 1].base;
     const int minw = p.min_weight;
-    uint8_t *tmp = p.cns_tmp + nb + c0;
+    uint8_t *tmp = first ? p.cns_tmp0 + nb : p.cns_tmp + nb + c0;
     int v = c0, cs = c0 >> 6, idx = 0;
     uint32_t steps = 0;
     bool bad = false;
     // SUP: a flushed row's depths are gathered when it is flushed and stored at the next flush (or at the end), so that
     // no load of the support waits on the walk's chain
     const int32_t *cov = SUP ? p.cov + p.bbv_base[t] : nullptr;
-    uint32_t *stmp = SUP ? p.sup_tmp + nb + c0 : nullptr;
-    uint32_t *ptmp = POS ? p.pos_tmp + nb + c0 : nullptr;     // POS: _bbMap itself, a second scratch word per path base; DG_POS_BB: a backbone vertex
+    uint32_t *stmp = SUP ? (first ? p.sup_tmp0 + nb : p.sup_tmp + nb + c0) : nullptr;
+    uint32_t *ptmp = POS ? (first ? p.pos_tmp0 + nb : p.pos_tmp + nb + c0) : nullptr;   // POS: _bbMap itself, a second scratch word per path base; DG_POS_BB: a backbone vertex
     uint32_t pw = 0;
     int32_t pdep = 0;
     int prow = -1;
     bool sbad = false;
+    int mycut = -1;                                          // G: lane k holds cut number k, for piece 0
+    uint32_t endk = first ? DG_BP_ONE : 0u;                  // G: piece 0: the cut number reached (DG_BP_ONE: exit); others: 1 = the next cut
+    if constexpr (G) { if ((uint32_t)lane >= 1u && (uint32_t)lane < P.nseg) mycut = (int)P.crow[1 + lane]; }
     for (;;) {
-        if (v == c1) break;                                  // the next segment starts here
+        if constexpr (G) {
+            if (!first) { if (v == c1) { endk = 1; break; } }
+            else if (v != c0) {
+                const unsigned long long hit = __ballot(mycut == v);
+                if (hit) { endk = (uint32_t)__ffsll((long long)hit) - 1u; break; }
+            }
+            if (v > 64 * cs + 512) cs = v >> 6;              // (a jump: enter's edges lead anywhere; the ring starts over there)
+        } else if (v == c1) break;                           // the next segment starts here
         while (64 * cs < N && 64 * cs < v + 192) {           // (best, base, weight) of 64 ids ahead
             const int id = 64 * cs + lane;
             if (id < N) {
@@ -880,8 +955,13 @@ __global__ __launch_bounds__(64) void k_bp_walk(DgParams p) {
     if (lane == 0) {
         if (bad) dg_fail_target(p, t, DG_E_INTERNAL);
         p.bp_len[blockIdx.x] = (uint32_t)idx;
+        if constexpr (G) p.bp_end[blockIdx.x] = endk;
     }
 }
+template <bool SUP = false, bool POS = false>
+__global__ __launch_bounds__(64) void k_bp_walk(DgParams p) { dg_bp_walk_wave<SUP, POS, false>(p); }
+template <bool SUP = false, bool POS = false>
+__global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) { dg_bp_walk_wave<SUP, POS, true>(p); }
 
 // ---- the same walk with a row of eight lanes per (target, segment): eight pieces per wave (round 3; where k_bp_sweep_l
 // runs).  A step is one dependent round trip -- best[v], the vertex's base and weight: three words, fetched by lanes
@@ -893,7 +973,7 @@ __global__ __launch_bounds__(64) void k_bp_walk_r(DgParams p) {
     if (dg_failed(p)) return;
     const int l = threadIdx.x & (DG_BRW - 1);
     const uint32_t piece = blockIdx.x * (64u / DG_BRW) + threadIdx.x / DG_BRW;
-    const uint32_t t = piece / p.bp_max, seg = piece % p.bp_max;
+    const uint32_t t = piece / p.bp_max, seg = piece % p.bp_max;      // (its own prologue: see k_bp_sweep_l)
     if (t >= p.T || dg_tskip(p, t)) return;
     const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
     const uint32_t nseg = crow[0];
@@ -999,6 +1079,11 @@ __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
     // every maximal run of path vertices with weight >= minWeight that is long enough
     bool met = false, ovf = false;
     uint32_t offs = 0, nout = 0, keep = 0;
+    auto emit_segment = [&](const uint32_t from, const uint32_t to) {      // a run [from, to): a segment if it is long enough
+        if (to - from < minlen) return;
+        if (nout < seg_cap) { if (lane == 0) { segs[2 * nout] = (int)from; segs[2 * nout + 1] = (int)to; } nout++; keep = to; }
+        else ovf = true;
+    };
     for (uint32_t s = 0; s < nseg; s++) {
         const uint32_t len = s_off[s + 1] - s_off[s], g0s = s_off[s];
         const uint8_t *src = (p.gcuts && s == 0) ? p.cns_tmp0 + nb : tmp + s_c0[s];
@@ -1015,21 +1100,12 @@ __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
                 const uint32_t f = pos + (uint32_t)__ffsll((long long)look) - 1u;
                 const uint32_t g = g0s + j0 + f;
                 if (!met) { offs = g; met = true; }
-                else {
-                    met = false;
-                    if (g - offs >= minlen) {
-                        if (nout < seg_cap) { if (lane == 0) { segs[2 * nout] = (int)offs; segs[2 * nout + 1] = (int)g; } nout++; keep = g; }
-                        else ovf = true;
-                    }
-                }
+                else { met = false; emit_segment(offs, g); }
                 pos = f + 1;
             }
         }
     }
-    if (met && total - offs >= minlen) {
-        if (nout < seg_cap) { if (lane == 0) { segs[2 * nout] = (int)offs; segs[2 * nout + 1] = (int)total; } nout++; keep = total; }
-        else ovf = true;
-    }
+    if (met) emit_segment(offs, total);
     // only the bases some segment covers are shipped
     __shared__ unsigned long long s_co, s_so;
     if (lane == 0) {
@@ -1048,29 +1124,21 @@ __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
         p.seg_first[t] = so; p.n_seg[t] = nout;
     }
     if (co == ~0ull) return;
-    uint8_t *out = p.cns + co;
-    for (uint32_t s = 0; s < nseg; s++) {
-        const uint32_t g0s = s_off[s], len = s_off[s + 1] - s_off[s];
-        const uint8_t *src = (p.gcuts && s == 0) ? p.cns_tmp0 + nb : tmp + s_c0[s];
-        for (uint32_t j = lane; j < len && g0s + j < keep; j += 64) out[g0s + j] = (uint8_t)(src[j] & 0x7fu);
-    }
-    if constexpr (SUP) {
+    // The kept prefix [0, keep) of the joined path, a lane per base: put(x, o) for the word x of the walks' scratch that
+    // goes to place o of the arena.  tmp: the walks' scratch, a piece's words at its first id; tmp0: piece 0's own, where
+    // the pieces are k_cuts2's.  A per-base output is one more call of this.
+    auto kept = [&](const auto *tmp0, const auto *tmp, auto put) {
         for (uint32_t s = 0; s < nseg; s++) {
             const uint32_t g0s = s_off[s], len = s_off[s + 1] - s_off[s];
-            const uint32_t *src = (p.gcuts && s == 0) ? p.sup_tmp0 + nb : p.sup_tmp + nb + s_c0[s];
-            for (uint32_t j = lane; j < len && g0s + j < keep; j += 64) {
-                const uint32_t x = src[j];
-                p.sup_w[co + g0s + j] = (uint16_t)(x & 0xffffu);
-                p.sup_d[co + g0s + j] = (uint16_t)(x >> 16);
-            }
+            const auto *src = (p.gcuts && s == 0) ? tmp0 + nb : tmp + nb + s_c0[s];
+            for (uint32_t j = lane; j < len && g0s + j < keep; j += 64) put(src[j], co + g0s + j);
         }
-    }
+    };
+    kept(p.cns_tmp0, p.cns_tmp, [&](const uint8_t x, const uint64_t o) { p.cns[o] = (uint8_t)(x & 0x7fu); });
+    if constexpr (SUP)
+        kept(p.sup_tmp0, p.sup_tmp, [&](const uint32_t x, const uint64_t o) { p.sup_w[o] = (uint16_t)(x & 0xffffu); p.sup_d[o] = (uint16_t)(x >> 16); });
     if constexpr (POS) {
-        for (uint32_t s = 0; s < nseg; s++) {
-            const uint32_t g0s = s_off[s], len = s_off[s + 1] - s_off[s];
-            const uint32_t *src = (p.gcuts && s == 0) ? p.pos_tmp0 + nb : p.pos_tmp + nb + s_c0[s];
-            for (uint32_t j = lane; j < len && g0s + j < keep; j += 64) p.pos_out[co + g0s + j] = p.ed_seg ? src[j] : src[j] & ~DG_POS_BB;
-        }
+        kept(p.pos_tmp0, p.pos_tmp, [&](const uint32_t x, const uint64_t o) { p.pos_out[o] = p.ed_seg ? x : x & ~DG_POS_BB; });
         // (edits: which target a segment belongs to, for the wave that scans it)
         if (p.ed_seg) for (uint32_t i = lane; i < nout; i += 64) p.ed_seg[so + i].tgt = t;
     }
@@ -1080,20 +1148,8 @@ __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
     }
 }
 
-
 // ====================================================================================
-// bestPath on the pieces of k_cuts2 (partial-span pileups, p.gcuts): see dg_bp_sweep.
-//   k_bp_xtree        the tree of vertices that lead to exit and nowhere else: absolute scores at once
-//   k_bp_sweep_ab     one sweep per piece for A (cut worth 0, exit -inf) and B (cut -inf, exit 0) of every vertex;
-//                     the last piece, which ends in the exit vertex, gets its absolute scores and choices at once
-//   k_bp_comb         per target: the absolute score of every cut, from the last one down:
-//                     score[c_k] = max(A_k + score[c_k+1], B_k); the exactness bound; deferred vertices reset
-//   k_bp_abs          the absolute score of every vertex of the other pieces: max(A + score[upper cut], B)
-//   k_bp_choose       their first-maximum choices, each from its own out-list
-//   k_bp_sweep_abs_g  a target that failed the bound, has too many deferred vertices or is one piece: one sweep, whole
-//   k_bp_defer        the deferred vertices nobody asked for (enter is the last of them)
-//   k_bp_walk_g       the best-edge walk in pieces: from every cut to the next cut or to exit, and from
-//                     enter to the first cut it meets;  k_bp_join chains the pieces that are on the path
+// bestPath on the pieces of k_cuts2 (partial-span pileups, p.gcuts): see dg_bp_sweep and the list at the top of the file.
 // ====================================================================================
 
 // the tree of vertices that lead to exit and nowhere else (see dg_bp_sweep): absolute scores, final flag 2.0
@@ -1118,8 +1174,7 @@ __global__ __launch_bounds__(64) void k_bp_xtree(DgParams p) {
             if (sv == 0) continue;                          // (enter is k_bp_defer's)
             const DgNode ns = nd[sv];
             if ((ns.flags & DG_NF_DELETED) || ns.out_len != 1 || p.score[nb + sv].y == 2.0f) continue;
-            const float w = td == DG_TT_TEN ? -10.0f : (float)(int)pool[ns.out_off + 1u] - td;       // :404-408
-            p.score[nb + sv] = make_float2(w + sz, 2.0f);
+            p.score[nb + sv] = make_float2(dg_bp_edge_w(td, (int)pool[ns.out_off + 1u]) + sz, 2.0f);
             p.best[nb + sv] = z;
             nd[sv].flags |= DG_NF_DEFER;                    // the segments' streams pass over it
             if (qt < N) q[qt++] = sv;
@@ -1130,25 +1185,12 @@ __global__ __launch_bounds__(64) void k_bp_xtree(DgParams p) {
 // the targets that k_bp_sweep_ab's pieces do not take, in one piece as the reference does it (every vertex in the
 // stream, the deferred ones too)
 __global__ __launch_bounds__(64) void k_bp_sweep_abs_g(DgParams p) {
-    const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
-    if (dg_failed(p) || dg_tskip(p, t)) return;
-    const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
-    const uint32_t nseg = crow[0];
-    if (seg >= nseg) return;
-    const int lane = threadIdx.x;
-    const uint64_t nb = p.node_base[t];
+    DgBpPiece P;
+    if (!dg_bp_piece_open(p, blockIdx.x, P)) return;
     __shared__ DgBpShared S;
-    const int N = (int)p.n_nodes[t];
-    float2 *score = p.score + nb;
-    const bool one = p.defer[(uint64_t)t * (DG_DEFER_MAX + 1u)] == DG_BP_ONE || nseg <= 1;
-    if (!one || seg != 0) return;
-    float amax = 0.0f;
-    bool bad = false, stuck = false;
-    for (int i = lane; i < N; i += 64) score[i] = make_float2(0.0f, 0.0f);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    dg_bp_sweep(S, p.nodes + nb, p.best + nb, score, p.pool + p.pool_base[t], p.bp_tt + nb, N - 1, 0, -1,
-                p.stk + (uint64_t)blockIdx.x * p.stk_words, (int)p.stk_words, lane, amax, bad, stuck);
-    if (bad && lane == 0) { if (stuck) dg_fail_target(p, t, DG_E_INTERNAL); else { dg_fail(p, DG_E_STACK); p.st->bad_target = t; } }
+    const bool one = p.defer[(uint64_t)P.t * (DG_DEFER_MAX + 1u)] == DG_BP_ONE || P.nseg <= 1;
+    if (!one || P.seg != 0) return;
+    dg_bp_sweep_whole(p, P.t, S, p.stk + (uint64_t)blockIdx.x * p.stk_words, (int)threadIdx.x);
 }
 
 // ---- the pieces in ONE sweep ----------------------------------------------------------------------------------------
@@ -1160,23 +1202,20 @@ __global__ __launch_bounds__(64) void k_bp_sweep_abs_g(DgParams p) {
 // on the way -- the maximum it finds must BE the vertex's
 // absolute score, else the target is swept again in one piece.
 __global__ __launch_bounds__(64) void k_bp_sweep_ab(DgParams p) {
-    const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
-    if (dg_failed(p) || dg_tskip(p, t)) return;
-    const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
-    const uint32_t nseg = crow[0];
-    if (seg >= nseg) return;
-    if (p.defer[(uint64_t)t * (DG_DEFER_MAX + 1u)] == DG_BP_ONE || nseg <= 1) return;       // k_bp_sweep_abs_g has it, whole
+    DgBpPiece P;
+    if (!dg_bp_piece_open(p, blockIdx.x, P)) return;
+    const uint32_t t = P.t;
+    if (p.defer[(uint64_t)t * (DG_DEFER_MAX + 1u)] == DG_BP_ONE || P.nseg <= 1) return;     // k_bp_sweep_abs_g has it, whole
     const int lane = threadIdx.x;
-    const uint64_t nb = p.node_base[t];
+    const uint64_t nb = P.nb;
     __shared__ DgBpShared S;
     __shared__ DgBpSharedB SB;
-    const int N = (int)p.n_nodes[t];
+    const int N = P.N;
     float2 *score = p.score + nb;
     float amax = 0.0f;
     bool bad = false, stuck = false;
-    const bool last = seg + 1 == nseg;
-    const int c_bot = (int)crow[1 + seg];
-    const int c_top = last ? -1 : (int)crow[2 + seg];
+    const int c_bot = P.c_bot, c_top = P.c_top;
+    const bool last = c_top < 0;
     const int v_top = last ? N - 1 : c_top - 1;
     float *ab = p.bp_ab + 4ull * blockIdx.x;
     if (last)       // the last piece ends in exit: its scores are absolute at once, its choices final
@@ -1193,21 +1232,17 @@ __global__ __launch_bounds__(64) void k_bp_sweep_ab(DgParams p) {
         const float b = last ? 0.0f : p.score_b[nb + c_bot];
         if (lane == 0) { ab[0] = a; ab[1] = b; ab[3] = amax; }
     }
-    if (bad && lane == 0) { if (stuck) dg_fail_target(p, t, DG_E_INTERNAL); else { dg_fail(p, DG_E_STACK); p.st->bad_target = t; } }
+    if (bad && lane == 0) dg_bp_sweep_failed(p, t, stuck);
 }
 
 // absolute scores of the pieces' vertices: max(A + score[upper cut], B); one block per (target, piece)
 __global__ __launch_bounds__(256) void k_bp_abs(DgParams p) {
-    const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
-    if (dg_failed(p) || dg_tskip(p, t)) return;
-    const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
-    const uint32_t nseg = crow[0];
-    if (seg + 1 >= nseg) return;                                       // (the last piece is absolute already)
-    if (p.defer[(uint64_t)t * (DG_DEFER_MAX + 1u)] == DG_BP_ONE) return;
-    const uint64_t nb = p.node_base[t];
+    DgBpPiece P;
+    if (!dg_bp_piece_open(p, blockIdx.x, P) || P.c_top < 0) return;     // (the last piece is absolute already)
+    if (p.defer[(uint64_t)P.t * (DG_DEFER_MAX + 1u)] == DG_BP_ONE) return;
+    const uint64_t nb = P.nb;
     const float s = p.bp_ab[4ull * blockIdx.x + 2];
-    const int c_bot = (int)crow[1 + seg], c_top = (int)crow[2 + seg];
-    for (int v = c_bot + (int)threadIdx.x; v < c_top; v += 256) {
+    for (int v = P.c_bot + (int)threadIdx.x; v < P.c_top; v += 256) {
         const float2 sg = p.score[nb + v];
         if (sg.y != 1.0f) continue;                                    // not scored (deleted, deferred) or the exit tree's (2.0: absolute)
         const float via_a = sg.x + s, via_b = p.score_b[nb + v];
@@ -1216,38 +1251,41 @@ __global__ __launch_bounds__(256) void k_bp_abs(DgParams p) {
 }
 
 // the first-maximum choice of every vertex of the pieces (AlnGraphBoost.cpp:399-416), from absolute scores
+// One vertex's choice from the scores in HBM: the first maximum over its out-list in list order, strict '>' (:399-416).
+// Returns the maximum (0 and bd = -1 without an out-edge: the exit vertex, the map default).  ready: every successor
+// has a final score -- but for xid, which counts as it stands (the exit vertex has no score of its own: 0).  STOP: the
+// loop ends at the first successor that has none (the result is not used then).
+template <bool STOP>
+__device__ __forceinline__ float dg_bp_first_max(const DgNode *nd, const uint32_t *pool, const float *tt, const float2 *score,
+                                                 const int v, const int xid, int &bd, bool &ready) {
+    const uint32_t out_len = nd[v].out_len, out_off = nd[v].out_off;
+    float mx = 0.0f;
+    bd = -1; ready = true;
+    for (uint32_t e = 0; e < out_len; e++) {
+        const int d = (int)pool[out_off + 2u * e];
+        const float2 sd = score[d];
+        if (sd.y < 1.0f && d != xid) { ready = false; if (STOP) break; }
+        const float ns = dg_bp_edge_w(tt[d], (int)pool[out_off + 2u * e + 1u]) + sd.x;
+        if (e == 0 || ns > mx) { mx = ns; bd = d; }
+    }
+    return mx;
+}
+
 __global__ __launch_bounds__(256) void k_bp_choose(DgParams p) {
-    const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
-    if (dg_failed(p) || dg_tskip(p, t)) return;
-    const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
-    const uint32_t nseg = crow[0];
-    if (seg + 1 >= nseg) return;
-    uint32_t *dl = p.defer + (uint64_t)t * (DG_DEFER_MAX + 1u);
+    DgBpPiece P;
+    if (!dg_bp_piece_open(p, blockIdx.x, P) || P.c_top < 0) return;
+    uint32_t *dl = p.defer + (uint64_t)P.t * (DG_DEFER_MAX + 1u);
     if (dl[0] == DG_BP_ONE) return;
-    const uint64_t nb = p.node_base[t];
-    const DgNode *nd = p.nodes + nb;
-    const uint32_t *pool = p.pool + p.pool_base[t];
-    const float *tt = p.bp_tt + nb;
+    const uint64_t nb = P.nb;
     const float2 *score = p.score + nb;
-    const int c_bot = (int)crow[1 + seg], c_top = (int)crow[2 + seg];
     bool wrong = false;
-    for (int v = c_bot + (int)threadIdx.x; v < c_top; v += 256) {
+    for (int v = P.c_bot + (int)threadIdx.x; v < P.c_top; v += 256) {
         const float2 sv = score[v];
         if (sv.y != 1.0f) continue;
-        const uint4 h = *reinterpret_cast<const uint4 *>(&nd[v]);
-        const uint32_t out_len = h.x & 0xffffu, out_off = (reinterpret_cast<const uint4 *>(&nd[v]) + 1)->x;
-        float mx = 0.0f;
-        int bd = -1;
-        for (uint32_t e = 0; e < out_len; e++) {
-            const int d = (int)pool[out_off + 2u * e];
-            const float2 sd = score[d];
-            const float td = tt[d];
-            const float w = td == DG_TT_TEN ? -10.0f : (float)(int)pool[out_off + 2u * e + 1u] - td;     // :404-408
-            const float ns = w + sd.x;
-            // (the exit vertex has no score of its own: 0, the map default; every other successor has one by now)
-            if (sd.y < 1.0f && d != (int)p.n_nodes[t] - 1) wrong = true;
-            if (e == 0 || ns > mx) { mx = ns; bd = d; }                 // strict '>': the first maximum wins
-        }
+        int bd;
+        bool ready;
+        const float mx = dg_bp_first_max<false>(p.nodes + nb, p.pool + p.pool_base[P.t], p.bp_tt + nb, score, v, P.N - 1, bd, ready);
+        if (!ready) wrong = true;                                       // every successor but exit has its score by now
         if (mx != sv.x) wrong = true;                                   // the recurrence must hold with the absolute scores
         p.best[nb + v] = bd;
     }
@@ -1263,18 +1301,15 @@ __global__ __launch_bounds__(64) void k_bp_comb(DgParams p) {
     if (nseg <= 1 || dl[0] == DG_BP_ONE) return;
     const uint64_t nb = p.node_base[t];
     if (threadIdx.x == 0) {
-        // every score is a multiple of 0.5: fp32 is exact below 2^23.  What the pieces' relative and the
-        // reference's absolute arithmetic can form stays below 2^22 if every piece's largest value, the
-        // absolute score of its upper cut and one edge term do (k_bp_check has the argument); else one piece
+        // the bound (dg_bp_exact) on every piece, with the absolute score of its upper cut; else one piece
         bool redo = (p.flags & DG_F_RESWEEP) != 0;
-        const float K = (float)(uint32_t)(p.aln_begin[t + 1] - p.aln_begin[t]);
-        const float wmax = K > 10.0f ? K : 10.0f;
+        const float wmax = dg_bp_wmax(p, t);
         float *ab = p.bp_ab + 4ull * ((uint64_t)t * p.bp_max);
         float abs_ = ab[4 * (nseg - 1)];                                   // the last piece's first vertex, absolute (also when k_bp_xtree scored it)
-        if (!(ab[4 * (nseg - 1) + 3] + wmax < 4194304.0f)) redo = true;
+        if (!dg_bp_exact(ab[4 * (nseg - 1) + 3], 0.0f, wmax)) redo = true; // (the last piece ends in exit: nothing above it)
         for (int k = nseg - 2; k >= 0; k--) {
             ab[4 * k + 2] = abs_;
-            if (!(ab[4 * k + 3] + fabsf(abs_) + wmax < 4194304.0f)) redo = true;
+            if (!dg_bp_exact(ab[4 * k + 3], abs_, wmax)) redo = true;
             if (k >= 1) {
                 const float2 sc = p.score[nb + crow[1 + k]];
                 const float viaA = ab[4 * k] + abs_, viaB = ab[4 * k + 1];
@@ -1309,121 +1344,13 @@ __global__ __launch_bounds__(64) void k_bp_defer(DgParams p) {
         for (uint32_t i = 0; i < n; i++) {
             const int v = (int)dl[1 + i];
             if (score[v].y >= 1.0f || (nd[v].flags & DG_NF_DELETED)) continue;
-            const DgNode nv = nd[v];
-            bool ready = true;
-            float mx = 0.0f;
-            int bd = -1;
-            for (uint32_t e = 0; e < nv.out_len; e++) {
-                const int d = (int)pool[nv.out_off + 2u * e];
-                const float2 sd = score[d];
-                if (sd.y < 1.0f) { ready = false; break; }
-                const float td = tt[d];
-                const float w = td == DG_TT_TEN ? -10.0f : (float)(int)pool[nv.out_off + 2u * e + 1u] - td;     // :404-408
-                const float ns = w + sd.x;
-                if (e == 0 || ns > mx) { mx = ns; bd = d; }                 // :399-416 first maximum, strict '>'
-            }
+            int bd;
+            bool ready;
+            const float mx = dg_bp_first_max<true>(nd, pool, tt, score, v, -1, bd, ready);
             if (!ready) { left++; continue; }
             score[v] = make_float2(mx, 1.0f);
             best[v] = bd;
         }
     }
     if (left) dg_fail_target(p, t, DG_E_INTERNAL);
-}
-
-template <bool SUP = false, bool POS = false>
-__global__ __launch_bounds__(64) void k_bp_walk_g(DgParams p) {
-    constexpr bool SB = SUP || POS;
-    const uint32_t t = blockIdx.x / p.bp_max, seg = blockIdx.x % p.bp_max;
-    if (dg_failed(p) || dg_tskip(p, t)) return;
-    const uint32_t *crow = p.cuts_bp + (uint64_t)t * (p.bp_max + 2u);
-    const uint32_t nseg = crow[0];
-    if (seg >= nseg) return;
-    const int lane = threadIdx.x;
-    const uint64_t nb = p.node_base[t];
-    __shared__ typename std::conditional<SB, DgWalkSharedS, DgWalkShared>::type W;
-    const DgNode *nd = p.nodes + nb;
-    const int32_t *best = p.best + nb;
-    const int N = (int)p.n_nodes[t];
-    for (int i = lane; i < DG_WR; i += 64) W.wtag[i] = -1;
-    const int c0 = (int)crow[1 + seg];
-    const int c1 = seg + 1 < nseg ? (int)crow[2 + seg] : -1;
-    const int mycut = (uint32_t)lane >= 1u && (uint32_t)lane < nseg ? (int)crow[1 + lane] : -1;   // piece 0 stops at any cut
-    const uint8_t eb = nd[0].base, xb = nd[N - 1].base;
-    const int minw = p.min_weight;
-    uint8_t *tmp = seg == 0 ? p.cns_tmp0 + nb : p.cns_tmp + nb + c0;
-    int v = c0, cs = c0 >> 6, idx = 0;
-    uint32_t steps = 0, endk = 0;                          // endk: piece 0: cut index reached (DG_BP_ONE: exit); others: 1 = the next cut
-    bool bad = false;
-    const int32_t *cov = SUP ? p.cov + p.bbv_base[t] : nullptr;    // (SUP: as in k_bp_walk)
-    uint32_t *stmp = SUP ? (seg == 0 ? p.sup_tmp0 + nb : p.sup_tmp + nb + c0) : nullptr;
-    uint32_t *ptmp = POS ? (seg == 0 ? p.pos_tmp0 + nb : p.pos_tmp + nb + c0) : nullptr;
-    uint32_t pw = 0;
-    int32_t pdep = 0;
-    int prow = -1;
-    bool sbad = false;
-    if (seg == 0) endk = DG_BP_ONE;
-    for (;;) {
-        if (seg != 0) { if (v == c1) { endk = 1; break; } }
-        else if (v != c0) {
-            const unsigned long long hit = __ballot(mycut == v);
-            if (hit) { endk = (uint32_t)__ffsll((long long)hit) - 1u; break; }
-        }
-        if (v > 64 * cs + 512) cs = v >> 6;                  // (a jump: enter's edges lead anywhere)
-        while (64 * cs < N && 64 * cs < v + 192) {           // (best, base, weight) of 64 ids ahead
-            const int id = 64 * cs + lane;
-            if (id < N) {
-                const uint4 h = *reinterpret_cast<const uint4 *>(&nd[id]);
-                const int b = best[id];
-                const int xw = id & (DG_WR - 1);
-                W.wtag[xw] = id; W.wbest[xw] = b; W.wbase[xw] = (int)(h.y & 0xffu); W.wweight[xw] = (int)h.z;
-                if constexpr (SB) W.wbase[xw] = (int)(h.y & 0xffu) | (nd[id].bbpos << 8);     // (bbpos < 2^18)
-                if constexpr (POS) W.wbase[xw] |= (int)(((h.y >> 8) & DG_NF_BACKBONE) << 30);  // the vertex's kind rides above it
-            }
-            cs++;
-        }
-        const int xw = v & (DG_WR - 1);
-        int nxt, w, bbp = 0;
-        uint8_t base;
-        const int wt = W.wtag[xw], wb = W.wbest[xw], wa = W.wbase[xw], ww = W.wweight[xw];
-        if (__builtin_amdgcn_readfirstlane(wt) == v) {
-            nxt = __builtin_amdgcn_readfirstlane(wb); base = (uint8_t)__builtin_amdgcn_readfirstlane(wa);
-            w = __builtin_amdgcn_readfirstlane(ww);
-            if constexpr (SB) bbp = __builtin_amdgcn_readfirstlane(wa) >> 8;
-        } else {
-            const uint4 h = *reinterpret_cast<const uint4 *>(&nd[v]);
-            nxt = __builtin_amdgcn_readfirstlane(best[v]);
-            base = (uint8_t)__builtin_amdgcn_readfirstlane((int)(h.y & 0xffu));
-            w = __builtin_amdgcn_readfirstlane((int)h.z);
-            if constexpr (SB) bbp = __builtin_amdgcn_readfirstlane(nd[v].bbpos);
-            if constexpr (POS) bbp |= __builtin_amdgcn_readfirstlane((int)(((h.y >> 8) & DG_NF_BACKBONE) << 22));
-        }
-        if (!(base == eb || base == xb)) {
-            if (lane == 0) W.wbuf[idx & 63] = (unsigned char)(base | (w >= minw ? 0x80u : 0u));
-            if constexpr (SB) { if (lane == 0) { W.sw[idx & 63] = (uint32_t)w; W.sb[idx & 63] = (uint32_t)bbp; } }
-            if ((idx & 63) == 63) {
-                tmp[(idx & ~63) + lane] = W.wbuf[lane];
-                if constexpr (SUP) {
-                    if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
-                    pw = W.sw[lane]; pdep = cov[W.sb[lane] & DG_WALK_BBM(POS)]; prow = idx & ~63;
-                }
-                if constexpr (POS) ptmp[(idx & ~63) + lane] = dg_pos_word(W.sb[lane]);
-            }
-            idx++;
-        }
-        if (nxt < 0) break;
-        v = nxt;
-        if (++steps > (uint32_t)N) { bad = true; break; }
-    }
-    if (lane < (idx & 63)) tmp[(idx & ~63) + lane] = W.wbuf[lane];     // the last, partial row
-    if constexpr (SUP) {
-        if (prow >= 0) sbad |= dg_sup_put(stmp + prow + lane, pw, pdep);
-        if (lane < (idx & 63)) sbad |= dg_sup_put(stmp + (idx & ~63) + lane, W.sw[lane], cov[W.sb[lane] & DG_WALK_BBM(POS)]);
-        if (__ballot(sbad)) bad = true;
-    }
-    if constexpr (POS) { if (lane < (idx & 63)) ptmp[(idx & ~63) + lane] = dg_pos_word(W.sb[lane]); }
-    if (lane == 0) {
-        if (bad) dg_fail_target(p, t, DG_E_INTERNAL);
-        p.bp_len[blockIdx.x] = (uint32_t)idx;
-        p.bp_end[blockIdx.x] = endk;
-    }
 }

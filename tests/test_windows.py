@@ -307,6 +307,39 @@ def test_positions_partial_span_pileups():
     assert len(flat) != len(set(flat))
 
 
+def _shifted_pileup(rng, tlen, lo, hi, n_reads):
+    """A random_target pileup over positions [lo, hi) of a longer random backbone: nothing covers the rest."""
+    alns, bb = random_target(rng, hi - lo, n_reads, sub=0.04, ins=0.08, dele=0.05)
+    fill = bytes(b"ACGT"[i] for i in rng.integers(0, 4, tlen - (hi - lo)))
+    return tlen, [(s + lo, q, t) for s, q, t in alns], fill[:lo] + bb + fill[lo:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_backbone", [False, True])
+def test_positions_walk_lands_far_from_enter(with_backbone):
+    """k_bp_walk_g's first piece when enter's best edge lands hundreds of ids away (the staging ring starts over after
+    the jump; the piece stops at a cut that is not the first one), and a path that leaves for exit early.  With the
+    backbones the uncovered vertices have weight 1: the -10 edges."""
+    from pbdagcon_amd import capi
+    rng = np.random.default_rng(7)
+    targets = [_shifted_pileup(rng, 1500, 900, 1500, 12), _shifted_pileup(rng, 1500, 0, 600, 12),
+               _shifted_pileup(rng, 2000, 700, 1400, 16)]
+    batch = batch_from_targets(targets, with_backbone=with_backbone)
+    exp = oracle_batch(batch, 3, 100, 5)
+    exp_pos = wt.batch_positions(batch, 3, 100, 5)
+    # what the test is about, on the reference's answer alone: the path's first base lies far behind enter (targets 0, 2),
+    # its last one far before exit (target 1)
+    assert all(len(segs) >= 1 for segs in exp_pos)
+    lo = [min(p for s in segs for p in s[3]) for segs in exp_pos]
+    hi = [max(p for s in segs for p in s[3]) for segs in exp_pos]
+    assert lo[0] >= 800 and hi[1] <= 700 and lo[2] >= 600, (lo, hi)
+    kw = dict(min_cov=3, min_len=100, trim=5)
+    for extra, more in ((0, dict(max_segments=0)), (capi.FLAG_DEBUG_RESWEEP, dict(max_segments=0)),
+                        (0, dict(max_segments=64)), (capi.FLAG_DEBUG_RESWEEP, dict(max_segments=64)),
+                        (0, dict(max_segments=16, min_segment_len=4))):
+        _both_ways(batch, exp, exp_pos, extra, **kw, **more)
+
+
 @pytest.mark.gpu
 def test_positions_real_backbone_and_resweep():
     from pbdagcon_amd import capi, synth

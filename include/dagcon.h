@@ -57,7 +57,8 @@ typedef enum dagcon_status {
                                            dagcon_debug_graph shows the graph before mergeNodes */
 #define DAGCON_FLAG_STOP_AFTER_MERGE 4u /* debug: stop after mergeNodes */
 #define DAGCON_FLAG_DEBUG_RESWEEP 16u   /* debug: treat the segmented bestPath sweep as inexact, so that
-                                           every target takes the one-piece re-sweep (tests only) */
+                                           every target takes the one-piece re-sweep (tests only; targets that take
+                                           it by themselves, scores past 2^22: tests/test_bestpath_bound.py) */
 #define DAGCON_FLAG_LOCAL_ALIGN 32u    /* dagcon_align / dagcon_consensus_pre align local ends (see dagcon_align):
                                           read ends that do not align stay out of the alignment */
 #define DAGCON_FLAG_BASE_SUPPORT 64u  /* keep the support of every consensus base: dagcon_fetch_support */

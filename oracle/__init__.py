@@ -369,8 +369,16 @@ def faithful_lib():
     return _CF
 
 
+class ScoreStats(C.Structure):
+    _fields_ = [("enter", C.c_double), ("min", C.c_double), ("max", C.c_double)]
+
+
 def consensus_target_blob(tlen, starts, offs, lens, qblob, tblob, min_len=500, trim=50,
-                          min_weight=6, backbone=None, faithful=False):
+                          min_weight=6, backbone=None, faithful=False, wide=False, stats=False):
+    """main.cpp:130-138 for one target from the batch layout: [(range0, range1, seq)].
+    stats=True: (segments, {"enter", "min", "max"}) -- bestPath's score[enter] and its smallest and largest score over
+    all vertices (og_consensus_target_blob_stats).  wide=True (implies that entry point): the recurrence in double,
+    which is exact arithmetic; the default is the reference's fp32."""
     import numpy as np
     L = lib()
     o = Opts(min_len, trim, min_weight)
@@ -378,17 +386,30 @@ def consensus_target_blob(tlen, starts, offs, lens, qblob, tblob, min_len=500, t
     bad = C.c_long(-1)
     qp = qblob.ctypes.data if isinstance(qblob, np.ndarray) else C.cast(C.c_char_p(qblob), C.c_void_p)
     tp = tblob.ctypes.data if isinstance(tblob, np.ndarray) else C.cast(C.c_char_p(tblob), C.c_void_p)
-    fn = faithful_lib().cf_consensus_target_blob if faithful else L.og_consensus_target_blob
-    rc = fn(
-        tlen, backbone, len(starts),
-        starts.ctypes.data_as(C.POINTER(C.c_uint32)),
-        offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-        lens.ctypes.data_as(C.POINTER(C.c_uint32)),
-        qp, tp, C.byref(o), C.byref(segs), C.byref(bad))
+    args = [tlen, backbone, len(starts),
+            starts.ctypes.data_as(C.POINTER(C.c_uint32)),
+            offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+            lens.ctypes.data_as(C.POINTER(C.c_uint32)),
+            qp, tp, C.byref(o)]
+    st = ScoreStats()
+    if wide or stats:
+        if faithful:
+            raise ValueError("the faithful build has neither wide nor stats")
+        L.og_consensus_target_blob_stats.restype = C.c_long
+        L.og_consensus_target_blob_stats.argtypes = [
+            C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+            C.c_void_p, C.c_void_p, C.POINTER(Opts), C.c_int, C.POINTER(C.POINTER(Segment)), C.POINTER(C.c_long),
+            C.POINTER(ScoreStats)]
+        rc = L.og_consensus_target_blob_stats(*args, int(bool(wide)), C.byref(segs), C.byref(bad), C.byref(st))
+    else:
+        fn = faithful_lib().cf_consensus_target_blob if faithful else L.og_consensus_target_blob
+        rc = fn(*args, C.byref(segs), C.byref(bad))
     if rc == -2:
         raise ValueError(f"non-conforming alignment #{bad.value}")
     if rc < 0:
         raise RuntimeError("oracle hit a state the reference treats as undefined")
     out = [(segs[i].range0, segs[i].range1, segs[i].seq) for i in range(rc)]
     L.og_free_segments(segs, rc)
+    if stats:
+        return out, {"enter": st.enter, "min": st.min, "max": st.max}
     return out

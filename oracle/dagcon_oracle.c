@@ -771,6 +771,78 @@ size_t og_best_path(og_graph *g, int32_t **path_out) {
     return pn;
 }
 
+/* og_best_path once more, for the tests that need to know how large the scores got: the same traversal, the same
+ * list order and strict '>', with the scores in T -- float: the operations of og_best_path, value for value; double:
+ * the recurrence as exact arithmetic has it (every value is a multiple of 0.5, far below 2^53).  og_best_path itself
+ * stays as it is: it is the checker, and this one is checked against it. */
+#define OG_BEST_PATH_T(NAME, T, T_LOWEST, C10, CHALF)                                                    \
+static size_t NAME(og_graph *g, int32_t **path_out, og_score_stats *st) {                               \
+    for (size_t e = 0; e < g->ne; e++) g->edges[e].visited = 0;                                          \
+    int32_t *best_edge = (int32_t *)malloc(g->nn * sizeof(int32_t));                                     \
+    T *score = (T *)calloc(g->nn, sizeof(T));                                                            \
+    for (size_t i = 0; i < g->nn; i++) best_edge[i] = -1;                                                \
+    size_t qcap = g->nn + 16, qh = 0, qt = 0;                                                            \
+    int32_t *queue = (int32_t *)malloc(qcap * sizeof(int32_t));                                          \
+    queue[qt++] = g->exit_;                                                                              \
+    score[g->exit_] = 0;                                                                                 \
+    T lo = 0, hi = 0;                                                                                    \
+    while (qh < qt) {                                                                                    \
+        int32_t n = queue[qh++];                                                                         \
+        int found = 0;                                                                                   \
+        T best = T_LOWEST;                                                                               \
+        int32_t best_e = -1;                                                                             \
+        for (size_t i = 0; i < g->nodes[n].out.n; i++) {                                                 \
+            int32_t oe = g->nodes[n].out.v[i];                                                           \
+            int32_t t = g->edges[oe].dst;                                                                \
+            const og_node *tn = &g->nodes[t];                                                            \
+            T s = score[t], ns;                                                                          \
+            if (tn->backbone && tn->weight == 1) {                                                       \
+                ns = s - C10;                                                                            \
+            } else {                                                                                     \
+                const og_node *bb = &g->nodes[tn->bbmap];                                                \
+                ns = (T)g->edges[oe].count - (T)bb->coverage * CHALF + s;                                \
+            }                                                                                            \
+            if (ns > best) { best = ns; best_e = oe; found = 1; }                                        \
+        }                                                                                                \
+        if (found) { score[n] = best; best_edge[n] = best_e; }                                           \
+        if (score[n] < lo) lo = score[n];                                                                \
+        if (score[n] > hi) hi = score[n];                                                                \
+        for (size_t i = 0; i < g->nodes[n].in.n; i++) {                                                  \
+            og_edge *ie = &g->edges[g->nodes[n].in.v[i]];                                                \
+            ie->visited = 1;                                                                             \
+            int32_t s = ie->src;                                                                         \
+            int not_visited = 0;                                                                         \
+            for (size_t k = 0; k < g->nodes[s].out.n; k++)                                               \
+                if (!g->edges[g->nodes[s].out.v[k]].visited) not_visited++;                              \
+            if (not_visited == 0) {                                                                      \
+                if (qt == qcap) { qcap *= 2; queue = (int32_t *)realloc(queue, qcap * sizeof(int32_t)); } \
+                queue[qt++] = s;                                                                         \
+            }                                                                                            \
+        }                                                                                                \
+    }                                                                                                    \
+    st->enter = (double)score[g->enter]; st->min = (double)lo; st->max = (double)hi;                     \
+    size_t pcap = 64, pn = 0;                                                                            \
+    int32_t *path = (int32_t *)malloc(pcap * sizeof(int32_t));                                           \
+    int32_t prev = g->enter;                                                                             \
+    for (;;) {                                                                                           \
+        if (pn == pcap) { pcap *= 2; path = (int32_t *)realloc(path, pcap * sizeof(int32_t)); }          \
+        path[pn++] = prev;                                                                               \
+        if (best_edge[prev] < 0) break;                                                                  \
+        prev = g->edges[best_edge[prev]].dst;                                                            \
+        if (pn > g->nn + 1) { g->error = 1; break; }                                                     \
+    }                                                                                                    \
+    free(queue); free(score); free(best_edge);                                                           \
+    *path_out = path;                                                                                    \
+    return pn;                                                                                           \
+}
+OG_BEST_PATH_T(best_path_stats_f32, float, -FLT_MAX, 10.0f, 0.5f)
+OG_BEST_PATH_T(best_path_stats_f64, double, -DBL_MAX, 10.0, 0.5)
+#undef OG_BEST_PATH_T
+
+size_t og_best_path_stats(og_graph *g, int wide, int32_t **path_out, og_score_stats *st) {
+    return wide ? best_path_stats_f64(g, path_out, st) : best_path_stats_f32(g, path_out, st);
+}
+
 /* AlnGraphBoost.cpp:285-325 */
 char *og_consensus_longest(og_graph *g, int min_weight) {
     int32_t *path; size_t pn = og_best_path(g, &path);
@@ -794,9 +866,9 @@ char *og_consensus_longest(og_graph *g, int min_weight) {
     return r;
 }
 
-/* AlnGraphBoost.cpp:327-373 */
-size_t og_consensus_all(og_graph *g, int min_weight, size_t min_len, og_segment **segs_out) {
-    int32_t *path; size_t pn = og_best_path(g, &path);
+/* AlnGraphBoost.cpp:327-373, behind its call of bestPath; frees path */
+static size_t consensus_all_path(og_graph *g, int32_t *path, size_t pn, int min_weight, size_t min_len,
+                                 og_segment **segs_out) {
     char *cns = (char *)malloc(pn + 1);
     size_t ns = 0, scap = 4;
     og_segment *segs = (og_segment *)malloc(scap * sizeof(og_segment));
@@ -827,6 +899,11 @@ size_t og_consensus_all(og_graph *g, int min_weight, size_t min_len, og_segment 
     free(cns); free(path);
     *segs_out = segs;
     return ns;
+}
+
+size_t og_consensus_all(og_graph *g, int min_weight, size_t min_len, og_segment **segs_out) {
+    int32_t *path; size_t pn = og_best_path(g, &path);
+    return consensus_all_path(g, path, pn, min_weight, min_len, segs_out);
 }
 
 void og_free_segments(og_segment *segs, size_t n) {
@@ -904,7 +981,8 @@ static long consensus_target_impl(uint32_t tlen, const char *backbone, size_t n_
                                   const char *const *tstrs, const uint64_t *offs,
                                   const uint32_t *lens32, const size_t *lens,
                                   const char *qblob, const char *tblob,
-                                  const og_opts *opts, og_segment **segs, long *bad_aln) {
+                                  const og_opts *opts, og_segment **segs, long *bad_aln,
+                                  int wide, og_score_stats *stats) {
     og_graph *g = backbone ? og_graph_new_seq(backbone, tlen) : og_graph_new_len(tlen);
     size_t cap = 0;
     char *qn = NULL, *tn = NULL;
@@ -932,7 +1010,12 @@ static long consensus_target_impl(uint32_t tlen, const char *backbone, size_t n_
     int rc = og_merge_nodes(g);                                  /* main.cpp:137 */
     long ns = -1;
     if (rc == 0) {
-        ns = (long)og_consensus_all(g, opts->min_weight, opts->min_len, segs); /* :138 */
+        if (stats) {                                             /* (og_consensus_target_blob_stats) */
+            int32_t *path; size_t pn = og_best_path_stats(g, wide, &path, stats);
+            ns = (long)consensus_all_path(g, path, pn, opts->min_weight, opts->min_len, segs);
+        } else {
+            ns = (long)og_consensus_all(g, opts->min_weight, opts->min_len, segs); /* :138 */
+        }
         if (g->error) { og_free_segments(*segs, (size_t)ns); *segs = NULL; ns = -1; }
     }
     og_graph_free(g);
@@ -944,7 +1027,7 @@ long og_consensus_target(uint32_t tlen, const char *backbone, size_t n_alns,
                          const char *const *tstrs, const size_t *lens,
                          const og_opts *opts, og_segment **segs, long *bad_aln) {
     return consensus_target_impl(tlen, backbone, n_alns, starts, qstrs, tstrs, NULL, NULL,
-                                 lens, NULL, NULL, opts, segs, bad_aln);
+                                 lens, NULL, NULL, opts, segs, bad_aln, 0, NULL);
 }
 
 long og_consensus_target_blob(uint32_t tlen, const char *backbone, size_t n_alns,
@@ -953,5 +1036,14 @@ long og_consensus_target_blob(uint32_t tlen, const char *backbone, size_t n_alns
                               const char *tblob, const og_opts *opts,
                               og_segment **segs, long *bad_aln) {
     return consensus_target_impl(tlen, backbone, n_alns, starts, NULL, NULL, offs, lens,
-                                 NULL, qblob, tblob, opts, segs, bad_aln);
+                                 NULL, qblob, tblob, opts, segs, bad_aln, 0, NULL);
+}
+
+long og_consensus_target_blob_stats(uint32_t tlen, const char *backbone, size_t n_alns,
+                                    const uint32_t *starts, const uint64_t *offs,
+                                    const uint32_t *lens, const char *qblob,
+                                    const char *tblob, const og_opts *opts, int wide,
+                                    og_segment **segs, long *bad_aln, og_score_stats *stats) {
+    return consensus_target_impl(tlen, backbone, n_alns, starts, NULL, NULL, offs, lens,
+                                 NULL, qblob, tblob, opts, segs, bad_aln, wide, stats);
 }

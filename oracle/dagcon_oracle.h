@@ -158,6 +158,20 @@ long og_consensus_target_blob(uint32_t tlen, const char *backbone, size_t n_alns
                               const char *tblob, const og_opts *opts,
                               og_segment **segs, long *bad_aln);
 
+/* og_consensus_target_blob, and how large bestPath's scores got: score[enter] and the smallest and largest score
+ * over all vertices, as the recurrence computed them.  wide = 0: the recurrence in float, the operations of
+ * og_best_path (same results as og_consensus_target_blob).  wide != 0: the same recurrence in double -- same list
+ * order, same strict '>' -- which is exact arithmetic for these values; past 2^23 its choices differ from the
+ * reference's, whose float rounding decides there.  For tests that must know on which side of 2^22 and 2^23 an
+ * input lies (tests/test_bestpath_bound.py). */
+typedef struct og_score_stats { double enter, min, max; } og_score_stats;
+size_t og_best_path_stats(og_graph *g, int wide, int32_t **path, og_score_stats *stats);
+long og_consensus_target_blob_stats(uint32_t tlen, const char *backbone, size_t n_alns,
+                                    const uint32_t *starts, const uint64_t *offs,
+                                    const uint32_t *lens, const char *qblob,
+                                    const char *tblob, const og_opts *opts, int wide,
+                                    og_segment **segs, long *bad_aln, og_score_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

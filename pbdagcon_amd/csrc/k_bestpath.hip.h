@@ -49,8 +49,9 @@
 //                     (:327-373) over them, and the output.
 // The walks and the join come in four (SUP, POS) instances: per-base support and per-base positions.
 //
-// fp32 throughout; every value is a multiple of 0.5 below 2^23, so the arithmetic is
-// exact (-ffp-contract=off).
+// fp32 throughout (-ffp-contract=off).  Every value is a multiple of 0.5: exact below 2^23.  Beyond
+// that it is the reference's own rounding, which the whole sweep reproduces (dg_bp_sweep_whole: the
+// reference's operations in its order) and the pieces do not; dg_bp_exact keeps them apart.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>

@@ -2,7 +2,9 @@
 
 Integer / byte / index work: everything must be bit-exact.  The one floating
 point quantity (bestPath scores, fp32) only decides comparisons; its values
-are exact multiples of 0.5, so there is no tolerance anywhere in this file.
+are multiples of 0.5, exact below 2^23, and beyond that the reference's own
+rounding, reproduced by the whole sweep (tests/test_bestpath_bound.py), so
+there is no tolerance anywhere in this file.
 """
 import numpy as np
 import pytest

@@ -413,6 +413,70 @@ typedef struct dagcon_site_reads {
 int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out);
 
 /*
+ * Consensus per read group: a tally of the two-way split, and a second batch derived on the device from the first (off by
+ * default; a context switch that needs dagcon_set_pileup and dagcon_set_site_reads with phase != 0 on at the same upload).
+ * This is this build's own rule, PARITY UNPINNED, in the terms of rules 1 to 4 of the site reads above.
+ * 6. The tally.  Per site k of target t, four counts over the entries (x, k) with M(x, k) != 0 and hap[x] != 0:
+ *      P1: hap 1, M = +1     M1: hap 1, M = -1     P2: hap 2, M = +1     M2: hap 2, M = -1
+ *    With sigma = phase[k]: agree_k = P1 + M2 for sigma = +1, M1 + P2 for sigma = -1, 0 for sigma = 0; disagree_k is the
+ *    other pair under the same condition.  The site is SEPARATING iff sigma != 0 and both terms of agree_k are >= 1: each
+ *    label shows its own allele there at least once.
+ *    Per target: n1, n2, n0 the taken alignments with hap 1, 2, 0; n_sep the number of separating sites; agree and disagree
+ *    the sums of agree_k and disagree_k over its sites; K the alignments the pipeline holds for the target, those of at
+ *    least min_len columns (taken or not).  The target is SPLIT iff its status is DAGCON_OK and n_sep >= min_sites and
+ *    n1 >= min_reads and n2 >= min_reads and K - n2 >= max(1, min_cov) and K - n1 >= max(1, min_cov).  Everything is in
+ *    integers; nothing depends on an order.  min_sites = 0 / min_reads = 0 mean the defaults 2 and 3, this build's own
+ *    choice: one site is what a systematic error gives, and three reads a label are the least that outvote one error.
+ * 7. The groups.  Group g (1, 2) of a split target holds the target's alignments among those K whose hap is g or 0, in
+ *    their own order; the alignments that are not taken (empty after the trim) are in both groups too.  Unlabelled reads
+ *    carry the regions without sites, where the groups do not differ: without them a group's consensus would break off
+ *    wherever its labelled reads end.  K - n2 and K - n1 are the sizes of groups 1 and 2: the last two conditions of rule 6
+ *    say that either group is a target the pipeline builds a graph for.
+ * dagcon_set_hap_consensus: NULL turns it off.  The switch is read at the upload; with any of the three switches off at
+ * the upload no buffer, memset, launch or copy differs from a context that never heard of it and no kernel does other
+ * work (k_norm_chunk tests one kernel argument, NULL for every batch but dagcon_upload_haps' own, whose groups share
+ * strings and so cannot share the scratch that lies at a string's offset), and
+ * dagcon_fetch_hap_tally and dagcon_upload_haps are DAGCON_ERR_STATE; the same before a dagcon_fetch and under
+ * DAGCON_FLAG_STOP_AFTER_BUILD / _MERGE.  With all three on, the kernels of csrc/k_hap.hip.h run behind the split in
+ * every execution of the run.
+ * dagcon_fetch_hap_tally: the arrays are copied when it is called (the per-target records also by dagcon_upload_haps).
+ * A failed target has zeros and is not split; site_counts holds P1 M1 P2 M2 per site of dagcon_fetch_pileup_sites, which
+ * leaves out a failed target's sites.  Owned by the context, valid as long as the results of the same fetch.
+ * dagcon_upload_haps: valid exactly when dagcon_fetch_hap_tally is.  It copies hap[] (one byte an alignment) and the
+ * per-target records to the host and uploads a batch of two targets per split target, in target order, label 1 then
+ * label 2, by rule 7, with the tlen (and the backbone, if the first batch had one) of its target.  The strings are those
+ * the first batch left on the device, whichever way they came in: none crosses the bus and none is copied.  It is an
+ * upload like any other: the results of the first batch and dagcon_fetch_md_targets stop being valid, every optional
+ * output (edits, edit support, pile-up, site reads, tally) is off for the derived batch and its fetch DAGCON_ERR_STATE,
+ * the record filter has nothing to do, and a second dagcon_upload_haps in a row is DAGCON_ERR_STATE.  min_cov, min_len,
+ * trim, min_weight and the context's flags (DAGCON_FLAG_BASE_SUPPORT / _BASE_POS with their fetches among them) hold as
+ * for dagcon_upload; a group with fewer reads than min_weight lets few bases out, which is the caller's option to set as
+ * for any shallow target.  No split target: a batch of 0 targets, which runs and fetches with n_targets == 0.  A
+ * dagcon_upload_haps that fails leaves the context as any failed upload does: the first batch's results are gone.  Then
+ * dagcon_run / dagcon_sync / dagcon_fetch as ever: per group the result is that of dagcon_consensus on the group's
+ * strings, byte for byte.
+ * dagcon_fetch_hap_map: what the derived batch holds; valid from dagcon_upload_haps to the next upload.
+ */
+typedef struct dagcon_hap_opts { uint32_t min_sites, min_reads; } dagcon_hap_opts;  /* 0, 0: the defaults 2 and 3, this build's own choice */
+int dagcon_set_hap_consensus(dagcon_ctx *ctx, const dagcon_hap_opts *o);   /* NULL: off (the default) */
+typedef struct dagcon_hap_tally {
+    uint32_t n_targets;
+    const uint32_t *n1, *n2, *n0, *n_sep, *agree, *disagree;   /* [n_targets] */
+    const uint8_t *split;                                      /* [n_targets] */
+    const uint16_t *site_counts;                               /* P1 M1 P2 M2 per site of dagcon_fetch_pileup_sites */
+} dagcon_hap_tally;
+int dagcon_fetch_hap_tally(dagcon_ctx *ctx, dagcon_hap_tally *out);
+int dagcon_upload_haps(dagcon_ctx *ctx);                       /* then dagcon_run / _sync / _fetch as ever */
+typedef struct dagcon_hap_map {
+    uint32_t n_targets;                /* 2 x the split targets; == dagcon_results.n_targets of the fetch that follows */
+    const uint32_t *src_target;        /* [n_targets] target of the first batch, ascending; label 1 then label 2 */
+    const uint8_t *label;              /* [n_targets] 1 or 2 */
+    const uint64_t *aln_begin;         /* [n_targets + 1] */
+    const uint64_t *aln_src;           /* the caller's index of each alignment: dagcon_site_reads.aln_src's meaning */
+} dagcon_hap_map;
+int dagcon_fetch_hap_map(dagcon_ctx *ctx, dagcon_hap_map *out);
+
+/*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses
  * alignment records straight into such a buffer gets its dagcon_upload at link speed instead of
  * through the driver's staging copies.  Optional: any host memory is accepted by dagcon_upload.

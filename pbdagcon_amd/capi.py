@@ -45,6 +45,7 @@ EXPORTS = [
     "dagcon_set_edit_support", "dagcon_fetch_edit_support",
     "dagcon_set_pileup", "dagcon_fetch_pileup", "dagcon_fetch_pileup_sites",
     "dagcon_set_site_reads", "dagcon_fetch_site_reads",
+    "dagcon_set_hap_consensus", "dagcon_fetch_hap_tally", "dagcon_upload_haps", "dagcon_fetch_hap_map",
     "dagcon_upload_cigar_md", "dagcon_consensus_cigar_md", "dagcon_fetch_md_targets",
 ]
 ABI_VERSION = 2
@@ -161,6 +162,25 @@ class SiteReads(C.Structure):
                 ("hap", C.POINTER(C.c_uint8)), ("phase", C.POINTER(C.c_int8))]
 
 
+class HapOpts(C.Structure):
+    """dagcon_hap_opts: a target is split when it has at least min_sites separating sites and min_reads alignments of
+    either label; 0, 0 are the defaults 2 and 3 (include/dagcon.h has the rule)."""
+    _fields_ = [("min_sites", C.c_uint32), ("min_reads", C.c_uint32)]
+
+
+class HapTally(C.Structure):
+    """dagcon_hap_tally: per target n1, n2, n0, n_sep, agree, disagree and split; P1 M1 P2 M2 per site of dagcon_pileup_sites."""
+    _fields_ = [("n_targets", C.c_uint32), ("n1", C.POINTER(C.c_uint32)), ("n2", C.POINTER(C.c_uint32)), ("n0", C.POINTER(C.c_uint32)),
+                ("n_sep", C.POINTER(C.c_uint32)), ("agree", C.POINTER(C.c_uint32)), ("disagree", C.POINTER(C.c_uint32)),
+                ("split", C.POINTER(C.c_uint8)), ("site_counts", C.POINTER(C.c_uint16))]
+
+
+class HapMap(C.Structure):
+    """dagcon_hap_map: the targets of the batch dagcon_upload_haps derived, two per split target of the first batch."""
+    _fields_ = [("n_targets", C.c_uint32), ("src_target", C.POINTER(C.c_uint32)), ("label", C.POINTER(C.c_uint8)),
+                ("aln_begin", C.POINTER(C.c_uint64)), ("aln_src", C.POINTER(C.c_uint64))]
+
+
 class Edits(C.Structure):
     """dagcon_edits: per segment its target span and its edits (include/dagcon.h has the definition)."""
     _fields_ = [("n_segments", C.c_uint64), ("n", C.c_uint64), ("seg_t0", C.POINTER(C.c_uint32)),
@@ -247,6 +267,10 @@ def load() -> C.CDLL:
     L.dagcon_fetch_pileup_sites.argtypes = [vp, C.POINTER(PileupSites)]
     L.dagcon_set_site_reads.argtypes = [vp, C.POINTER(SiteReadsOpts)]
     L.dagcon_fetch_site_reads.argtypes = [vp, C.POINTER(SiteReads)]
+    L.dagcon_set_hap_consensus.argtypes = [vp, C.POINTER(HapOpts)]
+    L.dagcon_fetch_hap_tally.argtypes = [vp, C.POINTER(HapTally)]
+    L.dagcon_upload_haps.argtypes = [vp]
+    L.dagcon_fetch_hap_map.argtypes = [vp, C.POINTER(HapMap)]
     L.dagcon_upload_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int]
     L.dagcon_consensus_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int,
                                             C.POINTER(Results)]
@@ -930,6 +954,49 @@ class Context:
                 "ent_site": arr(sr.ent_site, ne, np.uint64), "ent_code": arr(sr.ent_code, ne, np.uint8),
                 "hap": arr(sr.hap, n, np.uint8) if sr.hap else None,
                 "phase": arr(sr.phase, n_site, np.int8) if sr.phase else None}
+
+    def set_hap_consensus(self, min_sites=0, min_reads=0):
+        """dagcon_set_hap_consensus for every later upload made with set_pileup and set_site_reads(True) on: the device
+        tallies how well the two labels separate (hap_tally()) and upload_haps() derives a batch of two groups per split
+        target.  0, 0: the defaults 2 and 3.  set_hap_consensus(None): off."""
+        if min_sites is None:
+            self._chk(self.L.dagcon_set_hap_consensus(self.h, None))
+            return
+        o = HapOpts(min_sites, min_reads)
+        self._chk(self.L.dagcon_set_hap_consensus(self.h, C.byref(o)))
+
+    def hap_tally(self) -> dict:
+        """dagcon_fetch_hap_tally (copies): n1, n2, n0, n_sep, agree, disagree (uint32) and split (uint8) per target;
+        site_counts (uint16, [sites, 4]: P1 M1 P2 M2 per site of pileup_sites())."""
+        ht = HapTally()
+        self._chk(self.L.dagcon_fetch_hap_tally(self.h, C.byref(ht)))
+        ps = PileupSites()
+        self._chk(self.L.dagcon_fetch_pileup_sites(self.h, C.byref(ps)))
+        T = int(ht.n_targets)
+        n_site = int(ps.site_begin[int(ps.n_targets)])
+        out = {k: (np.ctypeslib.as_array(getattr(ht, k), shape=(T,)).copy() if T else np.zeros(0, np.uint32))
+               for k in ("n1", "n2", "n0", "n_sep", "agree", "disagree")}
+        out["split"] = np.ctypeslib.as_array(ht.split, shape=(T,)).copy() if T else np.zeros(0, np.uint8)
+        out["site_counts"] = np.ctypeslib.as_array(ht.site_counts, shape=(n_site, 4)).copy() if n_site else np.zeros((0, 4), np.uint16)
+        return out
+
+    def upload_haps(self):
+        """dagcon_upload_haps: the batch of the groups, built from what the first batch left on the device; then run(),
+        sync(), fetch() as after any upload."""
+        self._chk(self.L.dagcon_upload_haps(self.h))
+
+    def hap_map(self) -> dict:
+        """dagcon_fetch_hap_map (copies): src_target (uint32) and label (uint8) per target of the derived batch, aln_begin
+        (uint64, one more) and aln_src (uint64, the caller's index of each of its alignments)."""
+        hm = HapMap()
+        self._chk(self.L.dagcon_fetch_hap_map(self.h, C.byref(hm)))
+        T = int(hm.n_targets)
+        begin = np.ctypeslib.as_array(hm.aln_begin, shape=(T + 1,)).copy()
+        n = int(begin[T])
+        return {"src_target": np.ctypeslib.as_array(hm.src_target, shape=(T,)).copy() if T else np.zeros(0, np.uint32),
+                "label": np.ctypeslib.as_array(hm.label, shape=(T,)).copy() if T else np.zeros(0, np.uint8),
+                "aln_begin": begin,
+                "aln_src": np.ctypeslib.as_array(hm.aln_src, shape=(n,)).copy() if n else np.zeros(0, np.uint64)}
 
     def edits(self) -> dict:
         """dagcon_fetch_edits (copies): seg_t0, seg_t1 (uint32, one per segment of the last results, in their order),

@@ -67,6 +67,7 @@ struct PlaceBufs {
 struct InBufs {
     DevBuf q, t, aln_off, aln_len, aln_start, aln_tgt, tlen, aln_begin, tactive, bb, bb_off, mat_base, bbv_base, matc_base, matc_stride;
     DevBuf norm_off, ch_aln, ch_base, ck_base;
+    DevBuf tmp_off;                                 // dagcon_upload_haps: where each alignment's normalisation scratch lies (its groups share strings)
     DevBuf ed_tbase;                                // dagcon_set_edits: where each target's bases begin in cg.t
     DevBuf pile_begin;                              // dagcon_set_pileup: where each target's positions begin in run.pile
 };
@@ -90,15 +91,17 @@ struct RunBufs {
     // dagcon_set_site_reads: a bit and a rank word per 64 positions; per alignment its entry count, offset, hap and signed
     // entries; per entry its site and code; per site its phase, sign rule and a round's sum
     DevBuf sr_bits, sr_rank, sr_cnt, sr_off, sr_site, sr_code, sr_hap, sr_sigma, sr_kind, sr_acc, sr_nz;
-    std::array<DevBuf *, 73> all() {
+    DevBuf hap_cnt, hap_rec;                        // dagcon_set_hap_consensus: 8 B per site (cleared before every run), DG_HAP_REC words per target
+    std::array<DevBuf *, 75> all() {
         return {&nmis, &n_lo, &n_hi, &n_start, &n_ins, &n_del, &ch_k0, &ch_next, &ch_w, &ch_tb, &ch_flag, &ch_src, &ch_out, &ch_adv, &n_lb, &norm_tmp, &ckpt,
                 &node_base, &n_nodes, &pool_base, &pool_size, &pool_top, &t_nins, &cov, &gcount, &gbase, &bid, &best, &queue, &score, &cns_tmp, &bp_tt,
                 &stk, &cuts, &cuts_bp, &bp_stat, &bp_len, &rd, &pro_state, &sh_cnt, &wl_first, &queue0, &bp_end, &bp_ab, &defer, &cns_tmp0, &cns,
                 &seg, &worklist, &seg_done, &sup_tmp, &sup_tmp0, &sup, &pos_tmp, &pos_tmp0, &pos, &ed_seg, &ed_out, &evid, &pile, &pile_tile, &pile_site,
-                &sr_bits, &sr_rank, &sr_cnt, &sr_off, &sr_site, &sr_code, &sr_hap, &sr_sigma, &sr_kind, &sr_acc, &sr_nz};
+                &sr_bits, &sr_rank, &sr_cnt, &sr_off, &sr_site, &sr_code, &sr_hap, &sr_sigma, &sr_kind, &sr_acc, &sr_nz,
+                &hap_cnt, &hap_rec};
     }
 };
-static_assert(sizeof(RunBufs) == 73 * sizeof(DevBuf), "RunBufs::all() must name every member");
+static_assert(sizeof(RunBufs) == 75 * sizeof(DevBuf), "RunBufs::all() must name every member");
 // ArenaBufs: the arenas with a treatment of their own -- matC is cleared before every run, the others are filled under
 // DAGCON_POISON bits 1 (matA, matD), 2 (nodes, pool) and 4 (score_b, norm)
 struct ArenaBufs {
@@ -166,6 +169,7 @@ struct Ctx {
     uint32_t emit_shift = 9;                        // 512 backbone positions per k_emit wave
     uint32_t n_chunks = 0;
     uint64_t tmp_main = 0, tmp_cap = 0;
+    bool tmp_shared = false;                        // the batch on the device is dagcon_upload_haps': in.tmp_off holds its scratch offsets
 
     // device buffers (each frees itself with the context)
     InBufs in;
@@ -204,6 +208,10 @@ struct Ctx {
     bool sr_on = false, sr_batch = false;
     dagcon_site_reads_opts sr_opts = {0u, 0u}, sr_batch_opts = {0u, 0u};
     std::vector<uint64_t> h_aln_src;                // [A]
+    // dagcon_set_hap_consensus: the switch; whether the batch on the device was uploaded under it (and under the pile-up
+    // and the site reads with phase on) and with which options (the defaults filled in)
+    bool hap_on = false, hap_batch = false;
+    dagcon_hap_opts hap_opts = {0u, 0u}, hap_batch_opts = {0u, 0u};
     // the growing arenas: run.ed_out (and run.evid beside it), run.pile_site, run.sr_site / sr_code.  The status block
     // holds 16 bytes for the edits' total, then 16 for the sites', whose second word is the entries'
     GrowArena ed_arena{"edits", DG_E_ED_OVF, true, &DgParams::ed_top, &DgParams::ed_cap};
@@ -256,6 +264,16 @@ struct Ctx {
     std::vector<uint64_t> s_begin;
     std::vector<uint32_t> s_pos;
     std::vector<uint16_t> s_counts;
+    bool hap_valid = false;             // the last fetch was of a batch with dagcon_set_hap_consensus on (dagcon_fetch_hap_tally, dagcon_upload_haps)
+    bool hap_fetched = false;           // y_rec holds that run's records, zeros for a failed target
+    bool hap_sites_fetched = false;     // y_counts holds that run's site counters, in the host's order of the sites
+    std::vector<uint32_t> y_rec;        // [6][T]: n1, n2, n0, n_sep, agree, disagree
+    std::vector<uint8_t> y_split;       // [T]
+    std::vector<uint16_t> y_counts;     // [4 * sites] P1 M1 P2 M2
+    bool hapmap_valid = false;          // the batch on the device is dagcon_upload_haps': the arrays below describe it (dagcon_fetch_hap_map)
+    std::vector<uint32_t> m_src_target;
+    std::vector<uint8_t> m_label;
+    std::vector<uint64_t> m_aln_begin, m_aln_src;
     bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
 
     // The one place where results stop being valid.  A fetch drops what the fetch before it left; a run drops that and
@@ -264,9 +282,10 @@ struct Ctx {
     // brought, and stay readable until the next fetch replaces them.  (The *_batch latches are the upload's own business.)
     void drop_results(const Fresh lv) {
         ed_valid = pos_pending = evid_valid = pile_valid = pile_fetched = sr_valid = sr_fetched = false;
+        hap_valid = hap_fetched = hap_sites_fetched = false;
         if (lv != Fresh::RUN) sup_valid = pos_valid = false;
         if (lv != Fresh::FETCH) fetched = false;
-        if (lv == Fresh::UPLOAD) uploaded = ran = md_valid = md_fetched = false;
+        if (lv == Fresh::UPLOAD) uploaded = ran = md_valid = md_fetched = hapmap_valid = false;
     }
 
     // debug dump storage

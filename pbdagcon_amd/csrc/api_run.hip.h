@@ -142,6 +142,7 @@ int ensure_arenas(Ctx *c) {
             ENSURE(c, c->run.sr_hap, (size_t)c->A); ENSURE(c, c->run.sr_nz, A4);
             ENSURE(c, c->run.sr_sigma, c->site_arena.cap); ENSURE(c, c->run.sr_kind, c->site_arena.cap); ENSURE(c, c->run.sr_acc, c->site_arena.cap * 4);
         }
+        if (c->hap_batch) { ENSURE(c, c->run.hap_cnt, c->site_arena.cap * 8); ENSURE(c, c->run.hap_rec, (size_t)c->T * DG_HAP_REC * 4); }
     }
     ENSURE(c, c->run.seg, 2 * seg_stride(c) * 4);
     if (int r = c->r_seg.reserve(c, 2 * (size_t)c->seg_cap * 4)) return r;
@@ -181,7 +182,7 @@ void fill_params(Ctx *c, DgParams &p) {
     p.ch_flag = c->run.ch_flag.as<uint32_t>(); p.ch_src = c->run.ch_src.as<uint64_t>();
     p.ch_out = c->run.ch_out.as<uint32_t>(); p.ch_adv = c->run.ch_adv.as<uint32_t>();
     p.n_lb = c->run.n_lb.as<uint32_t>(); p.norm_tmp = c->run.norm_tmp.as<uint16_t>();
-    p.tmp_main = c->tmp_main; p.tmp_cap = c->tmp_cap;
+    p.tmp_main = c->tmp_main; p.tmp_cap = c->tmp_cap; p.tmp_off = c->tmp_shared ? c->in.tmp_off.as<const uint64_t>() : nullptr;
     p.ckpt = c->run.ckpt.as<uint32_t>(); p.ck_base = c->in.ck_base.as<const uint32_t>(); p.emit_shift = c->emit_shift;
     p.node_base = c->run.node_base.as<uint64_t>(); p.n_nodes = c->run.n_nodes.as<uint32_t>();
     p.pool_base = c->run.pool_base.as<uint64_t>(); p.pool_size = c->run.pool_size.as<uint32_t>();
@@ -244,6 +245,11 @@ void fill_params(Ctx *c, DgParams &p) {
         if (p.sr_phase) {
             p.sr_hap = c->run.sr_hap.as<uint8_t>(); p.sr_nz = c->run.sr_nz.as<uint32_t>();
             p.sr_sigma = c->run.sr_sigma.as<int8_t>(); p.sr_kind = c->run.sr_kind.as<uint8_t>(); p.sr_acc = c->run.sr_acc.as<int>();
+        }
+        if (c->hap_batch) {
+            p.hap_cnt = c->run.hap_cnt.as<uint32_t>(); p.hap_rec = c->run.hap_rec.as<uint32_t>();
+            p.hap_min_sites = c->hap_batch_opts.min_sites; p.hap_min_reads = c->hap_batch_opts.min_reads;
+            p.hap_min_cov = std::max<uint32_t>(1u, c->opts.min_cov);
         }
     }
 }
@@ -405,6 +411,13 @@ int launch_all(Ctx *c) {
                 hipLaunchKernelGGL(k_sr_scan, dim3(1), dim3(1024), 0, s, p);
                 if (c->A > 0) hipLaunchKernelGGL(k_sr_walk<true>, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
                 if (p.sr_phase && c->A > 0) hipLaunchKernelGGL(k_sr_split, dim3(c->T), dim3(256), 0, s, p);
+                if (c->hap_batch && c->A > 0) {
+                    // the tally of the split (k_hap.hip.h): the sites' counters start from zero in every execution, a
+                    // re-run included; a wave per alignment, then a block per target
+                    HIPCHK(c, hipMemsetAsync(c->run.hap_cnt.p, 0, p.site_cap * 8, s));
+                    hipLaunchKernelGGL(k_hap_tally, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
+                    hipLaunchKernelGGL(k_hap_targets, dim3(c->T), dim3(256), 0, s, p);
+                }
             }
         }
     }
@@ -475,13 +488,16 @@ int dagcon_create(const dagcon_opts *opts, dagcon_ctx **out) {
 void dagcon_destroy(dagcon_ctx *ctx) { delete reinterpret_cast<Ctx *>(ctx); }
 
 // dev_q / dev_t: the blobs are on the device already (dagcon_consensus_pre: the aligner's output), b->qstr / tstr unused
-static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q, const void *dev_t) {
+// shared: alignments of the batch may name the same strings (dagcon_upload_haps)
+static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q, const void *dev_t, const bool shared = false) {
     if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->drop_results(Fresh::UPLOAD);
     c->ed_batch = c->evid_batch = false;                    // (a record upload with edits on says so after the hand-over)
     c->pile_batch = c->pile_on; c->pile_batch_opts = c->pile_opts;
     c->sr_batch = c->sr_on && c->pile_on; c->sr_batch_opts = c->sr_opts;
+    c->hap_batch = c->hap_on && c->sr_batch && c->sr_opts.phase != 0;
+    c->hap_batch_opts = {c->hap_opts.min_sites ? c->hap_opts.min_sites : 2u, c->hap_opts.min_reads ? c->hap_opts.min_reads : 3u};
     c->h_aln_src.clear();
     c->h_cig_bad.clear();
     c->rs_valid = false;
@@ -608,7 +624,17 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     }
     c->h_ch_base[c->A] = (uint32_t)c->h_ch_aln.size();
     c->n_chunks = (uint32_t)c->h_ch_aln.size();
-    c->tmp_main = (2ull * b->blob_bytes + 8ull * c->n_chunks + 15ull) & ~7ull;
+    // the scratch of the chunked normalizeGaps: two columns per input column at the alignment's own offset in the blob;
+    // where alignments share strings, at the columns in front of it in the batch instead
+    c->tmp_shared = shared;
+    uint64_t tmp_cols = b->blob_bytes;
+    std::vector<uint64_t> tmp_off;
+    if (shared) {
+        tmp_off.resize(c->A);
+        tmp_cols = 0;
+        for (uint32_t a = 0; a < c->A; a++) { tmp_off[a] = tmp_cols; tmp_cols += c->h_aln_len[a]; }
+    }
+    c->tmp_main = (2ull * tmp_cols + 8ull * c->n_chunks + 15ull) & ~7ull;
     c->tmp_cap = c->tmp_main + std::max<uint64_t>(c->tmp_main / 16, 1ull << 20);
 
     // inputs -> HBM
@@ -618,7 +644,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
         HIPCHK(c, hipMemcpyAsync(c->in.q.p, dev_q ? dev_q : b->qstr, b->blob_bytes, dev_q ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->in.t.p, dev_t ? dev_t : b->tstr, b->blob_bytes, dev_t ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     }
-    if (c->have_bb) {
+    if (c->have_bb && (const void *)b->backbone != c->in.bb.p) {             // (dagcon_upload_haps: the backbones are there already)
         UPLOAD(c, c->in.bb, b->backbone, bb_bytes);
     }
     int r;
@@ -638,6 +664,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     UPLOAD(c, c->in.ch_aln, c->h_ch_aln);
     UPLOAD(c, c->in.ck_base, c->h_ck_base);
     UPLOAD(c, c->in.norm_off, c->h_norm_off);
+    if (shared) UPLOAD(c, c->in.tmp_off, tmp_off);          // (a local: upload_impl waits for the stream before it returns)
     if (c->pile_batch) {
         // a target's positions [pile_begin[t], + tlen): every target has them, the ones no graph is built for too (all zero)
         c->h_pile_begin.assign((size_t)T + 1, 0);
@@ -958,6 +985,7 @@ static int unpack_sites(Ctx *c, const FetchPlan &f) {
         c->sr_n_site = n_site;
         if (int r = arena_total(c, c->sr_arena, T && c->h_pile_begin.back(), c->sr_n_ent)) return r;
         c->sr_valid = true;
+        c->hap_valid = c->hap_batch;
     }
     return DAGCON_OK;
 }
@@ -1162,6 +1190,130 @@ int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out) {
     out->aln_tgt = c->x_tgt.data(); out->aln_src = c->x_src.data(); out->ent_begin = c->x_begin.data();
     out->ent_site = c->x_site.data(); out->ent_code = c->x_code.data();
     out->hap = phase ? c->x_hap.data() : nullptr; out->phase = phase ? c->x_phase.data() : nullptr;
+    return DAGCON_OK;
+}
+
+int dagcon_set_hap_consensus(dagcon_ctx *ctx, const dagcon_hap_opts *o) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!o) { c->hap_on = false; return DAGCON_OK; }
+    c->hap_opts = *o;
+    c->hap_on = true;
+    return DAGCON_OK;
+}
+
+static const char *const k_hap_state = "without the results of an upload made with dagcon_set_pileup, dagcon_set_site_reads (phase on) and "
+                                       "dagcon_set_hap_consensus on (a switch off at the upload, no fetch yet, stopped before bestPath, or the "
+                                       "batch is dagcon_upload_haps' own)";
+
+// the per-target records of the tally, once a fetch: n1 n2 n0 n_sep agree disagree and the split bit; a failed target has zeros
+static int hap_records(Ctx *c) {
+    if (c->hap_fetched) return DAGCON_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t T = c->T;
+    const bool ran = T && c->A && c->h_pile_begin.back();          // (otherwise launch_all started none of the kernels)
+    std::vector<uint32_t> rec((size_t)T * DG_HAP_REC, 0u);
+    if (ran) HIPCHK(c, d2h(c, rec.data(), c->run.hap_rec.p, rec.size() * 4));
+    c->y_rec.assign((size_t)6 * T + 1, 0u); c->y_split.assign((size_t)T + 1, 0);
+    for (uint32_t t = 0; t < T; t++) {
+        if (c->r_status[t] != DAGCON_OK) continue;
+        const uint32_t *r = &rec[(size_t)t * DG_HAP_REC];
+        const uint64_t K = c->h_aln_begin[t + 1] - c->h_aln_begin[t];
+        if (r[6] > 1u || r[7] || (uint64_t)r[0] + r[1] + r[2] > K)
+            return fail(c, DAGCON_ERR_INTERNAL, "k_hap_targets: target %u of %llu alignments has n1 %u, n2 %u, n0 %u, split %u", t, (unsigned long long)K, r[0], r[1], r[2], r[6]);
+        for (int i = 0; i < 6; i++) c->y_rec[(size_t)i * T + t] = r[i];
+        c->y_split[t] = (uint8_t)r[6];
+    }
+    c->hap_fetched = true;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_hap_tally(dagcon_ctx *ctx, dagcon_hap_tally *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->hap_valid || !c->pile_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_hap_tally %s", k_hap_state);
+    if (int r = hap_records(c)) return r;
+    const uint32_t T = c->T;
+    if (!c->hap_sites_fetched) {
+        // 8 bytes a site, in the device's order; the host's list leaves out the sites of failed targets
+        const uint64_t ns = c->sr_n_site;
+        std::vector<uint16_t> dev((size_t)ns * 4 + 4, 0);
+        if (ns && c->A) HIPCHK(c, d2h(c, dev.data(), c->run.hap_cnt.p, (size_t)ns * 8));
+        c->y_counts.assign(c->s_pos.size() * 4 + 4, 0);
+        for (uint32_t t = 0; t < T; t++) {
+            if (c->r_status[t] != DAGCON_OK) continue;
+            const uint64_t n = c->s_begin[t + 1] - c->s_begin[t];
+            if (c->s_dev_begin[t] + n > ns) return fail(c, DAGCON_ERR_INTERNAL, "k_hap_tally: target %u has sites [%llu, + %llu) of %llu", t, (unsigned long long)c->s_dev_begin[t], (unsigned long long)n, (unsigned long long)ns);
+            if (n) memcpy(&c->y_counts[c->s_begin[t] * 4], &dev[c->s_dev_begin[t] * 4], (size_t)n * 8);
+        }
+        c->hap_sites_fetched = true;
+    }
+    out->n_targets = T;
+    out->n1 = c->y_rec.data(); out->n2 = out->n1 + T; out->n0 = out->n2 + T;
+    out->n_sep = out->n0 + T; out->agree = out->n_sep + T; out->disagree = out->agree + T;
+    out->split = c->y_split.data(); out->site_counts = c->y_counts.data();
+    return DAGCON_OK;
+}
+
+int dagcon_upload_haps(dagcon_ctx *ctx) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->hap_valid || !c->pile_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_upload_haps %s", k_hap_state);
+    if (int r = hap_records(c)) return r;
+    const uint32_t T = c->T, A = c->A;
+    std::vector<uint8_t> hap((size_t)A, 0);
+    if (T && A && c->h_pile_begin.back()) HIPCHK(c, d2h(c, hap.data(), c->run.sr_hap.p, (size_t)A));
+    // the plan, on the host: one byte an alignment and one record a target say everything upload_impl needs.  Group g of a
+    // split target: its alignments of the device batch with hap g or 0 (the ones the graph did not take are 0 too)
+    std::vector<uint32_t> tlen, start, len, src_target;
+    std::vector<uint64_t> begin(1, 0), off, bb_off, src;
+    std::vector<uint8_t> label;
+    for (uint32_t t = 0; t < T; t++) {
+        if (!c->y_split[t]) continue;
+        for (uint8_t g = 1; g <= 2; g++) {
+            for (uint64_t a = c->h_aln_begin[t]; a < c->h_aln_begin[t + 1]; a++) {
+                if (hap[a] > 2u) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_split: alignment %llu has hap %u", (unsigned long long)a, hap[a]);
+                if (hap[a] && hap[a] != g) continue;
+                off.push_back(c->h_aln_off[a]); len.push_back(c->h_aln_len[a]); start.push_back(c->h_aln_start[a]);
+                src.push_back(c->h_aln_src[a]);
+            }
+            tlen.push_back(c->h_tlen[t]); bb_off.push_back(c->h_bb_off[t]);
+            src_target.push_back(t); label.push_back(g); begin.push_back(off.size());
+        }
+    }
+    dagcon_batch db;
+    memset(&db, 0, sizeof db);
+    db.n_targets = (uint32_t)tlen.size(); db.tlen = tlen.data(); db.aln_begin = begin.data();
+    db.aln_start = start.data(); db.aln_off = off.data(); db.aln_len = len.data();
+    db.blob_bytes = c->blob_bytes;
+    if (c->have_bb) { db.backbone = c->in.bb.as<const char>(); db.backbone_off = bb_off.data(); }    // (in.bb itself: nothing is copied)
+    // an upload like any other, with every optional output off for it; the switches themselves stay as the caller set them
+    // (put back when the guard goes, whichever way this function is left)
+    struct SwitchesOff {
+        Ctx *c;
+        const bool pile_on, sr_on, hap_on;
+        explicit SwitchesOff(Ctx *x) : c(x), pile_on(x->pile_on), sr_on(x->sr_on), hap_on(x->hap_on) { c->pile_on = c->sr_on = c->hap_on = false; }
+        ~SwitchesOff() { c->pile_on = pile_on; c->sr_on = sr_on; c->hap_on = hap_on; }
+    };
+    int r;
+    {
+        const SwitchesOff off(c);
+        r = upload_impl(ctx, &db, c->in.q.p, c->in.t.p, true);
+    }
+    if (r != DAGCON_OK) return r;                                    // (as after any failed upload: the first batch's results are gone)
+    src_target.push_back(0); label.push_back(0); src.push_back(0);   // (no NULL for an empty array)
+    c->m_src_target.swap(src_target); c->m_label.swap(label); c->m_aln_begin.swap(begin); c->m_aln_src.swap(src);
+    c->hapmap_valid = true;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_hap_map(dagcon_ctx *ctx, dagcon_hap_map *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->hapmap_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_hap_map without a dagcon_upload_haps as the last upload");
+    out->n_targets = (uint32_t)(c->m_aln_begin.size() - 1);
+    out->src_target = c->m_src_target.data(); out->label = c->m_label.data();
+    out->aln_begin = c->m_aln_begin.data(); out->aln_src = c->m_aln_src.data();
     return DAGCON_OK;
 }
 

@@ -34,6 +34,7 @@
 #include "k_evidence.hip.h"
 #include "k_pileup.hip.h"
 #include "k_site_reads.hip.h"
+#include "k_hap.hip.h"
 #include "api_ctx.h"
 #include "api_run.hip.h"
 #include "api_align.hip.h"

@@ -137,6 +137,7 @@ struct DgParams {
     const uint32_t *ck_base;       // [A]
     uint32_t emit_shift;           // log2 of the positions per k_emit wave (>= 4: whole 16-position batches)
     uint64_t tmp_main, tmp_cap;    // uint16 units: start of the re-run region, end of the scratch
+    const uint64_t *tmp_off;       // [A] NULL: an alignment's scratch lies at its aln_off; dagcon_upload_haps, whose groups share strings: where it lies
     // ---- per target work arrays ----
     uint64_t *node_base;
     uint32_t *n_nodes;
@@ -255,7 +256,12 @@ struct DgParams {
     uint8_t *sr_kind;              // [site_cap] what decides an entry's sign at the site (dg_sr_kind)
     int *sr_acc;                   // [site_cap] the sum over a site's entries of a round
     uint32_t *sr_nz;               // [A] entries with a sign
+    // ---- the tally of the split (dagcon_set_hap_consensus; NULL / 0 otherwise): k_hap.hip.h ----
+    uint32_t *hap_cnt;             // [2 * site_cap] a site's words: P1 | M1 << 16, P2 | M2 << 16 (cleared before every run)
+    uint32_t *hap_rec;             // [DG_HAP_REC * T] a target's record: n1 n2 n0 n_sep agree disagree split 0
+    uint32_t hap_min_sites, hap_min_reads, hap_min_cov;    // dagcon_hap_opts (the defaults filled in), max(1, min_cov)
 };
+#define DG_HAP_REC 8u
 #define DG_SR_TAKEN 0x80000000u
 #define DG_POS_BB 0x80000000u
 

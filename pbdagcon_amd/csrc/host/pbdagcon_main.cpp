@@ -53,6 +53,7 @@
 #include "vcf.h"
 #include "pileup.h"
 #include "site_reads.h"
+#include "hap.h"
 
 namespace {
 
@@ -72,7 +73,9 @@ struct Opts {
     bool want_edits() const { return !edits.empty() || !vcf.empty(); }
     DgPileOpts pile;                   // --pileup FILE, --sites FILE [--site-min-frac F] [--site-min-count N] (every mode): what the alignments show per position
     DgSiteReadOpts sr;                 // --site-reads FILE, --haplotag FILE (whole targets, not -a): which read shows which allele at the sites; a two-way split
-    bool want_pile() const { return pile.on() || sr.on(); }   // (the site reads need the pile-up, whether or not its files are asked for)
+    DgHapOpts hap;                     // --hap-consensus FILE, --hap-sites FILE (where --haplotag goes): a consensus per group of the split, the split's tally
+    bool want_sr() const { return sr.on() || hap.on(); }      // (the tally needs the site reads and the split, whether or not their files are asked for)
+    bool want_pile() const { return pile.on() || want_sr(); } // (the site reads need the pile-up, whether or not its files are asked for)
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
     int pinned = -1;                   // --pinned 0|1: page-locked blobs (-1: when the input is several batches long)
@@ -87,7 +90,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -208,6 +211,17 @@ void usage(FILE *f) {
             "                      with w = the vertex's weight, c = max(its backbone position's coverage, w), x = c - w + 1:\n"
             "                      Q = floor(10 log10((c + 2) / x)), in exact integer arithmetic, printed as 33 + Q\n"
             "                      (with --polish: the support of the last round)\n"
+            "  --hap-consensus FILE  where --haplotag goes: a target whose reads split into two groups that separate at N or more\n"
+            "                      sites (--hap-min-sites, default 2), each group with N or more reads (--hap-min-reads, default 3)\n"
+            "                      and deep enough for -c, gets a consensus per group from a second run on the GPU, on the reads\n"
+            "                      that are still there: a group is its labelled reads and the target's unlabelled ones.  FILE gets\n"
+            "                      one FASTA record per segment, >RNAME/hap1/r0_r1 and >RNAME/hap2/r0_r1; the thresholds of the sites\n"
+            "                      are --site-min-frac and --site-min-count.  stdout does not change.  This build's own rule, parity unpinned\n"
+            "  --hap-sites FILE    the same inputs: one line per target, #target RNAME N1 N2 N0 SEP AGREE DISAGREE SPLIT (reads of label\n"
+            "                      1, 2 and none, separating sites, entries that agree and disagree with the sites' phase, 1 when the\n"
+            "                      target is split), and behind it one line per site with a phase: RNAME POS PHASE P1 M1 P2 M2, how many\n"
+            "                      reads of label 1 and 2 show the site's first (P) and second (M) allele; POS is 1-based, as in\n"
+            "                      --sites.  Counted on the GPU.  This build's own rule, parity unpinned\n"
             "  -v, --verbose       per-target progress on stderr\n"
             "  --polish N          with -a: N more rounds, each with the previous round's consensus as the backbone the reads\n"
             "                      are re-aligned to (README.md:14-15 of the reference: 'the new consensus can be used as a new\n"
@@ -278,6 +292,16 @@ int parse_args(int argc, char **argv, Opts &o) {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --haplotag needs a file name\n"); return 2; }
             o.sr.haplotag = argv[++i];
         }
+        else if (a == "--hap-consensus") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --hap-consensus needs a file name\n"); return 2; }
+            o.hap.consensus = argv[++i];
+        }
+        else if (a == "--hap-sites") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --hap-sites needs a file name\n"); return 2; }
+            o.hap.sites = argv[++i];
+        }
+        else if (a == "--hap-min-sites") { if (!need(&o.hap.min_sites)) return 2; o.hap.sites_set = true; }
+        else if (a == "--hap-min-reads") { if (!need(&o.hap.min_reads)) return 2; o.hap.reads_set = true; }
         else if (a == "--site-min-frac") {
             if (i + 1 >= argc || !dg_parse_ppm(argv[i + 1], &o.pile.min_frac_ppm)) { fprintf(stderr, "PARSE ERROR: --site-min-frac takes a fraction in [0, 1] with at most six decimal places\n"); return 2; }
             i++; o.pile.frac_set = true;
@@ -351,7 +375,10 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (!o.vcf.empty() && !records) { fprintf(stderr, "PARSE ERROR: --vcf needs --sam, --bam or --paf\n"); return 2; }
     if (!o.vcf.empty() && o.dump) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --dump-parsed (nothing is run, the file would not be written)\n"); return 2; }
     if (!o.vcf.empty() && o.window) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --window (the stitch splits and fuses edits: a fused edit has no single count)\n"); return 2; }
-    if ((o.pile.frac_set || o.pile.count_set) && o.pile.sites.empty() && !o.sr.on()) { fprintf(stderr, "PARSE ERROR: --site-min-frac and --site-min-count need --sites\n"); return 2; }
+    if ((o.pile.frac_set || o.pile.count_set) && o.pile.sites.empty() && !o.want_sr()) { fprintf(stderr, "PARSE ERROR: --site-min-frac and --site-min-count need --sites\n"); return 2; }
+    if ((o.hap.sites_set || o.hap.reads_set) && !o.hap.on()) { fprintf(stderr, "PARSE ERROR: --hap-min-sites and --hap-min-reads need --hap-consensus or --hap-sites\n"); return 2; }
+    if (o.hap.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
+    if (o.hap.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (o.sr.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
     if (o.sr.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (o.pile.on() && o.polish) { fprintf(stderr, "PARSE ERROR: --pileup and --sites do not go with --polish (the backbone changes under the positions)\n"); return 2; }
@@ -446,7 +473,8 @@ struct Batch {
     std::string pileup, sites;         // --pileup, --sites: the batch's lines of those files
     std::vector<std::string> qnames;   // --site-reads, --haplotag: the records' read names (the input's pages may be gone by the time they are written)
     std::string site_reads, haplotag;  // and the batch's lines of those files
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); }
+    std::string hap_out, hap_sites;    // --hap-consensus, --hap-sites: the batch's records and lines of those files
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); hap_out.clear(); hap_sites.clear(); }
 };
 
 FILE *g_edits = nullptr;                                  // --edits FILE, written batch by batch in output order
@@ -458,6 +486,7 @@ std::string g_vcf_contigs;
 bool g_vcf_bad = false;
 FILE *g_pileup = nullptr, *g_sites = nullptr;              // --pileup FILE, --sites FILE, written batch by batch in output order
 FILE *g_site_reads = nullptr, *g_haplotag = nullptr;       // --site-reads FILE, --haplotag FILE, the same way
+FILE *g_hap_out = nullptr, *g_hap_sites = nullptr;         // --hap-consensus FILE, --hap-sites FILE, the same way
 bool g_pile_bad = false;
 unsigned long long g_over_error = 0, g_over_depth = 0;     // records --max-error / --max-depth left out, all batches (under g_tmu)
 bool g_timing = false;                                    // PBDAGCON_TIMING=1: where the wall time of the run went, on stderr (seconds)
@@ -471,6 +500,36 @@ double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::
 bool ok(dagcon_ctx *ctx, int rc, const char *what) {
     if (rc != DAGCON_OK) fprintf(stderr, "pbdagcon: %s failed (%d): %s\n", what, rc, dagcon_last_error(ctx));
     return rc == DAGCON_OK;
+}
+
+// --hap-sites, --hap-consensus: the tally's lines; then the second run on the same context, from what the first left on
+// the device, and its records.  What the first run's fetches point at is gone after dagcon_upload_haps
+int append_haps(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_pileup_sites &ps, const dagcon_site_reads &sr) {
+    dagcon_hap_tally ht;
+    memset(&ht, 0, sizeof ht);
+    if (!ok(ctx, dagcon_fetch_hap_tally(ctx, &ht), "tally of the split")) return 1;
+    if (!o.hap.sites.empty())
+        for (uint32_t g = 0; g < ht.n_targets; g++) {
+            dg_hap_target_line(b.hap_sites, b.ids[g], ht.n1[g], ht.n2[g], ht.n0[g], ht.n_sep[g], ht.agree[g], ht.disagree[g], ht.split[g]);
+            for (uint64_t s = ps.site_begin[g]; s < ps.site_begin[g + 1]; s++)
+                if (sr.phase[s]) dg_hap_site_line(b.hap_sites, b.ids[g], ps.pos[s], sr.phase[s], ht.site_counts + 4 * s);
+        }
+    if (o.hap.consensus.empty()) return 0;
+    dagcon_results r;
+    dagcon_hap_map hm;
+    int rc = dagcon_upload_haps(ctx);
+    if (rc == DAGCON_OK) rc = dagcon_run(ctx);
+    if (rc == DAGCON_OK) rc = dagcon_fetch(ctx, &r);
+    if (rc == DAGCON_OK) rc = dagcon_fetch_hap_map(ctx, &hm);
+    if (!ok(ctx, rc, "consensus per group")) return 1;
+    for (uint32_t g = 0; g < r.n_targets; g++) {
+        const std::string id = dg_hap_id(b.ids[hm.src_target[g]], hm.label[g]);
+        if (r.target_status[g] != DAGCON_OK)
+            fprintf(stderr, "pbdagcon: warning: group %s skipped (%s)\n", id.c_str(), dg_status_text(r.target_status[g], "an alignment leaves the backbone or holds a non-printable byte"));
+        for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++)
+            if (!dg_append_result(b.hap_out, false, id, r.range0[s], r.range1[s], r.seq_blob + r.seq_off[s], r.seq_len[s], nullptr, nullptr)) return 1;
+    }
+    return 0;
 }
 
 // the records of the results to b.out (main.cpp:141-143), warnings to stderr
@@ -489,10 +548,10 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
     if (!o.pile.pileup.empty() && !ok(ctx, dagcon_fetch_pileup(ctx, &pu), "pile-up")) return 1;
     dagcon_pileup_sites ps;
     memset(&ps, 0, sizeof ps);
-    if ((!o.pile.sites.empty() || o.sr.on()) && !ok(ctx, dagcon_fetch_pileup_sites(ctx, &ps), "pile-up sites")) return 1;
+    if ((!o.pile.sites.empty() || o.want_sr()) && !ok(ctx, dagcon_fetch_pileup_sites(ctx, &ps), "pile-up sites")) return 1;
     dagcon_site_reads sr;
     memset(&sr, 0, sizeof sr);
-    if (o.sr.on() && !ok(ctx, dagcon_fetch_site_reads(ctx, &sr), "site reads")) return 1;
+    if (o.want_sr() && !ok(ctx, dagcon_fetch_site_reads(ctx, &sr), "site reads")) return 1;
     uint64_t sr_x = 0;                                      // (aln_tgt ascends: one walk over the taken alignments)
     const char *nonconforming = o.mode == MODE_RECORDS ? dg_kind(o.kind).nonconforming : "an alignment leaves the backbone or holds a non-printable byte";
     for (uint32_t g = 0; g < r.n_targets; g++) {
@@ -539,7 +598,7 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
             b.n_edits += ed.edit_begin[s + 1] - ed.edit_begin[s];
         }
     }
-    return 0;
+    return o.hap.on() ? append_haps(ctx, b, o, ps, sr) : 0;             // (last: the second run takes the place of everything above)
 }
 
 // the batch's own strings as the library's batch
@@ -811,9 +870,13 @@ struct Workers {
             const dagcon_pileup_opts po = {o.pile.min_count, o.pile.min_frac_ppm};
             if ((rc = dagcon_set_pileup(ctx, &po)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
         }
-        if (rc == DAGCON_OK && o.sr.on()) {
-            const dagcon_site_reads_opts so = {o.sr.phase() ? 1u : 0u, 0u};
+        if (rc == DAGCON_OK && o.want_sr()) {
+            const dagcon_site_reads_opts so = {o.sr.phase() || o.hap.on() ? 1u : 0u, 0u};
             if ((rc = dagcon_set_site_reads(ctx, &so)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
+        }
+        if (rc == DAGCON_OK && o.hap.on()) {
+            const dagcon_hap_opts ho = {o.hap.min_sites, o.hap.min_reads};
+            if ((rc = dagcon_set_hap_consensus(ctx, &ho)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
         }
         dagcon_ctx *actx = ctx;                             // --local --polish: the first alignment on a local context of its own
         if (rc == DAGCON_OK && o.local && o.polish) {       // (aligns only: the support comes from ctx's last round)
@@ -857,6 +920,8 @@ struct Workers {
                     if (g_sites && fwrite(d->sites.data(), 1, d->sites.size(), g_sites) != d->sites.size()) g_pile_bad = true;
                     if (g_site_reads && fwrite(d->site_reads.data(), 1, d->site_reads.size(), g_site_reads) != d->site_reads.size()) g_pile_bad = true;
                     if (g_haplotag && fwrite(d->haplotag.data(), 1, d->haplotag.size(), g_haplotag) != d->haplotag.size()) g_pile_bad = true;
+                    if (g_hap_out && fwrite(d->hap_out.data(), 1, d->hap_out.size(), g_hap_out) != d->hap_out.size()) g_pile_bad = true;
+                    if (g_hap_sites && fwrite(d->hap_sites.data(), 1, d->hap_sites.size(), g_hap_sites) != d->hap_sites.size()) g_pile_bad = true;
                     d->clear();
                     free_list.push_back(d);
                     print_seq++;
@@ -1356,8 +1421,11 @@ int main(int argc, char **argv) {
     if (!o.pile.sites.empty() && !(g_sites = fopen(o.pile.sites.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.pile.sites.c_str()); return 1; }
     if (!o.sr.site_reads.empty() && !(g_site_reads = fopen(o.sr.site_reads.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.sr.site_reads.c_str()); return 1; }
     if (!o.sr.haplotag.empty() && !(g_haplotag = fopen(o.sr.haplotag.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.sr.haplotag.c_str()); return 1; }
+    if (!o.hap.consensus.empty() && !(g_hap_out = fopen(o.hap.consensus.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.consensus.c_str()); return 1; }
+    if (!o.hap.sites.empty() && !(g_hap_sites = fopen(o.hap.sites.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.sites.c_str()); return 1; }
     auto close_pile = [&](int status) {
-        const std::pair<FILE **, const std::string *> files[] = {{&g_pileup, &o.pile.pileup}, {&g_sites, &o.pile.sites}, {&g_site_reads, &o.sr.site_reads}, {&g_haplotag, &o.sr.haplotag}};
+        const std::pair<FILE **, const std::string *> files[] = {{&g_pileup, &o.pile.pileup}, {&g_sites, &o.pile.sites}, {&g_site_reads, &o.sr.site_reads}, {&g_haplotag, &o.sr.haplotag},
+                                                                 {&g_hap_out, &o.hap.consensus}, {&g_hap_sites, &o.hap.sites}};
         for (const auto &f : files) {
             if (!*f.first) continue;
             const bool bad = fclose(*f.first) != 0 || g_pile_bad;
@@ -1406,7 +1474,7 @@ int main(int argc, char **argv) {
         if (fclose(g_edits) != 0) { fprintf(stderr, "pbdagcon: error writing %s\n", o.edits.c_str()); status = 1; fast_exit = false; }
         if (o.verbose) fprintf(stderr, "pbdagcon: %llu edits written to %s\n", g_n_edits, o.edits.c_str());
     }
-    if (g_pileup || g_sites || g_site_reads || g_haplotag) {
+    if (g_pileup || g_sites || g_site_reads || g_haplotag || g_hap_out || g_hap_sites) {
         const int ps = close_pile(0);
         if (ps) { status = ps; fast_exit = false; }
     }

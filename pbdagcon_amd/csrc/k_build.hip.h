@@ -198,7 +198,9 @@ __global__ __launch_bounds__(LANES, RETRY ? 1 : 5) void k_norm_chunk(DgParams p)
         k0 = dg_chunk_start(q, t, len, c);
         if (k0 != DG_CH_NONE) {
             uint16_t *win = s_win + threadIdx.x * (NW + 2u);
-            src = (2ull * (off + k0) + 8ull * g + 7ull) & ~7ull;     // 16-byte aligned, regions stay disjoint
+            // (two alignments that share their strings, dagcon_upload_haps, get their scratch by tmp_off)
+            const uint64_t soff = p.tmp_off ? p.tmp_off[a] : off;
+            src = (2ull * (soff + k0) + 8ull * g + 7ull) & ~7ull;    // 16-byte aligned, regions stay disjoint
             for (;;) {
                 uint32_t k1 = len;
                 for (; cn < nwin; cn++) {

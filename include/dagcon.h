@@ -376,7 +376,7 @@ int dagcon_fetch_pileup_sites(dagcon_ctx *ctx, dagcon_pileup_sites *out);
  *    coordinate p (rule 2 of the pile-up).  An entry holds one byte, code = cls | ins << 3: cls 0..5 for A C G T N DEL by
  *    exactly the classification of that rule, ins = 1 iff an insertion run of this alignment is counted at p by the
  *    pile-up's INS rule.  The inserted bases themselves are not compared: two alignments that insert different bases
- *    behind p carry the same code.  The entries of an alignment are in ascending position, ent_begin[x] .. ent_begin[x + 1];
+ *    behind p carry the same code (dagcon_set_site_alleles, rule 8 below, compares them).  The entries of an alignment are in ascending position, ent_begin[x] .. ent_begin[x + 1];
  *    ent_site is an index into the arrays of dagcon_fetch_pileup_sites.  For every site the entries' classes add up to
  *    the site's six counts and their ins bits to its INS.
  * 3. Signs.  An entry gets M in {+1, 0, -1} from its site's counts, s2 the second largest of the six as in the site rule.
@@ -447,7 +447,7 @@ int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out);
  * label 2, by rule 7, with the tlen (and the backbone, if the first batch had one) of its target.  The strings are those
  * the first batch left on the device, whichever way they came in: none crosses the bus and none is copied.  It is an
  * upload like any other: the results of the first batch and dagcon_fetch_md_targets stop being valid, every optional
- * output (edits, edit support, pile-up, site reads, tally) is off for the derived batch and its fetch DAGCON_ERR_STATE,
+ * output (edits, edit support, pile-up, site reads, site alleles, tally) is off for the derived batch and its fetch DAGCON_ERR_STATE,
  * the record filter has nothing to do, and a second dagcon_upload_haps in a row is DAGCON_ERR_STATE.  min_cov, min_len,
  * trim, min_weight and the context's flags (DAGCON_FLAG_BASE_SUPPORT / _BASE_POS with their fetches among them) hold as
  * for dagcon_upload; a group with fewer reads than min_weight lets few bases out, which is the caller's option to set as
@@ -475,6 +475,55 @@ typedef struct dagcon_hap_map {
     const uint64_t *aln_src;           /* the caller's index of each alignment: dagcon_site_reads.aln_src's meaning */
 } dagcon_hap_map;
 int dagcon_fetch_hap_map(dagcon_ctx *ctx, dagcon_hap_map *out);
+
+/*
+ * Site alleles: the alleles themselves at the sites of the pile-up, counted per site and named per entry (off by
+ * default; a context switch that needs dagcon_set_pileup and dagcon_set_site_reads on at the same upload).  The code of
+ * rule 2 of the site reads says A C G T N DEL and "an insertion run starts here"; normalizeGaps writes a mismatch as the
+ * target base dropped and the read base inserted behind it, so a substitution is DEL + ins and the base it put there
+ * lives in the inserted run alone.  This is this build's own rule, PARITY UNPINNED, in the terms of the pile-up and of
+ * rules 1 to 7 above.
+ * 8. The allele of an entry.  Entry (x, k) is alignment x at site k, at position p.  Let i be the column of x with
+ *    t != '-' and coordinate p, and R the columns i + 1, i + 2, .. for as long as they lie inside the alignment's trimmed
+ *    columns and have t == '-' and q != '-'.  The allele is the byte string q[i] (left out when it is '-') followed by
+ *    the q bytes of R: the read's bases between target base p and target base p + 1.  Each byte is mapped as the pile-up
+ *    classifies: b & 0xDF in A C G T gives that letter, anything else N.  Its length L may be 0: a deletion.  By
+ *    construction cls == DEL iff q[i] == '-', and the entry's ins bit is set iff R is not empty.
+ *    The key is a 64-bit integer with the codes A = 1, C = 2, G = 3, T = 4, N = 5: base j < min(L, 20) contributes
+ *    code << (3 * (19 - j)), and bit 60 is set iff L > 20 (the allele is LONG).  Unsigned comparison of keys is
+ *    lexicographic on the first 20 bases, a shorter allele before its extensions, long alleles last.  Long alleles
+ *    with the same first 20 bases have the same key and COUNT AS ONE ALLELE: the rule does not look past 20 bases.
+ *    Text: the bases, "-" for the empty allele, a trailing "+" when long (dagcon_allele_text).
+ *    The table of a site: the distinct keys of its entries, each with its count, ordered by count descending, ties by
+ *    key ascending; alleles [al_begin[k], al_begin[k + 1]).  The counts add up to the site's depth, the sum of its six
+ *    counters.  ent_allele[e] is the index of entry e's key within its site's table, e in the order of
+ *    dagcon_fetch_site_reads' entries.  With phase on at the upload each allele also has c1, c2, c0: its entries whose
+ *    alignment has hap 1, 2, 0; c1 + c2 + c0 == count.  A failed target has no alleles and no entries.
+ * dagcon_set_site_alleles: the switch is read at the upload; without dagcon_set_pileup and dagcon_set_site_reads on at
+ * the same upload it is as if off.  With it off no kernel, buffer, memset, launch or copy differs from a context that
+ * never heard of it.  With it on, the kernels of csrc/k_alleles.hip.h run behind those of the site reads (the counts per
+ * label behind the split) in every execution of the run; they need no arena of their own: the entries of a site number
+ * its depth, and a table is no longer than that.  The arrays stay on the device and are copied only when
+ * dagcon_fetch_site_alleles is called (the tables are gathered into arrays of their own size by one more kernel then:
+ * 16 bytes an allele; a run holds 20 bytes an entry and 28 a site), which converts them as dagcon_fetch_site_reads converts its own (it calls it):
+ * the sites are those of dagcon_fetch_pileup_sites in their order, the entries those of dagcon_fetch_site_reads in
+ * theirs.  DAGCON_ERR_STATE wherever dagcon_fetch_site_reads is, and when the switch was off at the upload; the derived
+ * batch of dagcon_upload_haps has it off.  Owned by the context, valid as long as the results of the same fetch.
+ * dagcon_allele_text: host only, needs no device and no context; cap counts the terminating 0 (22 bytes hold every key).
+ * DAGCON_ERR_INVALID_ARG for a buffer too small and for an integer that is no key.
+ */
+typedef struct dagcon_site_alleles {
+    uint64_t n_sites;                 /* the sites of dagcon_fetch_pileup_sites, same order */
+    const uint64_t *al_begin;         /* [n_sites + 1] */
+    const uint64_t *key;              /* [n] */
+    const uint32_t *count;            /* [n] */
+    const uint16_t *hap_count;        /* [3 n]: c1 c2 c0; NULL when phase was off */
+    uint64_t n_ent;                   /* the entries of dagcon_fetch_site_reads, same order */
+    const uint16_t *ent_allele;       /* [n_ent] index within the entry's site */
+} dagcon_site_alleles;
+int dagcon_set_site_alleles(dagcon_ctx *ctx, int on);
+int dagcon_fetch_site_alleles(dagcon_ctx *ctx, dagcon_site_alleles *out);
+int dagcon_allele_text(uint64_t key, char *out, size_t cap);   /* host only; needs no device */
 
 /*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses

@@ -45,6 +45,7 @@ EXPORTS = [
     "dagcon_set_edit_support", "dagcon_fetch_edit_support",
     "dagcon_set_pileup", "dagcon_fetch_pileup", "dagcon_fetch_pileup_sites",
     "dagcon_set_site_reads", "dagcon_fetch_site_reads",
+    "dagcon_set_site_alleles", "dagcon_fetch_site_alleles", "dagcon_allele_text",
     "dagcon_set_hap_consensus", "dagcon_fetch_hap_tally", "dagcon_upload_haps", "dagcon_fetch_hap_map",
     "dagcon_upload_cigar_md", "dagcon_consensus_cigar_md", "dagcon_fetch_md_targets",
 ]
@@ -162,6 +163,14 @@ class SiteReads(C.Structure):
                 ("hap", C.POINTER(C.c_uint8)), ("phase", C.POINTER(C.c_int8))]
 
 
+class SiteAlleles(C.Structure):
+    """dagcon_site_alleles: per site of dagcon_pileup_sites its table of alleles (key, count, c1 c2 c0), per entry of
+    dagcon_site_reads the index of its allele (include/dagcon.h has the rule)."""
+    _fields_ = [("n_sites", C.c_uint64), ("al_begin", C.POINTER(C.c_uint64)), ("key", C.POINTER(C.c_uint64)),
+                ("count", C.POINTER(C.c_uint32)), ("hap_count", C.POINTER(C.c_uint16)), ("n_ent", C.c_uint64),
+                ("ent_allele", C.POINTER(C.c_uint16))]
+
+
 class HapOpts(C.Structure):
     """dagcon_hap_opts: a target is split when it has at least min_sites separating sites and min_reads alignments of
     either label; 0, 0 are the defaults 2 and 3 (include/dagcon.h has the rule)."""
@@ -267,6 +276,9 @@ def load() -> C.CDLL:
     L.dagcon_fetch_pileup_sites.argtypes = [vp, C.POINTER(PileupSites)]
     L.dagcon_set_site_reads.argtypes = [vp, C.POINTER(SiteReadsOpts)]
     L.dagcon_fetch_site_reads.argtypes = [vp, C.POINTER(SiteReads)]
+    L.dagcon_set_site_alleles.argtypes = [vp, C.c_int]
+    L.dagcon_fetch_site_alleles.argtypes = [vp, C.POINTER(SiteAlleles)]
+    L.dagcon_allele_text.argtypes = [C.c_uint64, C.c_char_p, C.c_size_t]
     L.dagcon_set_hap_consensus.argtypes = [vp, C.POINTER(HapOpts)]
     L.dagcon_fetch_hap_tally.argtypes = [vp, C.POINTER(HapTally)]
     L.dagcon_upload_haps.argtypes = [vp]
@@ -280,6 +292,15 @@ def load() -> C.CDLL:
     L.dagcon_host_free.restype = None
     _LIB = L
     return L
+
+
+def allele_text(key) -> str:
+    """dagcon_allele_text: the bases of an allele's key, "-" for the empty allele, a trailing "+" when it is long."""
+    buf = C.create_string_buffer(24)
+    r = load().dagcon_allele_text(int(key), buf, 24)
+    if r != 0:
+        raise DagconError(r, "dagcon_allele_text: %#x is no key" % int(key))
+    return buf.value.decode()
 
 
 def default_opts() -> Opts:
@@ -954,6 +975,27 @@ class Context:
                 "ent_site": arr(sr.ent_site, ne, np.uint64), "ent_code": arr(sr.ent_code, ne, np.uint8),
                 "hap": arr(sr.hap, n, np.uint8) if sr.hap else None,
                 "phase": arr(sr.phase, n_site, np.int8) if sr.phase else None}
+
+    def set_site_alleles(self, on=True):
+        """dagcon_set_site_alleles for every later upload made with set_pileup and set_site_reads on: the device groups and
+        counts the alleles themselves at each site (site_alleles())."""
+        self._chk(self.L.dagcon_set_site_alleles(self.h, 1 if on else 0))
+
+    def site_alleles(self) -> dict:
+        """dagcon_fetch_site_alleles (copies): al_begin (uint64, one per site of pileup_sites() and one more); key (uint64),
+        count (uint32) and hap_count (uint16, [alleles, 3]: c1 c2 c0; None when phase was off) per allele; ent_allele
+        (uint16, per entry of site_reads(): the index of its allele within its site's table)."""
+        sa = SiteAlleles()
+        self._chk(self.L.dagcon_fetch_site_alleles(self.h, C.byref(sa)))
+        ns, ne = int(sa.n_sites), int(sa.n_ent)
+
+        def arr(ptr, k, dt):
+            return np.ctypeslib.as_array(ptr, shape=(k,)).copy() if k else np.zeros(0, dt)
+        begin = np.ctypeslib.as_array(sa.al_begin, shape=(ns + 1,)).copy()
+        n = int(begin[ns])
+        return {"al_begin": begin, "key": arr(sa.key, n, np.uint64), "count": arr(sa.count, n, np.uint32),
+                "hap_count": (arr(sa.hap_count, 3 * n, np.uint16).reshape(n, 3) if sa.hap_count else None),
+                "ent_allele": arr(sa.ent_allele, ne, np.uint16)}
 
     def set_hap_consensus(self, min_sites=0, min_reads=0):
         """dagcon_set_hap_consensus for every later upload made with set_pileup and set_site_reads(True) on: the device

@@ -143,6 +143,15 @@ int ensure_arenas(Ctx *c) {
             ENSURE(c, c->run.sr_sigma, c->site_arena.cap); ENSURE(c, c->run.sr_kind, c->site_arena.cap); ENSURE(c, c->run.sr_acc, c->site_arena.cap * 4);
         }
         if (c->hap_batch) { ENSURE(c, c->run.hap_cnt, c->site_arena.cap * 8); ENSURE(c, c->run.hap_rec, (size_t)c->T * DG_HAP_REC * 4); }
+        if (c->al_batch) {
+            const size_t ne = c->sr_arena.cap, ns = c->site_arena.cap;
+            // (20 bytes an entry and 28 a site; the compact tables wait for dagcon_fetch_site_alleles, which knows their size)
+            ENSURE(c, c->run.al_map, ne * 2); ENSURE(c, c->run.al_idx, ne * 2);
+            ENSURE(c, c->run.al_soff, ns * 8); ENSURE(c, c->run.al_cur, (ns + 1) * 4); ENSURE(c, c->run.al_nd, ns * 4);
+            ENSURE(c, c->run.al_deep, ns * 4); ENSURE(c, c->run.al_toff, ns * 8);
+            ENSURE(c, c->run.al_srt, ne * 8); ENSURE(c, c->run.al_tcnt, ne * 4); ENSURE(c, c->run.al_thap, ne * 4);
+            ENSURE(c, c->run.al_tot, 16);
+        }
     }
     ENSURE(c, c->run.seg, 2 * seg_stride(c) * 4);
     if (int r = c->r_seg.reserve(c, 2 * (size_t)c->seg_cap * 4)) return r;
@@ -250,6 +259,15 @@ void fill_params(Ctx *c, DgParams &p) {
             p.hap_cnt = c->run.hap_cnt.as<uint32_t>(); p.hap_rec = c->run.hap_rec.as<uint32_t>();
             p.hap_min_sites = c->hap_batch_opts.min_sites; p.hap_min_reads = c->hap_batch_opts.min_reads;
             p.hap_min_cov = std::max<uint32_t>(1u, c->opts.min_cov);
+        }
+        if (c->al_batch) {
+            p.al_map = c->run.al_map.as<uint16_t>(); p.al_idx = c->run.al_idx.as<uint16_t>();
+            p.al_soff = c->run.al_soff.as<unsigned long long>(); p.al_cur = c->run.al_cur.as<uint32_t>(); p.al_nd = c->run.al_nd.as<uint32_t>();
+            p.al_deep = c->run.al_deep.as<uint32_t>(); p.al_toff = c->run.al_toff.as<unsigned long long>();
+            p.al_srt = c->run.al_srt.as<unsigned long long>(); p.al_tcnt = c->run.al_tcnt.as<uint32_t>(); p.al_thap = c->run.al_thap.as<uint32_t>();
+            p.al_ckey = c->run.al_ckey.as<unsigned long long>(); p.al_ccnt = c->run.al_ccnt.as<uint32_t>(); p.al_chap = c->run.al_chap.as<uint32_t>();
+            p.al_ent_top = c->run.al_tot.as<unsigned long long>(); p.al_top = p.al_ent_top + 1;
+            p.al_nocap = ~0ull;
         }
     }
 }
@@ -411,6 +429,19 @@ int launch_all(Ctx *c) {
                 hipLaunchKernelGGL(k_sr_scan, dim3(1), dim3(1024), 0, s, p);
                 if (c->A > 0) hipLaunchKernelGGL(k_sr_walk<true>, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
                 if (p.sr_phase && c->A > 0) hipLaunchKernelGGL(k_sr_split, dim3(c->T), dim3(256), 0, s, p);
+                if (c->al_batch && c->A > 0) {
+                    // the alleles at the sites (k_alleles.hip.h): a stretch per site, the keys, a table per site, the
+                    // tables' places, an index per entry (and the counts per label, behind the split).
+                    // The sites' cursors start from zero in every execution, a re-run included
+                    const dim3 sg((uint32_t)((p.site_cap + 3) / 4)), ag((c->A + 3) / 4);
+                    HIPCHK(c, hipMemsetAsync(c->run.al_cur.p, 0, (p.site_cap + 1) * 4, s));
+                    hipLaunchKernelGGL(k_al_soff, dim3(1), dim3(1024), 0, s, p);
+                    hipLaunchKernelGGL(k_al_keys, ag, dim3(256), 0, s, p);
+                    hipLaunchKernelGGL(k_al_table, sg, dim3(256), 0, s, p);
+                    hipLaunchKernelGGL(k_al_table_deep, dim3(1024), dim3(256), 0, s, p);
+                    hipLaunchKernelGGL(k_al_tscan, dim3(1), dim3(1024), 0, s, p);
+                    hipLaunchKernelGGL(k_al_index, ag, dim3(256), 0, s, p);
+                }
                 if (c->hap_batch && c->A > 0) {
                     // the tally of the split (k_hap.hip.h): the sites' counters start from zero in every execution, a
                     // re-run included; a wave per alignment, then a block per target
@@ -497,6 +528,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->pile_batch = c->pile_on; c->pile_batch_opts = c->pile_opts;
     c->sr_batch = c->sr_on && c->pile_on; c->sr_batch_opts = c->sr_opts;
     c->hap_batch = c->hap_on && c->sr_batch && c->sr_opts.phase != 0;
+    c->al_batch = c->al_on && c->sr_batch;
     c->hap_batch_opts = {c->hap_opts.min_sites ? c->hap_opts.min_sites : 2u, c->hap_opts.min_reads ? c->hap_opts.min_reads : 3u};
     c->h_aln_src.clear();
     c->h_cig_bad.clear();
@@ -1193,6 +1225,108 @@ int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out) {
     return DAGCON_OK;
 }
 
+int dagcon_set_site_alleles(dagcon_ctx *ctx, int on) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    reinterpret_cast<Ctx *>(ctx)->al_on = on != 0;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_site_alleles(dagcon_ctx *ctx, dagcon_site_alleles *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->al_batch || !c->sr_valid || !c->pile_valid)
+        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_site_alleles without the results of an upload made with dagcon_set_pileup, dagcon_set_site_reads and "
+                                         "dagcon_set_site_alleles on (a switch off at the upload, no fetch yet, or stopped before bestPath)");
+    const bool phase = c->sr_batch_opts.phase != 0;
+    if (!c->al_fetched) {
+        // the entries in the host's terms first (which of the device's survive, and each one's site); then the copies
+        // dagcon_fetch left out: the tables' places, the compact tables, an index per entry.  A failed target's sites and
+        // entries go, as in dagcon_fetch_site_reads
+        dagcon_site_reads sr;
+        if (int r = dagcon_fetch_site_reads(ctx, &sr)) return r;
+        HIPCHK(c, hipSetDevice(c->device));
+        const uint32_t A = c->A, T = c->T;
+        const uint64_t ne = c->sr_n_ent, ns = c->sr_n_site;
+        const bool ran = T && A && c->h_pile_begin.back();           // (otherwise launch_all started none of the kernels)
+        unsigned long long tot[2] = {0ull, 0ull};
+        if (ran) HIPCHK(c, d2h(c, tot, c->run.al_tot.p, sizeof tot));
+        const uint64_t na = tot[1];
+        if (na > c->sr_arena.cap || (!ran && (ne || ns)))
+            return fail(c, DAGCON_ERR_INTERNAL, "k_al_tscan: %llu alleles in an arena of %llu", (unsigned long long)na, (unsigned long long)c->sr_arena.cap);
+        std::vector<uint64_t> toff((size_t)ns), key((size_t)na);
+        std::vector<uint32_t> nd((size_t)ns), cnt((size_t)A, 0), count((size_t)na), hapw((size_t)na);
+        std::vector<uint16_t> idx((size_t)ne);
+        if (ns) { HIPCHK(c, d2h(c, toff.data(), c->run.al_toff.p, (size_t)ns * 8)); HIPCHK(c, d2h(c, nd.data(), c->run.al_nd.p, (size_t)ns * 4)); }
+        if (na) {
+            // the compact copy, now that its size is known: room, zeros (a table k_al_pack refuses stays empty and fails
+            // the checks below), the copy on the stream
+            ENSURE(c, c->run.al_ckey, (size_t)na * 8); ENSURE(c, c->run.al_ccnt, (size_t)na * 4); ENSURE(c, c->run.al_chap, (size_t)na * 4);
+            HIPCHK(c, hipMemsetAsync(c->run.al_ckey.p, 0, (size_t)na * 8, c->stream));
+            HIPCHK(c, hipMemsetAsync(c->run.al_ccnt.p, 0, (size_t)na * 4, c->stream));
+            HIPCHK(c, hipMemsetAsync(c->run.al_chap.p, 0, (size_t)na * 4, c->stream));
+            DgParams p;
+            fill_params(c, p);
+            hipLaunchKernelGGL(k_al_pack, dim3((uint32_t)((p.site_cap + 3) / 4)), dim3(256), 0, c->stream, p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, d2h(c, key.data(), c->run.al_ckey.p, (size_t)na * 8)); HIPCHK(c, d2h(c, count.data(), c->run.al_ccnt.p, (size_t)na * 4));
+            HIPCHK(c, d2h(c, hapw.data(), c->run.al_chap.p, (size_t)na * 4));
+        }
+        if (ne) HIPCHK(c, d2h(c, idx.data(), c->run.al_idx.p, (size_t)ne * 2));
+        if (ran) HIPCHK(c, d2h(c, cnt.data(), c->run.sr_cnt.p, (size_t)A * 4));
+        c->z_begin.assign(1, 0); c->z_key.clear(); c->z_count.clear(); c->z_hap.clear(); c->z_ent.clear();
+        for (uint32_t t = 0; t < T; t++) {
+            if (c->r_status[t] != DAGCON_OK) continue;
+            for (uint64_t j = c->s_begin[t]; j < c->s_begin[t + 1]; j++) {
+                const uint64_t d = c->s_dev_begin[t] + (j - c->s_begin[t]);
+                uint64_t depth = 0, sum = 0;
+                for (int q = 0; q < 6; q++) depth += c->s_counts[j * 8 + q];
+                if (d >= ns || toff[d] > na || nd[d] > na - toff[d] || !nd[d])
+                    return fail(c, DAGCON_ERR_INTERNAL, "k_al_table: site %llu of target %u has alleles [%llu, + %u) of %llu", (unsigned long long)d, t,
+                                (unsigned long long)(d < ns ? toff[d] : 0), d < ns ? nd[d] : 0u, (unsigned long long)na);
+                for (uint64_t i = toff[d]; i < toff[d] + nd[d]; i++) {
+                    const uint32_t c1 = hapw[i] & 0xFFFFu, c2 = hapw[i] >> 16;
+                    sum += count[i];
+                    if ((key[i] >> 61) || !count[i] || (uint64_t)c1 + c2 > count[i])
+                        return fail(c, DAGCON_ERR_INTERNAL, "k_al_table: allele %llu of site %llu: key %llx, count %u, c1 %u, c2 %u", (unsigned long long)(i - toff[d]),
+                                    (unsigned long long)d, (unsigned long long)key[i], count[i], c1, c2);
+                    c->z_key.push_back(key[i]); c->z_count.push_back(count[i]);
+                    c->z_hap.push_back((uint16_t)c1); c->z_hap.push_back((uint16_t)c2); c->z_hap.push_back((uint16_t)(count[i] - c1 - c2));
+                }
+                if (sum != depth) return fail(c, DAGCON_ERR_INTERNAL, "k_al_table: the alleles of site %llu count %llu entries, its depth is %llu", (unsigned long long)d,
+                                              (unsigned long long)sum, (unsigned long long)depth);
+                c->z_begin.push_back(c->z_key.size());
+            }
+        }
+        // the entries, in the order of dagcon_fetch_site_reads (x_site: each one's site there)
+        uint64_t e = 0;
+        for (uint32_t a = 0; a < A; a++) {
+            const uint32_t t = c->h_aln_tgt[a], n = cnt[a] & ~DG_SR_TAKEN;
+            const uint64_t e0 = e;
+            e += n;
+            if (e > ne) return fail(c, DAGCON_ERR_INTERNAL, "k_al_index: the alignments hold more than the %llu entries of the batch (alignment %u)", (unsigned long long)ne, a);
+            if (c->r_status[t] != DAGCON_OK || !(cnt[a] & DG_SR_TAKEN)) continue;
+            for (uint64_t j = e0; j < e; j++) {
+                const uint64_t x = c->z_ent.size();
+                if (x + 1 >= c->x_site.size() || idx[j] >= c->z_begin[c->x_site[x] + 1] - c->z_begin[c->x_site[x]])
+                    return fail(c, DAGCON_ERR_INTERNAL, "k_al_index: entry %llu of alignment %u has allele %u", (unsigned long long)(j - e0), a, idx[j]);
+                c->z_ent.push_back(idx[j]);
+            }
+        }
+        if (c->z_ent.size() + 1 != c->x_site.size())
+            return fail(c, DAGCON_ERR_INTERNAL, "k_al_index: %llu entries with an allele, %llu entries", (unsigned long long)c->z_ent.size(), (unsigned long long)(c->x_site.size() - 1));
+        c->z_key.push_back(0); c->z_count.push_back(0); c->z_ent.push_back(0); c->z_hap.insert(c->z_hap.end(), 3, 0);   // (no NULL for an empty array)
+        c->al_fetched = true;
+    }
+    out->n_sites = c->z_begin.size() - 1;
+    out->al_begin = c->z_begin.data(); out->key = c->z_key.data(); out->count = c->z_count.data();
+    out->hap_count = phase ? c->z_hap.data() : nullptr;
+    out->n_ent = c->z_ent.size() - 1; out->ent_allele = c->z_ent.data();
+    return DAGCON_OK;
+}
+
+// host only: the one implementation is the command line's (host/alleles.h)
+int dagcon_allele_text(uint64_t key, char *out, size_t cap) { return dg_allele_text(key, out, cap); }
+
 int dagcon_set_hap_consensus(dagcon_ctx *ctx, const dagcon_hap_opts *o) {
     if (!ctx) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
@@ -1291,9 +1425,9 @@ int dagcon_upload_haps(dagcon_ctx *ctx) {
     // (put back when the guard goes, whichever way this function is left)
     struct SwitchesOff {
         Ctx *c;
-        const bool pile_on, sr_on, hap_on;
-        explicit SwitchesOff(Ctx *x) : c(x), pile_on(x->pile_on), sr_on(x->sr_on), hap_on(x->hap_on) { c->pile_on = c->sr_on = c->hap_on = false; }
-        ~SwitchesOff() { c->pile_on = pile_on; c->sr_on = sr_on; c->hap_on = hap_on; }
+        const bool pile_on, sr_on, hap_on, al_on;
+        explicit SwitchesOff(Ctx *x) : c(x), pile_on(x->pile_on), sr_on(x->sr_on), hap_on(x->hap_on), al_on(x->al_on) { c->pile_on = c->sr_on = c->hap_on = c->al_on = false; }
+        ~SwitchesOff() { c->pile_on = pile_on; c->sr_on = sr_on; c->hap_on = hap_on; c->al_on = al_on; }
     };
     int r;
     {

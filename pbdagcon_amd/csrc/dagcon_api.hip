@@ -35,6 +35,8 @@
 #include "k_pileup.hip.h"
 #include "k_site_reads.hip.h"
 #include "k_hap.hip.h"
+#include "k_alleles.hip.h"
+#include "host/alleles.h"
 #include "api_ctx.h"
 #include "api_run.hip.h"
 #include "api_align.hip.h"

@@ -260,6 +260,21 @@ struct DgParams {
     uint32_t *hap_cnt;             // [2 * site_cap] a site's words: P1 | M1 << 16, P2 | M2 << 16 (cleared before every run)
     uint32_t *hap_rec;             // [DG_HAP_REC * T] a target's record: n1 n2 n0 n_sep agree disagree split 0
     uint32_t hap_min_sites, hap_min_reads, hap_min_cov;    // dagcon_hap_opts (the defaults filled in), max(1, min_cov)
+    // ---- the alleles at the sites (dagcon_set_site_alleles; NULL / 0 otherwise): k_alleles.hip.h ----
+    unsigned long long *al_soff;   // [site_cap] where a site's stretch begins: the depths of the sites in front (k_al_soff)
+    uint32_t *al_cur;              // [site_cap + 1] entries a site's stretch holds (cleared before every run); last: the deep sites listed
+    unsigned long long *al_srt;    // [sr_cap] a site's stretch: its entries' keys, then (k_al_table) its table's keys at the front
+    uint32_t *al_tcnt;             // [sr_cap] parallel to al_srt: the count of a table's allele
+    uint32_t *al_thap;             // [sr_cap] parallel to al_srt: c1 | c2 << 16 of a table's allele (phase on)
+    uint32_t *al_nd;               // [site_cap] alleles of a site's table
+    uint32_t *al_deep;             // [site_cap] the sites of more than 64 entries, in no order
+    unsigned long long *al_toff;   // [site_cap] where a site's table begins in the compact arrays (k_al_tscan)
+    uint16_t *al_idx;              // [sr_cap] parallel to sr_site / sr_code: an entry's place in its site's stretch (k_al_keys), then its allele's index in the site's table (k_al_index)
+    uint16_t *al_map;              // [sr_cap] parallel to al_srt: the allele's index of the entry that holds this place of the stretch
+    unsigned long long *al_ckey;   // [*al_top, at the fetch] the tables, site after site: key, count, c1 | c2 << 16
+    uint32_t *al_ccnt, *al_chap;
+    unsigned long long *al_ent_top, *al_top;   // the sum of the depths; the alleles of the batch (words of their own, fetched when asked)
+    uint64_t al_nocap;             // 2^64 - 1: the two scans have no arena of their own to outgrow
 };
 #define DG_HAP_REC 8u
 #define DG_SR_TAKEN 0x80000000u

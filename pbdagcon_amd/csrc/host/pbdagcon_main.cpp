@@ -53,6 +53,7 @@
 #include "vcf.h"
 #include "pileup.h"
 #include "site_reads.h"
+#include "alleles.h"
 #include "hap.h"
 
 namespace {
@@ -74,7 +75,9 @@ struct Opts {
     DgPileOpts pile;                   // --pileup FILE, --sites FILE [--site-min-frac F] [--site-min-count N] (every mode): what the alignments show per position
     DgSiteReadOpts sr;                 // --site-reads FILE, --haplotag FILE (whole targets, not -a): which read shows which allele at the sites; a two-way split
     DgHapOpts hap;                     // --hap-consensus FILE, --hap-sites FILE (where --haplotag goes): a consensus per group of the split, the split's tally
-    bool want_sr() const { return sr.on() || hap.on(); }      // (the tally needs the site reads and the split, whether or not their files are asked for)
+    DgAlleleOpts al;                   // --site-alleles FILE, --site-vcf FILE (where --site-reads goes): the alleles themselves at the sites, counted
+    bool want_sr() const { return sr.on() || hap.on() || al.on(); }   // (the tally and the alleles need the site reads, whether or not their files are asked for)
+    bool want_phase() const { return sr.phase() || hap.on(); }        // the split: --haplotag, --hap-consensus or --hap-sites
     bool want_pile() const { return pile.on() || want_sr(); } // (the site reads need the pile-up, whether or not its files are asked for)
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
     std::vector<int> devices{0};       // --devices: one consensus worker (thread + context) per GPU
@@ -90,7 +93,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [--site-alleles FILE] [--site-vcf FILE] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -222,6 +225,21 @@ void usage(FILE *f) {
             "                      target is split), and behind it one line per site with a phase: RNAME POS PHASE P1 M1 P2 M2, how many\n"
             "                      reads of label 1 and 2 show the site's first (P) and second (M) allele; POS is 1-based, as in\n"
             "                      --sites.  Counted on the GPU.  This build's own rule, parity unpinned\n"
+            "  --site-alleles FILE where --site-reads goes: FILE lists the alleles themselves at each position --sites would list (the\n"
+            "                      same thresholds), one line per allele: RNAME POS REF DEPTH ALLELE COUNT H1 H2 H0, tab-separated,\n"
+            "                      a target's sites ascending, a site's alleles by COUNT descending.  ALLELE is what a read has\n"
+            "                      between this target base and the next: its bases, - for none (a deleted base), so a\n"
+            "                      substitution reads as the new base and an insertion as the kept base and the inserted ones; a\n"
+            "                      trailing + says more than 20 bases (alleles that agree in the first 20 count as one).  H1 H2 H0\n"
+            "                      are the COUNT reads by their group of the split, . unless --haplotag, --hap-consensus or\n"
+            "                      --hap-sites is given.  Counted on the GPU; stdout does not change.  This build's own rule; the\n"
+            "                      reference has no such output\n"
+            "  --site-vcf FILE     with --sam, --bam or --paf: the same tables as VCFv4.2, one record per site that has an ALT:\n"
+            "                      RNAME POS . REF ALT . . DP=depth;AD=ref,alt1,..  (and AD1=..;AD2=.. per group with the split on).\n"
+            "                      ALT is every allele that is not the REF base, has no + and has COUNT >= --site-min-count; a\n"
+            "                      deleted base takes the target base in front as anchor for the whole record (the base behind at\n"
+            "                      position 1; a target of one base has no records).  Adjacent sites are NOT joined: a deletion\n"
+            "                      of three bases is three records.  No genotype is called\n"
             "  -v, --verbose       per-target progress on stderr\n"
             "  --polish N          with -a: N more rounds, each with the previous round's consensus as the backbone the reads\n"
             "                      are re-aligned to (README.md:14-15 of the reference: 'the new consensus can be used as a new\n"
@@ -287,6 +305,14 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--site-reads") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --site-reads needs a file name\n"); return 2; }
             o.sr.site_reads = argv[++i];
+        }
+        else if (a == "--site-alleles") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --site-alleles needs a file name\n"); return 2; }
+            o.al.alleles = argv[++i];
+        }
+        else if (a == "--site-vcf") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --site-vcf needs a file name\n"); return 2; }
+            o.al.vcf = argv[++i];
         }
         else if (a == "--haplotag") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --haplotag needs a file name\n"); return 2; }
@@ -381,6 +407,9 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (o.hap.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (o.sr.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
     if (o.sr.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
+    if (o.al.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --site-alleles and --site-vcf do not go with --window, -a or --polish (they go where --site-reads goes)\n"); return 2; }
+    if (o.al.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --site-alleles and --site-vcf do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
+    if (!o.al.vcf.empty() && !records) { fprintf(stderr, "PARSE ERROR: --site-vcf needs --sam, --bam or --paf (REF comes from the target's bases)\n"); return 2; }
     if (o.pile.on() && o.polish) { fprintf(stderr, "PARSE ERROR: --pileup and --sites do not go with --polish (the backbone changes under the positions)\n"); return 2; }
     if (o.pile.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --pileup and --sites do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
@@ -474,7 +503,8 @@ struct Batch {
     std::vector<std::string> qnames;   // --site-reads, --haplotag: the records' read names (the input's pages may be gone by the time they are written)
     std::string site_reads, haplotag;  // and the batch's lines of those files
     std::string hap_out, hap_sites;    // --hap-consensus, --hap-sites: the batch's records and lines of those files
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); hap_out.clear(); hap_sites.clear(); }
+    std::string site_alleles, site_vcf, site_contigs;   // --site-alleles, --site-vcf: the batch's lines of those files, and its targets' ##contig lines
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); hap_out.clear(); hap_sites.clear(); site_alleles.clear(); site_vcf.clear(); site_contigs.clear(); }
 };
 
 FILE *g_edits = nullptr;                                  // --edits FILE, written batch by batch in output order
@@ -487,6 +517,10 @@ bool g_vcf_bad = false;
 FILE *g_pileup = nullptr, *g_sites = nullptr;              // --pileup FILE, --sites FILE, written batch by batch in output order
 FILE *g_site_reads = nullptr, *g_haplotag = nullptr;       // --site-reads FILE, --haplotag FILE, the same way
 FILE *g_hap_out = nullptr, *g_hap_sites = nullptr;         // --hap-consensus FILE, --hap-sites FILE, the same way
+FILE *g_site_alleles = nullptr;                            // --site-alleles FILE, the same way
+// --site-vcf FILE, as --vcf: the header names every target, so the records wait in an unnamed temporary file
+FILE *g_site_vcf = nullptr, *g_site_vcf_lines = nullptr;
+std::string g_site_vcf_contigs;
 bool g_pile_bad = false;
 unsigned long long g_over_error = 0, g_over_depth = 0;     // records --max-error / --max-depth left out, all batches (under g_tmu)
 bool g_timing = false;                                    // PBDAGCON_TIMING=1: where the wall time of the run went, on stderr (seconds)
@@ -552,6 +586,9 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
     dagcon_site_reads sr;
     memset(&sr, 0, sizeof sr);
     if (o.want_sr() && !ok(ctx, dagcon_fetch_site_reads(ctx, &sr), "site reads")) return 1;
+    dagcon_site_alleles sa;
+    memset(&sa, 0, sizeof sa);
+    if (o.al.on() && !ok(ctx, dagcon_fetch_site_alleles(ctx, &sa), "site alleles")) return 1;
     uint64_t sr_x = 0;                                      // (aln_tgt ascends: one walk over the taken alignments)
     const char *nonconforming = o.mode == MODE_RECORDS ? dg_kind(o.kind).nonconforming : "an alignment leaves the backbone or holds a non-printable byte";
     for (uint32_t g = 0; g < r.n_targets; g++) {
@@ -571,6 +608,11 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
             const uint64_t x0 = sr_x;
             while (sr_x < sr.n_aln && sr.aln_tgt[sr_x] == g) sr_x++;
             dg_site_read_lines(o.sr.site_reads.empty() ? nullptr : &b.site_reads, o.sr.haplotag.empty() ? nullptr : &b.haplotag, b.ids[g], ps, sr, g, x0, sr_x, b.qnames);
+        }
+        if (o.al.on()) {
+            const char *tb = o.mode == MODE_RECORDS ? b.t.data() + b.toff[g] : nullptr;
+            if (!o.al.vcf.empty()) dg_vcf_contig(b.site_contigs, b.ids[g], b.tlen[g]);
+            dg_site_allele_lines(o.al.alleles.empty() ? nullptr : &b.site_alleles, o.al.vcf.empty() ? nullptr : &b.site_vcf, b.ids[g], ps, sa, g, tb, b.tlen[g], o.pile.min_count);
         }
         if (r.target_status[g] != DAGCON_OK)
             fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(), dg_status_text(r.target_status[g], nonconforming));
@@ -653,7 +695,7 @@ int run_records(dagcon_ctx *ctx, Batch &b, const Opts &o) {
     const int rc = dg_consensus_records(ctx, o.kind, ra, nullptr, &r);
     if (g_timing) fprintf(stderr, "pbdagcon timing: %s%s batch of %zu records: %s %.3f\n", dg_kind(o.kind).flag, o.pick.text().c_str(), b.start.size(), dg_kind(o.kind).entry, wall() - t0);
     if (!ok(ctx, rc, "consensus")) return 1;
-    if (dg_kind_md(o.kind) && (o.want_edits() || o.pile.on())) {           // REF of the edits and of the pile-up lines: the targets as the device rebuilt them, in b.t's layout
+    if (dg_kind_md(o.kind) && (o.want_edits() || o.pile.on() || o.al.on())) {   // REF of the edits, of the pile-up lines and of the alleles' lines and records: the targets as the device rebuilt them, in b.t's layout
         const char *tb = nullptr;
         uint64_t tn = 0;
         if (!ok(ctx, dagcon_fetch_md_targets(ctx, &tb, &tn), "rebuilt targets")) return 1;
@@ -871,9 +913,10 @@ struct Workers {
             if ((rc = dagcon_set_pileup(ctx, &po)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
         }
         if (rc == DAGCON_OK && o.want_sr()) {
-            const dagcon_site_reads_opts so = {o.sr.phase() || o.hap.on() ? 1u : 0u, 0u};
+            const dagcon_site_reads_opts so = {o.want_phase() ? 1u : 0u, 0u};
             if ((rc = dagcon_set_site_reads(ctx, &so)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
         }
+        if (rc == DAGCON_OK && o.al.on() && (rc = dagcon_set_site_alleles(ctx, 1)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
         if (rc == DAGCON_OK && o.hap.on()) {
             const dagcon_hap_opts ho = {o.hap.min_sites, o.hap.min_reads};
             if ((rc = dagcon_set_hap_consensus(ctx, &ho)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
@@ -922,6 +965,8 @@ struct Workers {
                     if (g_haplotag && fwrite(d->haplotag.data(), 1, d->haplotag.size(), g_haplotag) != d->haplotag.size()) g_pile_bad = true;
                     if (g_hap_out && fwrite(d->hap_out.data(), 1, d->hap_out.size(), g_hap_out) != d->hap_out.size()) g_pile_bad = true;
                     if (g_hap_sites && fwrite(d->hap_sites.data(), 1, d->hap_sites.size(), g_hap_sites) != d->hap_sites.size()) g_pile_bad = true;
+                    if (g_site_alleles && fwrite(d->site_alleles.data(), 1, d->site_alleles.size(), g_site_alleles) != d->site_alleles.size()) g_pile_bad = true;
+                    if (g_site_vcf) { g_site_vcf_contigs += d->site_contigs; if (fwrite(d->site_vcf.data(), 1, d->site_vcf.size(), g_site_vcf_lines) != d->site_vcf.size()) g_pile_bad = true; }
                     d->clear();
                     free_list.push_back(d);
                     print_seq++;
@@ -1423,8 +1468,22 @@ int main(int argc, char **argv) {
     if (!o.sr.haplotag.empty() && !(g_haplotag = fopen(o.sr.haplotag.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.sr.haplotag.c_str()); return 1; }
     if (!o.hap.consensus.empty() && !(g_hap_out = fopen(o.hap.consensus.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.consensus.c_str()); return 1; }
     if (!o.hap.sites.empty() && !(g_hap_sites = fopen(o.hap.sites.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.sites.c_str()); return 1; }
+    if (!o.al.alleles.empty() && !(g_site_alleles = fopen(o.al.alleles.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.al.alleles.c_str()); return 1; }
+    if (!o.al.vcf.empty() && (!(g_site_vcf = fopen(o.al.vcf.c_str(), "w")) || !(g_site_vcf_lines = tmpfile()))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.al.vcf.c_str()); return 1; }
     auto close_pile = [&](int status) {
+        if (g_site_vcf) {
+            // the header, now that every target is known, then the records that waited
+            std::string head;
+            dg_site_vcf_header(head, g_site_vcf_contigs, o.want_phase());
+            bool wrote = fwrite(head.data(), 1, head.size(), g_site_vcf) == head.size();
+            rewind(g_site_vcf_lines);
+            char buf[65536];
+            for (size_t k; wrote && (k = fread(buf, 1, sizeof buf, g_site_vcf_lines)) > 0;) wrote = fwrite(buf, 1, k, g_site_vcf) == k;
+            if (!wrote || ferror(g_site_vcf_lines)) g_pile_bad = true;
+            fclose(g_site_vcf_lines); g_site_vcf_lines = nullptr;
+        }
         const std::pair<FILE **, const std::string *> files[] = {{&g_pileup, &o.pile.pileup}, {&g_sites, &o.pile.sites}, {&g_site_reads, &o.sr.site_reads}, {&g_haplotag, &o.sr.haplotag},
+                                                                 {&g_site_alleles, &o.al.alleles}, {&g_site_vcf, &o.al.vcf},
                                                                  {&g_hap_out, &o.hap.consensus}, {&g_hap_sites, &o.hap.sites}};
         for (const auto &f : files) {
             if (!*f.first) continue;
@@ -1474,7 +1533,7 @@ int main(int argc, char **argv) {
         if (fclose(g_edits) != 0) { fprintf(stderr, "pbdagcon: error writing %s\n", o.edits.c_str()); status = 1; fast_exit = false; }
         if (o.verbose) fprintf(stderr, "pbdagcon: %llu edits written to %s\n", g_n_edits, o.edits.c_str());
     }
-    if (g_pileup || g_sites || g_site_reads || g_haplotag || g_hap_out || g_hap_sites) {
+    if (g_pileup || g_sites || g_site_reads || g_haplotag || g_hap_out || g_hap_sites || g_site_alleles || g_site_vcf) {
         const int ps = close_pile(0);
         if (ps) { status = ps; fast_exit = false; }
     }

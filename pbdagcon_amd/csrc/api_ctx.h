@@ -165,7 +165,7 @@ struct Ctx {
     std::vector<uint64_t> h_aln_begin, h_aln_off, h_mat_base, h_bbv_base, h_bb_off, h_matc_base;
     std::vector<uint32_t> h_matc_stride;
     uint64_t matc_cells = 0;
-    bool wide_cells = false;                        // this upload met an insertion run of more than 255 columns: 32-bit matC cells
+    bool wide_cells = false;                        // an insertion run of more than 255 columns: 32-bit matC cells (met by this upload's run, or by the one before and in this batch's strings)
     std::vector<uint8_t> h_tactive;
     std::vector<uint32_t> h_ch_base, h_ch_aln;      // chunk tables of k_norm_*
     std::vector<uint64_t> h_norm_off;               // column buffer of each alignment

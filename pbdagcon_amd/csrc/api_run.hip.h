@@ -518,6 +518,21 @@ int dagcon_create(const dagcon_opts *opts, dagcon_ctx **out) {
 // ~Ctx: the device, the wait for the stream, the events and the stream; then every buffer frees itself
 void dagcon_destroy(dagcon_ctx *ctx) { delete reinterpret_cast<Ctx *>(ctx); }
 
+// whether a target string of the batch holds more than 255 gap columns in a row: the batch that follows one that needed
+// 32-bit run cells (DG_E_RUN_WIDE) and is of its kind starts with them, instead of paying the same re-run at every upload.
+// The raw strings decide: a run that only normalizeGaps makes that long still costs its re-run, as in any other batch
+static bool has_long_gap_run(const char *tstr, const std::vector<uint64_t> &off, const std::vector<uint32_t> &len) {
+    for (size_t a = 0; a < len.size(); a++) {
+        const char *s = tstr + off[a];
+        uint32_t run = 0;
+        for (uint32_t i = 0; i < len[a]; i++) {
+            run = s[i] == '-' || s[i] == '.' ? run + 1 : 0;
+            if (run > 255u) return true;
+        }
+    }
+    return false;
+}
+
 // dev_q / dev_t: the blobs are on the device already (dagcon_consensus_pre: the aligner's output), b->qstr / tstr unused
 // shared: alignments of the batch may name the same strings (dagcon_upload_haps)
 static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q, const void *dev_t, const bool shared = false) {
@@ -533,7 +548,10 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->h_aln_src.clear();
     c->h_cig_bad.clear();
     c->rs_valid = false;
-    c->wide_cells = false;                             // (one batch with a very long insertion run does not slow the ones after it)
+    // one batch with a very long insertion run does not slow the ones after it: the mark is dropped here, and kept below only
+    // for a batch that shows such a run itself (has_long_gap_run: looked for in that state alone)
+    const bool was_wide = c->wide_cells;
+    c->wide_cells = false;
     const uint32_t T = b->n_targets;
     if (T && (!b->tlen || !b->aln_begin)) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/aln_begin is NULL");
     const uint64_t A_all = T ? b->aln_begin[T] : 0;
@@ -603,6 +621,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     }
     // cuts for partial-span pileups (prologue + worklist + epilogue): where the reads are full-span the cut
     // vertices every read passes through are the same ones, found without that machinery
+    if (was_wide && !dev_t && b->tstr) c->wide_cells = has_long_gap_run(b->tstr, c->h_aln_off, c->h_aln_len);
     c->full_span = n_whole == (uint64_t)c->h_aln_len.size();
     // shortest stretch worth a worker: 768 positions when that already fills the chip, shorter (down to 192)
     // for small batches, whose waves would otherwise be few and long
@@ -815,7 +834,7 @@ static int fetch_status(Ctx *c) {
         if (f & DG_E_STACK) c->stk_words *= 4;
         if (f & DG_E_LIST_OVF) c->worklist_cap *= 4;
         if (f & DG_E_LOG_OVF) c->sh_log *= 2;
-        if (f & DG_E_RUN_WIDE) c->wide_cells = true;       // (until the next upload)
+        if (f & DG_E_RUN_WIDE) c->wide_cells = true;       // (until the upload of a batch without such a run)
         for (const GrowRef &r : c->growing())
             if ((f & r.g->ovf) && r.g->o_top) r.g->cap = *sb.h<uint64_t>(r.g->o_top) + 1024;
         if (f & DG_E_OUT_OVF) {

@@ -100,7 +100,7 @@ def test_lane_edges(gpu_ctx_factory):
 
 
 def test_wide_batch_then_narrow_batch(gpu_ctx_factory):
-    """The mark a run of more than 255 columns leaves on a context lasts until the next upload."""
+    """The mark a run of more than 255 columns leaves on a context lasts until the upload of a batch without such a run."""
     rng = np.random.default_rng(9)
     wide = batch_from_targets([_target(rng, 640, 8, {1: dict(runs=[(320, 400)])}), _target(rng, 500, 6, {})])
     narrow = batch_from_targets([_target(rng, 640, 8, {1: dict(runs=[(320, 255)])}), _target(rng, 900, 9, {4: dict(runs=[(77, 9)])})])

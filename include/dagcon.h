@@ -920,8 +920,8 @@ typedef struct dagcon_graph_dump {
 } dagcon_graph_dump;
 int dagcon_debug_graph(dagcon_ctx *ctx, uint32_t target, dagcon_graph_dump *out);
 
-/* Diagnostic builds (-DDG_STAMPS) only: sixteen raw device counters of the last
- * run (in-kernel cycle stamps of target 0); all zero in the shipped build. */
+/* Kept for ABI 2.  The in-kernel cycle stamps that filled these sixteen counters in a
+ * diagnostic build are gone: no build fills them any more, out8[0..15] are set to zero. */
 int dagcon_debug_counters(dagcon_ctx *ctx, unsigned long long *out8);
 
 /* Records of the last dagcon_align / dagcon_consensus_pre on this context whose corners the widest band could not

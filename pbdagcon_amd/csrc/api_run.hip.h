@@ -1482,15 +1482,10 @@ int dagcon_fetch_edits(dagcon_ctx *ctx, dagcon_edits *out) {
     return DAGCON_OK;
 }
 
-// diagnostic builds (-DDG_STAMPS) only: raw device counters of the last run
+// kept for ABI 2: no build fills the counters any more, sixteen zeros
 int dagcon_debug_counters(dagcon_ctx *ctx, unsigned long long *out8) {
     if (!ctx || !out8) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    DgStatus st;
-    HIPCHK(c, d2h(c, &st, c->sb.dev.p, sizeof st));
-    for (int i = 0; i < 16; i++) out8[i] = st.dbg[i];
+    for (int i = 0; i < 16; i++) out8[i] = 0;
     return DAGCON_OK;
 }
 

@@ -21,6 +21,14 @@
 //   * lists longer than a wave take the reference-literal single-lane path
 //     (dgg_*), on the same ordered slot lists.
 //
+// Where the rule lives.  Everything a visit does once it has something to merge is written once, as templates over a
+// lane-group policy (DgWave here, DgRow in k_merge_q.hip.h): the merge of one group (dg_merge_in_group /
+// dg_merge_out_group), the FIFO bookkeeping (dg_release) and the visit around them (dg_visit_merging: the frames of
+// mergeInNodes, the hand-over to dgg_*, the out loop, the single-lane loop for a list longer than the group).  The
+// sweeps -- dg_merge_segment for a wave, dq_merge_segment for a row -- keep what is a different design in each: the
+// loop over the queue and the one-look fast path for a visit that merges nothing.  Apart as well, and only here: the
+// prologue's level counting, k_merge_fin, the cuts kernels, and the literal dgg_* functions.
+//
 // All list primitives keep the container semantics of
 // boost::adjacency_list<vecS,vecS,bidirectionalS> (append on add_edge, stable
 // erase on clear_vertex, edge(u,v) = first match).
@@ -79,23 +87,6 @@ __device__ __forceinline__ void dgg_fail(DgGraph &g, uint32_t bit) {
     }
     g.err = true;
 }
-// The wave-level code keeps every value that steers control flow provably wave-uniform (the
-// compiler then keeps it in SGPRs and branches without exec masks): g.err of the wave's DgGraph
-// is only ever assigned uniform values.  Single-lane stretches work on a private copy (DG_LANE0).
-__device__ __forceinline__ void dgw_fail(DgGraph &g, uint32_t bit, int lane) {
-    if (lane == 0) {
-        if (bit & DG_E_TARGET_MASK) atomicOr(g.tfail, bit);
-        else { atomicOr(&g.st->err_flags, bit); g.st->bad_target = g.t; }
-    }
-    g.err = true;
-}
-#define DG_LANE0(G, BODY)                                          \
-    do {                                                           \
-        bool e_ = false;                                           \
-        if (lane == 0) { DgGraph gs = (G); BODY; e_ = gs.err; }    \
-        DG_WAVE_FENCE();                                           \
-        (G).err = __any((int)e_) != 0;                             \
-    } while (0)
 
 // ---- ordered slot lists (single lane) --------------------------------------
 #define DGG_SH_IN(g, v) ((g).sh && (v) == (g).X)
@@ -402,7 +393,7 @@ __device__ inline void dgg_merge_out(DgGraph &g, int n) {
 #define DG_NV(G, V) (*reinterpret_cast<DgNode *>(reinterpret_cast<char *>((G).nd) + (((uint32_t)(V)) << 5)))
 #define DG_LT(lane) ((1ull << (lane)) - 1ull)
 // orders this wave's earlier stores (a single lane's, on the literal path) before its
-// later loads; the worker is one wave, so no s_barrier is involved
+// later loads; the worker is one wave, or a row of lanes of one (k_merge_q), so no s_barrier is involved
 #define DG_WAVE_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup")
 
 __device__ __forceinline__ uint4 dg_lo16(const DgNode *n) { return *reinterpret_cast<const uint4 *>(n); }
@@ -438,16 +429,61 @@ __device__ __forceinline__ int dg_wave_incl_scan(int v, int lane) {
 // wave kernels keep the one they were tuned with and k_merge_q the other.  All five kernels sit at a pinned occupancy
 // with spilled scalar registers, and the other choice moves their register allocation: the wave kernels by -38 .. +6
 // instructions, k_merge_q by +20 and 0.5 ms of 10.7 at configs[1] (profiles/merge_lanes/).  Nothing else may hang on it.
+// For the sweep around the merge rule (dg_release, dg_visit_merging) a policy also gives: IN_W (the longest in-list a
+// frame of mergeInNodes takes on its lanes; the wave stops at half of itself), qent / RING / ent (an entry of the
+// group's LDS ring of its youngest queue entries, their number, and the entry that says "v, look its record up").
+#define DG_IN_STACK 48              // frames of mergeInNodes kept in LDS; a deeper recursion is finished by dgg_merge_in
+#define DG_QRING 256
 struct DgWave {
     typedef unsigned long long mask;
     static constexpr int W = 64;
+    static constexpr int IN_W = 32;
     static constexpr bool row_text = false;
+    typedef int qent;
+    static constexpr uint32_t RING = DG_QRING;
+    static __device__ __forceinline__ qent ent(int v) { return v; }
     static __device__ __forceinline__ mask ballot(bool p) { return __ballot(p); }
     static __device__ __forceinline__ int rl(int v, int l) { return DG_RL(v, l); }
     static __device__ __forceinline__ int ffs(mask m) { return __ffsll((long long)m); }
     static __device__ __forceinline__ int popc(mask m) { return __popcll(m); }
     static __device__ __forceinline__ mask lt(int lane) { return DG_LT(lane); }
 };
+
+// The group-level code keeps every value that steers control flow provably group-uniform (for a wave the compiler
+// then keeps it in SGPRs and branches without exec masks): g.err of the group's DgGraph is only ever assigned
+// uniform values.  Single-lane stretches work on a private copy (DG_LANE0).
+__device__ __forceinline__ void dg_fail_lane0(DgGraph &g, uint32_t bit, int lane) {
+    if (lane == 0) {
+        if (bit & DG_E_TARGET_MASK) atomicOr(g.tfail, bit);
+        else { atomicOr(&g.st->err_flags, bit); g.st->bad_target = g.t; }
+    }
+    g.err = true;
+}
+// BODY on lane 0 of the group, on a copy `gs` of the DgGraph GR; did it fail, every lane of the group learns
+#define DG_LANE0(G, GR, BODY)                                      \
+    do {                                                           \
+        bool e_ = false;                                           \
+        if (lane == 0) { DgGraph gs = (GR); BODY; e_ = gs.err; }   \
+        DG_WAVE_FENCE();                                           \
+        (GR).err = G::ballot(e_) != 0;                             \
+    } while (0)
+
+// ---- the FIFO bookkeeping of a visit (AlnGraphBoost.cpp:143-158), all out-edges in one step ------------
+// A live lane holds an out-neighbour v of the visited vertex and pend, v's pending counter minus this edge: the
+// edge is marked visited (pending stored), and the neighbours whose in-edges are now all visited are queued in
+// lane (= out-list) order, in the queue and in the ring (`e`, the lane's ring entry for v).  Returns the new tail;
+// a tail beyond N, more vertices queued than the segment has, cannot happen (the caller fails the target).
+template <class G>
+__device__ __forceinline__ uint32_t dg_release(DgGraph &g, bool live, int v, int pend, uint32_t qt, uint32_t N,
+                                           typename G::qent *ring, typename G::qent e, int lane) {
+    const typename G::mask rm = G::ballot(live && pend == 0);
+    if (live) DG_NV(g, v).pending = pend;
+    if (live && pend == 0) {
+        const uint32_t pos = qt + (uint32_t)G::popc(rm & G::lt(lane));
+        if (pos < N) { g.queue[pos] = v; ring[pos & (G::RING - 1)] = e; }
+    }
+    return qt + (uint32_t)G::popc(rm);
+}
 
 template <class G>
 __device__ __forceinline__ int dg_sum_masked(int v, typename G::mask m) {
@@ -816,10 +852,144 @@ __global__ __launch_bounds__(64) void k_cuts(DgParams p) {
     }
 }
 
-// ---- mergeNodes (AlnGraphBoost.cpp:129-160): one wave per (target, segment) ----
-#define DG_IN_STACK 48
-#define DG_QRING 256
+// ---- the visit that has something to merge, once, for a group of lanes ------------------------------
+// mergeInNodes(u) with its recursion on an explicit stack, mergeOutNodes(u), then the FIFO bookkeeping: the visit of
+// a dequeued vertex u of AlnGraphBoost.cpp:137-158, by the lane group G (the wave in k_merge, k_merge_list,
+// k_merge_pro and k_merge_fin; a row in k_merge_q).  Whatever does not fit the group -- a list longer than it, more
+// than DG_IN_STACK open frames, a refused group -- goes the reference-literal way (dgg_*) on lane 0; `scalar` says
+// that the literal functions have taken the visit over.
+//   X        a list entry that is nobody's to merge or to release: the exit vertex where it is shared between the
+//            workers (k_merge_list), -1 where every vertex is the sweep's own, DG_TOMB for rows (no such entry);
+//   skip_in  in[u] is the previous segment's business; in_only: out[u] is the next one's (the caller's segment is
+//            done after this visit);
+//   adj      SH only: 1 if u is a neighbour of the shared enter / exit vertex, -1 if nobody has looked yet;
+//   s_stk    [2 * DG_IN_STACK] words of LDS, ring: the group's G::RING youngest queue entries;
+//   qt       the queue's tail; the new tail is returned (by value, like dg_release: a tail the callers hand over by
+//            reference costs the wave kernels 30 - 100 instructions, profiles/merge_visit/checks.txt).
+// SH: compiled with the checks for lists shared between segment workers (DgGraph::sh; the kernels of p.gcuts).
+// A failure is left in g.err (group-uniform; an int, and no boolean is made of it here: see DgGraph::err).
+// What stays with the callers, because it is a different design in each: the one-look fast path in front of this
+// (dg_merge_segment: 32 + 32 entries and the next record prefetched; dq_merge_segment: 4 + 4 entries and the record
+// carried in the ring) and the loop around it (the wave's levels and look-ahead, the row's two phases).
+template <class G, bool SH>
+__device__ __forceinline__ uint32_t dg_visit_merging(DgGraph &g, const int u, const int X, const bool skip_in, const bool in_only,
+                                                 int adj, uint32_t qt, const uint32_t N, int *s_stk,
+                                                 typename G::qent *ring, const int lane) {
+    typedef typename G::mask gmask;
+    const bool sh = SH && g.sh;
+    bool scalar = false;
+    // ---------------- mergeInNodes(u), recursion on an explicit stack ----------------
+    int sp = skip_in ? 0 : 1;
+    int fr_n = u, fr_last = -1;                       // top frame lives in registers
+    if constexpr (SH) {
+        if (adj < 0) {
+            // long lists: look for the shared vertices among u's neighbours
+            const DgNode nq = DG_NV(g, u);
+            bool f = false;
+            if (!skip_in) for (int i = lane; i < nq.in_len; i += G::W) f |= (DG_NV(g, DG_PW(g, nq.in_off + i)).flags & DG_NF_SHARED) != 0;
+            if (!in_only) for (int i = lane; i < nq.out_len; i += G::W) f |= (int)DG_PW(g, nq.out_off + 2 * i) == X;
+            adj = G::ballot(f) ? 1 : 0;
+        }
+        if (adj) scalar = true;                       // next to enter / exit: the literal path handles their lists
+    }
+    while (sp > 0 && !scalar) {
+        const uint4 nl = dg_lo16(&DG_NV(g, fr_n)), nh = dg_hi16(&DG_NV(g, fr_n));
+        if (DG_H_INLEN(nl) > G::IN_W) { scalar = true; break; }
+        const bool valid = lane < DG_H_INLEN(nl);
+        int s = 0;
+        if (valid) s = (int)DG_PW(g, DG_H2_INOFF(nh) + lane);
+        uint4 h = make_uint4(0, 0, 0, 0);
+        if (valid) h = dg_lo16(&DG_NV(g, s));
+        const gmask cand = G::ballot(valid && DG_H_OUTLEN(h) == 1 && !(sh && ((h.y >> 8) & DG_NF_SHARED)));
+        gmask M = 0;
+        int b = 256;
+        if (G::popc(cand) >= 2) b = dg_pick_group<G>(cand, DG_H_BASE(h), fr_last, lane, &M);
+        if (b == 256) {                               // frame done: pop
+            sp--;
+            if (sp > 0) { fr_n = s_stk[2 * (sp - 1)]; fr_last = s_stk[2 * (sp - 1) + 1]; }
+            continue;
+        }
+        if (sp >= DG_IN_STACK) { scalar = true; break; }
+        int an = -1;
+        if (!dg_merge_in_group<G>(g, fr_n, DG_H2_INOFF(nh), M, s, h, valid, lane, &an)) { scalar = true; break; }
+        if (g.err) break;
+        fr_last = b;
+        if (lane == 0) { s_stk[2 * (sp - 1)] = fr_n; s_stk[2 * (sp - 1) + 1] = fr_last; }
+        sp++;                                         // :213 recurse on the survivor
+        fr_n = an; fr_last = -1;
+    }
+    if (scalar && !g.err && sp > 0) {
+        // finish every open frame, deepest first, on the reference-literal path;
+        // groups already merged are gone, so re-evaluating a frame from scratch is exact
+        DG_LANE0(G, g, {
+            dgg_merge_in(gs, fr_n);
+            for (int f = sp - 2; f >= 0 && !gs.err; f--) dgg_merge_in(gs, s_stk[2 * f]);
+        });
+    }
 
+    if (in_only) return qt;                           // the next segment's worker does the rest of this visit
+    // ---------------- mergeOutNodes(u) + FIFO bookkeeping ----------------
+    bool done = false;
+    if (scalar) {
+        if (!g.err) DG_LANE0(G, g, { dgg_merge_out(gs, u); });
+    }
+    int last_out = -1;
+    while (!done && !g.err) {
+        const uint4 ul = dg_lo16(&DG_NV(g, u)), uh = dg_hi16(&DG_NV(g, u));
+        const int out_len = DG_H_OUTLEN(ul);
+        const uint32_t u_off = DG_H2_OUTOFF(uh);
+        if (out_len > G::W) break;                    // bookkeeping by the single-lane loop below
+        const bool valid = lane < out_len;
+        int d = 0, cnt = 0;
+        if (valid) { d = (int)DG_PW(g, u_off + 2 * lane); cnt = (int)DG_PW(g, u_off + 2 * lane + 1); }
+        uint4 h = make_uint4(0, 0, 0, 0);
+        if (valid) h = dg_lo16(&DG_NV(g, d));
+        if (!scalar) {
+            const gmask cand = G::ballot(valid && DG_H_INLEN(h) == 1 && d != X);
+            gmask M = 0;
+            int b = 256;
+            if (G::popc(cand) >= 2) b = dg_pick_group<G>(cand, DG_H_BASE(h), last_out, lane, &M);
+            if (b != 256) {
+                if (dg_merge_out_group<G>(g, u, u_off, M, d, cnt, h, valid, lane)) {
+                    last_out = b;
+                    continue;                         // re-read u's list, look for the next group
+                }
+                DG_LANE0(G, g, { dgg_merge_out(gs, u); });   // a list longer than the group: literal path
+                scalar = true;
+                continue;
+            }
+        }
+        // mark out-edges visited, enqueue targets whose in-edges are now all visited, in out-list order
+        // (not the exit vertex where it is k_merge_fin's)
+        qt = dg_release<G>(g, valid && d != X, d, DG_H_PEND(h) - 1, qt, N, ring, G::ent(d), lane);
+        if (qt > N) dg_fail_lane0(g, DG_E_INTERNAL, lane);
+        done = true;
+    }
+    if (!done && !g.err) {
+        // out list longer than the group: the same bookkeeping, an entry after the other
+        uint32_t nqt = qt;
+        DG_LANE0(G, g, {
+            if (!scalar) dgg_merge_out(gs, u);
+            const uint32_t off = gs.nd[u].out_off;
+            const int len = gs.nd[u].out_len;
+            for (int i = 0; i < len && !gs.err; i++) {
+                const int v = (int)gs.pool[off + 2 * i];
+                if (v == X) continue;
+                const int pend = gs.nd[v].pending - 1;
+                gs.nd[v].pending = pend;
+                if (pend == 0) {
+                    if (nqt >= N) { dgg_fail(gs, DG_E_INTERNAL); break; }
+                    ring[nqt & (G::RING - 1)] = G::ent(v);
+                    gs.queue[nqt++] = v;
+                }
+            }
+        });
+        qt = (uint32_t)G::rl((int)nqt, 0);
+    }
+    return qt;
+}
+
+// ---- mergeNodes (AlnGraphBoost.cpp:129-160): one wave per (target, segment) ----
 // One segment [c_start, c_end] of target t, swept by the calling wave.  c_end = 0x7fffffff: the segment
 // runs to the exit vertex.
 // mode DG_MM_WORKER: a segment between two cuts (with p.gcuts: enter / exit shared, exit not visited, the
@@ -870,9 +1040,6 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
     bool have_next = false;
     DgNode nu_next;                 // record of u_next, requested before the previous visit's stores
     nu_next.out_len = 0; nu_next.in_len = 0;
-#ifdef DG_STAMPS
-    unsigned long long c_fast = 0, c_slow = 0, n_fast = 0, n_slow = 0, n_scalar = 0, t_prev = clock64(), c_a = 0, c_b = 0, c_c = 0, c_grp = 0, ng_in = 0, ng_out = 0, c_odd = 0, n_odd = 0, q_a = 0, q_b = 0, q_c = 0, q_d = 0;
-#endif
     while (qh < qt && !failed) {
         if (mode == DG_MM_PROLOGUE) {
             if (qh == lvl_end) { lvl++; lvl_end = qt; }
@@ -887,36 +1054,24 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
         else u = __builtin_amdgcn_readfirstlane(g.queue[qh]);
         have_next = false;
         qh++;
-        bool scalar = false, merged = false;
-        (void)merged;
-#ifdef DG_STAMPS
-        unsigned long long ts_pre = 0, ts_in = 0, acc_grp = 0, n_grp_in = 0, n_grp_out = 0;
-        const unsigned long long ts0 = clock64();
-#endif
         if (mode != DG_MM_PROLOGUE && (u < c_start || u > c_hi)) {    // cannot happen (see k_cuts): refuse rather than race
-            dgw_fail(g, DG_E_INTERNAL, lane);
+            dg_fail_lane0(g, DG_E_INTERNAL, lane);
             break;
         }
         const bool skip_in = mode == DG_MM_WORKER && c_start != 0 && u == c_start; // the previous segment's worker merges in[u]
         const bool in_only = u == c_end;                  // ... which is this, for the next segment
-        if (in_only && qh != qt) { dgw_fail(g, DG_E_INTERNAL, lane); break; }
+        if (in_only && qh != qt) { dg_fail_lane0(g, DG_E_INTERNAL, lane); break; }
         int adj = sh ? -1 : 0;                            // 1: u is a neighbour of the shared enter / exit vertex (-1: not looked yet)
         if (mode == DG_MM_PROLOGUE && u == (int)NT - 1 && lane == 0) p.pro_state[4u * t + 3u] |= 1u;   // exit visited already
 
         // ---------------- the common case in one look: no merge group on either side --------
         {
-#ifdef DG_STAMPS
-            const unsigned long long tq0 = clock64();
-#endif
             // gfx950 counts stores in vmcnt, so a load issued behind the previous visit's stores
             // waits for them to reach L2: the record was requested before those stores went out
             DgNode nu;
             if (pre) nu = nu_next; else nu = DG_NV(g, u);
             const int eff_in = skip_in ? 0 : (int)nu.in_len, eff_out = in_only ? 0 : (int)nu.out_len;
             if (eff_in <= 32 && eff_out <= 32) {
-#ifdef DG_STAMPS
-                const unsigned long long tq1 = clock64();
-#endif
                 const bool is_in = lane < 32;
                 const int idx = lane & 31;
                 const bool valid = is_in ? idx < eff_in : idx < eff_out;
@@ -924,10 +1079,6 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
                 const uint32_t ea = is_in ? nu.in_off + (uint32_t)idx : nu.out_off + 2u * (uint32_t)idx;
                 int nbr = 0, cnt = 0;
                 if (valid) { nbr = (int)DG_PW(g, ea); cnt = (int)DG_PW(g, ea + 1); }
-#ifdef DG_STAMPS
-                asm volatile("" ::"v"(nbr), "v"(cnt));
-                const unsigned long long tq2 = clock64();
-#endif
                 uint4 h = make_uint4(0, 0, 0, 0);
                 if (valid) h = dg_lo16(&DG_NV(g, nbr));
                 // in lanes: out_len == 1 (low half of h.x), out lanes: in_len == 1 (high half); with shared
@@ -937,9 +1088,6 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
                 adj = __ballot(shn) ? 1 : 0;
                 if (adj) goto generic;
                 const unsigned long long cand = __ballot(((h.x >> (is_in ? 0u : 16u)) & 0xffffu) == 1u);
-#ifdef DG_STAMPS
-                const unsigned long long tq3 = clock64();
-#endif
                 const unsigned long long c_in = cand & 0xffffffffull;
                 unsigned long long M = 0;
                 bool in_work = false;
@@ -955,15 +1103,7 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
                         int b = 256;
                         if (__popcll(c_out) >= 2) b = dg_pick_group<DgWave>(c_out, DG_H_BASE(h), last_out, lane, &M);
                         if (b == 256) break;
-#ifdef DG_STAMPS
-                        const unsigned long long tg0 = clock64();
-#endif
-                        const bool okg = dg_merge_out_group<DgWave>(g, u, nu.out_off, M, nbr, cnt, h, live, lane);
-#ifdef DG_STAMPS
-                        c_grp += clock64() - tg0; ng_out++;
-#endif
-                        if (!okg) { bail = true; break; }
-                        merged = true;
+                        if (!dg_merge_out_group<DgWave>(g, u, nu.out_off, M, nbr, cnt, h, live, lane)) { bail = true; break; }
                         if (g.err) break;
                         last_out = b;
                         const int an_lane = __ffsll((long long)M) - 1;
@@ -972,11 +1112,11 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
                     }
                     if (!bail) {
                         if (!g.err) {
-                            // AlnGraphBoost.cpp:143-158
                             const int pend = DG_H_PEND(h) - 1;
-                            const unsigned long long rm = __ballot(live && pend == 0);
                             // the next vertex to visit is known now: the queue's head, or the first
-                            // vertex this visit enqueues
+                            // vertex this visit enqueues (rm: dg_release's own ballot, taken here as well so
+                            // that the record is asked for in front of this visit's stores)
+                            const unsigned long long rm = __ballot(live && pend == 0);
                             if (qh < qt) {
                                 if (qt - qh <= DG_QRING) { u_next = __builtin_amdgcn_readfirstlane(s_ring[qh & (DG_QRING - 1)]); have_next = true; }
                             } else if (rm) {
@@ -985,18 +1125,10 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
                             // (a vertex this visit releases still shows pending 1 in this copy; the
                             // visit of a vertex never reads its own pending counter)
                             if (have_next) nu_next = DG_NV(g, u_next);
-                            if (live) DG_NV(g, nbr).pending = pend;
-                            if (live && pend == 0) {
-                                const uint32_t pos = qt + (uint32_t)__popcll(rm & DG_LT(lane));
-                                if (pos < N) { g.queue[pos] = nbr; s_ring[pos & (DG_QRING - 1)] = nbr; }
-                            }
-                            qt += (uint32_t)__popcll(rm);
-                            if (qt > N) dgw_fail(g, DG_E_INTERNAL, lane);
+                            qt = dg_release<DgWave>(g, live, nbr, pend, qt, N, s_ring, nbr, lane);
+                            if (qt > N) dg_fail_lane0(g, DG_E_INTERNAL, lane);
                         }
                         failed = g.err;
-#ifdef DG_STAMPS
-                        { unsigned long long now = clock64(); if (merged) { c_slow += now - t_prev; n_slow++; } else { c_fast += now - t_prev; n_fast++; c_odd += tq0 - t_prev; q_a += tq1 - tq0; q_b += tq2 - tq1; q_c += tq3 - tq2; q_d += now - tq3; } t_prev = now; }
-#endif
                         continue;
                     }
                     // a list longer than a wave is involved: nothing was modified by the refused
@@ -1006,151 +1138,14 @@ __device__ __forceinline__ void dg_merge_segment(const DgParams &p, const uint32
         }
 
     generic:
-#ifdef DG_STAMPS
-        ts_pre = clock64();
-#endif
-        // ---------------- mergeInNodes(u), recursion on an explicit stack ----------------
-        int sp = skip_in ? 0 : 1;
-        int fr_n = u, fr_last = -1;                       // top frame lives in registers
-        if (adj < 0) {
-            // long lists: look for the shared vertices among u's neighbours
-            const DgNode nq = DG_NV(g, u);
-            bool f = false;
-            if (!skip_in) for (int i = lane; i < nq.in_len; i += 64) f |= (DG_NV(g, DG_PW(g, nq.in_off + i)).flags & DG_NF_SHARED) != 0;
-            if (!in_only) for (int i = lane; i < nq.out_len; i += 64) f |= (int)DG_PW(g, nq.out_off + 2 * i) == X;
-            adj = __ballot(f) ? 1 : 0;
-        }
-        if (adj) scalar = true;                           // next to enter / exit: the literal path handles their lists
-        while (sp > 0 && !scalar) {
-            const DgNode nn = DG_NV(g, fr_n);
-            if (nn.in_len > 32) { scalar = true; break; }
-            const bool valid = lane < nn.in_len;
-            int s = 0;
-            if (valid) s = (int)DG_PW(g, nn.in_off + lane);
-            uint4 h = make_uint4(0, 0, 0, 0);
-            if (valid) h = dg_lo16(&DG_NV(g, s));
-            const unsigned long long cand = __ballot(valid && DG_H_OUTLEN(h) == 1 && !(sh && ((h.y >> 8) & DG_NF_SHARED)));
-            unsigned long long M = 0;
-            int b = 256;
-            if (__popcll(cand) >= 2) b = dg_pick_group<DgWave>(cand, DG_H_BASE(h), fr_last, lane, &M);
-            if (b == 256) {                               // frame done: pop
-                sp--;
-                if (sp > 0) { fr_n = s_stk[2 * (sp - 1)]; fr_last = s_stk[2 * (sp - 1) + 1]; }
-                continue;
-            }
-            if (sp >= DG_IN_STACK) { scalar = true; break; }
-            int an = -1;
-#ifdef DG_STAMPS
-            const unsigned long long tg0 = clock64();
-#endif
-            if (!dg_merge_in_group<DgWave>(g, fr_n, nn.in_off, M, s, h, valid, lane, &an)) { scalar = true; break; }
-#ifdef DG_STAMPS
-            acc_grp += clock64() - tg0; n_grp_in++;
-#endif
-            merged = true;
-            if (g.err) break;
-            fr_last = b;
-            if (lane == 0) { s_stk[2 * (sp - 1)] = fr_n; s_stk[2 * (sp - 1) + 1] = fr_last; }
-            sp++;                                         // :213 recurse on the survivor
-            fr_n = an; fr_last = -1;
-        }
-        if (scalar && !g.err && sp > 0) {
-            // finish every open frame, deepest first, on the reference-literal path;
-            // groups already merged are gone, so re-evaluating a frame from scratch is exact
-            DG_LANE0(g, {
-                dgg_merge_in(gs, fr_n);
-                for (int f = sp - 2; f >= 0 && !gs.err; f--) dgg_merge_in(gs, s_stk[2 * f]);
-            });
-        }
-
-#ifdef DG_STAMPS
-        ts_in = clock64();
-#endif
+        // ---------------- the visit that has something to merge (or lists too long for one look) --------
+        qt = dg_visit_merging<DgWave, GC>(g, u, X, skip_in, in_only, adj, qt, N, s_stk, s_ring, lane);
         if (in_only) break;                               // the next segment's worker does the rest of this visit
-        // ---------------- mergeOutNodes(u) + FIFO bookkeeping ----------------
-        bool done = false;
-        if (scalar) {
-            if (!g.err) DG_LANE0(g, { dgg_merge_out(gs, u); });
-        }
-        int last_out = -1;
-        while (!done && !g.err) {
-            const DgNode nu = DG_NV(g, u);
-            const int out_len = nu.out_len;
-            if (out_len > 64) break;                      // bookkeeping by the single-lane loop below
-            const bool valid = lane < out_len;
-            int d = 0, cnt = 0;
-            if (valid) { d = (int)DG_PW(g, nu.out_off + 2 * lane); cnt = (int)DG_PW(g, nu.out_off + 2 * lane + 1); }
-            uint4 h = make_uint4(0, 0, 0, 0);
-            if (valid) h = dg_lo16(&DG_NV(g, d));
-            if (!scalar) {
-                const unsigned long long cand = __ballot(valid && DG_H_INLEN(h) == 1 && d != X);
-                unsigned long long M = 0;
-                int b = 256;
-                if (__popcll(cand) >= 2) b = dg_pick_group<DgWave>(cand, DG_H_BASE(h), last_out, lane, &M);
-                if (b != 256) {
-#ifdef DG_STAMPS
-                    const unsigned long long tg0 = clock64();
-                    const bool okg = dg_merge_out_group<DgWave>(g, u, nu.out_off, M, d, cnt, h, valid, lane);
-                    acc_grp += clock64() - tg0; n_grp_out++;
-                    if (okg) {
-#else
-                    if (dg_merge_out_group<DgWave>(g, u, nu.out_off, M, d, cnt, h, valid, lane)) {
-#endif
-                        merged = true;
-                        last_out = b;
-                        continue;                         // re-read u's list, look for the next group
-                    }
-                    DG_LANE0(g, { dgg_merge_out(gs, u); });   // a list longer than a wave: literal path
-                    scalar = true;
-                    continue;
-                }
-            }
-            // AlnGraphBoost.cpp:143-158: mark out-edges visited, enqueue targets whose
-            // in-edges are now all visited, in out-list order
-            const int pend = DG_H_PEND(h) - 1;
-            const bool bk = valid && d != X;              // (the exit vertex is k_merge_fin's)
-            if (bk) DG_NV(g, d).pending = pend;
-            const unsigned long long rm = __ballot(bk && pend == 0);
-            if (bk && pend == 0) {
-                const uint32_t pos = qt + (uint32_t)__popcll(rm & DG_LT(lane));
-                if (pos < N) { g.queue[pos] = d; s_ring[pos & (DG_QRING - 1)] = d; }
-            }
-            qt += (uint32_t)__popcll(rm);
-            if (qt > N) dgw_fail(g, DG_E_INTERNAL, lane);
-            done = true;
-        }
-        if (!done && !g.err) {
-            // out list longer than a wave
-            uint32_t nqt = qt;
-            DG_LANE0(g, {
-                if (!scalar) dgg_merge_out(gs, u);
-                const uint32_t off = gs.nd[u].out_off;
-                const int len = gs.nd[u].out_len;
-                for (int i = 0; i < len && !gs.err; i++) {
-                    const int v = (int)gs.pool[off + 2 * i];
-                    if (v == X) continue;
-                    const int pend = gs.nd[v].pending - 1;
-                    gs.nd[v].pending = pend;
-                    if (pend == 0) {
-                        if (nqt >= N) { dgg_fail(gs, DG_E_INTERNAL); break; }
-                        s_ring[nqt & (DG_QRING - 1)] = v;
-                        gs.queue[nqt++] = v;
-                    }
-                }
-            });
-            qt = (uint32_t)DG_RL(nqt, 0);
-        }
         failed = g.err;
-#ifdef DG_STAMPS
-        { unsigned long long now = clock64(); if (merged || scalar) { c_slow += now - t_prev; n_slow++; n_scalar += scalar; c_a += ts_pre - ts0; c_b += ts_in - ts_pre; c_c += now - ts_in; c_grp += acc_grp; ng_in += n_grp_in; ng_out += n_grp_out; } else { c_fast += now - t_prev; n_fast++; c_odd += now - t_prev; n_odd++; } t_prev = now; }
-#endif
     }
     if (mode == DG_MM_PROLOGUE && lane == 0) {
         p.pro_state[4u * t] = qh; p.pro_state[4u * t + 1u] = qt; p.pro_state[4u * t + 2u] = qh;
     }
-#ifdef DG_STAMPS
-    if (t == 0 && c_start == 0 && lane == 0) { p.st->dbg[0] = n_fast; p.st->dbg[1] = n_slow; p.st->dbg[2] = c_fast; p.st->dbg[3] = c_slow; p.st->dbg[4] = n_scalar; p.st->dbg[5] = c_a; p.st->dbg[6] = c_b; p.st->dbg[7] = c_c; p.st->dbg[8] = c_grp; p.st->dbg[9] = ng_in; p.st->dbg[10] = ng_out; p.st->dbg[11] = c_odd; p.st->dbg[12] = q_a; p.st->dbg[13] = q_b; p.st->dbg[14] = q_c; p.st->dbg[15] = q_d; }
-#endif
 }
 
 // mergeNodes (AlnGraphBoost.cpp:129-160): one wave per (target, segment of p.cuts)

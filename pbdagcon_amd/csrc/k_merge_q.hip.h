@@ -10,9 +10,12 @@
 // single-lane path (dgg_*), as lists longer than a wave do in k_merge.
 //
 // Exactness is inherited: every row runs exactly the sweep of dg_merge_segment on its own segment, and segments
-// touch disjoint state (the cut argument above k_cuts).  The merge of a group is not written again here: it is
-// k_merge.hip.h's dg_merge_in_group / dg_merge_out_group, instantiated for a row (DgRow) where k_merge instantiates
-// them for the wave (DgWave).  Full-span pileups only (p.gcuts == 0).
+// touch disjoint state (the cut argument above k_cuts).  A visit that has something to merge is not written again
+// here: it is k_merge.hip.h's dg_visit_merging (with dg_merge_in_group / dg_merge_out_group and dg_release under it),
+// instantiated for a row (DgRow) where the wave kernels instantiate it for the wave (DgWave); so are the lane-0
+// plumbing (DG_LANE0, dg_fail_lane0) and the fence.  What is this file's own is a different design from the wave's:
+// the two-phase loop of dq_merge_segment and its one-look path, 4 + 4 entries with the record carried in the ring.
+// Full-span pileups only (p.gcuts == 0).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dagcon_dev.h"
@@ -31,28 +34,16 @@ typedef uint32_t qmask;              // one bit per lane of the row
 __device__ __forceinline__ qmask dq_ballot(bool p) { return (qmask)((__ballot(p) >> (threadIdx.x & (64u - DQ_W))) & (unsigned long long)DQ_ALL); }
 __device__ __forceinline__ int dq_rl(int v, int l) { return __shfl(v, l, DQ_W); }          // lane l of the caller's row
 #define DQ_LT(lane) ((1u << (lane)) - 1u)
-// a row's earlier stores before its later loads (a single lane's, on the literal path)
-#define DQ_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup")
-#define DQ_LANE0(G, BODY)                                          \
-    do {                                                           \
-        bool e_ = false;                                           \
-        if (lane == 0) { DgGraph gs = (G); BODY; e_ = gs.err; }    \
-        DQ_FENCE();                                                \
-        (G).err = dq_ballot(e_) != 0;                              \
-    } while (0)
-
-__device__ __forceinline__ void dq_fail(DgGraph &g, uint32_t bit, int lane) {
-    if (lane == 0) {
-        if (bit & DG_E_TARGET_MASK) atomicOr(g.tfail, bit);
-        else { atomicOr(&g.st->err_flags, bit); g.st->bad_target = g.t; }
-    }
-    g.err = true;
-}
-// the row as a lane group of the merge rule (dg_merge_in_group / dg_merge_out_group, k_merge.hip.h)
+// the row as a lane group of the merge rule and of the merging visit (dg_merge_in_group / dg_merge_out_group,
+// dg_release, dg_visit_merging: k_merge.hip.h)
 struct DgRow {
     typedef qmask mask;
     static constexpr int W = DQ_W;
+    static constexpr int IN_W = DQ_W;
     static constexpr bool row_text = true;
+    typedef int4 qent;
+    static constexpr uint32_t RING = DQ_RING;
+    static __device__ __forceinline__ qent ent(int v) { return make_int4(v, -1, 0, 0); }      // (lens = -1: see dq_merge_segment)
     static __device__ __forceinline__ mask ballot(bool p) { return dq_ballot(p); }
     static __device__ __forceinline__ int rl(int v, int l) { return dq_rl(v, l); }
     static __device__ __forceinline__ int ffs(mask m) { return __ffs((int)m); }
@@ -60,7 +51,6 @@ struct DgRow {
     static __device__ __forceinline__ mask lt(int lane) { return DQ_LT(lane); }
 };
 
-#define DQ_IN_STACK 48
 // what a row is doing (dq_merge_segment)
 #define DQ_ST_RUN 0                  // visits that merge nothing, one after the other
 #define DQ_ST_NEED 1                 // its visit has a merge group or a long list: the generic code
@@ -88,7 +78,7 @@ __device__ __forceinline__ void dq_merge_segment(const DgParams &p, const uint32
     // -- lens = -1: not so.  The record of a queued vertex does not change before its visit: whoever could touch its lists
     // is one of its predecessors, or has one of them for a predecessor, and those have all been visited)
     if (lane == 0) { g.queue[0] = c_start; s_ring[0] = make_int4(c_start, -1, 0, 0); }
-    DQ_FENCE();
+    DG_WAVE_FENCE();
     // Two phases per round, so that the rows of a wave spend their time on the same code: (A) every row runs
     // through the visits that merge nothing (one look, the FIFO bookkeeping) until it meets a visit that has a merge
     // group, or a list longer than half a row, to deal with -- rows that have met theirs wait; (B) those visits, by
@@ -108,7 +98,7 @@ __device__ __forceinline__ void dq_merge_segment(const DgParams &p, const uint32
             qh++;
             const bool in_only = u == c_end;               // the next segment's worker does the rest of that visit
             if (u < c_start || u > c_hi || (in_only && qh != qt)) {       // cannot happen (see k_cuts)
-                dq_fail(g, DG_E_INTERNAL, lane);
+                dg_fail_lane0(g, DG_E_INTERNAL, lane);
                 st = DQ_ST_END;
             } else {
                 const bool skip_in = c_start != 0 && u == c_start;        // the previous segment's worker merges in[u]
@@ -150,127 +140,18 @@ __device__ __forceinline__ void dq_merge_segment(const DgParams &p, const uint32
                     if (work) st = DQ_ST_NEED;
                     else if (in_only) st = DQ_ST_END;      // nothing to merge in front of the cut: segment done
                     else {
-                        // AlnGraphBoost.cpp:143-158
-                        const bool live = valid && !is_in;
-                        const int pend = DG_H_PEND(h) - 1;
-                        const qmask rm = dq_ballot(live && pend == 0);
-                        if (live) DG_NV(g, nbr).pending = pend;
-                        if (live && pend == 0) {
-                            const uint32_t pos = qt + (uint32_t)__popc(rm & DQ_LT(lane));
-                            if (pos < N) { g.queue[pos] = nbr; s_ring[pos & (DQ_RING - 1)] = make_int4(nbr, (int)h.x, (int)ho.x, (int)ho.y); }
-                        }
-                        qt += (uint32_t)__popc(rm);
-                        if (qt > N) { dq_fail(g, DG_E_INTERNAL, lane); st = DQ_ST_END; }
+                        // the FIFO bookkeeping; the record of a vertex queued here is at hand, and goes into the ring
+                        qt = dg_release<DgRow>(g, valid && !is_in, nbr, DG_H_PEND(h) - 1, qt, N, s_ring, make_int4(nbr, (int)h.x, (int)ho.x, (int)ho.y), lane);
+                        if (qt > N) { dg_fail_lane0(g, DG_E_INTERNAL, lane); st = DQ_ST_END; }
                     }
                 }
             }
         }
         if (st != DQ_ST_NEED) break;                       // the queue ran dry, the cut was reached, or something failed
         const bool skip_in = c_start != 0 && u == c_start, in_only = u == c_end;
-        bool scalar = false;
-
-        // ---------------- mergeInNodes(u), recursion on an explicit stack ----------------
-        int sp = skip_in ? 0 : 1;
-        int fr_n = u, fr_last = -1;                       // top frame lives in registers
-        while (sp > 0 && !scalar) {
-            const uint4 nl = dg_lo16(&DG_NV(g, fr_n)), nh = dg_hi16(&DG_NV(g, fr_n));
-            if (DG_H_INLEN(nl) > DQ_W) { scalar = true; break; }
-            const bool valid = lane < DG_H_INLEN(nl);
-            int s = 0;
-            if (valid) s = (int)DG_PW(g, DG_H2_INOFF(nh) + lane);
-            uint4 h = make_uint4(0, 0, 0, 0);
-            if (valid) h = dg_lo16(&DG_NV(g, s));
-            const qmask cand = dq_ballot(valid && DG_H_OUTLEN(h) == 1);
-            qmask M = 0;
-            int b = 256;
-            if (__popc(cand) >= 2) b = dg_pick_group<DgRow>(cand, DG_H_BASE(h), fr_last, lane, &M);
-            if (b == 256) {                               // frame done: pop
-                sp--;
-                if (sp > 0) { fr_n = s_stk[2 * (sp - 1)]; fr_last = s_stk[2 * (sp - 1) + 1]; }
-                continue;
-            }
-            if (sp >= DQ_IN_STACK) { scalar = true; break; }
-            int an = -1;
-            if (!dg_merge_in_group<DgRow>(g, fr_n, DG_H2_INOFF(nh), M, s, h, valid, lane, &an)) { scalar = true; break; }
-            if (g.err) break;
-            fr_last = b;
-            if (lane == 0) { s_stk[2 * (sp - 1)] = fr_n; s_stk[2 * (sp - 1) + 1] = fr_last; }
-            sp++;                                         // :213 recurse on the survivor
-            fr_n = an; fr_last = -1;
-        }
-        if (scalar && !g.err && sp > 0) {
-            // finish every open frame, deepest first, on the reference-literal path; groups already merged are gone,
-            // so re-evaluating a frame from scratch is exact
-            DQ_LANE0(g, {
-                dgg_merge_in(gs, fr_n);
-                for (int f = sp - 2; f >= 0 && !gs.err; f--) dgg_merge_in(gs, s_stk[2 * f]);
-            });
-        }
+        // (B) the visit that has something to merge: dg_visit_merging, the text the wave kernels run
+        qt = dg_visit_merging<DgRow, false>(g, u, X, skip_in, in_only, 0, qt, N, s_stk, s_ring, lane);
         if (in_only) break;                               // the next segment's worker does the rest of this visit
-        // ---------------- mergeOutNodes(u) + FIFO bookkeeping ----------------
-        bool done = false;
-        if (scalar) {
-            if (!g.err) DQ_LANE0(g, { dgg_merge_out(gs, u); });
-        }
-        int last_out = -1;
-        while (!done && !g.err) {
-            const uint4 ul = dg_lo16(&DG_NV(g, u)), uh = dg_hi16(&DG_NV(g, u));
-            const int out_len = DG_H_OUTLEN(ul);
-            if (out_len > DQ_W) break;                    // bookkeeping by the single-lane loop below
-            const bool valid = lane < out_len;
-            int d = 0, cnt = 0;
-            if (valid) { d = (int)DG_PW(g, DG_H2_OUTOFF(uh) + 2 * lane); cnt = (int)DG_PW(g, DG_H2_OUTOFF(uh) + 2 * lane + 1); }
-            uint4 h = make_uint4(0, 0, 0, 0);
-            if (valid) h = dg_lo16(&DG_NV(g, d));
-            if (!scalar) {
-                const qmask cand = dq_ballot(valid && DG_H_INLEN(h) == 1 && d != X);
-                qmask M = 0;
-                int b = 256;
-                if (__popc(cand) >= 2) b = dg_pick_group<DgRow>(cand, DG_H_BASE(h), last_out, lane, &M);
-                if (b != 256) {
-                    if (dg_merge_out_group<DgRow>(g, u, DG_H2_OUTOFF(uh), M, d, cnt, h, valid, lane)) {
-                        last_out = b;
-                        continue;                         // re-read u's list, look for the next group
-                    }
-                    DQ_LANE0(g, { dgg_merge_out(gs, u); });   // a list longer than a row: literal path
-                    scalar = true;
-                    continue;
-                }
-            }
-            // AlnGraphBoost.cpp:143-158
-            const int pend = DG_H_PEND(h) - 1;
-            const bool bk = valid && d != X;
-            if (bk) DG_NV(g, d).pending = pend;
-            const qmask rm = dq_ballot(bk && pend == 0);
-            if (bk && pend == 0) {
-                const uint32_t pos = qt + (uint32_t)__popc(rm & DQ_LT(lane));
-                if (pos < N) { g.queue[pos] = d; s_ring[pos & (DQ_RING - 1)] = make_int4(d, -1, 0, 0); }
-            }
-            qt += (uint32_t)__popc(rm);
-            if (qt > N) dq_fail(g, DG_E_INTERNAL, lane);
-            done = true;
-        }
-        if (!done && !g.err) {
-            // out list longer than a row
-            uint32_t nqt = qt;
-            DQ_LANE0(g, {
-                if (!scalar) dgg_merge_out(gs, u);
-                const uint32_t off = gs.nd[u].out_off;
-                const int len = gs.nd[u].out_len;
-                for (int i = 0; i < len && !gs.err; i++) {
-                    const int v = (int)gs.pool[off + 2 * i];
-                    if (v == X) continue;
-                    const int pend = gs.nd[v].pending - 1;
-                    gs.nd[v].pending = pend;
-                    if (pend == 0) {
-                        if (nqt >= N) { dgg_fail(gs, DG_E_INTERNAL); break; }
-                        s_ring[nqt & (DQ_RING - 1)] = make_int4(v, -1, 0, 0);
-                        gs.queue[nqt++] = v;
-                    }
-                }
-            });
-            qt = (uint32_t)dq_rl((int)nqt, 0);
-        }
         if (g.err) break;
         st = DQ_ST_RUN;
     }
@@ -283,7 +164,7 @@ __device__ __forceinline__ void dq_merge_segment(const DgParams &p, const uint32
 #define DQ_WAVES 6
 #endif
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DQ_WAVES, DQ_WAVES))) void k_merge_q(DgParams p) {
-    __shared__ int s_stk[DQ_ROWS][2 * DQ_IN_STACK];
+    __shared__ int s_stk[DQ_ROWS][2 * DG_IN_STACK];
     __shared__ int4 s_ring[DQ_ROWS][DQ_RING];
     const uint32_t row = threadIdx.x / DQ_W;
     const uint32_t pair = blockIdx.x * DQ_ROWS + row;

@@ -1,8 +1,9 @@
 """Pileups that cross the fixed-size limits of the mergeNodes sweeps on purpose, for tests/test_merge_limits.py.
 
 The three sweeps (k_merge, k_merge_q and the partial-span dg_merge_segment<true>) keep a few fixed-size structures and
-a second code path behind each: 48 frames of the mergeInNodes recursion in LDS (DG_IN_STACK / DQ_IN_STACK), then the
-single-lane literal path; the youngest 256 / 16 queue entries in LDS (DG_QRING / DQ_RING), then the queue in memory;
+a second code path behind each: 48 frames of the mergeInNodes recursion in LDS (DG_IN_STACK, in dg_visit_merging: one
+text for all three), then the single-lane literal path; the youngest 256 / 16 queue entries in LDS (DG_QRING /
+DQ_RING), then the queue in memory;
 a row of 8 lanes (4 + 4 on its one-look path) and a wave of 64 (32 + 32 on its one-look path) as list widths, then
 the literal path; stk_words of scratch, then DG_E_STACK and a re-run; and the host's span rule, which takes a batch
 for full-span on (start == 1, columns >= target bases) alone.  Random pileups at the depths and run lengths the other
@@ -217,7 +218,8 @@ def fan(letters, levels, tlen=24, p=12):
 FANS = {"fan32": (b"GT", 5), "fan27": (b"GTN", 3), "fan512": (b"GT", 9), "fan400": (LETTERS20, 2)}
 FAN_RING = {"fan32": 16, "fan27": 16, "fan512": 256, "fan400": 256}      # the ring its occupancy must pass
 
-WIDTHS = (4, 5, 8, 9, 32, 33, 64, 65)     # rows: 4 + 4 one look, 8 generic; waves: 32 + 32 one look and the in side, 64 out
+# rows: 4 + 4 one look, 8 in dg_visit_merging (DgRow::IN_W and W); waves: 32 + 32 one look and DgWave::IN_W, 64 out
+WIDTHS = (4, 5, 8, 9, 32, 33, 64, 65)
 
 
 def width_out(L):

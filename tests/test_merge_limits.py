@@ -93,7 +93,8 @@ def test_fans_pass_the_rings(name):
 
 def test_widths_are_exact():
     """Lists with a group of exactly 4, 5 (a row's one-look half and one more), 8, 9 (a row), 32, 33 (a wave's one-look half,
-    and the longest in list its generic path takes), 64, 65 (a wave) entries, once on the in side with nothing to merge
+    and the longest in list dg_visit_merging takes on a wave, DgWave::IN_W), 64, 65 (a wave) entries, once on the in side
+    with nothing to merge
     on the out side and once the other way round.  Measured: the longest list with a group is the width, on its side;
     the other side merges no group at all."""
     c, figs = _figures("widths")

@@ -112,6 +112,9 @@ __device__ __forceinline__ bool dg_bp_piece_open(const DgParams &p, const uint32
 // LDS per sweep wave is what bounds the waves in flight (8 segments x 1000 targets want
 // ~8 KB each): only the chunk being swept needs its edges staged, and successors are
 // almost always within a few hundred ids
+// (every fixed size below, DG_BL_STK / DG_BRW / DG_BRR / DG_BRP of the rows and DG_BP_PIECES are crossed from both sides
+// by tests/test_bestpath_limits.py: widths_* DG_BOUT, DG_BRW, a round of 64; suffix DG_BL_STK, DG_BSTK, DG_BFAR; waiters
+// DG_BDEF; reach DG_SR, DG_BR, DG_BRR, DG_BRP, DG_WR, v + 192, 64 * cs + 512; pieces DG_BP_PIECES)
 #ifndef DG_SR
 #define DG_SR 256            // finished scores (id & 255)
 #define DG_BOUT 6            // out edges kept in a staged slot

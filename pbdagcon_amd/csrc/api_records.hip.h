@@ -852,6 +852,21 @@ static int dump_target(Ctx *c, const char *e) {
             }
             fwrite(&nl, 4, 1, f);
             if (nl) fwrite(wl.data(), 4, wl.size(), f);
+            // (... and, for tests/test_cut_limits.py, what the cuts were decided on: the target's sh_cnt row, its defer
+            // row, pro_state[4t .. 4t + 3], its reads K, then rd_s, rd_e, rd_lead, rd_trail of each)
+            if (c->gcuts && c->run.sh_cnt.p && c->run.defer.p && c->run.pro_state.p && c->run.rd.p) {
+                const uint64_t ab = c->h_aln_begin[t];
+                const uint32_t K = (uint32_t)(c->h_aln_begin[t + 1] - ab);
+                std::vector<uint32_t> sh(2 + 2 * DG_SH_MAX), df(DG_DEFER_MAX + 1), ps(4), rd(4 * (size_t)K);
+                (void)hipMemcpy(sh.data(), c->run.sh_cnt.as<uint32_t>() + (uint64_t)t * sh.size(), sh.size() * 4, hipMemcpyDeviceToHost);
+                (void)hipMemcpy(df.data(), c->run.defer.as<uint32_t>() + (uint64_t)t * df.size(), df.size() * 4, hipMemcpyDeviceToHost);
+                (void)hipMemcpy(ps.data(), c->run.pro_state.as<uint32_t>() + 4ull * t, 16, hipMemcpyDeviceToHost);
+                for (int j = 0; j < 4 && K; j++)
+                    (void)hipMemcpy(rd.data() + (size_t)j * K, c->run.rd.as<uint32_t>() + (uint64_t)j * c->A + ab, (size_t)K * 4, hipMemcpyDeviceToHost);
+                fwrite(sh.data(), 4, sh.size(), f); fwrite(df.data(), 4, df.size(), f); fwrite(ps.data(), 4, 4, f);
+                fwrite(&K, 4, 1, f);
+                if (K) fwrite(rd.data(), 4, rd.size(), f);
+            }
             fclose(f);
         }
     }

@@ -526,6 +526,51 @@ int dagcon_fetch_site_alleles(dagcon_ctx *ctx, dagcon_site_alleles *out);
 int dagcon_allele_text(uint64_t key, char *out, size_t cap);   /* host only; needs no device */
 
 /*
+ * Phase across windows: the read labels of neighbouring windows joined into blocks (off by default; a context switch that
+ * needs a windows upload with dagcon_set_pileup and dagcon_set_site_reads with phase != 0 on at the same upload).  Rule 4
+ * labels every window on its own: the seed of a window is label 1, so label 1 of one window and label 1 of the next are
+ * unrelated names.  A record that crosses a window boundary has a piece in both windows, and both pieces have a label.
+ * This is this build's own rule, PARITY UNPINNED, in the terms of rules 1 to 4 of the site reads above.
+ * 9. Given W windows (target[] ascending, begin[] ascending inside a target):
+ *    9.1 Predecessor.  Window w has the predecessor w - 1 iff w > 0 and target[w] == target[w - 1].
+ *    9.2 Pair counts.  For a window w with a predecessor, over the records that have a taken alignment (rule 1) in both
+ *        w - 1 and w with hap != 0 in both: same[w] counts those whose two labels are equal, diff[w] those whose labels
+ *        differ.  Without a predecessor both are 0.  A record has at most one piece per window, so nothing is counted
+ *        twice.  A failed window, a window below min_cov and a window without an informative site have no labelled
+ *        alignments: they link to nothing on either side.
+ *    9.3 Link.  hi = max(same, diff), lo = min(same, diff).  Window w is linked to its predecessor iff hi >= min_links
+ *        and hi > lo and lo * 1000000 <= max_conflict_ppm * (hi + lo), in 64-bit integers.  min_links == 0 means the
+ *        default 3 (the reasoning of min_reads in rule 6: the least that outvotes one error), max_conflict_ppm == 0 the
+ *        default 250000; both defaults are this build's own choice.
+ *    9.4 Orientation and blocks.  An unlinked window has flip[w] = 0 and block[w] = w.  A linked window has
+ *        flip[w] = flip[w - 1] ^ (diff[w] > same[w]) and block[w] = block[w - 1].  A block is a maximal run of linked
+ *        windows; its id is the index of its first window.
+ *    9.5 Oriented labels.  hap[x] is the site reads' hap[x] when that is 0 or flip of its window is 0, else 3 - hap[x];
+ *        phase[k] is the site reads' phase[k], negated when flip of the site's window is 1.  x is in the order of
+ *        dagcon_fetch_site_reads, k in the order of dagcon_fetch_pileup_sites.  The arrays of dagcon_fetch_site_reads,
+ *        dagcon_fetch_hap_tally and dagcon_fetch_site_alleles stay per window.
+ *    Nothing in the rule depends on an order.
+ * dagcon_set_window_phase: NULL turns it off; max_conflict_ppm > 1000000 is DAGCON_ERR_INVALID_ARG (the switch stays as it
+ * was).  The switch is read at the upload and takes effect for an upload with windows, by any of the window entry points
+ * (dagcon_upload_cigar_windows, _packed, _strand, _cs, _md with windows != NULL), made with the pile-up and the site reads
+ * with phase != 0 on.  In every other case it is as if off: no kernel, buffer, memset, launch or copy differs from a
+ * context that never heard of it, and dagcon_fetch_window_phase is DAGCON_ERR_STATE; the same wherever
+ * dagcon_fetch_site_reads is.  The derived batch of dagcon_upload_haps has it off.  With it on, the host uploads 4 bytes an
+ * alignment (its record) and 4 a window (its target), and the kernels of csrc/k_winlink.hip.h run right behind the split in
+ * every execution of the run.  The arrays stay on the device and are copied only when dagcon_fetch_window_phase is called,
+ * which converts them as dagcon_fetch_site_reads converts its own (it calls it).  Owned by the context, valid as long as
+ * the results of the same fetch.
+ */
+typedef struct dagcon_window_phase_opts { uint32_t min_links, max_conflict_ppm; } dagcon_window_phase_opts;   /* 0, 0: the defaults 3 and 250000 */
+int dagcon_set_window_phase(dagcon_ctx *ctx, const dagcon_window_phase_opts *o);   /* NULL: off (the default) */
+typedef struct dagcon_window_phase {
+    uint32_t n_windows; const uint32_t *same, *diff, *block; const uint8_t *flip;   /* [n_windows] */
+    uint64_t n_aln;   const uint8_t *hap;     /* oriented; the alignments of dagcon_fetch_site_reads, same order */
+    uint64_t n_sites; const int8_t *phase;    /* oriented; the sites of dagcon_fetch_pileup_sites, same order */
+} dagcon_window_phase;
+int dagcon_fetch_window_phase(dagcon_ctx *ctx, dagcon_window_phase *out);
+
+/*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses
  * alignment records straight into such a buffer gets its dagcon_upload at link speed instead of
  * through the driver's staging copies.  Optional: any host memory is accepted by dagcon_upload.

@@ -48,6 +48,7 @@ EXPORTS = [
     "dagcon_set_site_alleles", "dagcon_fetch_site_alleles", "dagcon_allele_text",
     "dagcon_set_hap_consensus", "dagcon_fetch_hap_tally", "dagcon_upload_haps", "dagcon_fetch_hap_map",
     "dagcon_upload_cigar_md", "dagcon_consensus_cigar_md", "dagcon_fetch_md_targets",
+    "dagcon_set_window_phase", "dagcon_fetch_window_phase",
 ]
 ABI_VERSION = 2
 
@@ -184,6 +185,21 @@ class HapTally(C.Structure):
                 ("split", C.POINTER(C.c_uint8)), ("site_counts", C.POINTER(C.c_uint16))]
 
 
+class WindowPhaseOpts(C.Structure):
+    """dagcon_window_phase_opts: a window is linked to the one in front when max(same, diff) >= min_links, the two differ and
+    the smaller is at most max_conflict_ppm of their sum; 0, 0 are the defaults 3 and 250000 (include/dagcon.h, rule 9)."""
+    _fields_ = [("min_links", C.c_uint32), ("max_conflict_ppm", C.c_uint32)]
+
+
+class WindowPhase(C.Structure):
+    """dagcon_window_phase: per window same, diff, block and flip; the oriented hap per alignment of dagcon_site_reads and
+    the oriented phase per site of dagcon_pileup_sites."""
+    _fields_ = [("n_windows", C.c_uint32), ("same", C.POINTER(C.c_uint32)), ("diff", C.POINTER(C.c_uint32)),
+                ("block", C.POINTER(C.c_uint32)), ("flip", C.POINTER(C.c_uint8)),
+                ("n_aln", C.c_uint64), ("hap", C.POINTER(C.c_uint8)),
+                ("n_sites", C.c_uint64), ("phase", C.POINTER(C.c_int8))]
+
+
 class HapMap(C.Structure):
     """dagcon_hap_map: the targets of the batch dagcon_upload_haps derived, two per split target of the first batch."""
     _fields_ = [("n_targets", C.c_uint32), ("src_target", C.POINTER(C.c_uint32)), ("label", C.POINTER(C.c_uint8)),
@@ -283,6 +299,8 @@ def load() -> C.CDLL:
     L.dagcon_fetch_hap_tally.argtypes = [vp, C.POINTER(HapTally)]
     L.dagcon_upload_haps.argtypes = [vp]
     L.dagcon_fetch_hap_map.argtypes = [vp, C.POINTER(HapMap)]
+    L.dagcon_set_window_phase.argtypes = [vp, C.POINTER(WindowPhaseOpts)]
+    L.dagcon_fetch_window_phase.argtypes = [vp, C.POINTER(WindowPhase)]
     L.dagcon_upload_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int]
     L.dagcon_consensus_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int,
                                             C.POINTER(Results)]
@@ -1039,6 +1057,28 @@ class Context:
                 "label": np.ctypeslib.as_array(hm.label, shape=(T,)).copy() if T else np.zeros(0, np.uint8),
                 "aln_begin": begin,
                 "aln_src": np.ctypeslib.as_array(hm.aln_src, shape=(n,)).copy() if n else np.zeros(0, np.uint64)}
+
+    def set_window_phase(self, min_links=0, max_conflict_ppm=0):
+        """dagcon_set_window_phase for every later windows upload made with set_pileup and set_site_reads(True) on: the
+        device joins the labels of neighbouring windows into blocks (window_phase()).  0, 0: the defaults 3 and 250000.
+        set_window_phase(None): off."""
+        if min_links is None:
+            self._chk(self.L.dagcon_set_window_phase(self.h, None))
+            return
+        o = WindowPhaseOpts(min_links, max_conflict_ppm)
+        self._chk(self.L.dagcon_set_window_phase(self.h, C.byref(o)))
+
+    def window_phase(self) -> dict:
+        """dagcon_fetch_window_phase (copies): same, diff, block (uint32) and flip (uint8) per window; hap (uint8, oriented,
+        per alignment of site_reads()) and phase (int8, oriented, per site of pileup_sites())."""
+        wp = WindowPhase()
+        self._chk(self.L.dagcon_fetch_window_phase(self.h, C.byref(wp)))
+        W, n, ns = int(wp.n_windows), int(wp.n_aln), int(wp.n_sites)
+
+        def arr(ptr, k, dt):
+            return np.ctypeslib.as_array(ptr, shape=(k,)).copy() if k else np.zeros(0, dt)
+        return {"same": arr(wp.same, W, np.uint32), "diff": arr(wp.diff, W, np.uint32), "block": arr(wp.block, W, np.uint32),
+                "flip": arr(wp.flip, W, np.uint8), "hap": arr(wp.hap, n, np.uint8), "phase": arr(wp.phase, ns, np.int8)}
 
     def edits(self) -> dict:
         """dagcon_fetch_edits (copies): seg_t0, seg_t1 (uint32, one per segment of the last results, in their order),

@@ -70,6 +70,7 @@ struct InBufs {
     DevBuf tmp_off;                                 // dagcon_upload_haps: where each alignment's normalisation scratch lies (its groups share strings)
     DevBuf ed_tbase;                                // dagcon_set_edits: where each target's bases begin in cg.t
     DevBuf pile_begin;                              // dagcon_set_pileup: where each target's positions begin in run.pile
+    DevBuf wl_rec, wl_tgt;                          // dagcon_set_window_phase: each alignment's record, each window's target
 };
 // RunBufs: what the kernels of a run fill and nobody clears.  all() is the set DAGCON_POISON & 8 fills with 0xEE bytes
 // before every run (launch_all): a new member goes into it, and the static_assert below says so
@@ -92,21 +93,22 @@ struct RunBufs {
     // entries; per entry its site and code; per site its phase, sign rule and a round's sum
     DevBuf sr_bits, sr_rank, sr_cnt, sr_off, sr_site, sr_code, sr_hap, sr_sigma, sr_kind, sr_acc, sr_nz;
     DevBuf hap_cnt, hap_rec;                        // dagcon_set_hap_consensus: 8 B per site (cleared before every run), DG_HAP_REC words per target
+    DevBuf wl_cnt, wl_block, wl_flip, wl_hap, wl_phase;    // dagcon_set_window_phase: 8 + 4 + 1 B per window, 1 B per alignment, 1 B per site
     // dagcon_set_site_alleles: per entry its place, then its allele's index; per site its stretch's offset, its cursor
     // (cleared before every run), its table's size and offset, the list of the deep sites; the stretches (keys, counts,
     // counts per label, the places' indices); the compact tables (sized and filled at the fetch); the two totals
     DevBuf al_map, al_idx, al_soff, al_cur, al_nd, al_deep, al_toff, al_srt, al_tcnt, al_thap, al_ckey, al_ccnt, al_chap, al_tot;
-    std::array<DevBuf *, 89> all() {
+    std::array<DevBuf *, 94> all() {
         return {&nmis, &n_lo, &n_hi, &n_start, &n_ins, &n_del, &ch_k0, &ch_next, &ch_w, &ch_tb, &ch_flag, &ch_src, &ch_out, &ch_adv, &n_lb, &norm_tmp, &ckpt,
                 &node_base, &n_nodes, &pool_base, &pool_size, &pool_top, &t_nins, &cov, &gcount, &gbase, &bid, &best, &queue, &score, &cns_tmp, &bp_tt,
                 &stk, &cuts, &cuts_bp, &bp_stat, &bp_len, &rd, &pro_state, &sh_cnt, &wl_first, &queue0, &bp_end, &bp_ab, &defer, &cns_tmp0, &cns,
                 &seg, &worklist, &seg_done, &sup_tmp, &sup_tmp0, &sup, &pos_tmp, &pos_tmp0, &pos, &ed_seg, &ed_out, &evid, &pile, &pile_tile, &pile_site,
                 &sr_bits, &sr_rank, &sr_cnt, &sr_off, &sr_site, &sr_code, &sr_hap, &sr_sigma, &sr_kind, &sr_acc, &sr_nz,
-                &hap_cnt, &hap_rec,
+                &hap_cnt, &hap_rec, &wl_cnt, &wl_block, &wl_flip, &wl_hap, &wl_phase,
                 &al_map, &al_idx, &al_soff, &al_cur, &al_nd, &al_deep, &al_toff, &al_srt, &al_tcnt, &al_thap, &al_ckey, &al_ccnt, &al_chap, &al_tot};
     }
 };
-static_assert(sizeof(RunBufs) == 89 * sizeof(DevBuf), "RunBufs::all() must name every member");
+static_assert(sizeof(RunBufs) == 94 * sizeof(DevBuf), "RunBufs::all() must name every member");
 // ArenaBufs: the arenas with a treatment of their own -- matC is cleared before every run, the others are filled under
 // DAGCON_POISON bits 1 (matA, matD), 2 (nodes, pool) and 4 (score_b, norm)
 struct ArenaBufs {
@@ -220,6 +222,10 @@ struct Ctx {
     // dagcon_set_site_alleles: the switch; whether the batch on the device was uploaded under it (and under the pile-up and
     // the site reads)
     bool al_on = false, al_batch = false;
+    // dagcon_set_window_phase: the switch; whether the batch on the device is a windows upload made under it (and under the
+    // pile-up and the site reads with phase on) and with which options (the defaults filled in)
+    bool wl_on = false, wl_batch = false;
+    dagcon_window_phase_opts wl_opts = {0u, 0u}, wl_batch_opts = {0u, 0u};
     // the growing arenas: run.ed_out (and run.evid beside it), run.pile_site, run.sr_site / sr_code.  The status block
     // holds 16 bytes for the edits' total, then 16 for the sites', whose second word is the entries'
     GrowArena ed_arena{"edits", DG_E_ED_OVF, true, &DgParams::ed_top, &DgParams::ed_cap};
@@ -282,6 +288,12 @@ struct Ctx {
     std::vector<uint64_t> z_begin, z_key;
     std::vector<uint32_t> z_count;
     std::vector<uint16_t> z_hap, z_ent;
+    bool wl_valid = false;              // the last fetch was of a batch with dagcon_set_window_phase on (dagcon_fetch_window_phase)
+    bool wl_fetched = false;            // the arrays below are that run's, in the host's order of the alignments and the sites
+    std::vector<uint32_t> x_dev;        // [n_aln] the device's index of alignment x (filled by dagcon_fetch_site_reads for such a batch)
+    std::vector<uint32_t> w_same, w_diff, w_block;
+    std::vector<uint8_t> w_flip, w_hap;
+    std::vector<int8_t> w_phase;
     bool hapmap_valid = false;          // the batch on the device is dagcon_upload_haps': the arrays below describe it (dagcon_fetch_hap_map)
     std::vector<uint32_t> m_src_target;
     std::vector<uint8_t> m_label;
@@ -294,7 +306,7 @@ struct Ctx {
     // brought, and stay readable until the next fetch replaces them.  (The *_batch latches are the upload's own business.)
     void drop_results(const Fresh lv) {
         ed_valid = pos_pending = evid_valid = pile_valid = pile_fetched = sr_valid = sr_fetched = false;
-        hap_valid = hap_fetched = hap_sites_fetched = al_fetched = false;
+        hap_valid = hap_fetched = hap_sites_fetched = al_fetched = wl_valid = wl_fetched = false;
         if (lv != Fresh::RUN) sup_valid = pos_valid = false;
         if (lv != Fresh::FETCH) fetched = false;
         if (lv == Fresh::UPLOAD) uploaded = ran = md_valid = md_fetched = hapmap_valid = false;

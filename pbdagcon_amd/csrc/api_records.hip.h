@@ -494,6 +494,21 @@ int edits_arm(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
     return DAGCON_OK;
 }
 
+// dagcon_set_window_phase: the batch the hand-over left is a windows upload whose labels the run is to join.  Each
+// alignment's record (4 bytes; h_aln_src holds it) and each window's target go up, the run's arrays get their room
+int window_phase_arm(Ctx *c, const dagcon_windows *wn) {
+    std::vector<uint32_t> rec(c->h_aln_src.size());
+    for (size_t a = 0; a < rec.size(); a++) rec[a] = (uint32_t)c->h_aln_src[a];
+    c->wl_batch = true;
+    c->wl_batch_opts = {c->wl_opts.min_links ? c->wl_opts.min_links : 3u, c->wl_opts.max_conflict_ppm ? c->wl_opts.max_conflict_ppm : 250000u};
+    int r;
+    UPLOAD(c, c->in.wl_rec, rec);
+    UPLOAD(c, c->in.wl_tgt, wn->target, (size_t)c->T);
+    if ((r = ensure_arenas(c))) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));                   // (rec is a local)
+    return DAGCON_OK;
+}
+
 // what follows the scan and the judgement of every record intake: rate, pick, plan, expand, hand-over
 int records_finish(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn, const RecordSource &src, CigarScan &sc, const CigarVerdict &v) {
     int r;
@@ -507,6 +522,7 @@ int records_finish(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const d
     if ((r = wn ? plan_windows(c, b, wn, sc, v, pk, pl) : plan_whole(c, b, sc, v, pk, pl))) return r;
     if ((r = cigar_expand(c, b, src, sc, pl))) return r;
     if ((r = cigar_hand_over(ctx, c, b, pl, v, pk))) return r;
+    if (wn && c->wl_on && c->sr_batch && c->sr_batch_opts.phase && (r = window_phase_arm(c, wn))) return r;
     return c->edits_on ? edits_arm(c, b, wn) : DAGCON_OK;
 }
 

@@ -143,6 +143,10 @@ int ensure_arenas(Ctx *c) {
             ENSURE(c, c->run.sr_sigma, c->site_arena.cap); ENSURE(c, c->run.sr_kind, c->site_arena.cap); ENSURE(c, c->run.sr_acc, c->site_arena.cap * 4);
         }
         if (c->hap_batch) { ENSURE(c, c->run.hap_cnt, c->site_arena.cap * 8); ENSURE(c, c->run.hap_rec, (size_t)c->T * DG_HAP_REC * 4); }
+        if (c->wl_batch) {
+            ENSURE(c, c->run.wl_cnt, (size_t)c->T * 8); ENSURE(c, c->run.wl_block, (size_t)c->T * 4); ENSURE(c, c->run.wl_flip, (size_t)c->T);
+            ENSURE(c, c->run.wl_hap, (size_t)c->A); ENSURE(c, c->run.wl_phase, c->site_arena.cap);
+        }
         if (c->al_batch) {
             const size_t ne = c->sr_arena.cap, ns = c->site_arena.cap;
             // (20 bytes an entry and 28 a site; the compact tables wait for dagcon_fetch_site_alleles, which knows their size)
@@ -259,6 +263,12 @@ void fill_params(Ctx *c, DgParams &p) {
             p.hap_cnt = c->run.hap_cnt.as<uint32_t>(); p.hap_rec = c->run.hap_rec.as<uint32_t>();
             p.hap_min_sites = c->hap_batch_opts.min_sites; p.hap_min_reads = c->hap_batch_opts.min_reads;
             p.hap_min_cov = std::max<uint32_t>(1u, c->opts.min_cov);
+        }
+        if (c->wl_batch) {
+            p.wl_rec = c->in.wl_rec.as<const uint32_t>(); p.wl_tgt = c->in.wl_tgt.as<const uint32_t>();
+            p.wl_cnt = c->run.wl_cnt.as<uint32_t>(); p.wl_block = c->run.wl_block.as<uint32_t>(); p.wl_flip = c->run.wl_flip.as<uint8_t>();
+            p.wl_hap = c->run.wl_hap.as<uint8_t>(); p.wl_phase = c->run.wl_phase.as<int8_t>();
+            p.wl_min_links = c->wl_batch_opts.min_links; p.wl_max_ppm = c->wl_batch_opts.max_conflict_ppm;
         }
         if (c->al_batch) {
             p.al_map = c->run.al_map.as<uint16_t>(); p.al_idx = c->run.al_idx.as<uint16_t>();
@@ -429,6 +439,13 @@ int launch_all(Ctx *c) {
                 hipLaunchKernelGGL(k_sr_scan, dim3(1), dim3(1024), 0, s, p);
                 if (c->A > 0) hipLaunchKernelGGL(k_sr_walk<true>, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
                 if (p.sr_phase && c->A > 0) hipLaunchKernelGGL(k_sr_split, dim3(c->T), dim3(256), 0, s, p);
+                if (c->wl_batch && c->A > 0) {
+                    // the windows' labels joined into blocks (k_winlink.hip.h): a wave per window, one scan, a thread per
+                    // alignment and site.  Every word they leave is written in every execution: nothing to clear
+                    hipLaunchKernelGGL(k_wl_pairs, dim3((c->T + 3) / 4), dim3(256), 0, s, p);
+                    hipLaunchKernelGGL(k_wl_scan, dim3(1), dim3(1024), 0, s, p);
+                    hipLaunchKernelGGL(k_wl_apply, dim3((uint32_t)((std::max<uint64_t>(c->A, p.site_cap) + 255) / 256)), dim3(256), 0, s, p);
+                }
                 if (c->al_batch && c->A > 0) {
                     // the alleles at the sites (k_alleles.hip.h): a stretch per site, the keys, a table per site, the
                     // tables' places, an index per entry (and the counts per label, behind the split).
@@ -544,6 +561,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->sr_batch = c->sr_on && c->pile_on; c->sr_batch_opts = c->sr_opts;
     c->hap_batch = c->hap_on && c->sr_batch && c->sr_opts.phase != 0;
     c->al_batch = c->al_on && c->sr_batch;
+    c->wl_batch = false;                                    // (a windows upload with the switch on says so after the hand-over)
     c->hap_batch_opts = {c->hap_opts.min_sites ? c->hap_opts.min_sites : 2u, c->hap_opts.min_reads ? c->hap_opts.min_reads : 3u};
     c->h_aln_src.clear();
     c->h_cig_bad.clear();
@@ -1037,6 +1055,7 @@ static int unpack_sites(Ctx *c, const FetchPlan &f) {
         if (int r = arena_total(c, c->sr_arena, T && c->h_pile_begin.back(), c->sr_n_ent)) return r;
         c->sr_valid = true;
         c->hap_valid = c->hap_batch;
+        c->wl_valid = c->wl_batch;
     }
     return DAGCON_OK;
 }
@@ -1208,7 +1227,7 @@ int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out) {
         if (ne) { HIPCHK(c, d2h(c, site.data(), c->run.sr_site.p, (size_t)ne * 4)); HIPCHK(c, d2h(c, code.data(), c->run.sr_code.p, (size_t)ne)); }
         if (phase && ran && A) HIPCHK(c, d2h(c, hap.data(), c->run.sr_hap.p, (size_t)A));
         if (phase && ns) HIPCHK(c, d2h(c, sigma.data(), c->run.sr_sigma.p, (size_t)ns));
-        c->x_tgt.clear(); c->x_src.clear(); c->x_begin.assign(1, 0); c->x_site.clear(); c->x_code.clear(); c->x_hap.clear();
+        c->x_tgt.clear(); c->x_src.clear(); c->x_begin.assign(1, 0); c->x_site.clear(); c->x_code.clear(); c->x_hap.clear(); c->x_dev.clear();
         uint64_t e = 0;
         for (uint32_t a = 0; a < A; a++) {
             const uint32_t t = c->h_aln_tgt[a], n = cnt[a] & ~DG_SR_TAKEN;
@@ -1227,6 +1246,7 @@ int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out) {
             c->x_tgt.push_back(t); c->x_src.push_back(c->h_aln_src[a]); c->x_begin.push_back(c->x_site.size());
             if (hap[a] > 2u) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_split: alignment %u has hap %u", a, hap[a]);
             c->x_hap.push_back(hap[a]);
+            if (c->wl_batch) c->x_dev.push_back(a);
         }
         if (e != ne) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_walk: the alignments hold %llu entries, the batch %llu", (unsigned long long)e, (unsigned long long)ne);
         c->x_phase.assign(c->s_pos.size() + 1, 0);
@@ -1405,6 +1425,69 @@ int dagcon_fetch_hap_tally(dagcon_ctx *ctx, dagcon_hap_tally *out) {
     out->n1 = c->y_rec.data(); out->n2 = out->n1 + T; out->n0 = out->n2 + T;
     out->n_sep = out->n0 + T; out->agree = out->n_sep + T; out->disagree = out->agree + T;
     out->split = c->y_split.data(); out->site_counts = c->y_counts.data();
+    return DAGCON_OK;
+}
+
+int dagcon_set_window_phase(dagcon_ctx *ctx, const dagcon_window_phase_opts *o) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!o) { c->wl_on = false; return DAGCON_OK; }
+    if (o->max_conflict_ppm > 1000000u) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_window_phase: max_conflict_ppm %u is more than 1000000", o->max_conflict_ppm);
+    c->wl_opts = *o;
+    c->wl_on = true;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_window_phase(dagcon_ctx *ctx, dagcon_window_phase *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->wl_valid || !c->sr_valid || !c->pile_valid)
+        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_window_phase without the results of a windows upload made with dagcon_set_pileup, dagcon_set_site_reads "
+                                         "(phase on) and dagcon_set_window_phase on (a switch off at the upload, no windows, no fetch yet, or stopped before bestPath)");
+    const uint32_t T = c->T;
+    if (!c->wl_fetched) {
+        // the alignments and the sites go into the host's order as in dagcon_fetch_site_reads, which says which stay (x_dev)
+        dagcon_site_reads sr;
+        if (int r = dagcon_fetch_site_reads(ctx, &sr)) return r;
+        const uint32_t A = c->A;
+        const uint64_t ns = c->sr_n_site;
+        const bool ran = T && A && c->h_pile_begin.back();         // (otherwise launch_all started none of the kernels)
+        std::vector<uint32_t> cnt((size_t)T * 2, 0u);
+        std::vector<uint8_t> hap((size_t)A, 0);
+        std::vector<int8_t> sigma((size_t)ns, 0);
+        c->w_block.assign((size_t)T + 1, 0u); c->w_flip.assign((size_t)T + 1, 0);
+        for (uint32_t t = 0; t < T; t++) c->w_block[t] = t;
+        if (ran) {
+            HIPCHK(c, d2h(c, cnt.data(), c->run.wl_cnt.p, (size_t)T * 8));
+            HIPCHK(c, d2h(c, c->w_block.data(), c->run.wl_block.p, (size_t)T * 4));
+            HIPCHK(c, d2h(c, c->w_flip.data(), c->run.wl_flip.p, (size_t)T));
+            HIPCHK(c, d2h(c, hap.data(), c->run.wl_hap.p, (size_t)A));
+            if (ns) HIPCHK(c, d2h(c, sigma.data(), c->run.wl_phase.p, (size_t)ns));
+        }
+        c->w_same.assign((size_t)T + 1, 0u); c->w_diff.assign((size_t)T + 1, 0u);
+        for (uint32_t t = 0; t < T; t++) {
+            c->w_same[t] = cnt[2 * (size_t)t]; c->w_diff[t] = cnt[2 * (size_t)t + 1];
+            if (c->w_block[t] > t || c->w_flip[t] > 1u || (c->w_block[t] == t && c->w_flip[t]))
+                return fail(c, DAGCON_ERR_INTERNAL, "k_wl_scan: window %u has block %u, flip %u", t, c->w_block[t], c->w_flip[t]);
+        }
+        const size_t nx = c->x_dev.size();
+        c->w_hap.assign(nx + 1, 0);
+        for (size_t x = 0; x < nx; x++) {
+            const uint8_t h = hap[c->x_dev[x]];
+            if (h > 2u) return fail(c, DAGCON_ERR_INTERNAL, "k_wl_apply: alignment %u has hap %u", c->x_dev[x], h);
+            c->w_hap[x] = h;
+        }
+        c->w_phase.assign(c->s_pos.size() + 1, 0);
+        for (uint32_t t = 0; t < T; t++) {
+            if (c->r_status[t] != DAGCON_OK) continue;
+            for (uint64_t j = c->s_begin[t]; j < c->s_begin[t + 1]; j++) c->w_phase[j] = sigma[c->s_dev_begin[t] + (j - c->s_begin[t])];
+        }
+        c->wl_fetched = true;
+    }
+    out->n_windows = T;
+    out->same = c->w_same.data(); out->diff = c->w_diff.data(); out->block = c->w_block.data(); out->flip = c->w_flip.data();
+    out->n_aln = c->x_dev.size(); out->hap = c->w_hap.data();
+    out->n_sites = c->s_pos.size(); out->phase = c->w_phase.data();
     return DAGCON_OK;
 }
 

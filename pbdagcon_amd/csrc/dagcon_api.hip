@@ -36,6 +36,7 @@
 #include "k_site_reads.hip.h"
 #include "k_hap.hip.h"
 #include "k_alleles.hip.h"
+#include "k_winlink.hip.h"
 #include "host/alleles.h"
 #include "api_ctx.h"
 #include "api_run.hip.h"

@@ -274,6 +274,15 @@ struct DgParams {
     uint32_t *al_ccnt, *al_chap;
     unsigned long long *al_ent_top, *al_top;   // the sum of the depths; the alleles of the batch (words of their own, fetched when asked)
     uint64_t al_nocap;             // 2^64 - 1: the two scans have no arena of their own to outgrow
+    // ---- the windows' labels joined into blocks (dagcon_set_window_phase; NULL / 0 otherwise): k_winlink.hip.h ----
+    const uint32_t *wl_rec;        // [A] the record an alignment is a piece of; ascending inside a window
+    const uint32_t *wl_tgt;        // [T] the target a window lies on: the window in front is its predecessor iff it has the same
+    uint32_t *wl_cnt;              // [2 * T] a window's same, diff (k_wl_pairs)
+    uint32_t *wl_block;            // [T] the first window of its block (k_wl_scan)
+    uint8_t *wl_flip;              // [T] its orientation
+    uint8_t *wl_hap;               // [A] sr_hap, oriented (k_wl_apply)
+    int8_t *wl_phase;              // [site_cap] sr_sigma, oriented
+    uint32_t wl_min_links, wl_max_ppm;     // dagcon_window_phase_opts (the defaults filled in)
 };
 #define DG_HAP_REC 8u
 #define DG_SR_TAKEN 0x80000000u

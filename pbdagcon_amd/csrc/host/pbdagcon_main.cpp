@@ -73,6 +73,7 @@ struct Opts {
     std::string vcf;                   // --vcf FILE (MODE_RECORDS, whole targets): the edits as VCF with the reads behind each
     bool want_edits() const { return !edits.empty() || !vcf.empty(); }
     DgPileOpts pile;                   // --pileup FILE, --sites FILE [--site-min-frac F] [--site-min-count N] (every mode): what the alignments show per position
+    DgWinPhaseOpts wp;                 // --phase-windows [--phase-min-links N] [--phase-max-conflict F]: --site-reads / --haplotag with --window, the windows' labels joined (windows.h)
     DgSiteReadOpts sr;                 // --site-reads FILE, --haplotag FILE (whole targets, not -a): which read shows which allele at the sites; a two-way split
     DgHapOpts hap;                     // --hap-consensus FILE, --hap-sites FILE (where --haplotag goes): a consensus per group of the split, the split's tally
     DgAlleleOpts al;                   // --site-alleles FILE, --site-vcf FILE (where --site-reads goes): the alleles themselves at the sites, counted
@@ -161,6 +162,17 @@ void usage(FILE *f) {
             "                      not indexes into the consensus string; a break in the consensus starts a new record\n"
             "  --overlap O         with --window: bases a window is widened by on either side (default 1000); at least\n"
             "                      --trim + 64, so that trimming at a window's ends does not thin the coverage inside its core\n"
+            "  --phase-windows     with --window and --site-reads FILE and / or --haplotag FILE: the two-way read split across\n"
+            "                      the windows.  Every window is split on its own; a read that crosses a window boundary has a\n"
+            "                      piece, and a label, in both windows.  A window is linked to the one in front when at least\n"
+            "                      --phase-min-links N (default 3) such reads agree on how the two windows' labels correspond\n"
+            "                      and at most the fraction --phase-max-conflict F (default 0.25; decimal text with at most six\n"
+            "                      places) of them disagree; linked windows form a block with one naming of the labels, found\n"
+            "                      on the GPU.  --site-reads FILE then has the lines of the sites inside the windows' cores,\n"
+            "                      POS in target coordinates; --haplotag FILE has one line per record with a piece the graph\n"
+            "                      took, RNAME QNAME HAP SITES PS: HAP by the vote of the record's pieces in the block that holds\n"
+            "                      most of them, PS 1 + the first core position of that block (. when no piece has a label).\n"
+            "                      The consensus on stdout is unchanged.  This build's own rule, parity unpinned\n"
             "  --max-error F       with --sam, --bam or --paf: leave out the records whose read disagrees with the target in more\n"
             "                      than the fraction F of the alignment's columns (mismatches + inserted + deleted bases; = and X\n"
             "                      ops are not trusted, the bases are compared, case ignored).  F is decimal text in [0, 1] with\n"
@@ -333,6 +345,12 @@ int parse_args(int argc, char **argv, Opts &o) {
             i++; o.pile.frac_set = true;
         }
         else if (a == "--site-min-count") { if (!need(&o.pile.min_count)) return 2; o.pile.count_set = true; }
+        else if (a == "--phase-windows") o.wp.on = true;
+        else if (a == "--phase-min-links") { if (!need(&o.wp.min_links)) return 2; o.wp.links_set = true; }
+        else if (a == "--phase-max-conflict") {
+            if (i + 1 >= argc || !dg_parse_ppm(argv[i + 1], &o.wp.max_conflict_ppm)) { fprintf(stderr, "PARSE ERROR: --phase-max-conflict takes a fraction in [0, 1] with at most six decimal places\n"); return 2; }
+            i++; o.wp.conflict_set = true;
+        }
         else if (a == "--window") { if (!need(&o.window) || !o.window) { fprintf(stderr, "PARSE ERROR: --window takes a positive number of bases\n"); return 2; } }
         else if (a == "--max-error") {
             if (i + 1 >= argc || !dg_parse_ppm(argv[i + 1], &o.pick.max_error_ppm)) { fprintf(stderr, "PARSE ERROR: --max-error takes a fraction in [0, 1] with at most six decimal places\n"); return 2; }
@@ -405,7 +423,10 @@ int parse_args(int argc, char **argv, Opts &o) {
     if ((o.hap.sites_set || o.hap.reads_set) && !o.hap.on()) { fprintf(stderr, "PARSE ERROR: --hap-min-sites and --hap-min-reads need --hap-consensus or --hap-sites\n"); return 2; }
     if (o.hap.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
     if (o.hap.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
-    if (o.sr.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
+    if (o.wp.on && !o.window) { fprintf(stderr, "PARSE ERROR: --phase-windows needs --window\n"); return 2; }
+    if (o.wp.on && !o.sr.on()) { fprintf(stderr, "PARSE ERROR: --phase-windows needs --site-reads FILE or --haplotag FILE\n"); return 2; }
+    if ((o.wp.links_set || o.wp.conflict_set) && !o.wp.on) { fprintf(stderr, "PARSE ERROR: --phase-min-links and --phase-max-conflict need --phase-windows\n"); return 2; }
+    if (o.sr.on() && ((o.window && !o.wp.on) || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
     if (o.sr.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (o.al.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --site-alleles and --site-vcf do not go with --window, -a or --polish (they go where --site-reads goes)\n"); return 2; }
     if (o.al.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --site-alleles and --site-vcf do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
@@ -1497,7 +1518,7 @@ int main(int argc, char **argv) {
     // ---- --window: the window driver takes the records from here (windows.h) ----
     if (o.window && !o.dump) {
         DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0], o.pick, o.edits.empty() ? nullptr : o.edits.c_str(),
-                     g_pileup, g_sites, o.pile.min_count, o.pile.min_frac_ppm};
+                     g_pileup, g_sites, o.pile.min_count, o.pile.min_frac_ppm, g_site_reads, g_haplotag, o.wp};
         if (o.kind == DG_REC_PACKED) { DgBamSource src(bam, ref); return close_pile(dg_run_windows(wo, src, ref)); }
         if (o.kind == DG_REC_PACKED_MD) { DgBamMdSource src(bam, ref); return close_pile(dg_run_windows(wo, src, ref)); }
         if (o.kind == DG_REC_PLAIN_MD) { DgSamMdSource src(in.data, in.size, ref); return close_pile(dg_run_windows(wo, src, ref)); }

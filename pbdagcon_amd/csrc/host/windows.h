@@ -46,6 +46,11 @@
 //
 // The pile-up (--pileup FILE, --sites FILE; pileup.h) needs no stitch: the cores tile the target, so the line of target
 // position p is that of position p - begin of the window whose core holds p, written group by group in window order.
+//
+// The read split across windows (--phase-windows with --site-reads FILE / --haplotag FILE; window_phase.h has the lines
+// and the host's part of the rule, include/dagcon.h rule 9 the rule).  Every group is uploaded with the pile-up, the site
+// reads with phase on and dagcon_set_window_phase; inside a group the links are the device's, between two groups the host
+// links the one pair of windows from the pieces it kept of the last window, and orientation and block carry over.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -60,6 +65,7 @@
 #include "intake.h"
 #include "pileup.h"
 #include "sam.h"
+#include "window_phase.h"
 
 struct DgPieceEdit { long long t_pos, t_len, c_off, c_len; };   // target [t_pos, t_pos + t_len) -> seq[c_off, c_off + c_len)
 
@@ -165,6 +171,8 @@ struct DgWinOpts {
     const char *edits;                                     // --edits FILE, or NULL
     FILE *pileup = nullptr, *sites = nullptr;              // --pileup / --sites: open files, or NULL (the caller closes them)
     uint32_t site_min_count = 0, site_min_ppm = 0;
+    FILE *site_reads = nullptr, *haplotag = nullptr;       // --phase-windows with --site-reads / --haplotag: open files, or NULL
+    DgWinPhaseOpts wp;
 };
 
 // SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
@@ -234,7 +242,7 @@ template <class Source> unsigned long long dg_source_no_md(const Source &, long)
 template <class Source>
 inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref) {
     struct Rec { uint32_t pos, s, e, q_len; const char *q; size_t q_bytes; uint64_t op0; uint32_t nops; bool reverse; uint32_t t_span; const char *md; uint32_t md_len; };   // q, q_bytes: its bytes of the q blob
-    struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; std::vector<uint8_t> fate; std::string rebuilt; };   // fate: DAGCON_FATE_* per record, over all groups; rebuilt: md kinds with --edits, the target as the device made it
+    struct Tgt { std::string name; DgRefSeqs::Span sp; std::vector<Rec> recs; uint32_t max_span = 0; std::vector<uint8_t> fate; std::string rebuilt; std::vector<std::string> qnames; };   // fate: DAGCON_FATE_* per record, over all groups; rebuilt: md kinds with --edits, the target as the device made it
     constexpr bool MD = dg_kind_md(Source::kind);
     std::vector<Tgt> tgts;
     std::vector<uint32_t> ops;
@@ -274,6 +282,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         r.s = (uint32_t)s0; r.e = (uint32_t)e0;
         t.max_span = std::max(t.max_span, r.e > r.s ? r.e - r.s : 0u);
         t.recs.push_back(r);
+        if (o.wp.on) t.qnames.emplace_back(ar.qname, ar.qname_len);        // --phase-windows: the files name the reads
     }
     if (o.verbose && src.skipped) fprintf(stderr, "pbdagcon: %llu %s\n", src.skipped, kd.skipped_what);
     dg_report_no_md(Source::kind, dg_source_no_md(src, 0));
@@ -300,11 +309,24 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
     }
     // --pileup / --sites: a position's line comes from the window whose core holds it
     const bool pile = o.pileup || o.sites, want_rebuilt = ef || pile;
-    if (pile) {
+    if (pile || o.wp.on) {
         const dagcon_pileup_opts po = {o.site_min_count, o.site_min_ppm};
         if ((rc = dagcon_set_pileup(ctx, &po)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); if (ef) fclose(ef); dagcon_destroy(ctx); return 1; }
     }
-    std::string pile_out, site_out;
+    if (o.wp.on) {
+        const dagcon_site_reads_opts so = {1u, 0u};
+        const dagcon_window_phase_opts wo = {o.wp.min_links, o.wp.max_conflict_ppm};
+        if ((rc = dagcon_set_site_reads(ctx, &so)) != DAGCON_OK || (rc = dagcon_set_window_phase(ctx, &wo)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); if (ef) fclose(ef); dagcon_destroy(ctx); return 1; }
+    }
+    // --phase-windows: per record of the current target its pieces' votes and its signed entries inside the cores; the
+    // last window of the group before (its target, its link, its taken pieces) for the link across the groups
+    struct RecAcc { bool taken = false; uint64_t sites = 0; std::vector<DgWpVote> pieces; };
+    std::vector<RecAcc> acc;
+    long long prev_tgt = -1;
+    DgWpLink prev_link{0, 0};
+    std::vector<DgWpPiece> prev_pieces;
+    unsigned long long n_blocks = 0;
+    std::string pile_out, site_out, reads_out, tags_out;
     for (Tgt &t : tgts) t.fate.assign(t.recs.size(), 0);
     int status = 0;
     DgStitch st;
@@ -335,6 +357,18 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             fwrite(out.data(), 1, out.size(), ef);
             out.clear();
         }
+        if (o.wp.on) {
+            // --haplotag: the records of the target that have a taken piece, in record order
+            const Tgt &t = tgts[(size_t)cur_tgt];
+            for (size_t i = 0; i < acc.size() && o.haplotag; i++) {
+                if (!acc[i].taken) continue;
+                unsigned hap = 0;
+                uint64_t block = 0;
+                const bool labelled = dg_wp_vote(acc[i].pieces, hap, block);
+                dg_wp_haplotag_line(tags_out, t.name, t.qnames[i], hap, acc[i].sites, labelled, labelled ? (uint64_t)wins[block].c0 + 1u : 0u);
+            }
+            acc.clear();
+        }
         std::string().swap(tgts[(size_t)cur_tgt].rebuilt);
         st.reset();
         return true;
@@ -349,6 +383,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         std::vector<uint8_t> b_rev;                            // stranded sources: one flag per record
         std::vector<uint32_t> b_cslen, b_tspan;                // cs sources: qblob holds the texts
         std::vector<uint8_t *> b_fate;                         // where each record's fate is kept (a record goes out with every group it meets)
+        std::vector<uint32_t> b_idx;                           // --phase-windows: each record's index among its target's
         std::vector<uint64_t> b_mdoff;                         // md sources: the texts, back to back in mdblob
         std::vector<uint32_t> b_mdlen;
         std::string mdblob;
@@ -369,6 +404,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             for (; it != t.recs.end() && it->s < hi; ++it) {
                 if (it->e <= lo) continue;
                 b_fate.push_back(&t.fate[(size_t)(it - t.recs.begin())]);
+                if (o.wp.on) b_idx.push_back((uint32_t)(it - t.recs.begin()));
                 b_pos.push_back(it->pos); b_qoff.push_back(qblob.size()); b_qlen.push_back(it->q_len);
                 qblob.append(it->q, it->q_bytes);
                 if ((Source::kind == DG_REC_CS)) { b_cslen.push_back((uint32_t)it->q_bytes); b_tspan.push_back(it->t_span); }
@@ -406,7 +442,15 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         if (rc == DAGCON_OK && o.pileup) rc = dagcon_fetch_pileup(ctx, &pu);
         dagcon_pileup_sites ps;
         memset(&ps, 0, sizeof ps);
-        if (rc == DAGCON_OK && o.sites) rc = dagcon_fetch_pileup_sites(ctx, &ps);
+        if (rc == DAGCON_OK && (o.sites || o.wp.on)) rc = dagcon_fetch_pileup_sites(ctx, &ps);
+        dagcon_site_reads sr;
+        memset(&sr, 0, sizeof sr);
+        dagcon_window_phase wp;
+        memset(&wp, 0, sizeof wp);
+        if (rc == DAGCON_OK && o.wp.on) rc = dagcon_fetch_site_reads(ctx, &sr);
+        if (rc == DAGCON_OK && o.wp.on) rc = dagcon_fetch_window_phase(ctx, &wp);
+        uint64_t sr_x = 0;                                     // the taken alignments ascend in their window: one walk
+        DgWpLink first_link{0, 0};                             // the link of the group's first window, in the run's terms
         if (rc == DAGCON_OK && want_rebuilt && MD) {           // REF of the edits and of the pile-up lines: the group's stretch of every target, as the device rebuilt it
             const char *tb = nullptr;
             uint64_t tn = 0;
@@ -426,8 +470,45 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
             if ((long long)w.tgt != cur_tgt) {
                 if (!flush_target()) { status = 1; break; }
                 cur_tgt = w.tgt;
+                if (o.wp.on) acc.assign(tgts[w.tgt].recs.size(), RecAcc());
             }
             const size_t g = k - w0;
+            if (o.wp.on) {
+                const Tgt &t = tgts[w.tgt];
+                const uint64_t x0 = sr_x;
+                while (sr_x < sr.n_aln && sr.aln_tgt[sr_x] == g) sr_x++;
+                // the window's link in the run's terms: the first of a group by the host's pair rule against the last window of
+                // the group before, the others from the device's arrays (its block 0 is the first window's)
+                DgWpLink link;
+                if (g == 0) {
+                    std::vector<DgWpPiece> cur;
+                    for (uint64_t x = x0; x < sr_x; x++) cur.push_back(DgWpPiece{b_idx[sr.aln_src[x]], sr.hap[x]});
+                    uint32_t same = 0, diff = 0;
+                    const bool has_prev = prev_tgt == (long long)w.tgt;
+                    if (has_prev) dg_wp_pair(prev_pieces, cur, same, diff);
+                    link = first_link = dg_wp_step(has_prev, prev_link, k, same, diff, o.wp.min_links, o.wp.max_conflict_ppm);
+                } else if (wp.block[g] == 0) link = DgWpLink{(uint8_t)(wp.flip[g] ^ first_link.flip), first_link.block};
+                else link = DgWpLink{wp.flip[g], (uint64_t)w0 + wp.block[g]};
+                n_blocks += link.block == k;
+                const bool turn = wp.block[g] == 0 && first_link.flip != 0;     // (the device oriented block 0 as if its first window were unlinked)
+                const uint32_t lo = w.c0 - w.begin, hi = w.c1 - w.begin;
+                for (uint64_t x = x0; x < sr_x; x++) {
+                    RecAcc &a = acc[b_idx[sr.aln_src[x]]];
+                    const uint8_t h = wp.hap[x];
+                    a.taken = true;
+                    a.pieces.push_back(DgWpVote{link.block, (uint8_t)(h && turn ? 3u - h : h)});
+                    for (uint64_t e = sr.ent_begin[x]; e < sr.ent_begin[x + 1]; e++) {
+                        const uint32_t p = ps.pos[sr.ent_site[e]];
+                        a.sites += p >= lo && p < hi && dg_sr_sign(sr.ent_code[e], ps.counts + 8 * sr.ent_site[e]) != 0;
+                    }
+                }
+                if (o.site_reads) dg_wp_site_read_lines(reads_out, t.name, ps, sr, (uint32_t)g, x0, sr_x, lo, hi, w.begin, [&](uint64_t x) -> const std::string & { return t.qnames[b_idx[sr.aln_src[x]]]; });
+                if (k + 1 == w1) {
+                    prev_tgt = w.tgt; prev_link = link;
+                    prev_pieces.clear();
+                    for (uint64_t x = x0; x < sr_x; x++) prev_pieces.push_back(DgWpPiece{b_idx[sr.aln_src[x]], sr.hap[x]});
+                }
+            }
             if (pile) {
                 const Tgt &t = tgts[w.tgt];
                 const char *tb = MD ? t.rebuilt.data() : ref.bases.data() + t.sp.off;
@@ -452,10 +533,14 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         }
         if (o.pileup && fwrite(pile_out.data(), 1, pile_out.size(), o.pileup) != pile_out.size()) { fprintf(stderr, "pbdagcon: error writing the --pileup file\n"); status = 1; }
         if (o.sites && fwrite(site_out.data(), 1, site_out.size(), o.sites) != site_out.size()) { fprintf(stderr, "pbdagcon: error writing the --sites file\n"); status = 1; }
-        pile_out.clear(); site_out.clear();
+        if (o.site_reads && fwrite(reads_out.data(), 1, reads_out.size(), o.site_reads) != reads_out.size()) { fprintf(stderr, "pbdagcon: error writing the --site-reads file\n"); status = 1; }
+        if (o.haplotag && fwrite(tags_out.data(), 1, tags_out.size(), o.haplotag) != tags_out.size()) { fprintf(stderr, "pbdagcon: error writing the --haplotag file\n"); status = 1; }
+        pile_out.clear(); site_out.clear(); reads_out.clear(); tags_out.clear();
         w0 = w1;
     }
     if (status == 0 && !flush_target()) status = 1;
+    if (o.haplotag && !tags_out.empty() && fwrite(tags_out.data(), 1, tags_out.size(), o.haplotag) != tags_out.size()) { fprintf(stderr, "pbdagcon: error writing the --haplotag file\n"); status = 1; }
+    if (o.wp.on && o.verbose) fprintf(stderr, "pbdagcon: --phase-windows: %llu blocks over %zu windows\n", n_blocks, wins.size());
     unsigned long long over_error = 0, over_depth = 0;
     for (const Tgt &t : tgts)
         for (const uint8_t f : t.fate) { over_error += (f & DAGCON_FATE_MAX_ERROR) != 0; over_depth += (f & DAGCON_FATE_MAX_DEPTH) != 0; }

@@ -1,4 +1,5 @@
-// api_ctx.h -- the context: owning buffers, the named buffer sets, the status block, Ctx, errors, ensure() and upload()
+// api_ctx.h -- the context: owning buffers, the named buffer sets, the status block, the optional outputs' records and result
+// arrays, Ctx, errors, ensure(), upload() and d2h()
 // (one translation unit with dagcon_api.hip, which includes it once).
 namespace {
 
@@ -142,6 +143,76 @@ struct GrowArena {
 struct GrowRef { GrowArena *g; bool on; };          // an arena, and whether the batch on the device was uploaded with its output on
 
 enum class Fresh { FETCH, RUN, UPLOAD };            // what is new when results stop being valid (Ctx::drop_results)
+enum class Intake { STRINGS, RECORDS, WINDOWS, HAPS };    // how a batch comes to upload_impl: as strings, from the record intake (whole targets, windows), from dagcon_upload_haps
+
+// One optional output of a run (api_outputs.hip.h): the text its fetches fail with; the switch (dagcon_set_*); whether the
+// batch on the device was uploaded under it and under everything it rests on (latch_outputs); whether the last fetch
+// brought its results; whether the copies that fetch left out have been made (the output's own fetch makes them when asked)
+struct Output {
+    const char *missing;
+    bool on = false, batch = false, valid = false, fetched = false;
+};
+
+// What the outputs' fetches return, by output: host arrays the context owns, valid as long as the results of the same fetch.
+// dagcon_fetch_edits: per segment its target range and where its edits begin, per edit its place and length in the target
+// and in seq_blob; dagcon_fetch_edit_support: per edit its window and the alignments that span it, carry the consensus'
+// allele, the target's
+struct EditsOut {
+    std::vector<uint32_t> t0, t1, tpos, tlen, clen, w_begin, w_end, span, alt, ref;
+    std::vector<uint64_t> begin, coff;
+};
+// dagcon_fetch_pileup_sites: where a target's sites begin, each site's position and counts; and the site map of the other
+// fetches -- where a target's sites begin in the device's list (begin: in the host's), and that list's length
+struct SitesOut {
+    std::vector<uint64_t> begin, dev_begin;         // [T + 1]
+    std::vector<uint32_t> pos;
+    std::vector<uint16_t> counts;
+    uint64_t n_dev = 0;
+};
+// dagcon_fetch_site_reads: per kept alignment its target, the caller's index, where its entries begin and its label; per
+// entry its site and code; per site its phase.  n_dev_ent: the entries of the device, kept or not
+struct SiteReadsOut {
+    uint64_t n_dev_ent = 0;
+    std::vector<uint32_t> tgt;
+    std::vector<uint64_t> src, begin, site;
+    std::vector<uint8_t> code, hap;
+    std::vector<int8_t> phase;
+};
+// dagcon_fetch_site_alleles: where a site's alleles begin; per allele its key, count and counts per label; per entry its allele
+struct AllelesOut {
+    std::vector<uint64_t> begin, key;
+    std::vector<uint32_t> count;
+    std::vector<uint16_t> hap, ent;
+};
+// dagcon_fetch_hap_tally: two lazy parts -- the per-target records (Output::fetched; dagcon_upload_haps reads them too),
+// zeros for a failed target, and the site counters in the host's order of the sites (sites_fetched)
+struct HapOut {
+    bool sites_fetched = false;
+    std::vector<uint32_t> rec;          // [6][T]: n1, n2, n0, n_sep, agree, disagree
+    std::vector<uint8_t> split;         // [T]
+    std::vector<uint16_t> counts;       // [4 * sites] P1 M1 P2 M2
+};
+// dagcon_fetch_window_phase: per window, per kept alignment, per site, in the host's order
+struct WinPhaseOut {
+    std::vector<uint32_t> same, diff, block;
+    std::vector<uint8_t> flip, hap;
+    std::vector<int8_t> phase;
+};
+// dagcon_fetch_hap_map: the batch on the device is dagcon_upload_haps' (valid), and what it holds
+struct HapMapOut {
+    bool valid = false;
+    std::vector<uint32_t> src_target;
+    std::vector<uint8_t> label;
+    std::vector<uint64_t> aln_begin, aln_src;
+};
+// The kept alignments of a fetched run in the device's order (host_order builds it at the first fetch that needs it): each
+// one's index on the device and its stretch of the device's entry arrays.  Its target and the caller's index are
+// h_aln_tgt / h_aln_src at that index
+struct HostOrder {
+    bool built = false;
+    std::vector<uint32_t> aln, ent_n;
+    std::vector<uint64_t> ent_begin;
+};
 
 struct Ctx {
     dagcon_opts opts;
@@ -199,39 +270,41 @@ struct Ctx {
     std::vector<uint32_t> rs_match, rs_mismatch, rs_ins, rs_del;
     std::vector<uint8_t> rs_fate;
     StatBlock sb;                                   // DgStatus, tfail, cns_len, n_seg, cns_off, seg_first
-    // dagcon_set_edits: the switch; whether the batch on the device is a record upload made under it (its buffers:
-    // run.ed_seg, run.ed_out, in.ed_tbase)
-    bool edits_on = false, ed_batch = false;
-    // dagcon_set_edit_support: the switch (on only while edits_on is); whether the batch on the device was armed under it
-    bool evid_on = false, evid_batch = false;
+    // The optional outputs (api_outputs.hip.h), one record each, and beside it its options as set and as latched for the
+    // batch on the device (latch_outputs holds the rule, and fills the defaults in).  outputs() lists them: whatever
+    // happens to all of them walks that list.
+    // dagcon_set_edits (its buffers: run.ed_seg, run.ed_out, in.ed_tbase) and dagcon_set_edit_support (on only while edits are)
+    Output o_ed{"without the results of a record upload made with dagcon_set_edits on (edits off, another kind of upload, no fetch yet, or stopped before bestPath)"};
+    Output o_evid{"without the results of a record upload made with dagcon_set_edit_support on (switch off at the upload, edits off, another kind of upload, "
+                  "no fetch yet, or stopped before bestPath)"};
     std::vector<uint64_t> h_ed_tbase;
-    // dagcon_set_pileup: the switch and its thresholds; whether the batch on the device was uploaded under it (its buffers:
-    // in.pile_begin, run.pile, run.pile_tile, run.pile_site), and the thresholds of that upload
-    bool pile_on = false, pile_batch = false;
+    // dagcon_set_pileup and its thresholds (its buffers: in.pile_begin, run.pile, run.pile_tile, run.pile_site)
+    Output o_pile{"without the results of an upload made with dagcon_set_pileup on (switch off at the upload, no fetch yet, or stopped before bestPath)"};
     dagcon_pileup_opts pile_opts = {0u, 0u}, pile_batch_opts = {0u, 0u};
     std::vector<uint64_t> h_pile_begin;             // [T + 1]
-    // dagcon_set_site_reads: the switch; whether the batch on the device was uploaded under it (and under the pile-up) and
-    // with which options; per alignment of the device the index the caller knows it by; the entry arena's size
-    bool sr_on = false, sr_batch = false;
+    // dagcon_set_site_reads; per alignment of the device the index the caller knows it by
+    Output o_sr{"without the results of an upload made with dagcon_set_pileup and dagcon_set_site_reads on (a switch off at the upload, no fetch yet, or "
+                "stopped before bestPath)"};
     dagcon_site_reads_opts sr_opts = {0u, 0u}, sr_batch_opts = {0u, 0u};
     std::vector<uint64_t> h_aln_src;                // [A]
-    // dagcon_set_hap_consensus: the switch; whether the batch on the device was uploaded under it (and under the pile-up
-    // and the site reads with phase on) and with which options (the defaults filled in)
-    bool hap_on = false, hap_batch = false;
+    // dagcon_set_site_alleles
+    Output o_al{"without the results of an upload made with dagcon_set_pileup, dagcon_set_site_reads and dagcon_set_site_alleles on (a switch off at the "
+                "upload, no fetch yet, or stopped before bestPath)"};
+    // dagcon_set_hap_consensus
+    Output o_hap{"without the results of an upload made with dagcon_set_pileup, dagcon_set_site_reads (phase on) and dagcon_set_hap_consensus on (a switch "
+                 "off at the upload, no fetch yet, stopped before bestPath, or the batch is dagcon_upload_haps' own)"};
     dagcon_hap_opts hap_opts = {0u, 0u}, hap_batch_opts = {0u, 0u};
-    // dagcon_set_site_alleles: the switch; whether the batch on the device was uploaded under it (and under the pile-up and
-    // the site reads)
-    bool al_on = false, al_batch = false;
-    // dagcon_set_window_phase: the switch; whether the batch on the device is a windows upload made under it (and under the
-    // pile-up and the site reads with phase on) and with which options (the defaults filled in)
-    bool wl_on = false, wl_batch = false;
+    // dagcon_set_window_phase
+    Output o_wl{"without the results of a windows upload made with dagcon_set_pileup, dagcon_set_site_reads (phase on) and dagcon_set_window_phase on (a "
+                "switch off at the upload, no windows, no fetch yet, or stopped before bestPath)"};
     dagcon_window_phase_opts wl_opts = {0u, 0u}, wl_batch_opts = {0u, 0u};
+    std::array<Output *, 7> outputs() { return {&o_ed, &o_evid, &o_pile, &o_sr, &o_al, &o_hap, &o_wl}; }
     // the growing arenas: run.ed_out (and run.evid beside it), run.pile_site, run.sr_site / sr_code.  The status block
     // holds 16 bytes for the edits' total, then 16 for the sites', whose second word is the entries'
     GrowArena ed_arena{"edits", DG_E_ED_OVF, true, &DgParams::ed_top, &DgParams::ed_cap};
     GrowArena site_arena{"sites", DG_E_SITE_OVF, true, &DgParams::site_top, &DgParams::site_cap};
     GrowArena sr_arena{"site entries", DG_E_SR_OVF, false, &DgParams::sr_top, &DgParams::sr_cap};
-    std::array<GrowRef, 3> growing() { return {{{&ed_arena, ed_batch}, {&site_arena, pile_batch}, {&sr_arena, sr_batch}}}; }
+    std::array<GrowRef, 3> growing() { return {{{&ed_arena, o_ed.batch}, {&site_arena, o_pile.batch}, {&sr_arena, o_sr.batch}}}; }
     long ed_cap_env = 0;                            // DAGCON_EDITS_CAP (tests): first size of the edit arena, so that the re-run is met
 
     uint64_t norm_cap = 0, node_cap = 0, pool_cap = 0, cns_cap = 0, seg_cap = 0;
@@ -258,58 +331,29 @@ struct Ctx {
     bool pos_pending = false;           // edits on: the positions stay on the device until dagcon_fetch_positions asks for them
     uint64_t r_nb = 0;                  // seq_bytes of the last fetch
     PinBuf r_ed;                        // the DgEdSeg records of the last fetch, then its DgEdit records
-    bool ed_valid = false;              // the arrays below are those of the last fetch (dagcon_fetch_edits)
-    std::vector<uint32_t> e_t0, e_t1, e_tpos, e_tlen, e_clen;
-    std::vector<uint64_t> e_begin, e_coff;
-    bool evid_valid = false;              // the arrays below are those of the last fetch (dagcon_fetch_edit_support)
-    std::vector<uint32_t> v_begin, v_end, v_span, v_alt, v_ref;
-    bool pile_valid = false;            // the site arrays below are those of the last fetch (dagcon_fetch_pileup_sites)
-    bool pile_fetched = false;          // r_pile holds the counts of the same run (dagcon_fetch_pileup copies them when asked)
     PinBuf r_site;                      // the DgSite records of the last fetch
-    PinBuf r_pile;                      // uint16_t, eight per position
-    bool sr_valid = false;              // the last fetch was of a batch with dagcon_set_site_reads on: sr_n_ent, sr_n_site, s_dev_begin are its
-    bool sr_fetched = false;            // the arrays below are that run's (dagcon_fetch_site_reads copies them when asked)
-    uint64_t sr_n_ent = 0, sr_n_site = 0;
-    std::vector<uint64_t> s_dev_begin;  // [T + 1] where a target's sites begin in the device's list (s_begin: in the host's)
-    std::vector<uint32_t> x_tgt;
-    std::vector<uint64_t> x_src, x_begin, x_site;
-    std::vector<uint8_t> x_code, x_hap;
-    std::vector<int8_t> x_phase;
-    std::vector<uint64_t> s_begin;
-    std::vector<uint32_t> s_pos;
-    std::vector<uint16_t> s_counts;
-    bool hap_valid = false;             // the last fetch was of a batch with dagcon_set_hap_consensus on (dagcon_fetch_hap_tally, dagcon_upload_haps)
-    bool hap_fetched = false;           // y_rec holds that run's records, zeros for a failed target
-    bool hap_sites_fetched = false;     // y_counts holds that run's site counters, in the host's order of the sites
-    std::vector<uint32_t> y_rec;        // [6][T]: n1, n2, n0, n_sep, agree, disagree
-    std::vector<uint8_t> y_split;       // [T]
-    std::vector<uint16_t> y_counts;     // [4 * sites] P1 M1 P2 M2
-    bool al_fetched = false;            // the arrays below are the last fetch's run's (dagcon_fetch_site_alleles copies them when asked)
-    std::vector<uint64_t> z_begin, z_key;
-    std::vector<uint32_t> z_count;
-    std::vector<uint16_t> z_hap, z_ent;
-    bool wl_valid = false;              // the last fetch was of a batch with dagcon_set_window_phase on (dagcon_fetch_window_phase)
-    bool wl_fetched = false;            // the arrays below are that run's, in the host's order of the alignments and the sites
-    std::vector<uint32_t> x_dev;        // [n_aln] the device's index of alignment x (filled by dagcon_fetch_site_reads for such a batch)
-    std::vector<uint32_t> w_same, w_diff, w_block;
-    std::vector<uint8_t> w_flip, w_hap;
-    std::vector<int8_t> w_phase;
-    bool hapmap_valid = false;          // the batch on the device is dagcon_upload_haps': the arrays below describe it (dagcon_fetch_hap_map)
-    std::vector<uint32_t> m_src_target;
-    std::vector<uint8_t> m_label;
-    std::vector<uint64_t> m_aln_begin, m_aln_src;
+    PinBuf r_pile;                      // uint16_t, eight per position (o_pile.fetched: of the same run; dagcon_fetch_pileup copies them when asked)
+    EditsOut r_edits;
+    SitesOut r_sites;
+    SiteReadsOut r_reads;
+    AllelesOut r_alleles;
+    HapOut r_haps;
+    WinPhaseOut r_winphase;
+    HapMapOut r_hapmap;
+    HostOrder order;
     bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
 
     // The one place where results stop being valid.  A fetch drops what the fetch before it left; a run drops that and
     // `fetched`; an upload drops that and `uploaded`, `ran` and the rebuilt targets.  One exception to upload > run > fetch:
     // a run alone leaves sup_valid and pos_valid -- r_sup and r_pos are host copies that still hold what the last fetch
-    // brought, and stay readable until the next fetch replaces them.  (The *_batch latches are the upload's own business.)
+    // brought, and stay readable until the next fetch replaces them.  (The outputs' `batch` latches are the upload's own
+    // business: latch_outputs.)
     void drop_results(const Fresh lv) {
-        ed_valid = pos_pending = evid_valid = pile_valid = pile_fetched = sr_valid = sr_fetched = false;
-        hap_valid = hap_fetched = hap_sites_fetched = al_fetched = wl_valid = wl_fetched = false;
+        for (Output *o : outputs()) o->valid = o->fetched = false;
+        pos_pending = r_haps.sites_fetched = order.built = false;
         if (lv != Fresh::RUN) sup_valid = pos_valid = false;
         if (lv != Fresh::FETCH) fetched = false;
-        if (lv == Fresh::UPLOAD) uploaded = ran = md_valid = md_fetched = hapmap_valid = false;
+        if (lv == Fresh::UPLOAD) uploaded = ran = md_valid = md_fetched = r_hapmap.valid = false;
     }
 
     // debug dump storage
@@ -379,6 +423,13 @@ int upload(Ctx *c, DevBuf &b, const X *host, size_t n) {
 }
 template <typename X>
 int upload(Ctx *c, DevBuf &b, const std::vector<X> &v) { return upload(c, b, v.data(), v.size()); }
+
+// device -> host on the context's own stream.  (hipMemcpy would go through the null stream, and the stream is
+// non-blocking so that a second context on the same GPU is not serialised against this one's copies.)
+hipError_t d2h(Ctx *c, void *dst, const void *src, size_t bytes) {
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(c->stream);
+}
 
 #define UPLOAD(c, buf, ...)                                  \
     do {                                                     \

@@ -45,7 +45,7 @@ class RecordSource {
 Ctx *intake_reset(dagcon_ctx *ctx) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->drop_results(Fresh::UPLOAD);
-    c->ed_batch = c->evid_batch = c->pile_batch = c->sr_batch = false;     // (upload_impl and edits_arm latch them)
+    for (Output *o : c->outputs()) o->batch = false;               // (upload_impl latches them: latch_outputs)
     return c;
 }
 
@@ -458,7 +458,7 @@ int cigar_hand_over(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const 
     db.n_targets = (uint32_t)pl.bad.size(); db.tlen = pl.pieces ? pl.tlen.data() : b->tlen; db.aln_begin = pl.beg.data();
     db.aln_start = pl.start.data(); db.aln_off = pl.off.data(); db.aln_len = pl.len.data();
     db.blob_bytes = pl.bytes;
-    const int r = upload_impl(ctx, &db, c->in.q.p, c->in.t.p);       // (synchronises the stream: the caller's locals may go)
+    const int r = upload_impl(ctx, &db, c->in.q.p, c->in.t.p, pl.pieces ? Intake::WINDOWS : Intake::RECORDS);   // (synchronises the stream: the caller's locals may go)
     if (r != DAGCON_OK) { (void)hipStreamSynchronize(c->stream); return r; }
     c->h_cig_bad = pl.bad;
     for (uint64_t &x : c->h_aln_src) x = pl.rec[x];                // (dagcon_set_site_reads: upload_impl left the index into pl's arrays)
@@ -476,35 +476,26 @@ int cigar_hand_over(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const 
     return DAGCON_OK;
 }
 
-// dagcon_set_edits: the batch the hand-over left is one whose edits the run is to report.  Each of the pipeline's targets
-// gets the place of its first base in cg.t (a window's: its target's, plus its begin), the status block a word for the
-// edit count, the arena a first size (grown by the re-run when DG_E_ED_OVF says so)
+// dagcon_set_edits: the batch the hand-over left is one whose edits the run is to report (latched, with its room, by
+// upload_impl).  What only the intake knows: the place of each pipeline target's first base in cg.t (a window's: its
+// target's, plus its begin)
 int edits_arm(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
     const uint32_t T = c->T;
     c->h_ed_tbase.assign(T, 0);
     for (uint32_t t = 0; t < T; t++) c->h_ed_tbase[t] = wn ? b->t_off[wn->target[t]] + wn->begin[t] : b->t_off[t];
-    c->ed_batch = true;
-    c->evid_batch = c->evid_on;
-    c->ed_arena.cap = c->ed_cap_env > 0 ? (uint64_t)c->ed_cap_env : std::max<uint64_t>(c->ed_arena.cap, c->sum_bb / 8 + 1024);
-    int r;
     UPLOAD(c, c->in.ed_tbase, c->h_ed_tbase);
-    if ((r = ensure_stat(c, T))) return r;
-    if ((r = ensure_arenas(c))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DAGCON_OK;
 }
 
-// dagcon_set_window_phase: the batch the hand-over left is a windows upload whose labels the run is to join.  Each
-// alignment's record (4 bytes; h_aln_src holds it) and each window's target go up, the run's arrays get their room
+// dagcon_set_window_phase: the batch the hand-over left is a windows upload whose labels the run is to join (latched, with
+// its room, by upload_impl).  What only the intake knows: each alignment's record (4 bytes; h_aln_src holds it) and each
+// window's target
 int window_phase_arm(Ctx *c, const dagcon_windows *wn) {
     std::vector<uint32_t> rec(c->h_aln_src.size());
     for (size_t a = 0; a < rec.size(); a++) rec[a] = (uint32_t)c->h_aln_src[a];
-    c->wl_batch = true;
-    c->wl_batch_opts = {c->wl_opts.min_links ? c->wl_opts.min_links : 3u, c->wl_opts.max_conflict_ppm ? c->wl_opts.max_conflict_ppm : 250000u};
-    int r;
     UPLOAD(c, c->in.wl_rec, rec);
     UPLOAD(c, c->in.wl_tgt, wn->target, (size_t)c->T);
-    if ((r = ensure_arenas(c))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));                   // (rec is a local)
     return DAGCON_OK;
 }
@@ -522,8 +513,8 @@ int records_finish(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const d
     if ((r = wn ? plan_windows(c, b, wn, sc, v, pk, pl) : plan_whole(c, b, sc, v, pk, pl))) return r;
     if ((r = cigar_expand(c, b, src, sc, pl))) return r;
     if ((r = cigar_hand_over(ctx, c, b, pl, v, pk))) return r;
-    if (wn && c->wl_on && c->sr_batch && c->sr_batch_opts.phase && (r = window_phase_arm(c, wn))) return r;
-    return c->edits_on ? edits_arm(c, b, wn) : DAGCON_OK;
+    if (c->o_wl.batch && (r = window_phase_arm(c, wn))) return r;
+    return c->o_ed.batch ? edits_arm(c, b, wn) : DAGCON_OK;
 }
 
 // SAM-style input: position + ungapped read + CIGAR per record, target bases once per target.  k_cigar_scan sizes every

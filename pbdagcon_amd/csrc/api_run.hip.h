@@ -1,6 +1,24 @@
-// api_run.hip.h -- a batch through the pipeline: plan, arenas, parameters, launches; upload, run, fetch, getters, normalize
+// api_run.hip.h -- a batch through the pipeline: plan, arenas, parameters, launches; upload, run, fetch of the consensus with
+// its support and positions, timings, normalize.  The optional outputs' side of every step is in api_outputs.hip.h
 // (one translation unit with dagcon_api.hip, which includes it once).
 namespace {
+
+// what this fetch brings back and how much of it: decided once from the status block, read by the steps behind it
+struct FetchPlan {
+    bool full, want_sup, want_pos, lazy_pos, want_ed, want_evid, want_pile;       // (the outputs' own: outputs_plan)
+    uint64_t nseg, nb, n_ed, n_site;
+    size_t ed_seg_bytes, ed_bytes, evid_bytes;      // r_ed: the DgEdSeg records, then the DgEdit records, then the DgEvid records (all 8-byte aligned)
+};
+
+// the optional outputs' side of every step (api_outputs.hip.h)
+void latch_outputs(Ctx *c, Intake kind);
+int outputs_room(Ctx *c);
+void outputs_params(Ctx *c, DgParams &p);
+int outputs_launch(Ctx *c, const DgParams &p);
+int outputs_upload(Ctx *c, const dagcon_batch *b);
+int outputs_plan(Ctx *c, FetchPlan &f);
+int outputs_copies(Ctx *c, const FetchPlan &f, bool &queued);
+int outputs_unpack(Ctx *c, const FetchPlan &f);
 
 // ---- how many pieces the merge / bestPath sweeps of a batch are cut into (host arithmetic only: exported as
 // dagcon_debug_plan so that a CPU test can sweep it; every grid size derived from it is > 0) ----
@@ -121,42 +139,7 @@ int ensure_arenas(Ctx *c) {
         if (c->gcuts) ENSURE(c, c->run.pos_tmp0, c->node_cap * 4);
         ENSURE(c, c->run.pos, c->cns_cap * 4);
     }
-    if (c->ed_batch) {
-        ENSURE(c, c->run.ed_seg, c->seg_cap * sizeof(DgEdSeg));
-        ENSURE(c, c->run.ed_out, c->ed_arena.cap * sizeof(DgEdit));
-        if (c->evid_batch) ENSURE(c, c->run.evid, c->ed_arena.cap * sizeof(DgEvid));
-    }
-    if (c->pile_batch) {
-        const uint64_t pn = c->h_pile_begin.back();
-        ENSURE(c, c->run.pile, pn * 16);
-        ENSURE(c, c->run.pile_tile, (pn + DG_PILE_TILE - 1) / DG_PILE_TILE * 8);
-        ENSURE(c, c->run.pile_site, c->site_arena.cap * sizeof(DgSite));
-    }
-    if (c->sr_batch) {
-        const uint64_t words = (c->h_pile_begin.back() + 63) / 64;
-        const size_t A4 = (size_t)c->A * 4;
-        ENSURE(c, c->run.sr_bits, words * 8); ENSURE(c, c->run.sr_rank, words * 4);
-        ENSURE(c, c->run.sr_cnt, A4); ENSURE(c, c->run.sr_off, 2 * A4);
-        ENSURE(c, c->run.sr_site, c->sr_arena.cap * 4); ENSURE(c, c->run.sr_code, c->sr_arena.cap);
-        if (c->sr_batch_opts.phase) {
-            ENSURE(c, c->run.sr_hap, (size_t)c->A); ENSURE(c, c->run.sr_nz, A4);
-            ENSURE(c, c->run.sr_sigma, c->site_arena.cap); ENSURE(c, c->run.sr_kind, c->site_arena.cap); ENSURE(c, c->run.sr_acc, c->site_arena.cap * 4);
-        }
-        if (c->hap_batch) { ENSURE(c, c->run.hap_cnt, c->site_arena.cap * 8); ENSURE(c, c->run.hap_rec, (size_t)c->T * DG_HAP_REC * 4); }
-        if (c->wl_batch) {
-            ENSURE(c, c->run.wl_cnt, (size_t)c->T * 8); ENSURE(c, c->run.wl_block, (size_t)c->T * 4); ENSURE(c, c->run.wl_flip, (size_t)c->T);
-            ENSURE(c, c->run.wl_hap, (size_t)c->A); ENSURE(c, c->run.wl_phase, c->site_arena.cap);
-        }
-        if (c->al_batch) {
-            const size_t ne = c->sr_arena.cap, ns = c->site_arena.cap;
-            // (20 bytes an entry and 28 a site; the compact tables wait for dagcon_fetch_site_alleles, which knows their size)
-            ENSURE(c, c->run.al_map, ne * 2); ENSURE(c, c->run.al_idx, ne * 2);
-            ENSURE(c, c->run.al_soff, ns * 8); ENSURE(c, c->run.al_cur, (ns + 1) * 4); ENSURE(c, c->run.al_nd, ns * 4);
-            ENSURE(c, c->run.al_deep, ns * 4); ENSURE(c, c->run.al_toff, ns * 8);
-            ENSURE(c, c->run.al_srt, ne * 8); ENSURE(c, c->run.al_tcnt, ne * 4); ENSURE(c, c->run.al_thap, ne * 4);
-            ENSURE(c, c->run.al_tot, 16);
-        }
-    }
+    if (int r = outputs_room(c)) return r;
     ENSURE(c, c->run.seg, 2 * seg_stride(c) * 4);
     if (int r = c->r_seg.reserve(c, 2 * (size_t)c->seg_cap * 4)) return r;
     ENSURE(c, c->arena.matC, matc_bytes(c) + 256);          // (grows for the re-run with 32-bit cells)
@@ -239,47 +222,7 @@ void fill_params(Ctx *c, DgParams &p) {
     }
     for (const GrowRef &r : c->growing())                   // ed_top / ed_cap, site_top / site_cap, sr_top / sr_cap
         if (r.on) { p.*(r.g->p_top) = c->sb.d<unsigned long long>(r.g->o_top); p.*(r.g->p_cap) = r.g->cap; }
-    if (c->ed_batch) {
-        p.ed_seg = c->run.ed_seg.as<DgEdSeg>(); p.ed_out = c->run.ed_out.as<DgEdit>();
-        p.ed_t = c->cg.t.as<const uint8_t>(); p.ed_tbase = c->in.ed_tbase.as<const uint64_t>();
-        if (c->evid_batch) p.evid = c->run.evid.as<DgEvid>();
-    }
-    if (c->pile_batch) {
-        p.pile = c->run.pile.as<uint32_t>(); p.pile_begin = c->in.pile_begin.as<const uint64_t>(); p.pile_n = c->h_pile_begin.back();
-        p.pile_tile = c->run.pile_tile.as<unsigned long long>();
-        p.pile_site = c->run.pile_site.as<DgSite>();
-        p.pile_min_count = c->pile_batch_opts.min_count; p.pile_min_ppm = c->pile_batch_opts.min_frac_ppm;
-    }
-    if (c->sr_batch) {
-        p.sr_bits = c->run.sr_bits.as<unsigned long long>(); p.sr_rank = c->run.sr_rank.as<uint32_t>();
-        p.sr_cnt = c->run.sr_cnt.as<uint32_t>(); p.sr_off = c->run.sr_off.as<unsigned long long>();
-        p.sr_site = c->run.sr_site.as<uint32_t>(); p.sr_code = c->run.sr_code.as<uint8_t>();
-        p.sr_phase = c->sr_batch_opts.phase; p.sr_rounds = c->sr_batch_opts.rounds ? c->sr_batch_opts.rounds : 8u;
-        if (p.sr_phase) {
-            p.sr_hap = c->run.sr_hap.as<uint8_t>(); p.sr_nz = c->run.sr_nz.as<uint32_t>();
-            p.sr_sigma = c->run.sr_sigma.as<int8_t>(); p.sr_kind = c->run.sr_kind.as<uint8_t>(); p.sr_acc = c->run.sr_acc.as<int>();
-        }
-        if (c->hap_batch) {
-            p.hap_cnt = c->run.hap_cnt.as<uint32_t>(); p.hap_rec = c->run.hap_rec.as<uint32_t>();
-            p.hap_min_sites = c->hap_batch_opts.min_sites; p.hap_min_reads = c->hap_batch_opts.min_reads;
-            p.hap_min_cov = std::max<uint32_t>(1u, c->opts.min_cov);
-        }
-        if (c->wl_batch) {
-            p.wl_rec = c->in.wl_rec.as<const uint32_t>(); p.wl_tgt = c->in.wl_tgt.as<const uint32_t>();
-            p.wl_cnt = c->run.wl_cnt.as<uint32_t>(); p.wl_block = c->run.wl_block.as<uint32_t>(); p.wl_flip = c->run.wl_flip.as<uint8_t>();
-            p.wl_hap = c->run.wl_hap.as<uint8_t>(); p.wl_phase = c->run.wl_phase.as<int8_t>();
-            p.wl_min_links = c->wl_batch_opts.min_links; p.wl_max_ppm = c->wl_batch_opts.max_conflict_ppm;
-        }
-        if (c->al_batch) {
-            p.al_map = c->run.al_map.as<uint16_t>(); p.al_idx = c->run.al_idx.as<uint16_t>();
-            p.al_soff = c->run.al_soff.as<unsigned long long>(); p.al_cur = c->run.al_cur.as<uint32_t>(); p.al_nd = c->run.al_nd.as<uint32_t>();
-            p.al_deep = c->run.al_deep.as<uint32_t>(); p.al_toff = c->run.al_toff.as<unsigned long long>();
-            p.al_srt = c->run.al_srt.as<unsigned long long>(); p.al_tcnt = c->run.al_tcnt.as<uint32_t>(); p.al_thap = c->run.al_thap.as<uint32_t>();
-            p.al_ckey = c->run.al_ckey.as<unsigned long long>(); p.al_ccnt = c->run.al_ccnt.as<uint32_t>(); p.al_chap = c->run.al_chap.as<uint32_t>();
-            p.al_ent_top = c->run.al_tot.as<unsigned long long>(); p.al_top = p.al_ent_top + 1;
-            p.al_nocap = ~0ull;
-        }
-    }
+    outputs_params(c, p);
 }
 
 // stage a1: count, chunked normalizeGaps + trimAln, and the sequential kernel for what is left
@@ -409,65 +352,7 @@ int launch_all(Ctx *c) {
         }
         DG_BP_LAUNCH(k_bp_join, dim3(c->T));
 #undef DG_BP_LAUNCH
-        if (c->ed_batch) {
-            // the edits (k_edits.hip.h): count, place, write; a wave per segment of the arena (seg_top is the device's)
-            const dim3 eg((uint32_t)((c->seg_cap + 3) / 4));
-            hipLaunchKernelGGL(k_ed_scan_seg<false>, eg, dim3(256), 0, s, p);
-            hipLaunchKernelGGL(k_ed_scan, dim3(1), dim3(1024), 0, s, p);
-            hipLaunchKernelGGL(k_ed_scan_seg<true>, eg, dim3(256), 0, s, p);
-            if (c->evid_batch) {
-                // read support per edit (k_evidence.hip.h): windows and groups per segment, a wave per alignment, the copy
-                hipLaunchKernelGGL(k_ev_windows, eg, dim3(256), 0, s, p);
-                if (c->A > 0) hipLaunchKernelGGL(k_ev_count, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
-                hipLaunchKernelGGL(k_ev_spread, eg, dim3(256), 0, s, p);
-            }
-        }
-        if (c->pile_batch && p.pile_n) {
-            // the pile-up (k_pileup.hip.h): the counters start from zero in every execution, a re-run included; a wave per
-            // alignment; then the sites: mark and count per tile, one scan, write
-            HIPCHK(c, hipMemsetAsync(c->run.pile.p, 0, p.pile_n * 16, s));
-            if (c->A > 0) hipLaunchKernelGGL(k_pile_count, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
-            const dim3 tg((uint32_t)((p.pile_n + DG_PILE_TILE - 1) / DG_PILE_TILE));
-            hipLaunchKernelGGL(k_pile_sites<false>, tg, dim3(DG_PILE_TILE), 0, s, p);
-            hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(1024), 0, s, p);
-            hipLaunchKernelGGL(k_pile_sites<true>, tg, dim3(DG_PILE_TILE), 0, s, p);
-            if (c->sr_batch) {
-                // the reads at the sites (k_site_reads.hip.h): a bit per site position, count, scan, write; then the split
-                HIPCHK(c, hipMemsetAsync(c->run.sr_bits.p, 0, (p.pile_n + 63) / 64 * 8, s));
-                hipLaunchKernelGGL(k_sr_mark, dim3((uint32_t)((p.site_cap + 255) / 256)), dim3(256), 0, s, p);
-                if (c->A > 0) hipLaunchKernelGGL(k_sr_walk<false>, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
-                hipLaunchKernelGGL(k_sr_scan, dim3(1), dim3(1024), 0, s, p);
-                if (c->A > 0) hipLaunchKernelGGL(k_sr_walk<true>, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
-                if (p.sr_phase && c->A > 0) hipLaunchKernelGGL(k_sr_split, dim3(c->T), dim3(256), 0, s, p);
-                if (c->wl_batch && c->A > 0) {
-                    // the windows' labels joined into blocks (k_winlink.hip.h): a wave per window, one scan, a thread per
-                    // alignment and site.  Every word they leave is written in every execution: nothing to clear
-                    hipLaunchKernelGGL(k_wl_pairs, dim3((c->T + 3) / 4), dim3(256), 0, s, p);
-                    hipLaunchKernelGGL(k_wl_scan, dim3(1), dim3(1024), 0, s, p);
-                    hipLaunchKernelGGL(k_wl_apply, dim3((uint32_t)((std::max<uint64_t>(c->A, p.site_cap) + 255) / 256)), dim3(256), 0, s, p);
-                }
-                if (c->al_batch && c->A > 0) {
-                    // the alleles at the sites (k_alleles.hip.h): a stretch per site, the keys, a table per site, the
-                    // tables' places, an index per entry (and the counts per label, behind the split).
-                    // The sites' cursors start from zero in every execution, a re-run included
-                    const dim3 sg((uint32_t)((p.site_cap + 3) / 4)), ag((c->A + 3) / 4);
-                    HIPCHK(c, hipMemsetAsync(c->run.al_cur.p, 0, (p.site_cap + 1) * 4, s));
-                    hipLaunchKernelGGL(k_al_soff, dim3(1), dim3(1024), 0, s, p);
-                    hipLaunchKernelGGL(k_al_keys, ag, dim3(256), 0, s, p);
-                    hipLaunchKernelGGL(k_al_table, sg, dim3(256), 0, s, p);
-                    hipLaunchKernelGGL(k_al_table_deep, dim3(1024), dim3(256), 0, s, p);
-                    hipLaunchKernelGGL(k_al_tscan, dim3(1), dim3(1024), 0, s, p);
-                    hipLaunchKernelGGL(k_al_index, ag, dim3(256), 0, s, p);
-                }
-                if (c->hap_batch && c->A > 0) {
-                    // the tally of the split (k_hap.hip.h): the sites' counters start from zero in every execution, a
-                    // re-run included; a wave per alignment, then a block per target
-                    HIPCHK(c, hipMemsetAsync(c->run.hap_cnt.p, 0, p.site_cap * 8, s));
-                    hipLaunchKernelGGL(k_hap_tally, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
-                    hipLaunchKernelGGL(k_hap_targets, dim3(c->T), dim3(256), 0, s, p);
-                }
-            }
-        }
+        if ((r = outputs_launch(c, p))) return r;
     }
     HIPCHK(c, hipEventRecord(c->ev[4], s));
     HIPCHK(c, hipGetLastError());
@@ -551,18 +436,13 @@ static bool has_long_gap_run(const char *tstr, const std::vector<uint64_t> &off,
 }
 
 // dev_q / dev_t: the blobs are on the device already (dagcon_consensus_pre: the aligner's output), b->qstr / tstr unused
-// shared: alignments of the batch may name the same strings (dagcon_upload_haps)
-static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q, const void *dev_t, const bool shared = false) {
+// kind: where the batch comes from, which says what it may run with (latch_outputs); dagcon_upload_haps': its alignments
+// may name the same strings
+static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q, const void *dev_t, const Intake kind = Intake::STRINGS) {
     if (!ctx || !b) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->drop_results(Fresh::UPLOAD);
-    c->ed_batch = c->evid_batch = false;                    // (a record upload with edits on says so after the hand-over)
-    c->pile_batch = c->pile_on; c->pile_batch_opts = c->pile_opts;
-    c->sr_batch = c->sr_on && c->pile_on; c->sr_batch_opts = c->sr_opts;
-    c->hap_batch = c->hap_on && c->sr_batch && c->sr_opts.phase != 0;
-    c->al_batch = c->al_on && c->sr_batch;
-    c->wl_batch = false;                                    // (a windows upload with the switch on says so after the hand-over)
-    c->hap_batch_opts = {c->hap_opts.min_sites ? c->hap_opts.min_sites : 2u, c->hap_opts.min_reads ? c->hap_opts.min_reads : 3u};
+    latch_outputs(c, kind);
     c->h_aln_src.clear();
     c->h_cig_bad.clear();
     c->rs_valid = false;
@@ -610,7 +490,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
             c->h_aln_start.push_back(b->aln_start[a]);
             c->h_aln_off.push_back(b->aln_off[a]);
             c->h_aln_tgt.push_back(t);
-            if (c->sr_batch) c->h_aln_src.push_back(a);
+            if (c->o_sr.batch) c->h_aln_src.push_back(a);
             c->sum_len += len;
             // (a read that spans the target begins at its first base and has a column per target base; necessary, not
             // sufficient -- a read that ends early and inserts a lot passes too: the batch is then exact all the same, with
@@ -695,6 +575,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     c->n_chunks = (uint32_t)c->h_ch_aln.size();
     // the scratch of the chunked normalizeGaps: two columns per input column at the alignment's own offset in the blob;
     // where alignments share strings, at the columns in front of it in the batch instead
+    const bool shared = kind == Intake::HAPS;
     c->tmp_shared = shared;
     uint64_t tmp_cols = b->blob_bytes;
     std::vector<uint64_t> tmp_off;
@@ -734,20 +615,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     UPLOAD(c, c->in.ck_base, c->h_ck_base);
     UPLOAD(c, c->in.norm_off, c->h_norm_off);
     if (shared) UPLOAD(c, c->in.tmp_off, tmp_off);          // (a local: upload_impl waits for the stream before it returns)
-    if (c->pile_batch) {
-        // a target's positions [pile_begin[t], + tlen): every target has them, the ones no graph is built for too (all zero)
-        c->h_pile_begin.assign((size_t)T + 1, 0);
-        for (uint32_t t = 0; t < T; t++) c->h_pile_begin[t + 1] = c->h_pile_begin[t] + b->tlen[t];
-        UPLOAD(c, c->in.pile_begin, c->h_pile_begin);
-        // first guess, as for the edits; a run with more sites records their number and is repeated (DG_E_SITE_OVF)
-        c->site_arena.cap = std::max<uint64_t>(c->site_arena.cap, c->h_pile_begin[T] / 8 + 1024);
-        if (c->sr_batch) {
-            // a site index is 32 bits wide in an entry
-            if (c->h_pile_begin[T] > 0xFFFFFFF0ull) return fail(c, DAGCON_ERR_UNSUPPORTED, "dagcon_set_site_reads: more than 2^32 - 16 target positions in a batch");
-            // first guess: one column in 64 an entry; a run with more records their number and is repeated (DG_E_SR_OVF)
-            c->sr_arena.cap = std::max<uint64_t>(c->sr_arena.cap, c->sum_len / 64 + 4096);
-        }
-    }
+    if ((r = outputs_upload(c, b))) return r;
     ENSURE(c, c->run.ckpt, c->n_ckpt * 4);
 
     // work arrays whose size the host knows
@@ -805,13 +673,6 @@ int dagcon_sync(dagcon_ctx *ctx) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DAGCON_OK;
-}
-
-// device -> host on the context's own stream.  (hipMemcpy would go through the null stream, and the stream is
-// non-blocking so that a second context on the same GPU is not serialised against this one's copies.)
-static hipError_t d2h(Ctx *c, void *dst, const void *src, size_t bytes) {
-    hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(c->stream);
 }
 
 // the stages' times of a run the stream has finished, from its events
@@ -901,50 +762,33 @@ static int arena_total(Ctx *c, const GrowArena &g, const bool ran, uint64_t &n) 
     return DAGCON_OK;
 }
 
-// what this fetch brings back and how much of it: decided once from the status block, read by the steps behind it
-struct FetchPlan {
-    bool full, want_sup, want_pos, lazy_pos, want_ed, want_evid, want_pile;
-    uint64_t nseg, nb, n_ed, n_site;
-    size_t ed_seg_bytes, ed_bytes, evid_bytes;      // r_ed: the DgEdSeg records, then the DgEdit records, then the DgEvid records (all 8-byte aligned)
-};
-
 // the sizes, each checked against its arena; the results of the fetch before stop being valid; room for the copies
 static int fetch_plan(Ctx *c, FetchPlan &f) {
     int r;
-    const uint32_t T = c->T;
     f.nseg = c->h_st.seg_top; f.nb = c->h_st.cns_top;
     if (2 * f.nseg * 4 > c->r_seg.cap || f.nseg > c->seg_cap) return fail(c, DAGCON_ERR_INTERNAL, "%llu segments in an arena of %llu", (unsigned long long)f.nseg, (unsigned long long)c->seg_cap);
     if ((r = c->r_blob.reserve(c, f.nb + 1))) return r;
     c->r_blob.as<char>()[f.nb] = 0;
     f.full = !(c->opts.flags & (DAGCON_FLAG_STOP_AFTER_BUILD | DAGCON_FLAG_STOP_AFTER_MERGE));
     f.want_sup = f.full && (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT); f.want_pos = f.full && (c->opts.flags & DAGCON_FLAG_BASE_POS);
+    if ((r = outputs_plan(c, f))) return r;
     // edits on: the edits come instead of the positions, which stay on the device for dagcon_fetch_positions to ask for
-    f.want_ed = f.full && c->ed_batch; f.lazy_pos = f.want_pos && f.want_ed;
-    if ((r = arena_total(c, c->ed_arena, f.want_ed && T, f.n_ed))) return r;
+    f.lazy_pos = f.want_pos && f.want_ed;
     c->drop_results(Fresh::FETCH);
     c->r_nb = f.nb;
-    // the pile-up's sites come back here; its counts, 16 bytes a position, stay on the device until dagcon_fetch_pileup
-    f.want_pile = f.full && c->pile_batch;
-    if ((r = arena_total(c, c->site_arena, f.want_pile && T && c->h_pile_begin.back(), f.n_site))) return r;
-    if (f.want_pile && (r = c->r_site.reserve(c, (size_t)f.n_site * sizeof(DgSite) + 1))) return r;
-    f.want_evid = f.want_ed && c->evid_batch;
-    f.ed_seg_bytes = (size_t)f.nseg * sizeof(DgEdSeg); f.ed_bytes = f.ed_seg_bytes + (size_t)f.n_ed * sizeof(DgEdit);
-    f.evid_bytes = f.want_evid ? (size_t)f.n_ed * sizeof(DgEvid) : 0;
-    if (f.want_ed && (r = c->r_ed.reserve(c, f.ed_bytes + f.evid_bytes + 1))) return r;
     if (f.want_sup && (r = c->r_sup.reserve(c, 2 * (size_t)(f.nb + 1) * 2))) return r;     // (two halves of nb + 1 entries)
     if (f.want_pos && !f.lazy_pos) c->r_pos.resize(f.nb + 1);
     return DAGCON_OK;
 }
 
 // round 2: what the status sizes -- the segments' ranges (the first seg_top entries of either array), the blob, the
-// support (weights then depths: the device keeps them apart, no host pass over them), the positions, the edit records
-// and the sites -- enqueued together, one wait
+// support (weights then depths: the device keeps them apart, no host pass over them), the positions, and what the optional
+// outputs bring (the edit records, the sites) -- enqueued together, one wait
 static int fetch_copies(Ctx *c, const FetchPlan &f) {
     const uint32_t T = c->T;
     const uint64_t nseg = f.nseg, nb = f.nb;
     int32_t *m_r0 = c->r_seg.as<int32_t>(), *m_r1 = m_r0 + nseg;
     uint16_t *const m_sup = c->r_sup.as<uint16_t>();
-    char *const m_edb = c->r_ed.as<char>();
     bool queued = false;
     if (T && f.full && nseg) {
         HIPCHK(c, hipMemcpyAsync(m_r0, c->run.seg.p, nseg * 4, hipMemcpyDeviceToHost, c->stream));
@@ -958,13 +802,7 @@ static int fetch_copies(Ctx *c, const FetchPlan &f) {
         queued = true;
     }
     if (f.want_pos && !f.lazy_pos && nb) { HIPCHK(c, hipMemcpyAsync(c->r_pos.data(), c->run.pos.p, nb * 4, hipMemcpyDeviceToHost, c->stream)); queued = true; }
-    if (f.want_ed && T && nseg) {
-        HIPCHK(c, hipMemcpyAsync(m_edb, c->run.ed_seg.p, f.ed_seg_bytes, hipMemcpyDeviceToHost, c->stream));
-        if (f.n_ed) HIPCHK(c, hipMemcpyAsync(m_edb + f.ed_seg_bytes, c->run.ed_out.p, (size_t)f.n_ed * sizeof(DgEdit), hipMemcpyDeviceToHost, c->stream));
-        if (f.evid_bytes) HIPCHK(c, hipMemcpyAsync(m_edb + f.ed_bytes, c->run.evid.p, f.evid_bytes, hipMemcpyDeviceToHost, c->stream));
-        queued = true;
-    }
-    if (f.n_site) { HIPCHK(c, hipMemcpyAsync(c->r_site.p, c->run.pile_site.p, (size_t)f.n_site * sizeof(DgSite), hipMemcpyDeviceToHost, c->stream)); queued = true; }
+    if (int r = outputs_copies(c, f, queued)) return r;
     if (queued) HIPCHK(c, hipStreamSynchronize(c->stream));
     if (f.want_sup) { c->r_sup_n = nb; c->sup_valid = true; }
     if (f.want_pos && !f.lazy_pos) c->pos_valid = true;
@@ -972,24 +810,13 @@ static int fetch_copies(Ctx *c, const FetchPlan &f) {
     return DAGCON_OK;
 }
 
-// the segments of every target that came through, in the host's order; with them each segment's edit record, its edits
-// and their support, from the device's order into the host's.  bases: the consensus bases of the batch
-static int unpack_segments(Ctx *c, const FetchPlan &f, uint64_t &bases) {
+// the segments of every target that came through, in the host's order.  bases: the consensus bases of the batch
+static void unpack_segments(Ctx *c, const FetchPlan &f, uint64_t &bases) {
     const StatBlock &sb = c->sb;
     const uint32_t T = c->T;
     const uint32_t *m_tfail = sb.h<uint32_t>(sb.o_tfail), *m_n_seg = sb.h<uint32_t>(sb.o_n_seg);
     const uint64_t *m_cns_off = sb.h<uint64_t>(sb.o_cns_off), *m_seg_first = sb.h<uint64_t>(sb.o_seg_first);
     const int32_t *m_r0 = c->r_seg.as<int32_t>(), *m_r1 = m_r0 + f.nseg;
-    const char *const m_edb = c->r_ed.as<char>();
-    const DgEdSeg *m_es = reinterpret_cast<const DgEdSeg *>(m_edb);
-    const DgEdit *m_ed = reinterpret_cast<const DgEdit *>(m_edb + f.ed_seg_bytes);
-    const DgEvid *m_evid = reinterpret_cast<const DgEvid *>(m_edb + f.ed_bytes);
-    const bool want_ed = f.want_ed, want_evid = f.want_evid;
-    if (want_evid) { c->v_begin.clear(); c->v_end.clear(); c->v_span.clear(); c->v_alt.clear(); c->v_ref.clear(); }
-    if (want_ed) {
-        c->e_t0.clear(); c->e_t1.clear(); c->e_begin.clear();
-        c->e_tpos.clear(); c->e_tlen.clear(); c->e_clen.clear(); c->e_coff.clear();
-    }
     c->r_seg_begin.assign(T + 1, 0);
     c->r_range0.clear(); c->r_range1.clear(); c->r_seq_off.clear(); c->r_seq_len.clear();
     bases = 0;
@@ -1003,61 +830,9 @@ static int unpack_segments(Ctx *c, const FetchPlan &f, uint64_t &bases) {
             c->r_seq_off.push_back(m_cns_off[t] + (uint64_t)r0);
             c->r_seq_len.push_back((uint32_t)(r1 - r0));
             bases += (uint64_t)(r1 - r0);
-            if (!want_ed) continue;
-            const DgEdSeg &es = m_es[s];
-            if (es.tgt != t || es.off > f.n_ed || es.cnt > f.n_ed - es.off)
-                return fail(c, DAGCON_ERR_INTERNAL, "k_ed_scan: segment %llu of target %u has edits [%llu, + %u) of %llu, target %u",
-                            (unsigned long long)s, t, (unsigned long long)es.off, es.cnt, (unsigned long long)f.n_ed, es.tgt);
-            c->e_t0.push_back(es.t0); c->e_t1.push_back(es.t1); c->e_begin.push_back(c->e_tpos.size());
-            for (uint32_t k = 0; k < es.cnt; k++) {
-                const DgEdit &e = m_ed[es.off + k];
-                c->e_tpos.push_back(e.t_pos); c->e_tlen.push_back(e.t_len); c->e_coff.push_back(e.c_off); c->e_clen.push_back(e.c_len);
-                if (want_evid) {
-                    const DgEvid &v = m_evid[es.off + k];
-                    c->v_begin.push_back(v.gL); c->v_end.push_back(v.gR);
-                    c->v_span.push_back(v.span); c->v_alt.push_back(v.alt); c->v_ref.push_back(v.ref);
-                }
-            }
         }
     }
     c->r_seg_begin[T] = c->r_range0.size();
-    if (want_ed) { c->e_begin.push_back(c->e_tpos.size()); c->ed_valid = true; }
-    c->evid_valid = want_evid;
-    return DAGCON_OK;
-}
-
-// the pile-up's sites.  The device lists them in the order of the positions: a target's are one stretch, the targets
-// ascend.  A target the host reports as failed has none (one that failed on the device has none there either)
-static int unpack_sites(Ctx *c, const FetchPlan &f) {
-    const uint32_t T = c->T;
-    const uint64_t n_site = f.n_site;
-    const DgSite *m_site = c->r_site.as<const DgSite>();
-    c->s_begin.assign((size_t)T + 1, 0); c->s_pos.clear(); c->s_counts.clear();
-    if (c->sr_batch) c->s_dev_begin.assign((size_t)T + 1, n_site);
-    uint64_t k = 0;
-    for (uint32_t t = 0; t < T; t++) {
-        c->s_begin[t] = c->s_pos.size();
-        if (c->sr_batch) c->s_dev_begin[t] = k;
-        for (; k < n_site && m_site[k].tgt == t; k++) {
-            const DgSite &x = m_site[k];
-            if (x.pos >= c->h_tlen[t]) return fail(c, DAGCON_ERR_INTERNAL, "k_pile_sites: site %llu of target %u at position %u of %u", (unsigned long long)k, t, x.pos, c->h_tlen[t]);
-            if (c->r_status[t] != DAGCON_OK) continue;
-            c->s_pos.push_back(x.pos);
-            for (int j = 0; j < 4; j++) { c->s_counts.push_back((uint16_t)(x.w[j] & 0xFFFFu)); c->s_counts.push_back((uint16_t)(x.w[j] >> 16)); }
-        }
-    }
-    if (k != n_site) return fail(c, DAGCON_ERR_INTERNAL, "k_pile_sites: site %llu of %llu is out of order (target %u)", (unsigned long long)k, (unsigned long long)n_site, m_site[k].tgt);
-    c->s_begin[T] = c->s_pos.size();
-    c->pile_valid = true;
-    if (c->sr_batch) {
-        // the entries stay on the device until dagcon_fetch_site_reads; their number came with the status block
-        c->sr_n_site = n_site;
-        if (int r = arena_total(c, c->sr_arena, T && c->h_pile_begin.back(), c->sr_n_ent)) return r;
-        c->sr_valid = true;
-        c->hap_valid = c->hap_batch;
-        c->wl_valid = c->wl_batch;
-    }
-    return DAGCON_OK;
 }
 
 int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
@@ -1072,8 +847,8 @@ int dagcon_fetch(dagcon_ctx *ctx, dagcon_results *res) {
     uint64_t bases = 0;
     if ((r = fetch_plan(c, f))) return r;
     if ((r = fetch_copies(c, f))) return r;
-    if ((r = unpack_segments(c, f, bases))) return r;
-    if (f.want_pile && (r = unpack_sites(c, f))) return r;
+    unpack_segments(c, f, bases);
+    if ((r = outputs_unpack(c, f))) return r;
     c->tm.consensus_bases = bases;
     c->tm.algorithmic_bytes = 2ull * c->sum_len + bases;
     c->tm.n_alignments = c->A;
@@ -1121,447 +896,6 @@ int dagcon_fetch_positions(dagcon_ctx *ctx, const uint32_t **pos, uint64_t *n) {
         return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_positions without the results of a consensus (no fetch yet, or stopped before bestPath)");
     *pos = c->r_pos.data();
     *n = c->r_pos.size() - 1;
-    return DAGCON_OK;
-}
-
-int dagcon_set_edits(dagcon_ctx *ctx, int on) {
-    if (!ctx) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!(c->opts.flags & DAGCON_FLAG_BASE_POS))
-        return fail(c, DAGCON_ERR_STATE, "dagcon_set_edits on a context created without DAGCON_FLAG_BASE_POS");
-    c->edits_on = on != 0;
-    if (!c->edits_on) c->evid_on = false;
-    return DAGCON_OK;
-}
-
-int dagcon_set_edit_support(dagcon_ctx *ctx, int on) {
-    if (!ctx) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->edits_on) return fail(c, DAGCON_ERR_STATE, "dagcon_set_edit_support without dagcon_set_edits on");
-    c->evid_on = on != 0;
-    return DAGCON_OK;
-}
-
-int dagcon_fetch_edit_support(dagcon_ctx *ctx, dagcon_edit_support *out) {
-    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->edits_on || !c->ed_valid || !c->evid_valid)
-        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_edit_support without the results of a record upload made with dagcon_set_edit_support "
-                                         "on (switch off at the upload, edits off, another kind of upload, no fetch yet, or stopped before bestPath)");
-    out->n = c->v_begin.size();
-    out->w_begin = c->v_begin.data(); out->w_end = c->v_end.data();
-    out->span = c->v_span.data(); out->alt = c->v_alt.data(); out->ref = c->v_ref.data();
-    return DAGCON_OK;
-}
-
-int dagcon_set_pileup(dagcon_ctx *ctx, const dagcon_pileup_opts *o) {
-    if (!ctx) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!o) { c->pile_on = false; return DAGCON_OK; }
-    if (o->min_frac_ppm > 1000000u) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_pileup: min_frac_ppm %u is more than 1000000", o->min_frac_ppm);
-    c->pile_opts = *o;
-    c->pile_on = true;
-    return DAGCON_OK;
-}
-
-static const char *const k_pile_state = "without the results of an upload made with dagcon_set_pileup on (switch off at the upload, no fetch "
-                                        "yet, or stopped before bestPath)";
-
-int dagcon_fetch_pileup_sites(dagcon_ctx *ctx, dagcon_pileup_sites *out) {
-    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->pile_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_pileup_sites %s", k_pile_state);
-    out->n_targets = c->T;
-    out->site_begin = c->s_begin.data(); out->pos = c->s_pos.data(); out->counts = c->s_counts.data();
-    return DAGCON_OK;
-}
-
-int dagcon_fetch_pileup(dagcon_ctx *ctx, dagcon_pileup *out) {
-    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->pile_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_pileup %s", k_pile_state);
-    if (!c->pile_fetched) {
-        // the copy dagcon_fetch left out: 16 bytes a position, only when asked for
-        HIPCHK(c, hipSetDevice(c->device));
-        const uint64_t pn = c->h_pile_begin.back();
-        if (int r = c->r_pile.reserve(c, (size_t)pn * 16 + 16)) return r;
-        if (pn) HIPCHK(c, d2h(c, c->r_pile.p, c->run.pile.p, (size_t)pn * 16));
-        // a failed target: all zero, whatever was counted before it failed
-        for (uint32_t t = 0; t < c->T; t++)
-            if (c->r_status[t] != DAGCON_OK) memset(c->r_pile.as<char>() + 16 * c->h_pile_begin[t], 0, (size_t)16 * c->h_tlen[t]);
-        c->pile_fetched = true;
-    }
-    out->n_targets = c->T;
-    out->pos_begin = c->h_pile_begin.data(); out->counts = c->r_pile.as<uint16_t>();
-    return DAGCON_OK;
-}
-
-int dagcon_set_site_reads(dagcon_ctx *ctx, const dagcon_site_reads_opts *o) {
-    if (!ctx) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!o) { c->sr_on = false; return DAGCON_OK; }
-    if (o->rounds > 64u) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_site_reads: %u rounds are more than 64", o->rounds);
-    c->sr_opts = *o;
-    c->sr_on = true;
-    return DAGCON_OK;
-}
-
-int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out) {
-    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->sr_valid || !c->pile_valid)
-        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_site_reads without the results of an upload made with dagcon_set_pileup and dagcon_set_site_reads on "
-                                         "(a switch off at the upload, no fetch yet, or stopped before bestPath)");
-    const bool phase = c->sr_batch_opts.phase != 0;
-    if (!c->sr_fetched) {
-        // the copies dagcon_fetch left out, and the device's arrays in the host's terms: the alignments of a failed target
-        // and the ones the graph did not take go, a site's index becomes the one dagcon_fetch_pileup_sites lists it under
-        HIPCHK(c, hipSetDevice(c->device));
-        const uint32_t A = c->A, T = c->T;
-        const uint64_t ne = c->sr_n_ent, ns = c->sr_n_site;
-        const bool ran = T && c->h_pile_begin.back();               // (otherwise launch_all started none of the kernels)
-        std::vector<uint32_t> cnt((size_t)A, 0), site((size_t)ne);
-        std::vector<uint8_t> code((size_t)ne), hap((size_t)A, 0);
-        std::vector<int8_t> sigma((size_t)ns, 0);
-        if (ran && A) HIPCHK(c, d2h(c, cnt.data(), c->run.sr_cnt.p, (size_t)A * 4));
-        if (ne) { HIPCHK(c, d2h(c, site.data(), c->run.sr_site.p, (size_t)ne * 4)); HIPCHK(c, d2h(c, code.data(), c->run.sr_code.p, (size_t)ne)); }
-        if (phase && ran && A) HIPCHK(c, d2h(c, hap.data(), c->run.sr_hap.p, (size_t)A));
-        if (phase && ns) HIPCHK(c, d2h(c, sigma.data(), c->run.sr_sigma.p, (size_t)ns));
-        c->x_tgt.clear(); c->x_src.clear(); c->x_begin.assign(1, 0); c->x_site.clear(); c->x_code.clear(); c->x_hap.clear(); c->x_dev.clear();
-        uint64_t e = 0;
-        for (uint32_t a = 0; a < A; a++) {
-            const uint32_t t = c->h_aln_tgt[a], n = cnt[a] & ~DG_SR_TAKEN;
-            const uint64_t e0 = e;
-            e += n;
-            if (e > ne) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_walk: the alignments hold more than the %llu entries of the batch (alignment %u)", (unsigned long long)ne, a);
-            if (c->r_status[t] != DAGCON_OK || !(cnt[a] & DG_SR_TAKEN)) continue;
-            const uint64_t d0 = c->s_dev_begin[t], d1 = c->s_dev_begin[t + 1];
-            for (uint64_t j = e0; j < e; j++) {
-                if (site[j] < d0 || site[j] >= d1 || (code[j] & 7u) > 5u || (code[j] >> 4))
-                    return fail(c, DAGCON_ERR_INTERNAL, "k_sr_walk: entry %llu of alignment %u: site %u, code %u (target %u has sites [%llu, %llu))", (unsigned long long)(j - e0), a,
-                                site[j], code[j], t, (unsigned long long)d0, (unsigned long long)d1);
-                c->x_site.push_back(site[j] - d0 + c->s_begin[t]);
-                c->x_code.push_back(code[j]);
-            }
-            c->x_tgt.push_back(t); c->x_src.push_back(c->h_aln_src[a]); c->x_begin.push_back(c->x_site.size());
-            if (hap[a] > 2u) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_split: alignment %u has hap %u", a, hap[a]);
-            c->x_hap.push_back(hap[a]);
-            if (c->wl_batch) c->x_dev.push_back(a);
-        }
-        if (e != ne) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_walk: the alignments hold %llu entries, the batch %llu", (unsigned long long)e, (unsigned long long)ne);
-        c->x_phase.assign(c->s_pos.size() + 1, 0);
-        for (uint32_t t = 0; t < T && phase; t++) {
-            if (c->r_status[t] != DAGCON_OK) continue;
-            for (uint64_t j = c->s_begin[t]; j < c->s_begin[t + 1]; j++) c->x_phase[j] = sigma[c->s_dev_begin[t] + (j - c->s_begin[t])];
-        }
-        c->x_site.push_back(0); c->x_code.push_back(0); c->x_tgt.push_back(0); c->x_src.push_back(0); c->x_hap.push_back(0);   // (no NULL for an empty array)
-        c->sr_fetched = true;
-    }
-    out->n_aln = c->x_begin.size() - 1;
-    out->aln_tgt = c->x_tgt.data(); out->aln_src = c->x_src.data(); out->ent_begin = c->x_begin.data();
-    out->ent_site = c->x_site.data(); out->ent_code = c->x_code.data();
-    out->hap = phase ? c->x_hap.data() : nullptr; out->phase = phase ? c->x_phase.data() : nullptr;
-    return DAGCON_OK;
-}
-
-int dagcon_set_site_alleles(dagcon_ctx *ctx, int on) {
-    if (!ctx) return DAGCON_ERR_INVALID_ARG;
-    reinterpret_cast<Ctx *>(ctx)->al_on = on != 0;
-    return DAGCON_OK;
-}
-
-int dagcon_fetch_site_alleles(dagcon_ctx *ctx, dagcon_site_alleles *out) {
-    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->al_batch || !c->sr_valid || !c->pile_valid)
-        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_site_alleles without the results of an upload made with dagcon_set_pileup, dagcon_set_site_reads and "
-                                         "dagcon_set_site_alleles on (a switch off at the upload, no fetch yet, or stopped before bestPath)");
-    const bool phase = c->sr_batch_opts.phase != 0;
-    if (!c->al_fetched) {
-        // the entries in the host's terms first (which of the device's survive, and each one's site); then the copies
-        // dagcon_fetch left out: the tables' places, the compact tables, an index per entry.  A failed target's sites and
-        // entries go, as in dagcon_fetch_site_reads
-        dagcon_site_reads sr;
-        if (int r = dagcon_fetch_site_reads(ctx, &sr)) return r;
-        HIPCHK(c, hipSetDevice(c->device));
-        const uint32_t A = c->A, T = c->T;
-        const uint64_t ne = c->sr_n_ent, ns = c->sr_n_site;
-        const bool ran = T && A && c->h_pile_begin.back();           // (otherwise launch_all started none of the kernels)
-        unsigned long long tot[2] = {0ull, 0ull};
-        if (ran) HIPCHK(c, d2h(c, tot, c->run.al_tot.p, sizeof tot));
-        const uint64_t na = tot[1];
-        if (na > c->sr_arena.cap || (!ran && (ne || ns)))
-            return fail(c, DAGCON_ERR_INTERNAL, "k_al_tscan: %llu alleles in an arena of %llu", (unsigned long long)na, (unsigned long long)c->sr_arena.cap);
-        std::vector<uint64_t> toff((size_t)ns), key((size_t)na);
-        std::vector<uint32_t> nd((size_t)ns), cnt((size_t)A, 0), count((size_t)na), hapw((size_t)na);
-        std::vector<uint16_t> idx((size_t)ne);
-        if (ns) { HIPCHK(c, d2h(c, toff.data(), c->run.al_toff.p, (size_t)ns * 8)); HIPCHK(c, d2h(c, nd.data(), c->run.al_nd.p, (size_t)ns * 4)); }
-        if (na) {
-            // the compact copy, now that its size is known: room, zeros (a table k_al_pack refuses stays empty and fails
-            // the checks below), the copy on the stream
-            ENSURE(c, c->run.al_ckey, (size_t)na * 8); ENSURE(c, c->run.al_ccnt, (size_t)na * 4); ENSURE(c, c->run.al_chap, (size_t)na * 4);
-            HIPCHK(c, hipMemsetAsync(c->run.al_ckey.p, 0, (size_t)na * 8, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->run.al_ccnt.p, 0, (size_t)na * 4, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->run.al_chap.p, 0, (size_t)na * 4, c->stream));
-            DgParams p;
-            fill_params(c, p);
-            hipLaunchKernelGGL(k_al_pack, dim3((uint32_t)((p.site_cap + 3) / 4)), dim3(256), 0, c->stream, p);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, d2h(c, key.data(), c->run.al_ckey.p, (size_t)na * 8)); HIPCHK(c, d2h(c, count.data(), c->run.al_ccnt.p, (size_t)na * 4));
-            HIPCHK(c, d2h(c, hapw.data(), c->run.al_chap.p, (size_t)na * 4));
-        }
-        if (ne) HIPCHK(c, d2h(c, idx.data(), c->run.al_idx.p, (size_t)ne * 2));
-        if (ran) HIPCHK(c, d2h(c, cnt.data(), c->run.sr_cnt.p, (size_t)A * 4));
-        c->z_begin.assign(1, 0); c->z_key.clear(); c->z_count.clear(); c->z_hap.clear(); c->z_ent.clear();
-        for (uint32_t t = 0; t < T; t++) {
-            if (c->r_status[t] != DAGCON_OK) continue;
-            for (uint64_t j = c->s_begin[t]; j < c->s_begin[t + 1]; j++) {
-                const uint64_t d = c->s_dev_begin[t] + (j - c->s_begin[t]);
-                uint64_t depth = 0, sum = 0;
-                for (int q = 0; q < 6; q++) depth += c->s_counts[j * 8 + q];
-                if (d >= ns || toff[d] > na || nd[d] > na - toff[d] || !nd[d])
-                    return fail(c, DAGCON_ERR_INTERNAL, "k_al_table: site %llu of target %u has alleles [%llu, + %u) of %llu", (unsigned long long)d, t,
-                                (unsigned long long)(d < ns ? toff[d] : 0), d < ns ? nd[d] : 0u, (unsigned long long)na);
-                for (uint64_t i = toff[d]; i < toff[d] + nd[d]; i++) {
-                    const uint32_t c1 = hapw[i] & 0xFFFFu, c2 = hapw[i] >> 16;
-                    sum += count[i];
-                    if ((key[i] >> 61) || !count[i] || (uint64_t)c1 + c2 > count[i])
-                        return fail(c, DAGCON_ERR_INTERNAL, "k_al_table: allele %llu of site %llu: key %llx, count %u, c1 %u, c2 %u", (unsigned long long)(i - toff[d]),
-                                    (unsigned long long)d, (unsigned long long)key[i], count[i], c1, c2);
-                    c->z_key.push_back(key[i]); c->z_count.push_back(count[i]);
-                    c->z_hap.push_back((uint16_t)c1); c->z_hap.push_back((uint16_t)c2); c->z_hap.push_back((uint16_t)(count[i] - c1 - c2));
-                }
-                if (sum != depth) return fail(c, DAGCON_ERR_INTERNAL, "k_al_table: the alleles of site %llu count %llu entries, its depth is %llu", (unsigned long long)d,
-                                              (unsigned long long)sum, (unsigned long long)depth);
-                c->z_begin.push_back(c->z_key.size());
-            }
-        }
-        // the entries, in the order of dagcon_fetch_site_reads (x_site: each one's site there)
-        uint64_t e = 0;
-        for (uint32_t a = 0; a < A; a++) {
-            const uint32_t t = c->h_aln_tgt[a], n = cnt[a] & ~DG_SR_TAKEN;
-            const uint64_t e0 = e;
-            e += n;
-            if (e > ne) return fail(c, DAGCON_ERR_INTERNAL, "k_al_index: the alignments hold more than the %llu entries of the batch (alignment %u)", (unsigned long long)ne, a);
-            if (c->r_status[t] != DAGCON_OK || !(cnt[a] & DG_SR_TAKEN)) continue;
-            for (uint64_t j = e0; j < e; j++) {
-                const uint64_t x = c->z_ent.size();
-                if (x + 1 >= c->x_site.size() || idx[j] >= c->z_begin[c->x_site[x] + 1] - c->z_begin[c->x_site[x]])
-                    return fail(c, DAGCON_ERR_INTERNAL, "k_al_index: entry %llu of alignment %u has allele %u", (unsigned long long)(j - e0), a, idx[j]);
-                c->z_ent.push_back(idx[j]);
-            }
-        }
-        if (c->z_ent.size() + 1 != c->x_site.size())
-            return fail(c, DAGCON_ERR_INTERNAL, "k_al_index: %llu entries with an allele, %llu entries", (unsigned long long)c->z_ent.size(), (unsigned long long)(c->x_site.size() - 1));
-        c->z_key.push_back(0); c->z_count.push_back(0); c->z_ent.push_back(0); c->z_hap.insert(c->z_hap.end(), 3, 0);   // (no NULL for an empty array)
-        c->al_fetched = true;
-    }
-    out->n_sites = c->z_begin.size() - 1;
-    out->al_begin = c->z_begin.data(); out->key = c->z_key.data(); out->count = c->z_count.data();
-    out->hap_count = phase ? c->z_hap.data() : nullptr;
-    out->n_ent = c->z_ent.size() - 1; out->ent_allele = c->z_ent.data();
-    return DAGCON_OK;
-}
-
-// host only: the one implementation is the command line's (host/alleles.h)
-int dagcon_allele_text(uint64_t key, char *out, size_t cap) { return dg_allele_text(key, out, cap); }
-
-int dagcon_set_hap_consensus(dagcon_ctx *ctx, const dagcon_hap_opts *o) {
-    if (!ctx) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!o) { c->hap_on = false; return DAGCON_OK; }
-    c->hap_opts = *o;
-    c->hap_on = true;
-    return DAGCON_OK;
-}
-
-static const char *const k_hap_state = "without the results of an upload made with dagcon_set_pileup, dagcon_set_site_reads (phase on) and "
-                                       "dagcon_set_hap_consensus on (a switch off at the upload, no fetch yet, stopped before bestPath, or the "
-                                       "batch is dagcon_upload_haps' own)";
-
-// the per-target records of the tally, once a fetch: n1 n2 n0 n_sep agree disagree and the split bit; a failed target has zeros
-static int hap_records(Ctx *c) {
-    if (c->hap_fetched) return DAGCON_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const uint32_t T = c->T;
-    const bool ran = T && c->A && c->h_pile_begin.back();          // (otherwise launch_all started none of the kernels)
-    std::vector<uint32_t> rec((size_t)T * DG_HAP_REC, 0u);
-    if (ran) HIPCHK(c, d2h(c, rec.data(), c->run.hap_rec.p, rec.size() * 4));
-    c->y_rec.assign((size_t)6 * T + 1, 0u); c->y_split.assign((size_t)T + 1, 0);
-    for (uint32_t t = 0; t < T; t++) {
-        if (c->r_status[t] != DAGCON_OK) continue;
-        const uint32_t *r = &rec[(size_t)t * DG_HAP_REC];
-        const uint64_t K = c->h_aln_begin[t + 1] - c->h_aln_begin[t];
-        if (r[6] > 1u || r[7] || (uint64_t)r[0] + r[1] + r[2] > K)
-            return fail(c, DAGCON_ERR_INTERNAL, "k_hap_targets: target %u of %llu alignments has n1 %u, n2 %u, n0 %u, split %u", t, (unsigned long long)K, r[0], r[1], r[2], r[6]);
-        for (int i = 0; i < 6; i++) c->y_rec[(size_t)i * T + t] = r[i];
-        c->y_split[t] = (uint8_t)r[6];
-    }
-    c->hap_fetched = true;
-    return DAGCON_OK;
-}
-
-int dagcon_fetch_hap_tally(dagcon_ctx *ctx, dagcon_hap_tally *out) {
-    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->hap_valid || !c->pile_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_hap_tally %s", k_hap_state);
-    if (int r = hap_records(c)) return r;
-    const uint32_t T = c->T;
-    if (!c->hap_sites_fetched) {
-        // 8 bytes a site, in the device's order; the host's list leaves out the sites of failed targets
-        const uint64_t ns = c->sr_n_site;
-        std::vector<uint16_t> dev((size_t)ns * 4 + 4, 0);
-        if (ns && c->A) HIPCHK(c, d2h(c, dev.data(), c->run.hap_cnt.p, (size_t)ns * 8));
-        c->y_counts.assign(c->s_pos.size() * 4 + 4, 0);
-        for (uint32_t t = 0; t < T; t++) {
-            if (c->r_status[t] != DAGCON_OK) continue;
-            const uint64_t n = c->s_begin[t + 1] - c->s_begin[t];
-            if (c->s_dev_begin[t] + n > ns) return fail(c, DAGCON_ERR_INTERNAL, "k_hap_tally: target %u has sites [%llu, + %llu) of %llu", t, (unsigned long long)c->s_dev_begin[t], (unsigned long long)n, (unsigned long long)ns);
-            if (n) memcpy(&c->y_counts[c->s_begin[t] * 4], &dev[c->s_dev_begin[t] * 4], (size_t)n * 8);
-        }
-        c->hap_sites_fetched = true;
-    }
-    out->n_targets = T;
-    out->n1 = c->y_rec.data(); out->n2 = out->n1 + T; out->n0 = out->n2 + T;
-    out->n_sep = out->n0 + T; out->agree = out->n_sep + T; out->disagree = out->agree + T;
-    out->split = c->y_split.data(); out->site_counts = c->y_counts.data();
-    return DAGCON_OK;
-}
-
-int dagcon_set_window_phase(dagcon_ctx *ctx, const dagcon_window_phase_opts *o) {
-    if (!ctx) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!o) { c->wl_on = false; return DAGCON_OK; }
-    if (o->max_conflict_ppm > 1000000u) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_window_phase: max_conflict_ppm %u is more than 1000000", o->max_conflict_ppm);
-    c->wl_opts = *o;
-    c->wl_on = true;
-    return DAGCON_OK;
-}
-
-int dagcon_fetch_window_phase(dagcon_ctx *ctx, dagcon_window_phase *out) {
-    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->wl_valid || !c->sr_valid || !c->pile_valid)
-        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_window_phase without the results of a windows upload made with dagcon_set_pileup, dagcon_set_site_reads "
-                                         "(phase on) and dagcon_set_window_phase on (a switch off at the upload, no windows, no fetch yet, or stopped before bestPath)");
-    const uint32_t T = c->T;
-    if (!c->wl_fetched) {
-        // the alignments and the sites go into the host's order as in dagcon_fetch_site_reads, which says which stay (x_dev)
-        dagcon_site_reads sr;
-        if (int r = dagcon_fetch_site_reads(ctx, &sr)) return r;
-        const uint32_t A = c->A;
-        const uint64_t ns = c->sr_n_site;
-        const bool ran = T && A && c->h_pile_begin.back();         // (otherwise launch_all started none of the kernels)
-        std::vector<uint32_t> cnt((size_t)T * 2, 0u);
-        std::vector<uint8_t> hap((size_t)A, 0);
-        std::vector<int8_t> sigma((size_t)ns, 0);
-        c->w_block.assign((size_t)T + 1, 0u); c->w_flip.assign((size_t)T + 1, 0);
-        for (uint32_t t = 0; t < T; t++) c->w_block[t] = t;
-        if (ran) {
-            HIPCHK(c, d2h(c, cnt.data(), c->run.wl_cnt.p, (size_t)T * 8));
-            HIPCHK(c, d2h(c, c->w_block.data(), c->run.wl_block.p, (size_t)T * 4));
-            HIPCHK(c, d2h(c, c->w_flip.data(), c->run.wl_flip.p, (size_t)T));
-            HIPCHK(c, d2h(c, hap.data(), c->run.wl_hap.p, (size_t)A));
-            if (ns) HIPCHK(c, d2h(c, sigma.data(), c->run.wl_phase.p, (size_t)ns));
-        }
-        c->w_same.assign((size_t)T + 1, 0u); c->w_diff.assign((size_t)T + 1, 0u);
-        for (uint32_t t = 0; t < T; t++) {
-            c->w_same[t] = cnt[2 * (size_t)t]; c->w_diff[t] = cnt[2 * (size_t)t + 1];
-            if (c->w_block[t] > t || c->w_flip[t] > 1u || (c->w_block[t] == t && c->w_flip[t]))
-                return fail(c, DAGCON_ERR_INTERNAL, "k_wl_scan: window %u has block %u, flip %u", t, c->w_block[t], c->w_flip[t]);
-        }
-        const size_t nx = c->x_dev.size();
-        c->w_hap.assign(nx + 1, 0);
-        for (size_t x = 0; x < nx; x++) {
-            const uint8_t h = hap[c->x_dev[x]];
-            if (h > 2u) return fail(c, DAGCON_ERR_INTERNAL, "k_wl_apply: alignment %u has hap %u", c->x_dev[x], h);
-            c->w_hap[x] = h;
-        }
-        c->w_phase.assign(c->s_pos.size() + 1, 0);
-        for (uint32_t t = 0; t < T; t++) {
-            if (c->r_status[t] != DAGCON_OK) continue;
-            for (uint64_t j = c->s_begin[t]; j < c->s_begin[t + 1]; j++) c->w_phase[j] = sigma[c->s_dev_begin[t] + (j - c->s_begin[t])];
-        }
-        c->wl_fetched = true;
-    }
-    out->n_windows = T;
-    out->same = c->w_same.data(); out->diff = c->w_diff.data(); out->block = c->w_block.data(); out->flip = c->w_flip.data();
-    out->n_aln = c->x_dev.size(); out->hap = c->w_hap.data();
-    out->n_sites = c->s_pos.size(); out->phase = c->w_phase.data();
-    return DAGCON_OK;
-}
-
-int dagcon_upload_haps(dagcon_ctx *ctx) {
-    if (!ctx) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->hap_valid || !c->pile_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_upload_haps %s", k_hap_state);
-    if (int r = hap_records(c)) return r;
-    const uint32_t T = c->T, A = c->A;
-    std::vector<uint8_t> hap((size_t)A, 0);
-    if (T && A && c->h_pile_begin.back()) HIPCHK(c, d2h(c, hap.data(), c->run.sr_hap.p, (size_t)A));
-    // the plan, on the host: one byte an alignment and one record a target say everything upload_impl needs.  Group g of a
-    // split target: its alignments of the device batch with hap g or 0 (the ones the graph did not take are 0 too)
-    std::vector<uint32_t> tlen, start, len, src_target;
-    std::vector<uint64_t> begin(1, 0), off, bb_off, src;
-    std::vector<uint8_t> label;
-    for (uint32_t t = 0; t < T; t++) {
-        if (!c->y_split[t]) continue;
-        for (uint8_t g = 1; g <= 2; g++) {
-            for (uint64_t a = c->h_aln_begin[t]; a < c->h_aln_begin[t + 1]; a++) {
-                if (hap[a] > 2u) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_split: alignment %llu has hap %u", (unsigned long long)a, hap[a]);
-                if (hap[a] && hap[a] != g) continue;
-                off.push_back(c->h_aln_off[a]); len.push_back(c->h_aln_len[a]); start.push_back(c->h_aln_start[a]);
-                src.push_back(c->h_aln_src[a]);
-            }
-            tlen.push_back(c->h_tlen[t]); bb_off.push_back(c->h_bb_off[t]);
-            src_target.push_back(t); label.push_back(g); begin.push_back(off.size());
-        }
-    }
-    dagcon_batch db;
-    memset(&db, 0, sizeof db);
-    db.n_targets = (uint32_t)tlen.size(); db.tlen = tlen.data(); db.aln_begin = begin.data();
-    db.aln_start = start.data(); db.aln_off = off.data(); db.aln_len = len.data();
-    db.blob_bytes = c->blob_bytes;
-    if (c->have_bb) { db.backbone = c->in.bb.as<const char>(); db.backbone_off = bb_off.data(); }    // (in.bb itself: nothing is copied)
-    // an upload like any other, with every optional output off for it; the switches themselves stay as the caller set them
-    // (put back when the guard goes, whichever way this function is left)
-    struct SwitchesOff {
-        Ctx *c;
-        const bool pile_on, sr_on, hap_on, al_on;
-        explicit SwitchesOff(Ctx *x) : c(x), pile_on(x->pile_on), sr_on(x->sr_on), hap_on(x->hap_on), al_on(x->al_on) { c->pile_on = c->sr_on = c->hap_on = c->al_on = false; }
-        ~SwitchesOff() { c->pile_on = pile_on; c->sr_on = sr_on; c->hap_on = hap_on; c->al_on = al_on; }
-    };
-    int r;
-    {
-        const SwitchesOff off(c);
-        r = upload_impl(ctx, &db, c->in.q.p, c->in.t.p, true);
-    }
-    if (r != DAGCON_OK) return r;                                    // (as after any failed upload: the first batch's results are gone)
-    src_target.push_back(0); label.push_back(0); src.push_back(0);   // (no NULL for an empty array)
-    c->m_src_target.swap(src_target); c->m_label.swap(label); c->m_aln_begin.swap(begin); c->m_aln_src.swap(src);
-    c->hapmap_valid = true;
-    return DAGCON_OK;
-}
-
-int dagcon_fetch_hap_map(dagcon_ctx *ctx, dagcon_hap_map *out) {
-    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->hapmap_valid) return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_hap_map without a dagcon_upload_haps as the last upload");
-    out->n_targets = (uint32_t)(c->m_aln_begin.size() - 1);
-    out->src_target = c->m_src_target.data(); out->label = c->m_label.data();
-    out->aln_begin = c->m_aln_begin.data(); out->aln_src = c->m_aln_src.data();
-    return DAGCON_OK;
-}
-
-int dagcon_fetch_edits(dagcon_ctx *ctx, dagcon_edits *out) {
-    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c->edits_on || !c->ed_valid)
-        return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_edits without the results of a record upload made with dagcon_set_edits on (edits off, "
-                                         "another kind of upload, no fetch yet, or stopped before bestPath)");
-    out->n_segments = c->e_t0.size(); out->n = c->e_tpos.size();
-    out->seg_t0 = c->e_t0.data(); out->seg_t1 = c->e_t1.data(); out->edit_begin = c->e_begin.data();
-    out->t_pos = c->e_tpos.data(); out->t_len = c->e_tlen.data(); out->c_off = c->e_coff.data(); out->c_len = c->e_clen.data();
     return DAGCON_OK;
 }
 

@@ -5,7 +5,8 @@
 //   b  k_merge              | c  k_bestpath
 // There is no CPU fallback anywhere in it: without a HIP device
 // dagcon_create fails with DAGCON_ERR_NO_DEVICE.
-// One translation unit, cut by stage into the four api_* files included below.
+// One translation unit, cut by stage into the five api_* files included below; api_outputs.hip.h holds the host side of
+// every optional output of a run (its room, parameters, launches, fetch and entry points).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdarg>
@@ -40,5 +41,6 @@
 #include "host/alleles.h"
 #include "api_ctx.h"
 #include "api_run.hip.h"
+#include "api_outputs.hip.h"
 #include "api_align.hip.h"
 #include "api_records.hip.h"

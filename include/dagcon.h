@@ -447,7 +447,7 @@ int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out);
  * label 2, by rule 7, with the tlen (and the backbone, if the first batch had one) of its target.  The strings are those
  * the first batch left on the device, whichever way they came in: none crosses the bus and none is copied.  It is an
  * upload like any other: the results of the first batch and dagcon_fetch_md_targets stop being valid, every optional
- * output (edits, edit support, pile-up, site reads, site alleles, tally) is off for the derived batch and its fetch DAGCON_ERR_STATE,
+ * output (edits, edit support, pile-up, site reads, site alleles, joined sites, tally) is off for the derived batch and its fetch DAGCON_ERR_STATE,
  * the record filter has nothing to do, and a second dagcon_upload_haps in a row is DAGCON_ERR_STATE.  min_cov, min_len,
  * trim, min_weight and the context's flags (DAGCON_FLAG_BASE_SUPPORT / _BASE_POS with their fetches among them) hold as
  * for dagcon_upload; a group with fewer reads than min_weight lets few bases out, which is the caller's option to set as
@@ -524,6 +524,62 @@ typedef struct dagcon_site_alleles {
 int dagcon_set_site_alleles(dagcon_ctx *ctx, int on);
 int dagcon_fetch_site_alleles(dagcon_ctx *ctx, dagcon_site_alleles *out);
 int dagcon_allele_text(uint64_t key, char *out, size_t cap);   /* host only; needs no device */
+
+/*
+ * Joined sites: adjacent sites of the pile-up joined into runs, and per run what its alignments show at all of its sites
+ * at once (off by default; a context switch that needs dagcon_set_pileup, dagcon_set_site_reads and
+ * dagcon_set_site_alleles on at the same upload).  The tables of rule 8 keep every position on its own: a deletion of
+ * three bases is three sites with the empty allele, and two neighbouring substitutions no longer say whether the same
+ * alignments carry both.  This is this build's own rule, PARITY UNPINNED, in the terms of rules 1 to 8 above.
+ * 10. 10.1 Runs.  Take the sites in the order of dagcon_fetch_pileup_sites.  Site k > 0 CONTINUES site k - 1 iff both have
+ *          the same target and pos[k] == pos[k - 1] + 1.  A maximal chain of continuing sites is a stretch.  A stretch is
+ *          cut, from its first site, into runs of at most DG_JN_SITES = 16 sites: site k is a run head iff it does not
+ *          continue, or (k - first site of its stretch) % 16 == 0.  Every site lies in exactly one run; run r holds the
+ *          sites [run_begin[r], run_begin[r + 1]), m is its length.  The last position of one target and position 0 of
+ *          the next are never joined.
+ *     10.2 Members.  Alignment x SPANS run r iff it has an entry (rule 2) at every site of r; it is a PARTIAL member iff
+ *          it has an entry at at least one site of r but not at all of them.  spanning[r] and partial[r] count the two
+ *          kinds.  An alignment's target columns are consecutive positions, so its entries are consecutive sites.  For
+ *          every site k of r: depth(k) = spanning[r] + the partial members with an entry at k.
+ *     10.3 The joined key of a spanning member is a 64-bit integer.  Let a_j be ent_allele of its entry at the run's j-th
+ *          site, the index in that site's table (rule 8), and c_j = min(a_j, 15).  Then key = the sum over j < m of
+ *          c_j << (4 * (15 - j)); the unused low nibbles are 0.  Nibble 15 means "allele 15 or later of that site's
+ *          table": such alleles COUNT AS ONE, as long alleles do in rule 8.
+ *     10.4 The table of a run: the distinct keys of its spanning members, each with its count, ordered by count
+ *          descending, ties by key ascending (unsigned); joined alleles [jal_begin[r], jal_begin[r + 1]).  The counts add
+ *          up to spanning[r].  With phase on at the upload each joined allele also has c1, c2, c0 by hap of the alignment;
+ *          c1 + c2 + c0 == count.  ent_joined[e], one value per entry in the order of dagcon_fetch_site_reads, is the
+ *          index of the alignment's key in the table of the run that holds the entry's site, or 0xFFFF for a partial
+ *          member; all m entries of a spanning member carry the same value.  A failed target has no runs.
+ *     10.5 Text (host only; the command line's, csrc/host/joined.h).  A joined allele's bases are the texts of its sites'
+ *          alleles one after the other (dagcon_allele_text without "-"), or "-" when all are empty.  The allele is OPAQUE
+ *          and prints "*" when a nibble is 15 or a site's allele is long.
+ *     Nothing in the rule depends on an order.
+ * dagcon_set_site_join: the switch is read at the upload; without the three switches it rests on on at the same upload it
+ * is as if off.  With it off no kernel, buffer, memset, launch or copy differs from a context that never heard of it.
+ * With it on, the kernels of csrc/k_join.hip.h run behind those of the alleles in every execution of the run; they need
+ * no arena of their own: the spanning members of a run number at most the depth of its first site, and a table is no
+ * longer than that (a run holds 20 bytes an entry and 36 a site more).  The arrays stay on the device and are copied only
+ * when dagcon_fetch_joined_sites is called (the tables are gathered by one more kernel then: 16 bytes a joined allele),
+ * which converts them as dagcon_fetch_site_alleles converts its own (it calls it).  DAGCON_ERR_STATE wherever
+ * dagcon_fetch_site_alleles is, and when the switch was off at the upload; the derived batch of dagcon_upload_haps has it
+ * off.  Owned by the context, valid as long as the results of the same fetch.
+ */
+#define DG_JN_SITES 16u
+typedef struct dagcon_joined_sites {
+    uint64_t n_runs;
+    const uint64_t *run_begin;   /* [n_runs + 1] into the sites of dagcon_fetch_pileup_sites */
+    const uint32_t *spanning;    /* [n_runs] */
+    const uint32_t *partial;     /* [n_runs] */
+    const uint64_t *jal_begin;   /* [n_runs + 1] */
+    const uint64_t *key;         /* [n] */
+    const uint32_t *count;       /* [n] */
+    const uint16_t *hap_count;   /* [3 n] c1 c2 c0; NULL when phase was off */
+    uint64_t n_ent;              /* the entries of dagcon_fetch_site_reads, same order */
+    const uint16_t *ent_joined;  /* [n_ent] index within the table of the entry's run; 0xFFFF: a partial member */
+} dagcon_joined_sites;
+int dagcon_set_site_join(dagcon_ctx *ctx, int on);
+int dagcon_fetch_joined_sites(dagcon_ctx *ctx, dagcon_joined_sites *out);
 
 /*
  * Phase across windows: the read labels of neighbouring windows joined into blocks (off by default; a context switch that

@@ -46,6 +46,7 @@ EXPORTS = [
     "dagcon_set_pileup", "dagcon_fetch_pileup", "dagcon_fetch_pileup_sites",
     "dagcon_set_site_reads", "dagcon_fetch_site_reads",
     "dagcon_set_site_alleles", "dagcon_fetch_site_alleles", "dagcon_allele_text",
+    "dagcon_set_site_join", "dagcon_fetch_joined_sites",
     "dagcon_set_hap_consensus", "dagcon_fetch_hap_tally", "dagcon_upload_haps", "dagcon_fetch_hap_map",
     "dagcon_upload_cigar_md", "dagcon_consensus_cigar_md", "dagcon_fetch_md_targets",
     "dagcon_set_window_phase", "dagcon_fetch_window_phase",
@@ -172,6 +173,16 @@ class SiteAlleles(C.Structure):
                 ("ent_allele", C.POINTER(C.c_uint16))]
 
 
+class JoinedSites(C.Structure):
+    """dagcon_joined_sites: the runs of adjacent sites of dagcon_pileup_sites, per run its spanning and partial members and
+    its table of joined alleles (key, count, c1 c2 c0), per entry of dagcon_site_reads the index of its alignment's joined
+    allele or 0xFFFF (include/dagcon.h has the rule, 10)."""
+    _fields_ = [("n_runs", C.c_uint64), ("run_begin", C.POINTER(C.c_uint64)), ("spanning", C.POINTER(C.c_uint32)),
+                ("partial", C.POINTER(C.c_uint32)), ("jal_begin", C.POINTER(C.c_uint64)), ("key", C.POINTER(C.c_uint64)),
+                ("count", C.POINTER(C.c_uint32)), ("hap_count", C.POINTER(C.c_uint16)), ("n_ent", C.c_uint64),
+                ("ent_joined", C.POINTER(C.c_uint16))]
+
+
 class HapOpts(C.Structure):
     """dagcon_hap_opts: a target is split when it has at least min_sites separating sites and min_reads alignments of
     either label; 0, 0 are the defaults 2 and 3 (include/dagcon.h has the rule)."""
@@ -294,6 +305,8 @@ def load() -> C.CDLL:
     L.dagcon_fetch_site_reads.argtypes = [vp, C.POINTER(SiteReads)]
     L.dagcon_set_site_alleles.argtypes = [vp, C.c_int]
     L.dagcon_fetch_site_alleles.argtypes = [vp, C.POINTER(SiteAlleles)]
+    L.dagcon_set_site_join.argtypes = [vp, C.c_int]
+    L.dagcon_fetch_joined_sites.argtypes = [vp, C.POINTER(JoinedSites)]
     L.dagcon_allele_text.argtypes = [C.c_uint64, C.c_char_p, C.c_size_t]
     L.dagcon_set_hap_consensus.argtypes = [vp, C.POINTER(HapOpts)]
     L.dagcon_fetch_hap_tally.argtypes = [vp, C.POINTER(HapTally)]
@@ -1014,6 +1027,30 @@ class Context:
         return {"al_begin": begin, "key": arr(sa.key, n, np.uint64), "count": arr(sa.count, n, np.uint32),
                 "hap_count": (arr(sa.hap_count, 3 * n, np.uint16).reshape(n, 3) if sa.hap_count else None),
                 "ent_allele": arr(sa.ent_allele, ne, np.uint16)}
+
+    def set_site_join(self, on=True):
+        """dagcon_set_site_join for every later upload made with set_pileup, set_site_reads and set_site_alleles on: the
+        device joins adjacent sites into runs and counts what the alignments show at all of a run's sites (joined_sites())."""
+        self._chk(self.L.dagcon_set_site_join(self.h, 1 if on else 0))
+
+    def joined_sites(self) -> dict:
+        """dagcon_fetch_joined_sites (copies): run_begin (uint64, one per run and one more, into the sites of
+        pileup_sites()); spanning, partial (uint32 per run); jal_begin (uint64, one per run and one more); key (uint64),
+        count (uint32) and hap_count (uint16, [joined alleles, 3]: c1 c2 c0; None when phase was off) per joined allele;
+        ent_joined (uint16, per entry of site_reads(): the index within its run's table, 0xFFFF for a partial member)."""
+        js = JoinedSites()
+        self._chk(self.L.dagcon_fetch_joined_sites(self.h, C.byref(js)))
+        nr, ne = int(js.n_runs), int(js.n_ent)
+
+        def arr(ptr, k, dt):
+            return np.ctypeslib.as_array(ptr, shape=(k,)).copy() if k else np.zeros(0, dt)
+        begin = np.ctypeslib.as_array(js.jal_begin, shape=(nr + 1,)).copy()
+        n = int(begin[nr])
+        return {"run_begin": np.ctypeslib.as_array(js.run_begin, shape=(nr + 1,)).copy(), "spanning": arr(js.spanning, nr, np.uint32),
+                "partial": arr(js.partial, nr, np.uint32), "jal_begin": begin, "key": arr(js.key, n, np.uint64),
+                "count": arr(js.count, n, np.uint32),
+                "hap_count": (arr(js.hap_count, 3 * n, np.uint16).reshape(n, 3) if js.hap_count else None),
+                "ent_joined": arr(js.ent_joined, ne, np.uint16)}
 
     def set_hap_consensus(self, min_sites=0, min_reads=0):
         """dagcon_set_hap_consensus for every later upload made with set_pileup and set_site_reads(True) on: the device

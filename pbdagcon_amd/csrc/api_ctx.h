@@ -99,17 +99,23 @@ struct RunBufs {
     // (cleared before every run), its table's size and offset, the list of the deep sites; the stretches (keys, counts,
     // counts per label, the places' indices); the compact tables (sized and filled at the fetch); the two totals
     DevBuf al_map, al_idx, al_soff, al_cur, al_nd, al_deep, al_toff, al_srt, al_tcnt, al_thap, al_ckey, al_ccnt, al_chap, al_tot;
-    std::array<DevBuf *, 94> all() {
+    // dagcon_set_site_join: per site its run and its stretch's first site; per run its first site, its cursor and partial
+    // count (one buffer, cleared before every run), its table's size and offset, the list of the deep runs; per entry its
+    // member's place, then its joined allele's index; the stretches (keys, counts, counts per label, the places' indices);
+    // the compact tables (sized and filled at the fetch); the three totals
+    DevBuf jn_run, jn_sfirst, jn_rbeg, jn_cur, jn_nd, jn_deep, jn_toff, jn_key, jn_tcnt, jn_thap, jn_map, jn_idx, jn_ckey, jn_ccnt, jn_chap, jn_tot;
+    std::array<DevBuf *, 110> all() {
         return {&nmis, &n_lo, &n_hi, &n_start, &n_ins, &n_del, &ch_k0, &ch_next, &ch_w, &ch_tb, &ch_flag, &ch_src, &ch_out, &ch_adv, &n_lb, &norm_tmp, &ckpt,
                 &node_base, &n_nodes, &pool_base, &pool_size, &pool_top, &t_nins, &cov, &gcount, &gbase, &bid, &best, &queue, &score, &cns_tmp, &bp_tt,
                 &stk, &cuts, &cuts_bp, &bp_stat, &bp_len, &rd, &pro_state, &sh_cnt, &wl_first, &queue0, &bp_end, &bp_ab, &defer, &cns_tmp0, &cns,
                 &seg, &worklist, &seg_done, &sup_tmp, &sup_tmp0, &sup, &pos_tmp, &pos_tmp0, &pos, &ed_seg, &ed_out, &evid, &pile, &pile_tile, &pile_site,
                 &sr_bits, &sr_rank, &sr_cnt, &sr_off, &sr_site, &sr_code, &sr_hap, &sr_sigma, &sr_kind, &sr_acc, &sr_nz,
                 &hap_cnt, &hap_rec, &wl_cnt, &wl_block, &wl_flip, &wl_hap, &wl_phase,
-                &al_map, &al_idx, &al_soff, &al_cur, &al_nd, &al_deep, &al_toff, &al_srt, &al_tcnt, &al_thap, &al_ckey, &al_ccnt, &al_chap, &al_tot};
+                &al_map, &al_idx, &al_soff, &al_cur, &al_nd, &al_deep, &al_toff, &al_srt, &al_tcnt, &al_thap, &al_ckey, &al_ccnt, &al_chap, &al_tot,
+                &jn_run, &jn_sfirst, &jn_rbeg, &jn_cur, &jn_nd, &jn_deep, &jn_toff, &jn_key, &jn_tcnt, &jn_thap, &jn_map, &jn_idx, &jn_ckey, &jn_ccnt, &jn_chap, &jn_tot};
     }
 };
-static_assert(sizeof(RunBufs) == 94 * sizeof(DevBuf), "RunBufs::all() must name every member");
+static_assert(sizeof(RunBufs) == 110 * sizeof(DevBuf), "RunBufs::all() must name every member");
 // ArenaBufs: the arenas with a treatment of their own -- matC is cleared before every run, the others are filled under
 // DAGCON_POISON bits 1 (matA, matD), 2 (nodes, pool) and 4 (score_b, norm)
 struct ArenaBufs {
@@ -182,6 +188,13 @@ struct SiteReadsOut {
 struct AllelesOut {
     std::vector<uint64_t> begin, key;
     std::vector<uint32_t> count;
+    std::vector<uint16_t> hap, ent;
+};
+// dagcon_fetch_joined_sites: where a run's sites and its joined alleles begin; per run its spanning and partial members; per
+// joined allele its key, count and counts per label; per entry its joined allele
+struct JoinedOut {
+    std::vector<uint64_t> run_begin, begin, key;
+    std::vector<uint32_t> spanning, partial, count;
     std::vector<uint16_t> hap, ent;
 };
 // dagcon_fetch_hap_tally: two lazy parts -- the per-target records (Output::fetched; dagcon_upload_haps reads them too),
@@ -290,6 +303,9 @@ struct Ctx {
     // dagcon_set_site_alleles
     Output o_al{"without the results of an upload made with dagcon_set_pileup, dagcon_set_site_reads and dagcon_set_site_alleles on (a switch off at the "
                 "upload, no fetch yet, or stopped before bestPath)"};
+    // dagcon_set_site_join
+    Output o_jn{"without the results of an upload made with dagcon_set_pileup, dagcon_set_site_reads, dagcon_set_site_alleles and dagcon_set_site_join on (a "
+                "switch off at the upload, no fetch yet, or stopped before bestPath)"};
     // dagcon_set_hap_consensus
     Output o_hap{"without the results of an upload made with dagcon_set_pileup, dagcon_set_site_reads (phase on) and dagcon_set_hap_consensus on (a switch "
                  "off at the upload, no fetch yet, stopped before bestPath, or the batch is dagcon_upload_haps' own)"};
@@ -298,7 +314,7 @@ struct Ctx {
     Output o_wl{"without the results of a windows upload made with dagcon_set_pileup, dagcon_set_site_reads (phase on) and dagcon_set_window_phase on (a "
                 "switch off at the upload, no windows, no fetch yet, or stopped before bestPath)"};
     dagcon_window_phase_opts wl_opts = {0u, 0u}, wl_batch_opts = {0u, 0u};
-    std::array<Output *, 7> outputs() { return {&o_ed, &o_evid, &o_pile, &o_sr, &o_al, &o_hap, &o_wl}; }
+    std::array<Output *, 8> outputs() { return {&o_ed, &o_evid, &o_pile, &o_sr, &o_al, &o_jn, &o_hap, &o_wl}; }
     // the growing arenas: run.ed_out (and run.evid beside it), run.pile_site, run.sr_site / sr_code.  The status block
     // holds 16 bytes for the edits' total, then 16 for the sites', whose second word is the entries'
     GrowArena ed_arena{"edits", DG_E_ED_OVF, true, &DgParams::ed_top, &DgParams::ed_cap};
@@ -337,6 +353,7 @@ struct Ctx {
     SitesOut r_sites;
     SiteReadsOut r_reads;
     AllelesOut r_alleles;
+    JoinedOut r_joined;
     HapOut r_haps;
     WinPhaseOut r_winphase;
     HapMapOut r_hapmap;

@@ -1,5 +1,5 @@
 // api_outputs.hip.h -- the optional outputs of a run (edits and their support, the pile-up and its sites, the reads at the
-// sites, the window phase, the alleles, the haplotype tally), each one's host side in one place: its room, its kernel
+// sites, the window phase, the alleles, the joined sites, the haplotype tally), each one's host side in one place: its room, its kernel
 // parameters, its launches, its part of the fetch and its dagcon_set_* / dagcon_fetch_* entry points.  The pipeline
 // (api_run.hip.h) calls outputs_room, outputs_params, outputs_launch, outputs_upload and the outputs_plan / _copies /
 // _unpack steps of dagcon_fetch, at the end of this file; DESIGN.md says how to add an output.  (The entry points stand
@@ -12,7 +12,7 @@ namespace {
 // The dependency rule, once: which outputs the batch being uploaded runs with, and with which options (defaults filled
 // in).  Edits need a record upload and their support needs edits; the sites need the pile-up; the reads at the sites need
 // the sites; the alleles, the tally and the window phase need those reads, the last two with phase on; the window phase
-// needs a windows upload.  The batch of dagcon_upload_haps runs with none, whatever the switches say.
+// needs a windows upload; the joined sites need the alleles.  The batch of dagcon_upload_haps runs with none, whatever the switches say.
 void latch_outputs(Ctx *c, const Intake kind) {
     for (Output *o : c->outputs()) o->batch = false;
     if (kind == Intake::HAPS) return;
@@ -22,6 +22,7 @@ void latch_outputs(Ctx *c, const Intake kind) {
     c->o_sr.batch = c->o_sr.on && c->o_pile.batch;
     const bool phased = c->o_sr.batch && c->sr_opts.phase != 0;
     c->o_al.batch = c->o_al.on && c->o_sr.batch;
+    c->o_jn.batch = c->o_jn.on && c->o_al.batch;
     c->o_hap.batch = c->o_hap.on && phased;
     c->o_wl.batch = c->o_wl.on && phased && kind == Intake::WINDOWS;
     c->pile_batch_opts = c->pile_opts;
@@ -630,6 +631,171 @@ int dagcon_fetch_site_alleles(dagcon_ctx *ctx, dagcon_site_alleles *out) {
 // host only: the one implementation is the command line's (host/alleles.h)
 int dagcon_allele_text(uint64_t key, char *out, size_t cap) { return dg_allele_text(key, out, cap); }
 
+// ---- adjacent sites joined into runs (k_join.hip.h) ----
+namespace {
+
+int join_room(Ctx *c) {
+    if (!c->o_jn.batch) return DAGCON_OK;
+    const size_t ne = c->sr_arena.cap, ns = c->site_arena.cap;
+    // (20 bytes an entry and 36 a site; the compact tables wait for dagcon_fetch_joined_sites, which knows their size)
+    ENSURE(c, c->run.jn_run, ns * 4); ENSURE(c, c->run.jn_sfirst, ns * 4); ENSURE(c, c->run.jn_rbeg, (ns + 1) * 4);
+    ENSURE(c, c->run.jn_cur, (2 * ns + 1) * 4); ENSURE(c, c->run.jn_nd, ns * 4); ENSURE(c, c->run.jn_deep, ns * 4); ENSURE(c, c->run.jn_toff, ns * 8);
+    ENSURE(c, c->run.jn_key, ne * 8); ENSURE(c, c->run.jn_tcnt, ne * 4); ENSURE(c, c->run.jn_thap, ne * 4);
+    ENSURE(c, c->run.jn_map, ne * 2); ENSURE(c, c->run.jn_idx, ne * 2);
+    ENSURE(c, c->run.jn_tot, 32);
+    return DAGCON_OK;
+}
+
+void join_params(Ctx *c, DgParams &p) {
+    if (!c->o_jn.batch) return;
+    p.jn_run = c->run.jn_run.as<uint32_t>(); p.jn_sfirst = c->run.jn_sfirst.as<uint32_t>(); p.jn_rbeg = c->run.jn_rbeg.as<uint32_t>();
+    p.jn_cur = c->run.jn_cur.as<uint32_t>(); p.jn_part = p.jn_cur + c->site_arena.cap + 1;
+    p.jn_nd = c->run.jn_nd.as<uint32_t>(); p.jn_deep = c->run.jn_deep.as<uint32_t>(); p.jn_toff = c->run.jn_toff.as<unsigned long long>();
+    p.jn_key = c->run.jn_key.as<unsigned long long>(); p.jn_tcnt = c->run.jn_tcnt.as<uint32_t>(); p.jn_thap = c->run.jn_thap.as<uint32_t>();
+    p.jn_map = c->run.jn_map.as<uint16_t>(); p.jn_idx = c->run.jn_idx.as<uint16_t>();
+    p.jn_ckey = c->run.jn_ckey.as<unsigned long long>(); p.jn_ccnt = c->run.jn_ccnt.as<uint32_t>(); p.jn_chap = c->run.jn_chap.as<uint32_t>();
+    p.jn_st_top = c->run.jn_tot.as<unsigned long long>(); p.jn_run_top = p.jn_st_top + 1; p.jn_top = p.jn_st_top + 2;
+}
+
+int join_launch(Ctx *c, const DgParams &p) {
+    if (!c->o_jn.batch || !reads_ran(c)) return DAGCON_OK;
+    hipStream_t s = c->stream;
+    // the runs, the spanning members' keys, a table per run, the tables' places, an index per entry (and the counts per
+    // label).  The runs' cursors and partial counts start from zero in every execution, a re-run included
+    const dim3 rg((uint32_t)((p.site_cap + 3) / 4)), ag((c->A + 3) / 4);
+    HIPCHK(c, hipMemsetAsync(c->run.jn_cur.p, 0, (2 * p.site_cap + 1) * 4, s));
+    hipLaunchKernelGGL(k_jn_stretch, dim3(1), dim3(1024), 0, s, p);
+    hipLaunchKernelGGL(k_jn_runs, dim3(1), dim3(1024), 0, s, p);
+    hipLaunchKernelGGL(k_jn_keys, ag, dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_jn_table, rg, dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_jn_table_deep, dim3(1024), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_jn_tscan, dim3(1), dim3(1024), 0, s, p);
+    hipLaunchKernelGGL(k_jn_index, ag, dim3(256), 0, s, p);
+    return DAGCON_OK;
+}
+
+}  // namespace
+
+int dagcon_set_site_join(dagcon_ctx *ctx, int on) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    reinterpret_cast<Ctx *>(ctx)->o_jn.on = on != 0;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_joined_sites(dagcon_ctx *ctx, dagcon_joined_sites *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (int r = need(c, c->o_jn, "dagcon_fetch_joined_sites")) return r;
+    const bool phase = c->sr_batch_opts.phase != 0;
+    JoinedOut &o = c->r_joined;
+    if (!c->o_jn.fetched) {
+        // the sites, the entries and the alleles in the host's terms first; then the copies dagcon_fetch left out: the
+        // runs, their members' counts, the tables' places, the compact tables, an index per entry.  A failed target's
+        // sites, runs and entries go, as in dagcon_fetch_site_alleles
+        dagcon_site_alleles sa;
+        if (int r = dagcon_fetch_site_alleles(ctx, &sa)) return r;
+        HIPCHK(c, hipSetDevice(c->device));
+        const HostOrder &h = c->order;
+        const SitesOut &s = c->r_sites;
+        const std::vector<uint64_t> &x_site = c->r_reads.site;
+        const uint32_t T = c->T;
+        const uint64_t ne = c->r_reads.n_dev_ent, ns = s.n_dev;
+        const bool ran = reads_ran(c);
+        unsigned long long tot[3] = {0ull, 0ull, 0ull};
+        if (ran) HIPCHK(c, d2h(c, tot, c->run.jn_tot.p, sizeof tot));
+        const uint64_t nr = tot[1], nj = tot[2];
+        if (nr > ns || nj > c->sr_arena.cap || (ns && ran && !nr))
+            return fail(c, DAGCON_ERR_INTERNAL, "k_jn_runs: %llu runs of %llu sites, %llu joined alleles in an arena of %llu", (unsigned long long)nr, (unsigned long long)ns,
+                        (unsigned long long)nj, (unsigned long long)c->sr_arena.cap);
+        std::vector<uint32_t> rbeg((size_t)nr + 1, 0u), span((size_t)nr), part((size_t)nr), nd((size_t)nr), count((size_t)nj), hapw((size_t)nj);
+        std::vector<uint64_t> toff((size_t)nr), key((size_t)nj);
+        std::vector<uint16_t> idx((size_t)ne);
+        if (nr) {
+            HIPCHK(c, d2h(c, rbeg.data(), c->run.jn_rbeg.p, ((size_t)nr + 1) * 4)); HIPCHK(c, d2h(c, span.data(), c->run.jn_cur.p, (size_t)nr * 4));
+            HIPCHK(c, d2h(c, part.data(), c->run.jn_cur.as<uint32_t>() + c->site_arena.cap + 1, (size_t)nr * 4));
+            HIPCHK(c, d2h(c, nd.data(), c->run.jn_nd.p, (size_t)nr * 4)); HIPCHK(c, d2h(c, toff.data(), c->run.jn_toff.p, (size_t)nr * 8));
+        }
+        if (nj) {
+            // the compact copy, now that its size is known: room, zeros (a table k_jn_pack refuses stays empty and fails
+            // the checks below), the copy on the stream
+            ENSURE(c, c->run.jn_ckey, (size_t)nj * 8); ENSURE(c, c->run.jn_ccnt, (size_t)nj * 4); ENSURE(c, c->run.jn_chap, (size_t)nj * 4);
+            HIPCHK(c, hipMemsetAsync(c->run.jn_ckey.p, 0, (size_t)nj * 8, c->stream));
+            HIPCHK(c, hipMemsetAsync(c->run.jn_ccnt.p, 0, (size_t)nj * 4, c->stream));
+            HIPCHK(c, hipMemsetAsync(c->run.jn_chap.p, 0, (size_t)nj * 4, c->stream));
+            DgParams p;
+            fill_params(c, p);
+            hipLaunchKernelGGL(k_jn_pack, dim3((uint32_t)((p.site_cap + 3) / 4)), dim3(256), 0, c->stream, p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, d2h(c, key.data(), c->run.jn_ckey.p, (size_t)nj * 8)); HIPCHK(c, d2h(c, count.data(), c->run.jn_ccnt.p, (size_t)nj * 4));
+            HIPCHK(c, d2h(c, hapw.data(), c->run.jn_chap.p, (size_t)nj * 4));
+        }
+        if (ne) HIPCHK(c, d2h(c, idx.data(), c->run.jn_idx.p, (size_t)ne * 2));
+        o.run_begin.clear(); o.spanning.clear(); o.partial.clear(); o.begin.assign(1, 0); o.key.clear(); o.count.clear(); o.hap.clear(); o.ent.clear();
+        std::vector<uint32_t> run_of((size_t)s.pos.size() + 1, 0u);           // a host site's run
+        uint64_t r = 0;                                                       // the device's runs ascend with its sites
+        for (uint32_t t = 0; t < T; t++) {
+            const uint64_t d0 = s.dev_begin[t], d1 = s.dev_begin[t + 1];
+            while (r < nr && rbeg[r] < d0) r++;
+            if (c->r_status[t] != DAGCON_OK) continue;
+            uint64_t first = 0;                                               // of the stretch, in the host's list
+            for (uint64_t j = s.begin[t]; j < s.begin[t + 1]; j++) {
+                // rule 10.1 on the host's list; the device's run must begin exactly where the rule says
+                const bool cont = j > s.begin[t] && s.pos[j] == s.pos[j - 1] + 1u;
+                if (!cont) first = j;
+                const bool head = !cont || (j - first) % 16u == 0u;
+                const uint64_t d = d0 + (j - s.begin[t]);
+                const bool dev_head = r < nr && rbeg[r] == d;
+                if (head != dev_head || d >= d1)
+                    return fail(c, DAGCON_ERR_INTERNAL, "k_jn_runs: site %llu of target %u: a run head by the rule %d, on the device %d", (unsigned long long)d, t, (int)head, (int)dev_head);
+                if (head) {
+                    uint64_t depth = 0, sum = 0;
+                    for (int q = 0; q < 6; q++) depth += s.counts[j * 8 + q];
+                    if (toff[r] > nj || nd[r] > nj - toff[r] || span[r] > depth || (uint64_t)span[r] + part[r] < depth || (!nd[r]) != (!span[r]))
+                        return fail(c, DAGCON_ERR_INTERNAL, "k_jn_table: run %llu of target %u has joined alleles [%llu, + %u) of %llu, %u spanning and %u partial members, depth %llu",
+                                    (unsigned long long)r, t, (unsigned long long)toff[r], nd[r], (unsigned long long)nj, span[r], part[r], (unsigned long long)depth);
+                    for (uint64_t i = toff[r]; i < toff[r] + nd[r]; i++) {
+                        const uint32_t c1 = hapw[i] & 0xFFFFu, c2 = hapw[i] >> 16;
+                        sum += count[i];
+                        if (!count[i] || (uint64_t)c1 + c2 > count[i])
+                            return fail(c, DAGCON_ERR_INTERNAL, "k_jn_table: joined allele %llu of run %llu: key %llx, count %u, c1 %u, c2 %u", (unsigned long long)(i - toff[r]),
+                                        (unsigned long long)r, (unsigned long long)key[i], count[i], c1, c2);
+                        o.key.push_back(key[i]); o.count.push_back(count[i]);
+                        o.hap.push_back((uint16_t)c1); o.hap.push_back((uint16_t)c2); o.hap.push_back((uint16_t)(count[i] - c1 - c2));
+                    }
+                    if (sum != span[r]) return fail(c, DAGCON_ERR_INTERNAL, "k_jn_table: the joined alleles of run %llu count %llu members, %u span it", (unsigned long long)r,
+                                                    (unsigned long long)sum, span[r]);
+                    o.run_begin.push_back(j); o.spanning.push_back(span[r]); o.partial.push_back(part[r]); o.begin.push_back(o.key.size());
+                    r++;
+                }
+                run_of[j] = (uint32_t)(o.spanning.size() - 1);
+            }
+        }
+        o.run_begin.push_back(s.pos.size());
+        // the entries, in the order of dagcon_fetch_site_reads (x_site: each one's site there)
+        for (size_t k = 0; k < h.aln.size(); k++) {
+            const uint64_t e0 = h.ent_begin[k];
+            for (uint64_t j = e0; j < e0 + h.ent_n[k]; j++) {
+                const uint64_t x = o.ent.size();
+                if (x + 1 >= x_site.size()) return fail(c, DAGCON_ERR_INTERNAL, "k_jn_index: more than %llu entries", (unsigned long long)(x_site.size() - 1));
+                const uint32_t rr = run_of[x_site[x]];
+                if (idx[j] != 0xFFFFu && idx[j] >= o.begin[rr + 1] - o.begin[rr])
+                    return fail(c, DAGCON_ERR_INTERNAL, "k_jn_index: entry %llu of alignment %u has joined allele %u", (unsigned long long)(j - e0), h.aln[k], idx[j]);
+                o.ent.push_back(idx[j]);
+            }
+        }
+        if (o.ent.size() + 1 != x_site.size())
+            return fail(c, DAGCON_ERR_INTERNAL, "k_jn_index: %llu entries with a joined allele, %llu entries", (unsigned long long)o.ent.size(), (unsigned long long)(x_site.size() - 1));
+        pad(o.key, o.count, o.ent, o.hap, o.hap, o.hap, o.spanning, o.partial);
+        c->o_jn.fetched = true;
+    }
+    out->n_runs = o.run_begin.size() - 1;
+    out->run_begin = o.run_begin.data(); out->spanning = o.spanning.data(); out->partial = o.partial.data();
+    out->jal_begin = o.begin.data(); out->key = o.key.data(); out->count = o.count.data();
+    out->hap_count = phase ? o.hap.data() : nullptr;
+    out->n_ent = o.ent.size() - 1; out->ent_joined = o.ent.data();
+    return DAGCON_OK;
+}
+
 // ---- the tally of the split, and the batch of the groups (k_hap.hip.h) ----
 namespace {
 
@@ -775,11 +941,12 @@ namespace {
 int outputs_room(Ctx *c) {
     int r;
     if ((r = edits_room(c)) || (r = pile_room(c)) || (r = reads_room(c)) || (r = hap_room(c)) || (r = winphase_room(c))) return r;
-    return alleles_room(c);
+    if ((r = alleles_room(c))) return r;
+    return join_room(c);
 }
 
 void outputs_params(Ctx *c, DgParams &p) {
-    edits_params(c, p); pile_params(c, p); reads_params(c, p); hap_params(c, p); winphase_params(c, p); alleles_params(c, p);
+    edits_params(c, p); pile_params(c, p); reads_params(c, p); hap_params(c, p); winphase_params(c, p); alleles_params(c, p); join_params(c, p);
 }
 
 // between k_bp_join and the last event of a run that goes as far as bestPath (T > 0)
@@ -788,7 +955,7 @@ int outputs_launch(Ctx *c, const DgParams &p) {
     edits_launch(c, p);
     if ((r = pile_launch(c, p)) || (r = reads_launch(c, p))) return r;
     winphase_launch(c, p);
-    if ((r = alleles_launch(c, p))) return r;
+    if ((r = alleles_launch(c, p)) || (r = join_launch(c, p))) return r;
     return hap_launch(c, p);
 }
 

@@ -37,6 +37,7 @@
 #include "k_site_reads.hip.h"
 #include "k_hap.hip.h"
 #include "k_alleles.hip.h"
+#include "k_join.hip.h"
 #include "k_winlink.hip.h"
 #include "host/alleles.h"
 #include "api_ctx.h"

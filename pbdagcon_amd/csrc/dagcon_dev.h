@@ -283,6 +283,23 @@ struct DgParams {
     uint8_t *wl_hap;               // [A] sr_hap, oriented (k_wl_apply)
     int8_t *wl_phase;              // [site_cap] sr_sigma, oriented
     uint32_t wl_min_links, wl_max_ppm;     // dagcon_window_phase_opts (the defaults filled in)
+    // ---- adjacent sites joined into runs (dagcon_set_site_join; NULL / 0 otherwise): k_join.hip.h.  Last, so that every
+    // field above keeps its offset ----
+    uint32_t *jn_run;              // [site_cap] a site's stretch (k_jn_stretch), then its run (k_jn_runs)
+    uint32_t *jn_sfirst;           // [site_cap] a stretch's first site
+    uint32_t *jn_rbeg;             // [site_cap + 1] a run's first site; one more: the end of the last run
+    uint32_t *jn_cur;              // [site_cap + 1] spanning members a run's stretch holds (cleared before every run); last: the deep runs listed
+    uint32_t *jn_part;             // [site_cap] a run's partial members (cleared with jn_cur)
+    uint32_t *jn_nd;               // [site_cap] joined alleles of a run's table
+    uint32_t *jn_deep;             // [site_cap] the runs of more than 64 spanning members, in no order
+    unsigned long long *jn_toff;   // [site_cap] where a run's table begins in the compact arrays (k_jn_tscan)
+    unsigned long long *jn_key;    // [sr_cap] the stretch of a run's first site (al_soff): its spanning members' keys, then (k_jn_table) its table's keys at the front
+    uint32_t *jn_tcnt, *jn_thap;   // [sr_cap] parallel to jn_key: the count and c1 | c2 << 16 of a table's joined allele
+    uint16_t *jn_map;              // [sr_cap] parallel to jn_key: the joined allele's index of the member that holds this place
+    uint16_t *jn_idx;              // [sr_cap] parallel to sr_site: a spanning member's place (k_jn_keys), then its joined allele's index (k_jn_index); DG_JN_NONE: a partial member's entry
+    unsigned long long *jn_ckey;   // [*jn_top, at the fetch] the tables, run after run: key, count, c1 | c2 << 16
+    uint32_t *jn_ccnt, *jn_chap;
+    unsigned long long *jn_st_top, *jn_run_top, *jn_top;   // the stretches, the runs, the joined alleles of the batch (words of their own, fetched when asked)
 };
 #define DG_HAP_REC 8u
 #define DG_SR_TAKEN 0x80000000u

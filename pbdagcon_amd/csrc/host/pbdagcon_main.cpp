@@ -54,6 +54,7 @@
 #include "pileup.h"
 #include "site_reads.h"
 #include "alleles.h"
+#include "joined.h"
 #include "hap.h"
 
 namespace {
@@ -77,7 +78,9 @@ struct Opts {
     DgSiteReadOpts sr;                 // --site-reads FILE, --haplotag FILE (whole targets, not -a): which read shows which allele at the sites; a two-way split
     DgHapOpts hap;                     // --hap-consensus FILE, --hap-sites FILE (where --haplotag goes): a consensus per group of the split, the split's tally
     DgAlleleOpts al;                   // --site-alleles FILE, --site-vcf FILE (where --site-reads goes): the alleles themselves at the sites, counted
-    bool want_sr() const { return sr.on() || hap.on() || al.on(); }   // (the tally and the alleles need the site reads, whether or not their files are asked for)
+    DgJoinedOpts jn;                   // --joined-alleles FILE, --joined-vcf FILE (where --site-alleles / --site-vcf go): adjacent sites joined into one record
+    bool want_al() const { return al.on() || jn.on(); }               // (the joined sites need the alleles, whether or not their files are asked for)
+    bool want_sr() const { return sr.on() || hap.on() || want_al(); }   // (the tally and the alleles need the site reads, whether or not their files are asked for)
     bool want_phase() const { return sr.phase() || hap.on(); }        // the split: --haplotag, --hap-consensus or --hap-sites
     bool want_pile() const { return pile.on() || want_sr(); } // (the site reads need the pile-up, whether or not its files are asked for)
     bool fastq = false;                // --fastq: FASTQ records, qualities from the per-base support (fastq.h)
@@ -94,7 +97,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [--site-alleles FILE] [--site-vcf FILE] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [--site-alleles FILE] [--site-vcf FILE] [--joined-alleles FILE] [--joined-vcf FILE] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -252,6 +255,21 @@ void usage(FILE *f) {
             "                      deleted base takes the target base in front as anchor for the whole record (the base behind at\n"
             "                      position 1; a target of one base has no records).  Adjacent sites are NOT joined: a deletion\n"
             "                      of three bases is three records.  No genotype is called\n"
+            "  --joined-alleles FILE where --site-alleles goes: adjacent positions that --sites would list are joined into runs (of\n"
+            "                      at most 16; never across targets), and FILE lists what the reads that cover a whole run show\n"
+            "                      over all of it, one line per joined allele: RNAME POS END REF SPAN PARTIAL ALLELE COUNT H1 H2 H0,\n"
+            "                      tab-separated, POS and END 1-based inclusive, REF the target's bases there (. without them).\n"
+            "                      SPAN reads cover every position of the run, PARTIAL only some; ALLELE is the alleles of\n"
+            "                      --site-alleles one after the other, - for none (the whole run deleted), * when it cannot be\n"
+            "                      spelled (a + allele, or one past the 15th of its position's table).  Counted on the GPU;\n"
+            "                      stdout does not change.  This build's own rule; the reference has no such output\n"
+            "  --joined-vcf FILE   with --sam, --bam or --paf: the same tables as VCFv4.2, one record per run that has an ALT:\n"
+            "                      RNAME POS . REF ALT . . DP=span;PART=partial;AD=ref,alt1,..  (and AD1=..;AD2=.. with the split on).\n"
+            "                      A deletion of three bases is one record, and two neighbouring substitutions carried by the\n"
+            "                      same reads are one ALT.  ALT is every joined allele that is not *, differs from REF and has\n"
+            "                      COUNT >= --site-min-count; an empty one takes the base in front as anchor (the base behind the\n"
+            "                      run at position 1; a run that covers its whole target has no record).  Shared leading and\n"
+            "                      trailing bases of REF and ALT are NOT trimmed.  No genotype is called\n"
             "  -v, --verbose       per-target progress on stderr\n"
             "  --polish N          with -a: N more rounds, each with the previous round's consensus as the backbone the reads\n"
             "                      are re-aligned to (README.md:14-15 of the reference: 'the new consensus can be used as a new\n"
@@ -325,6 +343,14 @@ int parse_args(int argc, char **argv, Opts &o) {
         else if (a == "--site-vcf") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --site-vcf needs a file name\n"); return 2; }
             o.al.vcf = argv[++i];
+        }
+        else if (a == "--joined-alleles") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --joined-alleles needs a file name\n"); return 2; }
+            o.jn.alleles = argv[++i];
+        }
+        else if (a == "--joined-vcf") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --joined-vcf needs a file name\n"); return 2; }
+            o.jn.vcf = argv[++i];
         }
         else if (a == "--haplotag") {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --haplotag needs a file name\n"); return 2; }
@@ -431,6 +457,9 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (o.al.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --site-alleles and --site-vcf do not go with --window, -a or --polish (they go where --site-reads goes)\n"); return 2; }
     if (o.al.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --site-alleles and --site-vcf do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (!o.al.vcf.empty() && !records) { fprintf(stderr, "PARSE ERROR: --site-vcf needs --sam, --bam or --paf (REF comes from the target's bases)\n"); return 2; }
+    if (o.jn.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --joined-alleles and --joined-vcf do not go with --window, -a or --polish (they go where --site-reads goes)\n"); return 2; }
+    if (o.jn.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --joined-alleles and --joined-vcf do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
+    if (!o.jn.vcf.empty() && !records) { fprintf(stderr, "PARSE ERROR: --joined-vcf needs --sam, --bam or --paf (REF comes from the target's bases)\n"); return 2; }
     if (o.pile.on() && o.polish) { fprintf(stderr, "PARSE ERROR: --pileup and --sites do not go with --polish (the backbone changes under the positions)\n"); return 2; }
     if (o.pile.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --pileup and --sites do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (o.overlap_set && !o.window) { fprintf(stderr, "PARSE ERROR: --overlap needs --window\n"); return 2; }
@@ -525,7 +554,8 @@ struct Batch {
     std::string site_reads, haplotag;  // and the batch's lines of those files
     std::string hap_out, hap_sites;    // --hap-consensus, --hap-sites: the batch's records and lines of those files
     std::string site_alleles, site_vcf, site_contigs;   // --site-alleles, --site-vcf: the batch's lines of those files, and its targets' ##contig lines
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); hap_out.clear(); hap_sites.clear(); site_alleles.clear(); site_vcf.clear(); site_contigs.clear(); }
+    std::string joined_alleles, joined_vcf, joined_contigs;   // --joined-alleles, --joined-vcf: the same
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); hap_out.clear(); hap_sites.clear(); site_alleles.clear(); site_vcf.clear(); site_contigs.clear(); joined_alleles.clear(); joined_vcf.clear(); joined_contigs.clear(); }
 };
 
 FILE *g_edits = nullptr;                                  // --edits FILE, written batch by batch in output order
@@ -542,6 +572,9 @@ FILE *g_site_alleles = nullptr;                            // --site-alleles FIL
 // --site-vcf FILE, as --vcf: the header names every target, so the records wait in an unnamed temporary file
 FILE *g_site_vcf = nullptr, *g_site_vcf_lines = nullptr;
 std::string g_site_vcf_contigs;
+FILE *g_joined_alleles = nullptr;                          // --joined-alleles FILE and --joined-vcf FILE, as those two
+FILE *g_joined_vcf = nullptr, *g_joined_vcf_lines = nullptr;
+std::string g_joined_vcf_contigs;
 bool g_pile_bad = false;
 unsigned long long g_over_error = 0, g_over_depth = 0;     // records --max-error / --max-depth left out, all batches (under g_tmu)
 bool g_timing = false;                                    // PBDAGCON_TIMING=1: where the wall time of the run went, on stderr (seconds)
@@ -609,7 +642,10 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
     if (o.want_sr() && !ok(ctx, dagcon_fetch_site_reads(ctx, &sr), "site reads")) return 1;
     dagcon_site_alleles sa;
     memset(&sa, 0, sizeof sa);
-    if (o.al.on() && !ok(ctx, dagcon_fetch_site_alleles(ctx, &sa), "site alleles")) return 1;
+    if (o.want_al() && !ok(ctx, dagcon_fetch_site_alleles(ctx, &sa), "site alleles")) return 1;
+    dagcon_joined_sites js;
+    memset(&js, 0, sizeof js);
+    if (o.jn.on() && !ok(ctx, dagcon_fetch_joined_sites(ctx, &js), "joined sites")) return 1;
     uint64_t sr_x = 0;                                      // (aln_tgt ascends: one walk over the taken alignments)
     const char *nonconforming = o.mode == MODE_RECORDS ? dg_kind(o.kind).nonconforming : "an alignment leaves the backbone or holds a non-printable byte";
     for (uint32_t g = 0; g < r.n_targets; g++) {
@@ -634,6 +670,11 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
             const char *tb = o.mode == MODE_RECORDS ? b.t.data() + b.toff[g] : nullptr;
             if (!o.al.vcf.empty()) dg_vcf_contig(b.site_contigs, b.ids[g], b.tlen[g]);
             dg_site_allele_lines(o.al.alleles.empty() ? nullptr : &b.site_alleles, o.al.vcf.empty() ? nullptr : &b.site_vcf, b.ids[g], ps, sa, g, tb, b.tlen[g], o.pile.min_count);
+        }
+        if (o.jn.on()) {
+            const char *tb = o.mode == MODE_RECORDS ? b.t.data() + b.toff[g] : nullptr;
+            if (!o.jn.vcf.empty()) dg_vcf_contig(b.joined_contigs, b.ids[g], b.tlen[g]);
+            dg_joined_lines(o.jn.alleles.empty() ? nullptr : &b.joined_alleles, o.jn.vcf.empty() ? nullptr : &b.joined_vcf, b.ids[g], ps, sa, js, g, tb, b.tlen[g], o.pile.min_count);
         }
         if (r.target_status[g] != DAGCON_OK)
             fprintf(stderr, "pbdagcon: warning: target %s skipped (%s)\n", b.ids[g].c_str(), dg_status_text(r.target_status[g], nonconforming));
@@ -716,7 +757,7 @@ int run_records(dagcon_ctx *ctx, Batch &b, const Opts &o) {
     const int rc = dg_consensus_records(ctx, o.kind, ra, nullptr, &r);
     if (g_timing) fprintf(stderr, "pbdagcon timing: %s%s batch of %zu records: %s %.3f\n", dg_kind(o.kind).flag, o.pick.text().c_str(), b.start.size(), dg_kind(o.kind).entry, wall() - t0);
     if (!ok(ctx, rc, "consensus")) return 1;
-    if (dg_kind_md(o.kind) && (o.want_edits() || o.pile.on() || o.al.on())) {   // REF of the edits, of the pile-up lines and of the alleles' lines and records: the targets as the device rebuilt them, in b.t's layout
+    if (dg_kind_md(o.kind) && (o.want_edits() || o.pile.on() || o.want_al())) {   // REF of the edits, of the pile-up lines and of the alleles' lines and records: the targets as the device rebuilt them, in b.t's layout
         const char *tb = nullptr;
         uint64_t tn = 0;
         if (!ok(ctx, dagcon_fetch_md_targets(ctx, &tb, &tn), "rebuilt targets")) return 1;
@@ -937,7 +978,8 @@ struct Workers {
             const dagcon_site_reads_opts so = {o.want_phase() ? 1u : 0u, 0u};
             if ((rc = dagcon_set_site_reads(ctx, &so)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
         }
-        if (rc == DAGCON_OK && o.al.on() && (rc = dagcon_set_site_alleles(ctx, 1)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
+        if (rc == DAGCON_OK && o.want_al() && (rc = dagcon_set_site_alleles(ctx, 1)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
+        if (rc == DAGCON_OK && o.jn.on() && (rc = dagcon_set_site_join(ctx, 1)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
         if (rc == DAGCON_OK && o.hap.on()) {
             const dagcon_hap_opts ho = {o.hap.min_sites, o.hap.min_reads};
             if ((rc = dagcon_set_hap_consensus(ctx, &ho)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
@@ -988,6 +1030,8 @@ struct Workers {
                     if (g_hap_sites && fwrite(d->hap_sites.data(), 1, d->hap_sites.size(), g_hap_sites) != d->hap_sites.size()) g_pile_bad = true;
                     if (g_site_alleles && fwrite(d->site_alleles.data(), 1, d->site_alleles.size(), g_site_alleles) != d->site_alleles.size()) g_pile_bad = true;
                     if (g_site_vcf) { g_site_vcf_contigs += d->site_contigs; if (fwrite(d->site_vcf.data(), 1, d->site_vcf.size(), g_site_vcf_lines) != d->site_vcf.size()) g_pile_bad = true; }
+                    if (g_joined_alleles && fwrite(d->joined_alleles.data(), 1, d->joined_alleles.size(), g_joined_alleles) != d->joined_alleles.size()) g_pile_bad = true;
+                    if (g_joined_vcf) { g_joined_vcf_contigs += d->joined_contigs; if (fwrite(d->joined_vcf.data(), 1, d->joined_vcf.size(), g_joined_vcf_lines) != d->joined_vcf.size()) g_pile_bad = true; }
                     d->clear();
                     free_list.push_back(d);
                     print_seq++;
@@ -1491,20 +1535,30 @@ int main(int argc, char **argv) {
     if (!o.hap.sites.empty() && !(g_hap_sites = fopen(o.hap.sites.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.sites.c_str()); return 1; }
     if (!o.al.alleles.empty() && !(g_site_alleles = fopen(o.al.alleles.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.al.alleles.c_str()); return 1; }
     if (!o.al.vcf.empty() && (!(g_site_vcf = fopen(o.al.vcf.c_str(), "w")) || !(g_site_vcf_lines = tmpfile()))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.al.vcf.c_str()); return 1; }
+    if (!o.jn.alleles.empty() && !(g_joined_alleles = fopen(o.jn.alleles.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.jn.alleles.c_str()); return 1; }
+    if (!o.jn.vcf.empty() && (!(g_joined_vcf = fopen(o.jn.vcf.c_str(), "w")) || !(g_joined_vcf_lines = tmpfile()))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.jn.vcf.c_str()); return 1; }
     auto close_pile = [&](int status) {
+        // the header of a VCF, now that every target is known, then the records that waited
+        auto finish_vcf = [&](FILE *to, FILE *&lines, const std::string &head) {
+            bool wrote = fwrite(head.data(), 1, head.size(), to) == head.size();
+            rewind(lines);
+            char buf[65536];
+            for (size_t k; wrote && (k = fread(buf, 1, sizeof buf, lines)) > 0;) wrote = fwrite(buf, 1, k, to) == k;
+            if (!wrote || ferror(lines)) g_pile_bad = true;
+            fclose(lines); lines = nullptr;
+        };
         if (g_site_vcf) {
-            // the header, now that every target is known, then the records that waited
             std::string head;
             dg_site_vcf_header(head, g_site_vcf_contigs, o.want_phase());
-            bool wrote = fwrite(head.data(), 1, head.size(), g_site_vcf) == head.size();
-            rewind(g_site_vcf_lines);
-            char buf[65536];
-            for (size_t k; wrote && (k = fread(buf, 1, sizeof buf, g_site_vcf_lines)) > 0;) wrote = fwrite(buf, 1, k, g_site_vcf) == k;
-            if (!wrote || ferror(g_site_vcf_lines)) g_pile_bad = true;
-            fclose(g_site_vcf_lines); g_site_vcf_lines = nullptr;
+            finish_vcf(g_site_vcf, g_site_vcf_lines, head);
+        }
+        if (g_joined_vcf) {
+            std::string head;
+            dg_joined_vcf_header(head, g_joined_vcf_contigs, o.want_phase());
+            finish_vcf(g_joined_vcf, g_joined_vcf_lines, head);
         }
         const std::pair<FILE **, const std::string *> files[] = {{&g_pileup, &o.pile.pileup}, {&g_sites, &o.pile.sites}, {&g_site_reads, &o.sr.site_reads}, {&g_haplotag, &o.sr.haplotag},
-                                                                 {&g_site_alleles, &o.al.alleles}, {&g_site_vcf, &o.al.vcf},
+                                                                 {&g_site_alleles, &o.al.alleles}, {&g_site_vcf, &o.al.vcf}, {&g_joined_alleles, &o.jn.alleles}, {&g_joined_vcf, &o.jn.vcf},
                                                                  {&g_hap_out, &o.hap.consensus}, {&g_hap_sites, &o.hap.sites}};
         for (const auto &f : files) {
             if (!*f.first) continue;
@@ -1554,7 +1608,7 @@ int main(int argc, char **argv) {
         if (fclose(g_edits) != 0) { fprintf(stderr, "pbdagcon: error writing %s\n", o.edits.c_str()); status = 1; fast_exit = false; }
         if (o.verbose) fprintf(stderr, "pbdagcon: %llu edits written to %s\n", g_n_edits, o.edits.c_str());
     }
-    if (g_pileup || g_sites || g_site_reads || g_haplotag || g_hap_out || g_hap_sites || g_site_alleles || g_site_vcf) {
+    if (g_pileup || g_sites || g_site_reads || g_haplotag || g_hap_out || g_hap_sites || g_site_alleles || g_site_vcf || g_joined_alleles || g_joined_vcf) {
         const int ps = close_pile(0);
         if (ps) { status = ps; fast_exit = false; }
     }

@@ -1,6 +1,7 @@
-"""The carry of the one-block scan (csrc/k_scan.hip.h) behind the edits, the sites and the site entries: a round takes
-1,024 items, and the small batches of test_edits, test_edit_support, test_pileup and test_site_reads never reach a second
-one.  One record upload with all four outputs on, sized so that each of the three scans crosses its 1,024th item:
+"""The carry of the one-block scan (csrc/k_scan.hip.h) behind three of its eight users, the edits, the pile-up's tiles and
+the site entries (the other five, k_al_soff, k_al_tscan, k_jn_stretch, k_jn_runs and k_jn_tscan, are carried past their
+1,024th item by test_site_table_limits.py): a round takes 1,024 items, and the small batches of test_edits,
+test_edit_support, test_pileup and test_site_reads never reach a second one.  One record upload with all four outputs on, sized so that each of the three scans crosses its 1,024th item:
 
     k_ed_scan    an item is a target                  1,100 targets
     k_sr_scan    an item is an alignment              3,300 alignments

@@ -447,7 +447,7 @@ int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out);
  * label 2, by rule 7, with the tlen (and the backbone, if the first batch had one) of its target.  The strings are those
  * the first batch left on the device, whichever way they came in: none crosses the bus and none is copied.  It is an
  * upload like any other: the results of the first batch and dagcon_fetch_md_targets stop being valid, every optional
- * output (edits, edit support, pile-up, site reads, site alleles, joined sites, tally) is off for the derived batch and its fetch DAGCON_ERR_STATE,
+ * output (edits, edit support, pile-up, site reads, site alleles, joined sites, tally) is off for the derived batch and its fetch DAGCON_ERR_STATE (but for dagcon_set_hap_calls, rule 11 below),
  * the record filter has nothing to do, and a second dagcon_upload_haps in a row is DAGCON_ERR_STATE.  min_cov, min_len,
  * trim, min_weight and the context's flags (DAGCON_FLAG_BASE_SUPPORT / _BASE_POS with their fetches among them) hold as
  * for dagcon_upload; a group with fewer reads than min_weight lets few bases out, which is the caller's option to set as
@@ -625,6 +625,57 @@ typedef struct dagcon_window_phase {
     uint64_t n_sites; const int8_t *phase;    /* oriented; the sites of dagcon_fetch_pileup_sites, same order */
 } dagcon_window_phase;
 int dagcon_fetch_window_phase(dagcon_ctx *ctx, dagcon_window_phase *out);
+
+/*
+ * Hap calls: the edits of the two groups of a split target against their common target, and for every edit whether the
+ * other group carries it too (off by default; a context switch that needs dagcon_set_edits on).  The consensus of a group
+ * is the evidence: no likelihood, no limit on an allele's length.
+ * THIS BUILD'S OWN RULE, PARITY UNPINNED (the reference has no such output; tests/hap_calls_twin.py is its twin).
+ * 11. The derived targets of dagcon_upload_haps come in pairs: label 1 at an even d, label 2 at d ^ 1, both with the source
+ *     target src_target[d] (dagcon_fetch_hap_map).  With the switch in effect the derived batch reports its edits
+ *     (dagcon_fetch_edits, dagcon_fetch_positions; dagcon_fetch_edit_support iff the first batch ran with it) by the rules
+ *     of those fetches word for word, "target" read as "the source target (window) of the derived target": the edits
+ *     INVARIANT holds against the source target's bytes, and the support counts are over the group's alignments (the
+ *     unlabelled reads are in both groups, so the two groups' span may add up to more than the target's depth).
+ *     For an edit e = (t_pos, t_len, alt = seq_blob[c_off, c_off + c_len)) of derived target d, with d' = d ^ 1:
+ *     Occupied interval: o(e) = [t_pos, t_pos + max(t_len, 1)); a pure insertion occupies the base behind it.  Inside one
+ *     derived target the occupied intervals are disjoint and t_pos rises strictly over all of its segments (one edit per
+ *     gap between consecutive backbone bases, segments cut from one best path).
+ *     HOM (3):     d' has an edit with the same t_pos, t_len, c_len and the same alt bytes (exact bytes: case counts, as in
+ *                  the edits' trim); mate[e] is that edit.
+ *     CLASH (2):   otherwise, d' has an edit e' with o(e) and o(e') not disjoint; mate[e] is the lowest such e'.  (An
+ *                  insertion at p clashes with a substitution of [p, p + 1); substitutions of [p, p + 1) and
+ *                  [p + 1, p + 2) do not clash.)
+ *     HET (1):     otherwise, some segment of d' has t0' <= t_pos and t_pos + t_len <= t1': the partner's consensus is
+ *                  there and shows the target; mate = none.
+ *     NOCOVER (0): otherwise; all edits of a target whose partner failed (target_status != DAGCON_OK) or has no segment;
+ *                  mate = none.
+ *     HOM is tested first, then CLASH, then the cover.  HOM and CLASH are symmetric: mate[mate[e]] == e for HOM, and the
+ *     mate of a CLASH is itself CLASH.  Nothing in the rule depends on an order.
+ * dagcon_set_hap_calls: DAGCON_ERR_STATE unless dagcon_set_edits is on; turning the edits off turns it off.  The switch is
+ * read at dagcon_upload_haps and takes effect only when the first batch was a record upload (whole targets or windows) that
+ * ran with the edits.  In every other case (a string or dagcon_consensus_pre first batch, edits off at the first upload,
+ * the switch off) it is as if off: the derived batch runs with no optional output, exactly as described above, and no
+ * kernel, buffer, memset, launch or copy differs.  In effect, dagcon_upload_haps uploads 8 bytes a derived target (where
+ * its source target's bases lie in the record intake's target blob, which is still on the device) and k_hap_calls
+ * (csrc/k_hap_calls.hip.h) runs behind the edit kernels in every execution of the run.
+ * dagcon_fetch_hap_calls: the arrays (9 bytes an edit) are copied when it is called and brought from the device's edit
+ * order to that of dagcon_fetch_edits (failed targets drop out, mate is re-indexed).  A mate outside the partner's edits
+ * or a state above 3 is DAGCON_ERR_INTERNAL.  DAGCON_ERR_STATE wherever dagcon_fetch_edits is, when the switch did not take
+ * effect at dagcon_upload_haps, before the derived batch's dagcon_fetch, and after any later upload.  A derived batch of 0
+ * targets has n == 0.  Owned by the context, valid as long as the results of the same fetch.
+ */
+#define DAGCON_HC_NOCOVER 0
+#define DAGCON_HC_HET     1
+#define DAGCON_HC_CLASH   2
+#define DAGCON_HC_HOM     3
+int dagcon_set_hap_calls(dagcon_ctx *ctx, int on);
+typedef struct dagcon_hap_calls {
+    uint64_t n;              /* == dagcon_edits.n of the same fetch, same order */
+    const uint8_t  *state;   /* [n] DAGCON_HC_* */
+    const uint64_t *mate;    /* [n] index into the same arrays; UINT64_MAX: none */
+} dagcon_hap_calls;
+int dagcon_fetch_hap_calls(dagcon_ctx *ctx, dagcon_hap_calls *out);
 
 /*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses

@@ -50,7 +50,10 @@ EXPORTS = [
     "dagcon_set_hap_consensus", "dagcon_fetch_hap_tally", "dagcon_upload_haps", "dagcon_fetch_hap_map",
     "dagcon_upload_cigar_md", "dagcon_consensus_cigar_md", "dagcon_fetch_md_targets",
     "dagcon_set_window_phase", "dagcon_fetch_window_phase",
+    "dagcon_set_hap_calls", "dagcon_fetch_hap_calls",
 ]
+HC_NOCOVER, HC_HET, HC_CLASH, HC_HOM = 0, 1, 2, 3
+HC_NONE = 0xFFFFFFFFFFFFFFFF
 ABI_VERSION = 2
 
 
@@ -217,6 +220,10 @@ class HapMap(C.Structure):
                 ("aln_begin", C.POINTER(C.c_uint64)), ("aln_src", C.POINTER(C.c_uint64))]
 
 
+class HapCalls(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("state", C.POINTER(C.c_uint8)), ("mate", C.POINTER(C.c_uint64))]
+
+
 class Edits(C.Structure):
     """dagcon_edits: per segment its target span and its edits (include/dagcon.h has the definition)."""
     _fields_ = [("n_segments", C.c_uint64), ("n", C.c_uint64), ("seg_t0", C.POINTER(C.c_uint32)),
@@ -314,6 +321,8 @@ def load() -> C.CDLL:
     L.dagcon_fetch_hap_map.argtypes = [vp, C.POINTER(HapMap)]
     L.dagcon_set_window_phase.argtypes = [vp, C.POINTER(WindowPhaseOpts)]
     L.dagcon_fetch_window_phase.argtypes = [vp, C.POINTER(WindowPhase)]
+    L.dagcon_set_hap_calls.argtypes = [vp, C.c_int]
+    L.dagcon_fetch_hap_calls.argtypes = [vp, C.POINTER(HapCalls)]
     L.dagcon_upload_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int]
     L.dagcon_consensus_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int,
                                             C.POINTER(Results)]
@@ -1094,6 +1103,21 @@ class Context:
                 "label": np.ctypeslib.as_array(hm.label, shape=(T,)).copy() if T else np.zeros(0, np.uint8),
                 "aln_begin": begin,
                 "aln_src": np.ctypeslib.as_array(hm.aln_src, shape=(n,)).copy() if n else np.zeros(0, np.uint64)}
+
+    def set_hap_calls(self, on=True):
+        """dagcon_set_hap_calls (needs set_edits on): the batch upload_haps() derives from a record upload that ran with
+        the edits reports its own edits (and their support, if the first batch had it) and pairs the two groups' edits
+        (hap_calls())."""
+        self._chk(self.L.dagcon_set_hap_calls(self.h, 1 if on else 0))
+
+    def hap_calls(self) -> dict:
+        """dagcon_fetch_hap_calls (copies): per edit of edits() its state (uint8: HC_NOCOVER, HC_HET, HC_CLASH, HC_HOM) and
+        its mate (uint64 index into the same arrays, HC_NONE: none)."""
+        hc = HapCalls()
+        self._chk(self.L.dagcon_fetch_hap_calls(self.h, C.byref(hc)))
+        n = int(hc.n)
+        return {"state": np.ctypeslib.as_array(hc.state, shape=(n,)).copy() if n else np.zeros(0, np.uint8),
+                "mate": np.ctypeslib.as_array(hc.mate, shape=(n,)).copy() if n else np.zeros(0, np.uint64)}
 
     def set_window_phase(self, min_links=0, max_conflict_ppm=0):
         """dagcon_set_window_phase for every later windows upload made with set_pileup and set_site_reads(True) on: the

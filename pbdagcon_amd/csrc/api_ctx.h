@@ -104,7 +104,8 @@ struct RunBufs {
     // member's place, then its joined allele's index; the stretches (keys, counts, counts per label, the places' indices);
     // the compact tables (sized and filled at the fetch); the three totals
     DevBuf jn_run, jn_sfirst, jn_rbeg, jn_cur, jn_nd, jn_deep, jn_toff, jn_key, jn_tcnt, jn_thap, jn_map, jn_idx, jn_ckey, jn_ccnt, jn_chap, jn_tot;
-    std::array<DevBuf *, 110> all() {
+    DevBuf hc_state, hc_mate;                       // dagcon_set_hap_calls: a state byte and a mate index per edit, parallel to ed_out
+    std::array<DevBuf *, 112> all() {
         return {&nmis, &n_lo, &n_hi, &n_start, &n_ins, &n_del, &ch_k0, &ch_next, &ch_w, &ch_tb, &ch_flag, &ch_src, &ch_out, &ch_adv, &n_lb, &norm_tmp, &ckpt,
                 &node_base, &n_nodes, &pool_base, &pool_size, &pool_top, &t_nins, &cov, &gcount, &gbase, &bid, &best, &queue, &score, &cns_tmp, &bp_tt,
                 &stk, &cuts, &cuts_bp, &bp_stat, &bp_len, &rd, &pro_state, &sh_cnt, &wl_first, &queue0, &bp_end, &bp_ab, &defer, &cns_tmp0, &cns,
@@ -112,10 +113,11 @@ struct RunBufs {
                 &sr_bits, &sr_rank, &sr_cnt, &sr_off, &sr_site, &sr_code, &sr_hap, &sr_sigma, &sr_kind, &sr_acc, &sr_nz,
                 &hap_cnt, &hap_rec, &wl_cnt, &wl_block, &wl_flip, &wl_hap, &wl_phase,
                 &al_map, &al_idx, &al_soff, &al_cur, &al_nd, &al_deep, &al_toff, &al_srt, &al_tcnt, &al_thap, &al_ckey, &al_ccnt, &al_chap, &al_tot,
-                &jn_run, &jn_sfirst, &jn_rbeg, &jn_cur, &jn_nd, &jn_deep, &jn_toff, &jn_key, &jn_tcnt, &jn_thap, &jn_map, &jn_idx, &jn_ckey, &jn_ccnt, &jn_chap, &jn_tot};
+                &jn_run, &jn_sfirst, &jn_rbeg, &jn_cur, &jn_nd, &jn_deep, &jn_toff, &jn_key, &jn_tcnt, &jn_thap, &jn_map, &jn_idx, &jn_ckey, &jn_ccnt, &jn_chap, &jn_tot,
+                &hc_state, &hc_mate};
     }
 };
-static_assert(sizeof(RunBufs) == 110 * sizeof(DevBuf), "RunBufs::all() must name every member");
+static_assert(sizeof(RunBufs) == 112 * sizeof(DevBuf), "RunBufs::all() must name every member");
 // ArenaBufs: the arenas with a treatment of their own -- matC is cleared before every run, the others are filled under
 // DAGCON_POISON bits 1 (matA, matD), 2 (nodes, pool) and 4 (score_b, norm)
 struct ArenaBufs {
@@ -166,6 +168,15 @@ struct Output {
 struct EditsOut {
     std::vector<uint32_t> t0, t1, tpos, tlen, clen, w_begin, w_end, span, alt, ref;
     std::vector<uint64_t> begin, coff;
+    // dagcon_set_hap_calls only: each listed edit's index on the device, where each target's listed edits begin [T + 1],
+    // and the edits of the device
+    std::vector<uint64_t> dev_idx, tgt_begin;
+    uint64_t n_dev = 0;
+};
+// dagcon_fetch_hap_calls: per edit of dagcon_fetch_edits its state and its mate
+struct HapCallsOut {
+    std::vector<uint8_t> state;
+    std::vector<uint64_t> mate;
 };
 // dagcon_fetch_pileup_sites: where a target's sites begin, each site's position and counts; and the site map of the other
 // fetches -- where a target's sites begin in the device's list (begin: in the host's), and that list's length
@@ -314,7 +325,10 @@ struct Ctx {
     Output o_wl{"without the results of a windows upload made with dagcon_set_pileup, dagcon_set_site_reads (phase on) and dagcon_set_window_phase on (a "
                 "switch off at the upload, no windows, no fetch yet, or stopped before bestPath)"};
     dagcon_window_phase_opts wl_opts = {0u, 0u}, wl_batch_opts = {0u, 0u};
-    std::array<Output *, 8> outputs() { return {&o_ed, &o_evid, &o_pile, &o_sr, &o_al, &o_jn, &o_hap, &o_wl}; }
+    // dagcon_set_hap_calls (on only while edits are; latched for the batch of dagcon_upload_haps alone)
+    Output o_hc{"without the results of a dagcon_upload_haps made with dagcon_set_hap_calls on behind a record upload that ran with dagcon_set_edits on (a "
+                "switch off, another kind of first upload, no fetch yet, or stopped before bestPath)"};
+    std::array<Output *, 9> outputs() { return {&o_ed, &o_evid, &o_pile, &o_sr, &o_al, &o_jn, &o_hap, &o_wl, &o_hc}; }
     // the growing arenas: run.ed_out (and run.evid beside it), run.pile_site, run.sr_site / sr_code.  The status block
     // holds 16 bytes for the edits' total, then 16 for the sites', whose second word is the entries'
     GrowArena ed_arena{"edits", DG_E_ED_OVF, true, &DgParams::ed_top, &DgParams::ed_cap};
@@ -356,6 +370,7 @@ struct Ctx {
     JoinedOut r_joined;
     HapOut r_haps;
     WinPhaseOut r_winphase;
+    HapCallsOut r_hc;
     HapMapOut r_hapmap;
     HostOrder order;
     bool sup_valid = false;             // r_sup holds the support of the results of the last fetch

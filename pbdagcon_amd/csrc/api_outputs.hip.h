@@ -1,5 +1,5 @@
 // api_outputs.hip.h -- the optional outputs of a run (edits and their support, the pile-up and its sites, the reads at the
-// sites, the window phase, the alleles, the joined sites, the haplotype tally), each one's host side in one place: its room, its kernel
+// sites, the window phase, the alleles, the joined sites, the haplotype tally, the hap calls), each one's host side in one place: its room, its kernel
 // parameters, its launches, its part of the fetch and its dagcon_set_* / dagcon_fetch_* entry points.  The pipeline
 // (api_run.hip.h) calls outputs_room, outputs_params, outputs_launch, outputs_upload and the outputs_plan / _copies /
 // _unpack steps of dagcon_fetch, at the end of this file; DESIGN.md says how to add an output.  (The entry points stand
@@ -12,10 +12,19 @@ namespace {
 // The dependency rule, once: which outputs the batch being uploaded runs with, and with which options (defaults filled
 // in).  Edits need a record upload and their support needs edits; the sites need the pile-up; the reads at the sites need
 // the sites; the alleles, the tally and the window phase need those reads, the last two with phase on; the window phase
-// needs a windows upload; the joined sites need the alleles.  The batch of dagcon_upload_haps runs with none, whatever the switches say.
+// needs a windows upload; the joined sites need the alleles.  The batch of dagcon_upload_haps runs with none, whatever the
+// switches say -- unless dagcon_set_hap_calls is on and the batch it derives from ran with the edits latched (a record
+// upload, then: cg.t still holds its targets): then it runs with the edits, with their support iff that batch did, and
+// with the pairing of the two groups' edits.
 void latch_outputs(Ctx *c, const Intake kind) {
+    const bool had_ed = c->o_ed.batch, had_evid = c->o_evid.batch;
     for (Output *o : c->outputs()) o->batch = false;
-    if (kind == Intake::HAPS) return;
+    if (kind == Intake::HAPS) {
+        c->o_hc.batch = c->o_hc.on && c->o_ed.on && had_ed;
+        c->o_ed.batch = c->o_hc.batch;
+        c->o_evid.batch = c->o_hc.batch && had_evid;
+        return;
+    }
     c->o_ed.batch = c->o_ed.on && kind != Intake::STRINGS;
     c->o_evid.batch = c->o_evid.on && c->o_ed.batch;
     c->o_pile.batch = c->o_pile.on;
@@ -130,7 +139,10 @@ int edits_unpack(Ctx *c, const FetchPlan &f) {
     const DgEvid *m_evid = reinterpret_cast<const DgEvid *>(m_edb + f.ed_bytes);
     EditsOut &o = c->r_edits;
     o = EditsOut();
+    const bool calls = c->o_hc.batch;                 // dagcon_fetch_hap_calls brings its arrays into this order
+    o.n_dev = f.n_ed;
     for (uint32_t t = 0; t < c->T; t++) {
+        if (calls) o.tgt_begin.push_back(o.tpos.size());
         if (!c->h_tactive[t] || m_tfail[t]) continue;
         for (uint32_t i = 0; i < m_n_seg[t]; i++) {
             const uint64_t s = m_seg_first[t] + i;
@@ -142,6 +154,7 @@ int edits_unpack(Ctx *c, const FetchPlan &f) {
             for (uint32_t k = 0; k < es.cnt; k++) {
                 const DgEdit &e = m_ed[es.off + k];
                 o.tpos.push_back(e.t_pos); o.tlen.push_back(e.t_len); o.coff.push_back(e.c_off); o.clen.push_back(e.c_len);
+                if (calls) o.dev_idx.push_back(es.off + k);
                 if (f.want_evid) {
                     const DgEvid &v = m_evid[es.off + k];
                     o.w_begin.push_back(v.gL); o.w_end.push_back(v.gR);
@@ -151,6 +164,7 @@ int edits_unpack(Ctx *c, const FetchPlan &f) {
         }
     }
     o.begin.push_back(o.tpos.size());
+    if (calls) o.tgt_begin.push_back(o.tpos.size());
     return DAGCON_OK;
 }
 
@@ -162,7 +176,7 @@ int dagcon_set_edits(dagcon_ctx *ctx, int on) {
     if (!(c->opts.flags & DAGCON_FLAG_BASE_POS))
         return fail(c, DAGCON_ERR_STATE, "dagcon_set_edits on a context created without DAGCON_FLAG_BASE_POS");
     c->o_ed.on = on != 0;
-    if (!c->o_ed.on) c->o_evid.on = false;
+    if (!c->o_ed.on) c->o_evid.on = c->o_hc.on = false;
     return DAGCON_OK;
 }
 
@@ -799,6 +813,8 @@ int dagcon_fetch_joined_sites(dagcon_ctx *ctx, dagcon_joined_sites *out) {
 // ---- the tally of the split, and the batch of the groups (k_hap.hip.h) ----
 namespace {
 
+int calls_arm(Ctx *c, const std::vector<uint32_t> &src_target);      // dagcon_set_hap_calls, below: its part of dagcon_upload_haps
+
 int hap_room(Ctx *c) {
     if (!c->o_hap.batch) return DAGCON_OK;
     ENSURE(c, c->run.hap_cnt, c->site_arena.cap * 8); ENSURE(c, c->run.hap_rec, (size_t)c->T * DG_HAP_REC * 4);
@@ -917,6 +933,7 @@ int dagcon_upload_haps(dagcon_ctx *ctx) {
     if (c->have_bb) { db.backbone = c->in.bb.as<const char>(); db.backbone_off = bb_off.data(); }    // (in.bb itself: nothing is copied)
     // an upload like any other, but one that latches no optional output (Intake::HAPS); the switches stay as the caller set them
     if ((r = upload_impl(ctx, &db, c->in.q.p, c->in.t.p, Intake::HAPS))) return r;   // (as after any failed upload: the first batch's results are gone)
+    if ((r = calls_arm(c, src_target))) return r;
     pad(src_target, label, src);
     HapMapOut &m = c->r_hapmap;
     m.src_target.swap(src_target); m.label.swap(label); m.aln_begin.swap(begin); m.aln_src.swap(src);
@@ -935,24 +952,104 @@ int dagcon_fetch_hap_map(dagcon_ctx *ctx, dagcon_hap_map *out) {
     return DAGCON_OK;
 }
 
+// ---- the two groups' edits paired (k_hap_calls.hip.h) ----
+namespace {
+
+int calls_room(Ctx *c) {
+    if (!c->o_hc.batch) return DAGCON_OK;
+    ENSURE(c, c->run.hc_state, c->ed_arena.cap); ENSURE(c, c->run.hc_mate, c->ed_arena.cap * 8);
+    return DAGCON_OK;
+}
+
+void calls_params(Ctx *c, DgParams &p) {
+    if (!c->o_hc.batch) return;
+    p.hc_state = c->run.hc_state.as<uint8_t>(); p.hc_mate = c->run.hc_mate.as<unsigned long long>();
+}
+
+// behind the edit kernels, in every execution of the run (a re-run after DG_E_ED_OVF included): a wave per derived target
+void calls_launch(Ctx *c, const DgParams &p) {
+    if (!c->o_hc.batch || !c->T) return;
+    hipLaunchKernelGGL(k_hap_calls, dim3((c->T + 3) / 4), dim3(256), 0, c->stream, p);
+}
+
+// dagcon_upload_haps, behind its upload_impl: a derived target's bases are its source target's (a window's) in cg.t
+int calls_arm(Ctx *c, const std::vector<uint32_t> &src_target) {
+    if (!c->o_ed.batch) return DAGCON_OK;
+    std::vector<uint64_t> tbase(src_target.size());
+    for (size_t d = 0; d < tbase.size(); d++) tbase[d] = c->h_ed_tbase[src_target[d]];
+    c->h_ed_tbase.swap(tbase);
+    UPLOAD(c, c->in.ed_tbase, c->h_ed_tbase);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DAGCON_OK;
+}
+
+}  // namespace
+
+int dagcon_set_hap_calls(dagcon_ctx *ctx, int on) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c->o_ed.on) return fail(c, DAGCON_ERR_STATE, "dagcon_set_hap_calls without dagcon_set_edits on");
+    c->o_hc.on = on != 0;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_hap_calls(dagcon_ctx *ctx, dagcon_hap_calls *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (int r = need(c, c->o_hc, "dagcon_fetch_hap_calls", c->o_ed.on)) return r;
+    HapCallsOut &o = c->r_hc;
+    if (!c->o_hc.fetched) {
+        // the copies dagcon_fetch left out (9 bytes an edit), and the device's arrays in the order of dagcon_fetch_edits: a
+        // failed target's edits go, as in edits_unpack, and a mate becomes an index into the listed edits
+        HIPCHK(c, hipSetDevice(c->device));
+        const EditsOut &e = c->r_edits;
+        const uint64_t nd = e.n_dev, n = e.dev_idx.size();
+        const uint32_t T = c->T;
+        std::vector<uint8_t> state((size_t)nd);
+        std::vector<uint64_t> mate((size_t)nd), host_of((size_t)nd, UINT64_MAX);
+        if (nd) { HIPCHK(c, d2h(c, state.data(), c->run.hc_state.p, (size_t)nd)); HIPCHK(c, d2h(c, mate.data(), c->run.hc_mate.p, (size_t)nd * 8)); }
+        for (uint64_t i = 0; i < n; i++) host_of[e.dev_idx[i]] = i;
+        o.state.assign((size_t)n + 1, 0); o.mate.assign((size_t)n + 1, UINT64_MAX);
+        for (uint32_t d = 0; d < T; d++) {
+            // the partner's stretch of the listed edits: empty when it failed or there is none
+            const uint32_t dp = d ^ 1u;
+            const uint64_t q0 = dp < T ? e.tgt_begin[dp] : 0, q1 = dp < T ? e.tgt_begin[dp + 1] : 0;
+            for (uint64_t i = e.tgt_begin[d]; i < e.tgt_begin[d + 1]; i++) {
+                const uint64_t x = e.dev_idx[i];
+                const uint64_t m = mate[x] < nd ? host_of[mate[x]] : UINT64_MAX;
+                const bool paired = state[x] == DAGCON_HC_CLASH || state[x] == DAGCON_HC_HOM;
+                if (state[x] > DAGCON_HC_HOM || (mate[x] != UINT64_MAX && (m < q0 || m >= q1)) || paired != (m != UINT64_MAX))
+                    return fail(c, DAGCON_ERR_INTERNAL, "k_hap_calls: edit %llu of derived target %u has state %u and mate %llu (the partner's edits are [%llu, %llu))",
+                                (unsigned long long)(i - e.tgt_begin[d]), d, state[x], (unsigned long long)m, (unsigned long long)q0, (unsigned long long)q1);
+                o.state[i] = state[x]; o.mate[i] = m;
+            }
+        }
+        c->o_hc.fetched = true;
+    }
+    out->n = o.state.size() - 1;
+    out->state = o.state.data(); out->mate = o.mate.data();
+    return DAGCON_OK;
+}
+
 // ---- the pipeline's calls: every output in the order of its launches ----
 namespace {
 
 int outputs_room(Ctx *c) {
     int r;
     if ((r = edits_room(c)) || (r = pile_room(c)) || (r = reads_room(c)) || (r = hap_room(c)) || (r = winphase_room(c))) return r;
-    if ((r = alleles_room(c))) return r;
+    if ((r = alleles_room(c)) || (r = calls_room(c))) return r;
     return join_room(c);
 }
 
 void outputs_params(Ctx *c, DgParams &p) {
-    edits_params(c, p); pile_params(c, p); reads_params(c, p); hap_params(c, p); winphase_params(c, p); alleles_params(c, p); join_params(c, p);
+    edits_params(c, p); pile_params(c, p); reads_params(c, p); hap_params(c, p); winphase_params(c, p); alleles_params(c, p); join_params(c, p); calls_params(c, p);
 }
 
 // between k_bp_join and the last event of a run that goes as far as bestPath (T > 0)
 int outputs_launch(Ctx *c, const DgParams &p) {
     int r;
     edits_launch(c, p);
+    calls_launch(c, p);
     if ((r = pile_launch(c, p)) || (r = reads_launch(c, p))) return r;
     winphase_launch(c, p);
     if ((r = alleles_launch(c, p)) || (r = join_launch(c, p))) return r;

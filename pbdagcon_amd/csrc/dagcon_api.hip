@@ -36,6 +36,7 @@
 #include "k_pileup.hip.h"
 #include "k_site_reads.hip.h"
 #include "k_hap.hip.h"
+#include "k_hap_calls.hip.h"
 #include "k_alleles.hip.h"
 #include "k_join.hip.h"
 #include "k_winlink.hip.h"

@@ -300,6 +300,10 @@ struct DgParams {
     unsigned long long *jn_ckey;   // [*jn_top, at the fetch] the tables, run after run: key, count, c1 | c2 << 16
     uint32_t *jn_ccnt, *jn_chap;
     unsigned long long *jn_st_top, *jn_run_top, *jn_top;   // the stretches, the runs, the joined alleles of the batch (words of their own, fetched when asked)
+    // ---- the two groups' edits paired (dagcon_set_hap_calls on the batch of dagcon_upload_haps; NULL otherwise):
+    // k_hap_calls.hip.h.  Last, so that every field above keeps its offset ----
+    uint8_t *hc_state;             // [ed_cap] parallel to ed_out: DG_HC_*
+    unsigned long long *hc_mate;   // [ed_cap] parallel to ed_out: the partner's edit (index into ed_out), all ones: none
 };
 #define DG_HAP_REC 8u
 #define DG_SR_TAKEN 0x80000000u

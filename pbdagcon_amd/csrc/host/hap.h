@@ -11,12 +11,12 @@
 
 #include "../../../include/dagcon.h"
 
-// --hap-consensus FILE, --hap-sites FILE [--hap-min-sites N] [--hap-min-reads N]
+// --hap-consensus FILE, --hap-sites FILE, --hap-vcf FILE (hap_vcf.h) [--hap-min-sites N] [--hap-min-reads N]
 struct DgHapOpts {
-    std::string consensus, sites;
+    std::string consensus, sites, vcf;
     unsigned min_sites = 0, min_reads = 0;      // 0: the library's defaults
     bool sites_set = false, reads_set = false;
-    bool on() const { return !consensus.empty() || !sites.empty(); }
+    bool on() const { return !consensus.empty() || !sites.empty() || !vcf.empty(); }
 };
 
 inline void dg_hap_target_line(std::string &out, const std::string &rname, uint32_t n1, uint32_t n2, uint32_t n0, uint32_t n_sep, uint32_t agree,

@@ -56,6 +56,7 @@
 #include "alleles.h"
 #include "joined.h"
 #include "hap.h"
+#include "hap_vcf.h"
 
 namespace {
 
@@ -72,11 +73,12 @@ struct Opts {
     DgPick pick;                       // --max-error F, --max-depth N (MODE_RECORDS): the records are picked on the device
     std::string edits;                 // --edits FILE (MODE_RECORDS): where every record differs from its target
     std::string vcf;                   // --vcf FILE (MODE_RECORDS, whole targets): the edits as VCF with the reads behind each
-    bool want_edits() const { return !edits.empty() || !vcf.empty(); }
+    bool want_edits() const { return !edits.empty() || !vcf.empty() || !hap.vcf.empty(); }
+    bool want_edit_support() const { return !vcf.empty() || !hap.vcf.empty(); }   // (--hap-vcf FILE: the edits with their support, for both runs)
     DgPileOpts pile;                   // --pileup FILE, --sites FILE [--site-min-frac F] [--site-min-count N] (every mode): what the alignments show per position
     DgWinPhaseOpts wp;                 // --phase-windows [--phase-min-links N] [--phase-max-conflict F]: --site-reads / --haplotag with --window, the windows' labels joined (windows.h)
     DgSiteReadOpts sr;                 // --site-reads FILE, --haplotag FILE (whole targets, not -a): which read shows which allele at the sites; a two-way split
-    DgHapOpts hap;                     // --hap-consensus FILE, --hap-sites FILE (where --haplotag goes): a consensus per group of the split, the split's tally
+    DgHapOpts hap;                     // --hap-consensus FILE, --hap-sites FILE (where --haplotag goes): a consensus per group of the split, the split's tally; --hap-vcf FILE (records): the groups' edits paired
     DgAlleleOpts al;                   // --site-alleles FILE, --site-vcf FILE (where --site-reads goes): the alleles themselves at the sites, counted
     DgJoinedOpts jn;                   // --joined-alleles FILE, --joined-vcf FILE (where --site-alleles / --site-vcf go): adjacent sites joined into one record
     bool want_al() const { return al.on() || jn.on(); }               // (the joined sites need the alleles, whether or not their files are asked for)
@@ -97,7 +99,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [--site-alleles FILE] [--site-vcf FILE] [--joined-alleles FILE] [--joined-vcf FILE] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [--site-alleles FILE] [--site-vcf FILE] [--joined-alleles FILE] [--joined-vcf FILE] [--hap-vcf FILE] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -246,8 +248,8 @@ void usage(FILE *f) {
             "                      between this target base and the next: its bases, - for none (a deleted base), so a\n"
             "                      substitution reads as the new base and an insertion as the kept base and the inserted ones; a\n"
             "                      trailing + says more than 20 bases (alleles that agree in the first 20 count as one).  H1 H2 H0\n"
-            "                      are the COUNT reads by their group of the split, . unless --haplotag, --hap-consensus or\n"
-            "                      --hap-sites is given.  Counted on the GPU; stdout does not change.  This build's own rule; the\n"
+            "                      are the COUNT reads by their group of the split, . unless --haplotag, --hap-consensus,\n"
+            "                      --hap-sites or --hap-vcf is given.  Counted on the GPU; stdout does not change.  This build's own rule; the\n"
             "                      reference has no such output\n"
             "  --site-vcf FILE     with --sam, --bam or --paf: the same tables as VCFv4.2, one record per site that has an ALT:\n"
             "                      RNAME POS . REF ALT . . DP=depth;AD=ref,alt1,..  (and AD1=..;AD2=.. per group with the split on).\n"
@@ -271,6 +273,19 @@ void usage(FILE *f) {
             "                      run at position 1; a run that covers its whole target has no record).  Shared leading and\n"
             "                      trailing bases of REF and ALT are NOT trimmed.  No genotype is called\n"
             "  -v, --verbose       per-target progress on stderr\n"
+            "  --hap-vcf FILE      with --sam, --bam or --paf, where --hap-consensus goes: diploid calls from the two groups' consensus,\n"
+            "                      VCFv4.2 with one sample.  A target that is not split lists the edits of its consensus as\n"
+            "                      RNAME POS . REF ALT . . PAIR=UNSPLIT;DP=span;AD=ref,alt GT 1/1.  A split target lists the edits\n"
+            "                      of its two groups against the target, merged by position, GT:PS group 1 | group 2 with PS 1:\n"
+            "                      PAIR=HOM 1|1 when both groups' consensus carry the same edit (written once), PAIR=HET 1|0 or 0|1\n"
+            "                      when one does and the other covers the place, PAIR=CLASH 1|. and .|1 when the other carries a\n"
+            "                      different edit that touches it (two records, not one 1|2), PAIR=NOCOV 1|. or .|1 when the other\n"
+            "                      group has no consensus there; DP1=;AD1= and DP2=;AD2= are the read support in the edit's own\n"
+            "                      group (unlabelled reads are in both).  Insertions and deletions are anchored as in --vcf; REF\n"
+            "                      and ALT are not normalised and an allele has no length limit.  Turns on what it needs (the\n"
+            "                      pile-up, the split, the second run, the edits and their support); the pairing runs on the GPU;\n"
+            "                      stdout and every other file do not change.  Honours --site-min-*, --hap-min-*, --max-error and\n"
+            "                      --max-depth.  Not with --window, -a, --polish.  This build's own rule, parity unpinned\n"
             "  --polish N          with -a: N more rounds, each with the previous round's consensus as the backbone the reads\n"
             "                      are re-aligned to (README.md:14-15 of the reference: 'the new consensus can be used as a new\n"
             "                      backbone sequence to iteratively improve the consensus quality')\n"
@@ -364,6 +379,10 @@ int parse_args(int argc, char **argv, Opts &o) {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --hap-sites needs a file name\n"); return 2; }
             o.hap.sites = argv[++i];
         }
+        else if (a == "--hap-vcf") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --hap-vcf needs a file name\n"); return 2; }
+            o.hap.vcf = argv[++i];
+        }
         else if (a == "--hap-min-sites") { if (!need(&o.hap.min_sites)) return 2; o.hap.sites_set = true; }
         else if (a == "--hap-min-reads") { if (!need(&o.hap.min_reads)) return 2; o.hap.reads_set = true; }
         else if (a == "--site-min-frac") {
@@ -446,6 +465,7 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (!o.vcf.empty() && o.dump) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --dump-parsed (nothing is run, the file would not be written)\n"); return 2; }
     if (!o.vcf.empty() && o.window) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --window (the stitch splits and fuses edits: a fused edit has no single count)\n"); return 2; }
     if ((o.pile.frac_set || o.pile.count_set) && o.pile.sites.empty() && !o.want_sr()) { fprintf(stderr, "PARSE ERROR: --site-min-frac and --site-min-count need --sites\n"); return 2; }
+    if (!o.hap.vcf.empty() && !records) { fprintf(stderr, "PARSE ERROR: --hap-vcf needs --sam, --bam or --paf (REF comes from the target's bases)\n"); return 2; }
     if ((o.hap.sites_set || o.hap.reads_set) && !o.hap.on()) { fprintf(stderr, "PARSE ERROR: --hap-min-sites and --hap-min-reads need --hap-consensus or --hap-sites\n"); return 2; }
     if (o.hap.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
     if (o.hap.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
@@ -553,9 +573,10 @@ struct Batch {
     std::vector<std::string> qnames;   // --site-reads, --haplotag: the records' read names (the input's pages may be gone by the time they are written)
     std::string site_reads, haplotag;  // and the batch's lines of those files
     std::string hap_out, hap_sites;    // --hap-consensus, --hap-sites: the batch's records and lines of those files
+    std::string hap_vcf, hap_contigs;  // --hap-vcf: the batch's lines of that file, and its targets' ##contig lines
     std::string site_alleles, site_vcf, site_contigs;   // --site-alleles, --site-vcf: the batch's lines of those files, and its targets' ##contig lines
     std::string joined_alleles, joined_vcf, joined_contigs;   // --joined-alleles, --joined-vcf: the same
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); hap_out.clear(); hap_sites.clear(); site_alleles.clear(); site_vcf.clear(); site_contigs.clear(); joined_alleles.clear(); joined_vcf.clear(); joined_contigs.clear(); }
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); hap_out.clear(); hap_sites.clear(); hap_vcf.clear(); hap_contigs.clear(); site_alleles.clear(); site_vcf.clear(); site_contigs.clear(); joined_alleles.clear(); joined_vcf.clear(); joined_contigs.clear(); }
 };
 
 FILE *g_edits = nullptr;                                  // --edits FILE, written batch by batch in output order
@@ -568,6 +589,8 @@ bool g_vcf_bad = false;
 FILE *g_pileup = nullptr, *g_sites = nullptr;              // --pileup FILE, --sites FILE, written batch by batch in output order
 FILE *g_site_reads = nullptr, *g_haplotag = nullptr;       // --site-reads FILE, --haplotag FILE, the same way
 FILE *g_hap_out = nullptr, *g_hap_sites = nullptr;         // --hap-consensus FILE, --hap-sites FILE, the same way
+FILE *g_hap_vcf = nullptr, *g_hap_vcf_lines = nullptr;     // --hap-vcf FILE, as --site-vcf below: the records wait in an unnamed temporary file
+std::string g_hap_vcf_contigs;
 FILE *g_site_alleles = nullptr;                            // --site-alleles FILE, the same way
 // --site-vcf FILE, as --vcf: the header names every target, so the records wait in an unnamed temporary file
 FILE *g_site_vcf = nullptr, *g_site_vcf_lines = nullptr;
@@ -592,7 +615,19 @@ bool ok(dagcon_ctx *ctx, int rc, const char *what) {
 
 // --hap-sites, --hap-consensus: the tally's lines; then the second run on the same context, from what the first left on
 // the device, and its records.  What the first run's fetches point at is gone after dagcon_upload_haps
-int append_haps(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_pileup_sites &ps, const dagcon_site_reads &sr) {
+// one target's (one group's) edits [seg_begin[g], seg_begin[g + 1]) of a fetch as --hap-vcf writes them; hc NULL: unsplit,
+// else the group's states, and each mate as an index into the partner's edits, which begin at mate0
+std::vector<DgHapVcfEdit> hap_vcf_edits(const dagcon_results &r, const dagcon_edits &ed, const dagcon_edit_support &es, const uint32_t g,
+                                        const dagcon_hap_calls *hc, const uint64_t mate0) {
+    std::vector<DgHapVcfEdit> out;
+    for (uint64_t e = ed.edit_begin[r.seg_begin[g]]; e < ed.edit_begin[r.seg_begin[g + 1]]; e++)
+        out.push_back({ed.t_pos[e], ed.t_len[e], std::string(r.seq_blob + ed.c_off[e], ed.c_len[e]), es.span[e], es.ref[e], es.alt[e],
+                       hc ? hc->state[e] : 0u, hc && hc->mate[e] != UINT64_MAX ? (long long)(hc->mate[e] - mate0) : -1ll});
+    return out;
+}
+
+int append_haps(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_results &r1, const dagcon_edits &ed1, const dagcon_edit_support &es1,
+                const dagcon_pileup_sites &ps, const dagcon_site_reads &sr) {
     dagcon_hap_tally ht;
     memset(&ht, 0, sizeof ht);
     if (!ok(ctx, dagcon_fetch_hap_tally(ctx, &ht), "tally of the split")) return 1;
@@ -602,7 +637,14 @@ int append_haps(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_pileup_si
             for (uint64_t s = ps.site_begin[g]; s < ps.site_begin[g + 1]; s++)
                 if (sr.phase[s]) dg_hap_site_line(b.hap_sites, b.ids[g], ps.pos[s], sr.phase[s], ht.site_counts + 4 * s);
         }
-    if (o.hap.consensus.empty()) return 0;
+    if (o.hap.consensus.empty() && o.hap.vcf.empty()) return 0;
+    // --hap-vcf: an unsplit target's lines are the first run's own edits, taken here, before the second run takes their place
+    std::vector<std::string> vcf_lines(o.hap.vcf.empty() ? 0 : ht.n_targets);
+    for (uint32_t g = 0; g < vcf_lines.size(); g++) {
+        dg_vcf_contig(b.hap_contigs, b.ids[g], b.tlen[g]);
+        if (!ht.split[g] && r1.target_status[g] == DAGCON_OK)
+            dg_hap_vcf_unsplit(vcf_lines[g], b.ids[g], b.t.data() + b.toff[g], b.tlen[g], hap_vcf_edits(r1, ed1, es1, g, nullptr, 0));
+    }
     dagcon_results r;
     dagcon_hap_map hm;
     int rc = dagcon_upload_haps(ctx);
@@ -615,8 +657,23 @@ int append_haps(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_pileup_si
         if (r.target_status[g] != DAGCON_OK)
             fprintf(stderr, "pbdagcon: warning: group %s skipped (%s)\n", id.c_str(), dg_status_text(r.target_status[g], "an alignment leaves the backbone or holds a non-printable byte"));
         for (uint64_t s = r.seg_begin[g]; s < r.seg_begin[g + 1]; s++)
-            if (!dg_append_result(b.hap_out, false, id, r.range0[s], r.range1[s], r.seq_blob + r.seq_off[s], r.seq_len[s], nullptr, nullptr)) return 1;
+            if (!o.hap.consensus.empty() && !dg_append_result(b.hap_out, false, id, r.range0[s], r.range1[s], r.seq_blob + r.seq_off[s], r.seq_len[s], nullptr, nullptr)) return 1;
     }
+    if (o.hap.vcf.empty()) return 0;
+    // a split target's lines: the edits of its two groups, label 1 at d and label 2 at d + 1, with their support and states
+    dagcon_edits ed;
+    dagcon_edit_support es;
+    dagcon_hap_calls hc;
+    rc = dagcon_fetch_edits(ctx, &ed);
+    if (rc == DAGCON_OK) rc = dagcon_fetch_edit_support(ctx, &es);
+    if (rc == DAGCON_OK) rc = dagcon_fetch_hap_calls(ctx, &hc);
+    if (!ok(ctx, rc, "hap calls")) return 1;
+    for (uint32_t d = 0; d + 1 < r.n_targets; d += 2) {
+        const uint32_t g = hm.src_target[d];
+        const uint64_t b1 = ed.edit_begin[r.seg_begin[d]], b2 = ed.edit_begin[r.seg_begin[d + 1]];
+        dg_hap_vcf_split(vcf_lines[g], b.ids[g], b.t.data() + b.toff[g], b.tlen[g], hap_vcf_edits(r, ed, es, d, &hc, b2), hap_vcf_edits(r, ed, es, d + 1, &hc, b1));
+    }
+    for (const std::string &x : vcf_lines) b.hap_vcf += x;
     return 0;
 }
 
@@ -630,7 +687,7 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
     if (o.want_edits() && !ok(ctx, dagcon_fetch_edits(ctx, &ed), "edits")) return 1;
     dagcon_edit_support es;
     memset(&es, 0, sizeof es);
-    if (!o.vcf.empty() && !ok(ctx, dagcon_fetch_edit_support(ctx, &es), "edit support")) return 1;
+    if (o.want_edit_support() && !ok(ctx, dagcon_fetch_edit_support(ctx, &es), "edit support")) return 1;
     dagcon_pileup pu;
     memset(&pu, 0, sizeof pu);
     if (!o.pile.pileup.empty() && !ok(ctx, dagcon_fetch_pileup(ctx, &pu), "pile-up")) return 1;
@@ -702,7 +759,7 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
             b.n_edits += ed.edit_begin[s + 1] - ed.edit_begin[s];
         }
     }
-    return o.hap.on() ? append_haps(ctx, b, o, ps, sr) : 0;             // (last: the second run takes the place of everything above)
+    return o.hap.on() ? append_haps(ctx, b, o, r, ed, es, ps, sr) : 0;  // (last: the second run takes the place of everything above)
 }
 
 // the batch's own strings as the library's batch
@@ -966,7 +1023,8 @@ struct Workers {
         dagcon_ctx *ctx = nullptr;
         const double tc0 = wall();
         int rc = dg_create(o.min_cov, o.min_len, o.trim, dev[w], (o.local && !o.polish ? DAGCON_FLAG_LOCAL_ALIGN : 0u) | (o.fastq ? DAGCON_FLAG_BASE_SUPPORT : 0u) | (o.want_edits() ? DAGCON_FLAG_BASE_POS : 0u), &o.pick, &ctx);
-        if (rc == DAGCON_OK && o.want_edits() && ((rc = dagcon_set_edits(ctx, 1)) != DAGCON_OK || (!o.vcf.empty() && (rc = dagcon_set_edit_support(ctx, 1)) != DAGCON_OK))) {
+        if (rc == DAGCON_OK && o.want_edits() && ((rc = dagcon_set_edits(ctx, 1)) != DAGCON_OK || (o.want_edit_support() && (rc = dagcon_set_edit_support(ctx, 1)) != DAGCON_OK) ||
+                                                   (!o.hap.vcf.empty() && (rc = dagcon_set_hap_calls(ctx, 1)) != DAGCON_OK))) {
             fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx));
             dagcon_destroy(ctx); ctx = nullptr;
         }
@@ -1028,6 +1086,7 @@ struct Workers {
                     if (g_haplotag && fwrite(d->haplotag.data(), 1, d->haplotag.size(), g_haplotag) != d->haplotag.size()) g_pile_bad = true;
                     if (g_hap_out && fwrite(d->hap_out.data(), 1, d->hap_out.size(), g_hap_out) != d->hap_out.size()) g_pile_bad = true;
                     if (g_hap_sites && fwrite(d->hap_sites.data(), 1, d->hap_sites.size(), g_hap_sites) != d->hap_sites.size()) g_pile_bad = true;
+                    if (g_hap_vcf) { g_hap_vcf_contigs += d->hap_contigs; if (fwrite(d->hap_vcf.data(), 1, d->hap_vcf.size(), g_hap_vcf_lines) != d->hap_vcf.size()) g_pile_bad = true; }
                     if (g_site_alleles && fwrite(d->site_alleles.data(), 1, d->site_alleles.size(), g_site_alleles) != d->site_alleles.size()) g_pile_bad = true;
                     if (g_site_vcf) { g_site_vcf_contigs += d->site_contigs; if (fwrite(d->site_vcf.data(), 1, d->site_vcf.size(), g_site_vcf_lines) != d->site_vcf.size()) g_pile_bad = true; }
                     if (g_joined_alleles && fwrite(d->joined_alleles.data(), 1, d->joined_alleles.size(), g_joined_alleles) != d->joined_alleles.size()) g_pile_bad = true;
@@ -1533,6 +1592,7 @@ int main(int argc, char **argv) {
     if (!o.sr.haplotag.empty() && !(g_haplotag = fopen(o.sr.haplotag.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.sr.haplotag.c_str()); return 1; }
     if (!o.hap.consensus.empty() && !(g_hap_out = fopen(o.hap.consensus.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.consensus.c_str()); return 1; }
     if (!o.hap.sites.empty() && !(g_hap_sites = fopen(o.hap.sites.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.sites.c_str()); return 1; }
+    if (!o.hap.vcf.empty() && (!(g_hap_vcf = fopen(o.hap.vcf.c_str(), "w")) || !(g_hap_vcf_lines = tmpfile()))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.vcf.c_str()); return 1; }
     if (!o.al.alleles.empty() && !(g_site_alleles = fopen(o.al.alleles.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.al.alleles.c_str()); return 1; }
     if (!o.al.vcf.empty() && (!(g_site_vcf = fopen(o.al.vcf.c_str(), "w")) || !(g_site_vcf_lines = tmpfile()))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.al.vcf.c_str()); return 1; }
     if (!o.jn.alleles.empty() && !(g_joined_alleles = fopen(o.jn.alleles.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.jn.alleles.c_str()); return 1; }
@@ -1557,9 +1617,14 @@ int main(int argc, char **argv) {
             dg_joined_vcf_header(head, g_joined_vcf_contigs, o.want_phase());
             finish_vcf(g_joined_vcf, g_joined_vcf_lines, head);
         }
+        if (g_hap_vcf) {
+            std::string head;
+            dg_hap_vcf_header(head, g_hap_vcf_contigs);
+            finish_vcf(g_hap_vcf, g_hap_vcf_lines, head);
+        }
         const std::pair<FILE **, const std::string *> files[] = {{&g_pileup, &o.pile.pileup}, {&g_sites, &o.pile.sites}, {&g_site_reads, &o.sr.site_reads}, {&g_haplotag, &o.sr.haplotag},
                                                                  {&g_site_alleles, &o.al.alleles}, {&g_site_vcf, &o.al.vcf}, {&g_joined_alleles, &o.jn.alleles}, {&g_joined_vcf, &o.jn.vcf},
-                                                                 {&g_hap_out, &o.hap.consensus}, {&g_hap_sites, &o.hap.sites}};
+                                                                 {&g_hap_out, &o.hap.consensus}, {&g_hap_sites, &o.hap.sites}, {&g_hap_vcf, &o.hap.vcf}};
         for (const auto &f : files) {
             if (!*f.first) continue;
             const bool bad = fclose(*f.first) != 0 || g_pile_bad;
@@ -1608,7 +1673,7 @@ int main(int argc, char **argv) {
         if (fclose(g_edits) != 0) { fprintf(stderr, "pbdagcon: error writing %s\n", o.edits.c_str()); status = 1; fast_exit = false; }
         if (o.verbose) fprintf(stderr, "pbdagcon: %llu edits written to %s\n", g_n_edits, o.edits.c_str());
     }
-    if (g_pileup || g_sites || g_site_reads || g_haplotag || g_hap_out || g_hap_sites || g_site_alleles || g_site_vcf || g_joined_alleles || g_joined_vcf) {
+    if (g_pileup || g_sites || g_site_reads || g_haplotag || g_hap_out || g_hap_sites || g_hap_vcf || g_site_alleles || g_site_vcf || g_joined_alleles || g_joined_vcf) {
         const int ps = close_pile(0);
         if (ps) { status = ps; fast_exit = false; }
     }

@@ -26,9 +26,10 @@ inline void dg_vcf_columns(std::string &out) {
            "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
 }
 
+// the first five columns of a line, RNAME POS . REF ALT, anchored by the rule above (--hap-vcf writes them too)
 // tb: the target's bases [0, tlen); alt: the c_len replacing bytes
-inline void dg_vcf_line(std::string &out, const std::string &name, const char *tb, uint32_t tlen, uint32_t t_pos, uint32_t t_len,
-                        const char *alt, uint32_t c_len, uint32_t span, uint32_t n_ref, uint32_t n_alt, uint32_t gL, uint32_t gR) {
+inline void dg_vcf_anchored(std::string &out, const std::string &name, const char *tb, uint32_t tlen, uint32_t t_pos, uint32_t t_len,
+                            const char *alt, uint32_t c_len) {
     std::string ref(tb + t_pos, t_len), al(alt, c_len);
     uint64_t pos = (uint64_t)t_pos + 1;
     if (!t_len || !c_len) {
@@ -36,7 +37,13 @@ inline void dg_vcf_line(std::string &out, const std::string &name, const char *t
         else if (t_pos + t_len < tlen) { ref += tb[t_pos + t_len]; al += tb[t_pos + t_len]; pos = 1; }
         else { if (ref.empty()) ref = "."; if (al.empty()) al = "."; pos = 1; }
     }
+    out += name; out += '\t'; out += std::to_string(pos); out += "\t.\t"; out += ref; out += '\t'; out += al;
+}
+
+inline void dg_vcf_line(std::string &out, const std::string &name, const char *tb, uint32_t tlen, uint32_t t_pos, uint32_t t_len,
+                        const char *alt, uint32_t c_len, uint32_t span, uint32_t n_ref, uint32_t n_alt, uint32_t gL, uint32_t gR) {
+    dg_vcf_anchored(out, name, tb, tlen, t_pos, t_len, alt, c_len);
     char info[128];
     snprintf(info, sizeof info, "\t.\t.\tDP=%u;AD=%u,%u;WIN=%u-%u\n", span, n_ref, n_alt, gL + 1u, gR);
-    out += name; out += '\t'; out += std::to_string(pos); out += "\t.\t"; out += ref; out += '\t'; out += al; out += info;
+    out += info;
 }

@@ -5,7 +5,9 @@ this package.  The product (pbdagcon_amd) never does.
 
 `lib()` loads oracle/liboracle.so (built by oracle/Makefile from
 dagcon_oracle.c); `ref_lib()` loads oracle/_ref/libref_alignment.so (the
-reference's own Alignment.cpp compiled in place) when it exists.
+reference's own Alignment.cpp compiled in place) when it exists, and
+`ref_graph_lib()` oracle/_ref/libref_graph.so (the reference's own
+AlnGraphBoost.cpp compiled in place on oracle/bgl_standin) when it exists.
 """
 from __future__ import annotations
 
@@ -14,6 +16,7 @@ import os
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+REFERENCE = "/root/reference"        # oracle/Makefile's $(REF): where the reference lies, on a machine that has it
 _LIB = None
 _REF = None
 
@@ -35,8 +38,9 @@ def build(force: bool = False) -> None:
     need = (force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src)
             or not os.path.exists(cf)
             or os.path.getmtime(cf) < os.path.getmtime(os.path.join(_HERE, "cpu_faithful.cpp")))
-    need_ref = os.path.exists("/root/reference/src/cpp/Alignment.cpp") and (
-        force or not os.path.exists(ref_so))
+    ref_graph_so = os.path.join(_HERE, "_ref", "libref_graph.so")
+    need_ref = os.path.exists(os.path.join(REFERENCE, "src", "cpp", "Alignment.cpp")) and (
+        force or not os.path.exists(ref_so) or not os.path.exists(ref_graph_so))
     if need or need_ref:
         subprocess.check_call(["make", "-s", "-C", _HERE, "all"])
 
@@ -322,6 +326,199 @@ class Graph:
             ie = [(a[i], b[i]) for i in range(n)]
             out.append((base.raw.decode("latin1"), w.value, cv.value, bool(d.value), oe, ie))
         return out
+
+
+_REFG = None
+
+
+def ref_graph_lib():
+    """The reference's AlnGraphBoost.cpp on the BGL stand-in (oracle/ref_graph_glue.cpp), or None when oracle/_ref
+    was not built."""
+    global _REFG
+    if _REFG is not None:
+        return _REFG
+    so = os.path.join(_HERE, "_ref", "libref_graph.so")
+    if not os.path.exists(so):
+        return None
+    _REFG = _bind_ref_graph(C.CDLL(so))
+    return _REFG
+
+
+def _bind_ref_graph(R):
+    sz, u32, i32, cp, vp = C.c_size_t, C.c_uint32, C.c_int32, C.c_char_p, C.c_void_p
+    R.rg_new_seq.restype = vp
+    R.rg_new_seq.argtypes = [cp, sz]
+    R.rg_new_len.restype = vp
+    R.rg_new_len.argtypes = [sz]
+    R.rg_free.argtypes = [vp]
+    R.rg_free_ptr.argtypes = [vp]
+    R.rg_add_aln.argtypes = [vp, u32, cp, cp, sz]
+    R.rg_merge_nodes.argtypes = [vp]
+    R.rg_dangling_nodes.argtypes = [vp]
+    R.rg_consensus_longest.restype = vp
+    R.rg_consensus_longest.argtypes = [vp, C.c_int]
+    R.rg_consensus_all.restype = C.c_long
+    R.rg_consensus_all.argtypes = [vp, C.c_int, sz, C.POINTER(C.POINTER(Segment))]
+    R.rg_free_segments.argtypes = [C.POINTER(Segment), sz]
+    R.rg_best_path.restype = C.c_long
+    R.rg_best_path.argtypes = [vp, C.POINTER(C.POINTER(i32))]
+    R.rg_num_nodes.restype = sz
+    R.rg_num_nodes.argtypes = [vp]
+    R.rg_adjacency.restype = sz
+    R.rg_adjacency.argtypes = [vp, C.POINTER(C.POINTER(i32))]
+    blob = [u32, cp, sz, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(u32), vp, vp, C.POINTER(Opts)]
+    R.rg_target_graph.restype = vp
+    R.rg_target_graph.argtypes = blob
+    R.rg_consensus_target_blob.restype = C.c_long
+    R.rg_consensus_target_blob.argtypes = blob + [C.POINTER(C.POINTER(Segment))]
+    return R
+
+
+class RefGraph:
+    """Graph's methods on the reference's AlnGraphBoost (ref_graph_lib(), or a library given as `lib`: a build on another
+    stand-in).  best_path() returns the reference's AlnNodes as (base, weight, coverage, backbone, deleted): it has no
+    vertex ids to give."""
+
+    def __init__(self, backbone: bytes | None = None, blen: int | None = None, lib=None, handle=None):
+        self.R = lib if lib is not None else ref_graph_lib()
+        if handle is not None:
+            self.g = handle
+        elif backbone is not None:
+            self.g = self.R.rg_new_seq(backbone, len(backbone))
+        else:
+            self.g = self.R.rg_new_len(blen)
+
+    def __del__(self):
+        if getattr(self, "g", None):
+            self.R.rg_free(self.g)
+            self.g = None
+
+    def add_aln(self, start: int, q: bytes, t: bytes):
+        assert len(q) == len(t)
+        self.R.rg_add_aln(self.g, start, q, t, len(q))
+
+    def merge_nodes(self) -> int:
+        return self.R.rg_merge_nodes(self.g)
+
+    def consensus_longest(self, min_weight: int = 0) -> bytes:
+        p = self.R.rg_consensus_longest(self.g, min_weight)
+        if not p:
+            raise RuntimeError("no thread for the reference's call")
+        s = C.string_at(p)
+        self.R.rg_free_ptr(p)
+        return s
+
+    def consensus_all(self, min_weight: int = 0, min_len: int = 500):
+        segs = C.POINTER(Segment)()
+        n = self.R.rg_consensus_all(self.g, min_weight, min_len, C.byref(segs))
+        if n < 0:
+            raise RuntimeError("no thread for the reference's call")
+        out = [(segs[i].range0, segs[i].range1, segs[i].seq) for i in range(n)]
+        self.R.rg_free_segments(segs, n)
+        return out
+
+    def best_path(self):
+        p = C.POINTER(C.c_int32)()
+        n = self.R.rg_best_path(self.g, C.byref(p))
+        if n < 0:
+            raise RuntimeError("no thread for the reference's call")
+        out = [(chr(p[5 * i]), p[5 * i + 1], p[5 * i + 2], bool(p[5 * i + 3]), bool(p[5 * i + 4])) for i in range(n)]
+        self.R.rg_free_ptr(C.cast(p, C.c_void_p))
+        return out
+
+    def dangling_nodes(self) -> bool:
+        return bool(self.R.rg_dangling_nodes(self.g))
+
+    def num_nodes(self):
+        return self.R.rg_num_nodes(self.g)
+
+    def adjacency(self):
+        """Same shape as Graph.adjacency(), both lists in the reference's list order."""
+        p = C.POINTER(C.c_int32)()
+        n = self.R.rg_adjacency(self.g, C.byref(p))
+        a = p[:n]
+        self.R.rg_free_ptr(C.cast(p, C.c_void_p))
+        out, i = [], 0
+        while i < n:
+            base, w, cv, d, no = a[i:i + 5]
+            i += 5
+            oe = list(zip(a[i:i + 2 * no:2], a[i + 1:i + 2 * no:2]))
+            i += 2 * no
+            ni = a[i]
+            i += 1
+            ie = list(zip(a[i:i + 2 * ni:2], a[i + 1:i + 2 * ni:2]))
+            i += 2 * ni
+            out.append((chr(base), w, cv, bool(d), oe, ie))
+        return out
+
+
+def path_nodes(g: "Graph"):
+    """Graph.best_path() of the oracle as the reference returns it: (base, weight, coverage, backbone, deleted) per node."""
+    out = []
+    for v in g.best_path():
+        base = C.create_string_buffer(1)
+        w, cv, d, bb, bm = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+        g.L.og_node_info(g.g, v, base, C.byref(w), C.byref(cv), C.byref(d), C.byref(bb), C.byref(bm))
+        out.append((base.raw.decode("latin1"), w.value, cv.value, bool(bb.value), bool(d.value)))
+    return out
+
+
+def _blob_args(tlen, alns, min_len, trim, min_weight, backbone):
+    import numpy as np
+    n = len(alns)
+    starts = np.array([a[0] for a in alns], dtype=np.uint32)
+    lens = np.array([len(a[1]) for a in alns], dtype=np.uint32)
+    offs = np.zeros(n, dtype=np.uint64)
+    if n:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    qblob = b"".join(a[1] for a in alns)
+    tblob = b"".join(a[2] for a in alns)
+    keep = (starts, lens, offs, qblob, tblob)
+    o = Opts(min_len, trim, min_weight)
+    return keep, [tlen, backbone, n, starts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                  offs.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(C.POINTER(C.c_uint32)),
+                  C.cast(C.c_char_p(qblob), C.c_void_p), C.cast(C.c_char_p(tblob), C.c_void_p), C.byref(o)]
+
+
+def ref_target_graph(tlen: int, alns, min_len=500, trim=50, backbone=None, lib=None) -> RefGraph:
+    """main.cpp:130-137 on the reference for one target: the merged graph.  The input must conform (consensus_target
+    raises ValueError where it does not): the reference does not check."""
+    R = lib if lib is not None else ref_graph_lib()
+    keep, args = _blob_args(tlen, alns, min_len, trim, 0, backbone)
+    h = R.rg_target_graph(*args)
+    if not h:
+        raise RuntimeError("no thread for the reference's call")
+    return RefGraph(lib=R, handle=h)
+
+
+def ref_consensus_target(tlen: int, alns, min_len=500, trim=50, min_weight=6, backbone=None, lib=None):
+    """consensus_target on the reference's own code (main.cpp:128-138): [(range0, range1, seq)].  Conforming input only."""
+    R = lib if lib is not None else ref_graph_lib()
+    keep, args = _blob_args(tlen, alns, min_len, trim, min_weight, backbone)
+    return _ref_segments(R, args)
+
+
+def ref_consensus_target_blob(tlen, starts, offs, lens, qblob, tblob, min_len=500, trim=50, min_weight=6,
+                              backbone=None, lib=None):
+    """consensus_target_blob on the reference's own code.  Conforming input only."""
+    import numpy as np
+    R = lib if lib is not None else ref_graph_lib()
+    o = Opts(min_len, trim, min_weight)
+    qp = qblob.ctypes.data if isinstance(qblob, np.ndarray) else C.cast(C.c_char_p(qblob), C.c_void_p)
+    tp = tblob.ctypes.data if isinstance(tblob, np.ndarray) else C.cast(C.c_char_p(tblob), C.c_void_p)
+    return _ref_segments(R, [tlen, backbone, len(starts), starts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                             offs.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(C.POINTER(C.c_uint32)),
+                             qp, tp, C.byref(o)])
+
+
+def _ref_segments(R, args):
+    segs = C.POINTER(Segment)()
+    n = R.rg_consensus_target_blob(*args, C.byref(segs))
+    if n < 0:
+        raise RuntimeError("no thread for the reference's call")
+    out = [(segs[i].range0, segs[i].range1, segs[i].seq) for i in range(n)]
+    R.rg_free_segments(segs, n)
+    return out
 
 
 _libc = C.CDLL(None)

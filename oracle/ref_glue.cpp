@@ -4,8 +4,9 @@
 // /root/reference/src/cpp/Alignment.cpp, read in place (never copied), into
 // oracle/_ref/libref_alignment.so by oracle/Makefile.  It exists to pin the
 // oracle's restatement of normalizeGaps / trimAln / parseM5 / revComp against
-// the real code.  AlnGraphBoost.cpp cannot be built the same way: it needs
-// Boost.Graph, which this image does not have.
+// the real code.  AlnGraphBoost.cpp is built the same way by ref_graph_glue.cpp,
+// on this build's own stand-in for the Boost.Graph containers it uses
+// (bgl_standin/): that pins the graph stages.
 #include <cstring>
 #include <istream>
 #include <sstream>

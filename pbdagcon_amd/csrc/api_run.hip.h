@@ -584,8 +584,8 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
         tmp_cols = 0;
         for (uint32_t a = 0; a < c->A; a++) { tmp_off[a] = tmp_cols; tmp_cols += c->h_aln_len[a]; }
     }
-    c->tmp_main = (2ull * tmp_cols + 8ull * c->n_chunks + 15ull) & ~7ull;
-    c->tmp_cap = c->tmp_main + std::max<uint64_t>(c->tmp_main / 16, 1ull << 20);
+    c->tmp_main = dg_tmp_main(tmp_cols, c->n_chunks);
+    c->tmp_cap = dg_tmp_cap(c->tmp_main);
 
     // inputs -> HBM
     ENSURE(c, c->in.q, b->blob_bytes);
@@ -639,6 +639,8 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
 
     // first guesses for the data-dependent arenas; a run that finds them too
     // small records the exact need on the device and is repeated once.
+    // (tests/norm_limit_cases.py, arenas_fit, restates node_cap and pool_cap to keep its batches inside them: change it
+    // with them)
     c->node_cap = std::max<uint64_t>(c->node_cap, c->sum_bb + c->sum_len / 7 + 1024);
     c->pool_cap = std::max<uint64_t>(c->pool_cap, 8ull * c->node_cap + 80ull * c->sum_bb + 1024ull * T);
     c->cns_cap = std::max<uint64_t>(c->cns_cap, c->sum_bb + c->sum_bb / 4 + 1024);

@@ -50,6 +50,24 @@ DG_HD inline uint32_t dg_chunk_start(const uint8_t *q, const uint8_t *t, uint32_
     return DG_CH_NONE;
 }
 
+// The chunk scratch, in uint16 columns.  Main part: two columns per input column of the batch (tmp_cols) at the
+// chunk's own place, 8 more per window so that every chunk's stretch starts on a 16-byte boundary; behind it the
+// re-run region, a sixteenth of that and no less than 2^20 columns (k_norm_chunk's ovf_top counts into it).
+DG_HD_INLINE uint64_t dg_tmp_main(const uint64_t tmp_cols, const uint64_t n_chunks) {
+    return (2ull * tmp_cols + 8ull * n_chunks + 15ull) & ~7ull;
+}
+DG_HD_INLINE uint64_t dg_tmp_region(const uint64_t tmp_main) {
+    return tmp_main / 16 > (1ull << 20) ? tmp_main / 16 : 1ull << 20;
+}
+DG_HD_INLINE uint64_t dg_tmp_cap(const uint64_t tmp_main) { return tmp_main + dg_tmp_region(tmp_main); }
+
+// A seam for the CPU model of the stage (tests/native/norm_stage_host.cpp), which defines this macro before it includes
+// the header to read dg_norm_run's window cursors after every refill: the largest e - i and how often the ring came
+// round.  Nobody else defines it: here, and in every build of the library, it expands to nothing and the loop is unchanged.
+#ifndef DG_NORM_RUN_PROBE
+#define DG_NORM_RUN_PROBE(e, i)
+#endif
+
 struct DgChunkRun { uint32_t w, tb; bool dirty, overflow, badchar; };
 
 // normalizeGaps (Alignment.cpp:142-214) on the input columns [k0, k1) of an alignment, started
@@ -121,6 +139,7 @@ DG_HD inline DgChunkRun dg_norm_run(const uint8_t *q, const uint8_t *t, const ui
             if (ip == k1) e_end = e;
             if (ip == len) in_done = 1;
         }
+        DG_NORM_RUN_PROBE(e, i);
         // ---- Alignment.cpp:165-198 push gaps to the right, as far as the window reaches.
         // jt / jq only move forward (a column left of a cursor is never turned back into
         // a base).  A step that runs out of window stores what it has done to column i

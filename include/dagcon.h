@@ -447,7 +447,7 @@ int dagcon_fetch_site_reads(dagcon_ctx *ctx, dagcon_site_reads *out);
  * label 2, by rule 7, with the tlen (and the backbone, if the first batch had one) of its target.  The strings are those
  * the first batch left on the device, whichever way they came in: none crosses the bus and none is copied.  It is an
  * upload like any other: the results of the first batch and dagcon_fetch_md_targets stop being valid, every optional
- * output (edits, edit support, pile-up, site reads, site alleles, joined sites, tally) is off for the derived batch and its fetch DAGCON_ERR_STATE (but for dagcon_set_hap_calls, rule 11 below),
+ * output (edits, edit support, pile-up, site reads, site alleles, joined sites, tally) is off for the derived batch and its fetch DAGCON_ERR_STATE (but for dagcon_set_hap_calls, rule 11 below, and dagcon_set_window_keep, rule 12),
  * the record filter has nothing to do, and a second dagcon_upload_haps in a row is DAGCON_ERR_STATE.  min_cov, min_len,
  * trim, min_weight and the context's flags (DAGCON_FLAG_BASE_SUPPORT / _BASE_POS with their fetches among them) hold as
  * for dagcon_upload; a group with fewer reads than min_weight lets few bases out, which is the caller's option to set as
@@ -676,6 +676,57 @@ typedef struct dagcon_hap_calls {
     const uint64_t *mate;    /* [n] index into the same arrays; UINT64_MAX: none */
 } dagcon_hap_calls;
 int dagcon_fetch_hap_calls(dagcon_ctx *ctx, dagcon_hap_calls *out);
+
+/*
+ * The groups in the caller's orientation (host only).  dagcon_upload_haps names the groups of a split target by the labels
+ * of that target alone (rule 4: the seed is label 1).  A caller that has joined the labels of neighbouring windows (rule 9:
+ * flip, and whatever it links across its own uploads) says which targets carry the other naming:
+ * dagcon_upload_haps_swapped is dagcon_upload_haps in everything -- when it is valid, what it uploads, what it leaves --
+ * but for this: for a split target t with swap[t] != 0 the two groups change names.  The derived target with label 1 holds
+ * the target's alignments whose hap is 2 or 0, the one with label 2 those whose hap is 1 or 0 (rule 7 otherwise).  Pairs
+ * stay at d, d ^ 1, label 1 first; dagcon_hap_map.label is the caller's name after the swap, aln_src keeps its meaning; rule
+ * 11 holds unchanged on the pairs.  swap has one byte per target of the first batch; NULL swaps nothing, and
+ * dagcon_upload_haps is this call with NULL.
+ */
+int dagcon_upload_haps_swapped(dagcon_ctx *ctx, const uint8_t *swap);   /* swap: [n_targets of the first batch], or NULL */
+
+/*
+ * The kept part of every segment of a window, cut on the device (off by default; a context switch that needs
+ * DAGCON_FLAG_BASE_POS).  A window is consensus'd with an overlap on either side, and a stitch keeps of each segment the
+ * part inside the window's core.  Finding that part from dagcon_fetch_positions costs 4 bytes a base across the bus and a
+ * walk over every base on the host; the device finds it while the positions are still in HBM and hands back 16 bytes a
+ * segment.
+ * THIS BUILD'S OWN RULE, PARITY UNPINNED (the reference has no windows; tests/hap_contigs_twin.py: keep is its twin).
+ * 12. Given lo[t] <= hi[t] per target (window) t.  Take a segment of n bases on target t; P(i) is the value
+ *     dagcon_fetch_positions gives for its base i, 1-based and relative to the window.
+ *     i0 is the least i with P(i) > lo[t].  i1 is the least i >= i0 with P(i) > hi[t], or n if there is none.  Only first
+ *     crossings count and nothing assumes that P is monotone: a base in front of i0 with P > hi does not count.
+ *     The kept part is [i0, i1), with p_first = P(i0) and p_last = P(i1 - 1).  It is empty when no i0 exists or when
+ *     i1 == i0; the record is then 0 0 0 0.
+ *     With lo = core begin - window begin and hi = core end - window begin this is the cut a stitch of overlapping
+ *     windows makes: "cut at the core begin" is i0 > 0, "cut at the core end" is i1 < n.
+ * dagcon_set_window_keep: the arrays are copied by the call; NULL turns it off.  DAGCON_ERR_STATE on a context without
+ * DAGCON_FLAG_BASE_POS; lo[t] > hi[t] is DAGCON_ERR_INVALID_ARG and the switch stays as it was.  The switch is read at two
+ * points: at a windows upload, by any of the window entry points, and at dagcon_upload_haps / _swapped behind a windows
+ * upload, where derived target d takes lo / hi of src_target[d].  At both points n must equal the number of windows of the
+ * first batch: otherwise the upload returns DAGCON_ERR_INVALID_ARG before any launch (and leaves the context as any failed
+ * upload does).  In every other case it is as if off: no kernel, buffer, memset, launch or copy differs from a context
+ * that never heard of it.  In effect, the host uploads 8 bytes a target and k_win_keep (csrc/k_keep.hip.h) runs behind
+ * k_bp_join (behind the edit kernels where those run) in every execution of the run, re-runs included; and, as with the
+ * edits, the positions stay on the device and are copied only when dagcon_fetch_positions is called.
+ * dagcon_fetch_window_keep: the records (16 bytes a segment) are copied when it is called and brought from the device's
+ * segment order to that of dagcon_results, as dagcon_fetch_edits does for its arrays: a failed target has no segments and
+ * so no records.  DAGCON_ERR_STATE wherever dagcon_fetch_positions is, when the switch did not take effect at the upload,
+ * before the batch's dagcon_fetch, and after any later upload.  Owned by the context, valid as long as the results of the
+ * same fetch.
+ */
+typedef struct dagcon_window_keep_opts { uint32_t n; const uint32_t *lo, *hi; } dagcon_window_keep_opts;   /* copied by the call */
+int dagcon_set_window_keep(dagcon_ctx *ctx, const dagcon_window_keep_opts *o);    /* NULL: off (the default) */
+typedef struct dagcon_window_keep {
+    uint64_t n_segments;                              /* == dagcon_results.n_segments of the same fetch, same order */
+    const uint32_t *i0, *i1, *p_first, *p_last;       /* [n_segments] */
+} dagcon_window_keep;
+int dagcon_fetch_window_keep(dagcon_ctx *ctx, dagcon_window_keep *out);
 
 /*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses

@@ -51,6 +51,7 @@ EXPORTS = [
     "dagcon_upload_cigar_md", "dagcon_consensus_cigar_md", "dagcon_fetch_md_targets",
     "dagcon_set_window_phase", "dagcon_fetch_window_phase",
     "dagcon_set_hap_calls", "dagcon_fetch_hap_calls",
+    "dagcon_upload_haps_swapped", "dagcon_set_window_keep", "dagcon_fetch_window_keep",
 ]
 HC_NOCOVER, HC_HET, HC_CLASH, HC_HOM = 0, 1, 2, 3
 HC_NONE = 0xFFFFFFFFFFFFFFFF
@@ -224,6 +225,17 @@ class HapCalls(C.Structure):
     _fields_ = [("n", C.c_uint64), ("state", C.POINTER(C.c_uint8)), ("mate", C.POINTER(C.c_uint64))]
 
 
+class WindowKeepOpts(C.Structure):
+    """dagcon_window_keep_opts: lo and hi per window of the first batch (include/dagcon.h, rule 12)."""
+    _fields_ = [("n", C.c_uint32), ("lo", C.POINTER(C.c_uint32)), ("hi", C.POINTER(C.c_uint32))]
+
+
+class WindowKeep(C.Structure):
+    """dagcon_window_keep: per segment of the last results the kept part [i0, i1) and the positions of its two ends."""
+    _fields_ = [("n_segments", C.c_uint64), ("i0", C.POINTER(C.c_uint32)), ("i1", C.POINTER(C.c_uint32)),
+                ("p_first", C.POINTER(C.c_uint32)), ("p_last", C.POINTER(C.c_uint32))]
+
+
 class Edits(C.Structure):
     """dagcon_edits: per segment its target span and its edits (include/dagcon.h has the definition)."""
     _fields_ = [("n_segments", C.c_uint64), ("n", C.c_uint64), ("seg_t0", C.POINTER(C.c_uint32)),
@@ -323,6 +335,9 @@ def load() -> C.CDLL:
     L.dagcon_fetch_window_phase.argtypes = [vp, C.POINTER(WindowPhase)]
     L.dagcon_set_hap_calls.argtypes = [vp, C.c_int]
     L.dagcon_fetch_hap_calls.argtypes = [vp, C.POINTER(HapCalls)]
+    L.dagcon_upload_haps_swapped.argtypes = [vp, vp]
+    L.dagcon_set_window_keep.argtypes = [vp, C.POINTER(WindowKeepOpts)]
+    L.dagcon_fetch_window_keep.argtypes = [vp, C.POINTER(WindowKeep)]
     L.dagcon_upload_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int]
     L.dagcon_consensus_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int,
                                             C.POINTER(Results)]
@@ -1086,10 +1101,38 @@ class Context:
         out["site_counts"] = np.ctypeslib.as_array(ht.site_counts, shape=(n_site, 4)).copy() if n_site else np.zeros((0, 4), np.uint16)
         return out
 
-    def upload_haps(self):
+    def upload_haps(self, swap=None):
         """dagcon_upload_haps: the batch of the groups, built from what the first batch left on the device; then run(),
-        sync(), fetch() as after any upload."""
-        self._chk(self.L.dagcon_upload_haps(self.h))
+        sync(), fetch() as after any upload.  swap (one byte per target of the first batch): dagcon_upload_haps_swapped,
+        the two groups of a split target t with swap[t] != 0 change names."""
+        if swap is None:
+            self._chk(self.L.dagcon_upload_haps(self.h))
+            return
+        sw = np.ascontiguousarray(swap, dtype=np.uint8)
+        self._chk(self.L.dagcon_upload_haps_swapped(self.h, sw.ctypes.data))
+
+    def set_window_keep(self, lo, hi=None):
+        """dagcon_set_window_keep for every later windows upload and every upload_haps() behind one: lo and hi per window
+        of the first batch (copied); window_keep() then lists the kept part of every segment.  set_window_keep(None): off."""
+        if lo is None:
+            self._chk(self.L.dagcon_set_window_keep(self.h, None))
+            return
+        lo = np.ascontiguousarray(lo, dtype=np.uint32)
+        hi = np.ascontiguousarray(hi, dtype=np.uint32)
+        if lo.shape != hi.shape or lo.ndim != 1:
+            raise ValueError("lo and hi are one array each, of one length")
+        u32p = C.POINTER(C.c_uint32)
+        o = WindowKeepOpts(len(lo), lo.ctypes.data_as(u32p), hi.ctypes.data_as(u32p))
+        self._chk(self.L.dagcon_set_window_keep(self.h, C.byref(o)))
+
+    def window_keep(self) -> dict:
+        """dagcon_fetch_window_keep (copies): i0, i1, p_first, p_last (uint32), one per segment of the last results, in
+        their order."""
+        wk = WindowKeep()
+        self._chk(self.L.dagcon_fetch_window_keep(self.h, C.byref(wk)))
+        n = int(wk.n_segments)
+        return {k: np.ctypeslib.as_array(getattr(wk, k), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+                for k in ("i0", "i1", "p_first", "p_last")}
 
     def hap_map(self) -> dict:
         """dagcon_fetch_hap_map (copies): src_target (uint32) and label (uint8) per target of the derived batch, aln_begin

@@ -72,6 +72,7 @@ struct InBufs {
     DevBuf ed_tbase;                                // dagcon_set_edits: where each target's bases begin in cg.t
     DevBuf pile_begin;                              // dagcon_set_pileup: where each target's positions begin in run.pile
     DevBuf wl_rec, wl_tgt;                          // dagcon_set_window_phase: each alignment's record, each window's target
+    DevBuf keep_lo, keep_hi;                        // dagcon_set_window_keep: each target's (window's) lo and hi
 };
 // RunBufs: what the kernels of a run fill and nobody clears.  all() is the set DAGCON_POISON & 8 fills with 0xEE bytes
 // before every run (launch_all): a new member goes into it, and the static_assert below says so
@@ -105,7 +106,8 @@ struct RunBufs {
     // the compact tables (sized and filled at the fetch); the three totals
     DevBuf jn_run, jn_sfirst, jn_rbeg, jn_cur, jn_nd, jn_deep, jn_toff, jn_key, jn_tcnt, jn_thap, jn_map, jn_idx, jn_ckey, jn_ccnt, jn_chap, jn_tot;
     DevBuf hc_state, hc_mate;                       // dagcon_set_hap_calls: a state byte and a mate index per edit, parallel to ed_out
-    std::array<DevBuf *, 112> all() {
+    DevBuf keep;                                    // dagcon_set_window_keep: 16 B per segment, parallel to seg
+    std::array<DevBuf *, 113> all() {
         return {&nmis, &n_lo, &n_hi, &n_start, &n_ins, &n_del, &ch_k0, &ch_next, &ch_w, &ch_tb, &ch_flag, &ch_src, &ch_out, &ch_adv, &n_lb, &norm_tmp, &ckpt,
                 &node_base, &n_nodes, &pool_base, &pool_size, &pool_top, &t_nins, &cov, &gcount, &gbase, &bid, &best, &queue, &score, &cns_tmp, &bp_tt,
                 &stk, &cuts, &cuts_bp, &bp_stat, &bp_len, &rd, &pro_state, &sh_cnt, &wl_first, &queue0, &bp_end, &bp_ab, &defer, &cns_tmp0, &cns,
@@ -114,10 +116,10 @@ struct RunBufs {
                 &hap_cnt, &hap_rec, &wl_cnt, &wl_block, &wl_flip, &wl_hap, &wl_phase,
                 &al_map, &al_idx, &al_soff, &al_cur, &al_nd, &al_deep, &al_toff, &al_srt, &al_tcnt, &al_thap, &al_ckey, &al_ccnt, &al_chap, &al_tot,
                 &jn_run, &jn_sfirst, &jn_rbeg, &jn_cur, &jn_nd, &jn_deep, &jn_toff, &jn_key, &jn_tcnt, &jn_thap, &jn_map, &jn_idx, &jn_ckey, &jn_ccnt, &jn_chap, &jn_tot,
-                &hc_state, &hc_mate};
+                &hc_state, &hc_mate, &keep};
     }
 };
-static_assert(sizeof(RunBufs) == 112 * sizeof(DevBuf), "RunBufs::all() must name every member");
+static_assert(sizeof(RunBufs) == 113 * sizeof(DevBuf), "RunBufs::all() must name every member");
 // ArenaBufs: the arenas with a treatment of their own -- matC is cleared before every run, the others are filled under
 // DAGCON_POISON bits 1 (matA, matD), 2 (nodes, pool) and 4 (score_b, norm)
 struct ArenaBufs {
@@ -229,6 +231,10 @@ struct HapMapOut {
     std::vector<uint8_t> label;
     std::vector<uint64_t> aln_begin, aln_src;
 };
+// dagcon_fetch_window_keep: per segment of the last results, in their order
+struct KeepOut {
+    std::vector<uint32_t> i0, i1, p_first, p_last;
+};
 // The kept alignments of a fetched run in the device's order (host_order builds it at the first fetch that needs it): each
 // one's index on the device and its stretch of the device's entry arrays.  Its target and the caller's index are
 // h_aln_tgt / h_aln_src at that index
@@ -328,7 +334,15 @@ struct Ctx {
     // dagcon_set_hap_calls (on only while edits are; latched for the batch of dagcon_upload_haps alone)
     Output o_hc{"without the results of a dagcon_upload_haps made with dagcon_set_hap_calls on behind a record upload that ran with dagcon_set_edits on (a "
                 "switch off, another kind of first upload, no fetch yet, or stopped before bestPath)"};
-    std::array<Output *, 9> outputs() { return {&o_ed, &o_evid, &o_pile, &o_sr, &o_al, &o_jn, &o_hap, &o_wl, &o_hc}; }
+    // dagcon_set_window_keep (its buffers: in.keep_lo, in.keep_hi, run.keep): lo / hi as set, one pair per window of a first
+    // batch; latched for a windows upload and for the batch dagcon_upload_haps derives from one.  win_first / win_n: the
+    // first batch on the device (the one a dagcon_upload_haps derives from) was a windows upload, and of how many windows
+    Output o_keep{"without the results of a windows upload, or of a dagcon_upload_haps behind one, made with dagcon_set_window_keep on (switch off at the upload, "
+                  "no windows, no fetch yet, or stopped before bestPath)"};
+    std::vector<uint32_t> keep_lo, keep_hi;
+    bool win_first = false;
+    uint32_t win_n = 0;
+    std::array<Output *, 10> outputs() { return {&o_ed, &o_evid, &o_pile, &o_sr, &o_al, &o_jn, &o_hap, &o_wl, &o_hc, &o_keep}; }
     // the growing arenas: run.ed_out (and run.evid beside it), run.pile_site, run.sr_site / sr_code.  The status block
     // holds 16 bytes for the edits' total, then 16 for the sites', whose second word is the entries'
     GrowArena ed_arena{"edits", DG_E_ED_OVF, true, &DgParams::ed_top, &DgParams::ed_cap};
@@ -358,7 +372,7 @@ struct Ctx {
     uint64_t r_sup_n = 0;
     std::vector<uint32_t> r_pos;        // DAGCON_FLAG_BASE_POS: [seq_bytes] _bbMap of every consensus base
     bool pos_valid = false;
-    bool pos_pending = false;           // edits on: the positions stay on the device until dagcon_fetch_positions asks for them
+    bool pos_pending = false;           // edits or the kept parts on: the positions stay on the device until dagcon_fetch_positions asks for them
     uint64_t r_nb = 0;                  // seq_bytes of the last fetch
     PinBuf r_ed;                        // the DgEdSeg records of the last fetch, then its DgEdit records
     PinBuf r_site;                      // the DgSite records of the last fetch
@@ -372,6 +386,7 @@ struct Ctx {
     WinPhaseOut r_winphase;
     HapCallsOut r_hc;
     HapMapOut r_hapmap;
+    KeepOut r_keep;
     HostOrder order;
     bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
 

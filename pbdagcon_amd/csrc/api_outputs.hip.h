@@ -1,5 +1,5 @@
 // api_outputs.hip.h -- the optional outputs of a run (edits and their support, the pile-up and its sites, the reads at the
-// sites, the window phase, the alleles, the joined sites, the haplotype tally, the hap calls), each one's host side in one place: its room, its kernel
+// sites, the window phase, the alleles, the joined sites, the haplotype tally, the hap calls, the kept parts), each one's host side in one place: its room, its kernel
 // parameters, its launches, its part of the fetch and its dagcon_set_* / dagcon_fetch_* entry points.  The pipeline
 // (api_run.hip.h) calls outputs_room, outputs_params, outputs_launch, outputs_upload and the outputs_plan / _copies /
 // _unpack steps of dagcon_fetch, at the end of this file; DESIGN.md says how to add an output.  (The entry points stand
@@ -13,7 +13,8 @@ namespace {
 // in).  Edits need a record upload and their support needs edits; the sites need the pile-up; the reads at the sites need
 // the sites; the alleles, the tally and the window phase need those reads, the last two with phase on; the window phase
 // needs a windows upload; the joined sites need the alleles.  The batch of dagcon_upload_haps runs with none, whatever the
-// switches say -- unless dagcon_set_hap_calls is on and the batch it derives from ran with the edits latched (a record
+// switches say (but for the kept parts, which need a windows upload or the batch derived from one and nothing else) --
+// unless dagcon_set_hap_calls is on and the batch it derives from ran with the edits latched (a record
 // upload, then: cg.t still holds its targets): then it runs with the edits, with their support iff that batch did, and
 // with the pairing of the two groups' edits.
 void latch_outputs(Ctx *c, const Intake kind) {
@@ -23,6 +24,7 @@ void latch_outputs(Ctx *c, const Intake kind) {
         c->o_hc.batch = c->o_hc.on && c->o_ed.on && had_ed;
         c->o_ed.batch = c->o_hc.batch;
         c->o_evid.batch = c->o_hc.batch && had_evid;
+        c->o_keep.batch = c->o_keep.on && c->win_first;
         return;
     }
     c->o_ed.batch = c->o_ed.on && kind != Intake::STRINGS;
@@ -34,6 +36,7 @@ void latch_outputs(Ctx *c, const Intake kind) {
     c->o_jn.batch = c->o_jn.on && c->o_al.batch;
     c->o_hap.batch = c->o_hap.on && phased;
     c->o_wl.batch = c->o_wl.on && phased && kind == Intake::WINDOWS;
+    c->o_keep.batch = c->o_keep.on && kind == Intake::WINDOWS;
     c->pile_batch_opts = c->pile_opts;
     c->sr_batch_opts = c->sr_opts;
     c->hap_batch_opts = {c->hap_opts.min_sites ? c->hap_opts.min_sites : 2u, c->hap_opts.min_reads ? c->hap_opts.min_reads : 3u};
@@ -814,6 +817,8 @@ int dagcon_fetch_joined_sites(dagcon_ctx *ctx, dagcon_joined_sites *out) {
 namespace {
 
 int calls_arm(Ctx *c, const std::vector<uint32_t> &src_target);      // dagcon_set_hap_calls, below: its part of dagcon_upload_haps
+int keep_check(Ctx *c, bool windows, uint32_t n_windows);            // dagcon_set_window_keep, below: its parts
+int keep_arm(Ctx *c, const std::vector<uint32_t> *src_target);
 
 int hap_room(Ctx *c) {
     if (!c->o_hap.batch) return DAGCON_OK;
@@ -899,25 +904,31 @@ int dagcon_fetch_hap_tally(dagcon_ctx *ctx, dagcon_hap_tally *out) {
     return DAGCON_OK;
 }
 
-int dagcon_upload_haps(dagcon_ctx *ctx) {
+int dagcon_upload_haps(dagcon_ctx *ctx) { return dagcon_upload_haps_swapped(ctx, nullptr); }
+
+// swap[t] != 0: the two groups of split target t change names (the caller's orientation of its labels); NULL: none does
+int dagcon_upload_haps_swapped(dagcon_ctx *ctx, const uint8_t *swap) {
     if (!ctx) return DAGCON_ERR_INVALID_ARG;
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     int r;
     if ((r = need(c, c->o_hap, "dagcon_upload_haps")) || (r = hap_records(c))) return r;
+    if ((r = keep_check(c, c->win_first, c->win_n))) { c->drop_results(Fresh::UPLOAD); return r; }     // (before any launch; as after any failed upload)
     const uint32_t T = c->T, A = c->A;
     std::vector<uint8_t> hap((size_t)A, 0);
     if (reads_ran(c)) HIPCHK(c, d2h(c, hap.data(), c->run.sr_hap.p, (size_t)A));
     // the plan, on the host: one byte an alignment and one record a target say everything upload_impl needs.  Group g of a
-    // split target: its alignments of the device batch with hap g or 0 (the ones the graph did not take are 0 too)
+    // split target: its alignments of the device batch with hap g or 0 (the ones the graph did not take are 0 too); under
+    // swap[t] the group the caller names g is the device's 3 - g
     std::vector<uint32_t> tlen, start, len, src_target;
     std::vector<uint64_t> begin(1, 0), off, bb_off, src;
     std::vector<uint8_t> label;
     for (uint32_t t = 0; t < T; t++) {
         if (!c->r_haps.split[t]) continue;
         for (uint8_t g = 1; g <= 2; g++) {
+            const uint8_t dg = swap && swap[t] ? (uint8_t)(3u - g) : g;
             for (uint64_t a = c->h_aln_begin[t]; a < c->h_aln_begin[t + 1]; a++) {
                 if (hap[a] > 2u) return fail(c, DAGCON_ERR_INTERNAL, "k_sr_split: alignment %llu has hap %u", (unsigned long long)a, hap[a]);
-                if (hap[a] && hap[a] != g) continue;
+                if (hap[a] && hap[a] != dg) continue;
                 off.push_back(c->h_aln_off[a]); len.push_back(c->h_aln_len[a]); start.push_back(c->h_aln_start[a]);
                 src.push_back(c->h_aln_src[a]);
             }
@@ -933,7 +944,7 @@ int dagcon_upload_haps(dagcon_ctx *ctx) {
     if (c->have_bb) { db.backbone = c->in.bb.as<const char>(); db.backbone_off = bb_off.data(); }    // (in.bb itself: nothing is copied)
     // an upload like any other, but one that latches no optional output (Intake::HAPS); the switches stay as the caller set them
     if ((r = upload_impl(ctx, &db, c->in.q.p, c->in.t.p, Intake::HAPS))) return r;   // (as after any failed upload: the first batch's results are gone)
-    if ((r = calls_arm(c, src_target))) return r;
+    if ((r = calls_arm(c, src_target)) || (r = keep_arm(c, &src_target))) return r;
     pad(src_target, label, src);
     HapMapOut &m = c->r_hapmap;
     m.src_target.swap(src_target); m.label.swap(label); m.aln_begin.swap(begin); m.aln_src.swap(src);
@@ -1031,18 +1042,116 @@ int dagcon_fetch_hap_calls(dagcon_ctx *ctx, dagcon_hap_calls *out) {
     return DAGCON_OK;
 }
 
+// ---- the kept part of every segment of a window (k_keep.hip.h) ----
+namespace {
+
+// before any launch of an upload the switch would take effect for (a windows upload of n_windows windows, or the batch
+// dagcon_upload_haps derives from one): one lo / hi pair per window of the first batch
+int keep_check(Ctx *c, const bool windows, const uint32_t n_windows) {
+    if (!c->o_keep.on || !windows || c->keep_lo.size() == n_windows) return DAGCON_OK;
+    return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_window_keep: lo / hi for %zu windows, the first batch has %u", c->keep_lo.size(), n_windows);
+}
+
+int keep_room(Ctx *c) {
+    if (!c->o_keep.batch) return DAGCON_OK;
+    ENSURE(c, c->run.keep, c->seg_cap * sizeof(uint4));
+    return DAGCON_OK;
+}
+
+void keep_params(Ctx *c, DgParams &p) {
+    if (!c->o_keep.batch) return;
+    p.keep_out = c->run.keep.as<uint4>();
+    p.keep_lo = c->in.keep_lo.as<const uint32_t>(); p.keep_hi = c->in.keep_hi.as<const uint32_t>();
+}
+
+// behind k_bp_join and the edit kernels, in every execution of the run: a wave per segment of the arena (seg_top is the device's)
+void keep_launch(Ctx *c, const DgParams &p) {
+    if (!c->o_keep.batch) return;
+    hipLaunchKernelGGL(k_win_keep, dim3((uint32_t)((c->seg_cap + 3) / 4)), dim3(256), 0, c->stream, p);
+}
+
+// behind upload_impl: each target's lo and hi.  A windows upload: target t is window t; dagcon_upload_haps: derived target
+// d takes those of src_target[d]
+int keep_arm(Ctx *c, const std::vector<uint32_t> *src_target) {
+    if (!c->o_keep.batch) return DAGCON_OK;
+    const uint32_t T = c->T;
+    std::vector<uint32_t> lo((size_t)T), hi((size_t)T);
+    for (uint32_t t = 0; t < T; t++) {
+        const uint32_t w = src_target ? (*src_target)[t] : t;
+        if (w >= c->keep_lo.size()) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_window_keep: lo / hi for %zu windows, target %u is window %u", c->keep_lo.size(), t, w);
+        lo[t] = c->keep_lo[w]; hi[t] = c->keep_hi[w];
+    }
+    UPLOAD(c, c->in.keep_lo, lo);
+    UPLOAD(c, c->in.keep_hi, hi);
+    HIPCHK(c, hipStreamSynchronize(c->stream));                   // (lo and hi are locals)
+    return DAGCON_OK;
+}
+
+}  // namespace
+
+int dagcon_set_window_keep(dagcon_ctx *ctx, const dagcon_window_keep_opts *o) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!(c->opts.flags & DAGCON_FLAG_BASE_POS))
+        return fail(c, DAGCON_ERR_STATE, "dagcon_set_window_keep on a context created without DAGCON_FLAG_BASE_POS");
+    if (!o) { c->o_keep.on = false; return DAGCON_OK; }
+    if (o->n && (!o->lo || !o->hi)) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_window_keep: lo / hi is NULL");
+    for (uint32_t t = 0; t < o->n; t++)
+        if (o->lo[t] > o->hi[t]) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_window_keep: window %u has lo %u above hi %u", t, o->lo[t], o->hi[t]);
+    c->keep_lo.assign(o->lo, o->lo + o->n); c->keep_hi.assign(o->hi, o->hi + o->n);
+    c->o_keep.on = true;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_window_keep(dagcon_ctx *ctx, dagcon_window_keep *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (int r = need(c, c->o_keep, "dagcon_fetch_window_keep")) return r;
+    KeepOut &o = c->r_keep;
+    if (!c->o_keep.fetched) {
+        // the copy dagcon_fetch left out, 16 bytes a segment, and the records from the device's segment order into that of
+        // dagcon_results: the segments of every target that came through, as unpack_segments lists them
+        HIPCHK(c, hipSetDevice(c->device));
+        const StatBlock &sb = c->sb;
+        const uint32_t *m_tfail = sb.h<uint32_t>(sb.o_tfail), *m_n_seg = sb.h<uint32_t>(sb.o_n_seg);
+        const uint64_t *m_seg_first = sb.h<uint64_t>(sb.o_seg_first);
+        const uint64_t nseg = c->h_st.seg_top;
+        std::vector<uint32_t> rec((size_t)nseg * 4);
+        if (c->T && nseg) HIPCHK(c, d2h(c, rec.data(), c->run.keep.p, (size_t)nseg * 16));
+        o.i0.clear(); o.i1.clear(); o.p_first.clear(); o.p_last.clear();
+        for (uint32_t t = 0; t < c->T; t++) {
+            if (!c->h_tactive[t] || m_tfail[t]) continue;
+            for (uint32_t i = 0; i < m_n_seg[t]; i++) {
+                const uint64_t s = m_seg_first[t] + i, x = o.i0.size();
+                if (s >= nseg || x >= c->r_seq_len.size()) return fail(c, DAGCON_ERR_INTERNAL, "k_win_keep: segment %llu of target %u of %llu segments", (unsigned long long)s, t, (unsigned long long)nseg);
+                const uint32_t *r = &rec[(size_t)s * 4];
+                if (r[0] > r[1] || r[1] > c->r_seq_len[x] || (r[0] == r[1] && (r[0] | r[2] | r[3])))
+                    return fail(c, DAGCON_ERR_INTERNAL, "k_win_keep: segment %u of target %u has the part [%u, %u) of %u bases, positions %u and %u", i, t, r[0], r[1], c->r_seq_len[x], r[2], r[3]);
+                o.i0.push_back(r[0]); o.i1.push_back(r[1]); o.p_first.push_back(r[2]); o.p_last.push_back(r[3]);
+            }
+        }
+        if (o.i0.size() != c->r_seq_len.size())
+            return fail(c, DAGCON_ERR_INTERNAL, "k_win_keep: %zu records for %zu segments", o.i0.size(), c->r_seq_len.size());
+        pad(o.i0, o.i1, o.p_first, o.p_last);
+        c->o_keep.fetched = true;
+    }
+    out->n_segments = o.i0.size() - 1;
+    out->i0 = o.i0.data(); out->i1 = o.i1.data(); out->p_first = o.p_first.data(); out->p_last = o.p_last.data();
+    return DAGCON_OK;
+}
+
 // ---- the pipeline's calls: every output in the order of its launches ----
 namespace {
 
 int outputs_room(Ctx *c) {
     int r;
     if ((r = edits_room(c)) || (r = pile_room(c)) || (r = reads_room(c)) || (r = hap_room(c)) || (r = winphase_room(c))) return r;
-    if ((r = alleles_room(c)) || (r = calls_room(c))) return r;
+    if ((r = alleles_room(c)) || (r = calls_room(c)) || (r = keep_room(c))) return r;
     return join_room(c);
 }
 
 void outputs_params(Ctx *c, DgParams &p) {
-    edits_params(c, p); pile_params(c, p); reads_params(c, p); hap_params(c, p); winphase_params(c, p); alleles_params(c, p); join_params(c, p); calls_params(c, p);
+    edits_params(c, p); pile_params(c, p); reads_params(c, p); hap_params(c, p); winphase_params(c, p); alleles_params(c, p); join_params(c, p); calls_params(c, p); keep_params(c, p);
 }
 
 // between k_bp_join and the last event of a run that goes as far as bestPath (T > 0)
@@ -1050,6 +1159,7 @@ int outputs_launch(Ctx *c, const DgParams &p) {
     int r;
     edits_launch(c, p);
     calls_launch(c, p);
+    keep_launch(c, p);
     if ((r = pile_launch(c, p)) || (r = reads_launch(c, p))) return r;
     winphase_launch(c, p);
     if ((r = alleles_launch(c, p)) || (r = join_launch(c, p))) return r;

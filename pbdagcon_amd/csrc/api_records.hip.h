@@ -303,6 +303,7 @@ int plan_whole(Ctx *c, const dagcon_cigar_batch *b, CigarScan &sc, const CigarVe
 
 int check_windows(Ctx *c, const dagcon_cigar_batch *b, const dagcon_windows *wn) {
     const uint32_t T = b->n_targets, W = wn->n_windows;
+    if (int r = keep_check(c, true, W)) return r;                 // (dagcon_set_window_keep: before any launch)
     if (W && (!wn->target || !wn->begin || !wn->end)) return fail(c, DAGCON_ERR_INVALID_ARG, "window arrays are NULL");
     if (T && !b->tlen) return fail(c, DAGCON_ERR_INVALID_ARG, "tlen/t_off/rec_begin is NULL");
     for (uint32_t w = 0; w < W; w++) {
@@ -514,6 +515,7 @@ int records_finish(dagcon_ctx *ctx, Ctx *c, const dagcon_cigar_batch *b, const d
     if ((r = cigar_expand(c, b, src, sc, pl))) return r;
     if ((r = cigar_hand_over(ctx, c, b, pl, v, pk))) return r;
     if (c->o_wl.batch && (r = window_phase_arm(c, wn))) return r;
+    if ((r = keep_arm(c, nullptr))) return r;
     return c->o_ed.batch ? edits_arm(c, b, wn) : DAGCON_OK;
 }
 
@@ -541,6 +543,7 @@ int upload_cs(dagcon_ctx *ctx, const dagcon_cs_batch *b, const dagcon_windows *w
     uint32_t n = 0;
     int r = check_targets(c, T, b->tlen, b->t_off, b->rec_begin, b->t_blob, b->t_bytes, b->pos && b->q_len && b->cs_off && b->cs_len, n);
     if (r != DAGCON_OK) return r;
+    if (wn && (r = keep_check(c, true, wn->n_windows))) return r;   // (before k_cs_scan: check_windows comes behind it)
     std::vector<uint64_t> q_off((size_t)n + 1, 0);
     for (uint32_t a = 0; a < n; a++) {
         if (b->cs_off[a] > b->cs_bytes || b->cs_len[a] > b->cs_bytes - b->cs_off[a]) return fail(c, DAGCON_ERR_INVALID_ARG, "record %u runs past cs_blob", a);

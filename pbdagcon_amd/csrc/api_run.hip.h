@@ -443,6 +443,7 @@ static int upload_impl(dagcon_ctx *ctx, const dagcon_batch *b, const void *dev_q
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     c->drop_results(Fresh::UPLOAD);
     latch_outputs(c, kind);
+    if (kind != Intake::HAPS) { c->win_first = kind == Intake::WINDOWS; c->win_n = b->n_targets; }     // (the batch a dagcon_upload_haps derives from)
     c->h_aln_src.clear();
     c->h_cig_bad.clear();
     c->rs_valid = false;
@@ -774,8 +775,9 @@ static int fetch_plan(Ctx *c, FetchPlan &f) {
     f.full = !(c->opts.flags & (DAGCON_FLAG_STOP_AFTER_BUILD | DAGCON_FLAG_STOP_AFTER_MERGE));
     f.want_sup = f.full && (c->opts.flags & DAGCON_FLAG_BASE_SUPPORT); f.want_pos = f.full && (c->opts.flags & DAGCON_FLAG_BASE_POS);
     if ((r = outputs_plan(c, f))) return r;
-    // edits on: the edits come instead of the positions, which stay on the device for dagcon_fetch_positions to ask for
-    f.lazy_pos = f.want_pos && f.want_ed;
+    // edits on: the edits come instead of the positions, which stay on the device for dagcon_fetch_positions to ask for; so
+    // they do where the kept parts are in effect (dagcon_set_window_keep): 16 bytes a segment stand in for 4 a base
+    f.lazy_pos = f.want_pos && (f.want_ed || c->o_keep.batch);
     c->drop_results(Fresh::FETCH);
     c->r_nb = f.nb;
     if (f.want_sup && (r = c->r_sup.reserve(c, 2 * (size_t)(f.nb + 1) * 2))) return r;     // (two halves of nb + 1 entries)
@@ -887,7 +889,7 @@ int dagcon_fetch_positions(dagcon_ctx *ctx, const uint32_t **pos, uint64_t *n) {
     if (!(c->opts.flags & DAGCON_FLAG_BASE_POS))
         return fail(c, DAGCON_ERR_STATE, "dagcon_fetch_positions on a context created without DAGCON_FLAG_BASE_POS");
     if (c->pos_pending) {
-        // edits on: the copy dagcon_fetch left out; the kind bit the edit kernels read stays on the device
+        // edits or the kept parts on: the copy dagcon_fetch left out; the kind bit the edit kernels read stays on the device
         HIPCHK(c, hipSetDevice(c->device));
         c->r_pos.resize(c->r_nb + 1);
         if (c->r_nb) HIPCHK(c, d2h(c, c->r_pos.data(), c->run.pos.p, c->r_nb * 4));

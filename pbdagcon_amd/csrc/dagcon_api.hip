@@ -40,6 +40,7 @@
 #include "k_alleles.hip.h"
 #include "k_join.hip.h"
 #include "k_winlink.hip.h"
+#include "k_keep.hip.h"
 #include "host/alleles.h"
 #include "api_ctx.h"
 #include "api_run.hip.h"

@@ -304,6 +304,10 @@ struct DgParams {
     // k_hap_calls.hip.h.  Last, so that every field above keeps its offset ----
     uint8_t *hc_state;             // [ed_cap] parallel to ed_out: DG_HC_*
     unsigned long long *hc_mate;   // [ed_cap] parallel to ed_out: the partner's edit (index into ed_out), all ones: none
+    // ---- the kept part of every segment (dagcon_set_window_keep on a windows upload or on the batch dagcon_upload_haps
+    // derives from one; NULL otherwise): k_keep.hip.h.  Last, so that every field above keeps its offset ----
+    uint4 *keep_out;               // [seg_cap] in the order of seg_r0 / seg_r1: x = the segment's target (k_bp_join), then i0, i1, p_first, p_last (k_win_keep)
+    const uint32_t *keep_lo, *keep_hi;     // [T] a target's (a window's) lo and hi
 };
 #define DG_HAP_REC 8u
 #define DG_SR_TAKEN 0x80000000u

@@ -76,6 +76,8 @@ struct Opts {
     bool want_edits() const { return !edits.empty() || !vcf.empty() || !hap.vcf.empty(); }
     bool want_edit_support() const { return !vcf.empty() || !hap.vcf.empty(); }   // (--hap-vcf FILE: the edits with their support, for both runs)
     DgPileOpts pile;                   // --pileup FILE, --sites FILE [--site-min-frac F] [--site-min-count N] (every mode): what the alignments show per position
+    std::string hap_contigs, hap_windows;   // --hap-contigs FILE, --hap-windows FILE (with --window --phase-windows): phased contigs across windows (hap_contigs.h)
+    bool want_hc() const { return !hap_contigs.empty() || !hap_windows.empty(); }
     DgWinPhaseOpts wp;                 // --phase-windows [--phase-min-links N] [--phase-max-conflict F]: --site-reads / --haplotag with --window, the windows' labels joined (windows.h)
     DgSiteReadOpts sr;                 // --site-reads FILE, --haplotag FILE (whole targets, not -a): which read shows which allele at the sites; a two-way split
     DgHapOpts hap;                     // --hap-consensus FILE, --hap-sites FILE (where --haplotag goes): a consensus per group of the split, the split's tally; --hap-vcf FILE (records): the groups' edits paired
@@ -99,7 +101,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [--site-alleles FILE] [--site-vcf FILE] [--joined-alleles FILE] [--joined-vcf FILE] [--hap-vcf FILE] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [--site-alleles FILE] [--site-vcf FILE] [--joined-alleles FILE] [--joined-vcf FILE] [--hap-vcf FILE] [--window W --phase-windows --hap-contigs FILE [--hap-windows FILE]] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -293,6 +295,22 @@ void usage(FILE *f) {
             "                      targets dealt round-robin, records still printed in input order\n"
             "  --contexts N        consensus workers (thread + context) per GPU, 1..4: a batch's upload and formatting run\n"
             "                      beside another batch's kernels (default: 2 for inputs of several batches, else 1)\n"
+            "  --hap-contigs FILE  with --window and --phase-windows (either this or --hap-windows stands in for --site-reads /\n"
+            "                      --haplotag there): two phased sequences per phase block.  Every window whose reads split\n"
+            "                      (--hap-min-sites, --hap-min-reads as for --hap-consensus) is run again as its two read groups,\n"
+            "                      named in the block's orientation, and the groups' consensus is joined per label across the\n"
+            "                      windows as the plain stitch joins the windows: a part continues the piece before it when both\n"
+            "                      were cut at the core boundary between two neighbouring windows of one block.  An unsplit\n"
+            "                      window, a failed one and a block boundary end both contigs.  FASTA, >RNAME/hap{1|2}/PS/t0_t1\n"
+            "                      in target coordinates, PS as in --haplotag; records by t0, hap1 first; pieces shorter than -m\n"
+            "                      are dropped.  The cut of every segment at its window's core is made on the GPU (16 bytes a\n"
+            "                      segment come back, no per-base positions); stdout and every other file do not change.\n"
+            "                      Honours --site-min-*, --hap-min-* and --phase-min-links / --phase-max-conflict.  Not with -a,\n"
+            "                      --polish.  This build's own rule, parity unpinned\n"
+            "  --hap-windows FILE  the same inputs: one line per window, #window RNAME BEGIN END PS N1 N2 N0 SEP AGREE DISAGREE SPLIT\n"
+            "                      (the core, and the window's tally), then one line per site with a phase inside the core,\n"
+            "                      RNAME POS PHASE P1 M1 P2 M2 with POS 1-based in target coordinates; all in the block's\n"
+            "                      orientation (a flipped window's N1 / N2 and P1 M1 / P2 M2 change places, PHASE changes sign)\n"
             "  <input>             BLASR -m 5 file (.pre with -a, SAM with --sam, BAM with --bam, PAF with --paf) sorted by target, or - for stdin\n"
             "  version 0.3 (dagcon-mi355x)\n");
 }
@@ -383,6 +401,14 @@ int parse_args(int argc, char **argv, Opts &o) {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --hap-vcf needs a file name\n"); return 2; }
             o.hap.vcf = argv[++i];
         }
+        else if (a == "--hap-contigs") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --hap-contigs needs a file name\n"); return 2; }
+            o.hap_contigs = argv[++i];
+        }
+        else if (a == "--hap-windows") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --hap-windows needs a file name\n"); return 2; }
+            o.hap_windows = argv[++i];
+        }
         else if (a == "--hap-min-sites") { if (!need(&o.hap.min_sites)) return 2; o.hap.sites_set = true; }
         else if (a == "--hap-min-reads") { if (!need(&o.hap.min_reads)) return 2; o.hap.reads_set = true; }
         else if (a == "--site-min-frac") {
@@ -464,13 +490,15 @@ int parse_args(int argc, char **argv, Opts &o) {
     if (!o.vcf.empty() && !records) { fprintf(stderr, "PARSE ERROR: --vcf needs --sam, --bam or --paf\n"); return 2; }
     if (!o.vcf.empty() && o.dump) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --dump-parsed (nothing is run, the file would not be written)\n"); return 2; }
     if (!o.vcf.empty() && o.window) { fprintf(stderr, "PARSE ERROR: --vcf does not go with --window (the stitch splits and fuses edits: a fused edit has no single count)\n"); return 2; }
-    if ((o.pile.frac_set || o.pile.count_set) && o.pile.sites.empty() && !o.want_sr()) { fprintf(stderr, "PARSE ERROR: --site-min-frac and --site-min-count need --sites\n"); return 2; }
+    if (o.want_hc() && (!o.window || !o.wp.on || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --hap-contigs and --hap-windows need --window and --phase-windows and do not go with -a or --polish\n"); return 2; }
+    if (o.want_hc() && o.dump) { fprintf(stderr, "PARSE ERROR: --hap-contigs and --hap-windows do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
+    if ((o.pile.frac_set || o.pile.count_set) && o.pile.sites.empty() && !o.want_sr() && !o.want_hc()) { fprintf(stderr, "PARSE ERROR: --site-min-frac and --site-min-count need --sites\n"); return 2; }
     if (!o.hap.vcf.empty() && !records) { fprintf(stderr, "PARSE ERROR: --hap-vcf needs --sam, --bam or --paf (REF comes from the target's bases)\n"); return 2; }
-    if ((o.hap.sites_set || o.hap.reads_set) && !o.hap.on()) { fprintf(stderr, "PARSE ERROR: --hap-min-sites and --hap-min-reads need --hap-consensus or --hap-sites\n"); return 2; }
+    if ((o.hap.sites_set || o.hap.reads_set) && !o.hap.on() && !o.want_hc()) { fprintf(stderr, "PARSE ERROR: --hap-min-sites and --hap-min-reads need --hap-consensus or --hap-sites\n"); return 2; }
     if (o.hap.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
     if (o.hap.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
     if (o.wp.on && !o.window) { fprintf(stderr, "PARSE ERROR: --phase-windows needs --window\n"); return 2; }
-    if (o.wp.on && !o.sr.on()) { fprintf(stderr, "PARSE ERROR: --phase-windows needs --site-reads FILE or --haplotag FILE\n"); return 2; }
+    if (o.wp.on && !o.sr.on() && !o.want_hc()) { fprintf(stderr, "PARSE ERROR: --phase-windows needs --site-reads FILE or --haplotag FILE\n"); return 2; }
     if ((o.wp.links_set || o.wp.conflict_set) && !o.wp.on) { fprintf(stderr, "PARSE ERROR: --phase-min-links and --phase-max-conflict need --phase-windows\n"); return 2; }
     if (o.sr.on() && ((o.window && !o.wp.on) || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
     if (o.sr.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --site-reads and --haplotag do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
@@ -589,6 +617,7 @@ bool g_vcf_bad = false;
 FILE *g_pileup = nullptr, *g_sites = nullptr;              // --pileup FILE, --sites FILE, written batch by batch in output order
 FILE *g_site_reads = nullptr, *g_haplotag = nullptr;       // --site-reads FILE, --haplotag FILE, the same way
 FILE *g_hap_out = nullptr, *g_hap_sites = nullptr;         // --hap-consensus FILE, --hap-sites FILE, the same way
+FILE *g_hap_contigs = nullptr, *g_hap_windows = nullptr;   // --hap-contigs FILE, --hap-windows FILE, the same way
 FILE *g_hap_vcf = nullptr, *g_hap_vcf_lines = nullptr;     // --hap-vcf FILE, as --site-vcf below: the records wait in an unnamed temporary file
 std::string g_hap_vcf_contigs;
 FILE *g_site_alleles = nullptr;                            // --site-alleles FILE, the same way
@@ -1593,6 +1622,8 @@ int main(int argc, char **argv) {
     if (!o.hap.consensus.empty() && !(g_hap_out = fopen(o.hap.consensus.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.consensus.c_str()); return 1; }
     if (!o.hap.sites.empty() && !(g_hap_sites = fopen(o.hap.sites.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.sites.c_str()); return 1; }
     if (!o.hap.vcf.empty() && (!(g_hap_vcf = fopen(o.hap.vcf.c_str(), "w")) || !(g_hap_vcf_lines = tmpfile()))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.vcf.c_str()); return 1; }
+    if (!o.hap_contigs.empty() && !(g_hap_contigs = fopen(o.hap_contigs.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap_contigs.c_str()); return 1; }
+    if (!o.hap_windows.empty() && !(g_hap_windows = fopen(o.hap_windows.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap_windows.c_str()); return 1; }
     if (!o.al.alleles.empty() && !(g_site_alleles = fopen(o.al.alleles.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.al.alleles.c_str()); return 1; }
     if (!o.al.vcf.empty() && (!(g_site_vcf = fopen(o.al.vcf.c_str(), "w")) || !(g_site_vcf_lines = tmpfile()))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.al.vcf.c_str()); return 1; }
     if (!o.jn.alleles.empty() && !(g_joined_alleles = fopen(o.jn.alleles.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.jn.alleles.c_str()); return 1; }
@@ -1624,7 +1655,8 @@ int main(int argc, char **argv) {
         }
         const std::pair<FILE **, const std::string *> files[] = {{&g_pileup, &o.pile.pileup}, {&g_sites, &o.pile.sites}, {&g_site_reads, &o.sr.site_reads}, {&g_haplotag, &o.sr.haplotag},
                                                                  {&g_site_alleles, &o.al.alleles}, {&g_site_vcf, &o.al.vcf}, {&g_joined_alleles, &o.jn.alleles}, {&g_joined_vcf, &o.jn.vcf},
-                                                                 {&g_hap_out, &o.hap.consensus}, {&g_hap_sites, &o.hap.sites}, {&g_hap_vcf, &o.hap.vcf}};
+                                                                 {&g_hap_out, &o.hap.consensus}, {&g_hap_sites, &o.hap.sites}, {&g_hap_vcf, &o.hap.vcf},
+                                                                 {&g_hap_contigs, &o.hap_contigs}, {&g_hap_windows, &o.hap_windows}};
         for (const auto &f : files) {
             if (!*f.first) continue;
             const bool bad = fclose(*f.first) != 0 || g_pile_bad;
@@ -1638,6 +1670,7 @@ int main(int argc, char **argv) {
     if (o.window && !o.dump) {
         DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0], o.pick, o.edits.empty() ? nullptr : o.edits.c_str(),
                      g_pileup, g_sites, o.pile.min_count, o.pile.min_frac_ppm, g_site_reads, g_haplotag, o.wp};
+        wo.hap_contigs = g_hap_contigs; wo.hap_windows = g_hap_windows; wo.hap_min_sites = o.hap.min_sites; wo.hap_min_reads = o.hap.min_reads;
         if (o.kind == DG_REC_PACKED) { DgBamSource src(bam, ref); return close_pile(dg_run_windows(wo, src, ref)); }
         if (o.kind == DG_REC_PACKED_MD) { DgBamMdSource src(bam, ref); return close_pile(dg_run_windows(wo, src, ref)); }
         if (o.kind == DG_REC_PLAIN_MD) { DgSamMdSource src(in.data, in.size, ref); return close_pile(dg_run_windows(wo, src, ref)); }

@@ -51,6 +51,11 @@
 // and the host's part of the rule, include/dagcon.h rule 9 the rule).  Every group is uploaded with the pile-up, the site
 // reads with phase on and dagcon_set_window_phase; inside a group the links are the device's, between two groups the host
 // links the one pair of windows from the pieces it kept of the last window, and orientation and block carry over.
+//
+// The phased contigs (--phase-windows with --hap-contigs FILE / --hap-windows FILE; hap_contigs.h has the stitch, the
+// records and the lines).  Every group is also uploaded with dagcon_set_hap_consensus; behind the group's own results the
+// derived batch of its split windows runs in the block's orientation (dagcon_upload_haps_swapped with the windows' flip)
+// under dagcon_set_window_keep with the windows' cores, and its segments are joined per label from the keep records.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -62,6 +67,7 @@
 #include "../../../include/dagcon.h"
 #include "bam.h"
 #include "fastq.h"
+#include "hap_contigs.h"
 #include "intake.h"
 #include "pileup.h"
 #include "sam.h"
@@ -173,6 +179,9 @@ struct DgWinOpts {
     uint32_t site_min_count = 0, site_min_ppm = 0;
     FILE *site_reads = nullptr, *haplotag = nullptr;       // --phase-windows with --site-reads / --haplotag: open files, or NULL
     DgWinPhaseOpts wp;
+    FILE *hap_contigs = nullptr, *hap_windows = nullptr;   // --phase-windows with --hap-contigs / --hap-windows: open files, or NULL
+    uint32_t hap_min_sites = 0, hap_min_reads = 0;         // --hap-min-sites / --hap-min-reads (0: the library's defaults)
+    bool hc() const { return hap_contigs || hap_windows; }
 };
 
 // SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
@@ -318,6 +327,19 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         const dagcon_window_phase_opts wo = {o.wp.min_links, o.wp.max_conflict_ppm};
         if ((rc = dagcon_set_site_reads(ctx, &so)) != DAGCON_OK || (rc = dagcon_set_window_phase(ctx, &wo)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); if (ef) fclose(ef); dagcon_destroy(ctx); return 1; }
     }
+    if (o.hc()) {
+        const dagcon_hap_opts ho = {o.hap_min_sites, o.hap_min_reads};
+        if ((rc = dagcon_set_hap_consensus(ctx, &ho)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); if (ef) fclose(ef); dagcon_destroy(ctx); return 1; }
+    }
+    // --hap-contigs: the two labels' pieces of the current target of the derived batches (its state carries across the groups)
+    DgHapStitch hst[2];
+    long long hc_tgt = -1;
+    std::string contigs_out, hapwin_out;
+    unsigned long long n_derived = 0;
+    auto flush_contigs = [&]() {
+        if (hc_tgt >= 0 && o.hap_contigs) dg_hap_contig_records(contigs_out, tgts[(size_t)hc_tgt].name, hst, o.min_len, [&](uint64_t block) { return (uint64_t)wins[block].c0 + 1u; });
+        hst[0].reset(); hst[1].reset();
+    };
     // --phase-windows: per record of the current target its pieces' votes and its signed entries inside the cores; the
     // last window of the group before (its target, its link, its taken pieces) for the link across the groups
     struct RecAcc { bool taken = false; uint64_t sites = 0; std::vector<DgWpVote> pieces; };
@@ -450,6 +472,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         if (rc == DAGCON_OK && o.wp.on) rc = dagcon_fetch_site_reads(ctx, &sr);
         if (rc == DAGCON_OK && o.wp.on) rc = dagcon_fetch_window_phase(ctx, &wp);
         uint64_t sr_x = 0;                                     // the taken alignments ascend in their window: one walk
+        std::vector<DgWpLink> links(o.hc() ? w1 - w0 : 0, DgWpLink{0, 0});    // --hap-contigs / --hap-windows: every window's link in the run's terms
         DgWpLink first_link{0, 0};                             // the link of the group's first window, in the run's terms
         if (rc == DAGCON_OK && want_rebuilt && MD) {           // REF of the edits and of the pile-up lines: the group's stretch of every target, as the device rebuilt it
             const char *tb = nullptr;
@@ -490,6 +513,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
                 } else if (wp.block[g] == 0) link = DgWpLink{(uint8_t)(wp.flip[g] ^ first_link.flip), first_link.block};
                 else link = DgWpLink{wp.flip[g], (uint64_t)w0 + wp.block[g]};
                 n_blocks += link.block == k;
+                if (o.hc()) links[g] = link;
                 const bool turn = wp.block[g] == 0 && first_link.flip != 0;     // (the device oriented block 0 as if its first window were unlinked)
                 const uint32_t lo = w.c0 - w.begin, hi = w.c1 - w.begin;
                 for (uint64_t x = x0; x < sr_x; x++) {
@@ -531,6 +555,55 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
                        o.fastq ? sup.weight + off : nullptr, o.fastq ? sup.depth + off : nullptr, ef ? &se : nullptr);
             }
         }
+        // ---- the derived batch of the group's split windows, in the block's orientation (last: it takes the place of
+        // everything the fetches above point at) ----
+        if (o.hc() && status == 0) {
+            const uint32_t nw = (uint32_t)(w1 - w0);
+            dagcon_hap_tally ht;
+            memset(&ht, 0, sizeof ht);
+            if ((rc = dagcon_fetch_hap_tally(ctx, &ht)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); status = 1; break; }
+            std::vector<uint32_t> k_lo(nw), k_hi(nw);
+            std::vector<uint8_t> swap(nw);
+            for (uint32_t g = 0; g < nw; g++) {
+                const Win &w = wins[w0 + g];
+                k_lo[g] = w.c0 - w.begin; k_hi[g] = w.c1 - w.begin; swap[g] = links[g].flip;
+                if (!o.hap_windows) continue;
+                const std::string &name = tgts[w.tgt].name;
+                const bool flip = links[g].flip != 0;
+                dg_hap_window_line(hapwin_out, name, w.c0, w.c1, (uint64_t)wins[links[g].block].c0 + 1u, ht.n1[g], ht.n2[g], ht.n0[g], ht.n_sep[g], ht.agree[g], ht.disagree[g], ht.split[g], flip);
+                for (uint64_t s = ps.site_begin[g]; s < ps.site_begin[g + 1]; s++)
+                    if (sr.phase[s] && ps.pos[s] >= k_lo[g] && ps.pos[s] < k_hi[g])
+                        dg_hap_window_site_line(hapwin_out, name, (uint64_t)ps.pos[s] + w.begin + 1u, sr.phase[s], ht.site_counts + 4 * s, flip);
+            }
+            if (o.hap_contigs) {
+                const dagcon_window_keep_opts ko = {nw, k_lo.data(), k_hi.data()};
+                dagcon_results r2;
+                dagcon_hap_map hm;
+                dagcon_window_keep wk;
+                memset(&hm, 0, sizeof hm); memset(&wk, 0, sizeof wk);
+                if ((rc = dagcon_set_window_keep(ctx, &ko)) == DAGCON_OK) rc = dagcon_upload_haps_swapped(ctx, swap.data());
+                if (rc == DAGCON_OK) rc = dagcon_run(ctx);
+                if (rc == DAGCON_OK) rc = dagcon_fetch(ctx, &r2);
+                if (rc == DAGCON_OK) rc = dagcon_fetch_hap_map(ctx, &hm);
+                if (rc == DAGCON_OK) rc = dagcon_fetch_window_keep(ctx, &wk);          // (the derived batch's positions stay on the device)
+                if (rc == DAGCON_OK) rc = dagcon_set_window_keep(ctx, nullptr);       // (the next group's own upload runs without it)
+                if (rc != DAGCON_OK || wk.n_segments != r2.n_segments) { fprintf(stderr, "pbdagcon: %s\n", rc != DAGCON_OK ? dagcon_last_error(ctx) : "the kept parts do not match the segments"); status = 1; break; }
+                for (uint32_t d = 0; d < hm.n_targets; d++) {
+                    const uint32_t g = hm.src_target[d];
+                    const Win &w = wins[w0 + g];
+                    if ((long long)w.tgt != hc_tgt) { flush_contigs(); hc_tgt = w.tgt; }
+                    if (r2.target_status[d] != DAGCON_OK)
+                        fprintf(stderr, "pbdagcon: warning: %s window [%u, %u) hap%u skipped (%s)\n", tgts[w.tgt].name.c_str(), w.begin, w.end, (unsigned)hm.label[d],
+                                dg_status_text(r2.target_status[d], MD ? kd.nonconforming : DG_CIGAR_UNFIT));
+                    for (uint64_t s = r2.seg_begin[d]; s < r2.seg_begin[d + 1]; s++)
+                        hst[hm.label[d] == 2u ? 1 : 0].add(w.idx, w.begin, links[g].block, r2.seq_blob + r2.seq_off[s], r2.seq_len[s], wk.i0[s], wk.i1[s], wk.p_first[s], wk.p_last[s]);
+                }
+                n_derived += hm.n_targets;
+            }
+            if (o.hap_windows && fwrite(hapwin_out.data(), 1, hapwin_out.size(), o.hap_windows) != hapwin_out.size()) { fprintf(stderr, "pbdagcon: error writing the --hap-windows file\n"); status = 1; }
+            if (o.hap_contigs && fwrite(contigs_out.data(), 1, contigs_out.size(), o.hap_contigs) != contigs_out.size()) { fprintf(stderr, "pbdagcon: error writing the --hap-contigs file\n"); status = 1; }
+            hapwin_out.clear(); contigs_out.clear();
+        }
         if (o.pileup && fwrite(pile_out.data(), 1, pile_out.size(), o.pileup) != pile_out.size()) { fprintf(stderr, "pbdagcon: error writing the --pileup file\n"); status = 1; }
         if (o.sites && fwrite(site_out.data(), 1, site_out.size(), o.sites) != site_out.size()) { fprintf(stderr, "pbdagcon: error writing the --sites file\n"); status = 1; }
         if (o.site_reads && fwrite(reads_out.data(), 1, reads_out.size(), o.site_reads) != reads_out.size()) { fprintf(stderr, "pbdagcon: error writing the --site-reads file\n"); status = 1; }
@@ -540,7 +613,12 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
     }
     if (status == 0 && !flush_target()) status = 1;
     if (o.haplotag && !tags_out.empty() && fwrite(tags_out.data(), 1, tags_out.size(), o.haplotag) != tags_out.size()) { fprintf(stderr, "pbdagcon: error writing the --haplotag file\n"); status = 1; }
+    if (status == 0 && o.hap_contigs) {
+        flush_contigs();
+        if (fwrite(contigs_out.data(), 1, contigs_out.size(), o.hap_contigs) != contigs_out.size()) { fprintf(stderr, "pbdagcon: error writing the --hap-contigs file\n"); status = 1; }
+    }
     if (o.wp.on && o.verbose) fprintf(stderr, "pbdagcon: --phase-windows: %llu blocks over %zu windows\n", n_blocks, wins.size());
+    if (o.hap_contigs && o.verbose) fprintf(stderr, "pbdagcon: --hap-contigs: %llu derived windows\n", n_derived);
     unsigned long long over_error = 0, over_depth = 0;
     for (const Tgt &t : tgts)
         for (const uint8_t f : t.fate) { over_error += (f & DAGCON_FATE_MAX_ERROR) != 0; over_depth += (f & DAGCON_FATE_MAX_DEPTH) != 0; }

@@ -1145,6 +1145,8 @@ __global__ __launch_bounds__(64) void k_bp_join(DgParams p) {
         kept(p.pos_tmp0, p.pos_tmp, [&](const uint32_t x, const uint64_t o) { p.pos_out[o] = p.ed_seg ? x : x & ~DG_POS_BB; });
         // (edits: which target a segment belongs to, for the wave that scans it)
         if (p.ed_seg) for (uint32_t i = lane; i < nout; i += 64) p.ed_seg[so + i].tgt = t;
+        // (the kept parts: the same for k_win_keep, which replaces the word with the segment's record)
+        if (p.keep_out) for (uint32_t i = lane; i < nout; i += 64) p.keep_out[so + i] = make_uint4(t, 0u, 0u, 0u);
     }
     for (uint32_t i = lane; i < nout; i += 64) {
         p.seg_r0[so + i] = segs[2 * i];

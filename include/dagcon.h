@@ -729,6 +729,47 @@ typedef struct dagcon_window_keep {
 int dagcon_fetch_window_keep(dagcon_ctx *ctx, dagcon_window_keep *out);
 
 /*
+ * Site link: which sites are carried by the same reads as other sites near them, chosen on the device in front of the
+ * split (off by default; a context switch that needs dagcon_set_pileup and dagcon_set_site_reads with phase != 0 on at the
+ * same upload).  At thresholds a noisy pile-up needs, most sites are the reads' own errors and outvote the few real ones
+ * in rule 4; the reads that carry a real site's minor allele carry the minor allele of the real sites around it too, and
+ * an error's do not.  THIS BUILD'S OWN RULE, PARITY UNPINNED, in the terms of rules 1 to 4 of the site reads
+ * (tests/site_link_twin.py is its twin).  Everything is per target of the pipeline (with windows: per window).
+ * 13. 13.1 For site k let P_k be the taken alignments with M(x, k) = +1 (rule 3) and M_k those with M(x, k) = -1.
+ *     13.2 For two sites i != j of one target: pp = |P_i & P_j|, mm = |M_i & M_j|, pm = |P_i & M_j|, mp = |M_i & P_j|;
+ *          same = pp + mm, diff = pm + mp, lo = min(same, diff), hi = max(same, diff); cell = min(pp, mm) if same >= diff,
+ *          else min(pm, mp).  The two are PARTNERS iff lo * 1000000 <= max_conflict_ppm * (lo + hi) and cell >= min_cell,
+ *          in 64-bit integers.  same == diff == 0 gives cell = 0: no partners.
+ *     13.3 Only sites whose indices in the target's site list (ascending position, the order of
+ *          dagcon_fetch_pileup_sites) differ by at most `reach` are compared.
+ *     13.4 partners[k] is the number of partners of k; linked[k] = partners[k] >= min_partners.  A partner need not be
+ *          linked itself.
+ *     13.5 With the switch on, an entry at a site that is not linked has M = 0 in rule 4 (the split), in rule 6 (the
+ *          tally), in rule 9 and in the label counts of rules 8 and 10: everywhere a sign is read.  The entries, the
+ *          pile-up, the site list and the consensus do not change; a linked site keeps the sign of rule 3.
+ *     13.6 Defaults: max_conflict_ppm 100000, min_cell 3, min_partners 2, reach 256; a 0 in a field means its default
+ *          (1 ppm asks for no conflict at all).  They come from one experiment on synthetic reads (1 % substitutions,
+ *          10 % inserted and 4 % deleted bases, 40 reads deep, planted sites 1,000 bases apart) and from nothing else.
+ *     13.7 A failed target (target_status != DAGCON_OK) has no sites and so no entries in the arrays.
+ * dagcon_set_site_link: NULL turns it off; reach > 4096 is DAGCON_ERR_INVALID_ARG (the switch stays as it was).  The
+ * switch is read at the upload, whichever entry point makes it.  With any of the three switches off at the upload, or phase
+ * == 0, no kernel, buffer, memset, launch or copy differs from a context that never heard of it (k_sr_split tests one kernel
+ * argument, NULL then), and dagcon_fetch_site_link is DAGCON_ERR_STATE; the same before a dagcon_fetch, under
+ * DAGCON_FLAG_STOP_AFTER_BUILD / _MERGE and for the derived batch of dagcon_upload_haps.  With all on, the kernels of
+ * csrc/k_site_link.hip.h run between k_sr_walk and k_sr_split in every execution of the run, re-runs included; two bit
+ * rows a site ((deepest target's alignments + 63) / 64 words each) grow with the site arena.
+ * dagcon_fetch_site_link: 3 bytes a site, copied when it is called; the sites are those of dagcon_fetch_pileup_sites in
+ * their order.  Owned by the context, valid as long as the results of the same fetch.
+ */
+typedef struct dagcon_site_link_opts { uint32_t max_conflict_ppm, min_cell, min_partners, reach; } dagcon_site_link_opts;   /* 0: that field's default */
+int dagcon_set_site_link(dagcon_ctx *ctx, const dagcon_site_link_opts *o);    /* NULL: off (the default) */
+typedef struct dagcon_site_link {
+    uint64_t n_sites;                                 /* the sites of dagcon_fetch_pileup_sites, same order */
+    const uint16_t *partners; const uint8_t *linked;  /* [n_sites] */
+} dagcon_site_link;
+int dagcon_fetch_site_link(dagcon_ctx *ctx, dagcon_site_link *out);
+
+/*
  * Page-locked host memory for the input blobs (qstr / tstr / backbone): a caller that parses
  * alignment records straight into such a buffer gets its dagcon_upload at link speed instead of
  * through the driver's staging copies.  Optional: any host memory is accepted by dagcon_upload.

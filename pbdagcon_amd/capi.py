@@ -52,6 +52,7 @@ EXPORTS = [
     "dagcon_set_window_phase", "dagcon_fetch_window_phase",
     "dagcon_set_hap_calls", "dagcon_fetch_hap_calls",
     "dagcon_upload_haps_swapped", "dagcon_set_window_keep", "dagcon_fetch_window_keep",
+    "dagcon_set_site_link", "dagcon_fetch_site_link",
 ]
 HC_NOCOVER, HC_HET, HC_CLASH, HC_HOM = 0, 1, 2, 3
 HC_NONE = 0xFFFFFFFFFFFFFFFF
@@ -236,6 +237,18 @@ class WindowKeep(C.Structure):
                 ("p_first", C.POINTER(C.c_uint32)), ("p_last", C.POINTER(C.c_uint32))]
 
 
+class SiteLinkOpts(C.Structure):
+    """dagcon_site_link_opts: two sites are partners when at most max_conflict_ppm of the reads signed at both disagree and
+    the smaller of the two agreeing cells holds min_cell reads; a site is linked with min_partners partners among the
+    `reach` sites on either side; 0 in a field is its default: 100000, 3, 2, 256 (include/dagcon.h, rule 13)."""
+    _fields_ = [("max_conflict_ppm", C.c_uint32), ("min_cell", C.c_uint32), ("min_partners", C.c_uint32), ("reach", C.c_uint32)]
+
+
+class SiteLink(C.Structure):
+    """dagcon_site_link: partners and linked per site of dagcon_pileup_sites."""
+    _fields_ = [("n_sites", C.c_uint64), ("partners", C.POINTER(C.c_uint16)), ("linked", C.POINTER(C.c_uint8))]
+
+
 class Edits(C.Structure):
     """dagcon_edits: per segment its target span and its edits (include/dagcon.h has the definition)."""
     _fields_ = [("n_segments", C.c_uint64), ("n", C.c_uint64), ("seg_t0", C.POINTER(C.c_uint32)),
@@ -338,6 +351,8 @@ def load() -> C.CDLL:
     L.dagcon_upload_haps_swapped.argtypes = [vp, vp]
     L.dagcon_set_window_keep.argtypes = [vp, C.POINTER(WindowKeepOpts)]
     L.dagcon_fetch_window_keep.argtypes = [vp, C.POINTER(WindowKeep)]
+    L.dagcon_set_site_link.argtypes = [vp, C.POINTER(SiteLinkOpts)]
+    L.dagcon_fetch_site_link.argtypes = [vp, C.POINTER(SiteLink)]
     L.dagcon_upload_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int]
     L.dagcon_consensus_cigar_md.argtypes = [vp, C.POINTER(CigarBatch), C.POINTER(Windows), C.POINTER(MdTags), C.c_int,
                                             C.POINTER(Results)]
@@ -1133,6 +1148,25 @@ class Context:
         n = int(wk.n_segments)
         return {k: np.ctypeslib.as_array(getattr(wk, k), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
                 for k in ("i0", "i1", "p_first", "p_last")}
+
+    def set_site_link(self, max_conflict_ppm=0, min_cell=0, min_partners=0, reach=0):
+        """dagcon_set_site_link for every later upload made with set_pileup and set_site_reads(True) on: the device picks
+        the sites that the same reads carry as other sites near them (site_link()) and the split, the tally and every
+        label count take the other sites' entries as unsigned.  0 in a field: its default (100000, 3, 2, 256).
+        set_site_link(None): off."""
+        if max_conflict_ppm is None:
+            self._chk(self.L.dagcon_set_site_link(self.h, None))
+            return
+        o = SiteLinkOpts(max_conflict_ppm, min_cell, min_partners, reach)
+        self._chk(self.L.dagcon_set_site_link(self.h, C.byref(o)))
+
+    def site_link(self) -> dict:
+        """dagcon_fetch_site_link (copies): partners (uint16) and linked (uint8) per site of pileup_sites()."""
+        sl = SiteLink()
+        self._chk(self.L.dagcon_fetch_site_link(self.h, C.byref(sl)))
+        n = int(sl.n_sites)
+        return {"partners": np.ctypeslib.as_array(sl.partners, shape=(n,)).copy() if n else np.zeros(0, np.uint16),
+                "linked": np.ctypeslib.as_array(sl.linked, shape=(n,)).copy() if n else np.zeros(0, np.uint8)}
 
     def hap_map(self) -> dict:
         """dagcon_fetch_hap_map (copies): src_target (uint32) and label (uint8) per target of the derived batch, aln_begin

@@ -107,7 +107,8 @@ struct RunBufs {
     DevBuf jn_run, jn_sfirst, jn_rbeg, jn_cur, jn_nd, jn_deep, jn_toff, jn_key, jn_tcnt, jn_thap, jn_map, jn_idx, jn_ckey, jn_ccnt, jn_chap, jn_tot;
     DevBuf hc_state, hc_mate;                       // dagcon_set_hap_calls: a state byte and a mate index per edit, parallel to ed_out
     DevBuf keep;                                    // dagcon_set_window_keep: 16 B per segment, parallel to seg
-    std::array<DevBuf *, 113> all() {
+    DevBuf lk_rows, lk_partners, lk_linked;         // dagcon_set_site_link: two bit rows a site (cleared before every run), its partners, its linked byte
+    std::array<DevBuf *, 116> all() {
         return {&nmis, &n_lo, &n_hi, &n_start, &n_ins, &n_del, &ch_k0, &ch_next, &ch_w, &ch_tb, &ch_flag, &ch_src, &ch_out, &ch_adv, &n_lb, &norm_tmp, &ckpt,
                 &node_base, &n_nodes, &pool_base, &pool_size, &pool_top, &t_nins, &cov, &gcount, &gbase, &bid, &best, &queue, &score, &cns_tmp, &bp_tt,
                 &stk, &cuts, &cuts_bp, &bp_stat, &bp_len, &rd, &pro_state, &sh_cnt, &wl_first, &queue0, &bp_end, &bp_ab, &defer, &cns_tmp0, &cns,
@@ -116,10 +117,10 @@ struct RunBufs {
                 &hap_cnt, &hap_rec, &wl_cnt, &wl_block, &wl_flip, &wl_hap, &wl_phase,
                 &al_map, &al_idx, &al_soff, &al_cur, &al_nd, &al_deep, &al_toff, &al_srt, &al_tcnt, &al_thap, &al_ckey, &al_ccnt, &al_chap, &al_tot,
                 &jn_run, &jn_sfirst, &jn_rbeg, &jn_cur, &jn_nd, &jn_deep, &jn_toff, &jn_key, &jn_tcnt, &jn_thap, &jn_map, &jn_idx, &jn_ckey, &jn_ccnt, &jn_chap, &jn_tot,
-                &hc_state, &hc_mate, &keep};
+                &hc_state, &hc_mate, &keep, &lk_rows, &lk_partners, &lk_linked};
     }
 };
-static_assert(sizeof(RunBufs) == 113 * sizeof(DevBuf), "RunBufs::all() must name every member");
+static_assert(sizeof(RunBufs) == 116 * sizeof(DevBuf), "RunBufs::all() must name every member");
 // ArenaBufs: the arenas with a treatment of their own -- matC is cleared before every run, the others are filled under
 // DAGCON_POISON bits 1 (matA, matD), 2 (nodes, pool) and 4 (score_b, norm)
 struct ArenaBufs {
@@ -235,6 +236,11 @@ struct HapMapOut {
 struct KeepOut {
     std::vector<uint32_t> i0, i1, p_first, p_last;
 };
+// dagcon_fetch_site_link: per site of dagcon_fetch_pileup_sites, in the host's order
+struct SiteLinkOut {
+    std::vector<uint16_t> partners;
+    std::vector<uint8_t> linked;
+};
 // The kept alignments of a fetched run in the device's order (host_order builds it at the first fetch that needs it): each
 // one's index on the device and its stretch of the device's entry arrays.  Its target and the caller's index are
 // h_aln_tgt / h_aln_src at that index
@@ -342,7 +348,11 @@ struct Ctx {
     std::vector<uint32_t> keep_lo, keep_hi;
     bool win_first = false;
     uint32_t win_n = 0;
-    std::array<Output *, 10> outputs() { return {&o_ed, &o_evid, &o_pile, &o_sr, &o_al, &o_jn, &o_hap, &o_wl, &o_hc, &o_keep}; }
+    // dagcon_set_site_link (its buffers: run.lk_rows, run.lk_partners, run.lk_linked)
+    Output o_lk{"without the results of an upload made with dagcon_set_pileup, dagcon_set_site_reads (phase on) and dagcon_set_site_link on (a switch "
+                "off at the upload, no fetch yet, stopped before bestPath, or the batch is dagcon_upload_haps' own)"};
+    dagcon_site_link_opts lk_opts = {0u, 0u, 0u, 0u}, lk_batch_opts = {0u, 0u, 0u, 0u};
+    std::array<Output *, 11> outputs() { return {&o_ed, &o_evid, &o_pile, &o_sr, &o_al, &o_jn, &o_hap, &o_wl, &o_hc, &o_keep, &o_lk}; }
     // the growing arenas: run.ed_out (and run.evid beside it), run.pile_site, run.sr_site / sr_code.  The status block
     // holds 16 bytes for the edits' total, then 16 for the sites', whose second word is the entries'
     GrowArena ed_arena{"edits", DG_E_ED_OVF, true, &DgParams::ed_top, &DgParams::ed_cap};
@@ -387,6 +397,7 @@ struct Ctx {
     HapCallsOut r_hc;
     HapMapOut r_hapmap;
     KeepOut r_keep;
+    SiteLinkOut r_link;
     HostOrder order;
     bool sup_valid = false;             // r_sup holds the support of the results of the last fetch
 

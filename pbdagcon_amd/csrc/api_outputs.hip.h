@@ -1,5 +1,5 @@
 // api_outputs.hip.h -- the optional outputs of a run (edits and their support, the pile-up and its sites, the reads at the
-// sites, the window phase, the alleles, the joined sites, the haplotype tally, the hap calls, the kept parts), each one's host side in one place: its room, its kernel
+// sites, the window phase, the alleles, the joined sites, the haplotype tally, the hap calls, the kept parts, the site link), each one's host side in one place: its room, its kernel
 // parameters, its launches, its part of the fetch and its dagcon_set_* / dagcon_fetch_* entry points.  The pipeline
 // (api_run.hip.h) calls outputs_room, outputs_params, outputs_launch, outputs_upload and the outputs_plan / _copies /
 // _unpack steps of dagcon_fetch, at the end of this file; DESIGN.md says how to add an output.  (The entry points stand
@@ -11,7 +11,7 @@ namespace {
 
 // The dependency rule, once: which outputs the batch being uploaded runs with, and with which options (defaults filled
 // in).  Edits need a record upload and their support needs edits; the sites need the pile-up; the reads at the sites need
-// the sites; the alleles, the tally and the window phase need those reads, the last two with phase on; the window phase
+// the sites; the alleles, the tally, the site link and the window phase need those reads, the last three with phase on; the window phase
 // needs a windows upload; the joined sites need the alleles.  The batch of dagcon_upload_haps runs with none, whatever the
 // switches say (but for the kept parts, which need a windows upload or the batch derived from one and nothing else) --
 // unless dagcon_set_hap_calls is on and the batch it derives from ran with the edits latched (a record
@@ -41,6 +41,9 @@ void latch_outputs(Ctx *c, const Intake kind) {
     c->sr_batch_opts = c->sr_opts;
     c->hap_batch_opts = {c->hap_opts.min_sites ? c->hap_opts.min_sites : 2u, c->hap_opts.min_reads ? c->hap_opts.min_reads : 3u};
     c->wl_batch_opts = {c->wl_opts.min_links ? c->wl_opts.min_links : 3u, c->wl_opts.max_conflict_ppm ? c->wl_opts.max_conflict_ppm : 250000u};
+    c->o_lk.batch = c->o_lk.on && phased;
+    const dagcon_site_link_opts &lk = c->lk_opts;
+    c->lk_batch_opts = {lk.max_conflict_ppm ? lk.max_conflict_ppm : 100000u, lk.min_cell ? lk.min_cell : 3u, lk.min_partners ? lk.min_partners : 2u, lk.reach ? lk.reach : 256u};
 }
 
 // Whether the kernels behind the consensus ran in this batch: the launches below and every fetch ask here.  The sites'
@@ -316,6 +319,74 @@ int dagcon_fetch_pileup(dagcon_ctx *ctx, dagcon_pileup *out) {
     return DAGCON_OK;
 }
 
+// ---- the sites the same reads carry (k_site_link.hip.h): latched only with the split, whose launches it sits between ----
+namespace {
+
+int link_room(Ctx *c) {
+    if (!c->o_lk.batch) return DAGCON_OK;
+    const uint64_t words = (c->max_k + 63u) / 64u;
+    ENSURE(c, c->run.lk_rows, c->site_arena.cap * 2 * words * 8); ENSURE(c, c->run.lk_partners, c->site_arena.cap * 2); ENSURE(c, c->run.lk_linked, c->site_arena.cap);
+    return DAGCON_OK;
+}
+
+void link_params(Ctx *c, DgParams &p) {
+    if (!c->o_lk.batch) return;
+    p.lk_words = (c->max_k + 63u) / 64u; p.lk_row_cap = c->site_arena.cap * 2 * p.lk_words;
+    p.lk_rows = c->run.lk_rows.as<unsigned long long>(); p.lk_partners = c->run.lk_partners.as<uint16_t>(); p.lk_linked = c->run.lk_linked.as<uint8_t>();
+    p.lk_ppm = c->lk_batch_opts.max_conflict_ppm; p.lk_min_cell = c->lk_batch_opts.min_cell;
+    p.lk_min_partners = c->lk_batch_opts.min_partners; p.lk_reach = c->lk_batch_opts.reach;
+}
+
+// between k_sr_walk<true> and k_sr_split (reads_launch calls it there): the sites' kinds, the bit rows, the pairs.  The
+// rows start from zero in every execution, a re-run included; partners and linked are written for every site
+int link_launch(Ctx *c, const DgParams &p) {
+    if (!c->o_lk.batch || !reads_ran(c)) return DAGCON_OK;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemsetAsync(c->run.lk_rows.p, 0, p.lk_row_cap * 8, s));
+    hipLaunchKernelGGL(k_lk_kind, dim3((uint32_t)((p.site_cap + 255) / 256)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_lk_bits, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_lk_pairs, dim3((uint32_t)((p.site_cap + 3) / 4)), dim3(256), 0, s, p);
+    return DAGCON_OK;
+}
+
+}  // namespace
+
+int dagcon_set_site_link(dagcon_ctx *ctx, const dagcon_site_link_opts *o) {
+    if (!ctx) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!o) { c->o_lk.on = false; return DAGCON_OK; }
+    if (o->reach > DG_LK_MAX_REACH) return fail(c, DAGCON_ERR_INVALID_ARG, "dagcon_set_site_link: a reach of %u is more than %u", o->reach, DG_LK_MAX_REACH);
+    c->lk_opts = *o;
+    c->o_lk.on = true;
+    return DAGCON_OK;
+}
+
+int dagcon_fetch_site_link(dagcon_ctx *ctx, dagcon_site_link *out) {
+    if (!ctx || !out) return DAGCON_ERR_INVALID_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (int r = need(c, c->o_lk, "dagcon_fetch_site_link")) return r;
+    SiteLinkOut &o = c->r_link;
+    if (!c->o_lk.fetched) {
+        // the copies dagcon_fetch left out, 3 bytes a site, into the host's order of the sites: a failed target's go
+        HIPCHK(c, hipSetDevice(c->device));
+        const SitesOut &s = c->r_sites;
+        const uint64_t ns = s.n_dev;
+        std::vector<uint16_t> partners((size_t)ns + 1, 0);
+        std::vector<uint8_t> linked((size_t)ns + 1, 0);
+        if (ns && reads_ran(c)) { HIPCHK(c, d2h(c, partners.data(), c->run.lk_partners.p, (size_t)ns * 2)); HIPCHK(c, d2h(c, linked.data(), c->run.lk_linked.p, (size_t)ns)); }
+        o.partners.assign(s.pos.size() + 1, 0); o.linked.assign(s.pos.size() + 1, 0);
+        gather_sites(c, partners.data(), o.partners.data());
+        gather_sites(c, linked.data(), o.linked.data());
+        for (size_t k = 0; k < s.pos.size(); k++)
+            if (o.linked[k] > 1u || o.partners[k] > 2u * DG_LK_MAX_REACH || (o.linked[k] != 0) != (o.partners[k] >= c->lk_batch_opts.min_partners))
+                return fail(c, DAGCON_ERR_INTERNAL, "k_lk_pairs: site %zu has %u partners and linked %u", k, o.partners[k], o.linked[k]);
+        c->o_lk.fetched = true;
+    }
+    out->n_sites = c->r_sites.pos.size();
+    out->partners = o.partners.data(); out->linked = o.linked.data();
+    return DAGCON_OK;
+}
+
 // ---- the reads at the sites and the split (k_site_reads.hip.h) ----
 namespace {
 
@@ -355,6 +426,7 @@ int reads_launch(Ctx *c, const DgParams &p) {
     if (reads) hipLaunchKernelGGL(k_sr_walk<false>, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
     hipLaunchKernelGGL(k_sr_scan, dim3(1), dim3(1024), 0, s, p);
     if (reads) hipLaunchKernelGGL(k_sr_walk<true>, dim3((c->A + 3) / 4), dim3(256), 0, s, p);
+    if (int r = link_launch(c, p)) return r;
     if (p.sr_phase && reads) hipLaunchKernelGGL(k_sr_split, dim3(c->T), dim3(256), 0, s, p);
     return DAGCON_OK;
 }
@@ -1146,12 +1218,12 @@ namespace {
 int outputs_room(Ctx *c) {
     int r;
     if ((r = edits_room(c)) || (r = pile_room(c)) || (r = reads_room(c)) || (r = hap_room(c)) || (r = winphase_room(c))) return r;
-    if ((r = alleles_room(c)) || (r = calls_room(c)) || (r = keep_room(c))) return r;
+    if ((r = alleles_room(c)) || (r = calls_room(c)) || (r = keep_room(c)) || (r = link_room(c))) return r;
     return join_room(c);
 }
 
 void outputs_params(Ctx *c, DgParams &p) {
-    edits_params(c, p); pile_params(c, p); reads_params(c, p); hap_params(c, p); winphase_params(c, p); alleles_params(c, p); join_params(c, p); calls_params(c, p); keep_params(c, p);
+    edits_params(c, p); pile_params(c, p); reads_params(c, p); hap_params(c, p); winphase_params(c, p); alleles_params(c, p); join_params(c, p); calls_params(c, p); keep_params(c, p); link_params(c, p);
 }
 
 // between k_bp_join and the last event of a run that goes as far as bestPath (T > 0)

@@ -35,6 +35,7 @@
 #include "k_evidence.hip.h"
 #include "k_pileup.hip.h"
 #include "k_site_reads.hip.h"
+#include "k_site_link.hip.h"
 #include "k_hap.hip.h"
 #include "k_hap_calls.hip.h"
 #include "k_alleles.hip.h"

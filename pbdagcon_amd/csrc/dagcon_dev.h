@@ -308,6 +308,14 @@ struct DgParams {
     // derives from one; NULL otherwise): k_keep.hip.h.  Last, so that every field above keeps its offset ----
     uint4 *keep_out;               // [seg_cap] in the order of seg_r0 / seg_r1: x = the segment's target (k_bp_join), then i0, i1, p_first, p_last (k_win_keep)
     const uint32_t *keep_lo, *keep_hi;     // [T] a target's (a window's) lo and hi
+    // ---- the sites the same reads carry (dagcon_set_site_link, with the split; NULL / 0 otherwise): k_site_link.hip.h.
+    // Last, so that every field above keeps its offset ----
+    unsigned long long *lk_rows;   // [lk_row_cap] a site's rows: lk_words words P, then lk_words words M; bit x - aln_begin[t] (cleared before every run)
+    uint64_t lk_row_cap;           // site_cap * 2 * lk_words
+    uint16_t *lk_partners;         // [site_cap] a site's partners
+    uint8_t *lk_linked;            // [site_cap] 1: partners >= lk_min_partners; k_sr_split mutes the others
+    uint32_t lk_words;             // words of a row: (max_k + 63) / 64, one width for the batch
+    uint32_t lk_ppm, lk_min_cell, lk_min_partners, lk_reach;   // dagcon_site_link_opts (the defaults filled in)
 };
 #define DG_HAP_REC 8u
 #define DG_SR_TAKEN 0x80000000u

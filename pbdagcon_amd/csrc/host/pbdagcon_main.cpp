@@ -80,6 +80,7 @@ struct Opts {
     bool want_hc() const { return !hap_contigs.empty() || !hap_windows.empty(); }
     DgWinPhaseOpts wp;                 // --phase-windows [--phase-min-links N] [--phase-max-conflict F]: --site-reads / --haplotag with --window, the windows' labels joined (windows.h)
     DgSiteReadOpts sr;                 // --site-reads FILE, --haplotag FILE (whole targets, not -a): which read shows which allele at the sites; a two-way split
+    DgLinkOpts link;                   // --link-sites [--link-*], --linked-sites FILE (where the split goes): only the sites the same reads carry sign the split
     DgHapOpts hap;                     // --hap-consensus FILE, --hap-sites FILE (where --haplotag goes): a consensus per group of the split, the split's tally; --hap-vcf FILE (records): the groups' edits paired
     DgAlleleOpts al;                   // --site-alleles FILE, --site-vcf FILE (where --site-reads goes): the alleles themselves at the sites, counted
     DgJoinedOpts jn;                   // --joined-alleles FILE, --joined-vcf FILE (where --site-alleles / --site-vcf go): adjacent sites joined into one record
@@ -101,7 +102,7 @@ struct Opts {
 
 void usage(FILE *f) {
     fprintf(f,
-            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [--site-alleles FILE] [--site-vcf FILE] [--joined-alleles FILE] [--joined-vcf FILE] [--hap-vcf FILE] [--window W --phase-windows --hap-contigs FILE [--hap-windows FILE]] [-v] <input>\n"
+            "USAGE: pbdagcon [-j <int>] [-c <uint>] [-m <uint>] [-t <uint>] [-a [--local]] [--sam|--bam --ref <fasta> | --sam|--bam --md | --paf --ref <fasta> --reads <fasta|fastq> | --paf --cs --ref <fasta> [--window W [--overlap O]] [--max-error F] [--max-depth N] [--edits FILE] [--vcf FILE]] [--pileup FILE] [--sites FILE [--site-min-frac F] [--site-min-count N]] [--site-reads FILE] [--haplotag FILE] [--hap-consensus FILE [--hap-min-sites N] [--hap-min-reads N]] [--hap-sites FILE] [--fastq] [--site-alleles FILE] [--site-vcf FILE] [--joined-alleles FILE] [--joined-vcf FILE] [--hap-vcf FILE] [--window W --phase-windows --hap-contigs FILE [--hap-windows FILE]] [--link-sites [--link-max-conflict F] [--link-min-cell N] [--link-min-partners N] [--link-reach N]] [--linked-sites FILE] [-v] <input>\n"
             "  PBDAGCON is a tool that implements DAGCon (Directed Acyclic Graph Consensus); this build\n"
             "  runs the consensus on an MI355X through libdagcon_hip.so.\n"
             "  -j, --threads       host threads for parsing (default 4); the consensus runs on the GPU\n"
@@ -295,6 +296,22 @@ void usage(FILE *f) {
             "                      targets dealt round-robin, records still printed in input order\n"
             "  --contexts N        consensus workers (thread + context) per GPU, 1..4: a batch's upload and formatting run\n"
             "                      beside another batch's kernels (default: 2 for inputs of several batches, else 1)\n"
+            "  --link-sites        where --haplotag, --hap-consensus, --hap-sites and --hap-vcf go, and with --window --phase-windows\n"
+            "                      where --site-reads, --haplotag, --hap-contigs and --hap-windows go: only the sites that the same\n"
+            "                      reads carry as other sites near them sign the split.  Two sites of a target are partners when,\n"
+            "                      of the reads with one of the two alleles at both, at most F disagree (--link-max-conflict,\n"
+            "                      default 0.1, at most six decimal places) and the rarer agreeing combination is shown by N or\n"
+            "                      more reads (--link-min-cell, default 3); a site is linked when it has N or more partners\n"
+            "                      (--link-min-partners, default 2) among the N sites on either side of it in the target's site\n"
+            "                      list (--link-reach, default 256, at most 4096).  At a site that is not linked no read counts\n"
+            "                      as informative: HAP, SITES, the tally, H1 H2 H0 and everything else that rests on the split\n"
+            "                      follow; the sites themselves, their reads and their alleles are listed as before.  A 0 means\n"
+            "                      the default.  The defaults come from one experiment on synthetic reads (1 %% substitutions, 10 %%\n"
+            "                      inserted and 4 %% deleted bases) and from nothing else.  Chosen on the GPU; stdout does not\n"
+            "                      change.  This build's own rule, parity unpinned\n"
+            "  --linked-sites FILE the same inputs, implies --link-sites: one line per site, RNAME POS PARTNERS LINKED, POS 1-based\n"
+            "                      as in --sites, LINKED 1 or 0; with --window a position's line comes from the window whose core\n"
+            "                      holds it\n"
             "  --hap-contigs FILE  with --window and --phase-windows (either this or --hap-windows stands in for --site-reads /\n"
             "                      --haplotag there): two phased sequences per phase block.  Every window whose reads split\n"
             "                      (--hap-min-sites, --hap-min-reads as for --hap-consensus) is run again as its two read groups,\n"
@@ -409,6 +426,21 @@ int parse_args(int argc, char **argv, Opts &o) {
             if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --hap-windows needs a file name\n"); return 2; }
             o.hap_windows = argv[++i];
         }
+        else if (a == "--link-sites") o.link.on = true;
+        else if (a == "--linked-sites") {
+            if (i + 1 >= argc) { fprintf(stderr, "PARSE ERROR: --linked-sites needs a file name\n"); return 2; }
+            o.link.linked = argv[++i]; o.link.on = true;
+        }
+        else if (a == "--link-max-conflict") {
+            if (i + 1 >= argc || !dg_parse_ppm(argv[i + 1], &o.link.o.max_conflict_ppm)) { fprintf(stderr, "PARSE ERROR: --link-max-conflict takes a fraction in [0, 1] with at most six decimal places\n"); return 2; }
+            i++; o.link.opts_set = true;
+        }
+        else if (a == "--link-min-cell") { if (!need(&o.link.o.min_cell)) return 2; o.link.opts_set = true; }
+        else if (a == "--link-min-partners") { if (!need(&o.link.o.min_partners)) return 2; o.link.opts_set = true; }
+        else if (a == "--link-reach") {
+            if (!need(&o.link.o.reach) || o.link.o.reach > 4096u) { fprintf(stderr, "PARSE ERROR: --link-reach takes 0..4096\n"); return 2; }
+            o.link.opts_set = true;
+        }
         else if (a == "--hap-min-sites") { if (!need(&o.hap.min_sites)) return 2; o.hap.sites_set = true; }
         else if (a == "--hap-min-reads") { if (!need(&o.hap.min_reads)) return 2; o.hap.reads_set = true; }
         else if (a == "--site-min-frac") {
@@ -497,6 +529,9 @@ int parse_args(int argc, char **argv, Opts &o) {
     if ((o.hap.sites_set || o.hap.reads_set) && !o.hap.on() && !o.want_hc()) { fprintf(stderr, "PARSE ERROR: --hap-min-sites and --hap-min-reads need --hap-consensus or --hap-sites\n"); return 2; }
     if (o.hap.on() && (o.window || align || o.polish)) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --window, -a or --polish (the groups of neighbouring windows are named each on its own)\n"); return 2; }
     if (o.hap.on() && o.dump) { fprintf(stderr, "PARSE ERROR: --hap-consensus and --hap-sites do not go with --dump-parsed (nothing is run, the files would not be written)\n"); return 2; }
+    if (o.link.opts_set && !o.link.on) { fprintf(stderr, "PARSE ERROR: --link-max-conflict, --link-min-cell, --link-min-partners and --link-reach need --link-sites or --linked-sites\n"); return 2; }
+    if (o.link.on && !(o.window ? o.wp.on : o.want_phase())) { fprintf(stderr, "PARSE ERROR: --link-sites and --linked-sites need --haplotag, --hap-consensus, --hap-sites or --hap-vcf (with --window: --phase-windows)\n"); return 2; }
+    if (o.link.on && o.dump) { fprintf(stderr, "PARSE ERROR: --link-sites and --linked-sites do not go with --dump-parsed (nothing is run, the file would not be written)\n"); return 2; }
     if (o.wp.on && !o.window) { fprintf(stderr, "PARSE ERROR: --phase-windows needs --window\n"); return 2; }
     if (o.wp.on && !o.sr.on() && !o.want_hc()) { fprintf(stderr, "PARSE ERROR: --phase-windows needs --site-reads FILE or --haplotag FILE\n"); return 2; }
     if ((o.wp.links_set || o.wp.conflict_set) && !o.wp.on) { fprintf(stderr, "PARSE ERROR: --phase-min-links and --phase-max-conflict need --phase-windows\n"); return 2; }
@@ -601,10 +636,11 @@ struct Batch {
     std::vector<std::string> qnames;   // --site-reads, --haplotag: the records' read names (the input's pages may be gone by the time they are written)
     std::string site_reads, haplotag;  // and the batch's lines of those files
     std::string hap_out, hap_sites;    // --hap-consensus, --hap-sites: the batch's records and lines of those files
+    std::string linked_sites;          // --linked-sites: the batch's lines of that file
     std::string hap_vcf, hap_contigs;  // --hap-vcf: the batch's lines of that file, and its targets' ##contig lines
     std::string site_alleles, site_vcf, site_contigs;   // --site-alleles, --site-vcf: the batch's lines of those files, and its targets' ##contig lines
     std::string joined_alleles, joined_vcf, joined_contigs;   // --joined-alleles, --joined-vcf: the same
-    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); hap_out.clear(); hap_sites.clear(); hap_vcf.clear(); hap_contigs.clear(); site_alleles.clear(); site_vcf.clear(); site_contigs.clear(); joined_alleles.clear(); joined_vcf.clear(); joined_contigs.clear(); }
+    void clear() { ids.clear(); tlen.clear(); start.clear(); len.clear(); len2.clear(); begin.assign(1, 0); off.clear(); off2.clear(); strand.clear(); toff.clear(); opb.assign(1, 0); tsrc.clear(); ops.clear(); cs_len.clear(); tspan.clear(); reverse.clear(); md_off.clear(); md_len.clear(); md.clear(); q.n = 0; t.n = 0; out.clear(); edits.clear(); n_edits = 0; vcf.clear(); contigs.clear(); pileup.clear(); sites.clear(); qnames.clear(); site_reads.clear(); haplotag.clear(); hap_out.clear(); hap_sites.clear(); linked_sites.clear(); hap_vcf.clear(); hap_contigs.clear(); site_alleles.clear(); site_vcf.clear(); site_contigs.clear(); joined_alleles.clear(); joined_vcf.clear(); joined_contigs.clear(); }
 };
 
 FILE *g_edits = nullptr;                                  // --edits FILE, written batch by batch in output order
@@ -617,6 +653,7 @@ bool g_vcf_bad = false;
 FILE *g_pileup = nullptr, *g_sites = nullptr;              // --pileup FILE, --sites FILE, written batch by batch in output order
 FILE *g_site_reads = nullptr, *g_haplotag = nullptr;       // --site-reads FILE, --haplotag FILE, the same way
 FILE *g_hap_out = nullptr, *g_hap_sites = nullptr;         // --hap-consensus FILE, --hap-sites FILE, the same way
+FILE *g_linked_sites = nullptr;                            // --linked-sites FILE, the same way
 FILE *g_hap_contigs = nullptr, *g_hap_windows = nullptr;   // --hap-contigs FILE, --hap-windows FILE, the same way
 FILE *g_hap_vcf = nullptr, *g_hap_vcf_lines = nullptr;     // --hap-vcf FILE, as --site-vcf below: the records wait in an unnamed temporary file
 std::string g_hap_vcf_contigs;
@@ -726,6 +763,9 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
     dagcon_site_reads sr;
     memset(&sr, 0, sizeof sr);
     if (o.want_sr() && !ok(ctx, dagcon_fetch_site_reads(ctx, &sr), "site reads")) return 1;
+    dagcon_site_link sl;
+    memset(&sl, 0, sizeof sl);
+    if (o.link.on && !ok(ctx, dagcon_fetch_site_link(ctx, &sl), "site link")) return 1;
     dagcon_site_alleles sa;
     memset(&sa, 0, sizeof sa);
     if (o.want_al() && !ok(ctx, dagcon_fetch_site_alleles(ctx, &sa), "site alleles")) return 1;
@@ -750,8 +790,9 @@ int append_results(dagcon_ctx *ctx, Batch &b, const Opts &o, const dagcon_result
         if (o.sr.on()) {
             const uint64_t x0 = sr_x;
             while (sr_x < sr.n_aln && sr.aln_tgt[sr_x] == g) sr_x++;
-            dg_site_read_lines(o.sr.site_reads.empty() ? nullptr : &b.site_reads, o.sr.haplotag.empty() ? nullptr : &b.haplotag, b.ids[g], ps, sr, g, x0, sr_x, b.qnames);
+            dg_site_read_lines(o.sr.site_reads.empty() ? nullptr : &b.site_reads, o.sr.haplotag.empty() ? nullptr : &b.haplotag, b.ids[g], ps, sr, g, x0, sr_x, b.qnames, o.link.on ? sl.linked : nullptr);
         }
+        if (!o.link.linked.empty()) dg_linked_site_lines(b.linked_sites, b.ids[g], ps, sl, g, 0, b.tlen[g], 0);
         if (o.al.on()) {
             const char *tb = o.mode == MODE_RECORDS ? b.t.data() + b.toff[g] : nullptr;
             if (!o.al.vcf.empty()) dg_vcf_contig(b.site_contigs, b.ids[g], b.tlen[g]);
@@ -1067,6 +1108,7 @@ struct Workers {
         }
         if (rc == DAGCON_OK && o.want_al() && (rc = dagcon_set_site_alleles(ctx, 1)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
         if (rc == DAGCON_OK && o.jn.on() && (rc = dagcon_set_site_join(ctx, 1)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
+        if (rc == DAGCON_OK && o.link.on && (rc = dagcon_set_site_link(ctx, &o.link.o)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
         if (rc == DAGCON_OK && o.hap.on()) {
             const dagcon_hap_opts ho = {o.hap.min_sites, o.hap.min_reads};
             if ((rc = dagcon_set_hap_consensus(ctx, &ho)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); dagcon_destroy(ctx); ctx = nullptr; }
@@ -1115,6 +1157,7 @@ struct Workers {
                     if (g_haplotag && fwrite(d->haplotag.data(), 1, d->haplotag.size(), g_haplotag) != d->haplotag.size()) g_pile_bad = true;
                     if (g_hap_out && fwrite(d->hap_out.data(), 1, d->hap_out.size(), g_hap_out) != d->hap_out.size()) g_pile_bad = true;
                     if (g_hap_sites && fwrite(d->hap_sites.data(), 1, d->hap_sites.size(), g_hap_sites) != d->hap_sites.size()) g_pile_bad = true;
+                    if (g_linked_sites && fwrite(d->linked_sites.data(), 1, d->linked_sites.size(), g_linked_sites) != d->linked_sites.size()) g_pile_bad = true;
                     if (g_hap_vcf) { g_hap_vcf_contigs += d->hap_contigs; if (fwrite(d->hap_vcf.data(), 1, d->hap_vcf.size(), g_hap_vcf_lines) != d->hap_vcf.size()) g_pile_bad = true; }
                     if (g_site_alleles && fwrite(d->site_alleles.data(), 1, d->site_alleles.size(), g_site_alleles) != d->site_alleles.size()) g_pile_bad = true;
                     if (g_site_vcf) { g_site_vcf_contigs += d->site_contigs; if (fwrite(d->site_vcf.data(), 1, d->site_vcf.size(), g_site_vcf_lines) != d->site_vcf.size()) g_pile_bad = true; }
@@ -1621,6 +1664,7 @@ int main(int argc, char **argv) {
     if (!o.sr.haplotag.empty() && !(g_haplotag = fopen(o.sr.haplotag.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.sr.haplotag.c_str()); return 1; }
     if (!o.hap.consensus.empty() && !(g_hap_out = fopen(o.hap.consensus.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.consensus.c_str()); return 1; }
     if (!o.hap.sites.empty() && !(g_hap_sites = fopen(o.hap.sites.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.sites.c_str()); return 1; }
+    if (!o.link.linked.empty() && !(g_linked_sites = fopen(o.link.linked.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.link.linked.c_str()); return 1; }
     if (!o.hap.vcf.empty() && (!(g_hap_vcf = fopen(o.hap.vcf.c_str(), "w")) || !(g_hap_vcf_lines = tmpfile()))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap.vcf.c_str()); return 1; }
     if (!o.hap_contigs.empty() && !(g_hap_contigs = fopen(o.hap_contigs.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap_contigs.c_str()); return 1; }
     if (!o.hap_windows.empty() && !(g_hap_windows = fopen(o.hap_windows.c_str(), "w"))) { fprintf(stderr, "pbdagcon: cannot write %s\n", o.hap_windows.c_str()); return 1; }
@@ -1655,7 +1699,7 @@ int main(int argc, char **argv) {
         }
         const std::pair<FILE **, const std::string *> files[] = {{&g_pileup, &o.pile.pileup}, {&g_sites, &o.pile.sites}, {&g_site_reads, &o.sr.site_reads}, {&g_haplotag, &o.sr.haplotag},
                                                                  {&g_site_alleles, &o.al.alleles}, {&g_site_vcf, &o.al.vcf}, {&g_joined_alleles, &o.jn.alleles}, {&g_joined_vcf, &o.jn.vcf},
-                                                                 {&g_hap_out, &o.hap.consensus}, {&g_hap_sites, &o.hap.sites}, {&g_hap_vcf, &o.hap.vcf},
+                                                                 {&g_hap_out, &o.hap.consensus}, {&g_hap_sites, &o.hap.sites}, {&g_hap_vcf, &o.hap.vcf}, {&g_linked_sites, &o.link.linked},
                                                                  {&g_hap_contigs, &o.hap_contigs}, {&g_hap_windows, &o.hap_windows}};
         for (const auto &f : files) {
             if (!*f.first) continue;
@@ -1670,6 +1714,7 @@ int main(int argc, char **argv) {
     if (o.window && !o.dump) {
         DgWinOpts wo{o.min_cov, o.min_len, o.trim, o.window, o.overlap, o.batch_targets, o.fastq, o.verbose, o.devices[0], o.pick, o.edits.empty() ? nullptr : o.edits.c_str(),
                      g_pileup, g_sites, o.pile.min_count, o.pile.min_frac_ppm, g_site_reads, g_haplotag, o.wp};
+        wo.link = o.link.on ? &o.link.o : nullptr; wo.linked_sites = g_linked_sites;
         wo.hap_contigs = g_hap_contigs; wo.hap_windows = g_hap_windows; wo.hap_min_sites = o.hap.min_sites; wo.hap_min_reads = o.hap.min_reads;
         if (o.kind == DG_REC_PACKED) { DgBamSource src(bam, ref); return close_pile(dg_run_windows(wo, src, ref)); }
         if (o.kind == DG_REC_PACKED_MD) { DgBamMdSource src(bam, ref); return close_pile(dg_run_windows(wo, src, ref)); }
@@ -1706,7 +1751,7 @@ int main(int argc, char **argv) {
         if (fclose(g_edits) != 0) { fprintf(stderr, "pbdagcon: error writing %s\n", o.edits.c_str()); status = 1; fast_exit = false; }
         if (o.verbose) fprintf(stderr, "pbdagcon: %llu edits written to %s\n", g_n_edits, o.edits.c_str());
     }
-    if (g_pileup || g_sites || g_site_reads || g_haplotag || g_hap_out || g_hap_sites || g_hap_vcf || g_site_alleles || g_site_vcf || g_joined_alleles || g_joined_vcf) {
+    if (g_pileup || g_sites || g_site_reads || g_haplotag || g_linked_sites || g_hap_out || g_hap_sites || g_hap_vcf || g_site_alleles || g_site_vcf || g_joined_alleles || g_joined_vcf) {
         const int ps = close_pile(0);
         if (ps) { status = ps; fast_exit = false; }
     }

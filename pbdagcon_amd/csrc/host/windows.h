@@ -182,6 +182,8 @@ struct DgWinOpts {
     FILE *hap_contigs = nullptr, *hap_windows = nullptr;   // --phase-windows with --hap-contigs / --hap-windows: open files, or NULL
     uint32_t hap_min_sites = 0, hap_min_reads = 0;         // --hap-min-sites / --hap-min-reads (0: the library's defaults)
     bool hc() const { return hap_contigs || hap_windows; }
+    const dagcon_site_link_opts *link = nullptr;           // --link-sites with --phase-windows: its options, or NULL
+    FILE *linked_sites = nullptr;                          // --linked-sites: an open file, or NULL
 };
 
 // SAM text: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
@@ -327,6 +329,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         const dagcon_window_phase_opts wo = {o.wp.min_links, o.wp.max_conflict_ppm};
         if ((rc = dagcon_set_site_reads(ctx, &so)) != DAGCON_OK || (rc = dagcon_set_window_phase(ctx, &wo)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); if (ef) fclose(ef); dagcon_destroy(ctx); return 1; }
     }
+    if (o.link && (rc = dagcon_set_site_link(ctx, o.link)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); if (ef) fclose(ef); dagcon_destroy(ctx); return 1; }
     if (o.hc()) {
         const dagcon_hap_opts ho = {o.hap_min_sites, o.hap_min_reads};
         if ((rc = dagcon_set_hap_consensus(ctx, &ho)) != DAGCON_OK) { fprintf(stderr, "pbdagcon: %s\n", dagcon_last_error(ctx)); if (ef) fclose(ef); dagcon_destroy(ctx); return 1; }
@@ -348,7 +351,7 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
     DgWpLink prev_link{0, 0};
     std::vector<DgWpPiece> prev_pieces;
     unsigned long long n_blocks = 0;
-    std::string pile_out, site_out, reads_out, tags_out;
+    std::string pile_out, site_out, reads_out, tags_out, linked_out;
     for (Tgt &t : tgts) t.fate.assign(t.recs.size(), 0);
     int status = 0;
     DgStitch st;
@@ -471,6 +474,9 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         memset(&wp, 0, sizeof wp);
         if (rc == DAGCON_OK && o.wp.on) rc = dagcon_fetch_site_reads(ctx, &sr);
         if (rc == DAGCON_OK && o.wp.on) rc = dagcon_fetch_window_phase(ctx, &wp);
+        dagcon_site_link sl;
+        memset(&sl, 0, sizeof sl);
+        if (rc == DAGCON_OK && o.link) rc = dagcon_fetch_site_link(ctx, &sl);
         uint64_t sr_x = 0;                                     // the taken alignments ascend in their window: one walk
         std::vector<DgWpLink> links(o.hc() ? w1 - w0 : 0, DgWpLink{0, 0});    // --hap-contigs / --hap-windows: every window's link in the run's terms
         DgWpLink first_link{0, 0};                             // the link of the group's first window, in the run's terms
@@ -523,9 +529,10 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
                     a.pieces.push_back(DgWpVote{link.block, (uint8_t)(h && turn ? 3u - h : h)});
                     for (uint64_t e = sr.ent_begin[x]; e < sr.ent_begin[x + 1]; e++) {
                         const uint32_t p = ps.pos[sr.ent_site[e]];
-                        a.sites += p >= lo && p < hi && dg_sr_sign(sr.ent_code[e], ps.counts + 8 * sr.ent_site[e]) != 0;
+                        a.sites += p >= lo && p < hi && dg_sr_sign(sr.ent_code[e], ps.counts + 8 * sr.ent_site[e], o.link ? sl.linked[sr.ent_site[e]] : 1u) != 0;
                     }
                 }
+                if (o.linked_sites) dg_linked_site_lines(linked_out, t.name, ps, sl, (uint32_t)g, lo, hi, w.begin);
                 if (o.site_reads) dg_wp_site_read_lines(reads_out, t.name, ps, sr, (uint32_t)g, x0, sr_x, lo, hi, w.begin, [&](uint64_t x) -> const std::string & { return t.qnames[b_idx[sr.aln_src[x]]]; });
                 if (k + 1 == w1) {
                     prev_tgt = w.tgt; prev_link = link;
@@ -608,7 +615,8 @@ inline int dg_run_windows(const DgWinOpts &o, Source &src, const DgRefSeqs &ref)
         if (o.sites && fwrite(site_out.data(), 1, site_out.size(), o.sites) != site_out.size()) { fprintf(stderr, "pbdagcon: error writing the --sites file\n"); status = 1; }
         if (o.site_reads && fwrite(reads_out.data(), 1, reads_out.size(), o.site_reads) != reads_out.size()) { fprintf(stderr, "pbdagcon: error writing the --site-reads file\n"); status = 1; }
         if (o.haplotag && fwrite(tags_out.data(), 1, tags_out.size(), o.haplotag) != tags_out.size()) { fprintf(stderr, "pbdagcon: error writing the --haplotag file\n"); status = 1; }
-        pile_out.clear(); site_out.clear(); reads_out.clear(); tags_out.clear();
+        if (o.linked_sites && fwrite(linked_out.data(), 1, linked_out.size(), o.linked_sites) != linked_out.size()) { fprintf(stderr, "pbdagcon: error writing the --linked-sites file\n"); status = 1; }
+        pile_out.clear(); site_out.clear(); reads_out.clear(); tags_out.clear(); linked_out.clear();
         w0 = w1;
     }
     if (status == 0 && !flush_target()) status = 1;

@@ -16,7 +16,8 @@
 //                       before, the lanes in front.  The code is cls | ins << 3: cls by k_pile_count's classification, ins
 //                       when the column behind is the first of an insertion run (that column's own lane would count INS
 //                       for the same position; here the lane of the base looks one column ahead, lane 63 with a load).
-//   k_sr_split          phase on: a block per target.  A site's sign rule (k1, k2 or the insertion rule) goes to sr_kind;
+//   k_sr_split          phase on: a block per target.  A site's sign rule (k1, k2 or the insertion rule) goes to sr_kind
+//                       (DG_SR_MUTED for a site that dagcon_set_site_link found no partners for: k_site_link.hip.h);
 //                       the seed is the alignment with the most signed entries; then rounds of two steps, a wave per
 //                       alignment summing M * sigma over its entries (no atomics), and a wave per alignment adding M * h
 //                       to its sites' sums with integer atomicAdd (an integer sum does not depend on the order).  A round
@@ -140,8 +141,10 @@ struct DgSrScanItem {
 };
 __global__ __launch_bounds__(1024) void k_sr_scan(DgParams p) { dg_block_scan<DgSrScanItem>(p); }
 
-// what decides an entry's sign at a site: 0x80 an insertion site; otherwise k1 | k2 << 3, k2 == 7: no second class
-__device__ __forceinline__ uint32_t dg_sr_kind(const DgSite &s) {
+// what decides an entry's sign at a site: 0x80 an insertion site; otherwise k1 | k2 << 3, k2 == 7: no second class.
+// DG_SR_MUTED, both class fields 7, matches no class (a class is 0 .. 5): every entry's sign is 0 there
+#define DG_SR_MUTED 0x3Fu
+__host__ __device__ __forceinline__ uint32_t dg_sr_kind(const DgSite &s) {
     const uint32_t n[6] = {s.w[0] & 0xFFFFu, s.w[0] >> 16, s.w[1] & 0xFFFFu, s.w[1] >> 16, s.w[2] & 0xFFFFu, s.w[2] >> 16};
     const uint32_t ins = s.w[3] & 0xFFFFu;
     uint32_t depth = 0, k1 = 0;
@@ -156,7 +159,7 @@ __device__ __forceinline__ uint32_t dg_sr_kind(const DgSite &s) {
     if ((ins < rest ? ins : rest) > c2) return 0x80u;
     return k1 | (k2 << 3);
 }
-__device__ __forceinline__ int dg_sr_sign(const uint32_t code, const uint32_t kind) {
+__host__ __device__ __forceinline__ int dg_sr_sign(const uint32_t code, const uint32_t kind) {
     if (kind & 0x80u) return (code & 8u) ? -1 : 1;
     const uint32_t cls = code & 7u;
     return cls == (kind & 7u) ? 1 : cls == ((kind >> 3) & 7u) ? -1 : 0;
@@ -186,7 +189,8 @@ __global__ __launch_bounds__(256) void k_sr_split(DgParams p) {
     __shared__ int s_changed, s_bad;
     if (threadIdx.x == 0) { s_changed = 0; s_bad = 0; }
     for (unsigned long long k = s0 + threadIdx.x; k < s1; k += 256u) {
-        p.sr_kind[k] = (uint8_t)dg_sr_kind(p.pile_site[k]);
+        // (dagcon_set_site_link: a site that is not linked gets the kind under which every entry's sign is 0)
+        p.sr_kind[k] = p.lk_linked && !p.lk_linked[k] ? (uint8_t)DG_SR_MUTED : (uint8_t)dg_sr_kind(p.pile_site[k]);
         p.sr_sigma[k] = 0;
         p.sr_acc[k] = 0;
     }
